@@ -31,6 +31,67 @@ for _p in (ROOT, PKG):
         sys.path.insert(0, _p)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this many bytes of .npy files in all
+
+
+def dump_flow(directory, flow, budget=DUMP_BYTES, seed=0):
+    """--dump-outputs: the flow fields (n, h, w, 2) float32 the timed path handed back in its last step, as .npy files
+    under `directory`.  A batch that fits in `budget` bytes is written whole (flow.npy).  A larger one is written as a
+    fixed sample drawn with a seeded generator, the same for every run with the same arguments: the whole fields of
+    the pairs in flow_pairs_index.npy (flow_pairs.npy, at most half the budget) and single flow vectors spread over the
+    whole batch (flow_pixels.npy, (m, 2)) at the flat pixel indices in flow_pixels_index.npy (pair * h * w + y * w + x).
+    Indices are stored as float64, which holds them exactly."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    n, h, w, c = flow.shape
+    field = h * w * c * 4
+    if n * field <= budget:
+        np.save(os.path.join(directory, "flow.npy"), flow.cpu().numpy())
+        return
+    rng = np.random.default_rng(seed)
+    header = 128   # bytes of one .npy header
+    k = min(n, (budget // 2) // (field + 8 + 2 * header))
+    pairs = np.sort(rng.choice(n, size=k, replace=False))
+    m = (budget - k * (field + 8) - 4 * header) // (c * 4 + 8)
+    idx = np.unique(rng.integers(0, n * h * w, size=m, dtype=np.int64))
+    pix = flow.reshape(n * h * w, c)[torch.from_numpy(idx).to(flow.device)]
+    np.save(os.path.join(directory, "flow_pairs.npy"), flow[torch.from_numpy(pairs).to(flow.device)].cpu().numpy())
+    np.save(os.path.join(directory, "flow_pairs_index.npy"), pairs.astype(np.float64))
+    np.save(os.path.join(directory, "flow_pixels.npy"), pix.cpu().numpy())
+    np.save(os.path.join(directory, "flow_pixels_index.npy"), idx.astype(np.float64))
+
+
+def native_up_to_date():
+    """True when nsof/libnsof.so exists and `make -q` finds nothing to rebuild; asking writes nothing."""
+    import subprocess
+    if not os.path.exists(os.path.join(PKG, "nsof", "libnsof.so")):
+        return False
+    return subprocess.run(["make", "-q", "-C", PKG], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL).returncode == 0
+
+
+def writable_oracle():
+    """The CPU legs use the oracle's -march=native build, which oracle.perf_lib() compiles on first use under
+    oracle/_build.  A tree built by another account may not be writable here: then the oracle package is copied to a
+    private temporary directory and imported from there, and the tree is left as it is."""
+    import atexit
+    import shutil
+    import stat
+    import tempfile
+    home = os.path.join(ROOT, "oracle")
+    build_dir = os.path.join(home, "_build")
+    try:
+        with tempfile.TemporaryFile(dir=build_dir if os.path.isdir(build_dir) else home):
+            return
+    except OSError:
+        pass
+    tmp = tempfile.mkdtemp(prefix="nsof_bench_oracle_")
+    atexit.register(shutil.rmtree, tmp, True)
+    copy = os.path.join(tmp, "oracle")
+    shutil.copytree(home, copy, ignore=shutil.ignore_patterns("__pycache__"))   # keeps mtimes: built files stay current
+    for d, _, _ in os.walk(copy):
+        os.chmod(d, os.stat(d).st_mode | stat.S_IWUSR)   # copytree also copies the read-only modes of the directories
+    sys.path.insert(0, tmp)
 
 
 def synth_pairs_gpu(torch, dev, n, h, w, seed0):
@@ -136,7 +197,12 @@ def main():
     ap.add_argument("--mode", choices=["pairs", "sequence"], default="pairs",
                     help="pairs (headline): independent frame pairs; sequence: pairs+1 consecutive frames, the "
                          "per-frame work is shared between neighbouring pairs (nsof_farneback_u8_sequence_dev)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the flow fields of the last step as .npy files under DIR (rank 0's "
+                         "batch; a fixed seeded sample when it exceeds 64 MB, see dump_flow)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # ONE JSON line on stdout, whatever libraries print: RCCL writes a version banner to stdout when a process
     # group comes up.  Everything else that lands on file descriptor 1 is sent to stderr; the JSON line goes to the
@@ -145,8 +211,6 @@ def main():
     real_stdout = os.dup(1)
     os.dup2(2, 1)
 
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # see nsof/_lib.py: streams that share a hardware queue serialise
-
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -154,8 +218,10 @@ def main():
         if args.gpus != 1 or world != 1:
             raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run")
 
-    import __graft_entry__ as ge
-    ge.build_native()
+    if not native_up_to_date():   # a tree that is already built is not written to: it may not be this user's
+        import __graft_entry__ as ge
+        ge.build_native()
+    writable_oracle()
     import nsof  # noqa: E402  (preloads torch's HIP runtime, then libnsof.so)
     import torch
     from nsof import _lib
@@ -225,6 +291,8 @@ def main():
         for k in kernel_ids:
             prof[k] = ctx.prof_collect(k)
         ctx.prof_enable()
+    if args.dump_outputs and rank == 0:
+        dump_flow(args.dump_outputs, flow)
 
     exit_code = 0
     out = None

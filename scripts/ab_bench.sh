@@ -2,7 +2,7 @@
 # A/B of libnsof variants (scripts/build_variant.sh) on the HEADLINE bench itself (256 pairs 1080p, all levels, real pyramid
 # flow), alternating the variants REPS times on the same box: box-to-box spread (+-3 %) is larger than most kernel changes.
 #   bash scripts/ab_bench.sh base old c1i1 ...      (AB_PARAMS=A|B|C, AB_REPS=2)
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1
 for rep in $(seq 1 ${AB_REPS:-2}); do
 for v in "$@"; do

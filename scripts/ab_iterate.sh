@@ -2,7 +2,7 @@
 # A/B timing of libnsof variants (scripts/build_variant.sh) on the fused iteration stage.
 #   bash scripts/ab_iterate.sh name1 name2 ...     name = lib variant ("base" = the product library), optionally
 #   followed by +ENV=VALUE pairs, e.g.  base+NSOF_ITER_SPLIT=1
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1
 for spec in "$@"; do
   v=${spec%%+*}

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of libnsof variants (scripts/build_variant.sh) on lone calls: iterate milliseconds of scripts/latency_single.py per variant.
 #   SHAPES=0 bash scripts/ab_lone.sh base v1 v2 ...
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1 BANDS=0
 for v in "$@"; do
   if [ "$v" = base ]; then unset NSOF_LIB; else export NSOF_LIB=$REPO/neuromorphic-spatiotemporal-optical-flow_amd/nsof/libnsof_$v.so; fi

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B timing of libnsof variants on any stage of scripts/stage_bench.py:  AB_ARGS="--stages polyexp --poly-n 10 ..." bash scripts/ab_stage.sh base v1 v2+ENV=1
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1
 for spec in "$@"; do
   v=${spec%%+*}

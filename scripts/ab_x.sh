@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B timing of libnsof variants (scripts/build_variant.sh) on the exact-order iteration stage: prints the exact-mode launch time
 # of scripts/x_check.py for each variant ("base" = the product library).   bash scripts/ab_x.sh base v1 v2 ...
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1
 for v in "$@"; do
   if [ "$v" = base ]; then unset NSOF_LIB; else export NSOF_LIB=$REPO/neuromorphic-spatiotemporal-optical-flow_amd/nsof/libnsof_$v.so; fi

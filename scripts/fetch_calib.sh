@@ -1,7 +1,7 @@
 #!/bin/bash
 # FETCH_SIZE multipliers for 4 / 8 / 16-byte-per-lane streaming reads (scripts/fetch_calib.hip) -> gpurun_out/fetch_calibration.json
 set -e
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 rm -rf $REPO/gpurun_out/fetch_calib
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $REPO/gpurun_out/fetch_calib -- $REPO/scripts/fetch_calib > $REPO/gpurun_out/fetch_calib.log 2>&1

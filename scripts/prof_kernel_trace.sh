@@ -5,7 +5,7 @@
 #  then cover exactly the (steps + warmup) x 12 launches the bench line's roofline is computed from)
 set -e
 TAG=${1:-r01}; shift || true
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1            # no child processes from the profiled (GPU-initialised) process
 mkdir -p $REPO/gpurun_out
 cd /tmp && export TMPDIR=/tmp

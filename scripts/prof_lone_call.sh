@@ -3,7 +3,7 @@
 #   [SHAPES=0] NSOF_EXACT_IMPL=2k bash scripts/prof_lone_call.sh <tag>      (SHAPES: indices of latency_single's cases)
 set -e
 TAG=${1:-lone}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1 BANDS=0
 mkdir -p $REPO/gpurun_out
 cd /tmp && export TMPDIR=/tmp

@@ -3,7 +3,7 @@
 # the idle gap before it, from rocprofv3's kernel trace.   SHAPES=0 bash scripts/prof_lone_timeline.sh <tag>
 set -e
 TAG=${1:-tl}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1 BANDS=0 SHAPES=${SHAPES:-0}
 mkdir -p $REPO/gpurun_out
 cd /tmp && export TMPDIR=/tmp

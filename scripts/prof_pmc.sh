@@ -3,7 +3,7 @@
 # usage: bash scripts/prof_pmc.sh <tag> "<counters>" [stage_bench args...]
 set -e
 TAG=$1; CTRS=$2; shift 2
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1
 mkdir -p $REPO/gpurun_out
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 # rocprofv3 kernel stats of any python script of this repo:  bash scripts/prof_py_kernels.sh <tag> scripts/<x>.py [args...]
 set -e
 TAG=$1; shift
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1
 mkdir -p $REPO/gpurun_out
 cd /tmp && export TMPDIR=/tmp

@@ -7,7 +7,7 @@
 # usage: bash scripts/prof_traffic.sh <tag> [stage_bench args...]
 set -e
 TAG=${1:-r02}; shift || true
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1
 mkdir -p $REPO/gpurun_out
 cd /tmp && export TMPDIR=/tmp

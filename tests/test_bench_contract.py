@@ -125,3 +125,62 @@ def test_bench_prints_the_headline_when_the_gather_leg_hangs():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["value"] > 0 and "did not finish" in d["io_gather"]["error"]
     assert d["io_gather"]["exit_code"] == 4
+
+
+def test_dump_flow_writes_a_bounded_seeded_sample(tmp_path):
+    """bench.py --dump-outputs (dump_flow): a batch within the budget is written whole; a larger one as whole fields of
+    some pairs plus single flow vectors at stored flat indices, float32 / float64 only, within the budget, and the same
+    sample for the same input."""
+    import numpy as np
+    import torch
+    import bench
+    small = torch.randn(3, 10, 12, 2)
+    bench.dump_flow(str(tmp_path / "small"), small)
+    assert os.listdir(tmp_path / "small") == ["flow.npy"]
+    assert np.array_equal(np.load(tmp_path / "small" / "flow.npy"), small.numpy())
+    big = torch.randn(16, 100, 120, 2)
+    budget = 200_000
+    for d in ("a", "b"):
+        bench.dump_flow(str(tmp_path / d), big, budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["flow_pairs.npy", "flow_pairs_index.npy", "flow_pixels.npy", "flow_pixels_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert got[f[:-4]].dtype in (np.float32, np.float64)
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f))
+    pairs = got["flow_pairs_index"].astype(np.int64)
+    idx = got["flow_pixels_index"].astype(np.int64)
+    assert len(pairs) >= 1 and len(idx) > 1000
+    assert np.array_equal(got["flow_pairs"], big.numpy()[pairs])
+    assert np.array_equal(got["flow_pixels"], big.numpy().reshape(-1, 2)[idx])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs: two runs with the same arguments dump the same flow, the sample stays within 64 MB and agrees
+    with itself where the whole pair fields and the single vectors overlap; --steps sets the timed steps."""
+    import numpy as np
+    env = dict(os.environ, NSOF_SKIP_BUILD="1")
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--pairs", "4", "--steps", "3", "--warmup", "1",
+                              "--no-prof", "--no-config5", "--no-fast-leg", "--no-param-legs", "--e2e-pairs", "0",
+                              "--cpu-sample", "0", "--io", "none", "--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, text=True, env=env, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
+        assert d["steps"] == 3 and d["warmup"] == 1
+        files = sorted(os.listdir(tmp_path / run))
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64_000_000
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in files})
+    a, b = dumps
+    assert sorted(a) == ["flow_pairs", "flow_pairs_index", "flow_pixels", "flow_pixels_index"]   # 4 1080p fields > 64 MB
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    assert np.isfinite(a["flow_pairs"]).all() and np.isfinite(a["flow_pixels"]).all()
+    hw = 1080 * 1920
+    idx = a["flow_pixels_index"].astype(np.int64)
+    for j, pair in enumerate(a["flow_pairs_index"].astype(np.int64)):
+        mine = idx[idx // hw == pair]
+        assert np.array_equal(a["flow_pixels"][idx // hw == pair], a["flow_pairs"][j].reshape(-1, 2)[mine % hw])
