@@ -209,14 +209,18 @@ int nsof_stage_recip(nsof_ctx* ctx, long long n, const double* d_x, double* d_ou
 /* n_pairs pairs: R holds [n_pairs][2][5][h][w] (image 0 = prev, 1 = next). */
 int nsof_stage_update_matrices(nsof_ctx* ctx, int n_pairs, const float* d_R, const float* d_flow,
                                int width, int height, float* d_M);
+/* Box blur of M + 2x2 solve.  With NSOF_OPT_EXACT_ROWSUMS on (the default) it runs the unfused exact-order pair the
+ * driver uses (column sums, then the library's running row sums; scratch of n_pairs*5*w*h doubles from the context's
+ * workspace); off, the per-pixel-sum kernel of the fast mode. */
 int nsof_stage_blur_solve(nsof_ctx* ctx, int n_pairs, const float* d_M, int width, int height,
                           int winsize, float* d_flow);
 /* One fused Farneback iteration (matrix update + blur + solve): flow_out = step(R, flow_in).  d_flow_in and
- * d_flow_out must not alias.  winsize 2..17; larger windows take the unfused pair above. */
+ * d_flow_out must not alias.  winsize 2..15; larger windows take the unfused pair above. */
 int nsof_stage_iterate(nsof_ctx* ctx, int n_pairs, const float* d_R, const float* d_flow_in, int width, int height,
                        int winsize, float* d_flow_out);
 /* The same with flow_in = resample(d_coarse_flow [src_h][src_w][2]) * (1/pyr_scale) formed on the fly (first
- * iteration of a pyramid level): equals nsof_stage_flow_upsample followed by nsof_stage_iterate, bit for bit. */
+ * iteration of a pyramid level).  Tuning builds only; returns NSOF_EUNSUPPORTED in the release build (the symbol
+ * stays for the ABI). */
 int nsof_stage_iterate_upsample(nsof_ctx* ctx, int n_pairs, const float* d_R, const float* d_coarse_flow,
                                 int src_w, int src_h, int width, int height, int winsize, double pyr_scale,
                                 float* d_flow_out);

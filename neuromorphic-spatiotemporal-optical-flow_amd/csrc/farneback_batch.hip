@@ -175,12 +175,17 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
                                        p.pyr_scale, p.levels, p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags);
     }
 
-    // Items the work-list kernels cover: fused iteration available (window 2..15, >= 1 iteration, at least 2x2 px).
+    // Items the work-list kernels cover: fused iteration available (window 2..15, >= 1 iteration, at least 2x2 px), and
+    // at most 255 strips wide (a job of k_iterate_x's table names its strip in 8 bits); wider items run on their own.
     const bool het_params = p.iterations >= 1 && p.winsize / 2 >= 1 && p.winsize / 2 <= 7;
     const bool exact = ctx->opt_exact_rowsums != 0;
     std::vector<int> het, rest;
     for (int i = 0; i < n; i++)
-        (het_params && nsof_iterate_supported(p.winsize, descs[i].width, descs[i].height) ? het : rest).push_back(i);
+        (het_params && nsof_iterate_supported(p.winsize, descs[i].width, descs[i].height) &&
+                 (descs[i].width + NSOF_X_STRIP - 1) / NSOF_X_STRIP <= 255
+             ? het
+             : rest)
+            .push_back(i);
 
     if (!het.empty()) {
         const int nh = (int)het.size();
@@ -194,16 +199,23 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
             Li[j] = nsof_farneback_effective_levels(descs[het[j]].width, descs[het[j]].height, p.pyr_scale, p.levels);
             Lmax = std::max(Lmax, Li[j]);
         }
+        static const bool exact_2k = [] { const char* e = NSOF_AB_GETENV("NSOF_EXACT_IMPL"); return e && e[0] == '2'; }();
+        const bool exact_x = exact && !exact_2k;   // one fused kernel (k_iterate_x); 2k: column sums through HBM
+        // a list too small to fill the chip with (strip, item) jobs: the three-kernel small-batch form of the same order
+        long long jobs = 0;
+        for (int j = 0; j < nh; j++) {
+            jobs += (descs[het[j]].width + 191) / 192;
+            if ((unsigned long long)descs[het[j]].width * descs[het[j]].height * 40ull >= (1ull << 32)) jobs = 1ll << 40;   // 32-bit offsets per item
+        }
+        const bool exact_lat = exact_x && jobs <= ctx->opt_small_batch_jobs;
+        const bool use_xj = exact_x && !exact_lat;   // k_iterate_x runs the list: it needs its job tables
         // Per level: the item table (sorted into size classes), then the fused kernel's job table (8 counts + 8 lists).
         long long strips0 = 0;   // strips of the full-resolution level = the most any level has
-        for (int j = 0; j < nh; j++) {
-            const int st = (descs[het[j]].width + NSOF_X_STRIP - 1) / NSOF_X_STRIP;
-            if (st > 255) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "item %d: width %d above %d", het[j], descs[het[j]].width, 255 * NSOF_X_STRIP);
-            strips0 += st;
-        }
-        if (strips0 >= (1ll << 26) || nh >= (1 << 24))
+        for (int j = 0; j < nh; j++) strips0 += (descs[het[j]].width + NSOF_X_STRIP - 1) / NSOF_X_STRIP;
+        if (use_xj && (strips0 >= (1ll << 26) || nh >= (1 << 24)))
             return nsof_set_error(ctx, NSOF_EINVAL, "work list too long (%d items, %lld strips)", nh, strips0);
-        const size_t xj_words = align_up(8 + 8 * (size_t)strips0, 64);   // words per level at most (every strip in one list)
+        // words per level at most (every strip in one list)
+        const size_t xj_words = use_xj ? align_up(8 + 8 * (size_t)strips0, 64) : 0;
         const size_t items_bytes = align_up((size_t)(Lmax + 1) * nh * sizeof(nsof_het_item), 256);
         // two table slots used alternately: the upload of call c may still be queued when call c+1 builds its tables
         const size_t tab_bytes = align_up(items_bytes + (size_t)(Lmax + 1) * xj_words * sizeof(unsigned), 256);
@@ -267,24 +279,17 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
             }
             maxI = std::max(maxI, (size_t)oI); maxR = std::max(maxR, (size_t)oR); maxF = std::max(maxF, (size_t)oF);
             sort_into_classes(t, cnt[k], keyed, sorted, classes[k]);
-            xj_at[k] = xj_used;
-            xj_jobs[k] = build_xjobs(t, cnt[k], xj + xj_used, &xj_stride[k], keyed, lists);
-            xj_used += align_up(8 + 8 * (size_t)xj_stride[k], 64);
+            if (use_xj) {
+                xj_at[k] = xj_used;
+                xj_jobs[k] = build_xjobs(t, cnt[k], xj + xj_used, &xj_stride[k], keyed, lists);
+                xj_used += align_up(8 + 8 * (size_t)xj_stride[k], 64);
+            }
         }
         NSOF_HIP(ctx, hipMemcpyAsync((void*)d_tabs, tabs, items_bytes + xj_used * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
         NSOF_HIP(ctx, hipEventRecord(ctx->het_ev[slot], ctx->stream));
 
         // workspace: level images, expansions, two flow buffers (every level uses their leading part)
         const size_t szI = align_up(maxI * 4, 256), szR = align_up(maxR * 4, 256), szF = align_up(maxF * 8, 256);
-        static const bool exact_2k = [] { const char* e = NSOF_AB_GETENV("NSOF_EXACT_IMPL"); return e && e[0] == '2'; }();
-        const bool exact_x = exact && !exact_2k;   // one fused kernel (k_iterate_x); 2k: column sums through HBM
-        // a list too small to fill the chip with (strip, item) jobs: the three-kernel small-batch form of the same order
-        long long jobs = 0;
-        for (int j = 0; j < nh; j++) {
-            jobs += (descs[het[j]].width + 191) / 192;
-            if ((unsigned long long)descs[het[j]].width * descs[het[j]].height * 40ull >= (1ull << 32)) jobs = 1ll << 40;   // 32-bit offsets per item
-        }
-        const bool exact_lat = exact_x && jobs <= ctx->opt_small_batch_jobs;
         const size_t szV = (exact && !exact_x) || exact_lat ? szR : 0;   // column sums, 5 doubles per pixel = the expansion's footprint
         const size_t szM = exact_lat ? align_up(szR / 2, 256) : 0;        // matrices of the small-batch form, 5 floats per pixel
         if ((rc = nsof_ws_reserve(ctx, &ctx->ws, &ctx->ws_bytes, szI + szR + 2 * szF + szV + szM))) return rc;
@@ -536,7 +541,10 @@ __global__ __launch_bounds__(256) void k_paste_ordered(const PasteRec* __restric
         }
     }
     __syncthreads();
-    const int nl = min(n_later, 256);
+    // more than the LDS list holds: test every later rectangle of the table instead (dropping some would leave pixels
+    // with two writers)
+    const bool in_lds = n_later <= 256;
+    const int nl = in_lds ? n_later : 0;
     const float2* src = reinterpret_cast<const float2*>(tmp + r.tmp_off);
     float2* dst = reinterpret_cast<float2*>(r.dst);
     for (int i = blockIdx.x * 1024 + threadIdx.x; i < min(area, (int)(blockIdx.x + 1) * 1024); i += 256) {
@@ -544,6 +552,8 @@ __global__ __launch_bounds__(256) void k_paste_ordered(const PasteRec* __restric
         const int X = r.x0 + xx, Y = r.y0 + yy;
         bool covered = false;
         for (int k = 0; k < nl && !covered; k++) covered = X >= later[k].x && X < later[k].z && Y >= later[k].y && Y < later[k].w;
+        for (int j = r.idx + 1; !in_lds && j < cnt && !covered; j++)
+            covered = X >= fr[4 * j] && Y >= fr[4 * j + 1] && X < fr[4 * j + 2] && Y < fr[4 * j + 3];
         if (!covered) dst[(size_t)yy * canvas_pitch + xx] = src[i];
     }
 }

@@ -553,6 +553,11 @@ extern "C" int nsof_stage_blur_solve(nsof_ctx* ctx, int n_pairs, const float* d_
                                      int winsize, float* d_flow)
 {
     if (!ctx || !d_M || !d_flow || n_pairs < 1 || width < 1 || height < 1 || winsize < 2) return NSOF_EINVAL;
+    if (ctx->opt_exact_rowsums) {   // the library's row-sum order (k_blur_colsum + k_blur_rowsolve), as the driver runs it
+        const size_t need = (size_t)n_pairs * 5 * width * height * sizeof(double);
+        if (int rc = nsof_ws_reserve(ctx, &ctx->ws, &ctx->ws_bytes, need)) return rc;
+        return nsof_launch_blur_solve_exact(ctx, n_pairs, d_M, width, height, winsize, (double*)ctx->ws, d_flow);
+    }
     return nsof_launch_blur_solve(ctx, n_pairs, d_M, width, height, winsize, d_flow);
 }
 

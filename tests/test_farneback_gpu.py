@@ -3,8 +3,10 @@
 Tolerances.  north_star asks for max-abs 1e-4 against cv2; the oracle restates cv2's arithmetic
 (parity unpinned: cv2 is not available, see oracle/farneback_ref.c).  The HIP path follows the same
 operation order, so the stage tests demand bit-exact results wherever the order is identical
-(pyramid level, polynomial expansion, matrix update, flow resample) and <= 2 float ulps where only the
-double-precision row-sum order differs (blur + solve).  Whole-pipeline tolerance: 1e-5 px.
+(pyramid level, polynomial expansion, matrix update, flow resample).  In the default exact row-sum mode
+(NSOF_OPT_EXACT_ROWSUMS = 1) the blur + solve, the fused iteration and the whole pipeline are bit-identical to the
+oracle as well; only the fast mode (NSOF_OPT_EXACT_ROWSUMS = 0: each window summed directly, no oracle twin) is held to
+a tolerance: a few float ulps per stage, 1e-5 px for the pipeline (PIPE_TOL).
 """
 import ctypes as C
 
@@ -19,6 +21,27 @@ A = (0.5, 3, 15, 3, 5, 1.2, 0)
 B = (0.6, 3, 3, 3, 10, 1.05, 0)
 Cc = (0.6, 3, 4, 2, 1, 1.05, 0)
 PIPE_TOL = 1e-5
+
+
+@pytest.fixture
+def fast_mode(ctx):
+    """NSOF_OPT_EXACT_ROWSUMS = 0 (the fast mode) for one test; the default exact order is restored afterwards."""
+    from nsof import _lib
+    assert ctx.get_option(_lib.OPT_EXACT_ROWSUMS) == 1
+    ctx.set_option(_lib.OPT_EXACT_ROWSUMS, 0)
+    try:
+        yield 0
+    finally:
+        ctx.set_option(_lib.OPT_EXACT_ROWSUMS, 1)
+
+
+def _assert_flow(got, want, exact, tol=PIPE_TOL):
+    """Exact mode: the oracle's bits.  Fast mode: within `tol` px."""
+    if exact:
+        assert np.array_equal(got, want), f"max-abs {np.abs(got - want).max()}, {(got != want).sum()} values differ"
+    else:
+        err = np.abs(got - want).max()
+        assert err <= tol, f"max-abs {err}"
 
 
 def _dev(torch_dev, a):
@@ -135,10 +158,24 @@ def test_update_matrices_bit_exact(ctx, oracle, torch_dev, frames, shape):
     assert np.array_equal(got[0], want) and np.array_equal(got[1], want)
 
 
-@pytest.mark.parametrize("winsize", [15, 3, 4, 2, 31])
+@pytest.mark.parametrize("winsize", [15, 3, 4, 2, 31] + [w for w in range(2, 32) if w not in (15, 3, 4, 2, 31)])
 @pytest.mark.parametrize("shape", [(135, 240), (97, 531)])
 def test_blur_solve(ctx, oracle, torch_dev, winsize, shape):
+    """Exact mode (the default): the unfused exact pair (k_blur_colsum + k_blur_rowsolve) gives the oracle's bits, every
+    window 2..31."""
+    _blur_solve(ctx, oracle, torch_dev, 1, winsize, shape)
+
+
+@pytest.mark.parametrize("winsize", [15, 3, 4, 2, 31])
+@pytest.mark.parametrize("shape", [(135, 240), (97, 531)])
+def test_blur_solve_fast_mode(ctx, oracle, torch_dev, winsize, shape):
+    """Fast mode (the per-pixel window sums of k_blur_solve): a few float ulps."""
+    _blur_solve(ctx, oracle, torch_dev, 0, winsize, shape)
+
+
+def _blur_solve(ctx, oracle, torch_dev, rowsums, winsize, shape):
     import torch
+    from nsof import _lib
     from nsof import synth
     h, w = shape
     prev, nxt = synth.make_pair(9, h, w)
@@ -147,10 +184,17 @@ def test_blur_solve(ctx, oracle, torch_dev, winsize, shape):
     want, _ = oracle.update_flow_blur(R0, R1, flow, M, winsize, False)
     dM = _dev(torch_dev, _planar(M)[None])
     out = torch.empty((1, h, w, 2), dtype=torch.float32, device=torch_dev)
-    ctx.check(ctx._lib.nsof_stage_blur_solve(ctx.ptr, 1, dM.data_ptr(), w, h, winsize, out.data_ptr()))
-    ctx.synchronize()
+    ctx.set_option(_lib.OPT_EXACT_ROWSUMS, rowsums)
+    try:
+        ctx.check(ctx._lib.nsof_stage_blur_solve(ctx.ptr, 1, dM.data_ptr(), w, h, winsize, out.data_ptr()))
+        ctx.synchronize()
+    finally:
+        ctx.set_option(_lib.OPT_EXACT_ROWSUMS, 1)
     got = out.cpu().numpy()[0]
-    # column sums are order-identical; only the double row-sum order differs -> a few float ulps at most
+    if rowsums:
+        assert np.array_equal(got, want), f"max ulp {ulp_diff(got, want).max()}, {(got != want).sum()} values differ"
+        return
+    # fast mode: column sums are order-identical; only the double row-sum order differs -> a few float ulps at most
     d = np.abs(got - want)
     assert d.max() <= 1e-6 * max(1.0, np.abs(want).max()), d.max()
     assert (got != want).mean() < 0.01
@@ -159,7 +203,19 @@ def test_blur_solve(ctx, oracle, torch_dev, winsize, shape):
 @pytest.mark.parametrize("winsize", [15, 3, 4, 2, 9])
 @pytest.mark.parametrize("shape", [(135, 240), (97, 531), (20, 40)])
 def test_fused_iteration(ctx, oracle, torch_dev, winsize, shape):
-    """k_iterate == update_matrices followed by blur+solve (the unfused oracle stages)."""
+    """k_iterate_x (exact mode, the default) == update_matrices followed by blur+solve (the unfused oracle stages), bit
+    for bit."""
+    _fused_iteration(ctx, oracle, torch_dev, 1, winsize, shape)
+
+
+@pytest.mark.parametrize("winsize", [15, 3, 4, 2, 9])
+@pytest.mark.parametrize("shape", [(135, 240), (97, 531), (20, 40)])
+def test_fused_iteration_fast_mode(ctx, oracle, torch_dev, fast_mode, winsize, shape):
+    """k_iterate (fast mode) == the unfused oracle stages within float rounding."""
+    _fused_iteration(ctx, oracle, torch_dev, 0, winsize, shape)
+
+
+def _fused_iteration(ctx, oracle, torch_dev, rowsums, winsize, shape):
     import torch
     from nsof import synth
     h, w = shape
@@ -175,6 +231,9 @@ def test_fused_iteration(ctx, oracle, torch_dev, winsize, shape):
     ctx.synchronize()
     got = out.cpu().numpy()
     assert np.array_equal(got[0], got[1])
+    if rowsums:
+        assert np.array_equal(got[0], want), f"max ulp {ulp_diff(got[0], want).max()}, {(got[0] != want).sum()} values differ"
+        return
     d = np.abs(got[0] - want)
     assert d.max() <= 1e-6 * max(1.0, np.abs(want).max()), d.max()
     assert (got[0] != want).mean() < 0.01
@@ -199,27 +258,60 @@ def test_flow_upsample_bit_exact(ctx, oracle, torch_dev, pyr_scale, src, dst):
         assert np.array_equal(got[i], want)
 
 
+def test_iterate_upsample_is_unsupported_in_release_build(ctx, torch_dev):
+    """nsof_stage_iterate_upsample exists for the ABI; its kernel is in tuning builds only (include/nsof.h)."""
+    import torch
+    from nsof import _lib
+    h, w = 40, 64
+    R = torch.zeros((1, 2, 5 * h * w), dtype=torch.float32, device=torch_dev)
+    coarse = torch.zeros((1, h // 2, w // 2, 2), dtype=torch.float32, device=torch_dev)
+    out = torch.zeros((1, h, w, 2), dtype=torch.float32, device=torch_dev)
+    torch.cuda.synchronize()
+    rc = ctx._lib.nsof_stage_iterate_upsample(ctx.ptr, 1, R.data_ptr(), coarse.data_ptr(), w // 2, h // 2, w, h, 15, 0.5,
+                                              out.data_ptr())
+    assert rc == _lib.NSOF_EUNSUPPORTED
+    ctx.synchronize()
+    assert not out.any()
+
+
 @pytest.mark.parametrize("params", [A, B, Cc, (0.5, 1, 9, 1, 7, 1.5, 0), (0.8, 5, 7, 2, 3, 0.0, 0)],
                          ids=["A", "B", "C", "D", "E"])
 @pytest.mark.parametrize("shape", [(135, 240), (200, 303), (97, 131)])
 def test_pipeline_vs_oracle(nsof_lib, ctx, oracle, frames, params, shape):
+    _pipeline(nsof_lib, ctx, oracle, frames, 1, params, shape)
+
+
+@pytest.mark.parametrize("params", [A, B, Cc, (0.5, 1, 9, 1, 7, 1.5, 0), (0.8, 5, 7, 2, 3, 0.0, 0)],
+                         ids=["A", "B", "C", "D", "E"])
+@pytest.mark.parametrize("shape", [(135, 240), (200, 303), (97, 131)])
+def test_pipeline_vs_oracle_fast_mode(nsof_lib, ctx, oracle, frames, fast_mode, params, shape):
+    _pipeline(nsof_lib, ctx, oracle, frames, 0, params, shape)
+
+
+def _pipeline(nsof_lib, ctx, oracle, frames, rowsums, params, shape):
     prev, nxt = frames[shape]
     got = nsof_lib.calcOpticalFlowFarneback(prev, nxt, None, *params, ctx=ctx)
     want = oracle.farneback(prev, nxt, *params)
     assert got.shape == want.shape and got.dtype == np.float32
-    err = np.abs(got - want).max()
-    assert err <= PIPE_TOL, f"max-abs {err}"
+    _assert_flow(got, want, rowsums)
 
 
 def test_pipeline_1080p_vs_oracle(nsof_lib, ctx, oracle):
-    """BASELINE config 2 shape: one seeded synthetic 1920x1080 pair, params A and B."""
+    """BASELINE config 2 shape: one seeded synthetic 1920x1080 pair, params A and B (exact mode)."""
+    _pipeline_1080p(nsof_lib, ctx, oracle, 1)
+
+
+def test_pipeline_1080p_vs_oracle_fast_mode(nsof_lib, ctx, oracle, fast_mode):
+    _pipeline_1080p(nsof_lib, ctx, oracle, 0)
+
+
+def _pipeline_1080p(nsof_lib, ctx, oracle, rowsums):
     from nsof import synth
     prev, nxt = synth.make_pair(1234, 1080, 1920)
     for params in (A, B):
         got = nsof_lib.calcOpticalFlowFarneback(prev, nxt, None, *params, ctx=ctx)
         want = oracle.farneback(prev, nxt, *params)
-        err = np.abs(got - want).max()
-        assert err <= PIPE_TOL, f"{params}: max-abs {err}"
+        _assert_flow(got, want, rowsums)
     # known motion is recovered (interior, params A)
     got = nsof_lib.calcOpticalFlowFarneback(prev, nxt, None, *A, ctx=ctx)
     tf = synth.true_flow(1080, 1920)
@@ -287,35 +379,69 @@ def test_error_behaviour(nsof_lib, ctx, frames):
 
 
 def test_pipeline_4k_vs_oracle(nsof_lib, ctx, oracle):
-    """BASELINE config 5 frame size: one 3840x2160 pair, params A (the oracle needs ~4 s)."""
-    from nsof import synth
+    """BASELINE config 5 frame size: one 3840x2160 pair, params A (the oracle needs ~4 s): the oracle's bits in exact
+    mode, within PIPE_TOL in fast mode (one oracle run serves both)."""
+    from nsof import _lib, synth
     prev, nxt = synth.make_pair(5, 2160, 3840, shift=(3.0, 1.5))
     got = nsof_lib.calcOpticalFlowFarneback(prev, nxt, None, *A, ctx=ctx)
     want = oracle.farneback(prev, nxt, *A)
-    assert np.abs(got - want).max() <= PIPE_TOL
+    _assert_flow(got, want, True)
+    ctx.set_option(_lib.OPT_EXACT_ROWSUMS, 0)
+    try:
+        fast = nsof_lib.calcOpticalFlowFarneback(prev, nxt, None, *A, ctx=ctx)
+    finally:
+        ctx.set_option(_lib.OPT_EXACT_ROWSUMS, 1)
+    _assert_flow(fast, want, False)
 
 
 @pytest.mark.parametrize("shape", [(33, 40), (64, 64), (161, 161), (801, 801), (1080, 1920)])
 def test_context_reuse_across_shapes(nsof_lib, ctx, oracle, shape):
     """One context serves calls of changing size (workspace grows and is reused), as the ROI dispatcher needs."""
+    _context_reuse(nsof_lib, ctx, oracle, 1, shape)
+
+
+@pytest.mark.parametrize("shape", [(33, 40), (64, 64), (161, 161), (801, 801), (1080, 1920)])
+def test_context_reuse_across_shapes_fast_mode(nsof_lib, ctx, oracle, fast_mode, shape):
+    _context_reuse(nsof_lib, ctx, oracle, 0, shape)
+
+
+def _context_reuse(nsof_lib, ctx, oracle, rowsums, shape):
     from nsof import synth
     prev, nxt = synth.make_pair(shape[0], *shape)
     for params in (Cc, A):
         got = nsof_lib.calcOpticalFlowFarneback(prev, nxt, None, *params, ctx=ctx)
-        assert np.abs(got - oracle.farneback(prev, nxt, *params)).max() <= PIPE_TOL
+        _assert_flow(got, oracle.farneback(prev, nxt, *params), rowsums)
 
 
 def test_large_window_takes_unfused_path(nsof_lib, ctx, oracle, frames):
-    """winsize > 15 is outside the fused iteration kernels: the unfused pair must give the same result class."""
+    """winsize > 15 is outside the fused iteration kernels: the unfused pair gives the oracle's bits in exact mode."""
+    _large_window(nsof_lib, ctx, oracle, frames, 1)
+
+
+def test_large_window_takes_unfused_path_fast_mode(nsof_lib, ctx, oracle, frames, fast_mode):
+    _large_window(nsof_lib, ctx, oracle, frames, 0)
+
+
+def _large_window(nsof_lib, ctx, oracle, frames, rowsums):
     prev, nxt = frames[(200, 303)]
     p = (0.5, 2, 25, 2, 5, 1.2, 0)
     got = nsof_lib.calcOpticalFlowFarneback(prev, nxt, None, *p, ctx=ctx)
-    assert np.abs(got - oracle.farneback(prev, nxt, *p)).max() <= PIPE_TOL
+    _assert_flow(got, oracle.farneback(prev, nxt, *p), rowsums)
 
 
 def test_fuzz_parameters_vs_oracle(nsof_lib, ctx, oracle):
     """Seeded sweep over shapes and parameter combinations (exercises every templated kernel instance: poly_n 1..10,
-    window half-widths 1..8 and the unfused path beyond, blur sizes 3..31 incl. the runtime-size pyramid kernels)."""
+    window half-widths 1..8 and the unfused path beyond, blur sizes 3..31 incl. the runtime-size pyramid kernels):
+    the oracle's bits in exact mode."""
+    _fuzz(nsof_lib, ctx, oracle, 1)
+
+
+def test_fuzz_parameters_vs_oracle_fast_mode(nsof_lib, ctx, oracle, fast_mode):
+    """The same sweep in fast mode: within PIPE_TOL scaled by the flow's size, at most 1e-4."""
+    _fuzz(nsof_lib, ctx, oracle, 0)
+
+
+def _fuzz(nsof_lib, ctx, oracle, rowsums):
     from nsof import synth
     rng = np.random.default_rng(2024)
     worst = 0.0
@@ -327,6 +453,9 @@ def test_fuzz_parameters_vs_oracle(nsof_lib, ctx, oracle):
                                     rot_deg=float(rng.uniform(-1, 1)))
         got = nsof_lib.calcOpticalFlowFarneback(prev, nxt, None, *p, ctx=ctx)
         want = oracle.farneback(prev, nxt, *p)
+        if rowsums:
+            assert np.array_equal(got, want), (case, (h, w), p, float(np.abs(got - want).max()))
+            continue
         err = float(np.abs(got - want).max())
         worst = max(worst, err)
         assert err <= PIPE_TOL * max(1.0, float(np.abs(want).max()) / 10), (case, (h, w), p, err)
