@@ -138,6 +138,32 @@ int nsof_farneback_u8_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d
                                    double pyr_scale, int levels, int winsize, int iterations,
                                    int poly_n, double poly_sigma, int flags);
 
+/* Float frames (what cv2 takes after its convertTo(CV_32F)): the same three entries for float32 single-channel
+ * frames.  Every stride is in BYTES, as for the 8-bit entries; a row stride (and a pair / frame stride) must be a
+ * multiple of 4 and a row stride at least 4*width; frame pointers need only 4-byte alignment (crops that start at any
+ * element are fine; the pyramid kernels take their vector loads where rows are 16-byte aligned and scalar loads
+ * elsewhere).  Other argument checks, the flow layout, the host staging and the synchronisation are those of the
+ * 8-bit twins.  A float frame holding the values of an 8-bit frame gives the 8-bit entry's flow bit for bit.  The
+ * frames must be finite (the Python layer checks); work lists (nsof_pair_desc) stay 8-bit. */
+int nsof_farneback_f32(nsof_ctx* ctx,
+                       const float* prev, ptrdiff_t prev_stride,
+                       const float* next, ptrdiff_t next_stride,
+                       int width, int height,
+                       float* flow, ptrdiff_t flow_stride,
+                       double pyr_scale, int levels, int winsize, int iterations,
+                       int poly_n, double poly_sigma, int flags);
+int nsof_farneback_f32_batch_dev(nsof_ctx* ctx, int n_pairs,
+                                 const float* d_prev, const float* d_next,
+                                 ptrdiff_t row_stride, ptrdiff_t pair_stride,
+                                 int width, int height, float* d_flow,
+                                 double pyr_scale, int levels, int winsize, int iterations,
+                                 int poly_n, double poly_sigma, int flags);
+int nsof_farneback_f32_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_frames,
+                                    ptrdiff_t row_stride, ptrdiff_t frame_stride,
+                                    int width, int height, float* d_flow,
+                                    double pyr_scale, int levels, int winsize, int iterations,
+                                    int poly_n, double poly_sigma, int flags);
+
 /* One frame pair of a shape-heterogeneous batch: what ONE call of cv2.calcOpticalFlowFarneback(prev_region,
  * next_region, None, **farneback_params) receives and returns in the gated path -- optical_flow_seg.py:129-164
  * (one crop per connected component), :186-203 (the union box), :492-496 (the full frame) -- as plain pointers.
@@ -200,6 +226,9 @@ int nsof_farneback_level_size(int width, int height, double pyr_scale, int level
  * (channel 4), images back to back. */
 int nsof_stage_pyr_level(nsof_ctx* ctx, int n_img, const uint8_t* d_src, ptrdiff_t row_stride,
                          ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out);
+/* The same pyramid level from float32 frames (byte strides, multiples of 4). */
+int nsof_stage_pyr_level_f32(nsof_ctx* ctx, int n_img, const float* d_src, ptrdiff_t row_stride,
+                             ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out);
 int nsof_stage_polyexp(nsof_ctx* ctx, int n_img, const float* d_img, int width, int height,
                        int poly_n, double poly_sigma, float* d_R);
 /* Diagnostic: d_out[i] = the reciprocal the 2x2 solves use (rcp + Newton steps + residual correction, without the
@@ -294,6 +323,10 @@ int nsof_accum_set_slice_times(nsof_accum* acc, const int64_t* t_first, const in
  * mode NSOF_SURFACE_STATE: g = uint8(255 * w), the build-defined frame of the joined events -> flow pipeline. */
 enum { NSOF_SURFACE_CURRENT = 0, NSOF_SURFACE_STATE = 1 };
 int nsof_accum_surface_u8_dev(nsof_accum* acc, int which, int mode, uint8_t* d_out, ptrdiff_t row_stride);
+/* The same surface as a float32 frame on the DEVICE, d_out [H][row_stride_bytes / 4]: g computed as above and clipped to
+ * [0, 255], rounded to float instead of truncated to 8 bits (always finite; floor of it is the 8-bit frame's value).  The
+ * unquantised input of the float Farneback entries.  Asynchronous on the context's stream. */
+int nsof_accum_surface_f32_dev(nsof_accum* acc, int which, int mode, float* d_out, ptrdiff_t row_stride_bytes);
 /* nsof_accum_run + nsof_accum_surface_u8_dev of the state after the run's last slice, as one call: where the dense
  * scheme-1 update runs, its last pass writes the frame itself (no separate pass over the array, one launch less); the
  * frame is byte-identical to the two calls. */

@@ -150,8 +150,8 @@ __global__ __launch_bounds__(256) void k_fill(float* __restrict__ p, size_t n, f
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = v;
 }
 
-// The surface as an 8-bit frame, one pixel (modes: see k_surface_gray).
-__device__ __forceinline__ uint8_t surface_gray_one(float ww, float neg_lam, int mode)
+// The surface value of one pixel before its 8-bit truncation: g in [0, 255], double (modes: see k_surface_gray).
+__device__ __forceinline__ double surface_gray_value(float ww, float neg_lam, int mode)
 {
     double g;
     if (mode == 0) {
@@ -161,7 +161,12 @@ __device__ __forceinline__ uint8_t surface_gray_one(float ww, float neg_lam, int
         g = (double)(ww * 255.0f);
     }
     g = g < 0.0 ? 0.0 : (g > 255.0 ? 255.0 : g);   // NaN (I == 1 A exactly) cannot occur for R in [Ron, Roff]
-    return (uint8_t)g;
+    return g;
+}
+// The surface as an 8-bit frame, one pixel.
+__device__ __forceinline__ uint8_t surface_gray_one(float ww, float neg_lam, int mode)
+{
+    return (uint8_t)surface_gray_value(ww, neg_lam, mode);
 }
 // Where the fused dense update leaves the frame of the state it has just written (out == nullptr: nowhere).
 struct SurfOut {
@@ -595,6 +600,16 @@ __global__ __launch_bounds__(256) void k_surface_gray(const float* __restrict__ 
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= W || y >= H) return;
     out[(ptrdiff_t)y * stride + x] = surface_gray_one(w[(size_t)y * W + x], neg_lam, mode);
+}
+
+// The same surface as a float frame: g rounded to float32 instead of truncated to 8 bits (finite, in [0, 255]).
+__global__ __launch_bounds__(256) void k_surface_gray_f32(const float* __restrict__ w, float* __restrict__ out, int W, int H,
+                                                           ptrdiff_t stride, float neg_lam, int mode)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= W || y >= H) return;
+    reinterpret_cast<float*>(reinterpret_cast<char*>(out) + (ptrdiff_t)y * stride)[x] =
+        (float)surface_gray_value(w[(size_t)y * W + x], neg_lam, mode);
 }
 
 // ---- surface frames as copy + patch (round 4) ---------------------------------------------------------------------------
@@ -1396,6 +1411,20 @@ extern "C" int nsof_accum_surface_u8_dev(nsof_accum* a, int which, int mode, uin
     if (!a || !d_out || which < 0 || which > (a->split ? 1 : 0) || row_stride < a->W || mode < 0 || mode > 1) return NSOF_EINVAL;
     NSOF_HIP(a->ctx, hipSetDevice(a->ctx->device));
     return accum_surface(a, which, SurfOut{d_out, (long long)row_stride, a->W, (float)(-std::log(ROFF / RON)), mode});
+}
+
+extern "C" int nsof_accum_surface_f32_dev(nsof_accum* a, int which, int mode, float* d_out, ptrdiff_t row_stride_bytes)
+{
+    if (!a || !d_out || which < 0 || which > (a->split ? 1 : 0) || mode < 0 || mode > 1) return NSOF_EINVAL;
+    if (row_stride_bytes < (ptrdiff_t)a->W * 4 || (row_stride_bytes & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
+        return nsof_set_error(a->ctx, NSOF_EINVAL, "surface_f32: row stride must be a multiple of 4 and >= 4*W, pointer 4-byte aligned");
+    nsof_ctx* ctx = a->ctx;
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    dim3 grid((a->W + 255) / 256, a->H);
+    hipLaunchKernelGGL(k_surface_gray_f32, grid, dim3(256), 0, ctx->stream, a->w[which], d_out, a->W, a->H, row_stride_bytes,
+                       (float)(-std::log(ROFF / RON)), mode);
+    NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
 }
 
 extern "C" int nsof_accum_run_surface(nsof_accum* a, int64_t first_slice, int64_t n_slices, int which, int mode, uint8_t* d_out,

@@ -66,9 +66,22 @@ __device__ __forceinline__ void lin_coord_y(int d, double scale, int& s, float& 
 }
 
 // ---------------------------------------------------------------------------------------
-// Pyramid level preparation: u8 -> f32, separable Gaussian (sepFilter2D order), bilinear
+// Pyramid level preparation: u8 / f32 -> f32, separable Gaussian (sepFilter2D order), bilinear
 // resample of the blurred FULL-RES image to (wk, hk).
 // ---------------------------------------------------------------------------------------
+
+// Source frames are 8-bit (T = uint8_t) or float (T = float); row and image strides are in BYTES for both.  px() is
+// the one load-and-convert of a source pixel (u8: the exact conversion; f32: the value itself), srow() the start of a
+// byte-strided row.  For T = uint8_t both are exactly the expressions the 8-bit kernels always had.
+template <typename T>
+__device__ __forceinline__ float px(const T* p) { return (float)*p; }
+template <typename T>
+__device__ __forceinline__ const T* srow(const T* img, ptrdiff_t r, ptrdiff_t stride)
+{
+    return reinterpret_cast<const T*>(reinterpret_cast<const char*>(img) + r * stride);
+}
+template <typename T>
+constexpr bool kU8 = std::is_same<T, uint8_t>::value;
 
 // Row filter at an (unreflected) column c of one row, ordering per kernel size.
 // KS > 0: kernel size known at compile time (loops unroll, taps are scalar registers); KS == 0: runtime size,
@@ -100,16 +113,18 @@ __device__ __forceinline__ float col_filter(TapF tk, int ksize, int rr, LoadF hv
 // Geometry of one image of a pyramid-level launch.  HET == false: the uniform batch (every image has the kernel
 // arguments' shape, image z lives at src + z*img_stride and goes to out + z*wk*hk).  HET == true: image z belongs to
 // work item z/2 of the device table (z & 1: prev / next), see nsof_het_item.
+template <typename T>
 struct PrepImg {
-    const uint8_t* img;
+    const T* img;
     float* dst;
 };
-template <bool HET>
-__device__ __forceinline__ bool prep_geom(PrepImg& g, const uint8_t* src, ptrdiff_t& row_stride, ptrdiff_t img_stride,
+template <bool HET, typename T>
+__device__ __forceinline__ bool prep_geom(PrepImg<T>& g, const T* src, ptrdiff_t& row_stride, ptrdiff_t img_stride,
                                           int& W, int& H, int& wk, int& hk, float* out,
                                           const nsof_het_item* __restrict__ items, int want_flag)
 {
-    if constexpr (HET) {
+    if constexpr (HET) {   // (work lists are 8-bit only)
+        static_assert(kU8<T>, "work-list items carry 8-bit frames");
         const nsof_het_item& it = items[blockIdx.z >> 1];
         const int which = blockIdx.z & 1;
         if (want_flag >= 0 && (it.flags & NSOF_HET_VEC0) != want_flag) return false;
@@ -118,15 +133,15 @@ __device__ __forceinline__ bool prep_geom(PrepImg& g, const uint8_t* src, ptrdif
         g.img = it.src[which];
         g.dst = out + it.offI + (size_t)which * wk * hk;
     } else {
-        g.img = src + (ptrdiff_t)blockIdx.z * img_stride;
+        g.img = srow(src, blockIdx.z, img_stride);
         g.dst = out + (size_t)blockIdx.z * wk * hk;
     }
     return true;
 }
 
 // Same-size level (k = 0), generic: one thread per pixel, no resample.
-template <bool HET>
-__global__ __launch_bounds__(256) void k_prep_same(const uint8_t* __restrict__ src, ptrdiff_t row_stride,
+template <bool HET, typename T = uint8_t>
+__global__ __launch_bounds__(256) void k_prep_same(const T* __restrict__ src, ptrdiff_t row_stride,
                                                     ptrdiff_t img_stride, int W, int H, nsof_blur_taps t,
                                                     float* __restrict__ out, const nsof_het_item* __restrict__ items,
                                                     int want_flag)
@@ -135,16 +150,16 @@ __global__ __launch_bounds__(256) void k_prep_same(const uint8_t* __restrict__ s
     if (threadIdx.x < NSOF_MAX_BLUR_TAPS) s_tk[threadIdx.x] = t.k[threadIdx.x];
     __syncthreads();
     auto tk = [&](int j) { return s_tk[j]; };
-    PrepImg g;
+    PrepImg<T> g;
     int wk = W, hk = H;
     if (!prep_geom<HET>(g, src, row_stride, img_stride, W, H, wk, hk, out, items, want_flag)) return;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= W || y >= H) return;
-    const uint8_t* img = g.img;
+    const T* img = g.img;
     auto hv = [&](int rr) {
-        const uint8_t* rowp = img + (ptrdiff_t)reflect101(rr, H) * row_stride;
-        return row_filter<0>(tk, t.ksize, x, [&](int c) { return (float)rowp[reflect101(c, W)]; });
+        const T* rowp = srow(img, reflect101(rr, H), row_stride);
+        return row_filter<0>(tk, t.ksize, x, [&](int c) { return px(rowp + reflect101(c, W)); });
     };
     g.dst[(size_t)y * W + x] = col_filter<0>(tk, t.ksize, y, hv);
 }
@@ -153,14 +168,16 @@ __global__ __launch_bounds__(256) void k_prep_same(const uint8_t* __restrict__ s
 // One aligned dword load per row; the two bytes outside the dword come from the neighbouring lanes
 // (the wave's edge lanes fetch theirs from memory); row-filter results are shared between the three
 // output rows that use them; 16-B stores.  Requires 4-byte aligned rows (else k_prep_same).
+// T = float: the lane's 4 pixels are one aligned 16-B load per row (16-byte aligned rows, else k_prep_same), the two
+// outside values come from the neighbouring lanes the same way.
 constexpr int PREP0_ROWS = 8;
-template <bool HET>
-__global__ __launch_bounds__(256) void k_prep_same3_vec(const uint8_t* __restrict__ src, ptrdiff_t row_stride,
+template <bool HET, typename T = uint8_t>
+__global__ __launch_bounds__(256) void k_prep_same3_vec(const T* __restrict__ src, ptrdiff_t row_stride,
                                                          ptrdiff_t img_stride, int W, int H, float k0, float k1,
                                                          float* __restrict__ out,
                                                          const nsof_het_item* __restrict__ items)
 {
-    PrepImg g;
+    PrepImg<T> g;
     int wk = W, hk = H;
     if (!prep_geom<HET>(g, src, row_stride, img_stride, W, H, wk, hk, out, items, NSOF_HET_VEC0)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -169,17 +186,27 @@ __global__ __launch_bounds__(256) void k_prep_same3_vec(const uint8_t* __restric
     if (y0 >= H || blockIdx.x * 256 >= W) return;                 // wave-uniform
     const bool live = x < W;
     const int xl = live ? x : 0;                                  // dead lanes still take part in the shuffles
-    const uint8_t* img = g.img;
+    const T* img = g.img;
     float* dst = g.dst;
 
     auto hrow = [&](int rr, float (&h)[4]) {                      // row filter of source row rr (reflected)
-        const uint8_t* rowp = img + (ptrdiff_t)reflect101(rr, H) * row_stride;
-        const unsigned v = *reinterpret_cast<const unsigned*>(rowp + xl);
-        unsigned lft = __shfl_up(v, 1) >> 24, rgt = __shfl_down(v, 1) & 0xffu;
-        if (lane == 0 || x == 0) lft = rowp[reflect101(xl - 1, W)];
-        if (lane == 63 || x + 4 >= W) rgt = rowp[reflect101(xl + 4, W)];
-        const float s0 = (float)(v & 0xffu), s1 = (float)((v >> 8) & 0xffu), s2 = (float)((v >> 16) & 0xffu),
-                    s3 = (float)(v >> 24), sl = (float)lft, sr = (float)rgt;
+        const T* rowp = srow(img, reflect101(rr, H), row_stride);
+        float s0, s1, s2, s3, sl, sr;
+        if constexpr (kU8<T>) {
+            const unsigned v = *reinterpret_cast<const unsigned*>(rowp + xl);
+            unsigned lft = __shfl_up(v, 1) >> 24, rgt = __shfl_down(v, 1) & 0xffu;
+            if (lane == 0 || x == 0) lft = rowp[reflect101(xl - 1, W)];
+            if (lane == 63 || x + 4 >= W) rgt = rowp[reflect101(xl + 4, W)];
+            s0 = (float)(v & 0xffu); s1 = (float)((v >> 8) & 0xffu); s2 = (float)((v >> 16) & 0xffu);
+            s3 = (float)(v >> 24); sl = (float)lft; sr = (float)rgt;
+        } else {
+            const float4 v = *reinterpret_cast<const float4*>(rowp + xl);
+            sl = __shfl_up(v.w, 1);
+            sr = __shfl_down(v.x, 1);
+            if (lane == 0 || x == 0) sl = rowp[reflect101(xl - 1, W)];
+            if (lane == 63 || x + 4 >= W) sr = rowp[reflect101(xl + 4, W)];
+            s0 = v.x; s1 = v.y; s2 = v.z; s3 = v.w;
+        }
         h[0] = NSOF_MADD(sl + s1, k1, s0 * k0);
         h[1] = NSOF_MADD(s0 + s2, k1, s1 * k0);
         h[2] = NSOF_MADD(s1 + s3, k1, s2 * k0);
@@ -218,8 +245,11 @@ __global__ __launch_bounds__(256) void k_prep_same3_vec(const uint8_t* __restric
 //   * column filter at the two sampled rows, then resize's 2x2 blend (all four weights are exactly 0.5).
 // Same operation order as the other prep kernels (row_filter / col_filter), so the output is bit-identical.
 // The walk of one wave: column group `bx * 64 + lane`, output rows [seg * seg_rows, (seg + 1) * seg_rows) of image z.
-template <int S, int KS, int CW>
-__device__ __forceinline__ void prep_decim_body(const uint8_t* __restrict__ src, ptrdiff_t row_stride, ptrdiff_t img_stride,
+// T = float: the same walk over CW floats per lane (CW / 4 aligned 16-B loads per row, HB / 4 per halo side; the
+// launchers take CW = 8 and 16-byte aligned rows), prefetching one output row ahead only at S = 2 -- a raw f32 row is
+// four times the registers of an 8-bit one.
+template <int S, int KS, int CW, typename T = uint8_t>
+__device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdiff_t row_stride, ptrdiff_t img_stride,
                                                 int W, int H, int wk, int hk, int seg_rows, const nsof_blur_taps& t,
                                                 float* __restrict__ out, int bx, int seg, int z)
 {
@@ -231,14 +261,14 @@ __device__ __forceinline__ void prep_decim_body(const uint8_t* __restrict__ src,
     constexpr int WIN = HB + CW + HB;
     static_assert(NPX >= 1, "lane narrower than one output pixel");
     const int lane = threadIdx.x & 63;
-    const int T = bx * 64 + lane;                              // CW-column group
+    const int TG = bx * 64 + lane;                             // CW-column group
     const int dy0 = seg * seg_rows;
     if (dy0 >= hk) return;                                     // wave-uniform
     const int dy1 = min(dy0 + seg_rows, hk);
-    const bool live = CW * T < W;
-    const int xc0 = live ? CW * T : 0;
+    const bool live = CW * TG < W;
+    const int xc0 = live ? CW * TG : 0;
     const bool edge_l = xc0 == 0, edge_r = xc0 + CW >= W;
-    const uint8_t* img = src + (ptrdiff_t)z * img_stride;
+    const T* img = srow(src, z, img_stride);
     float* dst = out + (size_t)z * wk * hk;
     auto tk = [&](int j) { return t.k[j]; };                   // static index after unrolling
 
@@ -248,35 +278,64 @@ __device__ __forceinline__ void prep_decim_body(const uint8_t* __restrict__ src,
     // evaluates the row filter at this lane's sampled columns -> ring[slot]; between the two a row can stay in flight
     // while the rows before it are filtered (S <= 4: the rows of the NEXT output row are fetched before this one's are
     // used -- with one output row's 2 or 4 source rows in flight per wave the kernel waited for memory half the time).
-    struct Raw {
+    struct RawU8 {
         unsigned cw[CW / 4], hl[HD], hr[HD];
     };
+    struct RawF32 {
+        float4 cw[CW / 4], hl[HD], hr[HD];
+    };
+    using Raw = std::conditional_t<kU8<T>, RawU8, RawF32>;
     auto fetch = [&](int r, Raw& q) {
-        const uint8_t* rowp = img + (ptrdiff_t)reflect101(r, H) * row_stride + xc0;
-        if (CW == 16) {
-            const uint4 c = *reinterpret_cast<const uint4*>(rowp);
-            q.cw[0] = c.x; q.cw[1] = c.y; q.cw[(CW / 4 > 2) ? 2 : 0] = c.z; q.cw[(CW / 4 > 3) ? 3 : 0] = c.w;
-        } else {
-            const uint2 c = *reinterpret_cast<const uint2*>(rowp);
-            q.cw[0] = c.x; q.cw[1] = c.y;
-        }
-        const uint8_t* lp = edge_l ? rowp : rowp - HB;          // edge lanes: any valid address, value unused
-        const uint8_t* rp = edge_r ? rowp : rowp + CW;
+        const T* rowp = srow(img, reflect101(r, H), row_stride) + xc0;
+        if constexpr (!kU8<T>) {
 #pragma unroll
-        for (int d = 0; d < HD; d++) {
-            q.hl[d] = reinterpret_cast<const unsigned*>(lp)[d];
-            q.hr[d] = reinterpret_cast<const unsigned*>(rp)[d];
+            for (int d = 0; d < CW / 4; d++) q.cw[d] = reinterpret_cast<const float4*>(rowp)[d];
+            // edge lanes: any 16-byte aligned address inside the row, value unused (the launchers keep HB <= CW and
+            // W >= 64, so every load here stays inside the row)
+            const float4* lp = reinterpret_cast<const float4*>(edge_l ? rowp : rowp - HB);
+            const float4* rp = reinterpret_cast<const float4*>(edge_r ? rowp + CW - HB : rowp + CW);
+#pragma unroll
+            for (int d = 0; d < HD; d++) {
+                q.hl[d] = lp[d];
+                q.hr[d] = rp[d];
+            }
+        } else {
+            if (CW == 16) {
+                const uint4 c = *reinterpret_cast<const uint4*>(rowp);
+                q.cw[0] = c.x; q.cw[1] = c.y; q.cw[(CW / 4 > 2) ? 2 : 0] = c.z; q.cw[(CW / 4 > 3) ? 3 : 0] = c.w;
+            } else {
+                const uint2 c = *reinterpret_cast<const uint2*>(rowp);
+                q.cw[0] = c.x; q.cw[1] = c.y;
+            }
+            const uint8_t* lp = edge_l ? rowp : rowp - HB;          // edge lanes: any valid address, value unused
+            const uint8_t* rp = edge_r ? rowp : rowp + CW;
+#pragma unroll
+            for (int d = 0; d < HD; d++) {
+                q.hl[d] = reinterpret_cast<const unsigned*>(lp)[d];
+                q.hr[d] = reinterpret_cast<const unsigned*>(rp)[d];
+            }
         }
     };
     auto filt = [&](const Raw& q, float (&dstrow)[NC]) {
         float raw[WIN];   // window [xc0 - HB, xc0 + CW + HB) as loaded
+        if constexpr (kU8<T>) {
 #pragma unroll
-        for (int b = 0; b < HB; b++) {
-            raw[b] = (float)((q.hl[b >> 2] >> (8 * (b & 3))) & 0xffu);
-            raw[HB + CW + b] = (float)((q.hr[b >> 2] >> (8 * (b & 3))) & 0xffu);
+            for (int b = 0; b < HB; b++) {
+                raw[b] = (float)((q.hl[b >> 2] >> (8 * (b & 3))) & 0xffu);
+                raw[HB + CW + b] = (float)((q.hr[b >> 2] >> (8 * (b & 3))) & 0xffu);
+            }
+#pragma unroll
+            for (int b = 0; b < CW; b++) raw[HB + b] = (float)((q.cw[b >> 2] >> (8 * (b & 3))) & 0xffu);
+        } else {
+            auto el = [](const float4& v, int e) { return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w)); };
+#pragma unroll
+            for (int b = 0; b < HB; b++) {
+                raw[b] = el(q.hl[b >> 2], b & 3);
+                raw[HB + CW + b] = el(q.hr[b >> 2], b & 3);
+            }
+#pragma unroll
+            for (int b = 0; b < CW; b++) raw[HB + b] = el(q.cw[b >> 2], b & 3);
         }
-#pragma unroll
-        for (int b = 0; b < CW; b++) raw[HB + b] = (float)((q.cw[b >> 2] >> (8 * (b & 3))) & 0xffu);
         float fb[WIN];
 #pragma unroll
         for (int b = 0; b < CW; b++) fb[HB + b] = raw[HB + b];
@@ -301,7 +360,7 @@ __device__ __forceinline__ void prep_decim_body(const uint8_t* __restrict__ src,
 #ifndef NSOF_DECIM_PF
 #define NSOF_DECIM_PF 4
 #endif
-    constexpr bool PF = S <= NSOF_DECIM_PF;   // prefetch one output row ahead
+    constexpr bool PF = S <= (kU8<T> ? NSOF_DECIM_PF : 2);   // prefetch one output row ahead
 
     // relative row index rel = r - base, base = first row needed by output row dy0; slot = rel % RING
     const int base = S * dy0 + S / 2 - 1 - R;
@@ -346,7 +405,7 @@ __device__ __forceinline__ void prep_decim_body(const uint8_t* __restrict__ src,
                     const float t1 = B10 * 0.5f + B11 * 0.5f;
                     o[j] = t0 * 0.5f + t1 * 0.5f;
                 }
-                float* op = dst + (size_t)dy * wk + NPX * T;
+                float* op = dst + (size_t)dy * wk + NPX * TG;
                 if (NPX == 8) {
                     nsof_store_stream4(op, o[0], o[1 % NPX], o[2 % NPX], o[3 % NPX]);
                     nsof_store_stream4(op + 4, o[4 % NPX], o[5 % NPX], o[6 % NPX], o[7 % NPX]);
@@ -362,12 +421,12 @@ __device__ __forceinline__ void prep_decim_body(const uint8_t* __restrict__ src,
     }
 }
 
-template <int S, int KS, int CW>
-__global__ __launch_bounds__(256) void k_prep_decim(const uint8_t* __restrict__ src, ptrdiff_t row_stride,
+template <int S, int KS, int CW, typename T = uint8_t>
+__global__ __launch_bounds__(256) void k_prep_decim(const T* __restrict__ src, ptrdiff_t row_stride,
                                                      ptrdiff_t img_stride, int W, int H, int wk, int hk, int seg_rows,
                                                      nsof_blur_taps t, float* __restrict__ out)
 {
-    prep_decim_body<S, KS, CW>(src, row_stride, img_stride, W, H, wk, hk, seg_rows, t, out, blockIdx.x,
+    prep_decim_body<S, KS, CW, T>(src, row_stride, img_stride, W, H, wk, hk, seg_rows, t, out, blockIdx.x,
                                blockIdx.y * 4 + (threadIdx.x >> 6), blockIdx.z);
 }
 
@@ -380,23 +439,23 @@ struct Decim3 {
     float* out[3];
     int seg_rows[3];
 };
-template <int CW>
-__global__ __launch_bounds__(768) void k_prep_decim3(const uint8_t* __restrict__ src, ptrdiff_t row_stride,
+template <int CW, typename T = uint8_t>
+__global__ __launch_bounds__(768) void k_prep_decim3(const T* __restrict__ src, ptrdiff_t row_stride,
                                                       ptrdiff_t img_stride, int W, int H, Decim3 d)
 {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int seg = blockIdx.y * 4 + (wave & 3);
     if (wave < 4)
-        prep_decim_body<2, 3, CW>(src, row_stride, img_stride, W, H, W / 2, H / 2, d.seg_rows[0], d.t[0], d.out[0], blockIdx.x, seg, blockIdx.z);
+        prep_decim_body<2, 3, CW, T>(src, row_stride, img_stride, W, H, W / 2, H / 2, d.seg_rows[0], d.t[0], d.out[0], blockIdx.x, seg, blockIdx.z);
     else if (wave < 8)
-        prep_decim_body<4, 9, CW>(src, row_stride, img_stride, W, H, W / 4, H / 4, d.seg_rows[1], d.t[1], d.out[1], blockIdx.x, seg, blockIdx.z);
+        prep_decim_body<4, 9, CW, T>(src, row_stride, img_stride, W, H, W / 4, H / 4, d.seg_rows[1], d.t[1], d.out[1], blockIdx.x, seg, blockIdx.z);
     else
-        prep_decim_body<8, 19, CW>(src, row_stride, img_stride, W, H, W / 8, H / 8, d.seg_rows[2], d.t[2], d.out[2], blockIdx.x, seg, blockIdx.z);
+        prep_decim_body<8, 19, CW, T>(src, row_stride, img_stride, W, H, W / 8, H / 8, d.seg_rows[2], d.t[2], d.out[2], blockIdx.x, seg, blockIdx.z);
 }
 
 // Resampled level, generic fallback: one thread per destination pixel, no data sharing.
-template <bool HET>
-__global__ __launch_bounds__(256) void k_prep_naive(const uint8_t* __restrict__ src, ptrdiff_t row_stride,
+template <bool HET, typename T = uint8_t>
+__global__ __launch_bounds__(256) void k_prep_naive(const T* __restrict__ src, ptrdiff_t row_stride,
                                                      ptrdiff_t img_stride, int W, int H, int wk, int hk,
                                                      double scale_x, double scale_y, nsof_blur_taps t,
                                                      float* __restrict__ out, const nsof_het_item* __restrict__ items)
@@ -405,13 +464,13 @@ __global__ __launch_bounds__(256) void k_prep_naive(const uint8_t* __restrict__ 
     if (threadIdx.x < NSOF_MAX_BLUR_TAPS) s_tk[threadIdx.x] = t.k[threadIdx.x];
     __syncthreads();
     auto tk = [&](int j) { return s_tk[j]; };
-    PrepImg g;
+    PrepImg<T> g;
     prep_geom<HET>(g, src, row_stride, img_stride, W, H, wk, hk, out, items, -1);
     if constexpr (HET) { scale_x = 1. / ((double)wk / W); scale_y = 1. / ((double)hk / H); }
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (dx >= wk || dy >= hk) return;
-    const uint8_t* img = g.img;
+    const T* img = g.img;
     int sx, sy;
     float a1, b1;
     lin_coord_x(dx, scale_x, W, sx, a1);
@@ -421,8 +480,8 @@ __global__ __launch_bounds__(256) void k_prep_naive(const uint8_t* __restrict__ 
     const int r0 = clampi(sy, 0, H - 1), r1 = clampi(sy + 1, 0, H - 1);
     auto blur = [&](int rr, int cc) {
         auto hv = [&](int q) {
-            const uint8_t* rowp = img + (ptrdiff_t)reflect101(q, H) * row_stride;
-            return row_filter<0>(tk, t.ksize, cc, [&](int c) { return (float)rowp[reflect101(c, W)]; });
+            const T* rowp = srow(img, reflect101(q, H), row_stride);
+            return row_filter<0>(tk, t.ksize, cc, [&](int c) { return px(rowp + reflect101(c, W)); });
         };
         return col_filter<0>(tk, t.ksize, rr, hv);
     };
@@ -432,20 +491,20 @@ __global__ __launch_bounds__(256) void k_prep_naive(const uint8_t* __restrict__ 
 }
 
 // Resampled level, LDS-tiled: a 32x8 destination tile per 256-thread block.
-//   phase 1: source footprint (with blur halo, borders reflected) -> LDS as u8 (coalesced row segments)
+//   phase 1: source footprint (with blur halo, borders reflected) -> LDS as T (coalesced row segments)
 //   phase 2: row filter only at the 2 source columns each destination column samples
 //   phase 3: column filter only at the 2 source rows each destination row samples
 //   phase 4: bilinear blend (horizontal first, then vertical, as resize does)
 // KS = compile-time kernel size (3, 5, 9, 19: pyr_scale 0.5 / 0.6 with up to 3 levels) or 0 = runtime.
 constexpr int PREP_TW = 32, PREP_TH = 8;
-template <int KS, bool HET>
-__global__ __launch_bounds__(256) void k_prep_tiled(const uint8_t* __restrict__ src, ptrdiff_t row_stride,
+template <int KS, bool HET, typename T = uint8_t>
+__global__ __launch_bounds__(256) void k_prep_tiled(const T* __restrict__ src, ptrdiff_t row_stride,
                                                      ptrdiff_t img_stride, int W, int H, int wk, int hk,
                                                      double scale_x, double scale_y, int rw_cap, int rh_cap,
                                                      nsof_blur_taps t, float* __restrict__ out,
                                                      const nsof_het_item* __restrict__ items)
 {
-    PrepImg g;
+    PrepImg<T> g;
     prep_geom<HET>(g, src, row_stride, img_stride, W, H, wk, hk, out, items, -1);
     if constexpr (HET) {
         scale_x = 1. / ((double)wk / W);
@@ -455,7 +514,7 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const uint8_t* __restrict__ 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* sH = reinterpret_cast<float*>(smem);                 // [rh_cap][2*TW]
     float* sB = sH + (size_t)rh_cap * (2 * PREP_TW);            // [2*TH][2*TW]
-    unsigned char* sU = reinterpret_cast<unsigned char*>(sB + 2 * PREP_TH * 2 * PREP_TW);  // [rh_cap][rw_cap]
+    T* sU = reinterpret_cast<T*>(sB + 2 * PREP_TH * 2 * PREP_TW);  // [rh_cap][rw_cap]
     __shared__ int s_c[2 * PREP_TW];   // absolute source column per (dst col, 0/1)
     __shared__ int s_r[2 * PREP_TH];   // absolute source row per (dst row, 0/1)
     __shared__ float s_a[PREP_TW], s_b[PREP_TH];
@@ -464,7 +523,7 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const uint8_t* __restrict__ 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ksize = KS ? KS : t.ksize, r = ksize >> 1;
     const int dx0 = blockIdx.x * PREP_TW, dy0 = blockIdx.y * PREP_TH;
-    const uint8_t* img = g.img;
+    const T* img = g.img;
     auto tk = [&](int j) { return KS ? t.k[j] : s_tk[j]; };   // KS > 0: j is a constant after unrolling
 
     if (tid < PREP_TW) {
@@ -490,7 +549,7 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const uint8_t* __restrict__ 
     const int RW0 = s_c[2 * PREP_TW - 1] + r - C0 + 1;
     const int R0 = s_r[0] - r, RH = s_r[2 * PREP_TH - 1] + r - R0 + 1;
     // host sized rw_cap/rh_cap from the same arithmetic (+4 columns of slack for the aligned copy below)
-    const bool interior = C0 >= 0 && C0 + RW0 <= W && R0 >= 0 && R0 + RH <= H && (W & 3) == 0 &&
+    const bool interior = kU8<T> && C0 >= 0 && C0 + RW0 <= W && R0 >= 0 && R0 + RH <= H && (W & 3) == 0 &&
                           (row_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(img) & 3) == 0;
     if (interior) {
         // no border inside the footprint: copy whole aligned dwords (64 lanes x 4 B per wave-instruction)
@@ -498,13 +557,13 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const uint8_t* __restrict__ 
         C0 = C0a;   // the LDS image now starts at the aligned column
 #pragma unroll 4
         for (int rr = wave; rr < RH; rr += 4) {
-            const uint8_t* rowp = img + (ptrdiff_t)(R0 + rr) * row_stride + C0a;
+            const T* rowp = srow(img, R0 + rr, row_stride) + C0a;
             for (int d = lane; d < nd; d += 64)
                 *reinterpret_cast<unsigned*>(sU + rr * rw_cap + 4 * d) = *reinterpret_cast<const unsigned*>(rowp + 4 * d);
         }
     } else {
-        for (int rr = wave; rr < RH; rr += 4) {          // border tile: per byte, BORDER_REFLECT_101
-            const uint8_t* rowp = img + (ptrdiff_t)reflect101(R0 + rr, H) * row_stride;
+        for (int rr = wave; rr < RH; rr += 4) {          // border tile (and f32 frames): per pixel, BORDER_REFLECT_101
+            const T* rowp = srow(img, reflect101(R0 + rr, H), row_stride);
             for (int cc = lane; cc < RW0; cc += 64) sU[rr * rw_cap + cc] = rowp[reflect101(C0 + cc, W)];
         }
     }
@@ -513,8 +572,8 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const uint8_t* __restrict__ 
         const int cj = s_c[lane] - C0;                // this lane's sampled column, local
 #pragma unroll 2
         for (int rr = wave; rr < RH; rr += 4) {
-            const unsigned char* rowp = sU + rr * rw_cap;
-            sH[rr * (2 * PREP_TW) + lane] = row_filter<KS>(tk, ksize, cj, [&](int c) { return (float)rowp[c]; });
+            const T* rowp = sU + rr * rw_cap;
+            sH[rr * (2 * PREP_TW) + lane] = row_filter<KS>(tk, ksize, cj, [&](int c) { return px(rowp + c); });
         }
     }
     __syncthreads();
@@ -541,20 +600,20 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const uint8_t* __restrict__ 
 // contributes KS+1 consecutive bytes, fetched as unaligned dwords (L1/L2 resident: the u8 frame is 2 MB).
 // More arithmetic than the LDS-tiled variant but no per-tile overhead -- measured 3-6x faster at 1080p.
 // Pixels whose footprint leaves the image take a per-byte path with BORDER_REFLECT_101 indexing.
-template <int KS, bool HET>
-__global__ __launch_bounds__(256) void k_prep_direct(const uint8_t* __restrict__ src, ptrdiff_t row_stride,
+template <int KS, bool HET, typename T = uint8_t>
+__global__ __launch_bounds__(256) void k_prep_direct(const T* __restrict__ src, ptrdiff_t row_stride,
                                                       ptrdiff_t img_stride, int W, int H, int wk, int hk,
                                                       double scale_x, double scale_y, nsof_blur_taps t,
                                                       float* __restrict__ out, const nsof_het_item* __restrict__ items)
 {
     constexpr int R = KS / 2, NB = KS + 1, ND = (NB + 3) / 4;
-    PrepImg g;
+    PrepImg<T> g;
     prep_geom<HET>(g, src, row_stride, img_stride, W, H, wk, hk, out, items, -1);
     if constexpr (HET) { scale_x = 1. / ((double)wk / W); scale_y = 1. / ((double)hk / H); }
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (dx >= wk || dy >= hk) return;
-    const uint8_t* img = g.img;
+    const T* img = g.img;
     int sx, sy;
     float a1, b1;
     lin_coord_x(dx, scale_x, W, sx, a1);
@@ -568,24 +627,29 @@ __global__ __launch_bounds__(256) void k_prep_direct(const uint8_t* __restrict__
     float H0[KS + 1], H1[KS + 1];
 #pragma unroll
     for (int i = 0; i <= KS; i++) {
-        const uint8_t* rowp = img + (ptrdiff_t)reflect101(r0 - R + i, H) * row_stride;
-        float b[NB], bb[NB];   // bytes around c0 and around c1
+        const T* rowp = srow(img, reflect101(r0 - R + i, H), row_stride);
+        float b[NB], bb[NB];   // pixels around c0 and around c1
         if (fast) {
+            if constexpr (kU8<T>) {
 #pragma unroll
-            for (int d = 0; d < ND; d++) {
-                unsigned v;
-                __builtin_memcpy(&v, rowp + (c0 - R) + 4 * d, 4);   // unaligned dword load
+                for (int d = 0; d < ND; d++) {
+                    unsigned v;
+                    __builtin_memcpy(&v, rowp + (c0 - R) + 4 * d, 4);   // unaligned dword load
 #pragma unroll
-                for (int e = 0; e < 4; e++)
-                    if (4 * d + e < NB) b[4 * d + e] = (float)((v >> (8 * e)) & 0xffu);
+                    for (int e = 0; e < 4; e++)
+                        if (4 * d + e < NB) b[4 * d + e] = (float)((v >> (8 * e)) & 0xffu);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NB; j++) b[j] = rowp[c0 - R + j];
             }
             H0[i] = row_filter<KS>(tk, KS, R, [&](int c) { return b[c]; });
             H1[i] = row_filter<KS>(tk, KS, R + 1, [&](int c) { return b[c]; });
         } else {
 #pragma unroll
             for (int j = 0; j < KS; j++) {
-                b[j] = (float)rowp[reflect101(c0 - R + j, W)];
-                bb[j] = (float)rowp[reflect101(c1 - R + j, W)];
+                b[j] = px(rowp + reflect101(c0 - R + j, W));
+                bb[j] = px(rowp + reflect101(c1 - R + j, W));
             }
             H0[i] = row_filter<KS>(tk, KS, R, [&](int c) { return b[c]; });
             H1[i] = row_filter<KS>(tk, KS, R, [&](int c) { return bb[c]; });
@@ -627,8 +691,8 @@ __device__ __forceinline__ void prep_static_slots(F& f)
     }
 }
 
-template <int KS, bool WFAST>
-__device__ __forceinline__ void prep_walk_body(const uint8_t* __restrict__ img, ptrdiff_t row_stride, int W, int H, int wk, int hk,
+template <int KS, bool WFAST, typename T = uint8_t>
+__device__ __forceinline__ void prep_walk_body(const T* __restrict__ img, ptrdiff_t row_stride, int W, int H, int wk, int hk,
                                                double scale_y, int dy0, int dy_end, int dx, bool live, int c0, int c1, bool fast,
                                                float a1, const nsof_blur_taps& t, float* __restrict__ dst)
 {
@@ -638,7 +702,7 @@ __device__ __forceinline__ void prep_walk_body(const uint8_t* __restrict__ img, 
     const unsigned coff = (unsigned)(c0 - R);    // byte offset of this lane's window in a source row (fast lanes)
     // the KS + 1 bytes of source row rr (wave-uniform, any integer: reflected) around this lane's two columns, as raw dwords
     auto load_row = [&](int rr, unsigned (&raw)[ND]) {
-        const uint8_t* rowp = img + (ptrdiff_t)reflect101(rr, H) * row_stride;   // scalar
+        const T* rowp = srow(img, reflect101(rr, H), row_stride);   // scalar
 #pragma unroll
         for (int d = 0; d < ND; d++) __builtin_memcpy(&raw[d], rowp + coff + 4 * d, 4);   // unaligned dword loads
     };
@@ -655,18 +719,26 @@ __device__ __forceinline__ void prep_walk_body(const uint8_t* __restrict__ img, 
     };
     // border waves: per lane, per byte with BORDER_REFLECT_101 where the window leaves the image
     auto hrow_edge = [&](int rr, float& h0, float& h1) {
-        const uint8_t* rowp = img + (ptrdiff_t)reflect101(rr, H) * row_stride;
+        const T* rowp = srow(img, reflect101(rr, H), row_stride);
         if (fast) {
-            unsigned raw[ND];
+            if constexpr (kU8<T>) {
+                unsigned raw[ND];
 #pragma unroll
-            for (int d = 0; d < ND; d++) __builtin_memcpy(&raw[d], rowp + coff + 4 * d, 4);
-            filt_row(raw, h0, h1);
+                for (int d = 0; d < ND; d++) __builtin_memcpy(&raw[d], rowp + coff + 4 * d, 4);
+                filt_row(raw, h0, h1);
+            } else {   // f32: the NB values around c0 straight from the row
+                float b[NB];
+#pragma unroll
+                for (int j = 0; j < NB; j++) b[j] = rowp[coff + j];
+                h0 = row_filter<KS>(tk, KS, R, [&](int c) { return b[c]; });
+                h1 = row_filter<KS>(tk, KS, R + 1, [&](int c) { return b[c]; });
+            }
         } else {
             float b[NB], bb[NB];
 #pragma unroll
             for (int j = 0; j < KS; j++) {
-                b[j] = (float)rowp[reflect101(c0 - R + j, W)];
-                bb[j] = (float)rowp[reflect101(c1 - R + j, W)];
+                b[j] = px(rowp + reflect101(c0 - R + j, W));
+                bb[j] = px(rowp + reflect101(c1 - R + j, W));
             }
             h0 = row_filter<KS>(tk, KS, R, [&](int c) { return b[c]; });
             h1 = row_filter<KS>(tk, KS, R, [&](int c) { return bb[c]; });
@@ -742,8 +814,10 @@ __device__ __forceinline__ void prep_walk_body(const uint8_t* __restrict__ img, 
     }
 }
 
-template <int KS>
-__global__ __launch_bounds__(256) void k_prep_walk(const uint8_t* __restrict__ src, ptrdiff_t row_stride,
+// T = float: every wave takes the per-lane form (prep_walk_body<KS, false>): a block of KS + 1 raw f32 rows in flight
+// would be (KS + 1)^2 registers per lane.
+template <int KS, typename T = uint8_t>
+__global__ __launch_bounds__(256) void k_prep_walk(const T* __restrict__ src, ptrdiff_t row_stride,
                                                     ptrdiff_t img_stride, int W, int H, int wk, int hk, double scale_x,
                                                     double scale_y, int seg_rows, nsof_blur_taps t, float* __restrict__ out)
 {
@@ -755,17 +829,17 @@ __global__ __launch_bounds__(256) void k_prep_walk(const uint8_t* __restrict__ s
     const int dxr = blockIdx.x * 64 + lane;
     const bool live = dxr < wk;
     const int dx = live ? dxr : wk - 1;
-    const uint8_t* img = src + (ptrdiff_t)blockIdx.z * img_stride;
+    const T* img = srow(src, blockIdx.z, img_stride);
     float* dst = out + (size_t)blockIdx.z * wk * hk;
     int sx;
     float a1;
     lin_coord_x(dx, scale_x, W, sx, a1);
     const int c0 = sx, c1 = min(sx + 1, W - 1);
     const bool fast = c0 - R >= 0 && c0 - R + 4 * ND <= W && c1 == c0 + 1;
-    if (__all(fast))
-        prep_walk_body<KS, true>(img, row_stride, W, H, wk, hk, scale_y, dy0, dy_end, dx, live, c0, c1, true, a1, t, dst);
+    if (kU8<T> && __all(fast))
+        prep_walk_body<KS, kU8<T>, T>(img, row_stride, W, H, wk, hk, scale_y, dy0, dy_end, dx, live, c0, c1, true, a1, t, dst);
     else
-        prep_walk_body<KS, false>(img, row_stride, W, H, wk, hk, scale_y, dy0, dy_end, dx, live, c0, c1, fast, a1, t, dst);
+        prep_walk_body<KS, false, T>(img, row_stride, W, H, wk, hk, scale_y, dy0, dy_end, dx, live, c0, c1, fast, a1, t, dst);
 }
 
 // Resampled level, two passes (kernel sizes 9 and 19: levels 2 and 3 of the reference's parameter sets).
@@ -777,8 +851,8 @@ __global__ __launch_bounds__(256) void k_prep_walk(const uint8_t* __restrict__ s
 // Both are plain thread-per-output kernels (no LDS, no barriers, full occupancy); HA is 2-4 MB per frame and
 // is re-read from L2/MALL.  Same operation order as the tiled/direct kernels (bit-identical results).
 constexpr int PREPA_ROWS = 8;
-template <int KS>
-__global__ __launch_bounds__(256) void k_prep_rows(const uint8_t* __restrict__ src, ptrdiff_t row_stride,
+template <int KS, typename T = uint8_t>
+__global__ __launch_bounds__(256) void k_prep_rows(const T* __restrict__ src, ptrdiff_t row_stride,
                                                     ptrdiff_t img_stride, int W, int H, int wk, double scale_x,
                                                     nsof_blur_taps t, float* __restrict__ HA)
 {
@@ -792,26 +866,31 @@ __global__ __launch_bounds__(256) void k_prep_rows(const uint8_t* __restrict__ s
     const int c = (j & 1) ? min(sx + 1, W - 1) : sx;
     const bool fast = c - R >= 0 && c - R + 4 * ND <= W;
     auto tk = [&](int q) { return t.k[q]; };
-    const uint8_t* img = src + (ptrdiff_t)blockIdx.z * img_stride;
+    const T* img = srow(src, blockIdx.z, img_stride);
     float* dst = HA + ((size_t)blockIdx.z * H) * (2 * wk) + j;
 #pragma unroll 2
     for (int q = 0; q < PREPA_ROWS; q++) {
         const int r = rbase + q;
         if (r >= H) break;
-        const uint8_t* rowp = img + (ptrdiff_t)r * row_stride;
+        const T* rowp = srow(img, r, row_stride);
         float b[KS];
         if (fast) {
+            if constexpr (kU8<T>) {
 #pragma unroll
-            for (int d = 0; d < ND; d++) {
-                unsigned v;
-                __builtin_memcpy(&v, rowp + (c - R) + 4 * d, 4);   // unaligned dword load
+                for (int d = 0; d < ND; d++) {
+                    unsigned v;
+                    __builtin_memcpy(&v, rowp + (c - R) + 4 * d, 4);   // unaligned dword load
 #pragma unroll
-                for (int e = 0; e < 4; e++)
-                    if (4 * d + e < KS) b[4 * d + e] = (float)((v >> (8 * e)) & 0xffu);
+                    for (int e = 0; e < 4; e++)
+                        if (4 * d + e < KS) b[4 * d + e] = (float)((v >> (8 * e)) & 0xffu);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < KS; i++) b[i] = rowp[c - R + i];
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < KS; i++) b[i] = (float)rowp[reflect101(c - R + i, W)];
+            for (int i = 0; i < KS; i++) b[i] = px(rowp + reflect101(c - R + i, W));
         }
         dst[(size_t)r * (2 * wk)] = row_filter<KS>(tk, KS, R, [&](int i) { return b[i]; });
     }
@@ -1869,8 +1948,9 @@ void launch_polyexp_het_n(nsof_ctx* ctx, int n_img, const nsof_het_item* items, 
 // Levels 1..3 of a pyr_scale 0.5 pyramid in one launch (k_prep_decim3).  Returns NSOF_EUNSUPPORTED without launching
 // when the frames do not decimate exactly by 8 (or are not aligned for the vector walks): the caller then runs the
 // levels one by one.  out[k - 1]: level k's images, [n_img][H >> k][W >> k].
-int NSOF_PYR_NAME(nsof_launch_prep_decim3)(nsof_ctx* ctx, int n_img, const uint8_t* src, ptrdiff_t row_stride, ptrdiff_t img_stride,
-                                           int W, int H, const nsof_blur_taps* taps, float* const* out)
+namespace {
+int prep_decim3_impl(nsof_ctx* ctx, int n_img, const uint8_t* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H,
+                     const nsof_blur_taps* taps, float* const* out)
 {
     const int CWL = (W & 15) == 0 ? 16 : 8;
     const bool ok = (W & 7) == 0 && (H & 7) == 0 && W >= 64 && H > 19 && (row_stride % CWL) == 0 && (img_stride % CWL) == 0 &&
@@ -1899,20 +1979,23 @@ int NSOF_PYR_NAME(nsof_launch_prep_decim3)(nsof_ctx* ctx, int n_img, const uint8
     return NSOF_OK;
 }
 
-int NSOF_PYR_NAME(nsof_launch_prep)(nsof_ctx* ctx, int n_img, const uint8_t* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
-                     int H, int wk, int hk, const nsof_blur_taps& taps, float* out)
+template <typename T>
+int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H, int wk, int hk,
+              const nsof_blur_taps& taps, float* out)
 {
     nsof_prof_scope ps(ctx, NSOF_K_PREP);
+    // the 4-pixel lanes' vector row loads: a dword (u8) / 16 bytes (f32) at every 4th column
+    const int VA = kU8<T> ? 4 : 16;
+    const bool rows_va = (row_stride % VA) == 0 && (img_stride % VA) == 0 && (reinterpret_cast<uintptr_t>(src) % VA) == 0;
     if (wk == W && hk == H) {
-        const bool aligned = (W & 3) == 0 && (row_stride & 3) == 0 && (img_stride & 3) == 0 &&
-                             (reinterpret_cast<uintptr_t>(src) & 3) == 0 && W >= 8;
+        const bool aligned = (W & 3) == 0 && rows_va && W >= 8;
         if (taps.ksize == 3 && aligned) {
             dim3 grid((W / 4 + 63) / 64, (H + 4 * PREP0_ROWS - 1) / (4 * PREP0_ROWS), n_img);
-            hipLaunchKernelGGL(k_prep_same3_vec<false>, grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W,
+            hipLaunchKernelGGL((k_prep_same3_vec<false, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W,
                                H, taps.k[1], taps.k[2], out, nullptr);
         } else {
             dim3 grid((W + 63) / 64, (H + 3) / 4, n_img);
-            hipLaunchKernelGGL(k_prep_same<false>, grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
+            hipLaunchKernelGGL((k_prep_same<false, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
                                taps, out, nullptr, -1);
         }
     } else {
@@ -1921,16 +2004,18 @@ int NSOF_PYR_NAME(nsof_launch_prep)(nsof_ctx* ctx, int n_img, const uint8_t* src
         const int rw_cap = ((int)ceil(PREP_TW * scale_x) + 2 * r + 8 + 3) / 4 * 4;
         const int rh_cap = (int)ceil(PREP_TH * scale_y) + 2 * r + 4;
         const size_t smem = sizeof(float) * ((size_t)rh_cap * 2 * PREP_TW + 2 * PREP_TH * 2 * PREP_TW) +
-                            (size_t)rh_cap * rw_cap;
+                            (size_t)rh_cap * rw_cap * sizeof(T);
         const bool direct_ok = scale_x >= 1.0 && scale_y >= 1.0 &&
                                (taps.ksize == 3 || taps.ksize == 5);   // larger kernels: registers run out
         // exact decimation by 2 / 4 / 8 with the kernel sizes the pyr_scale 0.5 pyramid produces
         const int S = W / wk;
         static const bool force8 = NSOF_AB_GETENV("NSOF_DECIM_CW8") != nullptr;   // A/B: 8-column lanes everywhere
         const int CWL = ((W & 15) == 0 && !force8) ? 16 : 8;   // source columns per lane
-        const bool decim_ok = S >= 2 && W == S * wk && H == S * hk && (W % CWL) == 0 && W >= 64 &&
-                              (row_stride % CWL) == 0 && (img_stride % CWL) == 0 &&
-                              (reinterpret_cast<uintptr_t>(src) % CWL) == 0 &&
+        // f32: 16-byte aligned rows (float4 loads); 8-column lanes only while the blur halo fits in one (S = 2, 4)
+        const bool decim_al = kU8<T> ? (row_stride % CWL) == 0 && (img_stride % CWL) == 0 &&
+                                           (reinterpret_cast<uintptr_t>(src) % CWL) == 0
+                                     : rows_va && (CWL == 16 || S <= 4);
+        const bool decim_ok = S >= 2 && W == S * wk && H == S * hk && (W % CWL) == 0 && W >= 64 && decim_al &&
                               ((S == 2 && taps.ksize == 3) || (S == 4 && taps.ksize == 9) ||
                                (S == 8 && taps.ksize == 19)) &&
                               H > taps.ksize && NSOF_AB_GETENV("NSOF_PREP_NODECIM") == nullptr;
@@ -1953,7 +2038,7 @@ int NSOF_PYR_NAME(nsof_launch_prep)(nsof_ctx* ctx, int n_img, const uint8_t* src
             const int nseg = (hk + seg_rows - 1) / seg_rows;
             dim3 grid((W / CWL + 63) / 64, (nseg + 3) / 4, n_img);
 #define NSOF_DECIM(SS, KK, CC)                                                                                      \
-    hipLaunchKernelGGL((k_prep_decim<SS, KK, CC>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, \
+    hipLaunchKernelGGL((k_prep_decim<SS, KK, CC, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, \
                        H, wk, hk, seg_rows, taps, out)
             if (CWL == 16) {
                 if (S == 2) NSOF_DECIM(2, 3, 16);
@@ -1962,7 +2047,7 @@ int NSOF_PYR_NAME(nsof_launch_prep)(nsof_ctx* ctx, int n_img, const uint8_t* src
             } else {
                 if (S == 2) NSOF_DECIM(2, 3, 8);
                 else if (S == 4) NSOF_DECIM(4, 9, 8);
-                else NSOF_DECIM(8, 19, 8);
+                else if constexpr (kU8<T>) NSOF_DECIM(8, 19, 8);
             }
 #undef NSOF_DECIM
         } else if (scale_x >= 1.0 && scale_y >= 1.0 && scale_y < taps.ksize &&
@@ -1980,7 +2065,7 @@ int NSOF_PYR_NAME(nsof_launch_prep)(nsof_ctx* ctx, int n_img, const uint8_t* src
             const int nseg = (hk + seg_rows - 1) / seg_rows;
             dim3 grid((unsigned)waves_x, (nseg + 3) / 4, n_img);
 #define NSOF_PREP_WALK(KS)                                                                                          \
-    hipLaunchKernelGGL((k_prep_walk<KS>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H, wk, hk, \
+    hipLaunchKernelGGL((k_prep_walk<KS, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H, wk, hk, \
                        scale_x, scale_y, seg_rows, taps, out)
             if (taps.ksize == 3) NSOF_PREP_WALK(3);
             else if (taps.ksize == 5) NSOF_PREP_WALK(5);
@@ -1989,7 +2074,7 @@ int NSOF_PYR_NAME(nsof_launch_prep)(nsof_ctx* ctx, int n_img, const uint8_t* src
         } else if (direct_ok) {
             dim3 grid((wk + 63) / 64, (hk + 3) / 4, n_img);
 #define NSOF_PREP_DIRECT(KS)                                                                                       \
-    hipLaunchKernelGGL((k_prep_direct<KS, false>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, \
+    hipLaunchKernelGGL((k_prep_direct<KS, false, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, \
                        H, wk, hk, scale_x, scale_y, taps, out, nullptr)
             if (taps.ksize == 3) NSOF_PREP_DIRECT(3);
             else NSOF_PREP_DIRECT(5);
@@ -2001,14 +2086,14 @@ int NSOF_PYR_NAME(nsof_launch_prep)(nsof_ctx* ctx, int n_img, const uint8_t* src
             float* HA = static_cast<float*>(ctx->tmp);
             dim3 ga((2 * wk + 63) / 64, (H + 4 * PREPA_ROWS - 1) / (4 * PREPA_ROWS), n_img);
             dim3 gb((wk + 63) / 64, (hk + 3) / 4, n_img);
-            hipLaunchKernelGGL(k_prep_rows<19>, ga, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H, wk,
+            hipLaunchKernelGGL((k_prep_rows<19, T>), ga, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H, wk,
                                scale_x, taps, HA);
             hipLaunchKernelGGL(k_prep_cols<19>, gb, dim3(256), 0, ctx->stream, HA, W, H, wk, hk, scale_x, scale_y, taps,
                                out);
         } else if (smem <= 60 * 1024 && scale_x >= 1.0 && scale_y >= 1.0) {
             dim3 grid((wk + PREP_TW - 1) / PREP_TW, (hk + PREP_TH - 1) / PREP_TH, n_img);
 #define NSOF_PREP_TILED(KS)                                                                                        \
-    hipLaunchKernelGGL((k_prep_tiled<KS, false>), grid, dim3(256), smem, ctx->stream, src, row_stride, img_stride, \
+    hipLaunchKernelGGL((k_prep_tiled<KS, false, T>), grid, dim3(256), smem, ctx->stream, src, row_stride, img_stride, \
                        W, H, wk, hk, scale_x, scale_y, rw_cap, rh_cap, taps, out, nullptr)
             switch (taps.ksize) {
                 case 9: NSOF_PREP_TILED(9); break;
@@ -2018,12 +2103,30 @@ int NSOF_PYR_NAME(nsof_launch_prep)(nsof_ctx* ctx, int n_img, const uint8_t* src
 #undef NSOF_PREP_TILED
         } else {
             dim3 grid((wk + 63) / 64, (hk + 3) / 4, n_img);
-            hipLaunchKernelGGL(k_prep_naive<false>, grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
+            hipLaunchKernelGGL((k_prep_naive<false, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
                                wk, hk, scale_x, scale_y, taps, out, nullptr);
         }
     }
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
+}
+}  // namespace
+
+int NSOF_PYR_NAME(nsof_launch_prep_decim3)(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride,
+                                           int W, int H, const nsof_blur_taps* taps, float* const* out, int src_type)
+{
+    // f32 frames take the three one-level launches (k_prep_decim<.., float>): at 768 threads per workgroup a wave has
+    // 168 registers, and the float rows of the three walks side by side spilled (~400 registers' worth to scratch)
+    if (src_type == NSOF_SRC_F32) return NSOF_EUNSUPPORTED;
+    return prep_decim3_impl(ctx, n_img, static_cast<const uint8_t*>(src), row_stride, img_stride, W, H, taps, out);
+}
+
+int NSOF_PYR_NAME(nsof_launch_prep)(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
+                                    int H, int wk, int hk, const nsof_blur_taps& taps, float* out, int src_type)
+{
+    if (src_type == NSOF_SRC_F32)
+        return prep_impl(ctx, n_img, static_cast<const float*>(src), row_stride, img_stride, W, H, wk, hk, taps, out);
+    return prep_impl(ctx, n_img, static_cast<const uint8_t*>(src), row_stride, img_stride, W, H, wk, hk, taps, out);
 }
 
 #ifndef NSOF_PYR_FMA
@@ -2149,12 +2252,12 @@ int NSOF_PYR_NAME(nsof_launch_prep_het)(nsof_ctx* ctx, int n_items, const nsof_h
     if (level0) {   // same-size level: 3 taps; aligned items take the vector kernel, the others the generic one
         if (taps.ksize == 3 && n_vec > 0) {
             dim3 grid((max_wk / 4 + 63) / 64, (max_hk + 4 * PREP0_ROWS - 1) / (4 * PREP0_ROWS), nz);
-            hipLaunchKernelGGL(k_prep_same3_vec<true>, grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps.k[1],
+            hipLaunchKernelGGL((k_prep_same3_vec<true, uint8_t>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps.k[1],
                                taps.k[2], I, d_items);
         }
         if (taps.ksize != 3 || n_vec < n_items) {
             dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
-            hipLaunchKernelGGL(k_prep_same<true>, grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps, I, d_items,
+            hipLaunchKernelGGL((k_prep_same<true, uint8_t>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps, I, d_items,
                                taps.ksize == 3 ? 0 : -1);
         }
     } else {
@@ -2166,15 +2269,15 @@ int NSOF_PYR_NAME(nsof_launch_prep_het)(nsof_ctx* ctx, int n_items, const nsof_h
         if (taps.ksize == 3 || taps.ksize == 5) {
             dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
             if (taps.ksize == 3)
-                hipLaunchKernelGGL((k_prep_direct<3, true>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1.,
+                hipLaunchKernelGGL((k_prep_direct<3, true, uint8_t>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1.,
                                    1., taps, I, d_items);
             else
-                hipLaunchKernelGGL((k_prep_direct<5, true>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1.,
+                hipLaunchKernelGGL((k_prep_direct<5, true, uint8_t>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1.,
                                    1., taps, I, d_items);
         } else if (smem <= 60 * 1024) {
             dim3 grid((max_wk + PREP_TW - 1) / PREP_TW, (max_hk + PREP_TH - 1) / PREP_TH, nz);
 #define NSOF_PREP_TILED_HET(KS)                                                                                       \
-    hipLaunchKernelGGL((k_prep_tiled<KS, true>), grid, dim3(256), smem, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1., \
+    hipLaunchKernelGGL((k_prep_tiled<KS, true, uint8_t>), grid, dim3(256), smem, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1., \
                        rw_cap, rh_cap, taps, I, d_items)
             switch (taps.ksize) {
                 case 9: NSOF_PREP_TILED_HET(9); break;
@@ -2184,7 +2287,7 @@ int NSOF_PYR_NAME(nsof_launch_prep_het)(nsof_ctx* ctx, int n_items, const nsof_h
 #undef NSOF_PREP_TILED_HET
         } else {
             dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
-            hipLaunchKernelGGL(k_prep_naive<true>, grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1.,
+            hipLaunchKernelGGL((k_prep_naive<true, uint8_t>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1.,
                                taps, I, d_items);
         }
     }

@@ -514,6 +514,26 @@ extern "C" int nsof_stage_pyr_level(nsof_ctx* ctx, int n_img, const uint8_t* d_s
     return NSOF_PYR_SEL(ctx, nsof_launch_prep, n_img, d_src, row_stride, img_stride, width, height, wk, hk, taps, d_out);
 }
 
+extern "C" int nsof_stage_pyr_level_f32(nsof_ctx* ctx, int n_img, const float* d_src, ptrdiff_t row_stride,
+                                        ptrdiff_t img_stride, int width, int height, double pyr_scale, int level,
+                                        float* d_out)
+{
+    if (!ctx || !d_src || !d_out || n_img < 1) return NSOF_EINVAL;
+    if (width < 1 || row_stride < (ptrdiff_t)width * 4 || (row_stride & 3) || (img_stride & 3) ||
+        (reinterpret_cast<uintptr_t>(d_src) & 3))
+        return nsof_set_error(ctx, NSOF_EINVAL, "f32 frames: strides must be multiples of 4 bytes, row_stride >= 4*width, "
+                                                "pointer 4-byte aligned");
+    int wk, hk, ks;
+    double sg;
+    int rc = nsof_farneback_level_size(width, height, pyr_scale, level, &wk, &hk, &ks, &sg);
+    if (rc) return nsof_set_error(ctx, rc, "bad level geometry");
+    nsof_blur_taps taps;
+    if ((rc = nsof_host_blur_taps(ks, sg, &taps)))
+        return nsof_set_error(ctx, rc, "pyramid blur kernel size %d unsupported (max %d)", ks, NSOF_MAX_BLUR_TAPS - 1);
+    return NSOF_PYR_SEL(ctx, nsof_launch_prep, n_img, d_src, row_stride, img_stride, width, height, wk, hk, taps, d_out,
+                        NSOF_SRC_F32);
+}
+
 __global__ void k_recip_probe(long long n, const double* __restrict__ x, double* __restrict__ fast, double* __restrict__ ieee)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -599,17 +619,21 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 // Core of both device entry points.  sequence == false: n_pairs independent pairs (d_prev[i], d_next[i]);
 // sequence == true: n_pairs + 1 consecutive frames in d_prev (d_next unused), pair i = (frame i, frame i+1) -- every
 // frame's pyramid level and polynomial expansion is then computed once and shared by the two pairs it belongs to.
-int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const uint8_t* d_prev, const uint8_t* d_next,
+// src (nsof_src_type): 8-bit or float frames.  Only the pyramid stage reads the frames; the frame pointers below are
+// byte addresses and both strides are in bytes whatever the pixel type.
+int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* prev_frames, const void* next_frames,
                           ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height, float* d_flow,
                           double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma,
-                          int flags)
+                          int flags, int src)
 {
     if (!ctx) return NSOF_EINVAL;
-    if (sequence) d_next = d_prev;
+    const uint8_t* d_prev = static_cast<const uint8_t*>(prev_frames);
+    const uint8_t* d_next = sequence ? d_prev : static_cast<const uint8_t*>(next_frames);
     if (!d_prev || !d_next || !d_flow || n_pairs < 1) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer or n_pairs<1");
     int rc = nsof_check_farneback_params(ctx, width, height, pyr_scale, levels, winsize, iterations, poly_n, flags);
     if (rc) return rc;
-    if (row_stride < width) return nsof_set_error(ctx, NSOF_EINVAL, "row_stride < width");
+    const int px_bytes = src == NSOF_SRC_F32 ? 4 : 1;
+    if (row_stride < (ptrdiff_t)width * px_bytes) return nsof_set_error(ctx, NSOF_EINVAL, "row_stride < width * %d", px_bytes);
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const bool exact = ctx->opt_exact_rowsums != 0;
     // exact row-sum order: ONE fused kernel (k_iterate_x) where the window fits; NSOF_EXACT_IMPL=2k selects the older
@@ -635,7 +659,7 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const uint8_t
             const int nb = n_pairs - i < exact_chunk ? n_pairs - i : exact_chunk;
             rc = nsof_farneback_core(ctx, false, nb, d_prev + (ptrdiff_t)i * pair_stride, nx + (ptrdiff_t)i * pair_stride,
                                      row_stride, pair_stride, width, height, d_flow + (size_t)i * width * height * 2,
-                                     pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
+                                     pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, src);
             if (rc) return rc;
         }
         return NSOF_OK;
@@ -667,7 +691,7 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const uint8_t
                 rc = nsof_farneback_core(ctx, sequence, nb, d_prev + (ptrdiff_t)i * pair_stride,
                                          d_next + (ptrdiff_t)i * pair_stride, row_stride, pair_stride, width, height,
                                          d_flow + (size_t)i * width * height * 2, pyr_scale, levels, winsize, iterations,
-                                         poly_n, poly_sigma, flags);
+                                         poly_n, poly_sigma, flags, src);
                 if (rc) return rc;
             }
             return NSOF_OK;
@@ -755,10 +779,10 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const uint8_t
             if (int r = nsof_host_blur_taps(ks, sg, &bt))
                 return nsof_set_error(ctx, r, "pyramid blur kernel size %d unsupported (max %d)", ks, NSOF_MAX_BLUR_TAPS - 1);
             const size_t nk = (size_t)wk * hk;
-            if (sequence) return NSOF_PYR_SEL(ctx, nsof_launch_prep, (int)n_img, d_prev, row_stride, pair_stride, width, height, wk, hk, bt, I);
+            if (sequence) return NSOF_PYR_SEL(ctx, nsof_launch_prep, (int)n_img, d_prev, row_stride, pair_stride, width, height, wk, hk, bt, I, src);
             for (int i = 0; i < 2; i++)
                 if (int r = NSOF_PYR_SEL(ctx, nsof_launch_prep, n_pairs, i == 0 ? d_prev : d_next, row_stride, pair_stride, width, height, wk,
-                                             hk, bt, I + (size_t)i * B * nk))
+                                             hk, bt, I + (size_t)i * B * nk, src))
                     return r;
             return NSOF_OK;
         };
@@ -809,19 +833,21 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const uint8_t
     auto prep_level = [&](int wk, int hk, const nsof_blur_taps& bt, float* I) -> int {
         const size_t nk = (size_t)wk * hk;
         if (sequence || prep_merged)
-            return NSOF_PYR_SEL(ctx, nsof_launch_prep, (int)n_img, d_prev, row_stride, pair_stride, width, height, wk, hk, bt, I);
+            return NSOF_PYR_SEL(ctx, nsof_launch_prep, (int)n_img, d_prev, row_stride, pair_stride, width, height, wk, hk, bt, I, src);
         for (int i = 0; i < 2; i++)
             if (int r = NSOF_PYR_SEL(ctx, nsof_launch_prep, n_pairs, i == 0 ? d_prev : d_next, row_stride, pair_stride, width, height,
-                                     wk, hk, bt, I + (size_t)i * B * nk))
+                                     wk, hk, bt, I + (size_t)i * B * nk, src))
                 return r;
         return NSOF_OK;
     };
 
     // Level 0 (the frame's own size, 3-tap smoothing): the expansion kernel forms the level image itself from the 8-bit
     // frames (k_polyexp_rs<.., U8>): no pyramid launch, no image written and read back.  Not with the FMA twin of the
-    // pyramid stages nor with the float expansion (their kernels have no such form).
+    // pyramid stages nor with the float expansion (their kernels have no such form), nor for f32 frames: those take the
+    // two-kernel form (k_prep_same3_vec<.., float>, then the expansion of the level image).
     static const bool poly_u8_off = [] { const char* e = NSOF_AB_GETENV("NSOF_POLY_U8"); return e && e[0] == '0'; }();
-    const bool poly_u8 = !poly_u8_off && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && width >= 2 && height >= 2;
+    const bool poly_u8 = !poly_u8_off && src == NSOF_SRC_U8 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && width >= 2 &&
+                         height >= 2;
     float* Ifused[4] = {nullptr, nullptr, nullptr, nullptr};   // level images already made by the three-level launch
     auto level_expansion = [&](int k, int wk, int hk, const nsof_blur_taps& bt, float* I, float* Rk) -> int {
         if (k >= 1 && k <= 3 && Ifused[k]) return nsof_launch_polyexp(ctx, (int)n_img, Ifused[k], wk, hk, ptaps, Rk);
@@ -933,10 +959,10 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const uint8_t
         if (exact3) {
             float* I3[3] = {dI, dI + n_img * nk3[0], dI + n_img * (nk3[0] + nk3[1])};
             const bool one = sequence || prep_merged;
-            rc = NSOF_PYR_SEL(ctx, nsof_launch_prep_decim3, one ? (int)n_img : n_pairs, d_prev, row_stride, pair_stride, width, height, bt3, I3);
+            rc = NSOF_PYR_SEL(ctx, nsof_launch_prep_decim3, one ? (int)n_img : n_pairs, d_prev, row_stride, pair_stride, width, height, bt3, I3, src);
             if (rc == NSOF_OK && !one) {
                 float* I3n[3] = {I3[0] + B * nk3[0], I3[1] + B * nk3[1], I3[2] + B * nk3[2]};
-                rc = NSOF_PYR_SEL(ctx, nsof_launch_prep_decim3, n_pairs, d_next, row_stride, pair_stride, width, height, bt3, I3n);
+                rc = NSOF_PYR_SEL(ctx, nsof_launch_prep_decim3, n_pairs, d_next, row_stride, pair_stride, width, height, bt3, I3n, src);
             }
             if (rc == NSOF_OK) {
                 for (int k = 1; k <= 3; k++) Ifused[k] = I3[k - 1];
@@ -1027,6 +1053,94 @@ extern "C" int nsof_farneback_u8_sequence_dev(nsof_ctx* ctx, int n_frames, const
     if (n_frames < 2) return nsof_set_error(ctx, NSOF_EINVAL, "a sequence needs at least 2 frames");
     return nsof_farneback_core(ctx, true, n_frames - 1, d_frames, nullptr, row_stride, frame_stride, width, height, d_flow,
                           pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
+}
+
+// ---- float frames: the same driver with the f32 pyramid stage --------------------------------------------------
+// A float frame is addressed with byte strides like an 8-bit one: rows (and pairs / frames) must keep every pixel
+// 4-byte aligned.  The kernels take their vector forms only where rows are 16-byte aligned and fall back to scalar
+// loads elsewhere, so cropped views that start at any element are fine.
+static int check_f32_layout(nsof_ctx* ctx, const void* p, ptrdiff_t row_stride, ptrdiff_t img_stride, int width)
+{
+    if ((reinterpret_cast<uintptr_t>(p) & 3) != 0) return nsof_set_error(ctx, NSOF_EINVAL, "f32 frames must be 4-byte aligned");
+    if ((row_stride & 3) != 0 || row_stride < (ptrdiff_t)width * 4)
+        return nsof_set_error(ctx, NSOF_EINVAL, "f32 row_stride=%td must be a multiple of 4 and >= 4*width", row_stride);
+    if ((img_stride & 3) != 0) return nsof_set_error(ctx, NSOF_EINVAL, "f32 pair/frame stride=%td must be a multiple of 4", img_stride);
+    return NSOF_OK;
+}
+
+extern "C" int nsof_farneback_f32_batch_dev(nsof_ctx* ctx, int n_pairs, const float* d_prev, const float* d_next,
+                                            ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height,
+                                            float* d_flow, double pyr_scale, int levels, int winsize, int iterations,
+                                            int poly_n, double poly_sigma, int flags)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!d_prev || !d_next || !d_flow) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer");
+    int rc = check_f32_layout(ctx, d_prev, row_stride, pair_stride, width);
+    if (rc == NSOF_OK) rc = check_f32_layout(ctx, d_next, row_stride, pair_stride, width);
+    if (rc) return rc;
+    return nsof_farneback_core(ctx, false, n_pairs, d_prev, d_next, row_stride, pair_stride, width, height, d_flow, pyr_scale,
+                               levels, winsize, iterations, poly_n, poly_sigma, flags, NSOF_SRC_F32);
+}
+
+extern "C" int nsof_farneback_f32_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_frames,
+                                               ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
+                                               float* d_flow, double pyr_scale, int levels, int winsize,
+                                               int iterations, int poly_n, double poly_sigma, int flags)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (n_frames < 2) return nsof_set_error(ctx, NSOF_EINVAL, "a sequence needs at least 2 frames");
+    if (!d_frames || !d_flow) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer");
+    if (int rc = check_f32_layout(ctx, d_frames, row_stride, frame_stride, width)) return rc;
+    return nsof_farneback_core(ctx, true, n_frames - 1, d_frames, nullptr, row_stride, frame_stride, width, height, d_flow,
+                               pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, NSOF_SRC_F32);
+}
+
+extern "C" int nsof_farneback_f32(nsof_ctx* ctx, const float* prev, ptrdiff_t prev_stride, const float* next,
+                                  ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
+                                  double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                                  double poly_sigma, int flags)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!prev || !next || !flow) return nsof_set_error(ctx, NSOF_EINVAL, "null image pointer");
+    int rc = nsof_check_farneback_params(ctx, width, height, pyr_scale, levels, winsize, iterations, poly_n, flags);
+    if (rc) return rc;
+    if ((rc = check_f32_layout(ctx, prev, prev_stride, 0, width)) || (rc = check_f32_layout(ctx, next, next_stride, 0, width)))
+        return rc;
+    if (flow_stride < (ptrdiff_t)(width * 8)) return nsof_set_error(ctx, NSOF_EINVAL, "flow_stride < width*8");
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    // as nsof_farneback_u8: dense frames go straight from the caller's memory, strided ones are packed into pinned
+    // staging first; on the device the pair lies back to back (one pyramid launch per level for both frames)
+    const size_t n0 = (size_t)width * height, pitch = (size_t)width * 4;
+    const size_t szU = align_up(n0 * 4, 256), szF = align_up(n0 * 8, 256);
+    if ((rc = nsof_ws_reserve(ctx, &ctx->stage, &ctx->stage_bytes, 2 * szU + szF))) return rc;
+    if ((rc = nsof_hstage_reserve(ctx, 2 * szU + szF))) return rc;
+    char* hP = (char*)ctx->hstage;
+    char* hN = hP + szU;
+    float* hF = (float*)(hN + szU);
+    char* dP = (char*)ctx->stage;
+    char* dN = dP + szU;
+    float* dFl = (float*)(dN + szU);
+    const bool in_dense = prev_stride == (ptrdiff_t)pitch && next_stride == (ptrdiff_t)pitch;
+    const bool out_dense = flow_stride == (ptrdiff_t)width * 8;
+    if (in_dense) {
+        NSOF_HIP(ctx, hipMemcpyAsync(dP, prev, n0 * 4, hipMemcpyHostToDevice, ctx->stream));
+        NSOF_HIP(ctx, hipMemcpyAsync(dN, next, n0 * 4, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        for (int y = 0; y < height; y++) {
+            memcpy(hP + (size_t)y * pitch, (const char*)prev + (ptrdiff_t)y * prev_stride, pitch);
+            memcpy(hN + (size_t)y * pitch, (const char*)next + (ptrdiff_t)y * next_stride, pitch);
+        }
+        NSOF_HIP(ctx, hipMemcpyAsync(dP, hP, 2 * szU, hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = nsof_farneback_core(ctx, false, 1, dP, dN, (ptrdiff_t)pitch, (ptrdiff_t)szU, width, height, dFl, pyr_scale, levels,
+                             winsize, iterations, poly_n, poly_sigma, flags, NSOF_SRC_F32);
+    if (rc) return rc;
+    NSOF_HIP(ctx, hipMemcpyAsync(out_dense ? flow : hF, dFl, n0 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = nsof_stream_sync_checked(ctx))) return rc;
+    if (!out_dense)
+        for (int y = 0; y < height; y++)
+            memcpy((char*)flow + (ptrdiff_t)y * flow_stride, hF + (size_t)y * width * 2, (size_t)width * 8);
+    return NSOF_OK;
 }
 
 extern "C" int nsof_farneback_u8(nsof_ctx* ctx, const uint8_t* prev, ptrdiff_t prev_stride, const uint8_t* next,

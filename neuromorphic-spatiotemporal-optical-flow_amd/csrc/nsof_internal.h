@@ -111,13 +111,16 @@ struct nsof_prof_scope {
 };
 
 // ---- Farneback driver pieces shared between nsof_api.hip and farneback_batch.hip -------------------------------
+// Pixel type of the frames a uniform batch reads (the pyramid stage is the only one that reads them).  Frame pointers
+// stay byte addresses and every stride stays in bytes for both.
+enum nsof_src_type { NSOF_SRC_U8 = 0, NSOF_SRC_F32 = 1 };
 int nsof_check_farneback_params(nsof_ctx* ctx, int width, int height, double pyr_scale, int levels, int winsize,
                                 int iterations, int poly_n, int flags);
-// Uniform-shape device batch (sequence == true: n_pairs + 1 consecutive frames in d_prev).
-int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const uint8_t* d_prev, const uint8_t* d_next,
+// Uniform-shape device batch (sequence == true: n_pairs + 1 consecutive frames in d_prev); src: nsof_src_type.
+int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* d_prev, const void* d_next,
                         ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height, float* d_flow,
                         double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma,
-                        int flags);
+                        int flags, int src = NSOF_SRC_U8);
 void nsof_pipe_destroy(nsof_ctx* ctx);
 
 // ---- Farneback launchers (farneback_kernels.hip) ------------------------------------------
@@ -179,17 +182,18 @@ int nsof_launch_flow_upsample_het(nsof_ctx* ctx, int n_items, const nsof_het_ite
 // final: the flow goes to the items' own output fields (out / out_pitch) instead of flow_out.
 int nsof_launch_iterate_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, const float* R,
                             const float* flow_in, float* flow_out, bool final, int winsize);
-int nsof_launch_prep(nsof_ctx* ctx, int n_img, const uint8_t* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
-                     int H, int wk, int hk, const nsof_blur_taps& taps, float* out);
+// src: n_img frames of pixel type src_type (nsof_src_type), row / image strides in bytes.
+int nsof_launch_prep(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
+                     int H, int wk, int hk, const nsof_blur_taps& taps, float* out, int src_type = NSOF_SRC_U8);
 // The *_fma twins (farneback_kernels.hip compiled with -DNSOF_PYR_FMA): same taps and order, every tap / blend one fused
 // multiply-add -- selected by ctx->opt_pyr_fma through the *_sel wrappers below.
-int nsof_launch_prep_fma(nsof_ctx* ctx, int n_img, const uint8_t* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
-                         int H, int wk, int hk, const nsof_blur_taps& taps, float* out);
+int nsof_launch_prep_fma(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
+                         int H, int wk, int hk, const nsof_blur_taps& taps, float* out, int src_type = NSOF_SRC_U8);
 // Levels 1..3 of a pyr_scale 0.5 pyramid in one launch; NSOF_EUNSUPPORTED (nothing launched) when the frames do not qualify.
-int nsof_launch_prep_decim3(nsof_ctx* ctx, int n_img, const uint8_t* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
-                            int H, const nsof_blur_taps* taps, float* const* out);
-int nsof_launch_prep_decim3_fma(nsof_ctx* ctx, int n_img, const uint8_t* src, ptrdiff_t row_stride, ptrdiff_t img_stride,
-                                int W, int H, const nsof_blur_taps* taps, float* const* out);
+int nsof_launch_prep_decim3(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
+                            int H, const nsof_blur_taps* taps, float* const* out, int src_type = NSOF_SRC_U8);
+int nsof_launch_prep_decim3_fma(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride,
+                                int W, int H, const nsof_blur_taps* taps, float* const* out, int src_type = NSOF_SRC_U8);
 int nsof_launch_prep_het_fma(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items,
                              bool level0, const nsof_blur_taps& taps, float* I);
 int nsof_launch_flow_upsample_fma(nsof_ctx* ctx, int n_pairs, const float* src, int sw, int sh, float* dst, int dw,

@@ -44,6 +44,9 @@ SIGNATURES = {
     "nsof_farneback_u8": (_i, [_vp, _vp, _pd, _vp, _pd, _i, _i, _vp, _pd, _d, _i, _i, _i, _i, _d, _i]),
     "nsof_farneback_u8_batch_dev": (_i, [_vp, _i, _vp, _vp, _pd, _pd, _i, _i, _vp, _d, _i, _i, _i, _i, _d, _i]),
     "nsof_farneback_u8_sequence_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _d, _i, _i, _i, _i, _d, _i]),
+    "nsof_farneback_f32": (_i, [_vp, _vp, _pd, _vp, _pd, _i, _i, _vp, _pd, _d, _i, _i, _i, _i, _d, _i]),
+    "nsof_farneback_f32_batch_dev": (_i, [_vp, _i, _vp, _vp, _pd, _pd, _i, _i, _vp, _d, _i, _i, _i, _i, _d, _i]),
+    "nsof_farneback_f32_sequence_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _d, _i, _i, _i, _i, _d, _i]),
     "nsof_farneback_u8_batch": (_i, [_vp, _i, C.POINTER(PairDesc), _d, _i, _i, _i, _i, _d, _i]),
     "nsof_farneback_u8_batch_desc_dev": (_i, [_vp, _i, C.POINTER(PairDesc), _d, _i, _i, _i, _i, _d, _i]),
     "nsof_farneback_u8_roi_sequence_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _vp, _i, _vp, _d, _i, _i, _i, _i, _d, _i, _i,
@@ -53,6 +56,7 @@ SIGNATURES = {
     "nsof_farneback_effective_levels": (_i, [_i, _i, _d, _i]),
     "nsof_farneback_level_size": (_i, [_i, _i, _d, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_d)]),
     "nsof_stage_pyr_level": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _d, _i, _vp]),
+    "nsof_stage_pyr_level_f32": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _d, _i, _vp]),
     "nsof_stage_polyexp": (_i, [_vp, _i, _vp, _i, _i, _i, _d, _vp]),
     "nsof_stage_recip": (_i, [_vp, C.c_longlong, _vp, _vp, _vp]),
     "nsof_stage_update_matrices": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp]),
@@ -72,6 +76,7 @@ SIGNATURES = {
     "nsof_accum_set_slice_times": (_i, [_vp, _vp, _vp, _i64]),
     "nsof_accum_run": (_i, [_vp, _i64, _i64, _i64]),
     "nsof_accum_surface_u8_dev": (_i, [_vp, _i, _i, _vp, _pd]),
+    "nsof_accum_surface_f32_dev": (_i, [_vp, _i, _i, _vp, _pd]),
     "nsof_accum_run_surface": (_i, [_vp, _i64, _i64, _i, _i, _vp, _pd]),
     "nsof_accum_run_frames": (_i, [_vp, _i64, _i64, _i64, _i, _i, _vp, _pd, _pd]),
     "nsof_accum_set_frames_path": (_i, [_vp, _i]),

@@ -228,6 +228,17 @@ class Accumulator:
                                                                self.W if row_stride is None else int(row_stride)),
                        "accum_surface_u8")
 
+    def surface_f32(self, d_out, which=0, row_stride=None, mode="state"):
+        """The same surface as a float32 frame in DEVICE memory (torch float32 tensor / address; ``row_stride`` in BYTES,
+        default 4 * W): the value ``surface_u8`` truncates to 8 bits, clipped to [0, 255] and rounded to float instead
+        (``nsof_accum_surface_f32_dev``).  Always finite: the unquantised input of ``farneback_sequence``."""
+        if d_out is not None and getattr(d_out, "dtype", None) is not None and str(d_out.dtype) != "torch.float32":
+            raise NsofValueError(f"surface_f32 writes float32 (got {d_out.dtype})")
+        self.ctx.check(self.ctx._lib.nsof_accum_surface_f32_dev(self._p, which, {"current": 0, "state": 1}[mode],
+                                                                dev_ptr(d_out),
+                                                                4 * self.W if row_stride is None else int(row_stride)),
+                       "accum_surface_f32")
+
     def block_current(self, memsize, which=0, snapshot=-1, v_ds=1.0):
         """Block maximum of the device current ``v_ds / R`` over ``memsize x memsize`` pixel blocks, float64
         [H // memsize][W // memsize], reduced on the GPU (``nsof_accum_block_current``): the input of the gating image

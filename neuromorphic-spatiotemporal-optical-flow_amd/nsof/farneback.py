@@ -4,6 +4,10 @@ Reference call sites: /root/reference/optical_flow_seg.py:158,203,494 (and the _
 _yolo twins); always ``(prev_region, next_region, None, **farneback_params)`` with the keys
 ``pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags`` (:73-81); inputs may be
 strided ROI views ``gray[y0:y1, x0:x1]`` (:186-187).
+
+Frames of the other single-channel depths cv2 accepts (int8, uint16, int16, int32, float16, float32, float64) are
+converted with ``astype(np.float32)`` -- cv2's own first step, ``convertTo(CV_32F)`` -- and run through the float32
+entry points; uint8 frames take the 8-bit ones.
 """
 import ctypes as C
 from dataclasses import asdict, dataclass
@@ -36,6 +40,37 @@ PARAMS_B = FarnebackParams(0.6, 3, 3, 3, 10, 1.05, 0)   # autodriving, uav
 PARAMS_C = FarnebackParams(0.6, 3, 4, 2, 1, 1.05, 0)    # tabletennis
 
 
+# single-channel depths cv2.calcOpticalFlowFarneback takes (CV_8U, CV_8S, CV_16U, CV_16S, CV_32S, CV_16F, CV_32F, CV_64F)
+_ACCEPTED_DTYPES = tuple(np.dtype(t) for t in (np.uint8, np.int8, np.uint16, np.int16, np.int32, np.float16, np.float32,
+                                              np.float64))
+
+
+def _as_gray(a, name):
+    """A single-channel 2-D frame of an accepted depth (not converted)."""
+    if not isinstance(a, np.ndarray):
+        raise NsofValueError(f"{name} is not a numpy array (got {type(a).__name__})")
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if a.ndim != 2:
+        raise NsofValueError(f"{name} must be single-channel (shape {a.shape}); cv2 asserts channels() == 1")
+    if a.dtype not in _ACCEPTED_DTYPES:
+        raise NsofValueError(f"{name}: dtype {a.dtype} is not a depth cv2 takes (uint8, int8, uint16, int16, int32, "
+                             "float16, float32, float64)")
+    return a
+
+
+def _as_gray_f32(a, name):
+    """-> float32 frame with contiguous pixels and 4-byte aligned rows, every value finite."""
+    if a.dtype != np.float32:
+        with np.errstate(over="ignore"):   # float64 beyond float32's range becomes inf and is refused below
+            a = a.astype(np.float32)   # the same rounding as cv2's convertTo(CV_32F)
+    elif a.size and (a.strides[1] != 4 or a.strides[0] % 4 or a.ctypes.data % 4):
+        a = np.ascontiguousarray(a)
+    if not np.isfinite(a).all():
+        raise NsofValueError(f"{name} holds non-finite values (after conversion to float32)")
+    return a
+
+
 def _as_gray_u8(a, name):
     if not isinstance(a, np.ndarray):
         raise NsofValueError(f"{name} is not a numpy array (got {type(a).__name__})")
@@ -58,6 +93,10 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
                              *, ctx=None, exact=None, low_latency=None):
     """Same signature and result as ``cv2.calcOpticalFlowFarneback``: float32 (H, W, 2), (u, v) interleaved,
     such that ``next(x+u, y+v) ~ prev(x, y)``.  ``flow=None`` allocates; a matching float32 array is reused.
+    ``prev`` / ``next``: single-channel frames of one dtype, any of uint8, int8, uint16, int16, int32, float16, float32,
+    float64 (cv2's depths).  Other depths are converted with ``astype(np.float32)`` (cv2's ``convertTo(CV_32F)``; exact
+    except int32 above 2^24 and float64) and run on the float32 path; non-finite values raise, as do frames of two
+    different dtypes (cv2 would convert each on its own).
     ``exact`` (keyword only): True = box-filter row sums in the library's own order for this call
     (``NSOF_OPT_EXACT_ROWSUMS``, the context's default: bit-identical to the CPU restatement on any input),
     False = the fast mode (each pixel's window summed directly: a few per cent faster, up to ~8e-4 off where 2x2 systems
@@ -71,13 +110,19 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
     workgroup hand-over timed out never returns a flow field (``NSOF_EDEVICE``).
     The two keywords set context options around the call; the context's lock makes that safe for concurrent callers of
     one context."""
-    prev = _as_gray_u8(prev, "prev")
-    next = _as_gray_u8(next, "next")  # noqa: A001
+    prev = _as_gray(prev, "prev")
+    next = _as_gray(next, "next")  # noqa: A001
+    if prev.dtype != next.dtype:   # cv2 converts each on its own; here both frames must be of one depth
+        raise NsofValueError(f"prev ({prev.dtype}) and next ({next.dtype}) dtypes differ")
     if prev.shape != next.shape:
         raise NsofValueError(f"prev {prev.shape} and next {next.shape} sizes differ", _lib.NSOF_ESHAPE)
     h, w = prev.shape
     if h == 0 or w == 0:
         raise NsofValueError("empty input image", _lib.NSOF_ESHAPE)
+    if prev.dtype == np.uint8:
+        prev, next, entry = _as_gray_u8(prev, "prev"), _as_gray_u8(next, "next"), "nsof_farneback_u8"  # noqa: A001
+    else:
+        prev, next, entry = _as_gray_f32(prev, "prev"), _as_gray_f32(next, "next"), "nsof_farneback_f32"  # noqa: A001
     if (isinstance(flow, np.ndarray) and flow.dtype == np.float32 and flow.shape == (h, w, 2)
             and flow.strides[2] == 4 and flow.strides[1] == 8 and flow.flags.writeable):
         out = flow
@@ -97,9 +142,9 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
             saved_bands = ctx.get_option(_lib.OPT_ROW_BANDS)
             ctx.set_option(_lib.OPT_ROW_BANDS, 1 if low_latency else 0)
         try:
-            rc = ctx._lib.nsof_farneback_u8(ctx.ptr, prev.ctypes.data, prev.strides[0], next.ctypes.data, next.strides[0],
-                                            w, h, out.ctypes.data, out.strides[0], float(pyr_scale), int(levels),
-                                            int(winsize), int(iterations), int(poly_n), float(poly_sigma), int(flags))
+            rc = getattr(ctx._lib, entry)(ctx.ptr, prev.ctypes.data, prev.strides[0], next.ctypes.data, next.strides[0],
+                                          w, h, out.ctypes.data, out.strides[0], float(pyr_scale), int(levels),
+                                          int(winsize), int(iterations), int(poly_n), float(poly_sigma), int(flags))
         finally:
             if saved is not None:
                 ctx.set_option(_lib.OPT_EXACT_ROWSUMS, saved)
@@ -109,32 +154,56 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
     return out
 
 
+def _tensor_dtype(obj):
+    """'uint8' / 'float32' / ... of a torch tensor (or anything with a numpy-like dtype), None for raw addresses."""
+    dt = getattr(obj, "dtype", None)
+    return None if dt is None else str(dt).replace("torch.", "")
+
+
+def _frames_dtype(frames, dtype):
+    """The pixel type of device frames: a tensor's own dtype, else the ``dtype`` keyword (default uint8)."""
+    names = {_tensor_dtype(f) for f in frames} - {None}
+    if dtype is not None:
+        names.add(np.dtype(dtype).name)
+    names = names or {"uint8"}
+    if len(names) != 1:
+        raise NsofValueError(f"frames of different dtypes {sorted(names)}")
+    name = names.pop()
+    if name not in ("uint8", "float32"):
+        raise NsofValueError(f"device frames must be uint8 or float32 (got {name})")
+    return name
+
+
 def farneback_batch(d_prev, d_next, d_flow, n_pairs, height, width, params, *, row_stride=None, pair_stride=None,
-                    ctx=None):
-    """Device-resident batch: ``d_prev/d_next`` uint8 [n][H][row_stride], ``d_flow`` float32 [n][H][W][2]
-    (torch tensors or raw device addresses).  Asynchronous on the context's stream."""
+                    dtype=None, ctx=None):
+    """Device-resident batch: ``d_prev/d_next`` uint8 or float32 [n][H][row_stride], ``d_flow`` float32 [n][H][W][2]
+    (torch tensors or raw device addresses).  Strides are in BYTES (default: dense).  The frames' type is the tensors'
+    dtype; raw addresses are uint8 unless ``dtype=np.float32``.  Asynchronous on the context's stream."""
     ctx = ctx or default_context()
-    row_stride = width if row_stride is None else row_stride
+    f32 = _frames_dtype((d_prev, d_next), dtype) == "float32"
+    row_stride = width * (4 if f32 else 1) if row_stride is None else row_stride
     pair_stride = row_stride * height if pair_stride is None else pair_stride
     p = params
-    rc = ctx._lib.nsof_farneback_u8_batch_dev(ctx.ptr, n_pairs, dev_ptr(d_prev), dev_ptr(d_next), row_stride,
-                                              pair_stride, width, height, dev_ptr(d_flow), p.pyr_scale, p.levels,
-                                              p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags)
+    entry = ctx._lib.nsof_farneback_f32_batch_dev if f32 else ctx._lib.nsof_farneback_u8_batch_dev
+    rc = entry(ctx.ptr, n_pairs, dev_ptr(d_prev), dev_ptr(d_next), row_stride, pair_stride, width, height, dev_ptr(d_flow),
+               p.pyr_scale, p.levels, p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags)
     ctx.check(rc, "farneback_batch")
 
 
 def farneback_sequence(d_frames, d_flow, n_frames, height, width, params, *, row_stride=None, frame_stride=None,
-                       ctx=None):
-    """Device-resident sequence: ``d_frames`` uint8 [n_frames][H][row_stride]; ``d_flow`` float32
+                       dtype=None, ctx=None):
+    """Device-resident sequence: ``d_frames`` uint8 or float32 [n_frames][H][row_stride]; ``d_flow`` float32
     [n_frames-1][H][W][2] with flow i = frame i -> frame i+1 (the consecutive-pair walk of the reference's scripts).
-    Per-frame work (pyramid, polynomial expansion) is shared between neighbouring pairs."""
+    Per-frame work (pyramid, polynomial expansion) is shared between neighbouring pairs.  Strides in bytes and the
+    frames' type as for ``farneback_batch``."""
     ctx = ctx or default_context()
-    row_stride = width if row_stride is None else row_stride
+    f32 = _frames_dtype((d_frames,), dtype) == "float32"
+    row_stride = width * (4 if f32 else 1) if row_stride is None else row_stride
     frame_stride = row_stride * height if frame_stride is None else frame_stride
     p = params
-    rc = ctx._lib.nsof_farneback_u8_sequence_dev(ctx.ptr, n_frames, dev_ptr(d_frames), row_stride, frame_stride,
-                                                 width, height, dev_ptr(d_flow), p.pyr_scale, p.levels, p.winsize,
-                                                 p.iterations, p.poly_n, p.poly_sigma, p.flags)
+    entry = ctx._lib.nsof_farneback_f32_sequence_dev if f32 else ctx._lib.nsof_farneback_u8_sequence_dev
+    rc = entry(ctx.ptr, n_frames, dev_ptr(d_frames), row_stride, frame_stride, width, height, dev_ptr(d_flow), p.pyr_scale,
+               p.levels, p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags)
     ctx.check(rc, "farneback_sequence")
 
 
@@ -182,6 +251,9 @@ def _desc_array(pairs, flows, host):
             d.flow, d.flow_stride = flow.ctypes.data, flow.strides[0]
         else:
             h, w = int(prev.shape[0]), int(prev.shape[1])
+            if _tensor_dtype(prev) not in (None, "uint8") or _tensor_dtype(nxt) not in (None, "uint8"):
+                raise NsofValueError(f"pair {i}: work-list frames must be uint8 tensors (got {_tensor_dtype(prev)}, "
+                                     f"{_tensor_dtype(nxt)})")
             if tuple(nxt.shape[:2]) != (h, w):
                 raise NsofValueError(f"pair {i}: prev and next sizes differ", _lib.NSOF_ESHAPE)
             if prev.stride(1) != 1 or nxt.stride(1) != 1 or flow.stride(2) != 1 or flow.stride(1) != 2:
@@ -259,6 +331,8 @@ def farneback_roi_sequence_dev(frames, counts, rects, flows, params, *, gate_fra
     -> (n_crops, crop_pixels)."""
     ctx = ctx or default_context()
     kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
+    if _tensor_dtype(frames) not in (None, "uint8"):
+        raise NsofValueError(f"frames must be a uint8 tensor (got {_tensor_dtype(frames)}); work lists are 8-bit")
     n, h, w = (int(v) for v in frames.shape)
     if tuple(flows.shape) != (n - 1, h, w, 2) or not flows.is_contiguous() or frames.stride(2) != 1:
         raise NsofValueError("flows must be a contiguous (n-1, H, W, 2) tensor and the frames' pixel stride 1")
