@@ -247,9 +247,9 @@ int nsof_stage_blur_solve(nsof_ctx* ctx, int n_pairs, const float* d_M, int widt
  * d_flow_out must not alias.  winsize 2..15; larger windows take the unfused pair above. */
 int nsof_stage_iterate(nsof_ctx* ctx, int n_pairs, const float* d_R, const float* d_flow_in, int width, int height,
                        int winsize, float* d_flow_out);
-/* The same with flow_in = resample(d_coarse_flow [src_h][src_w][2]) * (1/pyr_scale) formed on the fly (first
- * iteration of a pyramid level).  Tuning builds only; returns NSOF_EUNSUPPORTED in the release build (the symbol
- * stays for the ABI). */
+/* Formerly the same with flow_in = resample(d_coarse_flow [src_h][src_w][2]) * (1/pyr_scale) formed on the fly.
+ * That kernel was removed (measured slower than the separate resample); the symbol stays for the ABI: it checks its
+ * arguments (NSOF_EINVAL) and otherwise returns NSOF_EUNSUPPORTED. */
 int nsof_stage_iterate_upsample(nsof_ctx* ctx, int n_pairs, const float* d_R, const float* d_coarse_flow,
                                 int src_w, int src_h, int width, int height, int winsize, double pyr_scale,
                                 float* d_flow_out);

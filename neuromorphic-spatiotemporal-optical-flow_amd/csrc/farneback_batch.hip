@@ -199,16 +199,14 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
             Li[j] = nsof_farneback_effective_levels(descs[het[j]].width, descs[het[j]].height, p.pyr_scale, p.levels);
             Lmax = std::max(Lmax, Li[j]);
         }
-        static const bool exact_2k = [] { const char* e = NSOF_AB_GETENV("NSOF_EXACT_IMPL"); return e && e[0] == '2'; }();
-        const bool exact_x = exact && !exact_2k;   // one fused kernel (k_iterate_x); 2k: column sums through HBM
         // a list too small to fill the chip with (strip, item) jobs: the three-kernel small-batch form of the same order
         long long jobs = 0;
         for (int j = 0; j < nh; j++) {
             jobs += (descs[het[j]].width + 191) / 192;
             if ((unsigned long long)descs[het[j]].width * descs[het[j]].height * 40ull >= (1ull << 32)) jobs = 1ll << 40;   // 32-bit offsets per item
         }
-        const bool exact_lat = exact_x && jobs <= ctx->opt_small_batch_jobs;
-        const bool use_xj = exact_x && !exact_lat;   // k_iterate_x runs the list: it needs its job tables
+        const bool exact_lat = exact && jobs <= ctx->opt_small_batch_jobs;
+        const bool use_xj = exact && !exact_lat;   // k_iterate_x runs the list: it needs its job tables
         // Per level: the item table (sorted into size classes), then the fused kernel's job table (8 counts + 8 lists).
         long long strips0 = 0;   // strips of the full-resolution level = the most any level has
         for (int j = 0; j < nh; j++) strips0 += (descs[het[j]].width + NSOF_X_STRIP - 1) / NSOF_X_STRIP;
@@ -290,7 +288,7 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
 
         // workspace: level images, expansions, two flow buffers (every level uses their leading part)
         const size_t szI = align_up(maxI * 4, 256), szR = align_up(maxR * 4, 256), szF = align_up(maxF * 8, 256);
-        const size_t szV = (exact && !exact_x) || exact_lat ? szR : 0;   // column sums, 5 doubles per pixel = the expansion's footprint
+        const size_t szV = exact_lat ? szR : 0;   // column sums, 5 doubles per pixel = the expansion's footprint
         const size_t szM = exact_lat ? align_up(szR / 2, 256) : 0;        // matrices of the small-batch form, 5 floats per pixel
         if ((rc = nsof_ws_reserve(ctx, &ctx->ws, &ctx->ws_bytes, szI + szR + 2 * szF + szV + szM))) return rc;
         char* base = (char*)ctx->ws;
@@ -328,12 +326,9 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
                 if (exact_lat)
                     rc = nsof_launch_iterate_lat_het(ctx, nk_items, dt, max_w[k], max_h[k], dR, fb[cur], fb[cur ^ 1], final, p.winsize,
                                                      dM, dV);
-                else if (exact_x)
+                else if (exact)
                     rc = nsof_launch_iterate_x_het(ctx, nk_items, dt, max_w[k], max_h[k], dR, szR / 4, fb[cur], fb[cur ^ 1], final,
                                                    p.winsize, d_xj + xj_at[k], xj_stride[k], xj_jobs[k]);
-                else if (exact)
-                    rc = nsof_launch_iterate_het_exact(ctx, nk_items, dt, max_w[k], max_h[k], dR, fb[cur], fb[cur ^ 1], final,
-                                                       p.winsize, dV);
                 else
                     rc = nsof_launch_iterate_het(ctx, nk_items, dt, max_w[k], dR, fb[cur], fb[cur ^ 1], final, p.winsize);
                 if (rc) return rc;

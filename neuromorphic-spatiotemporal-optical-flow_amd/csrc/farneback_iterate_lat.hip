@@ -186,7 +186,7 @@ __global__ __launch_bounds__(64 * LC_WAVES) void k_lat_colsum(const float* __res
 //                 as columns), 32 steps of S += V[x + m] - V[x - m - 1], S -> LDS
 //   solver waves  thread <-> pixel of the PREVIOUS tile: the 2x2 solve and the flow store
 //   loader waves  keep the ring fed, 4 chunks of 32 columns in flight in registers (coalesced 256-B row segments of V)
-// One barrier per tile.  Arithmetic and order as k_rowscan_solve / the library, bit for bit.  Rows per workgroup: 4 while
+// One barrier per tile.  Arithmetic and order as the library's, bit for bit.  Rows per workgroup: 4 while
 // that gives at most one workgroup per CU (the per-CU load rate is the limit: more, smaller workgroups win), else 8.
 #ifndef NSOF_LR_TW
 #define NSOF_LR_TW 32
@@ -433,14 +433,7 @@ int launch_lat_rowscan(nsof_ctx* ctx, int n, int W, int H, int max_h, const doub
 int lat_rowscan(nsof_ctx* ctx, int n, int W, int H, int max_h, const double* V, int winsize, float* flow_out,
                 const nsof_het_item* items, bool final)
 {
-#ifdef NSOF_AB
-    static const bool old = NSOF_AB_GETENV("NSOF_LAT_ROWSCAN_OLD") != nullptr;   // A/B: the two-kernel form's row scan
-    if (old)
-        return items ? nsof_launch_rowscan_solve_het(ctx, n, items, max_h, V, flow_out, final, winsize)
-                     : nsof_launch_rowscan_solve(ctx, n, V, W, H, winsize, flow_out);
-#endif
-    static const int rows_env = [] { const char* e = NSOF_AB_GETENV("NSOF_LR_ROWS"); return e ? atoi(e) : 0; }();   // A/B: 4 or 8
-    const bool rows4 = rows_env ? rows_env == 4 : (long long)((max_h + 3) / 4) * n <= 256;
+    const bool rows4 = (long long)((max_h + 3) / 4) * n <= 256;
     switch (winsize / 2) {
 #define NSOF_LR(MM)                                                                                                  \
     case MM:                                                                                                         \
@@ -454,7 +447,7 @@ int lat_rowscan(nsof_ctx* ctx, int n, int W, int H, int max_h, const double* V, 
 
 }  // namespace
 
-// M: 5 floats per pixel, V: 5 doubles per pixel (per pair; work list: at offR / 2 of each item, as the two-kernel form).
+// M: 5 floats per pixel, V: 5 doubles per pixel (per pair; work list: at offR / 2 of each item).
 int nsof_launch_iterate_lat(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
                             const float* flow_in, float* flow_out, int W, int H, int winsize, float* M, double* V)
 {

@@ -1908,18 +1908,11 @@ void launch_polyexp_n(nsof_ctx* ctx, int n_img, const float* img, int W, int H, 
     int seg_rows = ((H + segs - 1) / segs + 3) / 4 * 4;
     segs = (H + seg_rows - 1) / seg_rows;
     dim3 grid(strips, segs, n_img);
-#ifdef NSOF_AB
-    static const bool mono = [] { const char* e = NSOF_AB_GETENV("NSOF_POLYEXP"); return e && e[0] == 'm'; }();   // A/B: single-role kernel
-#endif
     if (u8)
         hipLaunchKernelGGL((k_polyexp_rs<N, false, true>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, nullptr, *u8);
     else if (ctx->opt_polyexp_f32)
         hipLaunchKernelGGL((k_polyexp<N, false, true>), grid, dim3(256), 0, ctx->stream, img, R, W, H, seg_rows, taps,
                            nullptr);
-#ifdef NSOF_AB   // NSOF_POLYEXP=mono: the single-role kernel with the exact arithmetic (superseded by k_polyexp_rs)
-    else if (mono)
-        hipLaunchKernelGGL((k_polyexp<N, false>), grid, dim3(256), 0, ctx->stream, img, R, W, H, seg_rows, taps, nullptr);
-#endif
     else
         hipLaunchKernelGGL((k_polyexp_rs<N, false>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, nullptr);
 }
@@ -2009,8 +2002,7 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
                                (taps.ksize == 3 || taps.ksize == 5);   // larger kernels: registers run out
         // exact decimation by 2 / 4 / 8 with the kernel sizes the pyr_scale 0.5 pyramid produces
         const int S = W / wk;
-        static const bool force8 = NSOF_AB_GETENV("NSOF_DECIM_CW8") != nullptr;   // A/B: 8-column lanes everywhere
-        const int CWL = ((W & 15) == 0 && !force8) ? 16 : 8;   // source columns per lane
+        const int CWL = (W & 15) == 0 ? 16 : 8;   // source columns per lane
         // f32: 16-byte aligned rows (float4 loads); 8-column lanes only while the blur halo fits in one (S = 2, 4)
         const bool decim_al = kU8<T> ? (row_stride % CWL) == 0 && (img_stride % CWL) == 0 &&
                                            (reinterpret_cast<uintptr_t>(src) % CWL) == 0
@@ -2018,7 +2010,7 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
         const bool decim_ok = S >= 2 && W == S * wk && H == S * hk && (W % CWL) == 0 && W >= 64 && decim_al &&
                               ((S == 2 && taps.ksize == 3) || (S == 4 && taps.ksize == 9) ||
                                (S == 8 && taps.ksize == 19)) &&
-                              H > taps.ksize && NSOF_AB_GETENV("NSOF_PREP_NODECIM") == nullptr;
+                              H > taps.ksize;
         if (decim_ok) {
             // segments of output rows: multiples of the unroll count, ~16 source rows of warm-up amortised
             const int U = S == 2 ? 2 : 3;
@@ -2079,7 +2071,7 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
             if (taps.ksize == 3) NSOF_PREP_DIRECT(3);
             else NSOF_PREP_DIRECT(5);
 #undef NSOF_PREP_DIRECT
-        } else if (taps.ksize == 19 && scale_x >= 1.0 && scale_y >= 1.0 && NSOF_AB_GETENV("NSOF_PREP_TILED") == nullptr) {
+        } else if (taps.ksize == 19 && scale_x >= 1.0 && scale_y >= 1.0) {
             // measured at 1080p x 64 frames: 19 taps 459 -> 244 us; 9 taps is still faster tiled (231 vs 254 us)
             int rc = nsof_ws_reserve(ctx, &ctx->tmp, &ctx->tmp_bytes, (size_t)n_img * H * 2 * wk * sizeof(float));
             if (rc) return rc;
@@ -2092,15 +2084,15 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
                                out);
         } else if (smem <= 60 * 1024 && scale_x >= 1.0 && scale_y >= 1.0) {
             dim3 grid((wk + PREP_TW - 1) / PREP_TW, (hk + PREP_TH - 1) / PREP_TH, n_img);
-#define NSOF_PREP_TILED(KS)                                                                                        \
+#define PREP_TILED(KS)                                                                                        \
     hipLaunchKernelGGL((k_prep_tiled<KS, false, T>), grid, dim3(256), smem, ctx->stream, src, row_stride, img_stride, \
                        W, H, wk, hk, scale_x, scale_y, rw_cap, rh_cap, taps, out, nullptr)
             switch (taps.ksize) {
-                case 9: NSOF_PREP_TILED(9); break;
-                case 19: NSOF_PREP_TILED(19); break;
-                default: NSOF_PREP_TILED(0); break;
+                case 9: PREP_TILED(9); break;
+                case 19: PREP_TILED(19); break;
+                default: PREP_TILED(0); break;
             }
-#undef NSOF_PREP_TILED
+#undef PREP_TILED
         } else {
             dim3 grid((wk + 63) / 64, (hk + 3) / 4, n_img);
             hipLaunchKernelGGL((k_prep_naive<false, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
@@ -2208,7 +2200,7 @@ int NSOF_PYR_NAME(nsof_launch_flow_upsample)(nsof_ctx* ctx, int n_pairs, const f
 {
     nsof_prof_scope ps(ctx, NSOF_K_UPSAMPLE);
     const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
-    if (dw >= sw && dh >= sh && sw >= 1 && sh >= 1 && dw >= 256 && NSOF_AB_GETENV("NSOF_UPSAMPLE_2X2") == nullptr) {
+    if (dw >= sw && dh >= sh && sw >= 1 && sh >= 1 && dw >= 256) {
         // upsampling: source steps of 0 or 1 between neighbours; rows wide enough for a lane per 2 columns
         dim3 g(((dw + 1) / 2 + 255) / 256, (dh + UPW_SEG - 1) / UPW_SEG, n_pairs);
         hipLaunchKernelGGL(k_flow_upsample_walk, g, dim3(256), 0, ctx->stream, src, sw, sh, dst, dw, dh, scale_x,
@@ -2276,15 +2268,15 @@ int NSOF_PYR_NAME(nsof_launch_prep_het)(nsof_ctx* ctx, int n_items, const nsof_h
                                    1., taps, I, d_items);
         } else if (smem <= 60 * 1024) {
             dim3 grid((max_wk + PREP_TW - 1) / PREP_TW, (max_hk + PREP_TH - 1) / PREP_TH, nz);
-#define NSOF_PREP_TILED_HET(KS)                                                                                       \
+#define PREP_TILED_HET(KS)                                                                                       \
     hipLaunchKernelGGL((k_prep_tiled<KS, true, uint8_t>), grid, dim3(256), smem, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1., \
                        rw_cap, rh_cap, taps, I, d_items)
             switch (taps.ksize) {
-                case 9: NSOF_PREP_TILED_HET(9); break;
-                case 19: NSOF_PREP_TILED_HET(19); break;
-                default: NSOF_PREP_TILED_HET(0); break;
+                case 9: PREP_TILED_HET(9); break;
+                case 19: PREP_TILED_HET(19); break;
+                default: PREP_TILED_HET(0); break;
             }
-#undef NSOF_PREP_TILED_HET
+#undef PREP_TILED_HET
         } else {
             dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
             hipLaunchKernelGGL((k_prep_naive<true, uint8_t>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1.,

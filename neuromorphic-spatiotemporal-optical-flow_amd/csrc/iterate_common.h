@@ -56,29 +56,19 @@ __device__ __forceinline__ void issue_row(RowIn& in, const Planes& R0, const Pla
     in.fx = fx - x1;
     in.fy = fy - y1;
     in.inside = (unsigned)x1 < (unsigned)(W - 1) && (unsigned)y1 < (unsigned)(H - 1);
-#if defined(NSOF_ABL) && NSOF_ABL == 3   // timing-only build: no R0 loads either
-    in.z = make_float4(d.x, d.y, d.x + 1.f, (float)pix);
-    in.z4 = d.y + 2.f;
-#else
     in.z = *reinterpret_cast<const float4*>(R0.q4 + pix * 16u);
     in.z4 = *reinterpret_cast<const float*>(R0.c4 + pix * 4u);
-#endif
     // The R1 gather is issued unconditionally, at a clamped (always valid) address when the sample falls
     // outside: a load under a lane-dependent branch cannot be counted by s_waitcnt vmcnt(N), which would
     // force every wait down to "almost nothing outstanding" and serialise the software pipeline.
     const int xs = clampi(x1, 0, W - 2), ys = clampi(y1, 0, H - 2);
     const unsigned o = (unsigned)ys * (unsigned)W + (unsigned)xs;
-#if defined(NSOF_ABL) && (NSOF_ABL == 1 || NSOF_ABL == 3)   // timing-only build: no R1 gather
-    in.t0 = in.t1 = in.b0 = in.b1 = make_float4(in.z.x + (float)o, in.z.y, in.z.z, in.z.w);
-    in.t4.a = in.t4.b = in.b4.a = in.b4.b = in.z4;
-#else
     in.t0 = *reinterpret_cast<const float4*>(R1.q4 + o * 16u);
     in.t1 = *reinterpret_cast<const float4*>(R1.q4 + o * 16u + 16u);
     in.b0 = *reinterpret_cast<const float4*>(R1.q4 + (o + (unsigned)W) * 16u);
     in.b1 = *reinterpret_cast<const float4*>(R1.q4 + (o + (unsigned)W) * 16u + 16u);
     in.t4 = *reinterpret_cast<const f2u*>(R1.c4 + o * 4u);
     in.b4 = *reinterpret_cast<const f2u*>(R1.c4 + (o + (unsigned)W) * 4u);
-#endif
 }
 
 // FarnebackUpdateMatrices for one pixel, from loaded inputs.

@@ -601,9 +601,8 @@ extern "C" int nsof_stage_iterate_upsample(nsof_ctx* ctx, int n_pairs, const flo
 {
     if (!ctx || !d_R || !d_coarse_flow || !d_flow_out || n_pairs < 1 || width < 1 || height < 1 || src_w < 1 || src_h < 1)
         return NSOF_EINVAL;
-    const size_t plane = (size_t)width * height;
-    return nsof_launch_iterate_upsample(ctx, n_pairs, d_R, d_R + 5 * plane, 10 * plane, d_coarse_flow, src_w, src_h,
-                                        (float)(1. / pyr_scale), d_flow_out, width, height, winsize);
+    (void)pyr_scale;
+    return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "fused upsample+iteration not available for winsize %d", winsize);
 }
 
 extern "C" int nsof_stage_flow_upsample(nsof_ctx* ctx, int n_pairs, const float* d_src, int sw, int sh, float* d_dst,
@@ -636,21 +635,13 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     if (row_stride < (ptrdiff_t)width * px_bytes) return nsof_set_error(ctx, NSOF_EINVAL, "row_stride < width * %d", px_bytes);
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const bool exact = ctx->opt_exact_rowsums != 0;
-    // exact row-sum order: ONE fused kernel (k_iterate_x) where the window fits; NSOF_EXACT_IMPL=2k selects the older
-    // two-kernel form (column sums through HBM) for A/B runs
-    static const bool exact_2k = [] { const char* e = NSOF_AB_GETENV("NSOF_EXACT_IMPL"); return e && e[0] == '2'; }();
-    static const char* fused_env0 = NSOF_AB_GETENV("NSOF_FUSED");
-    const bool exact_x = exact && !exact_2k && !(fused_env0 && fused_env0[0] == '0') && iterations > 0 &&
-                         nsof_iterate_x_supported(winsize, width, height);
+    // exact row-sum order: ONE fused kernel (k_iterate_x) where the window fits, else the unfused pair
+    const bool exact_x = exact && iterations > 0 && nsof_iterate_x_supported(winsize, width, height);
     // a batch too small to fill the chip with (strip, image) jobs takes the three-kernel small-batch form of the same
     // order (farneback_iterate_lat.hip; NSOF_OPT_SMALL_BATCH_JOBS)
     const bool exact_lat = exact_x && (long long)n_pairs * ((width + 191) / 192) <= ctx->opt_small_batch_jobs &&
                            (unsigned long long)width * height * 40ull < (1ull << 32);   // its kernels address a pair with 32-bit byte offsets
-    static const int exact_chunk = [] {
-        const char* e = NSOF_AB_GETENV("NSOF_EXACT_CHUNK");
-        const int v = e ? atoi(e) : 64;
-        return v < 1 ? 1 : v;
-    }();
+    const int exact_chunk = 64;
     if (exact && !exact_x && (sequence || n_pairs > exact_chunk)) {
         // the exact order keeps 40 B/px of column sums (+ 20 B/px of matrices) in HBM: 64 pairs of 1920x1080 at a time
         // (8 GB) fill the GPU -- the row walk has one thread per image row; a sequence is run as its pairs
@@ -706,18 +697,14 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     // (+ M [B][5][n0] only when the window is too large for the fused iteration kernel)
     const size_t n0 = (size_t)width * height, B = (size_t)n_pairs;
     const size_t n_img = sequence ? B + 1 : 2 * B;   // frames of a sequence, or B prev + B next frames
-    // Fused or unfused is decided once for the whole pyramid (inputs below 2x2 take the unfused pair).
-    // NSOF_FUSED=0 forces the unfused pair (A/B runs; measured slower even for a lone 1080p pair: 6.1 vs 4.0 ms).
-    static const char* fused_env = NSOF_AB_GETENV("NSOF_FUSED");
-    // exact row-sum order: the fused two-kernel form (phase A + row scan) where the window fits, else the unfused kernels
-    const bool exact_fused = exact && (exact_x || (nsof_iterate_exact_supported(winsize, width, height) && !(fused_env && fused_env[0] == '0')));
-    const bool fused = nsof_iterate_supported(winsize, width, height) && !(fused_env && fused_env[0] == '0') &&
-                       (!exact || exact_fused);
+    // Fused or unfused is decided once for the whole pyramid (inputs below 2x2 take the unfused pair); the exact
+    // row-sum order is fused only where k_iterate_x runs it.
+    const bool fused = nsof_iterate_supported(winsize, width, height) && (!exact || exact_x);
     const size_t szI = align_up(n_img * n0 * 4, 256), szR = align_up(n_img * 5 * n0 * 4, 256);
     const size_t szS = align_up(B * n0 * 8, 256), szM = fused && !exact_lat ? 0 : align_up(B * 5 * n0 * 4, 256);
-    const size_t szV = (exact && !exact_x) || exact_lat ? align_up(B * 5 * n0 * 8, 256) : 0;   // column sums of the two- / three-kernel exact order
+    const size_t szV = (exact && !exact_x) || exact_lat ? align_up(B * 5 * n0 * 8, 256) : 0;   // column sums of the unfused / three-kernel exact order
     if ((rc = nsof_ws_reserve(ctx, &ctx->ws, &ctx->ws_bytes, szI + szR + szS + szM + szV))) return rc;
-    char* base = (char*)ctx->ws;   // (re-derived below if the level overlap grows the workspace)
+    char* base = (char*)ctx->ws;   // (re-derived below if the small-batch schedule grows the workspace)
     float* dI = (float*)base;
     float* dR = (float*)(base + szI);
     float* dS = (float*)(base + szI + szR);
@@ -727,105 +714,8 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     // Each upsample and each fused iteration moves the flow to the other buffer, so the buffer the coarsest
     // level starts in is chosen such that the last iteration of level 0 writes A.
     float* fb[2] = {d_flow, dS};
-    // The coarse-to-fine resample is folded into the first iteration of each level when the fused kernel can do
-    // it; then only iterations move the flow between the buffers.
-    // Measured on MI355X (1080p x 128 pairs): folding costs more in the producers (4 gathers + the resample per
-    // row, 168 VGPRs) than the standalone resample kernel saves (24.6 -> 25.5 ms per step), so it is opt-in.
-    static const bool fold_env = NSOF_AB_GETENV("NSOF_FOLD_UPSAMPLE") != nullptr;
-    const bool fold_ups = fold_env && fused && !exact && iterations > 0 &&
-                          nsof_iterate_upsample_supported(winsize, width, height);
-    const int flips = fused ? (fold_ups ? (L + 1) * iterations : L * (1 + iterations) + iterations) : L;
+    const int flips = fused ? L * (1 + iterations) + iterations : L;
     int cur = flips & 1;
-
-    // ---- level overlap (opt-in experiment, NSOF_OVERLAP=1) -----------------------------------------------------------
-    // The iteration and expansion kernels hold a CU through its LDS (159 / 41 KB per workgroup) while the counters show
-    // VALU and HBM only 50-65 % busy; the pyramid-level and flow-resample kernels use no LDS and few registers.  On a
-    // side stream, the pyramid level of level k-1 runs next to the iterations of level k and the flow resample for
-    // level k-1 next to its polynomial expansion; events order the hand-overs.  Same kernels, arguments and results.
-    // Measured (256 pairs 1080p): every kernel slows down by what the others gain -- iterate 23.7 -> 26.3 ms, polyexp
-    // 8.9 -> 10.4, prep 2.9 -> 3.9, resample 1.5 -> 2.3 per step, 6877 vs 6804 pairs/s -- there is no idle capacity to
-    // harvest next to these kernels, so the single-stream order stays the default.
-#ifdef NSOF_AB
-    static const bool overlap_env = [] { const char* e = NSOF_AB_GETENV("NSOF_OVERLAP"); return e && e[0] == '1'; }();
-#endif
-#ifdef NSOF_AB   // tuning builds only: NSOF_OVERLAP=1 (level overlap on a side stream; measured no faster)
-    if (fused && !exact && !fold_ups && overlap_env && L >= 1 && iterations > 0) {
-        if (!ctx->side) NSOF_HIP(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-        while (ctx->ov_events.size() < (size_t)4 * (L + 1)) {
-            hipEvent_t ev;
-            NSOF_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            ctx->ov_events.push_back(ev);
-        }
-        auto EV = [&](int k, int which) { return ctx->ov_events[(size_t)4 * k + which]; };   // 0 prep, 1 poly, 2 iter, 3 ups
-        struct StreamSwap {
-            nsof_ctx* c; hipStream_t saved;
-            StreamSwap(nsof_ctx* cc, hipStream_t s) : c(cc), saved(cc->stream) { c->stream = s; }
-            ~StreamSwap() { c->stream = saved; }
-        };
-        // second level-image buffer behind the regular workspace
-        const size_t base_bytes = szI + szR + szS + szM + szV;
-        if ((rc = nsof_ws_reserve(ctx, &ctx->ws, &ctx->ws_bytes, base_bytes + szI))) return rc;
-        base = (char*)ctx->ws;
-        dI = (float*)base;
-        dR = (float*)(base + szI);
-        dS = (float*)(base + szI + szR);
-        fb[1] = dS;
-        float* Ibuf[2] = {dI, (float*)(base + base_bytes)};
-        auto prep_level = [&](int k, float* I) -> int {
-            int wk, hk, ks;
-            double sg;
-            nsof_farneback_level_size(width, height, pyr_scale, k, &wk, &hk, &ks, &sg);
-            nsof_blur_taps bt;
-            if (int r = nsof_host_blur_taps(ks, sg, &bt))
-                return nsof_set_error(ctx, r, "pyramid blur kernel size %d unsupported (max %d)", ks, NSOF_MAX_BLUR_TAPS - 1);
-            const size_t nk = (size_t)wk * hk;
-            if (sequence) return NSOF_PYR_SEL(ctx, nsof_launch_prep, (int)n_img, d_prev, row_stride, pair_stride, width, height, wk, hk, bt, I, src);
-            for (int i = 0; i < 2; i++)
-                if (int r = NSOF_PYR_SEL(ctx, nsof_launch_prep, n_pairs, i == 0 ? d_prev : d_next, row_stride, pair_stride, width, height, wk,
-                                             hk, bt, I + (size_t)i * B * nk, src))
-                    return r;
-            return NSOF_OK;
-        };
-        const hipStream_t mainS = ctx->stream, sideS = ctx->side;
-        if ((rc = prep_level(L, Ibuf[L & 1]))) return rc;
-        for (int k = L; k >= 0; k--) {
-            int wk, hk;
-            nsof_farneback_level_size(width, height, pyr_scale, k, &wk, &hk, nullptr, nullptr);
-            const size_t nk = (size_t)wk * hk;
-            if (k < L) NSOF_HIP(ctx, hipStreamWaitEvent(mainS, EV(k, 0), 0));          // this level's images are ready
-            if ((rc = nsof_launch_polyexp(ctx, (int)n_img, Ibuf[k & 1], wk, hk, ptaps, dR))) return rc;
-            if (k > 0) {   // next level's images: on the side stream, next to this level's iterations
-                NSOF_HIP(ctx, hipEventRecord(EV(k, 1), mainS));
-                NSOF_HIP(ctx, hipStreamWaitEvent(sideS, EV(k, 1), 0));
-                StreamSwap sw(ctx, sideS);
-                if ((rc = prep_level(k - 1, Ibuf[(k - 1) & 1]))) return rc;
-                NSOF_HIP(ctx, hipEventRecord(EV(k - 1, 0), sideS));
-            }
-            if (k == L) NSOF_HIP(ctx, hipMemsetAsync(fb[cur], 0, B * nk * 8, mainS));
-            else NSOF_HIP(ctx, hipStreamWaitEvent(mainS, EV(k, 3), 0));                // the resampled flow is ready
-            const float* R0 = dR;
-            const float* R1 = dR + (sequence ? (size_t)1 : B) * 5 * nk;
-            for (int it = 0; it < iterations; it++) {
-                if ((rc = nsof_launch_iterate(ctx, n_pairs, R0, R1, 5 * nk, fb[cur], fb[cur ^ 1], wk, hk, winsize))) return rc;
-                cur ^= 1;
-            }
-            if (k > 0) {   // resample this level's flow for the next one: on the side stream, next to its expansion
-                int w1, h1;
-                nsof_farneback_level_size(width, height, pyr_scale, k - 1, &w1, &h1, nullptr, nullptr);
-                NSOF_HIP(ctx, hipEventRecord(EV(k, 2), mainS));
-                NSOF_HIP(ctx, hipStreamWaitEvent(sideS, EV(k, 2), 0));
-                StreamSwap sw(ctx, sideS);
-                if ((rc = NSOF_PYR_SEL(ctx, nsof_launch_flow_upsample, n_pairs, fb[cur], wk, hk, fb[cur ^ 1], w1, h1, (float)(1. / pyr_scale))))
-                    return rc;
-                cur ^= 1;
-                NSOF_HIP(ctx, hipEventRecord(EV(k - 1, 3), sideS));
-            }
-        }
-        if (fb[cur] != d_flow)
-            NSOF_HIP(ctx, hipMemcpyAsync(d_flow, fb[cur], B * n0 * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        return NSOF_OK;
-    }
-#endif
 
     // prev and next frames of a batch that lie back to back (the host-pointer entry stages a lone pair that way) are one
     // array of 2 B images: one pyramid launch per level instead of two (a lone call's launches have a ~5 us floor each)
@@ -845,9 +735,7 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     // frames (k_polyexp_rs<.., U8>): no pyramid launch, no image written and read back.  Not with the FMA twin of the
     // pyramid stages nor with the float expansion (their kernels have no such form), nor for f32 frames: those take the
     // two-kernel form (k_prep_same3_vec<.., float>, then the expansion of the level image).
-    static const bool poly_u8_off = [] { const char* e = NSOF_AB_GETENV("NSOF_POLY_U8"); return e && e[0] == '0'; }();
-    const bool poly_u8 = !poly_u8_off && src == NSOF_SRC_U8 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && width >= 2 &&
-                         height >= 2;
+    const bool poly_u8 = src == NSOF_SRC_U8 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && width >= 2 && height >= 2;
     float* Ifused[4] = {nullptr, nullptr, nullptr, nullptr};   // level images already made by the three-level launch
     auto level_expansion = [&](int k, int wk, int hk, const nsof_blur_taps& bt, float* I, float* Rk) -> int {
         if (k >= 1 && k <= 3 && Ifused[k]) return nsof_launch_polyexp(ctx, (int)n_img, Ifused[k], wk, hk, ptaps, Rk);
@@ -944,8 +832,7 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     // pyr_scale 0.5 with three coarser levels (the headline configuration): levels 1..3 smooth and decimate the same
     // full-resolution frames -- one launch makes all three (k_prep_decim3), into the level-image buffer that level 0 no
     // longer needs before the coarser levels are done with it
-    static const bool decim3_off = [] { const char* e = NSOF_AB_GETENV("NSOF_DECIM3"); return e && e[0] == '0'; }();
-    if (L == 3 && !decim3_off) {
+    if (L == 3) {
         nsof_blur_taps bt3[3];
         size_t nk3[3];
         bool exact3 = true;
@@ -983,11 +870,8 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
             return nsof_set_error(ctx, rc, "pyramid blur kernel size %d unsupported (max %d)", ks,
                                   NSOF_MAX_BLUR_TAPS - 1);
         const size_t nk = (size_t)wk * hk;
-        bool pending_ups = false;
         if (!have_prev) {
             NSOF_HIP(ctx, hipMemsetAsync(fb[cur], 0, B * nk * 8, ctx->stream));
-        } else if (fold_ups) {
-            pending_ups = true;   // fb[cur] still holds the coarse flow (pw x ph)
         } else {
             if ((rc = NSOF_PYR_SEL(ctx, nsof_launch_flow_upsample, n_pairs, fb[cur], pw, ph, fb[cur ^ 1], wk, hk,
                                                 (float)(1. / pyr_scale))))
@@ -1001,15 +885,10 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
         const float* R1 = dR + (sequence ? (size_t)1 : B) * 5 * nk;
         if (fused) {
             for (int it = 0; it < iterations; it++) {
-                if (it == 0 && pending_ups)
-                    rc = nsof_launch_iterate_upsample(ctx, n_pairs, R0, R1, 5 * nk, fb[cur], pw, ph,
-                                                      (float)(1. / pyr_scale), fb[cur ^ 1], wk, hk, winsize);
-                else if (exact_lat)
+                if (exact_lat)
                     rc = nsof_launch_iterate_lat(ctx, n_pairs, R0, R1, 5 * nk, fb[cur], fb[cur ^ 1], wk, hk, winsize, dM, dV);
                 else if (exact_x)
                     rc = nsof_launch_iterate_x(ctx, n_pairs, R0, R1, 5 * nk, fb[cur], fb[cur ^ 1], wk, hk, winsize);
-                else if (exact_fused)
-                    rc = nsof_launch_iterate_exact(ctx, n_pairs, R0, R1, 5 * nk, fb[cur], fb[cur ^ 1], wk, hk, winsize, dV);
                 else
                     rc = nsof_launch_iterate(ctx, n_pairs, R0, R1, 5 * nk, fb[cur], fb[cur ^ 1], wk, hk, winsize);
                 if (rc) return rc;

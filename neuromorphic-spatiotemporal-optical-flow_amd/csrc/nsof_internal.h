@@ -52,8 +52,8 @@ struct nsof_ctx {
     int het_flip = 0;
     // pipelined host entry (nsof_farneback_u8_batch): copy streams, per-slot staging and events
     struct nsof_pipe* pipe = nullptr;
-    // level overlap of the uniform batch driver: a side stream for the LDS-free stages (pyramid level of the next
-    // level, flow resample) that share the CUs with the LDS-bound iteration / expansion kernels, and its events
+    // small-batch schedule of the uniform batch driver: a side stream for the pyramid levels and expansions of the
+    // finer levels, next to the iterations of the coarser ones, and the events that hand each level over
     hipStream_t side = nullptr;
     std::vector<hipEvent_t> ov_events;
     // exact-order fused iteration (farneback_iterate_x.hip): strip-to-strip carries (tagged granules, zeroed when
@@ -73,17 +73,6 @@ struct nsof_ctx {
     unsigned x_epoch = 0;
     bool x_dirty = false;
 };
-
-// Tuning / A-B switches.  Only builds made by scripts/build_variant.sh (-DNSOF_AB) read them; in the product library each
-// of them is the constant "unset" and the larger kernels they select are not compiled (#ifdef NSOF_AB in the sources).
-// The environment variables the PRODUCT reads are the context defaults documented in include/nsof.h (NSOF_POLYEXP_F32,
-// NSOF_EXACT_ROWSUMS, NSOF_PYR_FMA, NSOF_LAT_JOBS, NSOF_ROW_BANDS), the pipelined entry's NSOF_PIPE_CHUNK_MB /
-// NSOF_PIPE_FAIL_AFTER_CHUNK / NSOF_PIPE_TRACE and the chunking cap NSOF_MAX_PAIRS (test hooks).
-#ifdef NSOF_AB
-#define NSOF_AB_GETENV(name) getenv(name)
-#else
-#define NSOF_AB_GETENV(name) (static_cast<const char*>(nullptr))
-#endif
 
 int nsof_set_error(nsof_ctx* ctx, int code, const char* fmt, ...);
 int nsof_ws_reserve(nsof_ctx* ctx, void** buf, size_t* cur, size_t need);
@@ -165,12 +154,6 @@ int nsof_launch_iterate_lat(nsof_ctx* ctx, int n_pairs, const float* R0, const f
                             const float* flow_in, float* flow_out, int W, int H, int winsize, float* M, double* V);
 int nsof_launch_iterate_lat_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h, const float* R,
                                 const float* flow_in, float* flow_out, bool final, int winsize, float* M, double* V);
-int nsof_launch_rowscan_solve(nsof_ctx* ctx, int n_pairs, const double* V, int W, int H, int winsize, float* flow_out);
-int nsof_launch_rowscan_solve_het(nsof_ctx* ctx, int n_items, const nsof_het_item* items, int max_h, const double* V,
-                                  float* flow_out, bool final, int winsize);
-int nsof_launch_iterate_het_exact(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
-                                  const float* R, const float* flow_in, float* flow_out, bool final, int winsize,
-                                  double* vsum);
 // All launchers are asynchronous on ctx->stream and return an nsof_status.
 // The *_het twins take a device table of n_items entries; max_* are the largest extents over the table.
 int nsof_launch_prep_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items,
@@ -219,11 +202,6 @@ bool nsof_iterate_supported(int winsize, int W, int H);
 // Fused iteration; flow_in != flow_out.
 int nsof_launch_iterate(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
                         const float* flow_in, float* flow_out, int W, int H, int winsize);
-// Exact-order twin (row sums as one running sum per image row, the reference library's order): vsum = n_pairs * 5 * W * H
-// doubles of scratch (the column sums pass through HBM between its two kernels).
-bool nsof_iterate_exact_supported(int winsize, int W, int H);
-int nsof_launch_iterate_exact(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
-                              const float* flow_in, float* flow_out, int W, int H, int winsize, double* vsum);
 // Exact-order fused iteration in ONE kernel (running row sums inside the strip walker, strips chained by carries).
 bool nsof_iterate_x_supported(int winsize, int W, int H);
 int nsof_launch_iterate_x(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
@@ -240,11 +218,6 @@ int nsof_xsync_reserve(nsof_ctx* ctx, size_t carry_bytes, unsigned long long** c
 int nsof_xsync_check(nsof_ctx* ctx);
 // hipStreamSynchronize(ctx->stream) + nsof_xsync_check: the tail of every entry point that hands results to the host
 int nsof_stream_sync_checked(nsof_ctx* ctx);
-bool nsof_iterate_upsample_supported(int winsize, int W, int H);
-// First iteration of a level: flow_in = resample(coarse_flow [sh][sw][2]) * mul, computed on the fly.
-int nsof_launch_iterate_upsample(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
-                                 const float* coarse_flow, int sw, int sh, float mul, float* flow_out, int W, int H,
-                                 int winsize);
 
 // ---- streamed stores ----------------------------------------------------------------------------------------
 // Outputs that are not re-read before the caches have turned over (pyramid images, R, flow fields of a batch) are

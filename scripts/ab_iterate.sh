@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B timing of libnsof variants (scripts/build_variant.sh) on the fused iteration stage.
 #   bash scripts/ab_iterate.sh name1 name2 ...     name = lib variant ("base" = the product library), optionally
-#   followed by +ENV=VALUE pairs, e.g.  base+NSOF_ITER_SPLIT=1
+#   followed by +ENV=VALUE pairs, e.g.  base+NSOF_ROW_BANDS=1
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1
 for spec in "$@"; do

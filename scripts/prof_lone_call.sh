@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 kernel stats of lone calls (scripts/latency_single.py) under the environment given: usage
-#   [SHAPES=0] NSOF_EXACT_IMPL=2k bash scripts/prof_lone_call.sh <tag>      (SHAPES: indices of latency_single's cases)
+#   [SHAPES=0] NSOF_LAT_JOBS=0 bash scripts/prof_lone_call.sh <tag>      (SHAPES: indices of latency_single's cases)
 set -e
 TAG=${1:-lone}
 REPO=$(cd "$(dirname "$0")/.." && pwd)

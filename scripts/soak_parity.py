@@ -5,7 +5,6 @@ Not part of the test-suite (minutes of CPU oracle time); prints one JSON summary
     python scripts/soak_parity.py [--cases 400] [--seed 7] [--mode default|fastrows|fast]
 
 --mode default   the library's operation order in every stage (NSOF_OPT_EXACT_ROWSUMS=1): expected bit-identical everywhere
-                 (NSOF_EXACT_IMPL=2k in the environment runs the older two-kernel form of the same order)
 --mode fastrows  NSOF_OPT_EXACT_ROWSUMS=0 (per-pixel window sums: deviates at rank-deficient windows)
 --mode fast      NSOF_OPT_POLYEXP_F32 (float polynomial expansion: NOT bit-identical; the summary gives the error)
 A quarter of the cases are "low texture" frames (flat blocks, straight bars, a little noise: rank-deficient windows

@@ -95,7 +95,7 @@ def test_pyr_level_bit_exact(ctx, oracle, torch_dev, frames, pyr_scale, level, s
                                    (96, 64)])
 def test_pyr_level_exact_decimation_path(ctx, oracle, torch_dev, level, shape):
     """Dense, 16-byte aligned frames whose size divides by 2^level take the decimating walker kernel
-    (k_prep_decim); same bits as the oracle, and as the generic kernels (NSOF_PREP_NODECIM)."""
+    (k_prep_decim); same bits as the oracle."""
     import torch
     h, w = shape
     if h % (1 << level) or w % (1 << level) or h <= (3, 9, 19)[level - 1]:
@@ -259,7 +259,7 @@ def test_flow_upsample_bit_exact(ctx, oracle, torch_dev, pyr_scale, src, dst):
 
 
 def test_iterate_upsample_is_unsupported_in_release_build(ctx, torch_dev):
-    """nsof_stage_iterate_upsample exists for the ABI; its kernel is in tuning builds only (include/nsof.h)."""
+    """nsof_stage_iterate_upsample exists for the ABI; its kernel was removed (include/nsof.h)."""
     import torch
     from nsof import _lib
     h, w = 40, 64
