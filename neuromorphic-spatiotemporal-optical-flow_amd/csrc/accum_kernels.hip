@@ -537,11 +537,7 @@ __global__ __launch_bounds__(256) void k_frames_scatter_copy(const uint8_t* __re
             typedef unsigned u4v __attribute__((ext_vector_type(4)));
             const u4v* s4 = reinterpret_cast<const u4v*>(prev);
             u4v* d4 = reinterpret_cast<u4v*>(cur);
-#ifdef NSOF_ACC_COPY_PLAIN
-            for (long long i = tid; i < n16; i += nthreads) d4[i] = s4[i];
-#else
             for (long long i = tid; i < n16; i += nthreads) __builtin_nontemporal_store(s4[i], d4 + i);
-#endif
         } else {
             const long long n = (long long)W * H;
             for (long long i = tid; i < n; i += nthreads) {
@@ -1231,10 +1227,8 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
     const std::vector<long long>& rel = a->h_rel;
     NSOF_HIP(ctx, hipMemsetAsync(a->count, 0, 4 * sizeof(unsigned), ctx->stream));
     int par = 0;
-#ifndef NSOF_ACC_COPY_BLOCKS
-#define NSOF_ACC_COPY_BLOCKS 4096
-#endif
-    const unsigned copy_blocks = (unsigned)std::min<size_t>(NSOF_ACC_COPY_BLOCKS, (a->npx / 16 + 255) / 256 + 1);
+    constexpr size_t ACC_COPY_BLOCKS = 4096;
+    const unsigned copy_blocks = (unsigned)std::min<size_t>(ACC_COPY_BLOCKS, (a->npx / 16 + 255) / 256 + 1);
     for (int64_t k = 0; k < n_frames; k++) {
         const int64_t s0 = first_slice + k * every;
         const long long ge0 = rel[s0], gn = rel[s0 + every] - ge0;

@@ -26,32 +26,6 @@
 
 namespace {
 
-#ifdef NSOF_Q_TIMING
-// Tuning build only (scripts/build_variant.sh ... -DNSOF_Q_TIMING): shader-clock time that one wave of each role of
-// workgroup (0,0,0) spends working and waiting at the two barriers of a step; read back by scripts/q_timing.py.
-__device__ unsigned long long g_qt[16];
-#define QT_ON (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && (threadIdx.x & 255) == 0)
-#define QT_DECL unsigned long long qt_prev = __builtin_amdgcn_s_memtime()
-#define QT_MARK(slot)                                                      \
-    do {                                                                   \
-        const unsigned long long qt_now = __builtin_amdgcn_s_memtime();    \
-        if (QT_ON) atomicAdd(&g_qt[slot], qt_now - qt_prev);               \
-        qt_prev = qt_now;                                                  \
-    } while (0)
-extern "C" int nsof_debug_qtiming(unsigned long long* out16, int reset)
-{
-    if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_qt), sizeof(g_qt)) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[16] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_qt), z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#else
-#define QT_DECL
-#define QT_MARK(slot)
-#endif
-
 template <int MH, int COLS_ = 256>
 struct QGeom {
     static constexpr int COLS = COLS_, RB = 4;
@@ -110,24 +84,15 @@ __device__ __forceinline__ void q_producer_loop(float (*mring)[5][COLS], const P
     q_produce<MH, COLS, GP, 0, 1>(in, fl, mring, R0, R1, F, W, H, xc, col, 0, yb);
     __syncthreads();
     q_produce<MH, COLS, GP, 1, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, 1, yb);
-    QT_DECL;
     for (int tb = 0; tb < nsteps; tb += 2) {
-        QT_MARK(4 + 4 * GP + 2);                                                     // work before B1
         __syncthreads();                                                             // B1(tb)
-        QT_MARK(4 + 4 * GP + 3);                                                     // wait at B1
         q_produce<MH, COLS, GP, 1, 1>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 1, yb);
-        QT_MARK(4 + 4 * GP + 0);                                                     // work before B2
         __syncthreads();                                                             // B2(tb)
-        QT_MARK(4 + 4 * GP + 1);                                                     // wait at B2
         q_produce<MH, COLS, GP, 0, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 2, yb);
         if (tb + 1 >= nsteps) break;
-        QT_MARK(4 + 4 * GP + 2);
         __syncthreads();                                                             // B1(tb+1)
-        QT_MARK(4 + 4 * GP + 3);
         q_produce<MH, COLS, GP, 0, 1>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 2, yb);
-        QT_MARK(4 + 4 * GP + 0);
         __syncthreads();                                                             // B2(tb+1)
-        QT_MARK(4 + 4 * GP + 1);
         q_produce<MH, COLS, GP, 1, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 3, yb);
     }
 }
@@ -200,7 +165,6 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][COLS], void* s
     int slot_new = (2 * MH + 1) % RL;           // stream index m    -> slot 2m+1
     int slot_old = 0;                           // stream index -m-1 -> slot 0
     const bool own = col >= MH && col < MH + SW && x0 + col - MH < W;   // VOUT: this thread's column belongs to the strip
-    QT_DECL;
     for (int t = 0; t < nsteps; t++) {
         // column sums: four more rows enter the window of this thread's column
 #pragma unroll
@@ -219,9 +183,7 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][COLS], void* s
             slot_new = slot_new + 1 == RL ? 0 : slot_new + 1;
             slot_old = slot_old + 1 == RL ? 0 : slot_old + 1;
         }
-        QT_MARK(0);        // column sums
         __syncthreads();   // B1(t): column sums of step t visible
-        QT_MARK(1);        // wait at B1
         if constexpr (VOUT) {
             __syncthreads();   // B2(t): same barrier sequence as the solving variant
             continue;
@@ -262,9 +224,7 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][COLS], void* s
                     if (xo + p < W) dst[p] = o[p];
             }
         }
-        QT_MARK(2);        // row sums + solve
         __syncthreads();   // B2(t): column sums consumed, the buffer may be rewritten
-        QT_MARK(3);        // wait at B2
     }
 }
 
@@ -303,7 +263,6 @@ __global__ __launch_bounds__(3 * COLS) void k_iterate_q(const float* __restrict_
             fpitch = (size_t)W;
         }
     } else {
-#ifndef NSOF_NO_XCD_REMAP
         // XCD-aware placement: workgroups are dealt round-robin to the 8 XCDs (linear id % 8), each with its own L2.
         // With the natural (strip, pair) order the strips of a pair land on different L2s and their shared halo
         // columns and gather rows are fetched once per XCD; remapped, an XCD owns whole pairs.
@@ -314,7 +273,6 @@ __global__ __launch_bounds__(3 * COLS) void k_iterate_q(const float* __restrict_
             pair = (int)(j / gridDim.x);
             strip = (int)(j - (unsigned)pair * gridDim.x);
         }
-#endif
     }
     const int x0 = strip * SW;
     const int xc = clampi(x0 - MH + col, 0, W - 1);

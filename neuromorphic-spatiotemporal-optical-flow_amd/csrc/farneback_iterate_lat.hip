@@ -188,14 +188,7 @@ __global__ __launch_bounds__(64 * LC_WAVES) void k_lat_colsum(const float* __res
 //   loader waves  keep the ring fed, 4 chunks of 32 columns in flight in registers (coalesced 256-B row segments of V)
 // One barrier per tile.  Arithmetic and order as the library's, bit for bit.  Rows per workgroup: 4 while
 // that gives at most one workgroup per CU (the per-CU load rate is the limit: more, smaller workgroups win), else 8.
-#ifndef NSOF_LR_TW
-#define NSOF_LR_TW 32
-#endif
-#ifndef NSOF_LR_DEPTH
-#define NSOF_LR_DEPTH 4
-#endif
-constexpr int LR_TW = NSOF_LR_TW, LR_RING = 4 * LR_TW, LR_SLOTS = 6 * LR_TW, LR_DEPTH = NSOF_LR_DEPTH;
-static_assert(LR_TW == 16 || LR_TW == 32, "tile width");
+constexpr int LR_TW = 32, LR_RING = 4 * LR_TW, LR_SLOTS = 6 * LR_TW, LR_DEPTH = 4;
 template <int ROWS>
 struct LRGeom {
     static_assert(ROWS == 4 || ROWS == 8 || ROWS == 16, "rows per workgroup");
@@ -211,22 +204,6 @@ struct LRGeom {
     static constexpr int THREADS = CHAIN + SOLVE + LOAD;
     static constexpr size_t SMEM = sizeof(double) * (5 * PLANE + 2 * 5 * SPLANE);
 };
-
-#ifdef NSOF_LR_TIMING
-// Tuning build only (scripts/build_variant.sh lrt farneback_iterate_lat.hip -DNSOF_LR_TIMING; scripts/lr_timing.py): where one
-// workgroup of the row scan spends its time.  g_lrt: [role 0..2][work cycles, barrier-wait cycles], [6] steps, [7] kernel
-// shader cycles of wave 0, [8] the same span in s_memrealtime ticks (100 MHz): [7] / [8] = the shader clock in units of 100 MHz.
-__device__ unsigned long long g_lrt[16];
-extern "C" int nsof_debug_lrtiming(unsigned long long* out16, int reset)
-{
-    if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_lrt), sizeof(g_lrt)) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[16] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_lrt), z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
 
 template <class F, int... Ks>
 __device__ __forceinline__ void lr_steps(F& step, int s, int T, std::integer_sequence<int, Ks...>)
@@ -312,23 +289,9 @@ __global__ __launch_bounds__(LRGeom<LR_ROWS>::THREADS) void k_lat_rowscan(const 
     }
     // solver role: pixel (sj, sr) of the tile
     const int sj = li & (LR_TW - 1), sr = li / LR_TW;
-#ifdef NSOF_LR_TIMING
-    const bool lt_on = blockIdx.x == 1 && blockIdx.z == 0 && W >= 1024;
-    const bool lt_lead = lt_on && (tid == 0 || tid == LR_CHAIN || tid == LR_CHAIN + LR_SOLVE);
-    unsigned long long lt_work = 0, lt_wait = 0, lt_prev = __builtin_amdgcn_s_memtime();
-    const unsigned long long lt_t0 = lt_prev, lt_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
     auto step = [&](auto kc, int s) {
         constexpr int K = decltype(kc)::value;
-#ifdef NSOF_LR_TIMING
-        {
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            lt_wait += now - lt_prev;
-            lt_prev = now;
-        }
-#endif
         if (role == 0) {
-#if !(defined(NSOF_LR_ABL) && NSOF_LR_ABL == 2)   // timing-only build: no chain
             if (chain_on) {
                 const int b0 = (s * LR_TW - 8) & (LR_RING - 1);   // window columns [TW s - 8, TW s + TW + 6] at slots b0 .. b0 + TW + 14
                 typedef double lr_d2 __attribute__((ext_vector_type(2)));
@@ -351,64 +314,29 @@ __global__ __launch_bounds__(LRGeom<LR_ROWS>::THREADS) void k_lat_rowscan(const 
                     so[j / 2] = o;
                 }
             }
-#endif
         } else if (role == 2) {
             // keep the ring fed: chunk s + 2 was requested LR_DEPTH steps ago; request chunk s + 2 + LR_DEPTH
-#if !(defined(NSOF_LR_ABL) && NSOF_LR_ABL == 3)   // timing-only build: no ring refill
-#if !(defined(NSOF_LR_ABL) && NSOF_LR_ABL == 4)   // timing-only build: loads without the LDS writes
 #pragma unroll
             for (int k = 0; k < 5; k++) chunk_put(s + 2, k, regs[K][k]);
-#else
-            if (regs[K][0] == 1.2345e300) chunk_put(s + 2, 0, regs[K][1] + regs[K][2] + regs[K][3] + regs[K][4]);
-#endif
-#if defined(NSOF_LR_ABL) && NSOF_LR_ABL == 5      // timing-only build: LDS writes without the loads
-            if (s < 0) {
-#else
             if (s + 2 + LR_DEPTH <= T + 1) {
-#endif
 #pragma unroll
                 for (int k = 0; k < 5; k++) regs[K][k] = chunk_src(s + 2 + LR_DEPTH, k);
             }
-#endif
-        } else {
-#if defined(NSOF_LR_ABL) && NSOF_LR_ABL == 1      // timing-only build: no solve
-            if (s < 0) {
-#else
-            if (s > 0) {
-#endif
-                const int x = (s - 1) * LR_TW + sj, y = y0 + sr;
-                const double* sp = St + ((s - 1) & 1) * 5 * LR_SPLANE + sr * LR_JSTR + sj;
-                const double g11 = sp[0] * scale, g12 = sp[LR_SPLANE] * scale, g22 = sp[2 * LR_SPLANE] * scale;
-                const double h1 = sp[3 * LR_SPLANE] * scale, h2 = sp[4 * LR_SPLANE] * scale;
-                if (x < W && y < H) {
-                    const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
-                    Fout[(size_t)y * fpitch + x] =
-                        make_float2((float)((g11 * h2 - g12 * h1) * idet), (float)((g22 * h1 - g12 * h2) * idet));
-                }
+        } else if (s > 0) {
+            const int x = (s - 1) * LR_TW + sj, y = y0 + sr;
+            const double* sp = St + ((s - 1) & 1) * 5 * LR_SPLANE + sr * LR_JSTR + sj;
+            const double g11 = sp[0] * scale, g12 = sp[LR_SPLANE] * scale, g22 = sp[2 * LR_SPLANE] * scale;
+            const double h1 = sp[3 * LR_SPLANE] * scale, h2 = sp[4 * LR_SPLANE] * scale;
+            if (x < W && y < H) {
+                const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
+                Fout[(size_t)y * fpitch + x] =
+                    make_float2((float)((g11 * h2 - g12 * h1) * idet), (float)((g22 * h1 - g12 * h2) * idet));
             }
         }
-#ifdef NSOF_LR_TIMING
-        {
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            lt_work += now - lt_prev;
-            lt_prev = now;
-        }
-#endif
         __syncthreads();
     };
     // step T only solves the last tile (its chain / ring work is harmless); unrolled by the prefetch depth (register sets)
     for (int s = 0; s <= T; s += LR_DEPTH) lr_steps(step, s, T, std::make_integer_sequence<int, LR_DEPTH>{});
-#ifdef NSOF_LR_TIMING
-    if (lt_lead) {
-        atomicAdd(&g_lrt[2 * role], lt_work);
-        atomicAdd(&g_lrt[2 * role + 1], lt_wait);
-        if (tid == 0) {
-            atomicAdd(&g_lrt[6], (unsigned long long)(T + 1));
-            atomicAdd(&g_lrt[7], __builtin_amdgcn_s_memtime() - lt_t0);
-            atomicAdd(&g_lrt[8], __builtin_amdgcn_s_memrealtime() - lt_r0);
-        }
-    }
-#endif
 }
 
 template <int MH, int ROWS>

@@ -66,25 +66,15 @@ struct XGeom {
     static_assert(SW + HALO <= COLS && SW % 8 == 0, "strip geometry");
     static constexpr int NB = COLS / 64, REM = COLS % 64;   // full 64-column producer blocks, columns of the remainder wave
     static_assert(REM == 16, "the remainder wave maps 4 rows x 16 columns onto its 64 lanes");
-#ifndef NSOF_X_SEG0
-#define NSOF_X_SEG0 96
-#endif
-    static constexpr int SEG0 = NSOF_X_SEG0, SEG1 = SW - SEG0;   // the strip's two scan segments (see x_scanner_loop)
+    static constexpr int SEG0 = 96, SEG1 = SW - SEG0;   // the strip's two scan segments (see x_scanner_loop)
     static_assert(SEG0 % 8 == 0 && SEG1 % 8 == 0 && SEG0 >= SEG1 && SEG1 > 0, "segments: whole 8-column blocks, the left one not shorter");
     static constexpr int SVW = SW + 2;                      // doubles per (row, plane) of D / g (even: 16-byte rows)
     static constexpr int WAVES = NCW + 1 + 2 * NB + 1 + 1;   // ... + the solver wave (the last one: SIMD 3, next to the scanner)
     static constexpr int THREADS = 64 * WAVES;
-#ifndef NSOF_X_CQ
-#define NSOF_X_CQ 1
-#endif
-#ifndef NSOF_X_IOQ
-#define NSOF_X_IOQ 1
-#endif
     // Who solves which of a step's four rows: the consumers rows [0, CQ) (own column, before they overwrite it), the I/O
     // wave rows [CQ, CQ + IOQ), the solver wave the rest.  A wave issues one vector instruction per ~8 clocks whatever the
     // SIMD has free, so the split balances the LENGTH of the per-wave instruction streams, not only the SIMDs.
-    static constexpr int CQ = NSOF_X_CQ, IOQ = NSOF_X_IOQ;
-    static_assert(CQ >= 0 && IOQ >= 0 && CQ + IOQ <= 4, "rows of a step");
+    static constexpr int CQ = 1, IOQ = 1;
     static constexpr size_t SV1_BYTES = sizeof(double) * 4 * 5 * SVW;      // one buffer of D / g
     static constexpr size_t SV_BYTES = 2 * SV1_BYTES;
     static constexpr size_t VI_BYTES = sizeof(double) * 2 * 4 * 5 * MH;     // row-start column sums (strip 0), 2 buffers
@@ -111,67 +101,6 @@ struct XRing {
         M[4] = c[slot * cols + col];
     }
 };
-
-#ifdef NSOF_X_TIMING
-// Tuning build only (scripts/build_variant.sh xt farneback_iterate_x.hip -DNSOF_X_TIMING): constant-clock time that one wave
-// of each role of the workgroup with job (pair 0, strip 1) spends in each part of a step; read by scripts/x_timing.py.
-__device__ unsigned long long g_xt[48];
-#define XT_DECL(on_)                                                        \
-    const bool xt_on = (on_);                                               \
-    const bool xt_any = xt;                                                 \
-    unsigned long long xt_bar = 0;                                          \
-    unsigned long long xt_acc[4] = {0, 0, 0, 0}, xt_prev = __builtin_amdgcn_s_memtime()
-#define XT_MARK(slot)                                                       \
-    do {                                                                    \
-        const unsigned long long xt_now = __builtin_amdgcn_s_memtime();     \
-        xt_acc[(slot) & 3] += xt_now - xt_prev;                             \
-        xt_prev = xt_now;                                                   \
-    } while (0)
-#define XT_BAR()                                                            \
-    do {                                                                    \
-        const unsigned long long xb0_ = __builtin_amdgcn_s_memtime();       \
-        __syncthreads();                                                    \
-        xt_bar += __builtin_amdgcn_s_memtime() - xb0_;                      \
-    } while (0)
-#define XT_FLUSH(base)                                                      \
-    do {                                                                    \
-        if (xt_on)                                                          \
-            for (int k_ = 0; k_ < 4; k_++) atomicAdd(&g_xt[(base) + k_], xt_acc[k_]); \
-        if (xt_any && (threadIdx.x & 63) == 0) atomicAdd(&g_xt[32 + (threadIdx.x >> 6)], xt_bar); \
-    } while (0)
-extern "C" int nsof_debug_xtiming(unsigned long long* out32, int reset)
-{
-    if (out32 && hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_xt), sizeof(g_xt)) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[48] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_xt), z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#else
-#define XT_DECL(on_)
-#define XT_MARK(slot)
-#define XT_BAR() __syncthreads()
-#define XT_FLUSH(base)
-#endif
-
-#ifdef NSOF_X_JOBLOG
-// Tuning build only (scripts/build_variant.sh xjl farneback_iterate_x.hip -DNSOF_X_JOBLOG; scripts/x_joblog.py): per job the
-// 100 MHz real-time stamps of its start, of the moment its pipeline is primed (barrier Bb) and of its end, with the CU it ran
-// on -- the per-CU timeline of a launch (dispatch gaps between jobs, start-up cost, chain lag, tail).
-__device__ unsigned long long g_xjob[8192 * 4];
-__device__ unsigned g_xjob_n;
-extern "C" int nsof_debug_xjoblog(unsigned long long* out, unsigned* n, int reset)
-{
-    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_xjob), sizeof(g_xjob)) != hipSuccess) return -1;
-    if (n && hipMemcpyFromSymbol(n, HIP_SYMBOL(g_xjob_n), sizeof(unsigned)) != hipSuccess) return -1;
-    if (reset) {
-        unsigned z = 0;
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_xjob_n), &z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
 
 constexpr unsigned X_SPIN_LIMIT = 1u << 21;   // polls of a carry before giving up (seconds): the grid always drains
 
@@ -233,7 +162,7 @@ __device__ __forceinline__ void x_rows_above(const XRing& ring, const Planes& R0
 // Full producer wave: thread <-> ring column, rows 2 GP, 2 GP + 1 of every step.
 template <int MH, int GP>
 __device__ __forceinline__ void x_producer_loop(const XRing& ring, const Planes& R0, const Planes& R1,
-                                                const FlowSrc<false>& F, int W, int H, int xc, int col, int nimg, bool xt)
+                                                const FlowSrc<false>& F, int W, int H, int xc, int col, int nimg)
 {
     if constexpr (GP == 0) x_rows_above<MH>(ring, R0, R1, F, W, H, xc, col);
     RowIn in[2][2];
@@ -254,26 +183,17 @@ __device__ __forceinline__ void x_producer_loop(const XRing& ring, const Planes&
         x_produce<MH>(in[TS][0], fl[TS][0], ring, R0, R1, F, W, H, xc, col, 4 * t + MH + 2 * GP);
         x_produce<MH>(in[TS][1], fl[TS][1], ring, R0, R1, F, W, H, xc, col, 4 * t + MH + 2 * GP + 1);
     };
-#ifdef NSOF_X_PPRIO
-    if (GP == 1) __builtin_amdgcn_s_setprio(NSOF_X_PPRIO);
-#endif
     step(std::integral_constant<int, 0>{}, 0);
     __syncthreads();                                                                 // Ba
     step(std::integral_constant<int, 1>{}, 1);
-    XT_DECL(xt && (threadIdx.x & 63) == 0);
     __syncthreads();                                                                 // Bb
     for (int t = 0; t <= nimg; t += 2) {
-        XT_MARK(1);                                                                  // wait at the barrier
         step(std::integral_constant<int, 0>{}, t + 2);
-        XT_MARK(0);                                                                  // rows
-        XT_BAR();                                                                    // B(t)
+        __syncthreads();                                                             // B(t)
         if (t + 1 > nimg) break;
-        XT_MARK(1);
         step(std::integral_constant<int, 1>{}, t + 3);
-        XT_MARK(0);
-        XT_BAR();                                                                    // B(t+1)
+        __syncthreads();                                                             // B(t+1)
     }
-    XT_FLUSH(8 + 8 * GP);
 }
 
 // ---- the solves outside the consumers: lane <-> columns lane, lane + 64, lane + 128 of the strip ----------------------------
@@ -286,40 +206,34 @@ __device__ __forceinline__ void x_solve_rows(const double* sv, volatile lds_int*
 {
     using G = XGeom<MH>;
     constexpr int SVW = G::SVW, NBLK = G::SW / 64;
-    if constexpr (NQ > 0) {
-        double g[NBLK][NQ][5];
-        int us[NBLK];
+    double g[NBLK][NQ][5];
+    int us[NBLK];
 #pragma unroll
-        for (int b = 0; b < NBLK; b++) {
-            const int col = b * 64 + lane;
-            const int u = t - 1 - (col >= G::SEG0 ? 1 : 0);
-            us[b] = (u >= 0 && u < nimg && x0 + col < W) ? u : -1;
-            const double* p = sv + (u & 1) * (G::SV1_BYTES / sizeof(double)) + col;
+    for (int b = 0; b < NBLK; b++) {
+        const int col = b * 64 + lane;
+        const int u = t - 1 - (col >= G::SEG0 ? 1 : 0);
+        us[b] = (u >= 0 && u < nimg && x0 + col < W) ? u : -1;
+        const double* p = sv + (u & 1) * (G::SV1_BYTES / sizeof(double)) + col;
 #pragma unroll
-            for (int q = 0; q < NQ; q++)
+        for (int q = 0; q < NQ; q++)
 #pragma unroll
-                for (int c = 0; c < 5; c++) g[b][q][c] = p[((q + Q0) * 5 + c) * SVW];
+            for (int c = 0; c < 5; c++) g[b][q][c] = p[((q + Q0) * 5 + c) * SVW];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the sums are in registers ...
+    if (lane == 0) *flag = t + 1;                           // ... their slots may take the next D
+#pragma unroll
+    for (int b = 0; b < NBLK; b++) {
+        if (us[b] < 0) continue;
+        const int x = x0 + b * 64 + lane;
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            const int yo = 4 * us[b] + q + Q0;
+            const double g11 = g[b][q][0] * scale, g12 = g[b][q][1] * scale, g22 = g[b][q][2] * scale;
+            const double h1 = g[b][q][3] * scale, h2 = g[b][q][4] * scale;
+            const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
+            const float ox = (float)((g11 * h2 - g12 * h1) * idet), oy = (float)((g22 * h1 - g12 * h2) * idet);
+            if (yo < H) nsof_store_stream2(reinterpret_cast<float*>(Fout + (size_t)yo * fpitch + x), ox, oy);
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the sums are in registers ...
-        if (lane == 0) *flag = t + 1;                           // ... their slots may take the next D
-#ifndef NSOF_X_ABL_SOLVE   // timing-only ablation: no solve at all
-#pragma unroll
-        for (int b = 0; b < NBLK; b++) {
-            if (us[b] < 0) continue;
-            const int x = x0 + b * 64 + lane;
-#pragma unroll
-            for (int q = 0; q < NQ; q++) {
-                const int yo = 4 * us[b] + q + Q0;
-                const double g11 = g[b][q][0] * scale, g12 = g[b][q][1] * scale, g22 = g[b][q][2] * scale;
-                const double h1 = g[b][q][3] * scale, h2 = g[b][q][4] * scale;
-                const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
-                const float ox = (float)((g11 * h2 - g12 * h1) * idet), oy = (float)((g22 * h1 - g12 * h2) * idet);
-                if (yo < H) nsof_store_stream2(reinterpret_cast<float*>(Fout + (size_t)yo * fpitch + x), ox, oy);
-            }
-        }
-#endif
-    } else {
-        if (lane == 0) *flag = t + 1;
     }
 }
 
@@ -333,7 +247,7 @@ __device__ __forceinline__ void x_solve_rows(const double* sv, volatile lds_int*
 template <int MH>
 __device__ __forceinline__ void x_remainder_loop(const XRing& ring, double* cb, const Planes& R0, const Planes& R1,
                                                  const FlowSrc<false>& F, int W, int H, int xc, int col, int r, int nimg,
-                                                 gu64* cin, gu64* cout, unsigned epoch, gu32* err, bool xt, const double* sv,
+                                                 gu64* cin, gu64* cout, unsigned epoch, gu32* err, const double* sv,
                                                  volatile lds_int* ioflag, float2* Fout, size_t fpitch, int x0, double scale)
 {
     const int lane = threadIdx.x & 63;
@@ -402,23 +316,18 @@ __device__ __forceinline__ void x_remainder_loop(const XRing& ring, double* cb, 
     fetch_issue(0);
     x_produce<MH>(in[1], fl[1], ring, R0, R1, F, W, H, xc, col, 4 + MH + r);
     fetch_finish(0);
-    XT_DECL(xt && lane == 0);
     __syncthreads();                                                                 // Bb
     // window t: the scanner finishes segment 1 of step t-1 (its row-end sums: published in window t+1) and starts segment
     // 0 of step t+1 in the next window (its row-start sums: fetched now)
     auto window = [&](auto tsc, int t) {
         constexpr int TS = decltype(tsc)::value;
-        XT_MARK(1);
         if (t >= 2) publish(t - 2);
         if (t + 1 < nimg) fetch_issue(t + 1);
         x_produce<MH>(in[TS], fl[TS], ring, R0, R1, F, W, H, xc, col, 4 * (t + 2) + MH + r);
-        XT_MARK(0);
         // its share of the step's 2x2 solves (rows [CQ, CQ + IOQ)) while the carry fetch is in flight
         x_solve_rows<MH, XGeom<MH>::CQ, XGeom<MH>::IOQ>(sv, ioflag, Fout, fpitch, W, H, x0, nimg, scale, lane, t);
-        XT_MARK(3);
         if (t + 1 < nimg) fetch_finish(t + 1);
-        XT_MARK(2);
-        XT_BAR();                                                                    // B(t)
+        __syncthreads();                                                             // B(t)
     };
     for (int t = 0; t <= nimg; t += 2) {
         window(std::integral_constant<int, 0>{}, t);
@@ -427,7 +336,6 @@ __device__ __forceinline__ void x_remainder_loop(const XRing& ring, double* cb, 
     }
     publish(nimg - 1);
     x_solve_rows<MH, XGeom<MH>::CQ, XGeom<MH>::IOQ>(sv, ioflag, Fout, fpitch, W, H, x0, nimg, scale, lane, nimg + 1);   // window nimg + 1: the right half's last step
-    XT_FLUSH(12);
 }
 
 // ---- consumers: thread <-> output column j of the strip ----------------------------------------------------------
@@ -439,8 +347,7 @@ __device__ __forceinline__ void x_remainder_loop(const XRing& ring, double* cb, 
 // step's D for one more window: two register sets used alternately (the loop is unrolled by two).
 template <int MH>
 __device__ __forceinline__ void x_consumer_loop(const XRing& ring, double* sv, double* vinit, volatile lds_int* sflag, float2* Fout,
-                                                size_t fpitch, int W, int H, int x0, int j, int nimg, double scale, bool strip0,
-                                                bool xt, unsigned xjl_slot = 0)
+                                                size_t fpitch, int W, int H, int x0, int j, int nimg, double scale, bool strip0)
 {
     using G = XGeom<MH>;
     constexpr int RL = G::RL, SVW = G::SVW, HALO = G::HALO;
@@ -477,10 +384,6 @@ __device__ __forceinline__ void x_consumer_loop(const XRing& ring, double* sv, d
     // The scanner works on the strip's two halves a step apart (segment 1 of step s in the window after segment 0 of step
     // s), so the threads of the right half publish their D one window late (kept in registers meanwhile): lag = 1.
     const int lag = j >= G::SEG0 ? 1 : 0;
-#ifdef NSOF_X_CPRIO
-    __builtin_amdgcn_s_setprio(NSOF_X_CPRIO);
-#endif
-    XT_DECL(xt && j == 0);
     double D[2][4][5];   // D[s & 1] = D of step s
     // step s: four more rows enter the windows of this thread's two columns -> D[P], P = s & 1
     auto column_sums = [&](auto pc, int s) {
@@ -521,65 +424,53 @@ __device__ __forceinline__ void x_consumer_loop(const XRing& ring, double* sv, d
     column_sums(std::integral_constant<int, 0>{}, 0);
     if (!lag) publish(std::integral_constant<int, 0>{}, 0);
     __syncthreads();   // Bb: D(0) of the left half is published, step 1 is in the ring
-#ifdef NSOF_X_JOBLOG
-    if (threadIdx.x == 0 && xjl_slot < 8192u) g_xjob[4 * xjl_slot + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
     // window t (P = t & 1): D[P] = D(t), formed a window ago; column_sums(t + 1) -> D[P ^ 1]
     auto window = [&](auto pc, int t) {
         constexpr int P = decltype(pc)::value;
-        XT_MARK(1);        // wait at the barrier
-        if constexpr (G::CQ > 0) {   // rows the consumers still solve themselves (own column: read before it is overwritten)
-            const int u = t - 1 - lag;
-            if (u >= 0 && u < nimg && x < W) {
-                const double* svj = sv + (u & 1) * (G::SV1_BYTES / sizeof(double)) + j;
+        // rows the consumers still solve themselves (own column: read before it is overwritten)
+        const int u = t - 1 - lag;
+        if (u >= 0 && u < nimg && x < W) {
+            const double* svj = sv + (u & 1) * (G::SV1_BYTES / sizeof(double)) + j;
 #pragma unroll
-                for (int q = 0; q < G::CQ; q++) {
-                    const int yo = 4 * u + q;
-                    const double g11 = svj[(q * 5 + 0) * SVW] * scale, g12 = svj[(q * 5 + 1) * SVW] * scale;
-                    const double g22 = svj[(q * 5 + 2) * SVW] * scale;
-                    const double h1 = svj[(q * 5 + 3) * SVW] * scale, h2 = svj[(q * 5 + 4) * SVW] * scale;
-                    const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
-                    const float ox = (float)((g11 * h2 - g12 * h1) * idet), oy = (float)((g22 * h1 - g12 * h2) * idet);
-                    if (yo < H) nsof_store_stream2(reinterpret_cast<float*>(Fout + (size_t)yo * fpitch + x), ox, oy);
-                }
+            for (int q = 0; q < G::CQ; q++) {
+                const int yo = 4 * u + q;
+                const double g11 = svj[(q * 5 + 0) * SVW] * scale, g12 = svj[(q * 5 + 1) * SVW] * scale;
+                const double g22 = svj[(q * 5 + 2) * SVW] * scale;
+                const double h1 = svj[(q * 5 + 3) * SVW] * scale, h2 = svj[(q * 5 + 4) * SVW] * scale;
+                const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
+                const float ox = (float)((g11 * h2 - g12 * h1) * idet), oy = (float)((g22 * h1 - g12 * h2) * idet);
+                if (yo < H) nsof_store_stream2(reinterpret_cast<float*>(Fout + (size_t)yo * fpitch + x), ox, oy);
             }
         }
-        XT_MARK(2);        // solve
         if (t == nimg + 1) return;
         if (t + 1 < nimg) column_sums(std::integral_constant<int, P ^ 1>{}, t + 1);
         // the solver wave has taken g(t-1) (left half) / g(t-2) (right half) out of the slots D goes into now; the wait is
         // bounded like every other (a wave of this workgroup sets the flag; normally long before)
-        for (int spin = 0; (sflag[0] < t + 1 || (G::IOQ > 0 && sflag[1] < t + 1)) && spin < (1 << 22); spin++)
+        for (int spin = 0; (sflag[0] < t + 1 || sflag[1] < t + 1) && spin < (1 << 22); spin++)
             __builtin_amdgcn_s_sleep(1);
         if (lag) publish(std::integral_constant<int, P>{}, t);            // right half: D(t), formed a window ago
         else publish(std::integral_constant<int, P ^ 1>{}, t + 1);        // left half: D(t+1), at once
-        XT_MARK(0);        // column sums
-        XT_BAR();          // B(t)
+        __syncthreads();   // B(t)
     };
     for (int t = 0; t <= nimg + 1; t += 2) {
         window(std::integral_constant<int, 0>{}, t);
         if (t + 1 > nimg + 1) break;
         window(std::integral_constant<int, 1>{}, t + 1);
     }
-    XT_FLUSH(0);
 }
 
 // The solver wave (the workgroup's last: SIMD 3, next to the scanner and the I/O wave).
 template <int MH>
 __device__ __forceinline__ void x_solver_loop(const double* sv, volatile lds_int* sflag, float2* Fout, size_t fpitch, int W, int H,
-                                              int x0, int nimg, double scale, int lane, bool xt)
+                                              int x0, int nimg, double scale, int lane)
 {
     using G = XGeom<MH>;
     __syncthreads();   // Ba
     __syncthreads();   // Bb
-    XT_DECL(xt && lane == 0);
     for (int t = 0; t <= nimg + 1; t++) {
-        XT_MARK(1);        // wait at the barrier
         x_solve_rows<MH, G::CQ + G::IOQ, 4 - G::CQ - G::IOQ>(sv, sflag, Fout, fpitch, W, H, x0, nimg, scale, lane, t);
-        XT_MARK(2);        // read g, solve, store
-        if (t <= nimg) XT_BAR();   // B(t)
+        if (t <= nimg) __syncthreads();   // B(t)
     }
-    XT_FLUSH(20);
 }
 
 // ---- the scanner wave -------------------------------------------------------------------------------------------------
@@ -589,7 +480,7 @@ __device__ __forceinline__ void x_solver_loop(const double* sv, volatile lds_int
 // the value the first group ended on a window earlier.
 template <int MH>
 __device__ __forceinline__ void x_scanner_loop(double* sv, const double* vinit, double* cb, bool has_left, int nimg, int ncols,
-                                               int lane, bool xt)
+                                               int lane)
 {
     using G = XGeom<MH>;
     constexpr int SVW = G::SVW;
@@ -600,9 +491,7 @@ __device__ __forceinline__ void x_scanner_loop(double* sv, const double* vinit, 
     __syncthreads();   // Ba
     __builtin_amdgcn_s_setprio(3);   // the one dependent chain every other wave of the step ends up waiting for
     __syncthreads();   // Bb
-    XT_DECL(xt && lane == 0);
     for (int t = 0; t <= nimg; t++) {   // window t
-        XT_MARK(6);    // wait at the barrier
         const int step = t - seg;
         const double Sleft = __shfl(Smid, lane >= 20 ? lane - 20 : lane);
         d2* row = reinterpret_cast<d2*>(sv + (step & 1) * (G::SV1_BYTES / sizeof(double)) + l * SVW + seg * G::SEG0);
@@ -735,19 +624,13 @@ __device__ __forceinline__ void x_scanner_loop(double* sv, const double* vinit, 
             };
             // both segments run the stream of the shorter one together; the rest of the longer (left) one follows
             const int nb0 = ncols >> 3, nba = nb0 < G::SEG1 / 8 ? nb0 : G::SEG1 / 8;
-#ifdef NSOF_X_ABL_SCAN   // timing-only ablation: the scanner runs two thirds of its blocks (what three 64-column segments would cost)
-            scan_blocks(0, nba * 2 / 3);
-#else
             scan_blocks(0, nba);
             if (nb0 > nba && !seg) scan_blocks(nba, nb0 - nba);
-#endif
             if (seg) cb[(step & 1) * 20 + l] = S;   // the row-end sums: the I/O wave hands them to the right neighbour
             else Smid = S;
         }
-        XT_MARK(5);        // scan
-        XT_BAR();          // B(t)
+        __syncthreads();   // B(t)
     }
-    XT_FLUSH(4);
 }
 
 // tickets: 8 counters, 32 words apart.  carry: granules, see the launcher.  n: pairs (items with HET); nstrips: strips of
@@ -804,18 +687,6 @@ __global__ __launch_bounds__((XGeom<MH>::THREADS)) void k_iterate_x(
     __syncthreads();
     const int pair = job[0], strip = job[1];
     if (pair < 0 || pair >= n) return;   // block-uniform
-#ifdef NSOF_X_JOBLOG
-    unsigned xjl_slot = 0xffffffffu;
-    if (tid == 0) {
-        xjl_slot = atomicAdd(&g_xjob_n, 1u);
-        if (xjl_slot < 8192u) {
-            g_xjob[4 * xjl_slot] = __builtin_amdgcn_s_memrealtime();
-            const unsigned hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));   // HW_REG_HW_ID
-            g_xjob[4 * xjl_slot + 3] = ((unsigned long long)xcc_id() << 48) | ((unsigned long long)hw << 16) |
-                                       ((unsigned long long)(pair & 0xfff) << 4) | (unsigned)(strip & 0xf);
-        }
-    }
-#endif
     size_t fpitch = (size_t)W;
     gu64* cbase;
     if constexpr (HET) {
@@ -846,26 +717,16 @@ __global__ __launch_bounds__((XGeom<MH>::THREADS)) void k_iterate_x(
     const Planes R0 = planes_of(R0b + poff, plane);
     const Planes R1 = planes_of(R1b + poff, plane);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef NSOF_X_TIMING
-    const bool xt = pair == 0 && strip == 1;
-#else
-    const bool xt = false;
-#endif
     volatile lds_int* sflag = (volatile lds_int*)(job + 2);
     if (wave < G::NCW) {
         float2* Fout = reinterpret_cast<float2*>(flow_out) + (HET ? 0 : (size_t)pair * plane);
-#ifdef NSOF_X_JOBLOG
-        x_consumer_loop<MH>(ring, sv, vinit, sflag, Fout, fpitch, W, H, x0, tid, nimg, 1. / (block_size * block_size), strip == 0, xt, xjl_slot);
-        if (tid == 0 && xjl_slot < 8192u) g_xjob[4 * xjl_slot + 2] = __builtin_amdgcn_s_memrealtime();
-#else
-        x_consumer_loop<MH>(ring, sv, vinit, sflag, Fout, fpitch, W, H, x0, tid, nimg, 1. / (block_size * block_size), strip == 0, xt);
-#endif
+        x_consumer_loop<MH>(ring, sv, vinit, sflag, Fout, fpitch, W, H, x0, tid, nimg, 1. / (block_size * block_size), strip == 0);
     } else if (wave == G::WAVES - 1) {
         float2* Fout = reinterpret_cast<float2*>(flow_out) + (HET ? 0 : (size_t)pair * plane);
-        x_solver_loop<MH>(sv, sflag, Fout, fpitch, W, H, x0, nimg, 1. / (block_size * block_size), tid & 63, xt);
+        x_solver_loop<MH>(sv, sflag, Fout, fpitch, W, H, x0, nimg, 1. / (block_size * block_size), tid & 63);
     } else if (wave == G::NCW) {
         const int ncols = min(G::SEG0, (W - x0 + 7) & ~7);   // columns of the left segment
-        x_scanner_loop<MH>(sv, vinit, cb, strip > 0, nimg, ncols, tid & 63, xt);
+        x_scanner_loop<MH>(sv, vinit, cb, strip > 0, nimg, ncols, tid & 63);
     } else {
         // producers: waves NCW+1 .. NCW+NB rows 0,1 of blocks 0..NB-1; wave NCW+NB+1 the remainder; then rows 2,3
         const int pw = wave - (G::NCW + 1);
@@ -873,24 +734,10 @@ __global__ __launch_bounds__((XGeom<MH>::THREADS)) void k_iterate_x(
         FlowSrc<false> F;
         F.base = reinterpret_cast<const char*>(flow_in) + (HET ? 0 : (size_t)pair * plane * 8);
         F.W = (unsigned)W;
-        // wave -> role.  Waves go to SIMD (wave % 4).  NSOF_X_WAVEMAP=1: the light I/O wave shares SIMD 1 with the middle
-        // consumer wave (the one that publishes both halves, the longest of a step) and a rows-2,3 producer moves next to
-        // the scanner on SIMD 3: waves 4-6 rows 0,1 of blocks 0-2; 7 rows 2,3 of block 1; 8 rows 2,3 of block 0; 9 I/O; 10
-        // rows 2,3 of block 2.  Default (0): 4-6 rows 0,1; 7 I/O; 8-10 rows 2,3.
-#ifndef NSOF_X_WAVEMAP
-#define NSOF_X_WAVEMAP 0
-#endif
-        bool is_io;
-        int gp, blk;
-        if (NSOF_X_WAVEMAP == 1) {
-            is_io = pw == 5;
-            gp = pw < 3 ? 0 : 1;
-            blk = pw < 3 ? pw : (pw == 3 ? 1 : (pw == 4 ? 0 : 2));
-        } else {
-            is_io = pw == G::NB;
-            gp = pw < G::NB ? 0 : 1;
-            blk = pw < G::NB ? pw : pw - G::NB - 1;
-        }
+        // wave -> role.  Waves go to SIMD (wave % 4): 4-6 rows 0,1 of blocks 0-2; 7 I/O; 8-10 rows 2,3 of blocks 0-2.
+        const bool is_io = pw == G::NB;
+        const int gp = pw < G::NB ? 0 : 1;
+        const int blk = pw < G::NB ? pw : pw - G::NB - 1;
         if (is_io) {
             const int col = G::NB * 64 + (lane & 15), r = lane >> 4;
             const int xc = clampi(x0 - MH - 1 + col, 0, W - 1);
@@ -900,16 +747,16 @@ __global__ __launch_bounds__((XGeom<MH>::THREADS)) void k_iterate_x(
             // NSOF_OPT_DEBUG_FAULT bit 0 (test hook): strip 0 of item 0 keeps its carries to itself
             gu64* cout = x0 + SW < W && !((fault & 1) && pair == 0 && strip == 0) ? cbase + (size_t)strip * per_strip : nullptr;
             float2* Fout = reinterpret_cast<float2*>(flow_out) + (HET ? 0 : (size_t)pair * plane);
-            x_remainder_loop<MH>(ring, cb, R0, R1, F, W, H, xc, col, r, nimg, cin, cout, epoch, (gu32*)err, xt, sv, sflag + 1, Fout, fpitch,
+            x_remainder_loop<MH>(ring, cb, R0, R1, F, W, H, xc, col, r, nimg, cin, cout, epoch, (gu32*)err, sv, sflag + 1, Fout, fpitch,
                                  x0, 1. / (block_size * block_size));
         } else {
             const int col = blk * 64 + lane;
             const int xc = clampi(x0 - MH - 1 + col, 0, W - 1);
             F.xc = (unsigned)xc;
             if (gp == 0)
-                x_producer_loop<MH, 0>(ring, R0, R1, F, W, H, xc, col, nimg, xt && blk == 0);
+                x_producer_loop<MH, 0>(ring, R0, R1, F, W, H, xc, col, nimg);
             else
-                x_producer_loop<MH, 1>(ring, R0, R1, F, W, H, xc, col, nimg, xt && blk == 0);
+                x_producer_loop<MH, 1>(ring, R0, R1, F, W, H, xc, col, nimg);
         }
     }
 }

@@ -357,10 +357,7 @@ __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdi
         fetch(r, q);
         filt(q, dstrow);
     };
-#ifndef NSOF_DECIM_PF
-#define NSOF_DECIM_PF 4
-#endif
-    constexpr bool PF = S <= (kU8<T> ? NSOF_DECIM_PF : 2);   // prefetch one output row ahead
+    constexpr bool PF = S <= (kU8<T> ? 4 : 2);   // prefetch one output row ahead
 
     // relative row index rel = r - base, base = first row needed by output row dy0; slot = rel % RING
     const int base = S * dy0 + S / 2 - 1 - R;

@@ -223,7 +223,6 @@ int nsof_stream_sync_checked(nsof_ctx* ctx);
 // Outputs that are not re-read before the caches have turned over (pyramid images, R, flow fields of a batch) are
 // written with non-temporal stores: measured on MI355X, the flow resample kernel goes from 3.5 to 6.2 TB/s and the
 // level-0 pyramid kernel from 3.7 to 4.4 TB/s (plain stores write-allocate in L2 and evict what the gathers reuse).
-// NSOF_PLAIN_STORES builds the plain-store variant for A/B runs.
 #ifdef __HIPCC__
 typedef float nsof_f4v __attribute__((ext_vector_type(4)));
 typedef float nsof_f2v __attribute__((ext_vector_type(2)));
@@ -245,19 +244,11 @@ __device__ __forceinline__ double nsof_recip_normal(double x)
 
 __device__ __forceinline__ void nsof_store_stream4(float* p, float a, float b, float c, float d)
 {
-#ifndef NSOF_PLAIN_STORES
     __builtin_nontemporal_store((nsof_f4v){a, b, c, d}, reinterpret_cast<nsof_f4v*>(p));
-#else
-    *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
-#endif
 }
 // (Non-temporal LOADS of the once-read inputs of the iteration kernel were measured too: 3 % slower.)
 __device__ __forceinline__ void nsof_store_stream2(float* p, float a, float b)
 {
-#ifndef NSOF_PLAIN_STORES
     __builtin_nontemporal_store((nsof_f2v){a, b}, reinterpret_cast<nsof_f2v*>(p));
-#else
-    *reinterpret_cast<float2*>(p) = make_float2(a, b);
-#endif
 }
 #endif

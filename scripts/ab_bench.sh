@@ -1,6 +1,7 @@
 #!/bin/bash
-# A/B of libnsof variants (scripts/build_variant.sh) on the HEADLINE bench itself (256 pairs 1080p, all levels, real pyramid
-# flow), alternating the variants REPS times on the same box: box-to-box spread (+-3 %) is larger than most kernel changes.
+# A/B of libnsof variants (any nsof/libnsof_<name>.so, e.g. scripts/build_flags.sh) on the HEADLINE bench itself (256 pairs
+# 1080p, all levels, real pyramid flow), alternating the variants REPS times on the same box: box-to-box spread (+-3 %) is
+# larger than most kernel changes.
 #   bash scripts/ab_bench.sh base old c1i1 ...      (AB_PARAMS=A|B|C, AB_REPS=2)
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1

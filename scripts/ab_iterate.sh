@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B timing of libnsof variants (scripts/build_variant.sh) on the fused iteration stage.
+# A/B timing of libnsof variants (any nsof/libnsof_<name>.so, e.g. scripts/build_flags.sh) on the fused iteration stage.
 #   bash scripts/ab_iterate.sh name1 name2 ...     name = lib variant ("base" = the product library), optionally
 #   followed by +ENV=VALUE pairs, e.g.  base+NSOF_ROW_BANDS=1
 REPO=$(cd "$(dirname "$0")/.." && pwd)

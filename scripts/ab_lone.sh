@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of libnsof variants (scripts/build_variant.sh) on lone calls: iterate milliseconds of scripts/latency_single.py per variant.
+# A/B of libnsof variants (any nsof/libnsof_<name>.so, e.g. scripts/build_flags.sh) on lone calls: iterate milliseconds of scripts/latency_single.py per variant.
 #   SHAPES=0 bash scripts/ab_lone.sh base v1 v2 ...
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1 BANDS=0

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B timing of libnsof variants (scripts/build_variant.sh) on the exact-order iteration stage: prints the exact-mode launch time
+# A/B timing of libnsof variants (any nsof/libnsof_<name>.so, e.g. scripts/build_flags.sh) on the exact-order iteration stage: prints the exact-mode launch time
 # of scripts/x_check.py for each variant ("base" = the product library).   bash scripts/ab_x.sh base v1 v2 ...
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 export NSOF_SKIP_BUILD=1
