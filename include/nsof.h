@@ -144,7 +144,8 @@ int nsof_farneback_u8_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d
  * element are fine; the pyramid kernels take their vector loads where rows are 16-byte aligned and scalar loads
  * elsewhere).  Other argument checks, the flow layout, the host staging and the synchronisation are those of the
  * 8-bit twins.  A float frame holding the values of an 8-bit frame gives the 8-bit entry's flow bit for bit.  The
- * frames must be finite (the Python layer checks); work lists (nsof_pair_desc) stay 8-bit. */
+ * frames must be finite (the Python layer checks).  The work lists have float twins too (nsof_pair_desc_f32 and
+ * nsof_farneback_f32_batch* / nsof_farneback_f32_roi_sequence_dev below). */
 int nsof_farneback_f32(nsof_ctx* ctx,
                        const float* prev, ptrdiff_t prev_stride,
                        const float* next, ptrdiff_t next_stride,
@@ -210,7 +211,38 @@ int nsof_farneback_u8_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_
                                        const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale, int levels,
                                        int winsize, int iterations, int poly_n, double poly_sigma, int flags,
                                        int gate_frame, long long* n_calls, long long* n_pixels);
-/* Page-locked host memory for frames / flow fields handed to nsof_farneback_u8_batch (NULL on failure). */
+/* Float32 frames in work lists: the three entries above for float32 single-channel frames.  nsof_pair_desc_f32 has the
+ * fields of nsof_pair_desc in the same order; every stride stays in BYTES.  Layout rules are those of
+ * nsof_farneback_f32: frame pointers 4-byte aligned, row strides multiples of 4 and at least 4*width (for the ROI
+ * sequence: row_stride and frame_stride multiples of 4); a violation returns NSOF_EINVAL before anything is launched.
+ * A list holds one pixel type.  Results per pair == nsof_farneback_f32 of that pair, bit for bit, in the default mode;
+ * float frames holding 8-bit values give the 8-bit entries' flow bit for bit.  The frames must be finite (the Python
+ * layer checks).  Items start 16-byte aligned with row strides that are multiples of 16 and W % 4 == 0 take the vector
+ * form of the level-0 pyramid kernel, the others its scalar form; the result does not depend on it. */
+typedef struct nsof_pair_desc_f32 {
+    const float* prev;
+    ptrdiff_t prev_stride;
+    const float* next;
+    ptrdiff_t next_stride;
+    int width, height;
+    float* flow;
+    ptrdiff_t flow_stride;
+} nsof_pair_desc_f32;
+int nsof_farneback_f32_batch(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc_f32* pairs,
+                             double pyr_scale, int levels, int winsize, int iterations,
+                             int poly_n, double poly_sigma, int flags);
+int nsof_farneback_f32_batch_desc_dev(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc_f32* pairs,
+                                      double pyr_scale, int levels, int winsize, int iterations,
+                                      int poly_n, double poly_sigma, int flags);
+/* d_frames: n_frames float32 frames in HBM, row_stride / frame_stride in bytes; everything else as
+ * nsof_farneback_u8_roi_sequence_dev (each crop's flow == nsof_farneback_f32 of that crop, bit for bit). */
+int nsof_farneback_f32_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_frames, ptrdiff_t row_stride,
+                                        ptrdiff_t frame_stride, int width, int height, const int32_t* d_counts,
+                                        const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale, int levels,
+                                        int winsize, int iterations, int poly_n, double poly_sigma, int flags,
+                                        int gate_frame, long long* n_calls, long long* n_pixels);
+/* Page-locked host memory for frames / flow fields handed to nsof_farneback_u8_batch / nsof_farneback_f32_batch (NULL on
+ * failure). */
 void* nsof_host_alloc(size_t bytes);
 void nsof_host_free(void* p);
 

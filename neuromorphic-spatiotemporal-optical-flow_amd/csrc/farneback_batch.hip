@@ -11,6 +11,9 @@
 //     canvas without a paste.  Arithmetic per item is that of the per-call path, bit for bit.
 //   * nsof_farneback_u8_batch: the same for HOST memory, as a three-stage pipeline over chunks of the list
 //     (upload of chunk c+1 and download of chunk c-1 on their own streams while chunk c computes).
+//   * nsof_farneback_f32_*: the same three entries for float32 frames.  Only the pyramid stage reads frames, so a list
+//     differs from an 8-bit one in its pixel size (Params::src) alone: byte addresses and byte strides throughout,
+//     the float instantiations of the pyramid kernels, and level 0 in the two-kernel form (prep, then expansion).
 #include <sched.h>
 
 #include <algorithm>
@@ -32,6 +35,8 @@ struct Params {
     int levels, winsize, iterations, poly_n;
     double poly_sigma;
     int flags;
+    int src = NSOF_SRC_U8;   // nsof_src_type of every frame of the list
+    size_t px() const { return src == NSOF_SRC_F32 ? 4 : 1; }   // bytes per pixel
 };
 
 int validate_desc(nsof_ctx* ctx, int i, const nsof_pair_desc& d, const Params& p)
@@ -40,7 +45,14 @@ int validate_desc(nsof_ctx* ctx, int i, const nsof_pair_desc& d, const Params& p
     int rc = nsof_check_farneback_params(ctx, d.width, d.height, p.pyr_scale, p.levels, p.winsize, p.iterations, p.poly_n,
                                          p.flags);
     if (rc) return rc;
-    if (d.prev_stride < d.width || d.next_stride < d.width)
+    if (p.src == NSOF_SRC_F32) {   // the layout rules of nsof_farneback_f32
+        if ((reinterpret_cast<uintptr_t>(d.prev) & 3) || (reinterpret_cast<uintptr_t>(d.next) & 3))
+            return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: f32 frames must be 4-byte aligned", i);
+        if ((d.prev_stride & 3) || (d.next_stride & 3) || d.prev_stride < (ptrdiff_t)d.width * 4 ||
+            d.next_stride < (ptrdiff_t)d.width * 4)
+            return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: f32 row strides %td / %td must be multiples of 4 and >= 4*width",
+                                  i, d.prev_stride, d.next_stride);
+    } else if (d.prev_stride < d.width || d.next_stride < d.width)
         return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: row stride < width", i);
     if (d.flow_stride < (ptrdiff_t)d.width * 8 || (d.flow_stride & 7) || (reinterpret_cast<uintptr_t>(d.flow) & 7))
         return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: flow stride %lld / pointer must be multiples of 8 bytes and "
@@ -52,17 +64,17 @@ int validate_desc(nsof_ctx* ctx, int i, const nsof_pair_desc& d, const Params& p
 // packed densely, the result is copied into the caller's strided field.
 int fallback_item(nsof_ctx* ctx, const nsof_pair_desc& d, const Params& p)
 {
-    const size_t n0 = (size_t)d.width * d.height;
-    const size_t szU = align_up(n0, 256), szF = align_up(n0 * 8, 256);
+    const size_t n0 = (size_t)d.width * d.height, row = (size_t)d.width * p.px();
+    const size_t szU = align_up(n0 * p.px(), 256), szF = align_up(n0 * 8, 256);
     int rc = nsof_ws_reserve(ctx, &ctx->stage, &ctx->stage_bytes, 2 * szU + szF);
     if (rc) return rc;
     uint8_t* dP = (uint8_t*)ctx->stage;
     uint8_t* dN = dP + szU;
     float* dF = (float*)(dN + szU);
-    NSOF_HIP(ctx, hipMemcpy2DAsync(dP, d.width, d.prev, d.prev_stride, d.width, d.height, hipMemcpyDeviceToDevice, ctx->stream));
-    NSOF_HIP(ctx, hipMemcpy2DAsync(dN, d.width, d.next, d.next_stride, d.width, d.height, hipMemcpyDeviceToDevice, ctx->stream));
-    rc = nsof_farneback_core(ctx, false, 1, dP, dN, d.width, (ptrdiff_t)szU, d.width, d.height, dF, p.pyr_scale, p.levels,
-                             p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags);
+    NSOF_HIP(ctx, hipMemcpy2DAsync(dP, row, d.prev, d.prev_stride, row, d.height, hipMemcpyDeviceToDevice, ctx->stream));
+    NSOF_HIP(ctx, hipMemcpy2DAsync(dN, row, d.next, d.next_stride, row, d.height, hipMemcpyDeviceToDevice, ctx->stream));
+    rc = nsof_farneback_core(ctx, false, 1, dP, dN, (ptrdiff_t)row, (ptrdiff_t)szU, d.width, d.height, dF, p.pyr_scale, p.levels,
+                             p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags, p.src);
     if (rc) return rc;
     NSOF_HIP(ctx, hipMemcpy2DAsync(d.flow, d.flow_stride, dF, (size_t)d.width * 8, (size_t)d.width * 8, d.height,
                                    hipMemcpyDeviceToDevice, ctx->stream));
@@ -172,7 +184,7 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
         }
         if (uniform)
             return nsof_farneback_core(ctx, false, n, d0.prev, d0.next, d0.prev_stride, ps, d0.width, d0.height, d0.flow,
-                                       p.pyr_scale, p.levels, p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags);
+                                       p.pyr_scale, p.levels, p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags, p.src);
     }
 
     // Items the work-list kernels cover: fused iteration available (window 2..15, >= 1 iteration, at least 2x2 px), and
@@ -268,8 +280,9 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
                 it.offI = oI; it.offR = oR; it.offF = oF; it.offFc = offF_prev[j];
                 oI += align_up(2 * nk, 64); oR += align_up(10 * nk, 64); oF += align_up(nk, 32);
                 offF_prev[j] = it.offF;
-                const bool vec = (d.width & 3) == 0 && d.width >= 8 && (d.prev_stride & 3) == 0 && (d.next_stride & 3) == 0 &&
-                                 (reinterpret_cast<uintptr_t>(d.prev) & 3) == 0 && (reinterpret_cast<uintptr_t>(d.next) & 3) == 0;
+                const uintptr_t va = p.src == NSOF_SRC_F32 ? 15 : 3;   // k_prep_same3_vec's row loads: 16 B (f32) / 4 B (u8)
+                const bool vec = (d.width & 3) == 0 && d.width >= 8 && (d.prev_stride & va) == 0 && (d.next_stride & va) == 0 &&
+                                 (reinterpret_cast<uintptr_t>(d.prev) & va) == 0 && (reinterpret_cast<uintptr_t>(d.next) & va) == 0;
                 it.flags = vec ? NSOF_HET_VEC0 : 0;
                 max_w[k] = std::max(max_w[k], it.wk);
                 max_h[k] = std::max(max_h[k], it.hk);
@@ -314,10 +327,12 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
                 if ((rc = NSOF_PYR_SEL(ctx, nsof_launch_flow_upsample_het, c.count, dt + c.start, c.max_w, c.max_h, fb[cur],
                                        fb[cur ^ 1], (float)(1. / p.pyr_scale))))
                     return rc;
-                // level 0: the expansion kernel forms the level image from the frames itself (see nsof_farneback_core)
-                const bool u8 = k == 0 && btaps.ksize == 3 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32;
+                // level 0: the expansion kernel forms the level image from the 8-bit frames itself (see nsof_farneback_core);
+                // float frames take the two-kernel form
+                const bool u8 = k == 0 && btaps.ksize == 3 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && p.src == NSOF_SRC_U8;
                 const float blur3[2] = {btaps.k[1], btaps.k[2]};
-                if (!u8 && (rc = NSOF_PYR_SEL(ctx, nsof_launch_prep_het, c.count, dt + c.start, ht + c.start, k == 0, btaps, dI))) return rc;
+                if (!u8 && (rc = NSOF_PYR_SEL(ctx, nsof_launch_prep_het, c.count, dt + c.start, ht + c.start, k == 0, btaps, dI, p.src)))
+                    return rc;
                 if ((rc = nsof_launch_polyexp_het(ctx, c.count, dt + c.start, c.max_w, c.max_h, ptaps, dI, dR, u8 ? blur3 : nullptr))) return rc;
             }
             cur ^= 1;
@@ -562,15 +577,13 @@ __global__ __launch_bounds__(256) void k_paste_ordered(const PasteRec* __restric
 // canvases in place; a crop that overlaps an earlier crop of its pair (FLAG 1, extended component boxes) is computed into
 // a private buffer and pasted afterwards, in label order, as the reference's loop overwrites.  The only traffic over
 // PCIe is the rectangle table (16 bytes per ROI): the work list's shapes are needed on the host.
-extern "C" int nsof_farneback_u8_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, ptrdiff_t row_stride,
-                                                  ptrdiff_t frame_stride, int width, int height, const int32_t* d_counts,
-                                                  const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale,
-                                                  int levels, int winsize, int iterations, int poly_n, double poly_sigma,
-                                                  int flags, int gate_frame, long long* n_calls, long long* n_pixels)
+// p.src: the frames' pixel type (the crops' byte addresses and the row stride check follow its size).
+static int roi_sequence(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, ptrdiff_t row_stride, ptrdiff_t frame_stride,
+                        int width, int height, const int32_t* d_counts, const int32_t* d_rects, int max_rects, float* d_flows,
+                        const Params& p, int gate_frame, long long* n_calls, long long* n_pixels)
 {
-    if (!ctx) return NSOF_EINVAL;
     if (!d_frames || !d_counts || !d_rects || !d_flows || n_frames < 2 || max_rects < 1 || width < 1 || height < 1 ||
-        row_stride < width || (gate_frame != 0 && gate_frame != 1))
+        row_stride < (ptrdiff_t)(width * p.px()) || (gate_frame != 0 && gate_frame != 1))
         return nsof_set_error(ctx, NSOF_EINVAL, "roi_sequence: bad argument");
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const size_t canvas = (size_t)width * height * 2;   // floats per pair
@@ -600,8 +613,8 @@ extern "C" int nsof_farneback_u8_roi_sequence_dev(nsof_ctx* ctx, int n_frames, c
                 overlap = a1 > a0 && b1 > b0 && x0 < a1 && a0 < x1 && y0 < b1 && b0 < y1;
             }
             nsof_pair_desc d;
-            d.prev = d_frames + (size_t)k * frame_stride + (size_t)y0 * row_stride + x0;
-            d.next = d_frames + (size_t)(k + 1) * frame_stride + (size_t)y0 * row_stride + x0;
+            d.prev = d_frames + (size_t)k * frame_stride + (size_t)y0 * row_stride + x0 * p.px();
+            d.next = d_frames + (size_t)(k + 1) * frame_stride + (size_t)y0 * row_stride + x0 * p.px();
             d.prev_stride = d.next_stride = row_stride;
             d.width = x1 - x0;
             d.height = y1 - y0;
@@ -628,7 +641,6 @@ extern "C" int nsof_farneback_u8_roi_sequence_dev(nsof_ctx* ctx, int n_frames, c
         for (size_t i : tmp_slot)
             descs[i].flow = reinterpret_cast<float*>((char*)ctx->roi_tmp + reinterpret_cast<uintptr_t>(descs[i].flow));
     }
-    const Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
     for (size_t i = 0; i < descs.size(); i += 32767) {
         const int n = (int)std::min<size_t>(32767, descs.size() - i);
         if (int rc = het_core(ctx, n, descs.data() + i, p)) return rc;
@@ -664,13 +676,39 @@ extern "C" int nsof_farneback_u8_roi_sequence_dev(nsof_ctx* ctx, int n_frames, c
     return NSOF_OK;
 }
 
-extern "C" int nsof_farneback_u8_batch(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, double pyr_scale,
-                                       int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags)
+extern "C" int nsof_farneback_u8_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, ptrdiff_t row_stride,
+                                                  ptrdiff_t frame_stride, int width, int height, const int32_t* d_counts,
+                                                  const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale,
+                                                  int levels, int winsize, int iterations, int poly_n, double poly_sigma,
+                                                  int flags, int gate_frame, long long* n_calls, long long* n_pixels)
 {
     if (!ctx) return NSOF_EINVAL;
-    if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return nsof_set_error(ctx, NSOF_EINVAL, "bad pair list");
-    if (n_pairs == 0) return NSOF_OK;
     const Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
+    return roi_sequence(ctx, n_frames, d_frames, row_stride, frame_stride, width, height, d_counts, d_rects, max_rects, d_flows,
+                        p, gate_frame, n_calls, n_pixels);
+}
+
+extern "C" int nsof_farneback_f32_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_frames, ptrdiff_t row_stride,
+                                                   ptrdiff_t frame_stride, int width, int height, const int32_t* d_counts,
+                                                   const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale,
+                                                   int levels, int winsize, int iterations, int poly_n, double poly_sigma,
+                                                   int flags, int gate_frame, long long* n_calls, long long* n_pixels)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_frames) & 3) || (row_stride & 3) || (frame_stride & 3))
+        return nsof_set_error(ctx, NSOF_EINVAL, "roi_sequence: f32 frames must be 4-byte aligned and row_stride=%td / "
+                              "frame_stride=%td multiples of 4", row_stride, frame_stride);
+    Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
+    p.src = NSOF_SRC_F32;
+    return roi_sequence(ctx, n_frames, reinterpret_cast<const uint8_t*>(d_frames), row_stride, frame_stride, width, height,
+                        d_counts, d_rects, max_rects, d_flows, p, gate_frame, n_calls, n_pixels);
+}
+
+namespace {
+
+// The pipelined host entry of both pixel types (pairs: HOST pointers; p.src gives the pixel size).
+int batch_host(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, const Params& p)
+{
     for (int i = 0; i < n_pairs; i++)
         if (int rc = validate_desc(ctx, i, pairs[i], p)) return rc;
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
@@ -697,7 +735,7 @@ extern "C" int nsof_farneback_u8_batch(nsof_ctx* ctx, int n_pairs, const nsof_pa
         c.lo = i;
         while (i < n_pairs && (i == c.lo || (c.out_bytes < budget && i - c.lo < 8192))) {
             const size_t n0 = (size_t)pairs[i].width * pairs[i].height;
-            for (int f = 0; f < 2; f++) { c.in_off[f].push_back(c.in_bytes); c.in_bytes += align_up(n0, 256); }
+            for (int f = 0; f < 2; f++) { c.in_off[f].push_back(c.in_bytes); c.in_bytes += align_up(n0 * p.px(), 256); }
             c.out_off.push_back(c.out_bytes);
             c.out_bytes += align_up(n0 * 8, 256);
             i++;
@@ -708,8 +746,8 @@ extern "C" int nsof_farneback_u8_batch(nsof_ctx* ctx, int n_pairs, const nsof_pa
     std::vector<char> pin_in(2 * (size_t)n_pairs), pin_out(n_pairs);
     for (int i = 0; i < n_pairs; i++) {
         const nsof_pair_desc& d = pairs[i];
-        pin_in[2 * i] = d.prev_stride == d.width && is_pinned(d.prev);
-        pin_in[2 * i + 1] = d.next_stride == d.width && is_pinned(d.next);
+        pin_in[2 * i] = d.prev_stride == (ptrdiff_t)(d.width * p.px()) && is_pinned(d.prev);
+        pin_in[2 * i + 1] = d.next_stride == (ptrdiff_t)(d.width * p.px()) && is_pinned(d.next);
         pin_out[i] = d.flow_stride == (ptrdiff_t)d.width * 8 && is_pinned(d.flow);
     }
 
@@ -803,10 +841,11 @@ extern "C" int nsof_farneback_u8_batch(nsof_ctx* ctx, int n_pairs, const nsof_pa
             const ptrdiff_t st = f ? d.next_stride : d.prev_stride;
             uint8_t* dst = (uint8_t*)s.h_in + c.in_off[f][i - c.lo];
             const int y1 = std::min(y0 + 128, d.height);
-            if (st == (ptrdiff_t)d.width) {
-                memcpy(dst + (size_t)y0 * d.width, src + (ptrdiff_t)y0 * st, (size_t)(y1 - y0) * d.width);
+            const size_t row = (size_t)d.width * p.px();   // bytes of a packed row
+            if (st == (ptrdiff_t)row) {
+                memcpy(dst + (size_t)y0 * row, src + (ptrdiff_t)y0 * st, (size_t)(y1 - y0) * row);
             } else {
-                for (int y = y0; y < y1; y++) memcpy(dst + (size_t)y * d.width, src + (ptrdiff_t)y * st, (size_t)d.width);
+                for (int y = y0; y < y1; y++) memcpy(dst + (size_t)y * row, src + (ptrdiff_t)y * st, row);
             }
         });
         if (trace) thost[ci][1] = now_ms() - t_call;
@@ -819,7 +858,7 @@ extern "C" int nsof_farneback_u8_batch(nsof_ctx* ctx, int n_pairs, const nsof_pa
         } else {
             for (int i = c.lo; i < c.hi; i++)
                 for (int f = 0; f < 2; f++) {
-                    const size_t off = c.in_off[f][i - c.lo], n0 = (size_t)pairs[i].width * pairs[i].height;
+                    const size_t off = c.in_off[f][i - c.lo], n0 = (size_t)pairs[i].width * pairs[i].height * p.px();
                     const void* src = pin_in[2 * i + f] ? (const void*)(f ? pairs[i].next : pairs[i].prev)
                                                         : (const void*)((char*)s.h_in + off);
                     NSOF_HIP(ctx, hipMemcpyAsync((char*)s.d_in + off, src, n0, hipMemcpyHostToDevice, pp->s_in));
@@ -835,7 +874,7 @@ extern "C" int nsof_farneback_u8_batch(nsof_ctx* ctx, int n_pairs, const nsof_pa
             nsof_pair_desc& d = dd[i - c.lo];
             d.prev = (const uint8_t*)s.d_in + c.in_off[0][i - c.lo];
             d.next = (const uint8_t*)s.d_in + c.in_off[1][i - c.lo];
-            d.prev_stride = d.next_stride = pairs[i].width;
+            d.prev_stride = d.next_stride = (ptrdiff_t)(pairs[i].width * p.px());
             d.width = pairs[i].width;
             d.height = pairs[i].height;
             d.flow = (float*)((char*)s.d_out + c.out_off[i - c.lo]);
@@ -889,6 +928,56 @@ extern "C" int nsof_farneback_u8_batch(nsof_ctx* ctx, int n_pairs, const nsof_pa
     }
     drain.ok = true;
     return NSOF_OK;
+}
+
+// nsof_pair_desc_f32 -> the driver's byte-address descriptor (same fields, same order)
+std::vector<nsof_pair_desc> f32_descs(int n, const nsof_pair_desc_f32* pairs)
+{
+    std::vector<nsof_pair_desc> out(n);
+    for (int i = 0; i < n; i++) {
+        const nsof_pair_desc_f32& s = pairs[i];
+        out[i] = nsof_pair_desc{reinterpret_cast<const uint8_t*>(s.prev), s.prev_stride, reinterpret_cast<const uint8_t*>(s.next),
+                                s.next_stride, s.width, s.height, s.flow, s.flow_stride};
+    }
+    return out;
+}
+
+}  // namespace
+
+extern "C" int nsof_farneback_u8_batch(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, double pyr_scale,
+                                       int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return nsof_set_error(ctx, NSOF_EINVAL, "bad pair list");
+    if (n_pairs == 0) return NSOF_OK;
+    const Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
+    return batch_host(ctx, n_pairs, pairs, p);
+}
+
+extern "C" int nsof_farneback_f32_batch(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc_f32* pairs, double pyr_scale,
+                                        int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return nsof_set_error(ctx, NSOF_EINVAL, "bad pair list");
+    if (n_pairs == 0) return NSOF_OK;
+    Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
+    p.src = NSOF_SRC_F32;
+    const std::vector<nsof_pair_desc> d = f32_descs(n_pairs, pairs);
+    return batch_host(ctx, n_pairs, d.data(), p);
+}
+
+extern "C" int nsof_farneback_f32_batch_desc_dev(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc_f32* pairs, double pyr_scale,
+                                                 int levels, int winsize, int iterations, int poly_n, double poly_sigma,
+                                                 int flags)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return nsof_set_error(ctx, NSOF_EINVAL, "bad pair list");
+    if (n_pairs > 32767) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "n_pairs=%d exceeds 32767 per call", n_pairs);
+    if (n_pairs == 0) return NSOF_OK;
+    Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
+    p.src = NSOF_SRC_F32;
+    const std::vector<nsof_pair_desc> d = f32_descs(n_pairs, pairs);
+    return het_core(ctx, n_pairs, d.data(), p);
 }
 
 extern "C" void* nsof_host_alloc(size_t bytes)

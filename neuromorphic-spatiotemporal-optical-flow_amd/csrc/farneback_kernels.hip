@@ -123,14 +123,13 @@ __device__ __forceinline__ bool prep_geom(PrepImg<T>& g, const T* src, ptrdiff_t
                                           int& W, int& H, int& wk, int& hk, float* out,
                                           const nsof_het_item* __restrict__ items, int want_flag)
 {
-    if constexpr (HET) {   // (work lists are 8-bit only)
-        static_assert(kU8<T>, "work-list items carry 8-bit frames");
+    if constexpr (HET) {   // (a list's frames are all of one pixel type, the launch's T)
         const nsof_het_item& it = items[blockIdx.z >> 1];
         const int which = blockIdx.z & 1;
         if (want_flag >= 0 && (it.flags & NSOF_HET_VEC0) != want_flag) return false;
         W = it.W; H = it.H; wk = it.wk; hk = it.hk;
         row_stride = (ptrdiff_t)it.src_stride[which];
-        g.img = it.src[which];
+        g.img = reinterpret_cast<const T*>(it.src[which]);
         g.dst = out + it.offI + (size_t)which * wk * hk;
     } else {
         g.img = srow(src, blockIdx.z, img_stride);
@@ -2222,8 +2221,12 @@ int NSOF_PYR_NAME(nsof_launch_flow_upsample)(nsof_ctx* ctx, int n_pairs, const f
 // =========================================================================================
 // work-list (shape-heterogeneous) launchers: one launch per stage and level over a device table
 // =========================================================================================
-int NSOF_PYR_NAME(nsof_launch_prep_het)(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items,
-                         bool level0, const nsof_blur_taps& taps, float* I)
+namespace {
+// T: the pixel type of every item's frames (the list's src_type).  Kernel choice as for 8-bit items; with float frames
+// NSOF_HET_VEC0 means 16-byte aligned rows (k_prep_same3_vec's float4 loads), the scalar k_prep_same takes the rest.
+template <typename T>
+int prep_het_impl(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items, bool level0,
+                  const nsof_blur_taps& taps, float* I)
 {
     nsof_prof_scope ps(ctx, NSOF_K_PREP);
     int max_wk = 0, max_hk = 0, n_vec = 0;
@@ -2241,12 +2244,12 @@ int NSOF_PYR_NAME(nsof_launch_prep_het)(nsof_ctx* ctx, int n_items, const nsof_h
     if (level0) {   // same-size level: 3 taps; aligned items take the vector kernel, the others the generic one
         if (taps.ksize == 3 && n_vec > 0) {
             dim3 grid((max_wk / 4 + 63) / 64, (max_hk + 4 * PREP0_ROWS - 1) / (4 * PREP0_ROWS), nz);
-            hipLaunchKernelGGL((k_prep_same3_vec<true, uint8_t>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps.k[1],
+            hipLaunchKernelGGL((k_prep_same3_vec<true, T>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps.k[1],
                                taps.k[2], I, d_items);
         }
         if (taps.ksize != 3 || n_vec < n_items) {
             dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
-            hipLaunchKernelGGL((k_prep_same<true, uint8_t>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps, I, d_items,
+            hipLaunchKernelGGL((k_prep_same<true, T>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps, I, d_items,
                                taps.ksize == 3 ? 0 : -1);
         }
     } else {
@@ -2254,19 +2257,19 @@ int NSOF_PYR_NAME(nsof_launch_prep_het)(nsof_ctx* ctx, int n_items, const nsof_h
         const int rw_cap = ((int)ceil(PREP_TW * max_sx) + 2 * r + 8 + 3) / 4 * 4;
         const int rh_cap = (int)ceil(PREP_TH * max_sy) + 2 * r + 4;
         const size_t smem = sizeof(float) * ((size_t)rh_cap * 2 * PREP_TW + 2 * PREP_TH * 2 * PREP_TW) +
-                            (size_t)rh_cap * rw_cap;
+                            (size_t)rh_cap * rw_cap * sizeof(T);
         if (taps.ksize == 3 || taps.ksize == 5) {
             dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
             if (taps.ksize == 3)
-                hipLaunchKernelGGL((k_prep_direct<3, true, uint8_t>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1.,
+                hipLaunchKernelGGL((k_prep_direct<3, true, T>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1.,
                                    1., taps, I, d_items);
             else
-                hipLaunchKernelGGL((k_prep_direct<5, true, uint8_t>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1.,
+                hipLaunchKernelGGL((k_prep_direct<5, true, T>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1.,
                                    1., taps, I, d_items);
         } else if (smem <= 60 * 1024) {
             dim3 grid((max_wk + PREP_TW - 1) / PREP_TW, (max_hk + PREP_TH - 1) / PREP_TH, nz);
 #define PREP_TILED_HET(KS)                                                                                       \
-    hipLaunchKernelGGL((k_prep_tiled<KS, true, uint8_t>), grid, dim3(256), smem, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1., \
+    hipLaunchKernelGGL((k_prep_tiled<KS, true, T>), grid, dim3(256), smem, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1., \
                        rw_cap, rh_cap, taps, I, d_items)
             switch (taps.ksize) {
                 case 9: PREP_TILED_HET(9); break;
@@ -2276,12 +2279,20 @@ int NSOF_PYR_NAME(nsof_launch_prep_het)(nsof_ctx* ctx, int n_items, const nsof_h
 #undef PREP_TILED_HET
         } else {
             dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
-            hipLaunchKernelGGL((k_prep_naive<true, uint8_t>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1.,
+            hipLaunchKernelGGL((k_prep_naive<true, T>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1.,
                                taps, I, d_items);
         }
     }
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
+}
+}  // namespace
+
+int NSOF_PYR_NAME(nsof_launch_prep_het)(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items,
+                         bool level0, const nsof_blur_taps& taps, float* I, int src_type)
+{
+    if (src_type == NSOF_SRC_F32) return prep_het_impl<float>(ctx, n_items, d_items, h_items, level0, taps, I);
+    return prep_het_impl<uint8_t>(ctx, n_items, d_items, h_items, level0, taps, I);
 }
 
 #ifndef NSOF_PYR_FMA

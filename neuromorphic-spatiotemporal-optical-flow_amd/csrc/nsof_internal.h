@@ -127,7 +127,7 @@ struct nsof_poly_taps {
 int nsof_host_blur_taps(int ksize, double sigma, nsof_blur_taps* out);
 int nsof_host_poly_taps(int n, double sigma, nsof_poly_taps* out);
 
-// ---- shape-heterogeneous work lists (nsof_farneback_u8_batch*) ------------------------------------------------
+// ---- shape-heterogeneous work lists (nsof_farneback_u8_batch*, nsof_farneback_f32_batch*) -----------------------
 // One work item (a frame pair of its own shape) at ONE pyramid level.  The host builds one table per level (items
 // that have no such level are left out) and every stage is launched once per level over the whole table:
 // gridDim.z indexes the table (x2 for the per-image stages), gridDim.x/y are sized for the largest item and the
@@ -135,7 +135,8 @@ int nsof_host_poly_taps(int n, double sigma, nsof_poly_taps* out);
 // buffers: I (level images, f32; prev at offI, next at offI + wk*hk), R (expansions, f32; R0 at offR, R1 at
 // offR + 5*wk*hk), flow (float2; this level at offF, the coarser level's field at offFc).
 struct nsof_het_item {
-    const uint8_t* src[2];       // full-resolution u8 frames (prev, next), device memory
+    const uint8_t* src[2];       // full-resolution frames (prev, next), device BYTE addresses: 8-bit or float pixels,
+                                 // one type per list (the launch's src_type)
     long long src_stride[2];     // their row strides in bytes
     float* out;                  // the caller's flow field of this item (written by the last iteration of level 0)
     long long out_pitch;         // its row pitch in float2 units
@@ -143,7 +144,8 @@ struct nsof_het_item {
     int W, H;                    // full resolution
     int wk, hk;                  // this level
     int pw, ph;                  // coarser level (0: the item starts here, its incoming flow is zero)
-    int flags;                   // NSOF_HET_VEC0: both frames 4-byte aligned with W % 4 == 0 (vector level-0 kernel)
+    int flags;                   // NSOF_HET_VEC0 (vector level-0 kernel), W % 4 == 0 and W >= 8 with both frames and their
+                                 // row strides 4-byte (8-bit) / 16-byte (float) aligned
     int pad_;
 };
 enum { NSOF_HET_VEC0 = 1 };
@@ -156,8 +158,9 @@ int nsof_launch_iterate_lat_het(nsof_ctx* ctx, int n_items, const nsof_het_item*
                                 const float* flow_in, float* flow_out, bool final, int winsize, float* M, double* V);
 // All launchers are asynchronous on ctx->stream and return an nsof_status.
 // The *_het twins take a device table of n_items entries; max_* are the largest extents over the table.
+// src_type (nsof_src_type): the pixel type of every item's frames.
 int nsof_launch_prep_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items,
-                         bool level0, const nsof_blur_taps& taps, float* I);
+                         bool level0, const nsof_blur_taps& taps, float* I, int src_type = NSOF_SRC_U8);
 int nsof_launch_polyexp_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
                             const nsof_poly_taps& taps, const float* I, float* R, const float* blur3 = nullptr);
 int nsof_launch_flow_upsample_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
@@ -178,7 +181,7 @@ int nsof_launch_prep_decim3(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t
 int nsof_launch_prep_decim3_fma(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride,
                                 int W, int H, const nsof_blur_taps* taps, float* const* out, int src_type = NSOF_SRC_U8);
 int nsof_launch_prep_het_fma(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items,
-                             bool level0, const nsof_blur_taps& taps, float* I);
+                             bool level0, const nsof_blur_taps& taps, float* I, int src_type = NSOF_SRC_U8);
 int nsof_launch_flow_upsample_fma(nsof_ctx* ctx, int n_pairs, const float* src, int sw, int sh, float* dst, int dw,
                                   int dh, float mul);
 int nsof_launch_flow_upsample_het_fma(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,

@@ -75,6 +75,7 @@ class Context:
         return ms.value, n.value
 
     def close(self):
+        self.__dict__.pop("_nsof_f32_stage", None)   # farneback_pairs' page-locked conversion buffer of float lists
         if getattr(self, "_p", None) is not None:
             self._lib.nsof_destroy(self._p)
             self._p = None

@@ -234,14 +234,23 @@ def pinned_empty(shape, dtype=np.float32):
     return arr
 
 
-def _desc_array(pairs, flows, host):
-    """ctypes array of nsof_pair_desc for (prev, next) pairs and their flow fields (numpy arrays or, with
-    host=False, objects exposing data_ptr()/shape/stride() like torch CUDA tensors)."""
+def _desc_array(pairs, flows, host, f32=False):
+    """ctypes array of nsof_pair_desc (nsof_pair_desc_f32 with ``f32``: the same layout) for (prev, next) pairs and their
+    flow fields (numpy arrays or, with host=False, objects exposing data_ptr()/shape/stride() like torch CUDA tensors).
+    Host float32 frames must come from ``_f32_host_frames``."""
     descs = (_lib.PairDesc * len(pairs))()
     keep = []
+    px = 4 if f32 else 1
     for i, ((prev, nxt), flow) in enumerate(zip(pairs, flows)):
         d = descs[i]
-        if host:
+        if host and f32:
+            if prev.shape != nxt.shape:
+                raise NsofValueError(f"pair {i}: prev {prev.shape} and next {nxt.shape} sizes differ", _lib.NSOF_ESHAPE)
+            keep += [prev, nxt]
+            h, w = prev.shape
+            d.prev, d.prev_stride, d.next, d.next_stride = prev.ctypes.data, prev.strides[0], nxt.ctypes.data, nxt.strides[0]
+            d.flow, d.flow_stride = flow.ctypes.data, flow.strides[0]
+        elif host:
             prev, nxt = _as_gray_u8(prev, "prev"), _as_gray_u8(nxt, "next")
             if prev.shape != nxt.shape:
                 raise NsofValueError(f"pair {i}: prev {prev.shape} and next {nxt.shape} sizes differ", _lib.NSOF_ESHAPE)
@@ -251,14 +260,19 @@ def _desc_array(pairs, flows, host):
             d.flow, d.flow_stride = flow.ctypes.data, flow.strides[0]
         else:
             h, w = int(prev.shape[0]), int(prev.shape[1])
-            if _tensor_dtype(prev) not in (None, "uint8") or _tensor_dtype(nxt) not in (None, "uint8"):
+            if f32:
+                if _tensor_dtype(prev) != "float32" or _tensor_dtype(nxt) != "float32":
+                    raise NsofValueError(f"pair {i}: frames must be float32 tensors (got {_tensor_dtype(prev)}, "
+                                         f"{_tensor_dtype(nxt)}); 8-bit frames take farneback_pairs_dev")
+            elif _tensor_dtype(prev) not in (None, "uint8") or _tensor_dtype(nxt) not in (None, "uint8"):
                 raise NsofValueError(f"pair {i}: work-list frames must be uint8 tensors (got {_tensor_dtype(prev)}, "
-                                     f"{_tensor_dtype(nxt)})")
+                                     f"{_tensor_dtype(nxt)}); float32 frames take farneback_pairs_f32_dev")
             if tuple(nxt.shape[:2]) != (h, w):
                 raise NsofValueError(f"pair {i}: prev and next sizes differ", _lib.NSOF_ESHAPE)
             if prev.stride(1) != 1 or nxt.stride(1) != 1 or flow.stride(2) != 1 or flow.stride(1) != 2:
                 raise NsofValueError(f"pair {i}: pixel strides must be 1 (row strides are free)")
-            d.prev, d.prev_stride, d.next, d.next_stride = prev.data_ptr(), prev.stride(0), nxt.data_ptr(), nxt.stride(0)
+            d.prev, d.prev_stride = prev.data_ptr(), prev.stride(0) * px
+            d.next, d.next_stride = nxt.data_ptr(), nxt.stride(0) * px
             d.flow, d.flow_stride = flow.data_ptr(), flow.stride(0) * 4
         if h == 0 or w == 0:
             raise NsofValueError(f"pair {i}: empty input image", _lib.NSOF_ESHAPE)
@@ -266,12 +280,72 @@ def _desc_array(pairs, flows, host):
     return descs, keep
 
 
+def _host_list_is_u8(pairs):
+    """True when every frame of a host list is uint8; frames must be single-channel of a depth cv2 takes and the two
+    frames of a pair of one dtype (as ``calcOpticalFlowFarneback``)."""
+    u8 = True
+    for i, (prev, nxt) in enumerate(pairs):
+        a, b = _as_gray(prev, f"pairs[{i}] prev"), _as_gray(nxt, f"pairs[{i}] next")
+        if a.dtype != b.dtype:
+            raise NsofValueError(f"pair {i}: prev ({a.dtype}) and next ({b.dtype}) dtypes differ")
+        u8 = u8 and a.dtype == np.uint8
+    return u8
+
+
+_F32_STAGE_CAP = 256 << 20   # bytes of page-locked conversion buffer a context keeps at most
+
+
+def _f32_host_frames(pairs, ctx):
+    """The frames of a float list as float32 (``astype(np.float32)``, cv2's ``convertTo(CV_32F)``), every value checked
+    finite.  float32 frames whose layout the entry takes are used as they are; frames that need a conversion are
+    converted straight into a page-locked buffer kept on the context (the pipeline then uploads them without a staging
+    copy) while it has room -- at most ``_F32_STAGE_CAP`` bytes, released by ``Context.close`` -- and into ordinary
+    arrays beyond that (the pipeline packs those into its own bounded staging, as for any pageable frame).  Call with
+    ``ctx.lock`` held: the buffer is reused by the next call."""
+    grays = [(_as_gray(p, f"pairs[{i}] prev"), _as_gray(q, f"pairs[{i}] next")) for i, (p, q) in enumerate(pairs)]
+
+    def usable(a):
+        return a.dtype == np.float32 and (not a.size or (a.strides[1] == 4 and a.strides[0] % 4 == 0 and a.ctypes.data % 4 == 0))
+
+    def padded(a):
+        return (a.size * 4 + 255) // 256 * 256
+
+    need = min(sum(padded(a) for pq in grays for a in pq if not usable(a)), _F32_STAGE_CAP)
+    stage = getattr(ctx, "_nsof_f32_stage", None)
+    if need and (stage is None or stage.nbytes < need):
+        ctx._nsof_f32_stage = None   # the old buffer goes before the new one is taken
+        stage = pinned_empty((min(_F32_STAGE_CAP, max(need, int(1.25 * (0 if stage is None else stage.nbytes)))),),
+                             np.uint8)
+        ctx._nsof_f32_stage = stage
+    out, off = [], 0
+    for i, pq in enumerate(grays):
+        conv = []
+        for name, a in zip(("prev", "next"), pq):
+            if not usable(a):
+                if stage is not None and off + padded(a) <= stage.nbytes:
+                    dst = stage[off:off + a.size * 4].view(np.float32).reshape(a.shape)
+                    off += padded(a)
+                else:
+                    dst = np.empty(a.shape, np.float32)
+                with np.errstate(over="ignore", invalid="ignore"):   # float64 beyond float32's range -> inf, refused below
+                    np.copyto(dst, a, casting="unsafe")                # the conversion astype(np.float32) does
+                a = dst
+            if not np.isfinite(a).all():
+                raise NsofValueError(f"pairs[{i}] {name} holds non-finite values (after conversion to float32)")
+            conv.append(a)
+        out.append(tuple(conv))
+    return out
+
+
 def farneback_pairs(pairs, params, flows=None, *, pinned=False, ctx=None):
     """Flow of MANY independent (prev, next) pairs of ANY shapes with one parameter set -- the gated path's ROI
     calls (optical_flow_seg.py:129-164, :186-203) and full-frame calls (:492-496) of a whole sequence in one go
     (``nsof_farneback_u8_batch``): the pairs share every kernel launch and upload / compute / download overlap.
 
-    ``pairs``: [(prev, next), ...] uint8 2-D numpy arrays (strided ROI views allowed).  ``flows``: optional list of
+    ``pairs``: [(prev, next), ...] 2-D numpy arrays (strided ROI views allowed) of any depth ``calcOpticalFlowFarneback``
+    takes, one dtype per pair.  An all-uint8 list runs on the 8-bit entry; any other list is converted frame by frame
+    with ``astype(np.float32)`` (uint8 frames of a mixed list too) and runs on ``nsof_farneback_f32_batch``; non-finite
+    values raise before any device work.  ``flows``: optional list of
     float32 (h, w, 2) arrays to write into (views ``canvas[y0:y1, x0:x1]`` of a frame-sized canvas are written in
     place -- the paste of :162/:204); by default fresh arrays are returned, page-locked when ``pinned`` (then the
     result is copied straight from the GPU into the array).  Each result equals ``calcOpticalFlowFarneback`` of
@@ -293,11 +367,20 @@ def farneback_pairs(pairs, params, flows=None, *, pinned=False, ctx=None):
         raise NsofValueError("flows and pairs differ in length")
     if not pairs:
         return []
-    descs, keep = _desc_array(pairs, flows, host=True)
-    rc = ctx._lib.nsof_farneback_u8_batch(ctx.ptr, len(pairs), descs, float(kw["pyr_scale"]), int(kw["levels"]),
-                                          int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]),
-                                          float(kw["poly_sigma"]), int(kw["flags"]))
-    ctx.check(rc, "farneback_pairs")
+    if _host_list_is_u8(pairs):
+        descs, keep = _desc_array(pairs, flows, host=True)
+        rc = ctx._lib.nsof_farneback_u8_batch(ctx.ptr, len(pairs), descs, float(kw["pyr_scale"]), int(kw["levels"]),
+                                              int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]),
+                                              float(kw["poly_sigma"]), int(kw["flags"]))
+        ctx.check(rc, "farneback_pairs")
+        del keep
+        return flows
+    with ctx.lock:
+        descs, keep = _desc_array(_f32_host_frames(pairs, ctx), flows, host=True, f32=True)
+        rc = ctx._lib.nsof_farneback_f32_batch(ctx.ptr, len(pairs), descs, float(kw["pyr_scale"]), int(kw["levels"]),
+                                               int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]),
+                                               float(kw["poly_sigma"]), int(kw["flags"]))
+        ctx.check(rc, "farneback_pairs")
     del keep
     return flows
 
@@ -320,6 +403,34 @@ def farneback_pairs_dev(pairs, flows, params, *, ctx=None):
     ctx.check(rc, "farneback_pairs_dev")
 
 
+def farneback_pairs_f32_dev(pairs, flows, params, *, ctx=None):
+    """``farneback_pairs_dev`` for float32 frames (``nsof_farneback_f32_batch_desc_dev``): ``pairs`` = [(prev, next), ...]
+    of float32 CUDA tensors (crops of frames in HBM: rows 4-byte aligned, any row stride), ``flows`` as there.  Each
+    result equals ``calcOpticalFlowFarneback`` of that pair's frames bit for bit.  Other dtypes raise ``NsofValueError``.
+    Asynchronous on the context's stream."""
+    ctx = ctx or default_context()
+    kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
+    pairs, flows = list(pairs), list(flows)
+    if len(flows) != len(pairs):
+        raise NsofValueError("flows and pairs differ in length")
+    if not pairs:
+        return
+    descs, _ = _desc_array(pairs, flows, host=False, f32=True)
+    rc = ctx._lib.nsof_farneback_f32_batch_desc_dev(ctx.ptr, len(pairs), descs, float(kw["pyr_scale"]), int(kw["levels"]),
+                                                    int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]),
+                                                    float(kw["poly_sigma"]), int(kw["flags"]))
+    ctx.check(rc, "farneback_pairs_f32_dev")
+
+
+def _roi_sequence_args(frames, counts, rects, flows):
+    n, h, w = (int(v) for v in frames.shape)
+    if tuple(flows.shape) != (n - 1, h, w, 2) or not flows.is_contiguous() or frames.stride(2) != 1:
+        raise NsofValueError("flows must be a contiguous (n-1, H, W, 2) tensor and the frames' pixel stride 1")
+    if tuple(rects.shape[:1]) != (n,) or rects.shape[2] != 4 or not rects.is_contiguous() or not counts.is_contiguous():
+        raise NsofValueError("rects must be a contiguous (n, max_rects, 4) int32 tensor")
+    return n, h, w
+
+
 def farneback_roi_sequence_dev(frames, counts, rects, flows, params, *, gate_frame=0, ctx=None):
     """The gated path of a frame sequence on the device (``nsof_farneback_u8_roi_sequence_dev``; opticalFlow3D's crop ->
     flow -> paste loop, optical_flow_seg.py:129-164, 186-204): ``frames`` uint8 CUDA tensor [n][H][W] (row stride free),
@@ -332,12 +443,9 @@ def farneback_roi_sequence_dev(frames, counts, rects, flows, params, *, gate_fra
     ctx = ctx or default_context()
     kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
     if _tensor_dtype(frames) not in (None, "uint8"):
-        raise NsofValueError(f"frames must be a uint8 tensor (got {_tensor_dtype(frames)}); work lists are 8-bit")
-    n, h, w = (int(v) for v in frames.shape)
-    if tuple(flows.shape) != (n - 1, h, w, 2) or not flows.is_contiguous() or frames.stride(2) != 1:
-        raise NsofValueError("flows must be a contiguous (n-1, H, W, 2) tensor and the frames' pixel stride 1")
-    if tuple(rects.shape[:1]) != (n,) or rects.shape[2] != 4 or not rects.is_contiguous() or not counts.is_contiguous():
-        raise NsofValueError("rects must be a contiguous (n, max_rects, 4) int32 tensor")
+        raise NsofValueError(f"frames must be a uint8 tensor (got {_tensor_dtype(frames)}); float32 frames take "
+                             "farneback_roi_sequence_f32_dev")
+    n, h, w = _roi_sequence_args(frames, counts, rects, flows)
     calls, pixels = C.c_longlong(), C.c_longlong()
     rc = ctx._lib.nsof_farneback_u8_roi_sequence_dev(
         ctx.ptr, n, dev_ptr(frames), int(frames.stride(1)), int(frames.stride(0)), w, h, dev_ptr(counts), dev_ptr(rects),
@@ -345,6 +453,26 @@ def farneback_roi_sequence_dev(frames, counts, rects, flows, params, *, gate_fra
         int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]), int(kw["flags"]), int(gate_frame), C.byref(calls),
         C.byref(pixels))
     ctx.check(rc, "farneback_roi_sequence_dev")
+    return calls.value, pixels.value
+
+
+def farneback_roi_sequence_f32_dev(frames, counts, rects, flows, params, *, gate_frame=0, ctx=None):
+    """``farneback_roi_sequence_dev`` for float32 frames (``nsof_farneback_f32_roi_sequence_dev``): ``frames`` float32 CUDA
+    tensor [n][H][W] (row stride free); every crop's flow equals ``calcOpticalFlowFarneback`` of the float crops, pasted as
+    there.  Other dtypes raise ``NsofValueError``.  -> (n_crops, crop_pixels)."""
+    ctx = ctx or default_context()
+    kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
+    if _tensor_dtype(frames) != "float32":
+        raise NsofValueError(f"frames must be a float32 tensor (got {_tensor_dtype(frames)}); 8-bit frames take "
+                             "farneback_roi_sequence_dev")
+    n, h, w = _roi_sequence_args(frames, counts, rects, flows)
+    calls, pixels = C.c_longlong(), C.c_longlong()
+    rc = ctx._lib.nsof_farneback_f32_roi_sequence_dev(
+        ctx.ptr, n, dev_ptr(frames), int(frames.stride(1)) * 4, int(frames.stride(0)) * 4, w, h, dev_ptr(counts),
+        dev_ptr(rects), int(rects.shape[1]), dev_ptr(flows), float(kw["pyr_scale"]), int(kw["levels"]), int(kw["winsize"]),
+        int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]), int(kw["flags"]), int(gate_frame), C.byref(calls),
+        C.byref(pixels))
+    ctx.check(rc, "farneback_roi_sequence_f32_dev")
     return calls.value, pixels.value
 
 

@@ -92,7 +92,7 @@ def events_to_rois_host(x, y, p, t, sensor_hw, cfg, version=1, polarity="split",
 
 
 def events_to_roi_flows(x, y, p, t, sensor_hw, cfg, slice_us=1000, active_v=-6.0, silent_v=0.0, snapshot_every=33,
-                        surface_mode="state", ctx=None, max_rects=32, timings=None):
+                        surface_mode="state", ctx=None, max_rects=32, timings=None, surface_dtype="uint8"):
     """BASELINE config 3 as one pipeline on the device: event stream -> leaky-integrate surface (scheme 1) -> every
     ``snapshot_every`` slices an 8-bit surface frame AND the gating map of the same state -> ROI rectangles on the device
     (``gating.roi_from_surface_dev``) -> Farneback flow of every ROI crop between consecutive surface frames, all crops of
@@ -104,14 +104,20 @@ def events_to_roi_flows(x, y, p, t, sensor_hw, cfg, slice_us=1000, active_v=-6.0
     Events are uploaded once; frames, maps, rectangles and flow stay in HBM -- the only thing that crosses PCIe before the
     result is the rectangle table (16 bytes per ROI, one copy): the work list's shapes are needed on the host.
     Returns ``(frames uint8 [n][H][W], rects [[(x0, y0, x1, y1), ...] per frame], flows float32 [n-1][H][W][2])`` -- torch
-    CUDA tensors and the host-side rectangle lists; ``flows[k]`` is zero outside the ROIs of the gating frame."""
+    CUDA tensors and the host-side rectangle lists; ``flows[k]`` is zero outside the ROIs of the gating frame.
+    ``surface_dtype="float32"``: the surface frames are the unquantised float surface instead (``Accumulator.run`` of the
+    interval, then ``Accumulator.surface_f32``, same ``surface_mode``), ``frames`` is float32 and the crops run on
+    ``farneback_roi_sequence_f32_dev``.  The gating maps and so the rectangles do not depend on it."""
     import time
 
     import torch
 
     from .context import default_context
-    from .farneback import farneback_roi_sequence_dev
+    from .farneback import farneback_roi_sequence_dev, farneback_roi_sequence_f32_dev
     ctx = ctx or default_context()
+    if surface_dtype not in ("uint8", "float32"):
+        raise ValueError(f"surface_dtype must be 'uint8' or 'float32' (got {surface_dtype!r})")
+    f32 = surface_dtype == "float32"
     H, W = sensor_hw  # noqa: N806
     dev = torch.device("cuda", ctx.device)
     idx = slice_index_array(t, slice_us)
@@ -122,7 +128,7 @@ def events_to_roi_flows(x, y, p, t, sensor_hw, cfg, slice_us=1000, active_v=-6.0
     if rows > 64 or cols > 64:
         raise ValueError(f"gating map {rows}x{cols}: the device gating kernel takes maps up to 64x64 cells (use events_to_rois_host "
                          "+ farneback_pairs for finer grids)")
-    frames = torch.empty((n_frames, H, W), dtype=torch.uint8, device=dev)
+    frames = torch.empty((n_frames, H, W), dtype=torch.float32 if f32 else torch.uint8, device=dev)
     cur = torch.empty((n_frames, rows, cols), dtype=torch.float64, device=dev)
     flows = torch.empty((n_frames - 1, H, W, 2), dtype=torch.float32, device=dev)   # zero-filled by the flow call
     torch.cuda.synchronize(dev)
@@ -131,7 +137,11 @@ def events_to_roi_flows(x, y, p, t, sensor_hw, cfg, slice_us=1000, active_v=-6.0
         acc.set_events(x, y, p, t, idx)
         t0 = time.perf_counter()
         for k in range(n_frames):
-            acc.run_surface(k * snapshot_every, snapshot_every, frames[k], mode=surface_mode)
+            if f32:
+                acc.run(k * snapshot_every, snapshot_every)
+                acc.surface_f32(frames[k], mode=surface_mode)
+            else:
+                acc.run_surface(k * snapshot_every, snapshot_every, frames[k], mode=surface_mode)
             acc.block_current_dev(cfg.MEMSIZE, cur[k])
         counts, rtab = gating.roi_from_surface_dev(cur, n_frames, (rows, cols), (H, W), cfg, max_rects=max_rects, ctx=ctx)
         ctx.synchronize()
@@ -141,8 +151,9 @@ def events_to_roi_flows(x, y, p, t, sensor_hw, cfg, slice_us=1000, active_v=-6.0
             ctx.synchronize()
         t1 = time.perf_counter()
         # crop -> flow -> paste of every ROI of every pair: one native call builds the work list from the rectangle table
-        n_calls, n_pixels = farneback_roi_sequence_dev(frames, counts, rtab, flows, cfg.farneback_params,
-                                                       gate_frame=0 if cfg.bug_compatible else 1, ctx=ctx)
+        roi_flow = farneback_roi_sequence_f32_dev if f32 else farneback_roi_sequence_dev
+        n_calls, n_pixels = roi_flow(frames, counts, rtab, flows, cfg.farneback_params,
+                                     gate_frame=0 if cfg.bug_compatible else 1, ctx=ctx)
         ctx.synchronize()
         t2 = time.perf_counter()
         rects = gating.rects_to_host(counts, rtab, ctx=ctx)
