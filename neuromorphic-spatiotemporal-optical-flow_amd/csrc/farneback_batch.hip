@@ -312,12 +312,8 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
         float* dM = (float*)(base + szI + szR + 2 * szF + szV);
         int cur = 0;
         for (int k = Lmax; k >= 0; k--) {
-            int wk, hk, ks;
-            double sg;
-            nsof_farneback_level_size(64, 64, p.pyr_scale, k, &wk, &hk, &ks, &sg);   // blur taps depend on k only
-            nsof_blur_taps btaps;
-            if ((rc = nsof_host_blur_taps(ks, sg, &btaps)))
-                return nsof_set_error(ctx, rc, "pyramid blur kernel size %d unsupported (max %d)", ks, NSOF_MAX_BLUR_TAPS - 1);
+            nsof_blur_taps btaps;   // blur taps depend on k only
+            if ((rc = nsof_level_geom(ctx, 64, 64, p.pyr_scale, k, nullptr, nullptr, &btaps))) return rc;
             const nsof_het_item* dt = d_tabs + (size_t)k * nh;
             const nsof_het_item* ht = tabs + (size_t)k * nh;
             const int nk_items = cnt[k];

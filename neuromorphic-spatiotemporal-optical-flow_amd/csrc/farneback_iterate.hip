@@ -26,9 +26,9 @@
 
 namespace {
 
-template <int MH, int COLS_ = 256>
+template <int MH>
 struct QGeom {
-    static constexpr int COLS = COLS_, RB = 4;
+    static constexpr int COLS = 256, RB = 4;
     static constexpr int RL = 2 * MH + 1 + 2 * RB;
     static constexpr int SW = (COLS - 2 * MH) & ~3;         // a solve thread owns 4 whole pixels
     // Column sums of one (row, plane): the solve threads read 4 adjacent columns each, i.e. lanes 4 doubles apart -- a
@@ -41,35 +41,34 @@ struct QGeom {
     __host__ __device__ static constexpr int svi(int col) { return (col & 3) * SVSUB + (col >> 2); }
 };
 
-template <int MH, int COLS, int GP, int TS, int RR>
-__device__ __forceinline__ void q_produce(RowIn (&in)[2][2], FlowSrc<false>::Raw (&fl)[2][2], float (*mring)[5][COLS],
-                                          const Planes& R0, const Planes& R1, const FlowSrc<false>& F, int W, int H, int xc,
+template <int MH, int GP, int TS, int RR>
+__device__ __forceinline__ void q_produce(RowIn (&in)[2][2], float2 (&fl)[2][2], float (*mring)[5][QGeom<MH>::COLS],
+                                          const Planes& R0, const Planes& R1, const FlowSrc& F, int W, int H, int xc,
                                           int col, int t, int yb)
 {
-    constexpr int RL = QGeom<MH, COLS>::RL;
+    constexpr int RL = QGeom<MH>::RL;
     const int i = 4 * t + MH + 2 * GP + RR;                  // stream index of this row (row yb + i of the image)
     float Mn[5];
     matrix_from(in[TS][RR], xc, min(yb + i, H - 1), W, H, Mn);
     const int slot = (i + MH + 1) % RL;
 #pragma unroll
     for (int c = 0; c < 5; c++) mring[slot][c][col] = Mn[c];
-    issue_row(in[TS][RR], R0, R1, W, H, xc, min(yb + i + 8, H - 1), F.resolve(fl[TS][RR]));   // the same row of step t+2
+    issue_row(in[TS][RR], R0, R1, W, H, xc, min(yb + i + 8, H - 1), fl[TS][RR]);              // the same row of step t+2
     fl[TS][RR] = F.fetch(min(yb + i + 16, H - 1));                                            // its flow for step t+4
 }
 
-template <int MH, int COLS, int GP>
-__device__ __forceinline__ void q_producer_loop(float (*mring)[5][COLS], const Planes& R0, const Planes& R1,
-                                                const FlowSrc<false>& F, int W, int H, int xc, int col, int nsteps,
-                                                int yb)
+template <int MH, int GP>
+__device__ __forceinline__ void q_producer_loop(float (*mring)[5][QGeom<MH>::COLS], const Planes& R0, const Planes& R1,
+                                                const FlowSrc& F, int W, int H, int xc, int col, int nsteps, int yb)
 {
     RowIn in[2][2];
-    FlowSrc<false>::Raw fl[2][2];
+    float2 fl[2][2];
 #pragma unroll
     for (int ts = 0; ts < 2; ts++)
 #pragma unroll
         for (int rr = 0; rr < 2; rr++) {
             const int r = min(yb + 4 * ts + MH + 2 * GP + rr, H - 1);
-            issue_row(in[ts][rr], R0, R1, W, H, xc, r, F.at(r));
+            issue_row(in[ts][rr], R0, R1, W, H, xc, r, F.fetch(r));
         }
 #pragma unroll
     for (int ts = 0; ts < 2; ts++)
@@ -80,34 +79,30 @@ __device__ __forceinline__ void q_producer_loop(float (*mring)[5][COLS], const P
     //   B_init .. B1(0)        first row of step 1            (consumers: column sums of step 0)
     //   B1(t) .. B2(t)         second row of step t+1         (consumers: row sums + solve of step t)
     //   B2(t) .. B1(t+1)       first row of step t+2          (consumers: column sums of step t+1)
-    q_produce<MH, COLS, GP, 0, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, 0, yb);
-    q_produce<MH, COLS, GP, 0, 1>(in, fl, mring, R0, R1, F, W, H, xc, col, 0, yb);
+    q_produce<MH, GP, 0, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, 0, yb);
+    q_produce<MH, GP, 0, 1>(in, fl, mring, R0, R1, F, W, H, xc, col, 0, yb);
     __syncthreads();
-    q_produce<MH, COLS, GP, 1, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, 1, yb);
+    q_produce<MH, GP, 1, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, 1, yb);
     for (int tb = 0; tb < nsteps; tb += 2) {
         __syncthreads();                                                             // B1(tb)
-        q_produce<MH, COLS, GP, 1, 1>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 1, yb);
+        q_produce<MH, GP, 1, 1>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 1, yb);
         __syncthreads();                                                             // B2(tb)
-        q_produce<MH, COLS, GP, 0, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 2, yb);
+        q_produce<MH, GP, 0, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 2, yb);
         if (tb + 1 >= nsteps) break;
         __syncthreads();                                                             // B1(tb+1)
-        q_produce<MH, COLS, GP, 0, 1>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 2, yb);
+        q_produce<MH, GP, 0, 1>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 2, yb);
         __syncthreads();                                                             // B2(tb+1)
-        q_produce<MH, COLS, GP, 1, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 3, yb);
+        q_produce<MH, GP, 1, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 3, yb);
     }
 }
 
-// VOUT: instead of forming the row sums and solving, the column sums of the strip's own columns go to HBM
-// (Vout: [H][5][W] doubles of this pair).  No launcher uses it any more; the parameter stays so that the kernels'
-// symbols and code are unchanged.
-template <int MH, int COLS, bool VOUT = false>
-__device__ __forceinline__ void q_consumer_loop(float (*mring)[5][COLS], void* sv_raw, const Planes& R0,
-                                                const Planes& R1, const FlowSrc<false>& F, float2* Fout, size_t fpitch,
-                                                int W, int H, int x0, int xc, int col, int nsteps, double scale,
-                                                double* Vout, int yb, int ye)
+template <int MH>
+__device__ __forceinline__ void q_consumer_loop(float (*mring)[5][QGeom<MH>::COLS], void* sv_raw, const Planes& R0,
+                                                const Planes& R1, const FlowSrc& F, float2* Fout, size_t fpitch, int W,
+                                                int H, int x0, int xc, int col, int nsteps, double scale, int yb, int ye)
 {
-    using G = QGeom<MH, COLS>;
-    constexpr int RL = G::RL, SW = G::SW, TPR = COLS / 4;   // TPR solve threads per row
+    using G = QGeom<MH>;
+    constexpr int RL = G::RL, SW = G::SW, TPR = G::COLS / 4;   // TPR solve threads per row
     double (*sv)[5][G::SVW] = reinterpret_cast<double (*)[5][G::SVW]>(sv_raw);   // [4 rows][5 planes]
     double vs[5];
     if (yb > 0) {
@@ -116,7 +111,7 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][COLS], void* s
         // start differs from it in the sums' last bits (same class as the row-sum order).
         RowIn t[2];
         const int r0 = max(yb - MH - 1, 0);
-        issue_row(t[0], R0, R1, W, H, xc, r0, F.at(r0));
+        issue_row(t[0], R0, R1, W, H, xc, r0, F.fetch(r0));
 #pragma unroll
         for (int c = 0; c < 5; c++) vs[c] = 0.;
 #pragma unroll
@@ -124,7 +119,7 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][COLS], void* s
             const int r = clampi(yb - MH - 1 + j, 0, H - 1);
             if (j < 2 * MH) {
                 const int rn = clampi(yb - MH + j, 0, H - 1);
-                issue_row(t[(j + 1) & 1], R0, R1, W, H, xc, rn, F.at(rn));
+                issue_row(t[(j + 1) & 1], R0, R1, W, H, xc, rn, F.fetch(rn));
             }
             float Mi[5];
             matrix_from(t[j & 1], xc, r, W, H, Mi);
@@ -139,7 +134,7 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][COLS], void* s
         // ring slot of stream index i is (i + m + 1) % RL.
         RowIn t;
         float M0[5];
-        issue_row(t, R0, R1, W, H, xc, 0, F.at(0));
+        issue_row(t, R0, R1, W, H, xc, 0, F.fetch(0));
         matrix_from(t, xc, 0, W, H, M0);
 #pragma unroll
         for (int c = 0; c < 5; c++) {
@@ -151,7 +146,7 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][COLS], void* s
         for (int i = 1; i < MH; i++) {
             float Mi[5];
             const int r = min(i, H - 1);
-            issue_row(t, R0, R1, W, H, xc, r, F.at(r));
+            issue_row(t, R0, R1, W, H, xc, r, F.fetch(r));
             matrix_from(t, xc, r, W, H, Mi);
 #pragma unroll
             for (int c = 0; c < 5; c++) {
@@ -164,7 +159,6 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][COLS], void* s
     const int hrow = col / TPR, t4 = col % TPR;   // solve phase: COLS/4 threads per row, 4 pixels each
     int slot_new = (2 * MH + 1) % RL;           // stream index m    -> slot 2m+1
     int slot_old = 0;                           // stream index -m-1 -> slot 0
-    const bool own = col >= MH && col < MH + SW && x0 + col - MH < W;   // VOUT: this thread's column belongs to the strip
     for (int t = 0; t < nsteps; t++) {
         // column sums: four more rows enter the window of this thread's column
 #pragma unroll
@@ -173,21 +167,12 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][COLS], void* s
             for (int c = 0; c < 5; c++) {
                 const float d = mring[slot_new][c][col] - mring[slot_old][c][col];
                 vs[c] += (double)d;
-                if constexpr (VOUT) {
-                    if (own && yb + 4 * t + q < ye)
-                        __builtin_nontemporal_store(vs[c], Vout + ((size_t)(yb + 4 * t + q) * 5 + c) * W + (x0 + col - MH));
-                } else {
-                    sv[q][c][G::svi(col)] = vs[c];
-                }
+                sv[q][c][G::svi(col)] = vs[c];
             }
             slot_new = slot_new + 1 == RL ? 0 : slot_new + 1;
             slot_old = slot_old + 1 == RL ? 0 : slot_old + 1;
         }
         __syncthreads();   // B1(t): column sums of step t visible
-        if constexpr (VOUT) {
-            __syncthreads();   // B2(t): same barrier sequence as the solving variant
-            continue;
-        }
         const int yo = yb + 4 * t + hrow, xo = x0 + 4 * t4;
         if (4 * t4 < SW && yo < ye && xo < W) {
             const double (*svr)[G::SVW] = sv[hrow];
@@ -228,15 +213,18 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][COLS], void* s
     }
 }
 
-template <int MH, bool HET, int COLS = 256, bool VOUT = false>
-__global__ __launch_bounds__(3 * COLS) void k_iterate_q(const float* __restrict__ R0b, const float* __restrict__ R1b,
-                                                    size_t pair_stride, const float* __restrict__ flow_in,
-                                                    float* __restrict__ flow_out, int W, int H, int block_size,
-                                                    const nsof_het_item* __restrict__ items, int het_final,
-                                                    double* __restrict__ vsum_out = nullptr, int band_rows = 0)
+// The double* argument is unused: a reserved slot that keeps the argument layout (and band_rows' offset) fixed.
+template <int MH, bool HET>
+__global__ __launch_bounds__(3 * QGeom<MH>::COLS) void k_iterate_q(const float* __restrict__ R0b,
+                                                                   const float* __restrict__ R1b, size_t pair_stride,
+                                                                   const float* __restrict__ flow_in,
+                                                                   float* __restrict__ flow_out, int W, int H,
+                                                                   int block_size, const nsof_het_item* __restrict__ items,
+                                                                   int het_final, double* __restrict__ = nullptr,
+                                                                   int band_rows = 0)
 {
-    using G = QGeom<MH, COLS>;
-    constexpr int SW = G::SW;
+    using G = QGeom<MH>;
+    constexpr int SW = G::SW, COLS = G::COLS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_q[];
     void* sv = smem_q;                                                                          // [4 rows][5][SVW] doubles
     float (*mring)[5][COLS] = reinterpret_cast<float (*)[5][COLS]>(smem_q + G::SV_BYTES);       // [RL]
@@ -254,7 +242,6 @@ __global__ __launch_bounds__(3 * COLS) void k_iterate_q(const float* __restrict_
         pair_stride = 0;
         pair = 0;
         flow_in += 2 * it.offF;
-        if constexpr (VOUT) vsum_out += it.offR / 2;
         if (het_final) {
             flow_out = it.out;
             fpitch = (size_t)it.out_pitch;
@@ -279,7 +266,7 @@ __global__ __launch_bounds__(3 * COLS) void k_iterate_q(const float* __restrict_
     const size_t plane = (size_t)W * H;
     const Planes R0 = planes_of(R0b + (size_t)pair * pair_stride, plane);
     const Planes R1 = planes_of(R1b + (size_t)pair * pair_stride, plane);
-    FlowSrc<false> F;
+    FlowSrc F;
     F.base = reinterpret_cast<const char*>(flow_in) + (size_t)pair * plane * 8;
     F.W = (unsigned)W;
     F.xc = (unsigned)xc;
@@ -293,13 +280,12 @@ __global__ __launch_bounds__(3 * COLS) void k_iterate_q(const float* __restrict_
     }
     const int nsteps = (ye - yb + 3) / 4;
     if (role == 0)
-        q_consumer_loop<MH, COLS, VOUT>(mring, sv, R0, R1, F, Fout, fpitch, W, H, x0, xc, col, nsteps,
-                                        1. / (block_size * block_size), VOUT ? vsum_out + (size_t)pair * 5 * plane : nullptr,
-                                        yb, ye);
+        q_consumer_loop<MH>(mring, sv, R0, R1, F, Fout, fpitch, W, H, x0, xc, col, nsteps, 1. / (block_size * block_size),
+                            yb, ye);
     else if (role == 1)
-        q_producer_loop<MH, COLS, 0>(mring, R0, R1, F, W, H, xc, col, nsteps, yb);
+        q_producer_loop<MH, 0>(mring, R0, R1, F, W, H, xc, col, nsteps, yb);
     else
-        q_producer_loop<MH, COLS, 1>(mring, R0, R1, F, W, H, xc, col, nsteps, yb);
+        q_producer_loop<MH, 1>(mring, R0, R1, F, W, H, xc, col, nsteps, yb);
 }
 
 template <int MH>

@@ -108,21 +108,21 @@ constexpr unsigned X_SPIN_LIMIT = 1u << 21;   // polls of a carry before giving 
 // One row of M: consume the loads issued two steps ago, write the ring, issue the same row of step + 2 (i + 8) and fetch
 // its flow for step + 4 (i + 16).  i = stream index = image row (clamped at the bottom).
 template <int MH>
-__device__ __forceinline__ void x_produce(RowIn& in, FlowSrc<false>::Raw& fl, const XRing& ring, const Planes& R0,
-                                          const Planes& R1, const FlowSrc<false>& F, int W, int H, int xc, int col, int i)
+__device__ __forceinline__ void x_produce(RowIn& in, float2& fl, const XRing& ring, const Planes& R0,
+                                          const Planes& R1, const FlowSrc& F, int W, int H, int xc, int col, int i)
 {
     constexpr int RL = XGeom<MH>::RL;
     float Mn[5];
     matrix_from(in, xc, min(i, H - 1), W, H, Mn);
     ring.put((i + MH + 1) % RL, col, Mn);
-    issue_row(in, R0, R1, W, H, xc, min(i + 8, H - 1), F.resolve(fl));
+    issue_row(in, R0, R1, W, H, xc, min(i + 8, H - 1), fl);
     fl = F.fetch(min(i + 16, H - 1));
 }
 
 // rows 0..m-1 of the window of image row 0 for this thread's column; the m+1 rows above the image replicate row 0.
 // ring slot of stream index i is (i + m + 1) % RL.
 template <int MH>
-__device__ __forceinline__ void x_rows_above(const XRing& ring, const Planes& R0, const Planes& R1, const FlowSrc<false>& F,
+__device__ __forceinline__ void x_rows_above(const XRing& ring, const Planes& R0, const Planes& R1, const FlowSrc& F,
                                              int W, int H, int xc, int col)
 {
     // A job's start-up is a chain of memory latencies (flow -> gather address -> gather -> matrix), ~1.5-2 us each under
@@ -130,7 +130,7 @@ __device__ __forceinline__ void x_rows_above(const XRing& ring, const Planes& R0
     // flow of all m rows first, then the gathers of up to four rows in flight at once.
     float2 fl[MH];
 #pragma unroll
-    for (int i = 0; i < MH; i++) fl[i] = F.at(min(i, H - 1));
+    for (int i = 0; i < MH; i++) fl[i] = F.fetch(min(i, H - 1));
     constexpr int GRP = 4;
 #pragma unroll
     for (int g0 = 0; g0 < MH; g0 += GRP) {
@@ -162,17 +162,17 @@ __device__ __forceinline__ void x_rows_above(const XRing& ring, const Planes& R0
 // Full producer wave: thread <-> ring column, rows 2 GP, 2 GP + 1 of every step.
 template <int MH, int GP>
 __device__ __forceinline__ void x_producer_loop(const XRing& ring, const Planes& R0, const Planes& R1,
-                                                const FlowSrc<false>& F, int W, int H, int xc, int col, int nimg)
+                                                const FlowSrc& F, int W, int H, int xc, int col, int nimg)
 {
     if constexpr (GP == 0) x_rows_above<MH>(ring, R0, R1, F, W, H, xc, col);
     RowIn in[2][2];
-    FlowSrc<false>::Raw fl[2][2];
+    float2 fl[2][2];
 #pragma unroll
     for (int ts = 0; ts < 2; ts++)
 #pragma unroll
         for (int rr = 0; rr < 2; rr++) {
             const int r = min(4 * ts + MH + 2 * GP + rr, H - 1);
-            issue_row(in[ts][rr], R0, R1, W, H, xc, r, F.at(r));
+            issue_row(in[ts][rr], R0, R1, W, H, xc, r, F.fetch(r));
         }
 #pragma unroll
     for (int ts = 0; ts < 2; ts++)
@@ -246,7 +246,7 @@ __device__ __forceinline__ void x_solve_rows(const double* sv, volatile lds_int*
 // finds a stale tag is repeated, which delays this strip's barrier: the lag only grows until the fetches succeed).
 template <int MH>
 __device__ __forceinline__ void x_remainder_loop(const XRing& ring, double* cb, const Planes& R0, const Planes& R1,
-                                                 const FlowSrc<false>& F, int W, int H, int xc, int col, int r, int nimg,
+                                                 const FlowSrc& F, int W, int H, int xc, int col, int r, int nimg,
                                                  gu64* cin, gu64* cout, unsigned epoch, gu32* err, const double* sv,
                                                  volatile lds_int* ioflag, float2* Fout, size_t fpitch, int x0, double scale)
 {
@@ -303,11 +303,11 @@ __device__ __forceinline__ void x_remainder_loop(const XRing& ring, double* cb, 
     };
     if (r == 0) x_rows_above<MH>(ring, R0, R1, F, W, H, xc, col);
     RowIn in[2];
-    FlowSrc<false>::Raw fl[2];
+    float2 fl[2];
 #pragma unroll
     for (int ts = 0; ts < 2; ts++) {
         const int y = min(4 * ts + MH + r, H - 1);
-        issue_row(in[ts], R0, R1, W, H, xc, y, F.at(y));
+        issue_row(in[ts], R0, R1, W, H, xc, y, F.fetch(y));
     }
 #pragma unroll
     for (int ts = 0; ts < 2; ts++) fl[ts] = F.fetch(min(4 * (ts + 2) + MH + r, H - 1));
@@ -731,7 +731,7 @@ __global__ __launch_bounds__((XGeom<MH>::THREADS)) void k_iterate_x(
         // producers: waves NCW+1 .. NCW+NB rows 0,1 of blocks 0..NB-1; wave NCW+NB+1 the remainder; then rows 2,3
         const int pw = wave - (G::NCW + 1);
         const int lane = tid & 63;
-        FlowSrc<false> F;
+        FlowSrc F;
         F.base = reinterpret_cast<const char*>(flow_in) + (HET ? 0 : (size_t)pair * plane * 8);
         F.W = (unsigned)W;
         // wave -> role.  Waves go to SIMD (wave % 4): 4-6 rows 0,1 of blocks 0-2; 7 I/O; 8-10 rows 2,3 of blocks 0-2.

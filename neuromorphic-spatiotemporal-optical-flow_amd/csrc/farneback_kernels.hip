@@ -931,16 +931,17 @@ __global__ __launch_bounds__(256) void k_prep_cols(const float* __restrict__ HA,
 // ---------------------------------------------------------------------------------------
 // Polynomial expansion (FarnebackPolyExp).  24 B/px algorithmic: 4 read + 5 x 4 written.
 //
-// "Strip walker": a 256-thread block owns 256 image columns (SW output columns + NP halo on
-// each side) and walks down a row segment four rows per step.
+// "Strip walker": a block owns 256 image columns (SW output columns + NP halo on each side)
+// and walks down a row segment four rows per step.
 //   vertical pass   thread <-> column; the 2N+1 input rows of the column live in a register
 //                   window (one coalesced dword load per thread per new row, prefetched one
 //                   step ahead); r0/r1/r2 (float accumulation) go to LDS.
 //   horizontal pass wave <-> row, lane <-> 4 adjacent pixels; taps come from LDS as
-//                   ds_read_b128 and are reused across the 4 pixels in registers; the six
-//                   moments accumulate in double exactly as the reference library does
-//                   (b1,b4: double products -- exact, so written as fma; b2,b3,b5,b6: float
-//                   products widened afterwards); 5 coalesced float4 stores per lane.
+//                   ds_read_b128 and are reused across the 4 pixels in registers; in the exact
+//                   kernel (k_polyexp_rs) the six moments accumulate in double exactly as the
+//                   reference library does (b1,b4: double products -- exact, so written as fma;
+//                   b2,b3,b5,b6: float products widened afterwards); 5 coalesced float4 stores
+//                   per lane.
 // ---------------------------------------------------------------------------------------
 template <int N>
 struct PolyGeom {
@@ -949,41 +950,26 @@ struct PolyGeom {
     static constexpr int NV = (2 * NP + 4) / 4; // float4 per lane per moment row
 };
 
-// FAST (opt-in, nsof_set_option(NSOF_OPT_POLYEXP_F32)): the horizontal moments accumulate in float (fma) instead of
-// double -- NOT the reference library's arithmetic; results differ from the exact kernel in the last bits of R (see
-// DESIGN.md for the measured end-point error).  To keep the float sums small the image is taken relative to a
-// per-workgroup constant c (a constant image has zero derivatives, so the outputs do not depend on c; the
+// The NSOF_OPT_POLYEXP_F32 kernel (opt-in, nsof_set_option): the horizontal moments accumulate in float (fma) instead
+// of double -- NOT the reference library's arithmetic; results differ from the exact kernel (k_polyexp_rs) in the last
+// bits of R (see DESIGN.md for the measured end-point error).  To keep the float sums small the image is taken relative
+// to a per-workgroup constant c (a constant image has zero derivatives, so the outputs do not depend on c; the
 // second-derivative outputs b1*ig03 + b5*ig33 cancel their two large terms, which is where float would lose most).
-template <int N, bool HET, bool FAST = false>
+// `items` is unused: the argument list is the one k_polyexp_rs shares with its work-list form.
+template <int N>
 __global__ __launch_bounds__(256) void k_polyexp(const float* __restrict__ img, float* __restrict__ R, int W, int H,
                                                   int seg_rows, nsof_poly_taps tp,
                                                   const nsof_het_item* __restrict__ items)
 {
     using G = PolyGeom<N>;
-    size_t img_off, r_off;   // element offsets of this image / its expansion
-    if constexpr (HET) {
-        const nsof_het_item& it = items[blockIdx.z >> 1];
-        const size_t which = blockIdx.z & 1;
-        W = it.wk;
-        H = it.hk;
-        if (blockIdx.x * G::SW >= W || blockIdx.y * seg_rows >= H) return;   // block-uniform, before any barrier
-        img_off = it.offI + which * (size_t)W * H;
-        r_off = it.offR + which * 5 * (size_t)W * H;
-    } else {
-        img_off = (size_t)blockIdx.z * W * H;
-        r_off = (size_t)blockIdx.z * 5 * W * H;
-    }
+    const size_t img_off = (size_t)blockIdx.z * W * H;   // element offsets of this image / its expansion
+    const size_t r_off = (size_t)blockIdx.z * 5 * W * H;
     __shared__ __attribute__((aligned(16))) float sr[2][3][4][256];
-    // The 2N double-precision taps would not fit the scalar register file next to the float taps (SGPR
-    // spills cost more than the arithmetic); they live in LDS and are re-read (broadcast) once per step.
-    __shared__ double stap[2][N + 1];
-    __shared__ float ftap[2][N + 1];   // g, xg for the horizontal pass when N is large (see HT below)
+    __shared__ float ftap[2][N + 1];   // g, xg for the horizontal pass when N is large (see below)
     __shared__ float4 st[4][256];   // per-wave transpose buffer for the interleaved channel-0..3 stores
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid <= N) {
-        stap[0][tid] = tp.dg[tid];
-        stap[1][tid] = tp.dxxg[tid];
         ftap[0][tid] = tp.g[tid];
         ftap[1][tid] = tp.xg[tid];
     }
@@ -998,10 +984,8 @@ __global__ __launch_bounds__(256) void k_polyexp(const float* __restrict__ img, 
         return *reinterpret_cast<const float*>(Ib + ((unsigned)clampi(row, 0, H - 1) * (unsigned)W + (unsigned)xc) * 4u);
     };
 
-    // FAST: everything relative to the workgroup's first pixel
-    float cref = 0.f;
-    if constexpr (FAST)
-        cref = *reinterpret_cast<const float*>(Ib + ((unsigned)clampi(ys, 0, H - 1) * (unsigned)W + (unsigned)clampi(x0, 0, W - 1)) * 4u);
+    // everything relative to the workgroup's first pixel
+    const float cref = *reinterpret_cast<const float*>(Ib + ((unsigned)clampi(ys, 0, H - 1) * (unsigned)W + (unsigned)clampi(x0, 0, W - 1)) * 4u);
     // register window: win[j] = I[clamp(y - N + j)][xc]
     float win[2 * N + 1];
 #pragma unroll
@@ -1023,17 +1007,10 @@ __global__ __launch_bounds__(256) void k_polyexp(const float* __restrict__ img, 
 #pragma unroll
             for (int k = 1; k <= N; k++) {
                 const float a = win[N - k], b = win[N + k];
-                float p = a + b;
-                if constexpr (FAST) {
-                    t0 = fmaf(tp.g[k], p, t0);
-                    t2 = fmaf(tp.xxg[k], p, t2);
-                    t1 = fmaf(tp.xg[k], b - a, t1);
-                } else {
-                    t0 = t0 + tp.g[k] * p;
-                    t2 = t2 + tp.xxg[k] * p;
-                    p = b - a;
-                    t1 = t1 + tp.xg[k] * p;
-                }
+                const float p = a + b;
+                t0 = fmaf(tp.g[k], p, t0);
+                t2 = fmaf(tp.xxg[k], p, t2);
+                t1 = fmaf(tp.xg[k], b - a, t1);
             }
             sr[buf][0][q][tid] = t0;
             sr[buf][1][q][tid] = t1;
@@ -1060,101 +1037,36 @@ __global__ __launch_bounds__(256) void k_polyexp(const float* __restrict__ img, 
                     v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w;
                 }
             };
-            double t03[4];  // b1 * ig03, shared by the xx and yy outputs
             float o0[4], o1[4], o2[4], o3[4], o4[4];
-            if constexpr (FAST) {
-                // float accumulation, taps in registers (xxg included), one moment row at a time
-                float fg[N + 1], fxg[N + 1], fxxg[N + 1];
-#pragma unroll
-                for (int k = 0; k <= N; k++) {
-                    fg[k] = (N > 7) ? ftap[0][k] : tp.g[k];
-                    fxg[k] = (N > 7) ? ftap[1][k] : tp.xg[k];
-                    fxxg[k] = tp.xxg[k];
-                }
-                const float i11 = (float)tp.ig11, i03 = (float)tp.ig03, i33 = (float)tp.ig33, i55 = (float)tp.ig55;
-                float t03f[4];
-                {
-                    float v[4 * G::NV];
-                    load_row(0, v);
-#pragma unroll
-                    for (int p = 0; p < 4; p++) {
-                        const int c = G::NP + p;
-                        float a1 = v[c] * fg[0], a2 = 0.f, a4 = 0.f;
-#pragma unroll
-                        for (int k = 1; k <= N; k++) {
-                            const float hi = v[c + k], lo = v[c - k], sm = hi + lo;
-                            a1 = fmaf(sm, fg[k], a1);
-                            a4 = fmaf(sm, fxxg[k], a4);
-                            a2 = fmaf(hi - lo, fxg[k], a2);
-                        }
-                        t03f[p] = a1 * i03;
-                        o1[p] = a2 * i11;
-                        o3[p] = fmaf(a4, i33, t03f[p]);
-                    }
-                }
-                {
-                    float v[4 * G::NV];
-                    load_row(1, v);
-#pragma unroll
-                    for (int p = 0; p < 4; p++) {
-                        const int c = G::NP + p;
-                        float a3 = v[c] * fg[0], a6 = 0.f;
-#pragma unroll
-                        for (int k = 1; k <= N; k++) {
-                            const float hi = v[c + k], lo = v[c - k];
-                            a3 = fmaf(hi + lo, fg[k], a3);
-                            a6 = fmaf(hi - lo, fxg[k], a6);
-                        }
-                        o0[p] = a3 * i11;
-                        o4[p] = a6 * i55;
-                    }
-                }
-                {
-                    float v[4 * G::NV];
-                    load_row(2, v);
-#pragma unroll
-                    for (int p = 0; p < 4; p++) {
-                        const int c = G::NP + p;
-                        float a5 = v[c] * fg[0];
-#pragma unroll
-                        for (int k = 1; k <= N; k++) a5 = fmaf(v[c + k] + v[c - k], fg[k], a5);
-                        o2[p] = fmaf(a5, i33, t03f[p]);
-                    }
-                }
-            } else {
-            // Large radii: 3(N+1) float + 2N double taps exceed the scalar register file (the spills cost more than
-            // the arithmetic), so the horizontal pass takes its float taps from LDS into VGPRs as well.
-            constexpr bool HT = N > 7;
-            float hg[N + 1], hxg[N + 1];
+            // float accumulation, taps in registers (xxg included), one moment row at a time.  Large radii: the
+            // float taps would not fit the scalar register file (the spills cost more than the arithmetic), so g and
+            // xg come from LDS into VGPRs.
+            float fg[N + 1], fxg[N + 1], fxxg[N + 1];
 #pragma unroll
             for (int k = 0; k <= N; k++) {
-                hg[k] = HT ? ftap[0][k] : tp.g[k];
-                hxg[k] = HT ? ftap[1][k] : tp.xg[k];
+                fg[k] = (N > 7) ? ftap[0][k] : tp.g[k];
+                fxg[k] = (N > 7) ? ftap[1][k] : tp.xg[k];
+                fxxg[k] = tp.xxg[k];
             }
+            const float i11 = (float)tp.ig11, i03 = (float)tp.ig03, i33 = (float)tp.ig33, i55 = (float)tp.ig55;
+            float t03f[4];   // b1 * ig03, shared by the xx and yy outputs
             {
                 float v[4 * G::NV];
-                double dg[N + 1], dxxg[N + 1];
-#pragma unroll
-                for (int k = 1; k <= N; k++) {
-                    dg[k] = stap[0][k];
-                    dxxg[k] = stap[1][k];
-                }
                 load_row(0, v);
 #pragma unroll
                 for (int p = 0; p < 4; p++) {
                     const int c = G::NP + p;
-                    double a1 = (double)(v[c] * hg[0]), a2 = 0, a4 = 0;
+                    float a1 = v[c] * fg[0], a2 = 0.f, a4 = 0.f;
 #pragma unroll
                     for (int k = 1; k <= N; k++) {
-                        const float hi = v[c + k], lo = v[c - k];
-                        const double tg = (double)(hi + lo);
-                        a1 = fma(tg, dg[k], a1);     // product of two float-valued doubles is exact
-                        a4 = fma(tg, dxxg[k], a4);
-                        a2 += (double)((hi - lo) * hxg[k]);
+                        const float hi = v[c + k], lo = v[c - k], sm = hi + lo;
+                        a1 = fmaf(sm, fg[k], a1);
+                        a4 = fmaf(sm, fxxg[k], a4);
+                        a2 = fmaf(hi - lo, fxg[k], a2);
                     }
-                    t03[p] = a1 * tp.ig03;
-                    o1[p] = (float)(a2 * tp.ig11);
-                    o3[p] = (float)(t03[p] + a4 * tp.ig33);
+                    t03f[p] = a1 * i03;
+                    o1[p] = a2 * i11;
+                    o3[p] = fmaf(a4, i33, t03f[p]);
                 }
             }
             {
@@ -1163,15 +1075,15 @@ __global__ __launch_bounds__(256) void k_polyexp(const float* __restrict__ img, 
 #pragma unroll
                 for (int p = 0; p < 4; p++) {
                     const int c = G::NP + p;
-                    double a3 = (double)(v[c] * hg[0]), a6 = 0;
+                    float a3 = v[c] * fg[0], a6 = 0.f;
 #pragma unroll
                     for (int k = 1; k <= N; k++) {
                         const float hi = v[c + k], lo = v[c - k];
-                        a3 += (double)((hi + lo) * hg[k]);
-                        a6 += (double)((hi - lo) * hxg[k]);
+                        a3 = fmaf(hi + lo, fg[k], a3);
+                        a6 = fmaf(hi - lo, fxg[k], a6);
                     }
-                    o0[p] = (float)(a3 * tp.ig11);
-                    o4[p] = (float)(a6 * tp.ig55);
+                    o0[p] = a3 * i11;
+                    o4[p] = a6 * i55;
                 }
             }
             {
@@ -1180,13 +1092,12 @@ __global__ __launch_bounds__(256) void k_polyexp(const float* __restrict__ img, 
 #pragma unroll
                 for (int p = 0; p < 4; p++) {
                     const int c = G::NP + p;
-                    double a5 = (double)(v[c] * hg[0]);
+                    float a5 = v[c] * fg[0];
 #pragma unroll
-                    for (int k = 1; k <= N; k++) a5 += (double)((v[c + k] + v[c - k]) * hg[k]);
-                    o2[p] = (float)(t03[p] + a5 * tp.ig33);
+                    for (int k = 1; k <= N; k++) a5 = fmaf(v[c + k] + v[c - k], fg[k], a5);
+                    o2[p] = fmaf(a5, i33, t03f[p]);
                 }
             }
-            }   // !FAST
             // channel 4 of the lane's 4 pixels: one 16-B store
             float* c4 = reinterpret_cast<float*>(Rb) + 4u * plane + opix;
             if ((W & 3) == 0) {
@@ -1220,8 +1131,8 @@ __global__ __launch_bounds__(256) void k_polyexp(const float* __restrict__ img, 
 }
 
 // ---------------------------------------------------------------------------------------
-// Role-specialised strip walker (the default for the exact arithmetic): the same two passes, same arithmetic and order
-// as k_polyexp, run by different waves.  A workgroup has 8 waves: waves 0-3 (thread <-> column) run the vertical pass
+// Role-specialised strip walker (the default, the reference library's arithmetic): the same two passes as k_polyexp,
+// run by different waves.  A workgroup has 8 waves: waves 0-3 (thread <-> column) run the vertical pass
 // of step t+1 while waves 4-7 (wave <-> row, lane <-> 4 pixels) run the horizontal pass of step t on the other half of
 // the double-buffered moment rows; one barrier per step.  Neither role carries the other's registers across its
 // pass (the column window of 2N+1 rows on one side, the moment window and the double taps on the other), so the
@@ -1907,8 +1818,7 @@ void launch_polyexp_n(nsof_ctx* ctx, int n_img, const float* img, int W, int H, 
     if (u8)
         hipLaunchKernelGGL((k_polyexp_rs<N, false, true>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, nullptr, *u8);
     else if (ctx->opt_polyexp_f32)
-        hipLaunchKernelGGL((k_polyexp<N, false, true>), grid, dim3(256), 0, ctx->stream, img, R, W, H, seg_rows, taps,
-                           nullptr);
+        hipLaunchKernelGGL((k_polyexp<N>), grid, dim3(256), 0, ctx->stream, img, R, W, H, seg_rows, taps, nullptr);
     else
         hipLaunchKernelGGL((k_polyexp_rs<N, false>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, nullptr);
 }

@@ -110,71 +110,15 @@ __device__ __forceinline__ void matrix_from(const RowIn& in, int x, int y, int W
     M[4] = r6 * r2 + r5 * r3;
 }
 
-// Where a thread's flow_in comes from.  UPS = false: the level's own flow buffer.  UPS = true (first iteration of
-// every level but the coarsest): the previous, coarser level's flow is resampled on the fly with exactly the
-// arithmetic of k_flow_upsample (resize INTER_LINEAR, then "flow *= 1/pyr_scale") -- the full-resolution initial
-// flow is then never written to or read from HBM.
-__device__ __forceinline__ void lin_x(int d, double scale, int slen, int& s, float& a)
-{
-    float f = (float)((d + 0.5) * scale - 0.5);
-    s = floor_f(f);
-    a = f - s;
-    if (s < 0) { s = 0; a = 0.f; }
-    if (s >= slen - 1) { s = slen - 1; a = 0.f; }
-}
-template <bool UPS>
-struct FlowSrc;
-// fetch() only issues loads (the result is consumed windows later); resolve() turns what was fetched into the flow.
-template <>
-struct FlowSrc<false> {
+// Where a thread's flow_in comes from: the level's own flow buffer.  fetch() only issues the load (the result is
+// consumed windows later).
+struct FlowSrc {
     const char* base;   // flow_in of this pair
     unsigned W, xc;
-    using Raw = float2;
-    __device__ __forceinline__ Raw fetch(int r) const
+    __device__ __forceinline__ float2 fetch(int r) const
     {
         return *reinterpret_cast<const float2*>(base + ((unsigned)r * W + xc) * 8u);
     }
-    __device__ __forceinline__ float2 resolve(const Raw& v) const { return v; }
-    __device__ __forceinline__ float2 at(int r) const { return fetch(r); }
-};
-template <>
-struct FlowSrc<true> {
-    const char* base;   // coarse flow of this pair, [sh][sw][2]
-    int sw, sh, sx, c1;
-    float a0, a1, mul;
-    double scale_y;
-    struct Raw {
-        float2 p00, p01, p10, p11;
-        float b1;
-    };
-    __device__ __forceinline__ Raw fetch(int r) const
-    {
-        Raw v;
-        float f = (float)((r + 0.5) * scale_y - 0.5);
-        const int sy = floor_f(f);
-        v.b1 = f - sy;
-        const unsigned r0 = (unsigned)clampi(sy, 0, sh - 1) * (unsigned)sw, r1 = (unsigned)clampi(sy + 1, 0, sh - 1) * (unsigned)sw;
-        v.p00 = *reinterpret_cast<const float2*>(base + (r0 + (unsigned)sx) * 8u);
-        v.p01 = *reinterpret_cast<const float2*>(base + (r0 + (unsigned)c1) * 8u);
-        v.p10 = *reinterpret_cast<const float2*>(base + (r1 + (unsigned)sx) * 8u);
-        v.p11 = *reinterpret_cast<const float2*>(base + (r1 + (unsigned)c1) * 8u);
-        return v;
-    }
-    __device__ __forceinline__ float2 resolve(const Raw& v) const
-    {
-        const float b1 = v.b1, b0 = 1.f - b1;
-        float2 o;
-        {
-            const float t0 = v.p00.x * a0 + v.p01.x * a1, t1 = v.p10.x * a0 + v.p11.x * a1;
-            o.x = (t0 * b0 + t1 * b1) * mul;
-        }
-        {
-            const float t0 = v.p00.y * a0 + v.p01.y * a1, t1 = v.p10.y * a0 + v.p11.y * a1;
-            o.y = (t0 * b0 + t1 * b1) * mul;
-        }
-        return o;
-    }
-    __device__ __forceinline__ float2 at(int r) const { return resolve(fetch(r)); }
 };
 
 // > 64 KB of dynamic LDS needs the opt-in attribute, once per (kernel instance, device); contexts of several

@@ -499,39 +499,32 @@ int nsof_check_farneback_params(nsof_ctx* ctx, int width, int height, double pyr
 }
 
 // ---- stage entry points ---------------------------------------------------------------------
+static int stage_pyr_level(nsof_ctx* ctx, int src, int n_img, const void* d_src, ptrdiff_t row_stride,
+                           ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out)
+{
+    if (!ctx || !d_src || !d_out || n_img < 1) return NSOF_EINVAL;
+    if (src == NSOF_SRC_F32 && (width < 1 || row_stride < (ptrdiff_t)width * 4 || (row_stride & 3) || (img_stride & 3) ||
+                                (reinterpret_cast<uintptr_t>(d_src) & 3)))
+        return nsof_set_error(ctx, NSOF_EINVAL, "f32 frames: strides must be multiples of 4 bytes, row_stride >= 4*width, "
+                                                "pointer 4-byte aligned");
+    int wk, hk;
+    nsof_blur_taps taps;
+    if (int rc = nsof_level_geom(ctx, width, height, pyr_scale, level, &wk, &hk, &taps)) return rc;
+    return NSOF_PYR_SEL(ctx, nsof_launch_prep, n_img, d_src, row_stride, img_stride, width, height, wk, hk, taps, d_out, src);
+}
+
 extern "C" int nsof_stage_pyr_level(nsof_ctx* ctx, int n_img, const uint8_t* d_src, ptrdiff_t row_stride,
                                     ptrdiff_t img_stride, int width, int height, double pyr_scale, int level,
                                     float* d_out)
 {
-    if (!ctx || !d_src || !d_out || n_img < 1) return NSOF_EINVAL;
-    int wk, hk, ks;
-    double sg;
-    int rc = nsof_farneback_level_size(width, height, pyr_scale, level, &wk, &hk, &ks, &sg);
-    if (rc) return nsof_set_error(ctx, rc, "bad level geometry");
-    nsof_blur_taps taps;
-    if ((rc = nsof_host_blur_taps(ks, sg, &taps)))
-        return nsof_set_error(ctx, rc, "pyramid blur kernel size %d unsupported (max %d)", ks, NSOF_MAX_BLUR_TAPS - 1);
-    return NSOF_PYR_SEL(ctx, nsof_launch_prep, n_img, d_src, row_stride, img_stride, width, height, wk, hk, taps, d_out);
+    return stage_pyr_level(ctx, NSOF_SRC_U8, n_img, d_src, row_stride, img_stride, width, height, pyr_scale, level, d_out);
 }
 
 extern "C" int nsof_stage_pyr_level_f32(nsof_ctx* ctx, int n_img, const float* d_src, ptrdiff_t row_stride,
                                         ptrdiff_t img_stride, int width, int height, double pyr_scale, int level,
                                         float* d_out)
 {
-    if (!ctx || !d_src || !d_out || n_img < 1) return NSOF_EINVAL;
-    if (width < 1 || row_stride < (ptrdiff_t)width * 4 || (row_stride & 3) || (img_stride & 3) ||
-        (reinterpret_cast<uintptr_t>(d_src) & 3))
-        return nsof_set_error(ctx, NSOF_EINVAL, "f32 frames: strides must be multiples of 4 bytes, row_stride >= 4*width, "
-                                                "pointer 4-byte aligned");
-    int wk, hk, ks;
-    double sg;
-    int rc = nsof_farneback_level_size(width, height, pyr_scale, level, &wk, &hk, &ks, &sg);
-    if (rc) return nsof_set_error(ctx, rc, "bad level geometry");
-    nsof_blur_taps taps;
-    if ((rc = nsof_host_blur_taps(ks, sg, &taps)))
-        return nsof_set_error(ctx, rc, "pyramid blur kernel size %d unsupported (max %d)", ks, NSOF_MAX_BLUR_TAPS - 1);
-    return NSOF_PYR_SEL(ctx, nsof_launch_prep, n_img, d_src, row_stride, img_stride, width, height, wk, hk, taps, d_out,
-                        NSOF_SRC_F32);
+    return stage_pyr_level(ctx, NSOF_SRC_F32, n_img, d_src, row_stride, img_stride, width, height, pyr_scale, level, d_out);
 }
 
 __global__ void k_recip_probe(long long n, const double* __restrict__ x, double* __restrict__ fast, double* __restrict__ ieee)
@@ -693,20 +686,37 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     if ((rc = nsof_host_poly_taps(poly_n, poly_sigma, &ptaps))) return nsof_set_error(ctx, rc, "poly taps");
     const int L = nsof_farneback_effective_levels(width, height, pyr_scale, levels);
 
-    // workspace: I [n_img][n0] f32, R [n_img][5*n0] f32, S = second flow buffer [B][n0][2]
-    // (+ M [B][5][n0] only when the window is too large for the fused iteration kernel)
+    // workspace: I [n_img][nk] f32 and R [n_img][5*nk] f32 (level images and expansions), S = second flow buffer
+    // [B][n0][2] (+ M [B][5][n0] only when the window is too large for the fused iteration kernel)
     const size_t n0 = (size_t)width * height, B = (size_t)n_pairs;
     const size_t n_img = sequence ? B + 1 : 2 * B;   // frames of a sequence, or B prev + B next frames
     // Fused or unfused is decided once for the whole pyramid (inputs below 2x2 take the unfused pair); the exact
     // row-sum order is fused only where k_iterate_x runs it.
     const bool fused = nsof_iterate_supported(winsize, width, height) && (!exact || exact_x);
-    const size_t szI = align_up(n_img * n0 * 4, 256), szR = align_up(n_img * 5 * n0 * 4, 256);
+    // ---- small batches (the three-kernel exact form): the latency schedule ---------------------------------------------
+    // A lone call is a chain of ~50 launches that each use a fraction of the chip and cost >= ~5 us (profiles/
+    // r03_lone_call_timeline.txt: 762 us at 1080p, a third of it in the two coarsest levels).  Only the FLOW couples the
+    // levels; pyramid level and polynomial expansion of every level depend on the input frames alone.  So they move to a
+    // side stream (levels L-1 .. 0, into per-level buffers) and run next to the iterations of the coarser levels on the
+    // main stream; an event per level hands the expansion over.  Same kernels, same arguments, same bits.
+    const bool lat = exact_lat && fused && L >= 1 && iterations > 0;
+    // level images and expansions: one slot that every level reuses, or one slot per level for the latency schedule
+    std::vector<size_t> offI(L + 1), offR(L + 1);   // (zeros)
+    size_t szI = 0, szR = 0;
+    for (int k = 0; k <= (lat ? L : 0); k++) {
+        int wk, hk;
+        nsof_farneback_level_size(width, height, pyr_scale, k, &wk, &hk, nullptr, nullptr);
+        offI[k] = szI;
+        offR[k] = szR;
+        szI += align_up(n_img * (size_t)wk * hk * 4, 256);
+        szR += align_up(n_img * 5 * (size_t)wk * hk * 4, 256);
+    }
     const size_t szS = align_up(B * n0 * 8, 256), szM = fused && !exact_lat ? 0 : align_up(B * 5 * n0 * 4, 256);
     const size_t szV = (exact && !exact_x) || exact_lat ? align_up(B * 5 * n0 * 8, 256) : 0;   // column sums of the unfused / three-kernel exact order
     if ((rc = nsof_ws_reserve(ctx, &ctx->ws, &ctx->ws_bytes, szI + szR + szS + szM + szV))) return rc;
-    char* base = (char*)ctx->ws;   // (re-derived below if the small-batch schedule grows the workspace)
-    float* dI = (float*)base;
-    float* dR = (float*)(base + szI);
+    char* base = (char*)ctx->ws;
+    auto level_I = [&](int k) { return (float*)(base + offI[k]); };
+    auto level_R = [&](int k) { return (float*)(base + szI + offR[k]); };
     float* dS = (float*)(base + szI + szR);
     float* dM = (float*)(base + szI + szR + szS);
     double* dV = (double*)(base + szI + szR + szS + szM);
@@ -737,40 +747,22 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     // two-kernel form (k_prep_same3_vec<.., float>, then the expansion of the level image).
     const bool poly_u8 = src == NSOF_SRC_U8 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && width >= 2 && height >= 2;
     float* Ifused[4] = {nullptr, nullptr, nullptr, nullptr};   // level images already made by the three-level launch
-    auto level_expansion = [&](int k, int wk, int hk, const nsof_blur_taps& bt, float* I, float* Rk) -> int {
+    // pyramid level + expansion of level k on the current ctx->stream, into the level's slot
+    auto level_images = [&](int k, int wk, int hk, const nsof_blur_taps& bt) -> int {
+        float* Rk = level_R(k);
         if (k >= 1 && k <= 3 && Ifused[k]) return nsof_launch_polyexp(ctx, (int)n_img, Ifused[k], wk, hk, ptaps, Rk);
         if (poly_u8 && k == 0 && bt.ksize == 3 && wk == width && hk == height) {
             const bool one = sequence || prep_merged;
             return nsof_launch_polyexp_u8(ctx, (int)n_img, d_prev, one ? d_prev : d_next, one ? (int)n_img : n_pairs, row_stride,
                                           pair_stride, width, height, ptaps, bt.k[1], bt.k[2], Rk);
         }
-        if (int r = prep_level(wk, hk, bt, I)) return r;
-        return nsof_launch_polyexp(ctx, (int)n_img, I, wk, hk, ptaps, Rk);
+        if (int r = prep_level(wk, hk, bt, level_I(k))) return r;
+        return nsof_launch_polyexp(ctx, (int)n_img, level_I(k), wk, hk, ptaps, Rk);
     };
 
-    // ---- small batches (the three-kernel exact form): the latency schedule ---------------------------------------------
-    // A lone call is a chain of ~50 launches that each use a fraction of the chip and cost >= ~5 us (profiles/
-    // r03_lone_call_timeline.txt: 762 us at 1080p, a third of it in the two coarsest levels).  Only the FLOW couples the
-    // levels; pyramid level and polynomial expansion of every level depend on the input frames alone.  So they move to a
-    // side stream (levels L-1 .. 0, into per-level buffers) and run next to the iterations of the coarser levels on the
-    // main stream; an event per level hands the expansion over.  Same kernels, same arguments, same bits.
-    if (exact_lat && fused && L >= 1 && iterations > 0) {
-        std::vector<size_t> offI(L + 1), offR(L + 1);
-        size_t totI = 0, totR = 0;
-        for (int k = 0; k <= L; k++) {
-            int wk, hk;
-            nsof_farneback_level_size(width, height, pyr_scale, k, &wk, &hk, nullptr, nullptr);
-            offI[k] = totI; offR[k] = totR;
-            totI += align_up(n_img * (size_t)wk * hk * 4, 256);
-            totR += align_up(n_img * 5 * (size_t)wk * hk * 4, 256);
-        }
-        if ((rc = nsof_ws_reserve(ctx, &ctx->ws, &ctx->ws_bytes, totI + totR + szS + szM + szV))) return rc;
-        base = (char*)ctx->ws;
-        float* dS2 = (float*)(base + totI + totR);
-        float* dM2 = (float*)(base + totI + totR + szS);
-        double* dV2 = (double*)(base + totI + totR + szS + szM);
-        float* fl[2] = {d_flow, dS2};
-        int c = (L * (1 + iterations) + iterations) & 1;
+    const hipStream_t mainS = ctx->stream;
+    if (lat) {
+        // the coarsest level is needed first: main stream; levels L-1 .. 0 on the side stream, an event after each
         if (!ctx->side) NSOF_HIP(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
         while (ctx->ov_events.size() < (size_t)(L + 2)) {
             hipEvent_t ev;
@@ -782,68 +774,32 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
             StreamSwap(nsof_ctx* cc, hipStream_t st) : cx(cc), saved(cc->stream) { cx->stream = st; }
             ~StreamSwap() { cx->stream = saved; }
         };
-        auto level_images = [&](int k) -> int {   // pyramid level + expansion of level k on the CURRENT ctx->stream
-            int wk, hk, ks;
-            double sg;
-            nsof_farneback_level_size(width, height, pyr_scale, k, &wk, &hk, &ks, &sg);
-            nsof_blur_taps bt;
-            if (int r = nsof_host_blur_taps(ks, sg, &bt))
-                return nsof_set_error(ctx, r, "pyramid blur kernel size %d unsupported (max %d)", ks, NSOF_MAX_BLUR_TAPS - 1);
-            return level_expansion(k, wk, hk, bt, (float*)(base + offI[k]), (float*)(base + totI + offR[k]));
-        };
-        const hipStream_t mainS = ctx->stream, sideS = ctx->side;
+        const hipStream_t sideS = ctx->side;
         NSOF_HIP(ctx, hipEventRecord(ctx->ov_events[L + 1], mainS));            // the frames are on the device; earlier calls are done
         NSOF_HIP(ctx, hipStreamWaitEvent(sideS, ctx->ov_events[L + 1], 0));
-        if ((rc = level_images(L))) return rc;                                  // the coarsest level: needed first, main stream
-        {
-            StreamSwap sw(ctx, sideS);
-            for (int k = L - 1; k >= 0; k--) {
-                if ((rc = level_images(k))) return rc;
-                NSOF_HIP(ctx, hipEventRecord(ctx->ov_events[k], sideS));
-            }
-        }
-        int pw2 = 0, ph2 = 0;
         for (int k = L; k >= 0; k--) {
             int wk, hk;
-            nsof_farneback_level_size(width, height, pyr_scale, k, &wk, &hk, nullptr, nullptr);
-            const size_t nk = (size_t)wk * hk;
-            if (k == L) {
-                NSOF_HIP(ctx, hipMemsetAsync(fl[c], 0, B * nk * 8, mainS));
-            } else {
-                if ((rc = NSOF_PYR_SEL(ctx, nsof_launch_flow_upsample, n_pairs, fl[c], pw2, ph2, fl[c ^ 1], wk, hk, (float)(1. / pyr_scale))))
-                    return rc;
-                c ^= 1;
-                NSOF_HIP(ctx, hipStreamWaitEvent(mainS, ctx->ov_events[k], 0));   // this level's expansion is ready
-            }
-            const float* R0 = (const float*)(base + totI + offR[k]);
-            const float* R1 = R0 + (sequence ? (size_t)1 : B) * 5 * nk;
-            for (int it = 0; it < iterations; it++) {
-                if ((rc = nsof_launch_iterate_lat(ctx, n_pairs, R0, R1, 5 * nk, fl[c], fl[c ^ 1], wk, hk, winsize, dM2, dV2))) return rc;
-                c ^= 1;
-            }
-            pw2 = wk;
-            ph2 = hk;
+            nsof_blur_taps bt;
+            if ((rc = nsof_level_geom(ctx, width, height, pyr_scale, k, &wk, &hk, &bt))) return rc;
+            StreamSwap sw(ctx, k == L ? mainS : sideS);
+            if ((rc = level_images(k, wk, hk, bt))) return rc;
+            if (k < L) NSOF_HIP(ctx, hipEventRecord(ctx->ov_events[k], sideS));
         }
-        if (fl[c] != d_flow)
-            NSOF_HIP(ctx, hipMemcpyAsync(d_flow, fl[c], B * n0 * 8, hipMemcpyDeviceToDevice, mainS));
-        return NSOF_OK;
-    }
-
-    // pyr_scale 0.5 with three coarser levels (the headline configuration): levels 1..3 smooth and decimate the same
-    // full-resolution frames -- one launch makes all three (k_prep_decim3), into the level-image buffer that level 0 no
-    // longer needs before the coarser levels are done with it
-    if (L == 3) {
+    } else if (L == 3) {
+        // pyr_scale 0.5 with three coarser levels (the headline configuration): levels 1..3 smooth and decimate the same
+        // full-resolution frames -- one launch makes all three (k_prep_decim3), into the level-image buffer that level 0
+        // no longer needs before the coarser levels are done with it
         nsof_blur_taps bt3[3];
         size_t nk3[3];
         bool exact3 = true;
         for (int k = 1; k <= 3 && exact3; k++) {
-            int wk, hk, ks;
-            double sg;
-            nsof_farneback_level_size(width, height, pyr_scale, k, &wk, &hk, &ks, &sg);
-            exact3 = wk * (1 << k) == width && hk * (1 << k) == height && nsof_host_blur_taps(ks, sg, &bt3[k - 1]) == 0;
+            int wk, hk;
+            exact3 = nsof_level_geom(nullptr, width, height, pyr_scale, k, &wk, &hk, &bt3[k - 1]) == 0 &&
+                     wk * (1 << k) == width && hk * (1 << k) == height;
             nk3[k - 1] = (size_t)wk * hk;
         }
         if (exact3) {
+            float* dI = level_I(0);
             float* I3[3] = {dI, dI + n_img * nk3[0], dI + n_img * (nk3[0] + nk3[1])};
             const bool one = sequence || prep_merged;
             rc = NSOF_PYR_SEL(ctx, nsof_launch_prep_decim3, one ? (int)n_img : n_pairs, d_prev, row_stride, pair_stride, width, height, bt3, I3, src);
@@ -859,30 +815,29 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
         }
     }
 
-    bool have_prev = false;
     int pw = 0, ph = 0;
     for (int k = L; k >= 0; k--) {
-        int wk, hk, ks;
-        double sg;
-        nsof_farneback_level_size(width, height, pyr_scale, k, &wk, &hk, &ks, &sg);
+        int wk, hk;
         nsof_blur_taps btaps;
-        if ((rc = nsof_host_blur_taps(ks, sg, &btaps)))
-            return nsof_set_error(ctx, rc, "pyramid blur kernel size %d unsupported (max %d)", ks,
-                                  NSOF_MAX_BLUR_TAPS - 1);
+        if ((rc = nsof_level_geom(ctx, width, height, pyr_scale, k, &wk, &hk, &btaps))) return rc;
         const size_t nk = (size_t)wk * hk;
-        if (!have_prev) {
-            NSOF_HIP(ctx, hipMemsetAsync(fb[cur], 0, B * nk * 8, ctx->stream));
+        if (k == L) {
+            NSOF_HIP(ctx, hipMemsetAsync(fb[cur], 0, B * nk * 8, mainS));
         } else {
             if ((rc = NSOF_PYR_SEL(ctx, nsof_launch_flow_upsample, n_pairs, fb[cur], pw, ph, fb[cur ^ 1], wk, hk,
-                                                (float)(1. / pyr_scale))))
+                                   (float)(1. / pyr_scale))))
                 return rc;
             cur ^= 1;
         }
-        // image-major: dI [n_img][hk][wk], dR [n_img][5*hk*wk].  Pairs: all prev frames then all next frames
+        if (!lat) {
+            if ((rc = level_images(k, wk, hk, btaps))) return rc;
+        } else if (k < L) {
+            NSOF_HIP(ctx, hipStreamWaitEvent(mainS, ctx->ov_events[k], 0));   // this level's expansion is ready
+        }
+        // image-major: I [n_img][hk][wk], R [n_img][5*hk*wk].  Pairs: all prev frames then all next frames
         // (R1 = R0 + B images); sequence: the frames in order (R1 = R0 + 1 image).
-        if ((rc = level_expansion(k, wk, hk, btaps, dI, dR))) return rc;
-        const float* R0 = dR;
-        const float* R1 = dR + (sequence ? (size_t)1 : B) * 5 * nk;
+        const float* R0 = level_R(k);
+        const float* R1 = R0 + (sequence ? (size_t)1 : B) * 5 * nk;
         if (fused) {
             for (int it = 0; it < iterations; it++) {
                 if (exact_lat)
@@ -905,12 +860,11 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
                     if ((rc = nsof_launch_update_matrices(ctx, n_pairs, R0, R1, 5 * nk, flow, wk, hk, dM))) return rc;
             }
         }
-        have_prev = true;
         pw = wk;
         ph = hk;
     }
     if (fb[cur] != d_flow)  // cannot happen by construction; keep the result correct regardless
-        NSOF_HIP(ctx, hipMemcpyAsync(d_flow, fb[cur], B * n0 * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        NSOF_HIP(ctx, hipMemcpyAsync(d_flow, fb[cur], B * n0 * 8, hipMemcpyDeviceToDevice, mainS));
     return NSOF_OK;
 }
 
@@ -974,23 +928,26 @@ extern "C" int nsof_farneback_f32_sequence_dev(nsof_ctx* ctx, int n_frames, cons
                                pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, NSOF_SRC_F32);
 }
 
-extern "C" int nsof_farneback_f32(nsof_ctx* ctx, const float* prev, ptrdiff_t prev_stride, const float* next,
-                                  ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
-                                  double pyr_scale, int levels, int winsize, int iterations, int poly_n,
-                                  double poly_sigma, int flags)
+// The host-pointer pair entries, src: nsof_src_type.  Dense frames go straight from the caller's memory; strided host
+// views are packed row by row into a pinned staging buffer and moved with ONE linear copy per direction: hipMemcpy2D
+// degenerates to a copy per row for widths that are not nicely aligned (measured 12 ms for an 801x801 pair against
+// 3 ms of kernels).  On the device the pair lies back to back (one pyramid launch per level for both frames).
+static int farneback_host_pair(nsof_ctx* ctx, int src, const void* prev, ptrdiff_t prev_stride, const void* next,
+                               ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
+                               double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma,
+                               int flags)
 {
     if (!ctx) return NSOF_EINVAL;
     if (!prev || !next || !flow) return nsof_set_error(ctx, NSOF_EINVAL, "null image pointer");
     int rc = nsof_check_farneback_params(ctx, width, height, pyr_scale, levels, winsize, iterations, poly_n, flags);
     if (rc) return rc;
-    if ((rc = check_f32_layout(ctx, prev, prev_stride, 0, width)) || (rc = check_f32_layout(ctx, next, next_stride, 0, width)))
+    if (src == NSOF_SRC_F32 &&
+        ((rc = check_f32_layout(ctx, prev, prev_stride, 0, width)) || (rc = check_f32_layout(ctx, next, next_stride, 0, width))))
         return rc;
     if (flow_stride < (ptrdiff_t)(width * 8)) return nsof_set_error(ctx, NSOF_EINVAL, "flow_stride < width*8");
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    // as nsof_farneback_u8: dense frames go straight from the caller's memory, strided ones are packed into pinned
-    // staging first; on the device the pair lies back to back (one pyramid launch per level for both frames)
-    const size_t n0 = (size_t)width * height, pitch = (size_t)width * 4;
-    const size_t szU = align_up(n0 * 4, 256), szF = align_up(n0 * 8, 256);
+    const size_t n0 = (size_t)width * height, pitch = (size_t)width * (src == NSOF_SRC_F32 ? 4 : 1);
+    const size_t szU = align_up(pitch * height, 256), szF = align_up(n0 * 8, 256);
     if ((rc = nsof_ws_reserve(ctx, &ctx->stage, &ctx->stage_bytes, 2 * szU + szF))) return rc;
     if ((rc = nsof_hstage_reserve(ctx, 2 * szU + szF))) return rc;
     char* hP = (char*)ctx->hstage;
@@ -1002,8 +959,8 @@ extern "C" int nsof_farneback_f32(nsof_ctx* ctx, const float* prev, ptrdiff_t pr
     const bool in_dense = prev_stride == (ptrdiff_t)pitch && next_stride == (ptrdiff_t)pitch;
     const bool out_dense = flow_stride == (ptrdiff_t)width * 8;
     if (in_dense) {
-        NSOF_HIP(ctx, hipMemcpyAsync(dP, prev, n0 * 4, hipMemcpyHostToDevice, ctx->stream));
-        NSOF_HIP(ctx, hipMemcpyAsync(dN, next, n0 * 4, hipMemcpyHostToDevice, ctx->stream));
+        NSOF_HIP(ctx, hipMemcpyAsync(dP, prev, pitch * height, hipMemcpyHostToDevice, ctx->stream));
+        NSOF_HIP(ctx, hipMemcpyAsync(dN, next, pitch * height, hipMemcpyHostToDevice, ctx->stream));
     } else {
         for (int y = 0; y < height; y++) {
             memcpy(hP + (size_t)y * pitch, (const char*)prev + (ptrdiff_t)y * prev_stride, pitch);
@@ -1012,54 +969,7 @@ extern "C" int nsof_farneback_f32(nsof_ctx* ctx, const float* prev, ptrdiff_t pr
         NSOF_HIP(ctx, hipMemcpyAsync(dP, hP, 2 * szU, hipMemcpyHostToDevice, ctx->stream));
     }
     rc = nsof_farneback_core(ctx, false, 1, dP, dN, (ptrdiff_t)pitch, (ptrdiff_t)szU, width, height, dFl, pyr_scale, levels,
-                             winsize, iterations, poly_n, poly_sigma, flags, NSOF_SRC_F32);
-    if (rc) return rc;
-    NSOF_HIP(ctx, hipMemcpyAsync(out_dense ? flow : hF, dFl, n0 * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = nsof_stream_sync_checked(ctx))) return rc;
-    if (!out_dense)
-        for (int y = 0; y < height; y++)
-            memcpy((char*)flow + (ptrdiff_t)y * flow_stride, hF + (size_t)y * width * 2, (size_t)width * 8);
-    return NSOF_OK;
-}
-
-extern "C" int nsof_farneback_u8(nsof_ctx* ctx, const uint8_t* prev, ptrdiff_t prev_stride, const uint8_t* next,
-                                 ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
-                                 double pyr_scale, int levels, int winsize, int iterations, int poly_n,
-                                 double poly_sigma, int flags)
-{
-    if (!ctx) return NSOF_EINVAL;
-    if (!prev || !next || !flow) return nsof_set_error(ctx, NSOF_EINVAL, "null image pointer");
-    int rc = nsof_check_farneback_params(ctx, width, height, pyr_scale, levels, winsize, iterations, poly_n, flags);
-    if (rc) return rc;
-    if (flow_stride < (ptrdiff_t)(width * 8)) return nsof_set_error(ctx, NSOF_EINVAL, "flow_stride < width*8");
-    NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    // Strided host views are packed row by row into a pinned staging buffer and moved with ONE linear copy per
-    // direction: hipMemcpy2D degenerates to a copy per row for widths that are not nicely aligned (measured 12 ms
-    // for an 801x801 pair against 3 ms of kernels).
-    const size_t n0 = (size_t)width * height, pitch = (size_t)width;
-    const size_t szU = align_up(n0, 256), szF = align_up(n0 * 8, 256);
-    if ((rc = nsof_ws_reserve(ctx, &ctx->stage, &ctx->stage_bytes, 2 * szU + szF))) return rc;
-    if ((rc = nsof_hstage_reserve(ctx, 2 * szU + szF))) return rc;
-    uint8_t* hP = (uint8_t*)ctx->hstage;
-    uint8_t* hN = hP + szU;
-    float* hF = (float*)(hN + szU);
-    uint8_t* dP = (uint8_t*)ctx->stage;
-    uint8_t* dN = dP + szU;
-    float* dFl = (float*)(dN + szU);
-    const bool in_dense = prev_stride == (ptrdiff_t)width && next_stride == (ptrdiff_t)width;
-    const bool out_dense = flow_stride == (ptrdiff_t)width * 8;
-    if (in_dense) {   // contiguous frames: straight from the caller's memory
-        NSOF_HIP(ctx, hipMemcpyAsync(dP, prev, n0, hipMemcpyHostToDevice, ctx->stream));
-        NSOF_HIP(ctx, hipMemcpyAsync(dN, next, n0, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        for (int y = 0; y < height; y++) {
-            memcpy(hP + (size_t)y * width, prev + (ptrdiff_t)y * prev_stride, (size_t)width);
-            memcpy(hN + (size_t)y * width, next + (ptrdiff_t)y * next_stride, (size_t)width);
-        }
-        NSOF_HIP(ctx, hipMemcpyAsync(dP, hP, 2 * szU, hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = nsof_farneback_u8_batch_dev(ctx, 1, dP, dN, (ptrdiff_t)pitch, (ptrdiff_t)szU, width, height, dFl, pyr_scale,
-                                     levels, winsize, iterations, poly_n, poly_sigma, flags);
+                             winsize, iterations, poly_n, poly_sigma, flags, src);
     if (rc) return rc;
     NSOF_HIP(ctx, hipMemcpyAsync(out_dense ? flow : hF, dFl, n0 * 8, hipMemcpyDeviceToHost, ctx->stream));
     // a hand-over between workgroups that never arrived (the exact-order kernels' bounded waits) fails the call, as cv2
@@ -1069,6 +979,24 @@ extern "C" int nsof_farneback_u8(nsof_ctx* ctx, const uint8_t* prev, ptrdiff_t p
         for (int y = 0; y < height; y++)
             memcpy((char*)flow + (ptrdiff_t)y * flow_stride, hF + (size_t)y * width * 2, (size_t)width * 8);
     return NSOF_OK;
+}
+
+extern "C" int nsof_farneback_f32(nsof_ctx* ctx, const float* prev, ptrdiff_t prev_stride, const float* next,
+                                  ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
+                                  double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                                  double poly_sigma, int flags)
+{
+    return farneback_host_pair(ctx, NSOF_SRC_F32, prev, prev_stride, next, next_stride, width, height, flow, flow_stride,
+                               pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
+}
+
+extern "C" int nsof_farneback_u8(nsof_ctx* ctx, const uint8_t* prev, ptrdiff_t prev_stride, const uint8_t* next,
+                                 ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
+                                 double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                                 double poly_sigma, int flags)
+{
+    return farneback_host_pair(ctx, NSOF_SRC_U8, prev, prev_stride, next, next_stride, width, height, flow, flow_stride,
+                               pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
 }
 
 // ---- ROI gating (host arithmetic on maps of at most a few hundred cells) -------------------------------------------

@@ -125,6 +125,18 @@ struct nsof_poly_taps {
 };
 
 int nsof_host_blur_taps(int ksize, double sigma, nsof_blur_taps* out);
+// Size (wk / hk may be null) and pyramid blur taps of a level; on failure the error is set on ctx unless ctx is null.
+static inline int nsof_level_geom(nsof_ctx* ctx, int width, int height, double pyr_scale, int level, int* wk, int* hk,
+                                  nsof_blur_taps* bt)
+{
+    int ks;
+    double sg;
+    int rc = nsof_farneback_level_size(width, height, pyr_scale, level, wk, hk, &ks, &sg);
+    if (rc) return ctx ? nsof_set_error(ctx, rc, "bad level geometry") : rc;
+    if ((rc = nsof_host_blur_taps(ks, sg, bt)) && ctx)
+        return nsof_set_error(ctx, rc, "pyramid blur kernel size %d unsupported (max %d)", ks, NSOF_MAX_BLUR_TAPS - 1);
+    return rc;
+}
 int nsof_host_poly_taps(int n, double sigma, nsof_poly_taps* out);
 
 // ---- shape-heterogeneous work lists (nsof_farneback_u8_batch*, nsof_farneback_f32_batch*) -----------------------

@@ -243,15 +243,9 @@ def _desc_array(pairs, flows, host, f32=False):
     px = 4 if f32 else 1
     for i, ((prev, nxt), flow) in enumerate(zip(pairs, flows)):
         d = descs[i]
-        if host and f32:
-            if prev.shape != nxt.shape:
-                raise NsofValueError(f"pair {i}: prev {prev.shape} and next {nxt.shape} sizes differ", _lib.NSOF_ESHAPE)
-            keep += [prev, nxt]
-            h, w = prev.shape
-            d.prev, d.prev_stride, d.next, d.next_stride = prev.ctypes.data, prev.strides[0], nxt.ctypes.data, nxt.strides[0]
-            d.flow, d.flow_stride = flow.ctypes.data, flow.strides[0]
-        elif host:
-            prev, nxt = _as_gray_u8(prev, "prev"), _as_gray_u8(nxt, "next")
+        if host:
+            if not f32:
+                prev, nxt = _as_gray_u8(prev, "prev"), _as_gray_u8(nxt, "next")
             if prev.shape != nxt.shape:
                 raise NsofValueError(f"pair {i}: prev {prev.shape} and next {nxt.shape} sizes differ", _lib.NSOF_ESHAPE)
             keep += [prev, nxt]
@@ -369,26 +363,24 @@ def farneback_pairs(pairs, params, flows=None, *, pinned=False, ctx=None):
         return []
     if _host_list_is_u8(pairs):
         descs, keep = _desc_array(pairs, flows, host=True)
-        rc = ctx._lib.nsof_farneback_u8_batch(ctx.ptr, len(pairs), descs, float(kw["pyr_scale"]), int(kw["levels"]),
-                                              int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]),
-                                              float(kw["poly_sigma"]), int(kw["flags"]))
-        ctx.check(rc, "farneback_pairs")
+        _desc_batch_call(ctx, ctx._lib.nsof_farneback_u8_batch, descs, kw, "farneback_pairs")
         del keep
         return flows
     with ctx.lock:
         descs, keep = _desc_array(_f32_host_frames(pairs, ctx), flows, host=True, f32=True)
-        rc = ctx._lib.nsof_farneback_f32_batch(ctx.ptr, len(pairs), descs, float(kw["pyr_scale"]), int(kw["levels"]),
-                                               int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]),
-                                               float(kw["poly_sigma"]), int(kw["flags"]))
-        ctx.check(rc, "farneback_pairs")
+        _desc_batch_call(ctx, ctx._lib.nsof_farneback_f32_batch, descs, kw, "farneback_pairs")
     del keep
     return flows
 
 
-def farneback_pairs_dev(pairs, flows, params, *, ctx=None):
-    """Device-resident twin (``nsof_farneback_u8_batch_desc_dev``): ``pairs`` = [(prev, next), ...] of uint8 CUDA
-    tensors (any row stride: crops ``frame[y0:y1, x0:x1]`` of frames in HBM), ``flows`` = float32 (h, w, 2) CUDA
-    tensors or crops of a frame-sized canvas, written in place.  Asynchronous on the context's stream."""
+def _desc_batch_call(ctx, entry, descs, kw, what):
+    """One native work-list call (``nsof_farneback_{u8,f32}_batch[_desc_dev]``) on a descriptor array."""
+    rc = entry(ctx.ptr, len(descs), descs, float(kw["pyr_scale"]), int(kw["levels"]), int(kw["winsize"]),
+               int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]), int(kw["flags"]))
+    ctx.check(rc, what)
+
+
+def _pairs_dev(pairs, flows, params, ctx, f32):
     ctx = ctx or default_context()
     kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
     pairs, flows = list(pairs), list(flows)
@@ -396,11 +388,18 @@ def farneback_pairs_dev(pairs, flows, params, *, ctx=None):
         raise NsofValueError("flows and pairs differ in length")
     if not pairs:
         return
-    descs, _ = _desc_array(pairs, flows, host=False)
-    rc = ctx._lib.nsof_farneback_u8_batch_desc_dev(ctx.ptr, len(pairs), descs, float(kw["pyr_scale"]), int(kw["levels"]),
-                                                   int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]),
-                                                   float(kw["poly_sigma"]), int(kw["flags"]))
-    ctx.check(rc, "farneback_pairs_dev")
+    descs, _ = _desc_array(pairs, flows, host=False, f32=f32)
+    if f32:
+        _desc_batch_call(ctx, ctx._lib.nsof_farneback_f32_batch_desc_dev, descs, kw, "farneback_pairs_f32_dev")
+    else:
+        _desc_batch_call(ctx, ctx._lib.nsof_farneback_u8_batch_desc_dev, descs, kw, "farneback_pairs_dev")
+
+
+def farneback_pairs_dev(pairs, flows, params, *, ctx=None):
+    """Device-resident twin (``nsof_farneback_u8_batch_desc_dev``): ``pairs`` = [(prev, next), ...] of uint8 CUDA
+    tensors (any row stride: crops ``frame[y0:y1, x0:x1]`` of frames in HBM), ``flows`` = float32 (h, w, 2) CUDA
+    tensors or crops of a frame-sized canvas, written in place.  Asynchronous on the context's stream."""
+    _pairs_dev(pairs, flows, params, ctx, f32=False)
 
 
 def farneback_pairs_f32_dev(pairs, flows, params, *, ctx=None):
@@ -408,18 +407,7 @@ def farneback_pairs_f32_dev(pairs, flows, params, *, ctx=None):
     of float32 CUDA tensors (crops of frames in HBM: rows 4-byte aligned, any row stride), ``flows`` as there.  Each
     result equals ``calcOpticalFlowFarneback`` of that pair's frames bit for bit.  Other dtypes raise ``NsofValueError``.
     Asynchronous on the context's stream."""
-    ctx = ctx or default_context()
-    kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
-    pairs, flows = list(pairs), list(flows)
-    if len(flows) != len(pairs):
-        raise NsofValueError("flows and pairs differ in length")
-    if not pairs:
-        return
-    descs, _ = _desc_array(pairs, flows, host=False, f32=True)
-    rc = ctx._lib.nsof_farneback_f32_batch_desc_dev(ctx.ptr, len(pairs), descs, float(kw["pyr_scale"]), int(kw["levels"]),
-                                                    int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]),
-                                                    float(kw["poly_sigma"]), int(kw["flags"]))
-    ctx.check(rc, "farneback_pairs_f32_dev")
+    _pairs_dev(pairs, flows, params, ctx, f32=True)
 
 
 def _roi_sequence_args(frames, counts, rects, flows):
@@ -431,6 +419,28 @@ def _roi_sequence_args(frames, counts, rects, flows):
     return n, h, w
 
 
+def _roi_sequence_dev(frames, counts, rects, flows, params, gate_frame, ctx, f32):
+    ctx = ctx or default_context()
+    kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
+    if f32 and _tensor_dtype(frames) != "float32":
+        raise NsofValueError(f"frames must be a float32 tensor (got {_tensor_dtype(frames)}); 8-bit frames take "
+                             "farneback_roi_sequence_dev")
+    if not f32 and _tensor_dtype(frames) not in (None, "uint8"):
+        raise NsofValueError(f"frames must be a uint8 tensor (got {_tensor_dtype(frames)}); float32 frames take "
+                             "farneback_roi_sequence_f32_dev")
+    n, h, w = _roi_sequence_args(frames, counts, rects, flows)
+    px = 4 if f32 else 1   # strides in bytes
+    entry, what = ((ctx._lib.nsof_farneback_f32_roi_sequence_dev, "farneback_roi_sequence_f32_dev") if f32 else
+                   (ctx._lib.nsof_farneback_u8_roi_sequence_dev, "farneback_roi_sequence_dev"))
+    calls, pixels = C.c_longlong(), C.c_longlong()
+    rc = entry(ctx.ptr, n, dev_ptr(frames), int(frames.stride(1)) * px, int(frames.stride(0)) * px, w, h, dev_ptr(counts),
+               dev_ptr(rects), int(rects.shape[1]), dev_ptr(flows), float(kw["pyr_scale"]), int(kw["levels"]),
+               int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]), int(kw["flags"]),
+               int(gate_frame), C.byref(calls), C.byref(pixels))
+    ctx.check(rc, what)
+    return calls.value, pixels.value
+
+
 def farneback_roi_sequence_dev(frames, counts, rects, flows, params, *, gate_frame=0, ctx=None):
     """The gated path of a frame sequence on the device (``nsof_farneback_u8_roi_sequence_dev``; opticalFlow3D's crop ->
     flow -> paste loop, optical_flow_seg.py:129-164, 186-204): ``frames`` uint8 CUDA tensor [n][H][W] (row stride free),
@@ -440,40 +450,14 @@ def farneback_roi_sequence_dev(frames, counts, rects, flows, params, *, gate_fra
     optical_flow_seg.py:435; ``GatingConfig.bug_compatible``), 1 = the map of its second frame (what ``opticalFlow3D``
     is written to use).  All crops of all pairs form one work list; overlapping crops of a pair are pasted in label order.
     -> (n_crops, crop_pixels)."""
-    ctx = ctx or default_context()
-    kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
-    if _tensor_dtype(frames) not in (None, "uint8"):
-        raise NsofValueError(f"frames must be a uint8 tensor (got {_tensor_dtype(frames)}); float32 frames take "
-                             "farneback_roi_sequence_f32_dev")
-    n, h, w = _roi_sequence_args(frames, counts, rects, flows)
-    calls, pixels = C.c_longlong(), C.c_longlong()
-    rc = ctx._lib.nsof_farneback_u8_roi_sequence_dev(
-        ctx.ptr, n, dev_ptr(frames), int(frames.stride(1)), int(frames.stride(0)), w, h, dev_ptr(counts), dev_ptr(rects),
-        int(rects.shape[1]), dev_ptr(flows), float(kw["pyr_scale"]), int(kw["levels"]), int(kw["winsize"]),
-        int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]), int(kw["flags"]), int(gate_frame), C.byref(calls),
-        C.byref(pixels))
-    ctx.check(rc, "farneback_roi_sequence_dev")
-    return calls.value, pixels.value
+    return _roi_sequence_dev(frames, counts, rects, flows, params, gate_frame, ctx, f32=False)
 
 
 def farneback_roi_sequence_f32_dev(frames, counts, rects, flows, params, *, gate_frame=0, ctx=None):
     """``farneback_roi_sequence_dev`` for float32 frames (``nsof_farneback_f32_roi_sequence_dev``): ``frames`` float32 CUDA
     tensor [n][H][W] (row stride free); every crop's flow equals ``calcOpticalFlowFarneback`` of the float crops, pasted as
     there.  Other dtypes raise ``NsofValueError``.  -> (n_crops, crop_pixels)."""
-    ctx = ctx or default_context()
-    kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
-    if _tensor_dtype(frames) != "float32":
-        raise NsofValueError(f"frames must be a float32 tensor (got {_tensor_dtype(frames)}); 8-bit frames take "
-                             "farneback_roi_sequence_dev")
-    n, h, w = _roi_sequence_args(frames, counts, rects, flows)
-    calls, pixels = C.c_longlong(), C.c_longlong()
-    rc = ctx._lib.nsof_farneback_f32_roi_sequence_dev(
-        ctx.ptr, n, dev_ptr(frames), int(frames.stride(1)) * 4, int(frames.stride(0)) * 4, w, h, dev_ptr(counts),
-        dev_ptr(rects), int(rects.shape[1]), dev_ptr(flows), float(kw["pyr_scale"]), int(kw["levels"]), int(kw["winsize"]),
-        int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]), int(kw["flags"]), int(gate_frame), C.byref(calls),
-        C.byref(pixels))
-    ctx.check(rc, "farneback_roi_sequence_f32_dev")
-    return calls.value, pixels.value
+    return _roi_sequence_dev(frames, counts, rects, flows, params, gate_frame, ctx, f32=True)
 
 
 def effective_levels(width, height, pyr_scale, levels):
