@@ -512,6 +512,29 @@ int nsof_ssim_u8_dev(nsof_ctx* ctx, const uint8_t* d_a, ptrdiff_t a_stride, int 
                      double* ssim_out);
 int nsof_ssim_u8(nsof_ctx* ctx, const uint8_t* a, ptrdiff_t a_stride, int a_pixel_step, const uint8_t* b,
                  ptrdiff_t b_stride, int b_pixel_step, int width, int height, double data_range, double* ssim_out);
+/* The prediction step of every pair of a sequence in ONE launch (optical_flow_prediction.py:435-681, task_results
+ * :257-361 and the full-frame baseline :569-591).  d_frames: n_pairs + 1 interleaved 3-channel (BGR) uint8 frames,
+ * strides in bytes; pair k reads frame k + 1 and the flow canvas k of d_flows, float32 [n_pairs][height][width][2] (dense,
+ * 8-byte aligned), and writes prediction k of d_out, uint8 [n_pairs][height][width][3] (dense) -- in full: pixels
+ * outside the pair's region are copies of frame k + 1, so d_out needs no pre-fill.  Region: with d_counts / d_rects
+ * (the device table of nsof_roi_from_surface_dev, [n_maps] and [n_maps][max_rects][4], the table the ROI flow call
+ * consumed) the rectangles of map k + gate_frame (gate_frame 0 or 1, as nsof_farneback_u8_roi_sequence_dev), their union
+ * for merge_padding < 0 (FLAG 1 with MERGE_FLAG False; FLAG 2, one box), their bounding box padded by merge_padding
+ * and clipped to the frame for merge_padding >= 0 (MERGE_FLAG True, PADDING 20); a map without rectangles leaves the
+ * frame as it is.  The caller guarantees counts <= max_rects (the launch cannot see them beforehand; larger counts are
+ * read as max_rects).  d_counts == NULL: the whole frame (the baseline; border_mode NSOF_BORDER_CONSTANT, value 0).
+ * Every pixel is computed as nsof_predict_warp_u8_dev computes it (map = float32(float64(grid) + sign * flow)), so
+ * prediction k equals that entry applied box by box onto a copy of the frame, bit for bit.  Asynchronous. */
+int nsof_predict_sequence_u8_dev(nsof_ctx* ctx, int n_pairs, const uint8_t* d_frames, ptrdiff_t row_stride,
+                                 ptrdiff_t frame_stride, int width, int height, const float* d_flows, int sign,
+                                 const int32_t* d_counts, const int32_t* d_rects, int n_maps, int max_rects,
+                                 int gate_frame, int merge_padding, int border_mode, uint8_t* d_out);
+/* nsof_ssim_u8_dev of n image pairs (pair i at d_a + i * a_item_stride, d_b + i * b_item_stride, bytes) into the DEVICE
+ * doubles d_out[n]: same tile grid and reduction order per pair, so d_out[i] == nsof_ssim_u8_dev of pair i exactly.
+ * Asynchronous: never waits for the stream (only growing the context's workspace, on a first or larger call, does). */
+int nsof_ssim_u8_batch_dev(nsof_ctx* ctx, int n, const uint8_t* d_a, ptrdiff_t a_stride, ptrdiff_t a_item_stride,
+                           int a_pixel_step, const uint8_t* d_b, ptrdiff_t b_stride, ptrdiff_t b_item_stride,
+                           int b_pixel_step, int width, int height, double data_range, double* d_out);
 
 #ifdef __cplusplus
 }

@@ -6,8 +6,11 @@
 //                          the map from the flow canvas in the kernel (float32(double(x) - double(f)), as NumPy
 //                          does) so the float maps never exist in memory: 8 B/px flow in, CN B/px out, plus the
 //                          gathered source (read once through L2 for a smooth field).
+//   k_predict_seq_u8       the prediction of every pair of a sequence in one launch: remap_px<3, true> (k_remap_u8's
+//                          pixel) inside the region the device rectangle table gives, a copy of the frame outside.
 //   k_ssim_partial/final   SSIM of one channel: exact integer 7x7 window sums (separable, through LDS), S in double,
-//                          fixed-order reduction (per-block partials, then one block) -> deterministic.
+//                          fixed-order reduction (per-block partials, then one block) -> deterministic.  blockIdx.z of
+//                          the partials / blockIdx.x of the final block index the pairs of a batch.
 #include <cmath>
 #include <cstring>
 
@@ -27,14 +30,11 @@ struct MapSrc {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// One thread per destination pixel, all CN interleaved channels.
+// Destination pixel (x, y), all CN interleaved channels, written at o.
 template <int CN, bool FUSED>
-__global__ __launch_bounds__(256) void k_remap_u8(const uint8_t* __restrict__ src, ptrdiff_t sstride, int sw, int sh,
-                                                  MapSrc m, int dw, int dh, int border, int cval,
-                                                  uint8_t* __restrict__ dst, ptrdiff_t dstride)
+__device__ __forceinline__ void remap_px(const uint8_t* __restrict__ src, ptrdiff_t sstride, int sw, int sh,
+                                         const MapSrc& m, int x, int y, int border, int cval, uint8_t* __restrict__ o)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= dw || y >= dh) return;
     float mx, my;
     if (FUSED) {
         const float2 f = *(const float2*)(m.a + (ptrdiff_t)(m.y0 + y - m.oy) * m.astride + 2 * (m.x0 + x - m.ox));
@@ -50,7 +50,6 @@ __global__ __launch_bounds__(256) void k_remap_u8(const uint8_t* __restrict__ sr
     const int fx = lx & 31, fy = ly & 31;
     const int ix = clampi(lx >> 5, -32768, 32767), iy = clampi(ly >> 5, -32768, 32767);
     const int w0 = (32 - fx) * (32 - fy) * 32, w1 = fx * (32 - fy) * 32, w2 = (32 - fx) * fy * 32, w3 = fx * fy * 32;
-    uint8_t* o = dst + (ptrdiff_t)y * dstride + x * CN;
     int x0, x1, y0, y1;
     bool in00 = true, in01 = true, in10 = true, in11 = true;
     if (border == 1) {   // BORDER_REPLICATE: clamp the tap coordinates
@@ -93,17 +92,84 @@ __global__ __launch_bounds__(256) void k_remap_u8(const uint8_t* __restrict__ sr
     }
 }
 
+// One thread per destination pixel.
+template <int CN, bool FUSED>
+__global__ __launch_bounds__(256) void k_remap_u8(const uint8_t* __restrict__ src, ptrdiff_t sstride, int sw, int sh,
+                                                  MapSrc m, int dw, int dh, int border, int cval,
+                                                  uint8_t* __restrict__ dst, ptrdiff_t dstride)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= dw || y >= dh) return;
+    remap_px<CN, FUSED>(src, sstride, sw, sh, m, x, y, border, cval, dst + (ptrdiff_t)y * dstride + x * CN);
+}
+
+// The prediction of every pair of a sequence in one launch (nsof_predict_sequence_u8_dev): blockIdx.z = pair k, which
+// reads frame k+1 and flow canvas k [h][w][2] and writes prediction k [h][w][3] (dense) -- remap_px<3, true> inside
+// the pair's region, a copy of the frame outside, so no pre-fill pass.  The source is always the whole frame and the
+// map depends only on the pixel, so a pixel's value does not depend on which box covers it: "warp inside the union of
+// the boxes" equals the box-by-box composition of optical_flow_prediction.py:263-353.  TABLE: the region is the
+// rectangles of gating map k + gate_frame, or (merge_padding >= 0) their bounding box padded by merge_padding and
+// clipped to the frame (:268-275); counts above max_rects are clamped, a rectangle's values are only compared, never
+// used as addresses.  !TABLE: the whole frame (the full-frame baseline, :581-591).
+template <bool TABLE>
+__global__ __launch_bounds__(256) void k_predict_seq_u8(const uint8_t* __restrict__ frames, ptrdiff_t row_stride,
+                                                        ptrdiff_t frame_stride, int w, int h,
+                                                        const float* __restrict__ flows, int sign,
+                                                        const int* __restrict__ counts, const int* __restrict__ rects,
+                                                        int max_rects, int gate_frame, int merge_padding, int border,
+                                                        uint8_t* __restrict__ out)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), k = blockIdx.z;
+    if (x >= w || y >= h) return;
+    const uint8_t* src = frames + (ptrdiff_t)(k + 1) * frame_stride;
+    uint8_t* o = out + ((ptrdiff_t)k * h + y) * ((ptrdiff_t)w * 3) + 3 * x;
+    bool in = true;
+    if (TABLE) {   // the table row is the same for the whole block: scalar loads
+        const int g = k + gate_frame;
+        const int n = min(counts[g], max_rects);
+        const int* r = rects + (ptrdiff_t)g * max_rects * 4;
+        in = false;
+        if (merge_padding >= 0) {
+            if (n > 0) {
+                int x0 = r[0], y0 = r[1], x1 = r[2], y1 = r[3];
+                for (int i = 1; i < n; i++) {
+                    x0 = min(x0, r[4 * i]); y0 = min(y0, r[4 * i + 1]);
+                    x1 = max(x1, r[4 * i + 2]); y1 = max(y1, r[4 * i + 3]);
+                }
+                x0 = max(0, x0 - merge_padding); y0 = max(0, y0 - merge_padding);
+                x1 = min(w, x1 + merge_padding); y1 = min(h, y1 + merge_padding);
+                in = x >= x0 && x < x1 && y >= y0 && y < y1;
+            }
+        } else {
+            for (int i = 0; i < n; i++)
+                in |= x >= r[4 * i] && x < r[4 * i + 2] && y >= r[4 * i + 1] && y < r[4 * i + 3];
+        }
+    }
+    if (in) {
+        const MapSrc m{flows + (ptrdiff_t)k * h * w * 2, nullptr, 2 * (ptrdiff_t)w, 0, 0, 0, 0, 0, sign};
+        remap_px<3, true>(src, row_stride, w, h, m, x, y, border, 0, o);
+    } else {
+        const uint8_t* s = src + (ptrdiff_t)y * row_stride + 3 * x;
+        o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
+    }
+}
+
 // ---- SSIM ---------------------------------------------------------------------------------------------------
 constexpr int SX = 64, SY = 16, WIN = 7, PAD = 3;
 
+// blockIdx.z = image pair (a and b advanced by aitem / bitem bytes, partials by one tile grid per pair).
 __global__ __launch_bounds__(256) void k_ssim_partial(const uint8_t* __restrict__ a, ptrdiff_t astride, int aps,
-                                                      const uint8_t* __restrict__ b, ptrdiff_t bstride, int bps, int w,
-                                                      int h, double c1, double c2, double* __restrict__ partial)
+                                                      ptrdiff_t aitem, const uint8_t* __restrict__ b, ptrdiff_t bstride,
+                                                      int bps, ptrdiff_t bitem, int w, int h, double c1, double c2,
+                                                      double* __restrict__ partial)
 {
     __shared__ uint8_t ta[SY + 6][SX + 6], tb[SY + 6][SX + 6];
     __shared__ int hs[5][SY + 6][SX];     // horizontal 7-sums of a, b, a*a, b*b, a*b
     __shared__ double wsum[4];
     const int tid = threadIdx.x;
+    a += (ptrdiff_t)blockIdx.z * aitem;
+    b += (ptrdiff_t)blockIdx.z * bitem;
+    partial += (size_t)blockIdx.z * gridDim.x * gridDim.y;
     const int ox = blockIdx.x * SX + PAD, oy = blockIdx.y * SY + PAD;   // first output pixel of the tile
     for (int i = tid; i < (SY + 6) * (SX + 6); i += 256) {
         const int r = i / (SX + 6), c = i - r * (SX + 6);
@@ -145,10 +211,13 @@ __global__ __launch_bounds__(256) void k_ssim_partial(const uint8_t* __restrict_
     if (tid == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
 
+// One block per pair (blockIdx.x): its n partials in order -> out[blockIdx.x].
 __global__ __launch_bounds__(256) void k_ssim_final(const double* __restrict__ partial, int n, double count,
                                                     double* __restrict__ out)
 {
     __shared__ double red[256];
+    partial += (size_t)blockIdx.x * n;
+    out += blockIdx.x;
     double acc = 0;
     for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
     red[threadIdx.x] = acc;
@@ -337,8 +406,8 @@ extern "C" int nsof_ssim_u8_dev(nsof_ctx* ctx, const uint8_t* d_a, ptrdiff_t a_s
     const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
     {
         nsof_prof_scope ps(ctx, NSOF_K_SSIM);
-        hipLaunchKernelGGL(k_ssim_partial, grid, dim3(256), 0, ctx->stream, d_a, a_stride, a_pixel_step, d_b, b_stride,
-                           b_pixel_step, width, height, c1, c2, partial);
+        hipLaunchKernelGGL(k_ssim_partial, grid, dim3(256), 0, ctx->stream, d_a, a_stride, a_pixel_step, (ptrdiff_t)0,
+                           d_b, b_stride, b_pixel_step, (ptrdiff_t)0, width, height, c1, c2, partial);
     }
     hipLaunchKernelGGL(k_ssim_final, dim3(1), dim3(256), 0, ctx->stream, partial, nblk, (double)ow * (double)oh,
                        partial + nblk);
@@ -375,4 +444,73 @@ extern "C" int nsof_ssim_u8(nsof_ctx* ctx, const uint8_t* a, ptrdiff_t a_stride,
     NSOF_HIP(ctx, hipMemcpyAsync(ctx->stage, hA, 2 * sz, hipMemcpyHostToDevice, ctx->stream));
     return nsof_ssim_u8_dev(ctx, (const uint8_t*)ctx->stage, width, 1, (const uint8_t*)ctx->stage + sz, width, 1, width,
                             height, data_range, ssim_out);
+}
+
+extern "C" int nsof_predict_sequence_u8_dev(nsof_ctx* ctx, int n_pairs, const uint8_t* d_frames, ptrdiff_t row_stride,
+                                            ptrdiff_t frame_stride, int width, int height, const float* d_flows, int sign,
+                                            const int32_t* d_counts, const int32_t* d_rects, int n_maps, int max_rects,
+                                            int gate_frame, int merge_padding, int border_mode, uint8_t* d_out)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!d_frames || !d_flows || !d_out) return nsof_set_error(ctx, NSOF_EINVAL, "null pointer");
+    if (n_pairs < 1) return nsof_set_error(ctx, NSOF_ESHAPE, "predict_sequence: n_pairs %d < 1", n_pairs);
+    if (n_pairs > 65535) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "predict_sequence: more than 65535 pairs");
+    int rc = check_remap_args(ctx, 3, width, height, row_stride, width, height, 3 * (ptrdiff_t)width, border_mode);
+    if (rc) return rc;
+    if (frame_stride < row_stride * height) return nsof_set_error(ctx, NSOF_EINVAL, "predict_sequence: frame stride");
+    if (sign != 1 && sign != -1) return nsof_set_error(ctx, NSOF_EINVAL, "sign must be +1 or -1");
+    if (reinterpret_cast<uintptr_t>(d_flows) & 7) return nsof_set_error(ctx, NSOF_EINVAL, "flows must be 8-byte aligned");
+    if (d_counts) {
+        if (!d_rects) return nsof_set_error(ctx, NSOF_EINVAL, "predict_sequence: rects table missing");
+        if (max_rects < 1) return nsof_set_error(ctx, NSOF_EINVAL, "predict_sequence: max_rects %d < 1", max_rects);
+        if (gate_frame != 0 && gate_frame != 1) return nsof_set_error(ctx, NSOF_EINVAL, "gate_frame must be 0 or 1");
+        if (n_maps < n_pairs + gate_frame)
+            return nsof_set_error(ctx, NSOF_ESHAPE, "predict_sequence: %d maps for %d pairs (gate_frame %d)", n_maps,
+                                  n_pairs, gate_frame);
+        if (merge_padding > 65535) return nsof_set_error(ctx, NSOF_EINVAL, "predict_sequence: merge_padding");
+    }
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    const dim3 grid((width + 63) / 64, (height + 3) / 4, n_pairs);
+    nsof_prof_scope ps(ctx, NSOF_K_REMAP);
+    if (d_counts)
+        hipLaunchKernelGGL(k_predict_seq_u8<true>, grid, dim3(256), 0, ctx->stream, d_frames, row_stride, frame_stride,
+                           width, height, d_flows, sign, d_counts, d_rects, max_rects, gate_frame, merge_padding,
+                           border_mode, d_out);
+    else
+        hipLaunchKernelGGL(k_predict_seq_u8<false>, grid, dim3(256), 0, ctx->stream, d_frames, row_stride, frame_stride,
+                           width, height, d_flows, sign, nullptr, nullptr, 1, 0, -1, border_mode, d_out);
+    NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
+}
+
+extern "C" int nsof_ssim_u8_batch_dev(nsof_ctx* ctx, int n, const uint8_t* d_a, ptrdiff_t a_stride,
+                                      ptrdiff_t a_item_stride, int a_pixel_step, const uint8_t* d_b, ptrdiff_t b_stride,
+                                      ptrdiff_t b_item_stride, int b_pixel_step, int width, int height,
+                                      double data_range, double* d_out)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!d_a || !d_b || !d_out) return nsof_set_error(ctx, NSOF_EINVAL, "null pointer");
+    if (n < 1) return nsof_set_error(ctx, NSOF_ESHAPE, "ssim_batch: n %d < 1", n);
+    if (n > 65535) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "ssim_batch: more than 65535 pairs");
+    if (width < WIN || height < WIN)
+        return nsof_set_error(ctx, NSOF_ESHAPE, "ssim: win_size 7 exceeds the image extent %dx%d", width, height);
+    if (a_pixel_step < 1 || b_pixel_step < 1 || a_stride < (ptrdiff_t)width * a_pixel_step ||
+        b_stride < (ptrdiff_t)width * b_pixel_step || (n > 1 && (a_item_stride < 0 || b_item_stride < 0)))
+        return nsof_set_error(ctx, NSOF_EINVAL, "ssim: stride");
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    const int ow = width - 2 * PAD, oh = height - 2 * PAD;
+    const dim3 grid((ow + SX - 1) / SX, (oh + SY - 1) / SY, n);
+    const int nblk = grid.x * grid.y;   // same tile grid and reduction order per pair as nsof_ssim_u8_dev
+    int rc = nsof_ws_reserve(ctx, &ctx->tmp, &ctx->tmp_bytes, (size_t)n * nblk * sizeof(double));
+    if (rc) return rc;
+    double* partial = (double*)ctx->tmp;
+    const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
+    {
+        nsof_prof_scope ps(ctx, NSOF_K_SSIM);
+        hipLaunchKernelGGL(k_ssim_partial, grid, dim3(256), 0, ctx->stream, d_a, a_stride, a_pixel_step, a_item_stride,
+                           d_b, b_stride, b_pixel_step, b_item_stride, width, height, c1, c2, partial);
+    }
+    hipLaunchKernelGGL(k_ssim_final, dim3(n), dim3(256), 0, ctx->stream, partial, nblk, (double)ow * (double)oh, d_out);
+    NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
 }

@@ -28,7 +28,9 @@ from .gating import (GatingConfig, connectedComponentsWithStats, current_to_gray
 from .segment import (MORPH_CROSS, MORPH_ELLIPSE, MORPH_RECT, dilate, erode, getStructuringElement, motion_mask,  # noqa: F401,E402
                       motion_mask_dev, process_flow_region, task_results)
 from .predict import (BORDER_CONSTANT, BORDER_REPLICATE, INTER_LINEAR, calculateIntegralError, gray_u8_dev,  # noqa: F401,E402
-                      predict_region, predict_region_dev, remap, structural_similarity)
+                      predict_region, predict_region_dev, predict_sequence_dev, remap, ssim_batch_dev,
+                      structural_similarity)
+from .pipeline import prediction_sequence_dev, run_prediction  # noqa: F401,E402
 from .frames import compress_image, crop_image, im2double, imresize_lanczos3, process_images  # noqa: F401,E402
 from .flowviz import flow_to_image, flow_uv_to_colors, make_colorwheel, viz  # noqa: F401,E402
 

@@ -343,3 +343,169 @@ def run_segmentation(frames_bgr, gt_masks_bgr, mem_state, cfg, names=None, csv_p
                 csv.writer(fh).writerow(row)
     n = max(len(rows), 1)
     return rows, acc_mem / n, acc_orig / n
+
+
+# ---- the prediction experiment of optical_flow_prediction.py (__main__, :435-681) as a function ---------------------
+PREDICT_CSV_COLUMNS = ["Frame_Pair", "Original_Flow_Time", "Mem_Flow_Time", "Flow_Time_Improvement",
+                       "Flow_Time_Improvement_Percent", "Original_Pred_Time", "Mem_Pred_Time", "Combination_Time",
+                       "Original_SSIM", "Mem_SSIM", "Region_Percent", "Cal_Times", "Velocity_Times"]   # prediction.py:413-427
+PREDICT_PADDING = 20   # prediction.py PADDING: the merged box of FLAG 1 with MERGE_FLAG
+
+
+def prediction_boxes(regions, num_labels, flag, merge_flag, frame_hw, padding=PREDICT_PADDING):
+    """The boxes the prediction task warps for one pair (prediction.py:268-353): none without a component, the union box
+    (FLAG 2), every component box (FLAG 1), or their bounding box padded and clipped to the frame (FLAG 1 merged)."""
+    h, w = frame_hw
+    if num_labels <= 1:
+        return []
+    if flag != 1:
+        return [tuple(regions)]
+    if not merge_flag:
+        return [tuple(r) for r in regions]
+    return [(max(0, min(r[0] for r in regions) - padding), max(0, min(r[1] for r in regions) - padding),
+             min(w, max(r[2] for r in regions) + padding), min(h, max(r[3] for r in regions) + padding))]
+
+
+def run_prediction(frames_bgr, mem_state, cfg, names=None, csv_path=None, merge_flag=True, flow_fn=None, predict_fn=None,
+                   ssim_fn=None):
+    """The main loop of optical_flow_prediction.py for a sequence held in memory: for every pair (i, i+1), i < n-2, the
+    gated flow + prediction ("Mem", ``task_results`` with MERGE_FLAG = ``merge_flag``; the script passes True) and the
+    full-frame flow + prediction ("Original", BORDER_CONSTANT), their times, their SSIMs against frame i+2 (channel 2,
+    ``calculateIntegralError``) and the CSV row the script writes (same 13 columns, same formatting).  ``frames_bgr``:
+    uint8 [H][W][3] as ``cv2.imread`` returns them; ``mem_state``: the ``constructed3DMatrix`` stack.  ``flow_fn`` /
+    ``predict_fn`` / ``ssim_fn`` default to the GPU path (``calcOpticalFlowFarneback``, ``predict.task_results``,
+    ``predict.calculateIntegralError``); tests inject the CPU oracle.  ``predict_fn`` takes ``task_results``' arguments
+    (``times`` / ``comb_times`` / ``borderMode`` keywords included).  Returns ``(rows, ssim_mem, ssim_orig,
+    mean_mem_as_printed, mean_orig_as_printed)``: the per-pair SSIM lists and the means the script prints, which divide by
+    ``cnt - 1`` (prediction.py:678; None for a single pair)."""
+    import csv
+    import time
+
+    from . import predict
+    from .farneback import calcOpticalFlowFarneback
+    flow_fn = flow_fn or calcOpticalFlowFarneback
+    predict_fn = predict_fn or predict.task_results
+    ssim_fn = ssim_fn or predict.calculateIntegralError
+    names = names or [f"{i + 1}.jpg" for i in range(len(frames_bgr))]
+    rows, ssim_mem, ssim_orig = [], [], []
+    if csv_path:
+        with open(csv_path, "w", newline="") as fh:
+            csv.writer(fh).writerow(PREDICT_CSV_COLUMNS)
+    for i in range(len(frames_bgr) - 2):
+        cfg.mem_opticalflow_times.clear(); cfg.mem_cal_times.clear(); cfg.mem_velocity_times.clear()
+        memimg1, memimg2 = gating.gating_maps(mem_state, i, cfg)
+        prev_frame, next_frame = frames_bgr[i], frames_bgr[i + 1]
+        prev_gray = gating.frame_to_gray(prev_frame, "RGB2GRAY")
+        next_gray = gating.frame_to_gray(next_frame, "RGB2GRAY")
+        h, w = next_frame.shape[:2]
+        out = gating.opticalFlow3D(memimg1, memimg2, prev_gray, next_gray, cfg.MEMSIZE, cfg.MEMSIZE, cfg,
+                                   flow_fn=flow_fn)
+        flow, region_list = (-out[0]).astype(np.float32), out[3]
+        if cfg.FLAG == 1:
+            num_labels, regions = out[4], out[5]
+        else:
+            regions = out[4]
+            num_labels = 2 if tuple(regions) != (0, 0, 0, 0) else 1
+        mem_times, comb_times = [], []
+        pred = predict_fn(prev_frame, next_frame, flow, num_labels, regions, EST_FLAG=cfg.FLAG, MERGE_FLAG=merge_flag,
+                          times=mem_times, comb_times=comb_times)
+        s_mem = ssim_fn(pred, frames_bgr[i + 2])
+        # Original: full-frame flow and prediction (prediction.py:566-605)
+        t0 = time.time()
+        flow1 = flow_fn(prev_gray, next_gray, None, **cfg.farneback_params.as_kwargs())
+        t_orig_flow = time.time() - t0
+        flow1 = -flow1
+        t0 = time.time()
+        pred1 = predict_fn(prev_frame, next_frame, flow1.astype(np.float32), 2, (0, 0, w, h), EST_FLAG=2,
+                           MERGE_FLAG=False, borderMode=predict.BORDER_CONSTANT)
+        t_orig_pred = time.time() - t0
+        s_orig = ssim_fn(pred1, frames_bgr[i + 2])
+        ssim_mem.append(s_mem)
+        ssim_orig.append(s_orig)
+        t_mem_flow = cfg.mem_opticalflow_times[0]
+        imp = t_orig_flow - t_mem_flow
+        row = [f"{names[i + 1]}-{names[i]}", f"{t_orig_flow:.4f}", f"{t_mem_flow:.4f}", f"{imp:.4f}",
+               f"{imp / t_orig_flow * 100 if t_orig_flow else float('nan'):.2f}", f"{t_orig_pred:.4f}",
+               f"{mem_times[0]:.4f}", f"{comb_times[0]:.4f}", f"{s_orig:.4f}", f"{s_mem:.4f}", region_list,
+               ";".join(f"{t:.4f}" for t in cfg.mem_cal_times), ";".join(f"{t:.4f}" for t in cfg.mem_velocity_times)]
+        rows.append(row)
+        if csv_path:
+            with open(csv_path, "a", newline="") as fh:
+                csv.writer(fh).writerow(row)
+    cnt = len(rows)
+    mean_mem = sum(ssim_mem) / (cnt - 1) if cnt > 1 else None
+    mean_orig = sum(ssim_orig) / (cnt - 1) if cnt > 1 else None
+    return rows, ssim_mem, ssim_orig, mean_mem, mean_orig
+
+
+def prediction_sequence_dev(frames_bgr, mem_state, cfg, with_original=True, merge_flag=True, max_rects=32, ctx=None):
+    """``run_prediction``'s experiment for a whole sequence in HBM: ``frames_bgr`` uint8 CUDA tensor [n][H][W][3] (BGR as
+    ``cv2.imread`` gives them), ``mem_state`` the ``constructed3DMatrix`` stack.  Gray frames (``gray_u8_dev``), the device
+    gating table of slices OFFSET .. OFFSET+n-2 (one launch, ``gating.roi_from_surface_dev``; regrown once when a map has
+    more than ``max_rects`` components), the ROI flows of pairs 0 .. n-3 from that table (``farneback_roi_sequence_dev``,
+    gated as ``cfg.bug_compatible`` says), the full-frame flows (``farneback_sequence``), then one prediction warp and one
+    SSIM launch pair per path for all pairs (``predict.predict_sequence_dev`` reading the same table,
+    ``predict.ssim_batch_dev`` against frames 2 .. n-1).  Only the slices go up and the rectangle table comes back (one
+    copy, which also gives the host lists).  Returns a dict of CUDA tensors -- ``pred_mem`` / ``pred_orig`` uint8
+    [n-2][H][W][3], ``ssim_mem`` / ``ssim_orig`` float64 [n-2], ``flow_mem`` / ``flow_orig`` float32 [n-2][H][W][2] (the
+    un-negated Farneback flow; the ``orig`` entries are None without ``with_original``) -- and the host lists ``rects``
+    (the ROI rectangles of every pair) and ``boxes`` (the boxes its prediction warped, ``prediction_boxes``); equal to ``run_prediction`` with the GPU backends, bit for bit.  Synchronises at the
+    end, so the tensors can be read at once."""
+    import torch
+
+    from . import predict
+    from .context import default_context
+    from .farneback import farneback_roi_sequence_dev, farneback_sequence
+    ctx = ctx or default_context()
+    predict._u8_frames(frames_bgr, "prediction_sequence_dev")
+    if frames_bgr.dim() != 4 or frames_bgr.shape[3] != 3:
+        raise predict.NsofValueError("prediction_sequence_dev: uint8 [n][H][W][3] frames expected")
+    n, H, W = (int(v) for v in frames_bgr.shape[:3])  # noqa: N806
+    if n < 3:
+        raise ValueError(f"prediction_sequence_dev: {n} frames; the experiment needs at least 3")
+    rows, cols = int(mem_state.shape[0]), int(mem_state.shape[1])
+    if rows > H // cfg.MEMSIZE or cols > W // cfg.MEMSIZE:
+        raise ValueError(f"gating map {rows}x{cols} larger than the {H // cfg.MEMSIZE}x{W // cfg.MEMSIZE} transition picture")
+    if rows > 64 or cols > 64:
+        raise ValueError(f"gating map {rows}x{cols}: the device gating kernel takes maps up to 64x64 cells")
+    if mem_state.shape[2] < cfg.OFFSET + n - 1:
+        raise ValueError(f"the stack has {mem_state.shape[2]} slices; {n} frames need OFFSET + {n - 1}")
+    gf = 0 if cfg.bug_compatible else 1
+    dev = frames_bgr.device
+    cur = torch.from_numpy(np.ascontiguousarray(np.moveaxis(np.asarray(mem_state)[:, :, cfg.OFFSET:cfg.OFFSET + n - 1], 2, 0),
+                                                np.float64)).to(dev)
+    gray = torch.empty((n - 1, H, W), dtype=torch.uint8, device=dev)
+    flow_mem = torch.empty((n - 2, H, W, 2), dtype=torch.float32, device=dev)   # zero-filled by the ROI flow call
+    pred_mem = torch.empty((n - 2, H, W, 3), dtype=torch.uint8, device=dev)
+    ssim_mem = torch.empty((n - 2,), dtype=torch.float64, device=dev)
+    if with_original:
+        flow_orig = torch.empty_like(flow_mem)
+        pred_orig = torch.empty_like(pred_mem)
+        ssim_orig = torch.empty_like(ssim_mem)
+    else:
+        flow_orig = pred_orig = ssim_orig = None
+    torch.cuda.synchronize(dev)
+    for k in range(n - 1):
+        predict.gray_u8_dev(frames_bgr[k], gray[k], "RGB2GRAY", ctx=ctx)
+    counts, rtab = gating.roi_from_surface_dev(cur, n - 1, (rows, cols), (H, W), cfg, max_rects=max_rects, ctx=ctx)
+    ctx.synchronize()
+    c, r = counts.cpu().numpy(), rtab.cpu().numpy()
+    if c.max() > max_rects:   # more components than the table holds: one more (tiny) gating launch with room for all
+        counts, rtab = gating.roi_from_surface_dev(cur, n - 1, (rows, cols), (H, W), cfg, max_rects=int(c.max()), ctx=ctx)
+        ctx.synchronize()
+        c, r = counts.cpu().numpy(), rtab.cpu().numpy()
+    lists = [[tuple(int(v) for v in r[k, i]) for i in range(int(c[k]))] for k in range(n - 1)]
+    farneback_roi_sequence_dev(gray, counts, rtab, flow_mem, cfg.farneback_params, gate_frame=gf, ctx=ctx)
+    predict.predict_sequence_dev(frames_bgr, flow_mem, pred_mem, counts=counts, rects=rtab, gate_frame=gf,
+                                 merge_padding=PREDICT_PADDING if cfg.FLAG == 1 and merge_flag else None, ctx=ctx)
+    predict.ssim_batch_dev(pred_mem, frames_bgr[2:], out=ssim_mem, ctx=ctx)
+    if with_original:
+        farneback_sequence(gray, flow_orig, n - 1, H, W, cfg.farneback_params, row_stride=int(gray.stride(1)),
+                           frame_stride=int(gray.stride(0)), ctx=ctx)
+        predict.predict_sequence_dev(frames_bgr, flow_orig, pred_orig, border_mode=predict.BORDER_CONSTANT, ctx=ctx)
+        predict.ssim_batch_dev(pred_orig, frames_bgr[2:], out=ssim_orig, ctx=ctx)
+    ctx.synchronize()
+    rects = [lists[k + gf] for k in range(n - 2)]
+    boxes = [prediction_boxes(rs, len(rs) + 1, 1, merge_flag, (H, W)) if cfg.FLAG == 1 else rs for rs in rects]
+    return dict(pred_mem=pred_mem, pred_orig=pred_orig, ssim_mem=ssim_mem, ssim_orig=ssim_orig, flow_mem=flow_mem,
+                flow_orig=flow_orig, rects=rects, boxes=boxes)

@@ -114,9 +114,12 @@ def predict_region_dev(d_frame, d_flow, d_out, height, width, rect, channels=3, 
 
 
 def task_results(prev_frame, next_frame, flow, num_labels, regions_info, EST_FLAG=2, MERGE_FLAG=False, padding=20,  # noqa: N803
-                 sign=1, times=None, *, ctx=None):
+                 sign=1, times=None, *, ctx=None, comb_times=None, borderMode=BORDER_REPLICATE):  # noqa: N803
     """optical_flow_prediction.py:255-353.  ``flow`` is the canvas the caller already negated (:545), hence
-    ``sign=1`` here; pass the raw ``opticalFlow3D`` canvas with ``sign=-1`` to skip that host pass."""
+    ``sign=1`` here; pass the raw ``opticalFlow3D`` canvas with ``sign=-1`` to skip that host pass.  ``times`` /
+    ``comb_times`` (lists) receive the task's time and the time up to its box list, as the script's
+    ``mem_task_times`` / ``mem_combination_times``; ``borderMode`` is the remap's (the script's full-frame baseline,
+    :584-586, is this task on the box (0, 0, w, h) with BORDER_CONSTANT)."""
     t0 = time.time()
     h, w = prev_frame.shape[:2]
     new_frame = np.array(next_frame, copy=True)
@@ -128,8 +131,12 @@ def task_results(prev_frame, next_frame, flow, num_labels, regions_info, EST_FLA
             boxes = list(regions_info)
         else:
             boxes = [tuple(regions_info)]
+        if comb_times is not None:
+            comb_times.append(time.time() - t0)
         for box in boxes:   # later boxes see the original frame, like the reference (it always warps next_frame)
-            predict_region(next_frame, flow, box, out=new_frame, sign=sign, ctx=ctx)
+            predict_region(next_frame, flow, box, out=new_frame, sign=sign, borderMode=borderMode, ctx=ctx)
+    elif comb_times is not None:
+        comb_times.append(time.time() - t0)
     if times is not None:
         times.append(time.time() - t0)
     return new_frame
@@ -156,3 +163,93 @@ def structural_similarity(im1, im2, data_range=255.0, *, ctx=None):
 def calculateIntegralError(prediction, true, *, ctx=None):  # noqa: N802
     """optical_flow_prediction.py:113-115: SSIM of channel 2 (red of a BGR frame)."""
     return structural_similarity(np.asarray(true)[:, :, 2], np.asarray(prediction)[:, :, 2], data_range=255.0, ctx=ctx)
+
+
+def _u8_frames(t, what):
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise NsofValueError(f"{what}: a CUDA tensor expected", _lib.NSOF_EINVAL)
+    if t.dtype != torch.uint8:
+        raise NsofValueError(f"{what}: uint8 expected (got {t.dtype})", _lib.NSOF_EINVAL)
+
+
+def predict_sequence_dev(frames_bgr, flows, out=None, *, counts=None, rects=None, gate_frame=0, merge_padding=None,
+                         border_mode=BORDER_REPLICATE, sign=-1, ctx=None):
+    """The prediction step of every pair of a sequence in one launch (``nsof_predict_sequence_u8_dev``): pair k warps
+    frame k+1 of ``frames_bgr`` (uint8 CUDA tensor [n][H][W][3], pixels interleaved, row / frame strides free) with
+    ``sign * flows[k]`` (float32 CUDA tensor [n_pairs][H][W][2], contiguous; n >= n_pairs + 1) into ``out[k]`` (uint8
+    [n_pairs][H][W][3], contiguous; allocated when None).  Region of pair k: the rectangles of row ``k + gate_frame`` of
+    the device table ``counts`` / ``rects`` (``gating.roi_from_surface_dev``, the table the ROI flow call consumed) --
+    their union (``merge_padding=None``: FLAG 1 separate, FLAG 2) or their bounding box padded by ``merge_padding`` and
+    clipped (FLAG 1 merged, the script's PADDING 20) -- with the frame copied elsewhere; without a table the whole frame
+    (the full-frame baseline: pass ``border_mode=BORDER_CONSTANT``).  Each ``out[k]`` equals ``task_results`` of that
+    pair bit for bit.  The table's counts must not exceed ``rects.shape[1]`` (``gating.rects_to_host`` checks it).
+    Asynchronous on the context's stream."""
+    import torch
+    ctx = ctx or default_context()
+    _u8_frames(frames_bgr, "predict_sequence_dev")
+    if not isinstance(flows, torch.Tensor) or not flows.is_cuda or flows.dtype != torch.float32:
+        raise NsofValueError("predict_sequence_dev: flows must be a float32 CUDA tensor", _lib.NSOF_EINVAL)
+    if frames_bgr.dim() != 4 or frames_bgr.shape[3] != 3 or frames_bgr.stride(3) != 1 or frames_bgr.stride(2) != 3:
+        raise NsofValueError("predict_sequence_dev: frames must be [n][H][W][3] with interleaved pixels", _lib.NSOF_ESHAPE)
+    n, h, w = (int(v) for v in frames_bgr.shape[:3])
+    n_pairs = int(flows.shape[0]) if flows.dim() == 4 else 0
+    if tuple(flows.shape) != (n_pairs, h, w, 2) or not flows.is_contiguous() or n_pairs < 1 or n < n_pairs + 1:
+        raise NsofValueError(f"predict_sequence_dev: flows {tuple(flows.shape)} do not fit {n} frames of {h}x{w} "
+                             "(contiguous [n_pairs][H][W][2], n_pairs <= n - 1)", _lib.NSOF_ESHAPE)
+    if (counts is None) != (rects is None):
+        raise NsofValueError("predict_sequence_dev: pass counts and rects together", _lib.NSOF_EINVAL)
+    n_maps = max_rects = 0
+    if counts is not None:
+        if counts.dtype != torch.int32 or rects.dtype != torch.int32 or not counts.is_contiguous() or \
+                not rects.is_contiguous() or rects.dim() != 3 or rects.shape[2] != 4 or counts.shape != rects.shape[:1]:
+            raise NsofValueError("predict_sequence_dev: counts int32 [n_maps] and rects int32 [n_maps][max_rects][4] "
+                                 "(contiguous) expected", _lib.NSOF_ESHAPE)
+        n_maps, max_rects = int(rects.shape[0]), int(rects.shape[1])
+    if out is None:
+        out = torch.empty((n_pairs, h, w, 3), dtype=torch.uint8, device=frames_bgr.device)
+        torch.cuda.synchronize(frames_bgr.device)
+    else:
+        _u8_frames(out, "predict_sequence_dev")
+        if tuple(out.shape) != (n_pairs, h, w, 3) or not out.is_contiguous():
+            raise NsofValueError("predict_sequence_dev: out must be a contiguous uint8 [n_pairs][H][W][3] tensor",
+                                 _lib.NSOF_ESHAPE)
+    rc = ctx._lib.nsof_predict_sequence_u8_dev(
+        ctx.ptr, n_pairs, dev_ptr(frames_bgr), int(frames_bgr.stride(1)), int(frames_bgr.stride(0)), w, h, dev_ptr(flows),
+        int(sign), dev_ptr(counts), dev_ptr(rects), n_maps, max_rects, int(gate_frame),
+        -1 if merge_padding is None else int(merge_padding), int(border_mode), dev_ptr(out))
+    ctx.check(rc, "predict_sequence_dev")
+    return out
+
+
+def ssim_batch_dev(a, b, channel=2, out=None, *, ctx=None):
+    """``structural_similarity(b[i][..., channel], a[i][..., channel], data_range=255)`` of every pair i at once
+    (``nsof_ssim_u8_batch_dev``): ``a`` / ``b`` uint8 CUDA tensors [n][H][W][C] (``channel`` selects one interleaved
+    channel; default 2 = ``calculateIntegralError``) or [n][H][W]; results in ``out`` (float64 CUDA tensor [n],
+    allocated when None), each equal to the single-pair ``nsof_ssim_u8_dev`` exactly.  Asynchronous."""
+    import torch
+    ctx = ctx or default_context()
+    _u8_frames(a, "ssim_batch_dev")
+    _u8_frames(b, "ssim_batch_dev")
+    if a.shape != b.shape or a.dim() not in (3, 4) or a.shape[0] < 1:
+        raise NsofValueError(f"ssim_batch_dev: two [n][H][W][C] or [n][H][W] tensors of one shape expected (got "
+                             f"{tuple(a.shape)}, {tuple(b.shape)})", _lib.NSOF_ESHAPE)
+    n, h, w = (int(v) for v in a.shape[:3])
+    if a.dim() == 4:
+        if not 0 <= int(channel) < a.shape[3] or a.stride(3) != 1 or b.stride(3) != 1:
+            raise NsofValueError("ssim_batch_dev: channel out of range or channels not interleaved", _lib.NSOF_ESHAPE)
+        off = int(channel)
+    else:
+        off = 0
+    if min(h, w) < 7:
+        raise NsofValueError("ssim_batch_dev: win_size 7 exceeds the image extent", _lib.NSOF_ESHAPE)
+    if out is None:
+        out = torch.empty((n,), dtype=torch.float64, device=a.device)
+        torch.cuda.synchronize(a.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (n,) or not out.is_contiguous() or not out.is_cuda:
+        raise NsofValueError("ssim_batch_dev: out must be a contiguous float64 CUDA tensor [n]", _lib.NSOF_ESHAPE)
+    rc = ctx._lib.nsof_ssim_u8_batch_dev(
+        ctx.ptr, n, dev_ptr(b) + off, int(b.stride(1)), int(b.stride(0)), int(b.stride(2)), dev_ptr(a) + off,
+        int(a.stride(1)), int(a.stride(0)), int(a.stride(2)), w, h, 255.0, dev_ptr(out))
+    ctx.check(rc, "ssim_batch_dev")
+    return out
