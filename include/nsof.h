@@ -466,6 +466,26 @@ int nsof_morph_binary_u8_dev(nsof_ctx* ctx, int op, const uint8_t* d_src, ptrdif
  * bit-packed mask.  d_mask [h][mask_stride] uint8. */
 int nsof_motion_mask_dev(nsof_ctx* ctx, const float* d_flow, ptrdiff_t flow_stride_floats, int width, int height,
                          double thresh, int ksize, int iterations, uint8_t* d_mask, ptrdiff_t mask_stride);
+/* The head over the boxes of a whole sequence (optical_flow_seg.py task_results :253-320, the full-frame baseline
+ * :503-537).  d_flows: float32 [n_pairs][height][width][2] (dense, 8-byte aligned); d_masks: uint8
+ * [n_pairs][height][width] (dense).  box_counts[n_pairs] and boxes[sum of counts][4] of (x0, y0, x1, y1) are HOST
+ * arrays: a pair's boxes are consecutive and in paste order; box_counts == NULL is one whole-frame box per pair.
+ * Every pixel of every canvas is written: the mask of the LAST box that covers it, computed as nsof_motion_mask_dev
+ * computes it on the crop flow[y0:y1, x0:x1] (the crop's edges are image borders), or 0 where no box covers it.
+ * Empty boxes (x1 <= x0 or y1 <= y0) are skipped.  Boxes leaving the frame, n_pairs outside 1..65535, ksize outside
+ * 1..32, iterations outside 0..16 and null pointers return an nsof_status before anything is launched.
+ * Asynchronous: the box and job tables go up through a pinned copy that a later call rewrites only after this
+ * upload has finished (waiting for that, or growing the tables or the workspace, are its only waits). */
+int nsof_motion_mask_sequence_dev(nsof_ctx* ctx, int n_pairs, const float* d_flows, int width, int height,
+                                  const int32_t* box_counts, const int32_t* boxes, double thresh, int ksize,
+                                  int iterations, uint8_t* d_masks);
+/* optical_flow_seg.py calculate_pixel_accuracy of n masks against ground-truth frames, into the DEVICE doubles
+ * d_out[n]: d_masks uint8 [n][height][width] (dense, 0/255), d_gt interleaved BGR uint8 frames (strides in bytes),
+ * binarised as (BGR2GRAY(gt) > 127) ? 255 : 0 with cv2's fixed-point weights.  d_out[i] = (double)equal_pixels /
+ * (double)(width * height) * 100.0; the pixels are counted in integers, so the result is exact.  Asynchronous. */
+int nsof_pixel_accuracy_u8_batch_dev(nsof_ctx* ctx, int n, const uint8_t* d_masks, const uint8_t* d_gt,
+                                     ptrdiff_t gt_row_stride, ptrdiff_t gt_frame_stride, int width, int height,
+                                     double* d_out);
 /* Same with HOST pointers (flow row stride in bytes: ROI views of the flow canvas are passed as they are). */
 int nsof_motion_mask(nsof_ctx* ctx, const float* flow, ptrdiff_t flow_stride_bytes, int width, int height,
                      double thresh, int ksize, int iterations, uint8_t* mask, ptrdiff_t mask_stride);

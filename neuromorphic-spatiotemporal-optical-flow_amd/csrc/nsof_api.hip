@@ -257,6 +257,9 @@ extern "C" void nsof_destroy(nsof_ctx* ctx)
     if (ctx->paste_h) hipHostFree(ctx->paste_h);
     if (ctx->paste_d) hipFree(ctx->paste_d);
     if (ctx->paste_ev) hipEventDestroy(ctx->paste_ev);
+    if (ctx->seg_h) hipHostFree(ctx->seg_h);
+    if (ctx->seg_d) hipFree(ctx->seg_d);
+    if (ctx->seg_ev) hipEventDestroy(ctx->seg_ev);
     if (ctx->x_sync) hipFree(ctx->x_sync);
     for (auto ev : ctx->het_ev)
         if (ev) hipEventDestroy(ev);

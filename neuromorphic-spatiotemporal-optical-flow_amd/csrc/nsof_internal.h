@@ -67,6 +67,12 @@ struct nsof_ctx {
     void* paste_d = nullptr;
     size_t paste_bytes = 0;
     hipEvent_t paste_ev = nullptr;
+    // box and job tables of the batched segmentation head (nsof_motion_mask_sequence_dev): pinned host copy, device
+    // copy, the event after its last upload
+    void* seg_h = nullptr;
+    void* seg_d = nullptr;
+    size_t seg_bytes = 0;
+    hipEvent_t seg_ev = nullptr;
     unsigned long long* x_carry = nullptr;
     size_t x_carry_bytes = 0;
     unsigned* x_sync = nullptr;
@@ -255,6 +261,13 @@ __device__ __forceinline__ double nsof_recip_normal(double x)
     r = __builtin_fma(r, e, r);
     e = __builtin_fma(-x, r, 1.0);   // residual of the quotient q0 = 1 * r
     return __builtin_fma(e, r, r);
+}
+
+// cv2's fixed-point cvtColor to gray of one interleaved 3-channel 8-bit pixel (c0, c1, c2): weights in units of 2^-15,
+// w0 on c0 (RGB2GRAY 9798, 19235, 3735; BGR2GRAY 3735, 19235, 9798), rounded.  k_gray_u8 and the pixel-accuracy kernel.
+__device__ __forceinline__ unsigned nsof_gray_px(unsigned c0, unsigned c1, unsigned c2, int w0, int w1, int w2)
+{
+    return (c0 * w0 + c1 * w1 + c2 * w2 + (1u << 14)) >> 15;
 }
 
 __device__ __forceinline__ void nsof_store_stream4(float* p, float a, float b, float c, float d)

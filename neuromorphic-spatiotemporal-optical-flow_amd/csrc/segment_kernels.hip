@@ -13,6 +13,12 @@
 //                 Pixels outside the image never take part (cv2's default border for morphology), which is the
 //                 `inside` mask applied after every pass.  The bit image is 1/64 of the flow's size, so the halo
 //                 re-reads are free and the head as a whole stays bound by the one read of the flow.
+//   k_mag_pack_jobs / k_morph_jobs / k_mask_compose   the head over the boxes of a whole sequence: the two kernels
+//                 above applied per box (each box its own image) from host-built job lists, then one pass over every
+//                 canvas pixel that takes the bit of the last box covering it (the paste order of the reference).
+//   k_pa_partial / k_pa_final   pixel accuracy of a batch of masks against thresholded gray ground-truth frames,
+//                 counted in integers.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -44,22 +50,9 @@ __global__ __launch_bounds__(256) void k_mag_pack(const float* __restrict__ flow
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int k64 = blockIdx.x * 4 + wave;   // 64-pixel group of the row
     if (k64 * 2 >= wp) return;
-    const int x = k64 * 64 + lane;
-    const int y0 = blockIdx.y * 8;
-    float2 v[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const int y = y0 + r;
-        v[r] = (x < w && y < h) ? *(const float2*)(flow + (ptrdiff_t)y * fstride + 2 * x) : make_float2(0.f, 0.f);
-    }
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const int y = y0 + r;
-        const double a = v[r].x, b = v[r].y;
-        const bool set = x < w && y < h && sqrt(a * a + b * b) > thresh;   // cartToPolar on float64, then `mag > th`
-        const unsigned long long m = __ballot(set);
-        if (lane == 0 && y < h) *(unsigned long long*)(bits + (size_t)y * wp + 2 * k64) = m;
-    }
+#define PACK_BY blockIdx.y
+#include "segment_mag_pack.inc"
+#undef PACK_BY
 }
 
 __global__ __launch_bounds__(256) void k_u8_pack(const uint8_t* __restrict__ src, ptrdiff_t sstride, int w, int h,
@@ -144,70 +137,138 @@ __global__ __launch_bounds__(MORPH_THREADS) void k_morph_bits(const uint32_t* __
                                                               int top, int rows, uint32_t* __restrict__ out_bits,
                                                               uint8_t* __restrict__ out_u8, ptrdiff_t ostride)
 {
-    constexpr MorphElem fixed = ellipse10();
-    const MorphElem& el = FIXED10 ? fixed : el_arg;
-    extern __shared__ uint32_t lds[];
-    uint32_t* cur = lds;                       // [rows][TW]
-    uint32_t* H = lds + (size_t)rows * TW;     // [n_patterns][rows][TW]
-    const int tid = threadIdx.x;
-    const int gk0 = blockIdx.x * TILE_WORDS - HALO_WORDS;
-    const int gy0 = blockIdx.y * TILE_H - top;
-    const int n = rows * TW;
-    const int k = tid & (TW - 1);              // 1024 % TW == 0: a thread keeps its word column
-    const int gk = gk0 + k;
+#define TILE_BX blockIdx.x
+#define TILE_BY blockIdx.y
+#include "segment_morph_tile.inc"
+#undef TILE_BX
+#undef TILE_BY
+}
 
-    for (int i = tid; i < n; i += MORPH_THREADS) {
-        const int gy = gy0 + (i >> 4);
-        cur[i] = (gy >= 0 && gy < h && gk >= 0 && gk < wp) ? in_bits[(size_t)gy * wp + gk] : 0u;
+// ---- the head over the boxes of a whole sequence (nsof_motion_mask_sequence_dev) --------------------------------
+// Every non-empty box is an image of its own (cv2 sees the crop: its edges are image borders), with two bit images
+// in the workspace.  The host lists the boxes and one job per workgroup of each stage, so the grids are exact.
+struct SegBox {
+    unsigned long long off;   // word offset of the box's bit images in the workspace: A at off, B at off + wp * h
+    int pair, x0, y0, w, h, wp;
+};
+struct SegJob {
+    int box;
+    int tile;                 // pack: the 8-row group; morph: ty * tiles_x + tx
+};
+
+// Pack: one workgroup per (box, 8-row group); its 4 waves walk the row's 64-pixel groups.  Pair p's flow canvas is
+// [H][W][2] at flows + p * H * W * 2; the crop keeps the canvas row stride.
+__global__ __launch_bounds__(256) void k_mag_pack_jobs(const SegJob* __restrict__ jobs, const SegBox* __restrict__ boxes,
+                                                       const float* __restrict__ flows, int W, int H, double thresh,
+                                                       uint32_t* __restrict__ ws)
+{
+    const SegJob j = jobs[blockIdx.x];
+    const SegBox box = boxes[j.box];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* flow = flows + (((size_t)box.pair * H + box.y0) * W + box.x0) * 2;
+    const ptrdiff_t fstride = 2 * (ptrdiff_t)W;
+    const int w = box.w, h = box.h, wp = box.wp;
+    uint32_t* bits = ws + box.off;
+    for (int k64 = wave; k64 * 2 < wp; k64 += 4) {
+#define PACK_BY j.tile
+#include "segment_mag_pack.inc"
+#undef PACK_BY
     }
-    __syncthreads();
+}
 
-    for (int p = 0; p < n_pass; p++) {
-        const bool dil = (ops >> p) & 1u;
-        // H step: per distinct row pattern, OR of the funnel-shifted words (one v_alignbit per element column)
-        for (int i = tid; i < n; i += MORPH_THREADS) {
-            const int gy = gy0 + (i >> 4);
-            uint32_t lo = k > 0 ? cur[i - 1] : 0u, mid = cur[i], hi = k + 1 < TW ? cur[i + 1] : 0u;
-            if (!dil) {   // complement inside the image; outside stays 0 (= "does not take part" in a minimum)
-                lo = k > 0 ? ~lo & inside_bits(gy, gk - 1, w, h) : 0u;
-                mid = ~mid & inside_bits(gy, gk, w, h);
-                hi = k + 1 < TW ? ~hi & inside_bits(gy, gk + 1, w, h) : 0u;
-            }
-            h_patterns<0>(el, H, n, i, lo, mid, hi);
+// Morph: one workgroup per (box, tile), the tile walk of k_morph_bits on the box's own image.  src_b: read B, write A.
+template <bool FIXED10>
+__global__ __launch_bounds__(MORPH_THREADS) void k_morph_jobs(const SegJob* __restrict__ jobs,
+                                                              const SegBox* __restrict__ boxes, uint32_t* __restrict__ ws,
+                                                              int src_b, const MorphElem el_arg, int n_pass,
+                                                              unsigned ops, int top, int rows)
+{
+    const SegJob j = jobs[blockIdx.x];
+    const SegBox box = boxes[j.box];
+    const int w = box.w, h = box.h, wp = box.wp;
+    const int tiles_x = (wp + TILE_WORDS - 1) / TILE_WORDS;
+    const int ty = j.tile / tiles_x, tx = j.tile - ty * tiles_x;
+    const size_t img = (size_t)wp * h;
+    const uint32_t* in_bits = ws + box.off + (src_b ? img : 0);
+    uint32_t* out_bits = ws + box.off + (src_b ? 0 : img);
+    uint8_t* const out_u8 = nullptr;
+    const ptrdiff_t ostride = 0;
+#define TILE_BX tx
+#define TILE_BY ty
+#include "segment_morph_tile.inc"
+#undef TILE_BX
+#undef TILE_BY
+}
+
+// Compose: 4 canvas pixels per thread (256 x 4 per workgroup), blockIdx.z = pair.  A pixel takes the bit of the LAST
+// of its pair's boxes that covers it (the paste order of optical_flow_seg.py), 0 when none does; the scan walks the
+// pair's boxes from the end and stops once all 4 pixels are decided, so it has no cap on the box count.
+__global__ __launch_bounds__(256) void k_mask_compose(const SegBox* __restrict__ boxes, const int* __restrict__ first,
+                                                      const uint32_t* __restrict__ ws, int final_b, int w, int h,
+                                                      uint8_t* __restrict__ masks)
+{
+    const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, y = blockIdx.y * 4 + (threadIdx.x >> 6), k = blockIdx.z;
+    if (x >= w || y >= h) return;
+    const int n = min(4, w - x);
+    unsigned pending = (1u << n) - 1u, v = 0;
+    for (int i = first[k + 1] - 1; i >= first[k] && pending; i--) {
+        const SegBox b = boxes[i];
+        const int ry = y - b.y0;
+        if (ry < 0 || ry >= b.h) continue;
+        const uint32_t* row = ws + b.off + (final_b ? (size_t)b.wp * b.h : 0) + (size_t)ry * b.wp;
+        for (int p = 0; p < n; p++) {
+            const int rx = x + p - b.x0;
+            if (!((pending >> p) & 1u) || rx < 0 || rx >= b.w) continue;
+            pending &= ~(1u << p);
+            if ((row[rx >> 5] >> (rx & 31)) & 1u) v |= 0xffu << (8 * p);
         }
-        __syncthreads();
-        // V step: OR over the element rows of the matching H array
-        for (int i = tid; i < n; i += MORPH_THREADS) {
-            const int r = i >> 4;
-            const uint32_t acc = v_rows<0>(el, H, n, r, k, rows);
-            cur[i] = (dil ? acc : ~acc) & inside_bits(gy0 + r, gk, w, h);
-        }
-        __syncthreads();
     }
-
-    // write the tile's own rows/words
-    if (out_u8) {
-        for (int i = tid; i < TILE_H * TILE_WORDS * 8; i += MORPH_THREADS) {   // 4 pixels per item
-            const int r = i / (TILE_WORDS * 8), q = i - r * (TILE_WORDS * 8);
-            const int gy = blockIdx.y * TILE_H + r, gx = blockIdx.x * TILE_WORDS * 32 + q * 4;
-            if (gy >= h || gx >= w) continue;
-            const uint32_t word = cur[(r + top) * TW + HALO_WORDS + (q >> 3)];
-            const uint32_t nib = (word >> ((q & 7) * 4)) & 0xfu;
-            uint8_t* o = out_u8 + (ptrdiff_t)gy * ostride + gx;
-            if (gx + 4 <= w && (((uintptr_t)o) & 3) == 0) {
-                *(uint32_t*)o = ((nib & 1u) ? 0xffu : 0u) | ((nib & 2u) ? 0xff00u : 0u) | ((nib & 4u) ? 0xff0000u : 0u) |
-                                ((nib & 8u) ? 0xff000000u : 0u);
-            } else {
-                for (int b = 0; b < 4 && gx + b < w; b++) o[b] = (nib >> b) & 1u ? 255 : 0;
-            }
-        }
+    uint8_t* o = masks + ((size_t)k * h + y) * w + x;
+    if (n == 4 && (((uintptr_t)o) & 3) == 0) {
+        *(uint32_t*)o = v;
     } else {
-        for (int i = tid; i < TILE_H * TILE_WORDS; i += MORPH_THREADS) {
-            const int r = i / TILE_WORDS, kk = i - r * TILE_WORDS;
-            const int gy = blockIdx.y * TILE_H + r, gk = blockIdx.x * TILE_WORDS + kk;
-            if (gy < h && gk < wp) out_bits[(size_t)gy * wp + gk] = cur[(r + top) * TW + HALO_WORDS + kk];
-        }
+        for (int p = 0; p < n; p++) o[p] = (uint8_t)(v >> (8 * p));
     }
+}
+
+// ---- pixel accuracy of a batch (nsof_pixel_accuracy_u8_batch_dev) ------------------------------------------------
+constexpr int PA_ROWS = 8;   // rows per workgroup of the partial counts
+
+// Equal pixels of mask rows by*8 .. by*8+7 against (gray(gt) > 127 ? 255 : 0), blockIdx.z = item; integer partials.
+__global__ __launch_bounds__(256) void k_pa_partial(const uint8_t* __restrict__ masks, const uint8_t* __restrict__ gt,
+                                                    ptrdiff_t gt_row_stride, ptrdiff_t gt_frame_stride, int w, int h,
+                                                    unsigned* __restrict__ partial)
+{
+    __shared__ unsigned red[4];
+    const int k = blockIdx.z, y0 = blockIdx.x * PA_ROWS;
+    const int rows = min(PA_ROWS, h - y0);
+    const uint8_t* m = masks + ((size_t)k * h + y0) * w;
+    const uint8_t* g = gt + (ptrdiff_t)k * gt_frame_stride + (ptrdiff_t)y0 * gt_row_stride;
+    unsigned cnt = 0;
+    for (int r = 0; r < rows; r++)
+        for (int x = threadIdx.x; x < w; x += 256) {
+            const uint8_t* px = g + (ptrdiff_t)r * gt_row_stride + 3 * (ptrdiff_t)x;
+            const unsigned t = nsof_gray_px(px[0], px[1], px[2], 3735, 19235, 9798) > 127 ? 255u : 0u;   // BGR2GRAY
+            cnt += m[(size_t)r * w + x] == t;
+        }
+    for (int d = 32; d > 0; d >>= 1) cnt += __shfl_down(cnt, d);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[(size_t)k * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+// One workgroup per item (blockIdx.x): the sum of its n partials -> count / (w * h) * 100, as calculate_pixel_accuracy.
+__global__ __launch_bounds__(256) void k_pa_final(const unsigned* __restrict__ partial, int n, double pixels,
+                                                  double* __restrict__ out)
+{
+    __shared__ unsigned long long red[4];
+    partial += (size_t)blockIdx.x * n;
+    unsigned long long acc = 0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
+    for (int d = 32; d > 0; d >>= 1) acc += __shfl_down(acc, d);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = (double)(red[0] + red[1] + red[2] + red[3]) / pixels * 100.0;
 }
 
 int build_elem(nsof_ctx* ctx, const uint8_t* elem, int kw, int kh, int ax, int ay, MorphElem* out)
@@ -261,29 +322,44 @@ int build_elem(nsof_ctx* ctx, const uint8_t* elem, int kw, int kh, int ax, int a
 
 inline int words_per_row(int w) { return 2 * ((w + 63) / 64); }
 
+// Passes the next launch of a chain takes (at most `left`), its LDS tile rows and bytes: the halo must hold the
+// chunk's horizontal reach and the tile ((1 + patterns) arrays of rows x TW words) must fit the LDS.  Returns the pass
+// count, or an nsof_status (< 0) when not even one pass fits.
+int plan_chunk(nsof_ctx* ctx, const MorphElem& el, int left, int* rows_out, size_t* smem_out)
+{
+    const int reach_x = el.ax > el.kw - 1 - el.ax ? el.ax : el.kw - 1 - el.ax;
+    const int up = el.ay, down = el.kh - 1 - el.ay;
+    int chunk = left;
+    if (reach_x > 0 && chunk > (HALO_WORDS * 32) / reach_x) chunk = (HALO_WORDS * 32) / reach_x;
+    size_t smem;
+    int rows;
+    for (;; chunk--) {   // LDS budget: (1 + patterns) arrays of rows x TW words
+        rows = TILE_H + chunk * (up + down);
+        smem = (size_t)(1 + (el.n_patterns ? el.n_patterns : 1)) * rows * TW * 4;
+        if ((smem <= 144 * 1024 && rows <= MAX_ROWS) || chunk <= 1) break;
+    }
+    if (chunk < 1 || smem > 160 * 1024 || rows > MAX_ROWS)
+        return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "structuring element too tall for the LDS tile");
+    *rows_out = rows;
+    *smem_out = smem;
+    return chunk;
+}
+
 // Runs the chain `ops` (n_pass passes) on bits; result to out_u8.  scratch: second bit image for multi-chunk chains.
 int run_chain(nsof_ctx* ctx, uint32_t* bits, uint32_t* scratch, int w, int h, const MorphElem& el, int n_pass,
               unsigned ops, uint8_t* out_u8, ptrdiff_t ostride)
 {
     const int wp = words_per_row(w);
-    const int reach_x = el.ax > el.kw - 1 - el.ax ? el.ax : el.kw - 1 - el.ax;
-    const int up = el.ay, down = el.kh - 1 - el.ay;
+    const int up = el.ay;
     dim3 grid((wp + TILE_WORDS - 1) / TILE_WORDS, (h + TILE_H - 1) / TILE_H);
     int done = 0;
     uint32_t* src = bits;
     uint32_t* dst = scratch;
     do {
-        int chunk = n_pass - done;
-        if (reach_x > 0 && chunk > (HALO_WORDS * 32) / reach_x) chunk = (HALO_WORDS * 32) / reach_x;
         size_t smem;
         int rows;
-        for (;; chunk--) {   // LDS budget: (1 + patterns) arrays of rows x TW words
-            rows = TILE_H + chunk * (up + down);
-            smem = (size_t)(1 + (el.n_patterns ? el.n_patterns : 1)) * rows * TW * 4;
-            if ((smem <= 144 * 1024 && rows <= MAX_ROWS) || chunk <= 1) break;
-        }
-        if (chunk < 1 || smem > 160 * 1024 || rows > MAX_ROWS)
-            return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "structuring element too tall for the LDS tile");
+        const int chunk = plan_chunk(ctx, el, n_pass - done, &rows, &smem);
+        if (chunk < 0) return chunk;
         const bool last = done + chunk >= n_pass;
         constexpr MorphElem e10 = ellipse10();
         const bool fixed10 = memcmp(&el, &e10, sizeof(MorphElem)) == 0;
@@ -299,6 +375,27 @@ int run_chain(nsof_ctx* ctx, uint32_t* bits, uint32_t* scratch, int w, int h, co
         done += chunk;
         uint32_t* t = src; src = dst; dst = t;
     } while (done < n_pass);
+    return NSOF_OK;
+}
+
+// The chain of the motion head: `iterations` x (dilate, erode) with the ksize x ksize ellipse; with no iterations a
+// single identity pass (1x1 element).  Validates ksize (iterations are the caller's).
+int mask_chain(nsof_ctx* ctx, int ksize, int iterations, MorphElem* el, int* n_pass, unsigned* ops)
+{
+    if (ksize < 1 || ksize > MAX_K) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "ksize 1..%d supported", MAX_K);
+    uint8_t elem[MAX_K * MAX_K];
+    nsof_structuring_element(NSOF_MORPH_ELLIPSE, ksize, ksize, elem);
+    int rc = build_elem(ctx, elem, ksize, ksize, -1, -1, el);
+    if (rc) return rc;
+    if (iterations == 0) {
+        uint8_t one = 1;
+        *n_pass = 1;
+        *ops = 1u;
+        return build_elem(ctx, &one, 1, 1, 0, 0, el);
+    }
+    *ops = 0;
+    for (int k = 0; k < iterations; k++) *ops |= 1u << (2 * k);   // even passes dilate, odd passes erode
+    *n_pass = 2 * iterations;
     return NSOF_OK;
 }
 
@@ -377,11 +474,10 @@ extern "C" int nsof_motion_mask_dev(nsof_ctx* ctx, const float* d_flow, ptrdiff_
     if (iterations < 0 || iterations > 16) return nsof_set_error(ctx, NSOF_EINVAL, "iterations must be 0..16");
     if (flow_stride_floats < 2 * (ptrdiff_t)width || (flow_stride_floats & 1) || mask_stride < width)
         return nsof_set_error(ctx, NSOF_EINVAL, "bad stride");
-    if (ksize < 1 || ksize > MAX_K) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "ksize 1..%d supported", MAX_K);
-    uint8_t elem[MAX_K * MAX_K];
-    nsof_structuring_element(NSOF_MORPH_ELLIPSE, ksize, ksize, elem);
     MorphElem el;
-    int rc = build_elem(ctx, elem, ksize, ksize, -1, -1, &el);
+    int n_pass;
+    unsigned ops;
+    int rc = mask_chain(ctx, ksize, iterations, &el, &n_pass, &ops);
     if (rc) return rc;
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     uint32_t *a, *b;
@@ -393,15 +489,7 @@ extern "C" int nsof_motion_mask_dev(nsof_ctx* ctx, const float* d_flow, ptrdiff_
                            flow_stride_floats, width, height, thresh, a, wp);
     }
     NSOF_HIP(ctx, hipGetLastError());
-    // (dilate, erode) x iterations; with no iterations the chain is a single identity pass (1x1 element)
-    if (iterations == 0) {
-        uint8_t one = 1;
-        if ((rc = build_elem(ctx, &one, 1, 1, 0, 0, &el))) return rc;
-        return run_chain(ctx, a, b, width, height, el, 1, 1u, d_mask, mask_stride);
-    }
-    unsigned ops = 0;
-    for (int k = 0; k < iterations; k++) ops |= 1u << (2 * k);   // even passes dilate, odd passes erode
-    return run_chain(ctx, a, b, width, height, el, 2 * iterations, ops, d_mask, mask_stride);
+    return run_chain(ctx, a, b, width, height, el, n_pass, ops, d_mask, mask_stride);
 }
 
 extern "C" int nsof_motion_mask(nsof_ctx* ctx, const float* flow, ptrdiff_t flow_stride_bytes, int width, int height,
@@ -433,5 +521,152 @@ extern "C" int nsof_motion_mask(nsof_ctx* ctx, const float* flow, ptrdiff_t flow
     if (int rcs = nsof_stream_sync_checked(ctx)) return rcs;   // incl. a lost hand-over of the exact-order flow kernels
     if (!out_dense)
         for (int y = 0; y < height; y++) memcpy(mask + (ptrdiff_t)y * mask_stride, hM + (size_t)y * width, (size_t)width);
+    return NSOF_OK;
+}
+
+extern "C" int nsof_motion_mask_sequence_dev(nsof_ctx* ctx, int n_pairs, const float* d_flows, int width, int height,
+                                             const int32_t* box_counts, const int32_t* boxes, double thresh, int ksize,
+                                             int iterations, uint8_t* d_masks)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!d_flows || !d_masks) return nsof_set_error(ctx, NSOF_EINVAL, "null pointer");
+    if (n_pairs < 1) return nsof_set_error(ctx, NSOF_ESHAPE, "mask_sequence: n_pairs %d < 1", n_pairs);
+    if (n_pairs > 65535) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "mask_sequence: more than 65535 pairs");
+    if (width < 1 || height < 1) return nsof_set_error(ctx, NSOF_ESHAPE, "empty flow field");
+    if (iterations < 0 || iterations > 16) return nsof_set_error(ctx, NSOF_EINVAL, "iterations must be 0..16");
+    if (reinterpret_cast<uintptr_t>(d_flows) & 7) return nsof_set_error(ctx, NSOF_EINVAL, "flows must be 8-byte aligned");
+    MorphElem el;
+    int n_pass;
+    unsigned ops;
+    int rc = mask_chain(ctx, ksize, iterations, &el, &n_pass, &ops);
+    if (rc) return rc;
+    // the box list (empty boxes dropped, paste order kept), the first box of every pair, the two job lists
+    std::vector<SegBox> bx;
+    std::vector<int> first(n_pairs + 1);
+    size_t words = 0;
+    for (int k = 0, i = 0; k < n_pairs; k++) {
+        first[k] = (int)bx.size();
+        const int cnt = box_counts ? box_counts[k] : 1;
+        if (cnt < 0) return nsof_set_error(ctx, NSOF_EINVAL, "mask_sequence: box count %d of pair %d", cnt, k);
+        if (cnt > 0 && box_counts && !boxes) return nsof_set_error(ctx, NSOF_EINVAL, "null pointer");
+        for (int c = 0; c < cnt; c++, i += box_counts ? 1 : 0) {
+            const int32_t* r = box_counts ? boxes + 4 * (size_t)i : nullptr;
+            const int x0 = r ? r[0] : 0, y0 = r ? r[1] : 0, x1 = r ? r[2] : width, y1 = r ? r[3] : height;
+            if (x1 <= x0 || y1 <= y0) continue;
+            if (x0 < 0 || y0 < 0 || x1 > width || y1 > height)
+                return nsof_set_error(ctx, NSOF_EINVAL, "mask_sequence: box (%d,%d,%d,%d) of pair %d leaves the %dx%d frame",
+                                      x0, y0, x1, y1, k, width, height);
+            SegBox b;
+            b.pair = k; b.x0 = x0; b.y0 = y0; b.w = x1 - x0; b.h = y1 - y0; b.wp = words_per_row(b.w);
+            b.off = words;
+            words += (2 * (size_t)b.wp * b.h + 63) & ~(size_t)63;   // A and B, 256-byte aligned
+            bx.push_back(b);
+        }
+    }
+    first[n_pairs] = (int)bx.size();
+    if (bx.size() > (size_t)INT32_MAX) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "mask_sequence: too many boxes");
+    std::vector<SegJob> pack, morph;
+    for (size_t i = 0; i < bx.size(); i++) {
+        for (int t = 0; t < (bx[i].h + 7) / 8; t++) pack.push_back(SegJob{(int)i, t});
+        const int tiles = (bx[i].wp + TILE_WORDS - 1) / TILE_WORDS * ((bx[i].h + TILE_H - 1) / TILE_H);
+        for (int t = 0; t < tiles; t++) morph.push_back(SegJob{(int)i, t});
+    }
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    // one table: boxes | first | pack jobs | morph jobs, through the pinned copy (rewritten only after its last upload)
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_first = up16(bx.size() * sizeof(SegBox)), o_pack = o_first + up16(first.size() * sizeof(int));
+    const size_t o_morph = o_pack + up16(pack.size() * sizeof(SegJob));
+    const size_t bytes = o_morph + morph.size() * sizeof(SegJob);
+    if (!ctx->seg_ev) NSOF_HIP(ctx, hipEventCreateWithFlags(&ctx->seg_ev, hipEventDisableTiming));
+    else NSOF_HIP(ctx, hipEventSynchronize(ctx->seg_ev));   // the previous call's upload has left the pinned copy
+    if (ctx->seg_bytes < bytes) {
+        NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->seg_h) hipHostFree(ctx->seg_h);
+        if (ctx->seg_d) hipFree(ctx->seg_d);
+        ctx->seg_h = ctx->seg_d = nullptr;
+        ctx->seg_bytes = 0;
+        const size_t cap = (bytes + bytes / 2 + 4095) & ~(size_t)4095;
+        if (hipHostMalloc(&ctx->seg_h, cap, hipHostMallocDefault) != hipSuccess || hipMalloc(&ctx->seg_d, cap) != hipSuccess)
+            return nsof_set_error(ctx, NSOF_ENOMEM, "segmentation tables (%zu bytes)", cap);
+        ctx->seg_bytes = cap;
+    }
+    if ((rc = nsof_ws_reserve(ctx, &ctx->tmp, &ctx->tmp_bytes, words * 4 > 256 ? words * 4 : 256))) return rc;
+    char* h = (char*)ctx->seg_h;
+    memcpy(h, bx.data(), bx.size() * sizeof(SegBox));
+    memcpy(h + o_first, first.data(), first.size() * sizeof(int));
+    memcpy(h + o_pack, pack.data(), pack.size() * sizeof(SegJob));
+    memcpy(h + o_morph, morph.data(), morph.size() * sizeof(SegJob));
+    NSOF_HIP(ctx, hipMemcpyAsync(ctx->seg_d, ctx->seg_h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    NSOF_HIP(ctx, hipEventRecord(ctx->seg_ev, ctx->stream));
+    const char* d = (const char*)ctx->seg_d;
+    const SegBox* d_boxes = (const SegBox*)d;
+    const SegJob* d_pack = (const SegJob*)(d + o_pack);
+    const SegJob* d_morph = (const SegJob*)(d + o_morph);
+    uint32_t* ws = (uint32_t*)ctx->tmp;
+    constexpr size_t MAX_JOBS = 1u << 20;   // workgroups per launch (grid x threads stays far below 2^32)
+    int final_b = 0;
+    if (!bx.empty()) {
+        {
+            nsof_prof_scope ps(ctx, NSOF_K_SEGMENT);
+            for (size_t i = 0; i < pack.size(); i += MAX_JOBS)
+                hipLaunchKernelGGL(k_mag_pack_jobs, dim3((unsigned)std::min(MAX_JOBS, pack.size() - i)), dim3(256), 0,
+                                   ctx->stream, d_pack + i, d_boxes, d_flows, width, height, thresh, ws);
+        }
+        NSOF_HIP(ctx, hipGetLastError());
+        constexpr MorphElem e10 = ellipse10();
+        const bool fixed10 = memcmp(&el, &e10, sizeof(MorphElem)) == 0;
+        auto kern = fixed10 ? k_morph_jobs<true> : k_morph_jobs<false>;
+        for (int done = 0; done < n_pass;) {
+            size_t smem;
+            int rows;
+            const int chunk = plan_chunk(ctx, el, n_pass - done, &rows, &smem);
+            if (chunk < 0) return chunk;
+            if (smem > 64 * 1024)
+                NSOF_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            {
+                nsof_prof_scope ps(ctx, NSOF_K_MORPH);
+                for (size_t i = 0; i < morph.size(); i += MAX_JOBS)
+                    hipLaunchKernelGGL(kern, dim3((unsigned)std::min(MAX_JOBS, morph.size() - i)), dim3(MORPH_THREADS),
+                                       smem, ctx->stream, d_morph + i, d_boxes, ws, final_b, el, chunk, ops >> done,
+                                       chunk * el.ay, rows);
+            }
+            NSOF_HIP(ctx, hipGetLastError());
+            done += chunk;
+            final_b ^= 1;
+        }
+    }
+    {
+        nsof_prof_scope ps(ctx, NSOF_K_SEGMENT);
+        hipLaunchKernelGGL(k_mask_compose, dim3((width + 255) / 256, (height + 3) / 4, n_pairs), dim3(256), 0, ctx->stream,
+                           d_boxes, (const int*)(d + o_first), ws, final_b, width, height, d_masks);
+    }
+    NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
+}
+
+extern "C" int nsof_pixel_accuracy_u8_batch_dev(nsof_ctx* ctx, int n, const uint8_t* d_masks, const uint8_t* d_gt,
+                                                ptrdiff_t gt_row_stride, ptrdiff_t gt_frame_stride, int width, int height,
+                                                double* d_out)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!d_masks || !d_gt || !d_out) return nsof_set_error(ctx, NSOF_EINVAL, "null pointer");
+    if (n < 1) return nsof_set_error(ctx, NSOF_ESHAPE, "pixel_accuracy: n %d < 1", n);
+    if (n > 65535) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "pixel_accuracy: more than 65535 items");
+    if (width < 1 || height < 1) return nsof_set_error(ctx, NSOF_ESHAPE, "empty image");
+    if (gt_row_stride < 3 * (ptrdiff_t)width || (n > 1 && gt_frame_stride < gt_row_stride * height))
+        return nsof_set_error(ctx, NSOF_EINVAL, "pixel_accuracy: gt stride");
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    const int nblk = (height + PA_ROWS - 1) / PA_ROWS;
+    int rc = nsof_ws_reserve(ctx, &ctx->tmp, &ctx->tmp_bytes, (size_t)n * nblk * sizeof(unsigned));
+    if (rc) return rc;
+    unsigned* partial = (unsigned*)ctx->tmp;
+    {
+        nsof_prof_scope ps(ctx, NSOF_K_SEGMENT);
+        hipLaunchKernelGGL(k_pa_partial, dim3(nblk, 1, n), dim3(256), 0, ctx->stream, d_masks, d_gt, gt_row_stride,
+                           gt_frame_stride, width, height, partial);
+    }
+    hipLaunchKernelGGL(k_pa_final, dim3(n), dim3(256), 0, ctx->stream, partial, nblk,
+                       (double)((long long)width * height), d_out);
+    NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }

@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256) void k_gray_u8(const uint8_t* __restrict__ src
     const int n = min(4, W - x);
     unsigned packed = 0;
     for (int i = 0; i < n; i++) {
-        const unsigned g = ((unsigned)s[3 * i] * w0 + (unsigned)s[3 * i + 1] * w1 + (unsigned)s[3 * i + 2] * w2 + (1u << 14)) >> 15;
+        const unsigned g = nsof_gray_px(s[3 * i], s[3 * i + 1], s[3 * i + 2], w0, w1, w2);
         packed |= g << (8 * i);
     }
     if (n == 4 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {

@@ -438,31 +438,24 @@ def run_prediction(frames_bgr, mem_state, cfg, names=None, csv_path=None, merge_
     return rows, ssim_mem, ssim_orig, mean_mem, mean_orig
 
 
-def prediction_sequence_dev(frames_bgr, mem_state, cfg, with_original=True, merge_flag=True, max_rects=32, ctx=None):
-    """``run_prediction``'s experiment for a whole sequence in HBM: ``frames_bgr`` uint8 CUDA tensor [n][H][W][3] (BGR as
-    ``cv2.imread`` gives them), ``mem_state`` the ``constructed3DMatrix`` stack.  Gray frames (``gray_u8_dev``), the device
-    gating table of slices OFFSET .. OFFSET+n-2 (one launch, ``gating.roi_from_surface_dev``; regrown once when a map has
-    more than ``max_rects`` components), the ROI flows of pairs 0 .. n-3 from that table (``farneback_roi_sequence_dev``,
-    gated as ``cfg.bug_compatible`` says), the full-frame flows (``farneback_sequence``), then one prediction warp and one
-    SSIM launch pair per path for all pairs (``predict.predict_sequence_dev`` reading the same table,
-    ``predict.ssim_batch_dev`` against frames 2 .. n-1).  Only the slices go up and the rectangle table comes back (one
-    copy, which also gives the host lists).  Returns a dict of CUDA tensors -- ``pred_mem`` / ``pred_orig`` uint8
-    [n-2][H][W][3], ``ssim_mem`` / ``ssim_orig`` float64 [n-2], ``flow_mem`` / ``flow_orig`` float32 [n-2][H][W][2] (the
-    un-negated Farneback flow; the ``orig`` entries are None without ``with_original``) -- and the host lists ``rects``
-    (the ROI rectangles of every pair) and ``boxes`` (the boxes its prediction warped, ``prediction_boxes``); equal to ``run_prediction`` with the GPU backends, bit for bit.  Synchronises at the
-    end, so the tensors can be read at once."""
+def _sequence_flows(frames_bgr, mem_state, cfg, with_original, max_rects, ctx, what):
+    """The front half of the sequence experiments in HBM: checks, gray frames (``gray_u8_dev``, RGB2GRAY as the scripts
+    convert), the device gating table of slices OFFSET .. OFFSET+n-2 (one launch, ``gating.roi_from_surface_dev``;
+    regrown once when a map has more than ``max_rects`` components), the ROI flows of pairs 0 .. n-3 from that table
+    (``farneback_roi_sequence_dev``, gated as ``cfg.bug_compatible`` says) and, with ``with_original``, the full-frame
+    flows (``farneback_sequence``).  Returns ``(gray, counts, rtab, rects, flow_mem, flow_orig, gate_frame)``: the gray
+    frames (still being read by the flow calls: the caller holds them until it synchronises), the device table, the
+    host rectangle lists of every pair and the un-negated flows (``flow_orig`` None without the original)."""
     import torch
 
     from . import predict
-    from .context import default_context
     from .farneback import farneback_roi_sequence_dev, farneback_sequence
-    ctx = ctx or default_context()
-    predict._u8_frames(frames_bgr, "prediction_sequence_dev")
+    predict._u8_frames(frames_bgr, what)
     if frames_bgr.dim() != 4 or frames_bgr.shape[3] != 3:
-        raise predict.NsofValueError("prediction_sequence_dev: uint8 [n][H][W][3] frames expected")
+        raise predict.NsofValueError(f"{what}: uint8 [n][H][W][3] frames expected")
     n, H, W = (int(v) for v in frames_bgr.shape[:3])  # noqa: N806
     if n < 3:
-        raise ValueError(f"prediction_sequence_dev: {n} frames; the experiment needs at least 3")
+        raise ValueError(f"{what}: {n} frames; the experiment needs at least 3")
     rows, cols = int(mem_state.shape[0]), int(mem_state.shape[1])
     if rows > H // cfg.MEMSIZE or cols > W // cfg.MEMSIZE:
         raise ValueError(f"gating map {rows}x{cols} larger than the {H // cfg.MEMSIZE}x{W // cfg.MEMSIZE} transition picture")
@@ -476,14 +469,7 @@ def prediction_sequence_dev(frames_bgr, mem_state, cfg, with_original=True, merg
                                                 np.float64)).to(dev)
     gray = torch.empty((n - 1, H, W), dtype=torch.uint8, device=dev)
     flow_mem = torch.empty((n - 2, H, W, 2), dtype=torch.float32, device=dev)   # zero-filled by the ROI flow call
-    pred_mem = torch.empty((n - 2, H, W, 3), dtype=torch.uint8, device=dev)
-    ssim_mem = torch.empty((n - 2,), dtype=torch.float64, device=dev)
-    if with_original:
-        flow_orig = torch.empty_like(flow_mem)
-        pred_orig = torch.empty_like(pred_mem)
-        ssim_orig = torch.empty_like(ssim_mem)
-    else:
-        flow_orig = pred_orig = ssim_orig = None
+    flow_orig = torch.empty_like(flow_mem) if with_original else None
     torch.cuda.synchronize(dev)
     for k in range(n - 1):
         predict.gray_u8_dev(frames_bgr[k], gray[k], "RGB2GRAY", ctx=ctx)
@@ -496,16 +482,112 @@ def prediction_sequence_dev(frames_bgr, mem_state, cfg, with_original=True, merg
         c, r = counts.cpu().numpy(), rtab.cpu().numpy()
     lists = [[tuple(int(v) for v in r[k, i]) for i in range(int(c[k]))] for k in range(n - 1)]
     farneback_roi_sequence_dev(gray, counts, rtab, flow_mem, cfg.farneback_params, gate_frame=gf, ctx=ctx)
+    if with_original:
+        farneback_sequence(gray, flow_orig, n - 1, H, W, cfg.farneback_params, row_stride=int(gray.stride(1)),
+                           frame_stride=int(gray.stride(0)), ctx=ctx)
+    rects = [lists[k + gf] for k in range(n - 2)]
+    return gray, counts, rtab, rects, flow_mem, flow_orig, gf
+
+
+def _experiment_boxes(rects, cfg, merge_flag, frame_hw):
+    """The boxes of every pair from its ROI rectangles, as the scripts' ``task_results`` form them: the union box (FLAG 2,
+    the one rectangle of the device table), every rectangle (FLAG 1) or their padded bounding box (FLAG 1 merged)."""
+    return [prediction_boxes(rs, len(rs) + 1, 1, merge_flag, frame_hw) if cfg.FLAG == 1 else rs for rs in rects]
+
+
+def prediction_sequence_dev(frames_bgr, mem_state, cfg, with_original=True, merge_flag=True, max_rects=32, ctx=None):
+    """``run_prediction``'s experiment for a whole sequence in HBM: ``frames_bgr`` uint8 CUDA tensor [n][H][W][3] (BGR as
+    ``cv2.imread`` gives them), ``mem_state`` the ``constructed3DMatrix`` stack.  Gray frames, gating table, ROI and
+    full-frame flows as ``_sequence_flows`` computes them, then one prediction warp and one SSIM launch pair per path for
+    all pairs (``predict.predict_sequence_dev`` reading the same table, ``predict.ssim_batch_dev`` against frames
+    2 .. n-1).  Only the slices go up and the rectangle table comes back (one copy, which also gives the host lists).
+    Returns a dict of CUDA tensors -- ``pred_mem`` / ``pred_orig`` uint8 [n-2][H][W][3], ``ssim_mem`` / ``ssim_orig``
+    float64 [n-2], ``flow_mem`` / ``flow_orig`` float32 [n-2][H][W][2] (the un-negated Farneback flow; the ``orig``
+    entries are None without ``with_original``) -- and the host lists ``rects`` (the ROI rectangles of every pair) and
+    ``boxes`` (the boxes its prediction warped, ``prediction_boxes``); equal to ``run_prediction`` with the GPU backends,
+    bit for bit.  Synchronises at the end, so the tensors can be read at once."""
+    import torch
+
+    from . import predict
+    from .context import default_context
+    ctx = ctx or default_context()
+    gray, counts, rtab, rects, flow_mem, flow_orig, gf = _sequence_flows(frames_bgr, mem_state, cfg, with_original,
+                                                                         max_rects, ctx, "prediction_sequence_dev")
+    n, H, W = (int(v) for v in frames_bgr.shape[:3])  # noqa: N806
+    dev = frames_bgr.device
+    pred_mem = torch.empty((n - 2, H, W, 3), dtype=torch.uint8, device=dev)
+    ssim_mem = torch.empty((n - 2,), dtype=torch.float64, device=dev)
+    if with_original:
+        pred_orig = torch.empty_like(pred_mem)
+        ssim_orig = torch.empty_like(ssim_mem)
+    else:
+        pred_orig = ssim_orig = None
+    torch.cuda.synchronize(dev)
     predict.predict_sequence_dev(frames_bgr, flow_mem, pred_mem, counts=counts, rects=rtab, gate_frame=gf,
                                  merge_padding=PREDICT_PADDING if cfg.FLAG == 1 and merge_flag else None, ctx=ctx)
     predict.ssim_batch_dev(pred_mem, frames_bgr[2:], out=ssim_mem, ctx=ctx)
     if with_original:
-        farneback_sequence(gray, flow_orig, n - 1, H, W, cfg.farneback_params, row_stride=int(gray.stride(1)),
-                           frame_stride=int(gray.stride(0)), ctx=ctx)
         predict.predict_sequence_dev(frames_bgr, flow_orig, pred_orig, border_mode=predict.BORDER_CONSTANT, ctx=ctx)
         predict.ssim_batch_dev(pred_orig, frames_bgr[2:], out=ssim_orig, ctx=ctx)
     ctx.synchronize()
-    rects = [lists[k + gf] for k in range(n - 2)]
-    boxes = [prediction_boxes(rs, len(rs) + 1, 1, merge_flag, (H, W)) if cfg.FLAG == 1 else rs for rs in rects]
     return dict(pred_mem=pred_mem, pred_orig=pred_orig, ssim_mem=ssim_mem, ssim_orig=ssim_orig, flow_mem=flow_mem,
-                flow_orig=flow_orig, rects=rects, boxes=boxes)
+                flow_orig=flow_orig, rects=rects, boxes=_experiment_boxes(rects, cfg, merge_flag, (H, W)))
+
+
+def segmentation_sequence_dev(frames_bgr, gt_masks_bgr, mem_state, cfg, with_original=True, merge_flag=False, seg_th=1,
+                              max_rects=32, ctx=None, timings=None):
+    """``run_segmentation``'s experiment for a whole sequence in HBM: ``frames_bgr`` and ``gt_masks_bgr`` uint8 CUDA
+    tensors [n][H][W][3] (as ``cv2.imread`` gives them), ``mem_state`` the ``constructed3DMatrix`` stack.  Gray frames,
+    gating table, ROI and full-frame flows as ``_sequence_flows`` computes them; then per path ONE segmentation call
+    over all pairs (``segment.motion_mask_sequence_dev``: the Mem path on the boxes ``task_results`` forms from each
+    pair's rectangles, the Original path on the whole frame) and ONE pixel-accuracy call against ground-truth frames
+    1 .. n-2 (``segment.pixel_accuracy_batch_dev``).  Returns a dict: ``mask_mem`` / ``mask_orig`` uint8 [n-2][H][W],
+    ``pa_mem`` / ``pa_orig`` float64 [n-2], ``flow_mem`` / ``flow_orig`` float32 [n-2][H][W][2] (CUDA tensors; the
+    ``orig`` entries are None without ``with_original``), the host lists ``rects`` and ``boxes``, and ``mean_mem`` /
+    ``mean_orig``, the two means ``run_segmentation`` returns.  Equal to ``run_segmentation`` with the GPU backends, bit
+    for bit.  ``timings`` (a dict) receives the wall time of the flow stage and of the mask + accuracy stage of each
+    path.  Synchronises at the end."""
+    import time
+
+    import torch
+
+    from . import predict, segment
+    from .context import default_context
+    ctx = ctx or default_context()
+    predict._u8_frames(gt_masks_bgr, "segmentation_sequence_dev")
+    if gt_masks_bgr.dim() != 4 or tuple(gt_masks_bgr.shape) != tuple(frames_bgr.shape):
+        raise predict.NsofValueError(f"segmentation_sequence_dev: ground truth {tuple(gt_masks_bgr.shape)} does not match "
+                                     f"the frames {tuple(frames_bgr.shape)}")
+    t0 = time.perf_counter()
+    gray, counts, rtab, rects, flow_mem, flow_orig, gf = _sequence_flows(frames_bgr, mem_state, cfg, with_original,
+                                                                         max_rects, ctx, "segmentation_sequence_dev")
+    n, H, W = (int(v) for v in frames_bgr.shape[:3])  # noqa: N806
+    dev = frames_bgr.device
+    boxes = _experiment_boxes(rects, cfg, merge_flag, (H, W))
+    mask_mem = torch.empty((n - 2, H, W), dtype=torch.uint8, device=dev)
+    pa_mem = torch.empty((n - 2,), dtype=torch.float64, device=dev)
+    mask_orig = torch.empty_like(mask_mem) if with_original else None
+    pa_orig = torch.empty_like(pa_mem) if with_original else None
+    torch.cuda.synchronize(dev)
+    t1 = time.perf_counter()
+    gt = gt_masks_bgr[1:n - 1]
+    segment.motion_mask_sequence_dev(flow_mem, boxes, mask_mem, seg_th, ctx=ctx)
+    segment.pixel_accuracy_batch_dev(mask_mem, gt, pa_mem, ctx=ctx)
+    ctx.synchronize()
+    t2 = time.perf_counter()
+    if with_original:
+        segment.motion_mask_sequence_dev(flow_orig, None, mask_orig, seg_th, ctx=ctx)
+        segment.pixel_accuracy_batch_dev(mask_orig, gt, pa_orig, ctx=ctx)
+    ctx.synchronize()
+    t3 = time.perf_counter()
+    if timings is not None:
+        timings.update(flow_s=t1 - t0, seg_mem_s=t2 - t1, seg_orig_s=t3 - t2, pairs=n - 2)
+
+    def mean(t):   # run_segmentation's running sum, in pair order
+        acc = 0.0
+        for v in t.cpu().tolist():
+            acc += v
+        return acc / max(n - 2, 1)
+    return dict(mask_mem=mask_mem, mask_orig=mask_orig, pa_mem=pa_mem, pa_orig=pa_orig, flow_mem=flow_mem,
+                flow_orig=flow_orig, rects=rects, boxes=boxes, mean_mem=mean(pa_mem),
+                mean_orig=mean(pa_orig) if with_original else None)

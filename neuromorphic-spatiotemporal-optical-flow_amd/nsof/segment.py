@@ -94,6 +94,69 @@ def motion_mask_dev(d_flow, d_mask, height, width, seg_th=1, ksize=10, iteration
     ctx.check(rc, "motion_mask_dev")
 
 
+def motion_mask_sequence_dev(flows, boxes=None, out=None, seg_th=1, ksize=10, iterations=5, *, ctx=None):
+    """The head over the boxes of every pair of a sequence (``nsof_motion_mask_sequence_dev``): ``flows`` float32 CUDA
+    tensor [n_pairs][H][W][2] (contiguous), ``boxes`` a list per pair of ``(x0, y0, x1, y1)`` boxes in paste order, or
+    None for one whole-frame box per pair (the full-frame baseline).  ``out[k]`` (uint8 [n_pairs][H][W], contiguous;
+    allocated when None) is zero except where pair k's boxes lie, and there it is the ``motion_mask`` of the crop of
+    the last box that covers the pixel -- ``task_results`` of that pair, bit for bit.  Empty boxes are skipped.
+    Asynchronous on the context's stream."""
+    import torch
+    ctx = ctx or default_context()
+    if not isinstance(flows, torch.Tensor) or not flows.is_cuda or flows.dtype != torch.float32:
+        raise NsofValueError("motion_mask_sequence_dev: flows must be a float32 CUDA tensor", _lib.NSOF_EINVAL)
+    if flows.dim() != 4 or flows.shape[3] != 2 or not flows.is_contiguous() or flows.shape[0] < 1:
+        raise NsofValueError(f"motion_mask_sequence_dev: contiguous [n_pairs][H][W][2] flows expected (got "
+                             f"{tuple(flows.shape)})", _lib.NSOF_ESHAPE)
+    n, h, w = (int(v) for v in flows.shape[:3])
+    counts = table = None
+    if boxes is not None:
+        if len(boxes) != n:
+            raise NsofValueError(f"motion_mask_sequence_dev: {len(boxes)} box lists for {n} pairs", _lib.NSOF_ESHAPE)
+        counts = np.array([len(b) for b in boxes], np.int32)
+        table = np.array([tuple(int(v) for v in r) for b in boxes for r in b], np.int32).reshape(-1, 4)
+        table = np.ascontiguousarray(table) if table.size else np.zeros((1, 4), np.int32)
+    if out is None:
+        out = torch.empty((n, h, w), dtype=torch.uint8, device=flows.device)
+        torch.cuda.synchronize(flows.device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8 or \
+            tuple(out.shape) != (n, h, w) or not out.is_contiguous():
+        raise NsofValueError("motion_mask_sequence_dev: out must be a contiguous uint8 CUDA tensor [n_pairs][H][W]",
+                             _lib.NSOF_ESHAPE)
+    rc = ctx._lib.nsof_motion_mask_sequence_dev(
+        ctx.ptr, n, dev_ptr(flows), w, h, None if counts is None else counts.ctypes.data,
+        None if table is None else table.ctypes.data, float(seg_th), int(ksize), int(iterations), dev_ptr(out))
+    ctx.check(rc, "motion_mask_sequence_dev")
+    return out
+
+
+def pixel_accuracy_batch_dev(masks, gt_bgr, out=None, *, ctx=None):
+    """``calculate_pixel_accuracy(masks[i], (BGR2GRAY(gt_bgr[i]) > 127) * 255)`` of every item at once
+    (``nsof_pixel_accuracy_u8_batch_dev``): ``masks`` uint8 CUDA tensor [n][H][W] (contiguous), ``gt_bgr`` uint8 CUDA
+    tensor [n][H][W][3] (pixels interleaved, row / frame strides free).  Results in ``out`` (float64 CUDA tensor [n],
+    allocated when None), each equal to the host formula exactly.  Asynchronous."""
+    import torch
+    ctx = ctx or default_context()
+    for t, what in ((masks, "masks"), (gt_bgr, "gt_bgr")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
+            raise NsofValueError(f"pixel_accuracy_batch_dev: {what} must be a uint8 CUDA tensor", _lib.NSOF_EINVAL)
+    if masks.dim() != 3 or not masks.is_contiguous() or masks.shape[0] < 1 or gt_bgr.dim() != 4 or \
+            tuple(gt_bgr.shape) != tuple(masks.shape) + (3,) or gt_bgr.stride(3) != 1 or gt_bgr.stride(2) != 3:
+        raise NsofValueError(f"pixel_accuracy_batch_dev: contiguous masks [n][H][W] and interleaved frames [n][H][W][3] "
+                             f"expected (got {tuple(masks.shape)}, {tuple(gt_bgr.shape)})", _lib.NSOF_ESHAPE)
+    n, h, w = (int(v) for v in masks.shape)
+    if out is None:
+        out = torch.empty((n,), dtype=torch.float64, device=masks.device)
+        torch.cuda.synchronize(masks.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (n,) or \
+            not out.is_contiguous() or not out.is_cuda:
+        raise NsofValueError("pixel_accuracy_batch_dev: out must be a contiguous float64 CUDA tensor [n]", _lib.NSOF_ESHAPE)
+    rc = ctx._lib.nsof_pixel_accuracy_u8_batch_dev(ctx.ptr, n, dev_ptr(masks), dev_ptr(gt_bgr), int(gt_bgr.stride(1)),
+                                                   int(gt_bgr.stride(0)), w, h, dev_ptr(out))
+    ctx.check(rc, "pixel_accuracy_batch_dev")
+    return out
+
+
 def process_flow_region(mag, ang=None, seg_th=1, *, ctx=None):
     """optical_flow_seg.py:322-357 with the same arguments (``ang`` only feeds the unused hue image)."""
     mask = np.where(np.asarray(mag) > seg_th, np.uint8(255), np.uint8(0))
