@@ -430,9 +430,11 @@ int nsof_roi_from_surface(const double* current, int rows, int cols, int frame_w
                           int flag, int* rects, int max_rects);
 
 /* Device twin of nsof_roi_from_surface (replaces optical_flow_seg.py:115-121,211-252 for maps that are already in HBM):
- * n_maps gating maps at once, one wavefront each -- d_current: device currents, double, map k at d_current + k*map_stride
- * (rows x cols cells, at most 64 x 64); gray map, threshold, connected components in raster order (bit-parallel flood
- * fill), rectangles as above.  d_counts[k] = number of rectangles of map k (may exceed max_rects; only the first max_rects
+ * n_maps gating maps at once -- d_current: device currents, double, map k at d_current + k*map_stride (rows x cols
+ * cells, any size up to 2^27 cells; NSOF_ESHAPE when the map is larger than the frame's transition picture); gray map,
+ * threshold, connected components in raster order, rectangles as above.  Maps of at most 64 x 64 cells take one
+ * wavefront each (bit-parallel flood fill); larger maps a union-find over the context's workspace, processed in chunks
+ * of maps when a batch's scratch is large.  d_counts[k] = number of rectangles of map k (may exceed max_rects; only the first max_rects
  * are stored), d_rects[k][max_rects][4] = (x0, y0, x1, y1); d_gray (optional, may be NULL): the 8-bit gating maps
  * [n_maps][rows][cols].  All DEVICE memory; asynchronous on the context's stream. */
 int nsof_roi_from_surface_dev(nsof_ctx* ctx, const double* d_current, int n_maps, size_t map_stride, int rows, int cols,

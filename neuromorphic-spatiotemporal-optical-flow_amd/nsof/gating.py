@@ -267,9 +267,10 @@ def roi_from_surface(current, frame_hw, cfg):
 
 def roi_from_surface_dev(d_current, n_maps, map_hw, frame_hw, cfg, max_rects=32, ctx=None, want_gray=False, map_stride=None):
     """Device twin of ``roi_from_surface`` for ``n_maps`` gating maps already in HBM (``d_current``: torch float64 tensor
-    / device address, map k at ``+ k * map_stride`` doubles, default rows * cols): one wavefront per map forms the gray
-    map, thresholds it, labels the connected components in raster order and writes the crop rectangles
-    (``nsof_roi_from_surface_dev``; optical_flow_seg.py:115-121, 211-252).  Returns device tensors
+    / device address, map k at ``+ k * map_stride`` doubles, default rows * cols; any map size up to 2^27 cells that fits
+    the frame's transition picture): the device forms the gray map, thresholds it, labels the connected components in
+    raster order and writes the crop rectangles (``nsof_roi_from_surface_dev``; optical_flow_seg.py:115-121, 211-252) --
+    one wavefront per map up to 64 x 64 cells, a union-find over the context's workspace above that, same results.  Returns device tensors
     ``(counts int32 [n_maps], rects int32 [n_maps][max_rects][4][, gray uint8 [n_maps][rows][cols]])`` -- nothing is
     synchronised or copied to the host; ``rects_to_host`` fetches them in one small copy."""
     import torch

@@ -26,9 +26,10 @@ def events_to_rois(x, y, p, t, sensor_hw, cfg, version=1, polarity="split", slic
                    silent_v=0.0, snapshot_every=33, ctx=None, max_rects=32):
     """Run the accumulator over the stream and return, for every snapshot, the gating map and its ROI rectangles
     (x0, y0, x1, y1) in sensor pixels.  Everything between the event upload and the result stays in HBM: the block maxima of
-    the device current of every snapshot (``Accumulator.block_current_dev``), then ONE launch of the gating kernel over
-    all snapshots (``gating.roi_from_surface_dev``: gray map, threshold, connected components, rectangles -- one
-    wavefront per snapshot); the rectangle table and the tiny gray maps come back in one copy at the end."""
+    the device current of every snapshot (``Accumulator.block_current_dev``), then ONE gating call over all snapshots
+    (``gating.roi_from_surface_dev``: gray map, threshold, connected components, rectangles -- for every map size); the
+    rectangle table and the gray maps come back in one copy at the end.  With FLAG 2 a snapshot's list holds the union
+    box alone (or nothing)."""
     import torch
 
     from .context import default_context
@@ -36,15 +37,6 @@ def events_to_rois(x, y, p, t, sensor_hw, cfg, version=1, polarity="split", slic
     H, W = sensor_hw  # noqa: N806
     idx = slice_index_array(t, slice_us)
     rows, cols = H // cfg.MEMSIZE, W // cfg.MEMSIZE
-    if rows > 64 or cols > 64:
-        # the gating kernel holds a map in one wavefront (64 x 64 cells at most: the reference's maps are 13 x 24 and
-        # smaller); larger maps -- e.g. a 1280 x 720 sensor with MEMSIZE 8 -- take the host mirror of the same arithmetic
-        out = events_to_rois_host(x, y, p, t, sensor_hw, cfg, version, polarity, slice_us, active_v, silent_v,
-                                  snapshot_every, ctx=ctx)
-        if cfg.FLAG == 2:   # the union box, as the device kernel returns it
-            out = [(g, [(min(r[0] for r in rs), min(r[1] for r in rs), max(r[2] for r in rs), max(r[3] for r in rs))] if rs else [])
-                   for g, rs in out]
-        return out
     acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx)
     try:
         acc.step(x, y, p, t, idx, snap_every=snapshot_every)
@@ -125,9 +117,6 @@ def events_to_roi_flows(x, y, p, t, sensor_hw, cfg, slice_us=1000, active_v=-6.0
     if n_frames < 2:
         raise ValueError("the stream is shorter than two snapshots")
     rows, cols = H // cfg.MEMSIZE, W // cfg.MEMSIZE
-    if rows > 64 or cols > 64:
-        raise ValueError(f"gating map {rows}x{cols}: the device gating kernel takes maps up to 64x64 cells (use events_to_rois_host "
-                         "+ farneback_pairs for finer grids)")
     frames = torch.empty((n_frames, H, W), dtype=torch.float32 if f32 else torch.uint8, device=dev)
     cur = torch.empty((n_frames, rows, cols), dtype=torch.float64, device=dev)
     flows = torch.empty((n_frames - 1, H, W, 2), dtype=torch.float32, device=dev)   # zero-filled by the flow call
@@ -459,8 +448,6 @@ def _sequence_flows(frames_bgr, mem_state, cfg, with_original, max_rects, ctx, w
     rows, cols = int(mem_state.shape[0]), int(mem_state.shape[1])
     if rows > H // cfg.MEMSIZE or cols > W // cfg.MEMSIZE:
         raise ValueError(f"gating map {rows}x{cols} larger than the {H // cfg.MEMSIZE}x{W // cfg.MEMSIZE} transition picture")
-    if rows > 64 or cols > 64:
-        raise ValueError(f"gating map {rows}x{cols}: the device gating kernel takes maps up to 64x64 cells")
     if mem_state.shape[2] < cfg.OFFSET + n - 1:
         raise ValueError(f"the stack has {mem_state.shape[2]} slices; {n} frames need OFFSET + {n - 1}")
     gf = 0 if cfg.bug_compatible else 1
