@@ -557,6 +557,16 @@ int nsof_predict_sequence_u8_dev(nsof_ctx* ctx, int n_pairs, const uint8_t* d_fr
 int nsof_ssim_u8_batch_dev(nsof_ctx* ctx, int n, const uint8_t* d_a, ptrdiff_t a_stride, ptrdiff_t a_item_stride,
                            int a_pixel_step, const uint8_t* d_b, ptrdiff_t b_stride, ptrdiff_t b_item_stride,
                            int b_pixel_step, int width, int height, double data_range, double* d_out);
+/* Middlebury colour coding (flow_viz.flow_to_image, optical_flow_prediction.py:12-19, :524, :578) of n float32 (u,v)
+ * flow fields on the DEVICE: item i at d_flows + i*item_stride_floats, rows row_stride_floats apart; flow := sign*flow
+ * (sign +1 / -1), then np.clip(flow, 0, clip_flow) when clip_flow >= 0, then normalised by the item's own max
+ * magnitude + 1e-5 (max_flow < 0) or by max_flow + 1e-5.  d_out uint8 [H][W][3] per item (strides in bytes), RGB, or
+ * BGR with convert_to_bgr.  d_norms (optional, DEVICE float32 [n]) receives the float32 divisor used per item.
+ * Asynchronous on the context's stream; flows must be finite. */
+int nsof_flow_to_image_dev(nsof_ctx* ctx, int n, const float* d_flows, ptrdiff_t row_stride_floats,
+                           ptrdiff_t item_stride_floats, int width, int height, int sign, double clip_flow,
+                           double max_flow, int convert_to_bgr, uint8_t* d_out, ptrdiff_t out_row_stride,
+                           ptrdiff_t out_item_stride, float* d_norms);
 
 #ifdef __cplusplus
 }

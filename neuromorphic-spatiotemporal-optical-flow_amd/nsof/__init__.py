@@ -33,7 +33,7 @@ from .predict import (BORDER_CONSTANT, BORDER_REPLICATE, INTER_LINEAR, calculate
                       structural_similarity)
 from .pipeline import prediction_sequence_dev, run_prediction, run_segmentation, segmentation_sequence_dev  # noqa: F401,E402
 from .frames import compress_image, crop_image, im2double, imresize_lanczos3, process_images  # noqa: F401,E402
-from .flowviz import flow_to_image, flow_uv_to_colors, make_colorwheel, viz  # noqa: F401,E402
+from .flowviz import flow_to_image, flow_to_image_dev, flow_uv_to_colors, make_colorwheel, save_viz, viz  # noqa: F401,E402
 
 __all__ = ["calcOpticalFlowFarneback", "install", "uninstall", "FarnebackParams", "farneback_batch", "Context",
            "default_context", "simulate", "update_state", "resistance_exp", "Accumulator", "NsofError", "error"]

@@ -114,6 +114,7 @@ SIGNATURES = {
     "nsof_ssim_u8": (_i, [_vp, _vp, _pd, _i, _vp, _pd, _i, _i, _i, _d, C.POINTER(_d)]),
     "nsof_predict_sequence_u8_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "nsof_ssim_u8_batch_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _d, _vp]),
+    "nsof_flow_to_image_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _i, _d, _d, _i, _vp, _pd, _pd, _vp]),
 }
 
 _lib = None

@@ -482,7 +482,8 @@ def _experiment_boxes(rects, cfg, merge_flag, frame_hw):
     return [prediction_boxes(rs, len(rs) + 1, 1, merge_flag, frame_hw) if cfg.FLAG == 1 else rs for rs in rects]
 
 
-def prediction_sequence_dev(frames_bgr, mem_state, cfg, with_original=True, merge_flag=True, max_rects=32, ctx=None):
+def prediction_sequence_dev(frames_bgr, mem_state, cfg, with_original=True, merge_flag=True, max_rects=32, ctx=None,
+                            with_viz=False):
     """``run_prediction``'s experiment for a whole sequence in HBM: ``frames_bgr`` uint8 CUDA tensor [n][H][W][3] (BGR as
     ``cv2.imread`` gives them), ``mem_state`` the ``constructed3DMatrix`` stack.  Gray frames, gating table, ROI and
     full-frame flows as ``_sequence_flows`` computes them, then one prediction warp and one SSIM launch pair per path for
@@ -492,10 +493,12 @@ def prediction_sequence_dev(frames_bgr, mem_state, cfg, with_original=True, merg
     float64 [n-2], ``flow_mem`` / ``flow_orig`` float32 [n-2][H][W][2] (the un-negated Farneback flow; the ``orig``
     entries are None without ``with_original``) -- and the host lists ``rects`` (the ROI rectangles of every pair) and
     ``boxes`` (the boxes its prediction warped, ``prediction_boxes``); equal to ``run_prediction`` with the GPU backends,
-    bit for bit.  Synchronises at the end, so the tensors can be read at once."""
+    bit for bit.  ``with_viz`` adds ``viz_mem`` / ``viz_orig``, uint8 [n-2][H][W][3]: the script's ``viz`` of the
+    negated flows (:524, :578) in the B,G,R order it saves (``flowviz.flow_to_image_dev``, one call per path;
+    ``flowviz.save_viz`` writes them).  Synchronises at the end, so the tensors can be read at once."""
     import torch
 
-    from . import predict
+    from . import flowviz, predict
     from .context import default_context
     ctx = ctx or default_context()
     gray, counts, rtab, rects, flow_mem, flow_orig, gf = _sequence_flows(frames_bgr, mem_state, cfg, with_original,
@@ -509,6 +512,9 @@ def prediction_sequence_dev(frames_bgr, mem_state, cfg, with_original=True, merg
         ssim_orig = torch.empty_like(ssim_mem)
     else:
         pred_orig = ssim_orig = None
+    if with_viz:
+        viz_mem = torch.empty_like(pred_mem)
+        viz_orig = torch.empty_like(pred_mem) if with_original else None
     torch.cuda.synchronize(dev)
     predict.predict_sequence_dev(frames_bgr, flow_mem, pred_mem, counts=counts, rects=rtab, gate_frame=gf,
                                  merge_padding=PREDICT_PADDING if cfg.FLAG == 1 and merge_flag else None, ctx=ctx)
@@ -516,9 +522,16 @@ def prediction_sequence_dev(frames_bgr, mem_state, cfg, with_original=True, merg
     if with_original:
         predict.predict_sequence_dev(frames_bgr, flow_orig, pred_orig, border_mode=predict.BORDER_CONSTANT, ctx=ctx)
         predict.ssim_batch_dev(pred_orig, frames_bgr[2:], out=ssim_orig, ctx=ctx)
+    if with_viz:
+        flowviz.flow_to_image_dev(flow_mem, viz_mem, sign=-1, convert_to_bgr=True, ctx=ctx)
+        if with_original:
+            flowviz.flow_to_image_dev(flow_orig, viz_orig, sign=-1, convert_to_bgr=True, ctx=ctx)
     ctx.synchronize()
-    return dict(pred_mem=pred_mem, pred_orig=pred_orig, ssim_mem=ssim_mem, ssim_orig=ssim_orig, flow_mem=flow_mem,
-                flow_orig=flow_orig, rects=rects, boxes=_experiment_boxes(rects, cfg, merge_flag, (H, W)))
+    res = dict(pred_mem=pred_mem, pred_orig=pred_orig, ssim_mem=ssim_mem, ssim_orig=ssim_orig, flow_mem=flow_mem,
+               flow_orig=flow_orig, rects=rects, boxes=_experiment_boxes(rects, cfg, merge_flag, (H, W)))
+    if with_viz:
+        res.update(viz_mem=viz_mem, viz_orig=viz_orig)
+    return res
 
 
 def segmentation_sequence_dev(frames_bgr, gt_masks_bgr, mem_state, cfg, with_original=True, merge_flag=False, seg_th=1,
