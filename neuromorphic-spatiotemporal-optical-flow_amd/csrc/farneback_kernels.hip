@@ -1137,6 +1137,11 @@ __global__ __launch_bounds__(256) void k_polyexp(const float* __restrict__ img, 
 // the double-buffered moment rows; one barrier per step.  Neither role carries the other's registers across its
 // pass (the column window of 2N+1 rows on one side, the moment window and the double taps on the other), so the
 // taps stay in scalar registers and radius 10 fits 4 waves per SIMD where the single-role kernel spilled at 256.
+// Occupancy: 40 KiB of LDS lets 4 workgroups (8 waves per SIMD) share a CU when a wave fits 64 VGPRs and 80 SGPRs.  The
+// horizontal pass hands each output on as soon as it is final (moment row 2 before row 1, so b1 * ig03 dies early), which
+// keeps it near 46 VGPRs at N = 5 (82 when o0..o4 and t03 lived across all three rows: 2 workgroups per CU); for N <= 7
+// the launch bound asks for the 80 SGPRs, paid with a few scalar taps kept in VGPR lanes (v_readlane in the loop).
+// tests/test_codeobj_polyexp_budget.py holds the code object to that budget.
 // ---------------------------------------------------------------------------------------
 // U8 (the full-resolution level): the level image is not read from memory but formed in the vertical pass from the
 // 8-bit frame itself -- the 3 x 3 [k1 k0 k1] smoothing of k_prep_same3_vec, operation for operation -- so the
@@ -1150,7 +1155,7 @@ struct PolyU8 {
     float k0, k1;          // centre and side tap
 };
 template <int N, bool HET, bool U8 = false>
-__global__ __launch_bounds__(512) void k_polyexp_rs(const float* __restrict__ img, float* __restrict__ R, int W, int H,
+__global__ __launch_bounds__(512, N <= 7 ? 8 : 1) void k_polyexp_rs(const float* __restrict__ img, float* __restrict__ R, int W, int H,
                                                      int seg_rows, nsof_poly_taps tp,
                                                      const nsof_het_item* __restrict__ items, PolyU8 u8 = PolyU8{})
 {
@@ -1180,7 +1185,8 @@ __global__ __launch_bounds__(512) void k_polyexp_rs(const float* __restrict__ im
         }
     }
     __shared__ __attribute__((aligned(16))) float sr[2][3][4][256];
-    __shared__ float4 st[4][256];   // per-wave transpose buffer for the interleaved channel-0..3 stores
+    // per-wave transpose buffer for the interleaved channel-0..3 stores, one plane per channel: st[wave][c][pixel]
+    __shared__ __attribute__((aligned(16))) float st[4][4][256];
 
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;   // within the role
     const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
@@ -1298,10 +1304,14 @@ __global__ __launch_bounds__(512) void k_polyexp_rs(const float* __restrict__ im
                         v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w;
                     }
                 };
+                // each output goes out (to the transpose planes, or to memory) as soon as it is final, and moment row 2
+                // is taken before row 1 so that b1 * ig03 dies early: the live set stays one tap row plus the sums
+                auto put = [&](int c, const float (&o)[4]) {   // lane's 4 pixels of channel c: one conflict-free ds_write_b128
+                    *reinterpret_cast<float4*>(&st[wave][c][4 * lane]) = make_float4(o[0], o[1], o[2], o[3]);
+                };
                 double t03[4];  // b1 * ig03, shared by the xx and yy outputs
-                float o0[4], o1[4], o2[4], o3[4], o4[4];
                 {
-                    float v[4 * G::NV];
+                    float v[4 * G::NV], o1[4], o3[4];
                     load_row(0, v);
 #pragma unroll
                     for (int p = 0; p < 4; p++) {
@@ -1319,9 +1329,24 @@ __global__ __launch_bounds__(512) void k_polyexp_rs(const float* __restrict__ im
                         o1[p] = (float)(a2 * tp.ig11);
                         o3[p] = (float)(t03[p] + a4 * tp.ig33);
                     }
+                    put(1, o1);
+                    put(3, o3);
                 }
                 {
-                    float v[4 * G::NV];
+                    float v[4 * G::NV], o2[4];
+                    load_row(2, v);
+#pragma unroll
+                    for (int p = 0; p < 4; p++) {
+                        const int c = G::NP + p;
+                        double a5 = (double)(v[c] * tp.g[0]);
+#pragma unroll
+                        for (int k = 1; k <= N; k++) a5 += (double)((v[c + k] + v[c - k]) * tp.g[k]);
+                        o2[p] = (float)(t03[p] + a5 * tp.ig33);
+                    }
+                    put(2, o2);
+                }
+                {
+                    float v[4 * G::NV], o0[4], o4[4];
                     load_row(1, v);
 #pragma unroll
                     for (int p = 0; p < 4; p++) {
@@ -1336,37 +1361,25 @@ __global__ __launch_bounds__(512) void k_polyexp_rs(const float* __restrict__ im
                         o0[p] = (float)(a3 * tp.ig11);
                         o4[p] = (float)(a6 * tp.ig55);
                     }
-                }
-                {
-                    float v[4 * G::NV];
-                    load_row(2, v);
+                    put(0, o0);
+                    float* c4 = reinterpret_cast<float*>(Rb) + 4u * plane + opix;
+                    if ((W & 3) == 0) {
+                        nsof_store_stream4(c4, o4[0], o4[1], o4[2], o4[3]);
+                    } else {
 #pragma unroll
-                    for (int p = 0; p < 4; p++) {
-                        const int c = G::NP + p;
-                        double a5 = (double)(v[c] * tp.g[0]);
-#pragma unroll
-                        for (int k = 1; k <= N; k++) a5 += (double)((v[c + k] + v[c - k]) * tp.g[k]);
-                        o2[p] = (float)(t03[p] + a5 * tp.ig33);
+                        for (int p = 0; p < 4; p++)
+                            if (xo + p < W) c4[p] = o4[p];
                     }
                 }
-                float* c4 = reinterpret_cast<float*>(Rb) + 4u * plane + opix;
-                if ((W & 3) == 0) {
-                    nsof_store_stream4(c4, o4[0], o4[1], o4[2], o4[3]);
-                } else {
-#pragma unroll
-                    for (int p = 0; p < 4; p++)
-                        if (xo + p < W) c4[p] = o4[p];
-                }
-#pragma unroll
-                for (int p = 0; p < 4; p++) st[wave][4 * lane + (p ^ ((lane >> 1) & 3))] = make_float4(o0[p], o1[p], o2[p], o3[p]);
             }
             {
+                // every lane of the wave takes part (lanes beyond the strip read slots nobody wrote, and do not store)
                 float4* q4 = reinterpret_cast<float4*>(Rb) + (unsigned)yo * (unsigned)W + (unsigned)x0;
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const int px = 64 * k + lane;   // pixel within the strip row
-                    const float4 v = st[wave][(px & ~3) | ((px & 3) ^ ((px >> 3) & 3))];
-                    if (px < G::SW && yo < ye && x0 + px < W) nsof_store_stream4(reinterpret_cast<float*>(q4 + px), v.x, v.y, v.z, v.w);
+                    const float* s = &st[wave][0][px];
+                    if (px < G::SW && yo < ye && x0 + px < W) nsof_store_stream4(reinterpret_cast<float*>(q4 + px), s[0], s[256], s[512], s[768]);
                 }
             }
         }
