@@ -14,8 +14,10 @@
 //  * Scheme 2's refractory rule couples consecutive slices through next_ok, so its scatter
 //    runs one (tiny) launch per slice in stream order; the state update is still fused.
 //  * pow/exp go through double precision so that the float32 result is the correctly
-//    rounded one in all but ~1e-9 of cases (the reference's NumPy uses SIMD pow/exp that are
-//    themselves 1-4 ulp off libm; tolerances are stated in tests/test_accum_*.py).
+//    rounded one: equal to it on every state in [0, 1] outside the ~3e-7 of inputs that lie
+//    within 2^-43 of a rounding midpoint, and on those too as measured (tests/test_accum_cr_gpu.py;
+//    the reference's NumPy uses SIMD pow/exp that are themselves 1-4 ulp off libm, hence the
+//    tolerances against its goldens in tests/test_accum_gpu.py).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -82,9 +84,13 @@ __device__ __forceinline__ double exp_small(double y)   // |y| < 700
 }
 __device__ __forceinline__ float pow_f32(float x, float b)
 {
-    // a state outside [0,1] handed to the element-wise entry point can make x <= 0: NumPy gives nan for a negative
-    // base, 0 or inf for a zero base
-    if (!(x > 0.f)) return x < 0.f ? __builtin_nanf("") : (x == 0.f ? (b > 0.f ? 0.f : __builtin_inff()) : x);
+    // a state outside [0,1] handed to the element-wise entry point can make x <= 0: NumPy gives nan for a finite
+    // negative base, 0 or inf for a zero base, and for the base -inf (w = +inf) inf or 0 like the base +inf (the
+    // exponents are not odd integers)
+    if (!(x > 0.f)) {
+        if (x == 0.f || x == -__builtin_inff()) return b > 0.f ? (x == 0.f ? 0.f : __builtin_inff()) : (x == 0.f ? __builtin_inff() : 0.f);
+        return x < 0.f ? __builtin_nanf("") : x;
+    }
     if (x > 2.f || x < 1e-3f) return (float)exp((double)b * log((double)x));   // far outside the model's range
     return (float)exp_small((double)b * log_unit_range((double)x));
 }

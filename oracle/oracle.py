@@ -67,6 +67,16 @@ def _bind_accum(l):
         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
         C.c_int, C.c_int, C.c_int64, C.c_float, C.c_float,
         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    l.nsof_ref_accum_simulate_cr.restype = C.c_int
+    l.nsof_ref_accum_simulate_cr.argtypes = l.nsof_ref_accum_simulate.argtypes + [C.c_void_p] * 3
+    l.nsof_ref_accum_update_state_cr.restype = None
+    l.nsof_ref_accum_update_state_cr.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
+    l.nsof_ref_accum_pow_cr.restype = None
+    l.nsof_ref_accum_pow_cr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    l.nsof_ref_accum_resistance_cr.restype = None
+    l.nsof_ref_accum_resistance_cr.argtypes = [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]
+    l.nsof_ref_accum_surface.restype = None
+    l.nsof_ref_accum_surface.argtypes = [C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 4
 
 
 def accum_frames(imgs, dt=5e-4, n_sub=1000, th1=0.7, th2=1.5):
@@ -172,15 +182,21 @@ def perf_lib():
     return _perf
 
 
-def accum_slices_per_s(x, y, t, H, W, slice_us=1000, active_v=-6.0, silent_v=0.0, n_slices=20, n_threads=1):
+def accum_slices_per_s(x, y, t, H, W, slice_us=1000, active_v=-6.0, silent_v=0.0, n_slices=20, n_threads=1,
+                       rounding="libm"):
     """CPU rate of the reference's scheme-1 slice (V fill + event scatter + dense update_state over H x W) through the
-    perf build: the first ``n_slices`` slices of the stream, ``n_threads`` OpenMP threads.  Returns (slices/s, w)."""
+    perf build: the first ``n_slices`` slices of the stream, ``n_threads`` OpenMP threads.  Returns (slices/s, w); with
+    rounding="correct" (the correctly rounded update) (slices/s, w, band) with band = steps in the device band."""
+    cr = _rounding(rounding)
     import time
     l = perf_lib()
     l.nsof_ref_set_threads.argtypes = [C.c_int]
     l.nsof_ref_accum_slice_v1.restype = None
     l.nsof_ref_accum_slice_v1.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                           C.c_float, C.c_float]
+    l.nsof_ref_accum_slice_v1_cr.restype = None
+    l.nsof_ref_accum_slice_v1_cr.argtypes = l.nsof_ref_accum_slice_v1.argtypes + [C.c_void_p]
+    counts = np.zeros(2, np.int64)
     x = np.ascontiguousarray(x, np.int16)
     y = np.ascontiguousarray(y, np.int16)
     idx = accum_slice_bounds(np.ascontiguousarray(t, np.int64), slice_us)
@@ -191,10 +207,15 @@ def accum_slices_per_s(x, y, t, H, W, slice_us=1000, active_v=-6.0, silent_v=0.0
     t0 = time.perf_counter()
     for s in range(n_slices):
         lo, hi = int(idx[s]), int(idx[s + 1])
-        l.nsof_ref_accum_slice_v1(w.ctypes.data, V.ctypes.data, w.size, x[lo:].ctypes.data, y[lo:].ctypes.data, hi - lo, W,
-                                  active_v, silent_v)
+        args = [w.ctypes.data, V.ctypes.data, w.size, x[lo:].ctypes.data, y[lo:].ctypes.data, hi - lo, W, active_v, silent_v]
+        if cr:
+            l.nsof_ref_accum_slice_v1_cr(*args, counts.ctypes.data)
+        else:
+            l.nsof_ref_accum_slice_v1(*args)
     dt = time.perf_counter() - t0
     l.nsof_ref_set_threads(1)
+    if cr:
+        return n_slices / dt, w, _counts_ok(counts, "accum_slices_per_s")
     return n_slices / dt, w
 
 
@@ -315,19 +336,93 @@ def poly_prepare(n, sigma):
 
 
 # ---------------------------------------------------------------- accumulator
-def accum_update_state(w, V):
+# rounding="libm" (default): glibc powf / expf, the restatement of the reference that the goldens pin.
+# rounding="correct": every power and exp correctly rounded to float32 (accum_ref.c, "correctly rounded mode"); each entry
+# then also reports the DEVICE BAND -- the inputs whose exact value lies within 2^-43 of a float32 rounding midpoint, the
+# only ones on which the device may return the other neighbour.
+CR_BAND, CR_LONG, CR_UNDECIDED = 1, 2, 4
+_ROUNDINGS = ("libm", "correct")
+
+
+def _rounding(rounding):
+    if rounding not in _ROUNDINGS:
+        raise ValueError(f"rounding must be one of {_ROUNDINGS}, got {rounding!r}")
+    return rounding == "correct"
+
+
+def _counts_ok(counts, what):
+    if counts[1]:
+        raise RuntimeError(f"oracle {what}: {int(counts[1])} results within 2^-60 of a float32 midpoint even in long double")
+    return int(counts[0])
+
+
+def accum_update_state(w, V, rounding="libm"):
+    """update_state(w, V) in float32.  rounding="correct": returns (out, band) with band a bool mask of the elements in
+    the device band."""
     w = np.ascontiguousarray(w, np.float32)
     V = np.ascontiguousarray(V, np.float32)
     out = np.empty_like(w)
-    lib().nsof_ref_accum_update_state(w.ctypes.data, V.ctypes.data, out.ctypes.data, w.size)
-    return out
+    if not _rounding(rounding):
+        lib().nsof_ref_accum_update_state(w.ctypes.data, V.ctypes.data, out.ctypes.data, w.size)
+        return out
+    flags = np.empty(w.shape, np.uint8)
+    counts = np.zeros(2, np.int64)
+    lib().nsof_ref_accum_update_state_cr(w.ctypes.data, V.ctypes.data, out.ctypes.data, flags.ctypes.data, w.size,
+                                         counts.ctypes.data)
+    _counts_ok(counts, "update_state")
+    return out, (flags & CR_BAND) != 0
 
 
-def accum_resistance(w):
+def accum_pow(w, branch):
+    """The correctly rounded power term of update_state: branch 0 (V < voff) (1 - w*soff)^boff, branch 1 (V > von)
+    (1 - w*son)^bon, bases formed in float32.  Returns (power float32, flags uint8: CR_BAND | CR_LONG | CR_UNDECIDED).
+    Safe to call from several threads at once (ctypes releases the GIL)."""
     w = np.ascontiguousarray(w, np.float32)
     out = np.empty_like(w)
-    lib().nsof_ref_accum_resistance(w.ctypes.data, out.ctypes.data, w.size)
-    return out
+    flags = np.empty(w.shape, np.uint8)
+    counts = np.zeros(2, np.int64)
+    lib().nsof_ref_accum_pow_cr(w.ctypes.data, int(branch), out.ctypes.data, flags.ctypes.data, w.size,
+                                counts.ctypes.data)
+    _counts_ok(counts, "pow")
+    return out, flags
+
+
+def accum_resistance(w, rounding="libm"):
+    """resistance_exp(w) as float32.  rounding="correct": returns (out, band), the exp correctly rounded."""
+    w = np.ascontiguousarray(w, np.float32)
+    out = np.empty_like(w)
+    if not _rounding(rounding):
+        lib().nsof_ref_accum_resistance(w.ctypes.data, out.ctypes.data, w.size)
+        return out
+    flags = np.empty(w.shape, np.uint8)
+    counts = np.zeros(2, np.int64)
+    lib().nsof_ref_accum_resistance_cr(w.ctypes.data, out.ctypes.data, flags.ctypes.data, w.size, counts.ctypes.data)
+    _counts_ok(counts, "resistance")
+    return out, (flags & CR_BAND) != 0
+
+
+def _accum_surface(w, mode, f32):
+    w = np.ascontiguousarray(w, np.float32)
+    out = np.empty(w.shape, np.float32 if f32 else np.uint8)
+    flags = np.empty(w.shape, np.uint8)
+    counts = np.zeros(2, np.int64)
+    m = {"current": 0, "state": 1}[mode]
+    lib().nsof_ref_accum_surface(w.ctypes.data, w.size, m, None if f32 else out.ctypes.data,
+                                 out.ctypes.data if f32 else None, flags.ctypes.data, counts.ctypes.data)
+    _counts_ok(counts, "surface")
+    return out, (flags & CR_BAND) != 0
+
+
+def accum_surface_u8(w, mode):
+    """The device's 8-bit surface of states w (Accumulator.surface_u8): "current" = uint8(clip(-3366/log10(1/R) - 306))
+    on the correctly rounded R, g in long double; "state" = uint8(w * 255f).  Returns (u8, band): band marks the pixels
+    whose g lies within 1e-10 of an integer (or whose R is in the device band)."""
+    return _accum_surface(w, mode, False)
+
+
+def accum_surface_f32(w, mode):
+    """Accumulator.surface_f32: the same g clipped and rounded to float32.  Returns (f32, band)."""
+    return _accum_surface(w, mode, True)
 
 
 def accum_slice_bounds(t, slice_us):
@@ -338,8 +433,11 @@ def accum_slice_bounds(t, slice_us):
     return idx
 
 
-def accum_simulate(x, y, p, t, H, W, version, polarity, slice_us, active_v, silent_v):
-    """polarity: 'split' | 'magnitude'.  Returns dict(w_final, resistances[, w_final_b, resistances_b])."""
+def accum_simulate(x, y, p, t, H, W, version, polarity, slice_us, active_v, silent_v, rounding="libm"):
+    """polarity: 'split' | 'magnitude'.  Returns dict(w_final, resistances[, w_final_b, resistances_b]); with
+    rounding="correct" also band = the number of the run's steps and snapshot values in the device band, and band_px
+    [, band_px_b] = bool [H][W], the pixels whose trajectory had any of them (elsewhere the device must agree exactly)."""
+    cr = _rounding(rounding)
     x = np.ascontiguousarray(x, np.int16)
     y = np.ascontiguousarray(y, np.int16)
     p = np.ascontiguousarray(p, np.int8)
@@ -353,14 +451,25 @@ def accum_simulate(x, y, p, t, H, W, version, polarity, slice_us, active_v, sile
     ra = np.empty((nsnap, H, W), np.float32)
     wb = np.empty((H, W), np.float32) if split else None
     rb = np.empty((nsnap, H, W), np.float32) if split else None
-    rc = lib().nsof_ref_accum_simulate(
-        x.ctypes.data, y.ctypes.data, p.ctypes.data, t.ctypes.data, t.size, H, W, version, split, slice_us,
-        active_v, silent_v, wa.ctypes.data, ra.ctypes.data, wb.ctypes.data if split else None,
-        rb.ctypes.data if split else None, nsnap)
+    args = [x.ctypes.data, y.ctypes.data, p.ctypes.data, t.ctypes.data, t.size, H, W, version, split, slice_us,
+            active_v, silent_v, wa.ctypes.data, ra.ctypes.data, wb.ctypes.data if split else None,
+            rb.ctypes.data if split else None, nsnap]
+    counts = np.zeros(2, np.int64)
+    ba = np.zeros((H, W), np.uint8)
+    bb = np.zeros((H, W), np.uint8)
+    if cr:
+        rc = lib().nsof_ref_accum_simulate_cr(*args, counts.ctypes.data, ba.ctypes.data, bb.ctypes.data)
+    else:
+        rc = lib().nsof_ref_accum_simulate(*args)
     _chk(rc, "accum_simulate")
     out = dict(w_final=wa, resistances=ra)
     if split:
         out.update(w_final_b=wb, resistances_b=rb)
+    if cr:
+        out["band"] = _counts_ok(counts, "accum_simulate")
+        out["band_px"] = ba != 0
+        if split:
+            out["band_px_b"] = bb != 0
     return out
 
 
