@@ -765,26 +765,22 @@ struct nsof_accum {
     float active_v = 0, silent_v = 0;
     int force_dense = 0;   // nsof_accum_set_dense: 0 automatic, 1 every-pixel pass, -1 event-pixel update (where exact)
     size_t npx = 0;
-    float* w[2] = {nullptr, nullptr};
-    long long* next_ok[2] = {nullptr, nullptr};
-    unsigned* mask[2] = {nullptr, nullptr};
-    unsigned* mask_hi = nullptr;   // slices 32..63 of a dense scheme-1 group (allocated on first use, kept zero between groups)
-    unsigned long long* mask64 = nullptr;   // nsof_accum_run_frames (copy + patch): one 64-bit slice mask per pixel
-    // nsof_accum_run_frames (tile walk): bucket counters / offsets [intervals * tiles (+1)] and the 16-bit event records
-    unsigned* tile_cnt = nullptr;
-    unsigned* tile_off = nullptr;
-    unsigned short* tile_recs = nullptr;
-    size_t tile_nb_cap = 0, tile_rec_cap = 0;
-    unsigned* list[2] = {nullptr, nullptr};
-    size_t list_cap = 0;
-    unsigned* count = nullptr;  // [2]
+    nsof_dev_buf<float> w[2];
+    nsof_dev_buf<long long> next_ok[2];
+    nsof_dev_buf<unsigned> mask[2];
+    nsof_dev_buf<unsigned> mask_hi;   // slices 32..63 of a dense scheme-1 group (allocated on first use, kept zero between groups)
+    nsof_dev_buf<unsigned long long> mask64;   // nsof_accum_run_frames (copy + patch): one 64-bit slice mask per pixel
+    // nsof_accum_run_frames (tile walk): bucket offsets [intervals * tiles + 1] and the 16-bit event records
+    nsof_dev_buf<unsigned> tile_off;
+    nsof_dev_buf<unsigned short> tile_recs;
+    nsof_dev_buf<unsigned> list[2];
+    nsof_dev_buf<unsigned> count;  // [2]
     // event staging
-    short *dx = nullptr, *dy = nullptr;
-    signed char* dp = nullptr;
-    long long* dbounds = nullptr;
-    size_t ev_cap = 0, bounds_cap = 0;
+    nsof_dev_buf<short> dx, dy;
+    nsof_dev_buf<signed char> dp;
+    nsof_dev_buf<long long> dbounds;
     // snapshots
-    float* snap[2] = {nullptr, nullptr};
+    nsof_dev_buf<float> snap[2];
     int64_t snap_cap = 0, snap_count = 0;
     int64_t slice_counter = 0;
     // staged stream (nsof_accum_set_events / the staging half of nsof_accum_step_events): slice bounds relative to
@@ -793,25 +789,11 @@ struct nsof_accum {
     int frames_path = 0;     // nsof_accum_run_frames: 0 = the tile walk where it applies, 1 = copy + patch per interval (kept as the cross-check)
 };
 
-static int accum_alloc(nsof_ctx* ctx, void** p, size_t bytes)
-{
-    hipError_t e = hipMalloc(p, bytes ? bytes : 1);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return nsof_set_error(ctx, NSOF_ENOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    }
-    return NSOF_OK;
-}
-
 extern "C" void nsof_accum_destroy(nsof_accum* a)
 {
     if (!a) return;
     hipSetDevice(a->ctx->device);
     hipStreamSynchronize(a->ctx->stream);
-    for (int i = 0; i < 2; i++) {
-        hipFree(a->w[i]); hipFree(a->next_ok[i]); hipFree(a->mask[i]); hipFree(a->list[i]); hipFree(a->snap[i]);
-    }
-    hipFree(a->mask_hi); hipFree(a->mask64); hipFree(a->tile_cnt); hipFree(a->tile_off); hipFree(a->tile_recs); hipFree(a->count); hipFree(a->dx); hipFree(a->dy); hipFree(a->dp); hipFree(a->dbounds);
     delete a;
 }
 
@@ -822,9 +804,9 @@ extern "C" int nsof_accum_reset(nsof_accum* a)
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const int narr = a->split ? 2 : 1;
     for (int i = 0; i < narr; i++) {
-        hipLaunchKernelGGL(k_fill, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[i], a->npx, WINI);
-        NSOF_HIP(ctx, hipMemsetAsync(a->mask[i], 0, a->npx * sizeof(unsigned), ctx->stream));
-        if (a->scheme == 2) NSOF_HIP(ctx, hipMemsetAsync(a->next_ok[i], 0, a->npx * sizeof(long long), ctx->stream));
+        hipLaunchKernelGGL(k_fill, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[i].p, a->npx, WINI);
+        NSOF_HIP(ctx, hipMemsetAsync(a->mask[i].p, 0, a->npx * sizeof(unsigned), ctx->stream));
+        if (a->scheme == 2) NSOF_HIP(ctx, hipMemsetAsync(a->next_ok[i].p, 0, a->npx * sizeof(long long), ctx->stream));
     }
     NSOF_HIP(ctx, hipGetLastError());
     a->slice_counter = 0;
@@ -848,11 +830,11 @@ extern "C" int nsof_accum_create(nsof_ctx* ctx, int height, int width, int schem
     a->active_v = active_v; a->silent_v = silent_v;
     a->npx = (size_t)height * width;
     const int narr = a->split ? 2 : 1;
-    int rc = accum_alloc(ctx, (void**)&a->count, 4 * sizeof(unsigned));   // [parity][array]: groups alternate, see accum_advance
+    int rc = a->count.reserve(ctx, 4 * sizeof(unsigned));   // [parity][array]: groups alternate, see accum_advance
     for (int i = 0; i < narr && !rc; i++) {
-        rc = accum_alloc(ctx, (void**)&a->w[i], (a->npx + 4) * sizeof(float));
-        if (!rc) rc = accum_alloc(ctx, (void**)&a->mask[i], (a->npx + 4) * sizeof(unsigned));
-        if (!rc && scheme == 2) rc = accum_alloc(ctx, (void**)&a->next_ok[i], a->npx * sizeof(long long));
+        rc = a->w[i].reserve(ctx, (a->npx + 4) * sizeof(float));
+        if (!rc) rc = a->mask[i].reserve(ctx, (a->npx + 4) * sizeof(unsigned));
+        if (!rc && scheme == 2) rc = a->next_ok[i].reserve(ctx, a->npx * sizeof(long long));
     }
     if (!rc) rc = nsof_accum_reset(a);
     if (rc) { nsof_accum_destroy(a); return rc; }
@@ -881,22 +863,20 @@ static int accum_snapshot(nsof_accum* a)
     if (a->snap_count == a->snap_cap) {
         const int64_t ncap = a->snap_cap ? a->snap_cap * 2 : 16;
         for (int i = 0; i < narr; i++) {
-            float* nb = nullptr;
-            int rc = accum_alloc(ctx, (void**)&nb, (size_t)ncap * a->npx * sizeof(float));
-            if (rc) return rc;
+            nsof_dev_buf<float> nb;
+            if (int rc = nb.reserve(ctx, (size_t)ncap * a->npx * sizeof(float))) return rc;
             if (a->snap_count)
-                NSOF_HIP(ctx, hipMemcpyAsync(nb, a->snap[i], (size_t)a->snap_count * a->npx * sizeof(float),
+                NSOF_HIP(ctx, hipMemcpyAsync(nb.p, a->snap[i].p, (size_t)a->snap_count * a->npx * sizeof(float),
                                              hipMemcpyDeviceToDevice, ctx->stream));
             NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            hipFree(a->snap[i]);
-            a->snap[i] = nb;
+            a->snap[i].swap(nb);   // the old array goes with nb
         }
         a->snap_cap = ncap;
     }
     const float neg_lam = (float)(-std::log(ROFF / RON));
     for (int i = 0; i < narr; i++)
-        hipLaunchKernelGGL(k_resistance, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[i],
-                           a->snap[i] + (size_t)a->snap_count * a->npx, a->npx, neg_lam);
+        hipLaunchKernelGGL(k_resistance, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[i].p,
+                           a->snap[i].p + (size_t)a->snap_count * a->npx, a->npx, neg_lam);
     NSOF_HIP(ctx, hipGetLastError());
     a->snap_count++;
     return NSOF_OK;
@@ -924,29 +904,17 @@ static int accum_stage(nsof_accum* a, const int16_t* x, const int16_t* y, const 
                                   (int)x[e], (int)y[e], a->W, a->H);
     const int narr = a->split ? 2 : 1;
     int rc;
-    if ((size_t)n_ev > a->ev_cap) {
-        NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        hipFree(a->dx); hipFree(a->dy); hipFree(a->dp);
-        for (int i = 0; i < 2; i++) { hipFree(a->list[i]); a->list[i] = nullptr; }
-        a->dx = a->dy = nullptr; a->dp = nullptr;
-        const size_t cap = (size_t)n_ev + (size_t)n_ev / 4 + 1024;
-        if ((rc = accum_alloc(ctx, (void**)&a->dx, cap * 2)) || (rc = accum_alloc(ctx, (void**)&a->dy, cap * 2)) ||
-            (rc = accum_alloc(ctx, (void**)&a->dp, cap)))
-            return rc;
-        for (int i = 0; i < narr; i++)
-            if ((rc = accum_alloc(ctx, (void**)&a->list[i], cap * sizeof(unsigned)))) return rc;
-        a->ev_cap = cap;
-    }
-    if ((size_t)(n_slices + 1) > a->bounds_cap) {
-        NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        hipFree(a->dbounds);
-        if ((rc = accum_alloc(ctx, (void**)&a->dbounds, (size_t)(n_slices + 1) * 8))) return rc;
-        a->bounds_cap = (size_t)(n_slices + 1);
-    }
+    const size_t cap = (size_t)n_ev + (size_t)n_ev / 4 + 1024;   // events
+    if ((rc = a->dx.reserve(ctx, (size_t)n_ev * 2, cap * 2)) || (rc = a->dy.reserve(ctx, (size_t)n_ev * 2, cap * 2)) ||
+        (rc = a->dp.reserve(ctx, (size_t)n_ev, cap)))
+        return rc;
+    for (int i = 0; i < narr; i++)
+        if ((rc = a->list[i].reserve(ctx, (size_t)n_ev * sizeof(unsigned), cap * sizeof(unsigned)))) return rc;
+    if ((rc = a->dbounds.reserve(ctx, (size_t)(n_slices + 1) * 8))) return rc;
     if (n_ev > 0) {
-        NSOF_HIP(ctx, hipMemcpyAsync(a->dx, x + e0, (size_t)n_ev * 2, hipMemcpyHostToDevice, ctx->stream));
-        NSOF_HIP(ctx, hipMemcpyAsync(a->dy, y + e0, (size_t)n_ev * 2, hipMemcpyHostToDevice, ctx->stream));
-        if (p) NSOF_HIP(ctx, hipMemcpyAsync(a->dp, p + e0, (size_t)n_ev, hipMemcpyHostToDevice, ctx->stream));
+        NSOF_HIP(ctx, hipMemcpyAsync(a->dx.p, x + e0, (size_t)n_ev * 2, hipMemcpyHostToDevice, ctx->stream));
+        NSOF_HIP(ctx, hipMemcpyAsync(a->dy.p, y + e0, (size_t)n_ev * 2, hipMemcpyHostToDevice, ctx->stream));
+        if (p) NSOF_HIP(ctx, hipMemcpyAsync(a->dp.p, p + e0, (size_t)n_ev, hipMemcpyHostToDevice, ctx->stream));
     }
     a->h_rel.resize((size_t)n_slices + 1);
     for (int64_t s = 0; s <= n_slices; s++) a->h_rel[s] = (long long)(sb[s] - e0);
@@ -958,7 +926,7 @@ static int accum_stage(nsof_accum* a, const int16_t* x, const int16_t* y, const 
                 a->h_tfirst[s] = t[sb[s]];
                 a->h_tnext[s] = t[sb[s + 1] - 1] + REFRACTORY_US;
             }
-    NSOF_HIP(ctx, hipMemcpyAsync(a->dbounds, a->h_rel.data(), a->h_rel.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    NSOF_HIP(ctx, hipMemcpyAsync(a->dbounds.p, a->h_rel.data(), a->h_rel.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's arrays are not retained
     return NSOF_OK;
 }
@@ -986,7 +954,7 @@ static int accum_surface(nsof_accum* a, int which, const SurfOut& so)
 {
     nsof_ctx* ctx = a->ctx;
     dim3 grid((a->W + 255) / 256, a->H);
-    hipLaunchKernelGGL(k_surface_gray, grid, dim3(256), 0, ctx->stream, a->w[which], so.out, a->W, a->H, (ptrdiff_t)so.stride,
+    hipLaunchKernelGGL(k_surface_gray, grid, dim3(256), 0, ctx->stream, a->w[which].p, so.out, a->W, a->H, (ptrdiff_t)so.stride,
                        so.neg_lam, so.mode);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
@@ -1021,15 +989,15 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
     // the dense scheme-1 update takes groups of up to 64 slices (two mask words per pixel): a 33-slice frame interval is one
     // pass over the array instead of two
     const bool wide = a->scheme == 1 && !sparse;
-    if (wide && !a->mask_hi) {
-        if ((rc = accum_alloc(ctx, (void**)&a->mask_hi, a->npx * sizeof(unsigned) + 16))) return rc;
-        NSOF_HIP(ctx, hipMemsetAsync(a->mask_hi, 0, a->npx * sizeof(unsigned) + 16, ctx->stream));
+    if (wide && !a->mask_hi.p) {
+        if ((rc = a->mask_hi.reserve(ctx, a->npx * sizeof(unsigned) + 16))) return rc;
+        NSOF_HIP(ctx, hipMemsetAsync(a->mask_hi.p, 0, a->npx * sizeof(unsigned) + 16, ctx->stream));
     }
     const int64_t max_group = wide ? 2 * MAX_GROUP : MAX_GROUP;
     // List counters of the event-pixel update: two sets used alternately.  A group's update kernels zero the OTHER set -- the
     // one the next group's scatter appends to -- so the per-group 8-byte memset (a launch of its own) is gone: one per call.
     int par = 0;
-    if (sparse && s0 < s_end) NSOF_HIP(ctx, hipMemsetAsync(a->count, 0, 4 * sizeof(unsigned), ctx->stream));
+    if (sparse && s0 < s_end) NSOF_HIP(ctx, hipMemsetAsync(a->count.p, 0, 4 * sizeof(unsigned), ctx->stream));
     while (s0 < s_end) {
         // group = up to max_group slices, ending right after the next snapshot slice
         int64_t g = s_end - s0 < max_group ? s_end - s0 : max_group;
@@ -1039,20 +1007,20 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
             if (to_snap < g) g = to_snap;
         }
         const long long ge0 = rel[s0], ge1 = rel[s0 + g], gn = ge1 - ge0;
-        unsigned* const cnt = a->count + 2 * par;          // this group's counters; (the dense update has no list)
-        unsigned* const cnt_next = a->count + 2 * (par ^ 1);
+        unsigned* const cnt = a->count.p + 2 * par;          // this group's counters; (the dense update has no list)
+        unsigned* const cnt_next = a->count.p + 2 * (par ^ 1);
         if (sparse && gn == 0) NSOF_HIP(ctx, hipMemsetAsync(cnt_next, 0, 2 * sizeof(unsigned), ctx->stream));   // no update kernel will
-        unsigned* const l0 = sparse ? a->list[0] : nullptr;                      // the dense update reads no list
-        unsigned* const l1 = sparse ? a->list[a->split ? 1 : 0] : nullptr;
+        unsigned* const l0 = sparse ? a->list[0].p : nullptr;                      // the dense update reads no list
+        unsigned* const l1 = sparse ? a->list[a->split ? 1 : 0].p : nullptr;
         if (gn > 0) {
             nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
             if (a->scheme == 1) {
-                hipLaunchKernelGGL(k_scatter_v1, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream, a->dx,
-                                   a->dy, ge0, gn, a->dbounds + s0, (int)g, a->W, a->mask[0], l0, cnt, a->mask_hi);
+                hipLaunchKernelGGL(k_scatter_v1, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream, a->dx.p,
+                                   a->dy.p, ge0, gn, a->dbounds.p + s0, (int)g, a->W, a->mask[0].p, l0, cnt, a->mask_hi.p);
             } else {
-                hipLaunchKernelGGL(k_scatter_v2g, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream, a->dx, a->dy,
-                                   a->dp, ge0, gn, a->dbounds + s0, (int)g, a->W, a->split ? 1 : 0, a->mask[0], l0,
-                                   cnt, a->mask[a->split ? 1 : 0], l1, cnt + 1);
+                hipLaunchKernelGGL(k_scatter_v2g, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream, a->dx.p, a->dy.p,
+                                   a->dp.p, ge0, gn, a->dbounds.p + s0, (int)g, a->W, a->split ? 1 : 0, a->mask[0].p, l0,
+                                   cnt, a->mask[a->split ? 1 : 0].p, l1, cnt + 1);
             }
             NSOF_HIP(ctx, hipGetLastError());
         }
@@ -1072,18 +1040,18 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
                     if (sparse) {
                         if (gn > 0)
                             hipLaunchKernelGGL(k_update_sparse_v2, dim3(grid_for((size_t)gn, 1024)), dim3(256), 0, ctx->stream,
-                                               a->w[i], a->mask[i], a->next_ok[i], a->list[i], cnt + i, tab, v_act, cnt_next + i);
+                                               a->w[i].p, a->mask[i].p, a->next_ok[i].p, a->list[i].p, cnt + i, tab, v_act, cnt_next + i);
                     } else if (dead_zone) {
-                        hipLaunchKernelGGL(k_update_dense_v2<true>, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream, a->w[i],
-                                           a->mask[i], a->next_ok[i], n4, a->npx, (int)g, tab, v_act, a->silent_v);
+                        hipLaunchKernelGGL(k_update_dense_v2<true>, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream, a->w[i].p,
+                                           a->mask[i].p, a->next_ok[i].p, n4, a->npx, (int)g, tab, v_act, a->silent_v);
                     } else {
-                        hipLaunchKernelGGL(k_update_dense_v2<false>, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream, a->w[i],
-                                           a->mask[i], a->next_ok[i], n4, a->npx, (int)g, tab, v_act, a->silent_v);
+                        hipLaunchKernelGGL(k_update_dense_v2<false>, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream, a->w[i].p,
+                                           a->mask[i].p, a->next_ok[i].p, n4, a->npx, (int)g, tab, v_act, a->silent_v);
                     }
                 } else if (sparse) {
                     if (gn > 0)
                         hipLaunchKernelGGL(k_update_sparse, dim3(grid_for((size_t)gn, 1024)), dim3(256), 0, ctx->stream,
-                                           a->w[i], a->mask[i], a->list[i], cnt + i, (int)g, v_act, cnt_next + i);
+                                           a->w[i].p, a->mask[i].p, a->list[i].p, cnt + i, (int)g, v_act, cnt_next + i);
                 } else {
                     const size_t n4 = (a->npx + 3) / 4;
                     SurfOut so{nullptr, 0, a->W, 0.f, 0};
@@ -1093,12 +1061,12 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
                     }
                     if (dead_zone)
                         hipLaunchKernelGGL(k_update_dense<true>, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream,
-                                           a->w[i], a->mask[i], n4, a->npx, (int)g, v_act, a->silent_v, so,
-                                           g > MAX_GROUP ? a->mask_hi : nullptr);
+                                           a->w[i].p, a->mask[i].p, n4, a->npx, (int)g, v_act, a->silent_v, so,
+                                           g > MAX_GROUP ? a->mask_hi.p : nullptr);
                     else
                         hipLaunchKernelGGL(k_update_dense<false>, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream,
-                                           a->w[i], a->mask[i], n4, a->npx, (int)g, v_act, a->silent_v, so,
-                                           g > MAX_GROUP ? a->mask_hi : nullptr);
+                                           a->w[i].p, a->mask[i].p, n4, a->npx, (int)g, v_act, a->silent_v, so,
+                                           g > MAX_GROUP ? a->mask_hi.p : nullptr);
                 }
             }
             NSOF_HIP(ctx, hipGetLastError());
@@ -1149,7 +1117,7 @@ extern "C" int nsof_accum_surface_f32_dev(nsof_accum* a, int which, int mode, fl
     nsof_ctx* ctx = a->ctx;
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid((a->W + 255) / 256, a->H);
-    hipLaunchKernelGGL(k_surface_gray_f32, grid, dim3(256), 0, ctx->stream, a->w[which], d_out, a->W, a->H, row_stride_bytes,
+    hipLaunchKernelGGL(k_surface_gray_f32, grid, dim3(256), 0, ctx->stream, a->w[which].p, d_out, a->W, a->H, row_stride_bytes,
                        (float)(-std::log(ROFF / RON)), mode);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
@@ -1198,59 +1166,44 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
     if (tile_ok) {
         const unsigned ntiles = (unsigned)((a->npx + TILE_PX - 1) / TILE_PX);
         const size_t nb = (size_t)n_frames * ntiles;
-        if (nb + 1 > a->tile_nb_cap) {
-            NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            hipFree(a->tile_cnt); hipFree(a->tile_off);
-            a->tile_cnt = a->tile_off = nullptr;
-            a->tile_nb_cap = 0;
-            const size_t cap = nb + nb / 4 + 1024;
-            if ((rc = accum_alloc(ctx, (void**)&a->tile_off, cap * 4))) return rc;
-            a->tile_nb_cap = cap;
-        }
-        if ((size_t)n_ev > a->tile_rec_cap) {
-            NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            hipFree(a->tile_recs);
-            a->tile_recs = nullptr;
-            a->tile_rec_cap = 0;
-            const size_t cap = (size_t)n_ev + (size_t)n_ev / 4 + 1024;
-            if ((rc = accum_alloc(ctx, (void**)&a->tile_recs, cap * 2))) return rc;
-            a->tile_rec_cap = cap;
-        }
+        if ((rc = a->tile_off.reserve(ctx, (nb + 1) * 4, (nb + nb / 4 + 1024) * 4)) ||
+            (rc = a->tile_recs.reserve(ctx, (size_t)n_ev * 2, ((size_t)n_ev + (size_t)n_ev / 4 + 1024) * 2)))
+            return rc;
         nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
-        hipLaunchKernelGGL(k_tile_bucket, dim3((unsigned)n_frames), dim3(1024), (size_t)ntiles * 4, ctx->stream, a->dx, a->dy, ev0,
-                           a->dbounds + first_slice, (int)every, a->W, ntiles, a->tile_off, a->tile_recs, (int)n_frames);
-        hipLaunchKernelGGL(k_tile_frames, dim3((ntiles + 3) / 4), dim3(256), 0, ctx->stream, a->w[0], a->npx, a->W,
-                           (const unsigned*)a->tile_off, (const unsigned short*)a->tile_recs, ntiles, (int)n_frames, a->active_v, d_frames,
+        hipLaunchKernelGGL(k_tile_bucket, dim3((unsigned)n_frames), dim3(1024), (size_t)ntiles * 4, ctx->stream, a->dx.p, a->dy.p, ev0,
+                           a->dbounds.p + first_slice, (int)every, a->W, ntiles, a->tile_off.p, a->tile_recs.p, (int)n_frames);
+        hipLaunchKernelGGL(k_tile_frames, dim3((ntiles + 3) / 4), dim3(256), 0, ctx->stream, a->w[0].p, a->npx, a->W,
+                           (const unsigned*)a->tile_off.p, (const unsigned short*)a->tile_recs.p, ntiles, (int)n_frames, a->active_v, d_frames,
                            (long long)row_stride, (long long)frame_stride, neg_lam, mode);
         NSOF_HIP(ctx, hipGetLastError());
         a->slice_counter += n_frames * every;
         return NSOF_OK;
     }
-    if (!a->mask64) {   // per-pixel 64-bit slice masks of this path (kept zero between intervals)
-        if ((rc = accum_alloc(ctx, (void**)&a->mask64, a->npx * sizeof(unsigned long long)))) return rc;
-        NSOF_HIP(ctx, hipMemsetAsync(a->mask64, 0, a->npx * sizeof(unsigned long long), ctx->stream));
+    if (!a->mask64.p) {   // per-pixel 64-bit slice masks of this path (kept zero between intervals)
+        if ((rc = a->mask64.reserve(ctx, a->npx * sizeof(unsigned long long)))) return rc;
+        NSOF_HIP(ctx, hipMemsetAsync(a->mask64.p, 0, a->npx * sizeof(unsigned long long), ctx->stream));
     }
     const std::vector<long long>& rel = a->h_rel;
-    NSOF_HIP(ctx, hipMemsetAsync(a->count, 0, 4 * sizeof(unsigned), ctx->stream));
+    NSOF_HIP(ctx, hipMemsetAsync(a->count.p, 0, 4 * sizeof(unsigned), ctx->stream));
     int par = 0;
     constexpr size_t ACC_COPY_BLOCKS = 4096;
     const unsigned copy_blocks = (unsigned)std::min<size_t>(ACC_COPY_BLOCKS, (a->npx / 16 + 255) / 256 + 1);
     for (int64_t k = 0; k < n_frames; k++) {
         const int64_t s0 = first_slice + k * every;
         const long long ge0 = rel[s0], gn = rel[s0 + every] - ge0;
-        unsigned* const cnt = a->count + 2 * par;
-        unsigned* const cnt_next = a->count + 2 * (par ^ 1);
+        unsigned* const cnt = a->count.p + 2 * par;
+        unsigned* const cnt_next = a->count.p + 2 * (par ^ 1);
         uint8_t* const cur = d_frames + k * frame_stride;
         const uint8_t* const prev = k > 0 ? d_frames + (k - 1) * frame_stride : nullptr;
         nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
         if (prev || gn > 0) {
             const unsigned blocks = prev ? copy_blocks : (unsigned)((gn + 255) / 256);
             hipLaunchKernelGGL(k_frames_scatter_copy, dim3(blocks), dim3(256), 0, ctx->stream, prev, cur, a->W, a->H,
-                               (long long)row_stride, a->dx, a->dy, ge0, gn, a->dbounds + s0, (int)every, a->mask64, a->list[0], cnt);
+                               (long long)row_stride, a->dx.p, a->dy.p, ge0, gn, a->dbounds.p + s0, (int)every, a->mask64.p, a->list[0].p, cnt);
         }
         // (launched for an empty interval as well: it zeroes the next interval's counter)
         hipLaunchKernelGGL(k_frames_update_patch, dim3(grid_for((size_t)std::max<long long>(gn, 1), 1024)), dim3(256), 0, ctx->stream,
-                           a->w[0], a->mask64, a->list[0], cnt, a->active_v, cnt_next, cur, a->W,
+                           a->w[0].p, a->mask64.p, a->list[0].p, cnt, a->active_v, cnt_next, cur, a->W,
                            (long long)row_stride, neg_lam, mode);
         NSOF_HIP(ctx, hipGetLastError());
         if (k == 0) {   // the call's first frame has no predecessor to copy: one pass over the array
@@ -1270,10 +1223,10 @@ extern "C" int nsof_accum_read_state(nsof_accum* a, int which, float* w_out, int
     if (!a || which < 0 || which > (a->split ? 1 : 0)) return NSOF_EINVAL;
     nsof_ctx* ctx = a->ctx;
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    if (w_out) NSOF_HIP(ctx, hipMemcpyAsync(w_out, a->w[which], a->npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (w_out) NSOF_HIP(ctx, hipMemcpyAsync(w_out, a->w[which].p, a->npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (next_ok_out) {
-        if (a->next_ok[which])
-            NSOF_HIP(ctx, hipMemcpyAsync(next_ok_out, a->next_ok[which], a->npx * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (a->next_ok[which].p)
+            NSOF_HIP(ctx, hipMemcpyAsync(next_ok_out, a->next_ok[which].p, a->npx * 8, hipMemcpyDeviceToHost, ctx->stream));
         else
             memset(next_ok_out, 0, a->npx * 8);
     }
@@ -1289,9 +1242,9 @@ extern "C" int nsof_accum_write_state(nsof_accum* a, int which, const float* w_i
     nsof_ctx* ctx = a->ctx;
     if (slice_counter < 0) return nsof_set_error(ctx, NSOF_EINVAL, "negative slice counter");
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    if (w_in) NSOF_HIP(ctx, hipMemcpyAsync(a->w[which], w_in, a->npx * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if (next_ok_in && a->next_ok[which])
-        NSOF_HIP(ctx, hipMemcpyAsync(a->next_ok[which], next_ok_in, a->npx * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (w_in) NSOF_HIP(ctx, hipMemcpyAsync(a->w[which].p, w_in, a->npx * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (next_ok_in && a->next_ok[which].p)
+        NSOF_HIP(ctx, hipMemcpyAsync(a->next_ok[which].p, next_ok_in, a->npx * 8, hipMemcpyHostToDevice, ctx->stream));
     NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     a->slice_counter = slice_counter;
     return NSOF_OK;
@@ -1321,11 +1274,11 @@ extern "C" int nsof_accum_bincount_2d(nsof_ctx* ctx, const int16_t* x, const int
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const size_t npx = (size_t)height * width;
     const size_t szE = (n * 2 + 255) & ~(size_t)255, szC = (npx * 4 + 255) & ~(size_t)255;
-    int rc = nsof_ws_reserve(ctx, &ctx->stage, &ctx->stage_bytes, 2 * szE + szC);
+    int rc = ctx->stage.reserve(ctx, 2 * szE + szC);
     if (rc) return rc;
-    short* dx = (short*)ctx->stage;
-    short* dy = (short*)((char*)ctx->stage + szE);
-    int* dc = (int*)((char*)ctx->stage + 2 * szE);
+    short* dx = (short*)ctx->stage.p;
+    short* dy = (short*)((char*)ctx->stage.p + szE);
+    int* dc = (int*)((char*)ctx->stage.p + 2 * szE);
     NSOF_HIP(ctx, hipMemsetAsync(dc, 0, npx * 4, ctx->stream));
     if (n) {
         NSOF_HIP(ctx, hipMemcpyAsync(dx, x, n * 2, hipMemcpyHostToDevice, ctx->stream));
@@ -1353,7 +1306,7 @@ extern "C" int nsof_accum_read_w(nsof_accum* a, int which, float* out)
 {
     if (!a || !out || which < 0 || which > (a->split ? 1 : 0)) return NSOF_EINVAL;
     nsof_ctx* ctx = a->ctx;
-    NSOF_HIP(ctx, hipMemcpyAsync(out, a->w[which], a->npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NSOF_HIP(ctx, hipMemcpyAsync(out, a->w[which].p, a->npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NSOF_OK;
 }
@@ -1362,16 +1315,15 @@ extern "C" int nsof_accum_read_resistance(nsof_accum* a, int which, float* out)
 {
     if (!a || !out || which < 0 || which > (a->split ? 1 : 0)) return NSOF_EINVAL;
     nsof_ctx* ctx = a->ctx;
-    float* tmp = nullptr;
-    int rc = accum_alloc(ctx, (void**)&tmp, a->npx * sizeof(float));
+    nsof_dev_buf<float> tmp;
+    int rc = tmp.reserve(ctx, a->npx * sizeof(float));
     if (rc) return rc;
-    rc = nsof_accum_resistance_dev(ctx, a->w[which], tmp, a->npx);
+    rc = nsof_accum_resistance_dev(ctx, a->w[which].p, tmp.p, a->npx);
     if (!rc) {
-        hipError_t e = hipMemcpyAsync(out, tmp, a->npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+        hipError_t e = hipMemcpyAsync(out, tmp.p, a->npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) rc = nsof_set_error(ctx, NSOF_EDEVICE, "copy failed: %s", hipGetErrorString(e));
     }
-    hipFree(tmp);
     return rc;
 }
 
@@ -1408,13 +1360,13 @@ extern "C" int nsof_accum_block_current(nsof_accum* a, int which, int64_t snapsh
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const int rows = a->H / memsize, cols = a->W / memsize;
     const size_t bytes = sizeof(double) * rows * cols;
-    int rc = nsof_ws_reserve(ctx, &ctx->tmp, &ctx->tmp_bytes, bytes);
+    int rc = ctx->tmp.reserve(ctx, bytes);
     if (rc) return rc;
-    const float* src = snapshot < 0 ? a->w[which] : a->snap[which] + (size_t)snapshot * a->npx;
+    const float* src = snapshot < 0 ? a->w[which].p : a->snap[which].p + (size_t)snapshot * a->npx;
     hipLaunchKernelGGL(k_block_min_resistance, dim3(cols, rows), dim3(256), 0, ctx->stream, src, snapshot < 0 ? 1 : 0, a->W,
-                       memsize, cols, (float)(-std::log(ROFF / RON)), v_ds, (double*)ctx->tmp);
+                       memsize, cols, (float)(-std::log(ROFF / RON)), v_ds, (double*)ctx->tmp.p);
     NSOF_HIP(ctx, hipGetLastError());
-    NSOF_HIP(ctx, hipMemcpyAsync(out, ctx->tmp, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    NSOF_HIP(ctx, hipMemcpyAsync(out, ctx->tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NSOF_OK;
 }
@@ -1429,7 +1381,7 @@ extern "C" int nsof_accum_block_current_dev(nsof_accum* a, int which, int64_t sn
     nsof_ctx* ctx = a->ctx;
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const int rows = a->H / memsize, cols = a->W / memsize;
-    const float* src = snapshot < 0 ? a->w[which] : a->snap[which] + (size_t)snapshot * a->npx;
+    const float* src = snapshot < 0 ? a->w[which].p : a->snap[which].p + (size_t)snapshot * a->npx;
     hipLaunchKernelGGL(k_block_min_resistance, dim3(cols, rows), dim3(256), 0, ctx->stream, src, snapshot < 0 ? 1 : 0, a->W,
                        memsize, cols, (float)(-std::log(ROFF / RON)), v_ds, d_out);
     NSOF_HIP(ctx, hipGetLastError());
@@ -1443,7 +1395,7 @@ extern "C" int nsof_accum_read_snapshots(nsof_accum* a, int which, float* out, i
     const int64_t n = a->snap_count < max_count ? a->snap_count : max_count;
     if (n > 0) {
         if (!out) return NSOF_EINVAL;
-        NSOF_HIP(ctx, hipMemcpyAsync(out, a->snap[which], (size_t)n * a->npx * sizeof(float), hipMemcpyDeviceToHost,
+        NSOF_HIP(ctx, hipMemcpyAsync(out, a->snap[which].p, (size_t)n * a->npx * sizeof(float), hipMemcpyDeviceToHost,
                                      ctx->stream));
         NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
@@ -1478,10 +1430,11 @@ extern "C" int nsof_accum_frames_f64(nsof_ctx* ctx, const double* imgs, int n_fr
         return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const size_t npx = (size_t)height * width;
-    double *d_img = nullptr, *d_w = nullptr, *d_res = nullptr;
-    int rc = accum_alloc(ctx, (void**)&d_img, (size_t)n_frames * npx * 8);
-    if (!rc) rc = accum_alloc(ctx, (void**)&d_w, npx * 8);
-    if (!rc) rc = accum_alloc(ctx, (void**)&d_res, (size_t)n_frames * npx * 8);
+    nsof_dev_buf<double> img_buf, w_buf, res_buf;
+    int rc = img_buf.reserve(ctx, (size_t)n_frames * npx * 8);
+    if (!rc) rc = w_buf.reserve(ctx, npx * 8);
+    if (!rc) rc = res_buf.reserve(ctx, (size_t)n_frames * npx * 8);
+    double *d_img = img_buf.p, *d_w = w_buf.p, *d_res = res_buf.p;
     if (!rc) {
         const double lambda = std::log(ROFF / RON);
         std::vector<double> init(npx, 0.5), r0(npx, RON / std::exp(-lambda * 0.5));
@@ -1501,6 +1454,5 @@ extern "C" int nsof_accum_frames_f64(nsof_ctx* ctx, const double* imgs, int n_fr
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) rc = nsof_set_error(ctx, NSOF_EDEVICE, "frame accumulator: %s", hipGetErrorString(e));
     }
-    hipFree(d_img); hipFree(d_w); hipFree(d_res);
     return rc;
 }

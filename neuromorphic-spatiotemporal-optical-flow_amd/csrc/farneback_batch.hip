@@ -66,9 +66,9 @@ int fallback_item(nsof_ctx* ctx, const nsof_pair_desc& d, const Params& p)
 {
     const size_t n0 = (size_t)d.width * d.height, row = (size_t)d.width * p.px();
     const size_t szU = align_up(n0 * p.px(), 256), szF = align_up(n0 * 8, 256);
-    int rc = nsof_ws_reserve(ctx, &ctx->stage, &ctx->stage_bytes, 2 * szU + szF);
+    int rc = ctx->stage.reserve(ctx, 2 * szU + szF);
     if (rc) return rc;
-    uint8_t* dP = (uint8_t*)ctx->stage;
+    uint8_t* dP = (uint8_t*)ctx->stage.p;
     uint8_t* dN = dP + szU;
     float* dF = (float*)(dN + szU);
     NSOF_HIP(ctx, hipMemcpy2DAsync(dP, row, d.prev, d.prev_stride, row, d.height, hipMemcpyDeviceToDevice, ctx->stream));
@@ -227,28 +227,13 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
         // words per level at most (every strip in one list)
         const size_t xj_words = use_xj ? align_up(8 + 8 * (size_t)strips0, 64) : 0;
         const size_t items_bytes = align_up((size_t)(Lmax + 1) * nh * sizeof(nsof_het_item), 256);
-        // two table slots used alternately: the upload of call c may still be queued when call c+1 builds its tables
+        // two tables used alternately: the upload of call c may still be queued when call c+1 builds its tables
         const size_t tab_bytes = align_up(items_bytes + (size_t)(Lmax + 1) * xj_words * sizeof(unsigned), 256);
-        if (ctx->het_bytes < 2 * tab_bytes) {
-            NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->het_h) hipHostFree(ctx->het_h);
-            if (ctx->het_d) hipFree(ctx->het_d);
-            ctx->het_h = ctx->het_d = nullptr;
-            ctx->het_bytes = 0;
-            const size_t cap = align_up(tab_bytes * 4, 4096);
-            if (hipHostMalloc(&ctx->het_h, cap, hipHostMallocDefault) != hipSuccess || hipMalloc(&ctx->het_d, cap) != hipSuccess)
-                return nsof_set_error(ctx, NSOF_ENOMEM, "work-list tables (%zu bytes)", cap);
-            ctx->het_bytes = cap;
-        }
-        const int slot = ctx->het_flip;
+        nsof_table& tab = ctx->het[ctx->het_flip];
         ctx->het_flip ^= 1;
-        if (!ctx->het_ev[slot]) NSOF_HIP(ctx, hipEventCreateWithFlags(&ctx->het_ev[slot], hipEventDisableTiming));
-        else NSOF_HIP(ctx, hipEventSynchronize(ctx->het_ev[slot]));   // this slot's previous upload has left the pinned copy
-        const size_t slot_off = (size_t)slot * (ctx->het_bytes / 2);
-        nsof_het_item* tabs = (nsof_het_item*)((char*)ctx->het_h + slot_off);
-        const nsof_het_item* d_tabs = (const nsof_het_item*)((char*)ctx->het_d + slot_off);
-        unsigned* xj = (unsigned*)((char*)ctx->het_h + slot_off + items_bytes);
-        const unsigned* d_xj = (const unsigned*)((char*)ctx->het_d + slot_off + items_bytes);
+        if ((rc = tab.stage(ctx, tab_bytes, align_up(2 * tab_bytes, 2048)))) return rc;
+        nsof_het_item* tabs = (nsof_het_item*)tab.h.p;
+        unsigned* xj = (unsigned*)((char*)tab.h.p + items_bytes);
 
         // Build the tables, coarsest level first in memory order k = 0..Lmax (table k at tabs + k*nh).
         std::vector<int> cnt(Lmax + 1, 0), xj_jobs(Lmax + 1, 0), xj_stride(Lmax + 1, 1);
@@ -296,15 +281,17 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
                 xj_used += align_up(8 + 8 * (size_t)xj_stride[k], 64);
             }
         }
-        NSOF_HIP(ctx, hipMemcpyAsync((void*)d_tabs, tabs, items_bytes + xj_used * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
-        NSOF_HIP(ctx, hipEventRecord(ctx->het_ev[slot], ctx->stream));
+        const char* d_tab = (const char*)tab.upload(ctx, items_bytes + xj_used * sizeof(unsigned));
+        if (!d_tab) return NSOF_EDEVICE;
+        const nsof_het_item* d_tabs = (const nsof_het_item*)d_tab;
+        const unsigned* d_xj = (const unsigned*)(d_tab + items_bytes);
 
         // workspace: level images, expansions, two flow buffers (every level uses their leading part)
         const size_t szI = align_up(maxI * 4, 256), szR = align_up(maxR * 4, 256), szF = align_up(maxF * 8, 256);
         const size_t szV = exact_lat ? szR : 0;   // column sums, 5 doubles per pixel = the expansion's footprint
         const size_t szM = exact_lat ? align_up(szR / 2, 256) : 0;        // matrices of the small-batch form, 5 floats per pixel
-        if ((rc = nsof_ws_reserve(ctx, &ctx->ws, &ctx->ws_bytes, szI + szR + 2 * szF + szV + szM))) return rc;
-        char* base = (char*)ctx->ws;
+        if ((rc = ctx->ws.reserve(ctx, szI + szR + 2 * szF + szV + szM))) return rc;
+        char* base = (char*)ctx->ws.p;
         float* dI = (float*)base;
         float* dR = (float*)(base + szI);
         float* fb[2] = {(float*)(base + szI + szR), (float*)(base + szI + szR + szF)};
@@ -413,10 +400,8 @@ void parallel_rows(size_t n_tasks, const std::function<void(size_t)>& fn)
 struct nsof_pipe {
     hipStream_t s_in = nullptr, s_out = nullptr;
     struct Slot {
-        void* d_in = nullptr;  size_t d_in_bytes = 0;
-        void* d_out = nullptr; size_t d_out_bytes = 0;
-        void* h_in = nullptr;  size_t h_in_bytes = 0;
-        void* h_out = nullptr; size_t h_out_bytes = 0;
+        nsof_dev_buf<> d_in, d_out;
+        nsof_host_buf<> h_in, h_out;
         hipEvent_t in_done = nullptr, compute_done = nullptr, out_done = nullptr;
     } slot[3];
     static constexpr int NSLOT = 3;
@@ -427,10 +412,6 @@ void nsof_pipe_destroy(nsof_ctx* ctx)
     nsof_pipe* p = ctx->pipe;
     if (!p) return;
     for (auto& s : p->slot) {
-        if (s.d_in) hipFree(s.d_in);
-        if (s.d_out) hipFree(s.d_out);
-        if (s.h_in) hipHostFree(s.h_in);
-        if (s.h_out) hipHostFree(s.h_out);
         if (s.in_done) hipEventDestroy(s.in_done);
         if (s.compute_done) hipEventDestroy(s.compute_done);
         if (s.out_done) hipEventDestroy(s.out_done);
@@ -458,26 +439,6 @@ int pipe_get(nsof_ctx* ctx, nsof_pipe** out)
         }
     }
     *out = ctx->pipe;
-    return NSOF_OK;
-}
-
-int grow_dev(nsof_ctx* ctx, void** buf, size_t* cur, size_t need)
-{
-    if (*cur >= need) return NSOF_OK;
-    if (*buf) NSOF_HIP(ctx, hipFree(*buf));
-    *buf = nullptr; *cur = 0;
-    if (hipMalloc(buf, need) != hipSuccess) { *buf = nullptr; return nsof_set_error(ctx, NSOF_ENOMEM, "hipMalloc(%zu)", need); }
-    *cur = need;
-    return NSOF_OK;
-}
-int grow_host(nsof_ctx* ctx, void** buf, size_t* cur, size_t need)
-{
-    if (*cur >= need) return NSOF_OK;
-    if (*buf) NSOF_HIP(ctx, hipHostFree(*buf));
-    *buf = nullptr; *cur = 0;
-    *buf = nsof_pinned_alloc(ctx->device, need);
-    if (!*buf) return nsof_set_error(ctx, NSOF_ENOMEM, "hipHostMalloc(%zu)", need);
-    *cur = need;
     return NSOF_OK;
 }
 
@@ -633,9 +594,9 @@ static int roi_sequence(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, pt
     if (n_pixels) *n_pixels = pixels;
     if (descs.empty()) return NSOF_OK;
     if (tmp_floats) {
-        if (int rc = nsof_ws_reserve(ctx, &ctx->roi_tmp, &ctx->roi_tmp_bytes, tmp_floats * 4)) return rc;
+        if (int rc = ctx->roi_tmp.reserve(ctx, tmp_floats * 4)) return rc;
         for (size_t i : tmp_slot)
-            descs[i].flow = reinterpret_cast<float*>((char*)ctx->roi_tmp + reinterpret_cast<uintptr_t>(descs[i].flow));
+            descs[i].flow = reinterpret_cast<float*>((char*)ctx->roi_tmp.p + reinterpret_cast<uintptr_t>(descs[i].flow));
     }
     for (size_t i = 0; i < descs.size(); i += 32767) {
         const int n = (int)std::min<size_t>(32767, descs.size() - i);
@@ -643,28 +604,16 @@ static int roi_sequence(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, pt
     }
     if (!pastes.empty()) {
         const size_t bytes = pastes.size() * sizeof(PasteRec);
-        if (!ctx->paste_ev) NSOF_HIP(ctx, hipEventCreateWithFlags(&ctx->paste_ev, hipEventDisableTiming));
-        else NSOF_HIP(ctx, hipEventSynchronize(ctx->paste_ev));   // the previous call's upload has left the pinned copy
-        if (ctx->paste_bytes < bytes) {
-            NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->paste_h) hipHostFree(ctx->paste_h);
-            if (ctx->paste_d) hipFree(ctx->paste_d);
-            ctx->paste_h = ctx->paste_d = nullptr;
-            ctx->paste_bytes = 0;
-            const size_t cap = align_up(bytes + bytes / 2, 4096);
-            if (hipHostMalloc(&ctx->paste_h, cap, hipHostMallocDefault) != hipSuccess || hipMalloc(&ctx->paste_d, cap) != hipSuccess)
-                return nsof_set_error(ctx, NSOF_ENOMEM, "paste table (%zu bytes)", cap);
-            ctx->paste_bytes = cap;
-        }
-        memcpy(ctx->paste_h, pastes.data(), bytes);
-        NSOF_HIP(ctx, hipMemcpyAsync(ctx->paste_d, ctx->paste_h, bytes, hipMemcpyHostToDevice, ctx->stream));
-        NSOF_HIP(ctx, hipEventRecord(ctx->paste_ev, ctx->stream));
+        if (int rc = ctx->paste.stage(ctx, bytes, align_up(bytes + bytes / 2, 4096))) return rc;
+        memcpy(ctx->paste.h.p, pastes.data(), bytes);
+        const PasteRec* d_pastes = (const PasteRec*)ctx->paste.upload(ctx, bytes);
+        if (!d_pastes) return NSOF_EDEVICE;
         int max_area = 0;
         for (const PasteRec& q : pastes) max_area = std::max(max_area, q.w * q.h);
         for (size_t i = 0; i < pastes.size(); i += 65535) {
             const unsigned n = (unsigned)std::min<size_t>(65535, pastes.size() - i);
             hipLaunchKernelGGL(k_paste_ordered, dim3((unsigned)((max_area + 1023) / 1024), 1, n), dim3(256), 0, ctx->stream,
-                               (const PasteRec*)ctx->paste_d + i, (const float*)ctx->roi_tmp, d_counts, d_rects, max_rects,
+                               d_pastes + i, (const float*)ctx->roi_tmp.p, d_counts, d_rects, max_rects,
                                (size_t)width);
         }
         NSOF_HIP(ctx, hipGetLastError());
@@ -756,7 +705,7 @@ int batch_host(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, const Pa
         parallel_rows(rows.size(), [&](size_t t) {
             const int i = rows[t].first, y0 = rows[t].second;
             const nsof_pair_desc& d = pairs[i];
-            const char* src = (const char*)s.h_out + c.out_off[i - c.lo];
+            const char* src = (const char*)s.h_out.p + c.out_off[i - c.lo];
             for (int y = y0; y < std::min(y0 + 64, d.height); y++)
                 memcpy((char*)d.flow + (ptrdiff_t)y * d.flow_stride, src + (size_t)y * d.width * 8, (size_t)d.width * 8);
         });
@@ -811,17 +760,16 @@ int batch_host(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, const Pa
             if (!finished[ci - NS]) {
                 bool prev_pageable = false;
                 for (int i = chunks[ci - NS].lo; i < chunks[ci - NS].hi; i++) prev_pageable = prev_pageable || !pin_out[i];
-                if (prev_pageable || s.h_out_bytes < c.out_bytes || s.d_out_bytes < c.out_bytes || s.d_in_bytes < c.in_bytes ||
-                    s.h_in_bytes < c.in_bytes) {
+                if (prev_pageable || s.h_out.cap < c.out_bytes || s.d_out.cap < c.out_bytes || s.d_in.cap < c.in_bytes ||
+                    s.h_in.cap < c.in_bytes) {
                     if (int rc = finish(chunks[ci - NS], s)) return rc;
                     finished[ci - NS] = 1;
                 }
             }
         }
         int rc;
-        if ((rc = grow_dev(ctx, &s.d_in, &s.d_in_bytes, c.in_bytes)) || (rc = grow_dev(ctx, &s.d_out, &s.d_out_bytes, c.out_bytes)) ||
-            (rc = grow_host(ctx, &s.h_in, &s.h_in_bytes, c.in_bytes)) ||
-            (chunk_pageable_out && (rc = grow_host(ctx, &s.h_out, &s.h_out_bytes, c.out_bytes))))
+        if ((rc = s.d_in.reserve(ctx, c.in_bytes)) || (rc = s.d_out.reserve(ctx, c.out_bytes)) || (rc = s.h_in.reserve(ctx, c.in_bytes)) ||
+            (chunk_pageable_out && (rc = s.h_out.reserve(ctx, c.out_bytes))))
             return rc;
         // stage 1: frames -> device (pageable / strided sources are packed into the pinned slot buffer by a few threads)
         if (trace) thost[ci][0] = now_ms() - t_call;
@@ -835,7 +783,7 @@ int batch_host(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, const Pa
             const nsof_pair_desc& d = pairs[i];
             const uint8_t* src = f ? d.next : d.prev;
             const ptrdiff_t st = f ? d.next_stride : d.prev_stride;
-            uint8_t* dst = (uint8_t*)s.h_in + c.in_off[f][i - c.lo];
+            uint8_t* dst = (uint8_t*)s.h_in.p + c.in_off[f][i - c.lo];
             const int y1 = std::min(y0 + 128, d.height);
             const size_t row = (size_t)d.width * p.px();   // bytes of a packed row
             if (st == (ptrdiff_t)row) {
@@ -850,14 +798,14 @@ int batch_host(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, const Pa
         bool all_packed = true;
         for (int i = c.lo; i < c.hi; i++) all_packed = all_packed && !pin_in[2 * i] && !pin_in[2 * i + 1];
         if (all_packed) {
-            NSOF_HIP(ctx, hipMemcpyAsync(s.d_in, s.h_in, c.in_bytes, hipMemcpyHostToDevice, pp->s_in));
+            NSOF_HIP(ctx, hipMemcpyAsync(s.d_in.p, s.h_in.p, c.in_bytes, hipMemcpyHostToDevice, pp->s_in));
         } else {
             for (int i = c.lo; i < c.hi; i++)
                 for (int f = 0; f < 2; f++) {
                     const size_t off = c.in_off[f][i - c.lo], n0 = (size_t)pairs[i].width * pairs[i].height * p.px();
                     const void* src = pin_in[2 * i + f] ? (const void*)(f ? pairs[i].next : pairs[i].prev)
-                                                        : (const void*)((char*)s.h_in + off);
-                    NSOF_HIP(ctx, hipMemcpyAsync((char*)s.d_in + off, src, n0, hipMemcpyHostToDevice, pp->s_in));
+                                                        : (const void*)((char*)s.h_in.p + off);
+                    NSOF_HIP(ctx, hipMemcpyAsync((char*)s.d_in.p + off, src, n0, hipMemcpyHostToDevice, pp->s_in));
                 }
         }
         NSOF_HIP(ctx, hipEventRecord(s.in_done, pp->s_in));
@@ -868,12 +816,12 @@ int batch_host(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, const Pa
         dd.resize(c.hi - c.lo);
         for (int i = c.lo; i < c.hi; i++) {
             nsof_pair_desc& d = dd[i - c.lo];
-            d.prev = (const uint8_t*)s.d_in + c.in_off[0][i - c.lo];
-            d.next = (const uint8_t*)s.d_in + c.in_off[1][i - c.lo];
+            d.prev = (const uint8_t*)s.d_in.p + c.in_off[0][i - c.lo];
+            d.next = (const uint8_t*)s.d_in.p + c.in_off[1][i - c.lo];
             d.prev_stride = d.next_stride = (ptrdiff_t)(pairs[i].width * p.px());
             d.width = pairs[i].width;
             d.height = pairs[i].height;
-            d.flow = (float*)((char*)s.d_out + c.out_off[i - c.lo]);
+            d.flow = (float*)((char*)s.d_out.p + c.out_off[i - c.lo]);
             d.flow_stride = (ptrdiff_t)pairs[i].width * 8;
         }
         mark(ci, 2, ctx->stream);
@@ -888,18 +836,18 @@ int batch_host(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, const Pa
         if (!chunk_pageable_out) {
             for (int i = c.lo; i < c.hi; i++) {
                 const size_t off = c.out_off[i - c.lo], nb = (size_t)pairs[i].width * pairs[i].height * 8;
-                NSOF_HIP(ctx, hipMemcpyAsync(pairs[i].flow, (char*)s.d_out + off, nb, hipMemcpyDeviceToHost, pp->s_out));
+                NSOF_HIP(ctx, hipMemcpyAsync(pairs[i].flow, (char*)s.d_out.p + off, nb, hipMemcpyDeviceToHost, pp->s_out));
             }
         } else {
             bool none_pinned = true;
             for (int i = c.lo; i < c.hi; i++) none_pinned = none_pinned && !pin_out[i];
             if (none_pinned) {
-                NSOF_HIP(ctx, hipMemcpyAsync(s.h_out, s.d_out, c.out_bytes, hipMemcpyDeviceToHost, pp->s_out));
+                NSOF_HIP(ctx, hipMemcpyAsync(s.h_out.p, s.d_out.p, c.out_bytes, hipMemcpyDeviceToHost, pp->s_out));
             } else {
                 for (int i = c.lo; i < c.hi; i++) {
                     const size_t off = c.out_off[i - c.lo], nb = (size_t)pairs[i].width * pairs[i].height * 8;
-                    void* dst = pin_out[i] ? (void*)pairs[i].flow : (void*)((char*)s.h_out + off);
-                    NSOF_HIP(ctx, hipMemcpyAsync(dst, (char*)s.d_out + off, nb, hipMemcpyDeviceToHost, pp->s_out));
+                    void* dst = pin_out[i] ? (void*)pairs[i].flow : (void*)((char*)s.h_out.p + off);
+                    NSOF_HIP(ctx, hipMemcpyAsync(dst, (char*)s.d_out.p + off, nb, hipMemcpyDeviceToHost, pp->s_out));
                 }
             }
         }

@@ -779,7 +779,7 @@ int launch_x(nsof_ctx* ctx, int n, int max_w, int max_h, const float* R0, const 
     NSOF_HIP(ctx, hipMemsetAsync(tickets, 0, 8 * 32 * sizeof(unsigned), ctx->stream));
     unsigned epoch = ++ctx->x_epoch;
     if (epoch == 0) {   // wrapped: every tag in the buffer is stale but may match again -> clear it
-        NSOF_HIP(ctx, hipMemsetAsync(ctx->x_carry, 0, ctx->x_carry_bytes, ctx->stream));
+        NSOF_HIP(ctx, hipMemsetAsync(ctx->x_carry.p, 0, ctx->x_carry.cap, ctx->stream));
         epoch = ++ctx->x_epoch;
     }
     const unsigned grid = HET ? (unsigned)njobs : 8u * (unsigned)((n + 7) / 8) * (unsigned)nstrips;

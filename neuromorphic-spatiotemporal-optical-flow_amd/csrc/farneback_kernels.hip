@@ -1992,9 +1992,9 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
 #undef NSOF_PREP_DIRECT
         } else if (taps.ksize == 19 && scale_x >= 1.0 && scale_y >= 1.0) {
             // measured at 1080p x 64 frames: 19 taps 459 -> 244 us; 9 taps is still faster tiled (231 vs 254 us)
-            int rc = nsof_ws_reserve(ctx, &ctx->tmp, &ctx->tmp_bytes, (size_t)n_img * H * 2 * wk * sizeof(float));
+            int rc = ctx->tmp.reserve(ctx, (size_t)n_img * H * 2 * wk * sizeof(float));
             if (rc) return rc;
-            float* HA = static_cast<float*>(ctx->tmp);
+            float* HA = static_cast<float*>(ctx->tmp.p);
             dim3 ga((2 * wk + 63) / 64, (H + 4 * PREPA_ROWS - 1) / (4 * PREPA_ROWS), n_img);
             dim3 gb((wk + 63) / 64, (hk + 3) / 4, n_img);
             hipLaunchKernelGGL((k_prep_rows<19, T>), ga, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H, wk,

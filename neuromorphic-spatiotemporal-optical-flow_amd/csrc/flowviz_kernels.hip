@@ -241,9 +241,9 @@ extern "C" int nsof_flow_to_image_dev(nsof_ctx* ctx, int n, const float* d_flows
     const int neg = sign < 0;
     unsigned* slots = nullptr;
     if (!given) {
-        int rc = nsof_ws_reserve(ctx, &ctx->tmp, &ctx->tmp_bytes, (size_t)n * sizeof(unsigned));
+        int rc = ctx->tmp.reserve(ctx, (size_t)n * sizeof(unsigned));
         if (rc) return rc;
-        slots = (unsigned*)ctx->tmp;
+        slots = (unsigned*)ctx->tmp.p;
         NSOF_HIP(ctx, hipMemsetAsync(slots, 0, (size_t)n * sizeof(unsigned), ctx->stream));
     }
     const bool v4 = (reinterpret_cast<uintptr_t>(d_flows) & 15) == 0 && row_stride_floats % 4 == 0 &&

@@ -396,11 +396,11 @@ extern "C" int nsof_roi_from_surface_dev(nsof_ctx* ctx, const double* d_current,
     int* par = nullptr;
     int* tile_roots = nullptr;
     if (per_map) {
-        const size_t budget = std::max(ctx->ws_bytes, (size_t)64 << 20);
+        const size_t budget = std::max(ctx->ws.cap, (size_t)64 << 20);
         chunk = std::min(chunk, std::max<size_t>(1, budget / per_map));
         chunk = std::min(chunk, (size_t)n_maps);
-        if (int rc = nsof_ws_reserve(ctx, &ctx->ws, &ctx->ws_bytes, chunk * per_map)) return rc;
-        par = (int*)ctx->ws;
+        if (int rc = ctx->ws.reserve(ctx, chunk * per_map)) return rc;
+        par = (int*)ctx->ws.p;
         tile_roots = par + chunk * ncell;
     }
     for (int m0 = 0; m0 < n_maps; m0 += (int)chunk) {

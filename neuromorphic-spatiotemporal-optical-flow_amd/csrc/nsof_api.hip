@@ -26,50 +26,32 @@ int nsof_set_error(nsof_ctx* ctx, int code, const char* fmt, ...)
     return code;
 }
 
-int nsof_ws_reserve(nsof_ctx* ctx, void** buf, size_t* cur, size_t need)
-{
-    if (*cur >= need) return NSOF_OK;
-    if (*buf) {
-        NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        NSOF_HIP(ctx, hipFree(*buf));
-        *buf = nullptr;
-        *cur = 0;
-    }
-    hipError_t e = hipMalloc(buf, need);
-    if (e != hipSuccess) {
-        *buf = nullptr;
-        return nsof_set_error(ctx, NSOF_ENOMEM, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-    }
-    *cur = need;
-    return NSOF_OK;
-}
-
 int nsof_xsync_reserve(nsof_ctx* ctx, size_t carry_bytes, unsigned long long** carry, unsigned** tickets, unsigned** err)
 {
-    if (!ctx->x_sync) {
-        NSOF_HIP(ctx, hipMalloc((void**)&ctx->x_sync, 2048));
-        NSOF_HIP(ctx, hipMemsetAsync(ctx->x_sync, 0, 2048, ctx->stream));
+    if (!ctx->x_sync.p) {
+        if (int rc = ctx->x_sync.reserve(ctx, 2048)) return rc;
+        NSOF_HIP(ctx, hipMemsetAsync(ctx->x_sync.p, 0, 2048, ctx->stream));
     }
-    if (carry_bytes > ctx->x_carry_bytes) {
-        carry_bytes = (carry_bytes + (carry_bytes >> 3) + 4095) & ~(size_t)4095;   // some slack: shapes vary from call to call
-        if (int rc = nsof_ws_reserve(ctx, (void**)&ctx->x_carry, &ctx->x_carry_bytes, carry_bytes)) return rc;
-        NSOF_HIP(ctx, hipMemsetAsync(ctx->x_carry, 0, ctx->x_carry_bytes, ctx->stream));   // tag 0 = never written
+    if (carry_bytes > ctx->x_carry.cap) {
+        // some slack: shapes vary from call to call
+        if (int rc = ctx->x_carry.reserve(ctx, carry_bytes, (carry_bytes + (carry_bytes >> 3) + 4095) & ~(size_t)4095)) return rc;
+        NSOF_HIP(ctx, hipMemsetAsync(ctx->x_carry.p, 0, ctx->x_carry.cap, ctx->stream));   // tag 0 = never written
     }
-    *carry = ctx->x_carry;
-    *tickets = ctx->x_sync;
-    *err = ctx->x_sync + 256;
+    *carry = ctx->x_carry.p;
+    *tickets = ctx->x_sync.p;
+    *err = ctx->x_sync.p + 256;
     ctx->x_dirty = true;
     return NSOF_OK;
 }
 
 int nsof_xsync_check(nsof_ctx* ctx)
 {
-    if (!ctx->x_dirty || !ctx->x_sync) return NSOF_OK;
+    if (!ctx->x_dirty || !ctx->x_sync.p) return NSOF_OK;
     ctx->x_dirty = false;
     unsigned w = 0;
-    NSOF_HIP(ctx, hipMemcpy(&w, ctx->x_sync + 256, sizeof(w), hipMemcpyDeviceToHost));
+    NSOF_HIP(ctx, hipMemcpy(&w, ctx->x_sync.p + 256, sizeof(w), hipMemcpyDeviceToHost));
     if (w) {
-        NSOF_HIP(ctx, hipMemset(ctx->x_sync + 256, 0, sizeof(w)));
+        NSOF_HIP(ctx, hipMemset(ctx->x_sync.p + 256, 0, sizeof(w)));
         return nsof_set_error(ctx, NSOF_EDEVICE, "exact-order iteration: a hand-over between workgroups / waves never arrived (flags %u); results are invalid", w);
     }
     return NSOF_OK;
@@ -175,17 +157,43 @@ void* nsof_pinned_alloc(int device, size_t bytes)
     return p;
 }
 
-int nsof_hstage_reserve(nsof_ctx* ctx, size_t need)
+int nsof_buf_grow(nsof_ctx* ctx, bool pinned, void** p, size_t* cap, size_t need, size_t new_cap)
 {
-    if (ctx->hstage_bytes >= need) return NSOF_OK;
-    NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->hstage) hipHostFree(ctx->hstage);
-    ctx->hstage = nullptr;
-    ctx->hstage_bytes = 0;
-    ctx->hstage = nsof_pinned_alloc(ctx->device, need);
-    if (!ctx->hstage) return nsof_set_error(ctx, NSOF_ENOMEM, "hipHostMalloc(%zu) failed", need);
-    ctx->hstage_bytes = need;
+    if (*cap >= need) return NSOF_OK;
+    if (*p) {
+        NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));   // queued work may still touch the old allocation
+        NSOF_HIP(ctx, pinned ? hipHostFree(*p) : hipFree(*p));
+        *p = nullptr;
+        *cap = 0;
+    }
+    if (pinned) {
+        *p = nsof_pinned_alloc(ctx->device, new_cap);
+        if (!*p) return nsof_set_error(ctx, NSOF_ENOMEM, "hipHostMalloc(%zu) failed", new_cap);
+    } else if (hipError_t e = hipMalloc(p, new_cap)) {
+        *p = nullptr;
+        return nsof_set_error(ctx, NSOF_ENOMEM, "hipMalloc(%zu) failed: %s", new_cap, hipGetErrorString(e));
+    }
+    *cap = new_cap;
     return NSOF_OK;
+}
+
+int nsof_table::stage(nsof_ctx* ctx, size_t bytes, size_t cap)
+{
+    if (!ev) NSOF_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    else NSOF_HIP(ctx, hipEventSynchronize(ev));   // the previous upload has left the pinned copy
+    if (int rc = h.reserve(ctx, bytes, cap)) return rc;
+    return d.reserve(ctx, bytes, cap);
+}
+
+const void* nsof_table::upload(nsof_ctx* ctx, size_t bytes)
+{
+    hipError_t e = hipMemcpyAsync(d.p, h.p, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(ev, ctx->stream);
+    if (e != hipSuccess) {
+        nsof_set_error(ctx, NSOF_EDEVICE, "table upload (%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        return nullptr;
+    }
+    return d.p;
 }
 
 extern "C" const char* nsof_kernel_name(int id)
@@ -246,23 +254,6 @@ extern "C" void nsof_destroy(nsof_ctx* ctx)
         for (auto ev : s.start) hipEventDestroy(ev);
         for (auto ev : s.stop) hipEventDestroy(ev);
     }
-    if (ctx->ws) hipFree(ctx->ws);
-    if (ctx->stage) hipFree(ctx->stage);
-    if (ctx->tmp) hipFree(ctx->tmp);
-    if (ctx->hstage) hipHostFree(ctx->hstage);
-    if (ctx->het_h) hipHostFree(ctx->het_h);
-    if (ctx->het_d) hipFree(ctx->het_d);
-    if (ctx->x_carry) hipFree(ctx->x_carry);
-    if (ctx->roi_tmp) hipFree(ctx->roi_tmp);
-    if (ctx->paste_h) hipHostFree(ctx->paste_h);
-    if (ctx->paste_d) hipFree(ctx->paste_d);
-    if (ctx->paste_ev) hipEventDestroy(ctx->paste_ev);
-    if (ctx->seg_h) hipHostFree(ctx->seg_h);
-    if (ctx->seg_d) hipFree(ctx->seg_d);
-    if (ctx->seg_ev) hipEventDestroy(ctx->seg_ev);
-    if (ctx->x_sync) hipFree(ctx->x_sync);
-    for (auto ev : ctx->het_ev)
-        if (ev) hipEventDestroy(ev);
     nsof_pipe_destroy(ctx);
     for (auto ev : ctx->ov_events) hipEventDestroy(ev);
     if (ctx->side) hipStreamDestroy(ctx->side);
@@ -571,8 +562,8 @@ extern "C" int nsof_stage_blur_solve(nsof_ctx* ctx, int n_pairs, const float* d_
     if (!ctx || !d_M || !d_flow || n_pairs < 1 || width < 1 || height < 1 || winsize < 2) return NSOF_EINVAL;
     if (ctx->opt_exact_rowsums) {   // the library's row-sum order (k_blur_colsum + k_blur_rowsolve), as the driver runs it
         const size_t need = (size_t)n_pairs * 5 * width * height * sizeof(double);
-        if (int rc = nsof_ws_reserve(ctx, &ctx->ws, &ctx->ws_bytes, need)) return rc;
-        return nsof_launch_blur_solve_exact(ctx, n_pairs, d_M, width, height, winsize, (double*)ctx->ws, d_flow);
+        if (int rc = ctx->ws.reserve(ctx, need)) return rc;
+        return nsof_launch_blur_solve_exact(ctx, n_pairs, d_M, width, height, winsize, (double*)ctx->ws.p, d_flow);
     }
     return nsof_launch_blur_solve(ctx, n_pairs, d_M, width, height, winsize, d_flow);
 }
@@ -610,6 +601,37 @@ extern "C" int nsof_stage_flow_upsample(nsof_ctx* ctx, int n_pairs, const float*
 
 // ---- the Farneback driver --------------------------------------------------------------------
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Workspace of the uniform driver for B pairs: I [n_img][nk] f32 and R [n_img][5*nk] f32 (level images and
+// expansions: one slot that every level reuses, or one slot per level for the latency schedule `lat`), S = second flow
+// buffer [B][n0][2], M [B][5][n0] (the unfused iteration and the three-kernel exact form), V = column sums [B][5][n0] f64
+// (the unfused and the three-kernel exact order).  Offsets in bytes, in that order.
+struct Carve {
+    std::vector<size_t> offI, offR;   // per level, within I / R
+    size_t szI = 0, szR = 0, szS = 0, szM = 0, szV = 0;
+    size_t total() const { return szI + szR + szS + szM + szV; }
+};
+static Carve farneback_carve(size_t B, bool sequence, int width, int height, double pyr_scale, int L, bool lat, bool fused,
+                             bool exact, bool exact_x, bool exact_lat)
+{
+    Carve c;
+    c.offI.assign(L + 1, 0);
+    c.offR.assign(L + 1, 0);
+    const size_t n0 = (size_t)width * height;
+    const size_t n_img = sequence ? B + 1 : 2 * B;   // frames of a sequence, or B prev + B next frames
+    for (int k = 0; k <= (lat ? L : 0); k++) {
+        int wk, hk;
+        nsof_farneback_level_size(width, height, pyr_scale, k, &wk, &hk, nullptr, nullptr);
+        c.offI[k] = c.szI;
+        c.offR[k] = c.szR;
+        c.szI += align_up(n_img * (size_t)wk * hk * 4, 256);
+        c.szR += align_up(n_img * 5 * (size_t)wk * hk * 4, 256);
+    }
+    c.szS = align_up(B * n0 * 8, 256);
+    c.szM = fused && !exact_lat ? 0 : align_up(B * 5 * n0 * 4, 256);
+    c.szV = (exact && !exact_x) || exact_lat ? align_up(B * 5 * n0 * 8, 256) : 0;
+    return c;
+}
 
 // Core of both device entry points.  sequence == false: n_pairs independent pairs (d_prev[i], d_next[i]);
 // sequence == true: n_pairs + 1 consecutive frames in d_prev (d_next unused), pair i = (frame i, frame i+1) -- every
@@ -652,19 +674,38 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
         return NSOF_OK;
     }
 
+    const int L = nsof_farneback_effective_levels(width, height, pyr_scale, levels);
+    // Fused or unfused is decided once for the whole pyramid (inputs below 2x2 take the unfused pair); the exact
+    // row-sum order is fused only where k_iterate_x runs it.
+    const bool fused = nsof_iterate_supported(winsize, width, height) && (!exact || exact_x);
+    // ---- small batches (the three-kernel exact form): the latency schedule ---------------------------------------------
+    // A lone call is a chain of ~50 launches that each use a fraction of the chip and cost >= ~5 us (profiles/
+    // r03_lone_call_timeline.txt: 762 us at 1080p, a third of it in the two coarsest levels).  Only the FLOW couples the
+    // levels; pyramid level and polynomial expansion of every level depend on the input frames alone.  So they move to a
+    // side stream (levels L-1 .. 0, into per-level buffers) and run next to the iterations of the coarser levels on the
+    // main stream; an event per level hands the expansion over.  Same kernels, same arguments, same bits.
+    const bool lat = exact_lat && fused && L >= 1 && iterations > 0;
+    auto carve = [&](size_t b) {
+        return farneback_carve(b, sequence, width, height, pyr_scale, L, lat, fused, exact, exact_x, exact_lat);
+    };
+    const Carve cv = carve((size_t)n_pairs);
     {
-        // A batch whose workspace (56 B/px/pair = 116 MB per 1080p pair: level images, expansions, second flow buffer;
-        // + 20 / 40 B/px of matrices / column sums in the unfused / exact forms) would not fit the device's free memory is run in chunks of as many pairs as do
-        // fit -- same kernels on sub-ranges of the same buffers, so the result does not depend on the chunking.
-        // NSOF_MAX_PAIRS caps the chunk by hand (tests).
-        // (the latency schedule of small batches keeps the level images and expansions of EVERY level: at most levels + 1 times those terms)
-        const size_t per_pair = (size_t)width * height * ((4 * 2 + 20 * 2) * (exact_lat ? (size_t)levels + 1 : 1) + 8 + 20 +
-                                                          (exact && !exact_x ? 40 : 0) + (exact_lat ? 60 : 0)) + 4096;
-        size_t fit = ctx->ws_bytes / per_pair;   // what the workspace already holds needs no query (lone calls stay cheap)
-        if ((size_t)n_pairs > fit) {
+        // A batch whose workspace would not fit the device's free memory is run in chunks of as many pairs as do fit --
+        // same kernels on sub-ranges of the same buffers, so the result does not depend on the chunking.  A batch that
+        // fits the workspace already held needs no query (lone calls stay cheap).  NSOF_MAX_PAIRS caps the chunk by
+        // hand (tests).
+        size_t fit = (size_t)n_pairs;
+        if (cv.total() > ctx->ws.cap) {
             size_t free_b = 0, total_b = 0;
             NSOF_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-            fit = (size_t)((double)(free_b + ctx->ws_bytes) * 0.92) / per_pair;
+            const size_t budget = (size_t)((double)(free_b + ctx->ws.cap) * 0.92);
+            size_t lo = 0, hi = (size_t)n_pairs;   // the most pairs whose workspace fits the budget
+            while (lo < hi) {
+                const size_t mid = (lo + hi + 1) / 2;
+                if (carve(mid).total() <= budget) lo = mid;
+                else hi = mid - 1;
+            }
+            fit = lo;
         }
         if (const char* e = getenv("NSOF_MAX_PAIRS")) {
             const long v = atol(e);
@@ -687,39 +728,13 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
 
     nsof_poly_taps ptaps;
     if ((rc = nsof_host_poly_taps(poly_n, poly_sigma, &ptaps))) return nsof_set_error(ctx, rc, "poly taps");
-    const int L = nsof_farneback_effective_levels(width, height, pyr_scale, levels);
-
-    // workspace: I [n_img][nk] f32 and R [n_img][5*nk] f32 (level images and expansions), S = second flow buffer
-    // [B][n0][2] (+ M [B][5][n0] only when the window is too large for the fused iteration kernel)
     const size_t n0 = (size_t)width * height, B = (size_t)n_pairs;
-    const size_t n_img = sequence ? B + 1 : 2 * B;   // frames of a sequence, or B prev + B next frames
-    // Fused or unfused is decided once for the whole pyramid (inputs below 2x2 take the unfused pair); the exact
-    // row-sum order is fused only where k_iterate_x runs it.
-    const bool fused = nsof_iterate_supported(winsize, width, height) && (!exact || exact_x);
-    // ---- small batches (the three-kernel exact form): the latency schedule ---------------------------------------------
-    // A lone call is a chain of ~50 launches that each use a fraction of the chip and cost >= ~5 us (profiles/
-    // r03_lone_call_timeline.txt: 762 us at 1080p, a third of it in the two coarsest levels).  Only the FLOW couples the
-    // levels; pyramid level and polynomial expansion of every level depend on the input frames alone.  So they move to a
-    // side stream (levels L-1 .. 0, into per-level buffers) and run next to the iterations of the coarser levels on the
-    // main stream; an event per level hands the expansion over.  Same kernels, same arguments, same bits.
-    const bool lat = exact_lat && fused && L >= 1 && iterations > 0;
-    // level images and expansions: one slot that every level reuses, or one slot per level for the latency schedule
-    std::vector<size_t> offI(L + 1), offR(L + 1);   // (zeros)
-    size_t szI = 0, szR = 0;
-    for (int k = 0; k <= (lat ? L : 0); k++) {
-        int wk, hk;
-        nsof_farneback_level_size(width, height, pyr_scale, k, &wk, &hk, nullptr, nullptr);
-        offI[k] = szI;
-        offR[k] = szR;
-        szI += align_up(n_img * (size_t)wk * hk * 4, 256);
-        szR += align_up(n_img * 5 * (size_t)wk * hk * 4, 256);
-    }
-    const size_t szS = align_up(B * n0 * 8, 256), szM = fused && !exact_lat ? 0 : align_up(B * 5 * n0 * 4, 256);
-    const size_t szV = (exact && !exact_x) || exact_lat ? align_up(B * 5 * n0 * 8, 256) : 0;   // column sums of the unfused / three-kernel exact order
-    if ((rc = nsof_ws_reserve(ctx, &ctx->ws, &ctx->ws_bytes, szI + szR + szS + szM + szV))) return rc;
-    char* base = (char*)ctx->ws;
-    auto level_I = [&](int k) { return (float*)(base + offI[k]); };
-    auto level_R = [&](int k) { return (float*)(base + szI + offR[k]); };
+    const size_t n_img = sequence ? B + 1 : 2 * B;
+    const size_t szI = cv.szI, szR = cv.szR, szS = cv.szS, szM = cv.szM;
+    if ((rc = ctx->ws.reserve(ctx, cv.total()))) return rc;
+    char* base = (char*)ctx->ws.p;
+    auto level_I = [&](int k) { return (float*)(base + cv.offI[k]); };
+    auto level_R = [&](int k) { return (float*)(base + szI + cv.offR[k]); };
     float* dS = (float*)(base + szI + szR);
     float* dM = (float*)(base + szI + szR + szS);
     double* dV = (double*)(base + szI + szR + szS + szM);
@@ -951,12 +966,11 @@ static int farneback_host_pair(nsof_ctx* ctx, int src, const void* prev, ptrdiff
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n0 = (size_t)width * height, pitch = (size_t)width * (src == NSOF_SRC_F32 ? 4 : 1);
     const size_t szU = align_up(pitch * height, 256), szF = align_up(n0 * 8, 256);
-    if ((rc = nsof_ws_reserve(ctx, &ctx->stage, &ctx->stage_bytes, 2 * szU + szF))) return rc;
-    if ((rc = nsof_hstage_reserve(ctx, 2 * szU + szF))) return rc;
-    char* hP = (char*)ctx->hstage;
+    if ((rc = ctx->stage.reserve(ctx, 2 * szU + szF)) || (rc = ctx->hstage.reserve(ctx, 2 * szU + szF))) return rc;
+    char* hP = (char*)ctx->hstage.p;
     char* hN = hP + szU;
     float* hF = (float*)(hN + szU);
-    char* dP = (char*)ctx->stage;
+    char* dP = (char*)ctx->stage.p;
     char* dN = dP + szU;
     float* dFl = (float*)(dN + szU);
     const bool in_dense = prev_stride == (ptrdiff_t)pitch && next_stride == (ptrdiff_t)pitch;

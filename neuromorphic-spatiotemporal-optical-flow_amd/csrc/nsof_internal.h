@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <utility>
 #include <vector>
 
 #include "nsof.h"
@@ -16,6 +17,53 @@ struct nsof_prof_slot {
     size_t used = 0;
     double acc_ms = 0;       // already-collected time
     long long acc_launches = 0;
+};
+
+struct nsof_ctx;
+
+// ---- memory the library owns ---------------------------------------------------------------------------------------
+// Device memory (Pinned = false) or page-locked host memory on the GPU's NUMA node (Pinned = true) that grows on
+// demand and frees itself.  The rule every reuse keeps: memory that a queued copy or kernel may still touch is never
+// freed -- reserve() waits on ctx->stream before it lets an old allocation go.
+int nsof_buf_grow(nsof_ctx* ctx, bool pinned, void** p, size_t* cap, size_t need, size_t new_cap);
+template <class T, bool Pinned> struct nsof_buf {
+    T* p = nullptr;
+    size_t cap = 0;   // bytes
+    nsof_buf() = default;
+    nsof_buf(const nsof_buf&) = delete;
+    nsof_buf& operator=(const nsof_buf&) = delete;
+    ~nsof_buf()
+    {
+        if (p) (void)(Pinned ? hipHostFree((void*)p) : hipFree((void*)p));
+    }
+    // At least `need` bytes: an allocation that is smaller is replaced by one of `new_cap` bytes (>= need).
+    // NSOF_ENOMEM (set on ctx) if that fails.
+    int reserve(nsof_ctx* ctx, size_t need, size_t new_cap) { return nsof_buf_grow(ctx, Pinned, (void**)&p, &cap, need, new_cap); }
+    int reserve(nsof_ctx* ctx, size_t need) { return reserve(ctx, need, need); }
+    void swap(nsof_buf& o)
+    {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+    }
+};
+template <class T = void> using nsof_dev_buf = nsof_buf<T, false>;
+template <class T = void> using nsof_host_buf = nsof_buf<T, true>;
+
+// A table the host writes and one copy uploads: pinned staging, its device copy, and the event after its last upload.
+struct nsof_table {
+    nsof_host_buf<> h;
+    nsof_dev_buf<> d;
+    hipEvent_t ev = nullptr;
+    ~nsof_table()
+    {
+        if (ev) (void)hipEventDestroy(ev);
+    }
+    // `bytes` of host staging at h.p, once the previous upload has left it; a table smaller than `bytes` is replaced
+    // (both copies) by one of `cap` bytes.
+    int stage(nsof_ctx* ctx, size_t bytes, size_t cap);
+    // The first `bytes` of the staging to the device copy on ctx->stream; returns the device copy (nullptr on failure,
+    // the error set on ctx: NSOF_EDEVICE).
+    const void* upload(nsof_ctx* ctx, size_t bytes);
 };
 
 struct nsof_ctx {
@@ -32,23 +80,15 @@ struct nsof_ctx {
     int opt_pyr_fma = 0;       // NSOF_OPT_PYR_FMA: pyramid blur / resamples with fused multiply-adds (arithmetic variant twin)
     char err[512] = {0};
     // reusable device workspace of the Farneback driver
-    void* ws = nullptr;
-    size_t ws_bytes = 0;
+    nsof_dev_buf<> ws;
     // staging for the host-pointer entry point
-    void* stage = nullptr;
-    size_t stage_bytes = 0;
+    nsof_dev_buf<> stage;
     // pinned host staging of the host-pointer entry point (frames in, flow out)
-    void* hstage = nullptr;
-    size_t hstage_bytes = 0;
+    nsof_host_buf<> hstage;
     // row-filtered intermediate of the two-pass pyramid kernels
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
-    // work-list path: per-level item tables (pinned host copy + device copy, two slots used alternately) and the
-    // events that mark the end of each slot's last upload (the pinned copy is rewritten two calls later)
-    void* het_h = nullptr;
-    void* het_d = nullptr;
-    size_t het_bytes = 0;
-    hipEvent_t het_ev[2] = {nullptr, nullptr};
+    nsof_dev_buf<> tmp;
+    // work-list path: per-level item tables, two used alternately (the pinned copy of one is rewritten two calls later)
+    nsof_table het[2];
     int het_flip = 0;
     // pipelined host entry (nsof_farneback_u8_batch): copy streams, per-slot staging and events
     struct nsof_pipe* pipe = nullptr;
@@ -56,37 +96,25 @@ struct nsof_ctx {
     // finer levels, next to the iterations of the coarser ones, and the events that hand each level over
     hipStream_t side = nullptr;
     std::vector<hipEvent_t> ov_events;
+    // private flow buffers of ROI crops that overlap an earlier crop of the same frame pair (nsof_farneback_u8_roi_sequence_dev)
+    nsof_dev_buf<> roi_tmp;
+    // ... and the table of their ordered pastes
+    nsof_table paste;
+    // box and job tables of the batched segmentation head (nsof_motion_mask_sequence_dev)
+    nsof_table seg;
     // exact-order fused iteration (farneback_iterate_x.hip): strip-to-strip carries (tagged granules, zeroed when
     // allocated, never again: a launch's tag is its epoch), the per-XCD ticket counters + timeout word (x_sync:
     // tickets at word 0, timeout word at word 256), the launch epoch, and whether a launch's timeout word needs a look
-    // private flow buffers of ROI crops that overlap an earlier crop of the same frame pair (nsof_farneback_u8_roi_sequence_dev)
-    void* roi_tmp = nullptr;
-    size_t roi_tmp_bytes = 0;
-    // ... and the table of their ordered pastes (pinned host copy, device copy, the event after its last upload)
-    void* paste_h = nullptr;
-    void* paste_d = nullptr;
-    size_t paste_bytes = 0;
-    hipEvent_t paste_ev = nullptr;
-    // box and job tables of the batched segmentation head (nsof_motion_mask_sequence_dev): pinned host copy, device
-    // copy, the event after its last upload
-    void* seg_h = nullptr;
-    void* seg_d = nullptr;
-    size_t seg_bytes = 0;
-    hipEvent_t seg_ev = nullptr;
-    unsigned long long* x_carry = nullptr;
-    size_t x_carry_bytes = 0;
-    unsigned* x_sync = nullptr;
+    nsof_dev_buf<unsigned long long> x_carry;
+    nsof_dev_buf<unsigned> x_sync;
     unsigned x_epoch = 0;
     bool x_dirty = false;
 };
 
 int nsof_set_error(nsof_ctx* ctx, int code, const char* fmt, ...);
-int nsof_ws_reserve(nsof_ctx* ctx, void** buf, size_t* cur, size_t need);
 // Page-locked host memory on the GPU's NUMA node (best effort); NUMA node of a device from sysfs, -1 if unknown.
 void* nsof_pinned_alloc(int device, size_t bytes);
 int nsof_gpu_numa_node(int device);
-// Grow ctx->hstage (pinned host staging) to at least `need` bytes.
-int nsof_hstage_reserve(nsof_ctx* ctx, size_t need);
 
 #define NSOF_HIP(ctx, call)                                                                      \
     do {                                                                                         \

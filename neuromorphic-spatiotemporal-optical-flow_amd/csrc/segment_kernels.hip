@@ -402,10 +402,10 @@ int mask_chain(nsof_ctx* ctx, int ksize, int iterations, MorphElem* el, int* n_p
 int reserve_bits(nsof_ctx* ctx, int w, int h, uint32_t** a, uint32_t** b)
 {
     const size_t one = ((size_t)words_per_row(w) * h * 4 + 255) & ~(size_t)255;
-    int rc = nsof_ws_reserve(ctx, &ctx->tmp, &ctx->tmp_bytes, 2 * one);
+    int rc = ctx->tmp.reserve(ctx, 2 * one);
     if (rc) return rc;
-    *a = (uint32_t*)ctx->tmp;
-    *b = (uint32_t*)((char*)ctx->tmp + one);
+    *a = (uint32_t*)ctx->tmp.p;
+    *b = (uint32_t*)((char*)ctx->tmp.p + one);
     return NSOF_OK;
 }
 
@@ -504,12 +504,12 @@ extern "C" int nsof_motion_mask(nsof_ctx* ctx, const float* flow, ptrdiff_t flow
     const size_t n0 = (size_t)width * height;
     const size_t szF = (n0 * 8 + 255) & ~(size_t)255, szM = (n0 + 255) & ~(size_t)255;
     int rc;
-    if ((rc = nsof_ws_reserve(ctx, &ctx->stage, &ctx->stage_bytes, szF + szM))) return rc;
-    if ((rc = nsof_hstage_reserve(ctx, szF + szM))) return rc;
-    float* hF = (float*)ctx->hstage;
-    uint8_t* hM = (uint8_t*)ctx->hstage + szF;
-    float* dF = (float*)ctx->stage;
-    uint8_t* dM = (uint8_t*)ctx->stage + szF;
+    if ((rc = ctx->stage.reserve(ctx, szF + szM))) return rc;
+    if ((rc = ctx->hstage.reserve(ctx, szF + szM))) return rc;
+    float* hF = (float*)ctx->hstage.p;
+    uint8_t* hM = (uint8_t*)ctx->hstage.p + szF;
+    float* dF = (float*)ctx->stage.p;
+    uint8_t* dM = (uint8_t*)ctx->stage.p + szF;
     const bool in_dense = flow_stride_bytes == (ptrdiff_t)width * 8, out_dense = mask_stride == width;
     if (!in_dense)
         for (int y = 0; y < height; y++)
@@ -577,32 +577,19 @@ extern "C" int nsof_motion_mask_sequence_dev(nsof_ctx* ctx, int n_pairs, const f
     const size_t o_first = up16(bx.size() * sizeof(SegBox)), o_pack = o_first + up16(first.size() * sizeof(int));
     const size_t o_morph = o_pack + up16(pack.size() * sizeof(SegJob));
     const size_t bytes = o_morph + morph.size() * sizeof(SegJob);
-    if (!ctx->seg_ev) NSOF_HIP(ctx, hipEventCreateWithFlags(&ctx->seg_ev, hipEventDisableTiming));
-    else NSOF_HIP(ctx, hipEventSynchronize(ctx->seg_ev));   // the previous call's upload has left the pinned copy
-    if (ctx->seg_bytes < bytes) {
-        NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->seg_h) hipHostFree(ctx->seg_h);
-        if (ctx->seg_d) hipFree(ctx->seg_d);
-        ctx->seg_h = ctx->seg_d = nullptr;
-        ctx->seg_bytes = 0;
-        const size_t cap = (bytes + bytes / 2 + 4095) & ~(size_t)4095;
-        if (hipHostMalloc(&ctx->seg_h, cap, hipHostMallocDefault) != hipSuccess || hipMalloc(&ctx->seg_d, cap) != hipSuccess)
-            return nsof_set_error(ctx, NSOF_ENOMEM, "segmentation tables (%zu bytes)", cap);
-        ctx->seg_bytes = cap;
-    }
-    if ((rc = nsof_ws_reserve(ctx, &ctx->tmp, &ctx->tmp_bytes, words * 4 > 256 ? words * 4 : 256))) return rc;
-    char* h = (char*)ctx->seg_h;
+    if ((rc = ctx->seg.stage(ctx, bytes, (bytes + bytes / 2 + 4095) & ~(size_t)4095))) return rc;
+    if ((rc = ctx->tmp.reserve(ctx, words * 4 > 256 ? words * 4 : 256))) return rc;
+    char* h = (char*)ctx->seg.h.p;
     memcpy(h, bx.data(), bx.size() * sizeof(SegBox));
     memcpy(h + o_first, first.data(), first.size() * sizeof(int));
     memcpy(h + o_pack, pack.data(), pack.size() * sizeof(SegJob));
     memcpy(h + o_morph, morph.data(), morph.size() * sizeof(SegJob));
-    NSOF_HIP(ctx, hipMemcpyAsync(ctx->seg_d, ctx->seg_h, bytes, hipMemcpyHostToDevice, ctx->stream));
-    NSOF_HIP(ctx, hipEventRecord(ctx->seg_ev, ctx->stream));
-    const char* d = (const char*)ctx->seg_d;
+    const char* d = (const char*)ctx->seg.upload(ctx, bytes);
+    if (!d) return NSOF_EDEVICE;
     const SegBox* d_boxes = (const SegBox*)d;
     const SegJob* d_pack = (const SegJob*)(d + o_pack);
     const SegJob* d_morph = (const SegJob*)(d + o_morph);
-    uint32_t* ws = (uint32_t*)ctx->tmp;
+    uint32_t* ws = (uint32_t*)ctx->tmp.p;
     constexpr size_t MAX_JOBS = 1u << 20;   // workgroups per launch (grid x threads stays far below 2^32)
     int final_b = 0;
     if (!bx.empty()) {
@@ -657,9 +644,9 @@ extern "C" int nsof_pixel_accuracy_u8_batch_dev(nsof_ctx* ctx, int n, const uint
         return nsof_set_error(ctx, NSOF_EINVAL, "pixel_accuracy: gt stride");
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const int nblk = (height + PA_ROWS - 1) / PA_ROWS;
-    int rc = nsof_ws_reserve(ctx, &ctx->tmp, &ctx->tmp_bytes, (size_t)n * nblk * sizeof(unsigned));
+    int rc = ctx->tmp.reserve(ctx, (size_t)n * nblk * sizeof(unsigned));
     if (rc) return rc;
-    unsigned* partial = (unsigned*)ctx->tmp;
+    unsigned* partial = (unsigned*)ctx->tmp.p;
     {
         nsof_prof_scope ps(ctx, NSOF_K_SEGMENT);
         hipLaunchKernelGGL(k_pa_partial, dim3(nblk, 1, n), dim3(256), 0, ctx->stream, d_masks, d_gt, gt_row_stride,

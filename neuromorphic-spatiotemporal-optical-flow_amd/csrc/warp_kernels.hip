@@ -357,12 +357,12 @@ extern "C" int nsof_predict_warp_u8(nsof_ctx* ctx, const uint8_t* frame, ptrdiff
     const size_t rowb = (size_t)width * channels;
     const size_t szI = (rowb * height + 255) & ~(size_t)255, szF = ((size_t)rw * rh * 8 + 255) & ~(size_t)255;
     const size_t szO = ((size_t)rw * rh * channels + 255) & ~(size_t)255;
-    if ((rc = nsof_ws_reserve(ctx, &ctx->stage, &ctx->stage_bytes, szI + szF + szO))) return rc;
-    if ((rc = nsof_hstage_reserve(ctx, szI + szF + szO))) return rc;
-    uint8_t* hI = (uint8_t*)ctx->hstage;
+    if ((rc = ctx->stage.reserve(ctx, szI + szF + szO))) return rc;
+    if ((rc = ctx->hstage.reserve(ctx, szI + szF + szO))) return rc;
+    uint8_t* hI = (uint8_t*)ctx->hstage.p;
     float* hF = (float*)(hI + szI);
     uint8_t* hO = hI + szI + szF;
-    uint8_t* dI = (uint8_t*)ctx->stage;
+    uint8_t* dI = (uint8_t*)ctx->stage.p;
     float* dF = (float*)(dI + szI);
     uint8_t* dO = dI + szI + szF;
     const bool dense = frame_stride == (ptrdiff_t)rowb;
@@ -400,9 +400,9 @@ extern "C" int nsof_ssim_u8_dev(nsof_ctx* ctx, const uint8_t* d_a, ptrdiff_t a_s
     const int ow = width - 2 * PAD, oh = height - 2 * PAD;
     dim3 grid((ow + SX - 1) / SX, (oh + SY - 1) / SY);
     const int nblk = grid.x * grid.y;
-    int rc = nsof_ws_reserve(ctx, &ctx->tmp, &ctx->tmp_bytes, ((size_t)nblk + 1) * sizeof(double));
+    int rc = ctx->tmp.reserve(ctx, ((size_t)nblk + 1) * sizeof(double));
     if (rc) return rc;
-    double* partial = (double*)ctx->tmp;
+    double* partial = (double*)ctx->tmp.p;
     const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
     {
         nsof_prof_scope ps(ctx, NSOF_K_SSIM);
@@ -429,9 +429,9 @@ extern "C" int nsof_ssim_u8(nsof_ctx* ctx, const uint8_t* a, ptrdiff_t a_stride,
     // pack the one channel of each image into dense planes on the host side of the copy
     const size_t n0 = (size_t)width * height, sz = (n0 + 255) & ~(size_t)255;
     int rc;
-    if ((rc = nsof_ws_reserve(ctx, &ctx->stage, &ctx->stage_bytes, 2 * sz))) return rc;
-    if ((rc = nsof_hstage_reserve(ctx, 2 * sz))) return rc;
-    uint8_t* hA = (uint8_t*)ctx->hstage;
+    if ((rc = ctx->stage.reserve(ctx, 2 * sz))) return rc;
+    if ((rc = ctx->hstage.reserve(ctx, 2 * sz))) return rc;
+    uint8_t* hA = (uint8_t*)ctx->hstage.p;
     uint8_t* hB = hA + sz;
     for (int y = 0; y < height; y++) {
         const uint8_t* ra = a + (ptrdiff_t)y * a_stride;
@@ -441,8 +441,8 @@ extern "C" int nsof_ssim_u8(nsof_ctx* ctx, const uint8_t* a, ptrdiff_t a_stride,
             hB[(size_t)y * width + x] = rb[(ptrdiff_t)x * b_pixel_step];
         }
     }
-    NSOF_HIP(ctx, hipMemcpyAsync(ctx->stage, hA, 2 * sz, hipMemcpyHostToDevice, ctx->stream));
-    return nsof_ssim_u8_dev(ctx, (const uint8_t*)ctx->stage, width, 1, (const uint8_t*)ctx->stage + sz, width, 1, width,
+    NSOF_HIP(ctx, hipMemcpyAsync(ctx->stage.p, hA, 2 * sz, hipMemcpyHostToDevice, ctx->stream));
+    return nsof_ssim_u8_dev(ctx, (const uint8_t*)ctx->stage.p, width, 1, (const uint8_t*)ctx->stage.p + sz, width, 1, width,
                             height, data_range, ssim_out);
 }
 
@@ -501,9 +501,9 @@ extern "C" int nsof_ssim_u8_batch_dev(nsof_ctx* ctx, int n, const uint8_t* d_a, 
     const int ow = width - 2 * PAD, oh = height - 2 * PAD;
     const dim3 grid((ow + SX - 1) / SX, (oh + SY - 1) / SY, n);
     const int nblk = grid.x * grid.y;   // same tile grid and reduction order per pair as nsof_ssim_u8_dev
-    int rc = nsof_ws_reserve(ctx, &ctx->tmp, &ctx->tmp_bytes, (size_t)n * nblk * sizeof(double));
+    int rc = ctx->tmp.reserve(ctx, (size_t)n * nblk * sizeof(double));
     if (rc) return rc;
-    double* partial = (double*)ctx->tmp;
+    double* partial = (double*)ctx->tmp.p;
     const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
     {
         nsof_prof_scope ps(ctx, NSOF_K_SSIM);

@@ -83,16 +83,19 @@ def test_chunked_stepping_equals_one_shot(nsof_lib, ctx):
     from nsof.accumulator import Accumulator, slice_index_array
     idx = slice_index_array(d["t"], 1000)
     every = max(1, (len(idx) - 1) // 100)
-    acc = Accumulator(H, W, 2, "split", -6.0, 0.0, ctx=ctx)
-    for lo in range(0, len(idx) - 1, 37):
-        acc.step(d["x"], d["y"], d["p"], d["t"], idx[lo:lo + 38], snap_every=every)
-    wa, wb = acc.w(0), acc.w(1)
-    snaps = acc.snapshots()
-    acc.close()
     one = nsof_lib.simulate((d["x"], d["y"], d["p"], d["t"]), version=2, slice_us=1000, active_v=-6.0, silent_v=0.0,
                             polarity="split", sensor_size=(H, W), ctx=ctx)
-    assert np.array_equal(wa, one["w_final"]) and np.array_equal(wb, one["w_final_b"])
-    assert np.array_equal(snaps[0], one["resistances"]) and np.array_equal(snaps[1], one["resistances_b"])
+    n = len(idx) - 1
+    # steps of 37 slices; then steps of 1, 3 and the rest: the event staging grows while it holds the earlier steps' data
+    for cuts in (list(range(0, n, 37)) + [n], [0, 1, 4, n]):
+        acc = Accumulator(H, W, 2, "split", -6.0, 0.0, ctx=ctx)
+        for lo, hi in zip(cuts, cuts[1:]):
+            acc.step(d["x"], d["y"], d["p"], d["t"], idx[lo:hi + 1], snap_every=every)
+        wa, wb = acc.w(0), acc.w(1)
+        snaps = acc.snapshots()
+        acc.close()
+        assert np.array_equal(wa, one["w_final"]) and np.array_equal(wb, one["w_final_b"]), cuts[:4]
+        assert np.array_equal(snaps[0], one["resistances"]) and np.array_equal(snaps[1], one["resistances_b"]), cuts[:4]
 
 
 def test_large_sensor_many_slices_vs_oracle(nsof_lib, ctx, oracle):

@@ -219,6 +219,21 @@ def test_crowded_paste_later_rectangle_wins(nsof_lib, ctx, oracle):
         assert n_calls == len(table)
         got = flows[0].cpu().numpy()
         assert np.array_equal(got, want), (call, _diff(got, want))
+    # a fresh context: a table of two crops (one paste), then the whole table -- its work-list and paste tables and the
+    # private flow buffers grow while they hold the earlier call's data
+    fresh = nsof_lib.Context(0)
+    try:
+        for n in (2, len(table)):
+            d_counts = torch.tensor([n, 0], dtype=torch.int32, device=dev)
+            flows = torch.full((1, H, W, 2), 7.0, dtype=torch.float32, device=dev)
+            torch.cuda.synchronize()
+            n_calls, _ = nsof_lib.farneback_roi_sequence_dev(d_frames, d_counts, d_rects, flows, params, gate_frame=0, ctx=fresh)
+            fresh.synchronize()
+            assert n_calls == n
+        got = flows[0].cpu().numpy()
+        assert np.array_equal(got, want), _diff(got, want)
+    finally:
+        fresh.close()
 
 
 @pytest.mark.parametrize("exact", [1, 0])

@@ -98,16 +98,21 @@ def test_host_pairs_equal_lone_calls(nsof_lib, ctx, pyr_fma, exact, name, dtype)
 
 
 def test_route_small_batch_and_job_tables(nsof_lib, ctx):
-    """A short list takes the small-batch form (exact_lat); 40 crops of 200 columns (80 strip jobs) k_iterate_x's tables."""
+    """A short list takes the small-batch form (exact_lat); 40 crops of 200 columns (80 strip jobs) k_iterate_x's tables.
+    Both lists on a fresh context: its work-list tables and pipeline slots grow from the short list's to the long one's."""
     from nsof.farneback import farneback_pairs
     p = PARAM_SETS["A"]
     a, b = _frames(5, np.dtype("uint16"))
     small = [(a[0:30, 0:50], b[0:30, 0:50]), (a[7:60, 9:70], b[7:60, 9:70])]
-    _check_list(nsof_lib, ctx, small, farneback_pairs(small, p, ctx=ctx), p)
     big = [(a[y:y + 40 + y % 7, x:x + 200], b[y:y + 40 + y % 7, x:x + 200]) for y in range(0, 80, 10)
            for x in (0, 1, 50, 103, 204)]
     assert sum((q[0].shape[1] + 191) // 192 for q in big) > 64
-    _check_list(nsof_lib, ctx, big, farneback_pairs(big, p, ctx=ctx), p)
+    fresh = nsof_lib.Context(0)
+    try:
+        _check_list(nsof_lib, ctx, small, farneback_pairs(small, p, ctx=fresh), p)
+        _check_list(nsof_lib, ctx, big, farneback_pairs(big, p, ctx=fresh), p)
+    finally:
+        fresh.close()
 
 
 def test_route_uniform_fallback_chunks(nsof_lib, ctx, monkeypatch):

@@ -179,6 +179,15 @@ def test_mask_sequence_many_overlapping_boxes_and_long_reach(nsof_lib, ctx, orac
     got = segment.motion_mask_sequence_dev(flows, boxes, ctx=ctx)
     ctx.synchronize()
     assert np.array_equal(got.cpu().numpy(), _per_box(nsof_lib, ctx, flows, boxes))
+    # a fresh context: one box, then the 302 -- its box / job table grows while it holds the earlier call's data
+    fresh = nsof_lib.Context(0)
+    try:
+        segment.motion_mask_sequence_dev(flows, [[(7, 9, 150, 111)], [], []], ctx=fresh)
+        again = segment.motion_mask_sequence_dev(flows, boxes, ctx=fresh)
+        fresh.synchronize()
+        assert np.array_equal(again.cpu().numpy(), got.cpu().numpy())
+    finally:
+        fresh.close()
     # ksize 31: the element's reach splits the chain into several launches
     got = segment.motion_mask_sequence_dev(flows, boxes[1:] + [[(3, 2, 190, 118), (50, 40, 90, 80)]], ksize=31,
                                            iterations=3, ctx=ctx)
