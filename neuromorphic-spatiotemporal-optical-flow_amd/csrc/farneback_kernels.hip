@@ -43,8 +43,12 @@ __device__ __forceinline__ int reflect101(int p, int len)
     return p;
 }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// cvFloor(float) as its x86-64 build returns it for every float: NaN and
+// v >= 2^31 give INT_MIN, v < -2^31 (-inf included) INT_MAX.  A bare (int)v would give 0 for NaN here (v_cvt_i32_f32),
+// which sends a NaN flow into the bilinear sample instead of the out-of-image branch.
 __device__ __forceinline__ int floor_f(float v)
 {
+    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return v < 0.f ? 2147483647 : -2147483647 - 1;
     int i = (int)v;
     return i - (i > v);
 }

@@ -16,6 +16,14 @@
 // flip and the negations inside atan2 are sign-bit flips, np.clip(x, 0, c) keeps -0.0 (only x < 0 becomes +0.0), and
 // the division keeps the sign of a zero, so atan2(+-0, negative) lands on wheel entry 54 or 0 as on the host.
 //
+// Non-finite flows, where the NumPy coding has no answer (np.max propagates a NaN into every pixel's divisor, and a NaN
+// wheel position cannot index the wheel), are defined here instead:
+//   * the divisor is the largest magnitude over the pixels whose magnitude is not NaN (fmaxf skips NaN), + 1e-5;
+//     an infinite component makes it +inf, and every finite component then codes as 0;
+//   * a pixel whose normalised u or v is NaN (a NaN flow, or an infinite one over an infinite divisor) is (0, 0, 0),
+//     a colour no finite flow produces: one wheel channel is always 255 inside the unit circle and 191 outside;
+//   * an infinite normalised component (a finite divisor from max_flow) is an ordinary pixel outside the unit circle:
+//     atan2 of infinities is finite, so it gets the wheel colour of its direction times 0.75, as in NumPy.
 // Thread layout of both kernels: a wave covers 256 consecutive pixels of a row (4 per lane), a workgroup 4 waves, each
 // wave RPW rows; blockIdx.z = item.  V4: every row starts 16-byte aligned, so a lane's 4 pixels are two float4 loads.
 #include <cmath>
@@ -128,11 +136,15 @@ __global__ __launch_bounds__(256) void k_flowviz_max(const float* __restrict__ f
 // then 1 - rad * (1 - col) inside the unit circle or col * 0.75 outside, then floor(255 * col).
 __device__ __forceinline__ void color_px(float u, float v, uint8_t (&o)[3])
 {
+    if (u != u || v != v) {   // NaN: no wheel position (see the header); black marks the pixel
+        o[0] = o[1] = o[2] = 0;
+        return;
+    }
     const float rad = mag(u, v);
     const float a = (float)atan2(-(double)v, -(double)u);
     const float pos = __fmul_rn(__fdiv_rn(__fadd_rn(__fdiv_rn(a, PI_F), 1.f), 2.f), (float)(NCOLS - 1));
     int lo = (int)floorf(pos);
-    lo = min(max(lo, 0), NCOLS - 1);   // pos is in [0, 54] for finite input; the clamp keeps any index in the table
+    lo = min(max(lo, 0), NCOLS - 1);   // pos is in [0, 54] for non-NaN input; the clamp keeps any index in the table
     const int hi = lo + 1 == NCOLS ? 0 : lo + 1;
     const double frac = (double)pos - (double)lo;
     const bool small = rad <= 1.f;

@@ -44,9 +44,11 @@ __device__ __forceinline__ void remap_px(const uint8_t* __restrict__ src, ptrdif
         mx = m.a[(ptrdiff_t)y * m.astride + x];
         my = m.b[(ptrdiff_t)y * m.bstride + x];
     }
-    // cvRound(v * 32): the product is exact, rintf rounds half to even; saturate like the float -> int conversion
-    const int lx = (int)fminf(fmaxf(rintf(mx * 32.0f), -2147483648.0f), 2147483520.0f);
-    const int ly = (int)fminf(fmaxf(rintf(my * 32.0f), -2147483648.0f), 2147483520.0f);
+    // cvRound(v * 32) as x86 cv2 computes it (cvtss2si): rintf rounds half to even; NaN, +-inf and results outside
+    // the int range give INT_MIN, which puts the sample far left / above the source
+    const float rx = rintf(mx * 32.0f), ry = rintf(my * 32.0f);
+    const int lx = rx >= -2147483648.0f && rx < 2147483648.0f ? (int)rx : -2147483647 - 1;
+    const int ly = ry >= -2147483648.0f && ry < 2147483648.0f ? (int)ry : -2147483647 - 1;
     const int fx = lx & 31, fy = ly & 31;
     const int ix = clampi(lx >> 5, -32768, 32767), iy = clampi(ly >> 5, -32768, 32767);
     const int w0 = (32 - fx) * (32 - fy) * 32, w1 = fx * (32 - fy) * 32, w2 = (32 - fx) * fy * 32, w3 = fx * fy * 32;

@@ -29,6 +29,7 @@
  */
 #include <math.h>
 #include <float.h>
+#include <limits.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -44,9 +45,13 @@
 /* cvRound on x86-64 = cvtsd2si = round-half-to-even in the default rounding mode. */
 static int cv_round(double v) { return (int)lrint(v); }
 
-/* cvFloor(float): int i = (int)value; return i - (i > value); */
+/* cvFloor(float): int i = (int)value; return i - (i > value); -- for every float, as the x86-64 build of it returns:
+ * the truncating conversion gives INT_MIN for NaN and for values outside the int range, and the correction then
+ * wraps INT_MIN - 1 to INT_MAX for values below it.  Stated without the undefined conversion: NaN and v >= 2^31 give
+ * INT_MIN, v < -2^31 (-inf included) gives INT_MAX.  The device's floor_f returns the same. */
 static int cv_floor_f(float v)
 {
+    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return v < 0 ? INT_MAX : INT_MIN;
     int i = (int)v;
     return i - (i > v);
 }

@@ -10,6 +10,8 @@
  * cv2.remap lives in opencv-python (requirements.txt:1), absent here; restated from the published algorithm of
  * imgproc's remap for 8-bit sources and CV_32FC1 maps with INTER_LINEAR:
  *   sx = cvRound(map_x * 32), sy likewise (round half to even); integer part sx >> 5 saturated to int16,
+ *     where cvRound is x86 cv2's (cvtss2si): NaN, +-inf and products outside the int range give INT_MIN, so the
+ *     sample lands at (-32768, ...) -- left of / above the source -- whatever the sign of the overflow;
  *   fraction sx & 31; weights ((32-fx)(32-fy), fx(32-fy), (32-fx)fy, fx fy) * 32 (sum 2^15);
  *   dst = (v0 w0 + v1 w1 + v2 w2 + v3 w3 + 2^14) >> 15;
  *   taps outside the source: BORDER_REPLICATE clamps the tap coordinates, BORDER_CONSTANT (cv2's default, value 0)
@@ -22,12 +24,20 @@
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this.
  */
+#include <limits.h>
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+/* cvRound(float) of an x86-64 cv2 build: round half to even, INT_MIN for NaN, +-inf and out-of-range results. */
+static inline int cv_round_f(float v)
+{
+    float r = rintf(v);
+    return r >= -2147483648.0f && r < 2147483648.0f ? (int)r : INT_MIN;
+}
 
 /* border: 0 = BORDER_CONSTANT with value cval, 1 = BORDER_REPLICATE.  src: [sh][sstride] bytes, `cn` interleaved
  * channels; maps [dh][mstride] floats; dst [dh][dstride] bytes, cn interleaved channels. */
@@ -38,9 +48,9 @@ int nsof_ref_remap_linear_u8(const uint8_t* src, ptrdiff_t sstride, int sw, int 
     if (sw < 1 || sh < 1 || cn < 1 || dw < 0 || dh < 0 || (border != 0 && border != 1)) return -1;
     for (int y = 0; y < dh; y++)
         for (int x = 0; x < dw; x++) {
-            long lx = lrintf(mapx[y * mstride + x] * 32.0f), ly = lrintf(mapy[y * mstride + x] * 32.0f);
-            int fx = (int)(lx & 31), fy = (int)(ly & 31);
-            int ix = clampi((int)(lx >> 5), -32768, 32767), iy = clampi((int)(ly >> 5), -32768, 32767);
+            int lx = cv_round_f(mapx[y * mstride + x] * 32.0f), ly = cv_round_f(mapy[y * mstride + x] * 32.0f);
+            int fx = lx & 31, fy = ly & 31;
+            int ix = clampi(lx >> 5, -32768, 32767), iy = clampi(ly >> 5, -32768, 32767);
             int w0 = (32 - fx) * (32 - fy) * 32, w1 = fx * (32 - fy) * 32, w2 = (32 - fx) * fy * 32, w3 = fx * fy * 32;
             for (int c = 0; c < cn; c++) {
                 int v0, v1, v2, v3;
