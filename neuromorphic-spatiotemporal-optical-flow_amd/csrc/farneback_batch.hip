@@ -189,15 +189,12 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
 
     // Items the work-list kernels cover: fused iteration available (window 2..15, >= 1 iteration, at least 2x2 px), and
     // at most 255 strips wide (a job of k_iterate_x's table names its strip in 8 bits); wider items run on their own.
-    const bool het_params = p.iterations >= 1 && p.winsize / 2 >= 1 && p.winsize / 2 <= 7;
-    const bool exact = ctx->opt_exact_rowsums != 0;
+    auto het_params = [&](const nsof_pair_desc& d) {
+        return p.iterations >= 1 && nsof_iterate_supported(p.winsize, d.width, d.height) &&
+               (d.width + NSOF_X_STRIP - 1) / NSOF_X_STRIP <= 255;
+    };
     std::vector<int> het, rest;
-    for (int i = 0; i < n; i++)
-        (het_params && nsof_iterate_supported(p.winsize, descs[i].width, descs[i].height) &&
-                 (descs[i].width + NSOF_X_STRIP - 1) / NSOF_X_STRIP <= 255
-             ? het
-             : rest)
-            .push_back(i);
+    for (int i = 0; i < n; i++) (het_params(descs[i]) ? het : rest).push_back(i);
 
     if (!het.empty()) {
         const int nh = (int)het.size();
@@ -211,14 +208,12 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
             Li[j] = nsof_farneback_effective_levels(descs[het[j]].width, descs[het[j]].height, p.pyr_scale, p.levels);
             Lmax = std::max(Lmax, Li[j]);
         }
-        // a list too small to fill the chip with (strip, item) jobs: the three-kernel small-batch form of the same order
+        // every item takes a fused form (any of them stands for the list's shape); a list too small to fill the chip
+        // with (strip, item) jobs takes the small-batch form of the exact order
         long long jobs = 0;
-        for (int j = 0; j < nh; j++) {
-            jobs += (descs[het[j]].width + 191) / 192;
-            if ((unsigned long long)descs[het[j]].width * descs[het[j]].height * 40ull >= (1ull << 32)) jobs = 1ll << 40;   // 32-bit offsets per item
-        }
-        const bool exact_lat = exact && jobs <= ctx->opt_small_batch_jobs;
-        const bool use_xj = exact && !exact_lat;   // k_iterate_x runs the list: it needs its job tables
+        for (int j = 0; j < nh; j++) jobs += nsof_iterate_jobs(descs[het[j]].width, descs[het[j]].height);
+        const nsof_iter_form form = nsof_iterate_form(ctx, p.winsize, descs[het[0]].width, descs[het[0]].height, p.iterations, jobs);
+        const bool use_xj = form == NSOF_ITER_EXACT;   // k_iterate_x runs the list: it needs its job tables
         // Per level: the item table (sorted into size classes), then the fused kernel's job table (8 counts + 8 lists).
         long long strips0 = 0;   // strips of the full-resolution level = the most any level has
         for (int j = 0; j < nh; j++) strips0 += (descs[het[j]].width + NSOF_X_STRIP - 1) / NSOF_X_STRIP;
@@ -288,8 +283,9 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
 
         // workspace: level images, expansions, two flow buffers (every level uses their leading part)
         const size_t szI = align_up(maxI * 4, 256), szR = align_up(maxR * 4, 256), szF = align_up(maxF * 8, 256);
-        const size_t szV = exact_lat ? szR : 0;   // column sums, 5 doubles per pixel = the expansion's footprint
-        const size_t szM = exact_lat ? align_up(szR / 2, 256) : 0;        // matrices of the small-batch form, 5 floats per pixel
+        const bool lat = form == NSOF_ITER_EXACT_LAT;
+        const size_t szV = lat ? szR : 0;                        // column sums, 5 doubles per pixel = the expansion's footprint
+        const size_t szM = lat ? align_up(szR / 2, 256) : 0;     // matrices of the small-batch form, 5 floats per pixel
         if ((rc = ctx->ws.reserve(ctx, szI + szR + 2 * szF + szV + szM))) return rc;
         char* base = (char*)ctx->ws.p;
         float* dI = (float*)base;
@@ -321,10 +317,10 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
             cur ^= 1;
             for (int it = 0; it < p.iterations; it++) {
                 const bool final = k == 0 && it == p.iterations - 1;
-                if (exact_lat)
+                if (lat)
                     rc = nsof_launch_iterate_lat_het(ctx, nk_items, dt, max_w[k], max_h[k], dR, fb[cur], fb[cur ^ 1], final, p.winsize,
                                                      dM, dV);
-                else if (exact)
+                else if (use_xj)
                     rc = nsof_launch_iterate_x_het(ctx, nk_items, dt, max_w[k], max_h[k], dR, szR / 4, fb[cur], fb[cur ^ 1], final,
                                                    p.winsize, d_xj + xj_at[k], xj_stride[k], xj_jobs[k]);
                 else

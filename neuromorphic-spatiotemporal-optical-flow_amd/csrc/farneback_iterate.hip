@@ -193,11 +193,7 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][QGeom<MH>::COL
 #pragma unroll
                     for (int c = 0; c < 5; c++) g[c] += at(c, p + 2 * MH) - at(c, p - 1);
                 }
-                const double g11 = g[0] * scale, g12 = g[1] * scale, g22 = g[2] * scale;
-                const double h1 = g[3] * scale, h2 = g[4] * scale;
-                const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
-                o[p].x = (float)((g11 * h2 - g12 * h1) * idet);
-                o[p].y = (float)((g22 * h1 - g12 * h2) * idet);
+                o[p] = nsof_flow_solve(g[0], g[1], g[2], g[3], g[4], scale);
             }
             float2* dst = Fout + (size_t)yo * fpitch + xo;
             if (xo + 3 < W && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
@@ -332,12 +328,6 @@ int launch_iterate_q_het(nsof_ctx* ctx, int n_items, const nsof_het_item* items,
 }
 
 }  // namespace
-
-bool nsof_iterate_supported(int winsize, int W, int H)
-{
-    const int m = winsize / 2;
-    return m >= 1 && m <= 7 && W >= 2 && H >= 2;   // the clamped gather needs a 2x2 neighbourhood to exist
-}
 
 template <typename... A>
 static int launch_iterate_q_m(int m, A... a)

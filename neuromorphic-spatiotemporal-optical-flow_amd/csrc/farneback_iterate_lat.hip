@@ -5,10 +5,10 @@
 // library's summation order is sequential along y (column sums) and along x (row sums) -- but only THOSE recurrences
 // are: one double addition per row / column.  So for a batch too small to fill the chip the iteration is split into
 // three kernels, each as wide as its step allows, with the intermediates in HBM (they stay in the 256 MB MALL):
-//   k_lat_matrices   thread <-> pixel           FarnebackUpdateMatrices                                  M [5][h][w] f32
-//   k_lat_colsum     thread <-> (column, plane) the library's running column sums, top down (8 waves in turn) V [h][5][w] f64
-//   k_lat_rowscan    thread <-> (row, plane)    the library's running row sums, pipelined with the 2x2 solve of the
-//                                               previous 32-column tile
+//   k_update_matrices  thread <-> pixel           FarnebackUpdateMatrices                                  M [5][h][w] f32
+//   k_lat_colsum       thread <-> (column, plane) the library's running column sums, top down (8 waves in turn) V [h][5][w] f64
+//   k_lat_rowscan      thread <-> (row, plane)    the library's running row sums, pipelined with the 2x2 solve of the
+//                                                 previous 32-column tile
 // Same arithmetic, same order, same bits as k_iterate_x (upstream FarnebackUpdateFlow_Blur, optflowgf.cpp); 120 B/px of
 // extra HBM traffic (M and V written and read once each), which is why large batches keep the fused kernel.  Measured: a
 // lone 1920x1080 call 3.9 -> 1.2 ms host to host, cross-over with the fused kernel at 70-80 (strip, image) jobs.
@@ -21,8 +21,9 @@
 
 namespace {
 
+// FarnebackUpdateMatrices, thread <-> pixel: also the first kernel of the unfused iteration (nsof_launch_update_matrices).
 template <bool HET>
-__global__ __launch_bounds__(256) void k_lat_matrices(const float* __restrict__ R0b, const float* __restrict__ R1b,
+__global__ __launch_bounds__(256) void k_update_matrices(const float* __restrict__ R0b, const float* __restrict__ R1b,
                                                        size_t pair_stride, const float* __restrict__ flow_in, int W, int H,
                                                        float* __restrict__ M, const nsof_het_item* __restrict__ items)
 {
@@ -47,8 +48,19 @@ __global__ __launch_bounds__(256) void k_lat_matrices(const float* __restrict__ 
     const size_t plane = (size_t)W * H;
     const Planes R0 = planes_of(R0b, plane), R1 = planes_of(R1b, plane);
     const size_t pix = (size_t)y * W + x;
+    const float2 d = reinterpret_cast<const float2*>(flow_in)[pix];
     RowIn in;
-    issue_row(in, R0, R1, W, H, x, y, reinterpret_cast<const float2*>(flow_in)[pix]);
+    if (!HET && (W < 2 || H < 2)) {
+        // a frame of one row or one column (the unfused route, the stage entry): no sample falls inside it and there is
+        // no 2x2 block for issue_row's clamped gather, so only R0 is read
+        in.z = *reinterpret_cast<const float4*>(R0.q4 + pix * 16);
+        in.z4 = *reinterpret_cast<const float*>(R0.c4 + pix * 4);
+        in.dx = d.x;
+        in.dy = d.y;
+        in.inside = 0;
+    } else {
+        issue_row(in, R0, R1, W, H, x, y, d);
+    }
     float m5[5];
     matrix_from(in, x, y, W, H, m5);
 #pragma unroll
@@ -325,18 +337,21 @@ __global__ __launch_bounds__(LRGeom<LR_ROWS>::THREADS) void k_lat_rowscan(const 
         } else if (s > 0) {
             const int x = (s - 1) * LR_TW + sj, y = y0 + sr;
             const double* sp = St + ((s - 1) & 1) * 5 * LR_SPLANE + sr * LR_JSTR + sj;
-            const double g11 = sp[0] * scale, g12 = sp[LR_SPLANE] * scale, g22 = sp[2 * LR_SPLANE] * scale;
-            const double h1 = sp[3 * LR_SPLANE] * scale, h2 = sp[4 * LR_SPLANE] * scale;
-            if (x < W && y < H) {
-                const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
+            if (x < W && y < H)
                 Fout[(size_t)y * fpitch + x] =
-                    make_float2((float)((g11 * h2 - g12 * h1) * idet), (float)((g22 * h1 - g12 * h2) * idet));
-            }
+                    nsof_flow_solve(sp[0], sp[LR_SPLANE], sp[2 * LR_SPLANE], sp[3 * LR_SPLANE], sp[4 * LR_SPLANE], scale);
         }
         __syncthreads();
     };
     // step T only solves the last tile (its chain / ring work is harmless); unrolled by the prefetch depth (register sets)
     for (int s = 0; s <= T; s += LR_DEPTH) lr_steps(step, s, T, std::make_integer_sequence<int, LR_DEPTH>{});
+}
+
+void launch_update_matrices(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
+                            const float* flow_in, int W, int H, float* M)
+{
+    hipLaunchKernelGGL(k_update_matrices<false>, dim3((W + 63) / 64, (H + 3) / 4, n_pairs), dim3(256), 0, ctx->stream, R0, R1,
+                       pair_stride, flow_in, W, H, M, nullptr);
 }
 
 template <int MH, int ROWS>
@@ -375,6 +390,15 @@ int lat_rowscan(nsof_ctx* ctx, int n, int W, int H, int max_h, const double* V, 
 
 }  // namespace
 
+int nsof_launch_update_matrices(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
+                                const float* flow, int W, int H, float* M)
+{
+    nsof_prof_scope ps(ctx, NSOF_K_UPDMAT);
+    launch_update_matrices(ctx, n_pairs, R0, R1, pair_stride, flow, W, H, M);
+    NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
+}
+
 // M: 5 floats per pixel, V: 5 doubles per pixel (per pair; work list: at offR / 2 of each item).
 int nsof_launch_iterate_lat(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
                             const float* flow_in, float* flow_out, int W, int H, int winsize, float* M, double* V)
@@ -384,8 +408,7 @@ int nsof_launch_iterate_lat(nsof_ctx* ctx, int n_pairs, const float* R0, const f
     if (int rc = nsof_xsync_reserve(ctx, 0, &carry_unused, &tickets_unused, &err)) return rc;
     {
         nsof_prof_scope ps(ctx, NSOF_K_ITERATE);
-        hipLaunchKernelGGL(k_lat_matrices<false>, dim3((W + 63) / 64, (H + 3) / 4, n_pairs), dim3(256), 0, ctx->stream, R0, R1,
-                           pair_stride, flow_in, W, H, M, nullptr);
+        launch_update_matrices(ctx, n_pairs, R0, R1, pair_stride, flow_in, W, H, M);
         hipLaunchKernelGGL(k_lat_colsum<false>, dim3((W + 63) / 64, 5, n_pairs), dim3(64 * LC_WAVES), 0, ctx->stream, (const float*)M, W, H,
                            winsize / 2, V, nullptr, err, ctx->dbg_fault);
     }
@@ -400,7 +423,7 @@ int nsof_launch_iterate_lat_het(nsof_ctx* ctx, int n_items, const nsof_het_item*
     if (int rc = nsof_xsync_reserve(ctx, 0, &carry_unused, &tickets_unused, &err)) return rc;
     {
         nsof_prof_scope ps(ctx, NSOF_K_ITERATE);
-        hipLaunchKernelGGL(k_lat_matrices<true>, dim3((max_w + 63) / 64, (max_h + 3) / 4, n_items), dim3(256), 0, ctx->stream, R, R,
+        hipLaunchKernelGGL(k_update_matrices<true>, dim3((max_w + 63) / 64, (max_h + 3) / 4, n_items), dim3(256), 0, ctx->stream, R, R,
                            (size_t)0, flow_in, 0, 0, M, d_items);
         hipLaunchKernelGGL(k_lat_colsum<true>, dim3((max_w + 63) / 64, 5, n_items), dim3(64 * LC_WAVES), 0, ctx->stream, (const float*)M, 0, 0,
                            winsize / 2, V, d_items, err, ctx->dbg_fault);

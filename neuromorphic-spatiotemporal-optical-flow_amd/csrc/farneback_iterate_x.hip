@@ -228,11 +228,8 @@ __device__ __forceinline__ void x_solve_rows(const double* sv, volatile lds_int*
 #pragma unroll
         for (int q = 0; q < NQ; q++) {
             const int yo = 4 * us[b] + q + Q0;
-            const double g11 = g[b][q][0] * scale, g12 = g[b][q][1] * scale, g22 = g[b][q][2] * scale;
-            const double h1 = g[b][q][3] * scale, h2 = g[b][q][4] * scale;
-            const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
-            const float ox = (float)((g11 * h2 - g12 * h1) * idet), oy = (float)((g22 * h1 - g12 * h2) * idet);
-            if (yo < H) nsof_store_stream2(reinterpret_cast<float*>(Fout + (size_t)yo * fpitch + x), ox, oy);
+            const float2 o = nsof_flow_solve(g[b][q][0], g[b][q][1], g[b][q][2], g[b][q][3], g[b][q][4], scale);
+            if (yo < H) nsof_store_stream2(reinterpret_cast<float*>(Fout + (size_t)yo * fpitch + x), o.x, o.y);
         }
     }
 }
@@ -434,12 +431,9 @@ __device__ __forceinline__ void x_consumer_loop(const XRing& ring, double* sv, d
 #pragma unroll
             for (int q = 0; q < G::CQ; q++) {
                 const int yo = 4 * u + q;
-                const double g11 = svj[(q * 5 + 0) * SVW] * scale, g12 = svj[(q * 5 + 1) * SVW] * scale;
-                const double g22 = svj[(q * 5 + 2) * SVW] * scale;
-                const double h1 = svj[(q * 5 + 3) * SVW] * scale, h2 = svj[(q * 5 + 4) * SVW] * scale;
-                const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
-                const float ox = (float)((g11 * h2 - g12 * h1) * idet), oy = (float)((g22 * h1 - g12 * h2) * idet);
-                if (yo < H) nsof_store_stream2(reinterpret_cast<float*>(Fout + (size_t)yo * fpitch + x), ox, oy);
+                const double* s = svj + q * 5 * SVW;
+                const float2 o = nsof_flow_solve(s[0], s[SVW], s[2 * SVW], s[3 * SVW], s[4 * SVW], scale);
+                if (yo < H) nsof_store_stream2(reinterpret_cast<float*>(Fout + (size_t)yo * fpitch + x), o.x, o.y);
             }
         }
         if (t == nimg + 1) return;
@@ -790,12 +784,6 @@ int launch_x(nsof_ctx* ctx, int n, int max_w, int max_h, const float* R0, const 
 }
 
 }  // namespace
-
-bool nsof_iterate_x_supported(int winsize, int W, int H)
-{
-    const int m = winsize / 2;
-    return m >= 1 && m <= 7 && W >= 2 && H >= 2;
-}
 
 #define NSOF_X_SWITCH(HETV, ...)                                                                     \
     switch (winsize / 2) {                                                                           \

@@ -42,16 +42,6 @@ __device__ __forceinline__ int reflect101(int p, int len)
     } while ((unsigned)p >= (unsigned)len);
     return p;
 }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// cvFloor(float) as its x86-64 build returns it for every float: NaN and
-// v >= 2^31 give INT_MIN, v < -2^31 (-inf included) INT_MAX.  A bare (int)v would give 0 for NaN here (v_cvt_i32_f32),
-// which sends a NaN flow into the bilinear sample instead of the out-of-image branch.
-__device__ __forceinline__ int floor_f(float v)
-{
-    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return v < 0.f ? 2147483647 : -2147483647 - 1;
-    int i = (int)v;
-    return i - (i > v);
-}
 
 // resize(INTER_LINEAR) coordinate: f = (float)((d+0.5)*scale-0.5); s = floor(f); a = f-s.
 __device__ __forceinline__ void lin_coord_x(int d, double scale, int slen, int& s, float& a)
@@ -1392,68 +1382,6 @@ __global__ __launch_bounds__(512, N <= 7 ? 8 : 1) void k_polyexp_rs(const float*
 }
 
 // ---------------------------------------------------------------------------------------
-// FarnebackUpdateMatrices: one thread per pixel.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_update_matrices(const float* __restrict__ R0b, const float* __restrict__ R1b,
-                                                          size_t pair_stride, const float* __restrict__ flow,
-                                                          int W, int H, float* __restrict__ M)
-{
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    const size_t plane = (size_t)W * H;
-    const float* R0 = R0b + (size_t)blockIdx.z * pair_stride;
-    const float* R1 = R1b + (size_t)blockIdx.z * pair_stride;
-    const size_t pix = (size_t)y * W + x;
-    const float2 d = reinterpret_cast<const float2*>(flow)[(size_t)blockIdx.z * plane + pix];
-    const float dx = d.x, dy = d.y;
-    float fx = x + dx, fy = y + dy;
-    const int x1 = floor_f(fx), y1 = floor_f(fy);
-    fx -= x1;
-    fy -= y1;
-    float r2, r3, r4, r5, r6;
-    if ((unsigned)x1 < (unsigned)(W - 1) && (unsigned)y1 < (unsigned)(H - 1)) {
-        const float a00 = (1.f - fx) * (1.f - fy), a01 = fx * (1.f - fy), a10 = (1.f - fx) * fy, a11 = fx * fy;
-        const float4* q = reinterpret_cast<const float4*>(R1) + (size_t)y1 * W + x1;
-        const float* c4 = R1 + 4 * plane + (size_t)y1 * W + x1;
-        const float4 t0 = q[0], t1 = q[1], b0 = q[W], b1 = q[W + 1];
-        r2 = a00 * t0.x + a01 * t1.x + a10 * b0.x + a11 * b1.x;
-        r3 = a00 * t0.y + a01 * t1.y + a10 * b0.y + a11 * b1.y;
-        r4 = a00 * t0.z + a01 * t1.z + a10 * b0.z + a11 * b1.z;
-        r5 = a00 * t0.w + a01 * t1.w + a10 * b0.w + a11 * b1.w;
-        r6 = a00 * c4[0] + a01 * c4[1] + a10 * c4[W] + a11 * c4[W + 1];
-        const float4 z = reinterpret_cast<const float4*>(R0)[pix];
-        r4 = (z.z + r4) * 0.5f;
-        r5 = (z.w + r5) * 0.5f;
-        r6 = (R0[4 * plane + pix] + r6) * 0.25f;
-        r2 = (z.x - r2) * 0.5f;
-        r3 = (z.y - r3) * 0.5f;
-    } else {
-        const float4 z = reinterpret_cast<const float4*>(R0)[pix];
-        r4 = z.z;
-        r5 = z.w;
-        r6 = R0[4 * plane + pix] * 0.5f;
-        r2 = (z.x - 0.f) * 0.5f;
-        r3 = (z.y - 0.f) * 0.5f;
-    }
-    r2 += r4 * dy + r6 * dx;
-    r3 += r6 * dy + r5 * dx;
-    if ((unsigned)(x - 5) >= (unsigned)(W - 10) || (unsigned)(y - 5) >= (unsigned)(H - 10)) {
-        const float border[5] = {0.14f, 0.14f, 0.4472f, 0.4472f, 0.4472f};
-        auto bw = [&](int i) { return i == 0 || i == 1 ? border[0] : border[2]; };
-        const float scale = (x < 5 ? bw(x) : 1.f) * (x >= W - 5 ? bw(W - x - 1) : 1.f) * (y < 5 ? bw(y) : 1.f) *
-                            (y >= H - 5 ? bw(H - y - 1) : 1.f);
-        r2 *= scale; r3 *= scale; r4 *= scale; r5 *= scale; r6 *= scale;
-    }
-    float* Mz = M + (size_t)blockIdx.z * 5 * plane + pix;
-    Mz[0] = r4 * r4 + r6 * r6;
-    Mz[plane] = (r4 + r5) * r6;
-    Mz[2 * plane] = r5 * r5 + r6 * r6;
-    Mz[3 * plane] = r4 * r2 + r6 * r3;
-    Mz[4 * plane] = r6 * r2 + r5 * r3;
-}
-
-// ---------------------------------------------------------------------------------------
 // FarnebackUpdateFlow_Blur: (2m+1)^2 box sums of the 5 planes of M + per-pixel 2x2 solve.
 //
 // Strip walker over the full image height (the column sums are a running sum from row 0:
@@ -1527,11 +1455,7 @@ __global__ __launch_bounds__(256) void k_blur_solve(const float* __restrict__ M,
                     for (int c = 0; c < 5; c++)
                         g[c] += sv[wave][c][4 * lane + p + 2 * m] - sv[wave][c][4 * lane + p - 1];
                 }
-                const double g11 = g[0] * scale, g12 = g[1] * scale, g22 = g[2] * scale;
-                const double h1 = g[3] * scale, h2 = g[4] * scale;
-                const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
-                o[p].x = (float)((g11 * h2 - g12 * h1) * idet);
-                o[p].y = (float)((g22 * h1 - g12 * h2) * idet);
+                o[p] = nsof_flow_solve(g[0], g[1], g[2], g[3], g[4], scale);
             }
             float2* dst = fz + (size_t)yo * W + xo;
 #pragma unroll
@@ -1606,10 +1530,7 @@ __global__ __launch_bounds__(64) void k_blur_rowsolve(const double* __restrict__
     for (int x = 0; x < W; x++) {
 #pragma unroll
         for (int c = 0; c < 5; c++) g[c] += at(c, x + m) - at(c, x - m - 1);
-        const double g11 = g[0] * scale, g12 = g[1] * scale, g22 = g[2] * scale;
-        const double h1 = g[3] * scale, h2 = g[4] * scale;
-        const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
-        fz[x] = make_float2((float)((g11 * h2 - g12 * h1) * idet), (float)((g22 * h1 - g12 * h2) * idet));
+        fz[x] = nsof_flow_solve(g[0], g[1], g[2], g[3], g[4], scale);
     }
 }
 
@@ -2078,16 +1999,6 @@ int nsof_launch_polyexp(nsof_ctx* ctx, int n_img, const float* img, int W, int H
         case 10: launch_polyexp_n<10>(ctx, n_img, img, W, H, taps, R); break;
         default: return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "poly_n=%d outside 1..%d", taps.n, NSOF_MAX_POLY_N);
     }
-    NSOF_HIP(ctx, hipGetLastError());
-    return NSOF_OK;
-}
-
-int nsof_launch_update_matrices(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
-                                const float* flow, int W, int H, float* M)
-{
-    nsof_prof_scope ps(ctx, NSOF_K_UPDMAT);
-    dim3 grid((W + 63) / 64, (H + 3) / 4, n_pairs);
-    hipLaunchKernelGGL(k_update_matrices, grid, dim3(256), 0, ctx->stream, R0, R1, pair_stride, flow, W, H, M);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }

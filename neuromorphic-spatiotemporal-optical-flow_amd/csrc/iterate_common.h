@@ -1,4 +1,4 @@
-// Device helpers shared by the fused Farneback iteration kernels (farneback_iterate.hip, farneback_iterate_x.hip):
+// Device helpers shared by the Farneback iteration kernels (farneback_iterate*.hip):
 // the expansion layout, the per-row load bundle of a pixel, FarnebackUpdateMatrices for one pixel, the flow source.
 #pragma once
 #include <atomic>
@@ -8,17 +8,6 @@
 #include "nsof_internal.h"
 
 namespace {
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// cvFloor(float) as its x86-64 build returns it for every float: NaN and
-// v >= 2^31 give INT_MIN, v < -2^31 (-inf included) INT_MAX.  A bare (int)v would give 0 for NaN here (v_cvt_i32_f32),
-// which sends a NaN flow into the bilinear sample instead of the out-of-image branch.
-__device__ __forceinline__ int floor_f(float v)
-{
-    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return v < 0.f ? 2147483647 : -2147483647 - 1;
-    int i = (int)v;
-    return i - (i > v);
-}
 
 // R of one image: [h][w][4] f32 (channels 0-3 of a pixel = one aligned 16-B access) followed by [h][w] f32
 // (channel 4).  32-bit byte offsets against wave-uniform bases keep every load in the "SGPR base + VGPR offset"

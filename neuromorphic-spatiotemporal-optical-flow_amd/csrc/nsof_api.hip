@@ -560,7 +560,8 @@ extern "C" int nsof_stage_blur_solve(nsof_ctx* ctx, int n_pairs, const float* d_
                                      int winsize, float* d_flow)
 {
     if (!ctx || !d_M || !d_flow || n_pairs < 1 || width < 1 || height < 1 || winsize < 2) return NSOF_EINVAL;
-    if (ctx->opt_exact_rowsums) {   // the library's row-sum order (k_blur_colsum + k_blur_rowsolve), as the driver runs it
+    // the library's row-sum order (k_blur_colsum + k_blur_rowsolve) wherever the driver's form is exact
+    if (nsof_form_exact(nsof_iterate_form(ctx, winsize, width, height, 1, n_pairs * nsof_iterate_jobs(width, height)))) {
         const size_t need = (size_t)n_pairs * 5 * width * height * sizeof(double);
         if (int rc = ctx->ws.reserve(ctx, need)) return rc;
         return nsof_launch_blur_solve_exact(ctx, n_pairs, d_M, width, height, winsize, (double*)ctx->ws.p, d_flow);
@@ -573,13 +574,15 @@ extern "C" int nsof_stage_iterate(nsof_ctx* ctx, int n_pairs, const float* d_R, 
 {
     if (!ctx || !d_R || !d_flow_in || !d_flow_out || d_flow_in == d_flow_out || n_pairs < 1 || width < 1 || height < 1)
         return NSOF_EINVAL;
-    if (!nsof_iterate_supported(winsize, width, height)) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "winsize %d not fused", winsize);
+    const nsof_iter_form form = nsof_iterate_form(ctx, winsize, width, height, 1, n_pairs * nsof_iterate_jobs(width, height));
+    if (!nsof_form_fused(form)) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "winsize %d not fused", winsize);
     const size_t plane = (size_t)width * height;
-    if (ctx->opt_exact_rowsums && nsof_iterate_x_supported(winsize, width, height))
-        return nsof_launch_iterate_x(ctx, n_pairs, d_R, d_R + 5 * plane, 10 * plane, d_flow_in, d_flow_out, width, height,
-                                     winsize);
-    return nsof_launch_iterate(ctx, n_pairs, d_R, d_R + 5 * plane, 10 * plane, d_flow_in, d_flow_out, width, height,
-                               winsize);
+    if (form == NSOF_ITER_FAST)
+        return nsof_launch_iterate(ctx, n_pairs, d_R, d_R + 5 * plane, 10 * plane, d_flow_in, d_flow_out, width, height,
+                                   winsize);
+    // the exact order in its one-kernel form, small batches too (the stage has no workspace for the small-batch form)
+    return nsof_launch_iterate_x(ctx, n_pairs, d_R, d_R + 5 * plane, 10 * plane, d_flow_in, d_flow_out, width, height,
+                                 winsize);
 }
 
 extern "C" int nsof_stage_iterate_upsample(nsof_ctx* ctx, int n_pairs, const float* d_R, const float* d_coarse_flow,
@@ -604,15 +607,15 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 
 // Workspace of the uniform driver for B pairs: I [n_img][nk] f32 and R [n_img][5*nk] f32 (level images and
 // expansions: one slot that every level reuses, or one slot per level for the latency schedule `lat`), S = second flow
-// buffer [B][n0][2], M [B][5][n0] (the unfused iteration and the three-kernel exact form), V = column sums [B][5][n0] f64
-// (the unfused and the three-kernel exact order).  Offsets in bytes, in that order.
+// buffer [B][n0][2], M [B][5][n0] (the unfused forms and the small-batch form), V = column sums [B][5][n0] f64 (the
+// unfused and the small-batch exact forms).  Offsets in bytes, in that order.
 struct Carve {
     std::vector<size_t> offI, offR;   // per level, within I / R
     size_t szI = 0, szR = 0, szS = 0, szM = 0, szV = 0;
     size_t total() const { return szI + szR + szS + szM + szV; }
 };
-static Carve farneback_carve(size_t B, bool sequence, int width, int height, double pyr_scale, int L, bool lat, bool fused,
-                             bool exact, bool exact_x, bool exact_lat)
+static Carve farneback_carve(size_t B, bool sequence, int width, int height, double pyr_scale, int L, bool lat,
+                             nsof_iter_form form)
 {
     Carve c;
     c.offI.assign(L + 1, 0);
@@ -628,8 +631,10 @@ static Carve farneback_carve(size_t B, bool sequence, int width, int height, dou
         c.szR += align_up(n_img * 5 * (size_t)wk * hk * 4, 256);
     }
     c.szS = align_up(B * n0 * 8, 256);
-    c.szM = fused && !exact_lat ? 0 : align_up(B * 5 * n0 * 4, 256);
-    c.szV = (exact && !exact_x) || exact_lat ? align_up(B * 5 * n0 * 8, 256) : 0;
+    const bool M = form != NSOF_ITER_FAST && form != NSOF_ITER_EXACT;
+    const bool V = form == NSOF_ITER_UNFUSED_EXACT || form == NSOF_ITER_EXACT_LAT;
+    c.szM = M ? align_up(B * 5 * n0 * 4, 256) : 0;
+    c.szV = V ? align_up(B * 5 * n0 * 8, 256) : 0;
     return c;
 }
 
@@ -652,15 +657,10 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     const int px_bytes = src == NSOF_SRC_F32 ? 4 : 1;
     if (row_stride < (ptrdiff_t)width * px_bytes) return nsof_set_error(ctx, NSOF_EINVAL, "row_stride < width * %d", px_bytes);
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    const bool exact = ctx->opt_exact_rowsums != 0;
-    // exact row-sum order: ONE fused kernel (k_iterate_x) where the window fits, else the unfused pair
-    const bool exact_x = exact && iterations > 0 && nsof_iterate_x_supported(winsize, width, height);
-    // a batch too small to fill the chip with (strip, image) jobs takes the three-kernel small-batch form of the same
-    // order (farneback_iterate_lat.hip; NSOF_OPT_SMALL_BATCH_JOBS)
-    const bool exact_lat = exact_x && (long long)n_pairs * ((width + 191) / 192) <= ctx->opt_small_batch_jobs &&
-                           (unsigned long long)width * height * 40ull < (1ull << 32);   // its kernels address a pair with 32-bit byte offsets
+    const nsof_iter_form form = nsof_iterate_form(ctx, winsize, width, height, iterations,
+                                                  n_pairs * nsof_iterate_jobs(width, height));
     const int exact_chunk = 64;
-    if (exact && !exact_x && (sequence || n_pairs > exact_chunk)) {
+    if (form == NSOF_ITER_UNFUSED_EXACT && (sequence || n_pairs > exact_chunk)) {
         // the exact order keeps 40 B/px of column sums (+ 20 B/px of matrices) in HBM: 64 pairs of 1920x1080 at a time
         // (8 GB) fill the GPU -- the row walk has one thread per image row; a sequence is run as its pairs
         const uint8_t* nx = sequence ? d_prev + pair_stride : d_next;
@@ -675,19 +675,15 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     }
 
     const int L = nsof_farneback_effective_levels(width, height, pyr_scale, levels);
-    // Fused or unfused is decided once for the whole pyramid (inputs below 2x2 take the unfused pair); the exact
-    // row-sum order is fused only where k_iterate_x runs it.
-    const bool fused = nsof_iterate_supported(winsize, width, height) && (!exact || exact_x);
+    const bool fused = nsof_form_fused(form);
     // ---- small batches (the three-kernel exact form): the latency schedule ---------------------------------------------
     // A lone call is a chain of ~50 launches that each use a fraction of the chip and cost >= ~5 us (profiles/
     // r03_lone_call_timeline.txt: 762 us at 1080p, a third of it in the two coarsest levels).  Only the FLOW couples the
     // levels; pyramid level and polynomial expansion of every level depend on the input frames alone.  So they move to a
     // side stream (levels L-1 .. 0, into per-level buffers) and run next to the iterations of the coarser levels on the
     // main stream; an event per level hands the expansion over.  Same kernels, same arguments, same bits.
-    const bool lat = exact_lat && fused && L >= 1 && iterations > 0;
-    auto carve = [&](size_t b) {
-        return farneback_carve(b, sequence, width, height, pyr_scale, L, lat, fused, exact, exact_x, exact_lat);
-    };
+    const bool lat = form == NSOF_ITER_EXACT_LAT && L >= 1;
+    auto carve = [&](size_t b) { return farneback_carve(b, sequence, width, height, pyr_scale, L, lat, form); };
     const Carve cv = carve((size_t)n_pairs);
     {
         // A batch whose workspace would not fit the device's free memory is run in chunks of as many pairs as do fit --
@@ -858,9 +854,9 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
         const float* R1 = R0 + (sequence ? (size_t)1 : B) * 5 * nk;
         if (fused) {
             for (int it = 0; it < iterations; it++) {
-                if (exact_lat)
+                if (form == NSOF_ITER_EXACT_LAT)
                     rc = nsof_launch_iterate_lat(ctx, n_pairs, R0, R1, 5 * nk, fb[cur], fb[cur ^ 1], wk, hk, winsize, dM, dV);
-                else if (exact_x)
+                else if (form == NSOF_ITER_EXACT)
                     rc = nsof_launch_iterate_x(ctx, n_pairs, R0, R1, 5 * nk, fb[cur], fb[cur ^ 1], wk, hk, winsize);
                 else
                     rc = nsof_launch_iterate(ctx, n_pairs, R0, R1, 5 * nk, fb[cur], fb[cur ^ 1], wk, hk, winsize);
@@ -869,13 +865,11 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
             }
         } else {
             float* flow = fb[cur];
-            if ((rc = nsof_launch_update_matrices(ctx, n_pairs, R0, R1, 5 * nk, flow, wk, hk, dM))) return rc;
             for (int it = 0; it < iterations; it++) {
-                if (exact) rc = nsof_launch_blur_solve_exact(ctx, n_pairs, dM, wk, hk, winsize, dV, flow);
+                if ((rc = nsof_launch_update_matrices(ctx, n_pairs, R0, R1, 5 * nk, flow, wk, hk, dM))) return rc;
+                if (form == NSOF_ITER_UNFUSED_EXACT) rc = nsof_launch_blur_solve_exact(ctx, n_pairs, dM, wk, hk, winsize, dV, flow);
                 else rc = nsof_launch_blur_solve(ctx, n_pairs, dM, wk, hk, winsize, flow);
                 if (rc) return rc;
-                if (it < iterations - 1)
-                    if ((rc = nsof_launch_update_matrices(ctx, n_pairs, R0, R1, 5 * nk, flow, wk, hk, dM))) return rc;
             }
         }
         pw = wk;

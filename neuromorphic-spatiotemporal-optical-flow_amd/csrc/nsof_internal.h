@@ -196,6 +196,10 @@ struct nsof_het_item {
 };
 enum { NSOF_HET_VEC0 = 1 };
 
+// FarnebackUpdateMatrices (farneback_iterate_lat.hip), the first kernel of the unfused iteration.  R0/R1: the expansions of
+// prev/next of pair 0; pair z is at +z*pair_stride floats.
+int nsof_launch_update_matrices(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
+                                const float* flow, int W, int H, float* M);
 // Small-batch exact-order iteration (farneback_iterate_lat.hip): matrices, column sums and row scan as three wide kernels.
 // M: 5 floats, V: 5 doubles per pixel of the level (work list: at offR / 2 of each item).  winsize 2..15.
 int nsof_launch_iterate_lat(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
@@ -237,9 +241,6 @@ int nsof_launch_polyexp(nsof_ctx* ctx, int n_img, const float* img, int W, int H
 // Full-resolution level: pyramid level (3-tap smoothing, centre k0 / side k1) + expansion in one kernel, from the frames.
 int nsof_launch_polyexp_u8(nsof_ctx* ctx, int n_img, const uint8_t* src0, const uint8_t* src1, int nsplit, ptrdiff_t row_stride,
                            ptrdiff_t img_stride, int W, int H, const nsof_poly_taps& taps, float k0, float k1, float* R);
-// R0/R1: planar [5][h][w] expansion of prev/next of pair 0; pair z is at +z*pair_stride floats.
-int nsof_launch_update_matrices(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
-                                const float* flow, int W, int H, float* M);
 int nsof_launch_blur_solve(nsof_ctx* ctx, int n_pairs, const float* M, int W, int H, int winsize, float* flow);
 // The same in the reference library's exact summation order; VT: n_pairs * 5 * W * H doubles of scratch.
 int nsof_launch_blur_solve_exact(nsof_ctx* ctx, int n_pairs, const float* M, int W, int H, int winsize, double* VT,
@@ -247,12 +248,10 @@ int nsof_launch_blur_solve_exact(nsof_ctx* ctx, int n_pairs, const float* M, int
 int nsof_launch_flow_upsample(nsof_ctx* ctx, int n_pairs, const float* src, int sw, int sh, float* dst, int dw,
                               int dh, float mul);
 #define NSOF_PYR_SEL(ctx, fn, ...) ((ctx)->opt_pyr_fma ? fn##_fma(ctx, __VA_ARGS__) : fn(ctx, __VA_ARGS__))
-bool nsof_iterate_supported(int winsize, int W, int H);
 // Fused iteration; flow_in != flow_out.
 int nsof_launch_iterate(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
                         const float* flow_in, float* flow_out, int W, int H, int winsize);
 // Exact-order fused iteration in ONE kernel (running row sums inside the strip walker, strips chained by carries).
-bool nsof_iterate_x_supported(int winsize, int W, int H);
 int nsof_launch_iterate_x(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
                           const float* flow_in, float* flow_out, int W, int H, int winsize);
 // d_xjobs: the level's job table -- 8 counts, then 8 lists (one per XCD, `stride` entries apart) of item << 8 | strip;
@@ -261,6 +260,41 @@ int nsof_launch_iterate_x(nsof_ctx* ctx, int n_pairs, const float* R0, const flo
 int nsof_launch_iterate_x_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h, const float* R,
                               size_t R_floats, const float* flow_in, float* flow_out, bool final, int winsize,
                               const unsigned* d_xjobs, int stride, int njobs);
+
+// ---- the form of the iteration ------------------------------------------------------------------------------------
+// The fused kernels (k_iterate_q, k_iterate_x, the small-batch form) take windows 2..15 and need a 2x2 neighbourhood
+// for their clamped gather.
+static inline bool nsof_iterate_supported(int winsize, int W, int H)
+{
+    const int m = winsize / 2;
+    return m >= 1 && m <= 7 && W >= 2 && H >= 2;
+}
+// (strip, image) jobs of one W x H image at level 0, what a call is measured by for the small-batch form.  An image whose
+// pair the small-batch kernels cannot address with 32-bit byte offsets (40 W H >= 4 GB) counts as more than any call may
+// have.
+static inline long long nsof_iterate_jobs(int W, int H)
+{
+    return (unsigned long long)W * H * 40ull < (1ull << 32) ? (W + NSOF_X_STRIP - 1) / NSOF_X_STRIP : 1ll << 31;
+}
+enum nsof_iter_form {
+    NSOF_ITER_FAST,            // fused, per-pixel window sums: k_iterate_q
+    NSOF_ITER_EXACT,           // fused, the library's running row sums: k_iterate_x
+    NSOF_ITER_EXACT_LAT,       // the same order for small batches: k_update_matrices + k_lat_colsum + k_lat_rowscan
+    NSOF_ITER_UNFUSED_FAST,    // k_update_matrices + k_blur_solve
+    NSOF_ITER_UNFUSED_EXACT,   // k_update_matrices + k_blur_colsum + k_blur_rowsolve
+};
+// The form every iteration of a call takes, at every level: W x H is level 0, jobs the call's nsof_iterate_jobs summed
+// over its pairs.  The exact order is fused only where it iterates; calls of at most NSOF_OPT_SMALL_BATCH_JOBS jobs take
+// its small-batch form.
+static inline nsof_iter_form nsof_iterate_form(const nsof_ctx* ctx, int winsize, int W, int H, int iterations, long long jobs)
+{
+    const bool fused = nsof_iterate_supported(winsize, W, H);
+    if (!ctx->opt_exact_rowsums) return fused ? NSOF_ITER_FAST : NSOF_ITER_UNFUSED_FAST;
+    if (!fused || iterations < 1) return NSOF_ITER_UNFUSED_EXACT;
+    return jobs <= ctx->opt_small_batch_jobs ? NSOF_ITER_EXACT_LAT : NSOF_ITER_EXACT;
+}
+static inline bool nsof_form_fused(nsof_iter_form f) { return f <= NSOF_ITER_EXACT_LAT; }
+static inline bool nsof_form_exact(nsof_iter_form f) { return f != NSOF_ITER_FAST && f != NSOF_ITER_UNFUSED_FAST; }
 // Carry buffer of at least `carry_bytes` (0: whatever exists) + ticket / timeout words of that kernel.
 int nsof_xsync_reserve(nsof_ctx* ctx, size_t carry_bytes, unsigned long long** carry, unsigned** tickets, unsigned** err);
 // Reads the timeout word of the exact-order kernel after the stream has drained; NSOF_EDEVICE if a carry never arrived.
@@ -289,6 +323,26 @@ __device__ __forceinline__ double nsof_recip_normal(double x)
     r = __builtin_fma(r, e, r);
     e = __builtin_fma(-x, r, 1.0);   // residual of the quotient q0 = 1 * r
     return __builtin_fma(e, r, r);
+}
+
+// The 2x2 solve of FarnebackUpdateFlow_Blur for one pixel, from its window sums s0..s4 of the five planes of M and the
+// box filter's scale 1 / (winsize * winsize): each sum scaled, the regularised determinant, its reciprocal, the two products.
+__device__ __forceinline__ float2 nsof_flow_solve(double s0, double s1, double s2, double s3, double s4, double scale)
+{
+    const double g11 = s0 * scale, g12 = s1 * scale, g22 = s2 * scale, h1 = s3 * scale, h2 = s4 * scale;
+    const double idet = nsof_recip_normal(g11 * g22 - g12 * g12 + 1e-3);
+    return make_float2((float)((g11 * h2 - g12 * h1) * idet), (float)((g22 * h1 - g12 * h2) * idet));
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// cvFloor(float) as its x86-64 build returns it for every float: NaN and
+// v >= 2^31 give INT_MIN, v < -2^31 (-inf included) INT_MAX.  A bare (int)v would give 0 for NaN here (v_cvt_i32_f32),
+// which sends a NaN flow into the bilinear sample instead of the out-of-image branch.
+__device__ __forceinline__ int floor_f(float v)
+{
+    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return v < 0.f ? 2147483647 : -2147483647 - 1;
+    int i = (int)v;
+    return i - (i > v);
 }
 
 // cv2's fixed-point cvtColor to gray of one interleaved 3-channel 8-bit pixel (c0, c1, c2): weights in units of 2^-15,

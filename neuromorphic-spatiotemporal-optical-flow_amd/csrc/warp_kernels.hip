@@ -28,8 +28,6 @@ struct MapSrc {
     int sign;            // FUSED: map = grid + sign * flow
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // Destination pixel (x, y), all CN interleaved channels, written at o.
 template <int CN, bool FUSED>
 __device__ __forceinline__ void remap_px(const uint8_t* __restrict__ src, ptrdiff_t sstride, int sw, int sh,
