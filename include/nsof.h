@@ -241,6 +241,59 @@ int nsof_farneback_f32_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const float
                                         const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale, int levels,
                                         int winsize, int iterations, int poly_n, double poly_sigma, int flags,
                                         int gate_frame, long long* n_calls, long long* n_pixels);
+/* Typed entries: the entries above for frames of any pixel type cv2 takes natively on this path.  `pixel_type` is an
+ * nsof_pixel_type; frame pointers are `const void*` and every stride stays in BYTES.  U8 and F32 run exactly the code of
+ * their twins (nsof_farneback_u8*, nsof_farneback_f32*), with the same layout rules.  16-bit frames (U16: zero-extended,
+ * S16: sign-extended; both convert to float exactly) take the 8-bit path's fused pyramid kernels at 2 B/px and give the
+ * flow of the F32 entry on the frames' float32 values, bit for bit, in every mode.  Their layout rules: frame pointers
+ * 2-byte aligned, row, pair and frame strides multiples of 2, a row stride at least 2*width.  A violation, or an unknown
+ * pixel type, returns NSOF_EINVAL before anything is launched.  A list holds one pixel type. */
+typedef enum nsof_pixel_type {
+    NSOF_PIXEL_U8 = 0,
+    NSOF_PIXEL_F32 = 1,
+    NSOF_PIXEL_U16 = 2,
+    NSOF_PIXEL_S16 = 3,
+} nsof_pixel_type;
+/* nsof_pair_desc with untyped frames: the fields of nsof_pair_desc in the same order. */
+typedef struct nsof_pair_desc_px {
+    const void* prev;
+    ptrdiff_t prev_stride;
+    const void* next;
+    ptrdiff_t next_stride;
+    int width, height;
+    float* flow;
+    ptrdiff_t flow_stride;
+} nsof_pair_desc_px;
+int nsof_farneback_px(nsof_ctx* ctx, int pixel_type,
+                      const void* prev, ptrdiff_t prev_stride,
+                      const void* next, ptrdiff_t next_stride,
+                      int width, int height,
+                      float* flow, ptrdiff_t flow_stride,
+                      double pyr_scale, int levels, int winsize, int iterations,
+                      int poly_n, double poly_sigma, int flags);
+int nsof_farneback_px_batch_dev(nsof_ctx* ctx, int pixel_type, int n_pairs,
+                                const void* d_prev, const void* d_next,
+                                ptrdiff_t row_stride, ptrdiff_t pair_stride,
+                                int width, int height, float* d_flow,
+                                double pyr_scale, int levels, int winsize, int iterations,
+                                int poly_n, double poly_sigma, int flags);
+int nsof_farneback_px_sequence_dev(nsof_ctx* ctx, int pixel_type, int n_frames, const void* d_frames,
+                                   ptrdiff_t row_stride, ptrdiff_t frame_stride,
+                                   int width, int height, float* d_flow,
+                                   double pyr_scale, int levels, int winsize, int iterations,
+                                   int poly_n, double poly_sigma, int flags);
+int nsof_farneback_px_batch(nsof_ctx* ctx, int pixel_type, int n_pairs, const nsof_pair_desc_px* pairs,
+                            double pyr_scale, int levels, int winsize, int iterations,
+                            int poly_n, double poly_sigma, int flags);
+int nsof_farneback_px_batch_desc_dev(nsof_ctx* ctx, int pixel_type, int n_pairs, const nsof_pair_desc_px* pairs,
+                                     double pyr_scale, int levels, int winsize, int iterations,
+                                     int poly_n, double poly_sigma, int flags);
+int nsof_farneback_px_roi_sequence_dev(nsof_ctx* ctx, int pixel_type, int n_frames, const void* d_frames,
+                                       ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
+                                       const int32_t* d_counts, const int32_t* d_rects, int max_rects, float* d_flows,
+                                       double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                                       double poly_sigma, int flags, int gate_frame, long long* n_calls,
+                                       long long* n_pixels);
 /* Page-locked host memory for frames / flow fields handed to nsof_farneback_u8_batch / nsof_farneback_f32_batch (NULL on
  * failure). */
 void* nsof_host_alloc(size_t bytes);
@@ -261,6 +314,9 @@ int nsof_stage_pyr_level(nsof_ctx* ctx, int n_img, const uint8_t* d_src, ptrdiff
 /* The same pyramid level from float32 frames (byte strides, multiples of 4). */
 int nsof_stage_pyr_level_f32(nsof_ctx* ctx, int n_img, const float* d_src, ptrdiff_t row_stride,
                              ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out);
+/* The same pyramid level from frames of any nsof_pixel_type (the layout rules of the typed entries). */
+int nsof_stage_pyr_level_px(nsof_ctx* ctx, int pixel_type, int n_img, const void* d_src, ptrdiff_t row_stride,
+                            ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out);
 int nsof_stage_polyexp(nsof_ctx* ctx, int n_img, const float* d_img, int width, int height,
                        int poly_n, double poly_sigma, float* d_R);
 /* Diagnostic: d_out[i] = the reciprocal the 2x2 solves use (rcp + Newton steps + residual correction, without the

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <array>
 #include <chrono>
+#include <cstddef>
 #include <cstring>
 #include <functional>
 #include <thread>
@@ -36,7 +37,7 @@ struct Params {
     double poly_sigma;
     int flags;
     int src = NSOF_SRC_U8;   // nsof_src_type of every frame of the list
-    size_t px() const { return src == NSOF_SRC_F32 ? 4 : 1; }   // bytes per pixel
+    size_t px() const { return (size_t)nsof_src_bytes(src); }   // bytes per pixel
 };
 
 int validate_desc(nsof_ctx* ctx, int i, const nsof_pair_desc& d, const Params& p)
@@ -51,6 +52,13 @@ int validate_desc(nsof_ctx* ctx, int i, const nsof_pair_desc& d, const Params& p
         if ((d.prev_stride & 3) || (d.next_stride & 3) || d.prev_stride < (ptrdiff_t)d.width * 4 ||
             d.next_stride < (ptrdiff_t)d.width * 4)
             return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: f32 row strides %td / %td must be multiples of 4 and >= 4*width",
+                                  i, d.prev_stride, d.next_stride);
+    } else if (p.src == NSOF_SRC_U16 || p.src == NSOF_SRC_S16) {   // the layout rules of nsof_farneback_px for 16 bits
+        if ((reinterpret_cast<uintptr_t>(d.prev) & 1) || (reinterpret_cast<uintptr_t>(d.next) & 1))
+            return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: 16-bit frames must be 2-byte aligned", i);
+        if ((d.prev_stride & 1) || (d.next_stride & 1) || d.prev_stride < (ptrdiff_t)d.width * 2 ||
+            d.next_stride < (ptrdiff_t)d.width * 2)
+            return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: 16-bit row strides %td / %td must be even and >= 2*width",
                                   i, d.prev_stride, d.next_stride);
     } else if (d.prev_stride < d.width || d.next_stride < d.width)
         return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: row stride < width", i);
@@ -260,7 +268,7 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
                 it.offI = oI; it.offR = oR; it.offF = oF; it.offFc = offF_prev[j];
                 oI += align_up(2 * nk, 64); oR += align_up(10 * nk, 64); oF += align_up(nk, 32);
                 offF_prev[j] = it.offF;
-                const uintptr_t va = p.src == NSOF_SRC_F32 ? 15 : 3;   // k_prep_same3_vec's row loads: 16 B (f32) / 4 B (u8)
+                const uintptr_t va = 4 * p.px() - 1;   // k_prep_same3_vec's row loads: 4 B (u8) / 8 B (16-bit) / 16 B (f32)
                 const bool vec = (d.width & 3) == 0 && d.width >= 8 && (d.prev_stride & va) == 0 && (d.next_stride & va) == 0 &&
                                  (reinterpret_cast<uintptr_t>(d.prev) & va) == 0 && (reinterpret_cast<uintptr_t>(d.next) & va) == 0;
                 it.flags = vec ? NSOF_HET_VEC0 : 0;
@@ -306,13 +314,15 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
                 if ((rc = NSOF_PYR_SEL(ctx, nsof_launch_flow_upsample_het, c.count, dt + c.start, c.max_w, c.max_h, fb[cur],
                                        fb[cur ^ 1], (float)(1. / p.pyr_scale))))
                     return rc;
-                // level 0: the expansion kernel forms the level image from the 8-bit frames itself (see nsof_farneback_core);
-                // float frames take the two-kernel form
-                const bool u8 = k == 0 && btaps.ksize == 3 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && p.src == NSOF_SRC_U8;
+                // level 0: the expansion kernel forms the level image from the 8- or 16-bit frames itself (see
+                // nsof_farneback_core); float frames take the two-kernel form
+                const bool fused0 = k == 0 && btaps.ksize == 3 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && p.src != NSOF_SRC_F32;
                 const float blur3[2] = {btaps.k[1], btaps.k[2]};
-                if (!u8 && (rc = NSOF_PYR_SEL(ctx, nsof_launch_prep_het, c.count, dt + c.start, ht + c.start, k == 0, btaps, dI, p.src)))
+                if (!fused0 && (rc = NSOF_PYR_SEL(ctx, nsof_launch_prep_het, c.count, dt + c.start, ht + c.start, k == 0, btaps, dI, p.src)))
                     return rc;
-                if ((rc = nsof_launch_polyexp_het(ctx, c.count, dt + c.start, c.max_w, c.max_h, ptaps, dI, dR, u8 ? blur3 : nullptr))) return rc;
+                if ((rc = nsof_launch_polyexp_het(ctx, c.count, dt + c.start, c.max_w, c.max_h, ptaps, dI, dR, fused0 ? blur3 : nullptr,
+                                                  p.src)))
+                    return rc;
             }
             cur ^= 1;
             for (int it = 0; it < p.iterations; it++) {
@@ -933,4 +943,58 @@ extern "C" void* nsof_host_alloc(size_t bytes)
 extern "C" void nsof_host_free(void* p)
 {
     if (p) (void)hipHostFree(p);
+}
+
+// ---- typed work-list entries (nsof_pixel_type == nsof_src_type; nsof_pair_desc_px has nsof_pair_desc's layout) -------
+static_assert(sizeof(nsof_pair_desc_px) == sizeof(nsof_pair_desc) && offsetof(nsof_pair_desc_px, next) == offsetof(nsof_pair_desc, next) &&
+                  offsetof(nsof_pair_desc_px, flow_stride) == offsetof(nsof_pair_desc, flow_stride),
+              "nsof_pair_desc_px must keep nsof_pair_desc's layout");
+
+extern "C" int nsof_farneback_px_batch(nsof_ctx* ctx, int pixel_type, int n_pairs, const nsof_pair_desc_px* pairs,
+                                       double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma,
+                                       int flags)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!nsof_src_valid(pixel_type)) return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
+    if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return nsof_set_error(ctx, NSOF_EINVAL, "bad pair list");
+    if (n_pairs == 0) return NSOF_OK;
+    Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
+    p.src = pixel_type;
+    return batch_host(ctx, n_pairs, reinterpret_cast<const nsof_pair_desc*>(pairs), p);
+}
+
+extern "C" int nsof_farneback_px_batch_desc_dev(nsof_ctx* ctx, int pixel_type, int n_pairs, const nsof_pair_desc_px* pairs,
+                                                double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                                                double poly_sigma, int flags)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!nsof_src_valid(pixel_type)) return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
+    if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return nsof_set_error(ctx, NSOF_EINVAL, "bad pair list");
+    if (n_pairs > 32767) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "n_pairs=%d exceeds 32767 per call", n_pairs);
+    if (n_pairs == 0) return NSOF_OK;
+    Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
+    p.src = pixel_type;
+    return het_core(ctx, n_pairs, reinterpret_cast<const nsof_pair_desc*>(pairs), p);
+}
+
+extern "C" int nsof_farneback_px_roi_sequence_dev(nsof_ctx* ctx, int pixel_type, int n_frames, const void* d_frames,
+                                                  ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
+                                                  const int32_t* d_counts, const int32_t* d_rects, int max_rects, float* d_flows,
+                                                  double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                                                  double poly_sigma, int flags, int gate_frame, long long* n_calls,
+                                                  long long* n_pixels)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!nsof_src_valid(pixel_type)) return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
+    if (pixel_type == NSOF_SRC_F32)
+        return nsof_farneback_f32_roi_sequence_dev(ctx, n_frames, static_cast<const float*>(d_frames), row_stride, frame_stride,
+                                                   width, height, d_counts, d_rects, max_rects, d_flows, pyr_scale, levels,
+                                                   winsize, iterations, poly_n, poly_sigma, flags, gate_frame, n_calls, n_pixels);
+    if (pixel_type != NSOF_SRC_U8 && ((reinterpret_cast<uintptr_t>(d_frames) & 1) || (row_stride & 1) || (frame_stride & 1)))
+        return nsof_set_error(ctx, NSOF_EINVAL, "roi_sequence: 16-bit frames must be 2-byte aligned and row_stride=%td / "
+                              "frame_stride=%td even", row_stride, frame_stride);
+    Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
+    p.src = pixel_type;
+    return roi_sequence(ctx, n_frames, static_cast<const uint8_t*>(d_frames), row_stride, frame_stride, width, height,
+                        d_counts, d_rects, max_rects, d_flows, p, gate_frame, n_calls, n_pixels);
 }

@@ -64,9 +64,10 @@ __device__ __forceinline__ void lin_coord_y(int d, double scale, int& s, float& 
 // resample of the blurred FULL-RES image to (wk, hk).
 // ---------------------------------------------------------------------------------------
 
-// Source frames are 8-bit (T = uint8_t) or float (T = float); row and image strides are in BYTES for both.  px() is
-// the one load-and-convert of a source pixel (u8: the exact conversion; f32: the value itself), srow() the start of a
-// byte-strided row.  For T = uint8_t both are exactly the expressions the 8-bit kernels always had.
+// Source frames are 8-bit (T = uint8_t), 16-bit (uint16_t, int16_t) or float (T = float); row and image strides are in
+// BYTES for all.  px() is the one load-and-convert of a source pixel (integers: the exact conversion; f32: the value
+// itself), srow() the start of a byte-strided row.  For T = uint8_t both are exactly the expressions the 8-bit kernels
+// always had.
 template <typename T>
 __device__ __forceinline__ float px(const T* p) { return (float)*p; }
 template <typename T>
@@ -74,8 +75,31 @@ __device__ __forceinline__ const T* srow(const T* img, ptrdiff_t r, ptrdiff_t st
 {
     return reinterpret_cast<const T*>(reinterpret_cast<const char*>(img) + r * stride);
 }
+// Pixel-width trait.  Integer frames (8- and 16-bit) are read as packed dwords of kPPD<T> pixels where the kernels load
+// raw bytes; px_el<T>(v, e) is the exact conversion of pixel e of such a dword (unsigned: zero-extended, int16_t:
+// sign-extended) -- for uint8_t the expression the 8-bit kernels always had.
 template <typename T>
 constexpr bool kU8 = std::is_same<T, uint8_t>::value;
+template <typename T>
+constexpr bool kInt = std::is_integral<T>::value;
+template <typename T>
+constexpr int kPPD = kInt<T> ? 4 / (int)sizeof(T) : 1;
+template <typename T>
+__device__ __forceinline__ float px_el(unsigned v, int e)
+{
+    if constexpr (sizeof(T) == 1) return (float)((v >> (8 * e)) & 0xffu);
+    else if constexpr (std::is_signed<T>::value) return (float)(int)(short)(v >> (16 * e));
+    else return (float)((v >> (16 * e)) & 0xffffu);
+}
+// Four adjacent pixels of a 16-bit or float row as one aligned vector (8 / 16 bytes), and pixel e of it.
+template <typename T>
+using PxQuad = std::conditional_t<sizeof(T) == 2, uint2, float4>;
+template <typename T>
+__device__ __forceinline__ float quad_el(const PxQuad<T>& v, int e)
+{
+    if constexpr (sizeof(T) == 2) return px_el<T>(e < 2 ? v.x : v.y, e & 1);
+    else return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w));
+}
 
 // Row filter at an (unreflected) column c of one row, ordering per kernel size.
 // KS > 0: kernel size known at compile time (loops unroll, taps are scalar registers); KS == 0: runtime size,
@@ -161,8 +185,8 @@ __global__ __launch_bounds__(256) void k_prep_same(const T* __restrict__ src, pt
 // One aligned dword load per row; the two bytes outside the dword come from the neighbouring lanes
 // (the wave's edge lanes fetch theirs from memory); row-filter results are shared between the three
 // output rows that use them; 16-B stores.  Requires 4-byte aligned rows (else k_prep_same).
-// T = float: the lane's 4 pixels are one aligned 16-B load per row (16-byte aligned rows, else k_prep_same), the two
-// outside values come from the neighbouring lanes the same way.
+// T = float / 16-bit: the lane's 4 pixels are one aligned 16-B / 8-B load per row (rows aligned to that, else
+// k_prep_same), the two outside values come from the neighbouring lanes the same way.
 constexpr int PREP0_ROWS = 8;
 template <bool HET, typename T = uint8_t>
 __global__ __launch_bounds__(256) void k_prep_same3_vec(const T* __restrict__ src, ptrdiff_t row_stride,
@@ -193,12 +217,12 @@ __global__ __launch_bounds__(256) void k_prep_same3_vec(const T* __restrict__ sr
             s0 = (float)(v & 0xffu); s1 = (float)((v >> 8) & 0xffu); s2 = (float)((v >> 16) & 0xffu);
             s3 = (float)(v >> 24); sl = (float)lft; sr = (float)rgt;
         } else {
-            const float4 v = *reinterpret_cast<const float4*>(rowp + xl);
-            sl = __shfl_up(v.w, 1);
-            sr = __shfl_down(v.x, 1);
-            if (lane == 0 || x == 0) sl = rowp[reflect101(xl - 1, W)];
-            if (lane == 63 || x + 4 >= W) sr = rowp[reflect101(xl + 4, W)];
-            s0 = v.x; s1 = v.y; s2 = v.z; s3 = v.w;
+            const PxQuad<T> v = *reinterpret_cast<const PxQuad<T>*>(rowp + xl);
+            s0 = quad_el<T>(v, 0); s1 = quad_el<T>(v, 1); s2 = quad_el<T>(v, 2); s3 = quad_el<T>(v, 3);
+            sl = __shfl_up(s3, 1);
+            sr = __shfl_down(s0, 1);
+            if (lane == 0 || x == 0) sl = px(rowp + reflect101(xl - 1, W));
+            if (lane == 63 || x + 4 >= W) sr = px(rowp + reflect101(xl + 4, W));
         }
         h[0] = NSOF_MADD(sl + s1, k1, s0 * k0);
         h[1] = NSOF_MADD(s0 + s2, k1, s1 * k0);
@@ -238,9 +262,10 @@ __global__ __launch_bounds__(256) void k_prep_same3_vec(const T* __restrict__ sr
 //   * column filter at the two sampled rows, then resize's 2x2 blend (all four weights are exactly 0.5).
 // Same operation order as the other prep kernels (row_filter / col_filter), so the output is bit-identical.
 // The walk of one wave: column group `bx * 64 + lane`, output rows [seg * seg_rows, (seg + 1) * seg_rows) of image z.
-// T = float: the same walk over CW floats per lane (CW / 4 aligned 16-B loads per row, HB / 4 per halo side; the
-// launchers take CW = 8 and 16-byte aligned rows), prefetching one output row ahead only at S = 2 -- a raw f32 row is
-// four times the registers of an 8-bit one.
+// T = float / 16-bit: the same walk over CW pixels per lane (CW / 4 aligned 16-B / 8-B loads per row, HB / 4 per halo
+// side; rows 16- / 8-byte aligned), prefetching one output row ahead only at S = 2 for float -- a raw f32 row is four
+// times the registers of an 8-bit one -- and at S <= 4 for 16-bit, as for 8-bit.  Every load stays inside its row
+// (halo_l / halo_r below).
 template <int S, int KS, int CW, typename T = uint8_t>
 __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdiff_t row_stride, ptrdiff_t img_stride,
                                                 int W, int H, int wk, int hk, int seg_rows, const nsof_blur_taps& t,
@@ -274,23 +299,34 @@ __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdi
     struct RawU8 {
         unsigned cw[CW / 4], hl[HD], hr[HD];
     };
-    struct RawF32 {
-        float4 cw[CW / 4], hl[HD], hr[HD];
+    struct RawQ {   // 16-bit / f32: 4 pixels per 8-B / 16-B vector
+        PxQuad<T> cw[CW / 4], hl[HD], hr[HD];
     };
-    using Raw = std::conditional_t<kU8<T>, RawU8, RawF32>;
+    using Raw = std::conditional_t<kU8<T>, RawU8, RawQ>;
+    // Halo quad d of a side covers columns [xc0 - HB + 4d, +4) (left) / [xc0 + CW + 4d, +4) (right): whole quads, as
+    // W % CW == 0.  A lane reads at most R + 1 - S/2 (<= 6) columns beyond its segment, and the edge lanes reflect into
+    // their own pixels and their inner halo.  With HB <= CW the halos of every lane that is not at the image edge lie
+    // inside the row, and the edge lanes load theirs from their own segment (values unused).  With HB > CW (19 taps at
+    // S = 8 on 8-column lanes) the lane next to an edge would reach over the row's end by HB - CW columns: a quad that
+    // lies outside the row is loaded from rowp instead (its values are never used).  So every load stays in the row.
+    auto halo_l = [&](const T* rowp, int d) -> const T* {
+        if constexpr (HB > CW) return xc0 - HB + 4 * d >= 0 ? rowp - HB + 4 * d : rowp;
+        else return (edge_l ? rowp : rowp - HB) + 4 * d;
+    };
+    auto halo_r = [&](const T* rowp, int d) -> const T* {
+        if constexpr (HB > CW) return xc0 + CW + 4 * d + 4 <= W ? rowp + CW + 4 * d : rowp;
+        else return (edge_r ? rowp + (kU8<T> ? 0 : CW - HB) : rowp + CW) + 4 * d;
+    };
     auto fetch = [&](int r, Raw& q) {
         const T* rowp = srow(img, reflect101(r, H), row_stride) + xc0;
         if constexpr (!kU8<T>) {
+            using Q = PxQuad<T>;
 #pragma unroll
-            for (int d = 0; d < CW / 4; d++) q.cw[d] = reinterpret_cast<const float4*>(rowp)[d];
-            // edge lanes: any 16-byte aligned address inside the row, value unused (the launchers keep HB <= CW and
-            // W >= 64, so every load here stays inside the row)
-            const float4* lp = reinterpret_cast<const float4*>(edge_l ? rowp : rowp - HB);
-            const float4* rp = reinterpret_cast<const float4*>(edge_r ? rowp + CW - HB : rowp + CW);
+            for (int d = 0; d < CW / 4; d++) q.cw[d] = reinterpret_cast<const Q*>(rowp)[d];
 #pragma unroll
             for (int d = 0; d < HD; d++) {
-                q.hl[d] = lp[d];
-                q.hr[d] = rp[d];
+                q.hl[d] = *reinterpret_cast<const Q*>(halo_l(rowp, d));
+                q.hr[d] = *reinterpret_cast<const Q*>(halo_r(rowp, d));
             }
         } else {
             if (CW == 16) {
@@ -300,12 +336,10 @@ __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdi
                 const uint2 c = *reinterpret_cast<const uint2*>(rowp);
                 q.cw[0] = c.x; q.cw[1] = c.y;
             }
-            const uint8_t* lp = edge_l ? rowp : rowp - HB;          // edge lanes: any valid address, value unused
-            const uint8_t* rp = edge_r ? rowp : rowp + CW;
 #pragma unroll
             for (int d = 0; d < HD; d++) {
-                q.hl[d] = reinterpret_cast<const unsigned*>(lp)[d];
-                q.hr[d] = reinterpret_cast<const unsigned*>(rp)[d];
+                q.hl[d] = *reinterpret_cast<const unsigned*>(halo_l(rowp, d));
+                q.hr[d] = *reinterpret_cast<const unsigned*>(halo_r(rowp, d));
             }
         }
     };
@@ -320,14 +354,13 @@ __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdi
 #pragma unroll
             for (int b = 0; b < CW; b++) raw[HB + b] = (float)((q.cw[b >> 2] >> (8 * (b & 3))) & 0xffu);
         } else {
-            auto el = [](const float4& v, int e) { return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w)); };
 #pragma unroll
             for (int b = 0; b < HB; b++) {
-                raw[b] = el(q.hl[b >> 2], b & 3);
-                raw[HB + CW + b] = el(q.hr[b >> 2], b & 3);
+                raw[b] = quad_el<T>(q.hl[b >> 2], b & 3);
+                raw[HB + CW + b] = quad_el<T>(q.hr[b >> 2], b & 3);
             }
 #pragma unroll
-            for (int b = 0; b < CW; b++) raw[HB + b] = el(q.cw[b >> 2], b & 3);
+            for (int b = 0; b < CW; b++) raw[HB + b] = quad_el<T>(q.cw[b >> 2], b & 3);
         }
         float fb[WIN];
 #pragma unroll
@@ -350,7 +383,7 @@ __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdi
         fetch(r, q);
         filt(q, dstrow);
     };
-    constexpr bool PF = S <= (kU8<T> ? 4 : 2);   // prefetch one output row ahead
+    constexpr bool PF = S <= (sizeof(T) <= 2 ? 4 : 2);   // prefetch one output row ahead
 
     // relative row index rel = r - base, base = first row needed by output row dy0; slot = rel % RING
     const int base = S * dy0 + S / 2 - 1 - R;
@@ -539,17 +572,18 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const T* __restrict__ src, p
     const int RW0 = s_c[2 * PREP_TW - 1] + r - C0 + 1;
     const int R0 = s_r[0] - r, RH = s_r[2 * PREP_TH - 1] + r - R0 + 1;
     // host sized rw_cap/rh_cap from the same arithmetic (+4 columns of slack for the aligned copy below)
-    const bool interior = kU8<T> && C0 >= 0 && C0 + RW0 <= W && R0 >= 0 && R0 + RH <= H && (W & 3) == 0 &&
+    constexpr int PPD = kPPD<T>;   // integer frames: pixels per dword
+    const bool interior = kInt<T> && C0 >= 0 && C0 + RW0 <= W && R0 >= 0 && R0 + RH <= H && (W % PPD) == 0 &&
                           (row_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(img) & 3) == 0;
     if (interior) {
         // no border inside the footprint: copy whole aligned dwords (64 lanes x 4 B per wave-instruction)
-        const int C0a = C0 & ~3, nd = (C0 + RW0 - C0a + 3) >> 2;
+        const int C0a = C0 & ~(PPD - 1), nd = (C0 + RW0 - C0a + PPD - 1) / PPD;
         C0 = C0a;   // the LDS image now starts at the aligned column
 #pragma unroll 4
         for (int rr = wave; rr < RH; rr += 4) {
             const T* rowp = srow(img, R0 + rr, row_stride) + C0a;
             for (int d = lane; d < nd; d += 64)
-                *reinterpret_cast<unsigned*>(sU + rr * rw_cap + 4 * d) = *reinterpret_cast<const unsigned*>(rowp + 4 * d);
+                *reinterpret_cast<unsigned*>(sU + rr * rw_cap + PPD * d) = *reinterpret_cast<const unsigned*>(rowp + PPD * d);
         }
     } else {
         for (int rr = wave; rr < RH; rr += 4) {          // border tile (and f32 frames): per pixel, BORDER_REFLECT_101
@@ -596,7 +630,7 @@ __global__ __launch_bounds__(256) void k_prep_direct(const T* __restrict__ src, 
                                                       double scale_x, double scale_y, nsof_blur_taps t,
                                                       float* __restrict__ out, const nsof_het_item* __restrict__ items)
 {
-    constexpr int R = KS / 2, NB = KS + 1, ND = (NB + 3) / 4;
+    constexpr int R = KS / 2, NB = KS + 1, PPD = kPPD<T>, ND = (NB + PPD - 1) / PPD;
     PrepImg<T> g;
     prep_geom<HET>(g, src, row_stride, img_stride, W, H, wk, hk, out, items, -1);
     if constexpr (HET) { scale_x = 1. / ((double)wk / W); scale_y = 1. / ((double)hk / H); }
@@ -611,7 +645,7 @@ __global__ __launch_bounds__(256) void k_prep_direct(const T* __restrict__ src, 
     const float a0 = 1.f - a1, b0 = 1.f - b1;
     const int c0 = sx, c1 = min(sx + 1, W - 1);
     const int r0 = clampi(sy, 0, H - 1), r1 = clampi(sy + 1, 0, H - 1);
-    const bool fast = c0 - R >= 0 && c0 - R + 4 * ND <= W && c1 == c0 + 1;
+    const bool fast = c0 - R >= 0 && c0 - R + PPD * ND <= W && c1 == c0 + 1;
     auto tk = [&](int j) { return t.k[j]; };   // j is a compile-time constant after unrolling
 
     float H0[KS + 1], H1[KS + 1];
@@ -620,14 +654,14 @@ __global__ __launch_bounds__(256) void k_prep_direct(const T* __restrict__ src, 
         const T* rowp = srow(img, reflect101(r0 - R + i, H), row_stride);
         float b[NB], bb[NB];   // pixels around c0 and around c1
         if (fast) {
-            if constexpr (kU8<T>) {
+            if constexpr (kInt<T>) {
 #pragma unroll
                 for (int d = 0; d < ND; d++) {
                     unsigned v;
-                    __builtin_memcpy(&v, rowp + (c0 - R) + 4 * d, 4);   // unaligned dword load
+                    __builtin_memcpy(&v, rowp + (c0 - R) + PPD * d, 4);   // unaligned dword load
 #pragma unroll
-                    for (int e = 0; e < 4; e++)
-                        if (4 * d + e < NB) b[4 * d + e] = (float)((v >> (8 * e)) & 0xffu);
+                    for (int e = 0; e < PPD; e++)
+                        if (PPD * d + e < NB) b[PPD * d + e] = px_el<T>(v, e);
                 }
             } else {
 #pragma unroll
@@ -686,24 +720,24 @@ __device__ __forceinline__ void prep_walk_body(const T* __restrict__ img, ptrdif
                                                double scale_y, int dy0, int dy_end, int dx, bool live, int c0, int c1, bool fast,
                                                float a1, const nsof_blur_taps& t, float* __restrict__ dst)
 {
-    constexpr int R = KS / 2, NB = KS + 1, ND = (NB + 3) / 4;
+    constexpr int R = KS / 2, NB = KS + 1, PPD = kPPD<T>, ND = (NB + PPD - 1) / PPD;
     const float a0 = 1.f - a1;
     auto tk = [&](int j) { return t.k[j]; };   // j is a compile-time constant after unrolling
-    const unsigned coff = (unsigned)(c0 - R);    // byte offset of this lane's window in a source row (fast lanes)
-    // the KS + 1 bytes of source row rr (wave-uniform, any integer: reflected) around this lane's two columns, as raw dwords
+    const unsigned coff = (unsigned)(c0 - R);    // pixel offset of this lane's window in a source row (fast lanes)
+    // the KS + 1 pixels of source row rr (wave-uniform, any integer: reflected) around this lane's two columns, as raw dwords
     auto load_row = [&](int rr, unsigned (&raw)[ND]) {
         const T* rowp = srow(img, reflect101(rr, H), row_stride);   // scalar
 #pragma unroll
-        for (int d = 0; d < ND; d++) __builtin_memcpy(&raw[d], rowp + coff + 4 * d, 4);   // unaligned dword loads
+        for (int d = 0; d < ND; d++) __builtin_memcpy(&raw[d], rowp + coff + PPD * d, 4);   // unaligned dword loads
     };
-    // row-filtered values at columns c0 and c1 from those bytes
+    // row-filtered values at columns c0 and c1 from those pixels
     auto filt_row = [&](const unsigned (&raw)[ND], float& h0, float& h1) {
         float b[NB];
 #pragma unroll
         for (int d = 0; d < ND; d++)
 #pragma unroll
-            for (int e = 0; e < 4; e++)
-                if (4 * d + e < NB) b[4 * d + e] = (float)((raw[d] >> (8 * e)) & 0xffu);
+            for (int e = 0; e < PPD; e++)
+                if (PPD * d + e < NB) b[PPD * d + e] = px_el<T>(raw[d], e);
         h0 = row_filter<KS>(tk, KS, R, [&](int c) { return b[c]; });
         h1 = row_filter<KS>(tk, KS, R + 1, [&](int c) { return b[c]; });
     };
@@ -711,10 +745,10 @@ __device__ __forceinline__ void prep_walk_body(const T* __restrict__ img, ptrdif
     auto hrow_edge = [&](int rr, float& h0, float& h1) {
         const T* rowp = srow(img, reflect101(rr, H), row_stride);
         if (fast) {
-            if constexpr (kU8<T>) {
+            if constexpr (kInt<T>) {
                 unsigned raw[ND];
 #pragma unroll
-                for (int d = 0; d < ND; d++) __builtin_memcpy(&raw[d], rowp + coff + 4 * d, 4);
+                for (int d = 0; d < ND; d++) __builtin_memcpy(&raw[d], rowp + coff + PPD * d, 4);
                 filt_row(raw, h0, h1);
             } else {   // f32: the NB values around c0 straight from the row
                 float b[NB];
@@ -805,13 +839,13 @@ __device__ __forceinline__ void prep_walk_body(const T* __restrict__ img, ptrdif
 }
 
 // T = float: every wave takes the per-lane form (prep_walk_body<KS, false>): a block of KS + 1 raw f32 rows in flight
-// would be (KS + 1)^2 registers per lane.
+// would be (KS + 1)^2 registers per lane.  16-bit rows take the block form at twice the 8-bit registers.
 template <int KS, typename T = uint8_t>
 __global__ __launch_bounds__(256) void k_prep_walk(const T* __restrict__ src, ptrdiff_t row_stride,
                                                     ptrdiff_t img_stride, int W, int H, int wk, int hk, double scale_x,
                                                     double scale_y, int seg_rows, nsof_blur_taps t, float* __restrict__ out)
 {
-    constexpr int R = KS / 2, NB = KS + 1, ND = (NB + 3) / 4;
+    constexpr int R = KS / 2, NB = KS + 1, PPD = kPPD<T>, ND = (NB + PPD - 1) / PPD;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int dy0 = (blockIdx.y * 4 + wave) * seg_rows;
     if (dy0 >= hk) return;                                        // wave-uniform
@@ -825,9 +859,9 @@ __global__ __launch_bounds__(256) void k_prep_walk(const T* __restrict__ src, pt
     float a1;
     lin_coord_x(dx, scale_x, W, sx, a1);
     const int c0 = sx, c1 = min(sx + 1, W - 1);
-    const bool fast = c0 - R >= 0 && c0 - R + 4 * ND <= W && c1 == c0 + 1;
-    if (kU8<T> && __all(fast))
-        prep_walk_body<KS, kU8<T>, T>(img, row_stride, W, H, wk, hk, scale_y, dy0, dy_end, dx, live, c0, c1, true, a1, t, dst);
+    const bool fast = c0 - R >= 0 && c0 - R + PPD * ND <= W && c1 == c0 + 1;
+    if (kInt<T> && __all(fast))
+        prep_walk_body<KS, kInt<T>, T>(img, row_stride, W, H, wk, hk, scale_y, dy0, dy_end, dx, live, c0, c1, true, a1, t, dst);
     else
         prep_walk_body<KS, false, T>(img, row_stride, W, H, wk, hk, scale_y, dy0, dy_end, dx, live, c0, c1, fast, a1, t, dst);
 }
@@ -846,7 +880,7 @@ __global__ __launch_bounds__(256) void k_prep_rows(const T* __restrict__ src, pt
                                                     ptrdiff_t img_stride, int W, int H, int wk, double scale_x,
                                                     nsof_blur_taps t, float* __restrict__ HA)
 {
-    constexpr int R = KS / 2, ND = (KS + 3) / 4;
+    constexpr int R = KS / 2, PPD = kPPD<T>, ND = (KS + PPD - 1) / PPD;
     const int j = blockIdx.x * 64 + (threadIdx.x & 63);
     const int rbase = (blockIdx.y * 4 + (threadIdx.x >> 6)) * PREPA_ROWS;
     if (j >= 2 * wk || rbase >= H) return;
@@ -854,7 +888,7 @@ __global__ __launch_bounds__(256) void k_prep_rows(const T* __restrict__ src, pt
     float a;
     lin_coord_x(j >> 1, scale_x, W, sx, a);
     const int c = (j & 1) ? min(sx + 1, W - 1) : sx;
-    const bool fast = c - R >= 0 && c - R + 4 * ND <= W;
+    const bool fast = c - R >= 0 && c - R + PPD * ND <= W;
     auto tk = [&](int q) { return t.k[q]; };
     const T* img = srow(src, blockIdx.z, img_stride);
     float* dst = HA + ((size_t)blockIdx.z * H) * (2 * wk) + j;
@@ -865,14 +899,14 @@ __global__ __launch_bounds__(256) void k_prep_rows(const T* __restrict__ src, pt
         const T* rowp = srow(img, r, row_stride);
         float b[KS];
         if (fast) {
-            if constexpr (kU8<T>) {
+            if constexpr (kInt<T>) {
 #pragma unroll
                 for (int d = 0; d < ND; d++) {
                     unsigned v;
-                    __builtin_memcpy(&v, rowp + (c - R) + 4 * d, 4);   // unaligned dword load
+                    __builtin_memcpy(&v, rowp + (c - R) + PPD * d, 4);   // unaligned dword load
 #pragma unroll
-                    for (int e = 0; e < 4; e++)
-                        if (4 * d + e < KS) b[4 * d + e] = (float)((v >> (8 * e)) & 0xffu);
+                    for (int e = 0; e < PPD; e++)
+                        if (PPD * d + e < KS) b[PPD * d + e] = px_el<T>(v, e);
                 }
             } else {
 #pragma unroll
@@ -1137,25 +1171,25 @@ __global__ __launch_bounds__(256) void k_polyexp(const float* __restrict__ img, 
 // the launch bound asks for the 80 SGPRs, paid with a few scalar taps kept in VGPR lanes (v_readlane in the loop).
 // tests/test_codeobj_polyexp_budget.py holds the code object to that budget.
 // ---------------------------------------------------------------------------------------
-// U8 (the full-resolution level): the level image is not read from memory but formed in the vertical pass from the
-// 8-bit frame itself -- the 3 x 3 [k1 k0 k1] smoothing of k_prep_same3_vec, operation for operation -- so the
-// pyramid kernel of level 0 and the 8 B/px its image costs (written there, read here) disappear; the vertical-pass
-// waves have the issue slots for it (187 of their step's ~500 instruction slots were used).
-struct PolyU8 {
+// FRAME (the full-resolution level): the level image is not read from memory but formed in the vertical pass from the
+// integer frame itself (SRC: uint8_t, uint16_t or int16_t pixels) -- the 3 x 3 [k1 k0 k1] smoothing of k_prep_same3_vec,
+// operation for operation -- so the pyramid kernel of level 0 and the 8 B/px its image costs (written there, read here)
+// disappear; the vertical-pass waves have the issue slots for it (187 of their step's ~500 instruction slots were used).
+struct PolyFrame {
     const uint8_t* src0;   // images [0, nsplit) at src0 + z * img_stride, the others at src1 + (z - nsplit) * img_stride
-    const uint8_t* src1;
+    const uint8_t* src1;   // (byte addresses)
     long long row_stride, img_stride;
     int nsplit;
     float k0, k1;          // centre and side tap
 };
-template <int N, bool HET, bool U8 = false>
+template <int N, bool HET, bool FRAME = false, typename SRC = uint8_t>
 __global__ __launch_bounds__(512, N <= 7 ? 8 : 1) void k_polyexp_rs(const float* __restrict__ img, float* __restrict__ R, int W, int H,
                                                      int seg_rows, nsof_poly_taps tp,
-                                                     const nsof_het_item* __restrict__ items, PolyU8 u8 = PolyU8{})
+                                                     const nsof_het_item* __restrict__ items, PolyFrame fr = PolyFrame{})
 {
     using G = PolyGeom<N>;
     size_t img_off, r_off;   // element offsets of this image / its expansion
-    const uint8_t* sb = nullptr;   // U8: this image's frame
+    const uint8_t* sb = nullptr;   // FRAME: this image's frame (byte address)
     long long srs = 0;
     if constexpr (HET) {
         const nsof_het_item& it = items[blockIdx.z >> 1];
@@ -1165,17 +1199,17 @@ __global__ __launch_bounds__(512, N <= 7 ? 8 : 1) void k_polyexp_rs(const float*
         if (blockIdx.x * G::SW >= W || blockIdx.y * seg_rows >= H) return;   // block-uniform, before any barrier
         img_off = it.offI + which * (size_t)W * H;
         r_off = it.offR + which * 5 * (size_t)W * H;
-        if constexpr (U8) {
+        if constexpr (FRAME) {
             sb = it.src[which];
             srs = it.src_stride[which];
         }
     } else {
         img_off = (size_t)blockIdx.z * W * H;
         r_off = (size_t)blockIdx.z * 5 * W * H;
-        if constexpr (U8) {
+        if constexpr (FRAME) {
             const int z = blockIdx.z;
-            sb = z < u8.nsplit ? u8.src0 + (ptrdiff_t)z * u8.img_stride : u8.src1 + (ptrdiff_t)(z - u8.nsplit) * u8.img_stride;
-            srs = u8.row_stride;
+            sb = z < fr.nsplit ? fr.src0 + (ptrdiff_t)z * fr.img_stride : fr.src1 + (ptrdiff_t)(z - fr.nsplit) * fr.img_stride;
+            srs = fr.row_stride;
         }
     }
     __shared__ __attribute__((aligned(16))) float sr[2][3][4][256];
@@ -1196,18 +1230,19 @@ __global__ __launch_bounds__(512, N <= 7 ? 8 : 1) void k_polyexp_rs(const float*
         auto ld = [&](int row) {
             return *reinterpret_cast<const float*>(Ib + ((unsigned)clampi(row, 0, H - 1) * (unsigned)W + (unsigned)xc) * 4u);
         };
-        // U8: I[rc][xc] from the frame.  The rows are asked for in order, so the row-filtered values of rows rc - 1, rc,
+        // FRAME: I[rc][xc] from the frame.  The rows are asked for in order, so the row-filtered values of rows rc - 1, rc,
         // rc + 1 (reflected at the image border like the pyramid kernel's) are kept and one new row is filtered per
         // new rc; fetch3() only issues the loads of a row's three bytes (four rows ahead, like the float loads).
-        const int xl = U8 ? reflect101(xc - 1, W) : 0, xr = U8 ? reflect101(xc + 1, W) : 0;
+        const int xl = FRAME ? reflect101(xc - 1, W) : 0, xr = FRAME ? reflect101(xc + 1, W) : 0;
+        using RawPx = std::conditional_t<std::is_signed<SRC>::value, int, unsigned>;   // exact: sign- / zero-extended
         struct Raw3 {
-            unsigned l, c, r;
+            RawPx l, c, r;
         };
         auto fetch3 = [&](int srow) {   // srow: a row of the frame
-            const uint8_t* rp = sb + (ptrdiff_t)srow * srs;
+            const SRC* rp = reinterpret_cast<const SRC*>(sb + (ptrdiff_t)srow * srs);
             return Raw3{rp[xl], rp[xc], rp[xr]};
         };
-        auto hval = [&](const Raw3& q) { return NSOF_MADD((float)q.l + (float)q.r, u8.k1, (float)q.c * u8.k0); };
+        auto hval = [&](const Raw3& q) { return NSOF_MADD((float)q.l + (float)q.r, fr.k1, (float)q.c * fr.k0); };
         int rc_cur = 0;
         float hm = 0.f, h0 = 0.f, hp = 0.f, icur = 0.f;
         auto below = [&](int row) { return reflect101(clampi(row, 0, H - 1) + 1, H); };   // the frame row under clamp(row)
@@ -1217,7 +1252,7 @@ __global__ __launch_bounds__(512, N <= 7 ? 8 : 1) void k_polyexp_rs(const float*
                 hm = h0;
                 h0 = hp;
                 hp = hval(under);
-                icur = NSOF_MADD(hm + hp, u8.k1, h0 * u8.k0);
+                icur = NSOF_MADD(hm + hp, fr.k1, h0 * fr.k0);
                 rc_cur = rc;
             }
             return icur;
@@ -1225,12 +1260,12 @@ __global__ __launch_bounds__(512, N <= 7 ? 8 : 1) void k_polyexp_rs(const float*
         float win[2 * N + 1];   // win[j] = I[clamp(y - N + j)][xc]
         float pre[4];
         Raw3 praw[4];
-        if constexpr (U8) {
+        if constexpr (FRAME) {
             rc_cur = clampi(ys - N, 0, H - 1);
             hm = hval(fetch3(reflect101(rc_cur - 1, H)));
             h0 = hval(fetch3(rc_cur));
             hp = hval(fetch3(reflect101(rc_cur + 1, H)));
-            icur = NSOF_MADD(hm + hp, u8.k1, h0 * u8.k0);
+            icur = NSOF_MADD(hm + hp, fr.k1, h0 * fr.k0);
             win[0] = icur;
 #pragma unroll
             for (int j = 1; j <= 2 * N; j++) win[j] = advance(ys - N + j, fetch3(below(ys - N + j)));
@@ -1248,7 +1283,7 @@ __global__ __launch_bounds__(512, N <= 7 ? 8 : 1) void k_polyexp_rs(const float*
                 float nxt[4];
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
-                    if constexpr (U8) praw[q] = fetch3(below(y + 5 + N + q));
+                    if constexpr (FRAME) praw[q] = fetch3(below(y + 5 + N + q));
                     else nxt[q] = ld(y + 5 + N + q);
                 }
 #pragma unroll
@@ -1272,7 +1307,7 @@ __global__ __launch_bounds__(512, N <= 7 ? 8 : 1) void k_polyexp_rs(const float*
                 }
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
-                    if constexpr (U8) pre[q] = advance(y + 5 + N + q, praw[q]);
+                    if constexpr (FRAME) pre[q] = advance(y + 5 + N + q, praw[q]);
                     else pre[q] = nxt[q];
                 }
             }
@@ -1739,9 +1774,9 @@ __global__ __launch_bounds__(256) void k_flow_upsample_walk(const float* __restr
     }
 }
 
-template <int N>
+template <int N, typename SRC = uint8_t>
 void launch_polyexp_n(nsof_ctx* ctx, int n_img, const float* img, int W, int H, const nsof_poly_taps& taps, float* R,
-                      const PolyU8* u8 = nullptr)
+                      const PolyFrame* fr = nullptr)
 {
     using G = PolyGeom<N>;
     const int strips = (W + G::SW - 1) / G::SW;
@@ -1753,8 +1788,8 @@ void launch_polyexp_n(nsof_ctx* ctx, int n_img, const float* img, int W, int H, 
     int seg_rows = ((H + segs - 1) / segs + 3) / 4 * 4;
     segs = (H + seg_rows - 1) / seg_rows;
     dim3 grid(strips, segs, n_img);
-    if (u8)
-        hipLaunchKernelGGL((k_polyexp_rs<N, false, true>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, nullptr, *u8);
+    if (fr)
+        hipLaunchKernelGGL((k_polyexp_rs<N, false, true, SRC>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, nullptr, *fr);
     else if (ctx->opt_polyexp_f32)
         hipLaunchKernelGGL((k_polyexp<N>), grid, dim3(256), 0, ctx->stream, img, R, W, H, seg_rows, taps, nullptr);
     else
@@ -1762,9 +1797,9 @@ void launch_polyexp_n(nsof_ctx* ctx, int n_img, const float* img, int W, int H, 
 }
 
 // Work-list twin: W, H are the largest level extents over the table, n_img = 2 * items.
-template <int N>
+template <int N, typename SRC = uint8_t>
 void launch_polyexp_het_n(nsof_ctx* ctx, int n_img, const nsof_het_item* items, const float* img, int W, int H,
-                          const nsof_poly_taps& taps, float* R, const PolyU8* u8 = nullptr)
+                          const nsof_poly_taps& taps, float* R, const PolyFrame* fr = nullptr)
 {
     using G = PolyGeom<N>;
     const int strips = (W + G::SW - 1) / G::SW;
@@ -1773,7 +1808,7 @@ void launch_polyexp_het_n(nsof_ctx* ctx, int n_img, const nsof_het_item* items, 
     int seg_rows = ((H + segs - 1) / segs + 3) / 4 * 4;
     segs = (H + seg_rows - 1) / seg_rows;
     dim3 grid(strips, segs, n_img);
-    if (u8) hipLaunchKernelGGL((k_polyexp_rs<N, true, true>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, items, *u8);
+    if (fr) hipLaunchKernelGGL((k_polyexp_rs<N, true, true, SRC>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, items, *fr);
     else hipLaunchKernelGGL((k_polyexp_rs<N, true>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, items);
 }
 
@@ -1786,12 +1821,15 @@ void launch_polyexp_het_n(nsof_ctx* ctx, int n_img, const nsof_het_item* items, 
 // when the frames do not decimate exactly by 8 (or are not aligned for the vector walks): the caller then runs the
 // levels one by one.  out[k - 1]: level k's images, [n_img][H >> k][W >> k].
 namespace {
-int prep_decim3_impl(nsof_ctx* ctx, int n_img, const uint8_t* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H,
+template <typename T>
+int prep_decim3_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H,
                      const nsof_blur_taps* taps, float* const* out)
 {
-    const int CWL = (W & 15) == 0 ? 16 : 8;
-    const bool ok = (W & 7) == 0 && (H & 7) == 0 && W >= 64 && H > 19 && (row_stride % CWL) == 0 && (img_stride % CWL) == 0 &&
-                    (reinterpret_cast<uintptr_t>(src) % CWL) == 0 && taps[0].ksize == 3 && taps[1].ksize == 9 &&
+    // 16-bit frames take 8-column lanes: with 16 the three walks need 175 registers more than the 168 a wave has here
+    const int CWL = (W & 15) == 0 && kU8<T> ? 16 : 8;
+    const int AL = kU8<T> ? CWL : 8;   // the walks' row loads: a lane's CWL bytes (u8) / 8-byte quads (16-bit)
+    const bool ok = (W & 7) == 0 && (H & 7) == 0 && W >= 64 && H > 19 && (row_stride % AL) == 0 && (img_stride % AL) == 0 &&
+                    (reinterpret_cast<uintptr_t>(src) % AL) == 0 && taps[0].ksize == 3 && taps[1].ksize == 9 &&
                     taps[2].ksize == 19 && n_img <= 65535;
     if (!ok) return NSOF_EUNSUPPORTED;
     nsof_prof_scope ps(ctx, NSOF_K_PREP);
@@ -1810,8 +1848,12 @@ int prep_decim3_impl(nsof_ctx* ctx, int n_img, const uint8_t* src, ptrdiff_t row
     d.seg_rows[2] = src_rows / 8;
     const int nseg = (H / 8 + d.seg_rows[2] - 1) / d.seg_rows[2];
     dim3 grid((unsigned)waves_x, (nseg + 3) / 4, n_img);
-    if (CWL == 16) hipLaunchKernelGGL(k_prep_decim3<16>, grid, dim3(768), 0, ctx->stream, src, row_stride, img_stride, W, H, d);
-    else hipLaunchKernelGGL(k_prep_decim3<8>, grid, dim3(768), 0, ctx->stream, src, row_stride, img_stride, W, H, d);
+    if constexpr (kU8<T>) {
+        if (CWL == 16) hipLaunchKernelGGL((k_prep_decim3<16, T>), grid, dim3(768), 0, ctx->stream, src, row_stride, img_stride, W, H, d);
+        else hipLaunchKernelGGL((k_prep_decim3<8, T>), grid, dim3(768), 0, ctx->stream, src, row_stride, img_stride, W, H, d);
+    } else {
+        hipLaunchKernelGGL((k_prep_decim3<8, T>), grid, dim3(768), 0, ctx->stream, src, row_stride, img_stride, W, H, d);
+    }
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
@@ -1821,8 +1863,8 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
               const nsof_blur_taps& taps, float* out)
 {
     nsof_prof_scope ps(ctx, NSOF_K_PREP);
-    // the 4-pixel lanes' vector row loads: a dword (u8) / 16 bytes (f32) at every 4th column
-    const int VA = kU8<T> ? 4 : 16;
+    // the 4-pixel lanes' vector row loads: a dword (u8) / 8 bytes (16-bit) / 16 bytes (f32) at every 4th column
+    const int VA = 4 * (int)sizeof(T);
     const bool rows_va = (row_stride % VA) == 0 && (img_stride % VA) == 0 && (reinterpret_cast<uintptr_t>(src) % VA) == 0;
     if (wk == W && hk == H) {
         const bool aligned = (W & 3) == 0 && rows_va && W >= 8;
@@ -1847,10 +1889,11 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
         // exact decimation by 2 / 4 / 8 with the kernel sizes the pyr_scale 0.5 pyramid produces
         const int S = W / wk;
         const int CWL = (W & 15) == 0 ? 16 : 8;   // source columns per lane
-        // f32: 16-byte aligned rows (float4 loads); 8-column lanes only while the blur halo fits in one (S = 2, 4)
+        // 16-bit / f32: 8- / 16-byte aligned rows (4-pixel vector loads); f32 takes 8-column lanes only while the blur
+        // halo fits in one (S = 2, 4)
         const bool decim_al = kU8<T> ? (row_stride % CWL) == 0 && (img_stride % CWL) == 0 &&
                                            (reinterpret_cast<uintptr_t>(src) % CWL) == 0
-                                     : rows_va && (CWL == 16 || S <= 4);
+                                     : rows_va && (CWL == 16 || S <= 4 || sizeof(T) == 2);
         const bool decim_ok = S >= 2 && W == S * wk && H == S * hk && (W % CWL) == 0 && W >= 64 && decim_al &&
                               ((S == 2 && taps.ksize == 3) || (S == 4 && taps.ksize == 9) ||
                                (S == 8 && taps.ksize == 19)) &&
@@ -1883,7 +1926,7 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
             } else {
                 if (S == 2) NSOF_DECIM(2, 3, 8);
                 else if (S == 4) NSOF_DECIM(4, 9, 8);
-                else if constexpr (kU8<T>) NSOF_DECIM(8, 19, 8);
+                else if constexpr (sizeof(T) <= 2) NSOF_DECIM(8, 19, 8);
             }
 #undef NSOF_DECIM
         } else if (scale_x >= 1.0 && scale_y >= 1.0 && scale_y < taps.ksize &&
@@ -1953,34 +1996,69 @@ int NSOF_PYR_NAME(nsof_launch_prep_decim3)(nsof_ctx* ctx, int n_img, const void*
 {
     // f32 frames take the three one-level launches (k_prep_decim<.., float>): at 768 threads per workgroup a wave has
     // 168 registers, and the float rows of the three walks side by side spilled (~400 registers' worth to scratch)
-    if (src_type == NSOF_SRC_F32) return NSOF_EUNSUPPORTED;
-    return prep_decim3_impl(ctx, n_img, static_cast<const uint8_t*>(src), row_stride, img_stride, W, H, taps, out);
+    switch (src_type) {
+        case NSOF_SRC_U8: return prep_decim3_impl(ctx, n_img, static_cast<const uint8_t*>(src), row_stride, img_stride, W, H, taps, out);
+        case NSOF_SRC_U16: return prep_decim3_impl(ctx, n_img, static_cast<const uint16_t*>(src), row_stride, img_stride, W, H, taps, out);
+        case NSOF_SRC_S16: return prep_decim3_impl(ctx, n_img, static_cast<const int16_t*>(src), row_stride, img_stride, W, H, taps, out);
+        default: return NSOF_EUNSUPPORTED;
+    }
 }
 
 int NSOF_PYR_NAME(nsof_launch_prep)(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
                                     int H, int wk, int hk, const nsof_blur_taps& taps, float* out, int src_type)
 {
-    if (src_type == NSOF_SRC_F32)
-        return prep_impl(ctx, n_img, static_cast<const float*>(src), row_stride, img_stride, W, H, wk, hk, taps, out);
-    return prep_impl(ctx, n_img, static_cast<const uint8_t*>(src), row_stride, img_stride, W, H, wk, hk, taps, out);
+    switch (src_type) {
+        case NSOF_SRC_F32: return prep_impl(ctx, n_img, static_cast<const float*>(src), row_stride, img_stride, W, H, wk, hk, taps, out);
+        case NSOF_SRC_U16: return prep_impl(ctx, n_img, static_cast<const uint16_t*>(src), row_stride, img_stride, W, H, wk, hk, taps, out);
+        case NSOF_SRC_S16: return prep_impl(ctx, n_img, static_cast<const int16_t*>(src), row_stride, img_stride, W, H, wk, hk, taps, out);
+        default: return prep_impl(ctx, n_img, static_cast<const uint8_t*>(src), row_stride, img_stride, W, H, wk, hk, taps, out);
+    }
 }
 
 #ifndef NSOF_PYR_FMA
-// The expansion of the full-resolution level straight from the 8-bit frames (k_polyexp_rs<.., U8>): images [0, nsplit)
-// at src0 + z * img_stride, the rest at src1; k0 / k1 = centre / side tap of the level's 3-tap smoothing.
-int nsof_launch_polyexp_u8(nsof_ctx* ctx, int n_img, const uint8_t* src0, const uint8_t* src1, int nsplit, ptrdiff_t row_stride,
-                           ptrdiff_t img_stride, int W, int H, const nsof_poly_taps& taps, float k0, float k1, float* R)
+// The expansion of the full-resolution level straight from the integer frames (k_polyexp_rs<.., FRAME, SRC>): images
+// [0, nsplit) at src0 + z * img_stride, the rest at src1; k0 / k1 = centre / side tap of the level's 3-tap smoothing.
+namespace {
+template <typename SRC>
+int polyexp_fused_impl(nsof_ctx* ctx, int n_img, const PolyFrame& fr, int W, int H, const nsof_poly_taps& taps, float* R)
 {
-    nsof_prof_scope ps(ctx, NSOF_K_POLYEXP);
-    const PolyU8 u8{src0, src1, (long long)row_stride, (long long)img_stride, nsplit, k0, k1};
     switch (taps.n) {
-#define NSOF_PU(NN) case NN: launch_polyexp_n<NN>(ctx, n_img, nullptr, W, H, taps, R, &u8); break
+#define NSOF_PU(NN) case NN: launch_polyexp_n<NN, SRC>(ctx, n_img, nullptr, W, H, taps, R, &fr); break
         NSOF_PU(1); NSOF_PU(2); NSOF_PU(3); NSOF_PU(4); NSOF_PU(5); NSOF_PU(6); NSOF_PU(7); NSOF_PU(8); NSOF_PU(9); NSOF_PU(10);
 #undef NSOF_PU
         default: return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "poly_n=%d outside 1..%d", taps.n, NSOF_MAX_POLY_N);
     }
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
+}
+template <typename SRC>
+int polyexp_het_impl(nsof_ctx* ctx, int nz, const nsof_het_item* d_items, int max_w, int max_h, const nsof_poly_taps& taps,
+                     const float* I, float* R, const PolyFrame* fr)
+{
+    switch (taps.n) {
+#define NSOF_PH(NN) case NN: launch_polyexp_het_n<NN, SRC>(ctx, nz, d_items, I, max_w, max_h, taps, R, fr); break
+        NSOF_PH(1); NSOF_PH(2); NSOF_PH(3); NSOF_PH(4); NSOF_PH(5); NSOF_PH(6); NSOF_PH(7); NSOF_PH(8); NSOF_PH(9); NSOF_PH(10);
+#undef NSOF_PH
+        default: return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "poly_n=%d outside 1..%d", taps.n, NSOF_MAX_POLY_N);
+    }
+    NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
+}
+}  // namespace
+
+int nsof_launch_polyexp_frames(nsof_ctx* ctx, int n_img, const void* src0, const void* src1, int nsplit, ptrdiff_t row_stride,
+                           ptrdiff_t img_stride, int W, int H, const nsof_poly_taps& taps, float k0, float k1, float* R,
+                           int src_type)
+{
+    nsof_prof_scope ps(ctx, NSOF_K_POLYEXP);
+    const PolyFrame fr{static_cast<const uint8_t*>(src0), static_cast<const uint8_t*>(src1), (long long)row_stride,
+                    (long long)img_stride, nsplit, k0, k1};
+    switch (src_type) {
+        case NSOF_SRC_U8: return polyexp_fused_impl<uint8_t>(ctx, n_img, fr, W, H, taps, R);
+        case NSOF_SRC_U16: return polyexp_fused_impl<uint16_t>(ctx, n_img, fr, W, H, taps, R);
+        case NSOF_SRC_S16: return polyexp_fused_impl<int16_t>(ctx, n_img, fr, W, H, taps, R);
+        default: return nsof_set_error(ctx, NSOF_EINVAL, "fused level 0 takes integer frames only");
+    }
 }
 
 int nsof_launch_polyexp(nsof_ctx* ctx, int n_img, const float* img, int W, int H, const nsof_poly_taps& taps, float* R)
@@ -2060,8 +2138,10 @@ int NSOF_PYR_NAME(nsof_launch_flow_upsample)(nsof_ctx* ctx, int n_pairs, const f
 // work-list (shape-heterogeneous) launchers: one launch per stage and level over a device table
 // =========================================================================================
 namespace {
-// T: the pixel type of every item's frames (the list's src_type).  Kernel choice as for 8-bit items; with float frames
-// NSOF_HET_VEC0 means 16-byte aligned rows (k_prep_same3_vec's float4 loads), the scalar k_prep_same takes the rest.
+// T: the pixel type of every item's frames (the list's src_type).  Kernel choice as for 8-bit items; with 16-bit / float
+// frames NSOF_HET_VEC0 means 8- / 16-byte aligned rows (k_prep_same3_vec's 4-pixel loads), the scalar k_prep_same takes
+// the rest.  The LDS-tiled kernel's budget is 60 KB, and 78 KB for 16-bit frames: the 19-tap scale-8 level of large
+// crops needs ~75 KB at 2 B/px (50 KB at 1), and two workgroups still fit the CU's 160 KB.
 template <typename T>
 int prep_het_impl(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items, bool level0,
                   const nsof_blur_taps& taps, float* I)
@@ -2104,11 +2184,16 @@ int prep_het_impl(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, cons
             else
                 hipLaunchKernelGGL((k_prep_direct<5, true, T>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1.,
                                    1., taps, I, d_items);
-        } else if (smem <= 60 * 1024) {
+        } else if (smem <= (sizeof(T) == 2 ? 78 : 60) * 1024) {
             dim3 grid((max_wk + PREP_TW - 1) / PREP_TW, (max_hk + PREP_TH - 1) / PREP_TH, nz);
-#define PREP_TILED_HET(KS)                                                                                       \
-    hipLaunchKernelGGL((k_prep_tiled<KS, true, T>), grid, dim3(256), smem, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1., \
-                       rw_cap, rh_cap, taps, I, d_items)
+#define PREP_TILED_HET(KS)                                                                                                \
+    do {                                                                                                                  \
+        auto kern = k_prep_tiled<KS, true, T>;                                                                            \
+        if (smem > 64 * 1024)                                                                                             \
+            NSOF_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
+        hipLaunchKernelGGL(kern, grid, dim3(256), smem, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1., rw_cap, rh_cap,  \
+                           taps, I, d_items);                                                                             \
+    } while (0)
             switch (taps.ksize) {
                 case 9: PREP_TILED_HET(9); break;
                 case 19: PREP_TILED_HET(19); break;
@@ -2129,29 +2214,30 @@ int prep_het_impl(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, cons
 int NSOF_PYR_NAME(nsof_launch_prep_het)(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items,
                          bool level0, const nsof_blur_taps& taps, float* I, int src_type)
 {
-    if (src_type == NSOF_SRC_F32) return prep_het_impl<float>(ctx, n_items, d_items, h_items, level0, taps, I);
-    return prep_het_impl<uint8_t>(ctx, n_items, d_items, h_items, level0, taps, I);
+    switch (src_type) {
+        case NSOF_SRC_F32: return prep_het_impl<float>(ctx, n_items, d_items, h_items, level0, taps, I);
+        case NSOF_SRC_U16: return prep_het_impl<uint16_t>(ctx, n_items, d_items, h_items, level0, taps, I);
+        case NSOF_SRC_S16: return prep_het_impl<int16_t>(ctx, n_items, d_items, h_items, level0, taps, I);
+        default: return prep_het_impl<uint8_t>(ctx, n_items, d_items, h_items, level0, taps, I);
+    }
 }
 
 #ifndef NSOF_PYR_FMA
 // blur3: non-null at the full-resolution level = form the level image from the items' own frames (k0, k1 = centre / side
 // tap); I is not read then.
+// src_type: the items' pixel type (read only with blur3: 8- or 16-bit).
 int nsof_launch_polyexp_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
-                            const nsof_poly_taps& taps, const float* I, float* R, const float* blur3)
+                            const nsof_poly_taps& taps, const float* I, float* R, const float* blur3, int src_type)
 {
     nsof_prof_scope ps(ctx, NSOF_K_POLYEXP);
     const int nz = 2 * n_items;
-    PolyU8 u8v{};
-    if (blur3) { u8v.k0 = blur3[0]; u8v.k1 = blur3[1]; }
-    const PolyU8* u8 = blur3 ? &u8v : nullptr;
-    switch (taps.n) {
-#define NSOF_PH(NN) case NN: launch_polyexp_het_n<NN>(ctx, nz, d_items, I, max_w, max_h, taps, R, u8); break
-        NSOF_PH(1); NSOF_PH(2); NSOF_PH(3); NSOF_PH(4); NSOF_PH(5); NSOF_PH(6); NSOF_PH(7); NSOF_PH(8); NSOF_PH(9); NSOF_PH(10);
-#undef NSOF_PH
-        default: return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "poly_n=%d outside 1..%d", taps.n, NSOF_MAX_POLY_N);
-    }
-    NSOF_HIP(ctx, hipGetLastError());
-    return NSOF_OK;
+    PolyFrame frv{};
+    if (blur3) { frv.k0 = blur3[0]; frv.k1 = blur3[1]; }
+    const PolyFrame* fr = blur3 ? &frv : nullptr;
+    if (blur3 && src_type == NSOF_SRC_U16) return polyexp_het_impl<uint16_t>(ctx, nz, d_items, max_w, max_h, taps, I, R, fr);
+    if (blur3 && src_type == NSOF_SRC_S16) return polyexp_het_impl<int16_t>(ctx, nz, d_items, max_w, max_h, taps, I, R, fr);
+    if (blur3 && src_type == NSOF_SRC_F32) return nsof_set_error(ctx, NSOF_EINVAL, "fused level 0 takes integer frames only");
+    return polyexp_het_impl<uint8_t>(ctx, nz, d_items, max_w, max_h, taps, I, R, fr);
 }
 
 #endif  // !NSOF_PYR_FMA

@@ -497,10 +497,12 @@ static int stage_pyr_level(nsof_ctx* ctx, int src, int n_img, const void* d_src,
                            ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out)
 {
     if (!ctx || !d_src || !d_out || n_img < 1) return NSOF_EINVAL;
-    if (src == NSOF_SRC_F32 && (width < 1 || row_stride < (ptrdiff_t)width * 4 || (row_stride & 3) || (img_stride & 3) ||
-                                (reinterpret_cast<uintptr_t>(d_src) & 3)))
-        return nsof_set_error(ctx, NSOF_EINVAL, "f32 frames: strides must be multiples of 4 bytes, row_stride >= 4*width, "
-                                                "pointer 4-byte aligned");
+    if (!nsof_src_valid(src)) return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", src);
+    const int pb = nsof_src_bytes(src);
+    if (pb > 1 && (width < 1 || row_stride < (ptrdiff_t)width * pb || (row_stride % pb) || (img_stride % pb) ||
+                   (reinterpret_cast<uintptr_t>(d_src) % pb)))
+        return nsof_set_error(ctx, NSOF_EINVAL, "%d-byte frames: strides must be multiples of %d bytes, row_stride >= %d*width, "
+                                                "pointer %d-byte aligned", pb, pb, pb, pb);
     int wk, hk;
     nsof_blur_taps taps;
     if (int rc = nsof_level_geom(ctx, width, height, pyr_scale, level, &wk, &hk, &taps)) return rc;
@@ -519,6 +521,12 @@ extern "C" int nsof_stage_pyr_level_f32(nsof_ctx* ctx, int n_img, const float* d
                                         float* d_out)
 {
     return stage_pyr_level(ctx, NSOF_SRC_F32, n_img, d_src, row_stride, img_stride, width, height, pyr_scale, level, d_out);
+}
+
+extern "C" int nsof_stage_pyr_level_px(nsof_ctx* ctx, int pixel_type, int n_img, const void* d_src, ptrdiff_t row_stride,
+                                       ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out)
+{
+    return stage_pyr_level(ctx, pixel_type, n_img, d_src, row_stride, img_stride, width, height, pyr_scale, level, d_out);
 }
 
 __global__ void k_recip_probe(long long n, const double* __restrict__ x, double* __restrict__ fast, double* __restrict__ ieee)
@@ -641,7 +649,7 @@ static Carve farneback_carve(size_t B, bool sequence, int width, int height, dou
 // Core of both device entry points.  sequence == false: n_pairs independent pairs (d_prev[i], d_next[i]);
 // sequence == true: n_pairs + 1 consecutive frames in d_prev (d_next unused), pair i = (frame i, frame i+1) -- every
 // frame's pyramid level and polynomial expansion is then computed once and shared by the two pairs it belongs to.
-// src (nsof_src_type): 8-bit or float frames.  Only the pyramid stage reads the frames; the frame pointers below are
+// src (nsof_src_type): 8-bit, 16-bit or float frames.  Only the pyramid stage reads the frames; the frame pointers below are
 // byte addresses and both strides are in bytes whatever the pixel type.
 int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* prev_frames, const void* next_frames,
                           ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height, float* d_flow,
@@ -654,7 +662,7 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     if (!d_prev || !d_next || !d_flow || n_pairs < 1) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer or n_pairs<1");
     int rc = nsof_check_farneback_params(ctx, width, height, pyr_scale, levels, winsize, iterations, poly_n, flags);
     if (rc) return rc;
-    const int px_bytes = src == NSOF_SRC_F32 ? 4 : 1;
+    const int px_bytes = nsof_src_bytes(src);
     if (row_stride < (ptrdiff_t)width * px_bytes) return nsof_set_error(ctx, NSOF_EINVAL, "row_stride < width * %d", px_bytes);
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const nsof_iter_form form = nsof_iterate_form(ctx, winsize, width, height, iterations,
@@ -755,20 +763,20 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
         return NSOF_OK;
     };
 
-    // Level 0 (the frame's own size, 3-tap smoothing): the expansion kernel forms the level image itself from the 8-bit
-    // frames (k_polyexp_rs<.., U8>): no pyramid launch, no image written and read back.  Not with the FMA twin of the
-    // pyramid stages nor with the float expansion (their kernels have no such form), nor for f32 frames: those take the
-    // two-kernel form (k_prep_same3_vec<.., float>, then the expansion of the level image).
-    const bool poly_u8 = src == NSOF_SRC_U8 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && width >= 2 && height >= 2;
+    // Level 0 (the frame's own size, 3-tap smoothing): the expansion kernel forms the level image itself from the 8- or
+    // 16-bit frames (k_polyexp_rs<.., FRAME, SRC>): no pyramid launch, no image written and read back.  Not with the FMA
+    // twin of the pyramid stages nor with the float expansion (their kernels have no such form), nor for f32 frames:
+    // those take the two-kernel form (k_prep_same3_vec<.., float>, then the expansion of the level image).
+    const bool poly_frames = src != NSOF_SRC_F32 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && width >= 2 && height >= 2;
     float* Ifused[4] = {nullptr, nullptr, nullptr, nullptr};   // level images already made by the three-level launch
     // pyramid level + expansion of level k on the current ctx->stream, into the level's slot
     auto level_images = [&](int k, int wk, int hk, const nsof_blur_taps& bt) -> int {
         float* Rk = level_R(k);
         if (k >= 1 && k <= 3 && Ifused[k]) return nsof_launch_polyexp(ctx, (int)n_img, Ifused[k], wk, hk, ptaps, Rk);
-        if (poly_u8 && k == 0 && bt.ksize == 3 && wk == width && hk == height) {
+        if (poly_frames && k == 0 && bt.ksize == 3 && wk == width && hk == height) {
             const bool one = sequence || prep_merged;
-            return nsof_launch_polyexp_u8(ctx, (int)n_img, d_prev, one ? d_prev : d_next, one ? (int)n_img : n_pairs, row_stride,
-                                          pair_stride, width, height, ptaps, bt.k[1], bt.k[2], Rk);
+            return nsof_launch_polyexp_frames(ctx, (int)n_img, d_prev, one ? d_prev : d_next, one ? (int)n_img : n_pairs, row_stride,
+                                          pair_stride, width, height, ptaps, bt.k[1], bt.k[2], Rk, src);
         }
         if (int r = prep_level(wk, hk, bt, level_I(k))) return r;
         return nsof_launch_polyexp(ctx, (int)n_img, level_I(k), wk, hk, ptaps, Rk);
@@ -912,6 +920,15 @@ static int check_f32_layout(nsof_ctx* ctx, const void* p, ptrdiff_t row_stride, 
     if ((img_stride & 3) != 0) return nsof_set_error(ctx, NSOF_EINVAL, "f32 pair/frame stride=%td must be a multiple of 4", img_stride);
     return NSOF_OK;
 }
+// The same rules for 16-bit frames: every pixel 2-byte aligned, row stride >= 2*width.
+static int check_16_layout(nsof_ctx* ctx, const void* p, ptrdiff_t row_stride, ptrdiff_t img_stride, int width)
+{
+    if ((reinterpret_cast<uintptr_t>(p) & 1) != 0) return nsof_set_error(ctx, NSOF_EINVAL, "16-bit frames must be 2-byte aligned");
+    if ((row_stride & 1) != 0 || row_stride < (ptrdiff_t)width * 2)
+        return nsof_set_error(ctx, NSOF_EINVAL, "16-bit row_stride=%td must be even and >= 2*width", row_stride);
+    if ((img_stride & 1) != 0) return nsof_set_error(ctx, NSOF_EINVAL, "16-bit pair/frame stride=%td must be even", img_stride);
+    return NSOF_OK;
+}
 
 extern "C" int nsof_farneback_f32_batch_dev(nsof_ctx* ctx, int n_pairs, const float* d_prev, const float* d_next,
                                             ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height,
@@ -956,9 +973,12 @@ static int farneback_host_pair(nsof_ctx* ctx, int src, const void* prev, ptrdiff
     if (src == NSOF_SRC_F32 &&
         ((rc = check_f32_layout(ctx, prev, prev_stride, 0, width)) || (rc = check_f32_layout(ctx, next, next_stride, 0, width))))
         return rc;
+    if ((src == NSOF_SRC_U16 || src == NSOF_SRC_S16) &&
+        ((rc = check_16_layout(ctx, prev, prev_stride, 0, width)) || (rc = check_16_layout(ctx, next, next_stride, 0, width))))
+        return rc;
     if (flow_stride < (ptrdiff_t)(width * 8)) return nsof_set_error(ctx, NSOF_EINVAL, "flow_stride < width*8");
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n0 = (size_t)width * height, pitch = (size_t)width * (src == NSOF_SRC_F32 ? 4 : 1);
+    const size_t n0 = (size_t)width * height, pitch = (size_t)width * nsof_src_bytes(src);
     const size_t szU = align_up(pitch * height, 256), szF = align_up(n0 * 8, 256);
     if ((rc = ctx->stage.reserve(ctx, 2 * szU + szF)) || (rc = ctx->hstage.reserve(ctx, 2 * szU + szF))) return rc;
     char* hP = (char*)ctx->hstage.p;
@@ -1008,6 +1028,73 @@ extern "C" int nsof_farneback_u8(nsof_ctx* ctx, const uint8_t* prev, ptrdiff_t p
 {
     return farneback_host_pair(ctx, NSOF_SRC_U8, prev, prev_stride, next, next_stride, width, height, flow, flow_stride,
                                pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
+}
+
+// ---- typed entries (nsof_pixel_type == nsof_src_type): U8 / F32 go to their twins, 16-bit frames to the same driver --
+extern "C" int nsof_farneback_px(nsof_ctx* ctx, int pixel_type, const void* prev, ptrdiff_t prev_stride, const void* next,
+                                 ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
+                                 double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                                 double poly_sigma, int flags)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!nsof_src_valid(pixel_type)) return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
+    return farneback_host_pair(ctx, pixel_type, prev, prev_stride, next, next_stride, width, height, flow, flow_stride,
+                               pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
+}
+
+extern "C" int nsof_farneback_px_batch_dev(nsof_ctx* ctx, int pixel_type, int n_pairs, const void* d_prev, const void* d_next,
+                                           ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height, float* d_flow,
+                                           double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                                           double poly_sigma, int flags)
+{
+    if (!ctx) return NSOF_EINVAL;
+    switch (pixel_type) {
+        case NSOF_SRC_U8:
+            return nsof_farneback_u8_batch_dev(ctx, n_pairs, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_next),
+                                               row_stride, pair_stride, width, height, d_flow, pyr_scale, levels, winsize,
+                                               iterations, poly_n, poly_sigma, flags);
+        case NSOF_SRC_F32:
+            return nsof_farneback_f32_batch_dev(ctx, n_pairs, static_cast<const float*>(d_prev), static_cast<const float*>(d_next),
+                                                row_stride, pair_stride, width, height, d_flow, pyr_scale, levels, winsize,
+                                                iterations, poly_n, poly_sigma, flags);
+        case NSOF_SRC_U16:
+        case NSOF_SRC_S16: {
+            if (!d_prev || !d_next || !d_flow) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer");
+            int rc = check_16_layout(ctx, d_prev, row_stride, pair_stride, width);
+            if (rc == NSOF_OK) rc = check_16_layout(ctx, d_next, row_stride, pair_stride, width);
+            if (rc) return rc;
+            return nsof_farneback_core(ctx, false, n_pairs, d_prev, d_next, row_stride, pair_stride, width, height, d_flow,
+                                       pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, pixel_type);
+        }
+        default: return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
+    }
+}
+
+extern "C" int nsof_farneback_px_sequence_dev(nsof_ctx* ctx, int pixel_type, int n_frames, const void* d_frames,
+                                              ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
+                                              float* d_flow, double pyr_scale, int levels, int winsize, int iterations,
+                                              int poly_n, double poly_sigma, int flags)
+{
+    if (!ctx) return NSOF_EINVAL;
+    switch (pixel_type) {
+        case NSOF_SRC_U8:
+            return nsof_farneback_u8_sequence_dev(ctx, n_frames, static_cast<const uint8_t*>(d_frames), row_stride, frame_stride,
+                                                  width, height, d_flow, pyr_scale, levels, winsize, iterations, poly_n,
+                                                  poly_sigma, flags);
+        case NSOF_SRC_F32:
+            return nsof_farneback_f32_sequence_dev(ctx, n_frames, static_cast<const float*>(d_frames), row_stride, frame_stride,
+                                                   width, height, d_flow, pyr_scale, levels, winsize, iterations, poly_n,
+                                                   poly_sigma, flags);
+        case NSOF_SRC_U16:
+        case NSOF_SRC_S16: {
+            if (n_frames < 2) return nsof_set_error(ctx, NSOF_EINVAL, "a sequence needs at least 2 frames");
+            if (!d_frames || !d_flow) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer");
+            if (int rc = check_16_layout(ctx, d_frames, row_stride, frame_stride, width)) return rc;
+            return nsof_farneback_core(ctx, true, n_frames - 1, d_frames, nullptr, row_stride, frame_stride, width, height,
+                                       d_flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, pixel_type);
+        }
+        default: return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
+    }
 }
 
 // ---- ROI gating (host arithmetic on maps of at most a few hundred cells) -------------------------------------------

@@ -135,8 +135,11 @@ struct nsof_prof_scope {
 
 // ---- Farneback driver pieces shared between nsof_api.hip and farneback_batch.hip -------------------------------
 // Pixel type of the frames a uniform batch reads (the pyramid stage is the only one that reads them).  Frame pointers
-// stay byte addresses and every stride stays in bytes for both.
-enum nsof_src_type { NSOF_SRC_U8 = 0, NSOF_SRC_F32 = 1 };
+// stay byte addresses and every stride stays in bytes for all of them.  The values are those of the public
+// nsof_pixel_type.
+enum nsof_src_type { NSOF_SRC_U8 = 0, NSOF_SRC_F32 = 1, NSOF_SRC_U16 = 2, NSOF_SRC_S16 = 3 };
+static inline int nsof_src_bytes(int src) { return src == NSOF_SRC_F32 ? 4 : (src == NSOF_SRC_U8 ? 1 : 2); }
+static inline bool nsof_src_valid(int src) { return src >= NSOF_SRC_U8 && src <= NSOF_SRC_S16; }
 int nsof_check_farneback_params(nsof_ctx* ctx, int width, int height, double pyr_scale, int levels, int winsize,
                                 int iterations, int poly_n, int flags);
 // Uniform-shape device batch (sequence == true: n_pairs + 1 consecutive frames in d_prev); src: nsof_src_type.
@@ -181,8 +184,8 @@ int nsof_host_poly_taps(int n, double sigma, nsof_poly_taps* out);
 // buffers: I (level images, f32; prev at offI, next at offI + wk*hk), R (expansions, f32; R0 at offR, R1 at
 // offR + 5*wk*hk), flow (float2; this level at offF, the coarser level's field at offFc).
 struct nsof_het_item {
-    const uint8_t* src[2];       // full-resolution frames (prev, next), device BYTE addresses: 8-bit or float pixels,
-                                 // one type per list (the launch's src_type)
+    const uint8_t* src[2];       // full-resolution frames (prev, next), device BYTE addresses: 8-bit, 16-bit or float
+                                 // pixels, one type per list (the launch's src_type)
     long long src_stride[2];     // their row strides in bytes
     float* out;                  // the caller's flow field of this item (written by the last iteration of level 0)
     long long out_pitch;         // its row pitch in float2 units
@@ -191,7 +194,7 @@ struct nsof_het_item {
     int wk, hk;                  // this level
     int pw, ph;                  // coarser level (0: the item starts here, its incoming flow is zero)
     int flags;                   // NSOF_HET_VEC0 (vector level-0 kernel), W % 4 == 0 and W >= 8 with both frames and their
-                                 // row strides 4-byte (8-bit) / 16-byte (float) aligned
+                                 // row strides 4-byte (8-bit) / 8-byte (16-bit) / 16-byte (float) aligned
     int pad_;
 };
 enum { NSOF_HET_VEC0 = 1 };
@@ -212,7 +215,8 @@ int nsof_launch_iterate_lat_het(nsof_ctx* ctx, int n_items, const nsof_het_item*
 int nsof_launch_prep_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items,
                          bool level0, const nsof_blur_taps& taps, float* I, int src_type = NSOF_SRC_U8);
 int nsof_launch_polyexp_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
-                            const nsof_poly_taps& taps, const float* I, float* R, const float* blur3 = nullptr);
+                            const nsof_poly_taps& taps, const float* I, float* R, const float* blur3 = nullptr,
+                            int src_type = NSOF_SRC_U8);
 int nsof_launch_flow_upsample_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
                                   const float* src, float* dst, float mul);
 // final: the flow goes to the items' own output fields (out / out_pitch) instead of flow_out.
@@ -238,9 +242,11 @@ int nsof_launch_flow_upsample_het_fma(nsof_ctx* ctx, int n_items, const nsof_het
                                       const float* src, float* dst, float mul);
 int nsof_launch_polyexp(nsof_ctx* ctx, int n_img, const float* img, int W, int H, const nsof_poly_taps& taps,
                         float* R);
-// Full-resolution level: pyramid level (3-tap smoothing, centre k0 / side k1) + expansion in one kernel, from the frames.
-int nsof_launch_polyexp_u8(nsof_ctx* ctx, int n_img, const uint8_t* src0, const uint8_t* src1, int nsplit, ptrdiff_t row_stride,
-                           ptrdiff_t img_stride, int W, int H, const nsof_poly_taps& taps, float k0, float k1, float* R);
+// Full-resolution level: pyramid level (3-tap smoothing, centre k0 / side k1) + expansion in one kernel, from the 8-bit
+// or 16-bit frames (src_type: not NSOF_SRC_F32).
+int nsof_launch_polyexp_frames(nsof_ctx* ctx, int n_img, const void* src0, const void* src1, int nsplit, ptrdiff_t row_stride,
+                           ptrdiff_t img_stride, int W, int H, const nsof_poly_taps& taps, float k0, float k1, float* R,
+                           int src_type = NSOF_SRC_U8);
 int nsof_launch_blur_solve(nsof_ctx* ctx, int n_pairs, const float* M, int W, int H, int winsize, float* flow);
 // The same in the reference library's exact summation order; VT: n_pairs * 5 * W * H doubles of scratch.
 int nsof_launch_blur_solve_exact(nsof_ctx* ctx, int n_pairs, const float* M, int W, int H, int winsize, double* VT,

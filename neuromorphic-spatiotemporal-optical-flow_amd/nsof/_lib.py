@@ -21,13 +21,15 @@ OPT_PYR_FMA = 4
 OPT_SMALL_BATCH_JOBS = 5
 OPT_DEBUG_FAULT = 100   # test hook: see include/nsof.h
 NSOF_OK, NSOF_EINVAL, NSOF_ESHAPE, NSOF_EDEVICE, NSOF_ENOMEM, NSOF_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
+# nsof_pixel_type of include/nsof.h (the frames' pixel type of the typed entries nsof_farneback_px*)
+PIXEL_U8, PIXEL_F32, PIXEL_U16, PIXEL_S16 = 0, 1, 2, 3
 K_PREP, K_POLYEXP, K_UPSAMPLE, K_UPDMAT, K_BLUR, K_ACCUM, K_ITERATE, K_SEGMENT, K_MORPH, K_REMAP, K_SSIM, K_COUNT = range(12)
 
 _vp, _i, _d, _f, _sz, _pd, _i64 = C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_size_t, C.c_ssize_t, C.c_int64
 
 class PairDesc(C.Structure):
-    """``nsof_pair_desc`` of include/nsof.h: one frame pair of a shape-heterogeneous batch (``nsof_pair_desc_f32`` has the
-    same layout)."""
+    """``nsof_pair_desc`` of include/nsof.h: one frame pair of a shape-heterogeneous batch (``nsof_pair_desc_f32`` and
+    ``nsof_pair_desc_px`` have the same layout)."""
     _fields_ = [("prev", _vp), ("prev_stride", _pd), ("next", _vp), ("next_stride", _pd), ("width", _i), ("height", _i),
                 ("flow", _vp), ("flow_stride", _pd)]
 
@@ -56,12 +58,20 @@ SIGNATURES = {
     "nsof_farneback_f32_batch_desc_dev": (_i, [_vp, _i, C.POINTER(PairDesc), _d, _i, _i, _i, _i, _d, _i]),
     "nsof_farneback_f32_roi_sequence_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _vp, _i, _vp, _d, _i, _i, _i, _i, _d, _i, _i,
                                                  C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "nsof_farneback_px": (_i, [_vp, _i, _vp, _pd, _vp, _pd, _i, _i, _vp, _pd, _d, _i, _i, _i, _i, _d, _i]),
+    "nsof_farneback_px_batch_dev": (_i, [_vp, _i, _i, _vp, _vp, _pd, _pd, _i, _i, _vp, _d, _i, _i, _i, _i, _d, _i]),
+    "nsof_farneback_px_sequence_dev": (_i, [_vp, _i, _i, _vp, _pd, _pd, _i, _i, _vp, _d, _i, _i, _i, _i, _d, _i]),
+    "nsof_farneback_px_batch": (_i, [_vp, _i, _i, C.POINTER(PairDesc), _d, _i, _i, _i, _i, _d, _i]),
+    "nsof_farneback_px_batch_desc_dev": (_i, [_vp, _i, _i, C.POINTER(PairDesc), _d, _i, _i, _i, _i, _d, _i]),
+    "nsof_farneback_px_roi_sequence_dev": (_i, [_vp, _i, _i, _vp, _pd, _pd, _i, _i, _vp, _vp, _i, _vp, _d, _i, _i, _i, _i, _d, _i,
+                                                _i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "nsof_host_alloc": (_vp, [_sz]),
     "nsof_host_free": (None, [_vp]),
     "nsof_farneback_effective_levels": (_i, [_i, _i, _d, _i]),
     "nsof_farneback_level_size": (_i, [_i, _i, _d, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_d)]),
     "nsof_stage_pyr_level": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _d, _i, _vp]),
     "nsof_stage_pyr_level_f32": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _d, _i, _vp]),
+    "nsof_stage_pyr_level_px": (_i, [_vp, _i, _i, _vp, _pd, _pd, _i, _i, _d, _i, _vp]),
     "nsof_stage_polyexp": (_i, [_vp, _i, _vp, _i, _i, _i, _d, _vp]),
     "nsof_stage_recip": (_i, [_vp, C.c_longlong, _vp, _vp, _vp]),
     "nsof_stage_update_matrices": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp]),

@@ -5,9 +5,10 @@ _yolo twins); always ``(prev_region, next_region, None, **farneback_params)`` wi
 ``pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags`` (:73-81); inputs may be
 strided ROI views ``gray[y0:y1, x0:x1]`` (:186-187).
 
-Frames of the other single-channel depths cv2 accepts (int8, uint16, int16, int32, float16, float32, float64) are
-converted with ``astype(np.float32)`` -- cv2's own first step, ``convertTo(CV_32F)`` -- and run through the float32
-entry points; uint8 frames take the 8-bit ones.
+uint8 frames take the 8-bit entry points, uint16 and int16 frames the typed ones (``nsof_farneback_px*``: 16-bit pixels
+on the device, the 8-bit path's kernels, the float32 path's flow bit for bit).  Frames of the other single-channel
+depths cv2 accepts (int8, int32, float16, float32, float64) are converted with ``astype(np.float32)`` -- cv2's own first
+step, ``convertTo(CV_32F)`` -- and run through the float32 entry points.
 """
 import ctypes as C
 from dataclasses import asdict, dataclass
@@ -71,6 +72,20 @@ def _as_gray_f32(a, name):
     return a
 
 
+# numpy / torch dtype name -> nsof_pixel_type of the device frames the typed entries take
+_PIXEL_TYPES = {"uint8": _lib.PIXEL_U8, "float32": _lib.PIXEL_F32, "uint16": _lib.PIXEL_U16, "int16": _lib.PIXEL_S16}
+_PIXEL_BYTES = {"uint8": 1, "float32": 4, "uint16": 2, "int16": 2}
+
+
+def _as_gray_16(a):
+    """A uint16 / int16 frame in the layout nsof_farneback_px takes: contiguous pixels, a 2-byte aligned start and an even
+    row stride of at least 2 * width (row stride otherwise free, as for 8-bit frames).  Other views -- column-strided,
+    flipped (negative row stride) or unaligned -- are copied, as their astype(np.float32) was."""
+    if a.size and (a.strides[1] != 2 or a.strides[0] < 2 * a.shape[1] or a.strides[0] % 2 or a.ctypes.data % 2):
+        a = a.copy(order="C")   # a fresh, aligned array (ascontiguousarray keeps a contiguous unaligned one as it is)
+    return a
+
+
 def _as_gray_u8(a, name):
     if not isinstance(a, np.ndarray):
         raise NsofValueError(f"{name} is not a numpy array (got {type(a).__name__})")
@@ -94,9 +109,10 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
     """Same signature and result as ``cv2.calcOpticalFlowFarneback``: float32 (H, W, 2), (u, v) interleaved,
     such that ``next(x+u, y+v) ~ prev(x, y)``.  ``flow=None`` allocates; a matching float32 array is reused.
     ``prev`` / ``next``: single-channel frames of one dtype, any of uint8, int8, uint16, int16, int32, float16, float32,
-    float64 (cv2's depths).  Other depths are converted with ``astype(np.float32)`` (cv2's ``convertTo(CV_32F)``; exact
-    except int32 above 2^24 and float64) and run on the float32 path; non-finite values raise, as do frames of two
-    different dtypes (cv2 would convert each on its own).
+    float64 (cv2's depths).  uint16 / int16 frames go to the device as they are (``nsof_farneback_px``; the flow of
+    their float32 values, bit for bit); the other depths are converted with ``astype(np.float32)`` (cv2's
+    ``convertTo(CV_32F)``; exact except int32 above 2^24 and float64) and run on the float32 path; non-finite values
+    raise, as do frames of two different dtypes (cv2 would convert each on its own).
     ``exact`` (keyword only): True = box-filter row sums in the library's own order for this call
     (``NSOF_OPT_EXACT_ROWSUMS``, the context's default: bit-identical to the CPU restatement on any input),
     False = the fast mode (each pixel's window summed directly: a few per cent faster, up to ~8e-4 off where 2x2 systems
@@ -119,8 +135,12 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
     h, w = prev.shape
     if h == 0 or w == 0:
         raise NsofValueError("empty input image", _lib.NSOF_ESHAPE)
+    typed = ()   # the typed entry's pixel-type argument
     if prev.dtype == np.uint8:
         prev, next, entry = _as_gray_u8(prev, "prev"), _as_gray_u8(next, "next"), "nsof_farneback_u8"  # noqa: A001
+    elif prev.dtype in (np.uint16, np.int16):
+        prev, next, entry = _as_gray_16(prev), _as_gray_16(next), "nsof_farneback_px"  # noqa: A001
+        typed = (_PIXEL_TYPES[prev.dtype.name],)
     else:
         prev, next, entry = _as_gray_f32(prev, "prev"), _as_gray_f32(next, "next"), "nsof_farneback_f32"  # noqa: A001
     if (isinstance(flow, np.ndarray) and flow.dtype == np.float32 and flow.shape == (h, w, 2)
@@ -142,7 +162,7 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
             saved_bands = ctx.get_option(_lib.OPT_ROW_BANDS)
             ctx.set_option(_lib.OPT_ROW_BANDS, 1 if low_latency else 0)
         try:
-            rc = getattr(ctx._lib, entry)(ctx.ptr, prev.ctypes.data, prev.strides[0], next.ctypes.data, next.strides[0],
+            rc = getattr(ctx._lib, entry)(ctx.ptr, *typed, prev.ctypes.data, prev.strides[0], next.ctypes.data, next.strides[0],
                                           w, h, out.ctypes.data, out.strides[0], float(pyr_scale), int(levels),
                                           int(winsize), int(iterations), int(poly_n), float(poly_sigma), int(flags))
         finally:
@@ -161,7 +181,8 @@ def _tensor_dtype(obj):
 
 
 def _frames_dtype(frames, dtype):
-    """The pixel type of device frames: a tensor's own dtype, else the ``dtype`` keyword (default uint8)."""
+    """The pixel type of device frames: a tensor's own dtype, else the ``dtype`` keyword (default uint8); one of uint8,
+    float32, uint16, int16."""
     names = {_tensor_dtype(f) for f in frames} - {None}
     if dtype is not None:
         names.add(np.dtype(dtype).name)
@@ -169,41 +190,52 @@ def _frames_dtype(frames, dtype):
     if len(names) != 1:
         raise NsofValueError(f"frames of different dtypes {sorted(names)}")
     name = names.pop()
-    if name not in ("uint8", "float32"):
-        raise NsofValueError(f"device frames must be uint8 or float32 (got {name})")
+    if name not in _PIXEL_TYPES:
+        raise NsofValueError(f"device frames must be uint8, uint16, int16 or float32 (got {name})")
     return name
 
 
 def farneback_batch(d_prev, d_next, d_flow, n_pairs, height, width, params, *, row_stride=None, pair_stride=None,
                     dtype=None, ctx=None):
-    """Device-resident batch: ``d_prev/d_next`` uint8 or float32 [n][H][row_stride], ``d_flow`` float32 [n][H][W][2]
-    (torch tensors or raw device addresses).  Strides are in BYTES (default: dense).  The frames' type is the tensors'
-    dtype; raw addresses are uint8 unless ``dtype=np.float32``.  Asynchronous on the context's stream."""
+    """Device-resident batch: ``d_prev/d_next`` uint8, uint16, int16 or float32 [n][H][row_stride], ``d_flow`` float32
+    [n][H][W][2] (torch tensors or raw device addresses).  Strides are in BYTES (default: dense).  The frames' type is
+    the tensors' dtype; raw addresses are uint8 unless ``dtype=`` says otherwise (np.float32, np.uint16, np.int16).
+    16-bit frames run on ``nsof_farneback_px_batch_dev`` (rows 2-byte aligned).  Asynchronous on the context's stream."""
     ctx = ctx or default_context()
-    f32 = _frames_dtype((d_prev, d_next), dtype) == "float32"
-    row_stride = width * (4 if f32 else 1) if row_stride is None else row_stride
+    name = _frames_dtype((d_prev, d_next), dtype)
+    row_stride = width * _PIXEL_BYTES[name] if row_stride is None else row_stride
     pair_stride = row_stride * height if pair_stride is None else pair_stride
     p = params
-    entry = ctx._lib.nsof_farneback_f32_batch_dev if f32 else ctx._lib.nsof_farneback_u8_batch_dev
-    rc = entry(ctx.ptr, n_pairs, dev_ptr(d_prev), dev_ptr(d_next), row_stride, pair_stride, width, height, dev_ptr(d_flow),
-               p.pyr_scale, p.levels, p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags)
+    args = (dev_ptr(d_prev), dev_ptr(d_next), row_stride, pair_stride, width, height, dev_ptr(d_flow), p.pyr_scale, p.levels,
+            p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags)
+    if name == "float32":
+        rc = ctx._lib.nsof_farneback_f32_batch_dev(ctx.ptr, n_pairs, *args)
+    elif name == "uint8":
+        rc = ctx._lib.nsof_farneback_u8_batch_dev(ctx.ptr, n_pairs, *args)
+    else:
+        rc = ctx._lib.nsof_farneback_px_batch_dev(ctx.ptr, _PIXEL_TYPES[name], n_pairs, *args)
     ctx.check(rc, "farneback_batch")
 
 
 def farneback_sequence(d_frames, d_flow, n_frames, height, width, params, *, row_stride=None, frame_stride=None,
                        dtype=None, ctx=None):
-    """Device-resident sequence: ``d_frames`` uint8 or float32 [n_frames][H][row_stride]; ``d_flow`` float32
-    [n_frames-1][H][W][2] with flow i = frame i -> frame i+1 (the consecutive-pair walk of the reference's scripts).
-    Per-frame work (pyramid, polynomial expansion) is shared between neighbouring pairs.  Strides in bytes and the
-    frames' type as for ``farneback_batch``."""
+    """Device-resident sequence: ``d_frames`` uint8, uint16, int16 or float32 [n_frames][H][row_stride]; ``d_flow``
+    float32 [n_frames-1][H][W][2] with flow i = frame i -> frame i+1 (the consecutive-pair walk of the reference's
+    scripts).  Per-frame work (pyramid, polynomial expansion) is shared between neighbouring pairs.  Strides in bytes and
+    the frames' type as for ``farneback_batch``."""
     ctx = ctx or default_context()
-    f32 = _frames_dtype((d_frames,), dtype) == "float32"
-    row_stride = width * (4 if f32 else 1) if row_stride is None else row_stride
+    name = _frames_dtype((d_frames,), dtype)
+    row_stride = width * _PIXEL_BYTES[name] if row_stride is None else row_stride
     frame_stride = row_stride * height if frame_stride is None else frame_stride
     p = params
-    entry = ctx._lib.nsof_farneback_f32_sequence_dev if f32 else ctx._lib.nsof_farneback_u8_sequence_dev
-    rc = entry(ctx.ptr, n_frames, dev_ptr(d_frames), row_stride, frame_stride, width, height, dev_ptr(d_flow), p.pyr_scale,
-               p.levels, p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags)
+    args = (dev_ptr(d_frames), row_stride, frame_stride, width, height, dev_ptr(d_flow), p.pyr_scale, p.levels, p.winsize,
+            p.iterations, p.poly_n, p.poly_sigma, p.flags)
+    if name == "float32":
+        rc = ctx._lib.nsof_farneback_f32_sequence_dev(ctx.ptr, n_frames, *args)
+    elif name == "uint8":
+        rc = ctx._lib.nsof_farneback_u8_sequence_dev(ctx.ptr, n_frames, *args)
+    else:
+        rc = ctx._lib.nsof_farneback_px_sequence_dev(ctx.ptr, _PIXEL_TYPES[name], n_frames, *args)
     ctx.check(rc, "farneback_sequence")
 
 
@@ -234,13 +266,13 @@ def pinned_empty(shape, dtype=np.float32):
     return arr
 
 
-def _desc_array(pairs, flows, host, f32=False):
-    """ctypes array of nsof_pair_desc (nsof_pair_desc_f32 with ``f32``: the same layout) for (prev, next) pairs and their
-    flow fields (numpy arrays or, with host=False, objects exposing data_ptr()/shape/stride() like torch CUDA tensors).
-    Host float32 frames must come from ``_f32_host_frames``."""
+def _desc_array(pairs, flows, host, f32=False, px16=False):
+    """ctypes array of nsof_pair_desc (nsof_pair_desc_f32 with ``f32``, nsof_pair_desc_px of 16-bit device frames with
+    ``px16``: the same layout) for (prev, next) pairs and their flow fields (numpy arrays or, with host=False, objects
+    exposing data_ptr()/shape/stride() like torch CUDA tensors).  Host float32 frames must come from ``_f32_host_frames``."""
     descs = (_lib.PairDesc * len(pairs))()
     keep = []
-    px = 4 if f32 else 1
+    px = 4 if f32 else (2 if px16 else 1)
     for i, ((prev, nxt), flow) in enumerate(zip(pairs, flows)):
         d = descs[i]
         if host:
@@ -254,7 +286,11 @@ def _desc_array(pairs, flows, host, f32=False):
             d.flow, d.flow_stride = flow.ctypes.data, flow.strides[0]
         else:
             h, w = int(prev.shape[0]), int(prev.shape[1])
-            if f32:
+            if px16:
+                if _tensor_dtype(prev) not in ("uint16", "int16") or _tensor_dtype(nxt) not in ("uint16", "int16"):
+                    raise NsofValueError(f"pair {i}: frames must be uint16 or int16 tensors (got {_tensor_dtype(prev)}, "
+                                         f"{_tensor_dtype(nxt)})")
+            elif f32:
                 if _tensor_dtype(prev) != "float32" or _tensor_dtype(nxt) != "float32":
                     raise NsofValueError(f"pair {i}: frames must be float32 tensors (got {_tensor_dtype(prev)}, "
                                          f"{_tensor_dtype(nxt)}); 8-bit frames take farneback_pairs_dev")
@@ -373,20 +409,27 @@ def farneback_pairs(pairs, params, flows=None, *, pinned=False, ctx=None):
     return flows
 
 
-def _desc_batch_call(ctx, entry, descs, kw, what):
-    """One native work-list call (``nsof_farneback_{u8,f32}_batch[_desc_dev]``) on a descriptor array."""
-    rc = entry(ctx.ptr, len(descs), descs, float(kw["pyr_scale"]), int(kw["levels"]), int(kw["winsize"]),
+def _desc_batch_call(ctx, entry, descs, kw, what, *typed):
+    """One native work-list call (``nsof_farneback_{u8,f32}_batch[_desc_dev]``, or a typed ``nsof_farneback_px_batch*``
+    with its pixel type in ``typed``) on a descriptor array."""
+    rc = entry(ctx.ptr, *typed, len(descs), descs, float(kw["pyr_scale"]), int(kw["levels"]), int(kw["winsize"]),
                int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]), int(kw["flags"]))
     ctx.check(rc, what)
 
 
-def _pairs_dev(pairs, flows, params, ctx, f32):
+def _pairs_dev(pairs, flows, params, ctx, f32, px16=False):
     ctx = ctx or default_context()
     kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
     pairs, flows = list(pairs), list(flows)
     if len(flows) != len(pairs):
         raise NsofValueError("flows and pairs differ in length")
     if not pairs:
+        return
+    if px16:   # one 16-bit dtype per list: the typed entry's pixel type
+        name = _list_dtype_16((_tensor_dtype(f) for pair in pairs for f in pair), "farneback_pairs_16_dev")
+        descs, _ = _desc_array(pairs, flows, host=False, px16=True)
+        _desc_batch_call(ctx, ctx._lib.nsof_farneback_px_batch_desc_dev, descs, kw, "farneback_pairs_16_dev",
+                         _PIXEL_TYPES[name])
         return
     descs, _ = _desc_array(pairs, flows, host=False, f32=f32)
     if f32:
@@ -408,6 +451,40 @@ def farneback_pairs_f32_dev(pairs, flows, params, *, ctx=None):
     result equals ``calcOpticalFlowFarneback`` of that pair's frames bit for bit.  Other dtypes raise ``NsofValueError``.
     Asynchronous on the context's stream."""
     _pairs_dev(pairs, flows, params, ctx, f32=True)
+
+
+def _list_dtype_16(names, what):
+    """The one 16-bit dtype of a device list's frames (uint16 or int16); anything else raises."""
+    names = set(names)
+    if len(names) != 1 or not names <= {"uint16", "int16"}:
+        raise NsofValueError(f"{what}: frames must be all uint16 or all int16 tensors (got {sorted(map(str, names))})")
+    return names.pop()
+
+
+def farneback_pairs_16_dev(pairs, flows, params, *, ctx=None):
+    """``farneback_pairs_dev`` for uint16 or int16 frames (``nsof_farneback_px_batch_desc_dev``): ``pairs`` = [(prev,
+    next), ...] of CUDA tensors of ONE of those dtypes (crops ``frame[y0:y1, x0:x1]`` of frames in HBM: any row stride,
+    pixel stride 1), ``flows`` as there.  Each result equals ``calcOpticalFlowFarneback`` of that pair's frames as float32,
+    bit for bit.  Mixed or other dtypes raise ``NsofValueError``.  Asynchronous on the context's stream."""
+    _pairs_dev(pairs, flows, params, ctx, f32=False, px16=True)
+
+
+def farneback_roi_sequence_16_dev(frames, counts, rects, flows, params, *, gate_frame=0, ctx=None):
+    """``farneback_roi_sequence_dev`` for uint16 or int16 frames (``nsof_farneback_px_roi_sequence_dev``): ``frames`` a
+    uint16 or int16 CUDA tensor [n][H][W] (row stride free), everything else as there.  Each crop's flow equals
+    ``calcOpticalFlowFarneback`` of that crop as float32, bit for bit.  Returns (crops, their total area)."""
+    ctx = ctx or default_context()
+    kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
+    name = _list_dtype_16((_tensor_dtype(frames),), "farneback_roi_sequence_16_dev")
+    n, h, w = _roi_sequence_args(frames, counts, rects, flows)
+    calls, pixels = C.c_longlong(), C.c_longlong()
+    rc = ctx._lib.nsof_farneback_px_roi_sequence_dev(
+        ctx.ptr, _PIXEL_TYPES[name], n, dev_ptr(frames), int(frames.stride(1)) * 2, int(frames.stride(0)) * 2, w, h,
+        dev_ptr(counts), dev_ptr(rects), int(rects.shape[1]), dev_ptr(flows), float(kw["pyr_scale"]), int(kw["levels"]),
+        int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]), int(kw["flags"]),
+        int(gate_frame), C.byref(calls), C.byref(pixels))
+    ctx.check(rc, "farneback_roi_sequence_16_dev")
+    return calls.value, pixels.value
 
 
 def _roi_sequence_args(frames, counts, rects, flows):
