@@ -104,10 +104,45 @@ int nsof_set_option(nsof_ctx* ctx, int option, int value);
 int nsof_get_option(const nsof_ctx* ctx, int option, int* value);
 
 /* ---- stage 2: Farneback --------------------------------------------------------------- */
-/* Same argument meaning and order as cv2.calcOpticalFlowFarneback (see call sites above).
- * prev/next: HOST uint8 single-channel images, row strides in bytes (strided ROI views are
+/* Seven routes lead into the library: a lone host pair, a uniform device batch, a device sequence, a host work list, a
+ * device work list, the gated ROI sequence and the stage entry nsof_stage_pyr_level.  Each has ONE typed entry
+ * (nsof_farneback_px*, nsof_stage_pyr_level_px), documented below, which takes the frames' pixel type -- an
+ * nsof_pixel_type -- after the context: frame pointers are `const void*` and EVERY stride is in BYTES whatever the type.
+ * The nsof_farneback_u8* and nsof_farneback_f32* entries (and nsof_stage_pyr_level / nsof_stage_pyr_level_f32) are the
+ * typed entry with the pixel type named and typed pointers: they forward to it, so U8 and F32 frames run exactly the same
+ * code through either, with the same argument checks, flow layout, host staging and synchronisation.
+ *
+ * Pixel types: the ones cv2 takes natively on this path.  F32 is what cv2 computes on after its convertTo(CV_32F): a float
+ * frame holding the values of an 8-bit frame gives the 8-bit flow bit for bit.  Float frames must be finite (the Python
+ * layer checks).  16-bit frames (U16: zero-extended, S16: sign-extended; both convert to float exactly) take the 8-bit
+ * path's fused pyramid kernels at 2 B/px and give the flow of F32 frames holding the same values, bit for bit, in every
+ * mode.  A work list, a batch or a sequence holds one pixel type.
+ *
+ * Layout rule, one for every route, in terms of the pixel size s (U8 1, U16 / S16 2, F32 4 bytes): frame pointers
+ * s-byte aligned, row, pair and frame strides multiples of s, a row stride at least s * width.  Nothing more: crops that
+ * start at any element are fine (the pyramid kernels take their vector loads where rows are aligned for them -- 16 bytes
+ * for float frames -- and scalar loads elsewhere; the result does not depend on it).  The lone host pair takes ANY row
+ * stride for 8-bit frames (its rows are copied) and the stage entry leaves an 8-bit row stride unchecked.  Otherwise a
+ * violation, or an unknown pixel type, returns NSOF_EINVAL before anything is launched. */
+typedef enum nsof_pixel_type {
+    NSOF_PIXEL_U8 = 0,
+    NSOF_PIXEL_F32 = 1,
+    NSOF_PIXEL_U16 = 2,
+    NSOF_PIXEL_S16 = 3,
+} nsof_pixel_type;
+
+/* The lone host pair.  Same argument meaning and order as cv2.calcOpticalFlowFarneback (see call sites above).
+ * prev/next: HOST single-channel images of pixel_type, row strides in bytes (strided ROI views are
  * fine, optical_flow_seg.py:186-187); flow: HOST float32, interleaved (u,v), row stride in
  * bytes.  Pointers are not retained.  Blocks until the flow is in host memory. */
+int nsof_farneback_px(nsof_ctx* ctx, int pixel_type,
+                      const void* prev, ptrdiff_t prev_stride,
+                      const void* next, ptrdiff_t next_stride,
+                      int width, int height,
+                      float* flow, ptrdiff_t flow_stride,
+                      double pyr_scale, int levels, int winsize, int iterations,
+                      int poly_n, double poly_sigma, int flags);
+/* nsof_farneback_px(ctx, NSOF_PIXEL_U8, ...) */
 int nsof_farneback_u8(nsof_ctx* ctx,
                       const uint8_t* prev, ptrdiff_t prev_stride,
                       const uint8_t* next, ptrdiff_t next_stride,
@@ -115,37 +150,7 @@ int nsof_farneback_u8(nsof_ctx* ctx,
                       float* flow, ptrdiff_t flow_stride,
                       double pyr_scale, int levels, int winsize, int iterations,
                       int poly_n, double poly_sigma, int flags);
-
-/* Batched, device-resident twin: n_pairs frame pairs of one shape already in HBM.
- * d_prev/d_next: DEVICE uint8 [n_pairs][height][row_stride]; pair_stride in bytes.
- * d_flow: DEVICE float32 [n_pairs][height][width][2] (dense).  Asynchronous on the
- * context's stream. */
-int nsof_farneback_u8_batch_dev(nsof_ctx* ctx, int n_pairs,
-                                const uint8_t* d_prev, const uint8_t* d_next,
-                                ptrdiff_t row_stride, ptrdiff_t pair_stride,
-                                int width, int height, float* d_flow,
-                                double pyr_scale, int levels, int winsize, int iterations,
-                                int poly_n, double poly_sigma, int flags);
-
-/* Sequence twin: n_frames consecutive frames already in HBM, d_frames uint8 [n_frames][height][row_stride];
- * d_flow float32 [n_frames-1][height][width][2], flow i = (frame i -> frame i+1), exactly what n_frames-1 calls
- * of nsof_farneback_u8 on consecutive frames give (the reference's seg/ob/prediction loops walk a sequence this
- * way, optical_flow_seg.py:413-496).  Each frame's pyramid levels and polynomial expansion are computed once and
- * shared by the two pairs the frame belongs to.  Asynchronous on the context's stream. */
-int nsof_farneback_u8_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames,
-                                   ptrdiff_t row_stride, ptrdiff_t frame_stride,
-                                   int width, int height, float* d_flow,
-                                   double pyr_scale, int levels, int winsize, int iterations,
-                                   int poly_n, double poly_sigma, int flags);
-
-/* Float frames (what cv2 takes after its convertTo(CV_32F)): the same three entries for float32 single-channel
- * frames.  Every stride is in BYTES, as for the 8-bit entries; a row stride (and a pair / frame stride) must be a
- * multiple of 4 and a row stride at least 4*width; frame pointers need only 4-byte alignment (crops that start at any
- * element are fine; the pyramid kernels take their vector loads where rows are 16-byte aligned and scalar loads
- * elsewhere).  Other argument checks, the flow layout, the host staging and the synchronisation are those of the
- * 8-bit twins.  A float frame holding the values of an 8-bit frame gives the 8-bit entry's flow bit for bit.  The
- * frames must be finite (the Python layer checks).  The work lists have float twins too (nsof_pair_desc_f32 and
- * nsof_farneback_f32_batch* / nsof_farneback_f32_roi_sequence_dev below). */
+/* nsof_farneback_px(ctx, NSOF_PIXEL_F32, ...) */
 int nsof_farneback_f32(nsof_ctx* ctx,
                        const float* prev, ptrdiff_t prev_stride,
                        const float* next, ptrdiff_t next_stride,
@@ -153,12 +158,49 @@ int nsof_farneback_f32(nsof_ctx* ctx,
                        float* flow, ptrdiff_t flow_stride,
                        double pyr_scale, int levels, int winsize, int iterations,
                        int poly_n, double poly_sigma, int flags);
+
+/* The uniform device batch, the device-resident twin of the lone pair: n_pairs frame pairs of one shape already in HBM.
+ * d_prev/d_next: DEVICE frames of pixel_type [n_pairs][height][row_stride]; pair_stride in bytes.
+ * d_flow: DEVICE float32 [n_pairs][height][width][2] (dense).  Asynchronous on the
+ * context's stream. */
+int nsof_farneback_px_batch_dev(nsof_ctx* ctx, int pixel_type, int n_pairs,
+                                const void* d_prev, const void* d_next,
+                                ptrdiff_t row_stride, ptrdiff_t pair_stride,
+                                int width, int height, float* d_flow,
+                                double pyr_scale, int levels, int winsize, int iterations,
+                                int poly_n, double poly_sigma, int flags);
+/* nsof_farneback_px_batch_dev(ctx, NSOF_PIXEL_U8, ...) */
+int nsof_farneback_u8_batch_dev(nsof_ctx* ctx, int n_pairs,
+                                const uint8_t* d_prev, const uint8_t* d_next,
+                                ptrdiff_t row_stride, ptrdiff_t pair_stride,
+                                int width, int height, float* d_flow,
+                                double pyr_scale, int levels, int winsize, int iterations,
+                                int poly_n, double poly_sigma, int flags);
+/* nsof_farneback_px_batch_dev(ctx, NSOF_PIXEL_F32, ...) */
 int nsof_farneback_f32_batch_dev(nsof_ctx* ctx, int n_pairs,
                                  const float* d_prev, const float* d_next,
                                  ptrdiff_t row_stride, ptrdiff_t pair_stride,
                                  int width, int height, float* d_flow,
                                  double pyr_scale, int levels, int winsize, int iterations,
                                  int poly_n, double poly_sigma, int flags);
+
+/* The device sequence: n_frames consecutive frames already in HBM, d_frames of pixel_type [n_frames][height][row_stride];
+ * d_flow float32 [n_frames-1][height][width][2], flow i = (frame i -> frame i+1), exactly what n_frames-1 calls
+ * of nsof_farneback_px on consecutive frames give (the reference's seg/ob/prediction loops walk a sequence this
+ * way, optical_flow_seg.py:413-496).  Each frame's pyramid levels and polynomial expansion are computed once and
+ * shared by the two pairs the frame belongs to.  Asynchronous on the context's stream. */
+int nsof_farneback_px_sequence_dev(nsof_ctx* ctx, int pixel_type, int n_frames, const void* d_frames,
+                                   ptrdiff_t row_stride, ptrdiff_t frame_stride,
+                                   int width, int height, float* d_flow,
+                                   double pyr_scale, int levels, int winsize, int iterations,
+                                   int poly_n, double poly_sigma, int flags);
+/* nsof_farneback_px_sequence_dev(ctx, NSOF_PIXEL_U8, ...) */
+int nsof_farneback_u8_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames,
+                                   ptrdiff_t row_stride, ptrdiff_t frame_stride,
+                                   int width, int height, float* d_flow,
+                                   double pyr_scale, int levels, int winsize, int iterations,
+                                   int poly_n, double poly_sigma, int flags);
+/* nsof_farneback_px_sequence_dev(ctx, NSOF_PIXEL_F32, ...) */
 int nsof_farneback_f32_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_frames,
                                     ptrdiff_t row_stride, ptrdiff_t frame_stride,
                                     int width, int height, float* d_flow,
@@ -169,92 +211,9 @@ int nsof_farneback_f32_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_
  * next_region, None, **farneback_params) receives and returns in the gated path -- optical_flow_seg.py:129-164
  * (one crop per connected component), :186-203 (the union box), :492-496 (the full frame) -- as plain pointers.
  * flow_stride in bytes (a multiple of 8): a view flow_canvas[y0:y1, x0:x1] of a frame-sized float32 (H,W,2)
- * canvas is written in place, which is the paste of :162 / :204. */
-typedef struct nsof_pair_desc {
-    const uint8_t* prev;
-    ptrdiff_t prev_stride;
-    const uint8_t* next;
-    ptrdiff_t next_stride;
-    int width, height;
-    float* flow;
-    ptrdiff_t flow_stride;
-} nsof_pair_desc;
-
-/* n_pairs pairs of ANY shapes, one parameter set, HOST memory (pointers are not retained; blocks until every flow
- * field is in host memory).  All pairs share every kernel launch (a work list per pyramid level), so many small ROI
- * calls cost about as much as one; the list is processed in chunks whose upload, compute and download overlap on
- * three streams.  Buffers from nsof_host_alloc() (page-locked) are copied to/from directly, other memory goes
- * through an internal pinned staging buffer.  Result per pair == nsof_farneback_u8 of that pair, bit for bit, in the default
- * mode; with the opt-in modes that depend on the batch (NSOF_OPT_ROW_BANDS in automatic mode picks its band height from the
- * batch size; a uniform list takes the uniform driver, where NSOF_OPT_POLYEXP_F32 applies) only to their tolerance. */
-int nsof_farneback_u8_batch(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs,
-                            double pyr_scale, int levels, int winsize, int iterations,
-                            int poly_n, double poly_sigma, int flags);
-/* Device-resident twin: `pairs` is a HOST array whose prev/next/flow are DEVICE addresses (e.g. crops of frames
- * and of flow canvases already in HBM).  Asynchronous on the context's stream. */
-int nsof_farneback_u8_batch_desc_dev(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs,
-                                     double pyr_scale, int levels, int winsize, int iterations,
-                                     int poly_n, double poly_sigma, int flags);
-/* The gated path of a whole frame sequence on the device (opticalFlow3D's crop -> flow -> paste loop,
- * /root/reference/optical_flow_seg.py:129-164, 186-204): d_frames = n_frames 8-bit frames in HBM, d_counts / d_rects = the
- * ROI table nsof_roi_from_surface_dev wrote (rects [n_frames][max_rects][4] = x0, y0, x1, y1), d_flows =
- * [n_frames - 1][height][width][2] float canvases, zero-filled here.  Pair k = (frame k, frame k + 1) is gated by the
- * rectangles of frame k + gate_frame: 1 = the map of the pair's second frame (what opticalFlow3D is written to use,
- * memimg2), 0 = the map of its first frame (what the shipped scripts pass: memimg2 := memimg1, optical_flow_seg.py:435 --
- * the bug-compatible default of nsof.gating, SURVEY.md Appendix B.2); every crop of every pair is one item of ONE work list, written into the canvas in place;
- * a crop that overlaps an earlier crop of its pair is pasted after it, in label order, as the reference's loop
- * overwrites.  Each crop's flow equals nsof_farneback_u8 of that crop bit for bit.  Only the rectangle table crosses
- * PCIe (the work list's shapes are needed on the host; the call synchronises the stream once for it).  n_calls /
- * n_pixels (optional) receive the number of crops and their total area.  Asynchronous otherwise. */
-int nsof_farneback_u8_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, ptrdiff_t row_stride,
-                                       ptrdiff_t frame_stride, int width, int height, const int32_t* d_counts,
-                                       const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale, int levels,
-                                       int winsize, int iterations, int poly_n, double poly_sigma, int flags,
-                                       int gate_frame, long long* n_calls, long long* n_pixels);
-/* Float32 frames in work lists: the three entries above for float32 single-channel frames.  nsof_pair_desc_f32 has the
- * fields of nsof_pair_desc in the same order; every stride stays in BYTES.  Layout rules are those of
- * nsof_farneback_f32: frame pointers 4-byte aligned, row strides multiples of 4 and at least 4*width (for the ROI
- * sequence: row_stride and frame_stride multiples of 4); a violation returns NSOF_EINVAL before anything is launched.
- * A list holds one pixel type.  Results per pair == nsof_farneback_f32 of that pair, bit for bit, in the default mode;
- * float frames holding 8-bit values give the 8-bit entries' flow bit for bit.  The frames must be finite (the Python
- * layer checks).  Items start 16-byte aligned with row strides that are multiples of 16 and W % 4 == 0 take the vector
- * form of the level-0 pyramid kernel, the others its scalar form; the result does not depend on it. */
-typedef struct nsof_pair_desc_f32 {
-    const float* prev;
-    ptrdiff_t prev_stride;
-    const float* next;
-    ptrdiff_t next_stride;
-    int width, height;
-    float* flow;
-    ptrdiff_t flow_stride;
-} nsof_pair_desc_f32;
-int nsof_farneback_f32_batch(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc_f32* pairs,
-                             double pyr_scale, int levels, int winsize, int iterations,
-                             int poly_n, double poly_sigma, int flags);
-int nsof_farneback_f32_batch_desc_dev(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc_f32* pairs,
-                                      double pyr_scale, int levels, int winsize, int iterations,
-                                      int poly_n, double poly_sigma, int flags);
-/* d_frames: n_frames float32 frames in HBM, row_stride / frame_stride in bytes; everything else as
- * nsof_farneback_u8_roi_sequence_dev (each crop's flow == nsof_farneback_f32 of that crop, bit for bit). */
-int nsof_farneback_f32_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_frames, ptrdiff_t row_stride,
-                                        ptrdiff_t frame_stride, int width, int height, const int32_t* d_counts,
-                                        const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale, int levels,
-                                        int winsize, int iterations, int poly_n, double poly_sigma, int flags,
-                                        int gate_frame, long long* n_calls, long long* n_pixels);
-/* Typed entries: the entries above for frames of any pixel type cv2 takes natively on this path.  `pixel_type` is an
- * nsof_pixel_type; frame pointers are `const void*` and every stride stays in BYTES.  U8 and F32 run exactly the code of
- * their twins (nsof_farneback_u8*, nsof_farneback_f32*), with the same layout rules.  16-bit frames (U16: zero-extended,
- * S16: sign-extended; both convert to float exactly) take the 8-bit path's fused pyramid kernels at 2 B/px and give the
- * flow of the F32 entry on the frames' float32 values, bit for bit, in every mode.  Their layout rules: frame pointers
- * 2-byte aligned, row, pair and frame strides multiples of 2, a row stride at least 2*width.  A violation, or an unknown
- * pixel type, returns NSOF_EINVAL before anything is launched.  A list holds one pixel type. */
-typedef enum nsof_pixel_type {
-    NSOF_PIXEL_U8 = 0,
-    NSOF_PIXEL_F32 = 1,
-    NSOF_PIXEL_U16 = 2,
-    NSOF_PIXEL_S16 = 3,
-} nsof_pixel_type;
-/* nsof_pair_desc with untyped frames: the fields of nsof_pair_desc in the same order. */
+ * canvas is written in place, which is the paste of :162 / :204.  The three structs have the same fields in the same
+ * order (one layout) and differ in the type their frame pointers name: nsof_pair_desc_px (untyped frames) for the typed
+ * entries, nsof_pair_desc (8-bit) and nsof_pair_desc_f32 (float32) for their exports; every stride stays in BYTES. */
 typedef struct nsof_pair_desc_px {
     const void* prev;
     ptrdiff_t prev_stride;
@@ -264,37 +223,94 @@ typedef struct nsof_pair_desc_px {
     float* flow;
     ptrdiff_t flow_stride;
 } nsof_pair_desc_px;
-int nsof_farneback_px(nsof_ctx* ctx, int pixel_type,
-                      const void* prev, ptrdiff_t prev_stride,
-                      const void* next, ptrdiff_t next_stride,
-                      int width, int height,
-                      float* flow, ptrdiff_t flow_stride,
-                      double pyr_scale, int levels, int winsize, int iterations,
-                      int poly_n, double poly_sigma, int flags);
-int nsof_farneback_px_batch_dev(nsof_ctx* ctx, int pixel_type, int n_pairs,
-                                const void* d_prev, const void* d_next,
-                                ptrdiff_t row_stride, ptrdiff_t pair_stride,
-                                int width, int height, float* d_flow,
-                                double pyr_scale, int levels, int winsize, int iterations,
-                                int poly_n, double poly_sigma, int flags);
-int nsof_farneback_px_sequence_dev(nsof_ctx* ctx, int pixel_type, int n_frames, const void* d_frames,
-                                   ptrdiff_t row_stride, ptrdiff_t frame_stride,
-                                   int width, int height, float* d_flow,
-                                   double pyr_scale, int levels, int winsize, int iterations,
-                                   int poly_n, double poly_sigma, int flags);
+typedef struct nsof_pair_desc {
+    const uint8_t* prev;
+    ptrdiff_t prev_stride;
+    const uint8_t* next;
+    ptrdiff_t next_stride;
+    int width, height;
+    float* flow;
+    ptrdiff_t flow_stride;
+} nsof_pair_desc;
+typedef struct nsof_pair_desc_f32 {
+    const float* prev;
+    ptrdiff_t prev_stride;
+    const float* next;
+    ptrdiff_t next_stride;
+    int width, height;
+    float* flow;
+    ptrdiff_t flow_stride;
+} nsof_pair_desc_f32;
+
+/* The host work list: n_pairs pairs of ANY shapes, one parameter set, one pixel type, HOST memory (pointers are not
+ * retained; blocks until every flow field is in host memory).  All pairs share every kernel launch (a work list per
+ * pyramid level), so many small ROI calls cost about as much as one; the list is processed in chunks whose upload,
+ * compute and download overlap on three streams.  Buffers from nsof_host_alloc() (page-locked) are copied to/from
+ * directly, other memory goes through an internal pinned staging buffer.  The layout rule holds per pair (its frame
+ * pointers and row strides).  Result per pair == nsof_farneback_px of that pair, bit for bit, in the default
+ * mode; with the opt-in modes that depend on the batch (NSOF_OPT_ROW_BANDS in automatic mode picks its band height from the
+ * batch size; a uniform list takes the uniform driver, where NSOF_OPT_POLYEXP_F32 applies) only to their tolerance.
+ * Items that start aligned for the level-0 pyramid kernel's vector loads (4 bytes for 8-bit, 8 for 16-bit, 16 for float
+ * frames) with row strides that are multiples of that and W % 4 == 0, W >= 8 take its vector form, the others its scalar
+ * form; the result does not depend on it. */
 int nsof_farneback_px_batch(nsof_ctx* ctx, int pixel_type, int n_pairs, const nsof_pair_desc_px* pairs,
                             double pyr_scale, int levels, int winsize, int iterations,
                             int poly_n, double poly_sigma, int flags);
+/* nsof_farneback_px_batch(ctx, NSOF_PIXEL_U8, ...) */
+int nsof_farneback_u8_batch(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs,
+                            double pyr_scale, int levels, int winsize, int iterations,
+                            int poly_n, double poly_sigma, int flags);
+/* nsof_farneback_px_batch(ctx, NSOF_PIXEL_F32, ...) */
+int nsof_farneback_f32_batch(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc_f32* pairs,
+                             double pyr_scale, int levels, int winsize, int iterations,
+                             int poly_n, double poly_sigma, int flags);
+
+/* The device work list, the device-resident twin of the host one: `pairs` is a HOST array whose prev/next/flow are DEVICE
+ * addresses (e.g. crops of frames and of flow canvases already in HBM).  At most 32767 pairs per call
+ * (NSOF_EUNSUPPORTED beyond).  Asynchronous on the context's stream. */
 int nsof_farneback_px_batch_desc_dev(nsof_ctx* ctx, int pixel_type, int n_pairs, const nsof_pair_desc_px* pairs,
                                      double pyr_scale, int levels, int winsize, int iterations,
                                      int poly_n, double poly_sigma, int flags);
+/* nsof_farneback_px_batch_desc_dev(ctx, NSOF_PIXEL_U8, ...) */
+int nsof_farneback_u8_batch_desc_dev(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs,
+                                     double pyr_scale, int levels, int winsize, int iterations,
+                                     int poly_n, double poly_sigma, int flags);
+/* nsof_farneback_px_batch_desc_dev(ctx, NSOF_PIXEL_F32, ...) */
+int nsof_farneback_f32_batch_desc_dev(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc_f32* pairs,
+                                      double pyr_scale, int levels, int winsize, int iterations,
+                                      int poly_n, double poly_sigma, int flags);
+
+/* The gated path of a whole frame sequence on the device (opticalFlow3D's crop -> flow -> paste loop,
+ * /root/reference/optical_flow_seg.py:129-164, 186-204): d_frames = n_frames frames of pixel_type in HBM (row_stride /
+ * frame_stride in bytes, under the layout rule), d_counts / d_rects = the
+ * ROI table nsof_roi_from_surface_dev wrote (rects [n_frames][max_rects][4] = x0, y0, x1, y1), d_flows =
+ * [n_frames - 1][height][width][2] float canvases, zero-filled here.  Pair k = (frame k, frame k + 1) is gated by the
+ * rectangles of frame k + gate_frame: 1 = the map of the pair's second frame (what opticalFlow3D is written to use,
+ * memimg2), 0 = the map of its first frame (what the shipped scripts pass: memimg2 := memimg1, optical_flow_seg.py:435 --
+ * the bug-compatible default of nsof.gating, SURVEY.md Appendix B.2); every crop of every pair is one item of ONE work list, written into the canvas in place;
+ * a crop that overlaps an earlier crop of its pair is pasted after it, in label order, as the reference's loop
+ * overwrites.  Each crop's flow equals nsof_farneback_px of that crop bit for bit.  Only the rectangle table crosses
+ * PCIe (the work list's shapes are needed on the host; the call synchronises the stream once for it).  n_calls /
+ * n_pixels (optional) receive the number of crops and their total area.  Asynchronous otherwise. */
 int nsof_farneback_px_roi_sequence_dev(nsof_ctx* ctx, int pixel_type, int n_frames, const void* d_frames,
                                        ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
                                        const int32_t* d_counts, const int32_t* d_rects, int max_rects, float* d_flows,
                                        double pyr_scale, int levels, int winsize, int iterations, int poly_n,
                                        double poly_sigma, int flags, int gate_frame, long long* n_calls,
                                        long long* n_pixels);
-/* Page-locked host memory for frames / flow fields handed to nsof_farneback_u8_batch / nsof_farneback_f32_batch (NULL on
+/* nsof_farneback_px_roi_sequence_dev(ctx, NSOF_PIXEL_U8, ...) */
+int nsof_farneback_u8_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, ptrdiff_t row_stride,
+                                       ptrdiff_t frame_stride, int width, int height, const int32_t* d_counts,
+                                       const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale, int levels,
+                                       int winsize, int iterations, int poly_n, double poly_sigma, int flags,
+                                       int gate_frame, long long* n_calls, long long* n_pixels);
+/* nsof_farneback_px_roi_sequence_dev(ctx, NSOF_PIXEL_F32, ...) */
+int nsof_farneback_f32_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_frames, ptrdiff_t row_stride,
+                                        ptrdiff_t frame_stride, int width, int height, const int32_t* d_counts,
+                                        const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale, int levels,
+                                        int winsize, int iterations, int poly_n, double poly_sigma, int flags,
+                                        int gate_frame, long long* n_calls, long long* n_pixels);
+/* Page-locked host memory for frames / flow fields handed to nsof_farneback_px_batch and its two exports (NULL on
  * failure). */
 void* nsof_host_alloc(size_t bytes);
 void nsof_host_free(void* p);
@@ -309,14 +325,16 @@ int nsof_farneback_level_size(int width, int height, double pyr_scale, int level
  * float32; M planar [n_img][5][h][w] float32; the polynomial expansion R of ONE image is
  * 5*h*w float32 = [h][w][4] (channels 0..3 interleaved per pixel) followed by [h][w]
  * (channel 4), images back to back. */
-int nsof_stage_pyr_level(nsof_ctx* ctx, int n_img, const uint8_t* d_src, ptrdiff_t row_stride,
-                         ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out);
-/* The same pyramid level from float32 frames (byte strides, multiples of 4). */
-int nsof_stage_pyr_level_f32(nsof_ctx* ctx, int n_img, const float* d_src, ptrdiff_t row_stride,
-                             ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out);
-/* The same pyramid level from frames of any nsof_pixel_type (the layout rules of the typed entries). */
+/* Pyramid level `level` of n_img frames of any nsof_pixel_type (byte strides, under the layout rule of the Farneback
+ * entries). */
 int nsof_stage_pyr_level_px(nsof_ctx* ctx, int pixel_type, int n_img, const void* d_src, ptrdiff_t row_stride,
                             ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out);
+/* nsof_stage_pyr_level_px(ctx, NSOF_PIXEL_U8, ...) */
+int nsof_stage_pyr_level(nsof_ctx* ctx, int n_img, const uint8_t* d_src, ptrdiff_t row_stride,
+                         ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out);
+/* nsof_stage_pyr_level_px(ctx, NSOF_PIXEL_F32, ...) */
+int nsof_stage_pyr_level_f32(nsof_ctx* ctx, int n_img, const float* d_src, ptrdiff_t row_stride,
+                             ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out);
 int nsof_stage_polyexp(nsof_ctx* ctx, int n_img, const float* d_img, int width, int height,
                        int poly_n, double poly_sigma, float* d_R);
 /* Diagnostic: d_out[i] = the reciprocal the 2x2 solves use (rcp + Newton steps + residual correction, without the

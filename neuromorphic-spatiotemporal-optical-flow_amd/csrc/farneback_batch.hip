@@ -5,15 +5,17 @@
 // evaluation loop mixes those with full-frame calls (:492-496).  A crop of 520x200 px cannot fill 256 CUs -- the
 // fused iteration walks its rows serially in 3 workgroups -- so here MANY such calls share every launch:
 //
-//   * nsof_farneback_u8_batch_desc_dev: per level one launch per stage over a device table of work items
+//   * nsof_farneback_px_batch_desc_dev: per level one launch per stage over a device table of work items
 //     (nsof_het_item, nsof_internal.h); an item takes part from its own coarsest level on; the last iteration of
 //     level 0 writes straight into the caller's (strided) flow field, so an ROI result lands in the frame-sized
 //     canvas without a paste.  Arithmetic per item is that of the per-call path, bit for bit.
-//   * nsof_farneback_u8_batch: the same for HOST memory, as a three-stage pipeline over chunks of the list
+//   * nsof_farneback_px_batch: the same for HOST memory, as a three-stage pipeline over chunks of the list
 //     (upload of chunk c+1 and download of chunk c-1 on their own streams while chunk c computes).
-//   * nsof_farneback_f32_*: the same three entries for float32 frames.  Only the pyramid stage reads frames, so a list
-//     differs from an 8-bit one in its pixel size (Params::src) alone: byte addresses and byte strides throughout,
-//     the float instantiations of the pyramid kernels, and level 0 in the two-kernel form (prep, then expansion).
+//   * nsof_farneback_px_roi_sequence_dev: the crops of a gated frame sequence as one such list.
+// Only the pyramid stage reads frames, so a list of one pixel type differs from a list of another in its pixel size
+// (Params::src) alone: byte addresses and byte strides throughout, the pyramid kernels' instantiations for the type, and
+// for float frames level 0 in the two-kernel form (prep, then expansion).  The typed entries (nsof_farneback_px_*) do the
+// work; the nsof_farneback_u8_* and nsof_farneback_f32_* exports at the end of the file name the pixel type and forward.
 #include <sched.h>
 
 #include <algorithm>
@@ -31,12 +33,13 @@ namespace {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// What a typed entry was called with (built there, in that order; src first, so that leaving it out does not compile).
 struct Params {
+    int src;   // nsof_src_type of every frame of the list
     double pyr_scale;
     int levels, winsize, iterations, poly_n;
     double poly_sigma;
     int flags;
-    int src = NSOF_SRC_U8;   // nsof_src_type of every frame of the list
     size_t px() const { return (size_t)nsof_src_bytes(src); }   // bytes per pixel
 };
 
@@ -46,22 +49,12 @@ int validate_desc(nsof_ctx* ctx, int i, const nsof_pair_desc& d, const Params& p
     int rc = nsof_check_farneback_params(ctx, d.width, d.height, p.pyr_scale, p.levels, p.winsize, p.iterations, p.poly_n,
                                          p.flags);
     if (rc) return rc;
-    if (p.src == NSOF_SRC_F32) {   // the layout rules of nsof_farneback_f32
-        if ((reinterpret_cast<uintptr_t>(d.prev) & 3) || (reinterpret_cast<uintptr_t>(d.next) & 3))
-            return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: f32 frames must be 4-byte aligned", i);
-        if ((d.prev_stride & 3) || (d.next_stride & 3) || d.prev_stride < (ptrdiff_t)d.width * 4 ||
-            d.next_stride < (ptrdiff_t)d.width * 4)
-            return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: f32 row strides %td / %td must be multiples of 4 and >= 4*width",
-                                  i, d.prev_stride, d.next_stride);
-    } else if (p.src == NSOF_SRC_U16 || p.src == NSOF_SRC_S16) {   // the layout rules of nsof_farneback_px for 16 bits
-        if ((reinterpret_cast<uintptr_t>(d.prev) & 1) || (reinterpret_cast<uintptr_t>(d.next) & 1))
-            return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: 16-bit frames must be 2-byte aligned", i);
-        if ((d.prev_stride & 1) || (d.next_stride & 1) || d.prev_stride < (ptrdiff_t)d.width * 2 ||
-            d.next_stride < (ptrdiff_t)d.width * 2)
-            return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: 16-bit row strides %td / %td must be even and >= 2*width",
-                                  i, d.prev_stride, d.next_stride);
-    } else if (d.prev_stride < d.width || d.next_stride < d.width)
-        return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: row stride < width", i);
+    if ((rc = nsof_check_frame_layout(ctx, p.src, d.prev, d.prev_stride, 0, d.width, "pair %d prev", i)) ||
+        (rc = nsof_check_frame_layout(ctx, p.src, d.next, d.next_stride, 0, d.width, "pair %d next", i)))
+        return rc;
+    // the driver's own test, as in nsof_farneback_core: what an 8-bit frame, which has no layout to check, must still keep
+    if (d.prev_stride < (ptrdiff_t)(d.width * p.px()) || d.next_stride < (ptrdiff_t)(d.width * p.px()))
+        return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: row stride < width * %zu", i, p.px());
     if (d.flow_stride < (ptrdiff_t)d.width * 8 || (d.flow_stride & 7) || (reinterpret_cast<uintptr_t>(d.flow) & 7))
         return nsof_set_error(ctx, NSOF_EINVAL, "pair %d: flow stride %lld / pointer must be multiples of 8 bytes and "
                               "the stride >= width*8", i, (long long)d.flow_stride);
@@ -468,19 +461,7 @@ struct Chunk {
 
 }  // namespace
 
-extern "C" int nsof_farneback_u8_batch_desc_dev(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, double pyr_scale,
-                                                int levels, int winsize, int iterations, int poly_n, double poly_sigma,
-                                                int flags)
-{
-    if (!ctx) return NSOF_EINVAL;
-    if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return nsof_set_error(ctx, NSOF_EINVAL, "bad pair list");
-    if (n_pairs > 32767) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "n_pairs=%d exceeds 32767 per call", n_pairs);
-    if (n_pairs == 0) return NSOF_OK;
-    const Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-    return het_core(ctx, n_pairs, pairs, p);
-}
-
-// Ordered paste of the private crop fields of nsof_farneback_u8_roi_sequence_dev in ONE launch.  The reference's loop pastes
+// Ordered paste of the private crop fields of nsof_farneback_px_roi_sequence_dev in ONE launch.  The reference's loop pastes
 // a pair's crops one after the other, so where extended component boxes overlap the later component wins
 // (optical_flow_seg.py:162).  A crop that overlaps an earlier one is computed into a private field; its pixels go to the
 // canvas unless a LATER rectangle of the same gating frame covers them (that crop, private by construction, brings its own
@@ -540,7 +521,7 @@ __global__ __launch_bounds__(256) void k_paste_ordered(const PasteRec* __restric
 // canvases in place; a crop that overlaps an earlier crop of its pair (FLAG 1, extended component boxes) is computed into
 // a private buffer and pasted afterwards, in label order, as the reference's loop overwrites.  The only traffic over
 // PCIe is the rectangle table (16 bytes per ROI): the work list's shapes are needed on the host.
-// p.src: the frames' pixel type (the crops' byte addresses and the row stride check follow its size).
+// p.src: the frames' pixel type (the crops' byte addresses, the layout rule and the row stride check follow its size).
 static int roi_sequence(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, ptrdiff_t row_stride, ptrdiff_t frame_stride,
                         int width, int height, const int32_t* d_counts, const int32_t* d_rects, int max_rects, float* d_flows,
                         const Params& p, int gate_frame, long long* n_calls, long long* n_pixels)
@@ -548,6 +529,7 @@ static int roi_sequence(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, pt
     if (!d_frames || !d_counts || !d_rects || !d_flows || n_frames < 2 || max_rects < 1 || width < 1 || height < 1 ||
         row_stride < (ptrdiff_t)(width * p.px()) || (gate_frame != 0 && gate_frame != 1))
         return nsof_set_error(ctx, NSOF_EINVAL, "roi_sequence: bad argument");
+    if (int rc = nsof_check_frame_layout(ctx, p.src, d_frames, row_stride, frame_stride, width, "roi_sequence: d_frames")) return rc;
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const size_t canvas = (size_t)width * height * 2;   // floats per pair
     NSOF_HIP(ctx, hipMemsetAsync(d_flows, 0, (size_t)(n_frames - 1) * canvas * 4, ctx->stream));
@@ -627,37 +609,9 @@ static int roi_sequence(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, pt
     return NSOF_OK;
 }
 
-extern "C" int nsof_farneback_u8_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, ptrdiff_t row_stride,
-                                                  ptrdiff_t frame_stride, int width, int height, const int32_t* d_counts,
-                                                  const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale,
-                                                  int levels, int winsize, int iterations, int poly_n, double poly_sigma,
-                                                  int flags, int gate_frame, long long* n_calls, long long* n_pixels)
-{
-    if (!ctx) return NSOF_EINVAL;
-    const Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-    return roi_sequence(ctx, n_frames, d_frames, row_stride, frame_stride, width, height, d_counts, d_rects, max_rects, d_flows,
-                        p, gate_frame, n_calls, n_pixels);
-}
-
-extern "C" int nsof_farneback_f32_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_frames, ptrdiff_t row_stride,
-                                                   ptrdiff_t frame_stride, int width, int height, const int32_t* d_counts,
-                                                   const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale,
-                                                   int levels, int winsize, int iterations, int poly_n, double poly_sigma,
-                                                   int flags, int gate_frame, long long* n_calls, long long* n_pixels)
-{
-    if (!ctx) return NSOF_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(d_frames) & 3) || (row_stride & 3) || (frame_stride & 3))
-        return nsof_set_error(ctx, NSOF_EINVAL, "roi_sequence: f32 frames must be 4-byte aligned and row_stride=%td / "
-                              "frame_stride=%td multiples of 4", row_stride, frame_stride);
-    Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-    p.src = NSOF_SRC_F32;
-    return roi_sequence(ctx, n_frames, reinterpret_cast<const uint8_t*>(d_frames), row_stride, frame_stride, width, height,
-                        d_counts, d_rects, max_rects, d_flows, p, gate_frame, n_calls, n_pixels);
-}
-
 namespace {
 
-// The pipelined host entry of both pixel types (pairs: HOST pointers; p.src gives the pixel size).
+// The pipelined host entry (pairs: HOST pointers; p.src gives the pixel size).
 int batch_host(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, const Params& p)
 {
     for (int i = 0; i < n_pairs; i++)
@@ -880,55 +834,7 @@ int batch_host(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, const Pa
     return NSOF_OK;
 }
 
-// nsof_pair_desc_f32 -> the driver's byte-address descriptor (same fields, same order)
-std::vector<nsof_pair_desc> f32_descs(int n, const nsof_pair_desc_f32* pairs)
-{
-    std::vector<nsof_pair_desc> out(n);
-    for (int i = 0; i < n; i++) {
-        const nsof_pair_desc_f32& s = pairs[i];
-        out[i] = nsof_pair_desc{reinterpret_cast<const uint8_t*>(s.prev), s.prev_stride, reinterpret_cast<const uint8_t*>(s.next),
-                                s.next_stride, s.width, s.height, s.flow, s.flow_stride};
-    }
-    return out;
-}
-
 }  // namespace
-
-extern "C" int nsof_farneback_u8_batch(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, double pyr_scale,
-                                       int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags)
-{
-    if (!ctx) return NSOF_EINVAL;
-    if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return nsof_set_error(ctx, NSOF_EINVAL, "bad pair list");
-    if (n_pairs == 0) return NSOF_OK;
-    const Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-    return batch_host(ctx, n_pairs, pairs, p);
-}
-
-extern "C" int nsof_farneback_f32_batch(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc_f32* pairs, double pyr_scale,
-                                        int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags)
-{
-    if (!ctx) return NSOF_EINVAL;
-    if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return nsof_set_error(ctx, NSOF_EINVAL, "bad pair list");
-    if (n_pairs == 0) return NSOF_OK;
-    Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-    p.src = NSOF_SRC_F32;
-    const std::vector<nsof_pair_desc> d = f32_descs(n_pairs, pairs);
-    return batch_host(ctx, n_pairs, d.data(), p);
-}
-
-extern "C" int nsof_farneback_f32_batch_desc_dev(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc_f32* pairs, double pyr_scale,
-                                                 int levels, int winsize, int iterations, int poly_n, double poly_sigma,
-                                                 int flags)
-{
-    if (!ctx) return NSOF_EINVAL;
-    if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return nsof_set_error(ctx, NSOF_EINVAL, "bad pair list");
-    if (n_pairs > 32767) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "n_pairs=%d exceeds 32767 per call", n_pairs);
-    if (n_pairs == 0) return NSOF_OK;
-    Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-    p.src = NSOF_SRC_F32;
-    const std::vector<nsof_pair_desc> d = f32_descs(n_pairs, pairs);
-    return het_core(ctx, n_pairs, d.data(), p);
-}
 
 extern "C" void* nsof_host_alloc(size_t bytes)
 {
@@ -945,21 +851,29 @@ extern "C" void nsof_host_free(void* p)
     if (p) (void)hipHostFree(p);
 }
 
-// ---- typed work-list entries (nsof_pixel_type == nsof_src_type; nsof_pair_desc_px has nsof_pair_desc's layout) -------
-static_assert(sizeof(nsof_pair_desc_px) == sizeof(nsof_pair_desc) && offsetof(nsof_pair_desc_px, next) == offsetof(nsof_pair_desc, next) &&
-                  offsetof(nsof_pair_desc_px, flow_stride) == offsetof(nsof_pair_desc, flow_stride),
-              "nsof_pair_desc_px must keep nsof_pair_desc's layout");
+// ---- the work-list routes' entries ------------------------------------------------------------------------------------
+// The three descriptor structs of nsof.h have one layout (they differ in the type their frame pointers name); the drivers
+// take nsof_pair_desc, whose frame pointers are byte addresses.
+template <class D> constexpr bool is_pair_desc_layout()
+{
+    return sizeof(D) == sizeof(nsof_pair_desc) && offsetof(D, prev) == offsetof(nsof_pair_desc, prev) &&
+           offsetof(D, prev_stride) == offsetof(nsof_pair_desc, prev_stride) && offsetof(D, next) == offsetof(nsof_pair_desc, next) &&
+           offsetof(D, next_stride) == offsetof(nsof_pair_desc, next_stride) && offsetof(D, width) == offsetof(nsof_pair_desc, width) &&
+           offsetof(D, height) == offsetof(nsof_pair_desc, height) && offsetof(D, flow) == offsetof(nsof_pair_desc, flow) &&
+           offsetof(D, flow_stride) == offsetof(nsof_pair_desc, flow_stride);
+}
+static_assert(is_pair_desc_layout<nsof_pair_desc_px>(), "nsof_pair_desc_px must keep nsof_pair_desc's layout");
+static_assert(is_pair_desc_layout<nsof_pair_desc_f32>(), "nsof_pair_desc_f32 must keep nsof_pair_desc's layout");
+template <class D> static const nsof_pair_desc_px* as_px(const D* pairs) { return reinterpret_cast<const nsof_pair_desc_px*>(pairs); }
 
 extern "C" int nsof_farneback_px_batch(nsof_ctx* ctx, int pixel_type, int n_pairs, const nsof_pair_desc_px* pairs,
                                        double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma,
                                        int flags)
 {
-    if (!ctx) return NSOF_EINVAL;
-    if (!nsof_src_valid(pixel_type)) return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
+    if (int rc = nsof_check_typed(ctx, pixel_type)) return rc;
     if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return nsof_set_error(ctx, NSOF_EINVAL, "bad pair list");
     if (n_pairs == 0) return NSOF_OK;
-    Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-    p.src = pixel_type;
+    const Params p{pixel_type, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
     return batch_host(ctx, n_pairs, reinterpret_cast<const nsof_pair_desc*>(pairs), p);
 }
 
@@ -967,13 +881,11 @@ extern "C" int nsof_farneback_px_batch_desc_dev(nsof_ctx* ctx, int pixel_type, i
                                                 double pyr_scale, int levels, int winsize, int iterations, int poly_n,
                                                 double poly_sigma, int flags)
 {
-    if (!ctx) return NSOF_EINVAL;
-    if (!nsof_src_valid(pixel_type)) return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
+    if (int rc = nsof_check_typed(ctx, pixel_type)) return rc;
     if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return nsof_set_error(ctx, NSOF_EINVAL, "bad pair list");
     if (n_pairs > 32767) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "n_pairs=%d exceeds 32767 per call", n_pairs);
     if (n_pairs == 0) return NSOF_OK;
-    Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-    p.src = pixel_type;
+    const Params p{pixel_type, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
     return het_core(ctx, n_pairs, reinterpret_cast<const nsof_pair_desc*>(pairs), p);
 }
 
@@ -984,17 +896,61 @@ extern "C" int nsof_farneback_px_roi_sequence_dev(nsof_ctx* ctx, int pixel_type,
                                                   double poly_sigma, int flags, int gate_frame, long long* n_calls,
                                                   long long* n_pixels)
 {
-    if (!ctx) return NSOF_EINVAL;
-    if (!nsof_src_valid(pixel_type)) return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
-    if (pixel_type == NSOF_SRC_F32)
-        return nsof_farneback_f32_roi_sequence_dev(ctx, n_frames, static_cast<const float*>(d_frames), row_stride, frame_stride,
-                                                   width, height, d_counts, d_rects, max_rects, d_flows, pyr_scale, levels,
-                                                   winsize, iterations, poly_n, poly_sigma, flags, gate_frame, n_calls, n_pixels);
-    if (pixel_type != NSOF_SRC_U8 && ((reinterpret_cast<uintptr_t>(d_frames) & 1) || (row_stride & 1) || (frame_stride & 1)))
-        return nsof_set_error(ctx, NSOF_EINVAL, "roi_sequence: 16-bit frames must be 2-byte aligned and row_stride=%td / "
-                              "frame_stride=%td even", row_stride, frame_stride);
-    Params p{pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-    p.src = pixel_type;
+    if (int rc = nsof_check_typed(ctx, pixel_type)) return rc;
+    const Params p{pixel_type, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
     return roi_sequence(ctx, n_frames, static_cast<const uint8_t*>(d_frames), row_stride, frame_stride, width, height,
                         d_counts, d_rects, max_rects, d_flows, p, gate_frame, n_calls, n_pixels);
+}
+
+// ---- the 8-bit and float32 exports of these routes: the typed entry with the pixel type named ---------------------------
+extern "C" int nsof_farneback_u8_batch(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, double pyr_scale,
+                                       int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags)
+{
+    return nsof_farneback_px_batch(ctx, NSOF_PIXEL_U8, n_pairs, as_px(pairs), pyr_scale, levels, winsize, iterations, poly_n,
+                                   poly_sigma, flags);
+}
+
+extern "C" int nsof_farneback_f32_batch(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc_f32* pairs, double pyr_scale,
+                                        int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags)
+{
+    return nsof_farneback_px_batch(ctx, NSOF_PIXEL_F32, n_pairs, as_px(pairs), pyr_scale, levels, winsize, iterations, poly_n,
+                                   poly_sigma, flags);
+}
+
+extern "C" int nsof_farneback_u8_batch_desc_dev(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc* pairs, double pyr_scale,
+                                                int levels, int winsize, int iterations, int poly_n, double poly_sigma,
+                                                int flags)
+{
+    return nsof_farneback_px_batch_desc_dev(ctx, NSOF_PIXEL_U8, n_pairs, as_px(pairs), pyr_scale, levels, winsize, iterations,
+                                            poly_n, poly_sigma, flags);
+}
+
+extern "C" int nsof_farneback_f32_batch_desc_dev(nsof_ctx* ctx, int n_pairs, const nsof_pair_desc_f32* pairs, double pyr_scale,
+                                                 int levels, int winsize, int iterations, int poly_n, double poly_sigma,
+                                                 int flags)
+{
+    return nsof_farneback_px_batch_desc_dev(ctx, NSOF_PIXEL_F32, n_pairs, as_px(pairs), pyr_scale, levels, winsize, iterations,
+                                            poly_n, poly_sigma, flags);
+}
+
+extern "C" int nsof_farneback_u8_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, ptrdiff_t row_stride,
+                                                  ptrdiff_t frame_stride, int width, int height, const int32_t* d_counts,
+                                                  const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale,
+                                                  int levels, int winsize, int iterations, int poly_n, double poly_sigma,
+                                                  int flags, int gate_frame, long long* n_calls, long long* n_pixels)
+{
+    return nsof_farneback_px_roi_sequence_dev(ctx, NSOF_PIXEL_U8, n_frames, d_frames, row_stride, frame_stride, width, height,
+                                              d_counts, d_rects, max_rects, d_flows, pyr_scale, levels, winsize, iterations,
+                                              poly_n, poly_sigma, flags, gate_frame, n_calls, n_pixels);
+}
+
+extern "C" int nsof_farneback_f32_roi_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_frames, ptrdiff_t row_stride,
+                                                   ptrdiff_t frame_stride, int width, int height, const int32_t* d_counts,
+                                                   const int32_t* d_rects, int max_rects, float* d_flows, double pyr_scale,
+                                                   int levels, int winsize, int iterations, int poly_n, double poly_sigma,
+                                                   int flags, int gate_frame, long long* n_calls, long long* n_pixels)
+{
+    return nsof_farneback_px_roi_sequence_dev(ctx, NSOF_PIXEL_F32, n_frames, d_frames, row_stride, frame_stride, width, height,
+                                              d_counts, d_rects, max_rects, d_flows, pyr_scale, levels, winsize, iterations,
+                                              poly_n, poly_sigma, flags, gate_frame, n_calls, n_pixels);
 }

@@ -492,41 +492,54 @@ int nsof_check_farneback_params(nsof_ctx* ctx, int width, int height, double pyr
     return NSOF_OK;
 }
 
-// ---- stage entry points ---------------------------------------------------------------------
-static int stage_pyr_level(nsof_ctx* ctx, int src, int n_img, const void* d_src, ptrdiff_t row_stride,
-                           ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out)
+// ---- frame layout ---------------------------------------------------------------------------------------------------
+// The layout rule of frames of pixel type src (nsof_src_type), stated once: p is one frame, or the first of a stack of
+// frames img_stride bytes apart (0 for a lone frame).  Frames are addressed with byte strides whatever the pixel type, so
+// every pixel must stay aligned to its size: the start address and both strides multiples of the pixel size, and a row
+// stride that holds a row.  The kernels take their vector forms only where rows are aligned for them and scalar loads
+// elsewhere, so crops that start at any element are fine.  1-byte pixels have nothing to check here: what the 8-bit
+// routes ask of a row stride stays with their drivers.  `who` (printf-style) names the frame in the message.
+int nsof_check_frame_layout(nsof_ctx* ctx, int src, const void* p, ptrdiff_t row_stride, ptrdiff_t img_stride, int width,
+                            const char* who, ...)
 {
-    if (!ctx || !d_src || !d_out || n_img < 1) return NSOF_EINVAL;
-    if (!nsof_src_valid(src)) return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", src);
-    const int pb = nsof_src_bytes(src);
-    if (pb > 1 && (width < 1 || row_stride < (ptrdiff_t)width * pb || (row_stride % pb) || (img_stride % pb) ||
-                   (reinterpret_cast<uintptr_t>(d_src) % pb)))
-        return nsof_set_error(ctx, NSOF_EINVAL, "%d-byte frames: strides must be multiples of %d bytes, row_stride >= %d*width, "
-                                                "pointer %d-byte aligned", pb, pb, pb, pb);
+    const ptrdiff_t px = nsof_src_bytes(src);
+    if (px == 1 || (reinterpret_cast<uintptr_t>(p) % px == 0 && row_stride % px == 0 && img_stride % px == 0 &&
+                    row_stride >= px * width))
+        return NSOF_OK;
+    char name[64];
+    va_list ap;
+    va_start(ap, who);
+    vsnprintf(name, sizeof(name), who, ap);
+    va_end(ap);
+    return nsof_set_error(ctx, NSOF_EINVAL, "%s: %td-byte pixels need the address, the row stride (%td) and the image stride (%td) "
+                          "to be multiples of %td and the row stride >= %td*width", name, px, row_stride, img_stride, px, px);
+}
+
+// ---- stage entry points ---------------------------------------------------------------------
+extern "C" int nsof_stage_pyr_level_px(nsof_ctx* ctx, int pixel_type, int n_img, const void* d_src, ptrdiff_t row_stride,
+                                       ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out)
+{
+    if (int rc = nsof_check_typed(ctx, pixel_type)) return rc;
+    if (!d_src || !d_out || n_img < 1) return NSOF_EINVAL;
+    if (int rc = nsof_check_frame_layout(ctx, pixel_type, d_src, row_stride, img_stride, width, "d_src")) return rc;
     int wk, hk;
     nsof_blur_taps taps;
     if (int rc = nsof_level_geom(ctx, width, height, pyr_scale, level, &wk, &hk, &taps)) return rc;
-    return NSOF_PYR_SEL(ctx, nsof_launch_prep, n_img, d_src, row_stride, img_stride, width, height, wk, hk, taps, d_out, src);
+    return NSOF_PYR_SEL(ctx, nsof_launch_prep, n_img, d_src, row_stride, img_stride, width, height, wk, hk, taps, d_out, pixel_type);
 }
 
 extern "C" int nsof_stage_pyr_level(nsof_ctx* ctx, int n_img, const uint8_t* d_src, ptrdiff_t row_stride,
                                     ptrdiff_t img_stride, int width, int height, double pyr_scale, int level,
                                     float* d_out)
 {
-    return stage_pyr_level(ctx, NSOF_SRC_U8, n_img, d_src, row_stride, img_stride, width, height, pyr_scale, level, d_out);
+    return nsof_stage_pyr_level_px(ctx, NSOF_PIXEL_U8, n_img, d_src, row_stride, img_stride, width, height, pyr_scale, level, d_out);
 }
 
 extern "C" int nsof_stage_pyr_level_f32(nsof_ctx* ctx, int n_img, const float* d_src, ptrdiff_t row_stride,
                                         ptrdiff_t img_stride, int width, int height, double pyr_scale, int level,
                                         float* d_out)
 {
-    return stage_pyr_level(ctx, NSOF_SRC_F32, n_img, d_src, row_stride, img_stride, width, height, pyr_scale, level, d_out);
-}
-
-extern "C" int nsof_stage_pyr_level_px(nsof_ctx* ctx, int pixel_type, int n_img, const void* d_src, ptrdiff_t row_stride,
-                                       ptrdiff_t img_stride, int width, int height, double pyr_scale, int level, float* d_out)
-{
-    return stage_pyr_level(ctx, pixel_type, n_img, d_src, row_stride, img_stride, width, height, pyr_scale, level, d_out);
+    return nsof_stage_pyr_level_px(ctx, NSOF_PIXEL_F32, n_img, d_src, row_stride, img_stride, width, height, pyr_scale, level, d_out);
 }
 
 __global__ void k_recip_probe(long long n, const double* __restrict__ x, double* __restrict__ fast, double* __restrict__ ieee)
@@ -888,93 +901,54 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     return NSOF_OK;
 }
 
-extern "C" int nsof_farneback_u8_batch_dev(nsof_ctx* ctx, int n_pairs, const uint8_t* d_prev, const uint8_t* d_next,
-                                           ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height,
-                                           float* d_flow, double pyr_scale, int levels, int winsize, int iterations,
-                                           int poly_n, double poly_sigma, int flags)
+// ---- the uniform routes: device batch and device sequence ----------------------------------------------------------
+// Every route has ONE typed entry (nsof_pixel_type == nsof_src_type) that does the work, in this order: context, pixel
+// type, null pointers and counts, frame layout, then the driver with its parameter checks.  The nsof_farneback_u8* and
+// nsof_farneback_f32* exports name the pixel type and forward (the end of this file and of farneback_batch.hip).
+extern "C" int nsof_farneback_px_batch_dev(nsof_ctx* ctx, int pixel_type, int n_pairs, const void* d_prev, const void* d_next,
+                                           ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height, float* d_flow,
+                                           double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                                           double poly_sigma, int flags)
 {
-    return nsof_farneback_core(ctx, false, n_pairs, d_prev, d_next, row_stride, pair_stride, width, height, d_flow, pyr_scale,
-                          levels, winsize, iterations, poly_n, poly_sigma, flags);
-}
-
-extern "C" int nsof_farneback_u8_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames,
-                                              ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
-                                              float* d_flow, double pyr_scale, int levels, int winsize,
-                                              int iterations, int poly_n, double poly_sigma, int flags)
-{
-    if (!ctx) return NSOF_EINVAL;
-    if (n_frames < 2) return nsof_set_error(ctx, NSOF_EINVAL, "a sequence needs at least 2 frames");
-    return nsof_farneback_core(ctx, true, n_frames - 1, d_frames, nullptr, row_stride, frame_stride, width, height, d_flow,
-                          pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
-}
-
-// ---- float frames: the same driver with the f32 pyramid stage --------------------------------------------------
-// A float frame is addressed with byte strides like an 8-bit one: rows (and pairs / frames) must keep every pixel
-// 4-byte aligned.  The kernels take their vector forms only where rows are 16-byte aligned and fall back to scalar
-// loads elsewhere, so cropped views that start at any element are fine.
-static int check_f32_layout(nsof_ctx* ctx, const void* p, ptrdiff_t row_stride, ptrdiff_t img_stride, int width)
-{
-    if ((reinterpret_cast<uintptr_t>(p) & 3) != 0) return nsof_set_error(ctx, NSOF_EINVAL, "f32 frames must be 4-byte aligned");
-    if ((row_stride & 3) != 0 || row_stride < (ptrdiff_t)width * 4)
-        return nsof_set_error(ctx, NSOF_EINVAL, "f32 row_stride=%td must be a multiple of 4 and >= 4*width", row_stride);
-    if ((img_stride & 3) != 0) return nsof_set_error(ctx, NSOF_EINVAL, "f32 pair/frame stride=%td must be a multiple of 4", img_stride);
-    return NSOF_OK;
-}
-// The same rules for 16-bit frames: every pixel 2-byte aligned, row stride >= 2*width.
-static int check_16_layout(nsof_ctx* ctx, const void* p, ptrdiff_t row_stride, ptrdiff_t img_stride, int width)
-{
-    if ((reinterpret_cast<uintptr_t>(p) & 1) != 0) return nsof_set_error(ctx, NSOF_EINVAL, "16-bit frames must be 2-byte aligned");
-    if ((row_stride & 1) != 0 || row_stride < (ptrdiff_t)width * 2)
-        return nsof_set_error(ctx, NSOF_EINVAL, "16-bit row_stride=%td must be even and >= 2*width", row_stride);
-    if ((img_stride & 1) != 0) return nsof_set_error(ctx, NSOF_EINVAL, "16-bit pair/frame stride=%td must be even", img_stride);
-    return NSOF_OK;
-}
-
-extern "C" int nsof_farneback_f32_batch_dev(nsof_ctx* ctx, int n_pairs, const float* d_prev, const float* d_next,
-                                            ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height,
-                                            float* d_flow, double pyr_scale, int levels, int winsize, int iterations,
-                                            int poly_n, double poly_sigma, int flags)
-{
-    if (!ctx) return NSOF_EINVAL;
+    if (int rc = nsof_check_typed(ctx, pixel_type)) return rc;
     if (!d_prev || !d_next || !d_flow) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer");
-    int rc = check_f32_layout(ctx, d_prev, row_stride, pair_stride, width);
-    if (rc == NSOF_OK) rc = check_f32_layout(ctx, d_next, row_stride, pair_stride, width);
+    int rc = nsof_check_frame_layout(ctx, pixel_type, d_prev, row_stride, pair_stride, width, "d_prev");
+    if (rc == NSOF_OK) rc = nsof_check_frame_layout(ctx, pixel_type, d_next, row_stride, pair_stride, width, "d_next");
     if (rc) return rc;
     return nsof_farneback_core(ctx, false, n_pairs, d_prev, d_next, row_stride, pair_stride, width, height, d_flow, pyr_scale,
-                               levels, winsize, iterations, poly_n, poly_sigma, flags, NSOF_SRC_F32);
+                               levels, winsize, iterations, poly_n, poly_sigma, flags, pixel_type);
 }
 
-extern "C" int nsof_farneback_f32_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_frames,
-                                               ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
-                                               float* d_flow, double pyr_scale, int levels, int winsize,
-                                               int iterations, int poly_n, double poly_sigma, int flags)
+extern "C" int nsof_farneback_px_sequence_dev(nsof_ctx* ctx, int pixel_type, int n_frames, const void* d_frames,
+                                              ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
+                                              float* d_flow, double pyr_scale, int levels, int winsize, int iterations,
+                                              int poly_n, double poly_sigma, int flags)
 {
-    if (!ctx) return NSOF_EINVAL;
+    if (int rc = nsof_check_typed(ctx, pixel_type)) return rc;
     if (n_frames < 2) return nsof_set_error(ctx, NSOF_EINVAL, "a sequence needs at least 2 frames");
     if (!d_frames || !d_flow) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer");
-    if (int rc = check_f32_layout(ctx, d_frames, row_stride, frame_stride, width)) return rc;
+    if (int rc = nsof_check_frame_layout(ctx, pixel_type, d_frames, row_stride, frame_stride, width, "d_frames")) return rc;
     return nsof_farneback_core(ctx, true, n_frames - 1, d_frames, nullptr, row_stride, frame_stride, width, height, d_flow,
-                               pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, NSOF_SRC_F32);
+                               pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, pixel_type);
 }
 
-// The host-pointer pair entries, src: nsof_src_type.  Dense frames go straight from the caller's memory; strided host
-// views are packed row by row into a pinned staging buffer and moved with ONE linear copy per direction: hipMemcpy2D
-// degenerates to a copy per row for widths that are not nicely aligned (measured 12 ms for an 801x801 pair against
-// 3 ms of kernels).  On the device the pair lies back to back (one pyramid launch per level for both frames).
+// ---- the lone host pair ----------------------------------------------------------------------------------------------
+// src: nsof_src_type.  Dense frames go straight from the caller's memory; strided host views are packed row by row into
+// a pinned staging buffer and moved with ONE linear copy per direction: hipMemcpy2D degenerates to a copy per row for
+// widths that are not nicely aligned (measured 12 ms for an 801x801 pair against 3 ms of kernels).  On the device the
+// pair lies back to back (one pyramid launch per level for both frames).  8-bit frames take any row stride, a flipped
+// view's negative one included (nsof_check_frame_layout has nothing to check for them); the parameter checks come
+// before the layout check here, so an empty image is NSOF_ESHAPE whatever its strides.
 static int farneback_host_pair(nsof_ctx* ctx, int src, const void* prev, ptrdiff_t prev_stride, const void* next,
                                ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
                                double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma,
                                int flags)
 {
-    if (!ctx) return NSOF_EINVAL;
     if (!prev || !next || !flow) return nsof_set_error(ctx, NSOF_EINVAL, "null image pointer");
     int rc = nsof_check_farneback_params(ctx, width, height, pyr_scale, levels, winsize, iterations, poly_n, flags);
     if (rc) return rc;
-    if (src == NSOF_SRC_F32 &&
-        ((rc = check_f32_layout(ctx, prev, prev_stride, 0, width)) || (rc = check_f32_layout(ctx, next, next_stride, 0, width))))
-        return rc;
-    if ((src == NSOF_SRC_U16 || src == NSOF_SRC_S16) &&
-        ((rc = check_16_layout(ctx, prev, prev_stride, 0, width)) || (rc = check_16_layout(ctx, next, next_stride, 0, width))))
+    if ((rc = nsof_check_frame_layout(ctx, src, prev, prev_stride, 0, width, "prev")) ||
+        (rc = nsof_check_frame_layout(ctx, src, next, next_stride, 0, width, "next")))
         return rc;
     if (flow_stride < (ptrdiff_t)(width * 8)) return nsof_set_error(ctx, NSOF_EINVAL, "flow_stride < width*8");
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
@@ -1012,89 +986,69 @@ static int farneback_host_pair(nsof_ctx* ctx, int src, const void* prev, ptrdiff
     return NSOF_OK;
 }
 
-extern "C" int nsof_farneback_f32(nsof_ctx* ctx, const float* prev, ptrdiff_t prev_stride, const float* next,
-                                  ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
-                                  double pyr_scale, int levels, int winsize, int iterations, int poly_n,
-                                  double poly_sigma, int flags)
-{
-    return farneback_host_pair(ctx, NSOF_SRC_F32, prev, prev_stride, next, next_stride, width, height, flow, flow_stride,
-                               pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
-}
-
-extern "C" int nsof_farneback_u8(nsof_ctx* ctx, const uint8_t* prev, ptrdiff_t prev_stride, const uint8_t* next,
-                                 ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
-                                 double pyr_scale, int levels, int winsize, int iterations, int poly_n,
-                                 double poly_sigma, int flags)
-{
-    return farneback_host_pair(ctx, NSOF_SRC_U8, prev, prev_stride, next, next_stride, width, height, flow, flow_stride,
-                               pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
-}
-
-// ---- typed entries (nsof_pixel_type == nsof_src_type): U8 / F32 go to their twins, 16-bit frames to the same driver --
 extern "C" int nsof_farneback_px(nsof_ctx* ctx, int pixel_type, const void* prev, ptrdiff_t prev_stride, const void* next,
                                  ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
                                  double pyr_scale, int levels, int winsize, int iterations, int poly_n,
                                  double poly_sigma, int flags)
 {
-    if (!ctx) return NSOF_EINVAL;
-    if (!nsof_src_valid(pixel_type)) return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
+    if (int rc = nsof_check_typed(ctx, pixel_type)) return rc;
     return farneback_host_pair(ctx, pixel_type, prev, prev_stride, next, next_stride, width, height, flow, flow_stride,
                                pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
 }
 
-extern "C" int nsof_farneback_px_batch_dev(nsof_ctx* ctx, int pixel_type, int n_pairs, const void* d_prev, const void* d_next,
-                                           ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height, float* d_flow,
-                                           double pyr_scale, int levels, int winsize, int iterations, int poly_n,
-                                           double poly_sigma, int flags)
+// ---- the 8-bit and float32 exports of these routes: the typed entry with the pixel type named ---------------------------
+extern "C" int nsof_farneback_u8(nsof_ctx* ctx, const uint8_t* prev, ptrdiff_t prev_stride, const uint8_t* next,
+                                 ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
+                                 double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                                 double poly_sigma, int flags)
 {
-    if (!ctx) return NSOF_EINVAL;
-    switch (pixel_type) {
-        case NSOF_SRC_U8:
-            return nsof_farneback_u8_batch_dev(ctx, n_pairs, static_cast<const uint8_t*>(d_prev), static_cast<const uint8_t*>(d_next),
-                                               row_stride, pair_stride, width, height, d_flow, pyr_scale, levels, winsize,
-                                               iterations, poly_n, poly_sigma, flags);
-        case NSOF_SRC_F32:
-            return nsof_farneback_f32_batch_dev(ctx, n_pairs, static_cast<const float*>(d_prev), static_cast<const float*>(d_next),
-                                                row_stride, pair_stride, width, height, d_flow, pyr_scale, levels, winsize,
-                                                iterations, poly_n, poly_sigma, flags);
-        case NSOF_SRC_U16:
-        case NSOF_SRC_S16: {
-            if (!d_prev || !d_next || !d_flow) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer");
-            int rc = check_16_layout(ctx, d_prev, row_stride, pair_stride, width);
-            if (rc == NSOF_OK) rc = check_16_layout(ctx, d_next, row_stride, pair_stride, width);
-            if (rc) return rc;
-            return nsof_farneback_core(ctx, false, n_pairs, d_prev, d_next, row_stride, pair_stride, width, height, d_flow,
-                                       pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, pixel_type);
-        }
-        default: return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
-    }
+    return nsof_farneback_px(ctx, NSOF_PIXEL_U8, prev, prev_stride, next, next_stride, width, height, flow, flow_stride,
+                             pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
 }
 
-extern "C" int nsof_farneback_px_sequence_dev(nsof_ctx* ctx, int pixel_type, int n_frames, const void* d_frames,
-                                              ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
-                                              float* d_flow, double pyr_scale, int levels, int winsize, int iterations,
-                                              int poly_n, double poly_sigma, int flags)
+extern "C" int nsof_farneback_f32(nsof_ctx* ctx, const float* prev, ptrdiff_t prev_stride, const float* next,
+                                  ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
+                                  double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                                  double poly_sigma, int flags)
 {
-    if (!ctx) return NSOF_EINVAL;
-    switch (pixel_type) {
-        case NSOF_SRC_U8:
-            return nsof_farneback_u8_sequence_dev(ctx, n_frames, static_cast<const uint8_t*>(d_frames), row_stride, frame_stride,
-                                                  width, height, d_flow, pyr_scale, levels, winsize, iterations, poly_n,
-                                                  poly_sigma, flags);
-        case NSOF_SRC_F32:
-            return nsof_farneback_f32_sequence_dev(ctx, n_frames, static_cast<const float*>(d_frames), row_stride, frame_stride,
-                                                   width, height, d_flow, pyr_scale, levels, winsize, iterations, poly_n,
-                                                   poly_sigma, flags);
-        case NSOF_SRC_U16:
-        case NSOF_SRC_S16: {
-            if (n_frames < 2) return nsof_set_error(ctx, NSOF_EINVAL, "a sequence needs at least 2 frames");
-            if (!d_frames || !d_flow) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer");
-            if (int rc = check_16_layout(ctx, d_frames, row_stride, frame_stride, width)) return rc;
-            return nsof_farneback_core(ctx, true, n_frames - 1, d_frames, nullptr, row_stride, frame_stride, width, height,
-                                       d_flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, pixel_type);
-        }
-        default: return nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
-    }
+    return nsof_farneback_px(ctx, NSOF_PIXEL_F32, prev, prev_stride, next, next_stride, width, height, flow, flow_stride,
+                             pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
+}
+
+extern "C" int nsof_farneback_u8_batch_dev(nsof_ctx* ctx, int n_pairs, const uint8_t* d_prev, const uint8_t* d_next,
+                                           ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height,
+                                           float* d_flow, double pyr_scale, int levels, int winsize, int iterations,
+                                           int poly_n, double poly_sigma, int flags)
+{
+    return nsof_farneback_px_batch_dev(ctx, NSOF_PIXEL_U8, n_pairs, d_prev, d_next, row_stride, pair_stride, width, height,
+                                       d_flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
+}
+
+extern "C" int nsof_farneback_f32_batch_dev(nsof_ctx* ctx, int n_pairs, const float* d_prev, const float* d_next,
+                                            ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height,
+                                            float* d_flow, double pyr_scale, int levels, int winsize, int iterations,
+                                            int poly_n, double poly_sigma, int flags)
+{
+    return nsof_farneback_px_batch_dev(ctx, NSOF_PIXEL_F32, n_pairs, d_prev, d_next, row_stride, pair_stride, width, height,
+                                       d_flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
+}
+
+extern "C" int nsof_farneback_u8_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames,
+                                              ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
+                                              float* d_flow, double pyr_scale, int levels, int winsize,
+                                              int iterations, int poly_n, double poly_sigma, int flags)
+{
+    return nsof_farneback_px_sequence_dev(ctx, NSOF_PIXEL_U8, n_frames, d_frames, row_stride, frame_stride, width, height,
+                                          d_flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
+}
+
+extern "C" int nsof_farneback_f32_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_frames,
+                                               ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
+                                               float* d_flow, double pyr_scale, int levels, int winsize,
+                                               int iterations, int poly_n, double poly_sigma, int flags)
+{
+    return nsof_farneback_px_sequence_dev(ctx, NSOF_PIXEL_F32, n_frames, d_frames, row_stride, frame_stride, width, height,
+                                          d_flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
 }
 
 // ---- ROI gating (host arithmetic on maps of at most a few hundred cells) -------------------------------------------

@@ -90,13 +90,13 @@ struct nsof_ctx {
     // work-list path: per-level item tables, two used alternately (the pinned copy of one is rewritten two calls later)
     nsof_table het[2];
     int het_flip = 0;
-    // pipelined host entry (nsof_farneback_u8_batch): copy streams, per-slot staging and events
+    // pipelined host entry (nsof_farneback_px_batch): copy streams, per-slot staging and events
     struct nsof_pipe* pipe = nullptr;
     // small-batch schedule of the uniform batch driver: a side stream for the pyramid levels and expansions of the
     // finer levels, next to the iterations of the coarser ones, and the events that hand each level over
     hipStream_t side = nullptr;
     std::vector<hipEvent_t> ov_events;
-    // private flow buffers of ROI crops that overlap an earlier crop of the same frame pair (nsof_farneback_u8_roi_sequence_dev)
+    // private flow buffers of ROI crops that overlap an earlier crop of the same frame pair (nsof_farneback_px_roi_sequence_dev)
     nsof_dev_buf<> roi_tmp;
     // ... and the table of their ordered pastes
     nsof_table paste;
@@ -140,13 +140,23 @@ struct nsof_prof_scope {
 enum nsof_src_type { NSOF_SRC_U8 = 0, NSOF_SRC_F32 = 1, NSOF_SRC_U16 = 2, NSOF_SRC_S16 = 3 };
 static inline int nsof_src_bytes(int src) { return src == NSOF_SRC_F32 ? 4 : (src == NSOF_SRC_U8 ? 1 : 2); }
 static inline bool nsof_src_valid(int src) { return src >= NSOF_SRC_U8 && src <= NSOF_SRC_S16; }
+// The first two checks of every typed entry: a context, then a known pixel type.
+static inline int nsof_check_typed(nsof_ctx* ctx, int pixel_type)
+{
+    if (!ctx) return NSOF_EINVAL;
+    return nsof_src_valid(pixel_type) ? NSOF_OK : nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", pixel_type);
+}
+// The layout rule of a frame (nsof_api.hip): NSOF_EINVAL, the message starting with `who`, unless the start address and
+// both strides are multiples of the pixel size and the row stride is at least pixel size * width.
+int nsof_check_frame_layout(nsof_ctx* ctx, int src, const void* p, ptrdiff_t row_stride, ptrdiff_t img_stride, int width,
+                            const char* who, ...) __attribute__((format(printf, 7, 8)));
 int nsof_check_farneback_params(nsof_ctx* ctx, int width, int height, double pyr_scale, int levels, int winsize,
                                 int iterations, int poly_n, int flags);
 // Uniform-shape device batch (sequence == true: n_pairs + 1 consecutive frames in d_prev); src: nsof_src_type.
 int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* d_prev, const void* d_next,
                         ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height, float* d_flow,
                         double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma,
-                        int flags, int src = NSOF_SRC_U8);
+                        int flags, int src);
 void nsof_pipe_destroy(nsof_ctx* ctx);
 
 // ---- Farneback launchers (farneback_kernels.hip) ------------------------------------------
@@ -176,7 +186,7 @@ static inline int nsof_level_geom(nsof_ctx* ctx, int width, int height, double p
 }
 int nsof_host_poly_taps(int n, double sigma, nsof_poly_taps* out);
 
-// ---- shape-heterogeneous work lists (nsof_farneback_u8_batch*, nsof_farneback_f32_batch*) -----------------------
+// ---- shape-heterogeneous work lists (nsof_farneback_px_batch*, nsof_farneback_px_roi_sequence_dev) ----------------
 // One work item (a frame pair of its own shape) at ONE pyramid level.  The host builds one table per level (items
 // that have no such level are left out) and every stage is launched once per level over the whole table:
 // gridDim.z indexes the table (x2 for the per-image stages), gridDim.x/y are sized for the largest item and the
@@ -213,10 +223,10 @@ int nsof_launch_iterate_lat_het(nsof_ctx* ctx, int n_items, const nsof_het_item*
 // The *_het twins take a device table of n_items entries; max_* are the largest extents over the table.
 // src_type (nsof_src_type): the pixel type of every item's frames.
 int nsof_launch_prep_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items,
-                         bool level0, const nsof_blur_taps& taps, float* I, int src_type = NSOF_SRC_U8);
+                         bool level0, const nsof_blur_taps& taps, float* I, int src_type);
 int nsof_launch_polyexp_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
-                            const nsof_poly_taps& taps, const float* I, float* R, const float* blur3 = nullptr,
-                            int src_type = NSOF_SRC_U8);
+                            const nsof_poly_taps& taps, const float* I, float* R, const float* blur3,
+                            int src_type);
 int nsof_launch_flow_upsample_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
                                   const float* src, float* dst, float mul);
 // final: the flow goes to the items' own output fields (out / out_pitch) instead of flow_out.
@@ -224,18 +234,18 @@ int nsof_launch_iterate_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_i
                             const float* flow_in, float* flow_out, bool final, int winsize);
 // src: n_img frames of pixel type src_type (nsof_src_type), row / image strides in bytes.
 int nsof_launch_prep(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
-                     int H, int wk, int hk, const nsof_blur_taps& taps, float* out, int src_type = NSOF_SRC_U8);
+                     int H, int wk, int hk, const nsof_blur_taps& taps, float* out, int src_type);
 // The *_fma twins (farneback_kernels.hip compiled with -DNSOF_PYR_FMA): same taps and order, every tap / blend one fused
 // multiply-add -- selected by ctx->opt_pyr_fma through the *_sel wrappers below.
 int nsof_launch_prep_fma(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
-                         int H, int wk, int hk, const nsof_blur_taps& taps, float* out, int src_type = NSOF_SRC_U8);
+                         int H, int wk, int hk, const nsof_blur_taps& taps, float* out, int src_type);
 // Levels 1..3 of a pyr_scale 0.5 pyramid in one launch; NSOF_EUNSUPPORTED (nothing launched) when the frames do not qualify.
 int nsof_launch_prep_decim3(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
-                            int H, const nsof_blur_taps* taps, float* const* out, int src_type = NSOF_SRC_U8);
+                            int H, const nsof_blur_taps* taps, float* const* out, int src_type);
 int nsof_launch_prep_decim3_fma(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride,
-                                int W, int H, const nsof_blur_taps* taps, float* const* out, int src_type = NSOF_SRC_U8);
+                                int W, int H, const nsof_blur_taps* taps, float* const* out, int src_type);
 int nsof_launch_prep_het_fma(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items,
-                             bool level0, const nsof_blur_taps& taps, float* I, int src_type = NSOF_SRC_U8);
+                             bool level0, const nsof_blur_taps& taps, float* I, int src_type);
 int nsof_launch_flow_upsample_fma(nsof_ctx* ctx, int n_pairs, const float* src, int sw, int sh, float* dst, int dw,
                                   int dh, float mul);
 int nsof_launch_flow_upsample_het_fma(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
@@ -246,7 +256,7 @@ int nsof_launch_polyexp(nsof_ctx* ctx, int n_img, const float* img, int W, int H
 // or 16-bit frames (src_type: not NSOF_SRC_F32).
 int nsof_launch_polyexp_frames(nsof_ctx* ctx, int n_img, const void* src0, const void* src1, int nsplit, ptrdiff_t row_stride,
                            ptrdiff_t img_stride, int W, int H, const nsof_poly_taps& taps, float k0, float k1, float* R,
-                           int src_type = NSOF_SRC_U8);
+                           int src_type);
 int nsof_launch_blur_solve(nsof_ctx* ctx, int n_pairs, const float* M, int W, int H, int winsize, float* flow);
 // The same in the reference library's exact summation order; VT: n_pairs * 5 * W * H doubles of scratch.
 int nsof_launch_blur_solve_exact(nsof_ctx* ctx, int n_pairs, const float* M, int W, int H, int winsize, double* VT,

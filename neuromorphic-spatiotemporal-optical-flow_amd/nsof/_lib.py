@@ -34,8 +34,35 @@ class PairDesc(C.Structure):
                 ("flow", _vp), ("flow_stride", _pd)]
 
 
+_ll = C.POINTER(C.c_longlong)
+_fb = [_d, _i, _i, _i, _i, _d, _i]   # pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags
+# The typed entry of each Farneback route: context, nsof_pixel_type, then the route's arguments.
+_TYPED = {
+    "nsof_farneback_px": [_vp, _i, _vp, _pd, _vp, _pd, _i, _i, _vp, _pd] + _fb,
+    "nsof_farneback_px_batch_dev": [_vp, _i, _i, _vp, _vp, _pd, _pd, _i, _i, _vp] + _fb,
+    "nsof_farneback_px_sequence_dev": [_vp, _i, _i, _vp, _pd, _pd, _i, _i, _vp] + _fb,
+    "nsof_farneback_px_batch": [_vp, _i, _i, C.POINTER(PairDesc)] + _fb,
+    "nsof_farneback_px_batch_desc_dev": [_vp, _i, _i, C.POINTER(PairDesc)] + _fb,
+    "nsof_farneback_px_roi_sequence_dev": [_vp, _i, _i, _vp, _pd, _pd, _i, _i, _vp, _vp, _i, _vp] + _fb + [_i, _ll, _ll],
+    "nsof_stage_pyr_level_px": [_vp, _i, _i, _vp, _pd, _pd, _i, _i, _d, _i, _vp],
+}
+
+
+def _typed_signatures():
+    """The typed entries and their 8-bit / float32 exports, which take the same arguments without the pixel type
+    (nsof_farneback_px_batch -> nsof_farneback_u8_batch, nsof_farneback_f32_batch; nsof_stage_pyr_level_px ->
+    nsof_stage_pyr_level, nsof_stage_pyr_level_f32)."""
+    out = {}
+    for name, args in _TYPED.items():
+        out[name] = (_i, args)
+        for infix in ("" if name.startswith("nsof_stage") else "_u8", "_f32"):
+            out[name.replace("_px", infix, 1)] = (_i, args[:1] + args[2:])
+    return out
+
+
 # name -> (restype, argtypes); every symbol include/nsof.h declares
 SIGNATURES = {
+    **_typed_signatures(),
     "nsof_create": (_i, [_i, C.POINTER(_vp)]),
     "nsof_destroy": (None, [_vp]),
     "nsof_last_error": (C.c_char_p, [_vp]),
@@ -44,34 +71,10 @@ SIGNATURES = {
     "nsof_synchronize": (_i, [_vp]),
     "nsof_set_option": (_i, [_vp, _i, _i]),
     "nsof_get_option": (_i, [_vp, _i, C.POINTER(_i)]),
-    "nsof_farneback_u8": (_i, [_vp, _vp, _pd, _vp, _pd, _i, _i, _vp, _pd, _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_u8_batch_dev": (_i, [_vp, _i, _vp, _vp, _pd, _pd, _i, _i, _vp, _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_u8_sequence_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_f32": (_i, [_vp, _vp, _pd, _vp, _pd, _i, _i, _vp, _pd, _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_f32_batch_dev": (_i, [_vp, _i, _vp, _vp, _pd, _pd, _i, _i, _vp, _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_f32_sequence_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_u8_batch": (_i, [_vp, _i, C.POINTER(PairDesc), _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_u8_batch_desc_dev": (_i, [_vp, _i, C.POINTER(PairDesc), _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_u8_roi_sequence_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _vp, _i, _vp, _d, _i, _i, _i, _i, _d, _i, _i,
-                                                C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
-    "nsof_farneback_f32_batch": (_i, [_vp, _i, C.POINTER(PairDesc), _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_f32_batch_desc_dev": (_i, [_vp, _i, C.POINTER(PairDesc), _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_f32_roi_sequence_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _vp, _i, _vp, _d, _i, _i, _i, _i, _d, _i, _i,
-                                                 C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
-    "nsof_farneback_px": (_i, [_vp, _i, _vp, _pd, _vp, _pd, _i, _i, _vp, _pd, _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_px_batch_dev": (_i, [_vp, _i, _i, _vp, _vp, _pd, _pd, _i, _i, _vp, _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_px_sequence_dev": (_i, [_vp, _i, _i, _vp, _pd, _pd, _i, _i, _vp, _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_px_batch": (_i, [_vp, _i, _i, C.POINTER(PairDesc), _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_px_batch_desc_dev": (_i, [_vp, _i, _i, C.POINTER(PairDesc), _d, _i, _i, _i, _i, _d, _i]),
-    "nsof_farneback_px_roi_sequence_dev": (_i, [_vp, _i, _i, _vp, _pd, _pd, _i, _i, _vp, _vp, _i, _vp, _d, _i, _i, _i, _i, _d, _i,
-                                                _i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "nsof_host_alloc": (_vp, [_sz]),
     "nsof_host_free": (None, [_vp]),
     "nsof_farneback_effective_levels": (_i, [_i, _i, _d, _i]),
     "nsof_farneback_level_size": (_i, [_i, _i, _d, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_d)]),
-    "nsof_stage_pyr_level": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _d, _i, _vp]),
-    "nsof_stage_pyr_level_f32": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _d, _i, _vp]),
-    "nsof_stage_pyr_level_px": (_i, [_vp, _i, _i, _vp, _pd, _pd, _i, _i, _d, _i, _vp]),
     "nsof_stage_polyexp": (_i, [_vp, _i, _vp, _i, _i, _i, _d, _vp]),
     "nsof_stage_recip": (_i, [_vp, C.c_longlong, _vp, _vp, _vp]),
     "nsof_stage_update_matrices": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp]),

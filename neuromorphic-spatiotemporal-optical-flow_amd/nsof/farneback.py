@@ -5,10 +5,10 @@ _yolo twins); always ``(prev_region, next_region, None, **farneback_params)`` wi
 ``pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags`` (:73-81); inputs may be
 strided ROI views ``gray[y0:y1, x0:x1]`` (:186-187).
 
-uint8 frames take the 8-bit entry points, uint16 and int16 frames the typed ones (``nsof_farneback_px*``: 16-bit pixels
-on the device, the 8-bit path's kernels, the float32 path's flow bit for bit).  Frames of the other single-channel
-depths cv2 accepts (int8, int32, float16, float32, float64) are converted with ``astype(np.float32)`` -- cv2's own first
-step, ``convertTo(CV_32F)`` -- and run through the float32 entry points.
+Every native call goes through a typed entry (``nsof_farneback_px*``) with the frames' ``nsof_pixel_type``: uint8,
+uint16, int16 and float32 frames go to the device as they are (16-bit pixels run the 8-bit path's kernels and give the
+float32 path's flow bit for bit).  Frames of the other single-channel depths cv2 accepts (int8, int32, float16, float64)
+are converted with ``astype(np.float32)`` -- cv2's own first step, ``convertTo(CV_32F)`` -- and run as float32 frames.
 """
 import ctypes as C
 from dataclasses import asdict, dataclass
@@ -72,9 +72,15 @@ def _as_gray_f32(a, name):
     return a
 
 
-# numpy / torch dtype name -> nsof_pixel_type of the device frames the typed entries take
-_PIXEL_TYPES = {"uint8": _lib.PIXEL_U8, "float32": _lib.PIXEL_F32, "uint16": _lib.PIXEL_U16, "int16": _lib.PIXEL_S16}
-_PIXEL_BYTES = {"uint8": 1, "float32": 4, "uint16": 2, "int16": 2}
+# numpy / torch dtype name -> nsof_pixel_type of the frames the typed entries take (None: raw addresses, 8-bit frames)
+_PIXEL_TYPES = {"uint8": _lib.PIXEL_U8, "float32": _lib.PIXEL_F32, "uint16": _lib.PIXEL_U16, "int16": _lib.PIXEL_S16,
+                None: _lib.PIXEL_U8}
+# ... and -> the infix of the public device-list functions that take such frames (farneback_pairs<infix>_dev, ...)
+_DEV_INFIX = {"uint8": "", "float32": "_f32", "uint16": "_16", "int16": "_16"}
+
+
+def _pixel_bytes(name):
+    return np.dtype(name or "uint8").itemsize
 
 
 def _as_gray_16(a):
@@ -86,18 +92,9 @@ def _as_gray_16(a):
     return a
 
 
-def _as_gray_u8(a, name):
-    if not isinstance(a, np.ndarray):
-        raise NsofValueError(f"{name} is not a numpy array (got {type(a).__name__})")
-    if a.ndim == 3 and a.shape[2] == 1:
-        a = a[:, :, 0]
-    if a.ndim != 2:
-        raise NsofValueError(f"{name} must be single-channel (shape {a.shape}); cv2 asserts channels() == 1")
-    if a.dtype != np.uint8:
-        raise NsofValueError(f"{name} must be uint8 (got {a.dtype}); the reference only passes 8-bit gray frames")
-    if a.size and a.strides[1] != 1:  # pixel stride must be 1; row stride is free (ROI views)
-        a = np.ascontiguousarray(a)
-    return a
+def _as_gray_u8(a):
+    """A uint8 frame with pixel stride 1; the row stride is free (ROI views)."""
+    return np.ascontiguousarray(a) if a.size and a.strides[1] != 1 else a
 
 
 _DEFAULT_EXACT = None   # install(exact=...) sets it: None = the context's setting (NSOF_EXACT_ROWSUMS), True / False = forced
@@ -109,10 +106,10 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
     """Same signature and result as ``cv2.calcOpticalFlowFarneback``: float32 (H, W, 2), (u, v) interleaved,
     such that ``next(x+u, y+v) ~ prev(x, y)``.  ``flow=None`` allocates; a matching float32 array is reused.
     ``prev`` / ``next``: single-channel frames of one dtype, any of uint8, int8, uint16, int16, int32, float16, float32,
-    float64 (cv2's depths).  uint16 / int16 frames go to the device as they are (``nsof_farneback_px``; the flow of
-    their float32 values, bit for bit); the other depths are converted with ``astype(np.float32)`` (cv2's
-    ``convertTo(CV_32F)``; exact except int32 above 2^24 and float64) and run on the float32 path; non-finite values
-    raise, as do frames of two different dtypes (cv2 would convert each on its own).
+    float64 (cv2's depths).  uint8, uint16, int16 and float32 frames go to the device as they are (``nsof_farneback_px``;
+    16-bit frames give the flow of their float32 values, bit for bit); the other depths are converted with
+    ``astype(np.float32)`` (cv2's ``convertTo(CV_32F)``; exact except int32 above 2^24 and float64) and run as float32
+    frames; non-finite values raise, as do frames of two different dtypes (cv2 would convert each on its own).
     ``exact`` (keyword only): True = box-filter row sums in the library's own order for this call
     (``NSOF_OPT_EXACT_ROWSUMS``, the context's default: bit-identical to the CPU restatement on any input),
     False = the fast mode (each pixel's window summed directly: a few per cent faster, up to ~8e-4 off where 2x2 systems
@@ -135,14 +132,12 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
     h, w = prev.shape
     if h == 0 or w == 0:
         raise NsofValueError("empty input image", _lib.NSOF_ESHAPE)
-    typed = ()   # the typed entry's pixel-type argument
     if prev.dtype == np.uint8:
-        prev, next, entry = _as_gray_u8(prev, "prev"), _as_gray_u8(next, "next"), "nsof_farneback_u8"  # noqa: A001
+        prev, next = _as_gray_u8(prev), _as_gray_u8(next)  # noqa: A001
     elif prev.dtype in (np.uint16, np.int16):
-        prev, next, entry = _as_gray_16(prev), _as_gray_16(next), "nsof_farneback_px"  # noqa: A001
-        typed = (_PIXEL_TYPES[prev.dtype.name],)
+        prev, next = _as_gray_16(prev), _as_gray_16(next)  # noqa: A001
     else:
-        prev, next, entry = _as_gray_f32(prev, "prev"), _as_gray_f32(next, "next"), "nsof_farneback_f32"  # noqa: A001
+        prev, next = _as_gray_f32(prev, "prev"), _as_gray_f32(next, "next")  # noqa: A001
     if (isinstance(flow, np.ndarray) and flow.dtype == np.float32 and flow.shape == (h, w, 2)
             and flow.strides[2] == 4 and flow.strides[1] == 8 and flow.flags.writeable):
         out = flow
@@ -162,9 +157,10 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
             saved_bands = ctx.get_option(_lib.OPT_ROW_BANDS)
             ctx.set_option(_lib.OPT_ROW_BANDS, 1 if low_latency else 0)
         try:
-            rc = getattr(ctx._lib, entry)(ctx.ptr, *typed, prev.ctypes.data, prev.strides[0], next.ctypes.data, next.strides[0],
-                                          w, h, out.ctypes.data, out.strides[0], float(pyr_scale), int(levels),
-                                          int(winsize), int(iterations), int(poly_n), float(poly_sigma), int(flags))
+            rc = ctx._lib.nsof_farneback_px(ctx.ptr, _PIXEL_TYPES[prev.dtype.name], prev.ctypes.data, prev.strides[0],
+                                            next.ctypes.data, next.strides[0], w, h, out.ctypes.data, out.strides[0],
+                                            float(pyr_scale), int(levels), int(winsize), int(iterations), int(poly_n),
+                                            float(poly_sigma), int(flags))
         finally:
             if saved is not None:
                 ctx.set_option(_lib.OPT_EXACT_ROWSUMS, saved)
@@ -190,7 +186,7 @@ def _frames_dtype(frames, dtype):
     if len(names) != 1:
         raise NsofValueError(f"frames of different dtypes {sorted(names)}")
     name = names.pop()
-    if name not in _PIXEL_TYPES:
+    if name not in _DEV_INFIX:
         raise NsofValueError(f"device frames must be uint8, uint16, int16 or float32 (got {name})")
     return name
 
@@ -200,20 +196,15 @@ def farneback_batch(d_prev, d_next, d_flow, n_pairs, height, width, params, *, r
     """Device-resident batch: ``d_prev/d_next`` uint8, uint16, int16 or float32 [n][H][row_stride], ``d_flow`` float32
     [n][H][W][2] (torch tensors or raw device addresses).  Strides are in BYTES (default: dense).  The frames' type is
     the tensors' dtype; raw addresses are uint8 unless ``dtype=`` says otherwise (np.float32, np.uint16, np.int16).
-    16-bit frames run on ``nsof_farneback_px_batch_dev`` (rows 2-byte aligned).  Asynchronous on the context's stream."""
+    Runs on ``nsof_farneback_px_batch_dev`` (rows aligned to the pixel size).  Asynchronous on the context's stream."""
     ctx = ctx or default_context()
     name = _frames_dtype((d_prev, d_next), dtype)
-    row_stride = width * _PIXEL_BYTES[name] if row_stride is None else row_stride
+    row_stride = width * _pixel_bytes(name) if row_stride is None else row_stride
     pair_stride = row_stride * height if pair_stride is None else pair_stride
     p = params
-    args = (dev_ptr(d_prev), dev_ptr(d_next), row_stride, pair_stride, width, height, dev_ptr(d_flow), p.pyr_scale, p.levels,
-            p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags)
-    if name == "float32":
-        rc = ctx._lib.nsof_farneback_f32_batch_dev(ctx.ptr, n_pairs, *args)
-    elif name == "uint8":
-        rc = ctx._lib.nsof_farneback_u8_batch_dev(ctx.ptr, n_pairs, *args)
-    else:
-        rc = ctx._lib.nsof_farneback_px_batch_dev(ctx.ptr, _PIXEL_TYPES[name], n_pairs, *args)
+    rc = ctx._lib.nsof_farneback_px_batch_dev(ctx.ptr, _PIXEL_TYPES[name], n_pairs, dev_ptr(d_prev), dev_ptr(d_next), row_stride,
+                                              pair_stride, width, height, dev_ptr(d_flow), p.pyr_scale, p.levels, p.winsize,
+                                              p.iterations, p.poly_n, p.poly_sigma, p.flags)
     ctx.check(rc, "farneback_batch")
 
 
@@ -225,17 +216,12 @@ def farneback_sequence(d_frames, d_flow, n_frames, height, width, params, *, row
     the frames' type as for ``farneback_batch``."""
     ctx = ctx or default_context()
     name = _frames_dtype((d_frames,), dtype)
-    row_stride = width * _PIXEL_BYTES[name] if row_stride is None else row_stride
+    row_stride = width * _pixel_bytes(name) if row_stride is None else row_stride
     frame_stride = row_stride * height if frame_stride is None else frame_stride
     p = params
-    args = (dev_ptr(d_frames), row_stride, frame_stride, width, height, dev_ptr(d_flow), p.pyr_scale, p.levels, p.winsize,
-            p.iterations, p.poly_n, p.poly_sigma, p.flags)
-    if name == "float32":
-        rc = ctx._lib.nsof_farneback_f32_sequence_dev(ctx.ptr, n_frames, *args)
-    elif name == "uint8":
-        rc = ctx._lib.nsof_farneback_u8_sequence_dev(ctx.ptr, n_frames, *args)
-    else:
-        rc = ctx._lib.nsof_farneback_px_sequence_dev(ctx.ptr, _PIXEL_TYPES[name], n_frames, *args)
+    rc = ctx._lib.nsof_farneback_px_sequence_dev(ctx.ptr, _PIXEL_TYPES[name], n_frames, dev_ptr(d_frames), row_stride,
+                                                 frame_stride, width, height, dev_ptr(d_flow), p.pyr_scale, p.levels,
+                                                 p.winsize, p.iterations, p.poly_n, p.poly_sigma, p.flags)
     ctx.check(rc, "farneback_sequence")
 
 
@@ -266,37 +252,28 @@ def pinned_empty(shape, dtype=np.float32):
     return arr
 
 
-def _desc_array(pairs, flows, host, f32=False, px16=False):
-    """ctypes array of nsof_pair_desc (nsof_pair_desc_f32 with ``f32``, nsof_pair_desc_px of 16-bit device frames with
-    ``px16``: the same layout) for (prev, next) pairs and their flow fields (numpy arrays or, with host=False, objects
-    exposing data_ptr()/shape/stride() like torch CUDA tensors).  Host float32 frames must come from ``_f32_host_frames``."""
+def _desc_array(pairs, flows, host, name):
+    """ctypes array of nsof_pair_desc_px for the (prev, next) pairs of a list whose frames are of dtype ``name`` (a key of
+    ``_PIXEL_TYPES``; None: raw addresses, read as 8-bit frames) and their flow fields: numpy arrays whose layout the entry
+    takes (``_as_gray_u8`` / ``_f32_host_frames``) or, with host=False, objects exposing data_ptr()/shape/stride() like torch
+    CUDA tensors, every one of that dtype."""
     descs = (_lib.PairDesc * len(pairs))()
-    keep = []
-    px = 4 if f32 else (2 if px16 else 1)
+    px = _pixel_bytes(name)
     for i, ((prev, nxt), flow) in enumerate(zip(pairs, flows)):
         d = descs[i]
         if host:
-            if not f32:
-                prev, nxt = _as_gray_u8(prev, "prev"), _as_gray_u8(nxt, "next")
             if prev.shape != nxt.shape:
                 raise NsofValueError(f"pair {i}: prev {prev.shape} and next {nxt.shape} sizes differ", _lib.NSOF_ESHAPE)
-            keep += [prev, nxt]
             h, w = prev.shape
             d.prev, d.prev_stride, d.next, d.next_stride = prev.ctypes.data, prev.strides[0], nxt.ctypes.data, nxt.strides[0]
             d.flow, d.flow_stride = flow.ctypes.data, flow.strides[0]
         else:
             h, w = int(prev.shape[0]), int(prev.shape[1])
-            if px16:
-                if _tensor_dtype(prev) not in ("uint16", "int16") or _tensor_dtype(nxt) not in ("uint16", "int16"):
-                    raise NsofValueError(f"pair {i}: frames must be uint16 or int16 tensors (got {_tensor_dtype(prev)}, "
-                                         f"{_tensor_dtype(nxt)})")
-            elif f32:
-                if _tensor_dtype(prev) != "float32" or _tensor_dtype(nxt) != "float32":
-                    raise NsofValueError(f"pair {i}: frames must be float32 tensors (got {_tensor_dtype(prev)}, "
-                                         f"{_tensor_dtype(nxt)}); 8-bit frames take farneback_pairs_dev")
-            elif _tensor_dtype(prev) not in (None, "uint8") or _tensor_dtype(nxt) not in (None, "uint8"):
-                raise NsofValueError(f"pair {i}: work-list frames must be uint8 tensors (got {_tensor_dtype(prev)}, "
-                                     f"{_tensor_dtype(nxt)}); float32 frames take farneback_pairs_f32_dev")
+            for got in (_tensor_dtype(prev), _tensor_dtype(nxt)):
+                if (got or "uint8") != (name or "uint8"):   # raw addresses are 8-bit frames
+                    takes = f"farneback_pairs{_DEV_INFIX[got]}_dev" if got in _DEV_INFIX else "no work-list function"
+                    raise NsofValueError(f"pair {i}: the frames of this list must be {name or 'uint8'} tensors (got {got}); "
+                                         f"{got} frames take {takes}")
             if tuple(nxt.shape[:2]) != (h, w):
                 raise NsofValueError(f"pair {i}: prev and next sizes differ", _lib.NSOF_ESHAPE)
             if prev.stride(1) != 1 or nxt.stride(1) != 1 or flow.stride(2) != 1 or flow.stride(1) != 2:
@@ -307,19 +284,19 @@ def _desc_array(pairs, flows, host, f32=False, px16=False):
         if h == 0 or w == 0:
             raise NsofValueError(f"pair {i}: empty input image", _lib.NSOF_ESHAPE)
         d.width, d.height = w, h
-    return descs, keep
+    return descs
 
 
-def _host_list_is_u8(pairs):
-    """True when every frame of a host list is uint8; frames must be single-channel of a depth cv2 takes and the two
-    frames of a pair of one dtype (as ``calcOpticalFlowFarneback``)."""
-    u8 = True
+def _host_grays(pairs):
+    """The frames of a host list as single-channel arrays of a depth cv2 takes (not converted), the two frames of a pair
+    of one dtype (as ``calcOpticalFlowFarneback``)."""
+    grays = []
     for i, (prev, nxt) in enumerate(pairs):
         a, b = _as_gray(prev, f"pairs[{i}] prev"), _as_gray(nxt, f"pairs[{i}] next")
         if a.dtype != b.dtype:
             raise NsofValueError(f"pair {i}: prev ({a.dtype}) and next ({b.dtype}) dtypes differ")
-        u8 = u8 and a.dtype == np.uint8
-    return u8
+        grays.append((a, b))
+    return grays
 
 
 _F32_STAGE_CAP = 256 << 20   # bytes of page-locked conversion buffer a context keeps at most
@@ -370,11 +347,11 @@ def _f32_host_frames(pairs, ctx):
 def farneback_pairs(pairs, params, flows=None, *, pinned=False, ctx=None):
     """Flow of MANY independent (prev, next) pairs of ANY shapes with one parameter set -- the gated path's ROI
     calls (optical_flow_seg.py:129-164, :186-203) and full-frame calls (:492-496) of a whole sequence in one go
-    (``nsof_farneback_u8_batch``): the pairs share every kernel launch and upload / compute / download overlap.
+    (``nsof_farneback_px_batch``): the pairs share every kernel launch and upload / compute / download overlap.
 
     ``pairs``: [(prev, next), ...] 2-D numpy arrays (strided ROI views allowed) of any depth ``calcOpticalFlowFarneback``
-    takes, one dtype per pair.  An all-uint8 list runs on the 8-bit entry; any other list is converted frame by frame
-    with ``astype(np.float32)`` (uint8 frames of a mixed list too) and runs on ``nsof_farneback_f32_batch``; non-finite
+    takes, one dtype per pair.  An all-uint8 list runs as 8-bit frames; any other list is converted frame by frame
+    with ``astype(np.float32)`` (uint8 frames of a mixed list too) and runs as float32 frames; non-finite
     values raise before any device work.  ``flows``: optional list of
     float32 (h, w, 2) arrays to write into (views ``canvas[y0:y1, x0:x1]`` of a frame-sized canvas are written in
     place -- the paste of :162/:204); by default fresh arrays are returned, page-locked when ``pinned`` (then the
@@ -397,27 +374,30 @@ def farneback_pairs(pairs, params, flows=None, *, pinned=False, ctx=None):
         raise NsofValueError("flows and pairs differ in length")
     if not pairs:
         return []
-    if _host_list_is_u8(pairs):
-        descs, keep = _desc_array(pairs, flows, host=True)
-        _desc_batch_call(ctx, ctx._lib.nsof_farneback_u8_batch, descs, kw, "farneback_pairs")
-        del keep
+    grays = _host_grays(pairs)
+    if all(a.dtype == np.uint8 for a, _ in grays):
+        frames = [(_as_gray_u8(a), _as_gray_u8(b)) for a, b in grays]
+        _desc_batch_call(ctx, "nsof_farneback_px_batch", _desc_array(frames, flows, True, "uint8"), "uint8", kw,
+                         "farneback_pairs")
         return flows
-    with ctx.lock:
-        descs, keep = _desc_array(_f32_host_frames(pairs, ctx), flows, host=True, f32=True)
-        _desc_batch_call(ctx, ctx._lib.nsof_farneback_f32_batch, descs, kw, "farneback_pairs")
-    del keep
+    with ctx.lock:   # the conversion buffer of the context
+        frames = _f32_host_frames(grays, ctx)
+        _desc_batch_call(ctx, "nsof_farneback_px_batch", _desc_array(frames, flows, True, "float32"), "float32", kw,
+                         "farneback_pairs")
     return flows
 
 
-def _desc_batch_call(ctx, entry, descs, kw, what, *typed):
-    """One native work-list call (``nsof_farneback_{u8,f32}_batch[_desc_dev]``, or a typed ``nsof_farneback_px_batch*``
-    with its pixel type in ``typed``) on a descriptor array."""
-    rc = entry(ctx.ptr, *typed, len(descs), descs, float(kw["pyr_scale"]), int(kw["levels"]), int(kw["winsize"]),
-               int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]), int(kw["flags"]))
+def _desc_batch_call(ctx, entry, descs, name, kw, what):
+    """One native work-list call (``nsof_farneback_px_batch`` or ``nsof_farneback_px_batch_desc_dev``) on a descriptor
+    array of frames of dtype ``name``."""
+    rc = getattr(ctx._lib, entry)(ctx.ptr, _PIXEL_TYPES[name], len(descs), descs, float(kw["pyr_scale"]), int(kw["levels"]),
+                                  int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]),
+                                  int(kw["flags"]))
     ctx.check(rc, what)
 
 
-def _pairs_dev(pairs, flows, params, ctx, f32, px16=False):
+def _pairs_dev(pairs, flows, params, ctx, accepted, what):
+    """A device work list whose frames are all of ONE of the dtype names in ``accepted`` (None: raw addresses)."""
     ctx = ctx or default_context()
     kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
     pairs, flows = list(pairs), list(flows)
@@ -425,116 +405,87 @@ def _pairs_dev(pairs, flows, params, ctx, f32, px16=False):
         raise NsofValueError("flows and pairs differ in length")
     if not pairs:
         return
-    if px16:   # one 16-bit dtype per list: the typed entry's pixel type
-        name = _list_dtype_16((_tensor_dtype(f) for pair in pairs for f in pair), "farneback_pairs_16_dev")
-        descs, _ = _desc_array(pairs, flows, host=False, px16=True)
-        _desc_batch_call(ctx, ctx._lib.nsof_farneback_px_batch_desc_dev, descs, kw, "farneback_pairs_16_dev",
-                         _PIXEL_TYPES[name])
-        return
-    descs, _ = _desc_array(pairs, flows, host=False, f32=f32)
-    if f32:
-        _desc_batch_call(ctx, ctx._lib.nsof_farneback_f32_batch_desc_dev, descs, kw, "farneback_pairs_f32_dev")
-    else:
-        _desc_batch_call(ctx, ctx._lib.nsof_farneback_u8_batch_desc_dev, descs, kw, "farneback_pairs_dev")
+    name = _tensor_dtype(pairs[0][0])   # the list's dtype; one the function does not take is refused as pair 0's
+    name = name if name in accepted else accepted[0]
+    _desc_batch_call(ctx, "nsof_farneback_px_batch_desc_dev", _desc_array(pairs, flows, False, name), name, kw, what)
 
 
 def farneback_pairs_dev(pairs, flows, params, *, ctx=None):
-    """Device-resident twin (``nsof_farneback_u8_batch_desc_dev``): ``pairs`` = [(prev, next), ...] of uint8 CUDA
+    """Device-resident twin (``nsof_farneback_px_batch_desc_dev``): ``pairs`` = [(prev, next), ...] of uint8 CUDA
     tensors (any row stride: crops ``frame[y0:y1, x0:x1]`` of frames in HBM), ``flows`` = float32 (h, w, 2) CUDA
-    tensors or crops of a frame-sized canvas, written in place.  Asynchronous on the context's stream."""
-    _pairs_dev(pairs, flows, params, ctx, f32=False)
+    tensors or crops of a frame-sized canvas, written in place.  Other dtypes raise ``NsofValueError``.  Asynchronous on
+    the context's stream."""
+    _pairs_dev(pairs, flows, params, ctx, ("uint8", None), "farneback_pairs_dev")
 
 
 def farneback_pairs_f32_dev(pairs, flows, params, *, ctx=None):
-    """``farneback_pairs_dev`` for float32 frames (``nsof_farneback_f32_batch_desc_dev``): ``pairs`` = [(prev, next), ...]
+    """``farneback_pairs_dev`` for float32 frames: ``pairs`` = [(prev, next), ...]
     of float32 CUDA tensors (crops of frames in HBM: rows 4-byte aligned, any row stride), ``flows`` as there.  Each
     result equals ``calcOpticalFlowFarneback`` of that pair's frames bit for bit.  Other dtypes raise ``NsofValueError``.
     Asynchronous on the context's stream."""
-    _pairs_dev(pairs, flows, params, ctx, f32=True)
-
-
-def _list_dtype_16(names, what):
-    """The one 16-bit dtype of a device list's frames (uint16 or int16); anything else raises."""
-    names = set(names)
-    if len(names) != 1 or not names <= {"uint16", "int16"}:
-        raise NsofValueError(f"{what}: frames must be all uint16 or all int16 tensors (got {sorted(map(str, names))})")
-    return names.pop()
+    _pairs_dev(pairs, flows, params, ctx, ("float32",), "farneback_pairs_f32_dev")
 
 
 def farneback_pairs_16_dev(pairs, flows, params, *, ctx=None):
-    """``farneback_pairs_dev`` for uint16 or int16 frames (``nsof_farneback_px_batch_desc_dev``): ``pairs`` = [(prev,
+    """``farneback_pairs_dev`` for uint16 or int16 frames: ``pairs`` = [(prev,
     next), ...] of CUDA tensors of ONE of those dtypes (crops ``frame[y0:y1, x0:x1]`` of frames in HBM: any row stride,
     pixel stride 1), ``flows`` as there.  Each result equals ``calcOpticalFlowFarneback`` of that pair's frames as float32,
     bit for bit.  Mixed or other dtypes raise ``NsofValueError``.  Asynchronous on the context's stream."""
-    _pairs_dev(pairs, flows, params, ctx, f32=False, px16=True)
+    _pairs_dev(pairs, flows, params, ctx, ("uint16", "int16"), "farneback_pairs_16_dev")
 
 
-def farneback_roi_sequence_16_dev(frames, counts, rects, flows, params, *, gate_frame=0, ctx=None):
-    """``farneback_roi_sequence_dev`` for uint16 or int16 frames (``nsof_farneback_px_roi_sequence_dev``): ``frames`` a
-    uint16 or int16 CUDA tensor [n][H][W] (row stride free), everything else as there.  Each crop's flow equals
-    ``calcOpticalFlowFarneback`` of that crop as float32, bit for bit.  Returns (crops, their total area)."""
+def _roi_sequence_dev(frames, counts, rects, flows, params, gate_frame, ctx, accepted, what):
+    """The gated sequence (``nsof_farneback_px_roi_sequence_dev``) on frames of one of the dtype names in ``accepted``."""
     ctx = ctx or default_context()
     kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
-    name = _list_dtype_16((_tensor_dtype(frames),), "farneback_roi_sequence_16_dev")
-    n, h, w = _roi_sequence_args(frames, counts, rects, flows)
-    calls, pixels = C.c_longlong(), C.c_longlong()
-    rc = ctx._lib.nsof_farneback_px_roi_sequence_dev(
-        ctx.ptr, _PIXEL_TYPES[name], n, dev_ptr(frames), int(frames.stride(1)) * 2, int(frames.stride(0)) * 2, w, h,
-        dev_ptr(counts), dev_ptr(rects), int(rects.shape[1]), dev_ptr(flows), float(kw["pyr_scale"]), int(kw["levels"]),
-        int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]), int(kw["flags"]),
-        int(gate_frame), C.byref(calls), C.byref(pixels))
-    ctx.check(rc, "farneback_roi_sequence_16_dev")
-    return calls.value, pixels.value
-
-
-def _roi_sequence_args(frames, counts, rects, flows):
+    name = _tensor_dtype(frames)
+    if name not in accepted:
+        takes = f"farneback_roi_sequence{_DEV_INFIX[name]}_dev" if name in _DEV_INFIX else "no ROI-sequence function"
+        raise NsofValueError(f"{what}: frames must be a {' or '.join(filter(None, accepted))} tensor (got {name}); "
+                             f"{name} frames take {takes}")
     n, h, w = (int(v) for v in frames.shape)
     if tuple(flows.shape) != (n - 1, h, w, 2) or not flows.is_contiguous() or frames.stride(2) != 1:
         raise NsofValueError("flows must be a contiguous (n-1, H, W, 2) tensor and the frames' pixel stride 1")
     if tuple(rects.shape[:1]) != (n,) or rects.shape[2] != 4 or not rects.is_contiguous() or not counts.is_contiguous():
         raise NsofValueError("rects must be a contiguous (n, max_rects, 4) int32 tensor")
-    return n, h, w
-
-
-def _roi_sequence_dev(frames, counts, rects, flows, params, gate_frame, ctx, f32):
-    ctx = ctx or default_context()
-    kw = params.as_kwargs() if hasattr(params, "as_kwargs") else dict(params)
-    if f32 and _tensor_dtype(frames) != "float32":
-        raise NsofValueError(f"frames must be a float32 tensor (got {_tensor_dtype(frames)}); 8-bit frames take "
-                             "farneback_roi_sequence_dev")
-    if not f32 and _tensor_dtype(frames) not in (None, "uint8"):
-        raise NsofValueError(f"frames must be a uint8 tensor (got {_tensor_dtype(frames)}); float32 frames take "
-                             "farneback_roi_sequence_f32_dev")
-    n, h, w = _roi_sequence_args(frames, counts, rects, flows)
-    px = 4 if f32 else 1   # strides in bytes
-    entry, what = ((ctx._lib.nsof_farneback_f32_roi_sequence_dev, "farneback_roi_sequence_f32_dev") if f32 else
-                   (ctx._lib.nsof_farneback_u8_roi_sequence_dev, "farneback_roi_sequence_dev"))
+    px = _pixel_bytes(name)   # strides in bytes
     calls, pixels = C.c_longlong(), C.c_longlong()
-    rc = entry(ctx.ptr, n, dev_ptr(frames), int(frames.stride(1)) * px, int(frames.stride(0)) * px, w, h, dev_ptr(counts),
-               dev_ptr(rects), int(rects.shape[1]), dev_ptr(flows), float(kw["pyr_scale"]), int(kw["levels"]),
-               int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]), int(kw["flags"]),
-               int(gate_frame), C.byref(calls), C.byref(pixels))
+    rc = ctx._lib.nsof_farneback_px_roi_sequence_dev(
+        ctx.ptr, _PIXEL_TYPES[name], n, dev_ptr(frames), int(frames.stride(1)) * px, int(frames.stride(0)) * px, w, h,
+        dev_ptr(counts), dev_ptr(rects), int(rects.shape[1]), dev_ptr(flows), float(kw["pyr_scale"]), int(kw["levels"]),
+        int(kw["winsize"]), int(kw["iterations"]), int(kw["poly_n"]), float(kw["poly_sigma"]), int(kw["flags"]),
+        int(gate_frame), C.byref(calls), C.byref(pixels))
     ctx.check(rc, what)
     return calls.value, pixels.value
 
 
 def farneback_roi_sequence_dev(frames, counts, rects, flows, params, *, gate_frame=0, ctx=None):
-    """The gated path of a frame sequence on the device (``nsof_farneback_u8_roi_sequence_dev``; opticalFlow3D's crop ->
+    """The gated path of a frame sequence on the device (``nsof_farneback_px_roi_sequence_dev``; opticalFlow3D's crop ->
     flow -> paste loop, optical_flow_seg.py:129-164, 186-204): ``frames`` uint8 CUDA tensor [n][H][W] (row stride free),
     ``counts`` / ``rects`` the device ROI table of ``gating.roi_from_surface_dev``, ``flows`` float32 CUDA tensor
     [n-1][H][W][2] (contiguous; zero-filled by the call).  Pair k is gated by the rectangles of frame ``k + gate_frame``:
     0 (default) = the map of the pair's first frame, as the shipped scripts gate (``memimg2 := memimg1``,
     optical_flow_seg.py:435; ``GatingConfig.bug_compatible``), 1 = the map of its second frame (what ``opticalFlow3D``
     is written to use).  All crops of all pairs form one work list; overlapping crops of a pair are pasted in label order.
-    -> (n_crops, crop_pixels)."""
-    return _roi_sequence_dev(frames, counts, rects, flows, params, gate_frame, ctx, f32=False)
+    Other dtypes raise ``NsofValueError``.  -> (n_crops, crop_pixels)."""
+    return _roi_sequence_dev(frames, counts, rects, flows, params, gate_frame, ctx, ("uint8", None),
+                             "farneback_roi_sequence_dev")
 
 
 def farneback_roi_sequence_f32_dev(frames, counts, rects, flows, params, *, gate_frame=0, ctx=None):
-    """``farneback_roi_sequence_dev`` for float32 frames (``nsof_farneback_f32_roi_sequence_dev``): ``frames`` float32 CUDA
+    """``farneback_roi_sequence_dev`` for float32 frames: ``frames`` float32 CUDA
     tensor [n][H][W] (row stride free); every crop's flow equals ``calcOpticalFlowFarneback`` of the float crops, pasted as
     there.  Other dtypes raise ``NsofValueError``.  -> (n_crops, crop_pixels)."""
-    return _roi_sequence_dev(frames, counts, rects, flows, params, gate_frame, ctx, f32=True)
+    return _roi_sequence_dev(frames, counts, rects, flows, params, gate_frame, ctx, ("float32",),
+                             "farneback_roi_sequence_f32_dev")
+
+
+def farneback_roi_sequence_16_dev(frames, counts, rects, flows, params, *, gate_frame=0, ctx=None):
+    """``farneback_roi_sequence_dev`` for uint16 or int16 frames: ``frames`` a
+    uint16 or int16 CUDA tensor [n][H][W] (row stride free), everything else as there.  Each crop's flow equals
+    ``calcOpticalFlowFarneback`` of that crop as float32, bit for bit.  Returns (crops, their total area)."""
+    return _roi_sequence_dev(frames, counts, rects, flows, params, gate_frame, ctx, ("uint16", "int16"),
+                             "farneback_roi_sequence_16_dev")
 
 
 def effective_levels(width, height, pyr_scale, levels):

@@ -1,6 +1,7 @@
 """CPU: the typed entries of 16-bit frames (nsof_farneback_px*) are declared, exported and bound; the public pixel-type
 enum equals the library's internal source types; and every 16-bit instance of the pyramid kernels and of the fused
 level-0 expansion runs without scratch (no VGPR spills) -- read from the gfx950 code object inside libnsof.so."""
+import ctypes as C
 import os
 import re
 import subprocess
@@ -35,6 +36,15 @@ def test_px_entries_are_declared_exported_and_bound(nsof_lib):
         r, args = _lib.SIGNATURES[name]
         tr, targs = _lib.SIGNATURES[twin]
         assert r == tr and args[:1] + args[2:] == targs, name
+    # every entry of the seven routes -- the typed one and its 8-bit and float32 exports -- is exported and refuses a NULL
+    # context with NSOF_EINVAL, whatever else it is given (zeros): no forwarder crashes or is missing without a device
+    entries = sorted(n for n in _lib.SIGNATURES if n.startswith("nsof_farneback_") or n.startswith("nsof_stage_pyr_level"))
+    entries = [n for n in entries if n not in ("nsof_farneback_effective_levels", "nsof_farneback_level_size")]
+    assert len([n for n in entries if n.startswith("nsof_farneback_")]) == 18 and len(entries) == 21, entries
+    for name in entries:
+        zeros = [None if t in (C.c_void_p, C.POINTER(_lib.PairDesc), C.POINTER(C.c_longlong)) else 0
+                 for t in _lib.SIGNATURES[name][1]]
+        assert getattr(lib, name)(*zeros) == _lib.NSOF_EINVAL, name
 
 
 def test_pixel_type_enum_equals_src_type():

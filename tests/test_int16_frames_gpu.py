@@ -322,6 +322,61 @@ def test_typed_entries_equal_twins(nsof_lib, ctx, torch_dev):
         ctx.synchronize()
         assert _same(o_px.cpu().numpy(), o_tw.cpu().numpy()) and _same(o_px[0].cpu().numpy(), f_tw), pt
 
+        # Every other forwarder against its typed entry, on the same arguments: the same bits.  (The Python layer calls the
+        # typed entries only, so this is what runs the nsof_farneback_u8* / nsof_farneback_f32* exports; one that named the
+        # wrong pixel type would read the frames at another pixel size, or be refused for their layout.)
+        def both(forwarder, typed, args, shape, written=(...,)):
+            outs = []
+            for entry, lead in ((forwarder, ()), (typed, (pt,))):
+                o = torch.full(shape, float(len(outs)), dtype=torch.float32, device=torch_dev)
+                ctx.check(getattr(ctx._lib, entry)(ctx.ptr, *lead, *args(o)), entry)
+                ctx.synchronize()
+                outs.append(o.cpu().numpy())
+            assert all(_same(outs[0][ix], outs[1][ix]) for ix in written), (forwarder, pt)
+            return outs[1]
+
+        seq = _up(np.stack([q, r]), torch_dev)
+        got = both(twin + "_sequence_dev", "nsof_farneback_px_sequence_dev",
+                   lambda o: (2, seq.data_ptr(), 200 * px, 72 * 200 * px, 200, 72, o.data_ptr(), *_args(p)), (1, 72, 200, 2))
+        assert _same(got[0], f_tw), pt
+
+        def dev_list(o):   # the whole pair and a crop of it (rows 5..60, columns 8..136), each into its own canvas
+            descs = (_lib.PairDesc * 2)()
+            for i, (y0, y1, x0, x1) in enumerate(((0, 72, 0, 200), (5, 60, 8, 136))):
+                d = descs[i]
+                d.prev, d.next = tq[y0:y1, x0:x1].data_ptr(), tr[y0:y1, x0:x1].data_ptr()
+                d.prev_stride = d.next_stride = 200 * px
+                d.width, d.height, d.flow, d.flow_stride = x1 - x0, y1 - y0, o[i, y0:y1, x0:x1].data_ptr(), 1600
+            return (2, descs, *_args(p))
+        got = both(twin + "_batch_desc_dev", "nsof_farneback_px_batch_desc_dev", dev_list, (2, 72, 200, 2),
+                   written=((0,), (1, slice(5, 60), slice(8, 136))))
+        assert _same(got[0], f_tw), pt
+        assert not (got[1, 5:60, 8:136] == 1.0).all(), "the crop was not written"
+
+        hosts = []
+        for entry, lead in ((twin + "_batch", ()), ("nsof_farneback_px_batch", (pt,))):
+            f = np.full((72, 200, 2), float(len(hosts)), np.float32)
+            descs = (_lib.PairDesc * 1)()
+            d = descs[0]
+            d.prev, d.prev_stride, d.next, d.next_stride = q.ctypes.data, q.strides[0], r.ctypes.data, r.strides[0]
+            d.width, d.height, d.flow, d.flow_stride = 200, 72, f.ctypes.data, 1600
+            ctx.check(getattr(ctx._lib, entry)(ctx.ptr, *lead, 1, descs, *_args(p)), entry)
+            hosts.append(f)
+        assert _same(hosts[0], hosts[1]) and _same(hosts[0], f_tw), pt
+
+        counts = torch.tensor([2, 0], dtype=torch.int32, device=torch_dev)   # two overlapping crops of the one pair
+        rects = torch.tensor([[[8, 4, 136, 60], [100, 20, 196, 70]], [[0, 0, 0, 0], [0, 0, 0, 0]]], dtype=torch.int32,
+                             device=torch_dev)
+        got = both(twin + "_roi_sequence_dev", "nsof_farneback_px_roi_sequence_dev",
+                   lambda o: (2, seq.data_ptr(), 200 * px, 72 * 200 * px, 200, 72, counts.data_ptr(), rects.data_ptr(), 2,
+                              o.data_ptr(), *_args(p), 0, None, None), (1, 72, 200, 2))
+        assert got[0, 4:60, 8:136].any() and not got[0, :4].any(), pt
+
+        for level in (0, 1):
+            wk, hk = nsof_lib.level_size(200, 72, p.pyr_scale, level)[:2]
+            both("nsof_stage_pyr_level" + ("" if pt == _lib.PIXEL_U8 else "_f32"), "nsof_stage_pyr_level_px",
+                 lambda o: (1, tq.data_ptr(), 200 * px, 0, 200, 72, p.pyr_scale, level, o.data_ptr()), (hk, wk))   # noqa: B023
+
 
 # ---- 9. refusals --------------------------------------------------------------------------------------------------
 def test_refusals_before_launch(nsof_lib, ctx, torch_dev):
