@@ -42,18 +42,19 @@ struct QGeom {
 };
 
 template <int MH, int GP, int TS, int RR>
-__device__ __forceinline__ void q_produce(RowIn (&in)[2][2], float2 (&fl)[2][2], float (*mring)[5][QGeom<MH>::COLS],
+__device__ __forceinline__ void q_produce(RowIn (&in)[2][2], float2 (&dd)[2][2], float2 (&fl)[2][2], float (*mring)[5][QGeom<MH>::COLS],
                                           const Planes& R0, const Planes& R1, const FlowSrc& F, int W, int H, int xc,
                                           int col, int t, int yb)
 {
     constexpr int RL = QGeom<MH>::RL;
     const int i = 4 * t + MH + 2 * GP + RR;                  // stream index of this row (row yb + i of the image)
     float Mn[5];
-    matrix_from(in[TS][RR], xc, min(yb + i, H - 1), W, H, Mn);
+    matrix_from(in[TS][RR], dd[TS][RR].x, dd[TS][RR].y, xc, min(yb + i, H - 1), W, H, Mn);
     const int slot = (i + MH + 1) % RL;
 #pragma unroll
     for (int c = 0; c < 5; c++) mring[slot][c][col] = Mn[c];
     issue_row(in[TS][RR], R0, R1, W, H, xc, min(yb + i + 8, H - 1), fl[TS][RR]);              // the same row of step t+2
+    dd[TS][RR] = fl[TS][RR];
     fl[TS][RR] = F.fetch(min(yb + i + 16, H - 1));                                            // its flow for step t+4
 }
 
@@ -62,13 +63,14 @@ __device__ __forceinline__ void q_producer_loop(float (*mring)[5][QGeom<MH>::COL
                                                 const FlowSrc& F, int W, int H, int xc, int col, int nsteps, int yb)
 {
     RowIn in[2][2];
-    float2 fl[2][2];
+    float2 dd[2][2], fl[2][2];   // the flow of the rows in `in`, and of the rows issued next
 #pragma unroll
     for (int ts = 0; ts < 2; ts++)
 #pragma unroll
         for (int rr = 0; rr < 2; rr++) {
             const int r = min(yb + 4 * ts + MH + 2 * GP + rr, H - 1);
-            issue_row(in[ts][rr], R0, R1, W, H, xc, r, F.fetch(r));
+            dd[ts][rr] = F.fetch(r);
+            issue_row(in[ts][rr], R0, R1, W, H, xc, r, dd[ts][rr]);
         }
 #pragma unroll
     for (int ts = 0; ts < 2; ts++)
@@ -79,20 +81,20 @@ __device__ __forceinline__ void q_producer_loop(float (*mring)[5][QGeom<MH>::COL
     //   B_init .. B1(0)        first row of step 1            (consumers: column sums of step 0)
     //   B1(t) .. B2(t)         second row of step t+1         (consumers: row sums + solve of step t)
     //   B2(t) .. B1(t+1)       first row of step t+2          (consumers: column sums of step t+1)
-    q_produce<MH, GP, 0, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, 0, yb);
-    q_produce<MH, GP, 0, 1>(in, fl, mring, R0, R1, F, W, H, xc, col, 0, yb);
+    q_produce<MH, GP, 0, 0>(in, dd, fl, mring, R0, R1, F, W, H, xc, col, 0, yb);
+    q_produce<MH, GP, 0, 1>(in, dd, fl, mring, R0, R1, F, W, H, xc, col, 0, yb);
     __syncthreads();
-    q_produce<MH, GP, 1, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, 1, yb);
+    q_produce<MH, GP, 1, 0>(in, dd, fl, mring, R0, R1, F, W, H, xc, col, 1, yb);
     for (int tb = 0; tb < nsteps; tb += 2) {
         __syncthreads();                                                             // B1(tb)
-        q_produce<MH, GP, 1, 1>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 1, yb);
+        q_produce<MH, GP, 1, 1>(in, dd, fl, mring, R0, R1, F, W, H, xc, col, tb + 1, yb);
         __syncthreads();                                                             // B2(tb)
-        q_produce<MH, GP, 0, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 2, yb);
+        q_produce<MH, GP, 0, 0>(in, dd, fl, mring, R0, R1, F, W, H, xc, col, tb + 2, yb);
         if (tb + 1 >= nsteps) break;
         __syncthreads();                                                             // B1(tb+1)
-        q_produce<MH, GP, 0, 1>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 2, yb);
+        q_produce<MH, GP, 0, 1>(in, dd, fl, mring, R0, R1, F, W, H, xc, col, tb + 2, yb);
         __syncthreads();                                                             // B2(tb+1)
-        q_produce<MH, GP, 1, 0>(in, fl, mring, R0, R1, F, W, H, xc, col, tb + 3, yb);
+        q_produce<MH, GP, 1, 0>(in, dd, fl, mring, R0, R1, F, W, H, xc, col, tb + 3, yb);
     }
 }
 
@@ -110,8 +112,10 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][QGeom<MH>::COL
         // yb-m-1 .. yb+m-1, is summed directly -- the library's column sums are ONE running sum from row 0, so this
         // start differs from it in the sums' last bits (same class as the row-sum order).
         RowIn t[2];
+        float2 d[2];
         const int r0 = max(yb - MH - 1, 0);
-        issue_row(t[0], R0, R1, W, H, xc, r0, F.fetch(r0));
+        d[0] = F.fetch(r0);
+        issue_row(t[0], R0, R1, W, H, xc, r0, d[0]);
 #pragma unroll
         for (int c = 0; c < 5; c++) vs[c] = 0.;
 #pragma unroll
@@ -119,10 +123,11 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][QGeom<MH>::COL
             const int r = clampi(yb - MH - 1 + j, 0, H - 1);
             if (j < 2 * MH) {
                 const int rn = clampi(yb - MH + j, 0, H - 1);
-                issue_row(t[(j + 1) & 1], R0, R1, W, H, xc, rn, F.fetch(rn));
+                d[(j + 1) & 1] = F.fetch(rn);
+                issue_row(t[(j + 1) & 1], R0, R1, W, H, xc, rn, d[(j + 1) & 1]);
             }
             float Mi[5];
-            matrix_from(t[j & 1], xc, r, W, H, Mi);
+            matrix_from(t[j & 1], d[j & 1].x, d[j & 1].y, xc, r, W, H, Mi);
 #pragma unroll
             for (int c = 0; c < 5; c++) {
                 vs[c] += (double)Mi[c];
@@ -134,8 +139,9 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][QGeom<MH>::COL
         // ring slot of stream index i is (i + m + 1) % RL.
         RowIn t;
         float M0[5];
-        issue_row(t, R0, R1, W, H, xc, 0, F.fetch(0));
-        matrix_from(t, xc, 0, W, H, M0);
+        float2 d = F.fetch(0);
+        issue_row(t, R0, R1, W, H, xc, 0, d);
+        matrix_from(t, d.x, d.y, xc, 0, W, H, M0);
 #pragma unroll
         for (int c = 0; c < 5; c++) {
             vs[c] = (double)(M0[c] * (float)(MH + 2));   // float product, as "srow0[x]*(m+2)"
@@ -146,8 +152,9 @@ __device__ __forceinline__ void q_consumer_loop(float (*mring)[5][QGeom<MH>::COL
         for (int i = 1; i < MH; i++) {
             float Mi[5];
             const int r = min(i, H - 1);
-            issue_row(t, R0, R1, W, H, xc, r, F.fetch(r));
-            matrix_from(t, xc, r, W, H, Mi);
+            d = F.fetch(r);
+            issue_row(t, R0, R1, W, H, xc, r, d);
+            matrix_from(t, d.x, d.y, xc, r, W, H, Mi);
 #pragma unroll
             for (int c = 0; c < 5; c++) {
                 vs[c] += (double)Mi[c];

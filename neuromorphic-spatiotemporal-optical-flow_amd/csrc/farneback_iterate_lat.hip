@@ -55,14 +55,12 @@ __global__ __launch_bounds__(256) void k_update_matrices(const float* __restrict
         // no 2x2 block for issue_row's clamped gather, so only R0 is read
         in.z = *reinterpret_cast<const float4*>(R0.q4 + pix * 16);
         in.z4 = *reinterpret_cast<const float*>(R0.c4 + pix * 4);
-        in.dx = d.x;
-        in.dy = d.y;
         in.inside = 0;
     } else {
         issue_row(in, R0, R1, W, H, x, y, d);
     }
     float m5[5];
-    matrix_from(in, x, y, W, H, m5);
+    matrix_from(in, d.x, d.y, x, y, W, H, m5);
 #pragma unroll
     for (int c = 0; c < 5; c++) M[c * plane + pix] = m5[c];
 }

@@ -107,15 +107,19 @@ constexpr unsigned X_SPIN_LIMIT = 1u << 21;   // polls of a carry before giving 
 // ---- producers ------------------------------------------------------------------------------------------------------
 // One row of M: consume the loads issued two steps ago, write the ring, issue the same row of step + 2 (i + 8) and fetch
 // its flow for step + 4 (i + 16).  i = stream index = image row (clamped at the bottom).
+// A row's flow lives for four windows: fetched, the gather address two windows later, dx / dy of the matrix another two
+// later.  `dd` is the flow of the row in `in`, `fl` the one fetched two windows ago (it becomes `dd`; its register takes
+// the new fetch).
 template <int MH>
-__device__ __forceinline__ void x_produce(RowIn& in, float2& fl, const XRing& ring, const Planes& R0,
+__device__ __forceinline__ void x_produce(RowIn& in, float2& dd, float2& fl, const XRing& ring, const Planes& R0,
                                           const Planes& R1, const FlowSrc& F, int W, int H, int xc, int col, int i)
 {
     constexpr int RL = XGeom<MH>::RL;
     float Mn[5];
-    matrix_from(in, xc, min(i, H - 1), W, H, Mn);
+    matrix_from(in, dd.x, dd.y, xc, min(i, H - 1), W, H, Mn);
     ring.put((i + MH + 1) % RL, col, Mn);
     issue_row(in, R0, R1, W, H, xc, min(i + 8, H - 1), fl);
+    dd = fl;
     fl = F.fetch(min(i + 16, H - 1));
 }
 
@@ -142,7 +146,7 @@ __device__ __forceinline__ void x_rows_above(const XRing& ring, const Planes& R0
         for (int k = 0; k < GRP; k++)
             if (g0 + k < MH) {
                 float Mi[5];
-                matrix_from(t[k], xc, min(g0 + k, H - 1), W, H, Mi);
+                matrix_from(t[k], fl[g0 + k].x, fl[g0 + k].y, xc, min(g0 + k, H - 1), W, H, Mi);
                 if (g0 + k == 0) {
 #pragma unroll
                     for (int j = 0; j <= MH + 1; j++) ring.put(j, col, Mi);   // stream indices -m-1 .. 0
@@ -166,13 +170,14 @@ __device__ __forceinline__ void x_producer_loop(const XRing& ring, const Planes&
 {
     if constexpr (GP == 0) x_rows_above<MH>(ring, R0, R1, F, W, H, xc, col);
     RowIn in[2][2];
-    float2 fl[2][2];
+    float2 dd[2][2], fl[2][2];
 #pragma unroll
     for (int ts = 0; ts < 2; ts++)
 #pragma unroll
         for (int rr = 0; rr < 2; rr++) {
             const int r = min(4 * ts + MH + 2 * GP + rr, H - 1);
-            issue_row(in[ts][rr], R0, R1, W, H, xc, r, F.fetch(r));
+            dd[ts][rr] = F.fetch(r);
+            issue_row(in[ts][rr], R0, R1, W, H, xc, r, dd[ts][rr]);
         }
 #pragma unroll
     for (int ts = 0; ts < 2; ts++)
@@ -180,19 +185,27 @@ __device__ __forceinline__ void x_producer_loop(const XRing& ring, const Planes&
         for (int rr = 0; rr < 2; rr++) fl[ts][rr] = F.fetch(min(4 * (ts + 2) + MH + 2 * GP + rr, H - 1));
     auto step = [&](auto tsc, int t) {
         constexpr int TS = decltype(tsc)::value;
-        x_produce<MH>(in[TS][0], fl[TS][0], ring, R0, R1, F, W, H, xc, col, 4 * t + MH + 2 * GP);
-        x_produce<MH>(in[TS][1], fl[TS][1], ring, R0, R1, F, W, H, xc, col, 4 * t + MH + 2 * GP + 1);
+        x_produce<MH>(in[TS][0], dd[TS][0], fl[TS][0], ring, R0, R1, F, W, H, xc, col, 4 * t + MH + 2 * GP);
+        x_produce<MH>(in[TS][1], dd[TS][1], fl[TS][1], ring, R0, R1, F, W, H, xc, col, 4 * t + MH + 2 * GP + 1);
     };
     step(std::integral_constant<int, 0>{}, 0);
     __syncthreads();                                                                 // Ba
     step(std::integral_constant<int, 1>{}, 1);
     __syncthreads();                                                                 // Bb
-    for (int t = 0; t <= nimg; t += 2) {
+    // Two windows per trip and ONE exit, at the bottom; an odd last window follows the loop.  An exit between the two
+    // windows is laid out as a branch back to the loop's latch, and the compiler's wait insertion then merges "the loads of
+    // in[0] were issued last" into the loop header: every trip began by waiting for the loads its previous window had
+    // just issued (vmcnt(18), (9), (0): a full memory latency).
+    int t = 0;
+    for (; t < nimg; t += 2) {
         step(std::integral_constant<int, 0>{}, t + 2);
         __syncthreads();                                                             // B(t)
-        if (t + 1 > nimg) break;
         step(std::integral_constant<int, 1>{}, t + 3);
         __syncthreads();                                                             // B(t+1)
+    }
+    if (t == nimg) {
+        step(std::integral_constant<int, 0>{}, t + 2);
+        __syncthreads();                                                             // B(nimg)
     }
 }
 
@@ -300,18 +313,19 @@ __device__ __forceinline__ void x_remainder_loop(const XRing& ring, double* cb, 
     };
     if (r == 0) x_rows_above<MH>(ring, R0, R1, F, W, H, xc, col);
     RowIn in[2];
-    float2 fl[2];
+    float2 dd[2], fl[2];
 #pragma unroll
     for (int ts = 0; ts < 2; ts++) {
         const int y = min(4 * ts + MH + r, H - 1);
-        issue_row(in[ts], R0, R1, W, H, xc, y, F.fetch(y));
+        dd[ts] = F.fetch(y);
+        issue_row(in[ts], R0, R1, W, H, xc, y, dd[ts]);
     }
 #pragma unroll
     for (int ts = 0; ts < 2; ts++) fl[ts] = F.fetch(min(4 * (ts + 2) + MH + r, H - 1));
-    x_produce<MH>(in[0], fl[0], ring, R0, R1, F, W, H, xc, col, MH + r);
+    x_produce<MH>(in[0], dd[0], fl[0], ring, R0, R1, F, W, H, xc, col, MH + r);
     __syncthreads();                                                                 // Ba
     fetch_issue(0);
-    x_produce<MH>(in[1], fl[1], ring, R0, R1, F, W, H, xc, col, 4 + MH + r);
+    x_produce<MH>(in[1], dd[1], fl[1], ring, R0, R1, F, W, H, xc, col, 4 + MH + r);
     fetch_finish(0);
     __syncthreads();                                                                 // Bb
     // window t: the scanner finishes segment 1 of step t-1 (its row-end sums: published in window t+1) and starts segment
@@ -320,17 +334,18 @@ __device__ __forceinline__ void x_remainder_loop(const XRing& ring, double* cb, 
         constexpr int TS = decltype(tsc)::value;
         if (t >= 2) publish(t - 2);
         if (t + 1 < nimg) fetch_issue(t + 1);
-        x_produce<MH>(in[TS], fl[TS], ring, R0, R1, F, W, H, xc, col, 4 * (t + 2) + MH + r);
+        x_produce<MH>(in[TS], dd[TS], fl[TS], ring, R0, R1, F, W, H, xc, col, 4 * (t + 2) + MH + r);
         // its share of the step's 2x2 solves (rows [CQ, CQ + IOQ)) while the carry fetch is in flight
         x_solve_rows<MH, XGeom<MH>::CQ, XGeom<MH>::IOQ>(sv, ioflag, Fout, fpitch, W, H, x0, nimg, scale, lane, t);
         if (t + 1 < nimg) fetch_finish(t + 1);
         __syncthreads();                                                             // B(t)
     };
-    for (int t = 0; t <= nimg; t += 2) {
+    int t = 0;   // one exit, at the bottom: see x_producer_loop
+    for (; t < nimg; t += 2) {
         window(std::integral_constant<int, 0>{}, t);
-        if (t + 1 > nimg) break;
         window(std::integral_constant<int, 1>{}, t + 1);
     }
+    if (t == nimg) window(std::integral_constant<int, 0>{}, t);
     publish(nimg - 1);
     x_solve_rows<MH, XGeom<MH>::CQ, XGeom<MH>::IOQ>(sv, ioflag, Fout, fpitch, W, H, x0, nimg, scale, lane, nimg + 1);   // window nimg + 1: the right half's last step
 }

@@ -33,28 +33,42 @@ struct RowIn {
     float z4;             // R0 channel 4
     float4 t0, t1, b0, b1;  // R1 channels 0..3 at (y1,x1), (y1,x1+1), (y1+1,x1), (y1+1,x1+1)
     f2u t4, b4;           // R1 channel 4 at (y1, x1..x1+1) and (y1+1, x1..x1+1)
-    float dx, dy, fx, fy;
+    float fx, fy;
     int inside;
 };
 
-// Issue every load one (row, column) needs; `d` is the flow at that pixel (already loaded).
+// Issue every load one (row, column) needs; `d` is the flow at that pixel (already loaded; matrix_from takes it again).
+// W >= 2 and H >= 2 (nsof_iterate_supported): the clamped gather needs a 2x2 block.
+//
+// Sample coordinates without a branch: flx = floorf(fx) (v_floor_f32), the fraction fx - flx, `inside` decided on flx in
+// float, and an integer only for the clamped gather address.  This gives the M of the form it replaces
+// (x1 = floor_f(fx), fraction fx - x1, inside = 0 <= x1 <= W-2), bit for bit:
+//   * |fx| < 2^31: floorf(fx) == (float)floor_f(fx) exactly (below 2^24 both are the same small integer; from 2^24 on fx is
+//     an integer itself and floor_f(fx) a multiple of the float spacing there), so the fraction is the same operation on
+//     the same operands, and flx >= 0 && flx <= W-2 is x1 >= 0 && x1 <= W-2 (W-2 < 2^24 is exact as a float);
+//   * NaN, +-inf, |fx| >= 2^31: floor_f gives INT_MIN / INT_MAX, outside; here NaN fails both comparisons and the others
+//     fail one of them: outside in both forms;
+//   * outside, only the clamped address uses the index, and matrix_from does not read what that load returns (nor the
+//     fraction, which may be NaN here);
+//   * fx = x + d.x with x >= 0 from an integer is never -0.0 (x + d.x == 0 rounds to +0 for x > 0, and for x == 0 a d.x
+//     of -0.0 gives 0 + -0 = +0), so neither floorf nor the subtraction sees a signed zero the integer form did not.
 __device__ __forceinline__ void issue_row(RowIn& in, const Planes& R0, const Planes& R1, int W, int H, int x, int y,
                                           float2 d)
 {
     const unsigned pix = (unsigned)y * (unsigned)W + (unsigned)x;
-    in.dx = d.x;
-    in.dy = d.y;
-    float fx = x + d.x, fy = y + d.y;
-    const int x1 = floor_f(fx), y1 = floor_f(fy);
-    in.fx = fx - x1;
-    in.fy = fy - y1;
-    in.inside = (unsigned)x1 < (unsigned)(W - 1) && (unsigned)y1 < (unsigned)(H - 1);
+    const float fx = x + d.x, fy = y + d.y;
+    const float flx = __builtin_floorf(fx), fly = __builtin_floorf(fy);
+    const float xhi = (float)(W - 2), yhi = (float)(H - 2);
+    in.fx = fx - flx;
+    in.fy = fy - fly;
+    in.inside = flx >= 0.f && flx <= xhi && fly >= 0.f && fly <= yhi;
     in.z = *reinterpret_cast<const float4*>(R0.q4 + pix * 16u);
     in.z4 = *reinterpret_cast<const float*>(R0.c4 + pix * 4u);
     // The R1 gather is issued unconditionally, at a clamped (always valid) address when the sample falls
     // outside: a load under a lane-dependent branch cannot be counted by s_waitcnt vmcnt(N), which would
     // force every wait down to "almost nothing outstanding" and serialise the software pipeline.
-    const int xs = clampi(x1, 0, W - 2), ys = clampi(y1, 0, H - 2);
+    // Clamped in float, one v_med3_f32 each (0 <= hi: see above; a NaN gives the lower bound), then converted.
+    const int xs = (int)__builtin_amdgcn_fmed3f(flx, 0.f, xhi), ys = (int)__builtin_amdgcn_fmed3f(fly, 0.f, yhi);
     const unsigned o = (unsigned)ys * (unsigned)W + (unsigned)xs;
     in.t0 = *reinterpret_cast<const float4*>(R1.q4 + o * 16u);
     in.t1 = *reinterpret_cast<const float4*>(R1.q4 + o * 16u + 16u);
@@ -64,11 +78,10 @@ __device__ __forceinline__ void issue_row(RowIn& in, const Planes& R0, const Pla
     in.b4 = *reinterpret_cast<const f2u*>(R1.c4 + (o + (unsigned)W) * 4u);
 }
 
-// FarnebackUpdateMatrices for one pixel, from loaded inputs.
-__device__ __forceinline__ void matrix_from(const RowIn& in, int x, int y, int W, int H, float (&M)[5])
+// FarnebackUpdateMatrices for one pixel, from loaded inputs and the flow (dx, dy) issue_row was given for it.
+__device__ __forceinline__ void matrix_from(const RowIn& in, float dx, float dy, int x, int y, int W, int H, float (&M)[5])
 {
     float r2, r3, r4, r5, r6;
-    const float dx = in.dx, dy = in.dy;
     if (in.inside) {
         const float fx = in.fx, fy = in.fy;
         const float a00 = (1.f - fx) * (1.f - fy), a01 = fx * (1.f - fy), a10 = (1.f - fx) * fy, a11 = fx * fy;
