@@ -11,8 +11,8 @@
 //  * When silent_v lies in the device's dead zone [voff, von] (the default, 0 V) an inactive
 //    pixel is a bit-exact no-op (dw/dt = 0, clip is the identity on [0,1]); then only the
 //    pixels touched by events are visited (compacted list built by the scatter kernel).
-//  * Scheme 2's refractory rule couples consecutive slices through next_ok, so its scatter
-//    runs one (tiny) launch per slice in stream order; the state update is still fused.
+//  * Scheme 2's refractory rule couples consecutive slices through next_ok, but per pixel only:
+//    one scatter per group as in scheme 1, the eligibility walk inside the fused update (RefrTab).
 //  * pow/exp go through double precision so that the float32 result is the correctly
 //    rounded one: equal to it on every state in [0, 1] outside the ~3e-7 of inputs that lie
 //    within 2^-43 of a rounding midpoint, and on those too as measured (tests/test_accum_cr_gpu.py;
@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "nsof_internal.h"
@@ -183,14 +184,28 @@ struct SurfOut {
     int mode;
 };
 
-// Marks (pixel, slice bit); a pixel's first touch in this group enters the compact list once.  The list's counter is ONE
-// word: appended to per lane it serialises every first touch of a group at the L2 atomic unit (~10 ns each: 300 us for the
-// 33 k events of a 32-slice group at 1 M events/s, found with rocprofv3 in round 3), so the appends of a wave are
-// aggregated -- one atomicAdd of the wave's count, ranks from the ballot.  Call with the whole wave (inactive lanes pass
-// active = false); list == nullptr (dense update: no list is read) skips the list entirely.
-__device__ __forceinline__ void mark(unsigned* mask, unsigned* list, unsigned* count, unsigned pix, unsigned bit, bool active)
+// Largest s in [0, n_sl) with bounds[s] <= e: the slice of event e.  bounds = event indices of the slice boundaries
+// (n_sl + 1 entries).
+__device__ __forceinline__ int slice_of(const long long* bounds, int n_sl, long long e)
 {
-    const unsigned old = active ? atomicOr(&mask[pix], bit) : 1u;
+    int lo = 0, hi = n_sl;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (bounds[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Marks (pixel, slice bit) in a mask of 32- or 64-bit words; a pixel's first touch in this group enters the compact list
+// once, so no two threads of the list update ever hold the same pixel.  The list's counter is ONE word: appended to per lane
+// it serialises every first touch of a group at the L2 atomic unit (~10 ns each: 300 us for the 33 k events of a 32-slice
+// group at 1 M events/s, found with rocprofv3), so the appends of a wave are aggregated -- one atomicAdd of the wave's
+// count, ranks from the ballot.  Call with the whole wave (inactive lanes pass active = false); list == nullptr
+// (every-pixel update: no list is read) skips the list entirely.
+template <class MaskT>
+__device__ __forceinline__ void mark(MaskT* mask, unsigned* list, unsigned* count, unsigned pix, MaskT bit, bool active)
+{
+    const MaskT old = active ? atomicOr(&mask[pix], bit) : (MaskT)1;
     if (!list) return;
     const bool first = active && old == 0;
     const unsigned long long b = __ballot(first);
@@ -202,71 +217,141 @@ __device__ __forceinline__ void mark(unsigned* mask, unsigned* list, unsigned* c
     if (first) list[base + (unsigned)__popcll(b & ((1ull << lane) - 1ull))] = pix;
 }
 
-// Scheme 1 (:208-217): every event of the group marks (pixel, its slice).  bounds = event
-// indices of the group's slice boundaries (n_sl+1 entries), relative to ev0.
-__global__ __launch_bounds__(256) void k_scatter_v1(const short* __restrict__ x, const short* __restrict__ y,
-                                                     long long ev0, long long n_ev, const long long* __restrict__ bounds,
-                                                     int n_sl, int W, unsigned* mask, unsigned* list, unsigned* count,
-                                                     unsigned* mask_hi)
+// One scatter per group of slices, both schemes: every event marks (pixel, its slice) in its array's mask.
+//   split == 0  every event -> array 0 (scheme 1 :208-217, scheme 2 magnitude; p is not read)
+//   split == 1  p == 1 -> array 0, p == 0 -> array 1 (:238, :250; other polarity values drive nothing)
+// Slices 32..63 of a group (scheme 1's every-pixel update only: n_sl <= 32 otherwise) go to the second mask word mask_hi.
+__global__ __launch_bounds__(256) void k_scatter(const short* __restrict__ x, const short* __restrict__ y,
+                                                  const signed char* __restrict__ p, long long ev0, long long n_ev,
+                                                  const long long* __restrict__ bounds, int n_sl, int W, int split,
+                                                  unsigned* mask0, unsigned* list0, unsigned* count0, unsigned* mask1,
+                                                  unsigned* list1, unsigned* count1, unsigned* mask_hi)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool live = i < n_ev;
     const long long e = ev0 + (live ? i : 0);
-    int lo = 0, hi = n_sl;  // largest s with bounds[s] <= e
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (bounds[mid] <= e) lo = mid; else hi = mid;
+    int arr = 0;
+    if (split) {
+        const int pv = (int)p[e];
+        arr = pv == 1 ? 0 : (pv == 0 ? 1 : -1);
     }
-    // slices 32..63 of a group (dense update only: n_sl <= 32 otherwise) go to the second mask word
-    mark(lo < 32 ? mask : mask_hi, list, count, (unsigned)y[e] * (unsigned)W + (unsigned)x[e], 1u << (lo & 31), live);
+    const int s = slice_of(bounds, n_sl, e);
+    const unsigned pix = (unsigned)y[e] * (unsigned)W + (unsigned)x[e], bit = 1u << (s & 31);
+    mark(s < 32 ? mask0 : mask_hi, list0, count0, pix, bit, live && arr == 0);
+    if (split) mark(mask1, list1, count1, pix, bit, live && arr == 1);
 }
 
-// Fused state update over the touched pixels only (silent_v inside the dead zone).
-__global__ __launch_bounds__(256) void k_update_sparse(float* __restrict__ w, unsigned* __restrict__ mask,
-                                                        const unsigned* __restrict__ list,
-                                                        const unsigned* __restrict__ count, int n_sl, float v_act,
-                                                        unsigned* zero_next)
+// Scheme 2's refractory rule (event_mem_sim.py:237-269) looks like a chain over slices -- slice s+1 tests the next_ok that
+// slice s wrote -- but the chain is PER PIXEL: a pixel's next_ok depends on that pixel's own earlier events only, and within a
+// slice every event of a pixel sees the same next_ok (NumPy reads next_ok[ys, xs] before it writes).  So a group of up to 32
+// slices needs ONE scatter, "which slices have an event (of the array's polarity) at this pixel" (bit s of E), and the
+// eligibility walk moves into the fused state update: per touched pixel, over the set bits of E in slice order,
+//     if next_ok <= t_first[s]:  the pixel is driven in slice s;  next_ok = t_last[s] + REFRACTORY
+// with the per-slice constants in a 64-entry table.  No atomics on next_ok, two launches per group and array as in scheme 1.
+struct RefrTab {
+    long long t_first[32], t_next[32];
+};
+struct NoTab {};
+template <bool REFR>
+using TabArg = std::conditional_t<REFR, RefrTab, NoTab>;   // scheme 1 passes no table
+
+// slices with an event -> slices in which the pixel is driven; ok = the pixel's next_ok (updated)
+__device__ __forceinline__ unsigned refractory_walk(unsigned e, long long& ok, const long long* tf, const long long* tn)
 {
+    unsigned m = 0;
+    for (; e; e &= e - 1) {
+        const int s = __ffs((int)e) - 1;
+        if (ok <= tf[s]) {
+            m |= 1u << s;
+            ok = tn[s];
+        }
+    }
+    return m;
+}
+
+// The active drive once per set bit of m: the driven slices of a pixel in slice order (the silent ones are no-ops).
+template <class MaskT>
+__device__ __forceinline__ float replay_driven(float ww, MaskT m, const Drive& da)
+{
+    for (; m; m &= m - 1) ww = update_drive(ww, da);
+    return ww;
+}
+
+// Fused state update over the touched pixels only (silent_v inside the dead zone): walks the compact list, claims each
+// pixel's mask, replays its driven slices and stores w.
+//   REFR   scheme 2: the mask holds event bits; refractory_walk turns them into driven bits first
+//   MaskT  the mask word: 32 bits (groups of up to 32 slices), 64 bits (copy + patch: intervals of up to 64 slices)
+//   FRAME  the pixel's byte of the frame `so` is overwritten as well (copy + patch)
+template <bool REFR, class MaskT, bool FRAME>
+__global__ __launch_bounds__(256) void k_update_list(float* __restrict__ w, MaskT* __restrict__ mask,
+                                                      long long* __restrict__ next_ok, const unsigned* __restrict__ list,
+                                                      const unsigned* __restrict__ count, TabArg<REFR> tab, float v_act,
+                                                      unsigned* zero_next, SurfOut so)
+{
+    __shared__ long long tf[REFR ? 32 : 1], tn[REFR ? 32 : 1];
+    if constexpr (REFR) {
+        if (threadIdx.x < 32) { tf[threadIdx.x] = tab.t_first[threadIdx.x]; tn[threadIdx.x] = tab.t_next[threadIdx.x]; }
+        __syncthreads();
+    }
     const unsigned n = *count;
     if (zero_next && blockIdx.x == 0 && threadIdx.x == 0) *zero_next = 0;   // the NEXT group's list counter (other parity)
+    const Drive da = drive_of(v_act);
     for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const unsigned pix = list[i];
-        unsigned m = mask[pix];
+        MaskT m = mask[pix];
         mask[pix] = 0;
-        float ww = w[pix];
-        const Drive da = drive_of(v_act);
-        for (int s = 0; s < n_sl; s++, m >>= 1)
-            if (m & 1u) ww = update_drive(ww, da);
+        if constexpr (REFR) {
+            long long ok = next_ok[pix];
+            m = refractory_walk(m, ok, tf, tn);
+            if (!m) continue;
+            next_ok[pix] = ok;
+        }
+        const float ww = replay_driven(w[pix], m, da);
         w[pix] = ww;
+        if constexpr (FRAME) {
+            const unsigned yy = pix / (unsigned)so.W, xx = pix - yy * (unsigned)so.W;
+            so.out[(long long)yy * so.stride + xx] = surface_gray_one(ww, so.neg_lam, so.mode);
+        }
     }
 }
 
 // Fused state update over every pixel (silent_v outside the dead zone, or forced dense).
 // 4 pixels per thread: one 16-B load/store of w and of the mask per lane.
-// SIL_NOOP: silent_v lies in the dead zone [voff, von], where update_state leaves w bit-for-bit unchanged
-// (dw = 0, w already inside [0,1]), so only the slices whose bit is set are replayed (in slice order) -- the pass
-// is then bound by its one read and one write of the state instead of by 32 no-op evaluations per pixel.
-template <bool SIL_NOOP>
-__global__ __launch_bounds__(256) void k_update_dense(float* __restrict__ w, unsigned* __restrict__ mask, size_t n4,
-                                                       size_t n, int n_sl, float v_act, float v_sil, SurfOut so,
-                                                       unsigned* __restrict__ mask_hi)
+//   REFR      scheme 2: refractory_walk on every touched pixel, as in k_update_list; it has neither a second mask word nor
+//             a fused frame.  Scheme 1: m = slices 0..31 of the group, mh = slices 32..63 (groups of up to 64 slices: one
+//             pass over the array where a frame interval of 33 slices took two), and the frame of the new state in `so`.
+//   SIL_NOOP  silent_v lies in the dead zone [voff, von], where update_state leaves w bit-for-bit unchanged (dw = 0, w
+//             already inside [0,1]), so only the slices whose bit is set are replayed (in slice order) -- the pass is then
+//             bound by its one read and one write of the state instead of by 32 no-op evaluations per pixel.
+template <bool REFR, bool SIL_NOOP>
+__global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsigned* __restrict__ mask,
+                                                     unsigned* __restrict__ mask_hi, long long* __restrict__ next_ok, size_t n4,
+                                                     size_t n, int n_sl, TabArg<REFR> tab, float v_act, float v_sil, SurfOut so)
 {
+    __shared__ long long tf[REFR ? 32 : 1], tn[REFR ? 32 : 1];
+    if constexpr (REFR) {
+        if (threadIdx.x < 32) { tf[threadIdx.x] = tab.t_first[threadIdx.x]; tn[threadIdx.x] = tab.t_next[threadIdx.x]; }
+        __syncthreads();
+        mask_hi = nullptr;   // known at compile time: the scheme-2 instantiations carry no code for either
+        so.out = nullptr;
+    }
     const Drive da = drive_of(v_act), ds = drive_of(v_sil);
-    // m: slices 0..31 of the group, mh: slices 32..63 (groups of up to 64 slices: one pass over the array where a frame
-    // interval of 33 slices took two)
-    auto replay = [&](float ww, unsigned m, unsigned mh) {
-        if (SIL_NOOP) {
-            for (; m; m &= m - 1) ww = update_drive(ww, da);
-            for (; mh; mh &= mh - 1) ww = update_drive(ww, da);
-        } else {
-            for (int s = 0; s < n_sl; s++) {
-                const bool act = s < 32 ? (m >> s) & 1u : (mh >> (s - 32)) & 1u;
-                Drive d;
-                d.ka = act ? da.ka : ds.ka;
-                d.s = act ? da.s : ds.s;
-                d.b = act ? da.b : ds.b;
-                ww = update_drive(ww, d);
+    auto one = [&](float ww, unsigned m, unsigned mh, size_t pix) {
+        if constexpr (REFR) {
+            if (m) {
+                long long ok = next_ok[pix];
+                m = refractory_walk(m, ok, tf, tn);
+                if (m) next_ok[pix] = ok;
             }
+        }
+        if (SIL_NOOP) return replay_driven(replay_driven(ww, m, da), mh, da);
+        for (int s = 0; s < n_sl; s++) {
+            const bool act = (REFR || s < 32) ? (m >> s) & 1u : (mh >> (s - 32)) & 1u;
+            Drive d;
+            d.ka = act ? da.ka : ds.ka;
+            d.s = act ? da.s : ds.s;
+            d.b = act ? da.b : ds.b;
+            ww = update_drive(ww, d);
         }
         return ww;
     };
@@ -274,16 +359,19 @@ __global__ __launch_bounds__(256) void k_update_dense(float* __restrict__ w, uns
         if (4 * i + 3 < n) {
             float4 ww = reinterpret_cast<float4*>(w)[i];
             const uint4 mm = reinterpret_cast<uint4*>(mask)[i];
-            if (mm.x | mm.y | mm.z | mm.w) reinterpret_cast<uint4*>(mask)[i] = make_uint4(0, 0, 0, 0);
+            const bool any = (mm.x | mm.y | mm.z | mm.w) != 0;
+            // nothing driven: w unchanged bit for bit.  Scheme 1 stores every quad: its fused frame needs every pixel.
+            if (REFR && SIL_NOOP && !any) continue;
+            if (any) reinterpret_cast<uint4*>(mask)[i] = make_uint4(0, 0, 0, 0);
             uint4 mh = make_uint4(0, 0, 0, 0);
             if (mask_hi) {
                 mh = reinterpret_cast<uint4*>(mask_hi)[i];
                 if (mh.x | mh.y | mh.z | mh.w) reinterpret_cast<uint4*>(mask_hi)[i] = make_uint4(0, 0, 0, 0);
             }
-            ww.x = replay(ww.x, mm.x, mh.x);
-            ww.y = replay(ww.y, mm.y, mh.y);
-            ww.z = replay(ww.z, mm.z, mh.z);
-            ww.w = replay(ww.w, mm.w, mh.w);
+            ww.x = one(ww.x, mm.x, mh.x, 4 * i);
+            ww.y = one(ww.y, mm.y, mh.y, 4 * i + 1);
+            ww.z = one(ww.z, mm.z, mh.z, 4 * i + 2);
+            ww.w = one(ww.w, mm.w, mh.w, 4 * i + 3);
             reinterpret_cast<float4*>(w)[i] = ww;
             if (so.out) {   // the frame of the new state: saves the separate surface pass (4 B/px read again + a launch)
                 const uint8_t g0 = surface_gray_one(ww.x, so.neg_lam, so.mode), g1 = surface_gray_one(ww.y, so.neg_lam, so.mode);
@@ -306,139 +394,9 @@ __global__ __launch_bounds__(256) void k_update_dense(float* __restrict__ w, uns
                 const unsigned m = mask[j], mh = mask_hi ? mask_hi[j] : 0u;
                 mask[j] = 0;
                 if (mask_hi) mask_hi[j] = 0;
-                const float wj = replay(w[j], m, mh);
+                const float wj = one(w[j], m, mh, j);
                 w[j] = wj;
                 if (so.out) so.out[(j / (size_t)so.W) * so.stride + j % (size_t)so.W] = surface_gray_one(wj, so.neg_lam, so.mode);
-            }
-        }
-    }
-}
-
-// ---- scheme 2 without a launch per slice (round 3) ----------------------------------------------------------------------
-// The refractory rule (event_mem_sim.py:237-269) looks like a chain over slices -- slice s+1 tests the next_ok that slice s
-// wrote -- but the chain is PER PIXEL: a pixel's next_ok depends on that pixel's own earlier events only, and within a slice
-// every event of a pixel sees the same next_ok (NumPy reads next_ok[ys, xs] before it writes).  So a group of up to 32
-// slices needs ONE scatter, "which slices have an event (of the array's polarity) at this pixel" (bit s of E), and the
-// eligibility walk moves into the fused state update: per touched pixel, over the set bits of E in slice order,
-//     if next_ok <= t_first[s]:  the pixel is driven in slice s;  next_ok = t_last[s] + REFRACTORY
-// with the per-slice constants in a 64-entry table.  No atomics on next_ok, two launches per group and array as in scheme 1.
-struct RefrTab {
-    long long t_first[32], t_next[32];
-};
-
-// E bits of a group: split == 0: every event -> array 0 (magnitude mode); split == 1: p == 1 -> array 0, p == 0 -> array 1
-// (:238, :250; other polarity values drive nothing).  bounds as in k_scatter_v1.
-__global__ __launch_bounds__(256) void k_scatter_v2g(const short* __restrict__ x, const short* __restrict__ y,
-                                                      const signed char* __restrict__ p, long long ev0, long long n_ev,
-                                                      const long long* __restrict__ bounds, int n_sl, int W, int split,
-                                                      unsigned* mask0, unsigned* list0, unsigned* count0, unsigned* mask1,
-                                                      unsigned* list1, unsigned* count1)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const bool live = i < n_ev;
-    const long long e = ev0 + (live ? i : 0);
-    int arr = 0;
-    if (split) {
-        const int pv = (int)p[e];
-        arr = pv == 1 ? 0 : (pv == 0 ? 1 : -1);
-    }
-    int lo = 0, hi = n_sl;  // largest s with bounds[s] <= e
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (bounds[mid] <= e) lo = mid; else hi = mid;
-    }
-    const unsigned pix = (unsigned)y[e] * (unsigned)W + (unsigned)x[e];
-    mark(mask0, list0, count0, pix, 1u << lo, live && arr == 0);
-    if (split) mark(mask1, list1, count1, pix, 1u << lo, live && arr == 1);
-}
-
-// slices with an event -> slices in which the pixel is driven; ok = the pixel's next_ok (updated)
-__device__ __forceinline__ unsigned refractory_walk(unsigned e, long long& ok, const long long* tf, const long long* tn)
-{
-    unsigned m = 0;
-    for (; e; e &= e - 1) {
-        const int s = __ffs((int)e) - 1;
-        if (ok <= tf[s]) {
-            m |= 1u << s;
-            ok = tn[s];
-        }
-    }
-    return m;
-}
-
-__global__ __launch_bounds__(256) void k_update_sparse_v2(float* __restrict__ w, unsigned* __restrict__ mask,
-                                                           long long* __restrict__ next_ok, const unsigned* __restrict__ list,
-                                                           const unsigned* __restrict__ count, RefrTab tab, float v_act,
-                                                           unsigned* zero_next)
-{
-    __shared__ long long tf[32], tn[32];
-    if (threadIdx.x < 32) { tf[threadIdx.x] = tab.t_first[threadIdx.x]; tn[threadIdx.x] = tab.t_next[threadIdx.x]; }
-    __syncthreads();
-    const unsigned n = *count;
-    if (zero_next && blockIdx.x == 0 && threadIdx.x == 0) *zero_next = 0;   // the NEXT group's list counter (other parity)
-    const Drive da = drive_of(v_act);
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const unsigned pix = list[i];
-        const unsigned e = mask[pix];
-        mask[pix] = 0;
-        long long ok = next_ok[pix];
-        unsigned m = refractory_walk(e, ok, tf, tn);
-        if (m) {
-            next_ok[pix] = ok;
-            float ww = w[pix];
-            for (; m; m &= m - 1) ww = update_drive(ww, da);
-            w[pix] = ww;
-        }
-    }
-}
-
-template <bool SIL_NOOP>
-__global__ __launch_bounds__(256) void k_update_dense_v2(float* __restrict__ w, unsigned* __restrict__ mask,
-                                                          long long* __restrict__ next_ok, size_t n4, size_t n, int n_sl,
-                                                          RefrTab tab, float v_act, float v_sil)
-{
-    __shared__ long long tf[32], tn[32];
-    if (threadIdx.x < 32) { tf[threadIdx.x] = tab.t_first[threadIdx.x]; tn[threadIdx.x] = tab.t_next[threadIdx.x]; }
-    __syncthreads();
-    const Drive da = drive_of(v_act), ds = drive_of(v_sil);
-    auto one = [&](float ww, unsigned e, size_t pix) {
-        unsigned m = 0;
-        if (e) {
-            long long ok = next_ok[pix];
-            m = refractory_walk(e, ok, tf, tn);
-            if (m) next_ok[pix] = ok;
-        }
-        if (SIL_NOOP) {
-            for (; m; m &= m - 1) ww = update_drive(ww, da);
-        } else {
-            for (int s = 0; s < n_sl; s++) {
-                const bool act = (m >> s) & 1u;
-                Drive d;
-                d.ka = act ? da.ka : ds.ka;
-                d.s = act ? da.s : ds.s;
-                d.b = act ? da.b : ds.b;
-                ww = update_drive(ww, d);
-            }
-        }
-        return ww;
-    };
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        if (4 * i + 3 < n) {
-            float4 ww = reinterpret_cast<float4*>(w)[i];
-            const uint4 mm = reinterpret_cast<uint4*>(mask)[i];
-            const bool any = (mm.x | mm.y | mm.z | mm.w) != 0;
-            if (SIL_NOOP && !any) continue;                       // nothing driven: w unchanged bit for bit
-            if (any) reinterpret_cast<uint4*>(mask)[i] = make_uint4(0, 0, 0, 0);
-            ww.x = one(ww.x, mm.x, 4 * i);
-            ww.y = one(ww.y, mm.y, 4 * i + 1);
-            ww.z = one(ww.z, mm.z, 4 * i + 2);
-            ww.w = one(ww.w, mm.w, 4 * i + 3);
-            reinterpret_cast<float4*>(w)[i] = ww;
-        } else {
-            for (size_t j = 4 * i; j < n; j++) {
-                const unsigned e = mask[j];
-                mask[j] = 0;
-                w[j] = one(w[j], e, j);
             }
         }
     }
@@ -495,14 +453,13 @@ __global__ __launch_bounds__(256) void k_surface_gray_f32(const float* __restric
         (float)surface_gray_value(w[(size_t)y * W + x], neg_lam, mode);
 }
 
-// ---- surface frames as copy + patch (round 4) ---------------------------------------------------------------------------
+// ---- surface frames as copy + patch -------------------------------------------------------------------------------------
 // With the silent voltage in the dead zone a pixel without events keeps its state bit for bit, so the 8-bit frame of interval
 // k differs from that of interval k-1 only at the pixels the interval's events touch (0.4 % of a 3840x2160 sensor at 1 M
 // events/s and 33 ms per frame).  The every-pixel pass moves 17 B/px per interval to find that out; here an interval is
 //   A  k_frames_scatter_copy   frames[k] = frames[k-1] (2 B/px) while the interval's events are scattered into the per-pixel
 //                              slice masks (one 64-bit word: up to 64 slices) and the compact list of touched pixels
-//   B  k_frames_update_patch   the touched pixels replay their slices in order (the update of k_update_sparse), store w and
-//                              overwrite their byte of frames[k]
+//   B  k_update_list           the touched pixels replay their slices in order, store w and overwrite their byte of frames[k]
 // -- same states, same frames (tests/test_accum_gpu.py::test_run_frames_copy_patch_equals_dense_frames).
 __global__ __launch_bounds__(256) void k_frames_scatter_copy(const uint8_t* __restrict__ prev, uint8_t* __restrict__ cur, int W, int H,
                                                               long long row_stride, const short* __restrict__ x,
@@ -517,24 +474,7 @@ __global__ __launch_bounds__(256) void k_frames_scatter_copy(const uint8_t* __re
     for (long long i = tid; i < n_ev_pad; i += nthreads) {
         const bool live = i < n_ev;
         const long long e = ev0 + (live ? i : 0);
-        int lo = 0, hi = n_sl;  // largest s with bounds[s] <= e
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (bounds[mid] <= e) lo = mid; else hi = mid;
-        }
-        // ONE 64-bit slice mask per pixel: a pixel enters the list exactly once per interval (its first touch), so no two
-        // threads of the update ever hold the same pixel
-        const unsigned pix = (unsigned)y[e] * (unsigned)W + (unsigned)x[e];
-        const unsigned long long old = live ? atomicOr(&mask64[pix], 1ull << lo) : 1ull;
-        const bool first = live && old == 0;
-        const unsigned long long b = __ballot(first);
-        if (b) {
-            const int lane = threadIdx.x & 63, leader = __ffsll((long long)b) - 1;
-            unsigned base = 0;
-            if (lane == leader) base = atomicAdd(count, (unsigned)__popcll(b));
-            base = __shfl(base, leader);
-            if (first) list[base + (unsigned)__popcll(b & ((1ull << lane) - 1ull))] = pix;
-        }
+        mark(mask64, list, count, (unsigned)y[e] * (unsigned)W + (unsigned)x[e], 1ull << slice_of(bounds, n_sl, e), live);
     }
     // ... then this thread's share of the copy
     if (prev) {
@@ -554,29 +494,7 @@ __global__ __launch_bounds__(256) void k_frames_scatter_copy(const uint8_t* __re
     }
 }
 
-__global__ __launch_bounds__(256) void k_frames_update_patch(float* __restrict__ w, unsigned long long* __restrict__ mask64,
-                                                              const unsigned* __restrict__ list,
-                                                              const unsigned* __restrict__ count, float v_act, unsigned* zero_next,
-                                                              uint8_t* __restrict__ frame, int W, long long row_stride,
-                                                              float neg_lam, int mode)
-{
-    const unsigned n = *count;
-    if (zero_next && blockIdx.x == 0 && threadIdx.x == 0) *zero_next = 0;   // the NEXT interval's list counter (other parity)
-    const Drive da = drive_of(v_act);
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const unsigned pix = list[i];
-        unsigned long long m = mask64[pix];
-        mask64[pix] = 0;
-        float ww = w[pix];
-        for (; m; m >>= 1)
-            if (m & 1ull) ww = update_drive(ww, da);
-        w[pix] = ww;
-        const unsigned yy = pix / (unsigned)W, xx = pix - yy * (unsigned)W;
-        frame[(long long)yy * row_stride + xx] = surface_gray_one(ww, neg_lam, mode);
-    }
-}
-
-// ---- surface frames by a tile-persistent walk (round 4) -------------------------------------------------------------
+// ---- surface frames by a tile-persistent walk ---------------------------------------------------------------------
 // Pixels never interact, so nothing forces an interval to be a launch: a WAVE owns a tile of 1024 consecutive pixels for
 // the WHOLE run.  Its state (w, 4 KB), the 8-bit bytes of the current frame (1 KB) and a 64-bit slice mask per pixel (8 KB)
 // live in LDS; per interval it ORs the tile's events into the masks, lets one lane per touched pixel replay them
@@ -606,14 +524,10 @@ __global__ __launch_bounds__(1024) void k_tile_bucket(const short* __restrict__ 
     const long long lo = s_b[0], hi = s_b[every];
     const unsigned base = (unsigned)(lo - ev0);
     auto rec_of = [&](long long e, unsigned& tile) -> unsigned {
-        int a = 0, b = every;                     // largest s with s_b[s] <= e
-        while (b - a > 1) {
-            const int mid = (a + b) >> 1;
-            if (s_b[mid] <= e) a = mid; else b = mid;
-        }
+        const unsigned s = (unsigned)slice_of(s_b, every, e);
         const unsigned pix = (unsigned)y[e] * (unsigned)W + (unsigned)x[e];
         tile = pix >> TILE_SHIFT;
-        return (pix & (TILE_PX - 1)) | ((unsigned)a << TILE_SHIFT);
+        return (pix & (TILE_PX - 1)) | (s << TILE_SHIFT);
     };
     for (long long e = lo + tid; e < hi; e += 1024) {
         unsigned tile;
@@ -718,10 +632,9 @@ __global__ __launch_bounds__(256) void k_tile_frames(float* __restrict__ w, size
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                 auto settle = [&](unsigned r) {
                     const unsigned pix = r & (TILE_PX - 1);
-                    unsigned long long m = atomicExch(&ml[pix], 0ull);
+                    const unsigned long long m = atomicExch(&ml[pix], 0ull);
                     if (m) {
-                        float ww = wl[pix];
-                        for (; m; m &= m - 1) ww = update_drive(ww, da);
+                        const float ww = replay_driven(wl[pix], m, da);
                         wl[pix] = ww;
                         bl[pix] = surface_gray_one(ww, neg_lam, mode);
                     }
@@ -756,6 +669,20 @@ inline int grid_for(size_t n, int cap = 4096)
     size_t g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
 }
+
+// resistance_exp's exponent scale -ln(Roff / Ron), as the float32 the kernels take
+inline float neg_lam() { return (float)(-std::log(ROFF / RON)); }
+
+// List counters of the event-pixel update, [parity][array]: two sets used alternately.  A group's update kernels zero the
+// OTHER set -- the one the next group's scatter appends to -- so no group needs a memset (a launch of its own): one per call.
+struct ListCounts {
+    unsigned* base;
+    int par = 0;
+    hipError_t zero_all(hipStream_t s) const { return hipMemsetAsync(base, 0, 4 * sizeof(unsigned), s); }
+    unsigned* cur() const { return base + 2 * par; }
+    unsigned* next() const { return base + 2 * (par ^ 1); }
+    void flip() { par ^= 1; }
+};
 
 }  // namespace
 
@@ -873,10 +800,9 @@ static int accum_snapshot(nsof_accum* a)
         }
         a->snap_cap = ncap;
     }
-    const float neg_lam = (float)(-std::log(ROFF / RON));
     for (int i = 0; i < narr; i++)
         hipLaunchKernelGGL(k_resistance, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[i].p,
-                           a->snap[i].p + (size_t)a->snap_count * a->npx, a->npx, neg_lam);
+                           a->snap[i].p + (size_t)a->snap_count * a->npx, a->npx, neg_lam());
     NSOF_HIP(ctx, hipGetLastError());
     a->snap_count++;
     return NSOF_OK;
@@ -949,7 +875,12 @@ extern "C" int nsof_accum_set_slice_times(nsof_accum* a, const int64_t* t_first,
     return NSOF_OK;
 }
 
-// Advance over staged slices [s_begin, s_begin + n_slices).
+// The arguments every 8-bit surface entry point takes: an array of this accumulator, a surface mode, rows of at least W bytes.
+static bool surface_args_ok(const nsof_accum* a, int which, int mode, const uint8_t* d_out, ptrdiff_t row_stride)
+{
+    return a && d_out && which >= 0 && which <= (a->split ? 1 : 0) && row_stride >= a->W && mode >= 0 && mode <= 1;
+}
+
 static int accum_surface(nsof_accum* a, int which, const SurfOut& so)
 {
     nsof_ctx* ctx = a->ctx;
@@ -960,6 +891,7 @@ static int accum_surface(nsof_accum* a, int which, const SurfOut& so)
     return NSOF_OK;
 }
 
+// Advance over staged slices [s_begin, s_begin + n_slices).
 // surf (optional): after the LAST slice of the call the surface of array surf_which goes to surf->out as an 8-bit frame --
 // fused into the last group's dense scheme-1 update where that kernel runs, a separate k_surface_gray launch otherwise.
 static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64_t snap_every, const SurfOut* surf = nullptr,
@@ -994,10 +926,8 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
         NSOF_HIP(ctx, hipMemsetAsync(a->mask_hi.p, 0, a->npx * sizeof(unsigned) + 16, ctx->stream));
     }
     const int64_t max_group = wide ? 2 * MAX_GROUP : MAX_GROUP;
-    // List counters of the event-pixel update: two sets used alternately.  A group's update kernels zero the OTHER set -- the
-    // one the next group's scatter appends to -- so the per-group 8-byte memset (a launch of its own) is gone: one per call.
-    int par = 0;
-    if (sparse && s0 < s_end) NSOF_HIP(ctx, hipMemsetAsync(a->count.p, 0, 4 * sizeof(unsigned), ctx->stream));
+    ListCounts cnt{a->count.p};
+    if (sparse && s0 < s_end) NSOF_HIP(ctx, cnt.zero_all(ctx->stream));
     while (s0 < s_end) {
         // group = up to max_group slices, ending right after the next snapshot slice
         int64_t g = s_end - s0 < max_group ? s_end - s0 : max_group;
@@ -1007,73 +937,55 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
             if (to_snap < g) g = to_snap;
         }
         const long long ge0 = rel[s0], ge1 = rel[s0 + g], gn = ge1 - ge0;
-        unsigned* const cnt = a->count.p + 2 * par;          // this group's counters; (the dense update has no list)
-        unsigned* const cnt_next = a->count.p + 2 * (par ^ 1);
-        if (sparse && gn == 0) NSOF_HIP(ctx, hipMemsetAsync(cnt_next, 0, 2 * sizeof(unsigned), ctx->stream));   // no update kernel will
-        unsigned* const l0 = sparse ? a->list[0].p : nullptr;                      // the dense update reads no list
-        unsigned* const l1 = sparse ? a->list[a->split ? 1 : 0].p : nullptr;
+        if (sparse && gn == 0) NSOF_HIP(ctx, hipMemsetAsync(cnt.next(), 0, 2 * sizeof(unsigned), ctx->stream));   // no update kernel will
         if (gn > 0) {
             nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
-            if (a->scheme == 1) {
-                hipLaunchKernelGGL(k_scatter_v1, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream, a->dx.p,
-                                   a->dy.p, ge0, gn, a->dbounds.p + s0, (int)g, a->W, a->mask[0].p, l0, cnt, a->mask_hi.p);
-            } else {
-                hipLaunchKernelGGL(k_scatter_v2g, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream, a->dx.p, a->dy.p,
-                                   a->dp.p, ge0, gn, a->dbounds.p + s0, (int)g, a->W, a->split ? 1 : 0, a->mask[0].p, l0,
-                                   cnt, a->mask[a->split ? 1 : 0].p, l1, cnt + 1);
-            }
+            unsigned* const l0 = sparse ? a->list[0].p : nullptr;   // the every-pixel update reads no list
+            unsigned* const l1 = sparse ? a->list[a->split].p : nullptr;
+            hipLaunchKernelGGL(k_scatter, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream, a->dx.p, a->dy.p,
+                               a->dp.p, ge0, gn, a->dbounds.p + s0, (int)g, a->W, a->split, a->mask[0].p, l0, cnt.cur(),
+                               a->mask[a->split].p, l1, cnt.cur() + 1, a->mask_hi.p);
             NSOF_HIP(ctx, hipGetLastError());
         }
         {
             nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
-            RefrTab tab;
-            const bool refr = a->scheme == 2;
-            if (refr)
+            // array i of the group; R: std::true_type for scheme 2, whose kernels take the group's refractory table
+            auto update = [&](auto R, const auto& tab, int i) {
+                constexpr bool REFR = decltype(R)::value;
+                SurfOut so{nullptr, 0, a->W, 0.f, 0};
+                if (sparse) {
+                    if (gn > 0)
+                        hipLaunchKernelGGL((k_update_list<REFR, unsigned, false>), dim3(grid_for((size_t)gn, 1024)), dim3(256), 0,
+                                           ctx->stream, a->w[i].p, a->mask[i].p, a->next_ok[i].p, a->list[i].p, cnt.cur() + i, tab,
+                                           v_act, cnt.next() + i, so);
+                    return;
+                }
+                if (wide && surf && i == surf_which && s0 + g == s_end) {   // the call's last group: leave the frame as well
+                    so = *surf;
+                    surf_done = true;
+                }
+                const size_t n4 = (a->npx + 3) / 4;
+                auto* const kernel = dead_zone ? k_update_all<REFR, true> : k_update_all<REFR, false>;
+                hipLaunchKernelGGL(kernel, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream, a->w[i].p, a->mask[i].p,
+                                   g > MAX_GROUP ? a->mask_hi.p : nullptr, a->next_ok[i].p, n4, a->npx, (int)g, tab, v_act,
+                                   a->silent_v, so);
+            };
+            if (a->scheme == 2) {
+                RefrTab tab;
                 for (int s = 0; s < 32; s++) {
                     const bool live = s < g && rel[s0 + s + 1] > rel[s0 + s];
                     tab.t_first[s] = live ? a->h_tfirst[s0 + s] : 0;
                     tab.t_next[s] = live ? a->h_tnext[s0 + s] : 0;
                 }
-            for (int i = 0; i < narr; i++) {
-                if (refr) {
-                    const size_t n4 = (a->npx + 3) / 4;
-                    if (sparse) {
-                        if (gn > 0)
-                            hipLaunchKernelGGL(k_update_sparse_v2, dim3(grid_for((size_t)gn, 1024)), dim3(256), 0, ctx->stream,
-                                               a->w[i].p, a->mask[i].p, a->next_ok[i].p, a->list[i].p, cnt + i, tab, v_act, cnt_next + i);
-                    } else if (dead_zone) {
-                        hipLaunchKernelGGL(k_update_dense_v2<true>, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream, a->w[i].p,
-                                           a->mask[i].p, a->next_ok[i].p, n4, a->npx, (int)g, tab, v_act, a->silent_v);
-                    } else {
-                        hipLaunchKernelGGL(k_update_dense_v2<false>, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream, a->w[i].p,
-                                           a->mask[i].p, a->next_ok[i].p, n4, a->npx, (int)g, tab, v_act, a->silent_v);
-                    }
-                } else if (sparse) {
-                    if (gn > 0)
-                        hipLaunchKernelGGL(k_update_sparse, dim3(grid_for((size_t)gn, 1024)), dim3(256), 0, ctx->stream,
-                                           a->w[i].p, a->mask[i].p, a->list[i].p, cnt + i, (int)g, v_act, cnt_next + i);
-                } else {
-                    const size_t n4 = (a->npx + 3) / 4;
-                    SurfOut so{nullptr, 0, a->W, 0.f, 0};
-                    if (surf && i == surf_which && s0 + g == s_end) {   // the call's last group: leave the frame as well
-                        so = *surf;
-                        surf_done = true;
-                    }
-                    if (dead_zone)
-                        hipLaunchKernelGGL(k_update_dense<true>, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream,
-                                           a->w[i].p, a->mask[i].p, n4, a->npx, (int)g, v_act, a->silent_v, so,
-                                           g > MAX_GROUP ? a->mask_hi.p : nullptr);
-                    else
-                        hipLaunchKernelGGL(k_update_dense<false>, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream,
-                                           a->w[i].p, a->mask[i].p, n4, a->npx, (int)g, v_act, a->silent_v, so,
-                                           g > MAX_GROUP ? a->mask_hi.p : nullptr);
-                }
+                for (int i = 0; i < narr; i++) update(std::true_type{}, tab, i);
+            } else {
+                update(std::false_type{}, NoTab{}, 0);
             }
             NSOF_HIP(ctx, hipGetLastError());
         }
         a->slice_counter += g;
         s0 += g;
-        if (sparse) par ^= 1;
+        if (sparse) cnt.flip();
         if (snap_every > 0 && (a->slice_counter - 1) % snap_every == 0)
             if ((rc = accum_snapshot(a))) return rc;
     }
@@ -1104,9 +1016,9 @@ extern "C" int nsof_accum_run(nsof_accum* a, int64_t first_slice, int64_t n_slic
 
 extern "C" int nsof_accum_surface_u8_dev(nsof_accum* a, int which, int mode, uint8_t* d_out, ptrdiff_t row_stride)
 {
-    if (!a || !d_out || which < 0 || which > (a->split ? 1 : 0) || row_stride < a->W || mode < 0 || mode > 1) return NSOF_EINVAL;
+    if (!surface_args_ok(a, which, mode, d_out, row_stride)) return NSOF_EINVAL;
     NSOF_HIP(a->ctx, hipSetDevice(a->ctx->device));
-    return accum_surface(a, which, SurfOut{d_out, (long long)row_stride, a->W, (float)(-std::log(ROFF / RON)), mode});
+    return accum_surface(a, which, SurfOut{d_out, (long long)row_stride, a->W, neg_lam(), mode});
 }
 
 extern "C" int nsof_accum_surface_f32_dev(nsof_accum* a, int which, int mode, float* d_out, ptrdiff_t row_stride_bytes)
@@ -1118,7 +1030,7 @@ extern "C" int nsof_accum_surface_f32_dev(nsof_accum* a, int which, int mode, fl
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid((a->W + 255) / 256, a->H);
     hipLaunchKernelGGL(k_surface_gray_f32, grid, dim3(256), 0, ctx->stream, a->w[which].p, d_out, a->W, a->H, row_stride_bytes,
-                       (float)(-std::log(ROFF / RON)), mode);
+                       neg_lam(), mode);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
@@ -1126,8 +1038,8 @@ extern "C" int nsof_accum_surface_f32_dev(nsof_accum* a, int which, int mode, fl
 extern "C" int nsof_accum_run_surface(nsof_accum* a, int64_t first_slice, int64_t n_slices, int which, int mode, uint8_t* d_out,
                                       ptrdiff_t row_stride)
 {
-    if (!a || !d_out || which < 0 || which > (a->split ? 1 : 0) || row_stride < a->W || mode < 0 || mode > 1) return NSOF_EINVAL;
-    const SurfOut so{d_out, (long long)row_stride, a->W, (float)(-std::log(ROFF / RON)), mode};
+    if (!surface_args_ok(a, which, mode, d_out, row_stride)) return NSOF_EINVAL;
+    const SurfOut so{d_out, (long long)row_stride, a->W, neg_lam(), mode};
     return accum_advance(a, first_slice, n_slices, 0, &so, which);
 }
 
@@ -1137,27 +1049,26 @@ extern "C" int nsof_accum_run_surface(nsof_accum* a, int64_t first_slice, int64_
 extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t n_frames, int64_t every, int which, int mode,
                                      uint8_t* d_frames, ptrdiff_t row_stride, ptrdiff_t frame_stride)
 {
-    if (!a || !d_frames || which < 0 || which > (a->split ? 1 : 0) || row_stride < a->W || mode < 0 || mode > 1 || n_frames < 0 ||
-        every < 1 || frame_stride < 0)
-        return NSOF_EINVAL;
+    if (!surface_args_ok(a, which, mode, d_frames, row_stride) || n_frames < 0 || every < 1 || frame_stride < 0) return NSOF_EINVAL;
     nsof_ctx* ctx = a->ctx;
     if (n_frames == 0) return NSOF_OK;
     if (first_slice < 0 || (size_t)(first_slice + n_frames * every + 1) > a->h_rel.size())
         return nsof_set_error(ctx, NSOF_EINVAL, "slices [%lld, %lld) outside the staged stream", (long long)first_slice,
                               (long long)(first_slice + n_frames * every));
     const bool dead_zone = !(a->silent_v < VOFF) && !(a->silent_v > VON);
-    const float neg_lam = (float)(-std::log(ROFF / RON));
+    // frame k of the call, as the kernels take it
+    auto frame = [&](int64_t k) { return SurfOut{d_frames + k * frame_stride, (long long)row_stride, a->W, neg_lam(), mode}; };
     if (!(a->scheme == 1 && dead_zone && a->force_dense <= 0 && every <= 2 * MAX_GROUP)) {
         for (int64_t k = 0; k < n_frames; k++) {
-            const SurfOut so{d_frames + k * frame_stride, (long long)row_stride, a->W, neg_lam, mode};
+            const SurfOut so = frame(k);
             if (int rc = accum_advance(a, first_slice + k * every, every, 0, &so, which)) return rc;
         }
         return NSOF_OK;
     }
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
-    const std::vector<long long>& relv = a->h_rel;
-    const long long ev0 = relv[first_slice], n_ev = relv[first_slice + n_frames * every] - ev0;
+    const std::vector<long long>& rel = a->h_rel;
+    const long long ev0 = rel[first_slice], n_ev = rel[first_slice + n_frames * every] - ev0;
     // ---- the tile walk: whole run in four launches (frames write-only); needs 16-byte-addressable frame rows
     const bool tile_ok = (a->W & 15) == 0 && (row_stride & 15) == 0 && (frame_stride & 15) == 0 &&
                          (reinterpret_cast<uintptr_t>(d_frames) & 15) == 0 && n_frames >= 2 && n_ev < (1ll << 31) &&
@@ -1174,7 +1085,7 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
                            a->dbounds.p + first_slice, (int)every, a->W, ntiles, a->tile_off.p, a->tile_recs.p, (int)n_frames);
         hipLaunchKernelGGL(k_tile_frames, dim3((ntiles + 3) / 4), dim3(256), 0, ctx->stream, a->w[0].p, a->npx, a->W,
                            (const unsigned*)a->tile_off.p, (const unsigned short*)a->tile_recs.p, ntiles, (int)n_frames, a->active_v, d_frames,
-                           (long long)row_stride, (long long)frame_stride, neg_lam, mode);
+                           (long long)row_stride, (long long)frame_stride, neg_lam(), mode);
         NSOF_HIP(ctx, hipGetLastError());
         a->slice_counter += n_frames * every;
         return NSOF_OK;
@@ -1183,35 +1094,31 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
         if ((rc = a->mask64.reserve(ctx, a->npx * sizeof(unsigned long long)))) return rc;
         NSOF_HIP(ctx, hipMemsetAsync(a->mask64.p, 0, a->npx * sizeof(unsigned long long), ctx->stream));
     }
-    const std::vector<long long>& rel = a->h_rel;
-    NSOF_HIP(ctx, hipMemsetAsync(a->count.p, 0, 4 * sizeof(unsigned), ctx->stream));
-    int par = 0;
+    ListCounts cnt{a->count.p};
+    NSOF_HIP(ctx, cnt.zero_all(ctx->stream));
     constexpr size_t ACC_COPY_BLOCKS = 4096;
     const unsigned copy_blocks = (unsigned)std::min<size_t>(ACC_COPY_BLOCKS, (a->npx / 16 + 255) / 256 + 1);
     for (int64_t k = 0; k < n_frames; k++) {
         const int64_t s0 = first_slice + k * every;
         const long long ge0 = rel[s0], gn = rel[s0 + every] - ge0;
-        unsigned* const cnt = a->count.p + 2 * par;
-        unsigned* const cnt_next = a->count.p + 2 * (par ^ 1);
-        uint8_t* const cur = d_frames + k * frame_stride;
-        const uint8_t* const prev = k > 0 ? d_frames + (k - 1) * frame_stride : nullptr;
+        const SurfOut cur = frame(k);
+        const uint8_t* const prev = k > 0 ? frame(k - 1).out : nullptr;
         nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
         if (prev || gn > 0) {
             const unsigned blocks = prev ? copy_blocks : (unsigned)((gn + 255) / 256);
-            hipLaunchKernelGGL(k_frames_scatter_copy, dim3(blocks), dim3(256), 0, ctx->stream, prev, cur, a->W, a->H,
-                               (long long)row_stride, a->dx.p, a->dy.p, ge0, gn, a->dbounds.p + s0, (int)every, a->mask64.p, a->list[0].p, cnt);
+            hipLaunchKernelGGL(k_frames_scatter_copy, dim3(blocks), dim3(256), 0, ctx->stream, prev, cur.out, a->W, a->H,
+                               (long long)row_stride, a->dx.p, a->dy.p, ge0, gn, a->dbounds.p + s0, (int)every, a->mask64.p, a->list[0].p,
+                               cnt.cur());
         }
         // (launched for an empty interval as well: it zeroes the next interval's counter)
-        hipLaunchKernelGGL(k_frames_update_patch, dim3(grid_for((size_t)std::max<long long>(gn, 1), 1024)), dim3(256), 0, ctx->stream,
-                           a->w[0].p, a->mask64.p, a->list[0].p, cnt, a->active_v, cnt_next, cur, a->W,
-                           (long long)row_stride, neg_lam, mode);
+        hipLaunchKernelGGL((k_update_list<false, unsigned long long, true>), dim3(grid_for((size_t)std::max<long long>(gn, 1), 1024)),
+                           dim3(256), 0, ctx->stream, a->w[0].p, a->mask64.p, (long long*)nullptr, a->list[0].p, cnt.cur(), NoTab{},
+                           a->active_v, cnt.next(), cur);
         NSOF_HIP(ctx, hipGetLastError());
-        if (k == 0) {   // the call's first frame has no predecessor to copy: one pass over the array
-            const SurfOut so{cur, (long long)row_stride, a->W, neg_lam, mode};
-            if ((rc = accum_surface(a, which, so))) return rc;
-        }
+        // the call's first frame has no predecessor to copy: one pass over the array
+        if (k == 0 && (rc = accum_surface(a, which, cur))) return rc;
         a->slice_counter += every;
-        par ^= 1;
+        cnt.flip();
     }
     return NSOF_OK;
 }
@@ -1297,7 +1204,7 @@ extern "C" int nsof_accum_resistance_dev(nsof_ctx* ctx, const float* d_w, float*
     if (!ctx || !d_w || !d_out) return NSOF_EINVAL;
     if (!n) return NSOF_OK;
     hipLaunchKernelGGL(k_resistance, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_w, d_out, n,
-                       (float)(-std::log(ROFF / RON)));
+                       neg_lam());
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
@@ -1364,7 +1271,7 @@ extern "C" int nsof_accum_block_current(nsof_accum* a, int which, int64_t snapsh
     if (rc) return rc;
     const float* src = snapshot < 0 ? a->w[which].p : a->snap[which].p + (size_t)snapshot * a->npx;
     hipLaunchKernelGGL(k_block_min_resistance, dim3(cols, rows), dim3(256), 0, ctx->stream, src, snapshot < 0 ? 1 : 0, a->W,
-                       memsize, cols, (float)(-std::log(ROFF / RON)), v_ds, (double*)ctx->tmp.p);
+                       memsize, cols, neg_lam(), v_ds, (double*)ctx->tmp.p);
     NSOF_HIP(ctx, hipGetLastError());
     NSOF_HIP(ctx, hipMemcpyAsync(out, ctx->tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1383,7 +1290,7 @@ extern "C" int nsof_accum_block_current_dev(nsof_accum* a, int which, int64_t sn
     const int rows = a->H / memsize, cols = a->W / memsize;
     const float* src = snapshot < 0 ? a->w[which].p : a->snap[which].p + (size_t)snapshot * a->npx;
     hipLaunchKernelGGL(k_block_min_resistance, dim3(cols, rows), dim3(256), 0, ctx->stream, src, snapshot < 0 ? 1 : 0, a->W,
-                       memsize, cols, (float)(-std::log(ROFF / RON)), v_ds, d_out);
+                       memsize, cols, neg_lam(), v_ds, d_out);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }

@@ -107,15 +107,36 @@ def _refractory_edges(H, W, seed):
     return x[o].astype(np.int16), y[o].astype(np.int16), p[o].astype(np.int8), t[o]
 
 
-@pytest.mark.parametrize("polarity", ["split", "magnitude"])
-def test_scheme2_refractory_edges_exact(nsof_lib, ctx, oracle, polarity):
-    H, W = 40, 48
-    x, y, p, t = _refractory_edges(H, W, 3)
-    ref = oracle.accum_simulate(x, y, p, t, H, W, 2, polarity, 1000, -6.0, 0.0, rounding="correct")
+def _tail_stream(H, W):
+    from nsof import synth
+    return synth.make_events(3, W, H, 4000, 70_000, box=(12, 9))
+
+
+# case -> (H, W, stream, silent_v, dense).  The 37 x 45 sensor has 1665 pixels, 1665 % 4 == 1: the every-pixel update
+# (k_update_all) ends in its scalar tail there, which no sensor with a pixel count divisible by 4 reaches.
+_S2_CASES = {
+    "edges": (40, 48, lambda: _refractory_edges(40, 48, 3), 0.0, None),
+    "tail-list": (37, 45, lambda: _tail_stream(37, 45), 0.0, False),       # event-pixel update (k_update_list)
+    "tail-all-skip": (37, 45, lambda: _tail_stream(37, 45), 0.0, True),    # every-pixel, untouched quads skipped
+    "tail-all-leak": (37, 45, lambda: _tail_stream(37, 45), 0.3, None),    # every-pixel, all slices replayed
+}
+_S2_REFS = {}
+
+
+@pytest.mark.parametrize("polarity,case", [pytest.param(pol, case, id=pol if case == "edges" else f"{pol}-{case}")
+                                           for case in _S2_CASES for pol in ("split", "magnitude")])
+def test_scheme2_refractory_edges_exact(nsof_lib, ctx, oracle, polarity, case):
+    H, W, stream, silent_v, dense = _S2_CASES[case]
+    x, y, p, t = stream()
+    key = (H, W, polarity, silent_v)   # the list and the every-pixel update of one run share its reference
+    if key not in _S2_REFS:
+        _S2_REFS[key] = oracle.accum_simulate(x, y, p, t, H, W, 2, polarity, 1000, -6.0, silent_v, rounding="correct")
+    ref = _S2_REFS[key]
     assert ref["band"] == 0
-    out = nsof_lib.simulate((x, y, p, t), version=2, slice_us=1000, active_v=-6.0, silent_v=0.0, polarity=polarity,
-                            sensor_size=(H, W), ctx=ctx)
+    out = nsof_lib.simulate((x, y, p, t), version=2, slice_us=1000, active_v=-6.0, silent_v=silent_v, polarity=polarity,
+                            sensor_size=(H, W), ctx=ctx, dense=dense)
     for k in ("w_final", "resistances", "w_final_b", "resistances_b"):
+        assert (k in out) == (k in ref), k
         if k in ref:
             assert _same(out[k], ref[k]), k
 
@@ -234,7 +255,7 @@ def test_row_bands_world_size_one_exact(nsof_lib, ctx, oracle):
 # and every <= 64.  Of those, the TILE WALK (k_tile_bucket + k_tile_frames) needs tile_ok:
 #     W % 16 == 0, row stride % 16 == 0, frame stride % 16 == 0, frames base 16-byte aligned, n_frames >= 2,
 #     fewer than 2^31 events, at most 15000 tiles of 1024 pixels, and the path not set to "copy_patch";
-# otherwise COPY + PATCH (k_frames_scatter_copy + k_frames_update_patch) per interval.
+# otherwise COPY + PATCH (k_frames_scatter_copy + k_update_list with the frame byte) per interval.
 
 def _stream(W, H, n_slices, seed, extra=(), gap=None):
     """Background events over n_slices ms plus `extra` (x, y, t) events; gap = (t0, t1): no events in [t0, t1)."""
