@@ -39,7 +39,7 @@ typedef enum nsof_status {
     NSOF_ESHAPE = -2,       /* prev/next shapes differ or are empty */
     NSOF_EDEVICE = -3,      /* HIP runtime / device failure, or no gfx950 device */
     NSOF_ENOMEM = -4,       /* host or device allocation failed */
-    NSOF_EUNSUPPORTED = -5  /* flags the reference never uses (USE_INITIAL_FLOW=4, FARNEBACK_GAUSSIAN=256) */
+    NSOF_EUNSUPPORTED = -5  /* parameters outside what is built: flags other than 0 / NSOF_FARNEBACK_GAUSSIAN, winsize 1, ... */
 } nsof_status;
 
 typedef struct nsof_ctx nsof_ctx;
@@ -124,6 +124,14 @@ int nsof_get_option(const nsof_ctx* ctx, int option, int* value);
  * for float frames -- and scalar loads elsewhere; the result does not depend on it).  The lone host pair takes ANY row
  * stride for 8-bit frames (its rows are copied) and the stage entry leaves an 8-bit row stride unchecked.  Otherwise a
  * violation, or an unknown pixel type, returns NSOF_EINVAL before anything is launched. */
+/* flags, cv2's values.  0: the box window (FarnebackUpdateFlow_Blur).  NSOF_FARNEBACK_GAUSSIAN (256): every iteration
+ * weights its window with a separable Gaussian of sigma 0.3 * (winsize / 2) (FarnebackUpdateFlow_GaussianBlur); winsize 2m
+ * and 2m + 1 then give the same flow, winsize up to 193.  Such a call runs k_update_matrices + k_gauss_blur_solve per
+ * iteration on every route, whatever the context's options; a work list of mixed shapes runs item by item.
+ * NSOF_USE_INITIAL_FLOW (4) is not implemented: it, and every other non-zero value, returns NSOF_EUNSUPPORTED before
+ * anything is launched. */
+enum { NSOF_USE_INITIAL_FLOW = 4, NSOF_FARNEBACK_GAUSSIAN = 256 };
+
 typedef enum nsof_pixel_type {
     NSOF_PIXEL_U8 = 0,
     NSOF_PIXEL_F32 = 1,
@@ -349,6 +357,10 @@ int nsof_stage_update_matrices(nsof_ctx* ctx, int n_pairs, const float* d_R, con
  * workspace); off, the per-pixel-sum kernel of the fast mode. */
 int nsof_stage_blur_solve(nsof_ctx* ctx, int n_pairs, const float* d_M, int width, int height,
                           int winsize, float* d_flow);
+/* The same stage with the Gaussian window of NSOF_FARNEBACK_GAUSSIAN (k_gauss_blur_solve): d_M [n_pairs][5][h][w] planar,
+ * d_flow [n_pairs][h][w][2] written; winsize 2..193. */
+int nsof_stage_gauss_blur_solve(nsof_ctx* ctx, int n_pairs, const float* d_M, int width, int height,
+                                int winsize, float* d_flow);
 /* One fused Farneback iteration (matrix update + blur + solve): flow_out = step(R, flow_in).  d_flow_in and
  * d_flow_out must not alias.  winsize 2..15; larger windows take the unfused pair above. */
 int nsof_stage_iterate(nsof_ctx* ctx, int n_pairs, const float* d_R, const float* d_flow_in, int width, int height,

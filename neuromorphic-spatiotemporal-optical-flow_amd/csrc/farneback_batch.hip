@@ -189,9 +189,10 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
     }
 
     // Items the work-list kernels cover: fused iteration available (window 2..15, >= 1 iteration, at least 2x2 px), and
-    // at most 255 strips wide (a job of k_iterate_x's table names its strip in 8 bits); wider items run on their own.
+    // at most 255 strips wide (a job of k_iterate_x's table names its strip in 8 bits); wider items run on their own.  The
+    // Gaussian window has no work-list kernel: every item of such a list runs on its own.
     auto het_params = [&](const nsof_pair_desc& d) {
-        return p.iterations >= 1 && nsof_iterate_supported(p.winsize, d.width, d.height) &&
+        return !(p.flags & NSOF_FARNEBACK_GAUSSIAN) && p.iterations >= 1 && nsof_iterate_supported(p.winsize, d.width, d.height) &&
                (d.width + NSOF_X_STRIP - 1) / NSOF_X_STRIP <= 255;
     };
     std::vector<int> het, rest;
@@ -213,7 +214,7 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
         // with (strip, item) jobs takes the small-batch form of the exact order
         long long jobs = 0;
         for (int j = 0; j < nh; j++) jobs += nsof_iterate_jobs(descs[het[j]].width, descs[het[j]].height);
-        const nsof_iter_form form = nsof_iterate_form(ctx, p.winsize, descs[het[0]].width, descs[het[0]].height, p.iterations, jobs);
+        const nsof_iter_form form = nsof_iterate_form(ctx, p.winsize, descs[het[0]].width, descs[het[0]].height, p.iterations, jobs, p.flags);
         const bool use_xj = form == NSOF_ITER_EXACT;   // k_iterate_x runs the list: it needs its job tables
         // Per level: the item table (sorted into size classes), then the fused kernel's job table (8 counts + 8 lists).
         long long strips0 = 0;   // strips of the full-resolution level = the most any level has

@@ -485,10 +485,13 @@ int nsof_check_farneback_params(nsof_ctx* ctx, int width, int height, double pyr
     if (poly_n < 1 || poly_n > NSOF_MAX_POLY_N)
         return nsof_set_error(ctx, poly_n < 1 ? NSOF_EINVAL : NSOF_EUNSUPPORTED, "poly_n=%d outside 1..%d", poly_n,
                               NSOF_MAX_POLY_N);
-    if (flags != 0)
+    if (flags != 0 && flags != NSOF_FARNEBACK_GAUSSIAN)
         return nsof_set_error(ctx, NSOF_EUNSUPPORTED,
-                              "flags=%d: OPTFLOW_USE_INITIAL_FLOW / OPTFLOW_FARNEBACK_GAUSSIAN are not implemented "
-                              "(the reference always passes flags=0)", flags);
+                              "flags=%d: OPTFLOW_USE_INITIAL_FLOW (4) is not implemented, and no bit other than 256 is known",
+                              flags);
+    if (flags && winsize / 2 > NSOF_GAUSS_MAX_M)
+        return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "winsize=%d too large for the Gaussian window (max %d)", winsize,
+                              2 * NSOF_GAUSS_MAX_M + 1);
     return NSOF_OK;
 }
 
@@ -582,7 +585,7 @@ extern "C" int nsof_stage_blur_solve(nsof_ctx* ctx, int n_pairs, const float* d_
 {
     if (!ctx || !d_M || !d_flow || n_pairs < 1 || width < 1 || height < 1 || winsize < 2) return NSOF_EINVAL;
     // the library's row-sum order (k_blur_colsum + k_blur_rowsolve) wherever the driver's form is exact
-    if (nsof_form_exact(nsof_iterate_form(ctx, winsize, width, height, 1, n_pairs * nsof_iterate_jobs(width, height)))) {
+    if (nsof_form_exact(nsof_iterate_form(ctx, winsize, width, height, 1, n_pairs * nsof_iterate_jobs(width, height), 0))) {
         const size_t need = (size_t)n_pairs * 5 * width * height * sizeof(double);
         if (int rc = ctx->ws.reserve(ctx, need)) return rc;
         return nsof_launch_blur_solve_exact(ctx, n_pairs, d_M, width, height, winsize, (double*)ctx->ws.p, d_flow);
@@ -590,12 +593,19 @@ extern "C" int nsof_stage_blur_solve(nsof_ctx* ctx, int n_pairs, const float* d_
     return nsof_launch_blur_solve(ctx, n_pairs, d_M, width, height, winsize, d_flow);
 }
 
+extern "C" int nsof_stage_gauss_blur_solve(nsof_ctx* ctx, int n_pairs, const float* d_M, int width, int height,
+                                           int winsize, float* d_flow)
+{
+    if (!ctx || !d_M || !d_flow || n_pairs < 1 || n_pairs > 65535 || width < 1 || height < 1 || winsize < 2) return NSOF_EINVAL;
+    return nsof_launch_gauss_blur_solve(ctx, n_pairs, d_M, width, height, winsize, d_flow);
+}
+
 extern "C" int nsof_stage_iterate(nsof_ctx* ctx, int n_pairs, const float* d_R, const float* d_flow_in, int width,
                                   int height, int winsize, float* d_flow_out)
 {
     if (!ctx || !d_R || !d_flow_in || !d_flow_out || d_flow_in == d_flow_out || n_pairs < 1 || width < 1 || height < 1)
         return NSOF_EINVAL;
-    const nsof_iter_form form = nsof_iterate_form(ctx, winsize, width, height, 1, n_pairs * nsof_iterate_jobs(width, height));
+    const nsof_iter_form form = nsof_iterate_form(ctx, winsize, width, height, 1, n_pairs * nsof_iterate_jobs(width, height), 0);
     if (!nsof_form_fused(form)) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "winsize %d not fused", winsize);
     const size_t plane = (size_t)width * height;
     if (form == NSOF_ITER_FAST)
@@ -629,7 +639,7 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 // Workspace of the uniform driver for B pairs: I [n_img][nk] f32 and R [n_img][5*nk] f32 (level images and
 // expansions: one slot that every level reuses, or one slot per level for the latency schedule `lat`), S = second flow
 // buffer [B][n0][2], M [B][5][n0] (the unfused forms and the small-batch form), V = column sums [B][5][n0] f64 (the
-// unfused and the small-batch exact forms).  Offsets in bytes, in that order.
+// unfused and the small-batch exact forms; the Gaussian form has none).  Offsets in bytes, in that order.
 struct Carve {
     std::vector<size_t> offI, offR;   // per level, within I / R
     size_t szI = 0, szR = 0, szS = 0, szM = 0, szV = 0;
@@ -679,7 +689,7 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     if (row_stride < (ptrdiff_t)width * px_bytes) return nsof_set_error(ctx, NSOF_EINVAL, "row_stride < width * %d", px_bytes);
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const nsof_iter_form form = nsof_iterate_form(ctx, winsize, width, height, iterations,
-                                                  n_pairs * nsof_iterate_jobs(width, height));
+                                                  n_pairs * nsof_iterate_jobs(width, height), flags);
     const int exact_chunk = 64;
     if (form == NSOF_ITER_UNFUSED_EXACT && (sequence || n_pairs > exact_chunk)) {
         // the exact order keeps 40 B/px of column sums (+ 20 B/px of matrices) in HBM: 64 pairs of 1920x1080 at a time
@@ -888,7 +898,8 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
             float* flow = fb[cur];
             for (int it = 0; it < iterations; it++) {
                 if ((rc = nsof_launch_update_matrices(ctx, n_pairs, R0, R1, 5 * nk, flow, wk, hk, dM))) return rc;
-                if (form == NSOF_ITER_UNFUSED_EXACT) rc = nsof_launch_blur_solve_exact(ctx, n_pairs, dM, wk, hk, winsize, dV, flow);
+                if (form == NSOF_ITER_UNFUSED_GAUSS) rc = nsof_launch_gauss_blur_solve(ctx, n_pairs, dM, wk, hk, winsize, flow);
+                else if (form == NSOF_ITER_UNFUSED_EXACT) rc = nsof_launch_blur_solve_exact(ctx, n_pairs, dM, wk, hk, winsize, dV, flow);
                 else rc = nsof_launch_blur_solve(ctx, n_pairs, dM, wk, hk, winsize, flow);
                 if (rc) return rc;
             }

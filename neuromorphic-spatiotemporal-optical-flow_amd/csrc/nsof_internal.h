@@ -261,6 +261,15 @@ int nsof_launch_blur_solve(nsof_ctx* ctx, int n_pairs, const float* M, int W, in
 // The same in the reference library's exact summation order; VT: n_pairs * 5 * W * H doubles of scratch.
 int nsof_launch_blur_solve_exact(nsof_ctx* ctx, int n_pairs, const float* M, int W, int H, int winsize, double* VT,
                                  float* flow);
+// FarnebackUpdateFlow_GaussianBlur (farneback_gauss.hip): separable Gaussian window + solve in one launch, flow in place.
+// Windows up to 2 * NSOF_GAUSS_LDS_MAX_M + 1 take the tiled LDS kernel, larger ones (up to 2 * NSOF_GAUSS_MAX_M + 1) a
+// slow per-pixel form.  The taps k[0..winsize/2] are formed on the host and passed by value.
+#define NSOF_GAUSS_LDS_MAX_M 16
+#define NSOF_GAUSS_MAX_M 96
+struct nsof_gauss_taps {
+    float k[NSOF_GAUSS_MAX_M + 1];
+};
+int nsof_launch_gauss_blur_solve(nsof_ctx* ctx, int n_pairs, const float* M, int W, int H, int winsize, float* flow);
 int nsof_launch_flow_upsample(nsof_ctx* ctx, int n_pairs, const float* src, int sw, int sh, float* dst, int dw,
                               int dh, float mul);
 #define NSOF_PYR_SEL(ctx, fn, ...) ((ctx)->opt_pyr_fma ? fn##_fma(ctx, __VA_ARGS__) : fn(ctx, __VA_ARGS__))
@@ -298,12 +307,15 @@ enum nsof_iter_form {
     NSOF_ITER_EXACT_LAT,       // the same order for small batches: k_update_matrices + k_lat_colsum + k_lat_rowscan
     NSOF_ITER_UNFUSED_FAST,    // k_update_matrices + k_blur_solve
     NSOF_ITER_UNFUSED_EXACT,   // k_update_matrices + k_blur_colsum + k_blur_rowsolve
+    NSOF_ITER_UNFUSED_GAUSS,   // k_update_matrices + k_gauss_blur_solve (flags & NSOF_FARNEBACK_GAUSSIAN)
 };
 // The form every iteration of a call takes, at every level: W x H is level 0, jobs the call's nsof_iterate_jobs summed
 // over its pairs.  The exact order is fused only where it iterates; calls of at most NSOF_OPT_SMALL_BATCH_JOBS jobs take
-// its small-batch form.
-static inline nsof_iter_form nsof_iterate_form(const nsof_ctx* ctx, int winsize, int W, int H, int iterations, long long jobs)
+// its small-batch form.  The Gaussian window (flags, as the entry points take them) has one form, whatever the rest says.
+static inline nsof_iter_form nsof_iterate_form(const nsof_ctx* ctx, int winsize, int W, int H, int iterations, long long jobs,
+                                               int flags)
 {
+    if (flags & NSOF_FARNEBACK_GAUSSIAN) return NSOF_ITER_UNFUSED_GAUSS;
     const bool fused = nsof_iterate_supported(winsize, W, H);
     if (!ctx->opt_exact_rowsums) return fused ? NSOF_ITER_FAST : NSOF_ITER_UNFUSED_FAST;
     if (!fused || iterations < 1) return NSOF_ITER_UNFUSED_EXACT;

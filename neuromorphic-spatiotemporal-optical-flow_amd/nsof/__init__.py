@@ -14,7 +14,7 @@ All arithmetic runs in libnsof.so (HIP, gfx950).  No fallbacks.
 """
 from .errors import NsofError, error  # noqa: F401
 from .context import Context, default_context  # noqa: F401
-from .farneback import (FarnebackParams, StreamPool, calcOpticalFlowFarneback, effective_levels, farneback_batch,  # noqa: F401
+from .farneback import (OPTFLOW_FARNEBACK_GAUSSIAN, OPTFLOW_USE_INITIAL_FLOW, FarnebackParams, StreamPool, calcOpticalFlowFarneback, effective_levels, farneback_batch,  # noqa: F401
                         farneback_many, farneback_pairs, farneback_pairs_16_dev, farneback_pairs_dev,
                         farneback_pairs_f32_dev, farneback_roi_sequence_16_dev, farneback_roi_sequence_dev,
                         farneback_roi_sequence_f32_dev,

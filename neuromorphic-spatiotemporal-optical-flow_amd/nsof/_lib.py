@@ -79,6 +79,7 @@ SIGNATURES = {
     "nsof_stage_recip": (_i, [_vp, C.c_longlong, _vp, _vp, _vp]),
     "nsof_stage_update_matrices": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp]),
     "nsof_stage_blur_solve": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
+    "nsof_stage_gauss_blur_solve": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
     "nsof_stage_iterate": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "nsof_stage_iterate_upsample": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp]),
     "nsof_stage_flow_upsample": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _d]),

@@ -20,6 +20,12 @@ from .context import Context, default_context, dev_ptr
 from .errors import NsofValueError
 
 
+# cv2's flag values.  The Gaussian window is built (every entry passes ``flags`` to the library as it is); an initial flow is
+# not: the library refuses it, and every other non-zero value, with NSOF_EUNSUPPORTED.
+OPTFLOW_USE_INITIAL_FLOW = 4
+OPTFLOW_FARNEBACK_GAUSSIAN = 256
+
+
 @dataclass(frozen=True)
 class FarnebackParams:
     """Keyword set of the reference's ``farneback_params`` dict (optical_flow_seg.py:73-81)."""
