@@ -497,6 +497,36 @@ int nsof_accum_block_current_dev(nsof_accum* acc, int which, int64_t snapshot, i
  * of dt/n_sub_steps.  w_out [H][W]; res_out [n_frames][H][W] (initial array, then one snapshot per pair). */
 int nsof_accum_frames_f64(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
                           int n_sub_steps, double th1, double th2, double* w_out, double* res_out);
+/* The same run on DEVICE arrays in ONE launch (one thread per grid pixel walks every frame pair), asynchronous on the
+ * context's stream, nothing copied: d_imgs [n_frames][H][W]; d_w [H][W]; d_res [n_frames][H][W], slice 0 the initial array
+ * and slice f + 1 the state after pair (f, f + 1); d_current (may be NULL) [n_frames - 1][H][W], d_current[f] = v_ds /
+ * d_res[f + 1] as an IEEE double division -- the device current of a grid that already is the gating map, the layout
+ * nsof_roi_from_surface_dev reads.  d_w and d_res equal nsof_accum_frames_f64's outputs bit for bit. */
+int nsof_accum_frames_f64_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
+                              int n_sub_steps, double th1, double th2, double v_ds, double* d_w, double* d_res,
+                              double* d_current);
+/* compress_image of the same script (:111-121) for a stack of 8-bit DEVICE frames: imresize(im2double(frame), [out_h
+ * out_w], 'lanczos3') of n_frames frames into d_out [n_frames][out_h][out_w] (DEVICE, dense float64).  d_frames points
+ * at the first pixel of the region to compress -- a crop is a pointer offset plus width and height -- with row_stride and
+ * frame_stride in bytes under the layout rule above.  wts_y / ind_y [out_h][taps_y] and wts_x / ind_x [out_w][taps_x] are
+ * HOST tables: per output sample its tap weights and the mirrored 0-based source indices of the taps
+ * (nsof_lanczos3_contributions, or the Python mirror's nsof.frames._contributions); they are copied through the
+ * context's table buffer and not retained.  Arithmetic, order included: im2double(v) = double(v) / 255.0; the axis with
+ * the smaller scale goes first (out_h * width <= out_w * height: rows first); every output starts at 0.0 and takes its
+ * taps left to right, acc = acc + w[k] * v[k], the product rounded before the sum; the intermediate is float64.  With the
+ * mirror's tables the result equals the mirror's bit for bit.  Needs 1 <= out_w <= width and 1 <= out_h <= height: a scale
+ * above 1 is NSOF_EUNSUPPORTED; a null pointer, n_frames < 1, a tap count < 1, an empty output, a row stride below the
+ * width or a source index outside the frame NSOF_EINVAL -- all before anything is launched.  Asynchronous on the
+ * context's stream (it waits only for its own previous table upload, or to grow a buffer). */
+int nsof_frames_compress_u8_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames, ptrdiff_t row_stride,
+                                ptrdiff_t frame_stride, int width, int height, int out_w, int out_h, const double* wts_y,
+                                const int32_t* ind_y, int taps_y, const double* wts_x, const int32_t* ind_x, int taps_x,
+                                double* d_out);
+/* The tap table of one axis of that resize, host only (the `contributions` routine of imresize.m as nsof.frames states
+ * it): *taps = the taps per output sample (the columns that carry a non-zero weight for some output); with wts != NULL
+ * also wts / ind [out_len][*taps] (cap_taps >= *taps, else NSOF_EINVAL), indices mirrored at both image ends as often as
+ * a window wider than the image needs.  With wts == NULL only the count. */
+int nsof_lanczos3_contributions(int in_len, int out_len, double* wts, int32_t* ind, int cap_taps, int* taps);
 /* slice_indices() of event_mem_sim.py:78-83 on a HOST timestamp array: returns the number
  * of bounds and fills idx (if not NULL) with up to cap entries. */
 int64_t nsof_accum_slice_bounds(const int64_t* t, int64_t n, int64_t slice_us, int64_t* idx, int64_t cap);

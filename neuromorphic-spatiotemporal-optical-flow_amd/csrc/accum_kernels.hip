@@ -413,19 +413,48 @@ __device__ __forceinline__ double frame_update(double w, double V, double dt)
     return nw < 0 ? 0 : (nw > 1 ? 1 : nw);
 }
 
+// One frame pair of one grid pixel: the state after n_sub sub-steps under the drive voltage of |a - b|.
+__device__ __forceinline__ double frame_pair(double a, double b, double ww, double dts, int n_sub, double th1, double th2)
+{
+    const double d = fabs(a * 256 - b * 256);
+    double V = d > th1 ? (d + 4) * 0.75 : (d - 5.5) * 0.6;   // func2 == func3 in the source
+    V = V > 0 ? -(0.3 * V + 0) : (V < 0 ? -(3 * V + -3) : 0.0);
+    for (int s = 0; s < n_sub; s++) ww = frame_update(ww, V, dts);
+    return ww;
+}
+
 __global__ __launch_bounds__(64) void k_frame_step(const double* __restrict__ a, const double* __restrict__ b,
                                                     double* __restrict__ w, double* __restrict__ res, size_t n,
                                                     double dts, int n_sub, double th1, double th2, double lambda)
 {
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
-    const double d = fabs(a[i] * 256 - b[i] * 256);
-    double V = d > th1 ? (d + 4) * 0.75 : (d - 5.5) * 0.6;   // func2 == func3 in the source
-    V = V > 0 ? -(0.3 * V + 0) : (V < 0 ? -(3 * V + -3) : 0.0);
-    double ww = w[i];
-    for (int s = 0; s < n_sub; s++) ww = frame_update(ww, V, dts);
+    const double ww = frame_pair(a[i], b[i], w[i], dts, n_sub, th1, th2);
     w[i] = ww;
     res[i] = RON / exp(-lambda * (1 - ww));
+}
+
+// The whole run in one launch: one thread per grid pixel walks every frame pair (a pixel's pairs are one dependent
+// chain, the pixels are independent).  imgs [n_frames][n]; res [n_frames][n], slice 0 = r0 (the initial resistance, formed
+// on the host as nsof_accum_frames_f64 forms it); current [n_frames - 1][n] = v_ds / res[f + 1] (optional).
+__global__ __launch_bounds__(64) void k_frames_run(const double* __restrict__ imgs, int n_frames, double* __restrict__ w,
+                                                    double* __restrict__ res, double* __restrict__ current, size_t n,
+                                                    double dts, int n_sub, double th1, double th2, double lambda, double r0,
+                                                    double v_ds)
+{
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    double ww = 0.5, b = imgs[i];
+    res[i] = r0;
+    for (int f = 0; f + 1 < n_frames; f++) {
+        const double a = b;
+        b = imgs[(size_t)(f + 1) * n + i];
+        ww = frame_pair(a, b, ww, dts, n_sub, th1, th2);
+        const double r = RON / exp(-lambda * (1 - ww));
+        res[(size_t)(f + 1) * n + i] = r;
+        if (current) current[(size_t)f * n + i] = v_ds / r;
+    }
+    w[i] = ww;
 }
 
 // Temporal-prior surface as an 8-bit frame.
@@ -1362,4 +1391,24 @@ extern "C" int nsof_accum_frames_f64(nsof_ctx* ctx, const double* imgs, int n_fr
         if (e != hipSuccess) rc = nsof_set_error(ctx, NSOF_EDEVICE, "frame accumulator: %s", hipGetErrorString(e));
     }
     return rc;
+}
+
+// The same run on DEVICE arrays, one launch, nothing copied or synchronised: d_imgs [n_frames][H][W], d_w [H][W],
+// d_res [n_frames][H][W], d_current [n_frames - 1][H][W] = v_ds / d_res[f + 1] (may be NULL).  Same w and res as
+// nsof_accum_frames_f64, bit for bit: the same device functions in the same order per pixel.
+extern "C" int nsof_accum_frames_f64_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
+                                         int n_sub_steps, double th1, double th2, double v_ds, double* d_w, double* d_res,
+                                         double* d_current)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!d_imgs || !d_w || !d_res || n_frames < 1 || height < 1 || width < 1 || n_sub_steps < 1)
+        return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
+    const size_t npx = (size_t)height * width;
+    if (npx > 0xffffffffull - 63) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "grid of %zu pixels: too large for one launch", npx);
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    const double lambda = std::log(ROFF / RON);
+    hipLaunchKernelGGL(k_frames_run, dim3((unsigned)((npx + 63) / 64)), dim3(64), 0, ctx->stream, d_imgs, n_frames, d_w, d_res,
+                       d_current, npx, dt / n_sub_steps, n_sub_steps, th1, th2, lambda, RON / std::exp(-lambda * 0.5), v_ds);
+    NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
 }

@@ -374,6 +374,31 @@ def simulate_frames(compressed_images, dt=0.0005, n_sub_steps=1000, th1=0.7, th2
     return w, res
 
 
+def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, v_ds=1.0, *, ctx=None):
+    """``simulate_frames`` on a float64 CUDA tensor [n][H][W] (``frames.process_images_dev``'s output) in one launch
+    (``nsof_accum_frames_f64_dev``): returns ``(w [H][W], resistances [n][H][W], current [n-1][H][W])`` as float64 CUDA
+    tensors -- ``w`` and ``resistances`` equal ``simulate_frames`` bit for bit, ``current[f] = v_ds / resistances[f + 1]``
+    is the device current after pair (f, f+1), the layout ``gating.roi_from_surface_dev`` reads.  Nothing is copied;
+    asynchronous on the context's stream."""
+    torch = _torch()
+    if not isinstance(compressed, torch.Tensor) or not compressed.is_cuda:
+        raise NsofValueError("simulate_frames_dev: a CUDA tensor expected", _lib.NSOF_EINVAL)
+    if compressed.dtype != torch.float64:
+        raise NsofValueError(f"simulate_frames_dev: float64 expected (got {compressed.dtype})", _lib.NSOF_EINVAL)
+    if compressed.dim() != 3 or compressed.shape[0] < 1 or not compressed.is_contiguous():
+        raise NsofValueError("simulate_frames_dev: contiguous [n][H][W] frames expected", _lib.NSOF_ESHAPE)
+    ctx = ctx or default_context()
+    n, H, W = (int(v) for v in compressed.shape)  # noqa: N806
+    dev = compressed.device
+    w = torch.empty((H, W), dtype=torch.float64, device=dev)
+    res = torch.empty((n, H, W), dtype=torch.float64, device=dev)
+    cur = torch.empty((n - 1, H, W), dtype=torch.float64, device=dev)
+    ctx.check(ctx._lib.nsof_accum_frames_f64_dev(ctx.ptr, dev_ptr(compressed), n, H, W, float(dt), int(n_sub_steps),
+                                                 float(th1), float(th2), float(v_ds), dev_ptr(w), dev_ptr(res),
+                                                 dev_ptr(cur) if n > 1 else None), "simulate_frames_dev")
+    return w, res, cur
+
+
 def _save_outputs(prefix, out, version, slice_us, polarity, h5_path):
     """File set of event_mem_sim.py:289-322 (npz keys ``w_final`` / ``resistances``; json.gz metadata)."""
     np.savez_compressed(prefix.with_suffix(f".V{version}.npz"), w_final=out["w_final"],

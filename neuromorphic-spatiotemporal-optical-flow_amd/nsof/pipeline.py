@@ -429,7 +429,8 @@ def run_prediction(frames_bgr, mem_state, cfg, names=None, csv_path=None, merge_
 
 def _sequence_flows(frames_bgr, mem_state, cfg, with_original, max_rects, ctx, what):
     """The front half of the sequence experiments in HBM: checks, gray frames (``gray_u8_dev``, RGB2GRAY as the scripts
-    convert), the device gating table of slices OFFSET .. OFFSET+n-2 (one launch, ``gating.roi_from_surface_dev``;
+    convert), the gating slices (a host ``(rows, cols, T)`` stack goes up; a float64 CUDA tensor [T][rows][cols], e.g.
+    ``gating_stack_from_frames_dev``'s, is sliced where it is), the device gating table of slices OFFSET .. OFFSET+n-2 (one launch, ``gating.roi_from_surface_dev``;
     regrown once when a map has more than ``max_rects`` components), the ROI flows of pairs 0 .. n-3 from that table
     (``farneback_roi_sequence_dev``, gated as ``cfg.bug_compatible`` says) and, with ``with_original``, the full-frame
     flows (``farneback_sequence``).  Returns ``(gray, counts, rtab, rects, flow_mem, flow_orig, gate_frame)``: the gray
@@ -445,15 +446,23 @@ def _sequence_flows(frames_bgr, mem_state, cfg, with_original, max_rects, ctx, w
     n, H, W = (int(v) for v in frames_bgr.shape[:3])  # noqa: N806
     if n < 3:
         raise ValueError(f"{what}: {n} frames; the experiment needs at least 3")
-    rows, cols = int(mem_state.shape[0]), int(mem_state.shape[1])
+    on_device = isinstance(mem_state, torch.Tensor)   # [T][rows][cols] in HBM; a host stack is (rows, cols, T)
+    if on_device and (not mem_state.is_cuda or mem_state.device != frames_bgr.device or mem_state.dtype != torch.float64
+                      or mem_state.dim() != 3 or not mem_state.is_contiguous()):
+        raise predict.NsofValueError(f"{what}: a gating stack given as a tensor must be a contiguous float64 "
+                                     f"[T][rows][cols] tensor on {frames_bgr.device}")
+    rows, cols, slices = (int(mem_state.shape[i]) for i in ((1, 2, 0) if on_device else (0, 1, 2)))
     if rows > H // cfg.MEMSIZE or cols > W // cfg.MEMSIZE:
         raise ValueError(f"gating map {rows}x{cols} larger than the {H // cfg.MEMSIZE}x{W // cfg.MEMSIZE} transition picture")
-    if mem_state.shape[2] < cfg.OFFSET + n - 1:
-        raise ValueError(f"the stack has {mem_state.shape[2]} slices; {n} frames need OFFSET + {n - 1}")
+    if slices < cfg.OFFSET + n - 1:
+        raise ValueError(f"the stack has {slices} slices; {n} frames need OFFSET + {n - 1}")
     gf = 0 if cfg.bug_compatible else 1
     dev = frames_bgr.device
-    cur = torch.from_numpy(np.ascontiguousarray(np.moveaxis(np.asarray(mem_state)[:, :, cfg.OFFSET:cfg.OFFSET + n - 1], 2, 0),
-                                                np.float64)).to(dev)
+    if on_device:
+        cur = mem_state[cfg.OFFSET:cfg.OFFSET + n - 1]   # a view: the slices are read where they are
+    else:
+        cur = torch.from_numpy(np.ascontiguousarray(np.moveaxis(np.asarray(mem_state)[:, :, cfg.OFFSET:cfg.OFFSET + n - 1], 2, 0),
+                                                    np.float64)).to(dev)
     gray = torch.empty((n - 1, H, W), dtype=torch.uint8, device=dev)
     flow_mem = torch.empty((n - 2, H, W, 2), dtype=torch.float32, device=dev)   # zero-filled by the ROI flow call
     flow_orig = torch.empty_like(flow_mem) if with_original else None
@@ -474,6 +483,38 @@ def _sequence_flows(frames_bgr, mem_state, cfg, with_original, max_rects, ctx, w
                            frame_stride=int(gray.stride(0)), ctx=ctx)
     rects = [lists[k + gf] for k in range(n - 2)]
     return gray, counts, rtab, rects, flow_mem, flow_orig, gf
+
+
+def gating_stack_from_frames_dev(frames_bgr, cfg, m=None, n=None, region=None, ctx=None, **sim):
+    """The gating stack of a video, simulated in HBM: ``frames_bgr`` uint8 CUDA tensor [k][H][W][3] (BGR as ``cv2.imread``
+    gives them) -> gray frames (``gray_u8_dev``, the RGB2GRAY the flow stage converts with) -> Lanczos-3 grids of
+    ``region`` (``(region_ul, region_lr)``, MATLAB corners; the whole frame by default) compressed by ``m`` columns and ``n``
+    rows per cell (``frames.process_images_dev``; both default to ``cfg.MEMSIZE``, so the grid is the transition picture)
+    -> the array run over all pairs in one launch (``simulate_frames_dev``; ``sim`` passes ``dt``, ``n_sub_steps``,
+    ``th1``, ``th2``, ``v_ds`` on).  Returns the device currents, float64 CUDA tensor [k-1][rows][cols]: slice f is the
+    array after pair (f, f+1) -- what ``prediction_sequence_dev`` / ``segmentation_sequence_dev`` take as ``mem_state``
+    without a copy.  Equal to ``frames.process_images`` -> ``simulate_frames`` -> ``v_ds / resistances[1:]`` on the host gray
+    frames, bit for bit.  Nothing visits the host; synchronises at the end (the intermediates are released)."""
+    import torch
+
+    from . import frames as fr
+    from . import predict
+    from .accumulator import simulate_frames_dev
+    from .context import default_context
+    predict._u8_frames(frames_bgr, "gating_stack_from_frames_dev")
+    if frames_bgr.dim() != 4 or frames_bgr.shape[3] != 3 or frames_bgr.shape[0] < 2:
+        raise predict.NsofValueError("gating_stack_from_frames_dev: at least two uint8 [k][H][W][3] frames expected")
+    ctx = ctx or default_context()
+    k, H, W = (int(v) for v in frames_bgr.shape[:3])  # noqa: N806
+    gray = torch.empty((k, H, W), dtype=torch.uint8, device=frames_bgr.device)
+    torch.cuda.synchronize(frames_bgr.device)
+    for i in range(k):
+        predict.gray_u8_dev(frames_bgr[i], gray[i], "RGB2GRAY", ctx=ctx)
+    ul, lr = region if region is not None else (None, None)
+    grids = fr.process_images_dev(gray, cfg.MEMSIZE if m is None else m, cfg.MEMSIZE if n is None else n, ul, lr, ctx=ctx)
+    cur = simulate_frames_dev(grids, ctx=ctx, **sim)[2]
+    ctx.synchronize()
+    return cur
 
 
 def _experiment_boxes(rects, cfg, merge_flag, frame_hw):
