@@ -398,12 +398,34 @@ const char* nsof_kernel_name(int kernel_id);
 /* ---- stage 1: synaptic accumulator ---------------------------------------------------- */
 typedef struct nsof_accum nsof_accum;
 
-/* Device constants follow event_mem_sim.py:20-34 (PARAMS, DT=5e-4, THETA_EVENTS=1,
- * REFRACTORY_US=800).  scheme: 1 = boxcar window, 2 = DC bias + event overlay (:208-286).
+/* Device constants default to event_mem_sim.py:20-34 (PARAMS, DT=5e-4, REFRACTORY_US=800; nsof_accum_create_p takes
+ * others); THETA_EVENTS=1 is fixed.  scheme: 1 = boxcar window, 2 = DC bias + event overlay (:208-286).
  * polarity_split: scheme 2 only -- 1 = 'split' (ON p==1 -> array A, OFF p==0 -> array B),
  * 0 = 'magnitude' (one array). */
 int nsof_accum_create(nsof_ctx* ctx, int height, int width, int scheme, int polarity_split,
                       float active_v, float silent_v, nsof_accum** out);
+/* The device model as an argument, as the reference takes it (update_state(w, V, p=PARAMS, dt=DT), resistance_exp(w,
+ * p=PARAMS); REFRACTORY_US is the module knob simulate reads).  The entries above and below that take no parameters are
+ * the _p entries with NULL, i.e. with the values nsof_accum_default_params returns (the fitted device of the paper).
+ * float32 paths: every field is rounded to float32 once on the host, as NumPy rounds the Python scalars next to a
+ * float32 array; dw/dt = (k * (V/v0 - 1) ** alpha) * (1 - w*s) ** b in that order, each power evaluated in double from the
+ * float32 operands and rounded once, alpha == 1 calling no power; a base <= 0 or non-finite follows np.power on float32
+ * operands (integer exponents keep the sign for odd ones).  float64 frame path: the same fields as doubles.
+ * Refused with NSOF_EINVAL before anything is launched: a non-finite field (or one that is not finite as float32),
+ * !(voff < 0 < von), son or soff outside [0, 1], Ron <= 0 or Roff <= 0, wini outside [0, 1], dt <= 0, refractory_us < 0.
+ * Not a parameter: scheme 1's event threshold THETA_EVENTS stays 1 (a count threshold needs per-slice counters instead
+ * of mask bits); per-pixel parameter maps and the linear resistance map are not supported either. */
+typedef struct nsof_accum_params {      /* keys of PARAMS (event_mem_sim.py:20-27); won / woff are read by nothing and not carried */
+    double alphaoff, alphaon, voff, von, koff, kon, son, soff, bon, boff, Ron, Roff, wini;
+    double dt;                          /* DT, seconds */
+    int64_t refractory_us;              /* REFRACTORY_US */
+} nsof_accum_params;
+void nsof_accum_default_params(nsof_accum_params* out);
+/* nsof_accum_create for an array of the given device (params NULL = defaults); the model is fixed for the accumulator's life
+ * and every update form, surface, snapshot, block current and reset (w = wini) of it uses it. */
+int nsof_accum_create_p(nsof_ctx* ctx, int height, int width, int scheme, int polarity_split, float active_v, float silent_v,
+                        const nsof_accum_params* params, nsof_accum** out);
+int nsof_accum_get_params(const nsof_accum* acc, nsof_accum_params* out);
 void nsof_accum_destroy(nsof_accum* acc);
 /* With silent_v in the dead zone an idle pixel is a bit-exact no-op, so two updates give the same state: the event-pixel
  * update (only touched pixels, groups of 32 slices) and the every-pixel pass (scheme 1: groups of 64 slices, no lists).
@@ -411,7 +433,7 @@ void nsof_accum_destroy(nsof_accum* acc);
  * 1280x720 0.39 vs 0.75-0.89 ms per 30 surface frames, 3840x2160 0.97 vs 1.21 ms), the event-pixel update beyond and in
  * scheme 2; > 0 = always the every-pixel pass (the roofline run); < 0 = the event-pixel update wherever it is exact. */
 int nsof_accum_set_dense(nsof_accum* acc, int force_dense);
-/* Reset w to wini (0.5) and the refractory maps to 0. */
+/* Reset w to the model's wini (default 0.5) and the refractory maps to 0. */
 int nsof_accum_reset(nsof_accum* acc);
 /* Advance by n_slices time slices.  Events are HOST arrays (x,y int16; p int8; t int64 us,
  * sorted) as in the /CD/events group (event_mem_sim.py:69-75); slice_bounds has
@@ -471,12 +493,17 @@ int nsof_accum_write_state(nsof_accum* acc, int which, const float* w_in, const 
                            int64_t slice_counter);
 /* Dense element-wise update_state on DEVICE arrays (event_mem_sim.py:40-57). */
 int nsof_accum_update_state_dev(nsof_ctx* ctx, const float* d_w, const float* d_V, float* d_out, size_t n);
+/* update_state(w, V, p, dt): dt is params->dt. */
+int nsof_accum_update_state_p_dev(nsof_ctx* ctx, const nsof_accum_params* params, const float* d_w, const float* d_V,
+                                  float* d_out, size_t n);
 /* bincount_2d(x, y, H, W) of event_mem_sim.py:100-104: events per pixel, int32 [H][W].  HOST arrays in and out;
  * events outside the sensor are an error (np.bincount would raise or grow the array). */
 int nsof_accum_bincount_2d(nsof_ctx* ctx, const int16_t* x, const int16_t* y, size_t n, int height, int width,
                            int32_t* counts_out);
 /* Dense resistance_exp on DEVICE arrays (event_mem_sim.py:60-63). */
 int nsof_accum_resistance_dev(nsof_ctx* ctx, const float* d_w, float* d_out, size_t n);
+/* resistance_exp(w, p). */
+int nsof_accum_resistance_p_dev(nsof_ctx* ctx, const nsof_accum_params* params, const float* d_w, float* d_out, size_t n);
 /* Copy state to HOST: which = 0 (array A) or 1 (array B, split mode). */
 int nsof_accum_read_w(nsof_accum* acc, int which, float* w_out);
 int nsof_accum_read_resistance(nsof_accum* acc, int which, float* r_out);
@@ -497,6 +524,12 @@ int nsof_accum_block_current_dev(nsof_accum* acc, int which, int64_t snapshot, i
  * of dt/n_sub_steps.  w_out [H][W]; res_out [n_frames][H][W] (initial array, then one snapshot per pair). */
 int nsof_accum_frames_f64(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
                           int n_sub_steps, double th1, double th2, double* w_out, double* res_out);
+/* simulate_memristor_array(..., params): the same run for the given device (NULL = defaults), the fields read as doubles;
+ * the array starts at wini, lambda = ln(Roff / Ron).  dt stays the argument it is: params->dt and params->refractory_us
+ * are checked with the rest of the set and not read. */
+int nsof_accum_frames_f64_p(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
+                            int n_sub_steps, double th1, double th2, const nsof_accum_params* params, double* w_out,
+                            double* res_out);
 /* The same run on DEVICE arrays in ONE launch (one thread per grid pixel walks every frame pair), asynchronous on the
  * context's stream, nothing copied: d_imgs [n_frames][H][W]; d_w [H][W]; d_res [n_frames][H][W], slice 0 the initial array
  * and slice f + 1 the state after pair (f, f + 1); d_current (may be NULL) [n_frames - 1][H][W], d_current[f] = v_ds /
@@ -505,6 +538,9 @@ int nsof_accum_frames_f64(nsof_ctx* ctx, const double* imgs, int n_frames, int h
 int nsof_accum_frames_f64_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
                               int n_sub_steps, double th1, double th2, double v_ds, double* d_w, double* d_res,
                               double* d_current);
+int nsof_accum_frames_f64_p_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
+                                int n_sub_steps, double th1, double th2, double v_ds, const nsof_accum_params* params,
+                                double* d_w, double* d_res, double* d_current);
 /* compress_image of the same script (:111-121) for a stack of 8-bit DEVICE frames: imresize(im2double(frame), [out_h
  * out_w], 'lanczos3') of n_frames frames into d_out [n_frames][out_h][out_w] (DEVICE, dense float64).  d_frames points
  * at the first pixel of the region to compress -- a crop is a pointer offset plus width and height -- with row_stride and

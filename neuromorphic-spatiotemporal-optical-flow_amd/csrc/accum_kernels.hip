@@ -13,6 +13,9 @@
 //    pixels touched by events are visited (compacted list built by the scatter kernel).
 //  * Scheme 2's refractory rule couples consecutive slices through next_ok, but per pixel only:
 //    one scatter per group as in scheme 1, the eligibility walk inside the fused update (RefrTab).
+//  * The device model (PARAMS, DT, REFRACTORY_US of the reference) is an argument of the accumulator (nsof_accum_params):
+//    float32 fields by value in the kernel arguments, the fitted device of the paper as a compile-time instantiation of
+//    the hot kernels (DevF, fitted_f below).
 //  * pow/exp go through double precision so that the float32 result is the correctly
 //    rounded one: equal to it on every state in [0, 1] outside the ~3e-7 of inputs that lie
 //    within 2^-43 of a rounding midpoint, and on those too as measured (tests/test_accum_cr_gpu.py;
@@ -29,15 +32,48 @@
 
 namespace {
 
-// event_mem_sim.py:20-34
-constexpr float VOFF = (float)-0.2, VON = (float)0.1;
-constexpr float KOFF = (float)51.03, KON = (float)-2.91;
-constexpr float SON = (float)0.2, SOFF = (float)0.8;
-constexpr float BON = (float)-5.12, BOFF = (float)3.10;
-constexpr float DT = (float)5e-4;
-constexpr double RON = 163305.0, ROFF = 2104377.0;
-constexpr long long REFRACTORY_US = 800;
-constexpr float WINI = 0.5f;
+// The device model (PARAMS, DT of event_mem_sim.py:20-30) as the float32 kernels take it: every field of nsof_accum_params
+// rounded to float32 ONCE on the host -- NumPy does the same to the Python scalars of PARAMS next to a float32 array -- and
+// neg_lam = (float)(-ln(Roff / Ron)), the logarithm taken in double as np.log takes it.  Passed BY VALUE in the kernel
+// arguments: uniform, so the fields sit in SGPRs; no __constant__ symbol is written per call and no pixel loads anything
+// for them, and two accumulators with different devices run back to back on one context.
+struct DevF {
+    float voff, von, koff, kon, son, soff, bon, boff, alphaoff, alphaon, dt, ron, neg_lam;
+};
+// The same model for the float64 frame-driven path; lambda = ln(Roff / Ron).
+struct DevD {
+    double voff, von, koff, kon, son, soff, bon, boff, alphaoff, alphaon, ron, lambda, wini;
+};
+// The fitted device of the paper (event_mem_sim.py:20-34) as compile-time constants.  The hot kernels -- the fused updates,
+// the tile walk, the float64 frame loop -- are instantiated twice: FITTED takes an empty argument and folds these constants, so
+// the default path runs the code it ran before the parameters became arguments (same bits, same time: measured, a run-time
+// model cost the launch-bound scheme-2 groups 1.5-2.5 %); the other instantiation reads the argument.  NULL or default
+// parameters are routed to FITTED (Model::fitted).
+__host__ __device__ constexpr DevF fitted_f()
+{
+    return DevF{(float)-0.2, (float)0.1, (float)51.03, (float)-2.91, (float)0.2, (float)0.8, (float)-5.12, (float)3.10,
+                1.f, 1.f, (float)5e-4, 163305.f, -0x1.473018p+1f /* (float)-ln(2104377 / 163305) */};
+}
+__host__ __device__ constexpr DevD fitted_d()
+{
+    return DevD{-0.2, 0.1, 51.03, -2.91, 0.2, 0.8, -5.12, 3.10, 1.0, 1.0, 163305.0, 0.0 /* lambda: never read, see FrameArg */, 0.5};
+}
+struct NoModel {};
+template <bool FITTED>
+using ModelArg = std::conditional_t<FITTED, NoModel, DevF>;
+__device__ __forceinline__ DevF model_arg(const DevF& p) { return p; }
+__device__ __forceinline__ DevF model_arg(NoModel) { return fitted_f(); }
+// The float64 frame loop: lambda = ln(Roff / Ron) is formed on the host in either case (std::log is no constant expression).
+struct FittedD { double lambda; };
+template <bool FITTED>
+using FrameArg = std::conditional_t<FITTED, FittedD, DevD>;
+__device__ __forceinline__ DevD frame_arg(const DevD& p) { return p; }
+__device__ __forceinline__ DevD frame_arg(FittedD a)
+{
+    DevD p = fitted_d();
+    p.lambda = a.lambda;
+    return p;
+}
 constexpr int MAX_GROUP = 32;
 
 // x ** b for the float32 state update, evaluated in double and rounded once (NumPy's float32 power is accurate to
@@ -85,71 +121,94 @@ __device__ __forceinline__ double exp_small(double y)   // |y| < 700
 }
 __device__ __forceinline__ float pow_f32(float x, float b)
 {
-    // a state outside [0,1] handed to the element-wise entry point can make x <= 0: NumPy gives nan for a finite
-    // negative base, 0 or inf for a zero base, and for the base -inf (w = +inf) inf or 0 like the base +inf (the
-    // exponents are not odd integers)
+    // A state outside [0,1] handed to the element-wise entry point can make x <= 0 or non-finite; the result then follows
+    // np.power on float32 operands (C99 powf): x ** 0 = 1 for every x, NaN included; a finite negative base gives nan for a
+    // non-integer exponent and (-1)^b |x|^b for an integer one; the bases 0 and -inf give 0 or inf by the sign of b, and
+    // carry the base's sign for an odd integer b.  (A float of magnitude >= 2^24 is an even integer.)
     if (!(x > 0.f)) {
-        if (x == 0.f || x == -__builtin_inff()) return b > 0.f ? (x == 0.f ? 0.f : __builtin_inff()) : (x == 0.f ? __builtin_inff() : 0.f);
-        return x < 0.f ? __builtin_nanf("") : x;
+        if (b == 0.f) return 1.f;
+        if (x != x) return x;
+        const bool whole = truncf(b) == b, odd = whole && fabsf(b) < 16777216.f && ((long long)b & 1);
+        if (x == 0.f || x == -__builtin_inff()) {
+            const float r = ((x == 0.f) == (b > 0.f)) ? 0.f : __builtin_inff();
+            return odd ? copysignf(r, x) : r;
+        }
+        if (!whole) return __builtin_nanf("");
+        const float r = (float)exp((double)b * log((double)-x));
+        return odd ? -r : r;
     }
-    if (x > 2.f || x < 1e-3f) return (float)exp((double)b * log((double)x));   // far outside the model's range
+    // The library path: a base far outside the model's range (1 - w*s lies in [0.2, 1] for the fitted device; another
+    // device's s may reach 0), or an exponent beyond 100 -- exp_small wants |b ln x| < 700, and |ln x| <= 6.91 on [1e-3, 2].
+    // The test on b is uniform: a scalar compare.
+    if (x > 2.f || x < 1e-3f || !(fabsf(b) <= 100.f)) return b == 0.f ? 1.f : (float)exp((double)b * log((double)x));
     return (float)exp_small((double)b * log_unit_range((double)x));
 }
 
-__device__ __forceinline__ float update_one(float w, float V)
+// k * (V/v0 - 1) ** alpha: the first product of the reference's "k * A**alpha * B**b".  alpha == 1 (the fitted device) calls
+// no pow: x ** 1 is x.
+__device__ __forceinline__ float drive_gain(float V, float v0, float k, float alpha)
+{
+    const float a = V / v0 - 1.f;
+    return k * (alpha == 1.f ? a : pow_f32(a, alpha));
+}
+
+__device__ __forceinline__ float update_one(float w, float V, const DevF& p)
 {
     float dwdt = 0.f;
-    if (V < VOFF) {
-        const float a = V / VOFF - 1.f;
-        const float b = pow_f32(1.f - w * SOFF, BOFF);
-        dwdt = KOFF * a * b;
-    } else if (V > VON) {
-        const float a = V / VON - 1.f;
-        const float b = pow_f32(1.f - w * SON, BON);
-        dwdt = KON * a * b;
+    if (V < p.voff) {
+        const float b = pow_f32(1.f - w * p.soff, p.boff);
+        dwdt = drive_gain(V, p.voff, p.koff, p.alphaoff) * b;
+    } else if (V > p.von) {
+        const float b = pow_f32(1.f - w * p.son, p.bon);
+        dwdt = drive_gain(V, p.von, p.kon, p.alphaon) * b;
     }
-    const float wn = w + dwdt * DT;
+    const float wn = w + dwdt * p.dt;
     return wn < 0.f ? 0.f : (wn > 1.f ? 1.f : wn);
 }
 
 // A slice's voltage is one of two values per run (active / silent), so everything of update_one that depends on V
-// alone is evaluated once: the branch taken, k * (V/v0 - 1) (the first product of "k * a * b", same rounding), and the
-// (s, b) pair of the power term.  The per-slice step is then branch-free: one pow, two multiplies, one add, the clip.
+// alone is evaluated once: the branch taken, k * (V/v0 - 1) ** alpha (the first product of "k * A**alpha * B**b", same
+// rounding; the power, where alpha != 1, once per voltage and never per slice), and the (s, b) pair of the power term.  The
+// per-slice step is then branch-free: one pow, two multiplies, one add, the clip.
 struct Drive {
-    float ka, s, b;   // ka = 0 in the dead zone: dw = 0 * pow(..) = 0, w unchanged, as in update_one
+    // dead zone: ka = 0 and the power term is (1 - w*0) ** 1 = 1 whatever the device's s and b, so dw = 0 * 1 = 0 and a finite
+    // w is unchanged bit for bit, as in update_one (a term like (1 - w*s) ** b could overflow for another device: 0 * inf)
+    float ka, s, b, dt;
 };
-__device__ __forceinline__ Drive drive_of(float V)
+__device__ __forceinline__ Drive drive_of(float V, const DevF& p)
 {
     Drive d;
-    if (V < VOFF) { d.ka = KOFF * (V / VOFF - 1.f); d.s = SOFF; d.b = BOFF; }
-    else if (V > VON) { d.ka = KON * (V / VON - 1.f); d.s = SON; d.b = BON; }
-    else { d.ka = 0.f; d.s = SOFF; d.b = BOFF; }
+    d.dt = p.dt;
+    if (V < p.voff) { d.ka = drive_gain(V, p.voff, p.koff, p.alphaoff); d.s = p.soff; d.b = p.boff; }
+    else if (V > p.von) { d.ka = drive_gain(V, p.von, p.kon, p.alphaon); d.s = p.son; d.b = p.bon; }
+    else { d.ka = 0.f; d.s = 0.f; d.b = 1.f; }
     return d;
 }
 __device__ __forceinline__ float update_drive(float w, const Drive& d)
 {
-    const float wn = w + (d.ka * pow_f32(1.f - w * d.s, d.b)) * DT;
+    const float wn = w + (d.ka * pow_f32(1.f - w * d.s, d.b)) * d.dt;
     return wn < 0.f ? 0.f : (wn > 1.f ? 1.f : wn);
 }
 
-__device__ __forceinline__ float resistance_one(float w, float neg_lam)
+// resistance_exp: Ron / exp(-lam * (1 - w)), every operand float32 as NumPy makes them (the quotient of two floats formed in
+// double and rounded once is the float32 quotient)
+__device__ __forceinline__ float resistance_one(float w, const DevF& p)
 {
-    const float e = (float)exp((double)(neg_lam * (1.0f - w)));
-    return (float)(RON / (double)e);
+    const float e = (float)exp((double)(p.neg_lam * (1.0f - w)));
+    return (float)((double)p.ron / (double)e);
 }
 
 __global__ __launch_bounds__(256) void k_update_state(const float* __restrict__ w, const float* __restrict__ V,
-                                                       float* __restrict__ out, size_t n)
+                                                       float* __restrict__ out, size_t n, DevF p)
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-        out[i] = update_one(w[i], V[i]);
+        out[i] = update_one(w[i], V[i], p);
 }
 
-__global__ __launch_bounds__(256) void k_resistance(const float* __restrict__ w, float* __restrict__ out, size_t n,
-                                                     float neg_lam)
+__global__ __launch_bounds__(256) void k_resistance(const float* __restrict__ w, float* __restrict__ out, size_t n, DevF p)
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-        out[i] = resistance_one(w[i], neg_lam);
+        out[i] = resistance_one(w[i], p);
 }
 
 __global__ __launch_bounds__(256) void k_fill(float* __restrict__ p, size_t n, float v)
@@ -158,29 +217,28 @@ __global__ __launch_bounds__(256) void k_fill(float* __restrict__ p, size_t n, f
 }
 
 // The surface value of one pixel before its 8-bit truncation: g in [0, 255], double (modes: see k_surface_gray).
-__device__ __forceinline__ double surface_gray_value(float ww, float neg_lam, int mode)
+__device__ __forceinline__ double surface_gray_value(float ww, const DevF& p, int mode)
 {
     double g;
     if (mode == 0) {
-        const double r = (double)resistance_one(ww, neg_lam);
+        const double r = (double)resistance_one(ww, p);
         g = -3366.0 / log10(1.0 / r) - 306.0;
     } else {
         g = (double)(ww * 255.0f);
     }
-    g = g < 0.0 ? 0.0 : (g > 255.0 ? 255.0 : g);   // NaN (I == 1 A exactly) cannot occur for R in [Ron, Roff]
+    g = g < 0.0 ? 0.0 : (g > 255.0 ? 255.0 : g);   // NaN (I == 1 A exactly, R == 1 Ohm) does not occur for the fitted R in [Ron, Roff]
     return g;
 }
 // The surface as an 8-bit frame, one pixel.
-__device__ __forceinline__ uint8_t surface_gray_one(float ww, float neg_lam, int mode)
+__device__ __forceinline__ uint8_t surface_gray_one(float ww, const DevF& p, int mode)
 {
-    return (uint8_t)surface_gray_value(ww, neg_lam, mode);
+    return (uint8_t)surface_gray_value(ww, p, mode);
 }
 // Where the fused dense update leaves the frame of the state it has just written (out == nullptr: nowhere).
 struct SurfOut {
     uint8_t* out;
     long long stride;
     int W;
-    float neg_lam;
     int mode;
 };
 
@@ -282,12 +340,14 @@ __device__ __forceinline__ float replay_driven(float ww, MaskT m, const Drive& d
 //   REFR   scheme 2: the mask holds event bits; refractory_walk turns them into driven bits first
 //   MaskT  the mask word: 32 bits (groups of up to 32 slices), 64 bits (copy + patch: intervals of up to 64 slices)
 //   FRAME  the pixel's byte of the frame `so` is overwritten as well (copy + patch)
-template <bool REFR, class MaskT, bool FRAME>
+//   FITTED the fitted device as compile-time constants (ModelArg)
+template <bool REFR, class MaskT, bool FRAME, bool FITTED>
 __global__ __launch_bounds__(256) void k_update_list(float* __restrict__ w, MaskT* __restrict__ mask,
                                                       long long* __restrict__ next_ok, const unsigned* __restrict__ list,
                                                       const unsigned* __restrict__ count, TabArg<REFR> tab, float v_act,
-                                                      unsigned* zero_next, SurfOut so)
+                                                      unsigned* zero_next, SurfOut so, ModelArg<FITTED> model)
 {
+    const DevF p = model_arg(model);
     __shared__ long long tf[REFR ? 32 : 1], tn[REFR ? 32 : 1];
     if constexpr (REFR) {
         if (threadIdx.x < 32) { tf[threadIdx.x] = tab.t_first[threadIdx.x]; tn[threadIdx.x] = tab.t_next[threadIdx.x]; }
@@ -295,7 +355,7 @@ __global__ __launch_bounds__(256) void k_update_list(float* __restrict__ w, Mask
     }
     const unsigned n = *count;
     if (zero_next && blockIdx.x == 0 && threadIdx.x == 0) *zero_next = 0;   // the NEXT group's list counter (other parity)
-    const Drive da = drive_of(v_act);
+    const Drive da = drive_of(v_act, p);
     for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const unsigned pix = list[i];
         MaskT m = mask[pix];
@@ -310,7 +370,7 @@ __global__ __launch_bounds__(256) void k_update_list(float* __restrict__ w, Mask
         w[pix] = ww;
         if constexpr (FRAME) {
             const unsigned yy = pix / (unsigned)so.W, xx = pix - yy * (unsigned)so.W;
-            so.out[(long long)yy * so.stride + xx] = surface_gray_one(ww, so.neg_lam, so.mode);
+            so.out[(long long)yy * so.stride + xx] = surface_gray_one(ww, p, so.mode);
         }
     }
 }
@@ -323,11 +383,13 @@ __global__ __launch_bounds__(256) void k_update_list(float* __restrict__ w, Mask
 //   SIL_NOOP  silent_v lies in the dead zone [voff, von], where update_state leaves w bit-for-bit unchanged (dw = 0, w
 //             already inside [0,1]), so only the slices whose bit is set are replayed (in slice order) -- the pass is then
 //             bound by its one read and one write of the state instead of by 32 no-op evaluations per pixel.
-template <bool REFR, bool SIL_NOOP>
+template <bool REFR, bool SIL_NOOP, bool FITTED>
 __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsigned* __restrict__ mask,
                                                      unsigned* __restrict__ mask_hi, long long* __restrict__ next_ok, size_t n4,
-                                                     size_t n, int n_sl, TabArg<REFR> tab, float v_act, float v_sil, SurfOut so)
+                                                     size_t n, int n_sl, TabArg<REFR> tab, float v_act, float v_sil, SurfOut so,
+                                                     ModelArg<FITTED> model)
 {
+    const DevF p = model_arg(model);
     __shared__ long long tf[REFR ? 32 : 1], tn[REFR ? 32 : 1];
     if constexpr (REFR) {
         if (threadIdx.x < 32) { tf[threadIdx.x] = tab.t_first[threadIdx.x]; tn[threadIdx.x] = tab.t_next[threadIdx.x]; }
@@ -335,7 +397,7 @@ __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsig
         mask_hi = nullptr;   // known at compile time: the scheme-2 instantiations carry no code for either
         so.out = nullptr;
     }
-    const Drive da = drive_of(v_act), ds = drive_of(v_sil);
+    const Drive da = drive_of(v_act, p), ds = drive_of(v_sil, p);
     auto one = [&](float ww, unsigned m, unsigned mh, size_t pix) {
         if constexpr (REFR) {
             if (m) {
@@ -348,6 +410,7 @@ __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsig
         for (int s = 0; s < n_sl; s++) {
             const bool act = (REFR || s < 32) ? (m >> s) & 1u : (mh >> (s - 32)) & 1u;
             Drive d;
+            d.dt = da.dt;
             d.ka = act ? da.ka : ds.ka;
             d.s = act ? da.s : ds.s;
             d.b = act ? da.b : ds.b;
@@ -374,8 +437,8 @@ __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsig
             ww.w = one(ww.w, mm.w, mh.w, 4 * i + 3);
             reinterpret_cast<float4*>(w)[i] = ww;
             if (so.out) {   // the frame of the new state: saves the separate surface pass (4 B/px read again + a launch)
-                const uint8_t g0 = surface_gray_one(ww.x, so.neg_lam, so.mode), g1 = surface_gray_one(ww.y, so.neg_lam, so.mode);
-                const uint8_t g2 = surface_gray_one(ww.z, so.neg_lam, so.mode), g3 = surface_gray_one(ww.w, so.neg_lam, so.mode);
+                const uint8_t g0 = surface_gray_one(ww.x, p, so.mode), g1 = surface_gray_one(ww.y, p, so.mode);
+                const uint8_t g2 = surface_gray_one(ww.z, p, so.mode), g3 = surface_gray_one(ww.w, p, so.mode);
                 const size_t px = 4 * i;
                 const size_t yy = px / (size_t)so.W, xx = px - yy * (size_t)so.W;
                 if (xx + 3 < (size_t)so.W && ((so.stride | (long long)xx) & 3) == 0 && (reinterpret_cast<uintptr_t>(so.out) & 3) == 0) {
@@ -396,7 +459,7 @@ __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsig
                 if (mask_hi) mask_hi[j] = 0;
                 const float wj = one(w[j], m, mh, j);
                 w[j] = wj;
-                if (so.out) so.out[(j / (size_t)so.W) * so.stride + j % (size_t)so.W] = surface_gray_one(wj, so.neg_lam, so.mode);
+                if (so.out) so.out[(j / (size_t)so.W) * so.stride + j % (size_t)so.W] = surface_gray_one(wj, p, so.mode);
             }
         }
     }
@@ -404,53 +467,64 @@ __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsig
 
 // Frame-driven variant (/root/reference/simulation/simulationcode_v4_transistor_uav.m:146-227, 332-347), float64:
 // drive voltage from the absolute difference of two compressed frames, then n_sub Euler sub-steps of the same ODE.
-__device__ __forceinline__ double frame_update(double w, double V, double dt)
+// update_state(w, V, dt, params) of the script (:173-181): k * A^alpha * B^b, left to right; alpha == 1 calls no pow.
+__device__ __forceinline__ double frame_gain(double V, double v0, double k, double alpha)
+{
+    const double a = V / v0 - 1;
+    return k * (alpha == 1.0 ? a : pow(a, alpha));
+}
+__device__ __forceinline__ double frame_update(double w, double V, double dt, const DevD& p)
 {
     double dwdt = 0.0;
-    if (V < -0.2) dwdt = 51.03 * (V / -0.2 - 1) * pow(1 - w * 0.8, 3.10);
-    else if (V > 0.1) dwdt = -2.91 * (V / 0.1 - 1) * pow(1 - w * 0.2, -5.12);
+    if (V < p.voff) dwdt = frame_gain(V, p.voff, p.koff, p.alphaoff) * pow(1 - w * p.soff, p.boff);
+    else if (V > p.von) dwdt = frame_gain(V, p.von, p.kon, p.alphaon) * pow(1 - w * p.son, p.bon);
     const double nw = w + dwdt * dt;
     return nw < 0 ? 0 : (nw > 1 ? 1 : nw);
 }
 
 // One frame pair of one grid pixel: the state after n_sub sub-steps under the drive voltage of |a - b|.
-__device__ __forceinline__ double frame_pair(double a, double b, double ww, double dts, int n_sub, double th1, double th2)
+__device__ __forceinline__ double frame_pair(double a, double b, double ww, double dts, int n_sub, double th1, double th2,
+                                             const DevD& p)
 {
     const double d = fabs(a * 256 - b * 256);
     double V = d > th1 ? (d + 4) * 0.75 : (d - 5.5) * 0.6;   // func2 == func3 in the source
     V = V > 0 ? -(0.3 * V + 0) : (V < 0 ? -(3 * V + -3) : 0.0);
-    for (int s = 0; s < n_sub; s++) ww = frame_update(ww, V, dts);
+    for (int s = 0; s < n_sub; s++) ww = frame_update(ww, V, dts, p);
     return ww;
 }
 
+template <bool FITTED>
 __global__ __launch_bounds__(64) void k_frame_step(const double* __restrict__ a, const double* __restrict__ b,
                                                     double* __restrict__ w, double* __restrict__ res, size_t n,
-                                                    double dts, int n_sub, double th1, double th2, double lambda)
+                                                    double dts, int n_sub, double th1, double th2, FrameArg<FITTED> model)
 {
+    const DevD p = frame_arg(model);
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
-    const double ww = frame_pair(a[i], b[i], w[i], dts, n_sub, th1, th2);
+    const double ww = frame_pair(a[i], b[i], w[i], dts, n_sub, th1, th2, p);
     w[i] = ww;
-    res[i] = RON / exp(-lambda * (1 - ww));
+    res[i] = p.ron / exp(-p.lambda * (1 - ww));
 }
 
 // The whole run in one launch: one thread per grid pixel walks every frame pair (a pixel's pairs are one dependent
 // chain, the pixels are independent).  imgs [n_frames][n]; res [n_frames][n], slice 0 = r0 (the initial resistance, formed
 // on the host as nsof_accum_frames_f64 forms it); current [n_frames - 1][n] = v_ds / res[f + 1] (optional).
+template <bool FITTED>
 __global__ __launch_bounds__(64) void k_frames_run(const double* __restrict__ imgs, int n_frames, double* __restrict__ w,
                                                     double* __restrict__ res, double* __restrict__ current, size_t n,
-                                                    double dts, int n_sub, double th1, double th2, double lambda, double r0,
-                                                    double v_ds)
+                                                    double dts, int n_sub, double th1, double th2, FrameArg<FITTED> model,
+                                                    double r0, double v_ds)
 {
+    const DevD p = frame_arg(model);
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
-    double ww = 0.5, b = imgs[i];
+    double ww = p.wini, b = imgs[i];
     res[i] = r0;
     for (int f = 0; f + 1 < n_frames; f++) {
         const double a = b;
         b = imgs[(size_t)(f + 1) * n + i];
-        ww = frame_pair(a, b, ww, dts, n_sub, th1, th2);
-        const double r = RON / exp(-lambda * (1 - ww));
+        ww = frame_pair(a, b, ww, dts, n_sub, th1, th2, p);
+        const double r = p.ron / exp(-p.lambda * (1 - ww));
         res[(size_t)(f + 1) * n + i] = r;
         if (current) current[(size_t)f * n + i] = v_ds / r;
     }
@@ -465,21 +539,21 @@ __global__ __launch_bounds__(64) void k_frames_run(const double* __restrict__ im
 //   mode 1  build-defined linear map of the state itself, g = uint8(255 * w) (float32 product, truncated): the frame
 //           the joined events -> surface -> flow pipeline (BASELINE config 5) hands to the flow stage.
 __global__ __launch_bounds__(256) void k_surface_gray(const float* __restrict__ w, uint8_t* __restrict__ out, int W, int H,
-                                                       ptrdiff_t stride, float neg_lam, int mode)
+                                                       ptrdiff_t stride, DevF p, int mode)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= W || y >= H) return;
-    out[(ptrdiff_t)y * stride + x] = surface_gray_one(w[(size_t)y * W + x], neg_lam, mode);
+    out[(ptrdiff_t)y * stride + x] = surface_gray_one(w[(size_t)y * W + x], p, mode);
 }
 
 // The same surface as a float frame: g rounded to float32 instead of truncated to 8 bits (finite, in [0, 255]).
 __global__ __launch_bounds__(256) void k_surface_gray_f32(const float* __restrict__ w, float* __restrict__ out, int W, int H,
-                                                           ptrdiff_t stride, float neg_lam, int mode)
+                                                           ptrdiff_t stride, DevF p, int mode)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= W || y >= H) return;
     reinterpret_cast<float*>(reinterpret_cast<char*>(out) + (ptrdiff_t)y * stride)[x] =
-        (float)surface_gray_value(w[(size_t)y * W + x], neg_lam, mode);
+        (float)surface_gray_value(w[(size_t)y * W + x], p, mode);
 }
 
 // ---- surface frames as copy + patch -------------------------------------------------------------------------------------
@@ -592,11 +666,13 @@ __global__ __launch_bounds__(1024) void k_tile_bucket(const short* __restrict__ 
     }
 }
 
+template <bool FITTED>
 __global__ __launch_bounds__(256) void k_tile_frames(float* __restrict__ w, size_t npx, int W, const unsigned* __restrict__ off,
                                                       const unsigned short* __restrict__ recs, unsigned ntiles, int n_frames,
                                                       float v_act, uint8_t* __restrict__ frames, long long row_stride,
-                                                      long long frame_stride, float neg_lam, int mode)
+                                                      long long frame_stride, ModelArg<FITTED> model, int mode)
 {
+    const DevF p = model_arg(model);
     __shared__ unsigned long long s_mask[4][TILE_PX];
     __shared__ __attribute__((aligned(16))) float s_w[4][TILE_PX];
     __shared__ __attribute__((aligned(16))) uint8_t s_b[4][TILE_PX];
@@ -616,11 +692,11 @@ __global__ __launch_bounds__(256) void k_tile_frames(float* __restrict__ w, size
         f4v v = live ? reinterpret_cast<const f4v*>(w + p0)[j] : (f4v){0.f, 0.f, 0.f, 0.f};
         reinterpret_cast<f4v*>(wl + lane * 16)[j] = v;
 #pragma unroll
-        for (int q = 0; q < 4; q++) bl[lane * 16 + 4 * j + q] = surface_gray_one(v[q], neg_lam, mode);
+        for (int q = 0; q < 4; q++) bl[lane * 16 + 4 * j + q] = surface_gray_one(v[q], p, mode);
     }
 #pragma unroll
     for (int j = 0; j < 16; j++) ml[lane * 16 + j] = 0ull;
-    const Drive da = drive_of(v_act);
+    const Drive da = drive_of(v_act, p);
     bool dirty = false;
     for (int kb = 0; kb < n_frames; kb += 63) {
         // the bucket bounds of up to 63 intervals of this tile, one per lane (lane i: the start of interval kb + i)
@@ -665,7 +741,7 @@ __global__ __launch_bounds__(256) void k_tile_frames(float* __restrict__ w, size
                     if (m) {
                         const float ww = replay_driven(wl[pix], m, da);
                         wl[pix] = ww;
-                        bl[pix] = surface_gray_one(ww, neg_lam, mode);
+                        bl[pix] = surface_gray_one(ww, p, mode);
                     }
                 };
                 if (rcur != 0xffffffffu) settle(rcur);
@@ -699,8 +775,74 @@ inline int grid_for(size_t n, int cap = 4096)
     return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
 }
 
-// resistance_exp's exponent scale -ln(Roff / Ron), as the float32 the kernels take
-inline float neg_lam() { return (float)(-std::log(ROFF / RON)); }
+// event_mem_sim.py:20-34
+inline nsof_accum_params default_params()
+{
+    nsof_accum_params p;
+    p.alphaoff = 1; p.alphaon = 1; p.voff = -0.2; p.von = 0.1; p.koff = 51.03; p.kon = -2.91; p.son = 0.2; p.soff = 0.8;
+    p.bon = -5.12; p.boff = 3.10; p.Ron = 163305.0; p.Roff = 2104377.0; p.wini = 0.5;
+    p.dt = 5e-4;
+    p.refractory_us = 800;
+    return p;
+}
+
+// A parameter set the kernels can run (NULL: the defaults), with its float32 and float64 device forms; everything else is
+// refused before anything is launched.  The sign tests are made on the float32 values too: those are what the float32
+// kernels divide by and compare with.
+struct Model {
+    nsof_accum_params prm;
+    DevF f;
+    DevD d;
+    float wini_f;
+    bool fitted;   // every field equals the fitted device's: the FITTED kernel instantiations apply
+};
+// f(std::true_type, NoModel) for the fitted device, f(std::false_type, DevF) otherwise: the kernel instantiation and its argument
+template <class Fn>
+void with_model(const Model& m, Fn&& f)
+{
+    if (m.fitted) f(std::true_type{}, NoModel{});
+    else f(std::false_type{}, m.f);
+}
+template <class Fn>
+void with_frame_model(const Model& m, Fn&& f)
+{
+    if (m.fitted) f(std::true_type{}, FittedD{m.d.lambda});
+    else f(std::false_type{}, m.d);
+}
+int model_of(nsof_ctx* ctx, const nsof_accum_params* in, Model* m)
+{
+    const nsof_accum_params p = in ? *in : default_params();
+    const double fields[] = {p.alphaoff, p.alphaon, p.voff, p.von, p.koff, p.kon, p.son, p.soff, p.bon, p.boff, p.Ron, p.Roff, p.wini, p.dt};
+    static const char* const names[] = {"alphaoff", "alphaon", "voff", "von", "koff", "kon", "son", "soff", "bon", "boff", "Ron", "Roff", "wini", "dt"};
+    for (int i = 0; i < 14; i++)
+        if (!std::isfinite(fields[i]) || !std::isfinite((float)fields[i]))
+            return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameter %s = %g is not a finite float32", names[i], fields[i]);
+    if (!(p.voff < 0 && 0 < p.von) || !((float)p.voff < 0.f && 0.f < (float)p.von))
+        return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: voff < 0 < von required (voff %g, von %g)", p.voff, p.von);
+    if (!(p.son >= 0 && p.son <= 1 && p.soff >= 0 && p.soff <= 1))
+        return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: son, soff must lie in [0, 1] (son %g, soff %g)", p.son, p.soff);
+    if (!(p.Ron > 0 && p.Roff > 0) || !((float)p.Ron > 0.f))
+        return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: Ron, Roff must be positive (Ron %g, Roff %g)", p.Ron, p.Roff);
+    if (!(p.wini >= 0 && p.wini <= 1)) return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: wini %g outside [0, 1]", p.wini);
+    if (!(p.dt > 0) || !((float)p.dt > 0.f)) return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: dt %g must be positive", p.dt);
+    if (p.refractory_us < 0)
+        return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: refractory_us %lld is negative", (long long)p.refractory_us);
+    const double lambda = std::log(p.Roff / p.Ron);
+    if (!std::isfinite(lambda)) return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: ln(Roff / Ron) is not finite");
+    m->prm = p;
+    m->f = DevF{(float)p.voff, (float)p.von, (float)p.koff, (float)p.kon, (float)p.son, (float)p.soff, (float)p.bon, (float)p.boff,
+                (float)p.alphaoff, (float)p.alphaon, (float)p.dt, (float)p.Ron, (float)(-lambda)};
+    m->d = DevD{p.voff, p.von, p.koff, p.kon, p.son, p.soff, p.bon, p.boff, p.alphaoff, p.alphaon, p.Ron, lambda, p.wini};
+    m->wini_f = (float)p.wini;
+    // The model's own fields decide (dt as the float32 the kernels multiply by; refractory_us never reaches a kernel).  The
+    // constants of fitted_f / fitted_d, neg_lam's literal included, are pinned by the tests that hold the default path to the
+    // correctly rounded reference bit for bit.
+    const nsof_accum_params q = default_params();
+    m->fitted = p.alphaoff == q.alphaoff && p.alphaon == q.alphaon && p.voff == q.voff && p.von == q.von && p.koff == q.koff &&
+                p.kon == q.kon && p.son == q.son && p.soff == q.soff && p.bon == q.bon && p.boff == q.boff && p.Ron == q.Ron &&
+                p.Roff == q.Roff && p.wini == q.wini && (float)p.dt == (float)q.dt;
+    return NSOF_OK;
+}
 
 // List counters of the event-pixel update, [parity][array]: two sets used alternately.  A group's update kernels zero the
 // OTHER set -- the one the next group's scatter appends to -- so no group needs a memset (a launch of its own): one per call.
@@ -742,6 +884,7 @@ struct nsof_accum {
     // staged stream (nsof_accum_set_events / the staging half of nsof_accum_step_events): slice bounds relative to
     // the first staged event, and for scheme 2 the first / last+refractory timestamp of every slice
     std::vector<long long> h_rel, h_tfirst, h_tnext;
+    Model model;             // the device the array is made of (nsof_accum_create_p), fixed for the accumulator's life
     int frames_path = 0;     // nsof_accum_run_frames: 0 = the tile walk where it applies, 1 = copy + patch per interval (kept as the cross-check)
 };
 
@@ -760,7 +903,7 @@ extern "C" int nsof_accum_reset(nsof_accum* a)
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const int narr = a->split ? 2 : 1;
     for (int i = 0; i < narr; i++) {
-        hipLaunchKernelGGL(k_fill, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[i].p, a->npx, WINI);
+        hipLaunchKernelGGL(k_fill, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[i].p, a->npx, a->model.wini_f);
         NSOF_HIP(ctx, hipMemsetAsync(a->mask[i].p, 0, a->npx * sizeof(unsigned), ctx->stream));
         if (a->scheme == 2) NSOF_HIP(ctx, hipMemsetAsync(a->next_ok[i].p, 0, a->npx * sizeof(long long), ctx->stream));
     }
@@ -770,11 +913,31 @@ extern "C" int nsof_accum_reset(nsof_accum* a)
     return NSOF_OK;
 }
 
+extern "C" void nsof_accum_default_params(nsof_accum_params* out)
+{
+    if (out) *out = default_params();
+}
+
+extern "C" int nsof_accum_get_params(const nsof_accum* a, nsof_accum_params* out)
+{
+    if (!a || !out) return NSOF_EINVAL;
+    *out = a->model.prm;
+    return NSOF_OK;
+}
+
 extern "C" int nsof_accum_create(nsof_ctx* ctx, int height, int width, int scheme, int polarity_split, float active_v,
                                  float silent_v, nsof_accum** out)
 {
+    return nsof_accum_create_p(ctx, height, width, scheme, polarity_split, active_v, silent_v, nullptr, out);
+}
+
+extern "C" int nsof_accum_create_p(nsof_ctx* ctx, int height, int width, int scheme, int polarity_split, float active_v,
+                                   float silent_v, const nsof_accum_params* params, nsof_accum** out)
+{
     if (!ctx || !out) return NSOF_EINVAL;
     *out = nullptr;
+    Model model;
+    if (int rc = model_of(ctx, params, &model)) return rc;
     if (height < 1 || width < 1 || (scheme != 1 && scheme != 2))
         return nsof_set_error(ctx, NSOF_EINVAL, "bad accumulator geometry %dx%d or scheme %d", height, width, scheme);
     if ((size_t)height * width > 0xFFFFFFFFull) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "sensor too large");
@@ -782,6 +945,7 @@ extern "C" int nsof_accum_create(nsof_ctx* ctx, int height, int width, int schem
     nsof_accum* a = new (std::nothrow) nsof_accum();
     if (!a) return nsof_set_error(ctx, NSOF_ENOMEM, "out of host memory");
     a->ctx = ctx; a->H = height; a->W = width; a->scheme = scheme;
+    a->model = model;
     a->split = (scheme == 2 && polarity_split) ? 1 : 0;
     a->active_v = active_v; a->silent_v = silent_v;
     a->npx = (size_t)height * width;
@@ -831,7 +995,7 @@ static int accum_snapshot(nsof_accum* a)
     }
     for (int i = 0; i < narr; i++)
         hipLaunchKernelGGL(k_resistance, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[i].p,
-                           a->snap[i].p + (size_t)a->snap_count * a->npx, a->npx, neg_lam());
+                           a->snap[i].p + (size_t)a->snap_count * a->npx, a->npx, a->model.f);
     NSOF_HIP(ctx, hipGetLastError());
     a->snap_count++;
     return NSOF_OK;
@@ -879,7 +1043,7 @@ static int accum_stage(nsof_accum* a, const int16_t* x, const int16_t* y, const 
         for (int64_t s = 0; s < n_slices; s++)
             if (sb[s + 1] > sb[s]) {
                 a->h_tfirst[s] = t[sb[s]];
-                a->h_tnext[s] = t[sb[s + 1] - 1] + REFRACTORY_US;
+                a->h_tnext[s] = t[sb[s + 1] - 1] + a->model.prm.refractory_us;
             }
     NSOF_HIP(ctx, hipMemcpyAsync(a->dbounds.p, a->h_rel.data(), a->h_rel.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's arrays are not retained
@@ -887,7 +1051,7 @@ static int accum_stage(nsof_accum* a, const int16_t* x, const int16_t* y, const 
 }
 
 // Scheme 2 reads two timestamps per slice -- its first event's (the refractory test, event_mem_sim.py:243,253,265) and
-// its last event's (+ REFRACTORY_US -> next_ok, :246,256,267) -- and they belong to the slice of the WHOLE stream.  A
+// its last event's (+ refractory_us -> next_ok, :246,256,267) -- and they belong to the slice of the WHOLE stream.  A
 // row band (nsof.dist.simulate_banded) stages only its own events, whose first / last differ: the caller hands the
 // global table over, and the band's state then equals its rows of the unsharded run.
 extern "C" int nsof_accum_set_slice_times(nsof_accum* a, const int64_t* t_first, const int64_t* t_last, int64_t n_slices)
@@ -899,9 +1063,15 @@ extern "C" int nsof_accum_set_slice_times(nsof_accum* a, const int64_t* t_first,
     if (a->scheme != 2) return NSOF_OK;   // scheme 1 reads no timestamps
     for (int64_t s = 0; s < n_slices; s++) {
         a->h_tfirst[s] = t_first[s];
-        a->h_tnext[s] = t_last[s] + REFRACTORY_US;
+        a->h_tnext[s] = t_last[s] + a->model.prm.refractory_us;
     }
     return NSOF_OK;
+}
+
+// The silent voltage leaves an idle pixel bit for bit unchanged: the float32 comparisons update_one makes.
+static bool dead_zone_of(const nsof_accum* a)
+{
+    return !(a->silent_v < a->model.f.voff) && !(a->silent_v > a->model.f.von);
 }
 
 // The arguments every 8-bit surface entry point takes: an array of this accumulator, a surface mode, rows of at least W bytes.
@@ -915,7 +1085,7 @@ static int accum_surface(nsof_accum* a, int which, const SurfOut& so)
     nsof_ctx* ctx = a->ctx;
     dim3 grid((a->W + 255) / 256, a->H);
     hipLaunchKernelGGL(k_surface_gray, grid, dim3(256), 0, ctx->stream, a->w[which].p, so.out, a->W, a->H, (ptrdiff_t)so.stride,
-                       so.neg_lam, so.mode);
+                       a->model.f, so.mode);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
@@ -934,7 +1104,7 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
     const int narr = a->split ? 2 : 1;
     int rc;
     const std::vector<long long>& rel = a->h_rel;
-    const bool dead_zone = !(a->silent_v < VOFF) && !(a->silent_v > VON);
+    const bool dead_zone = dead_zone_of(a);
     // Scheme 1 with the silent voltage in the dead zone: the event-pixel update (lists, groups of 32 slices) and the
     // every-pixel pass (groups of 64 slices, no lists) give the same bits; which one is faster depends on the sensor size.
     // Measured with a frame every 33 slices (scripts/accum_mode_probe.py): 1280x720 0.39 vs 0.75-0.89 ms per 30 frames,
@@ -981,12 +1151,14 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
             // array i of the group; R: std::true_type for scheme 2, whose kernels take the group's refractory table
             auto update = [&](auto R, const auto& tab, int i) {
                 constexpr bool REFR = decltype(R)::value;
-                SurfOut so{nullptr, 0, a->W, 0.f, 0};
+                SurfOut so{nullptr, 0, a->W, 0};
                 if (sparse) {
                     if (gn > 0)
-                        hipLaunchKernelGGL((k_update_list<REFR, unsigned, false>), dim3(grid_for((size_t)gn, 1024)), dim3(256), 0,
-                                           ctx->stream, a->w[i].p, a->mask[i].p, a->next_ok[i].p, a->list[i].p, cnt.cur() + i, tab,
-                                           v_act, cnt.next() + i, so);
+                        with_model(a->model, [&](auto D, auto model) {
+                            hipLaunchKernelGGL((k_update_list<REFR, unsigned, false, decltype(D)::value>), dim3(grid_for((size_t)gn, 1024)),
+                                               dim3(256), 0, ctx->stream, a->w[i].p, a->mask[i].p, a->next_ok[i].p, a->list[i].p,
+                                               cnt.cur() + i, tab, v_act, cnt.next() + i, so, model);
+                        });
                     return;
                 }
                 if (wide && surf && i == surf_which && s0 + g == s_end) {   // the call's last group: leave the frame as well
@@ -994,10 +1166,13 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
                     surf_done = true;
                 }
                 const size_t n4 = (a->npx + 3) / 4;
-                auto* const kernel = dead_zone ? k_update_all<REFR, true> : k_update_all<REFR, false>;
-                hipLaunchKernelGGL(kernel, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream, a->w[i].p, a->mask[i].p,
-                                   g > MAX_GROUP ? a->mask_hi.p : nullptr, a->next_ok[i].p, n4, a->npx, (int)g, tab, v_act,
-                                   a->silent_v, so);
+                with_model(a->model, [&](auto D, auto model) {
+                    constexpr bool FITTED = decltype(D)::value;
+                    auto* const kernel = dead_zone ? k_update_all<REFR, true, FITTED> : k_update_all<REFR, false, FITTED>;
+                    hipLaunchKernelGGL(kernel, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream, a->w[i].p, a->mask[i].p,
+                                       g > MAX_GROUP ? a->mask_hi.p : nullptr, a->next_ok[i].p, n4, a->npx, (int)g, tab, v_act,
+                                       a->silent_v, so, model);
+                });
             };
             if (a->scheme == 2) {
                 RefrTab tab;
@@ -1047,7 +1222,7 @@ extern "C" int nsof_accum_surface_u8_dev(nsof_accum* a, int which, int mode, uin
 {
     if (!surface_args_ok(a, which, mode, d_out, row_stride)) return NSOF_EINVAL;
     NSOF_HIP(a->ctx, hipSetDevice(a->ctx->device));
-    return accum_surface(a, which, SurfOut{d_out, (long long)row_stride, a->W, neg_lam(), mode});
+    return accum_surface(a, which, SurfOut{d_out, (long long)row_stride, a->W, mode});
 }
 
 extern "C" int nsof_accum_surface_f32_dev(nsof_accum* a, int which, int mode, float* d_out, ptrdiff_t row_stride_bytes)
@@ -1059,7 +1234,7 @@ extern "C" int nsof_accum_surface_f32_dev(nsof_accum* a, int which, int mode, fl
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid((a->W + 255) / 256, a->H);
     hipLaunchKernelGGL(k_surface_gray_f32, grid, dim3(256), 0, ctx->stream, a->w[which].p, d_out, a->W, a->H, row_stride_bytes,
-                       neg_lam(), mode);
+                       a->model.f, mode);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
@@ -1068,7 +1243,7 @@ extern "C" int nsof_accum_run_surface(nsof_accum* a, int64_t first_slice, int64_
                                       ptrdiff_t row_stride)
 {
     if (!surface_args_ok(a, which, mode, d_out, row_stride)) return NSOF_EINVAL;
-    const SurfOut so{d_out, (long long)row_stride, a->W, neg_lam(), mode};
+    const SurfOut so{d_out, (long long)row_stride, a->W, mode};
     return accum_advance(a, first_slice, n_slices, 0, &so, which);
 }
 
@@ -1084,9 +1259,9 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
     if (first_slice < 0 || (size_t)(first_slice + n_frames * every + 1) > a->h_rel.size())
         return nsof_set_error(ctx, NSOF_EINVAL, "slices [%lld, %lld) outside the staged stream", (long long)first_slice,
                               (long long)(first_slice + n_frames * every));
-    const bool dead_zone = !(a->silent_v < VOFF) && !(a->silent_v > VON);
+    const bool dead_zone = dead_zone_of(a);
     // frame k of the call, as the kernels take it
-    auto frame = [&](int64_t k) { return SurfOut{d_frames + k * frame_stride, (long long)row_stride, a->W, neg_lam(), mode}; };
+    auto frame = [&](int64_t k) { return SurfOut{d_frames + k * frame_stride, (long long)row_stride, a->W, mode}; };
     if (!(a->scheme == 1 && dead_zone && a->force_dense <= 0 && every <= 2 * MAX_GROUP)) {
         for (int64_t k = 0; k < n_frames; k++) {
             const SurfOut so = frame(k);
@@ -1112,9 +1287,11 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
         nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
         hipLaunchKernelGGL(k_tile_bucket, dim3((unsigned)n_frames), dim3(1024), (size_t)ntiles * 4, ctx->stream, a->dx.p, a->dy.p, ev0,
                            a->dbounds.p + first_slice, (int)every, a->W, ntiles, a->tile_off.p, a->tile_recs.p, (int)n_frames);
-        hipLaunchKernelGGL(k_tile_frames, dim3((ntiles + 3) / 4), dim3(256), 0, ctx->stream, a->w[0].p, a->npx, a->W,
-                           (const unsigned*)a->tile_off.p, (const unsigned short*)a->tile_recs.p, ntiles, (int)n_frames, a->active_v, d_frames,
-                           (long long)row_stride, (long long)frame_stride, neg_lam(), mode);
+        with_model(a->model, [&](auto D, auto model) {
+            hipLaunchKernelGGL(k_tile_frames<decltype(D)::value>, dim3((ntiles + 3) / 4), dim3(256), 0, ctx->stream, a->w[0].p, a->npx,
+                               a->W, (const unsigned*)a->tile_off.p, (const unsigned short*)a->tile_recs.p, ntiles, (int)n_frames,
+                               a->active_v, d_frames, (long long)row_stride, (long long)frame_stride, model, mode);
+        });
         NSOF_HIP(ctx, hipGetLastError());
         a->slice_counter += n_frames * every;
         return NSOF_OK;
@@ -1140,9 +1317,11 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
                                cnt.cur());
         }
         // (launched for an empty interval as well: it zeroes the next interval's counter)
-        hipLaunchKernelGGL((k_update_list<false, unsigned long long, true>), dim3(grid_for((size_t)std::max<long long>(gn, 1), 1024)),
-                           dim3(256), 0, ctx->stream, a->w[0].p, a->mask64.p, (long long*)nullptr, a->list[0].p, cnt.cur(), NoTab{},
-                           a->active_v, cnt.next(), cur);
+        with_model(a->model, [&](auto D, auto model) {
+            hipLaunchKernelGGL((k_update_list<false, unsigned long long, true, decltype(D)::value>),
+                               dim3(grid_for((size_t)std::max<long long>(gn, 1), 1024)), dim3(256), 0, ctx->stream, a->w[0].p,
+                               a->mask64.p, (long long*)nullptr, a->list[0].p, cnt.cur(), NoTab{}, a->active_v, cnt.next(), cur, model);
+        });
         NSOF_HIP(ctx, hipGetLastError());
         // the call's first frame has no predecessor to copy: one pass over the array
         if (k == 0 && (rc = accum_surface(a, which, cur))) return rc;
@@ -1186,14 +1365,22 @@ extern "C" int nsof_accum_write_state(nsof_accum* a, int which, const float* w_i
     return NSOF_OK;
 }
 
-extern "C" int nsof_accum_update_state_dev(nsof_ctx* ctx, const float* d_w, const float* d_V, float* d_out, size_t n)
+extern "C" int nsof_accum_update_state_p_dev(nsof_ctx* ctx, const nsof_accum_params* params, const float* d_w, const float* d_V,
+                                             float* d_out, size_t n)
 {
     if (!ctx || !d_w || !d_V || !d_out) return NSOF_EINVAL;
+    Model model;
+    if (int rc = model_of(ctx, params, &model)) return rc;
     if (!n) return NSOF_OK;
     nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
-    hipLaunchKernelGGL(k_update_state, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_w, d_V, d_out, n);
+    hipLaunchKernelGGL(k_update_state, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_w, d_V, d_out, n, model.f);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
+}
+
+extern "C" int nsof_accum_update_state_dev(nsof_ctx* ctx, const float* d_w, const float* d_V, float* d_out, size_t n)
+{
+    return nsof_accum_update_state_p_dev(ctx, nullptr, d_w, d_V, d_out, n);
 }
 
 // Host arrays in, host histogram out (the reference calls it on the events of one slice).
@@ -1228,14 +1415,20 @@ extern "C" int nsof_accum_bincount_2d(nsof_ctx* ctx, const int16_t* x, const int
     return NSOF_OK;
 }
 
-extern "C" int nsof_accum_resistance_dev(nsof_ctx* ctx, const float* d_w, float* d_out, size_t n)
+extern "C" int nsof_accum_resistance_p_dev(nsof_ctx* ctx, const nsof_accum_params* params, const float* d_w, float* d_out, size_t n)
 {
     if (!ctx || !d_w || !d_out) return NSOF_EINVAL;
+    Model model;
+    if (int rc = model_of(ctx, params, &model)) return rc;
     if (!n) return NSOF_OK;
-    hipLaunchKernelGGL(k_resistance, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_w, d_out, n,
-                       neg_lam());
+    hipLaunchKernelGGL(k_resistance, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_w, d_out, n, model.f);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
+}
+
+extern "C" int nsof_accum_resistance_dev(nsof_ctx* ctx, const float* d_w, float* d_out, size_t n)
+{
+    return nsof_accum_resistance_p_dev(ctx, nullptr, d_w, d_out, n);
 }
 
 extern "C" int nsof_accum_read_w(nsof_accum* a, int which, float* out)
@@ -1254,7 +1447,7 @@ extern "C" int nsof_accum_read_resistance(nsof_accum* a, int which, float* out)
     nsof_dev_buf<float> tmp;
     int rc = tmp.reserve(ctx, a->npx * sizeof(float));
     if (rc) return rc;
-    rc = nsof_accum_resistance_dev(ctx, a->w[which].p, tmp.p, a->npx);
+    rc = nsof_accum_resistance_p_dev(ctx, &a->model.prm, a->w[which].p, tmp.p, a->npx);
     if (!rc) {
         hipError_t e = hipMemcpyAsync(out, tmp.p, a->npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1270,7 +1463,7 @@ extern "C" int64_t nsof_accum_snapshot_count(const nsof_accum* a) { return a ? a
 // max(v_ds / R) = v_ds / min(R) exactly (division by a positive float is monotone), so a block reduces min(R) in
 // float32 -- R from a stored snapshot, or resistance_one(w) of the current state -- and thread 0 divides in double.
 __global__ __launch_bounds__(256) void k_block_min_resistance(const float* __restrict__ src, int is_w, int W, int memsize,
-                                                               int cols, float neg_lam, double v_ds, double* __restrict__ out)
+                                                               int cols, DevF p, double v_ds, double* __restrict__ out)
 {
     __shared__ float part[4];
     const int bx = blockIdx.x, by = blockIdx.y;
@@ -1278,7 +1471,7 @@ __global__ __launch_bounds__(256) void k_block_min_resistance(const float* __res
     float m = INFINITY;
     for (int i = threadIdx.x; i < memsize * memsize; i += 256) {
         const float v = base[(size_t)(i / memsize) * W + (i % memsize)];
-        m = fminf(m, is_w ? resistance_one(v, neg_lam) : v);
+        m = fminf(m, is_w ? resistance_one(v, p) : v);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o));
@@ -1300,7 +1493,7 @@ extern "C" int nsof_accum_block_current(nsof_accum* a, int which, int64_t snapsh
     if (rc) return rc;
     const float* src = snapshot < 0 ? a->w[which].p : a->snap[which].p + (size_t)snapshot * a->npx;
     hipLaunchKernelGGL(k_block_min_resistance, dim3(cols, rows), dim3(256), 0, ctx->stream, src, snapshot < 0 ? 1 : 0, a->W,
-                       memsize, cols, neg_lam(), v_ds, (double*)ctx->tmp.p);
+                       memsize, cols, a->model.f, v_ds, (double*)ctx->tmp.p);
     NSOF_HIP(ctx, hipGetLastError());
     NSOF_HIP(ctx, hipMemcpyAsync(out, ctx->tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1319,7 +1512,7 @@ extern "C" int nsof_accum_block_current_dev(nsof_accum* a, int which, int64_t sn
     const int rows = a->H / memsize, cols = a->W / memsize;
     const float* src = snapshot < 0 ? a->w[which].p : a->snap[which].p + (size_t)snapshot * a->npx;
     hipLaunchKernelGGL(k_block_min_resistance, dim3(cols, rows), dim3(256), 0, ctx->stream, src, snapshot < 0 ? 1 : 0, a->W,
-                       memsize, cols, neg_lam(), v_ds, d_out);
+                       memsize, cols, a->model.f, v_ds, d_out);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
@@ -1361,9 +1554,21 @@ extern "C" int64_t nsof_accum_slice_bounds(const int64_t* t, int64_t n, int64_t 
 extern "C" int nsof_accum_frames_f64(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
                                      int n_sub_steps, double th1, double th2, double* w_out, double* res_out)
 {
+    return nsof_accum_frames_f64_p(ctx, imgs, n_frames, height, width, dt, n_sub_steps, th1, th2, nullptr, w_out, res_out);
+}
+
+// The same with the device model as an argument (NULL: the defaults); the step dt stays the argument it is, params->dt and
+// params->refractory_us are checked with the rest of the set and not read.
+extern "C" int nsof_accum_frames_f64_p(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
+                                       int n_sub_steps, double th1, double th2, const nsof_accum_params* params, double* w_out,
+                                       double* res_out)
+{
     if (!ctx) return NSOF_EINVAL;
     if (!imgs || !w_out || !res_out || n_frames < 1 || height < 1 || width < 1 || n_sub_steps < 1)
         return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
+    Model model;
+    if (int rc = model_of(ctx, params, &model)) return rc;
+    const DevD& md = model.d;
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const size_t npx = (size_t)height * width;
     nsof_dev_buf<double> img_buf, w_buf, res_buf;
@@ -1372,16 +1577,17 @@ extern "C" int nsof_accum_frames_f64(nsof_ctx* ctx, const double* imgs, int n_fr
     if (!rc) rc = res_buf.reserve(ctx, (size_t)n_frames * npx * 8);
     double *d_img = img_buf.p, *d_w = w_buf.p, *d_res = res_buf.p;
     if (!rc) {
-        const double lambda = std::log(ROFF / RON);
-        std::vector<double> init(npx, 0.5), r0(npx, RON / std::exp(-lambda * 0.5));
+        std::vector<double> init(npx, md.wini), r0(npx, md.ron / std::exp(-md.lambda * (1 - md.wini)));
         hipError_t e = hipMemcpyAsync(d_img, imgs, (size_t)n_frames * npx * 8, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(d_w, init.data(), npx * 8, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(d_res, r0.data(), npx * 8, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         for (int f = 0; f + 1 < n_frames && e == hipSuccess; f++) {
-            hipLaunchKernelGGL(k_frame_step, dim3((unsigned)((npx + 63) / 64)), dim3(64), 0, ctx->stream,
-                               d_img + (size_t)f * npx, d_img + (size_t)(f + 1) * npx, d_w, d_res + (size_t)(f + 1) * npx,
-                               npx, dt / n_sub_steps, n_sub_steps, th1, th2, lambda);
+            with_frame_model(model, [&](auto D, auto fm) {
+                hipLaunchKernelGGL(k_frame_step<decltype(D)::value>, dim3((unsigned)((npx + 63) / 64)), dim3(64), 0, ctx->stream,
+                                   d_img + (size_t)f * npx, d_img + (size_t)(f + 1) * npx, d_w, d_res + (size_t)(f + 1) * npx,
+                                   npx, dt / n_sub_steps, n_sub_steps, th1, th2, fm);
+            });
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(w_out, d_w, npx * 8, hipMemcpyDeviceToHost, ctx->stream);
@@ -1400,15 +1606,28 @@ extern "C" int nsof_accum_frames_f64_dev(nsof_ctx* ctx, const double* d_imgs, in
                                          int n_sub_steps, double th1, double th2, double v_ds, double* d_w, double* d_res,
                                          double* d_current)
 {
+    return nsof_accum_frames_f64_p_dev(ctx, d_imgs, n_frames, height, width, dt, n_sub_steps, th1, th2, v_ds, nullptr, d_w, d_res,
+                                       d_current);
+}
+
+extern "C" int nsof_accum_frames_f64_p_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
+                                           int n_sub_steps, double th1, double th2, double v_ds, const nsof_accum_params* params,
+                                           double* d_w, double* d_res, double* d_current)
+{
     if (!ctx) return NSOF_EINVAL;
     if (!d_imgs || !d_w || !d_res || n_frames < 1 || height < 1 || width < 1 || n_sub_steps < 1)
         return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
+    Model model;
+    if (int rc = model_of(ctx, params, &model)) return rc;
+    const DevD& md = model.d;
     const size_t npx = (size_t)height * width;
     if (npx > 0xffffffffull - 63) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "grid of %zu pixels: too large for one launch", npx);
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    const double lambda = std::log(ROFF / RON);
-    hipLaunchKernelGGL(k_frames_run, dim3((unsigned)((npx + 63) / 64)), dim3(64), 0, ctx->stream, d_imgs, n_frames, d_w, d_res,
-                       d_current, npx, dt / n_sub_steps, n_sub_steps, th1, th2, lambda, RON / std::exp(-lambda * 0.5), v_ds);
+    with_frame_model(model, [&](auto D, auto fm) {
+        hipLaunchKernelGGL(k_frames_run<decltype(D)::value>, dim3((unsigned)((npx + 63) / 64)), dim3(64), 0, ctx->stream, d_imgs,
+                           n_frames, d_w, d_res, d_current, npx, dt / n_sub_steps, n_sub_steps, th1, th2, fm,
+                           md.ron / std::exp(-md.lambda * (1 - md.wini)), v_ds);
+    });
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }

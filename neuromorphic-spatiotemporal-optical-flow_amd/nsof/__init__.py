@@ -7,7 +7,7 @@ Mirrors the two interfaces the reference's scripts call on the hot path:
   ``cv2.calcOpticalFlowFarneback`` at /root/reference/optical_flow_seg.py:203
   (``farneback_params`` dict at :73-81); ``install()`` assigns it onto ``cv2`` so the
   reference's seg/ob/prediction scripts run unmodified where cv2 exists.
-* ``simulate(...)``, ``update_state(w, V)``, ``resistance_exp(w)`` -- the accumulator of
+* ``simulate(...)``, ``update_state(w, V, p, dt)``, ``resistance_exp(w, p)`` -- the accumulator of
   /root/reference/eventsim/event_mem_sim.py:40-63,164-286.
 
 All arithmetic runs in libnsof.so (HIP, gfx950).  No fallbacks.
@@ -20,7 +20,7 @@ from .farneback import (OPTFLOW_FARNEBACK_GAUSSIAN, OPTFLOW_USE_INITIAL_FLOW, Fa
                         farneback_roi_sequence_f32_dev,
                         farneback_sequence, install, level_size,
                         pinned_empty, uninstall)
-from .accumulator import (PARAMS, DT, THETA_EVENTS, REFRACTORY_US, Accumulator, bincount_2d,  # noqa: F401
+from .accumulator import (PARAMS, DT, THETA_EVENTS, REFRACTORY_US, Accumulator, accum_params, bincount_2d,  # noqa: F401
                           generate_synthetic_events, load_events, resistance_exp, simulate, simulate_frames, simulate_frames_dev,
                           slice_indices, update_state)
 

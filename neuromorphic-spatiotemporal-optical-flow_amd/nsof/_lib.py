@@ -34,6 +34,13 @@ class PairDesc(C.Structure):
                 ("flow", _vp), ("flow_stride", _pd)]
 
 
+class AccumParams(C.Structure):
+    """``nsof_accum_params`` of include/nsof.h: the accumulator's device model, dt and refractory time."""
+    _fields_ = [(k, _d) for k in ("alphaoff", "alphaon", "voff", "von", "koff", "kon", "son", "soff", "bon", "boff", "Ron",
+                                  "Roff", "wini", "dt")] + [("refractory_us", _i64)]
+
+
+_ap = C.POINTER(AccumParams)
 _ll = C.POINTER(C.c_longlong)
 _fb = [_d, _i, _i, _i, _i, _d, _i]   # pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags
 # The typed entry of each Farneback route: context, nsof_pixel_type, then the route's arguments.
@@ -87,6 +94,13 @@ SIGNATURES = {
     "nsof_prof_collect": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(C.c_longlong)]),
     "nsof_kernel_name": (C.c_char_p, [_i]),
     "nsof_accum_create": (_i, [_vp, _i, _i, _i, _i, _f, _f, C.POINTER(_vp)]),
+    "nsof_accum_default_params": (None, [_ap]),
+    "nsof_accum_create_p": (_i, [_vp, _i, _i, _i, _i, _f, _f, _ap, C.POINTER(_vp)]),
+    "nsof_accum_get_params": (_i, [_vp, _ap]),
+    "nsof_accum_update_state_p_dev": (_i, [_vp, _ap, _vp, _vp, _vp, _sz]),
+    "nsof_accum_resistance_p_dev": (_i, [_vp, _ap, _vp, _vp, _sz]),
+    "nsof_accum_frames_f64_p": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _ap, _vp, _vp]),
+    "nsof_accum_frames_f64_p_dev": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _d, _ap, _vp, _vp, _vp]),
     "nsof_accum_destroy": (None, [_vp]),
     "nsof_accum_set_dense": (_i, [_vp, _i]),
     "nsof_accum_reset": (_i, [_vp]),

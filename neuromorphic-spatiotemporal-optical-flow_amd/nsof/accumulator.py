@@ -1,7 +1,7 @@
 """Synaptic accumulator: host-side mirror of /root/reference/eventsim/event_mem_sim.py.
 
-Same names and argument meaning as the reference (``PARAMS``, ``DT``, ``update_state(w, V)``,
-``resistance_exp(w)``, ``slice_indices(t, slice_us)``, ``load_events(h5_path)``, ``simulate(...)``);
+Same names and argument meaning as the reference (``PARAMS``, ``DT``, ``REFRACTORY_US``, ``update_state(w, V, p, dt)``,
+``resistance_exp(w, p)``, ``slice_indices(t, slice_us)``, ``load_events(h5_path)``, ``simulate(...)``);
 the arithmetic runs in libnsof.so on the GPU.
 """
 import ctypes as C
@@ -15,7 +15,8 @@ from . import _lib
 from .context import default_context, dev_ptr
 from .errors import NsofValueError
 
-# event_mem_sim.py:20-34 (informational mirror; the device constants are compiled into libnsof.so)
+# event_mem_sim.py:20-34: the defaults of every ``p`` / ``params`` / ``dt`` / ``refractory_us`` argument below (the library's
+# own defaults, ``nsof_accum_default_params``, hold the same values).  won / woff are kept for the metadata file; nothing reads them.
 PARAMS = dict(alphaoff=1, alphaon=1, voff=-0.2, von=0.1, koff=51.03, kon=-2.91, son=0.2, soff=0.8,
               bon=-5.12, boff=3.10, Ron=163_305, Roff=2_104_377, won=1, woff=0, wini=0.5)
 DT = 5e-4
@@ -23,13 +24,55 @@ THETA_EVENTS = 1
 REFRACTORY_US = 800
 
 
+_PARAM_KEYS = ("alphaoff", "alphaon", "voff", "von", "koff", "kon", "son", "soff", "bon", "boff", "Ron", "Roff", "wini")
+
+
+def _number(name, v):
+    try:
+        return float(v)
+    except (TypeError, ValueError):
+        raise NsofValueError(f"accumulator parameter {name} = {v!r} is not a number") from None
+
+
+def accum_params(params=None, dt=None, refractory_us=None):
+    """The ``nsof_accum_params`` struct of a parameter mapping (``None``: ``PARAMS``), ``dt`` (``None``: ``DT``) and
+    ``refractory_us`` (``None``: ``REFRACTORY_US``).  A missing key raises ``NsofValueError`` naming it; extra keys (the
+    reference's ``won`` / ``woff``) are ignored.  The value checks are the library's (``NSOF_EINVAL`` before any launch)."""
+    p = PARAMS if params is None else params
+    try:
+        missing = [k for k in _PARAM_KEYS if k not in p]
+    except TypeError:
+        raise NsofValueError("params must be a mapping with the keys of nsof.PARAMS") from None
+    if missing:
+        raise NsofValueError(f"params lacks the key {missing[0]!r}" + (f" (and {missing[1:]})" if missing[1:] else ""))
+    out = _lib.AccumParams()
+    for k in _PARAM_KEYS:
+        setattr(out, k, _number(k, p[k]))
+    out.dt = _number("dt", DT if dt is None else dt)
+    r = REFRACTORY_US if refractory_us is None else refractory_us
+    if isinstance(r, float) and not r.is_integer():
+        raise NsofValueError(f"refractory_us = {r!r} is not a whole number of microseconds")
+    try:
+        out.refractory_us = int(r)
+    except (TypeError, ValueError, OverflowError):
+        raise NsofValueError(f"refractory_us = {r!r} is not a whole number of microseconds") from None
+    return out
+
+
+def _params_dict(ap):
+    """(params dict with the reference's keys, dt, refractory_us) of an ``AccumParams`` -- what the metadata file records."""
+    d = {k: getattr(ap, k) for k in _PARAM_KEYS}
+    return d, ap.dt, int(ap.refractory_us)
+
+
 def _torch():
     import torch
     return torch
 
 
-def update_state(w, V, *, ctx=None):  # noqa: N803
-    """``update_state(w, V)`` of event_mem_sim.py:40-57 for float32 arrays (numpy in -> numpy out)."""
+def update_state(w, V, p=PARAMS, dt=DT, *, ctx=None):  # noqa: N803
+    """``update_state(w, V, p=PARAMS, dt=DT)`` of event_mem_sim.py:40-57 for float32 arrays (numpy in -> numpy out)."""
+    ap = accum_params(p, dt)
     ctx = ctx or default_context()
     w = np.ascontiguousarray(w, np.float32)
     V = np.ascontiguousarray(V, np.float32)  # noqa: N806
@@ -40,14 +83,15 @@ def update_state(w, V, *, ctx=None):  # noqa: N803
     dw, dv = torch.from_numpy(w).to(dev), torch.from_numpy(V).to(dev)
     out = torch.empty_like(dw)
     torch.cuda.synchronize(dev)
-    ctx.check(ctx._lib.nsof_accum_update_state_dev(ctx.ptr, dev_ptr(dw), dev_ptr(dv), dev_ptr(out), w.size),
+    ctx.check(ctx._lib.nsof_accum_update_state_p_dev(ctx.ptr, C.byref(ap), dev_ptr(dw), dev_ptr(dv), dev_ptr(out), w.size),
               "update_state")
     ctx.synchronize()
     return out.cpu().numpy()
 
 
-def resistance_exp(w, *, ctx=None):
-    """``resistance_exp(w)`` of event_mem_sim.py:60-63, returned as float32 (as the reference stores it, :292)."""
+def resistance_exp(w, p=PARAMS, *, ctx=None):
+    """``resistance_exp(w, p=PARAMS)`` of event_mem_sim.py:60-63, returned as float32 (as the reference stores it, :292)."""
+    ap = accum_params(p)
     ctx = ctx or default_context()
     w = np.ascontiguousarray(w, np.float32)
     torch = _torch()
@@ -55,7 +99,7 @@ def resistance_exp(w, *, ctx=None):
     dw = torch.from_numpy(w).to(dev)
     out = torch.empty_like(dw)
     torch.cuda.synchronize(dev)
-    ctx.check(ctx._lib.nsof_accum_resistance_dev(ctx.ptr, dev_ptr(dw), dev_ptr(out), w.size), "resistance_exp")
+    ctx.check(ctx._lib.nsof_accum_resistance_p_dev(ctx.ptr, C.byref(ap), dev_ptr(dw), dev_ptr(out), w.size), "resistance_exp")
     ctx.synchronize()
     return out.cpu().numpy()
 
@@ -133,10 +177,15 @@ def load_events(h5_path):
 
 
 class Accumulator:
-    """Device-resident array state (w, refractory maps) that can be advanced chunk by chunk."""
+    """Device-resident array state (w, refractory maps) that can be advanced chunk by chunk.
+
+    ``params`` (a mapping with the keys of ``PARAMS``), ``dt`` and ``refractory_us`` give the device the array is made of
+    (``None``: the module's ``PARAMS`` / ``DT`` / ``REFRACTORY_US``); they are fixed for the accumulator's life and read
+    back as ``self.params`` / ``self.dt`` / ``self.refractory_us``."""
 
     def __init__(self, height, width, version=1, polarity="split", active_v=-8.0, silent_v=0.0, *, ctx=None,
-                 dense=None, frames_path=None):
+                 dense=None, frames_path=None, params=None, dt=None, refractory_us=None):
+        ap = accum_params(params, dt, refractory_us)
         if version not in (1, 2):
             raise NsofValueError("version must be 1 or 2")
         if polarity not in ("split", "magnitude"):
@@ -145,9 +194,13 @@ class Accumulator:
         self.H, self.W, self.version = int(height), int(width), version
         self.split = version == 2 and polarity == "split"
         p = C.c_void_p()
-        self.ctx.check(self.ctx._lib.nsof_accum_create(self.ctx.ptr, self.H, self.W, version, int(self.split),
-                                                       float(active_v), float(silent_v), C.byref(p)), "accum_create")
+        self.ctx.check(self.ctx._lib.nsof_accum_create_p(self.ctx.ptr, self.H, self.W, version, int(self.split),
+                                                         float(active_v), float(silent_v), C.byref(ap), C.byref(p)),
+                       "accum_create")
         self._p = p
+        used = _lib.AccumParams()
+        self.ctx.check(self.ctx._lib.nsof_accum_get_params(self._p, C.byref(used)), "accum_get_params")
+        self.params, self.dt, self.refractory_us = _params_dict(used)
         if dense is not None:   # None: automatic; True: the every-pixel pass; False: the event-pixel update where it is exact
             self.ctx.check(self.ctx._lib.nsof_accum_set_dense(self._p, 1 if dense else -1), "accum_set_dense")
         if frames_path is not None:   # run_frames: "tiles" (default where it applies) or "copy_patch"
@@ -312,7 +365,7 @@ class Accumulator:
 
 
 def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, save_video=False, polarity="split",
-             *, sensor_size=None, out_prefix=None, ctx=None, dense=None):
+             *, sensor_size=None, out_prefix=None, ctx=None, dense=None, params=None, dt=None, refractory_us=None):
     """``simulate`` of event_mem_sim.py:164-286.
 
     ``events``: an HDF5 path with a ``/CD/events`` group (as the reference) or a tuple ``(x, y, p, t)`` of arrays.
@@ -320,11 +373,15 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
     (every ``max(1, nslices // 100)`` slices).  With ``out_prefix`` (or an HDF5 path) the same
     ``.V{version}.npz`` / ``.V2_b.npz`` / ``.json.gz`` files as the reference (:289-322) are written.
     ``save_video`` is accepted for signature compatibility; MP4 previews are not produced.
+    ``params`` / ``dt`` / ``refractory_us``: the device model, as for ``Accumulator`` (the reference reads its module
+    globals ``PARAMS`` / ``REFRACTORY_US`` and ``update_state``'s default ``dt``).  The metadata file records the values
+    that were used.
     """
     if version not in (1, 2):
         raise NsofValueError("version must be 1 or 2")
     if polarity not in ("split", "magnitude"):
         raise NsofValueError("polarity must be 'split' or 'magnitude'")
+    accum_params(params, dt, refractory_us)   # a missing key is reported before the events are read
     h5_path = None
     if isinstance(events, (str, Path)):
         h5_path = Path(events)
@@ -341,7 +398,13 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
     idx = slice_index_array(t, slice_us)
     nslices = max(len(idx) - 1, 0)
     every = max(1, nslices // 100)
-    acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, dense=dense)
+    acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, dense=dense, params=params, dt=dt,
+                      refractory_us=refractory_us)
+    # what the metadata file records: the model this run uses, written with the caller's own numbers (the accumulator holds
+    # the same values as doubles; the defaults stay the integers the reference writes), plus won / woff, which nothing reads
+    src = PARAMS if params is None else params
+    used = ({k: src.get(k, PARAMS[k]) for k in PARAMS}, DT if dt is None else dt,
+            REFRACTORY_US if refractory_us is None else int(refractory_us))
     try:
         acc.step(x, y, p, t, idx, snap_every=every)
         snaps = acc.snapshots()
@@ -352,15 +415,17 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
         acc.close()
     prefix = Path(out_prefix) if out_prefix is not None else h5_path
     if prefix is not None:
-        _save_outputs(prefix, out, version, slice_us, polarity, h5_path)
+        _save_outputs(prefix, out, version, slice_us, polarity, h5_path, *used)
     return out
 
 
-def simulate_frames(compressed_images, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, *, ctx=None):
+def simulate_frames(compressed_images, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, *, ctx=None, params=None):
     """Frame-driven accumulator of /root/reference/simulation/simulationcode_v4_transistor_uav.m
     (``simulate_memristor_array``, :187-227): ``compressed_images`` float64 [n][H][W] in [0,1] (the output of the
     script's Lanczos ``compress_image``).  Returns ``(w_array, resistances_over_time)`` with the initial snapshot
-    first, as the script stores them.  uav: th1=0.7, th2=1.5; vehicle: th1=2."""
+    first, as the script stores them.  uav: th1=0.7, th2=1.5; vehicle: th1=2.  ``params``: the script's ``params`` struct as
+    a mapping with the keys of ``PARAMS`` (``None``: ``PARAMS``), read as float64; ``dt`` is the argument it is."""
+    ap = accum_params(params)
     ctx = ctx or default_context()
     imgs = np.ascontiguousarray(compressed_images, np.float64)
     if imgs.ndim != 3:
@@ -368,18 +433,19 @@ def simulate_frames(compressed_images, dt=0.0005, n_sub_steps=1000, th1=0.7, th2
     n, H, W = imgs.shape  # noqa: N806
     w = np.empty((H, W), np.float64)
     res = np.empty((n, H, W), np.float64)
-    ctx.check(ctx._lib.nsof_accum_frames_f64(ctx.ptr, imgs.ctypes.data, n, H, W, float(dt), int(n_sub_steps),
-                                             float(th1), float(th2), w.ctypes.data, res.ctypes.data),
+    ctx.check(ctx._lib.nsof_accum_frames_f64_p(ctx.ptr, imgs.ctypes.data, n, H, W, float(dt), int(n_sub_steps),
+                                               float(th1), float(th2), C.byref(ap), w.ctypes.data, res.ctypes.data),
               "simulate_frames")
     return w, res
 
 
-def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, v_ds=1.0, *, ctx=None):
+def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, v_ds=1.0, *, ctx=None, params=None):
     """``simulate_frames`` on a float64 CUDA tensor [n][H][W] (``frames.process_images_dev``'s output) in one launch
     (``nsof_accum_frames_f64_dev``): returns ``(w [H][W], resistances [n][H][W], current [n-1][H][W])`` as float64 CUDA
     tensors -- ``w`` and ``resistances`` equal ``simulate_frames`` bit for bit, ``current[f] = v_ds / resistances[f + 1]``
     is the device current after pair (f, f+1), the layout ``gating.roi_from_surface_dev`` reads.  Nothing is copied;
-    asynchronous on the context's stream."""
+    asynchronous on the context's stream.  ``params`` as for ``simulate_frames``."""
+    ap = accum_params(params)
     torch = _torch()
     if not isinstance(compressed, torch.Tensor) or not compressed.is_cuda:
         raise NsofValueError("simulate_frames_dev: a CUDA tensor expected", _lib.NSOF_EINVAL)
@@ -393,14 +459,19 @@ def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.
     w = torch.empty((H, W), dtype=torch.float64, device=dev)
     res = torch.empty((n, H, W), dtype=torch.float64, device=dev)
     cur = torch.empty((n - 1, H, W), dtype=torch.float64, device=dev)
-    ctx.check(ctx._lib.nsof_accum_frames_f64_dev(ctx.ptr, dev_ptr(compressed), n, H, W, float(dt), int(n_sub_steps),
-                                                 float(th1), float(th2), float(v_ds), dev_ptr(w), dev_ptr(res),
-                                                 dev_ptr(cur) if n > 1 else None), "simulate_frames_dev")
+    ctx.check(ctx._lib.nsof_accum_frames_f64_p_dev(ctx.ptr, dev_ptr(compressed), n, H, W, float(dt), int(n_sub_steps),
+                                                   float(th1), float(th2), float(v_ds), C.byref(ap), dev_ptr(w), dev_ptr(res),
+                                                   dev_ptr(cur) if n > 1 else None), "simulate_frames_dev")
     return w, res, cur
 
 
-def _save_outputs(prefix, out, version, slice_us, polarity, h5_path):
-    """File set of event_mem_sim.py:289-322 (npz keys ``w_final`` / ``resistances``; json.gz metadata)."""
+def _save_outputs(prefix, out, version, slice_us, polarity, h5_path, params=None, dt=None, refractory_us=None):
+    """File set of event_mem_sim.py:289-322 (npz keys ``w_final`` / ``resistances``; json.gz metadata).  The metadata holds
+    the parameters, dt and refractory time the run USED (the reference writes its module globals, which a dt overridden
+    through ``update_state``'s default does not reach)."""
+    params = dict(PARAMS) if params is None else params
+    dt = DT if dt is None else dt
+    refractory_us = REFRACTORY_US if refractory_us is None else refractory_us
     np.savez_compressed(prefix.with_suffix(f".V{version}.npz"), w_final=out["w_final"],
                         resistances=out["resistances"].astype(np.float32))
     if version == 2:
@@ -409,9 +480,9 @@ def _save_outputs(prefix, out, version, slice_us, polarity, h5_path):
                                 resistances=out["resistances_b"].astype(np.float32))
         else:
             np.savez_compressed(prefix.with_suffix(".V2_b.npz"), w_final=np.array([]), resistances=np.array([]))
-    meta = dict(version=version, slice_us=slice_us, fps=1_000_000 / slice_us, params=PARAMS, dt=DT,
+    meta = dict(version=version, slice_us=slice_us, fps=1_000_000 / slice_us, params=params, dt=dt,
                 scheme="boxcar" if version == 1 else "dc_bias_overlay", polarity=polarity if version == 2 else None,
                 theta_events=THETA_EVENTS if version == 1 else None,
-                refractory_us=REFRACTORY_US if version == 2 else None, event_file=str(h5_path or prefix))
+                refractory_us=refractory_us if version == 2 else None, event_file=str(h5_path or prefix))
     with gzip.open(prefix.with_suffix(f".V{version}.json.gz"), "wt") as fp:
         json.dump(meta, fp, indent=2)

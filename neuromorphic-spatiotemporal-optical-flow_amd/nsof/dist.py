@@ -287,6 +287,31 @@ def simulate_banded(x, y, p, t, sensor_hw, slice_us, simulate_band, dst=0, devic
     return tuple(outs) if isinstance(res, (tuple, list)) else outs[0]
 
 
+def accumulator_band(version=1, polarity="split", active_v=-8.0, silent_v=0.0, *, ctx=None, params=None, dt=None,
+                     refractory_us=None):
+    """The ``simulate_band`` callback of ``simulate_banded`` on a GPU: one ``Accumulator`` per band, ``set_events`` ->
+    ``set_slice_times`` -> ``run`` -> ``w``.  ``params`` / ``dt`` / ``refractory_us`` go to the accumulator unchanged."""
+    def simulate_band(xb, yb, pb, tb, idx, hw, slice_times):
+        import numpy as np
+
+        from .accumulator import Accumulator
+        rows, w = hw
+        split = version == 2 and polarity == "split"
+        if rows == 0:
+            empty = np.zeros((0, w), np.float32)
+            return (empty, empty.copy()) if split else empty
+        acc = Accumulator(rows, w, version, polarity, active_v, silent_v, ctx=ctx, params=params, dt=dt,
+                          refractory_us=refractory_us)
+        try:
+            acc.set_events(xb, yb, pb, tb, idx)
+            acc.set_slice_times(*slice_times)
+            acc.run(0, len(idx) - 1)
+            return (acc.w(0), acc.w(1)) if split else acc.w(0)
+        finally:
+            acc.close()
+    return simulate_band
+
+
 # ---- sequence end to end: accumulator bands -> surface frames on every rank -> pairs sharded (SURVEY.md section 8e) ----
 def events_to_flow_sharded(x, y, p, t, sensor_hw, slice_us, snapshot_every, band_frames, flow_of_frames, device=None,
                            stats=None):
