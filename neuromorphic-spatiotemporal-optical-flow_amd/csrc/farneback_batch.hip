@@ -305,14 +305,14 @@ int het_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const Params& p)
             // incoming flow of the level (resample of the coarser level's field, zero for items that start here), level
             // image and expansion: grids over the largest extents of a size class, one launch per class
             for (const HetClass& c : classes[k]) {
-                if ((rc = NSOF_PYR_SEL(ctx, nsof_launch_flow_upsample_het, c.count, dt + c.start, c.max_w, c.max_h, fb[cur],
+                if ((rc = nsof_launch_flow_upsample_het(ctx, c.count, dt + c.start, c.max_w, c.max_h, fb[cur],
                                        fb[cur ^ 1], (float)(1. / p.pyr_scale))))
                     return rc;
                 // level 0: the expansion kernel forms the level image from the 8- or 16-bit frames itself (see
                 // nsof_farneback_core); float frames take the two-kernel form
                 const bool fused0 = k == 0 && btaps.ksize == 3 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && p.src != NSOF_SRC_F32;
                 const float blur3[2] = {btaps.k[1], btaps.k[2]};
-                if (!fused0 && (rc = NSOF_PYR_SEL(ctx, nsof_launch_prep_het, c.count, dt + c.start, ht + c.start, k == 0, btaps, dI, p.src)))
+                if (!fused0 && (rc = nsof_launch_prep_het(ctx, c.count, dt + c.start, ht + c.start, k == 0, btaps, dI, p.src)))
                     return rc;
                 if ((rc = nsof_launch_polyexp_het(ctx, c.count, dt + c.start, c.max_w, c.max_h, ptaps, dI, dR, fused0 ? blur3 : nullptr,
                                                   p.src)))

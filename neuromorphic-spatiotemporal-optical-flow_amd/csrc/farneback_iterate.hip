@@ -336,33 +336,6 @@ int launch_iterate_q_het(nsof_ctx* ctx, int n_items, const nsof_het_item* items,
 
 }  // namespace
 
-template <typename... A>
-static int launch_iterate_q_m(int m, A... a)
-{
-    switch (m) {
-        case 1: return launch_iterate_q<1>(a...);
-        case 2: return launch_iterate_q<2>(a...);
-        case 3: return launch_iterate_q<3>(a...);
-        case 4: return launch_iterate_q<4>(a...);
-        case 5: return launch_iterate_q<5>(a...);
-        case 6: return launch_iterate_q<6>(a...);
-        default: return launch_iterate_q<7>(a...);
-    }
-}
-template <typename... A>
-static int launch_iterate_q_het_m(int m, A... a)
-{
-    switch (m) {
-        case 1: return launch_iterate_q_het<1>(a...);
-        case 2: return launch_iterate_q_het<2>(a...);
-        case 3: return launch_iterate_q_het<3>(a...);
-        case 4: return launch_iterate_q_het<4>(a...);
-        case 5: return launch_iterate_q_het<5>(a...);
-        case 6: return launch_iterate_q_het<6>(a...);
-        default: return launch_iterate_q_het<7>(a...);
-    }
-}
-
 // flow_in and flow_out must be different buffers (rows y+m of flow_in are read while row y of flow_out is written).
 int nsof_launch_iterate(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
                         const float* flow_in, float* flow_out, int W, int H, int winsize)
@@ -370,7 +343,11 @@ int nsof_launch_iterate(nsof_ctx* ctx, int n_pairs, const float* R0, const float
     const int m = winsize / 2;
     if (m < 1 || m > 7) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "fused iteration supports winsize 2..15");
     nsof_prof_scope ps(ctx, NSOF_K_ITERATE);
-    if (int rc = launch_iterate_q_m(m, ctx, n_pairs, R0, R1, pair_stride, flow_in, flow_out, W, H, winsize)) return rc;
+    int rc = NSOF_OK;
+    nsof_with_int<1, 7>(m, [&](auto mh) {
+        rc = launch_iterate_q<decltype(mh)::value>(ctx, n_pairs, R0, R1, pair_stride, flow_in, flow_out, W, H, winsize);
+    });
+    if (rc) return rc;
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
@@ -382,7 +359,11 @@ int nsof_launch_iterate_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_i
     const int m = winsize / 2;
     if (m < 1 || m > 7) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "work-list iteration supports winsize 2..15");
     nsof_prof_scope ps(ctx, NSOF_K_ITERATE);
-    if (int rc = launch_iterate_q_het_m(m, ctx, n_items, d_items, max_w, R, flow_in, flow_out, final, winsize)) return rc;
+    int rc = NSOF_OK;
+    nsof_with_int<1, 7>(m, [&](auto mh) {
+        rc = launch_iterate_q_het<decltype(mh)::value>(ctx, n_items, d_items, max_w, R, flow_in, flow_out, final, winsize);
+    });
+    if (rc) return rc;
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }

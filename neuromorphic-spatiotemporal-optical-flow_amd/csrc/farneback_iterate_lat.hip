@@ -375,15 +375,13 @@ int lat_rowscan(nsof_ctx* ctx, int n, int W, int H, int max_h, const double* V, 
                 const nsof_het_item* items, bool final)
 {
     const bool rows4 = (long long)((max_h + 3) / 4) * n <= 256;
-    switch (winsize / 2) {
-#define NSOF_LR(MM)                                                                                                  \
-    case MM:                                                                                                         \
-        return rows4 ? launch_lat_rowscan<MM, 4>(ctx, n, W, H, max_h, V, winsize, flow_out, items, final)            \
-                     : launch_lat_rowscan<MM, 8>(ctx, n, W, H, max_h, V, winsize, flow_out, items, final)
-        NSOF_LR(1); NSOF_LR(2); NSOF_LR(3); NSOF_LR(4); NSOF_LR(5); NSOF_LR(6); NSOF_LR(7);
-#undef NSOF_LR
-    }
-    return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "small-batch exact iteration supports winsize 2..15");
+    int rc = NSOF_OK;
+    const bool known = nsof_with_int<1, 7>(winsize / 2, [&](auto mh) {
+        constexpr int MH = decltype(mh)::value;
+        rc = rows4 ? launch_lat_rowscan<MH, 4>(ctx, n, W, H, max_h, V, winsize, flow_out, items, final)
+                   : launch_lat_rowscan<MH, 8>(ctx, n, W, H, max_h, V, winsize, flow_out, items, final);
+    });
+    return known ? rc : nsof_set_error(ctx, NSOF_EUNSUPPORTED, "small-batch exact iteration supports winsize 2..15");
 }
 
 }  // namespace

@@ -800,25 +800,17 @@ int launch_x(nsof_ctx* ctx, int n, int max_w, int max_h, const float* R0, const 
 
 }  // namespace
 
-#define NSOF_X_SWITCH(HETV, ...)                                                                     \
-    switch (winsize / 2) {                                                                           \
-        case 1: rc = launch_x<1, HETV>(__VA_ARGS__); break;                                          \
-        case 2: rc = launch_x<2, HETV>(__VA_ARGS__); break;                                          \
-        case 3: rc = launch_x<3, HETV>(__VA_ARGS__); break;                                          \
-        case 4: rc = launch_x<4, HETV>(__VA_ARGS__); break;                                          \
-        case 5: rc = launch_x<5, HETV>(__VA_ARGS__); break;                                          \
-        case 6: rc = launch_x<6, HETV>(__VA_ARGS__); break;                                          \
-        case 7: rc = launch_x<7, HETV>(__VA_ARGS__); break;                                          \
-        default: return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "exact-order fused iteration supports winsize 2..15"); \
-    }
-
 // Exact-order fused iteration (the library's running row sums).  flow_in != flow_out.
 int nsof_launch_iterate_x(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
                           const float* flow_in, float* flow_out, int W, int H, int winsize)
 {
     nsof_prof_scope ps(ctx, NSOF_K_ITERATE);
-    int rc;
-    NSOF_X_SWITCH(false, ctx, n_pairs, W, H, R0, R1, pair_stride, flow_in, flow_out, W, H, winsize, nullptr, false, nullptr, 0, 0)
+    int rc = NSOF_OK;
+    const bool known = nsof_with_int<1, 7>(winsize / 2, [&](auto mh) {
+        rc = launch_x<decltype(mh)::value, false>(ctx, n_pairs, W, H, R0, R1, pair_stride, flow_in, flow_out, W, H, winsize, nullptr,
+                                                  false, nullptr, 0, 0);
+    });
+    if (!known) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "exact-order fused iteration supports winsize 2..15");
     if (rc) return rc;
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
@@ -835,9 +827,12 @@ int nsof_launch_iterate_x_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d
     unsigned long long* carry;
     unsigned *tk, *er;
     if (int rc0 = nsof_xsync_reserve(ctx, R_floats * 4, &carry, &tk, &er)) return rc0;
-    int rc;
-    NSOF_X_SWITCH(true, ctx, n_items, max_w, max_h, R, R, (size_t)0, flow_in, flow_out, 0, 0, winsize, d_items, final, d_xjobs,
-                  stride, njobs)
+    int rc = NSOF_OK;
+    const bool known = nsof_with_int<1, 7>(winsize / 2, [&](auto mh) {
+        rc = launch_x<decltype(mh)::value, true>(ctx, n_items, max_w, max_h, R, R, (size_t)0, flow_in, flow_out, 0, 0, winsize, d_items,
+                                                 final, d_xjobs, stride, njobs);
+    });
+    if (!known) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "exact-order fused iteration supports winsize 2..15");
     if (rc) return rc;
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;

@@ -1,4 +1,6 @@
-// Farneback dense optical flow: HIP kernels for gfx950 (CDNA4, wave64).
+// Farneback dense optical flow, pyramid stage: the pyramid-level kernels (k_prep_*) and the coarse-to-fine flow resample
+// (k_flow_upsample*) for gfx950 (CDNA4, wave64).  The expansion is in farneback_polyexp.hip, the unfused box-window solve
+// in farneback_blur.hip, the iterations in farneback_iterate*.hip.
 //
 // Replaces the arithmetic the reference obtains from cv2.calcOpticalFlowFarneback
 // (call sites: /root/reference/optical_flow_seg.py:158,203,494 and the ob/prediction/yolo
@@ -6,42 +8,18 @@
 // placement (see DESIGN.md "numerics contract"); this translation unit is compiled with
 // -ffp-contract=off so that a*b+c stays two roundings unless fma() is written explicitly.
 //
-// All kernels are HBM/L2-bound stencils: no MFMA.  Layouts: images [n][h][w] f32,
-// R per image: [h][w][4] f32 (channels 0-3 interleaved: one 16-B access per pixel) followed by [h][w] f32 (channel 4)
-// -- the L1 serves 4 lanes per cycle whatever the access width, so the gather of the matrix update wants few, wide
-// loads.  M planar [n][5][h][w] f32 (unfused path only).  Flow [n][h][w][2].
+// All kernels are HBM/L2-bound stencils: no MFMA.  Layouts: images [n][h][w] f32, flow [n][h][w][2].
+//
+// Every kernel and the helpers between them take the arithmetic variant as their last template argument FMA: each tap
+// and blend is nsof_madd<FMA> (nsof_internal.h), the plain multiply-then-add or one fused multiply-add.  The launchers at
+// the end of the file read the variant from ctx->opt_pyr_fma (NSOF_OPT_PYR_FMA).
 #include <cstdlib>
 
 #include <type_traits>
 
 #include "nsof_internal.h"
 
-// This translation unit is compiled twice.  The regular object forms the float Gaussian blur and the bilinear resamples
-// (pyramid levels, flow resize) as the library's generic C++ path does: multiply, round, add, round.  With -DNSOF_PYR_FMA
-// (object farneback_kernels_fma.o) the same taps in the same order are CONTRACTED the way an AVX2+FMA3 build of the
-// library's vector code (v_muladd / v_fma in its separable-filter and resize loops) contracts them: one fused
-// multiply-add per tap / blend, the leading product still rounded -- the arithmetic variant twin of DESIGN.md section 2
-// (context option NSOF_OPT_PYR_FMA).  Only the pyramid-level and flow-resample launchers exist in that object.
-#ifdef NSOF_PYR_FMA
-#define NSOF_MADD(a, b, c) fmaf((a), (b), (c))
-#define NSOF_PYR_NAME(n) n##_fma
-#else
-#define NSOF_MADD(a, b, c) ((a) * (b) + (c))
-#define NSOF_PYR_NAME(n) n
-#endif
-
 namespace {
-
-__device__ __forceinline__ int reflect101(int p, int len)
-{
-    if ((unsigned)p < (unsigned)len) return p;
-    if (len == 1) return 0;
-    do {
-        if (p < 0) p = -p;
-        else p = 2 * len - 2 - p;
-    } while ((unsigned)p >= (unsigned)len);
-    return p;
-}
 
 // resize(INTER_LINEAR) coordinate: f = (float)((d+0.5)*scale-0.5); s = floor(f); a = f-s.
 __device__ __forceinline__ void lin_coord_x(int d, double scale, int slen, int& s, float& a)
@@ -105,26 +83,26 @@ __device__ __forceinline__ float quad_el(const PxQuad<T>& v, int e)
 // KS > 0: kernel size known at compile time (loops unroll, taps are scalar registers); KS == 0: runtime size,
 // the tap accessor `tk(j)` then reads a copy of the taps in LDS (a dynamically indexed kernel argument, or a
 // pointer to it, would be one dependent memory load per tap -- measured 10x slower).
-template <int KS, typename TapF, typename LoadF>
+template <int KS, bool FMA, typename TapF, typename LoadF>
 __device__ __forceinline__ float row_filter(TapF tk, int ksize, int c, LoadF ld)
 {
     const int ks = KS ? KS : ksize, r = ks >> 1;
-    if (ks == 3) return NSOF_MADD(ld(c - 1) + ld(c + 1), tk(2), ld(c) * tk(1));
-    if (ks == 5) return NSOF_MADD(ld(c - 2) + ld(c + 2), tk(4), NSOF_MADD(ld(c - 1) + ld(c + 1), tk(3), ld(c) * tk(2)));
+    if (ks == 3) return nsof_madd<FMA>(ld(c - 1) + ld(c + 1), tk(2), ld(c) * tk(1));
+    if (ks == 5) return nsof_madd<FMA>(ld(c - 2) + ld(c + 2), tk(4), nsof_madd<FMA>(ld(c - 1) + ld(c + 1), tk(3), ld(c) * tk(2)));
     float s = tk(0) * ld(c - r);
 #pragma unroll
-    for (int j = 1; j < ks; j++) s = NSOF_MADD(tk(j), ld(c - r + j), s);
+    for (int j = 1; j < ks; j++) s = nsof_madd<FMA>(tk(j), ld(c - r + j), s);
     return s;
 }
 // Column filter at (unreflected) row rr given an accessor of row-filtered values.
-template <int KS, typename TapF, typename LoadF>
+template <int KS, bool FMA, typename TapF, typename LoadF>
 __device__ __forceinline__ float col_filter(TapF tk, int ksize, int rr, LoadF hv)
 {
     const int ks = KS ? KS : ksize, r = ks >> 1;
-    if (ks == 3) return NSOF_MADD(hv(rr - 1) + hv(rr + 1), tk(2), hv(rr) * tk(1));
+    if (ks == 3) return nsof_madd<FMA>(hv(rr - 1) + hv(rr + 1), tk(2), hv(rr) * tk(1));
     float s = tk(r) * hv(rr);
 #pragma unroll
-    for (int j = 1; j <= r; j++) s = NSOF_MADD(tk(r + j), hv(rr + j) + hv(rr - j), s);
+    for (int j = 1; j <= r; j++) s = nsof_madd<FMA>(tk(r + j), hv(rr + j) + hv(rr - j), s);
     return s;
 }
 
@@ -157,7 +135,7 @@ __device__ __forceinline__ bool prep_geom(PrepImg<T>& g, const T* src, ptrdiff_t
 }
 
 // Same-size level (k = 0), generic: one thread per pixel, no resample.
-template <bool HET, typename T = uint8_t>
+template <bool HET, typename T, bool FMA>
 __global__ __launch_bounds__(256) void k_prep_same(const T* __restrict__ src, ptrdiff_t row_stride,
                                                     ptrdiff_t img_stride, int W, int H, nsof_blur_taps t,
                                                     float* __restrict__ out, const nsof_het_item* __restrict__ items,
@@ -176,9 +154,9 @@ __global__ __launch_bounds__(256) void k_prep_same(const T* __restrict__ src, pt
     const T* img = g.img;
     auto hv = [&](int rr) {
         const T* rowp = srow(img, reflect101(rr, H), row_stride);
-        return row_filter<0>(tk, t.ksize, x, [&](int c) { return px(rowp + reflect101(c, W)); });
+        return row_filter<0, FMA>(tk, t.ksize, x, [&](int c) { return px(rowp + reflect101(c, W)); });
     };
-    g.dst[(size_t)y * W + x] = col_filter<0>(tk, t.ksize, y, hv);
+    g.dst[(size_t)y * W + x] = col_filter<0, FMA>(tk, t.ksize, y, hv);
 }
 
 // Same-size level with the 3-tap kernel (every level 0): a lane owns 4 adjacent pixels of 8 consecutive rows.
@@ -188,7 +166,7 @@ __global__ __launch_bounds__(256) void k_prep_same(const T* __restrict__ src, pt
 // T = float / 16-bit: the lane's 4 pixels are one aligned 16-B / 8-B load per row (rows aligned to that, else
 // k_prep_same), the two outside values come from the neighbouring lanes the same way.
 constexpr int PREP0_ROWS = 8;
-template <bool HET, typename T = uint8_t>
+template <bool HET, typename T, bool FMA>
 __global__ __launch_bounds__(256) void k_prep_same3_vec(const T* __restrict__ src, ptrdiff_t row_stride,
                                                          ptrdiff_t img_stride, int W, int H, float k0, float k1,
                                                          float* __restrict__ out,
@@ -224,10 +202,10 @@ __global__ __launch_bounds__(256) void k_prep_same3_vec(const T* __restrict__ sr
             if (lane == 0 || x == 0) sl = px(rowp + reflect101(xl - 1, W));
             if (lane == 63 || x + 4 >= W) sr = px(rowp + reflect101(xl + 4, W));
         }
-        h[0] = NSOF_MADD(sl + s1, k1, s0 * k0);
-        h[1] = NSOF_MADD(s0 + s2, k1, s1 * k0);
-        h[2] = NSOF_MADD(s1 + s3, k1, s2 * k0);
-        h[3] = NSOF_MADD(s2 + sr, k1, s3 * k0);
+        h[0] = nsof_madd<FMA>(sl + s1, k1, s0 * k0);
+        h[1] = nsof_madd<FMA>(s0 + s2, k1, s1 * k0);
+        h[2] = nsof_madd<FMA>(s1 + s3, k1, s2 * k0);
+        h[3] = nsof_madd<FMA>(s2 + sr, k1, s3 * k0);
     };
     float hm[4], h0[4], hp[4];
     hrow(y0 - 1, hm);
@@ -239,10 +217,10 @@ __global__ __launch_bounds__(256) void k_prep_same3_vec(const T* __restrict__ sr
         hrow(y + 1, hp);
         if (live) {
             float4 o;
-            o.x = NSOF_MADD(hm[0] + hp[0], k1, h0[0] * k0);
-            o.y = NSOF_MADD(hm[1] + hp[1], k1, h0[1] * k0);
-            o.z = NSOF_MADD(hm[2] + hp[2], k1, h0[2] * k0);
-            o.w = NSOF_MADD(hm[3] + hp[3], k1, h0[3] * k0);
+            o.x = nsof_madd<FMA>(hm[0] + hp[0], k1, h0[0] * k0);
+            o.y = nsof_madd<FMA>(hm[1] + hp[1], k1, h0[1] * k0);
+            o.z = nsof_madd<FMA>(hm[2] + hp[2], k1, h0[2] * k0);
+            o.w = nsof_madd<FMA>(hm[3] + hp[3], k1, h0[3] * k0);
             nsof_store_stream4(dst + (size_t)y * W + x, o.x, o.y, o.z, o.w);
         }
 #pragma unroll
@@ -266,7 +244,7 @@ __global__ __launch_bounds__(256) void k_prep_same3_vec(const T* __restrict__ sr
 // side; rows 16- / 8-byte aligned), prefetching one output row ahead only at S = 2 for float -- a raw f32 row is four
 // times the registers of an 8-bit one -- and at S <= 4 for 16-bit, as for 8-bit.  Every load stays inside its row
 // (halo_l / halo_r below).
-template <int S, int KS, int CW, typename T = uint8_t>
+template <int S, int KS, int CW, typename T, bool FMA>
 __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdiff_t row_stride, ptrdiff_t img_stride,
                                                 int W, int H, int wk, int hk, int seg_rows, const nsof_blur_taps& t,
                                                 float* __restrict__ out, int bx, int seg, int z)
@@ -375,7 +353,7 @@ __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdi
 #pragma unroll
         for (int n = 0; n < NC; n++) {
             const int off = HB + S * (n >> 1) + S / 2 - 1 + (n & 1);
-            dstrow[n] = row_filter<KS>(tk, KS, off, [&](int q2) { return fb[q2]; });
+            dstrow[n] = row_filter<KS, FMA>(tk, KS, off, [&](int q2) { return fb[q2]; });
         }
     };
     auto load_row = [&](int r, float (&dstrow)[NC]) {
@@ -420,7 +398,7 @@ __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdi
 #pragma unroll
                 for (int j = 0; j < NPX; j++) {
                     auto col = [&](int n, int centre) {
-                        return col_filter<KS>(tk, KS, centre, [&](int q) { return ring[(S * u + q) % RING][n]; });
+                        return col_filter<KS, FMA>(tk, KS, centre, [&](int q) { return ring[(S * u + q) % RING][n]; });
                     };
                     const float B00 = col(2 * j, R), B01 = col(2 * j + 1, R);
                     const float B10 = col(2 * j, R + 1), B11 = col(2 * j + 1, R + 1);
@@ -444,13 +422,13 @@ __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdi
     }
 }
 
-template <int S, int KS, int CW, typename T = uint8_t>
+template <int S, int KS, int CW, typename T, bool FMA>
 __global__ __launch_bounds__(256) void k_prep_decim(const T* __restrict__ src, ptrdiff_t row_stride,
                                                      ptrdiff_t img_stride, int W, int H, int wk, int hk, int seg_rows,
                                                      nsof_blur_taps t, float* __restrict__ out)
 {
-    prep_decim_body<S, KS, CW, T>(src, row_stride, img_stride, W, H, wk, hk, seg_rows, t, out, blockIdx.x,
-                               blockIdx.y * 4 + (threadIdx.x >> 6), blockIdx.z);
+    prep_decim_body<S, KS, CW, T, FMA>(src, row_stride, img_stride, W, H, wk, hk, seg_rows, t, out, blockIdx.x,
+                                       blockIdx.y * 4 + (threadIdx.x >> 6), blockIdx.z);
 }
 
 // Levels 1, 2, 3 of a pyr_scale 0.5 pyramid in ONE launch: twelve waves per workgroup, four per level, all over the same
@@ -462,22 +440,22 @@ struct Decim3 {
     float* out[3];
     int seg_rows[3];
 };
-template <int CW, typename T = uint8_t>
+template <int CW, typename T, bool FMA>
 __global__ __launch_bounds__(768) void k_prep_decim3(const T* __restrict__ src, ptrdiff_t row_stride,
                                                       ptrdiff_t img_stride, int W, int H, Decim3 d)
 {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int seg = blockIdx.y * 4 + (wave & 3);
     if (wave < 4)
-        prep_decim_body<2, 3, CW, T>(src, row_stride, img_stride, W, H, W / 2, H / 2, d.seg_rows[0], d.t[0], d.out[0], blockIdx.x, seg, blockIdx.z);
+        prep_decim_body<2, 3, CW, T, FMA>(src, row_stride, img_stride, W, H, W / 2, H / 2, d.seg_rows[0], d.t[0], d.out[0], blockIdx.x, seg, blockIdx.z);
     else if (wave < 8)
-        prep_decim_body<4, 9, CW, T>(src, row_stride, img_stride, W, H, W / 4, H / 4, d.seg_rows[1], d.t[1], d.out[1], blockIdx.x, seg, blockIdx.z);
+        prep_decim_body<4, 9, CW, T, FMA>(src, row_stride, img_stride, W, H, W / 4, H / 4, d.seg_rows[1], d.t[1], d.out[1], blockIdx.x, seg, blockIdx.z);
     else
-        prep_decim_body<8, 19, CW, T>(src, row_stride, img_stride, W, H, W / 8, H / 8, d.seg_rows[2], d.t[2], d.out[2], blockIdx.x, seg, blockIdx.z);
+        prep_decim_body<8, 19, CW, T, FMA>(src, row_stride, img_stride, W, H, W / 8, H / 8, d.seg_rows[2], d.t[2], d.out[2], blockIdx.x, seg, blockIdx.z);
 }
 
 // Resampled level, generic fallback: one thread per destination pixel, no data sharing.
-template <bool HET, typename T = uint8_t>
+template <bool HET, typename T, bool FMA>
 __global__ __launch_bounds__(256) void k_prep_naive(const T* __restrict__ src, ptrdiff_t row_stride,
                                                      ptrdiff_t img_stride, int W, int H, int wk, int hk,
                                                      double scale_x, double scale_y, nsof_blur_taps t,
@@ -504,13 +482,13 @@ __global__ __launch_bounds__(256) void k_prep_naive(const T* __restrict__ src, p
     auto blur = [&](int rr, int cc) {
         auto hv = [&](int q) {
             const T* rowp = srow(img, reflect101(q, H), row_stride);
-            return row_filter<0>(tk, t.ksize, cc, [&](int c) { return px(rowp + reflect101(c, W)); });
+            return row_filter<0, FMA>(tk, t.ksize, cc, [&](int c) { return px(rowp + reflect101(c, W)); });
         };
-        return col_filter<0>(tk, t.ksize, rr, hv);
+        return col_filter<0, FMA>(tk, t.ksize, rr, hv);
     };
-    const float t0 = NSOF_MADD(blur(r0, c0), a0, blur(r0, c1) * a1);
-    const float t1 = NSOF_MADD(blur(r1, c0), a0, blur(r1, c1) * a1);
-    g.dst[(size_t)dy * wk + dx] = NSOF_MADD(t0, b0, t1 * b1);
+    const float t0 = nsof_madd<FMA>(blur(r0, c0), a0, blur(r0, c1) * a1);
+    const float t1 = nsof_madd<FMA>(blur(r1, c0), a0, blur(r1, c1) * a1);
+    g.dst[(size_t)dy * wk + dx] = nsof_madd<FMA>(t0, b0, t1 * b1);
 }
 
 // Resampled level, LDS-tiled: a 32x8 destination tile per 256-thread block.
@@ -520,7 +498,8 @@ __global__ __launch_bounds__(256) void k_prep_naive(const T* __restrict__ src, p
 //   phase 4: bilinear blend (horizontal first, then vertical, as resize does)
 // KS = compile-time kernel size (3, 5, 9, 19: pyr_scale 0.5 / 0.6 with up to 3 levels) or 0 = runtime.
 constexpr int PREP_TW = 32, PREP_TH = 8;
-template <int KS, bool HET, typename T = uint8_t>
+constexpr int tiled_ks(int ksize) { return ksize == 9 || ksize == 19 ? ksize : 0; }   // the KS a kernel size takes
+template <int KS, bool HET, typename T, bool FMA>
 __global__ __launch_bounds__(256) void k_prep_tiled(const T* __restrict__ src, ptrdiff_t row_stride,
                                                      ptrdiff_t img_stride, int W, int H, int wk, int hk,
                                                      double scale_x, double scale_y, int rw_cap, int rh_cap,
@@ -597,14 +576,14 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const T* __restrict__ src, p
 #pragma unroll 2
         for (int rr = wave; rr < RH; rr += 4) {
             const T* rowp = sU + rr * rw_cap;
-            sH[rr * (2 * PREP_TW) + lane] = row_filter<KS>(tk, ksize, cj, [&](int c) { return px(rowp + c); });
+            sH[rr * (2 * PREP_TW) + lane] = row_filter<KS, FMA>(tk, ksize, cj, [&](int c) { return px(rowp + c); });
         }
     }
     __syncthreads();
 #pragma unroll
     for (int q = wave; q < 2 * PREP_TH; q += 4)       // 16 sampled rows x 64 sampled columns
         sB[q * (2 * PREP_TW) + lane] =
-            col_filter<KS>(tk, ksize, s_r[q] - R0, [&](int rr) { return sH[rr * (2 * PREP_TW) + lane]; });
+            col_filter<KS, FMA>(tk, ksize, s_r[q] - R0, [&](int rr) { return sH[rr * (2 * PREP_TW) + lane]; });
     __syncthreads();
     const int tx = tid & 31, ty = tid >> 5;
     const int dx = dx0 + tx, dy = dy0 + ty;
@@ -612,9 +591,9 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const T* __restrict__ src, p
         const float a1 = s_a[tx], a0 = 1.f - a1, b1 = s_b[ty], b0 = 1.f - b1;
         const float* B0 = sB + (2 * ty) * (2 * PREP_TW) + 2 * tx;
         const float* B1 = B0 + 2 * PREP_TW;
-        const float t0 = NSOF_MADD(B0[0], a0, B0[1] * a1);
-        const float t1 = NSOF_MADD(B1[0], a0, B1[1] * a1);
-        g.dst[(size_t)dy * wk + dx] = NSOF_MADD(t0, b0, t1 * b1);
+        const float t0 = nsof_madd<FMA>(B0[0], a0, B0[1] * a1);
+        const float t1 = nsof_madd<FMA>(B1[0], a0, B1[1] * a1);
+        g.dst[(size_t)dy * wk + dx] = nsof_madd<FMA>(t0, b0, t1 * b1);
     }
 }
 
@@ -624,7 +603,7 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const T* __restrict__ src, p
 // contributes KS+1 consecutive bytes, fetched as unaligned dwords (L1/L2 resident: the u8 frame is 2 MB).
 // More arithmetic than the LDS-tiled variant but no per-tile overhead -- measured 3-6x faster at 1080p.
 // Pixels whose footprint leaves the image take a per-byte path with BORDER_REFLECT_101 indexing.
-template <int KS, bool HET, typename T = uint8_t>
+template <int KS, bool HET, typename T, bool FMA>
 __global__ __launch_bounds__(256) void k_prep_direct(const T* __restrict__ src, ptrdiff_t row_stride,
                                                       ptrdiff_t img_stride, int W, int H, int wk, int hk,
                                                       double scale_x, double scale_y, nsof_blur_taps t,
@@ -667,29 +646,29 @@ __global__ __launch_bounds__(256) void k_prep_direct(const T* __restrict__ src, 
 #pragma unroll
                 for (int j = 0; j < NB; j++) b[j] = rowp[c0 - R + j];
             }
-            H0[i] = row_filter<KS>(tk, KS, R, [&](int c) { return b[c]; });
-            H1[i] = row_filter<KS>(tk, KS, R + 1, [&](int c) { return b[c]; });
+            H0[i] = row_filter<KS, FMA>(tk, KS, R, [&](int c) { return b[c]; });
+            H1[i] = row_filter<KS, FMA>(tk, KS, R + 1, [&](int c) { return b[c]; });
         } else {
 #pragma unroll
             for (int j = 0; j < KS; j++) {
                 b[j] = px(rowp + reflect101(c0 - R + j, W));
                 bb[j] = px(rowp + reflect101(c1 - R + j, W));
             }
-            H0[i] = row_filter<KS>(tk, KS, R, [&](int c) { return b[c]; });
-            H1[i] = row_filter<KS>(tk, KS, R, [&](int c) { return bb[c]; });
+            H0[i] = row_filter<KS, FMA>(tk, KS, R, [&](int c) { return b[c]; });
+            H1[i] = row_filter<KS, FMA>(tk, KS, R, [&](int c) { return bb[c]; });
         }
     }
     // rows of H0/H1 are r0-R .. r0-R+KS; the window of r1 = r0+1 starts one entry later
-    const float B00 = col_filter<KS>(tk, KS, R, [&](int q) { return H0[q]; });
-    const float B01 = col_filter<KS>(tk, KS, R, [&](int q) { return H1[q]; });
+    const float B00 = col_filter<KS, FMA>(tk, KS, R, [&](int q) { return H0[q]; });
+    const float B01 = col_filter<KS, FMA>(tk, KS, R, [&](int q) { return H1[q]; });
     float B10 = B00, B11 = B01;
     if (r1 != r0) {
-        B10 = col_filter<KS>(tk, KS, R + 1, [&](int q) { return H0[q]; });
-        B11 = col_filter<KS>(tk, KS, R + 1, [&](int q) { return H1[q]; });
+        B10 = col_filter<KS, FMA>(tk, KS, R + 1, [&](int q) { return H0[q]; });
+        B11 = col_filter<KS, FMA>(tk, KS, R + 1, [&](int q) { return H1[q]; });
     }
-    const float t0 = NSOF_MADD(B00, a0, B01 * a1);
-    const float t1 = NSOF_MADD(B10, a0, B11 * a1);
-    g.dst[(size_t)dy * wk + dx] = NSOF_MADD(t0, b0, t1 * b1);
+    const float t0 = nsof_madd<FMA>(B00, a0, B01 * a1);
+    const float t1 = nsof_madd<FMA>(B10, a0, B11 * a1);
+    g.dst[(size_t)dy * wk + dx] = nsof_madd<FMA>(t0, b0, t1 * b1);
 }
 
 // Resampled level, walking: thread <-> destination column, a wave walks a segment of destination rows top to bottom.
@@ -715,7 +694,7 @@ __device__ __forceinline__ void prep_static_slots(F& f)
     }
 }
 
-template <int KS, bool WFAST, typename T = uint8_t>
+template <int KS, bool WFAST, typename T, bool FMA>
 __device__ __forceinline__ void prep_walk_body(const T* __restrict__ img, ptrdiff_t row_stride, int W, int H, int wk, int hk,
                                                double scale_y, int dy0, int dy_end, int dx, bool live, int c0, int c1, bool fast,
                                                float a1, const nsof_blur_taps& t, float* __restrict__ dst)
@@ -738,8 +717,8 @@ __device__ __forceinline__ void prep_walk_body(const T* __restrict__ img, ptrdif
 #pragma unroll
             for (int e = 0; e < PPD; e++)
                 if (PPD * d + e < NB) b[PPD * d + e] = px_el<T>(raw[d], e);
-        h0 = row_filter<KS>(tk, KS, R, [&](int c) { return b[c]; });
-        h1 = row_filter<KS>(tk, KS, R + 1, [&](int c) { return b[c]; });
+        h0 = row_filter<KS, FMA>(tk, KS, R, [&](int c) { return b[c]; });
+        h1 = row_filter<KS, FMA>(tk, KS, R + 1, [&](int c) { return b[c]; });
     };
     // border waves: per lane, per byte with BORDER_REFLECT_101 where the window leaves the image
     auto hrow_edge = [&](int rr, float& h0, float& h1) {
@@ -754,8 +733,8 @@ __device__ __forceinline__ void prep_walk_body(const T* __restrict__ img, ptrdif
                 float b[NB];
 #pragma unroll
                 for (int j = 0; j < NB; j++) b[j] = rowp[coff + j];
-                h0 = row_filter<KS>(tk, KS, R, [&](int c) { return b[c]; });
-                h1 = row_filter<KS>(tk, KS, R + 1, [&](int c) { return b[c]; });
+                h0 = row_filter<KS, FMA>(tk, KS, R, [&](int c) { return b[c]; });
+                h1 = row_filter<KS, FMA>(tk, KS, R + 1, [&](int c) { return b[c]; });
             }
         } else {
             float b[NB], bb[NB];
@@ -764,8 +743,8 @@ __device__ __forceinline__ void prep_walk_body(const T* __restrict__ img, ptrdif
                 b[j] = px(rowp + reflect101(c0 - R + j, W));
                 bb[j] = px(rowp + reflect101(c1 - R + j, W));
             }
-            h0 = row_filter<KS>(tk, KS, R, [&](int c) { return b[c]; });
-            h1 = row_filter<KS>(tk, KS, R, [&](int c) { return bb[c]; });
+            h0 = row_filter<KS, FMA>(tk, KS, R, [&](int c) { return b[c]; });
+            h1 = row_filter<KS, FMA>(tk, KS, R, [&](int c) { return bb[c]; });
         }
     };
     // destination row dy -> its two source rows and the vertical weight, all wave-uniform (SGPRs)
@@ -810,16 +789,16 @@ __device__ __forceinline__ void prep_walk_body(const T* __restrict__ img, ptrdif
             else hrow_edge(r, H0[u], H1[u]);
             if (r == last) {                                       // scalar
                 const float b0 = 1.f - b1;
-                const float B00 = col_filter<KS>(tk, KS, R, [&](int q) { return H0[(u + 1 + q) % NB]; });
-                const float B01 = col_filter<KS>(tk, KS, R, [&](int q) { return H1[(u + 1 + q) % NB]; });
+                const float B00 = col_filter<KS, FMA>(tk, KS, R, [&](int q) { return H0[(u + 1 + q) % NB]; });
+                const float B01 = col_filter<KS, FMA>(tk, KS, R, [&](int q) { return H1[(u + 1 + q) % NB]; });
                 float B10 = B00, B11 = B01;
                 if (r1 != r0) {
-                    B10 = col_filter<KS>(tk, KS, R + 1, [&](int q) { return H0[(u + 1 + q) % NB]; });
-                    B11 = col_filter<KS>(tk, KS, R + 1, [&](int q) { return H1[(u + 1 + q) % NB]; });
+                    B10 = col_filter<KS, FMA>(tk, KS, R + 1, [&](int q) { return H0[(u + 1 + q) % NB]; });
+                    B11 = col_filter<KS, FMA>(tk, KS, R + 1, [&](int q) { return H1[(u + 1 + q) % NB]; });
                 }
-                const float t0 = NSOF_MADD(B00, a0, B01 * a1);
-                const float t1 = NSOF_MADD(B10, a0, B11 * a1);
-                if (live) __builtin_nontemporal_store(NSOF_MADD(t0, b0, t1 * b1), dst + (size_t)dy * wk + dx);
+                const float t0 = nsof_madd<FMA>(B00, a0, B01 * a1);
+                const float t1 = nsof_madd<FMA>(B10, a0, B11 * a1);
+                if (live) __builtin_nontemporal_store(nsof_madd<FMA>(t0, b0, t1 * b1), dst + (size_t)dy * wk + dx);
                 dy++;
                 if (dy < dy_end) {
                     row_coord(dy, r0, r1, b1);
@@ -840,7 +819,7 @@ __device__ __forceinline__ void prep_walk_body(const T* __restrict__ img, ptrdif
 
 // T = float: every wave takes the per-lane form (prep_walk_body<KS, false>): a block of KS + 1 raw f32 rows in flight
 // would be (KS + 1)^2 registers per lane.  16-bit rows take the block form at twice the 8-bit registers.
-template <int KS, typename T = uint8_t>
+template <int KS, typename T, bool FMA>
 __global__ __launch_bounds__(256) void k_prep_walk(const T* __restrict__ src, ptrdiff_t row_stride,
                                                     ptrdiff_t img_stride, int W, int H, int wk, int hk, double scale_x,
                                                     double scale_y, int seg_rows, nsof_blur_taps t, float* __restrict__ out)
@@ -861,9 +840,9 @@ __global__ __launch_bounds__(256) void k_prep_walk(const T* __restrict__ src, pt
     const int c0 = sx, c1 = min(sx + 1, W - 1);
     const bool fast = c0 - R >= 0 && c0 - R + PPD * ND <= W && c1 == c0 + 1;
     if (kInt<T> && __all(fast))
-        prep_walk_body<KS, kInt<T>, T>(img, row_stride, W, H, wk, hk, scale_y, dy0, dy_end, dx, live, c0, c1, true, a1, t, dst);
+        prep_walk_body<KS, kInt<T>, T, FMA>(img, row_stride, W, H, wk, hk, scale_y, dy0, dy_end, dx, live, c0, c1, true, a1, t, dst);
     else
-        prep_walk_body<KS, false, T>(img, row_stride, W, H, wk, hk, scale_y, dy0, dy_end, dx, live, c0, c1, fast, a1, t, dst);
+        prep_walk_body<KS, false, T, FMA>(img, row_stride, W, H, wk, hk, scale_y, dy0, dy_end, dx, live, c0, c1, fast, a1, t, dst);
 }
 
 // Resampled level, two passes (kernel sizes 9 and 19: levels 2 and 3 of the reference's parameter sets).
@@ -875,7 +854,7 @@ __global__ __launch_bounds__(256) void k_prep_walk(const T* __restrict__ src, pt
 // Both are plain thread-per-output kernels (no LDS, no barriers, full occupancy); HA is 2-4 MB per frame and
 // is re-read from L2/MALL.  Same operation order as the tiled/direct kernels (bit-identical results).
 constexpr int PREPA_ROWS = 8;
-template <int KS, typename T = uint8_t>
+template <int KS, typename T, bool FMA>
 __global__ __launch_bounds__(256) void k_prep_rows(const T* __restrict__ src, ptrdiff_t row_stride,
                                                     ptrdiff_t img_stride, int W, int H, int wk, double scale_x,
                                                     nsof_blur_taps t, float* __restrict__ HA)
@@ -916,11 +895,11 @@ __global__ __launch_bounds__(256) void k_prep_rows(const T* __restrict__ src, pt
 #pragma unroll
             for (int i = 0; i < KS; i++) b[i] = px(rowp + reflect101(c - R + i, W));
         }
-        dst[(size_t)r * (2 * wk)] = row_filter<KS>(tk, KS, R, [&](int i) { return b[i]; });
+        dst[(size_t)r * (2 * wk)] = row_filter<KS, FMA>(tk, KS, R, [&](int i) { return b[i]; });
     }
 }
 
-template <int KS>
+template <int KS, bool FMA>
 __global__ __launch_bounds__(256) void k_prep_cols(const float* __restrict__ HA, int W, int H, int wk, int hk,
                                                     double scale_x, double scale_y, nsof_blur_taps t,
                                                     float* __restrict__ out)
@@ -944,634 +923,22 @@ __global__ __launch_bounds__(256) void k_prep_cols(const float* __restrict__ HA,
         H0[i] = h.x;
         H1[i] = h.y;
     }
-    const float B00 = col_filter<KS>(tk, KS, R, [&](int q) { return H0[q]; });
-    const float B01 = col_filter<KS>(tk, KS, R, [&](int q) { return H1[q]; });
+    const float B00 = col_filter<KS, FMA>(tk, KS, R, [&](int q) { return H0[q]; });
+    const float B01 = col_filter<KS, FMA>(tk, KS, R, [&](int q) { return H1[q]; });
     float B10 = B00, B11 = B01;
     if (r1 != r0) {
-        B10 = col_filter<KS>(tk, KS, R + 1, [&](int q) { return H0[q]; });
-        B11 = col_filter<KS>(tk, KS, R + 1, [&](int q) { return H1[q]; });
+        B10 = col_filter<KS, FMA>(tk, KS, R + 1, [&](int q) { return H0[q]; });
+        B11 = col_filter<KS, FMA>(tk, KS, R + 1, [&](int q) { return H1[q]; });
     }
-    const float t0 = NSOF_MADD(B00, a0, B01 * a1);
-    const float t1 = NSOF_MADD(B10, a0, B11 * a1);
-    out[((size_t)blockIdx.z * hk + dy) * wk + dx] = NSOF_MADD(t0, b0, t1 * b1);
-}
-
-// ---------------------------------------------------------------------------------------
-// Polynomial expansion (FarnebackPolyExp).  24 B/px algorithmic: 4 read + 5 x 4 written.
-//
-// "Strip walker": a block owns 256 image columns (SW output columns + NP halo on each side)
-// and walks down a row segment four rows per step.
-//   vertical pass   thread <-> column; the 2N+1 input rows of the column live in a register
-//                   window (one coalesced dword load per thread per new row, prefetched one
-//                   step ahead); r0/r1/r2 (float accumulation) go to LDS.
-//   horizontal pass wave <-> row, lane <-> 4 adjacent pixels; taps come from LDS as
-//                   ds_read_b128 and are reused across the 4 pixels in registers; in the exact
-//                   kernel (k_polyexp_rs) the six moments accumulate in double exactly as the
-//                   reference library does (b1,b4: double products -- exact, so written as fma;
-//                   b2,b3,b5,b6: float products widened afterwards); 5 coalesced float4 stores
-//                   per lane.
-// ---------------------------------------------------------------------------------------
-template <int N>
-struct PolyGeom {
-    static constexpr int NP = (N + 3) / 4 * 4;  // halo padded so LDS vectors stay 16-B aligned
-    static constexpr int SW = 256 - 2 * NP;     // output columns per block
-    static constexpr int NV = (2 * NP + 4) / 4; // float4 per lane per moment row
-};
-
-// The NSOF_OPT_POLYEXP_F32 kernel (opt-in, nsof_set_option): the horizontal moments accumulate in float (fma) instead
-// of double -- NOT the reference library's arithmetic; results differ from the exact kernel (k_polyexp_rs) in the last
-// bits of R (see DESIGN.md for the measured end-point error).  To keep the float sums small the image is taken relative
-// to a per-workgroup constant c (a constant image has zero derivatives, so the outputs do not depend on c; the
-// second-derivative outputs b1*ig03 + b5*ig33 cancel their two large terms, which is where float would lose most).
-// `items` is unused: the argument list is the one k_polyexp_rs shares with its work-list form.
-template <int N>
-__global__ __launch_bounds__(256) void k_polyexp(const float* __restrict__ img, float* __restrict__ R, int W, int H,
-                                                  int seg_rows, nsof_poly_taps tp,
-                                                  const nsof_het_item* __restrict__ items)
-{
-    using G = PolyGeom<N>;
-    const size_t img_off = (size_t)blockIdx.z * W * H;   // element offsets of this image / its expansion
-    const size_t r_off = (size_t)blockIdx.z * 5 * W * H;
-    __shared__ __attribute__((aligned(16))) float sr[2][3][4][256];
-    __shared__ float ftap[2][N + 1];   // g, xg for the horizontal pass when N is large (see below)
-    __shared__ float4 st[4][256];   // per-wave transpose buffer for the interleaved channel-0..3 stores
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid <= N) {
-        ftap[0][tid] = tp.g[tid];
-        ftap[1][tid] = tp.xg[tid];
-    }
-    const int x0 = blockIdx.x * G::SW;
-    const int ys = blockIdx.y * seg_rows, ye = min(ys + seg_rows, H);
-    const unsigned plane = (unsigned)W * (unsigned)H;
-    // wave-uniform bases + 32-bit byte offsets: loads/stores stay in "SGPR base + VGPR offset" form
-    const char* Ib = reinterpret_cast<const char*>(img + img_off);
-    char* Rb = reinterpret_cast<char*>(R + r_off);
-    const int xc = clampi(x0 - G::NP + tid, 0, W - 1);
-    auto ld = [&](int row) {
-        return *reinterpret_cast<const float*>(Ib + ((unsigned)clampi(row, 0, H - 1) * (unsigned)W + (unsigned)xc) * 4u);
-    };
-
-    // everything relative to the workgroup's first pixel
-    const float cref = *reinterpret_cast<const float*>(Ib + ((unsigned)clampi(ys, 0, H - 1) * (unsigned)W + (unsigned)clampi(x0, 0, W - 1)) * 4u);
-    // register window: win[j] = I[clamp(y - N + j)][xc]
-    float win[2 * N + 1];
-#pragma unroll
-    for (int j = 0; j <= 2 * N; j++) win[j] = ld(ys - N + j) - cref;
-    float pre[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) pre[q] = ld(ys + 1 + N + q) - cref;
-
-    int buf = 0;
-    for (int y = ys; y < ye; y += 4, buf ^= 1) {
-        float nxt[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) nxt[q] = ld(y + 5 + N + q) - cref;
-
-        // ---- vertical pass: 4 rows for this thread's column
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            float t0 = win[N] * tp.g[0], t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int k = 1; k <= N; k++) {
-                const float a = win[N - k], b = win[N + k];
-                const float p = a + b;
-                t0 = fmaf(tp.g[k], p, t0);
-                t2 = fmaf(tp.xxg[k], p, t2);
-                t1 = fmaf(tp.xg[k], b - a, t1);
-            }
-            sr[buf][0][q][tid] = t0;
-            sr[buf][1][q][tid] = t1;
-            sr[buf][2][q][tid] = t2;
-#pragma unroll
-            for (int j = 0; j < 2 * N; j++) win[j] = win[j + 1];
-            win[2 * N] = pre[q];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) pre[q] = nxt[q];
-        __syncthreads();
-
-        // ---- horizontal pass: wave <-> row, lane <-> 4 pixels; each moment row is consumed and its
-        //      outputs stored before the next one is read (keeps the live register set small)
-        const int yo = y + wave;
-        const int xo = x0 + 4 * lane;
-        if (4 * lane < G::SW && yo < ye && xo < W) {
-            const unsigned opix = (unsigned)yo * (unsigned)W + (unsigned)xo;
-            auto load_row = [&](int a, float (&v)[4 * G::NV]) {
-                const float4* p4 = reinterpret_cast<const float4*>(&sr[buf][a][wave][4 * lane]);
-#pragma unroll
-                for (int i = 0; i < G::NV; i++) {
-                    const float4 f = p4[i];
-                    v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w;
-                }
-            };
-            float o0[4], o1[4], o2[4], o3[4], o4[4];
-            // float accumulation, taps in registers (xxg included), one moment row at a time.  Large radii: the
-            // float taps would not fit the scalar register file (the spills cost more than the arithmetic), so g and
-            // xg come from LDS into VGPRs.
-            float fg[N + 1], fxg[N + 1], fxxg[N + 1];
-#pragma unroll
-            for (int k = 0; k <= N; k++) {
-                fg[k] = (N > 7) ? ftap[0][k] : tp.g[k];
-                fxg[k] = (N > 7) ? ftap[1][k] : tp.xg[k];
-                fxxg[k] = tp.xxg[k];
-            }
-            const float i11 = (float)tp.ig11, i03 = (float)tp.ig03, i33 = (float)tp.ig33, i55 = (float)tp.ig55;
-            float t03f[4];   // b1 * ig03, shared by the xx and yy outputs
-            {
-                float v[4 * G::NV];
-                load_row(0, v);
-#pragma unroll
-                for (int p = 0; p < 4; p++) {
-                    const int c = G::NP + p;
-                    float a1 = v[c] * fg[0], a2 = 0.f, a4 = 0.f;
-#pragma unroll
-                    for (int k = 1; k <= N; k++) {
-                        const float hi = v[c + k], lo = v[c - k], sm = hi + lo;
-                        a1 = fmaf(sm, fg[k], a1);
-                        a4 = fmaf(sm, fxxg[k], a4);
-                        a2 = fmaf(hi - lo, fxg[k], a2);
-                    }
-                    t03f[p] = a1 * i03;
-                    o1[p] = a2 * i11;
-                    o3[p] = fmaf(a4, i33, t03f[p]);
-                }
-            }
-            {
-                float v[4 * G::NV];
-                load_row(1, v);
-#pragma unroll
-                for (int p = 0; p < 4; p++) {
-                    const int c = G::NP + p;
-                    float a3 = v[c] * fg[0], a6 = 0.f;
-#pragma unroll
-                    for (int k = 1; k <= N; k++) {
-                        const float hi = v[c + k], lo = v[c - k];
-                        a3 = fmaf(hi + lo, fg[k], a3);
-                        a6 = fmaf(hi - lo, fxg[k], a6);
-                    }
-                    o0[p] = a3 * i11;
-                    o4[p] = a6 * i55;
-                }
-            }
-            {
-                float v[4 * G::NV];
-                load_row(2, v);
-#pragma unroll
-                for (int p = 0; p < 4; p++) {
-                    const int c = G::NP + p;
-                    float a5 = v[c] * fg[0];
-#pragma unroll
-                    for (int k = 1; k <= N; k++) a5 = fmaf(v[c + k] + v[c - k], fg[k], a5);
-                    o2[p] = fmaf(a5, i33, t03f[p]);
-                }
-            }
-            // channel 4 of the lane's 4 pixels: one 16-B store
-            float* c4 = reinterpret_cast<float*>(Rb) + 4u * plane + opix;
-            if ((W & 3) == 0) {
-                nsof_store_stream4(c4, o4[0], o4[1], o4[2], o4[3]);
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; p++)
-                    if (xo + p < W) c4[p] = o4[p];
-            }
-            // channels 0-3: a lane holds 4 consecutive pixels x 16 B; stored as is, one instruction would write 16 B
-            // per lane at a 64-B stride.  Transpose through LDS (per wave) so that every store instruction writes
-            // 64 consecutive pixels = 1 KiB contiguous.
-#pragma unroll
-            // (swizzled within each lane's 4 slots: unswizzled, the 8 lanes a ds_write_b128 serves per LDS cycle hit
-            //  only 2 of the 8 bank groups -- PMC: 63 % of this kernel's LDS cycles were bank conflicts)
-            for (int p = 0; p < 4; p++) st[wave][4 * lane + (p ^ ((lane >> 1) & 3))] = make_float4(o0[p], o1[p], o2[p], o3[p]);
-        }
-        {
-            // every lane of the wave takes part (lanes beyond the strip read slots nobody wrote, and do not store)
-            const int yo2 = y + wave;
-            float4* q4 = reinterpret_cast<float4*>(Rb) + (unsigned)yo2 * (unsigned)W + (unsigned)x0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int px = 64 * k + lane;   // pixel within the strip row
-                const float4 v = st[wave][(px & ~3) | ((px & 3) ^ ((px >> 3) & 3))];   // pixel px sits in lane px/4's slot
-                if (px < G::SW && yo2 < ye && x0 + px < W) nsof_store_stream4(reinterpret_cast<float*>(q4 + px), v.x, v.y, v.z, v.w);
-            }
-        }
-        // no second barrier: the next step writes the other LDS buffer (st is private to a wave)
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// Role-specialised strip walker (the default, the reference library's arithmetic): the same two passes as k_polyexp,
-// run by different waves.  A workgroup has 8 waves: waves 0-3 (thread <-> column) run the vertical pass
-// of step t+1 while waves 4-7 (wave <-> row, lane <-> 4 pixels) run the horizontal pass of step t on the other half of
-// the double-buffered moment rows; one barrier per step.  Neither role carries the other's registers across its
-// pass (the column window of 2N+1 rows on one side, the moment window and the double taps on the other), so the
-// taps stay in scalar registers and radius 10 fits 4 waves per SIMD where the single-role kernel spilled at 256.
-// Occupancy: 40 KiB of LDS lets 4 workgroups (8 waves per SIMD) share a CU when a wave fits 64 VGPRs and 80 SGPRs.  The
-// horizontal pass hands each output on as soon as it is final (moment row 2 before row 1, so b1 * ig03 dies early), which
-// keeps it near 46 VGPRs at N = 5 (82 when o0..o4 and t03 lived across all three rows: 2 workgroups per CU); for N <= 7
-// the launch bound asks for the 80 SGPRs, paid with a few scalar taps kept in VGPR lanes (v_readlane in the loop).
-// tests/test_codeobj_polyexp_budget.py holds the code object to that budget.
-// ---------------------------------------------------------------------------------------
-// FRAME (the full-resolution level): the level image is not read from memory but formed in the vertical pass from the
-// integer frame itself (SRC: uint8_t, uint16_t or int16_t pixels) -- the 3 x 3 [k1 k0 k1] smoothing of k_prep_same3_vec,
-// operation for operation -- so the pyramid kernel of level 0 and the 8 B/px its image costs (written there, read here)
-// disappear; the vertical-pass waves have the issue slots for it (187 of their step's ~500 instruction slots were used).
-struct PolyFrame {
-    const uint8_t* src0;   // images [0, nsplit) at src0 + z * img_stride, the others at src1 + (z - nsplit) * img_stride
-    const uint8_t* src1;   // (byte addresses)
-    long long row_stride, img_stride;
-    int nsplit;
-    float k0, k1;          // centre and side tap
-};
-template <int N, bool HET, bool FRAME = false, typename SRC = uint8_t>
-__global__ __launch_bounds__(512, N <= 7 ? 8 : 1) void k_polyexp_rs(const float* __restrict__ img, float* __restrict__ R, int W, int H,
-                                                     int seg_rows, nsof_poly_taps tp,
-                                                     const nsof_het_item* __restrict__ items, PolyFrame fr = PolyFrame{})
-{
-    using G = PolyGeom<N>;
-    size_t img_off, r_off;   // element offsets of this image / its expansion
-    const uint8_t* sb = nullptr;   // FRAME: this image's frame (byte address)
-    long long srs = 0;
-    if constexpr (HET) {
-        const nsof_het_item& it = items[blockIdx.z >> 1];
-        const size_t which = blockIdx.z & 1;
-        W = it.wk;
-        H = it.hk;
-        if (blockIdx.x * G::SW >= W || blockIdx.y * seg_rows >= H) return;   // block-uniform, before any barrier
-        img_off = it.offI + which * (size_t)W * H;
-        r_off = it.offR + which * 5 * (size_t)W * H;
-        if constexpr (FRAME) {
-            sb = it.src[which];
-            srs = it.src_stride[which];
-        }
-    } else {
-        img_off = (size_t)blockIdx.z * W * H;
-        r_off = (size_t)blockIdx.z * 5 * W * H;
-        if constexpr (FRAME) {
-            const int z = blockIdx.z;
-            sb = z < fr.nsplit ? fr.src0 + (ptrdiff_t)z * fr.img_stride : fr.src1 + (ptrdiff_t)(z - fr.nsplit) * fr.img_stride;
-            srs = fr.row_stride;
-        }
-    }
-    __shared__ __attribute__((aligned(16))) float sr[2][3][4][256];
-    // per-wave transpose buffer for the interleaved channel-0..3 stores, one plane per channel: st[wave][c][pixel]
-    __shared__ __attribute__((aligned(16))) float st[4][4][256];
-
-    const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;   // within the role
-    const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-    const int x0 = blockIdx.x * G::SW;
-    const int ys = blockIdx.y * seg_rows, ye = min(ys + seg_rows, H);
-    const int nsteps = (ye - ys + 3) / 4;
-    const unsigned plane = (unsigned)W * (unsigned)H;
-
-    if (role == 0) {
-        // ---- vertical pass: 4 rows per step for this thread's column
-        const char* Ib = reinterpret_cast<const char*>(img + img_off);
-        const int xc = clampi(x0 - G::NP + tid, 0, W - 1);
-        auto ld = [&](int row) {
-            return *reinterpret_cast<const float*>(Ib + ((unsigned)clampi(row, 0, H - 1) * (unsigned)W + (unsigned)xc) * 4u);
-        };
-        // FRAME: I[rc][xc] from the frame.  The rows are asked for in order, so the row-filtered values of rows rc - 1, rc,
-        // rc + 1 (reflected at the image border like the pyramid kernel's) are kept and one new row is filtered per
-        // new rc; fetch3() only issues the loads of a row's three bytes (four rows ahead, like the float loads).
-        const int xl = FRAME ? reflect101(xc - 1, W) : 0, xr = FRAME ? reflect101(xc + 1, W) : 0;
-        using RawPx = std::conditional_t<std::is_signed<SRC>::value, int, unsigned>;   // exact: sign- / zero-extended
-        struct Raw3 {
-            RawPx l, c, r;
-        };
-        auto fetch3 = [&](int srow) {   // srow: a row of the frame
-            const SRC* rp = reinterpret_cast<const SRC*>(sb + (ptrdiff_t)srow * srs);
-            return Raw3{rp[xl], rp[xc], rp[xr]};
-        };
-        auto hval = [&](const Raw3& q) { return NSOF_MADD((float)q.l + (float)q.r, fr.k1, (float)q.c * fr.k0); };
-        int rc_cur = 0;
-        float hm = 0.f, h0 = 0.f, hp = 0.f, icur = 0.f;
-        auto below = [&](int row) { return reflect101(clampi(row, 0, H - 1) + 1, H); };   // the frame row under clamp(row)
-        auto advance = [&](int row, const Raw3& under) {   // I[clamp(row)][xc]; under = fetch3(below(row))
-            const int rc = clampi(row, 0, H - 1);
-            if (rc != rc_cur) {   // block-uniform; rows come in order: rc == rc_cur + 1
-                hm = h0;
-                h0 = hp;
-                hp = hval(under);
-                icur = NSOF_MADD(hm + hp, fr.k1, h0 * fr.k0);
-                rc_cur = rc;
-            }
-            return icur;
-        };
-        float win[2 * N + 1];   // win[j] = I[clamp(y - N + j)][xc]
-        float pre[4];
-        Raw3 praw[4];
-        if constexpr (FRAME) {
-            rc_cur = clampi(ys - N, 0, H - 1);
-            hm = hval(fetch3(reflect101(rc_cur - 1, H)));
-            h0 = hval(fetch3(rc_cur));
-            hp = hval(fetch3(reflect101(rc_cur + 1, H)));
-            icur = NSOF_MADD(hm + hp, fr.k1, h0 * fr.k0);
-            win[0] = icur;
-#pragma unroll
-            for (int j = 1; j <= 2 * N; j++) win[j] = advance(ys - N + j, fetch3(below(ys - N + j)));
-#pragma unroll
-            for (int q = 0; q < 4; q++) pre[q] = advance(ys + 1 + N + q, fetch3(below(ys + 1 + N + q)));
-        } else {
-#pragma unroll
-            for (int j = 0; j <= 2 * N; j++) win[j] = ld(ys - N + j);
-#pragma unroll
-            for (int q = 0; q < 4; q++) pre[q] = ld(ys + 1 + N + q);
-        }
-        for (int t = 0; t <= nsteps; t++) {
-            if (t < nsteps) {
-                const int y = ys + 4 * t, buf = t & 1;
-                float nxt[4];
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    if constexpr (FRAME) praw[q] = fetch3(below(y + 5 + N + q));
-                    else nxt[q] = ld(y + 5 + N + q);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    float t0 = win[N] * tp.g[0], t1 = 0.f, t2 = 0.f;
-#pragma unroll
-                    for (int k = 1; k <= N; k++) {
-                        const float a = win[N - k], b = win[N + k];
-                        float p = a + b;
-                        t0 = t0 + tp.g[k] * p;
-                        t2 = t2 + tp.xxg[k] * p;
-                        p = b - a;
-                        t1 = t1 + tp.xg[k] * p;
-                    }
-                    sr[buf][0][q][tid] = t0;
-                    sr[buf][1][q][tid] = t1;
-                    sr[buf][2][q][tid] = t2;
-#pragma unroll
-                    for (int j = 0; j < 2 * N; j++) win[j] = win[j + 1];
-                    win[2 * N] = pre[q];
-                }
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    if constexpr (FRAME) pre[q] = advance(y + 5 + N + q, praw[q]);
-                    else pre[q] = nxt[q];
-                }
-            }
-            __syncthreads();
-        }
-        return;
-    }
-
-    // ---- horizontal pass: wave <-> row, lane <-> 4 pixels, one step behind the vertical pass
-    char* Rb = reinterpret_cast<char*>(R + r_off);
-    for (int t = 0; t <= nsteps; t++) {
-        if (t >= 1) {
-            const int y = ys + 4 * (t - 1), buf = (t - 1) & 1;
-            const int yo = y + wave;
-            const int xo = x0 + 4 * lane;
-            if (4 * lane < G::SW && yo < ye && xo < W) {
-                const unsigned opix = (unsigned)yo * (unsigned)W + (unsigned)xo;
-                auto load_row = [&](int a, float (&v)[4 * G::NV]) {
-                    const float4* p4 = reinterpret_cast<const float4*>(&sr[buf][a][wave][4 * lane]);
-#pragma unroll
-                    for (int i = 0; i < G::NV; i++) {
-                        const float4 f = p4[i];
-                        v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w;
-                    }
-                };
-                // each output goes out (to the transpose planes, or to memory) as soon as it is final, and moment row 2
-                // is taken before row 1 so that b1 * ig03 dies early: the live set stays one tap row plus the sums
-                auto put = [&](int c, const float (&o)[4]) {   // lane's 4 pixels of channel c: one conflict-free ds_write_b128
-                    *reinterpret_cast<float4*>(&st[wave][c][4 * lane]) = make_float4(o[0], o[1], o[2], o[3]);
-                };
-                double t03[4];  // b1 * ig03, shared by the xx and yy outputs
-                {
-                    float v[4 * G::NV], o1[4], o3[4];
-                    load_row(0, v);
-#pragma unroll
-                    for (int p = 0; p < 4; p++) {
-                        const int c = G::NP + p;
-                        double a1 = (double)(v[c] * tp.g[0]), a2 = 0, a4 = 0;
-#pragma unroll
-                        for (int k = 1; k <= N; k++) {
-                            const float hi = v[c + k], lo = v[c - k];
-                            const double tg = (double)(hi + lo);
-                            a1 = fma(tg, tp.dg[k], a1);     // product of two float-valued doubles is exact
-                            a4 = fma(tg, tp.dxxg[k], a4);
-                            a2 += (double)((hi - lo) * tp.xg[k]);
-                        }
-                        t03[p] = a1 * tp.ig03;
-                        o1[p] = (float)(a2 * tp.ig11);
-                        o3[p] = (float)(t03[p] + a4 * tp.ig33);
-                    }
-                    put(1, o1);
-                    put(3, o3);
-                }
-                {
-                    float v[4 * G::NV], o2[4];
-                    load_row(2, v);
-#pragma unroll
-                    for (int p = 0; p < 4; p++) {
-                        const int c = G::NP + p;
-                        double a5 = (double)(v[c] * tp.g[0]);
-#pragma unroll
-                        for (int k = 1; k <= N; k++) a5 += (double)((v[c + k] + v[c - k]) * tp.g[k]);
-                        o2[p] = (float)(t03[p] + a5 * tp.ig33);
-                    }
-                    put(2, o2);
-                }
-                {
-                    float v[4 * G::NV], o0[4], o4[4];
-                    load_row(1, v);
-#pragma unroll
-                    for (int p = 0; p < 4; p++) {
-                        const int c = G::NP + p;
-                        double a3 = (double)(v[c] * tp.g[0]), a6 = 0;
-#pragma unroll
-                        for (int k = 1; k <= N; k++) {
-                            const float hi = v[c + k], lo = v[c - k];
-                            a3 += (double)((hi + lo) * tp.g[k]);
-                            a6 += (double)((hi - lo) * tp.xg[k]);
-                        }
-                        o0[p] = (float)(a3 * tp.ig11);
-                        o4[p] = (float)(a6 * tp.ig55);
-                    }
-                    put(0, o0);
-                    float* c4 = reinterpret_cast<float*>(Rb) + 4u * plane + opix;
-                    if ((W & 3) == 0) {
-                        nsof_store_stream4(c4, o4[0], o4[1], o4[2], o4[3]);
-                    } else {
-#pragma unroll
-                        for (int p = 0; p < 4; p++)
-                            if (xo + p < W) c4[p] = o4[p];
-                    }
-                }
-            }
-            {
-                // every lane of the wave takes part (lanes beyond the strip read slots nobody wrote, and do not store)
-                float4* q4 = reinterpret_cast<float4*>(Rb) + (unsigned)yo * (unsigned)W + (unsigned)x0;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int px = 64 * k + lane;   // pixel within the strip row
-                    const float* s = &st[wave][0][px];
-                    if (px < G::SW && yo < ye && x0 + px < W) nsof_store_stream4(reinterpret_cast<float*>(q4 + px), s[0], s[256], s[512], s[768]);
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// FarnebackUpdateFlow_Blur: (2m+1)^2 box sums of the 5 planes of M + per-pixel 2x2 solve.
-//
-// Strip walker over the full image height (the column sums are a running sum from row 0:
-// each row adds double(float(M[y+m] - M[y-m-1])) -- the float rounding of the difference is
-// part of the reference arithmetic and is reproduced).  thread <-> column keeps the 5
-// column sums in registers as doubles; 4 rows per step go to LDS; wave <-> row, lane <-> 4
-// pixels forms the row sums (first pixel direct, then sliding) and solves.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_blur_solve(const float* __restrict__ M, int W, int H, int m, int block_size,
-                                                     float* __restrict__ flow)
-{
-    __shared__ double sv[4][5][256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int SW = (256 - 2 * m) & ~3;  // multiple of 4: every lane owns 4 whole pixels
-    const int x0 = blockIdx.x * SW;
-    const size_t plane = (size_t)W * H;
-    const float* Mz = M + (size_t)blockIdx.z * 5 * plane;
-    float2* fz = reinterpret_cast<float2*>(flow) + (size_t)blockIdx.z * plane;
-    const int xc = clampi(x0 - m + tid, 0, W - 1);
-    const float* Mc = Mz + xc;
-    const double scale = 1. / (block_size * block_size);
-
-    double vs[5];
-#pragma unroll
-    for (int c = 0; c < 5; c++) {
-        vs[c] = (double)(Mc[c * plane] * (float)(m + 2));  // float product, as "srow0[x]*(m+2)"
-        for (int y = 1; y < m; y++) vs[c] += (double)Mc[c * plane + (size_t)min(y, H - 1) * W];
-    }
-    float pa[4][5], pb[4][5];
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-#pragma unroll
-        for (int c = 0; c < 5; c++) {
-            pa[q][c] = Mc[c * plane + (size_t)min(q + m, H - 1) * W];
-            pb[q][c] = Mc[c * plane + (size_t)max(q - m - 1, 0) * W];
-        }
-
-    for (int y = 0; y < H; y += 4) {
-        float na[4][5], nb[4][5];
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-#pragma unroll
-            for (int c = 0; c < 5; c++) {
-                na[q][c] = Mc[c * plane + (size_t)min(y + 4 + q + m, H - 1) * W];
-                nb[q][c] = Mc[c * plane + (size_t)max(y + 4 + q - m - 1, 0) * W];
-            }
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-#pragma unroll
-            for (int c = 0; c < 5; c++) {
-                const float d = pa[q][c] - pb[q][c];
-                vs[c] += (double)d;
-                sv[q][c][tid] = vs[c];
-            }
-        __syncthreads();
-        const int yo = y + wave, xo = x0 + 4 * lane;
-        if (4 * lane < SW && yo < H && xo < W) {
-            double g[5];
-            float2 o[4];
-#pragma unroll
-            for (int p = 0; p < 4; p++) {
-                if (p == 0) {
-#pragma unroll
-                    for (int c = 0; c < 5; c++) {
-                        double s = 0;
-                        for (int j = 0; j <= 2 * m; j++) s += sv[wave][c][4 * lane + j];
-                        g[c] = s;
-                    }
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 5; c++)
-                        g[c] += sv[wave][c][4 * lane + p + 2 * m] - sv[wave][c][4 * lane + p - 1];
-                }
-                o[p] = nsof_flow_solve(g[0], g[1], g[2], g[3], g[4], scale);
-            }
-            float2* dst = fz + (size_t)yo * W + xo;
-#pragma unroll
-            for (int p = 0; p < 4; p++)
-                if (4 * lane + p < SW && xo + p < W) dst[p] = o[p];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-#pragma unroll
-            for (int c = 0; c < 5; c++) {
-                pa[q][c] = na[q][c];
-                pb[q][c] = nb[q][c];
-            }
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// FarnebackUpdateFlow_Blur in the reference library's EXACT summation order (NSOF_OPT_EXACT_ROWSUMS).
-//
-// The library forms the (2m+1)-wide ROW sums as ONE running sum along the whole image row, in double:
-// g += vsum[x+m] - vsum[x-m-1] for x = 0..W-1.  The production kernels sum each pixel's window directly -- the same
-// numbers to about 1e-16 relative.  Where the 2x2 system is rank deficient (straight edges, flat areas: g11*g22 -
-// g12^2 cancels down to the 1e-3 regulariser) those last bits decide the flow's 4th decimal, so on real footage a few
-// pixels per frame differ from the library by 1e-4..1e-3.  This pair of kernels reproduces the
-// library's order bit for bit at roughly half the speed: the column sums go to HBM (transposed, 40 B/px) and a
-// thread walks each image row from left to right.
-// ---------------------------------------------------------------------------------------
-// thread <-> column: vertical running sums of the 5 planes of M -> VT [n][5][W][H] (transposed: row index fastest)
-__global__ __launch_bounds__(256) void k_blur_colsum(const float* __restrict__ M, int W, int H, int m,
-                                                      double* __restrict__ VT)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    if (x >= W) return;
-    const size_t plane = (size_t)W * H;
-    const float* Mc = M + (size_t)blockIdx.z * 5 * plane + x;
-    double* V = VT + (size_t)blockIdx.z * 5 * plane + (size_t)x * H;
-    double vs[5];
-#pragma unroll
-    for (int c = 0; c < 5; c++) {
-        vs[c] = (double)(Mc[c * plane] * (float)(m + 2));   // float product, as "srow0[x]*(m+2)"
-        for (int y = 1; y < m; y++) vs[c] += (double)Mc[c * plane + (size_t)min(y, H - 1) * W];
-    }
-    for (int y = 0; y < H; y++) {
-        const size_t ra = (size_t)min(y + m, H - 1) * W, rb = (size_t)max(y - m - 1, 0) * W;
-#pragma unroll
-        for (int c = 0; c < 5; c++) {
-            const float d = Mc[c * plane + ra] - Mc[c * plane + rb];   // rounded to float before it is added
-            vs[c] += (double)d;
-            V[c * plane + y] = vs[c];
-        }
-    }
-}
-
-// thread <-> row: the library's running row sums + the 2x2 solve, left to right
-__global__ __launch_bounds__(64) void k_blur_rowsolve(const double* __restrict__ VT, int W, int H, int m, int block_size,
-                                                       float* __restrict__ flow)
-{
-    const int y = blockIdx.x * 64 + threadIdx.x;
-    if (y >= H) return;
-    const size_t plane = (size_t)W * H;
-    const double* V = VT + (size_t)blockIdx.z * 5 * plane + y;          // V[c*plane + x*H]
-    float2* fz = reinterpret_cast<float2*>(flow) + (size_t)blockIdx.z * plane + (size_t)y * W;
-    const double scale = 1. / (block_size * block_size);
-    auto at = [&](int c, int x) { return V[c * plane + (size_t)clampi(x, 0, W - 1) * H]; };
-    double g[5];
-#pragma unroll
-    for (int c = 0; c < 5; c++) {
-        g[c] = at(c, 0) * (m + 2);
-        for (int x = 1; x < m; x++) g[c] += at(c, x);
-    }
-    for (int x = 0; x < W; x++) {
-#pragma unroll
-        for (int c = 0; c < 5; c++) g[c] += at(c, x + m) - at(c, x - m - 1);
-        fz[x] = nsof_flow_solve(g[0], g[1], g[2], g[3], g[4], scale);
-    }
+    const float t0 = nsof_madd<FMA>(B00, a0, B01 * a1);
+    const float t1 = nsof_madd<FMA>(B10, a0, B11 * a1);
+    out[((size_t)blockIdx.z * hk + dy) * wk + dx] = nsof_madd<FMA>(t0, b0, t1 * b1);
 }
 
 // ---------------------------------------------------------------------------------------
 // Coarse-to-fine flow resample: resize(prevFlow, INTER_LINEAR) then "flow *= 1/pyr_scale".
 // ---------------------------------------------------------------------------------------
+template <bool FMA>
 __global__ __launch_bounds__(256) void k_flow_upsample(const float* __restrict__ src, int sw, int sh,
                                                         float* __restrict__ dst, int dw, int dh, double scale_x,
                                                         double scale_y, float mul)
@@ -1591,12 +958,12 @@ __global__ __launch_bounds__(256) void k_flow_upsample(const float* __restrict__
     const float2 p10 = S[(size_t)r1 * sw + sx], p11 = S[(size_t)r1 * sw + c1];
     float2 o;
     {
-        const float t0 = NSOF_MADD(p00.x, a0, p01.x * a1), t1 = NSOF_MADD(p10.x, a0, p11.x * a1);
-        o.x = NSOF_MADD(t0, b0, t1 * b1) * mul;
+        const float t0 = nsof_madd<FMA>(p00.x, a0, p01.x * a1), t1 = nsof_madd<FMA>(p10.x, a0, p11.x * a1);
+        o.x = nsof_madd<FMA>(t0, b0, t1 * b1) * mul;
     }
     {
-        const float t0 = NSOF_MADD(p00.y, a0, p01.y * a1), t1 = NSOF_MADD(p10.y, a0, p11.y * a1);
-        o.y = NSOF_MADD(t0, b0, t1 * b1) * mul;
+        const float t0 = nsof_madd<FMA>(p00.y, a0, p01.y * a1), t1 = nsof_madd<FMA>(p10.y, a0, p11.y * a1);
+        o.y = nsof_madd<FMA>(t0, b0, t1 * b1) * mul;
     }
     reinterpret_cast<float2*>(dst)[((size_t)blockIdx.z * dh + dy) * dw + dx] = o;
 }
@@ -1605,7 +972,7 @@ __global__ __launch_bounds__(256) void k_flow_upsample(const float* __restrict__
 // consecutive destination coordinates map to source coordinates at most one apart, so the block's 4 pixels
 // sample from a 3x3 source neighbourhood: 9 float2 loads + 2 float4 stores per 4 pixels instead of 16 + 4 (the L1
 // serves 4 lanes per cycle per instruction, whatever its width).  Same arithmetic per pixel as k_flow_upsample.
-template <bool HET>
+template <bool HET, bool FMA>
 __global__ __launch_bounds__(256) void k_flow_upsample2x2(const float* __restrict__ src, int sw, int sh,
                                                            float* __restrict__ dst, int dw, int dh, double scale_x,
                                                            double scale_y, float mul,
@@ -1665,12 +1032,12 @@ __global__ __launch_bounds__(256) void k_flow_upsample2x2(const float* __restric
             const float2 p10 = ro ? (co ? v[2][1] : v[2][0]) : (co ? v[1][1] : v[1][0]);
             const float2 p11 = ro ? (co ? v[2][2] : v[2][1]) : (co ? v[1][2] : v[1][1]);
             {
-                const float t0 = NSOF_MADD(p00.x, aa0, p01.x * aa1), t1 = NSOF_MADD(p10.x, aa0, p11.x * aa1);
-                o[j].x = NSOF_MADD(t0, bb0, t1 * bb1) * mul;
+                const float t0 = nsof_madd<FMA>(p00.x, aa0, p01.x * aa1), t1 = nsof_madd<FMA>(p10.x, aa0, p11.x * aa1);
+                o[j].x = nsof_madd<FMA>(t0, bb0, t1 * bb1) * mul;
             }
             {
-                const float t0 = NSOF_MADD(p00.y, aa0, p01.y * aa1), t1 = NSOF_MADD(p10.y, aa0, p11.y * aa1);
-                o[j].y = NSOF_MADD(t0, bb0, t1 * bb1) * mul;
+                const float t0 = nsof_madd<FMA>(p00.y, aa0, p01.y * aa1), t1 = nsof_madd<FMA>(p10.y, aa0, p11.y * aa1);
+                o[j].y = nsof_madd<FMA>(t0, bb0, t1 * bb1) * mul;
             }
         }
         float2* drow = D + (size_t)(dy0 + i) * dw + dx0;
@@ -1689,6 +1056,7 @@ __global__ __launch_bounds__(256) void k_flow_upsample2x2(const float* __restric
 // 2-3 destination rows that sample that source row.  Per-pixel arithmetic and its order are those of
 // k_flow_upsample.
 constexpr int UPW_SEG = 32;
+template <bool FMA>
 __global__ __launch_bounds__(256) void k_flow_upsample_walk(const float* __restrict__ src, int sw, int sh,
                                                              float* __restrict__ dst, int dw, int dh, double scale_x,
                                                              double scale_y, float mul)
@@ -1729,8 +1097,8 @@ __global__ __launch_bounds__(256) void k_flow_upsample_walk(const float* __restr
 #pragma unroll
         for (int i = 0; i < NPL; i++) {
             const float2 p0 = pick(V, i0[i]), p1 = pick(V, i1[i]);
-            h[i].x = NSOF_MADD(p0.x, a0[i], p1.x * a1[i]);
-            h[i].y = NSOF_MADD(p0.y, a0[i], p1.y * a1[i]);
+            h[i].x = nsof_madd<FMA>(p0.x, a0[i], p1.x * a1[i]);
+            h[i].y = nsof_madd<FMA>(p0.y, a0[i], p1.y * a1[i]);
         }
     };
     float2 hA[NPL], hB[NPL];
@@ -1760,8 +1128,8 @@ __global__ __launch_bounds__(256) void k_flow_upsample_walk(const float* __restr
 #pragma unroll
             for (int i = 0; i < NPL; i++) {
                 const float2 t0 = hA[i], t1 = same ? hA[i] : hB[i];
-                o[i].x = NSOF_MADD(t0.x, b0, t1.x * b1) * mul;
-                o[i].y = NSOF_MADD(t0.y, b0, t1.y * b1) * mul;
+                o[i].x = nsof_madd<FMA>(t0.x, b0, t1.x * b1) * mul;
+                o[i].y = nsof_madd<FMA>(t0.y, b0, t1.y * b1) * mul;
             }
             float2* drow = D + (size_t)dy * dw + dx0;
             if (dx0 + 1 < dw && (dw & 1) == 0) {
@@ -1774,44 +1142,6 @@ __global__ __launch_bounds__(256) void k_flow_upsample_walk(const float* __restr
     }
 }
 
-template <int N, typename SRC = uint8_t>
-void launch_polyexp_n(nsof_ctx* ctx, int n_img, const float* img, int W, int H, const nsof_poly_taps& taps, float* R,
-                      const PolyFrame* fr = nullptr)
-{
-    using G = PolyGeom<N>;
-    const int strips = (W + G::SW - 1) / G::SW;
-    // segment the height so that the grid has >= ~2048 blocks, but keep segments >= 64 rows
-    int segs = 1;
-    while (segs < 64 && (long long)strips * n_img * segs < 2048 && (H / (segs * 2)) >= 64) segs *= 2;
-    // a lone pair: segments down to 16 rows (each re-loads 2N+1 rows of warm-up) until there is a workgroup per CU
-    while (segs < 128 && (long long)strips * n_img * segs < 256 && (H / (segs * 2)) >= 16) segs *= 2;
-    int seg_rows = ((H + segs - 1) / segs + 3) / 4 * 4;
-    segs = (H + seg_rows - 1) / seg_rows;
-    dim3 grid(strips, segs, n_img);
-    if (fr)
-        hipLaunchKernelGGL((k_polyexp_rs<N, false, true, SRC>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, nullptr, *fr);
-    else if (ctx->opt_polyexp_f32)
-        hipLaunchKernelGGL((k_polyexp<N>), grid, dim3(256), 0, ctx->stream, img, R, W, H, seg_rows, taps, nullptr);
-    else
-        hipLaunchKernelGGL((k_polyexp_rs<N, false>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, nullptr);
-}
-
-// Work-list twin: W, H are the largest level extents over the table, n_img = 2 * items.
-template <int N, typename SRC = uint8_t>
-void launch_polyexp_het_n(nsof_ctx* ctx, int n_img, const nsof_het_item* items, const float* img, int W, int H,
-                          const nsof_poly_taps& taps, float* R, const PolyFrame* fr = nullptr)
-{
-    using G = PolyGeom<N>;
-    const int strips = (W + G::SW - 1) / G::SW;
-    int segs = 1;
-    while (segs < 64 && (long long)strips * n_img * segs < 2048 && (H / (segs * 2)) >= 64) segs *= 2;
-    int seg_rows = ((H + segs - 1) / segs + 3) / 4 * 4;
-    segs = (H + seg_rows - 1) / seg_rows;
-    dim3 grid(strips, segs, n_img);
-    if (fr) hipLaunchKernelGGL((k_polyexp_rs<N, true, true, SRC>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, items, *fr);
-    else hipLaunchKernelGGL((k_polyexp_rs<N, true>), grid, dim3(512), 0, ctx->stream, img, R, W, H, seg_rows, taps, items);
-}
-
 }  // namespace
 
 // =========================================================================================
@@ -1821,7 +1151,7 @@ void launch_polyexp_het_n(nsof_ctx* ctx, int n_img, const nsof_het_item* items, 
 // when the frames do not decimate exactly by 8 (or are not aligned for the vector walks): the caller then runs the
 // levels one by one.  out[k - 1]: level k's images, [n_img][H >> k][W >> k].
 namespace {
-template <typename T>
+template <typename T, bool FMA>
 int prep_decim3_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H,
                      const nsof_blur_taps* taps, float* const* out)
 {
@@ -1848,17 +1178,16 @@ int prep_decim3_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_strid
     d.seg_rows[2] = src_rows / 8;
     const int nseg = (H / 8 + d.seg_rows[2] - 1) / d.seg_rows[2];
     dim3 grid((unsigned)waves_x, (nseg + 3) / 4, n_img);
-    if constexpr (kU8<T>) {
-        if (CWL == 16) hipLaunchKernelGGL((k_prep_decim3<16, T>), grid, dim3(768), 0, ctx->stream, src, row_stride, img_stride, W, H, d);
-        else hipLaunchKernelGGL((k_prep_decim3<8, T>), grid, dim3(768), 0, ctx->stream, src, row_stride, img_stride, W, H, d);
-    } else {
-        hipLaunchKernelGGL((k_prep_decim3<8, T>), grid, dim3(768), 0, ctx->stream, src, row_stride, img_stride, W, H, d);
-    }
+    nsof_with_int<1, 2>(CWL / 8, [&](auto c) {
+        constexpr int CW = 8 * decltype(c)::value;
+        if constexpr (CW == 8 || kU8<T>)
+            hipLaunchKernelGGL((k_prep_decim3<CW, T, FMA>), grid, dim3(768), 0, ctx->stream, src, row_stride, img_stride, W, H, d);
+    });
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
 
-template <typename T>
+template <typename T, bool FMA>
 int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H, int wk, int hk,
               const nsof_blur_taps& taps, float* out)
 {
@@ -1870,11 +1199,11 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
         const bool aligned = (W & 3) == 0 && rows_va && W >= 8;
         if (taps.ksize == 3 && aligned) {
             dim3 grid((W / 4 + 63) / 64, (H + 4 * PREP0_ROWS - 1) / (4 * PREP0_ROWS), n_img);
-            hipLaunchKernelGGL((k_prep_same3_vec<false, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W,
+            hipLaunchKernelGGL((k_prep_same3_vec<false, T, FMA>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W,
                                H, taps.k[1], taps.k[2], out, nullptr);
         } else {
             dim3 grid((W + 63) / 64, (H + 3) / 4, n_img);
-            hipLaunchKernelGGL((k_prep_same<false, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
+            hipLaunchKernelGGL((k_prep_same<false, T, FMA>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
                                taps, out, nullptr, -1);
         }
     } else {
@@ -1916,19 +1245,17 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
             }
             const int nseg = (hk + seg_rows - 1) / seg_rows;
             dim3 grid((W / CWL + 63) / 64, (nseg + 3) / 4, n_img);
-#define NSOF_DECIM(SS, KK, CC)                                                                                      \
-    hipLaunchKernelGGL((k_prep_decim<SS, KK, CC, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, \
-                       H, wk, hk, seg_rows, taps, out)
-            if (CWL == 16) {
-                if (S == 2) NSOF_DECIM(2, 3, 16);
-                else if (S == 4) NSOF_DECIM(4, 9, 16);
-                else NSOF_DECIM(8, 19, 16);
-            } else {
-                if (S == 2) NSOF_DECIM(2, 3, 8);
-                else if (S == 4) NSOF_DECIM(4, 9, 8);
-                else if constexpr (sizeof(T) <= 2) NSOF_DECIM(8, 19, 8);
-            }
-#undef NSOF_DECIM
+            // level k = 1, 2, 3 (S = 2^k with 3, 9, 19 taps) x 8- or 16-column lanes; no float 8-column walk at S = 8
+            // (decim_al above)
+            nsof_with_int<1, 3>(S == 2 ? 1 : (S == 4 ? 2 : 3), [&](auto k) {
+                constexpr int SS = 1 << decltype(k)::value, KS = SS == 2 ? 3 : (SS == 4 ? 9 : 19);
+                nsof_with_int<1, 2>(CWL / 8, [&](auto c) {
+                    constexpr int CW = 8 * decltype(c)::value;
+                    if constexpr (CW == 16 || SS < 8 || sizeof(T) <= 2)
+                        hipLaunchKernelGGL((k_prep_decim<SS, KS, CW, T, FMA>), grid, dim3(256), 0, ctx->stream, src, row_stride,
+                                           img_stride, W, H, wk, hk, seg_rows, taps, out);
+                });
+            });
         } else if (scale_x >= 1.0 && scale_y >= 1.0 && scale_y < taps.ksize &&
                    (taps.ksize == 3 || taps.ksize == 5 || taps.ksize == 9)) {
             // measured per 128-image launch at 1080p, pyr_scale 0.6: level 1 (3 taps) 637 -> 334 us, level 2 (5 taps) 403 ->
@@ -1943,21 +1270,20 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
             while (seg_rows > 8 && waves_x * ((hk + seg_rows - 1) / seg_rows) * n_img < 2048) seg_rows /= 2;
             const int nseg = (hk + seg_rows - 1) / seg_rows;
             dim3 grid((unsigned)waves_x, (nseg + 3) / 4, n_img);
-#define NSOF_PREP_WALK(KS)                                                                                          \
-    hipLaunchKernelGGL((k_prep_walk<KS, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H, wk, hk, \
-                       scale_x, scale_y, seg_rows, taps, out)
-            if (taps.ksize == 3) NSOF_PREP_WALK(3);
-            else if (taps.ksize == 5) NSOF_PREP_WALK(5);
-            else NSOF_PREP_WALK(9);
-#undef NSOF_PREP_WALK
+            nsof_with_int<3, 9>(taps.ksize, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value;
+                if constexpr (KS == 3 || KS == 5 || KS == 9)
+                    hipLaunchKernelGGL((k_prep_walk<KS, T, FMA>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
+                                       wk, hk, scale_x, scale_y, seg_rows, taps, out);
+            });
         } else if (direct_ok) {
             dim3 grid((wk + 63) / 64, (hk + 3) / 4, n_img);
-#define NSOF_PREP_DIRECT(KS)                                                                                       \
-    hipLaunchKernelGGL((k_prep_direct<KS, false, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, \
-                       H, wk, hk, scale_x, scale_y, taps, out, nullptr)
-            if (taps.ksize == 3) NSOF_PREP_DIRECT(3);
-            else NSOF_PREP_DIRECT(5);
-#undef NSOF_PREP_DIRECT
+            nsof_with_int<3, 5>(taps.ksize, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value;
+                if constexpr (KS != 4)
+                    hipLaunchKernelGGL((k_prep_direct<KS, false, T, FMA>), grid, dim3(256), 0, ctx->stream, src, row_stride,
+                                       img_stride, W, H, wk, hk, scale_x, scale_y, taps, out, nullptr);
+            });
         } else if (taps.ksize == 19 && scale_x >= 1.0 && scale_y >= 1.0) {
             // measured at 1080p x 64 frames: 19 taps 459 -> 244 us; 9 taps is still faster tiled (231 vs 254 us)
             int rc = ctx->tmp.reserve(ctx, (size_t)n_img * H * 2 * wk * sizeof(float));
@@ -1965,24 +1291,21 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
             float* HA = static_cast<float*>(ctx->tmp.p);
             dim3 ga((2 * wk + 63) / 64, (H + 4 * PREPA_ROWS - 1) / (4 * PREPA_ROWS), n_img);
             dim3 gb((wk + 63) / 64, (hk + 3) / 4, n_img);
-            hipLaunchKernelGGL((k_prep_rows<19, T>), ga, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H, wk,
+            hipLaunchKernelGGL((k_prep_rows<19, T, FMA>), ga, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H, wk,
                                scale_x, taps, HA);
-            hipLaunchKernelGGL(k_prep_cols<19>, gb, dim3(256), 0, ctx->stream, HA, W, H, wk, hk, scale_x, scale_y, taps,
+            hipLaunchKernelGGL((k_prep_cols<19, FMA>), gb, dim3(256), 0, ctx->stream, HA, W, H, wk, hk, scale_x, scale_y, taps,
                                out);
         } else if (smem <= 60 * 1024 && scale_x >= 1.0 && scale_y >= 1.0) {
             dim3 grid((wk + PREP_TW - 1) / PREP_TW, (hk + PREP_TH - 1) / PREP_TH, n_img);
-#define PREP_TILED(KS)                                                                                        \
-    hipLaunchKernelGGL((k_prep_tiled<KS, false, T>), grid, dim3(256), smem, ctx->stream, src, row_stride, img_stride, \
-                       W, H, wk, hk, scale_x, scale_y, rw_cap, rh_cap, taps, out, nullptr)
-            switch (taps.ksize) {
-                case 9: PREP_TILED(9); break;
-                case 19: PREP_TILED(19); break;
-                default: PREP_TILED(0); break;
-            }
-#undef PREP_TILED
+            nsof_with_int<0, 19>(tiled_ks(taps.ksize), [&](auto ks) {
+                constexpr int KS = decltype(ks)::value;
+                if constexpr (KS == tiled_ks(KS))
+                    hipLaunchKernelGGL((k_prep_tiled<KS, false, T, FMA>), grid, dim3(256), smem, ctx->stream, src, row_stride,
+                                       img_stride, W, H, wk, hk, scale_x, scale_y, rw_cap, rh_cap, taps, out, nullptr);
+            });
         } else {
             dim3 grid((wk + 63) / 64, (hk + 3) / 4, n_img);
-            hipLaunchKernelGGL((k_prep_naive<false, T>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
+            hipLaunchKernelGGL((k_prep_naive<false, T, FMA>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
                                wk, hk, scale_x, scale_y, taps, out, nullptr);
         }
     }
@@ -1991,158 +1314,92 @@ int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrd
 }
 }  // namespace
 
-int NSOF_PYR_NAME(nsof_launch_prep_decim3)(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride,
-                                           int W, int H, const nsof_blur_taps* taps, float* const* out, int src_type)
+int nsof_launch_prep_decim3(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H,
+                            const nsof_blur_taps* taps, float* const* out, int src_type)
 {
     // f32 frames take the three one-level launches (k_prep_decim<.., float>): at 768 threads per workgroup a wave has
     // 168 registers, and the float rows of the three walks side by side spilled (~400 registers' worth to scratch)
-    switch (src_type) {
-        case NSOF_SRC_U8: return prep_decim3_impl(ctx, n_img, static_cast<const uint8_t*>(src), row_stride, img_stride, W, H, taps, out);
-        case NSOF_SRC_U16: return prep_decim3_impl(ctx, n_img, static_cast<const uint16_t*>(src), row_stride, img_stride, W, H, taps, out);
-        case NSOF_SRC_S16: return prep_decim3_impl(ctx, n_img, static_cast<const int16_t*>(src), row_stride, img_stride, W, H, taps, out);
-        default: return NSOF_EUNSUPPORTED;
-    }
+    int rc = NSOF_EUNSUPPORTED;
+    nsof_with_src_type(src_type, [&](auto px_tag) {
+        using T = typename decltype(px_tag)::type;
+        if constexpr (kInt<T>) {
+            const T* s = static_cast<const T*>(src);
+            rc = ctx->opt_pyr_fma ? prep_decim3_impl<T, true>(ctx, n_img, s, row_stride, img_stride, W, H, taps, out)
+                                  : prep_decim3_impl<T, false>(ctx, n_img, s, row_stride, img_stride, W, H, taps, out);
+        }
+    });
+    return rc;
 }
 
-int NSOF_PYR_NAME(nsof_launch_prep)(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
-                                    int H, int wk, int hk, const nsof_blur_taps& taps, float* out, int src_type)
+int nsof_launch_prep(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H, int wk,
+                     int hk, const nsof_blur_taps& taps, float* out, int src_type)
 {
-    switch (src_type) {
-        case NSOF_SRC_F32: return prep_impl(ctx, n_img, static_cast<const float*>(src), row_stride, img_stride, W, H, wk, hk, taps, out);
-        case NSOF_SRC_U16: return prep_impl(ctx, n_img, static_cast<const uint16_t*>(src), row_stride, img_stride, W, H, wk, hk, taps, out);
-        case NSOF_SRC_S16: return prep_impl(ctx, n_img, static_cast<const int16_t*>(src), row_stride, img_stride, W, H, wk, hk, taps, out);
-        default: return prep_impl(ctx, n_img, static_cast<const uint8_t*>(src), row_stride, img_stride, W, H, wk, hk, taps, out);
-    }
+    int rc = NSOF_OK;
+    const bool known = nsof_with_src_type(src_type, [&](auto px_tag) {
+        using T = typename decltype(px_tag)::type;
+        const T* s = static_cast<const T*>(src);
+        rc = ctx->opt_pyr_fma ? prep_impl<T, true>(ctx, n_img, s, row_stride, img_stride, W, H, wk, hk, taps, out)
+                              : prep_impl<T, false>(ctx, n_img, s, row_stride, img_stride, W, H, wk, hk, taps, out);
+    });
+    return known ? rc : nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", src_type);
 }
 
-#ifndef NSOF_PYR_FMA
-// The expansion of the full-resolution level straight from the integer frames (k_polyexp_rs<.., FRAME, SRC>): images
-// [0, nsplit) at src0 + z * img_stride, the rest at src1; k0 / k1 = centre / side tap of the level's 3-tap smoothing.
 namespace {
-template <typename SRC>
-int polyexp_fused_impl(nsof_ctx* ctx, int n_img, const PolyFrame& fr, int W, int H, const nsof_poly_taps& taps, float* R)
-{
-    switch (taps.n) {
-#define NSOF_PU(NN) case NN: launch_polyexp_n<NN, SRC>(ctx, n_img, nullptr, W, H, taps, R, &fr); break
-        NSOF_PU(1); NSOF_PU(2); NSOF_PU(3); NSOF_PU(4); NSOF_PU(5); NSOF_PU(6); NSOF_PU(7); NSOF_PU(8); NSOF_PU(9); NSOF_PU(10);
-#undef NSOF_PU
-        default: return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "poly_n=%d outside 1..%d", taps.n, NSOF_MAX_POLY_N);
-    }
-    NSOF_HIP(ctx, hipGetLastError());
-    return NSOF_OK;
-}
-template <typename SRC>
-int polyexp_het_impl(nsof_ctx* ctx, int nz, const nsof_het_item* d_items, int max_w, int max_h, const nsof_poly_taps& taps,
-                     const float* I, float* R, const PolyFrame* fr)
-{
-    switch (taps.n) {
-#define NSOF_PH(NN) case NN: launch_polyexp_het_n<NN, SRC>(ctx, nz, d_items, I, max_w, max_h, taps, R, fr); break
-        NSOF_PH(1); NSOF_PH(2); NSOF_PH(3); NSOF_PH(4); NSOF_PH(5); NSOF_PH(6); NSOF_PH(7); NSOF_PH(8); NSOF_PH(9); NSOF_PH(10);
-#undef NSOF_PH
-        default: return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "poly_n=%d outside 1..%d", taps.n, NSOF_MAX_POLY_N);
-    }
-    NSOF_HIP(ctx, hipGetLastError());
-    return NSOF_OK;
-}
-}  // namespace
-
-int nsof_launch_polyexp_frames(nsof_ctx* ctx, int n_img, const void* src0, const void* src1, int nsplit, ptrdiff_t row_stride,
-                           ptrdiff_t img_stride, int W, int H, const nsof_poly_taps& taps, float k0, float k1, float* R,
-                           int src_type)
-{
-    nsof_prof_scope ps(ctx, NSOF_K_POLYEXP);
-    const PolyFrame fr{static_cast<const uint8_t*>(src0), static_cast<const uint8_t*>(src1), (long long)row_stride,
-                    (long long)img_stride, nsplit, k0, k1};
-    switch (src_type) {
-        case NSOF_SRC_U8: return polyexp_fused_impl<uint8_t>(ctx, n_img, fr, W, H, taps, R);
-        case NSOF_SRC_U16: return polyexp_fused_impl<uint16_t>(ctx, n_img, fr, W, H, taps, R);
-        case NSOF_SRC_S16: return polyexp_fused_impl<int16_t>(ctx, n_img, fr, W, H, taps, R);
-        default: return nsof_set_error(ctx, NSOF_EINVAL, "fused level 0 takes integer frames only");
-    }
-}
-
-int nsof_launch_polyexp(nsof_ctx* ctx, int n_img, const float* img, int W, int H, const nsof_poly_taps& taps, float* R)
-{
-    nsof_prof_scope ps(ctx, NSOF_K_POLYEXP);
-    switch (taps.n) {
-        case 1: launch_polyexp_n<1>(ctx, n_img, img, W, H, taps, R); break;
-        case 2: launch_polyexp_n<2>(ctx, n_img, img, W, H, taps, R); break;
-        case 3: launch_polyexp_n<3>(ctx, n_img, img, W, H, taps, R); break;
-        case 4: launch_polyexp_n<4>(ctx, n_img, img, W, H, taps, R); break;
-        case 5: launch_polyexp_n<5>(ctx, n_img, img, W, H, taps, R); break;
-        case 6: launch_polyexp_n<6>(ctx, n_img, img, W, H, taps, R); break;
-        case 7: launch_polyexp_n<7>(ctx, n_img, img, W, H, taps, R); break;
-        case 8: launch_polyexp_n<8>(ctx, n_img, img, W, H, taps, R); break;
-        case 9: launch_polyexp_n<9>(ctx, n_img, img, W, H, taps, R); break;
-        case 10: launch_polyexp_n<10>(ctx, n_img, img, W, H, taps, R); break;
-        default: return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "poly_n=%d outside 1..%d", taps.n, NSOF_MAX_POLY_N);
-    }
-    NSOF_HIP(ctx, hipGetLastError());
-    return NSOF_OK;
-}
-
-int nsof_launch_blur_solve(nsof_ctx* ctx, int n_pairs, const float* M, int W, int H, int winsize, float* flow)
-{
-    const int m = winsize / 2;
-    if (m > 96) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "winsize=%d too large (max 193)", winsize);
-    nsof_prof_scope ps(ctx, NSOF_K_BLUR);
-    const int SW = (256 - 2 * m) & ~3;
-    dim3 grid((W + SW - 1) / SW, 1, n_pairs);
-    hipLaunchKernelGGL(k_blur_solve, grid, dim3(256), 0, ctx->stream, M, W, H, m, winsize, flow);
-    NSOF_HIP(ctx, hipGetLastError());
-    return NSOF_OK;
-}
-
-int nsof_launch_blur_solve_exact(nsof_ctx* ctx, int n_pairs, const float* M, int W, int H, int winsize, double* VT,
-                                 float* flow)
-{
-    const int m = winsize / 2;
-    nsof_prof_scope ps(ctx, NSOF_K_BLUR);
-    hipLaunchKernelGGL(k_blur_colsum, dim3((W + 255) / 256, 1, n_pairs), dim3(256), 0, ctx->stream, M, W, H, m, VT);
-    hipLaunchKernelGGL(k_blur_rowsolve, dim3((H + 63) / 64, 1, n_pairs), dim3(64), 0, ctx->stream, VT, W, H, m, winsize,
-                       flow);
-    NSOF_HIP(ctx, hipGetLastError());
-    return NSOF_OK;
-}
-
-#endif  // !NSOF_PYR_FMA
-
-int NSOF_PYR_NAME(nsof_launch_flow_upsample)(nsof_ctx* ctx, int n_pairs, const float* src, int sw, int sh, float* dst, int dw, int dh,
-                              float mul)
+template <bool FMA>
+int flow_upsample_impl(nsof_ctx* ctx, int n_pairs, const float* src, int sw, int sh, float* dst, int dw, int dh, float mul)
 {
     nsof_prof_scope ps(ctx, NSOF_K_UPSAMPLE);
     const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
     if (dw >= sw && dh >= sh && sw >= 1 && sh >= 1 && dw >= 256) {
         // upsampling: source steps of 0 or 1 between neighbours; rows wide enough for a lane per 2 columns
         dim3 g(((dw + 1) / 2 + 255) / 256, (dh + UPW_SEG - 1) / UPW_SEG, n_pairs);
-        hipLaunchKernelGGL(k_flow_upsample_walk, g, dim3(256), 0, ctx->stream, src, sw, sh, dst, dw, dh, scale_x,
+        hipLaunchKernelGGL(k_flow_upsample_walk<FMA>, g, dim3(256), 0, ctx->stream, src, sw, sh, dst, dw, dh, scale_x,
                            scale_y, mul);
         NSOF_HIP(ctx, hipGetLastError());
         return NSOF_OK;
     }
     if (dw >= sw && dh >= sh && sw >= 1 && sh >= 1) {   // upsampling: source steps of 0 or 1 between neighbours
         dim3 g2(((dw + 1) / 2 + 63) / 64, ((dh + 1) / 2 + 3) / 4, n_pairs);
-        hipLaunchKernelGGL(k_flow_upsample2x2<false>, g2, dim3(256), 0, ctx->stream, src, sw, sh, dst, dw, dh, scale_x,
+        hipLaunchKernelGGL((k_flow_upsample2x2<false, FMA>), g2, dim3(256), 0, ctx->stream, src, sw, sh, dst, dw, dh, scale_x,
                            scale_y, mul, nullptr);
         NSOF_HIP(ctx, hipGetLastError());
         return NSOF_OK;
     }
     dim3 grid((dw + 63) / 64, (dh + 3) / 4, n_pairs);
-    hipLaunchKernelGGL(k_flow_upsample, grid, dim3(256), 0, ctx->stream, src, sw, sh, dst, dw, dh, scale_x, scale_y,
+    hipLaunchKernelGGL(k_flow_upsample<FMA>, grid, dim3(256), 0, ctx->stream, src, sw, sh, dst, dw, dh, scale_x, scale_y,
                        mul);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
+}
+}  // namespace
+
+int nsof_launch_flow_upsample(nsof_ctx* ctx, int n_pairs, const float* src, int sw, int sh, float* dst, int dw, int dh, float mul)
+{
+    return ctx->opt_pyr_fma ? flow_upsample_impl<true>(ctx, n_pairs, src, sw, sh, dst, dw, dh, mul)
+                            : flow_upsample_impl<false>(ctx, n_pairs, src, sw, sh, dst, dw, dh, mul);
 }
 
 // =========================================================================================
 // work-list (shape-heterogeneous) launchers: one launch per stage and level over a device table
 // =========================================================================================
 namespace {
+template <int KS, typename T, bool FMA>
+int launch_tiled_het(nsof_ctx* ctx, dim3 grid, size_t smem, int rw_cap, int rh_cap, const nsof_blur_taps& taps, float* I,
+                     const nsof_het_item* d_items)
+{
+    auto kern = k_prep_tiled<KS, true, T, FMA>;
+    if (smem > 64 * 1024)
+        NSOF_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(kern, grid, dim3(256), smem, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1., rw_cap, rh_cap, taps, I,
+                       d_items);
+    return NSOF_OK;
+}
+
 // T: the pixel type of every item's frames (the list's src_type).  Kernel choice as for 8-bit items; with 16-bit / float
 // frames NSOF_HET_VEC0 means 8- / 16-byte aligned rows (k_prep_same3_vec's 4-pixel loads), the scalar k_prep_same takes
 // the rest.  The LDS-tiled kernel's budget is 60 KB, and 78 KB for 16-bit frames: the 19-tap scale-8 level of large
 // crops needs ~75 KB at 2 B/px (50 KB at 1), and two workgroups still fit the CU's 160 KB.
-template <typename T>
+template <typename T, bool FMA>
 int prep_het_impl(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items, bool level0,
                   const nsof_blur_taps& taps, float* I)
 {
@@ -2162,12 +1419,12 @@ int prep_het_impl(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, cons
     if (level0) {   // same-size level: 3 taps; aligned items take the vector kernel, the others the generic one
         if (taps.ksize == 3 && n_vec > 0) {
             dim3 grid((max_wk / 4 + 63) / 64, (max_hk + 4 * PREP0_ROWS - 1) / (4 * PREP0_ROWS), nz);
-            hipLaunchKernelGGL((k_prep_same3_vec<true, T>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps.k[1],
+            hipLaunchKernelGGL((k_prep_same3_vec<true, T, FMA>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps.k[1],
                                taps.k[2], I, d_items);
         }
         if (taps.ksize != 3 || n_vec < n_items) {
             dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
-            hipLaunchKernelGGL((k_prep_same<true, T>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps, I, d_items,
+            hipLaunchKernelGGL((k_prep_same<true, T, FMA>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps, I, d_items,
                                taps.ksize == 3 ? 0 : -1);
         }
     } else {
@@ -2178,31 +1435,23 @@ int prep_het_impl(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, cons
                             (size_t)rh_cap * rw_cap * sizeof(T);
         if (taps.ksize == 3 || taps.ksize == 5) {
             dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
-            if (taps.ksize == 3)
-                hipLaunchKernelGGL((k_prep_direct<3, true, T>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1.,
-                                   1., taps, I, d_items);
-            else
-                hipLaunchKernelGGL((k_prep_direct<5, true, T>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1.,
-                                   1., taps, I, d_items);
+            nsof_with_int<3, 5>(taps.ksize, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value;
+                if constexpr (KS != 4)
+                    hipLaunchKernelGGL((k_prep_direct<KS, true, T, FMA>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0,
+                                       1., 1., taps, I, d_items);
+            });
         } else if (smem <= (sizeof(T) == 2 ? 78 : 60) * 1024) {
             dim3 grid((max_wk + PREP_TW - 1) / PREP_TW, (max_hk + PREP_TH - 1) / PREP_TH, nz);
-#define PREP_TILED_HET(KS)                                                                                                \
-    do {                                                                                                                  \
-        auto kern = k_prep_tiled<KS, true, T>;                                                                            \
-        if (smem > 64 * 1024)                                                                                             \
-            NSOF_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-        hipLaunchKernelGGL(kern, grid, dim3(256), smem, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1., rw_cap, rh_cap,  \
-                           taps, I, d_items);                                                                             \
-    } while (0)
-            switch (taps.ksize) {
-                case 9: PREP_TILED_HET(9); break;
-                case 19: PREP_TILED_HET(19); break;
-                default: PREP_TILED_HET(0); break;
-            }
-#undef PREP_TILED_HET
+            int rc = NSOF_OK;
+            nsof_with_int<0, 19>(tiled_ks(taps.ksize), [&](auto ks) {
+                constexpr int KS = decltype(ks)::value;
+                if constexpr (KS == tiled_ks(KS)) rc = launch_tiled_het<KS, T, FMA>(ctx, grid, smem, rw_cap, rh_cap, taps, I, d_items);
+            });
+            if (rc) return rc;
         } else {
             dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
-            hipLaunchKernelGGL((k_prep_naive<true, T>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1.,
+            hipLaunchKernelGGL((k_prep_naive<true, T, FMA>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1.,
                                taps, I, d_items);
         }
     }
@@ -2211,44 +1460,25 @@ int prep_het_impl(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, cons
 }
 }  // namespace
 
-int NSOF_PYR_NAME(nsof_launch_prep_het)(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items,
-                         bool level0, const nsof_blur_taps& taps, float* I, int src_type)
+int nsof_launch_prep_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items, bool level0,
+                         const nsof_blur_taps& taps, float* I, int src_type)
 {
-    switch (src_type) {
-        case NSOF_SRC_F32: return prep_het_impl<float>(ctx, n_items, d_items, h_items, level0, taps, I);
-        case NSOF_SRC_U16: return prep_het_impl<uint16_t>(ctx, n_items, d_items, h_items, level0, taps, I);
-        case NSOF_SRC_S16: return prep_het_impl<int16_t>(ctx, n_items, d_items, h_items, level0, taps, I);
-        default: return prep_het_impl<uint8_t>(ctx, n_items, d_items, h_items, level0, taps, I);
-    }
+    int rc = NSOF_OK;
+    const bool known = nsof_with_src_type(src_type, [&](auto px_tag) {
+        using T = typename decltype(px_tag)::type;
+        rc = ctx->opt_pyr_fma ? prep_het_impl<T, true>(ctx, n_items, d_items, h_items, level0, taps, I)
+                              : prep_het_impl<T, false>(ctx, n_items, d_items, h_items, level0, taps, I);
+    });
+    return known ? rc : nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", src_type);
 }
 
-#ifndef NSOF_PYR_FMA
-// blur3: non-null at the full-resolution level = form the level image from the items' own frames (k0, k1 = centre / side
-// tap); I is not read then.
-// src_type: the items' pixel type (read only with blur3: 8- or 16-bit).
-int nsof_launch_polyexp_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
-                            const nsof_poly_taps& taps, const float* I, float* R, const float* blur3, int src_type)
-{
-    nsof_prof_scope ps(ctx, NSOF_K_POLYEXP);
-    const int nz = 2 * n_items;
-    PolyFrame frv{};
-    if (blur3) { frv.k0 = blur3[0]; frv.k1 = blur3[1]; }
-    const PolyFrame* fr = blur3 ? &frv : nullptr;
-    if (blur3 && src_type == NSOF_SRC_U16) return polyexp_het_impl<uint16_t>(ctx, nz, d_items, max_w, max_h, taps, I, R, fr);
-    if (blur3 && src_type == NSOF_SRC_S16) return polyexp_het_impl<int16_t>(ctx, nz, d_items, max_w, max_h, taps, I, R, fr);
-    if (blur3 && src_type == NSOF_SRC_F32) return nsof_set_error(ctx, NSOF_EINVAL, "fused level 0 takes integer frames only");
-    return polyexp_het_impl<uint8_t>(ctx, nz, d_items, max_w, max_h, taps, I, R, fr);
-}
-
-#endif  // !NSOF_PYR_FMA
-
-int NSOF_PYR_NAME(nsof_launch_flow_upsample_het)(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
+int nsof_launch_flow_upsample_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
                                   const float* src, float* dst, float mul)
 {
     nsof_prof_scope ps(ctx, NSOF_K_UPSAMPLE);
     dim3 g2(((max_w + 1) / 2 + 63) / 64, ((max_h + 1) / 2 + 3) / 4, n_items);
-    hipLaunchKernelGGL(k_flow_upsample2x2<true>, g2, dim3(256), 0, ctx->stream, src, 0, 0, dst, 0, 0, 1., 1., mul,
-                       d_items);
+    auto kern = ctx->opt_pyr_fma ? k_flow_upsample2x2<true, true> : k_flow_upsample2x2<true, false>;
+    hipLaunchKernelGGL(kern, g2, dim3(256), 0, ctx->stream, src, 0, 0, dst, 0, 0, 1., 1., mul, d_items);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }

@@ -528,7 +528,7 @@ extern "C" int nsof_stage_pyr_level_px(nsof_ctx* ctx, int pixel_type, int n_img,
     int wk, hk;
     nsof_blur_taps taps;
     if (int rc = nsof_level_geom(ctx, width, height, pyr_scale, level, &wk, &hk, &taps)) return rc;
-    return NSOF_PYR_SEL(ctx, nsof_launch_prep, n_img, d_src, row_stride, img_stride, width, height, wk, hk, taps, d_out, pixel_type);
+    return nsof_launch_prep(ctx, n_img, d_src, row_stride, img_stride, width, height, wk, hk, taps, d_out, pixel_type);
 }
 
 extern "C" int nsof_stage_pyr_level(nsof_ctx* ctx, int n_img, const uint8_t* d_src, ptrdiff_t row_stride,
@@ -630,7 +630,7 @@ extern "C" int nsof_stage_flow_upsample(nsof_ctx* ctx, int n_pairs, const float*
                                         int dw, int dh, double pyr_scale)
 {
     if (!ctx || !d_src || !d_dst || n_pairs < 1 || sw < 1 || sh < 1 || dw < 1 || dh < 1) return NSOF_EINVAL;
-    return NSOF_PYR_SEL(ctx, nsof_launch_flow_upsample, n_pairs, d_src, sw, sh, d_dst, dw, dh, (float)(1. / pyr_scale));
+    return nsof_launch_flow_upsample(ctx, n_pairs, d_src, sw, sh, d_dst, dw, dh, (float)(1. / pyr_scale));
 }
 
 // ---- the Farneback driver --------------------------------------------------------------------
@@ -778,9 +778,9 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
     auto prep_level = [&](int wk, int hk, const nsof_blur_taps& bt, float* I) -> int {
         const size_t nk = (size_t)wk * hk;
         if (sequence || prep_merged)
-            return NSOF_PYR_SEL(ctx, nsof_launch_prep, (int)n_img, d_prev, row_stride, pair_stride, width, height, wk, hk, bt, I, src);
+            return nsof_launch_prep(ctx, (int)n_img, d_prev, row_stride, pair_stride, width, height, wk, hk, bt, I, src);
         for (int i = 0; i < 2; i++)
-            if (int r = NSOF_PYR_SEL(ctx, nsof_launch_prep, n_pairs, i == 0 ? d_prev : d_next, row_stride, pair_stride, width, height,
+            if (int r = nsof_launch_prep(ctx, n_pairs, i == 0 ? d_prev : d_next, row_stride, pair_stride, width, height,
                                      wk, hk, bt, I + (size_t)i * B * nk, src))
                 return r;
         return NSOF_OK;
@@ -847,10 +847,10 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
             float* dI = level_I(0);
             float* I3[3] = {dI, dI + n_img * nk3[0], dI + n_img * (nk3[0] + nk3[1])};
             const bool one = sequence || prep_merged;
-            rc = NSOF_PYR_SEL(ctx, nsof_launch_prep_decim3, one ? (int)n_img : n_pairs, d_prev, row_stride, pair_stride, width, height, bt3, I3, src);
+            rc = nsof_launch_prep_decim3(ctx, one ? (int)n_img : n_pairs, d_prev, row_stride, pair_stride, width, height, bt3, I3, src);
             if (rc == NSOF_OK && !one) {
                 float* I3n[3] = {I3[0] + B * nk3[0], I3[1] + B * nk3[1], I3[2] + B * nk3[2]};
-                rc = NSOF_PYR_SEL(ctx, nsof_launch_prep_decim3, n_pairs, d_next, row_stride, pair_stride, width, height, bt3, I3n, src);
+                rc = nsof_launch_prep_decim3(ctx, n_pairs, d_next, row_stride, pair_stride, width, height, bt3, I3n, src);
             }
             if (rc == NSOF_OK) {
                 for (int k = 1; k <= 3; k++) Ifused[k] = I3[k - 1];
@@ -869,7 +869,7 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* p
         if (k == L) {
             NSOF_HIP(ctx, hipMemsetAsync(fb[cur], 0, B * nk * 8, mainS));
         } else {
-            if ((rc = NSOF_PYR_SEL(ctx, nsof_launch_flow_upsample, n_pairs, fb[cur], pw, ph, fb[cur ^ 1], wk, hk,
+            if ((rc = nsof_launch_flow_upsample(ctx, n_pairs, fb[cur], pw, ph, fb[cur ^ 1], wk, hk,
                                    (float)(1. / pyr_scale))))
                 return rc;
             cur ^= 1;

@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -114,6 +115,21 @@ struct nsof_ctx {
 };
 
 int nsof_set_error(nsof_ctx* ctx, int code, const char* fmt, ...);
+
+// ---- run-time value -> template argument ----------------------------------------------------------------------------
+// A launcher hands a generic lambda to one of these and instantiates its kernel from the tag the lambda is called with.
+// f(std::integral_constant<int, N>{}) for the N in [LO, HI] that equals v; false, f not called, when there is none.
+template <int LO, int HI, class Fn>
+bool nsof_with_int(int v, Fn&& f)
+{
+    if constexpr (LO <= HI) {
+        if (v != LO) return nsof_with_int<LO + 1, HI>(v, f);
+        f(std::integral_constant<int, LO>{});
+        return true;
+    } else {
+        return false;
+    }
+}
 // Page-locked host memory on the GPU's NUMA node (best effort); NUMA node of a device from sysfs, -1 if unknown.
 void* nsof_pinned_alloc(int device, size_t bytes);
 int nsof_gpu_numa_node(int device);
@@ -142,6 +158,19 @@ struct nsof_prof_scope {
 enum nsof_src_type { NSOF_SRC_U8 = 0, NSOF_SRC_F32 = 1, NSOF_SRC_U16 = 2, NSOF_SRC_S16 = 3 };
 static inline int nsof_src_bytes(int src) { return src == NSOF_SRC_F32 ? 4 : (src == NSOF_SRC_U8 ? 1 : 2); }
 static inline bool nsof_src_valid(int src) { return src >= NSOF_SRC_U8 && src <= NSOF_SRC_S16; }
+// f(nsof_px_tag<T>{}) for the pixel type T of src (an nsof_src_type); false, f not called, for any other value.
+template <class T> struct nsof_px_tag { using type = T; };
+template <class Fn>
+bool nsof_with_src_type(int src, Fn&& f)
+{
+    switch (src) {
+        case NSOF_SRC_U8: f(nsof_px_tag<uint8_t>{}); return true;
+        case NSOF_SRC_F32: f(nsof_px_tag<float>{}); return true;
+        case NSOF_SRC_U16: f(nsof_px_tag<uint16_t>{}); return true;
+        case NSOF_SRC_S16: f(nsof_px_tag<int16_t>{}); return true;
+        default: return false;
+    }
+}
 // The first two checks of every typed entry: a context, then a known pixel type.
 static inline int nsof_check_typed(nsof_ctx* ctx, int pixel_type)
 {
@@ -161,7 +190,7 @@ int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* d
                         int flags, int src);
 void nsof_pipe_destroy(nsof_ctx* ctx);
 
-// ---- Farneback launchers (farneback_kernels.hip) ------------------------------------------
+// ---- Farneback launchers (farneback_pyramid.hip, farneback_polyexp.hip, farneback_blur.hip) ----
 struct nsof_blur_taps {
     int ksize;
     float k[NSOF_MAX_BLUR_TAPS];
@@ -234,24 +263,13 @@ int nsof_launch_flow_upsample_het(nsof_ctx* ctx, int n_items, const nsof_het_ite
 // final: the flow goes to the items' own output fields (out / out_pitch) instead of flow_out.
 int nsof_launch_iterate_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, const float* R,
                             const float* flow_in, float* flow_out, bool final, int winsize);
+// The pyramid-level and flow-resample launchers (farneback_pyramid.hip) take the arithmetic variant from ctx->opt_pyr_fma.
 // src: n_img frames of pixel type src_type (nsof_src_type), row / image strides in bytes.
 int nsof_launch_prep(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
                      int H, int wk, int hk, const nsof_blur_taps& taps, float* out, int src_type);
-// The *_fma twins (farneback_kernels.hip compiled with -DNSOF_PYR_FMA): same taps and order, every tap / blend one fused
-// multiply-add -- selected by ctx->opt_pyr_fma through the *_sel wrappers below.
-int nsof_launch_prep_fma(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
-                         int H, int wk, int hk, const nsof_blur_taps& taps, float* out, int src_type);
 // Levels 1..3 of a pyr_scale 0.5 pyramid in one launch; NSOF_EUNSUPPORTED (nothing launched) when the frames do not qualify.
 int nsof_launch_prep_decim3(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
                             int H, const nsof_blur_taps* taps, float* const* out, int src_type);
-int nsof_launch_prep_decim3_fma(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride,
-                                int W, int H, const nsof_blur_taps* taps, float* const* out, int src_type);
-int nsof_launch_prep_het_fma(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items,
-                             bool level0, const nsof_blur_taps& taps, float* I, int src_type);
-int nsof_launch_flow_upsample_fma(nsof_ctx* ctx, int n_pairs, const float* src, int sw, int sh, float* dst, int dw,
-                                  int dh, float mul);
-int nsof_launch_flow_upsample_het_fma(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
-                                      const float* src, float* dst, float mul);
 int nsof_launch_polyexp(nsof_ctx* ctx, int n_img, const float* img, int W, int H, const nsof_poly_taps& taps,
                         float* R);
 // Full-resolution level: pyramid level (3-tap smoothing, centre k0 / side k1) + expansion in one kernel, from the 8-bit
@@ -274,7 +292,6 @@ struct nsof_gauss_taps {
 int nsof_launch_gauss_blur_solve(nsof_ctx* ctx, int n_pairs, const float* M, int W, int H, int winsize, float* flow);
 int nsof_launch_flow_upsample(nsof_ctx* ctx, int n_pairs, const float* src, int sw, int sh, float* dst, int dw,
                               int dh, float mul);
-#define NSOF_PYR_SEL(ctx, fn, ...) ((ctx)->opt_pyr_fma ? fn##_fma(ctx, __VA_ARGS__) : fn(ctx, __VA_ARGS__))
 // Fused iteration; flow_in != flow_out.
 int nsof_launch_iterate(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
                         const float* flow_in, float* flow_out, int W, int H, int winsize);
@@ -365,6 +382,27 @@ __device__ __forceinline__ float2 nsof_flow_solve(double s0, double s1, double s
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ int reflect101(int p, int len)
+{
+    if ((unsigned)p < (unsigned)len) return p;
+    if (len == 1) return 0;
+    do {
+        if (p < 0) p = -p;
+        else p = 2 * len - 2 - p;
+    } while ((unsigned)p >= (unsigned)len);
+    return p;
+}
+// a * b + c of the pyramid blur and the bilinear resamples in their two arithmetic variants (DESIGN.md section 2,
+// NSOF_OPT_PYR_FMA).  FMA = false: multiply, round, add, round, as the library's generic C++ path does (the units are
+// compiled with -ffp-contract=off).  FMA = true: one fused multiply-add, the way an AVX2+FMA3 build of the library's vector
+// code (v_muladd / v_fma in its separable-filter and resize loops) contracts the same taps in the same order; the leading
+// product of a sum is still rounded.
+template <bool FMA>
+__device__ __forceinline__ float nsof_madd(float a, float b, float c)
+{
+    if constexpr (FMA) return fmaf(a, b, c);
+    else return a * b + c;
+}
 // cvFloor(float) as its x86-64 build returns it for every float: NaN and
 // v >= 2^31 give INT_MIN, v < -2^31 (-inf included) INT_MAX.  A bare (int)v would give 0 for NaN here (v_cvt_i32_f32),
 // which sends a NaN flow into the bilinear sample instead of the out-of-image branch.

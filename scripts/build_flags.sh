@@ -12,8 +12,6 @@ for src in csrc/*.hip; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 $base $flags -I../include -Icsrc -c $src -o build_flags_$name/$b.o 2> build_flags_$name/$b.log &
   pids="$pids $!"
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 $base $flags -I../include -Icsrc -DNSOF_PYR_FMA -c csrc/farneback_kernels.hip -o build_flags_$name/farneback_kernels_fma.o 2> build_flags_$name/fma.log &
-pids="$pids $!"
 for p in $pids; do wait $p; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o nsof/libnsof_$name.so build_flags_$name/*.o
 rm -rf build_flags_$name

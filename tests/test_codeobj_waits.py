@@ -129,12 +129,12 @@ def counted_waits(insts, count):
 
 
 def expected_instantiations(src_text):
-    """(MH, HET) of every k_iterate_x the launchers instantiate: the NSOF_X_SWITCH cases x its invocations."""
-    macro = src_text[src_text.index("#define NSOF_X_SWITCH"):]
-    macro = macro[:macro.index("\n\n")]
-    mhs = {int(v) for v in re.findall(r"case\s+(\d+):\s*rc\s*=\s*launch_x<\s*(\d+)\s*,\s*HETV\s*>", macro) for v in [v[0]]}
-    hets = {v == "true" for v in re.findall(r"^\s*NSOF_X_SWITCH\((true|false),", src_text, re.M)}
-    return {(m, h) for m in mhs for h in hets}
+    """(MH, HET) of every k_iterate_x the launchers instantiate: each nsof_with_int<LO, HI>(winsize / 2, ..) whose lambda
+    calls launch_x<MH, HET> with the constant it is handed makes LO..HI for that HET."""
+    calls = re.findall(r"nsof_with_int<\s*(\d+)\s*,\s*(\d+)\s*>\(winsize / 2, \[&\]\(auto mh\) \{\s*"
+                       r"rc = launch_x<decltype\(mh\)::value, (true|false)>\(", src_text)
+    assert len(calls) == len(re.findall(r"\blaunch_x<", src_text)), "a launch_x<..> call this parser does not know"
+    return {(m, het == "true") for lo, hi, het in calls for m in range(int(lo), int(hi) + 1)}
 
 
 # ---- synthetic snippets: the checker bites without touching the kernel ----------------------------------------------

@@ -464,11 +464,16 @@ def _fuzz(nsof_lib, ctx, oracle, rowsums):
     assert worst <= 1e-4
 
 
-@pytest.mark.parametrize("shape", [(256, 272), (264, 328), (1080, 1920)])
-def test_three_level_pyramid_launch_batch_and_sequence(nsof_lib, ctx, oracle, torch_dev, shape):
+@pytest.mark.parametrize("shape,fma", [
+    pytest.param((256, 272), 0, id="shape0"), pytest.param((264, 328), 0, id="shape1"),
+    pytest.param((1080, 1920), 0, id="shape2"),   # (the ids the plain cases had before the variant became a parameter)
+    pytest.param((256, 272), 1, id="shape0-fma"), pytest.param((264, 328), 1, id="shape1-fma")])
+def test_three_level_pyramid_launch_batch_and_sequence(nsof_lib, ctx, oracle, torch_dev, shape, fma):
     """pyr_scale 0.5 with three coarser levels on frames that decimate exactly by 8: the batch driver makes levels 1-3
     in ONE launch (k_prep_decim3; 16- and 8-column lanes) and level 0 inside the expansion kernel.  A batch (prev and
-    next arrays apart: two launches) and a sequence (one array) through the fused-kernel path, against the oracle."""
+    next arrays apart: two launches) and a sequence (one array) through the fused-kernel path, against the oracle, in
+    both arithmetic variants of the pyramid (NSOF_OPT_PYR_FMA; lone calls never reach k_prep_decim3: they take the
+    small-batch schedule)."""
     import torch
     from nsof import _lib, synth
     h, w = shape
@@ -476,10 +481,12 @@ def test_three_level_pyramid_launch_batch_and_sequence(nsof_lib, ctx, oracle, to
     assert nsof_lib.effective_levels(w, h, 0.5, 3) == 3
     base, _ = synth.make_pair(31, h + 16, w + 16)
     frames = np.stack([np.ascontiguousarray(base[2 * i:2 * i + h, 3 * i:3 * i + w]) for i in range(n + 1)])
-    want = [oracle.farneback(frames[i], frames[i + 1], *A) for i in range(n)]
     P = nsof_lib.FarnebackParams(*A)
     ctx.set_option(_lib.OPT_SMALL_BATCH_JOBS, 0)
     try:
+        ctx.set_option(_lib.OPT_PYR_FMA, fma)
+        oracle.set_pyr_fma(bool(fma))
+        want = [oracle.farneback(frames[i], frames[i + 1], *A) for i in range(n)]
         dp, dn = _dev(torch_dev, frames[:-1].copy()), _dev(torch_dev, frames[1:].copy())
         df = torch.empty((n, h, w, 2), dtype=torch.float32, device=torch_dev)
         nsof_lib.farneback_batch(dp, dn, df, n, h, w, P, ctx=ctx)
@@ -492,6 +499,8 @@ def test_three_level_pyramid_launch_batch_and_sequence(nsof_lib, ctx, oracle, to
         seq = out.cpu().numpy()
     finally:
         ctx.set_option(_lib.OPT_SMALL_BATCH_JOBS, 64)
+        ctx.set_option(_lib.OPT_PYR_FMA, 0)
+        oracle.set_pyr_fma(False)
     for i in range(n):
         assert np.array_equal(got[i], want[i]), ("batch", i, float(np.abs(got[i] - want[i]).max()))
         assert np.array_equal(seq[i], want[i]), ("sequence", i, float(np.abs(seq[i] - want[i]).max()))
@@ -706,22 +715,30 @@ def test_more_pairs_than_one_grid_holds(nsof_lib, ctx, torch_dev):
 def test_pyramid_fma_variant_twin(nsof_lib, ctx, oracle, torch_dev):
     """NSOF_OPT_PYR_FMA: the arithmetic-variant twin of the pyramid stages (float Gaussian blur + bilinear resamples with
     one fused multiply-add per tap / blend, as an AVX2+FMA3 build of the library's vector loops contracts them).  GPU and
-    CPU oracle agree bit for bit IN EACH VARIANT -- pyramid levels of every kernel family (same-size, exact decimation,
-    generic scales), the flow resample, and the whole call for the reference's three parameter sets -- and the two
-    variants differ from each other (by what DESIGN.md section 2 reports)."""
+    CPU oracle agree bit for bit IN EACH VARIANT -- pyramid levels of every kernel family (same-size, exact decimation
+    with 16- and 8-column lanes, generic scales, the LDS-tiled kernel with run-time taps and the per-pixel fallback), the
+    flow resample, and the whole call for the reference's three parameter sets -- and the two variants differ from each
+    other (by what DESIGN.md section 2 reports)."""
     import torch
     from nsof import _lib, synth
     assert ctx.get_option(_lib.OPT_PYR_FMA) == 0
-    shapes = [(270, 480), (200, 303), (256, 512)]
+    levels = [(0.5, 0), (0.5, 1), (0.5, 2), (0.5, 3), (0.6, 1), (0.6, 2), (0.6, 3), (0.75, 2)]
+    shapes = [((270, 480), levels),
+              # pyr_scale 0.4: level 2 blurs with 13 taps (k_prep_tiled<0>, taps at run time), level 3 with 37 (the tile
+              # would need ~136 KB of LDS: k_prep_naive)
+              ((200, 303), levels + [(0.4, 2), (0.4, 3)]),
+              ((256, 512), levels),
+              # W % 16 == 8: k_prep_decim with 8-column lanes at /2, /4, /8
+              ((64, 72), [(0.5, 1), (0.5, 2), (0.5, 3)])]
     try:
         res = {}
         for fma in (0, 1):
             ctx.set_option(_lib.OPT_PYR_FMA, fma)
             oracle.set_pyr_fma(bool(fma))
-            for shape in shapes:
+            for shape, shape_levels in shapes:
                 prev, nxt = synth.make_pair(100 + shape[0], *shape)
                 d = _dev(torch_dev, np.stack([prev, nxt]))
-                for pyr_scale, level in [(0.5, 0), (0.5, 1), (0.5, 2), (0.5, 3), (0.6, 1), (0.6, 2), (0.6, 3), (0.75, 2)]:
+                for pyr_scale, level in shape_levels:
                     wk, hk, _, _ = nsof_lib.level_size(shape[1], shape[0], pyr_scale, level)
                     out = torch.empty((2, hk, wk), dtype=torch.float32, device=torch_dev)
                     ctx.check(ctx._lib.nsof_stage_pyr_level(ctx.ptr, 2, d.data_ptr(), shape[1], shape[0] * shape[1], shape[1],

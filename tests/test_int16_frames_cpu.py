@@ -85,9 +85,10 @@ def test_16bit_kernels_run_without_scratch(nsof_lib, tmp_path):
         elf.write_bytes(co)
         notes = subprocess.run([readelf, "--notes", str(elf)], check=True, capture_output=True, text=True).stdout
         for name, md in parse_kernel_metadata(notes).items():
-            # Itanium mangling: `t` = unsigned short, `s` = short as the last template argument (`tEE` / `sEE`, or the
-            # source-type argument of k_polyexp_rs after its three non-type arguments)
-            m = re.search(r"(k_prep_\w+?|k_polyexp_rs)I.*?([ts])E(?:EvP|Ev)", name)
+            # Itanium mangling: `t` = unsigned short, `s` = short as the last type argument (`tEE` / `sEE`: the source-type
+            # argument of k_polyexp_rs after its three non-type arguments; in the pyramid kernels the arithmetic variant
+            # follows it, `tLb0EEE` / `tLb1EEE`: both variants are held to the rule)
+            m = re.search(r"(k_prep_\w+?|k_polyexp_rs)I.*?([ts])(?:Lb[01]E)?E(?:EvP|Ev)", name)
             if not m or not (m.group(1).startswith("k_prep") or "ELb1E" in name):
                 continue
             found.setdefault(m.group(1), set()).add(m.group(2))
