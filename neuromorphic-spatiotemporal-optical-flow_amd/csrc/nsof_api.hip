@@ -1,7 +1,5 @@
-// libnsof.so host side: context, error channel, profiling hooks, Farneback level driver.
-// The level loop mirrors the driver of the reference's flow backend
-// (cv2.calcOpticalFlowFarneback, called at /root/reference/optical_flow_seg.py:203):
-// coarsest level first, every level resampled from the blurred FULL-RES frame.
+// libnsof.so host side: context, error channel, profiling hooks, filter taps, level geometry, stage entry points.
+// (The Farneback level driver is farneback_driver.hip.)
 #include <cctype>
 #include <cfloat>
 #include <cmath>
@@ -469,14 +467,14 @@ extern "C" int nsof_farneback_level_size(int width, int height, double pyr_scale
     return NSOF_OK;
 }
 
-int nsof_check_farneback_params(nsof_ctx* ctx, int width, int height, double pyr_scale, int levels, int winsize,
-                                int iterations, int poly_n, int flags)
+int nsof_check_farneback_params(nsof_ctx* ctx, int width, int height, const nsof_fb_params& p)
 {
+    const int levels = p.levels, winsize = p.winsize, iterations = p.iterations, poly_n = p.poly_n, flags = p.flags;
     if (width < 1 || height < 1) return nsof_set_error(ctx, NSOF_ESHAPE, "empty image %dx%d", width, height);
     if ((long long)width * height > (1ll << 27))   // kernels address one image with 32-bit byte offsets
         return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "image %dx%d exceeds 2^27 pixels", width, height);
-    if (!(pyr_scale > 0) || !(pyr_scale < 1))
-        return nsof_set_error(ctx, NSOF_EINVAL, "pyr_scale=%g must be in (0,1)", pyr_scale);
+    if (!(p.pyr_scale > 0) || !(p.pyr_scale < 1))
+        return nsof_set_error(ctx, NSOF_EINVAL, "pyr_scale=%g must be in (0,1)", p.pyr_scale);
     if (winsize == 1)  // upstream's running sums are ill-formed for a 1x1 window (m = 0); never used by the reference
         return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "winsize=1 is not supported");
     if (levels < 0 || winsize < 1 || iterations < 0)
@@ -631,435 +629,6 @@ extern "C" int nsof_stage_flow_upsample(nsof_ctx* ctx, int n_pairs, const float*
 {
     if (!ctx || !d_src || !d_dst || n_pairs < 1 || sw < 1 || sh < 1 || dw < 1 || dh < 1) return NSOF_EINVAL;
     return nsof_launch_flow_upsample(ctx, n_pairs, d_src, sw, sh, d_dst, dw, dh, (float)(1. / pyr_scale));
-}
-
-// ---- the Farneback driver --------------------------------------------------------------------
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// Workspace of the uniform driver for B pairs: I [n_img][nk] f32 and R [n_img][5*nk] f32 (level images and
-// expansions: one slot that every level reuses, or one slot per level for the latency schedule `lat`), S = second flow
-// buffer [B][n0][2], M [B][5][n0] (the unfused forms and the small-batch form), V = column sums [B][5][n0] f64 (the
-// unfused and the small-batch exact forms; the Gaussian form has none).  Offsets in bytes, in that order.
-struct Carve {
-    std::vector<size_t> offI, offR;   // per level, within I / R
-    size_t szI = 0, szR = 0, szS = 0, szM = 0, szV = 0;
-    size_t total() const { return szI + szR + szS + szM + szV; }
-};
-static Carve farneback_carve(size_t B, bool sequence, int width, int height, double pyr_scale, int L, bool lat,
-                             nsof_iter_form form)
-{
-    Carve c;
-    c.offI.assign(L + 1, 0);
-    c.offR.assign(L + 1, 0);
-    const size_t n0 = (size_t)width * height;
-    const size_t n_img = sequence ? B + 1 : 2 * B;   // frames of a sequence, or B prev + B next frames
-    for (int k = 0; k <= (lat ? L : 0); k++) {
-        int wk, hk;
-        nsof_farneback_level_size(width, height, pyr_scale, k, &wk, &hk, nullptr, nullptr);
-        c.offI[k] = c.szI;
-        c.offR[k] = c.szR;
-        c.szI += align_up(n_img * (size_t)wk * hk * 4, 256);
-        c.szR += align_up(n_img * 5 * (size_t)wk * hk * 4, 256);
-    }
-    c.szS = align_up(B * n0 * 8, 256);
-    const bool M = form != NSOF_ITER_FAST && form != NSOF_ITER_EXACT;
-    const bool V = form == NSOF_ITER_UNFUSED_EXACT || form == NSOF_ITER_EXACT_LAT;
-    c.szM = M ? align_up(B * 5 * n0 * 4, 256) : 0;
-    c.szV = V ? align_up(B * 5 * n0 * 8, 256) : 0;
-    return c;
-}
-
-// Core of both device entry points.  sequence == false: n_pairs independent pairs (d_prev[i], d_next[i]);
-// sequence == true: n_pairs + 1 consecutive frames in d_prev (d_next unused), pair i = (frame i, frame i+1) -- every
-// frame's pyramid level and polynomial expansion is then computed once and shared by the two pairs it belongs to.
-// src (nsof_src_type): 8-bit, 16-bit or float frames.  Only the pyramid stage reads the frames; the frame pointers below are
-// byte addresses and both strides are in bytes whatever the pixel type.
-int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* prev_frames, const void* next_frames,
-                          ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height, float* d_flow,
-                          double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma,
-                          int flags, int src)
-{
-    if (!ctx) return NSOF_EINVAL;
-    const uint8_t* d_prev = static_cast<const uint8_t*>(prev_frames);
-    const uint8_t* d_next = sequence ? d_prev : static_cast<const uint8_t*>(next_frames);
-    if (!d_prev || !d_next || !d_flow || n_pairs < 1) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer or n_pairs<1");
-    int rc = nsof_check_farneback_params(ctx, width, height, pyr_scale, levels, winsize, iterations, poly_n, flags);
-    if (rc) return rc;
-    const int px_bytes = nsof_src_bytes(src);
-    if (row_stride < (ptrdiff_t)width * px_bytes) return nsof_set_error(ctx, NSOF_EINVAL, "row_stride < width * %d", px_bytes);
-    NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    const nsof_iter_form form = nsof_iterate_form(ctx, winsize, width, height, iterations,
-                                                  n_pairs * nsof_iterate_jobs(width, height), flags);
-    const int exact_chunk = 64;
-    if (form == NSOF_ITER_UNFUSED_EXACT && (sequence || n_pairs > exact_chunk)) {
-        // the exact order keeps 40 B/px of column sums (+ 20 B/px of matrices) in HBM: 64 pairs of 1920x1080 at a time
-        // (8 GB) fill the GPU -- the row walk has one thread per image row; a sequence is run as its pairs
-        const uint8_t* nx = sequence ? d_prev + pair_stride : d_next;
-        for (int i = 0; i < n_pairs; i += exact_chunk) {
-            const int nb = n_pairs - i < exact_chunk ? n_pairs - i : exact_chunk;
-            rc = nsof_farneback_core(ctx, false, nb, d_prev + (ptrdiff_t)i * pair_stride, nx + (ptrdiff_t)i * pair_stride,
-                                     row_stride, pair_stride, width, height, d_flow + (size_t)i * width * height * 2,
-                                     pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, src);
-            if (rc) return rc;
-        }
-        return NSOF_OK;
-    }
-
-    const int L = nsof_farneback_effective_levels(width, height, pyr_scale, levels);
-    const bool fused = nsof_form_fused(form);
-    // ---- small batches (the three-kernel exact form): the latency schedule ---------------------------------------------
-    // A lone call is a chain of ~50 launches that each use a fraction of the chip and cost >= ~5 us (profiles/
-    // r03_lone_call_timeline.txt: 762 us at 1080p, a third of it in the two coarsest levels).  Only the FLOW couples the
-    // levels; pyramid level and polynomial expansion of every level depend on the input frames alone.  So they move to a
-    // side stream (levels L-1 .. 0, into per-level buffers) and run next to the iterations of the coarser levels on the
-    // main stream; an event per level hands the expansion over.  Same kernels, same arguments, same bits.
-    const bool lat = form == NSOF_ITER_EXACT_LAT && L >= 1;
-    auto carve = [&](size_t b) { return farneback_carve(b, sequence, width, height, pyr_scale, L, lat, form); };
-    const Carve cv = carve((size_t)n_pairs);
-    {
-        // A batch whose workspace would not fit the device's free memory is run in chunks of as many pairs as do fit --
-        // same kernels on sub-ranges of the same buffers, so the result does not depend on the chunking.  A batch that
-        // fits the workspace already held needs no query (lone calls stay cheap).  NSOF_MAX_PAIRS caps the chunk by
-        // hand (tests).
-        size_t fit = (size_t)n_pairs;
-        if (cv.total() > ctx->ws.cap) {
-            size_t free_b = 0, total_b = 0;
-            NSOF_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-            const size_t budget = (size_t)((double)(free_b + ctx->ws.cap) * 0.92);
-            size_t lo = 0, hi = (size_t)n_pairs;   // the most pairs whose workspace fits the budget
-            while (lo < hi) {
-                const size_t mid = (lo + hi + 1) / 2;
-                if (carve(mid).total() <= budget) lo = mid;
-                else hi = mid - 1;
-            }
-            fit = lo;
-        }
-        if (const char* e = getenv("NSOF_MAX_PAIRS")) {
-            const long v = atol(e);
-            if (v >= 1 && (size_t)v < fit) fit = (size_t)v;
-        }
-        if (fit < 1) fit = 1;
-        if (fit > 32767) fit = 32767;   // 2 * pairs images go on gridDim.z of one launch
-        if ((size_t)n_pairs > fit) {
-            for (int i = 0; i < n_pairs; i += (int)fit) {
-                const int nb = n_pairs - i < (int)fit ? n_pairs - i : (int)fit;
-                rc = nsof_farneback_core(ctx, sequence, nb, d_prev + (ptrdiff_t)i * pair_stride,
-                                         d_next + (ptrdiff_t)i * pair_stride, row_stride, pair_stride, width, height,
-                                         d_flow + (size_t)i * width * height * 2, pyr_scale, levels, winsize, iterations,
-                                         poly_n, poly_sigma, flags, src);
-                if (rc) return rc;
-            }
-            return NSOF_OK;
-        }
-    }
-
-    nsof_poly_taps ptaps;
-    if ((rc = nsof_host_poly_taps(poly_n, poly_sigma, &ptaps))) return nsof_set_error(ctx, rc, "poly taps");
-    const size_t n0 = (size_t)width * height, B = (size_t)n_pairs;
-    const size_t n_img = sequence ? B + 1 : 2 * B;
-    const size_t szI = cv.szI, szR = cv.szR, szS = cv.szS, szM = cv.szM;
-    if ((rc = ctx->ws.reserve(ctx, cv.total()))) return rc;
-    char* base = (char*)ctx->ws.p;
-    auto level_I = [&](int k) { return (float*)(base + cv.offI[k]); };
-    auto level_R = [&](int k) { return (float*)(base + szI + cv.offR[k]); };
-    float* dS = (float*)(base + szI + szR);
-    float* dM = (float*)(base + szI + szR + szS);
-    double* dV = (double*)(base + szI + szR + szS + szM);
-    // Two flow buffers, A = the caller's output and S = scratch; every level uses their leading B*nk pixels.
-    // Each upsample and each fused iteration moves the flow to the other buffer, so the buffer the coarsest
-    // level starts in is chosen such that the last iteration of level 0 writes A.
-    float* fb[2] = {d_flow, dS};
-    const int flips = fused ? L * (1 + iterations) + iterations : L;
-    int cur = flips & 1;
-
-    // prev and next frames of a batch that lie back to back (the host-pointer entry stages a lone pair that way) are one
-    // array of 2 B images: one pyramid launch per level instead of two (a lone call's launches have a ~5 us floor each)
-    const bool prep_merged = !sequence && d_next == d_prev + (ptrdiff_t)n_pairs * pair_stride;
-    auto prep_level = [&](int wk, int hk, const nsof_blur_taps& bt, float* I) -> int {
-        const size_t nk = (size_t)wk * hk;
-        if (sequence || prep_merged)
-            return nsof_launch_prep(ctx, (int)n_img, d_prev, row_stride, pair_stride, width, height, wk, hk, bt, I, src);
-        for (int i = 0; i < 2; i++)
-            if (int r = nsof_launch_prep(ctx, n_pairs, i == 0 ? d_prev : d_next, row_stride, pair_stride, width, height,
-                                     wk, hk, bt, I + (size_t)i * B * nk, src))
-                return r;
-        return NSOF_OK;
-    };
-
-    // Level 0 (the frame's own size, 3-tap smoothing): the expansion kernel forms the level image itself from the 8- or
-    // 16-bit frames (k_polyexp_rs<.., FRAME, SRC>): no pyramid launch, no image written and read back.  Not with the FMA
-    // twin of the pyramid stages nor with the float expansion (their kernels have no such form), nor for f32 frames:
-    // those take the two-kernel form (k_prep_same3_vec<.., float>, then the expansion of the level image).
-    const bool poly_frames = src != NSOF_SRC_F32 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && width >= 2 && height >= 2;
-    float* Ifused[4] = {nullptr, nullptr, nullptr, nullptr};   // level images already made by the three-level launch
-    // pyramid level + expansion of level k on the current ctx->stream, into the level's slot
-    auto level_images = [&](int k, int wk, int hk, const nsof_blur_taps& bt) -> int {
-        float* Rk = level_R(k);
-        if (k >= 1 && k <= 3 && Ifused[k]) return nsof_launch_polyexp(ctx, (int)n_img, Ifused[k], wk, hk, ptaps, Rk);
-        if (poly_frames && k == 0 && bt.ksize == 3 && wk == width && hk == height) {
-            const bool one = sequence || prep_merged;
-            return nsof_launch_polyexp_frames(ctx, (int)n_img, d_prev, one ? d_prev : d_next, one ? (int)n_img : n_pairs, row_stride,
-                                          pair_stride, width, height, ptaps, bt.k[1], bt.k[2], Rk, src);
-        }
-        if (int r = prep_level(wk, hk, bt, level_I(k))) return r;
-        return nsof_launch_polyexp(ctx, (int)n_img, level_I(k), wk, hk, ptaps, Rk);
-    };
-
-    const hipStream_t mainS = ctx->stream;
-    if (lat) {
-        // the coarsest level is needed first: main stream; levels L-1 .. 0 on the side stream, an event after each
-        if (!ctx->side) NSOF_HIP(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-        while (ctx->ov_events.size() < (size_t)(L + 2)) {
-            hipEvent_t ev;
-            NSOF_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            ctx->ov_events.push_back(ev);
-        }
-        struct StreamSwap {
-            nsof_ctx* cx; hipStream_t saved;
-            StreamSwap(nsof_ctx* cc, hipStream_t st) : cx(cc), saved(cc->stream) { cx->stream = st; }
-            ~StreamSwap() { cx->stream = saved; }
-        };
-        const hipStream_t sideS = ctx->side;
-        NSOF_HIP(ctx, hipEventRecord(ctx->ov_events[L + 1], mainS));            // the frames are on the device; earlier calls are done
-        NSOF_HIP(ctx, hipStreamWaitEvent(sideS, ctx->ov_events[L + 1], 0));
-        for (int k = L; k >= 0; k--) {
-            int wk, hk;
-            nsof_blur_taps bt;
-            if ((rc = nsof_level_geom(ctx, width, height, pyr_scale, k, &wk, &hk, &bt))) return rc;
-            StreamSwap sw(ctx, k == L ? mainS : sideS);
-            if ((rc = level_images(k, wk, hk, bt))) return rc;
-            if (k < L) NSOF_HIP(ctx, hipEventRecord(ctx->ov_events[k], sideS));
-        }
-    } else if (L == 3) {
-        // pyr_scale 0.5 with three coarser levels (the headline configuration): levels 1..3 smooth and decimate the same
-        // full-resolution frames -- one launch makes all three (k_prep_decim3), into the level-image buffer that level 0
-        // no longer needs before the coarser levels are done with it
-        nsof_blur_taps bt3[3];
-        size_t nk3[3];
-        bool exact3 = true;
-        for (int k = 1; k <= 3 && exact3; k++) {
-            int wk, hk;
-            exact3 = nsof_level_geom(nullptr, width, height, pyr_scale, k, &wk, &hk, &bt3[k - 1]) == 0 &&
-                     wk * (1 << k) == width && hk * (1 << k) == height;
-            nk3[k - 1] = (size_t)wk * hk;
-        }
-        if (exact3) {
-            float* dI = level_I(0);
-            float* I3[3] = {dI, dI + n_img * nk3[0], dI + n_img * (nk3[0] + nk3[1])};
-            const bool one = sequence || prep_merged;
-            rc = nsof_launch_prep_decim3(ctx, one ? (int)n_img : n_pairs, d_prev, row_stride, pair_stride, width, height, bt3, I3, src);
-            if (rc == NSOF_OK && !one) {
-                float* I3n[3] = {I3[0] + B * nk3[0], I3[1] + B * nk3[1], I3[2] + B * nk3[2]};
-                rc = nsof_launch_prep_decim3(ctx, n_pairs, d_next, row_stride, pair_stride, width, height, bt3, I3n, src);
-            }
-            if (rc == NSOF_OK) {
-                for (int k = 1; k <= 3; k++) Ifused[k] = I3[k - 1];
-            } else if (rc != NSOF_EUNSUPPORTED) {
-                return rc;
-            }
-        }
-    }
-
-    int pw = 0, ph = 0;
-    for (int k = L; k >= 0; k--) {
-        int wk, hk;
-        nsof_blur_taps btaps;
-        if ((rc = nsof_level_geom(ctx, width, height, pyr_scale, k, &wk, &hk, &btaps))) return rc;
-        const size_t nk = (size_t)wk * hk;
-        if (k == L) {
-            NSOF_HIP(ctx, hipMemsetAsync(fb[cur], 0, B * nk * 8, mainS));
-        } else {
-            if ((rc = nsof_launch_flow_upsample(ctx, n_pairs, fb[cur], pw, ph, fb[cur ^ 1], wk, hk,
-                                   (float)(1. / pyr_scale))))
-                return rc;
-            cur ^= 1;
-        }
-        if (!lat) {
-            if ((rc = level_images(k, wk, hk, btaps))) return rc;
-        } else if (k < L) {
-            NSOF_HIP(ctx, hipStreamWaitEvent(mainS, ctx->ov_events[k], 0));   // this level's expansion is ready
-        }
-        // image-major: I [n_img][hk][wk], R [n_img][5*hk*wk].  Pairs: all prev frames then all next frames
-        // (R1 = R0 + B images); sequence: the frames in order (R1 = R0 + 1 image).
-        const float* R0 = level_R(k);
-        const float* R1 = R0 + (sequence ? (size_t)1 : B) * 5 * nk;
-        if (fused) {
-            for (int it = 0; it < iterations; it++) {
-                if (form == NSOF_ITER_EXACT_LAT)
-                    rc = nsof_launch_iterate_lat(ctx, n_pairs, R0, R1, 5 * nk, fb[cur], fb[cur ^ 1], wk, hk, winsize, dM, dV);
-                else if (form == NSOF_ITER_EXACT)
-                    rc = nsof_launch_iterate_x(ctx, n_pairs, R0, R1, 5 * nk, fb[cur], fb[cur ^ 1], wk, hk, winsize);
-                else
-                    rc = nsof_launch_iterate(ctx, n_pairs, R0, R1, 5 * nk, fb[cur], fb[cur ^ 1], wk, hk, winsize);
-                if (rc) return rc;
-                cur ^= 1;
-            }
-        } else {
-            float* flow = fb[cur];
-            for (int it = 0; it < iterations; it++) {
-                if ((rc = nsof_launch_update_matrices(ctx, n_pairs, R0, R1, 5 * nk, flow, wk, hk, dM))) return rc;
-                if (form == NSOF_ITER_UNFUSED_GAUSS) rc = nsof_launch_gauss_blur_solve(ctx, n_pairs, dM, wk, hk, winsize, flow);
-                else if (form == NSOF_ITER_UNFUSED_EXACT) rc = nsof_launch_blur_solve_exact(ctx, n_pairs, dM, wk, hk, winsize, dV, flow);
-                else rc = nsof_launch_blur_solve(ctx, n_pairs, dM, wk, hk, winsize, flow);
-                if (rc) return rc;
-            }
-        }
-        pw = wk;
-        ph = hk;
-    }
-    if (fb[cur] != d_flow)  // cannot happen by construction; keep the result correct regardless
-        NSOF_HIP(ctx, hipMemcpyAsync(d_flow, fb[cur], B * n0 * 8, hipMemcpyDeviceToDevice, mainS));
-    return NSOF_OK;
-}
-
-// ---- the uniform routes: device batch and device sequence ----------------------------------------------------------
-// Every route has ONE typed entry (nsof_pixel_type == nsof_src_type) that does the work, in this order: context, pixel
-// type, null pointers and counts, frame layout, then the driver with its parameter checks.  The nsof_farneback_u8* and
-// nsof_farneback_f32* exports name the pixel type and forward (the end of this file and of farneback_batch.hip).
-extern "C" int nsof_farneback_px_batch_dev(nsof_ctx* ctx, int pixel_type, int n_pairs, const void* d_prev, const void* d_next,
-                                           ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height, float* d_flow,
-                                           double pyr_scale, int levels, int winsize, int iterations, int poly_n,
-                                           double poly_sigma, int flags)
-{
-    if (int rc = nsof_check_typed(ctx, pixel_type)) return rc;
-    if (!d_prev || !d_next || !d_flow) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer");
-    int rc = nsof_check_frame_layout(ctx, pixel_type, d_prev, row_stride, pair_stride, width, "d_prev");
-    if (rc == NSOF_OK) rc = nsof_check_frame_layout(ctx, pixel_type, d_next, row_stride, pair_stride, width, "d_next");
-    if (rc) return rc;
-    return nsof_farneback_core(ctx, false, n_pairs, d_prev, d_next, row_stride, pair_stride, width, height, d_flow, pyr_scale,
-                               levels, winsize, iterations, poly_n, poly_sigma, flags, pixel_type);
-}
-
-extern "C" int nsof_farneback_px_sequence_dev(nsof_ctx* ctx, int pixel_type, int n_frames, const void* d_frames,
-                                              ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
-                                              float* d_flow, double pyr_scale, int levels, int winsize, int iterations,
-                                              int poly_n, double poly_sigma, int flags)
-{
-    if (int rc = nsof_check_typed(ctx, pixel_type)) return rc;
-    if (n_frames < 2) return nsof_set_error(ctx, NSOF_EINVAL, "a sequence needs at least 2 frames");
-    if (!d_frames || !d_flow) return nsof_set_error(ctx, NSOF_EINVAL, "null buffer");
-    if (int rc = nsof_check_frame_layout(ctx, pixel_type, d_frames, row_stride, frame_stride, width, "d_frames")) return rc;
-    return nsof_farneback_core(ctx, true, n_frames - 1, d_frames, nullptr, row_stride, frame_stride, width, height, d_flow,
-                               pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, pixel_type);
-}
-
-// ---- the lone host pair ----------------------------------------------------------------------------------------------
-// src: nsof_src_type.  Dense frames go straight from the caller's memory; strided host views are packed row by row into
-// a pinned staging buffer and moved with ONE linear copy per direction: hipMemcpy2D degenerates to a copy per row for
-// widths that are not nicely aligned (measured 12 ms for an 801x801 pair against 3 ms of kernels).  On the device the
-// pair lies back to back (one pyramid launch per level for both frames).  8-bit frames take any row stride, a flipped
-// view's negative one included (nsof_check_frame_layout has nothing to check for them); the parameter checks come
-// before the layout check here, so an empty image is NSOF_ESHAPE whatever its strides.
-static int farneback_host_pair(nsof_ctx* ctx, int src, const void* prev, ptrdiff_t prev_stride, const void* next,
-                               ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
-                               double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma,
-                               int flags)
-{
-    if (!prev || !next || !flow) return nsof_set_error(ctx, NSOF_EINVAL, "null image pointer");
-    int rc = nsof_check_farneback_params(ctx, width, height, pyr_scale, levels, winsize, iterations, poly_n, flags);
-    if (rc) return rc;
-    if ((rc = nsof_check_frame_layout(ctx, src, prev, prev_stride, 0, width, "prev")) ||
-        (rc = nsof_check_frame_layout(ctx, src, next, next_stride, 0, width, "next")))
-        return rc;
-    if (flow_stride < (ptrdiff_t)(width * 8)) return nsof_set_error(ctx, NSOF_EINVAL, "flow_stride < width*8");
-    NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n0 = (size_t)width * height, pitch = (size_t)width * nsof_src_bytes(src);
-    const size_t szU = align_up(pitch * height, 256), szF = align_up(n0 * 8, 256);
-    if ((rc = ctx->stage.reserve(ctx, 2 * szU + szF)) || (rc = ctx->hstage.reserve(ctx, 2 * szU + szF))) return rc;
-    char* hP = (char*)ctx->hstage.p;
-    char* hN = hP + szU;
-    float* hF = (float*)(hN + szU);
-    char* dP = (char*)ctx->stage.p;
-    char* dN = dP + szU;
-    float* dFl = (float*)(dN + szU);
-    const bool in_dense = prev_stride == (ptrdiff_t)pitch && next_stride == (ptrdiff_t)pitch;
-    const bool out_dense = flow_stride == (ptrdiff_t)width * 8;
-    if (in_dense) {
-        NSOF_HIP(ctx, hipMemcpyAsync(dP, prev, pitch * height, hipMemcpyHostToDevice, ctx->stream));
-        NSOF_HIP(ctx, hipMemcpyAsync(dN, next, pitch * height, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        for (int y = 0; y < height; y++) {
-            memcpy(hP + (size_t)y * pitch, (const char*)prev + (ptrdiff_t)y * prev_stride, pitch);
-            memcpy(hN + (size_t)y * pitch, (const char*)next + (ptrdiff_t)y * next_stride, pitch);
-        }
-        NSOF_HIP(ctx, hipMemcpyAsync(dP, hP, 2 * szU, hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = nsof_farneback_core(ctx, false, 1, dP, dN, (ptrdiff_t)pitch, (ptrdiff_t)szU, width, height, dFl, pyr_scale, levels,
-                             winsize, iterations, poly_n, poly_sigma, flags, src);
-    if (rc) return rc;
-    NSOF_HIP(ctx, hipMemcpyAsync(out_dense ? flow : hF, dFl, n0 * 8, hipMemcpyDeviceToHost, ctx->stream));
-    // a hand-over between workgroups that never arrived (the exact-order kernels' bounded waits) fails the call, as cv2
-    // raises where it fails: the flow of such a launch is never handed back as a result
-    if ((rc = nsof_stream_sync_checked(ctx))) return rc;
-    if (!out_dense)
-        for (int y = 0; y < height; y++)
-            memcpy((char*)flow + (ptrdiff_t)y * flow_stride, hF + (size_t)y * width * 2, (size_t)width * 8);
-    return NSOF_OK;
-}
-
-extern "C" int nsof_farneback_px(nsof_ctx* ctx, int pixel_type, const void* prev, ptrdiff_t prev_stride, const void* next,
-                                 ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
-                                 double pyr_scale, int levels, int winsize, int iterations, int poly_n,
-                                 double poly_sigma, int flags)
-{
-    if (int rc = nsof_check_typed(ctx, pixel_type)) return rc;
-    return farneback_host_pair(ctx, pixel_type, prev, prev_stride, next, next_stride, width, height, flow, flow_stride,
-                               pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
-}
-
-// ---- the 8-bit and float32 exports of these routes: the typed entry with the pixel type named ---------------------------
-extern "C" int nsof_farneback_u8(nsof_ctx* ctx, const uint8_t* prev, ptrdiff_t prev_stride, const uint8_t* next,
-                                 ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
-                                 double pyr_scale, int levels, int winsize, int iterations, int poly_n,
-                                 double poly_sigma, int flags)
-{
-    return nsof_farneback_px(ctx, NSOF_PIXEL_U8, prev, prev_stride, next, next_stride, width, height, flow, flow_stride,
-                             pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
-}
-
-extern "C" int nsof_farneback_f32(nsof_ctx* ctx, const float* prev, ptrdiff_t prev_stride, const float* next,
-                                  ptrdiff_t next_stride, int width, int height, float* flow, ptrdiff_t flow_stride,
-                                  double pyr_scale, int levels, int winsize, int iterations, int poly_n,
-                                  double poly_sigma, int flags)
-{
-    return nsof_farneback_px(ctx, NSOF_PIXEL_F32, prev, prev_stride, next, next_stride, width, height, flow, flow_stride,
-                             pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
-}
-
-extern "C" int nsof_farneback_u8_batch_dev(nsof_ctx* ctx, int n_pairs, const uint8_t* d_prev, const uint8_t* d_next,
-                                           ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height,
-                                           float* d_flow, double pyr_scale, int levels, int winsize, int iterations,
-                                           int poly_n, double poly_sigma, int flags)
-{
-    return nsof_farneback_px_batch_dev(ctx, NSOF_PIXEL_U8, n_pairs, d_prev, d_next, row_stride, pair_stride, width, height,
-                                       d_flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
-}
-
-extern "C" int nsof_farneback_f32_batch_dev(nsof_ctx* ctx, int n_pairs, const float* d_prev, const float* d_next,
-                                            ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height,
-                                            float* d_flow, double pyr_scale, int levels, int winsize, int iterations,
-                                            int poly_n, double poly_sigma, int flags)
-{
-    return nsof_farneback_px_batch_dev(ctx, NSOF_PIXEL_F32, n_pairs, d_prev, d_next, row_stride, pair_stride, width, height,
-                                       d_flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
-}
-
-extern "C" int nsof_farneback_u8_sequence_dev(nsof_ctx* ctx, int n_frames, const uint8_t* d_frames,
-                                              ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
-                                              float* d_flow, double pyr_scale, int levels, int winsize,
-                                              int iterations, int poly_n, double poly_sigma, int flags)
-{
-    return nsof_farneback_px_sequence_dev(ctx, NSOF_PIXEL_U8, n_frames, d_frames, row_stride, frame_stride, width, height,
-                                          d_flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
-}
-
-extern "C" int nsof_farneback_f32_sequence_dev(nsof_ctx* ctx, int n_frames, const float* d_frames,
-                                               ptrdiff_t row_stride, ptrdiff_t frame_stride, int width, int height,
-                                               float* d_flow, double pyr_scale, int levels, int winsize,
-                                               int iterations, int poly_n, double poly_sigma, int flags)
-{
-    return nsof_farneback_px_sequence_dev(ctx, NSOF_PIXEL_F32, n_frames, d_frames, row_stride, frame_stride, width, height,
-                                          d_flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
 }
 
 // ---- ROI gating (host arithmetic on maps of at most a few hundred cells) -------------------------------------------

@@ -151,7 +151,7 @@ struct nsof_prof_scope {
     ~nsof_prof_scope();
 };
 
-// ---- Farneback driver pieces shared between nsof_api.hip and farneback_batch.hip -------------------------------
+// ---- Farneback driver pieces shared between farneback_driver.hip and farneback_batch.hip -------------------------------
 // Pixel type of the frames a uniform batch reads (the pyramid stage is the only one that reads them).  Frame pointers
 // stay byte addresses and every stride stays in bytes for all of them.  The values are those of the public
 // nsof_pixel_type.
@@ -181,13 +181,24 @@ static inline int nsof_check_typed(nsof_ctx* ctx, int pixel_type)
 // both strides are multiples of the pixel size and the row stride is at least pixel size * width.
 int nsof_check_frame_layout(nsof_ctx* ctx, int src, const void* p, ptrdiff_t row_stride, ptrdiff_t img_stride, int width,
                             const char* who, ...) __attribute__((format(printf, 7, 8)));
-int nsof_check_farneback_params(nsof_ctx* ctx, int width, int height, double pyr_scale, int levels, int winsize,
-                                int iterations, int poly_n, int flags);
-// Uniform-shape device batch (sequence == true: n_pairs + 1 consecutive frames in d_prev); src: nsof_src_type.
-int nsof_farneback_core(nsof_ctx* ctx, bool sequence, int n_pairs, const void* d_prev, const void* d_next,
-                        ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height, float* d_flow,
-                        double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma,
-                        int flags, int src);
+// What both drivers ask of a row stride whatever the pixel type (an 8-bit frame has no layout to check): it holds a row.
+static inline bool nsof_row_stride_holds(ptrdiff_t row_stride, int width, int src) { return row_stride >= (ptrdiff_t)width * nsof_src_bytes(src); }
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// The Farneback parameters as the entry points take them: every typed entry builds this once, everything below passes it on.
+struct nsof_fb_params { double pyr_scale; int levels, winsize, iterations, poly_n; double poly_sigma; int flags; };
+int nsof_check_farneback_params(nsof_ctx* ctx, int width, int height, const nsof_fb_params& p);
+// Frames of the uniform driver: n_pairs independent pairs (prev[i], next[i]), or (sequence) n_pairs + 1 consecutive frames
+// in prev, pair i = (frame i, frame i + 1), next unused.  Device BYTE addresses and byte strides whatever the pixel type
+// (src: nsof_src_type); pair_stride lies between consecutive frames of either array.
+struct nsof_fb_frames {
+    bool sequence;
+    int n_pairs;
+    const uint8_t *prev, *next;
+    ptrdiff_t row_stride, pair_stride;
+    int width, height, src;
+};
+// Uniform-shape device batch (farneback_driver.hip); d_flow: n_pairs dense fields.
+int nsof_farneback_core(nsof_ctx* ctx, const nsof_fb_frames& frames, float* d_flow, const nsof_fb_params& params);
 void nsof_pipe_destroy(nsof_ctx* ctx);
 
 // ---- Farneback launchers (farneback_pyramid.hip, farneback_polyexp.hip, farneback_blur.hip) ----
@@ -216,6 +227,14 @@ static inline int nsof_level_geom(nsof_ctx* ctx, int width, int height, double p
     return rc;
 }
 int nsof_host_poly_taps(int n, double sigma, nsof_poly_taps* out);
+// Level 0 (the frame's own size, 3-tap smoothing) is formed from the 8- or 16-bit frames by the expansion kernel itself
+// (k_polyexp_rs<.., FRAME, SRC>): no pyramid launch, no image written and read back.  Not with the FMA twin of the pyramid
+// stages nor with the float expansion (their kernels have no such form), nor for f32 frames: those take the two-kernel
+// form (k_prep_same3_vec<.., float>, then the expansion of the level image).  bt: the taps of level 0.
+static inline bool nsof_level0_from_frames(const nsof_ctx* ctx, int src, const nsof_blur_taps& bt)
+{
+    return src != NSOF_SRC_F32 && !ctx->opt_pyr_fma && !ctx->opt_polyexp_f32 && bt.ksize == 3;
+}
 
 // ---- shape-heterogeneous work lists (nsof_farneback_px_batch*, nsof_farneback_px_roi_sequence_dev) ----------------
 // One work item (a frame pair of its own shape) at ONE pyramid level.  The host builds one table per level (items

@@ -90,11 +90,14 @@ def test_dispatch_paths_bit_identical(nsof_lib, ctx, oracle, jobs, path, params,
     _check_all(nsof_lib, ctx, oracle, _frames(17 + n, n + 1, 97, 203), params, path)
 
 
-@pytest.mark.parametrize("winsize", [17, 9])
-def test_more_than_64_pairs(nsof_lib, ctx, oracle, jobs, winsize):
+@pytest.mark.parametrize("winsize,max_pairs", [(17, None), (9, None), (17, "40")], ids=["17", "9", "17-max_pairs40"])
+def test_more_than_64_pairs(nsof_lib, ctx, oracle, jobs, monkeypatch, winsize, max_pairs):
     """winsize 17: the unfused exact path runs batches above 64 pairs and every sequence in 64-pair chunks (a 65-pair
-    batch, a 66-frame sequence); winsize 9: the same sizes through k_iterate_x."""
+    batch, a 66-frame sequence); winsize 9: the same sizes through k_iterate_x.  NSOF_MAX_PAIRS=40: the 64-pair cap and the
+    cap by hand both bind."""
     jobs(0)
+    if max_pairs:
+        monkeypatch.setenv("NSOF_MAX_PAIRS", max_pairs)
     params = (0.5, 2, winsize, 2, 5, 1.1, 0)
     frames = _frames(5, 66, 24, 40)
     want = [oracle.farneback(frames[i], frames[i + 1], *params) for i in range(65)]
