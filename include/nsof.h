@@ -399,7 +399,8 @@ const char* nsof_kernel_name(int kernel_id);
 typedef struct nsof_accum nsof_accum;
 
 /* Device constants default to event_mem_sim.py:20-34 (PARAMS, DT=5e-4, REFRACTORY_US=800; nsof_accum_create_p takes
- * others); THETA_EVENTS=1 is fixed.  scheme: 1 = boxcar window, 2 = DC bias + event overlay (:208-286).
+ * others); scheme 1's THETA_EVENTS defaults to 1 (nsof_accum_set_event_threshold).  scheme: 1 = boxcar window, 2 = DC bias +
+ * event overlay (:208-286).
  * polarity_split: scheme 2 only -- 1 = 'split' (ON p==1 -> array A, OFF p==0 -> array B),
  * 0 = 'magnitude' (one array). */
 int nsof_accum_create(nsof_ctx* ctx, int height, int width, int scheme, int polarity_split,
@@ -413,8 +414,8 @@ int nsof_accum_create(nsof_ctx* ctx, int height, int width, int scheme, int pola
  * operands (integer exponents keep the sign for odd ones).  float64 frame path: the same fields as doubles.
  * Refused with NSOF_EINVAL before anything is launched: a non-finite field (or one that is not finite as float32),
  * !(voff < 0 < von), son or soff outside [0, 1], Ron <= 0 or Roff <= 0, wini outside [0, 1], dt <= 0, refractory_us < 0.
- * Not a parameter: scheme 1's event threshold THETA_EVENTS stays 1 (a count threshold needs per-slice counters instead
- * of mask bits); per-pixel parameter maps and the linear resistance map are not supported either. */
+ * Not a field of this struct: scheme 1's event threshold THETA_EVENTS is a setting of the accumulator
+ * (nsof_accum_set_event_threshold).  Per-pixel parameter maps and the linear resistance map are not supported. */
 typedef struct nsof_accum_params {      /* keys of PARAMS (event_mem_sim.py:20-27); won / woff are read by nothing and not carried */
     double alphaoff, alphaon, voff, von, koff, kon, son, soff, bon, boff, Ron, Roff, wini;
     double dt;                          /* DT, seconds */
@@ -433,6 +434,20 @@ void nsof_accum_destroy(nsof_accum* acc);
  * 1280x720 0.39 vs 0.75-0.89 ms per 30 surface frames, 3840x2160 0.97 vs 1.21 ms), the event-pixel update beyond and in
  * scheme 2; > 0 = always the every-pixel pass (the roofline run); < 0 = the event-pixel update wherever it is exact. */
 int nsof_accum_set_dense(nsof_accum* acc, int force_dense);
+/* Scheme 1's THETA_EVENTS (event_mem_sim.py:33, :208-217): a pixel pulses in a slice when at least theta events fall on it in
+ * that slice, whatever their polarity; default 1.  A run at theta is the theta == 1 run on the stream without the events of
+ * every (pixel, slice) cell that holds fewer than theta events -- every update form, snapshot, surface and frame follows.
+ * May be set between any two advancing calls and holds from the next one.  theta == 1 runs the kernels it always ran (one
+ * mask bit per slice).  theta > 1: the mask word holds a saturating counter of b = ceil(log2(theta + 1)) bits per slice (a
+ * compare-and-swap loop that stops at theta: no count overflows, theta up to INT32_MAX), so a group is 32 / b slices in
+ * the event-pixel update and 2 * (32 / b) in the every-pixel pass instead of 32 and 64, and no memory is added.
+ * nsof_accum_run_frames with theta > 1 never takes the tile walk: where copy + patch applies (every <= 64) it takes copy +
+ * patch, an interval in ceil(every / (64 / b)) rounds of (scatter, update of the touched pixels) on the one 64-bit word per
+ * pixel, the first round copying the frame; n_frames x nsof_accum_run_surface otherwise -- the same bytes either way.
+ * NSOF_EINVAL, with the value in the message and nothing launched, allocated or changed: theta < 1; theta != 1 on a scheme-2
+ * accumulator (the reference records theta_events = None there: the scheme has no count threshold). */
+int nsof_accum_set_event_threshold(nsof_accum* acc, int theta);
+int nsof_accum_get_event_threshold(const nsof_accum* acc, int* theta);
 /* Reset w to the model's wini (default 0.5) and the refractory maps to 0. */
 int nsof_accum_reset(nsof_accum* acc);
 /* Advance by n_slices time slices.  Events are HOST arrays (x,y int16; p int8; t int64 us,

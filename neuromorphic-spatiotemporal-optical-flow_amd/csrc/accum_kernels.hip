@@ -260,12 +260,8 @@ __device__ __forceinline__ int slice_of(const long long* bounds, int n_sl, long 
 // group at 1 M events/s, found with rocprofv3), so the appends of a wave are aggregated -- one atomicAdd of the wave's
 // count, ranks from the ballot.  Call with the whole wave (inactive lanes pass active = false); list == nullptr
 // (every-pixel update: no list is read) skips the list entirely.
-template <class MaskT>
-__device__ __forceinline__ void mark(MaskT* mask, unsigned* list, unsigned* count, unsigned pix, MaskT bit, bool active)
+__device__ __forceinline__ void list_append(unsigned* list, unsigned* count, unsigned pix, bool first)
 {
-    const MaskT old = active ? atomicOr(&mask[pix], bit) : (MaskT)1;
-    if (!list) return;
-    const bool first = active && old == 0;
     const unsigned long long b = __ballot(first);
     if (!b) return;
     const int lane = threadIdx.x & 63, leader = __ffsll((long long)b) - 1;
@@ -274,16 +270,75 @@ __device__ __forceinline__ void mark(MaskT* mask, unsigned* list, unsigned* coun
     base = __shfl(base, leader);
     if (first) list[base + (unsigned)__popcll(b & ((1ull << lane) - 1ull))] = pix;
 }
+template <class MaskT>
+__device__ __forceinline__ void mark(MaskT* mask, unsigned* list, unsigned* count, unsigned pix, MaskT bit, bool active)
+{
+    const MaskT old = active ? atomicOr(&mask[pix], bit) : (MaskT)1;
+    if (!list) return;
+    list_append(list, count, pix, active && old == 0);
+}
+
+// Scheme 1's event-count threshold (THETA_EVENTS of event_mem_sim.py:33, :208-217: a pixel pulses in a slice when
+// bincount_2d(x[sl], y[sl]) >= theta).  theta == 1 is the mask bit above.  theta > 1: the same mask word holds one saturating
+// counter of `bits` = ceil(log2(theta + 1)) bits per slice instead of one bit, so a 32-bit word carries spw = 32 / bits
+// slices of a group and a 64-bit word 64 / bits; a compare-and-swap loop adds 1 and stops at theta, so a field never
+// carries into its neighbour however many events the cell receives (theta <= INT32_MAX: bits <= 31).  "old word == 0" is
+// still the pixel's first touch in the group -- a count of 1 makes the word non-zero -- so the list append is mark's; the
+// update kernels turn fields into driven bits (field == theta) as they load the word and clear it as they always did: no
+// plane, no launch and no clearing step is added, and a group simply holds fewer slices.
+struct Theta {
+    int theta, bits, spw;   // spw: slices per 32-bit word
+};
+struct NoTheta {};
+template <bool COUNT>
+using ThetaArg = std::conditional_t<COUNT, Theta, NoTheta>;   // theta == 1 passes nothing: the instantiations it always ran
+
+// One event of (pixel, the slice whose field starts at bit `shift`).
+template <class MaskT>
+__device__ __forceinline__ void mark_count(MaskT* mask, unsigned* list, unsigned* count, unsigned pix, int shift, const Theta& th,
+                                           bool active)
+{
+    MaskT old = 1;
+    if (active) {
+        const MaskT fm = ((MaskT)1 << th.bits) - 1, one = (MaskT)1 << shift;
+        // a stale value costs a retry and nothing else: fields only grow within a group, so "saturated" stays true, and
+        // the first touch is decided by the compare-and-swap that replaces 0
+        MaskT cur = __hip_atomic_load(&mask[pix], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (;;) {
+            old = cur;
+            if (((cur >> shift) & fm) >= (MaskT)th.theta) break;   // saturated (cur != 0: no first touch)
+            const MaskT seen = atomicCAS(&mask[pix], cur, cur + one);
+            if (seen == cur) break;
+            cur = seen;
+        }
+    }
+    if (!list) return;
+    list_append(list, count, pix, active && old == 0);
+}
+
+// Counter fields of a mask word -> one bit per slice whose count reached theta (bit s = the word's s-th field).
+template <class MaskT>
+__device__ __forceinline__ MaskT driven_bits(MaskT f, const Theta& th)
+{
+    const MaskT fm = ((MaskT)1 << th.bits) - 1;
+    MaskT m = 0;
+    for (int s = 0; f; s++, f >>= th.bits)
+        if ((f & fm) >= (MaskT)th.theta) m |= (MaskT)1 << s;
+    return m;
+}
 
 // One scatter per group of slices, both schemes: every event marks (pixel, its slice) in its array's mask.
 //   split == 0  every event -> array 0 (scheme 1 :208-217, scheme 2 magnitude; p is not read)
 //   split == 1  p == 1 -> array 0, p == 0 -> array 1 (:238, :250; other polarity values drive nothing)
 // Slices 32..63 of a group (scheme 1's every-pixel update only: n_sl <= 32 otherwise) go to the second mask word mask_hi.
+//   COUNT  scheme 1 with theta > 1 (no split): the event counts into its slice's field (mark_count); slices th.spw..2 * th.spw - 1
+//          of a group are the second word's
+template <bool COUNT>
 __global__ __launch_bounds__(256) void k_scatter(const short* __restrict__ x, const short* __restrict__ y,
                                                   const signed char* __restrict__ p, long long ev0, long long n_ev,
                                                   const long long* __restrict__ bounds, int n_sl, int W, int split,
                                                   unsigned* mask0, unsigned* list0, unsigned* count0, unsigned* mask1,
-                                                  unsigned* list1, unsigned* count1, unsigned* mask_hi)
+                                                  unsigned* list1, unsigned* count1, unsigned* mask_hi, ThetaArg<COUNT> th)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool live = i < n_ev;
@@ -294,9 +349,15 @@ __global__ __launch_bounds__(256) void k_scatter(const short* __restrict__ x, co
         arr = pv == 1 ? 0 : (pv == 0 ? 1 : -1);
     }
     const int s = slice_of(bounds, n_sl, e);
-    const unsigned pix = (unsigned)y[e] * (unsigned)W + (unsigned)x[e], bit = 1u << (s & 31);
-    mark(s < 32 ? mask0 : mask_hi, list0, count0, pix, bit, live && arr == 0);
-    if (split) mark(mask1, list1, count1, pix, bit, live && arr == 1);
+    if constexpr (COUNT) {
+        const unsigned pix = (unsigned)y[e] * (unsigned)W + (unsigned)x[e];
+        const bool hi = s >= th.spw;
+        mark_count(hi ? mask_hi : mask0, list0, count0, pix, (hi ? s - th.spw : s) * th.bits, th, live);
+    } else {
+        const unsigned pix = (unsigned)y[e] * (unsigned)W + (unsigned)x[e], bit = 1u << (s & 31);
+        mark(s < 32 ? mask0 : mask_hi, list0, count0, pix, bit, live && arr == 0);
+        if (split) mark(mask1, list1, count1, pix, bit, live && arr == 1);
+    }
 }
 
 // Scheme 2's refractory rule (event_mem_sim.py:237-269) looks like a chain over slices -- slice s+1 tests the next_ok that
@@ -341,11 +402,12 @@ __device__ __forceinline__ float replay_driven(float ww, MaskT m, const Drive& d
 //   MaskT  the mask word: 32 bits (groups of up to 32 slices), 64 bits (copy + patch: intervals of up to 64 slices)
 //   FRAME  the pixel's byte of the frame `so` is overwritten as well (copy + patch)
 //   FITTED the fitted device as compile-time constants (ModelArg)
-template <bool REFR, class MaskT, bool FRAME, bool FITTED>
+//   COUNT  scheme 1 with theta > 1: the word holds counter fields; driven_bits turns them into driven bits first
+template <bool REFR, class MaskT, bool FRAME, bool FITTED, bool COUNT>
 __global__ __launch_bounds__(256) void k_update_list(float* __restrict__ w, MaskT* __restrict__ mask,
                                                       long long* __restrict__ next_ok, const unsigned* __restrict__ list,
                                                       const unsigned* __restrict__ count, TabArg<REFR> tab, float v_act,
-                                                      unsigned* zero_next, SurfOut so, ModelArg<FITTED> model)
+                                                      unsigned* zero_next, SurfOut so, ModelArg<FITTED> model, ThetaArg<COUNT> th)
 {
     const DevF p = model_arg(model);
     __shared__ long long tf[REFR ? 32 : 1], tn[REFR ? 32 : 1];
@@ -360,6 +422,10 @@ __global__ __launch_bounds__(256) void k_update_list(float* __restrict__ w, Mask
         const unsigned pix = list[i];
         MaskT m = mask[pix];
         mask[pix] = 0;
+        if constexpr (COUNT) {
+            m = driven_bits(m, th);
+            if (!m) continue;   // no cell of the pixel reached theta: state and frame byte stay
+        }
         if constexpr (REFR) {
             long long ok = next_ok[pix];
             m = refractory_walk(m, ok, tf, tn);
@@ -383,11 +449,12 @@ __global__ __launch_bounds__(256) void k_update_list(float* __restrict__ w, Mask
 //   SIL_NOOP  silent_v lies in the dead zone [voff, von], where update_state leaves w bit-for-bit unchanged (dw = 0, w
 //             already inside [0,1]), so only the slices whose bit is set are replayed (in slice order) -- the pass is then
 //             bound by its one read and one write of the state instead of by 32 no-op evaluations per pixel.
-template <bool REFR, bool SIL_NOOP, bool FITTED>
+//   COUNT     scheme 1 with theta > 1: both words hold counter fields, th.spw slices each; driven_bits first
+template <bool REFR, bool SIL_NOOP, bool FITTED, bool COUNT>
 __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsigned* __restrict__ mask,
                                                      unsigned* __restrict__ mask_hi, long long* __restrict__ next_ok, size_t n4,
                                                      size_t n, int n_sl, TabArg<REFR> tab, float v_act, float v_sil, SurfOut so,
-                                                     ModelArg<FITTED> model)
+                                                     ModelArg<FITTED> model, ThetaArg<COUNT> th)
 {
     const DevF p = model_arg(model);
     __shared__ long long tf[REFR ? 32 : 1], tn[REFR ? 32 : 1];
@@ -398,7 +465,13 @@ __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsig
         so.out = nullptr;
     }
     const Drive da = drive_of(v_act, p), ds = drive_of(v_sil, p);
+    int lo_sl = 32;   // slices of the first mask word
+    if constexpr (COUNT) lo_sl = th.spw;
     auto one = [&](float ww, unsigned m, unsigned mh, size_t pix) {
+        if constexpr (COUNT) {
+            m = driven_bits(m, th);
+            mh = driven_bits(mh, th);
+        }
         if constexpr (REFR) {
             if (m) {
                 long long ok = next_ok[pix];
@@ -408,7 +481,7 @@ __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsig
         }
         if (SIL_NOOP) return replay_driven(replay_driven(ww, m, da), mh, da);
         for (int s = 0; s < n_sl; s++) {
-            const bool act = (REFR || s < 32) ? (m >> s) & 1u : (mh >> (s - 32)) & 1u;
+            const bool act = (REFR || s < lo_sl) ? (m >> s) & 1u : (mh >> (s - lo_sl)) & 1u;
             Drive d;
             d.dt = da.dt;
             d.ka = act ? da.ka : ds.ka;
@@ -564,11 +637,14 @@ __global__ __launch_bounds__(256) void k_surface_gray_f32(const float* __restric
 //                              slice masks (one 64-bit word: up to 64 slices) and the compact list of touched pixels
 //   B  k_update_list           the touched pixels replay their slices in order, store w and overwrite their byte of frames[k]
 // -- same states, same frames (tests/test_accum_gpu.py::test_run_frames_copy_patch_equals_dense_frames).
+//   COUNT  theta > 1: counter fields in the 64-bit word (intervals of up to 64 / th.bits slices)
+template <bool COUNT>
 __global__ __launch_bounds__(256) void k_frames_scatter_copy(const uint8_t* __restrict__ prev, uint8_t* __restrict__ cur, int W, int H,
                                                               long long row_stride, const short* __restrict__ x,
                                                               const short* __restrict__ y, long long ev0, long long n_ev,
                                                               const long long* __restrict__ bounds, int n_sl,
-                                                              unsigned long long* mask64, unsigned* list, unsigned* count)
+                                                              unsigned long long* mask64, unsigned* list, unsigned* count,
+                                                              ThetaArg<COUNT> th)
 {
     const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nthreads = (long long)gridDim.x * 256;
     // the events of the interval FIRST (their atomics' latency then overlaps the copy; whole waves take part: the list append
@@ -577,7 +653,10 @@ __global__ __launch_bounds__(256) void k_frames_scatter_copy(const uint8_t* __re
     for (long long i = tid; i < n_ev_pad; i += nthreads) {
         const bool live = i < n_ev;
         const long long e = ev0 + (live ? i : 0);
-        mark(mask64, list, count, (unsigned)y[e] * (unsigned)W + (unsigned)x[e], 1ull << slice_of(bounds, n_sl, e), live);
+        if constexpr (COUNT)
+            mark_count(mask64, list, count, (unsigned)y[e] * (unsigned)W + (unsigned)x[e], slice_of(bounds, n_sl, e) * th.bits, th, live);
+        else
+            mark(mask64, list, count, (unsigned)y[e] * (unsigned)W + (unsigned)x[e], 1ull << slice_of(bounds, n_sl, e), live);
     }
     // ... then this thread's share of the copy
     if (prev) {
@@ -809,6 +888,20 @@ void with_frame_model(const Model& m, Fn&& f)
     if (m.fitted) f(std::true_type{}, FittedD{m.d.lambda});
     else f(std::false_type{}, m.d);
 }
+// The counter layout of a threshold: bits = ceil(log2(theta + 1)) per slice (theta >= 1, at most 31 bits).
+inline Theta theta_of(int theta)
+{
+    int bits = 1;
+    while ((1ll << bits) < (long long)theta + 1) bits++;
+    return Theta{theta, bits, 32 / bits};
+}
+// f(std::false_type, NoTheta) for theta == 1, f(std::true_type, Theta) for a count threshold
+template <class Fn>
+void with_theta(int theta, Fn&& f)
+{
+    if (theta == 1) f(std::false_type{}, NoTheta{});
+    else f(std::true_type{}, theta_of(theta));
+}
 int model_of(nsof_ctx* ctx, const nsof_accum_params* in, Model* m)
 {
     const nsof_accum_params p = in ? *in : default_params();
@@ -862,6 +955,7 @@ struct nsof_accum {
     int H = 0, W = 0, scheme = 1, split = 0;
     float active_v = 0, silent_v = 0;
     int force_dense = 0;   // nsof_accum_set_dense: 0 automatic, 1 every-pixel pass, -1 event-pixel update (where exact)
+    int theta = 1;         // nsof_accum_set_event_threshold: scheme 1's THETA_EVENTS
     size_t npx = 0;
     nsof_dev_buf<float> w[2];
     nsof_dev_buf<long long> next_ok[2];
@@ -973,6 +1067,23 @@ extern "C" int nsof_accum_set_dense(nsof_accum* a, int force_dense)
 {
     if (!a) return NSOF_EINVAL;
     a->force_dense = force_dense > 0 ? 1 : (force_dense < 0 ? -1 : 0);
+    return NSOF_OK;
+}
+
+extern "C" int nsof_accum_set_event_threshold(nsof_accum* a, int theta)
+{
+    if (!a) return NSOF_EINVAL;
+    if (theta < 1) return nsof_set_error(a->ctx, NSOF_EINVAL, "event threshold %d: at least 1 event", theta);
+    if (a->scheme == 2 && theta != 1)
+        return nsof_set_error(a->ctx, NSOF_EINVAL, "event threshold %d: scheme 2 has no count threshold (only 1 is accepted)", theta);
+    a->theta = theta;
+    return NSOF_OK;
+}
+
+extern "C" int nsof_accum_get_event_threshold(const nsof_accum* a, int* theta)
+{
+    if (!a || !theta) return NSOF_EINVAL;
+    *theta = a->theta;
     return NSOF_OK;
 }
 
@@ -1124,7 +1235,9 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
         if ((rc = a->mask_hi.reserve(ctx, a->npx * sizeof(unsigned) + 16))) return rc;
         NSOF_HIP(ctx, hipMemsetAsync(a->mask_hi.p, 0, a->npx * sizeof(unsigned) + 16, ctx->stream));
     }
-    const int64_t max_group = wide ? 2 * MAX_GROUP : MAX_GROUP;
+    // theta > 1: a mask word carries 32 / bits slices (Theta), so the groups are that much shorter
+    const int64_t word_slices = a->theta == 1 ? MAX_GROUP : theta_of(a->theta).spw;
+    const int64_t max_group = wide ? 2 * word_slices : word_slices;
     ListCounts cnt{a->count.p};
     if (sparse && s0 < s_end) NSOF_HIP(ctx, cnt.zero_all(ctx->stream));
     while (s0 < s_end) {
@@ -1141,23 +1254,28 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
             nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
             unsigned* const l0 = sparse ? a->list[0].p : nullptr;   // the every-pixel update reads no list
             unsigned* const l1 = sparse ? a->list[a->split].p : nullptr;
-            hipLaunchKernelGGL(k_scatter, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream, a->dx.p, a->dy.p,
-                               a->dp.p, ge0, gn, a->dbounds.p + s0, (int)g, a->W, a->split, a->mask[0].p, l0, cnt.cur(),
-                               a->mask[a->split].p, l1, cnt.cur() + 1, a->mask_hi.p);
+            with_theta(a->theta, [&](auto C, auto th) {
+                hipLaunchKernelGGL(k_scatter<decltype(C)::value>, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream, a->dx.p,
+                                   a->dy.p, a->dp.p, ge0, gn, a->dbounds.p + s0, (int)g, a->W, a->split, a->mask[0].p, l0, cnt.cur(),
+                                   a->mask[a->split].p, l1, cnt.cur() + 1, a->mask_hi.p, th);
+            });
             NSOF_HIP(ctx, hipGetLastError());
         }
         {
             nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
             // array i of the group; R: std::true_type for scheme 2, whose kernels take the group's refractory table
-            auto update = [&](auto R, const auto& tab, int i) {
-                constexpr bool REFR = decltype(R)::value;
+            // C: std::true_type for a count threshold (scheme 1 only: the setter refuses it for scheme 2)
+            auto update_c = [&](auto R, const auto& tab, int i, auto C, auto th) {
+                constexpr bool REFR = decltype(R)::value, COUNT = decltype(C)::value;
+                if constexpr (REFR && COUNT) return;
+                else {
                 SurfOut so{nullptr, 0, a->W, 0};
                 if (sparse) {
                     if (gn > 0)
                         with_model(a->model, [&](auto D, auto model) {
-                            hipLaunchKernelGGL((k_update_list<REFR, unsigned, false, decltype(D)::value>), dim3(grid_for((size_t)gn, 1024)),
-                                               dim3(256), 0, ctx->stream, a->w[i].p, a->mask[i].p, a->next_ok[i].p, a->list[i].p,
-                                               cnt.cur() + i, tab, v_act, cnt.next() + i, so, model);
+                            hipLaunchKernelGGL((k_update_list<REFR, unsigned, false, decltype(D)::value, COUNT>),
+                                               dim3(grid_for((size_t)gn, 1024)), dim3(256), 0, ctx->stream, a->w[i].p, a->mask[i].p,
+                                               a->next_ok[i].p, a->list[i].p, cnt.cur() + i, tab, v_act, cnt.next() + i, so, model, th);
                         });
                     return;
                 }
@@ -1168,11 +1286,15 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
                 const size_t n4 = (a->npx + 3) / 4;
                 with_model(a->model, [&](auto D, auto model) {
                     constexpr bool FITTED = decltype(D)::value;
-                    auto* const kernel = dead_zone ? k_update_all<REFR, true, FITTED> : k_update_all<REFR, false, FITTED>;
+                    auto* const kernel = dead_zone ? k_update_all<REFR, true, FITTED, COUNT> : k_update_all<REFR, false, FITTED, COUNT>;
                     hipLaunchKernelGGL(kernel, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream, a->w[i].p, a->mask[i].p,
-                                       g > MAX_GROUP ? a->mask_hi.p : nullptr, a->next_ok[i].p, n4, a->npx, (int)g, tab, v_act,
-                                       a->silent_v, so, model);
+                                       g > word_slices ? a->mask_hi.p : nullptr, a->next_ok[i].p, n4, a->npx, (int)g, tab, v_act,
+                                       a->silent_v, so, model, th);
                 });
+                }
+            };
+            auto update = [&](auto R, const auto& tab, int i) {
+                with_theta(a->theta, [&](auto C, auto th) { update_c(R, tab, i, C, th); });
             };
             if (a->scheme == 2) {
                 RefrTab tab;
@@ -1262,6 +1384,9 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
     const bool dead_zone = dead_zone_of(a);
     // frame k of the call, as the kernels take it
     auto frame = [&](int64_t k) { return SurfOut{d_frames + k * frame_stride, (long long)row_stride, a->W, mode}; };
+    // copy + patch scatters into ONE 64-bit word per pixel: 64 slices, or 64 / bits with a count threshold -- an interval
+    // then takes ceil(every / word64_slices) rounds of (scatter, list update), the first of which copies the frame
+    const int64_t word64_slices = a->theta == 1 ? 2 * MAX_GROUP : 64 / theta_of(a->theta).bits;
     if (!(a->scheme == 1 && dead_zone && a->force_dense <= 0 && every <= 2 * MAX_GROUP)) {
         for (int64_t k = 0; k < n_frames; k++) {
             const SurfOut so = frame(k);
@@ -1277,7 +1402,8 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
     const bool tile_ok = (a->W & 15) == 0 && (row_stride & 15) == 0 && (frame_stride & 15) == 0 &&
                          (reinterpret_cast<uintptr_t>(d_frames) & 15) == 0 && n_frames >= 2 && n_ev < (1ll << 31) &&
                          (a->npx + TILE_PX - 1) / TILE_PX <= 15000 &&   // the bucketing workgroup's histogram: 4 B per tile of LDS
-                         (size_t)n_frames * ((a->npx + TILE_PX - 1) / TILE_PX) < ((size_t)1 << 30) && a->frames_path != 1;
+                         (size_t)n_frames * ((a->npx + TILE_PX - 1) / TILE_PX) < ((size_t)1 << 30) && a->frames_path != 1 &&
+                         a->theta == 1;   // the walk's LDS masks hold bits, not counts
     if (tile_ok) {
         const unsigned ntiles = (unsigned)((a->npx + TILE_PX - 1) / TILE_PX);
         const size_t nb = (size_t)n_frames * ntiles;
@@ -1305,28 +1431,38 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
     constexpr size_t ACC_COPY_BLOCKS = 4096;
     const unsigned copy_blocks = (unsigned)std::min<size_t>(ACC_COPY_BLOCKS, (a->npx / 16 + 255) / 256 + 1);
     for (int64_t k = 0; k < n_frames; k++) {
-        const int64_t s0 = first_slice + k * every;
-        const long long ge0 = rel[s0], gn = rel[s0 + every] - ge0;
         const SurfOut cur = frame(k);
-        const uint8_t* const prev = k > 0 ? frame(k - 1).out : nullptr;
         nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
-        if (prev || gn > 0) {
-            const unsigned blocks = prev ? copy_blocks : (unsigned)((gn + 255) / 256);
-            hipLaunchKernelGGL(k_frames_scatter_copy, dim3(blocks), dim3(256), 0, ctx->stream, prev, cur.out, a->W, a->H,
-                               (long long)row_stride, a->dx.p, a->dy.p, ge0, gn, a->dbounds.p + s0, (int)every, a->mask64.p, a->list[0].p,
-                               cnt.cur());
+        // theta == 1: one round, the whole interval.  A later round without events is skipped whole: the counter it would
+        // append to is already zero and stays the current one.
+        for (int64_t r0 = 0; r0 < every; r0 += word64_slices) {
+            const int64_t s0 = first_slice + k * every + r0, rn = std::min<int64_t>(word64_slices, every - r0);
+            const long long ge0 = rel[s0], gn = rel[s0 + rn] - ge0;
+            if (r0 > 0 && gn == 0) continue;
+            const uint8_t* const prev = k > 0 && r0 == 0 ? frame(k - 1).out : nullptr;
+            if (prev || gn > 0) {
+                const unsigned blocks = prev ? copy_blocks : (unsigned)((gn + 255) / 256);
+                with_theta(a->theta, [&](auto C, auto th) {
+                    hipLaunchKernelGGL(k_frames_scatter_copy<decltype(C)::value>, dim3(blocks), dim3(256), 0, ctx->stream, prev, cur.out,
+                                       a->W, a->H, (long long)row_stride, a->dx.p, a->dy.p, ge0, gn, a->dbounds.p + s0, (int)rn,
+                                       a->mask64.p, a->list[0].p, cnt.cur(), th);
+                });
+            }
+            // (launched for an empty interval as well: it zeroes the next round's counter)
+            with_theta(a->theta, [&](auto C, auto th) {
+                with_model(a->model, [&](auto D, auto model) {
+                    hipLaunchKernelGGL((k_update_list<false, unsigned long long, true, decltype(D)::value, decltype(C)::value>),
+                                       dim3(grid_for((size_t)std::max<long long>(gn, 1), 1024)), dim3(256), 0, ctx->stream, a->w[0].p,
+                                       a->mask64.p, (long long*)nullptr, a->list[0].p, cnt.cur(), NoTab{}, a->active_v, cnt.next(), cur,
+                                       model, th);
+                });
+            });
+            NSOF_HIP(ctx, hipGetLastError());
+            cnt.flip();
         }
-        // (launched for an empty interval as well: it zeroes the next interval's counter)
-        with_model(a->model, [&](auto D, auto model) {
-            hipLaunchKernelGGL((k_update_list<false, unsigned long long, true, decltype(D)::value>),
-                               dim3(grid_for((size_t)std::max<long long>(gn, 1), 1024)), dim3(256), 0, ctx->stream, a->w[0].p,
-                               a->mask64.p, (long long*)nullptr, a->list[0].p, cnt.cur(), NoTab{}, a->active_v, cnt.next(), cur, model);
-        });
-        NSOF_HIP(ctx, hipGetLastError());
         // the call's first frame has no predecessor to copy: one pass over the array
         if (k == 0 && (rc = accum_surface(a, which, cur))) return rc;
         a->slice_counter += every;
-        cnt.flip();
     }
     return NSOF_OK;
 }

@@ -103,6 +103,8 @@ SIGNATURES = {
     "nsof_accum_frames_f64_p_dev": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _d, _ap, _vp, _vp, _vp]),
     "nsof_accum_destroy": (None, [_vp]),
     "nsof_accum_set_dense": (_i, [_vp, _i]),
+    "nsof_accum_set_event_threshold": (_i, [_vp, _i]),
+    "nsof_accum_get_event_threshold": (_i, [_vp, _vp]),
     "nsof_accum_reset": (_i, [_vp]),
     "nsof_accum_step_events": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
     "nsof_accum_set_events": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64]),

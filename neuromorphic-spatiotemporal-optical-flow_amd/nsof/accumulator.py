@@ -59,6 +59,21 @@ def accum_params(params=None, dt=None, refractory_us=None):
     return out
 
 
+def event_threshold(theta_events=None, version=1):
+    """Scheme 1's event-count threshold as the library takes it: ``None`` is the module's ``THETA_EVENTS``; anything but a
+    whole number >= 1 (that fits an int32), or a value other than 1 with ``version=2`` -- that scheme has no count
+    threshold -- raises ``NsofValueError``."""
+    th = THETA_EVENTS if theta_events is None else theta_events
+    whole = isinstance(th, (int, np.integer)) and not isinstance(th, (bool, np.bool_))
+    if isinstance(th, (float, np.floating)) and float(th).is_integer():
+        whole, th = True, int(th)
+    if not whole or not 1 <= int(th) <= 2**31 - 1:
+        raise NsofValueError(f"theta_events = {theta_events!r} is not a whole number of events >= 1")
+    if version == 2 and int(th) != 1:
+        raise NsofValueError(f"theta_events = {theta_events!r}: scheme 2 has no event-count threshold")
+    return int(th)
+
+
 def _params_dict(ap):
     """(params dict with the reference's keys, dt, refractory_us) of an ``AccumParams`` -- what the metadata file records."""
     d = {k: getattr(ap, k) for k in _PARAM_KEYS}
@@ -181,11 +196,14 @@ class Accumulator:
 
     ``params`` (a mapping with the keys of ``PARAMS``), ``dt`` and ``refractory_us`` give the device the array is made of
     (``None``: the module's ``PARAMS`` / ``DT`` / ``REFRACTORY_US``); they are fixed for the accumulator's life and read
-    back as ``self.params`` / ``self.dt`` / ``self.refractory_us``."""
+    back as ``self.params`` / ``self.dt`` / ``self.refractory_us``.  ``theta_events`` (``None``: ``THETA_EVENTS``) is scheme
+    1's event-count threshold: a pixel pulses in a slice that holds at least that many of its events (read back as
+    ``self.theta_events``)."""
 
     def __init__(self, height, width, version=1, polarity="split", active_v=-8.0, silent_v=0.0, *, ctx=None,
-                 dense=None, frames_path=None, params=None, dt=None, refractory_us=None):
+                 dense=None, frames_path=None, params=None, dt=None, refractory_us=None, theta_events=None):
         ap = accum_params(params, dt, refractory_us)
+        theta = event_threshold(theta_events, version)
         if version not in (1, 2):
             raise NsofValueError("version must be 1 or 2")
         if polarity not in ("split", "magnitude"):
@@ -201,11 +219,20 @@ class Accumulator:
         used = _lib.AccumParams()
         self.ctx.check(self.ctx._lib.nsof_accum_get_params(self._p, C.byref(used)), "accum_get_params")
         self.params, self.dt, self.refractory_us = _params_dict(used)
+        if theta != 1:
+            self.ctx.check(self.ctx._lib.nsof_accum_set_event_threshold(self._p, theta), "accum_set_event_threshold")
         if dense is not None:   # None: automatic; True: the every-pixel pass; False: the event-pixel update where it is exact
             self.ctx.check(self.ctx._lib.nsof_accum_set_dense(self._p, 1 if dense else -1), "accum_set_dense")
         if frames_path is not None:   # run_frames: "tiles" (default where it applies) or "copy_patch"
             self.ctx.check(self.ctx._lib.nsof_accum_set_frames_path(self._p, {"tiles": 0, "copy_patch": 1}[frames_path]),
                            "accum_set_frames_path")
+
+    @property
+    def theta_events(self):
+        """Scheme 1's event-count threshold this accumulator runs with (``nsof_accum_get_event_threshold``)."""
+        th = C.c_int()
+        self.ctx.check(self.ctx._lib.nsof_accum_get_event_threshold(self._p, C.byref(th)), "accum_get_event_threshold")
+        return th.value
 
     def reset(self):
         self.ctx.check(self.ctx._lib.nsof_accum_reset(self._p), "accum_reset")
@@ -365,7 +392,8 @@ class Accumulator:
 
 
 def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, save_video=False, polarity="split",
-             *, sensor_size=None, out_prefix=None, ctx=None, dense=None, params=None, dt=None, refractory_us=None):
+             *, sensor_size=None, out_prefix=None, ctx=None, dense=None, params=None, dt=None, refractory_us=None,
+             theta_events=None):
     """``simulate`` of event_mem_sim.py:164-286.
 
     ``events``: an HDF5 path with a ``/CD/events`` group (as the reference) or a tuple ``(x, y, p, t)`` of arrays.
@@ -374,14 +402,16 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
     ``.V{version}.npz`` / ``.V2_b.npz`` / ``.json.gz`` files as the reference (:289-322) are written.
     ``save_video`` is accepted for signature compatibility; MP4 previews are not produced.
     ``params`` / ``dt`` / ``refractory_us``: the device model, as for ``Accumulator`` (the reference reads its module
-    globals ``PARAMS`` / ``REFRACTORY_US`` and ``update_state``'s default ``dt``).  The metadata file records the values
-    that were used.
+    globals ``PARAMS`` / ``REFRACTORY_US`` and ``update_state``'s default ``dt``).  ``theta_events``: scheme 1's event-count
+    threshold (the reference's module global ``THETA_EVENTS``; ``None`` = this module's).  The metadata file records the
+    values that were used.
     """
     if version not in (1, 2):
         raise NsofValueError("version must be 1 or 2")
     if polarity not in ("split", "magnitude"):
         raise NsofValueError("polarity must be 'split' or 'magnitude'")
     accum_params(params, dt, refractory_us)   # a missing key is reported before the events are read
+    theta = event_threshold(theta_events, version)
     h5_path = None
     if isinstance(events, (str, Path)):
         h5_path = Path(events)
@@ -399,7 +429,7 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
     nslices = max(len(idx) - 1, 0)
     every = max(1, nslices // 100)
     acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, dense=dense, params=params, dt=dt,
-                      refractory_us=refractory_us)
+                      refractory_us=refractory_us, **({} if theta_events is None else dict(theta_events=theta)))
     # what the metadata file records: the model this run uses, written with the caller's own numbers (the accumulator holds
     # the same values as doubles; the defaults stay the integers the reference writes), plus won / woff, which nothing reads
     src = PARAMS if params is None else params
@@ -415,7 +445,7 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
         acc.close()
     prefix = Path(out_prefix) if out_prefix is not None else h5_path
     if prefix is not None:
-        _save_outputs(prefix, out, version, slice_us, polarity, h5_path, *used)
+        _save_outputs(prefix, out, version, slice_us, polarity, h5_path, *used, theta_events=theta)
     return out
 
 
@@ -465,13 +495,15 @@ def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.
     return w, res, cur
 
 
-def _save_outputs(prefix, out, version, slice_us, polarity, h5_path, params=None, dt=None, refractory_us=None):
+def _save_outputs(prefix, out, version, slice_us, polarity, h5_path, params=None, dt=None, refractory_us=None,
+                  theta_events=None):
     """File set of event_mem_sim.py:289-322 (npz keys ``w_final`` / ``resistances``; json.gz metadata).  The metadata holds
-    the parameters, dt and refractory time the run USED (the reference writes its module globals, which a dt overridden
+    the parameters, dt, refractory time and event threshold the run USED (the reference writes its module globals, which a dt overridden
     through ``update_state``'s default does not reach)."""
     params = dict(PARAMS) if params is None else params
     dt = DT if dt is None else dt
     refractory_us = REFRACTORY_US if refractory_us is None else refractory_us
+    theta_events = THETA_EVENTS if theta_events is None else theta_events
     np.savez_compressed(prefix.with_suffix(f".V{version}.npz"), w_final=out["w_final"],
                         resistances=out["resistances"].astype(np.float32))
     if version == 2:
@@ -482,7 +514,7 @@ def _save_outputs(prefix, out, version, slice_us, polarity, h5_path, params=None
             np.savez_compressed(prefix.with_suffix(".V2_b.npz"), w_final=np.array([]), resistances=np.array([]))
     meta = dict(version=version, slice_us=slice_us, fps=1_000_000 / slice_us, params=params, dt=dt,
                 scheme="boxcar" if version == 1 else "dc_bias_overlay", polarity=polarity if version == 2 else None,
-                theta_events=THETA_EVENTS if version == 1 else None,
+                theta_events=theta_events if version == 1 else None,
                 refractory_us=refractory_us if version == 2 else None, event_file=str(h5_path or prefix))
     with gzip.open(prefix.with_suffix(f".V{version}.json.gz"), "wt") as fp:
         json.dump(meta, fp, indent=2)

@@ -288,9 +288,10 @@ def simulate_banded(x, y, p, t, sensor_hw, slice_us, simulate_band, dst=0, devic
 
 
 def accumulator_band(version=1, polarity="split", active_v=-8.0, silent_v=0.0, *, ctx=None, params=None, dt=None,
-                     refractory_us=None):
+                     refractory_us=None, theta_events=None):
     """The ``simulate_band`` callback of ``simulate_banded`` on a GPU: one ``Accumulator`` per band, ``set_events`` ->
-    ``set_slice_times`` -> ``run`` -> ``w``.  ``params`` / ``dt`` / ``refractory_us`` go to the accumulator unchanged."""
+    ``set_slice_times`` -> ``run`` -> ``w``.  ``params`` / ``dt`` / ``refractory_us`` / ``theta_events`` go to the accumulator unchanged
+    (a cell of the count threshold is a pixel and a slice, so the bands need nothing from each other)."""
     def simulate_band(xb, yb, pb, tb, idx, hw, slice_times):
         import numpy as np
 
@@ -301,7 +302,7 @@ def accumulator_band(version=1, polarity="split", active_v=-8.0, silent_v=0.0, *
             empty = np.zeros((0, w), np.float32)
             return (empty, empty.copy()) if split else empty
         acc = Accumulator(rows, w, version, polarity, active_v, silent_v, ctx=ctx, params=params, dt=dt,
-                          refractory_us=refractory_us)
+                          refractory_us=refractory_us, theta_events=theta_events)
         try:
             acc.set_events(xb, yb, pb, tb, idx)
             acc.set_slice_times(*slice_times)

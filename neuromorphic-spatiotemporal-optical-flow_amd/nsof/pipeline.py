@@ -23,13 +23,15 @@ def surface_to_block_current(resistance, memsize, v_ds=1.0):
 
 
 def events_to_rois(x, y, p, t, sensor_hw, cfg, version=1, polarity="split", slice_us=1000, active_v=-6.0,
-                   silent_v=0.0, snapshot_every=33, ctx=None, max_rects=32, params=None, dt=None, refractory_us=None):
+                   silent_v=0.0, snapshot_every=33, ctx=None, max_rects=32, params=None, dt=None, refractory_us=None,
+                   theta_events=None):
     """Run the accumulator over the stream and return, for every snapshot, the gating map and its ROI rectangles
     (x0, y0, x1, y1) in sensor pixels.  Everything between the event upload and the result stays in HBM: the block maxima of
     the device current of every snapshot (``Accumulator.block_current_dev``), then ONE gating call over all snapshots
     (``gating.roi_from_surface_dev``: gray map, threshold, connected components, rectangles -- for every map size); the
     rectangle table and the gray maps come back in one copy at the end.  With FLAG 2 a snapshot's list holds the union
-    box alone (or nothing).  ``params`` / ``dt`` / ``refractory_us``: the accumulator's device model (``Accumulator``)."""
+    box alone (or nothing).  ``params`` / ``dt`` / ``refractory_us``: the accumulator's device model, ``theta_events``: scheme 1's event-count
+    threshold (``Accumulator``)."""
     import torch
 
     from .context import default_context
@@ -37,7 +39,8 @@ def events_to_rois(x, y, p, t, sensor_hw, cfg, version=1, polarity="split", slic
     H, W = sensor_hw  # noqa: N806
     idx = slice_index_array(t, slice_us)
     rows, cols = H // cfg.MEMSIZE, W // cfg.MEMSIZE
-    acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, params=params, dt=dt, refractory_us=refractory_us)
+    acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, params=params, dt=dt, refractory_us=refractory_us,
+                      theta_events=theta_events)
     try:
         acc.step(x, y, p, t, idx, snap_every=snapshot_every)
         n = acc.snapshot_count()
@@ -61,12 +64,13 @@ def events_to_rois(x, y, p, t, sensor_hw, cfg, version=1, polarity="split", slic
 
 
 def events_to_rois_host(x, y, p, t, sensor_hw, cfg, version=1, polarity="split", slice_us=1000, active_v=-6.0,
-                        silent_v=0.0, snapshot_every=33, ctx=None, params=None, dt=None, refractory_us=None):
+                        silent_v=0.0, snapshot_every=33, ctx=None, params=None, dt=None, refractory_us=None, theta_events=None):
     """The same through the host-side mirror of the reference's gating (``gating.connectedComponentsWithStats`` on the
     downloaded block currents): kept as the independent path the device kernel is tested against."""
     H, W = sensor_hw  # noqa: N806
     idx = slice_index_array(t, slice_us)
-    acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, params=params, dt=dt, refractory_us=refractory_us)
+    acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, params=params, dt=dt, refractory_us=refractory_us,
+                      theta_events=theta_events)
     try:
         acc.step(x, y, p, t, idx, snap_every=snapshot_every)
         blocks = [acc.block_current(cfg.MEMSIZE, snapshot=k) for k in range(acc.snapshot_count())]
@@ -85,7 +89,7 @@ def events_to_rois_host(x, y, p, t, sensor_hw, cfg, version=1, polarity="split",
 
 def events_to_roi_flows(x, y, p, t, sensor_hw, cfg, slice_us=1000, active_v=-6.0, silent_v=0.0, snapshot_every=33,
                         surface_mode="state", ctx=None, max_rects=32, timings=None, surface_dtype="uint8", params=None, dt=None,
-                        refractory_us=None):
+                        refractory_us=None, theta_events=None):
     """BASELINE config 3 as one pipeline on the device: event stream -> leaky-integrate surface (scheme 1) -> every
     ``snapshot_every`` slices an 8-bit surface frame AND the gating map of the same state -> ROI rectangles on the device
     (``gating.roi_from_surface_dev``) -> Farneback flow of every ROI crop between consecutive surface frames, all crops of
@@ -101,7 +105,8 @@ def events_to_roi_flows(x, y, p, t, sensor_hw, cfg, slice_us=1000, active_v=-6.0
     ``surface_dtype="float32"``: the surface frames are the unquantised float surface instead (``Accumulator.run`` of the
     interval, then ``Accumulator.surface_f32``, same ``surface_mode``), ``frames`` is float32 and the crops run on
     ``farneback_roi_sequence_f32_dev``.  The gating maps and so the rectangles do not depend on it.
-    ``params`` / ``dt`` / ``refractory_us``: the accumulator's device model (``Accumulator``)."""
+    ``params`` / ``dt`` / ``refractory_us``: the accumulator's device model, ``theta_events``: its event-count threshold
+    (``Accumulator``)."""
     import time
 
     import torch
@@ -123,7 +128,8 @@ def events_to_roi_flows(x, y, p, t, sensor_hw, cfg, slice_us=1000, active_v=-6.0
     cur = torch.empty((n_frames, rows, cols), dtype=torch.float64, device=dev)
     flows = torch.empty((n_frames - 1, H, W, 2), dtype=torch.float32, device=dev)   # zero-filled by the flow call
     torch.cuda.synchronize(dev)
-    acc = Accumulator(H, W, 1, "split", active_v, silent_v, ctx=ctx, params=params, dt=dt, refractory_us=refractory_us)
+    acc = Accumulator(H, W, 1, "split", active_v, silent_v, ctx=ctx, params=params, dt=dt, refractory_us=refractory_us,
+                      theta_events=theta_events)
     try:
         acc.set_events(x, y, p, t, idx)
         t0 = time.perf_counter()
@@ -157,7 +163,7 @@ def events_to_roi_flows(x, y, p, t, sensor_hw, cfg, slice_us=1000, active_v=-6.0
 
 def events_to_flow_sequence(x, y, p, t, sensor_hw, params=None, slice_us=1000, active_v=-6.0, silent_v=0.0,
                             snapshot_every=33, dense=None, ctx=None, timings=None, accum_params=None, dt=None,
-                            refractory_us=None):
+                            refractory_us=None, theta_events=None):
     """BASELINE config 5 as one device-resident pipeline: event stream -> dense scheme-1 accumulator update of every
     slice -> every ``snapshot_every`` slices the surface as an 8-bit frame (``Accumulator.surface_u8``, mode "state":
     uint8(255 * w) -- the reference's current -> gray map saturates for the simulator's w >= 0.5 and the reference has
@@ -168,7 +174,8 @@ def events_to_flow_sequence(x, y, p, t, sensor_hw, params=None, slice_us=1000, a
     previous one, ``nsof_accum_run_frames``), True = the every-pixel pass per interval (the roofline run), False = the
     event-pixel update.  Same frames either way.  ``timings`` (a dict) receives the wall time of the two stages.
     ``accum_params`` / ``dt`` / ``refractory_us``: the accumulator's device model, ``Accumulator``'s ``params`` / ``dt`` /
-    ``refractory_us`` (``params`` is taken here: the Farneback parameters)."""
+    ``refractory_us`` (``params`` is taken here: the Farneback parameters); ``theta_events``: its event-count threshold
+    (above 1 the frames come from copy + patch, never the tile walk: same bytes)."""
     import time
 
     import torch
@@ -188,7 +195,7 @@ def events_to_flow_sequence(x, y, p, t, sensor_hw, params=None, slice_us=1000, a
     flows = torch.empty((n_frames - 1, H, W, 2), dtype=torch.float32, device=dev)
     torch.cuda.synchronize(dev)
     acc = Accumulator(H, W, 1, "split", active_v, silent_v, ctx=ctx, dense=dense, params=accum_params, dt=dt,
-                      refractory_us=refractory_us)
+                      refractory_us=refractory_us, theta_events=theta_events)
     try:
         acc.set_events(x, y, p, t, idx)
         t0 = time.perf_counter()
@@ -207,12 +214,12 @@ def events_to_flow_sequence(x, y, p, t, sensor_hw, params=None, slice_us=1000, a
 
 def events_to_flow_sequence_sharded(x, y, p, t, sensor_hw, params=None, slice_us=1000, active_v=-6.0, silent_v=0.0,
                                     snapshot_every=33, dense=None, ctx=None, stats=None, accum_params=None, dt=None,
-                                    refractory_us=None):
+                                    refractory_us=None, theta_events=None):
     """``events_to_flow_sequence`` over the ranks of the current process group (one GPU each): accumulator row bands,
     all-gather of the 8-bit surface frames, contiguous shards of the frame pairs (``nsof.dist.events_to_flow_sharded``
     with the GPU accumulator and ``farneback_sequence`` as the two stages).  Returns ``((lo, hi), frames, flows_local)``
     -- torch CUDA tensors; ``flows_local`` are pairs ``lo .. hi-1`` of the sequence (None for a rank without pairs).
-    ``accum_params`` / ``dt`` / ``refractory_us`` as for ``events_to_flow_sequence``."""
+    ``accum_params`` / ``dt`` / ``refractory_us`` / ``theta_events`` as for ``events_to_flow_sequence``."""
     import torch
 
     from . import dist as nd
@@ -229,7 +236,7 @@ def events_to_flow_sequence_sharded(x, y, p, t, sensor_hw, params=None, slice_us
         if rows == 0:
             return out
         acc = Accumulator(rows, w, 1, "split", active_v, silent_v, ctx=ctx, dense=dense, params=accum_params, dt=dt,
-                          refractory_us=refractory_us)
+                          refractory_us=refractory_us, theta_events=theta_events)
         try:
             acc.set_events(xb, yb, pb, tb, idx)
             acc.run_frames(0, n_frames, every, out)
