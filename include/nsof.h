@@ -415,7 +415,8 @@ int nsof_accum_create(nsof_ctx* ctx, int height, int width, int scheme, int pola
  * Refused with NSOF_EINVAL before anything is launched: a non-finite field (or one that is not finite as float32),
  * !(voff < 0 < von), son or soff outside [0, 1], Ron <= 0 or Roff <= 0, wini outside [0, 1], dt <= 0, refractory_us < 0.
  * Not a field of this struct: scheme 1's event threshold THETA_EVENTS is a setting of the accumulator
- * (nsof_accum_set_event_threshold).  Per-pixel parameter maps and the linear resistance map are not supported. */
+ * (nsof_accum_set_event_threshold).  One device per array unless nsof_accum_set_param_maps hands in per-pixel planes.
+ * Per-pixel thresholds and the linear resistance map are not supported. */
 typedef struct nsof_accum_params {      /* keys of PARAMS (event_mem_sim.py:20-27); won / woff are read by nothing and not carried */
     double alphaoff, alphaon, voff, von, koff, kon, son, soff, bon, boff, Ron, Roff, wini;
     double dt;                          /* DT, seconds */
@@ -427,6 +428,39 @@ void nsof_accum_default_params(nsof_accum_params* out);
 int nsof_accum_create_p(nsof_ctx* ctx, int height, int width, int scheme, int polarity_split, float active_v, float silent_v,
                         const nsof_accum_params* params, nsof_accum** out);
 int nsof_accum_get_params(const nsof_accum* acc, nsof_accum_params* out);
+/* Per-pixel parameter maps: an array whose devices differ (fabrication spread in Ron / Roff, thresholds, rate constants,
+ * initial state).  keys[j] names a field of nsof_accum_params, maps[j] is its HOST float32 plane [H][W] (not retained).  A
+ * mapped key takes the pixel's float32 value, every other key keeps the accumulator's scalar (nsof_accum_get_params keeps
+ * returning the scalars); dt, refractory_us, theta and the two voltages stay scalars.  Per pixel the arithmetic is that of
+ * the uniform model with the pixel's own float32 fields, neg_lam = (float)(-ln(Roff / Ron)) with the logarithm in double of
+ * the values as held (a plane's float32 widened, a scalar's double): constant planes equal to the scalars give the uniform
+ * accumulator's bits.  Every update form, surface (u8, f32), snapshot, resistance read-out and block current follows.
+ * Accepted only on an accumulator that is fresh or has just been reset (slice counter 0, no snapshots); the call ends with a
+ * reset, and from then on nsof_accum_reset sets w to the wini plane where wini is mapped.  n_maps == 0 returns to the
+ * uniform model.  Synchronous.
+ * NSOF_EINVAL, the accumulator keeping its model and state: a key outside [0, NSOF_ACCUM_KEY_COUNT), a key given twice, a
+ * NULL plane, an accumulator that has advanced, and any pixel outside the domain nsof_accum_create_p checks -- non-finite,
+ * voff >= 0, von <= 0, son / soff / wini outside [0, 1], Ron or Roff <= 0 -- the message naming the key and the first such
+ * pixel (row, column, value).  The check is a host pass over the planes before anything is uploaded.
+ * Device form: one set-up kernel per call writes, per pixel, the drive (k * (V/v0 - 1) ** alpha, s, b) at the active and at
+ * the silent voltage and the pair (Ron, neg_lam); the update kernels read a pixel's 12-byte drive where they formed one
+ * from their arguments.  The dead-zone shortcut (nsof_accum_set_dense) holds when silent_v lies in [voff, von] at EVERY
+ * pixel; otherwise every advancing call takes the every-pixel pass with the per-pixel silent drive, whatever force_dense.
+ * nsof_accum_run_frames on a mapped accumulator takes copy + patch where it applies and n_frames x nsof_accum_run_surface
+ * otherwise; the tile walk has no mapped form and is routed around (nsof_accum_set_frames_path changes nothing then).
+ * Out of scope: the element-wise nsof_accum_update_state*_dev / nsof_accum_resistance*_dev entries and the float64
+ * frame-driven path nsof_accum_frames_f64* (one device per call), row-band sharding in nsof/dist.py (a band factory takes
+ * no maps), the linear resistance map, per-pixel thresholds. */
+enum {
+    NSOF_ACCUM_KEY_ALPHAOFF = 0, NSOF_ACCUM_KEY_ALPHAON, NSOF_ACCUM_KEY_VOFF, NSOF_ACCUM_KEY_VON, NSOF_ACCUM_KEY_KOFF,
+    NSOF_ACCUM_KEY_KON, NSOF_ACCUM_KEY_SON, NSOF_ACCUM_KEY_SOFF, NSOF_ACCUM_KEY_BON, NSOF_ACCUM_KEY_BOFF, NSOF_ACCUM_KEY_RON,
+    NSOF_ACCUM_KEY_ROFF, NSOF_ACCUM_KEY_WINI, NSOF_ACCUM_KEY_COUNT   /* = 13: the double fields of nsof_accum_params, in order */
+};
+int nsof_accum_set_param_maps(nsof_accum* acc, int n_maps, const int* keys, const float* const* maps);
+/* The plane of a mapped key as it was set, float32 [H][W] to HOST memory; NSOF_EINVAL if that key is uniform. */
+int nsof_accum_read_param_map(nsof_accum* acc, int key, float* out);
+/* Bit k of *mask set: key k is a map. */
+int nsof_accum_param_map_mask(const nsof_accum* acc, unsigned* mask);
 void nsof_accum_destroy(nsof_accum* acc);
 /* With silent_v in the dead zone an idle pixel is a bit-exact no-op, so two updates give the same state: the event-pixel
  * update (only touched pixels, groups of 32 slices) and the every-pixel pass (scheme 1: groups of 64 slices, no lists).
@@ -448,7 +482,7 @@ int nsof_accum_set_dense(nsof_accum* acc, int force_dense);
  * accumulator (the reference records theta_events = None there: the scheme has no count threshold). */
 int nsof_accum_set_event_threshold(nsof_accum* acc, int theta);
 int nsof_accum_get_event_threshold(const nsof_accum* acc, int* theta);
-/* Reset w to the model's wini (default 0.5) and the refractory maps to 0. */
+/* Reset w to the model's wini (default 0.5; the wini plane where one is set) and the refractory maps to 0. */
 int nsof_accum_reset(nsof_accum* acc);
 /* Advance by n_slices time slices.  Events are HOST arrays (x,y int16; p int8; t int64 us,
  * sorted) as in the /CD/events group (event_mem_sim.py:69-75); slice_bounds has

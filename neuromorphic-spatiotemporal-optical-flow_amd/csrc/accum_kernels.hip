@@ -15,7 +15,8 @@
 //    one scatter per group as in scheme 1, the eligibility walk inside the fused update (RefrTab).
 //  * The device model (PARAMS, DT, REFRACTORY_US of the reference) is an argument of the accumulator (nsof_accum_params):
 //    float32 fields by value in the kernel arguments, the fitted device of the paper as a compile-time instantiation of
-//    the hot kernels (DevF, fitted_f below).
+//    the hot kernels (DevF, fitted_f below).  Per-pixel parameter maps (nsof_accum_set_param_maps) are a third kind: one
+//    set-up kernel writes every pixel's drives and resistance pair, the hot kernels load them per driven pixel (MapF).
 //  * pow/exp go through double precision so that the float32 result is the correctly
 //    rounded one: equal to it on every state in [0, 1] outside the ~3e-7 of inputs that lie
 //    within 2^-43 of a rounding midpoint, and on those too as measured (tests/test_accum_cr_gpu.py;
@@ -45,10 +46,10 @@ struct DevD {
     double voff, von, koff, kon, son, soff, bon, boff, alphaoff, alphaon, ron, lambda, wini;
 };
 // The fitted device of the paper (event_mem_sim.py:20-34) as compile-time constants.  The hot kernels -- the fused updates,
-// the tile walk, the float64 frame loop -- are instantiated twice: FITTED takes an empty argument and folds these constants, so
+// the tile walk, the float64 frame loop -- are instantiated per model kind: the fitted one (MK_FITTED; FITTED in the float64 loop) takes an empty argument and folds these constants, so
 // the default path runs the code it ran before the parameters became arguments (same bits, same time: measured, a run-time
 // model cost the launch-bound scheme-2 groups 1.5-2.5 %); the other instantiation reads the argument.  NULL or default
-// parameters are routed to FITTED (Model::fitted).
+// parameters are routed to the fitted instantiation (Model::fitted); per-pixel planes are the third kind (MapF below).
 __host__ __device__ constexpr DevF fitted_f()
 {
     return DevF{(float)-0.2, (float)0.1, (float)51.03, (float)-2.91, (float)0.2, (float)0.8, (float)-5.12, (float)3.10,
@@ -59,10 +60,32 @@ __host__ __device__ constexpr DevD fitted_d()
     return DevD{-0.2, 0.1, 51.03, -2.91, 0.2, 0.8, -5.12, 3.10, 1.0, 1.0, 163305.0, 0.0 /* lambda: never read, see FrameArg */, 0.5};
 }
 struct NoModel {};
-template <bool FITTED>
-using ModelArg = std::conditional_t<FITTED, NoModel, DevF>;
+// Per-pixel parameter maps (nsof_accum_set_param_maps): the third kind of model.  The voltages are fixed per accumulator, so
+// everything a pixel's update needs is formed ONCE by k_setup_maps -- the active and the silent Drive (ka, s, b: 12 bytes
+// each, dt stays a scalar) and the pair (ron, neg_lam) of its resistance -- and the hot kernels load a pixel's drive where
+// they formed one from SGPRs: 12 bytes per driven pixel, nothing for an idle one.
+struct MapF {
+    const float* act;    // [npx][3]: drive_of(active voltage, the pixel's DevF)
+    const float* sil;    // [npx][3]: drive_of(silent_v, the pixel's DevF)
+    const float2* res;   // [npx]: (ron, neg_lam)
+    float dt;
+};
+// KIND of the hot kernels: the fitted device as compile-time constants / one device in the kernel arguments / per-pixel planes.
+// (int constants, not an unnamed enum: ModelArg<KIND> is part of every hot kernel's signature, and an unnamed type in a mangled
+// name is numbered differently by the host and the device pass -- the host would register a name the code object lacks)
+constexpr int MK_FITTED = 0, MK_UNIFORM = 1, MK_MAPPED = 2;
+template <int KIND>
+using ModelArg = std::conditional_t<KIND == MK_FITTED, NoModel, std::conditional_t<KIND == MK_UNIFORM, DevF, MapF>>;
+template <int KIND>
+using KindTag = std::integral_constant<int, KIND>;
 __device__ __forceinline__ DevF model_arg(const DevF& p) { return p; }
 __device__ __forceinline__ DevF model_arg(NoModel) { return fitted_f(); }
+__device__ __forceinline__ DevF model_arg(const MapF& m)   // dt is all the pixels share
+{
+    DevF p{};
+    p.dt = m.dt;
+    return p;
+}
 // The float64 frame loop: lambda = ln(Roff / Ron) is formed on the host in either case (std::log is no constant expression).
 struct FittedD { double lambda; };
 template <bool FITTED>
@@ -198,6 +221,30 @@ __device__ __forceinline__ float resistance_one(float w, const DevF& p)
     return (float)((double)p.ron / (double)e);
 }
 
+// A pixel's drive and resistance constants from the planes k_setup_maps wrote.
+__device__ __forceinline__ Drive drive_at(const float* __restrict__ plane, size_t pix, float dt)
+{
+    const float* q = plane + 3 * pix;
+    return Drive{q[0], q[1], q[2], dt};
+}
+// The model resistance_one / surface_gray_value read (ron, neg_lam; mode 1 of the surface reads neither: no load): the
+// uniform device itself, or pixel pix of a mapped one.
+struct MapRes {
+    const float2* res;
+};
+__device__ __forceinline__ const DevF& res_at(const DevF& p, size_t, int) { return p; }
+__device__ __forceinline__ DevF res_at(const float2* __restrict__ res, size_t pix, int mode)
+{
+    DevF q{};
+    if (mode == 0) {
+        const float2 r = res[pix];
+        q.ron = r.x;
+        q.neg_lam = r.y;
+    }
+    return q;
+}
+__device__ __forceinline__ DevF res_at(MapRes m, size_t pix, int mode) { return res_at(m.res, pix, mode); }
+
 __global__ __launch_bounds__(256) void k_update_state(const float* __restrict__ w, const float* __restrict__ V,
                                                        float* __restrict__ out, size_t n, DevF p)
 {
@@ -205,10 +252,12 @@ __global__ __launch_bounds__(256) void k_update_state(const float* __restrict__ 
         out[i] = update_one(w[i], V[i], p);
 }
 
-__global__ __launch_bounds__(256) void k_resistance(const float* __restrict__ w, float* __restrict__ out, size_t n, DevF p)
+//   ResT  DevF (one device) or MapRes (element i is pixel i of a mapped accumulator)
+template <class ResT>
+__global__ __launch_bounds__(256) void k_resistance(const float* __restrict__ w, float* __restrict__ out, size_t n, ResT p)
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-        out[i] = resistance_one(w[i], p);
+        out[i] = resistance_one(w[i], res_at(p, i, 0));
 }
 
 __global__ __launch_bounds__(256) void k_fill(float* __restrict__ p, size_t n, float v)
@@ -401,13 +450,14 @@ __device__ __forceinline__ float replay_driven(float ww, MaskT m, const Drive& d
 //   REFR   scheme 2: the mask holds event bits; refractory_walk turns them into driven bits first
 //   MaskT  the mask word: 32 bits (groups of up to 32 slices), 64 bits (copy + patch: intervals of up to 64 slices)
 //   FRAME  the pixel's byte of the frame `so` is overwritten as well (copy + patch)
-//   FITTED the fitted device as compile-time constants (ModelArg)
+//   KIND   the model (ModelArg): MK_FITTED the fitted device as compile-time constants, MK_UNIFORM one device in the arguments,
+//          MK_MAPPED every pixel its own (its active drive, and for the frame its resistance pair, loaded per listed pixel)
 //   COUNT  scheme 1 with theta > 1: the word holds counter fields; driven_bits turns them into driven bits first
-template <bool REFR, class MaskT, bool FRAME, bool FITTED, bool COUNT>
+template <bool REFR, class MaskT, bool FRAME, int KIND, bool COUNT>
 __global__ __launch_bounds__(256) void k_update_list(float* __restrict__ w, MaskT* __restrict__ mask,
                                                       long long* __restrict__ next_ok, const unsigned* __restrict__ list,
                                                       const unsigned* __restrict__ count, TabArg<REFR> tab, float v_act,
-                                                      unsigned* zero_next, SurfOut so, ModelArg<FITTED> model, ThetaArg<COUNT> th)
+                                                      unsigned* zero_next, SurfOut so, ModelArg<KIND> model, ThetaArg<COUNT> th)
 {
     const DevF p = model_arg(model);
     __shared__ long long tf[REFR ? 32 : 1], tn[REFR ? 32 : 1];
@@ -432,11 +482,14 @@ __global__ __launch_bounds__(256) void k_update_list(float* __restrict__ w, Mask
             if (!m) continue;
             next_ok[pix] = ok;
         }
-        const float ww = replay_driven(w[pix], m, da);
+        float ww;
+        if constexpr (KIND == MK_MAPPED) ww = replay_driven(w[pix], m, drive_at(model.act, pix, p.dt));
+        else ww = replay_driven(w[pix], m, da);
         w[pix] = ww;
         if constexpr (FRAME) {
             const unsigned yy = pix / (unsigned)so.W, xx = pix - yy * (unsigned)so.W;
-            so.out[(long long)yy * so.stride + xx] = surface_gray_one(ww, p, so.mode);
+            if constexpr (KIND == MK_MAPPED) so.out[(long long)yy * so.stride + xx] = surface_gray_one(ww, res_at(model.res, pix, so.mode), so.mode);
+            else so.out[(long long)yy * so.stride + xx] = surface_gray_one(ww, p, so.mode);
         }
     }
 }
@@ -450,11 +503,14 @@ __global__ __launch_bounds__(256) void k_update_list(float* __restrict__ w, Mask
 //             already inside [0,1]), so only the slices whose bit is set are replayed (in slice order) -- the pass is then
 //             bound by its one read and one write of the state instead of by 32 no-op evaluations per pixel.
 //   COUNT     scheme 1 with theta > 1: both words hold counter fields, th.spw slices each; driven_bits first
-template <bool REFR, bool SIL_NOOP, bool FITTED, bool COUNT>
+//   KIND      MK_MAPPED: a pixel loads its own drives -- the active one only, and only if it is driven, under SIL_NOOP (which
+//             then means: silent_v in the dead zone of EVERY pixel); both otherwise, a pixel whose own dead zone holds
+//             silent_v carrying the no-op drive (ka = 0) -- and its resistance pair for a mode-0 frame
+template <bool REFR, bool SIL_NOOP, int KIND, bool COUNT>
 __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsigned* __restrict__ mask,
                                                      unsigned* __restrict__ mask_hi, long long* __restrict__ next_ok, size_t n4,
                                                      size_t n, int n_sl, TabArg<REFR> tab, float v_act, float v_sil, SurfOut so,
-                                                     ModelArg<FITTED> model, ThetaArg<COUNT> th)
+                                                     ModelArg<KIND> model, ThetaArg<COUNT> th)
 {
     const DevF p = model_arg(model);
     __shared__ long long tf[REFR ? 32 : 1], tn[REFR ? 32 : 1];
@@ -479,6 +535,19 @@ __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsig
                 if (m) next_ok[pix] = ok;
             }
         }
+        if constexpr (KIND == MK_MAPPED) {
+            if (SIL_NOOP) {
+                if (!(m | mh)) return ww;
+                const Drive pa = drive_at(model.act, pix, p.dt);
+                return replay_driven(replay_driven(ww, m, pa), mh, pa);
+            }
+            const Drive pa = drive_at(model.act, pix, p.dt), ps = drive_at(model.sil, pix, p.dt);
+            for (int s = 0; s < n_sl; s++) {
+                const bool act = (REFR || s < lo_sl) ? (m >> s) & 1u : (mh >> (s - lo_sl)) & 1u;
+                ww = update_drive(ww, act ? pa : ps);
+            }
+            return ww;
+        } else {
         if (SIL_NOOP) return replay_driven(replay_driven(ww, m, da), mh, da);
         for (int s = 0; s < n_sl; s++) {
             const bool act = (REFR || s < lo_sl) ? (m >> s) & 1u : (mh >> (s - lo_sl)) & 1u;
@@ -490,6 +559,12 @@ __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsig
             ww = update_drive(ww, d);
         }
         return ww;
+        }
+    };
+    // the byte of the new state's frame at pixel pix
+    auto gray = [&](float v, size_t pix) {
+        if constexpr (KIND == MK_MAPPED) return surface_gray_one(v, res_at(model.res, pix, so.mode), so.mode);
+        else return surface_gray_one(v, p, so.mode);
     };
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         if (4 * i + 3 < n) {
@@ -510,9 +585,8 @@ __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsig
             ww.w = one(ww.w, mm.w, mh.w, 4 * i + 3);
             reinterpret_cast<float4*>(w)[i] = ww;
             if (so.out) {   // the frame of the new state: saves the separate surface pass (4 B/px read again + a launch)
-                const uint8_t g0 = surface_gray_one(ww.x, p, so.mode), g1 = surface_gray_one(ww.y, p, so.mode);
-                const uint8_t g2 = surface_gray_one(ww.z, p, so.mode), g3 = surface_gray_one(ww.w, p, so.mode);
                 const size_t px = 4 * i;
+                const uint8_t g0 = gray(ww.x, px), g1 = gray(ww.y, px + 1), g2 = gray(ww.z, px + 2), g3 = gray(ww.w, px + 3);
                 const size_t yy = px / (size_t)so.W, xx = px - yy * (size_t)so.W;
                 if (xx + 3 < (size_t)so.W && ((so.stride | (long long)xx) & 3) == 0 && (reinterpret_cast<uintptr_t>(so.out) & 3) == 0) {
                     *reinterpret_cast<unsigned*>(so.out + yy * so.stride + xx) =
@@ -532,7 +606,7 @@ __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsig
                 if (mask_hi) mask_hi[j] = 0;
                 const float wj = one(w[j], m, mh, j);
                 w[j] = wj;
-                if (so.out) so.out[(j / (size_t)so.W) * so.stride + j % (size_t)so.W] = surface_gray_one(wj, p, so.mode);
+                if (so.out) so.out[(j / (size_t)so.W) * so.stride + j % (size_t)so.W] = gray(wj, j);
             }
         }
     }
@@ -611,22 +685,27 @@ __global__ __launch_bounds__(64) void k_frames_run(const double* __restrict__ im
 //           w = 0: the event simulator's initial state w = 0.5 (I = 1.7 uA) already maps to 255.
 //   mode 1  build-defined linear map of the state itself, g = uint8(255 * w) (float32 product, truncated): the frame
 //           the joined events -> surface -> flow pipeline (BASELINE config 5) hands to the flow stage.
+//   ResT  DevF (one device) or MapRes (per-pixel resistance constants)
+template <class ResT>
 __global__ __launch_bounds__(256) void k_surface_gray(const float* __restrict__ w, uint8_t* __restrict__ out, int W, int H,
-                                                       ptrdiff_t stride, DevF p, int mode)
+                                                       ptrdiff_t stride, ResT p, int mode)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= W || y >= H) return;
-    out[(ptrdiff_t)y * stride + x] = surface_gray_one(w[(size_t)y * W + x], p, mode);
+    const size_t pix = (size_t)y * W + x;
+    out[(ptrdiff_t)y * stride + x] = surface_gray_one(w[pix], res_at(p, pix, mode), mode);
 }
 
 // The same surface as a float frame: g rounded to float32 instead of truncated to 8 bits (finite, in [0, 255]).
+template <class ResT>
 __global__ __launch_bounds__(256) void k_surface_gray_f32(const float* __restrict__ w, float* __restrict__ out, int W, int H,
-                                                           ptrdiff_t stride, DevF p, int mode)
+                                                           ptrdiff_t stride, ResT p, int mode)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= W || y >= H) return;
+    const size_t pix = (size_t)y * W + x;
     reinterpret_cast<float*>(reinterpret_cast<char*>(out) + (ptrdiff_t)y * stride)[x] =
-        (float)surface_gray_value(w[(size_t)y * W + x], p, mode);
+        (float)surface_gray_value(w[pix], res_at(p, pix, mode), mode);
 }
 
 // ---- surface frames as copy + patch -------------------------------------------------------------------------------------
@@ -745,11 +824,12 @@ __global__ __launch_bounds__(1024) void k_tile_bucket(const short* __restrict__ 
     }
 }
 
-template <bool FITTED>
+// (MK_FITTED / MK_UNIFORM only: a mapped accumulator takes copy + patch, see nsof_accum_run_frames)
+template <int KIND>
 __global__ __launch_bounds__(256) void k_tile_frames(float* __restrict__ w, size_t npx, int W, const unsigned* __restrict__ off,
                                                       const unsigned short* __restrict__ recs, unsigned ntiles, int n_frames,
                                                       float v_act, uint8_t* __restrict__ frames, long long row_stride,
-                                                      long long frame_stride, ModelArg<FITTED> model, int mode)
+                                                      long long frame_stride, ModelArg<KIND> model, int mode)
 {
     const DevF p = model_arg(model);
     __shared__ unsigned long long s_mask[4][TILE_PX];
@@ -873,14 +953,33 @@ struct Model {
     DevF f;
     DevD d;
     float wini_f;
-    bool fitted;   // every field equals the fitted device's: the FITTED kernel instantiations apply
+    bool fitted;   // every field equals the fitted device's: the MK_FITTED kernel instantiations apply
+    // per-pixel parameter maps (nsof_accum_set_param_maps; the planes belong to the accumulator's ParamMaps)
+    bool mapped = false;
+    MapF map{nullptr, nullptr, nullptr, 0.f};
 };
-// f(std::true_type, NoModel) for the fitted device, f(std::false_type, DevF) otherwise: the kernel instantiation and its argument
+// f(KindTag<MK_FITTED>, NoModel) for the fitted device, f(KindTag<MK_UNIFORM>, DevF) for another one, f(KindTag<MK_MAPPED>,
+// MapF) with parameter maps: the kernel instantiation and its argument
 template <class Fn>
 void with_model(const Model& m, Fn&& f)
 {
-    if (m.fitted) f(std::true_type{}, NoModel{});
-    else f(std::false_type{}, m.f);
+    if (m.mapped) f(KindTag<MK_MAPPED>{}, m.map);
+    else if (m.fitted) f(KindTag<MK_FITTED>{}, NoModel{});
+    else f(KindTag<MK_UNIFORM>{}, m.f);
+}
+// ... for the kernels that have no mapped form (the tile walk): the caller has routed a mapped accumulator elsewhere
+template <class Fn>
+void with_uniform_model(const Model& m, Fn&& f)
+{
+    if (m.fitted) f(KindTag<MK_FITTED>{}, NoModel{});
+    else f(KindTag<MK_UNIFORM>{}, m.f);
+}
+// f(DevF) or f(MapRes): the argument of the kernels that read a pixel's resistance only
+template <class Fn>
+void with_res(const Model& m, Fn&& f)
+{
+    if (m.mapped) f(MapRes{m.map.res});
+    else f(m.f);
 }
 template <class Fn>
 void with_frame_model(const Model& m, Fn&& f)
@@ -937,6 +1036,39 @@ int model_of(nsof_ctx* ctx, const nsof_accum_params* in, Model* m)
     return NSOF_OK;
 }
 
+// The set-up pass of the parameter maps (nsof_accum_set_param_maps), once per call: per pixel the DevF of that pixel -- a
+// mapped key's float32 value, an unmapped one's scalar -- and from it exactly what the uniform kernels form per launch:
+// drive_of at the accumulator's two voltages and (ron, neg_lam), neg_lam = (float)(-ln(Roff / Ron)) with the logarithm in
+// double of the values as held (a plane's float32 widened, the scalar's double).
+struct MapSrc {
+    const float* plane[NSOF_ACCUM_KEY_COUNT];   // nullptr: the key is uniform
+    float scalar[NSOF_ACCUM_KEY_COUNT];
+    double ron, roff;                           // the scalars' doubles
+    float dt;
+};
+__global__ __launch_bounds__(256) void k_setup_maps(MapSrc src, size_t n, float v_act, float v_sil, float* __restrict__ act,
+                                                     float* __restrict__ sil, float2* __restrict__ res)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        auto get = [&](int k) { return src.plane[k] ? src.plane[k][i] : src.scalar[k]; };
+        DevF p;
+        p.alphaoff = get(NSOF_ACCUM_KEY_ALPHAOFF); p.alphaon = get(NSOF_ACCUM_KEY_ALPHAON);
+        p.voff = get(NSOF_ACCUM_KEY_VOFF); p.von = get(NSOF_ACCUM_KEY_VON);
+        p.koff = get(NSOF_ACCUM_KEY_KOFF); p.kon = get(NSOF_ACCUM_KEY_KON);
+        p.son = get(NSOF_ACCUM_KEY_SON); p.soff = get(NSOF_ACCUM_KEY_SOFF);
+        p.bon = get(NSOF_ACCUM_KEY_BON); p.boff = get(NSOF_ACCUM_KEY_BOFF);
+        p.dt = src.dt;
+        p.ron = get(NSOF_ACCUM_KEY_RON);
+        const double ron = src.plane[NSOF_ACCUM_KEY_RON] ? (double)p.ron : src.ron;
+        const double roff = src.plane[NSOF_ACCUM_KEY_ROFF] ? (double)src.plane[NSOF_ACCUM_KEY_ROFF][i] : src.roff;
+        p.neg_lam = (float)(-log(roff / ron));
+        const Drive da = drive_of(v_act, p), ds = drive_of(v_sil, p);
+        act[3 * i] = da.ka; act[3 * i + 1] = da.s; act[3 * i + 2] = da.b;
+        sil[3 * i] = ds.ka; sil[3 * i + 1] = ds.s; sil[3 * i + 2] = ds.b;
+        res[i] = make_float2(p.ron, p.neg_lam);
+    }
+}
+
 // List counters of the event-pixel update, [parity][array]: two sets used alternately.  A group's update kernels zero the
 // OTHER set -- the one the next group's scatter appends to -- so no group needs a memset (a launch of its own): one per call.
 struct ListCounts {
@@ -978,7 +1110,13 @@ struct nsof_accum {
     // staged stream (nsof_accum_set_events / the staging half of nsof_accum_step_events): slice bounds relative to
     // the first staged event, and for scheme 2 the first / last+refractory timestamp of every slice
     std::vector<long long> h_rel, h_tfirst, h_tnext;
-    Model model;             // the device the array is made of (nsof_accum_create_p), fixed for the accumulator's life
+    Model model;             // the device the array is made of (nsof_accum_create_p): the scalars are fixed for the accumulator's life
+    // per-pixel parameter maps (nsof_accum_set_param_maps): the raw float32 planes of the mapped keys (kept for
+    // nsof_accum_read_param_map; the wini plane is what reset copies) and what k_setup_maps made of them (model.map points here)
+    unsigned map_mask = 0;
+    bool map_dead_zone = false;   // silent_v inside [voff, von] at EVERY pixel
+    nsof_dev_buf<float> map_plane[NSOF_ACCUM_KEY_COUNT];
+    nsof_dev_buf<float> map_act, map_sil, map_res;
     int frames_path = 0;     // nsof_accum_run_frames: 0 = the tile walk where it applies, 1 = copy + patch per interval (kept as the cross-check)
 };
 
@@ -997,13 +1135,139 @@ extern "C" int nsof_accum_reset(nsof_accum* a)
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const int narr = a->split ? 2 : 1;
     for (int i = 0; i < narr; i++) {
-        hipLaunchKernelGGL(k_fill, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[i].p, a->npx, a->model.wini_f);
+        if (a->map_mask >> NSOF_ACCUM_KEY_WINI & 1u)
+            NSOF_HIP(ctx, hipMemcpyAsync(a->w[i].p, a->map_plane[NSOF_ACCUM_KEY_WINI].p, a->npx * sizeof(float), hipMemcpyDeviceToDevice,
+                                         ctx->stream));
+        else
+            hipLaunchKernelGGL(k_fill, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[i].p, a->npx, a->model.wini_f);
         NSOF_HIP(ctx, hipMemsetAsync(a->mask[i].p, 0, a->npx * sizeof(unsigned), ctx->stream));
         if (a->scheme == 2) NSOF_HIP(ctx, hipMemsetAsync(a->next_ok[i].p, 0, a->npx * sizeof(long long), ctx->stream));
     }
     NSOF_HIP(ctx, hipGetLastError());
     a->slice_counter = 0;
     a->snap_count = 0;
+    return NSOF_OK;
+}
+
+// Per-pixel parameter maps: see include/nsof.h.  Everything that can refuse the call -- the arguments, the accumulator's state,
+// the domain of every pixel of every plane -- is decided on the host before the accumulator or the device is touched; the
+// new planes are allocated aside and swapped in only once they are all there.
+extern "C" int nsof_accum_set_param_maps(nsof_accum* a, int n_maps, const int* keys, const float* const* maps)
+{
+    if (!a) return NSOF_EINVAL;
+    nsof_ctx* ctx = a->ctx;
+    static const char* const names[NSOF_ACCUM_KEY_COUNT] = {"alphaoff", "alphaon", "voff", "von", "koff", "kon", "son", "soff", "bon",
+                                                           "boff", "Ron", "Roff", "wini"};
+    if (n_maps < 0 || n_maps > NSOF_ACCUM_KEY_COUNT || (n_maps > 0 && (!keys || !maps)))
+        return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: %d maps (0..%d, with their keys and planes)", n_maps, NSOF_ACCUM_KEY_COUNT);
+    const float* plane[NSOF_ACCUM_KEY_COUNT] = {};
+    for (int j = 0; j < n_maps; j++) {
+        const int k = keys[j];
+        if (k < 0 || k >= NSOF_ACCUM_KEY_COUNT) return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: key %d is no parameter (0..%d)", k, NSOF_ACCUM_KEY_COUNT - 1);
+        if (!maps[j]) return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: the plane of %s is NULL", names[k]);
+        if (plane[k]) return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: %s given twice", names[k]);
+        plane[k] = maps[j];
+    }
+    if (a->slice_counter != 0 || a->snap_count != 0)
+        return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: the accumulator has advanced (slice %lld, %lld snapshots); reset it first",
+                              (long long)a->slice_counter, (long long)a->snap_count);
+    const Model& mo = a->model;
+    const size_t npx = a->npx;
+    // the domain of model_of, per pixel of every plane, in the order the planes were given
+    for (int j = 0; j < n_maps; j++) {
+        const int k = keys[j];
+        const float* q = maps[j];
+        for (size_t i = 0; i < npx; i++) {
+            const float v = q[i];
+            const char* why = nullptr;
+            if (!std::isfinite(v)) why = "is not finite";
+            else if (k == NSOF_ACCUM_KEY_VOFF && !(v < 0.f)) why = "must be negative (voff < 0 < von)";
+            else if (k == NSOF_ACCUM_KEY_VON && !(v > 0.f)) why = "must be positive (voff < 0 < von)";
+            else if ((k == NSOF_ACCUM_KEY_SON || k == NSOF_ACCUM_KEY_SOFF || k == NSOF_ACCUM_KEY_WINI) && !(v >= 0.f && v <= 1.f)) why = "lies outside [0, 1]";
+            else if ((k == NSOF_ACCUM_KEY_RON || k == NSOF_ACCUM_KEY_ROFF) && !(v > 0.f)) why = "must be positive";
+            if (why)
+                return nsof_set_error(ctx, NSOF_EINVAL, "parameter map %s: pixel (row %zu, column %zu) = %g %s", names[k], i / (size_t)a->W,
+                                      i % (size_t)a->W, (double)v, why);
+        }
+    }
+    if (plane[NSOF_ACCUM_KEY_RON] || plane[NSOF_ACCUM_KEY_ROFF])   // (two positive floats: the quotient is a finite positive double)
+        for (size_t i = 0; i < npx; i++) {
+            const double ron = plane[NSOF_ACCUM_KEY_RON] ? (double)plane[NSOF_ACCUM_KEY_RON][i] : mo.prm.Ron;
+            const double roff = plane[NSOF_ACCUM_KEY_ROFF] ? (double)plane[NSOF_ACCUM_KEY_ROFF][i] : mo.prm.Roff;
+            if (!std::isfinite(std::log(roff / ron)))
+                return nsof_set_error(ctx, NSOF_EINVAL, "parameter maps Ron / Roff: ln(Roff / Ron) is not finite at pixel (row %zu, column %zu)",
+                                      i / (size_t)a->W, i % (size_t)a->W);
+        }
+    // silent_v inside the dead zone of EVERY pixel (the float32 comparisons update_one makes): what decides between the
+    // event-pixel update / the no-op silent slices and the every-pixel pass with a per-pixel silent drive
+    bool dead = true;
+    {
+        const float* vo = plane[NSOF_ACCUM_KEY_VOFF];
+        const float* vn = plane[NSOF_ACCUM_KEY_VON];
+        for (size_t i = 0; i < npx && dead; i++)
+            dead = !(a->silent_v < (vo ? vo[i] : mo.f.voff)) && !(a->silent_v > (vn ? vn[i] : mo.f.von));
+    }
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    if (n_maps == 0) {   // back to the uniform model (the planes stay allocated for a later call)
+        a->map_mask = 0;
+        a->model.mapped = false;
+        a->model.map = MapF{nullptr, nullptr, nullptr, 0.f};
+        return nsof_accum_reset(a);
+    }
+    nsof_dev_buf<float> np_[NSOF_ACCUM_KEY_COUNT], nact, nsil, nres;
+    int rc = nact.reserve(ctx, npx * 3 * sizeof(float));
+    if (!rc) rc = nsil.reserve(ctx, npx * 3 * sizeof(float));
+    if (!rc) rc = nres.reserve(ctx, npx * 2 * sizeof(float));
+    for (int k = 0; k < NSOF_ACCUM_KEY_COUNT && !rc; k++)
+        if (plane[k]) rc = np_[k].reserve(ctx, npx * sizeof(float));
+    if (rc) return rc;
+    const float scal[NSOF_ACCUM_KEY_COUNT] = {mo.f.alphaoff, mo.f.alphaon, mo.f.voff, mo.f.von, mo.f.koff, mo.f.kon, mo.f.son, mo.f.soff,
+                                              mo.f.bon, mo.f.boff, mo.f.ron, (float)mo.prm.Roff, mo.wini_f};
+    MapSrc src;
+    unsigned mask = 0;
+    for (int k = 0; k < NSOF_ACCUM_KEY_COUNT; k++) {
+        src.plane[k] = nullptr;
+        src.scalar[k] = scal[k];
+        if (!plane[k]) continue;
+        NSOF_HIP(ctx, hipMemcpyAsync(np_[k].p, plane[k], npx * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        src.plane[k] = np_[k].p;
+        mask |= 1u << k;
+    }
+    src.ron = mo.prm.Ron;
+    src.roff = mo.prm.Roff;
+    src.dt = mo.f.dt;
+    const float v_act = a->scheme == 1 ? a->active_v : a->silent_v + a->active_v;
+    hipLaunchKernelGGL(k_setup_maps, dim3(grid_for(npx)), dim3(256), 0, ctx->stream, src, npx, v_act, a->silent_v, nact.p, nsil.p,
+                       reinterpret_cast<float2*>(nres.p));
+    NSOF_HIP(ctx, hipGetLastError());
+    NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the caller's planes are not retained; the old ones are free to go
+    for (int k = 0; k < NSOF_ACCUM_KEY_COUNT; k++) a->map_plane[k].swap(np_[k]);
+    a->map_act.swap(nact);
+    a->map_sil.swap(nsil);
+    a->map_res.swap(nres);
+    a->map_mask = mask;
+    a->map_dead_zone = dead;
+    a->model.mapped = true;
+    a->model.map = MapF{a->map_act.p, a->map_sil.p, reinterpret_cast<const float2*>(a->map_res.p), mo.f.dt};
+    return nsof_accum_reset(a);
+}
+
+extern "C" int nsof_accum_read_param_map(nsof_accum* a, int key, float* out)
+{
+    if (!a || !out) return NSOF_EINVAL;
+    nsof_ctx* ctx = a->ctx;
+    if (key < 0 || key >= NSOF_ACCUM_KEY_COUNT || !(a->map_mask >> key & 1u))
+        return nsof_set_error(ctx, NSOF_EINVAL, "read_param_map: key %d is uniform (no map set)", key);
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    NSOF_HIP(ctx, hipMemcpyAsync(out, a->map_plane[key].p, a->npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NSOF_OK;
+}
+
+extern "C" int nsof_accum_param_map_mask(const nsof_accum* a, unsigned* mask)
+{
+    if (!a || !mask) return NSOF_EINVAL;
+    *mask = a->map_mask;
     return NSOF_OK;
 }
 
@@ -1105,8 +1369,10 @@ static int accum_snapshot(nsof_accum* a)
         a->snap_cap = ncap;
     }
     for (int i = 0; i < narr; i++)
-        hipLaunchKernelGGL(k_resistance, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[i].p,
-                           a->snap[i].p + (size_t)a->snap_count * a->npx, a->npx, a->model.f);
+        with_res(a->model, [&](auto res) {
+            hipLaunchKernelGGL(k_resistance<decltype(res)>, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[i].p,
+                               a->snap[i].p + (size_t)a->snap_count * a->npx, a->npx, res);
+        });
     NSOF_HIP(ctx, hipGetLastError());
     a->snap_count++;
     return NSOF_OK;
@@ -1182,6 +1448,7 @@ extern "C" int nsof_accum_set_slice_times(nsof_accum* a, const int64_t* t_first,
 // The silent voltage leaves an idle pixel bit for bit unchanged: the float32 comparisons update_one makes.
 static bool dead_zone_of(const nsof_accum* a)
 {
+    if (a->model.mapped) return a->map_dead_zone;   // ... at every pixel (nsof_accum_set_param_maps)
     return !(a->silent_v < a->model.f.voff) && !(a->silent_v > a->model.f.von);
 }
 
@@ -1195,8 +1462,10 @@ static int accum_surface(nsof_accum* a, int which, const SurfOut& so)
 {
     nsof_ctx* ctx = a->ctx;
     dim3 grid((a->W + 255) / 256, a->H);
-    hipLaunchKernelGGL(k_surface_gray, grid, dim3(256), 0, ctx->stream, a->w[which].p, so.out, a->W, a->H, (ptrdiff_t)so.stride,
-                       a->model.f, so.mode);
+    with_res(a->model, [&](auto res) {
+        hipLaunchKernelGGL(k_surface_gray<decltype(res)>, grid, dim3(256), 0, ctx->stream, a->w[which].p, so.out, a->W, a->H,
+                           (ptrdiff_t)so.stride, res, so.mode);
+    });
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
@@ -1285,8 +1554,8 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
                 }
                 const size_t n4 = (a->npx + 3) / 4;
                 with_model(a->model, [&](auto D, auto model) {
-                    constexpr bool FITTED = decltype(D)::value;
-                    auto* const kernel = dead_zone ? k_update_all<REFR, true, FITTED, COUNT> : k_update_all<REFR, false, FITTED, COUNT>;
+                    constexpr int KIND = decltype(D)::value;
+                    auto* const kernel = dead_zone ? k_update_all<REFR, true, KIND, COUNT> : k_update_all<REFR, false, KIND, COUNT>;
                     hipLaunchKernelGGL(kernel, dim3(grid_for(n4, 8192)), dim3(256), 0, ctx->stream, a->w[i].p, a->mask[i].p,
                                        g > word_slices ? a->mask_hi.p : nullptr, a->next_ok[i].p, n4, a->npx, (int)g, tab, v_act,
                                        a->silent_v, so, model, th);
@@ -1355,8 +1624,10 @@ extern "C" int nsof_accum_surface_f32_dev(nsof_accum* a, int which, int mode, fl
     nsof_ctx* ctx = a->ctx;
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid((a->W + 255) / 256, a->H);
-    hipLaunchKernelGGL(k_surface_gray_f32, grid, dim3(256), 0, ctx->stream, a->w[which].p, d_out, a->W, a->H, row_stride_bytes,
-                       a->model.f, mode);
+    with_res(a->model, [&](auto res) {
+        hipLaunchKernelGGL(k_surface_gray_f32<decltype(res)>, grid, dim3(256), 0, ctx->stream, a->w[which].p, d_out, a->W, a->H,
+                           row_stride_bytes, res, mode);
+    });
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
@@ -1403,7 +1674,8 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
                          (reinterpret_cast<uintptr_t>(d_frames) & 15) == 0 && n_frames >= 2 && n_ev < (1ll << 31) &&
                          (a->npx + TILE_PX - 1) / TILE_PX <= 15000 &&   // the bucketing workgroup's histogram: 4 B per tile of LDS
                          (size_t)n_frames * ((a->npx + TILE_PX - 1) / TILE_PX) < ((size_t)1 << 30) && a->frames_path != 1 &&
-                         a->theta == 1;   // the walk's LDS masks hold bits, not counts
+                         a->theta == 1 &&   // the walk's LDS masks hold bits, not counts
+                         !a->model.mapped;   // ... and its waves one drive: a mapped accumulator takes copy + patch
     if (tile_ok) {
         const unsigned ntiles = (unsigned)((a->npx + TILE_PX - 1) / TILE_PX);
         const size_t nb = (size_t)n_frames * ntiles;
@@ -1413,7 +1685,7 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
         nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
         hipLaunchKernelGGL(k_tile_bucket, dim3((unsigned)n_frames), dim3(1024), (size_t)ntiles * 4, ctx->stream, a->dx.p, a->dy.p, ev0,
                            a->dbounds.p + first_slice, (int)every, a->W, ntiles, a->tile_off.p, a->tile_recs.p, (int)n_frames);
-        with_model(a->model, [&](auto D, auto model) {
+        with_uniform_model(a->model, [&](auto D, auto model) {
             hipLaunchKernelGGL(k_tile_frames<decltype(D)::value>, dim3((ntiles + 3) / 4), dim3(256), 0, ctx->stream, a->w[0].p, a->npx,
                                a->W, (const unsigned*)a->tile_off.p, (const unsigned short*)a->tile_recs.p, ntiles, (int)n_frames,
                                a->active_v, d_frames, (long long)row_stride, (long long)frame_stride, model, mode);
@@ -1557,7 +1829,7 @@ extern "C" int nsof_accum_resistance_p_dev(nsof_ctx* ctx, const nsof_accum_param
     Model model;
     if (int rc = model_of(ctx, params, &model)) return rc;
     if (!n) return NSOF_OK;
-    hipLaunchKernelGGL(k_resistance, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_w, d_out, n, model.f);
+    hipLaunchKernelGGL(k_resistance<DevF>, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_w, d_out, n, model.f);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
@@ -1583,7 +1855,13 @@ extern "C" int nsof_accum_read_resistance(nsof_accum* a, int which, float* out)
     nsof_dev_buf<float> tmp;
     int rc = tmp.reserve(ctx, a->npx * sizeof(float));
     if (rc) return rc;
-    rc = nsof_accum_resistance_p_dev(ctx, &a->model.prm, a->w[which].p, tmp.p, a->npx);
+    if (a->model.mapped) {
+        hipLaunchKernelGGL(k_resistance<MapRes>, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[which].p, tmp.p, a->npx,
+                           MapRes{a->model.map.res});
+        if (hipGetLastError() != hipSuccess) rc = nsof_set_error(ctx, NSOF_EDEVICE, "resistance launch failed");
+    } else {
+        rc = nsof_accum_resistance_p_dev(ctx, &a->model.prm, a->w[which].p, tmp.p, a->npx);
+    }
     if (!rc) {
         hipError_t e = hipMemcpyAsync(out, tmp.p, a->npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1598,16 +1876,19 @@ extern "C" int64_t nsof_accum_snapshot_count(const nsof_accum* a) { return a ? a
 // (one value per block) formed on the device instead of from a downloaded surface.
 // max(v_ds / R) = v_ds / min(R) exactly (division by a positive float is monotone), so a block reduces min(R) in
 // float32 -- R from a stored snapshot, or resistance_one(w) of the current state -- and thread 0 divides in double.
+//   ResT  DevF (one device) or MapRes (per-pixel resistance constants, read where the source is the state)
+template <class ResT>
 __global__ __launch_bounds__(256) void k_block_min_resistance(const float* __restrict__ src, int is_w, int W, int memsize,
-                                                               int cols, DevF p, double v_ds, double* __restrict__ out)
+                                                               int cols, ResT p, double v_ds, double* __restrict__ out)
 {
     __shared__ float part[4];
     const int bx = blockIdx.x, by = blockIdx.y;
-    const float* base = src + ((size_t)by * memsize) * W + (size_t)bx * memsize;
+    const size_t base = ((size_t)by * memsize) * W + (size_t)bx * memsize;
     float m = INFINITY;
     for (int i = threadIdx.x; i < memsize * memsize; i += 256) {
-        const float v = base[(size_t)(i / memsize) * W + (i % memsize)];
-        m = fminf(m, is_w ? resistance_one(v, p) : v);
+        const size_t pix = base + (size_t)(i / memsize) * W + (i % memsize);
+        const float v = src[pix];
+        m = fminf(m, is_w ? resistance_one(v, res_at(p, pix, 0)) : v);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o));
@@ -1628,8 +1909,10 @@ extern "C" int nsof_accum_block_current(nsof_accum* a, int which, int64_t snapsh
     int rc = ctx->tmp.reserve(ctx, bytes);
     if (rc) return rc;
     const float* src = snapshot < 0 ? a->w[which].p : a->snap[which].p + (size_t)snapshot * a->npx;
-    hipLaunchKernelGGL(k_block_min_resistance, dim3(cols, rows), dim3(256), 0, ctx->stream, src, snapshot < 0 ? 1 : 0, a->W,
-                       memsize, cols, a->model.f, v_ds, (double*)ctx->tmp.p);
+    with_res(a->model, [&](auto res) {
+        hipLaunchKernelGGL(k_block_min_resistance<decltype(res)>, dim3(cols, rows), dim3(256), 0, ctx->stream, src,
+                           snapshot < 0 ? 1 : 0, a->W, memsize, cols, res, v_ds, (double*)ctx->tmp.p);
+    });
     NSOF_HIP(ctx, hipGetLastError());
     NSOF_HIP(ctx, hipMemcpyAsync(out, ctx->tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1647,8 +1930,10 @@ extern "C" int nsof_accum_block_current_dev(nsof_accum* a, int which, int64_t sn
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const int rows = a->H / memsize, cols = a->W / memsize;
     const float* src = snapshot < 0 ? a->w[which].p : a->snap[which].p + (size_t)snapshot * a->npx;
-    hipLaunchKernelGGL(k_block_min_resistance, dim3(cols, rows), dim3(256), 0, ctx->stream, src, snapshot < 0 ? 1 : 0, a->W,
-                       memsize, cols, a->model.f, v_ds, d_out);
+    with_res(a->model, [&](auto res) {
+        hipLaunchKernelGGL(k_block_min_resistance<decltype(res)>, dim3(cols, rows), dim3(256), 0, ctx->stream, src,
+                           snapshot < 0 ? 1 : 0, a->W, memsize, cols, res, v_ds, d_out);
+    });
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }

@@ -22,7 +22,7 @@ from .farneback import (OPTFLOW_FARNEBACK_GAUSSIAN, OPTFLOW_USE_INITIAL_FLOW, Fa
                         pinned_empty, uninstall)
 from .accumulator import (PARAMS, DT, THETA_EVENTS, REFRACTORY_US, Accumulator, accum_params, bincount_2d,  # noqa: F401
                           generate_synthetic_events, load_events, resistance_exp, simulate, simulate_frames, simulate_frames_dev,
-                          slice_indices, update_state)
+                          slice_indices, update_state, variability_maps)
 
 from .gating import (GatingConfig, connectedComponentsWithStats, current_to_gray, dataset_config, frame_to_gray,  # noqa: F401,E402
                      gating_maps, load_gating_stack, opticalFlow3D, process_merged_region, process_separate_regions, update_transition_pic)

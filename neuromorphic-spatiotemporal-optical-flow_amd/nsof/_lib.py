@@ -23,6 +23,8 @@ OPT_DEBUG_FAULT = 100   # test hook: see include/nsof.h
 NSOF_OK, NSOF_EINVAL, NSOF_ESHAPE, NSOF_EDEVICE, NSOF_ENOMEM, NSOF_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 # nsof_pixel_type of include/nsof.h (the frames' pixel type of the typed entries nsof_farneback_px*)
 PIXEL_U8, PIXEL_F32, PIXEL_U16, PIXEL_S16 = 0, 1, 2, 3
+# NSOF_ACCUM_KEY_* of include/nsof.h: the fields of nsof_accum_params a per-pixel map may replace, in struct order
+ACCUM_KEYS = ("alphaoff", "alphaon", "voff", "von", "koff", "kon", "son", "soff", "bon", "boff", "Ron", "Roff", "wini")
 K_PREP, K_POLYEXP, K_UPSAMPLE, K_UPDMAT, K_BLUR, K_ACCUM, K_ITERATE, K_SEGMENT, K_MORPH, K_REMAP, K_SSIM, K_COUNT = range(12)
 
 _vp, _i, _d, _f, _sz, _pd, _i64 = C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_size_t, C.c_ssize_t, C.c_int64
@@ -102,6 +104,9 @@ SIGNATURES = {
     "nsof_accum_frames_f64_p": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _ap, _vp, _vp]),
     "nsof_accum_frames_f64_p_dev": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _d, _ap, _vp, _vp, _vp]),
     "nsof_accum_destroy": (None, [_vp]),
+    "nsof_accum_set_param_maps": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_vp)]),
+    "nsof_accum_read_param_map": (_i, [_vp, _i, _vp]),
+    "nsof_accum_param_map_mask": (_i, [_vp, C.POINTER(C.c_uint)]),
     "nsof_accum_set_dense": (_i, [_vp, _i]),
     "nsof_accum_set_event_threshold": (_i, [_vp, _i]),
     "nsof_accum_get_event_threshold": (_i, [_vp, _vp]),

@@ -74,6 +74,66 @@ def event_threshold(theta_events=None, version=1):
     return int(th)
 
 
+def param_maps_arg(param_maps, shape=None):
+    """Per-pixel parameter maps as the library takes them: ``[(key, float32 [H][W])]`` in ``_PARAM_KEYS`` order (``None`` or an
+    empty mapping: ``[]``).  Raises ``NsofValueError`` -- before any context exists or the library is called -- for a key that
+    is no device parameter (``won`` / ``woff``, ``dt`` and ``refractory_us`` stay scalars), a plane that is not ``shape`` (where
+    given) and a non-finite value.  The domain of each value (``voff < 0 < von``, ...) is the library's check."""
+    if param_maps is None:
+        return []
+    try:
+        items = dict(param_maps.items())
+    except AttributeError:
+        raise NsofValueError("param_maps must be a mapping of parameter name -> [H][W] array") from None
+    unknown = [k for k in items if k not in _PARAM_KEYS]
+    if unknown:
+        raise NsofValueError(f"param_maps: {unknown[0]!r} is not a per-pixel parameter (one of {', '.join(_PARAM_KEYS)})")
+    out = []
+    for k in _PARAM_KEYS:
+        if k not in items:
+            continue
+        try:
+            a = np.ascontiguousarray(items[k], np.float32)
+        except (TypeError, ValueError):
+            raise NsofValueError(f"param_maps[{k!r}] is not an array of numbers") from None
+        if a.ndim != 2 or (shape is not None and a.shape != tuple(shape)):
+            raise NsofValueError(f"param_maps[{k!r}] is {a.shape}, the array is {tuple(shape) if shape is not None else '[H][W]'}",
+                                 _lib.NSOF_ESHAPE)
+        if not np.isfinite(a).all():
+            r, c = (int(v) for v in np.argwhere(~np.isfinite(a))[0])
+            raise NsofValueError(f"param_maps[{k!r}][{r}][{c}] = {a[r, c]} is not finite")
+        out.append((k, a))
+    return out
+
+
+def variability_maps(H, W, rel_sigma, params=None, seed=0):  # noqa: N803
+    """Device-to-device variability as parameter maps (host helper; the kernels know nothing about it): for every key of
+    ``rel_sigma`` the plane ``float32(p[key] * (1 + rel_sigma[key] * N(0, 1)))`` with ``p`` = ``params`` (``None``: ``PARAMS``),
+    drawn from ``np.random.default_rng(seed)`` in ``_PARAM_KEYS`` order -- the result does not depend on the mapping's order --
+    and clipped into the model's domain: ``voff`` / ``von`` / ``koff`` / ``kon`` keep their sign, ``son`` / ``soff`` / ``wini``
+    stay in [0, 1], ``Ron`` / ``Roff`` at least the smallest positive normal float32."""
+    p = PARAMS if params is None else params
+    unknown = [k for k in rel_sigma if k not in _PARAM_KEYS]
+    if unknown:
+        raise NsofValueError(f"variability_maps: {unknown[0]!r} is not a per-pixel parameter")
+    rng = np.random.default_rng(seed)
+    tiny = float(np.finfo(np.float32).tiny)
+    out = {}
+    for k in _PARAM_KEYS:
+        if k not in rel_sigma:
+            continue
+        nominal = _number(k, p[k])
+        v = nominal * (1.0 + _number(f"rel_sigma[{k!r}]", rel_sigma[k]) * rng.standard_normal((int(H), int(W))))
+        if k in ("voff", "von", "koff", "kon") and nominal != 0:
+            v = np.maximum(v, tiny) if nominal > 0 else np.minimum(v, -tiny)
+        elif k in ("son", "soff", "wini"):
+            v = np.clip(v, 0.0, 1.0)
+        elif k in ("Ron", "Roff"):
+            v = np.maximum(v, tiny)
+        out[k] = v.astype(np.float32)
+    return out
+
+
 def _params_dict(ap):
     """(params dict with the reference's keys, dt, refractory_us) of an ``AccumParams`` -- what the metadata file records."""
     d = {k: getattr(ap, k) for k in _PARAM_KEYS}
@@ -198,12 +258,15 @@ class Accumulator:
     (``None``: the module's ``PARAMS`` / ``DT`` / ``REFRACTORY_US``); they are fixed for the accumulator's life and read
     back as ``self.params`` / ``self.dt`` / ``self.refractory_us``.  ``theta_events`` (``None``: ``THETA_EVENTS``) is scheme
     1's event-count threshold: a pixel pulses in a slice that holds at least that many of its events (read back as
-    ``self.theta_events``)."""
+    ``self.theta_events``).  ``param_maps`` (a mapping key of ``PARAMS`` -> array-like [H][W], read as float32) makes those
+    parameters per pixel -- an array of devices that differ (``variability_maps``); the other keys keep their scalar, and
+    ``self.param_maps`` reads the planes back."""
 
     def __init__(self, height, width, version=1, polarity="split", active_v=-8.0, silent_v=0.0, *, ctx=None,
-                 dense=None, frames_path=None, params=None, dt=None, refractory_us=None, theta_events=None):
+                 dense=None, frames_path=None, params=None, dt=None, refractory_us=None, theta_events=None, param_maps=None):
         ap = accum_params(params, dt, refractory_us)
         theta = event_threshold(theta_events, version)
+        maps = param_maps_arg(param_maps, (int(height), int(width)))
         if version not in (1, 2):
             raise NsofValueError("version must be 1 or 2")
         if polarity not in ("split", "magnitude"):
@@ -226,6 +289,34 @@ class Accumulator:
         if frames_path is not None:   # run_frames: "tiles" (default where it applies) or "copy_patch"
             self.ctx.check(self.ctx._lib.nsof_accum_set_frames_path(self._p, {"tiles": 0, "copy_patch": 1}[frames_path]),
                            "accum_set_frames_path")
+        if maps:
+            try:
+                self._set_maps(maps)
+            except Exception:
+                self.close()
+                raise
+
+    def _set_maps(self, maps):
+        keys = (C.c_int * len(maps))(*[_PARAM_KEYS.index(k) for k, _ in maps])
+        planes = (C.c_void_p * len(maps))(*[a.ctypes.data for _, a in maps])
+        self.ctx.check(self.ctx._lib.nsof_accum_set_param_maps(self._p, len(maps), keys, planes), "accum_set_param_maps")
+
+    def set_param_maps(self, param_maps):
+        """Replace the per-pixel parameter maps (``None`` or empty: back to the uniform device) and reset the array
+        (``nsof_accum_set_param_maps``); accepted only before the first slice or right after ``reset()``."""
+        self._set_maps(param_maps_arg(param_maps, (self.H, self.W)))
+
+    @property
+    def param_maps(self):
+        """The per-pixel parameter maps in use, ``{key: float32 [H][W]}`` (empty for a uniform device)."""
+        mask = C.c_uint()
+        self.ctx.check(self.ctx._lib.nsof_accum_param_map_mask(self._p, C.byref(mask)), "accum_param_map_mask")
+        out = {}
+        for i, k in enumerate(_PARAM_KEYS):
+            if mask.value >> i & 1:
+                out[k] = np.empty((self.H, self.W), np.float32)
+                self.ctx.check(self.ctx._lib.nsof_accum_read_param_map(self._p, i, out[k].ctypes.data), "accum_read_param_map")
+        return out
 
     @property
     def theta_events(self):
@@ -393,7 +484,7 @@ class Accumulator:
 
 def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, save_video=False, polarity="split",
              *, sensor_size=None, out_prefix=None, ctx=None, dense=None, params=None, dt=None, refractory_us=None,
-             theta_events=None):
+             theta_events=None, param_maps=None):
     """``simulate`` of event_mem_sim.py:164-286.
 
     ``events``: an HDF5 path with a ``/CD/events`` group (as the reference) or a tuple ``(x, y, p, t)`` of arrays.
@@ -404,7 +495,8 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
     ``params`` / ``dt`` / ``refractory_us``: the device model, as for ``Accumulator`` (the reference reads its module
     globals ``PARAMS`` / ``REFRACTORY_US`` and ``update_state``'s default ``dt``).  ``theta_events``: scheme 1's event-count
     threshold (the reference's module global ``THETA_EVENTS``; ``None`` = this module's).  The metadata file records the
-    values that were used.
+    values that were used.  ``param_maps``: per-pixel parameters, as for ``Accumulator``; the ``.npz`` then also holds the planes
+    as ``map_<key>`` and the metadata lists their keys as ``param_maps``.
     """
     if version not in (1, 2):
         raise NsofValueError("version must be 1 or 2")
@@ -412,6 +504,7 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
         raise NsofValueError("polarity must be 'split' or 'magnitude'")
     accum_params(params, dt, refractory_us)   # a missing key is reported before the events are read
     theta = event_threshold(theta_events, version)
+    maps = param_maps_arg(param_maps)   # ... and so are a wrong key or a non-finite value (the shape: once the sensor is known)
     h5_path = None
     if isinstance(events, (str, Path)):
         h5_path = Path(events)
@@ -425,11 +518,13 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
             H, W = int(y.max()) + 1, int(x.max()) + 1  # noqa: N806  (event_mem_sim.py:74)
         else:
             H, W = sensor_size  # noqa: N806
+    maps = param_maps_arg(dict(maps), (int(H), int(W)))
     idx = slice_index_array(t, slice_us)
     nslices = max(len(idx) - 1, 0)
     every = max(1, nslices // 100)
     acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, dense=dense, params=params, dt=dt,
-                      refractory_us=refractory_us, **({} if theta_events is None else dict(theta_events=theta)))
+                      refractory_us=refractory_us, **({} if theta_events is None else dict(theta_events=theta)),
+                      **(dict(param_maps=dict(maps)) if maps else {}))
     # what the metadata file records: the model this run uses, written with the caller's own numbers (the accumulator holds
     # the same values as doubles; the defaults stay the integers the reference writes), plus won / woff, which nothing reads
     src = PARAMS if params is None else params
@@ -445,7 +540,7 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
         acc.close()
     prefix = Path(out_prefix) if out_prefix is not None else h5_path
     if prefix is not None:
-        _save_outputs(prefix, out, version, slice_us, polarity, h5_path, *used, theta_events=theta)
+        _save_outputs(prefix, out, version, slice_us, polarity, h5_path, *used, theta_events=theta, param_maps=maps)
     return out
 
 
@@ -496,16 +591,17 @@ def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.
 
 
 def _save_outputs(prefix, out, version, slice_us, polarity, h5_path, params=None, dt=None, refractory_us=None,
-                  theta_events=None):
+                  theta_events=None, param_maps=()):
     """File set of event_mem_sim.py:289-322 (npz keys ``w_final`` / ``resistances``; json.gz metadata).  The metadata holds
     the parameters, dt, refractory time and event threshold the run USED (the reference writes its module globals, which a dt overridden
-    through ``update_state``'s default does not reach)."""
+    through ``update_state``'s default does not reach).  ``param_maps`` (``[(key, plane)]``): stored as ``map_<key>`` next to
+    ``w_final`` and listed in the metadata; without maps neither file changes."""
     params = dict(PARAMS) if params is None else params
     dt = DT if dt is None else dt
     refractory_us = REFRACTORY_US if refractory_us is None else refractory_us
     theta_events = THETA_EVENTS if theta_events is None else theta_events
     np.savez_compressed(prefix.with_suffix(f".V{version}.npz"), w_final=out["w_final"],
-                        resistances=out["resistances"].astype(np.float32))
+                        resistances=out["resistances"].astype(np.float32), **{f"map_{k}": a for k, a in param_maps})
     if version == 2:
         if "w_final_b" in out:
             np.savez_compressed(prefix.with_suffix(".V2_b.npz"), w_final=out["w_final_b"],
@@ -516,5 +612,7 @@ def _save_outputs(prefix, out, version, slice_us, polarity, h5_path, params=None
                 scheme="boxcar" if version == 1 else "dc_bias_overlay", polarity=polarity if version == 2 else None,
                 theta_events=theta_events if version == 1 else None,
                 refractory_us=refractory_us if version == 2 else None, event_file=str(h5_path or prefix))
+    if param_maps:
+        meta["param_maps"] = [k for k, _ in param_maps]
     with gzip.open(prefix.with_suffix(f".V{version}.json.gz"), "wt") as fp:
         json.dump(meta, fp, indent=2)
