@@ -448,9 +448,9 @@ int nsof_accum_get_params(const nsof_accum* acc, nsof_accum_params* out);
  * pixel; otherwise every advancing call takes the every-pixel pass with the per-pixel silent drive, whatever force_dense.
  * nsof_accum_run_frames on a mapped accumulator takes copy + patch where it applies and n_frames x nsof_accum_run_surface
  * otherwise; the tile walk has no mapped form and is routed around (nsof_accum_set_frames_path changes nothing then).
- * Out of scope: the element-wise nsof_accum_update_state*_dev / nsof_accum_resistance*_dev entries and the float64
- * frame-driven path nsof_accum_frames_f64* (one device per call), row-band sharding in nsof/dist.py (a band factory takes
- * no maps), the linear resistance map, per-pixel thresholds. */
+ * Out of scope: the element-wise nsof_accum_update_state*_dev / nsof_accum_resistance*_dev entries (one device per call),
+ * row-band sharding in nsof/dist.py (a band factory takes no maps), the linear resistance map, per-pixel thresholds.  The
+ * float64 frame-driven path has maps of its own: nsof_accum_frames_f64_maps_dev. */
 enum {
     NSOF_ACCUM_KEY_ALPHAOFF = 0, NSOF_ACCUM_KEY_ALPHAON, NSOF_ACCUM_KEY_VOFF, NSOF_ACCUM_KEY_VON, NSOF_ACCUM_KEY_KOFF,
     NSOF_ACCUM_KEY_KON, NSOF_ACCUM_KEY_SON, NSOF_ACCUM_KEY_SOFF, NSOF_ACCUM_KEY_BON, NSOF_ACCUM_KEY_BOFF, NSOF_ACCUM_KEY_RON,
@@ -590,6 +590,37 @@ int nsof_accum_frames_f64_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames,
 int nsof_accum_frames_f64_p_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
                                 int n_sub_steps, double th1, double th2, double v_ds, const nsof_accum_params* params,
                                 double* d_w, double* d_res, double* d_current);
+/* The array run with a device model per cell AND per trial: device-to-device variability of the physical gating array, all
+ * n_trials Monte-Carlo trials of a study in one launch.  keys[j] names a field of nsof_accum_params (NSOF_ACCUM_KEY_*),
+ * planes[j] is its HOST float64 plane (not retained) of plane_trials[j] trials: n_trials ([T][H][W]) or 1 ([H][W], shared by
+ * all trials).  A mapped key takes the value of its (trial, cell), every other key the scalar of params (NULL = defaults); dt,
+ * th1, th2, v_ds and n_sub_steps stay scalars.  Values are read as doubles (a float32 plane widened is exact).  The frames
+ * d_imgs [n_frames][H][W] are shared by the trials; d_w [T][H][W], d_res [T][n_frames][H][W] (may be NULL), d_current
+ * [T][n_frames - 1][H][W] (may be NULL), each trial laid out as nsof_accum_frames_f64_dev lays out its one.
+ * Per (trial, cell) the arithmetic is the uniform entry's with that cell's fields -- the same device functions in the same
+ * order -- and the two values the uniform entry forms on the host are formed on the host here too, per (trial, cell), and
+ * uploaded as planes: lambda = log(Roff / Ron) and the initial resistance Ron / exp(-lambda * (1 - wini)).  So a cell's w,
+ * res and current equal, bit for bit, nsof_accum_frames_f64_p_dev's at that cell's parameters; constant planes equal to the
+ * scalars give the uniform entry's bits; with n_maps == 0, n_trials == 1 and d_res given the call IS that entry.
+ * Thread g of the launch is trial g / (H * W), cell g % (H * W), in workgroups of 64.  The planes go up through a buffer of
+ * the context, stream-ordered: the call waits only for its own previous upload to have left the pinned copy, or to grow it;
+ * otherwise asynchronous on the context's stream.
+ * NSOF_EINVAL, nothing uploaded, launched or written: n_trials < 1, a key outside [0, NSOF_ACCUM_KEY_COUNT) or given twice, a
+ * NULL plane, plane_trials[j] other than 1 or n_trials, and any value outside the domain nsof_accum_create_p checks
+ * (non-finite as double or as float32, voff >= 0, von <= 0, son / soff / wini outside [0, 1], Ron or Roff <= 0, ln(Roff /
+ * Ron) not finite) -- the message naming key, trial, row, column and value of the first one, planes in the order given.
+ * NSOF_EUNSUPPORTED: n_trials * H * W beyond one launch's index range.
+ * Out of scope: per-cell th1 / th2 / dt, the linear resistance map, float32 planes on the device. */
+int nsof_accum_frames_f64_maps_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
+                                   int n_sub_steps, double th1, double th2, double v_ds, const nsof_accum_params* params,
+                                   int n_trials, int n_maps, const int* keys, const double* const* planes,
+                                   const int* plane_trials, double* d_w, double* d_res, double* d_current);
+/* The same with HOST frames and outputs (w_out [T][H][W], res_out [T][n_frames][H][W]): upload, the one launch, download;
+ * the device entry's bits.  Synchronous. */
+int nsof_accum_frames_f64_maps(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
+                               int n_sub_steps, double th1, double th2, const nsof_accum_params* params, int n_trials,
+                               int n_maps, const int* keys, const double* const* planes, const int* plane_trials,
+                               double* w_out, double* res_out);
 /* compress_image of the same script (:111-121) for a stack of 8-bit DEVICE frames: imresize(im2double(frame), [out_h
  * out_w], 'lanczos3') of n_frames frames into d_out [n_frames][out_h][out_w] (DEVICE, dense float64).  d_frames points
  * at the first pixel of the region to compress -- a crop is a pointer offset plus width and height -- with row_stride and
@@ -642,6 +673,16 @@ int nsof_roi_from_surface_dev(nsof_ctx* ctx, const double* d_current, int n_maps
                               int frame_w, int frame_h, int memsize, int thres, int extend_left, int extend_right,
                               int extend_upper, int extend_lower, int connectivity, int flag, int max_rects, int* d_counts,
                               int* d_rects, unsigned char* d_gray);
+/* Gate statistics of a variability study (the stacks nsof_accum_frames_f64_maps_dev writes): d_current [n_trials][n_frames]
+ * [rows][cols] are the device currents of the trials, d_nominal [n_frames][rows][cols] those of the nominal array.  A cell
+ * is gated when its gating value -- the 8-bit value nsof_roi_from_surface_dev forms, the bytes of its d_gray -- is >= thres.
+ * d_counts int32 [n_frames][rows][cols]: the number of trials in which the cell is gated (gate probability = count /
+ * n_trials); d_flips int32 [n_trials][n_frames]: the number of cells of that trial's map whose gated bit differs from the
+ * nominal's.  Integer sums without atomics: exact, whatever the order.  One launch, any n_trials, maps from one cell on;
+ * all DEVICE memory, asynchronous on the context's stream.  NSOF_EUNSUPPORTED: a map above 2^27 cells, or sizes beyond one
+ * launch. */
+int nsof_gate_stats_dev(nsof_ctx* ctx, const double* d_current, const double* d_nominal, int n_trials, int n_frames, int rows,
+                        int cols, int thres, int* d_counts, int* d_flips);
 
 /* ---- next: motion-segmentation head on the flow field --------------------- */
 /* Replaces, in /root/reference/optical_flow_seg.py, the chain

@@ -22,6 +22,7 @@
 //    within 2^-43 of a rounding midpoint, and on those too as measured (tests/test_accum_cr_gpu.py;
 //    the reference's NumPy uses SIMD pow/exp that are themselves 1-4 ulp off libm, hence the
 //    tolerances against its goldens in tests/test_accum_gpu.py).
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -676,6 +677,44 @@ __global__ __launch_bounds__(64) void k_frames_run(const double* __restrict__ im
         if (current) current[(size_t)f * n + i] = v_ds / r;
     }
     w[i] = ww;
+}
+
+// The same run with a device model per (trial, cell) -- nsof_accum_frames_f64_maps_dev: thread g is trial g / n, cell g % n.
+// Every field of a thread's DevD is a scalar of the call or that thread's element of a plane [1 or n_trials][n] (trial
+// stride 0: shared by the trials); lambda and the initial resistance r0 are planes too, formed on the host with the
+// library's log / exp as the uniform entry forms its two scalars.  From there on the loop is k_frames_run's, statement for
+// statement, so a thread's bits are the uniform kernel's at that thread's parameters.  imgs [n_frames][n] is shared by the
+// trials; w [T][n], res [T][n_frames][n] (optional), current [T][n_frames - 1][n] (optional).
+enum { FM_VOFF, FM_VON, FM_KOFF, FM_KON, FM_SON, FM_SOFF, FM_BON, FM_BOFF, FM_ALPHAOFF, FM_ALPHAON, FM_RON, FM_LAMBDA, FM_WINI, FM_R0, FM_COUNT };
+struct FrameMaps {
+    const double* plane[FM_COUNT];   // nullptr: the field is the scalar
+    size_t stride[FM_COUNT];         // between the trials of a plane: 0 or n
+    double scalar[FM_COUNT];
+};
+__global__ __launch_bounds__(64) void k_frames_run_maps(const double* __restrict__ imgs, int n_frames, double* __restrict__ w,
+                                                         double* __restrict__ res, double* __restrict__ current, size_t n,
+                                                         size_t total, double dts, int n_sub, double th1, double th2, FrameMaps m,
+                                                         double v_ds)
+{
+    const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (g >= total) return;
+    const size_t trial = g / n, i = g - trial * n;
+    auto get = [&](int s) { return m.plane[s] ? m.plane[s][trial * m.stride[s] + i] : m.scalar[s]; };
+    const DevD p{get(FM_VOFF), get(FM_VON), get(FM_KOFF), get(FM_KON), get(FM_SON), get(FM_SOFF), get(FM_BON), get(FM_BOFF),
+                 get(FM_ALPHAOFF), get(FM_ALPHAON), get(FM_RON), get(FM_LAMBDA), get(FM_WINI)};
+    double* const rt = res ? res + trial * (size_t)n_frames * n : nullptr;
+    double* const ct = current ? current + trial * (size_t)(n_frames - 1) * n : nullptr;
+    double ww = p.wini, b = imgs[i];
+    if (rt) rt[i] = get(FM_R0);
+    for (int f = 0; f + 1 < n_frames; f++) {
+        const double a = b;
+        b = imgs[(size_t)(f + 1) * n + i];
+        ww = frame_pair(a, b, ww, dts, n_sub, th1, th2, p);
+        const double r = p.ron / exp(-p.lambda * (1 - ww));
+        if (rt) rt[(size_t)(f + 1) * n + i] = r;
+        if (ct) ct[(size_t)f * n + i] = v_ds / r;
+    }
+    w[g] = ww;
 }
 
 // Temporal-prior surface as an 8-bit frame.
@@ -2050,5 +2089,189 @@ extern "C" int nsof_accum_frames_f64_p_dev(nsof_ctx* ctx, const double* d_imgs, 
                            md.ron / std::exp(-md.lambda * (1 - md.wini)), v_ds);
     });
     NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
+}
+
+// ---- the frame-driven run with a device model per (trial, cell) ------------------------------------------------------
+namespace {
+
+const char* const kKeyNames[NSOF_ACCUM_KEY_COUNT] = {"alphaoff", "alphaon", "voff", "von", "koff", "kon", "son", "soff", "bon",
+                                                     "boff", "Ron", "Roff", "wini"};
+
+// The planes of a mapped frame-driven call, per key (nullptr: the key keeps its scalar) with their trial counts.
+struct FramePlanes {
+    const double* plane[NSOF_ACCUM_KEY_COUNT] = {};
+    int trials[NSOF_ACCUM_KEY_COUNT] = {};
+    bool any = false;
+};
+
+// Everything that can refuse a mapped frame-driven call, decided on the host before anything is uploaded, launched or
+// written: the arguments, the scalars (model_of) and every value of every plane against model_of's domain -- the tests
+// on the float32 value included, so a plane is refused exactly where the uniform entry refuses that scalar.
+int frame_planes_of(nsof_ctx* ctx, int n_frames, int height, int width, int n_sub_steps, const nsof_accum_params* params,
+                    int n_trials, int n_maps, const int* keys, const double* const* planes, const int* plane_trials, Model* model,
+                    FramePlanes* fp)
+{
+    if (n_frames < 1 || height < 1 || width < 1 || n_sub_steps < 1)
+        return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
+    if (n_trials < 1) return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: %d trials (at least 1)", n_trials);
+    if (n_maps < 0 || n_maps > NSOF_ACCUM_KEY_COUNT || (n_maps > 0 && (!keys || !planes || !plane_trials)))
+        return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: %d maps (0..%d, with their keys, planes and trial counts)", n_maps,
+                              NSOF_ACCUM_KEY_COUNT);
+    for (int j = 0; j < n_maps; j++) {
+        const int k = keys[j];
+        if (k < 0 || k >= NSOF_ACCUM_KEY_COUNT)
+            return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: key %d is no parameter (0..%d)", k, NSOF_ACCUM_KEY_COUNT - 1);
+        if (!planes[j]) return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: the plane of %s is NULL", kKeyNames[k]);
+        if (fp->plane[k]) return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: %s given twice", kKeyNames[k]);
+        if (plane_trials[j] != 1 && plane_trials[j] != n_trials)
+            return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: the plane of %s holds %d trials (1 or %d)", kKeyNames[k],
+                                  plane_trials[j], n_trials);
+        fp->plane[k] = planes[j];
+        fp->trials[k] = plane_trials[j];
+        fp->any = true;
+    }
+    if (int rc = model_of(ctx, params, model)) return rc;
+    const size_t npx = (size_t)height * width;
+    for (int j = 0; j < n_maps; j++) {
+        const int k = keys[j];
+        const double* q = planes[j];
+        for (size_t e = 0; e < (size_t)plane_trials[j] * npx; e++) {
+            const double v = q[e];
+            const float vf = (float)v;
+            const char* why = nullptr;
+            if (!std::isfinite(v) || !std::isfinite(vf)) why = "is not a finite float32";
+            else if (k == NSOF_ACCUM_KEY_VOFF && !(v < 0 && vf < 0.f)) why = "must be negative (voff < 0 < von)";
+            else if (k == NSOF_ACCUM_KEY_VON && !(v > 0 && vf > 0.f)) why = "must be positive (voff < 0 < von)";
+            else if ((k == NSOF_ACCUM_KEY_SON || k == NSOF_ACCUM_KEY_SOFF || k == NSOF_ACCUM_KEY_WINI) && !(v >= 0 && v <= 1)) why = "lies outside [0, 1]";
+            else if (k == NSOF_ACCUM_KEY_RON && !(v > 0 && vf > 0.f)) why = "must be positive";
+            else if (k == NSOF_ACCUM_KEY_ROFF && !(v > 0)) why = "must be positive";
+            if (why)
+                return nsof_set_error(ctx, NSOF_EINVAL, "frame map %s: trial %zu, row %zu, column %zu = %g %s", kKeyNames[k], e / npx,
+                                      e % npx / (size_t)width, e % (size_t)width, v, why);
+        }
+    }
+    return NSOF_OK;
+}
+
+}  // namespace
+
+extern "C" int nsof_accum_frames_f64_maps_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
+                                              int n_sub_steps, double th1, double th2, double v_ds, const nsof_accum_params* params,
+                                              int n_trials, int n_maps, const int* keys, const double* const* planes,
+                                              const int* plane_trials, double* d_w, double* d_res, double* d_current)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!d_imgs || !d_w) return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
+    Model model;
+    FramePlanes fp;
+    if (int rc = frame_planes_of(ctx, n_frames, height, width, n_sub_steps, params, n_trials, n_maps, keys, planes, plane_trials,
+                                 &model, &fp))
+        return rc;
+    if (!fp.any && n_trials == 1 && d_res)   // one device, one trial: the uniform entry
+        return nsof_accum_frames_f64_p_dev(ctx, d_imgs, n_frames, height, width, dt, n_sub_steps, th1, th2, v_ds, params, d_w,
+                                           d_res, d_current);
+    const size_t npx = (size_t)height * width;
+    if (npx > (0xffffffffull - 63) / (size_t)n_trials)
+        return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "%d trials of %zu cells: too large for one launch", n_trials, npx);
+    const size_t total = npx * (size_t)n_trials;
+    // lambda and r0 per (trial, cell) wherever Ron, Roff or wini is a plane: the host's log / exp, as the uniform entry's
+    const double *p_ron = fp.plane[NSOF_ACCUM_KEY_RON], *p_roff = fp.plane[NSOF_ACCUM_KEY_ROFF], *p_wini = fp.plane[NSOF_ACCUM_KEY_WINI];
+    const int t_lam = (p_ron || p_roff) ? std::max(fp.trials[NSOF_ACCUM_KEY_RON], fp.trials[NSOF_ACCUM_KEY_ROFF]) : 0;
+    const int t_r0 = (t_lam || p_wini) ? std::max(t_lam, fp.trials[NSOF_ACCUM_KEY_WINI]) : 0;
+    const nsof_accum_params& sp = model.prm;
+    auto at = [&](int k, double scalar, size_t t, size_t i) {
+        return fp.plane[k] ? fp.plane[k][(fp.trials[k] == 1 ? 0 : t) * npx + i] : scalar;
+    };
+    auto lambda_at = [&](size_t t, size_t i) {
+        return std::log(at(NSOF_ACCUM_KEY_ROFF, sp.Roff, t, i) / at(NSOF_ACCUM_KEY_RON, sp.Ron, t, i));
+    };
+    for (size_t e = 0; e < (size_t)t_lam * npx; e++)
+        if (!std::isfinite(lambda_at(e / npx, e % npx)))
+            return nsof_set_error(ctx, NSOF_EINVAL, "frame maps Ron / Roff: ln(Roff / Ron) is not finite at trial %zu, row %zu, column %zu",
+                                  e / npx, e % npx / (size_t)width, e % (size_t)width);
+    // slot -> key of nsof_accum_params (lambda and r0 have none)
+    static const int key_of[FM_COUNT] = {NSOF_ACCUM_KEY_VOFF, NSOF_ACCUM_KEY_VON, NSOF_ACCUM_KEY_KOFF, NSOF_ACCUM_KEY_KON,
+                                         NSOF_ACCUM_KEY_SON, NSOF_ACCUM_KEY_SOFF, NSOF_ACCUM_KEY_BON, NSOF_ACCUM_KEY_BOFF,
+                                         NSOF_ACCUM_KEY_ALPHAOFF, NSOF_ACCUM_KEY_ALPHAON, NSOF_ACCUM_KEY_RON, -1,
+                                         NSOF_ACCUM_KEY_WINI, -1};
+    const DevD& md = model.d;
+    FrameMaps fm;
+    const double scalars[FM_COUNT] = {md.voff, md.von, md.koff, md.kon, md.son, md.soff, md.bon, md.boff, md.alphaoff, md.alphaon,
+                                      md.ron, md.lambda, md.wini, md.ron / std::exp(-md.lambda * (1 - md.wini))};
+    size_t off[FM_COUNT], doubles = 0;
+    int trials[FM_COUNT];
+    for (int s = 0; s < FM_COUNT; s++) {
+        trials[s] = s == FM_LAMBDA ? t_lam : (s == FM_R0 ? t_r0 : fp.trials[key_of[s]]);
+        off[s] = doubles;
+        doubles += (size_t)trials[s] * npx;
+    }
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    const double* d_planes = nullptr;
+    if (doubles) {   // one table, through the pinned copy: waits for this entry's previous upload only (or to grow)
+        const size_t bytes = doubles * sizeof(double);
+        if (int rc = ctx->frame_maps.stage(ctx, bytes, (bytes + bytes / 2 + 4095) & ~(size_t)4095)) return rc;
+        double* h = (double*)ctx->frame_maps.h.p;
+        for (int s = 0; s < FM_COUNT; s++) {
+            double* dst = h + off[s];
+            const size_t cnt = (size_t)trials[s] * npx;
+            if (s == FM_LAMBDA) {
+                for (size_t e = 0; e < cnt; e++) dst[e] = lambda_at(e / npx, e % npx);
+            } else if (s == FM_R0) {
+                for (size_t e = 0; e < cnt; e++) {
+                    const size_t t = e / npx, i = e % npx;
+                    const double lam = t_lam ? h[off[FM_LAMBDA] + (t_lam == 1 ? 0 : t) * npx + i] : md.lambda;
+                    dst[e] = at(NSOF_ACCUM_KEY_RON, sp.Ron, t, i) / std::exp(-lam * (1 - at(NSOF_ACCUM_KEY_WINI, sp.wini, t, i)));
+                }
+            } else if (cnt) {
+                memcpy(dst, fp.plane[key_of[s]], cnt * sizeof(double));
+            }
+        }
+        d_planes = (const double*)ctx->frame_maps.upload(ctx, bytes);
+        if (!d_planes) return NSOF_EDEVICE;
+    }
+    for (int s = 0; s < FM_COUNT; s++) {
+        fm.plane[s] = trials[s] ? d_planes + off[s] : nullptr;
+        fm.stride[s] = trials[s] > 1 ? npx : 0;
+        fm.scalar[s] = scalars[s];
+    }
+    hipLaunchKernelGGL(k_frames_run_maps, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, d_imgs, n_frames, d_w, d_res,
+                       d_current, npx, total, dt / n_sub_steps, n_sub_steps, th1, th2, fm, v_ds);
+    NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
+}
+
+// The same on HOST frames and outputs: upload, the one launch, download -- the device entry's bits.
+extern "C" int nsof_accum_frames_f64_maps(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
+                                          int n_sub_steps, double th1, double th2, const nsof_accum_params* params, int n_trials,
+                                          int n_maps, const int* keys, const double* const* planes, const int* plane_trials,
+                                          double* w_out, double* res_out)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!imgs || !w_out || !res_out) return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
+    {   // refuse before anything is allocated or copied
+        Model model;
+        FramePlanes fp;
+        if (int rc = frame_planes_of(ctx, n_frames, height, width, n_sub_steps, params, n_trials, n_maps, keys, planes, plane_trials,
+                                     &model, &fp))
+            return rc;
+    }
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t npx = (size_t)height * width, nw = npx * (size_t)n_trials, nr = nw * (size_t)n_frames;
+    nsof_dev_buf<double> img_buf, w_buf, res_buf;
+    int rc = img_buf.reserve(ctx, (size_t)n_frames * npx * 8);
+    if (!rc) rc = w_buf.reserve(ctx, nw * 8);
+    if (!rc) rc = res_buf.reserve(ctx, nr * 8);
+    if (rc) return rc;
+    NSOF_HIP(ctx, hipMemcpyAsync(img_buf.p, imgs, (size_t)n_frames * npx * 8, hipMemcpyHostToDevice, ctx->stream));
+    rc = nsof_accum_frames_f64_maps_dev(ctx, img_buf.p, n_frames, height, width, dt, n_sub_steps, th1, th2, 1.0, params, n_trials,
+                                        n_maps, keys, planes, plane_trials, w_buf.p, res_buf.p, nullptr);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(w_out, w_buf.p, nw * 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(res_out, res_buf.p, nr * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);   // also before the buffers go
+    if (rc) return rc;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return nsof_set_error(ctx, NSOF_EDEVICE, "frame accumulator: %s", hipGetErrorString(e));
     return NSOF_OK;
 }

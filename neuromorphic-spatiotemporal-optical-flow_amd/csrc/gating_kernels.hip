@@ -26,6 +26,14 @@ __device__ __forceinline__ unsigned long long wave_or(unsigned long long v)
     return v;
 }
 
+// The 8-bit gating value of a device current (optical_flow_seg.py:426-431): every gating kernel's one expression.
+__device__ __forceinline__ int gate_gray(double current)
+{
+    double g = -3366.0 / log10(current) - 306.0;
+    g = g < 0.0 ? 0.0 : (g > 255.0 ? 255.0 : g);        // NaN (I <= 0) compares false twice and casts to 0
+    return (g == g) ? (int)(unsigned char)g : 0;
+}
+
 __global__ __launch_bounds__(64) void k_roi_gate(const double* __restrict__ cur, size_t map_stride, int rows, int cols, int fw,
                                                  int fh, int ms, int thres, int el, int er, int eu, int ed, int conn8, int flag,
                                                  int cap, int* __restrict__ counts, int* __restrict__ rects,
@@ -36,9 +44,7 @@ __global__ __launch_bounds__(64) void k_roi_gate(const double* __restrict__ cur,
     unsigned long long R = 0;
     if (lane < rows) {
         for (int c = 0; c < cols; c++) {
-            double g = -3366.0 / log10(m[(size_t)lane * cols + c]) - 306.0;
-            g = g < 0.0 ? 0.0 : (g > 255.0 ? 255.0 : g);        // NaN (I <= 0) compares false twice and casts to 0
-            const int gi = (g == g) ? (int)(unsigned char)g : 0;
+            const int gi = gate_gray(m[(size_t)lane * cols + c]);
             if (gray) gray[((size_t)k * rows + lane) * cols + c] = (unsigned char)gi;
             if (gi >= thres) R |= 1ull << c;
         }
@@ -191,9 +197,7 @@ __global__ __launch_bounds__(CCL_TILE) void k_ccl_init(const double* __restrict_
     const int i = t * CCL_TILE + tid;
     bool on = false;
     if (i < ncell) {
-        double g = -3366.0 / log10(cur[(size_t)k * map_stride + i]) - 306.0;   // the expression of k_roi_gate
-        g = g < 0.0 ? 0.0 : (g > 255.0 ? 255.0 : g);        // NaN (I <= 0) compares false twice and casts to 0
-        const int gi = (g == g) ? (int)(unsigned char)g : 0;
+        const int gi = gate_gray(cur[(size_t)k * map_stride + i]);
         if (gray) gray[(size_t)k * ncell + i] = (unsigned char)gi;
         on = gi >= thres;
     }
@@ -361,7 +365,67 @@ __global__ __launch_bounds__(CCL_TILE) void k_ccl_emit(int* __restrict__ counts,
     }
 }
 
+// ---- gate statistics of a variability study (nsof_gate_stats_dev) ----------------------------------------------------
+// cur [T][F][ncell] are the stacks of T trials, nom [F][ncell] the nominal array's; gated <=> gate_gray(I) >= thres.  One
+// launch, two kinds of workgroup (the kind is uniform per workgroup), no atomics -- integer sums, so the result does not
+// depend on the order:
+//   workgroups [0, n_cnt)    64 consecutive (frame, cell) positions each; wave v counts the trials v, v + 4, ... of its
+//                            lane's position (coalesced over the positions), the four partial counts meet in LDS
+//   workgroups [n_cnt, ...)  four (trial, frame) pairs each, one per wave: the lanes stride over the cells, a ballot per
+//                            round counts the cells whose gated bit differs from the nominal's
+constexpr int GS_BLOCK = 256;
+__global__ __launch_bounds__(GS_BLOCK) void k_gate_stats(const double* __restrict__ cur, const double* __restrict__ nom, int n_trials,
+                                                         size_t n_pos /* F * ncell */, int ncell, size_t n_pairs /* T * F */,
+                                                         unsigned n_cnt, int thres, int* __restrict__ counts, int* __restrict__ flips)
+{
+    __shared__ int s_part[GS_BLOCK];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (blockIdx.x < n_cnt) {
+        const size_t pos = (size_t)blockIdx.x * 64 + lane;
+        int c = 0;
+        if (pos < n_pos)
+            for (int t = wave; t < n_trials; t += GS_BLOCK / 64) c += gate_gray(cur[(size_t)t * n_pos + pos]) >= thres;
+        s_part[tid] = c;
+        __syncthreads();
+        if (wave == 0 && pos < n_pos) counts[pos] = s_part[lane] + s_part[64 + lane] + s_part[128 + lane] + s_part[192 + lane];
+        return;
+    }
+    const size_t pair = (size_t)(blockIdx.x - n_cnt) * (GS_BLOCK / 64) + wave;   // t * F + f
+    if (pair >= n_pairs) return;                                                   // (wave-uniform)
+    const size_t F = n_pos / (size_t)ncell, f = pair % F;
+    const double* a = cur + pair * (size_t)ncell;
+    const double* b = nom + f * (size_t)ncell;
+    int n = 0;
+    for (int c0 = 0; c0 < ncell; c0 += 64) {
+        const int c = c0 + lane;
+        const bool differs = c < ncell && (gate_gray(a[c]) >= thres) != (gate_gray(b[c]) >= thres);
+        n += __popcll(__ballot(differs));
+    }
+    if (lane == 0) flips[pair] = n;
+}
+
 }  // namespace
+
+extern "C" int nsof_gate_stats_dev(nsof_ctx* ctx, const double* d_current, const double* d_nominal, int n_trials, int n_frames,
+                                   int rows, int cols, int thres, int* d_counts, int* d_flips)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!d_current || !d_nominal || !d_counts || !d_flips || n_trials < 1 || n_frames < 1 || rows < 1 || cols < 1)
+        return nsof_set_error(ctx, NSOF_EINVAL, "bad gate-statistics arguments");
+    if ((long long)rows * cols > (1ll << 27))
+        return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "gating map %d x %d exceeds 2^27 cells", rows, cols);
+    const int ncell = rows * cols;
+    const size_t n_pos = (size_t)n_frames * ncell, n_pairs = (size_t)n_trials * n_frames;
+    const size_t n_cnt = (n_pos + 63) / 64, n_flip = (n_pairs + GS_BLOCK / 64 - 1) / (GS_BLOCK / 64);
+    if (n_cnt + n_flip > 0x7fffffffull)
+        return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "%d trials of %d maps of %d cells: too large for one launch", n_trials,
+                              n_frames, ncell);
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_gate_stats, dim3((unsigned)(n_cnt + n_flip)), dim3(GS_BLOCK), 0, ctx->stream, d_current, d_nominal, n_trials,
+                       n_pos, ncell, n_pairs, (unsigned)n_cnt, thres, d_counts, d_flips);
+    NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
+}
 
 // Device twin of nsof_roi_from_surface for n_maps maps at once; everything stays on the context's stream, nothing is
 // synchronised.  d_gray (optional): the 8-bit gating maps, [n_maps][rows][cols].

@@ -103,6 +103,11 @@ SIGNATURES = {
     "nsof_accum_resistance_p_dev": (_i, [_vp, _ap, _vp, _vp, _sz]),
     "nsof_accum_frames_f64_p": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _ap, _vp, _vp]),
     "nsof_accum_frames_f64_p_dev": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _d, _ap, _vp, _vp, _vp]),
+    "nsof_accum_frames_f64_maps_dev": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _d, _ap, _i, _i, C.POINTER(_i), C.POINTER(_vp),
+                                            C.POINTER(_i), _vp, _vp, _vp]),
+    "nsof_accum_frames_f64_maps": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _ap, _i, _i, C.POINTER(_i), C.POINTER(_vp),
+                                        C.POINTER(_i), _vp, _vp]),
+    "nsof_gate_stats_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "nsof_accum_destroy": (None, [_vp]),
     "nsof_accum_set_param_maps": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_vp)]),
     "nsof_accum_read_param_map": (_i, [_vp, _i, _vp]),

@@ -106,12 +106,75 @@ def param_maps_arg(param_maps, shape=None):
     return out
 
 
-def variability_maps(H, W, rel_sigma, params=None, seed=0):  # noqa: N803
+def frame_param_maps_arg(param_maps, shape=None):
+    """Per-cell, per-trial parameter planes as the frame-driven entries take them (``nsof_accum_frames_f64_maps*``):
+    ``(n_trials, [(key, float64 [1 or n_trials][H][W])])`` in ``_PARAM_KEYS`` order.  A plane is ``[H][W]`` (shared by the
+    trials) or ``[T][H][W]`` (one per trial), float32 or float64 -- read as float64, a float32 plane widened is exact;
+    ``n_trials`` is the ``T`` of the 3-D planes, 1 when every plane is 2-D (or the mapping is empty).  Raises
+    ``NsofValueError`` -- before any context exists or the library is called -- for a key that is no device parameter, a
+    plane that is neither 2-D nor 3-D or not ``shape`` (where given; ``NSOF_ESHAPE``), 3-D planes whose trial counts differ,
+    and a non-finite value.  The domain of each value (``voff < 0 < von``, ...) is the library's check."""
+    if param_maps is None:
+        return 1, []
+    try:
+        items = dict(param_maps.items())
+    except AttributeError:
+        raise NsofValueError("param_maps must be a mapping of parameter name -> [H][W] or [T][H][W] array") from None
+    unknown = [k for k in items if k not in _PARAM_KEYS]
+    if unknown:
+        raise NsofValueError(f"param_maps: {unknown[0]!r} is not a per-cell parameter (one of {', '.join(_PARAM_KEYS)})")
+    out, trials = [], None
+    for k in _PARAM_KEYS:
+        if k not in items:
+            continue
+        try:
+            a = np.ascontiguousarray(items[k], np.float64)
+        except (TypeError, ValueError):
+            raise NsofValueError(f"param_maps[{k!r}] is not an array of numbers") from None
+        if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[0] < 1) or (shape is not None and a.shape[-2:] != tuple(shape)):
+            raise NsofValueError(f"param_maps[{k!r}] is {a.shape}, the array is "
+                                 f"{tuple(shape) if shape is not None else '[H][W]'} (with or without a leading trial axis)",
+                                 _lib.NSOF_ESHAPE)
+        if a.ndim == 3:
+            if trials is not None and a.shape[0] != trials[1]:
+                raise NsofValueError(f"param_maps[{k!r}] holds {a.shape[0]} trials, param_maps[{trials[0]!r}] {trials[1]}",
+                                     _lib.NSOF_ESHAPE)
+            trials = trials or (k, a.shape[0])
+        else:
+            a = a[None]
+        if not np.isfinite(a).all():
+            t, r, c = (int(v) for v in np.argwhere(~np.isfinite(a))[0])
+            raise NsofValueError(f"param_maps[{k!r}] trial {t}, row {r}, column {c} = {a[t, r, c]} is not finite")
+        out.append((k, a))
+    return (trials[1] if trials else 1), out
+
+
+def _frame_maps_c(n_trials, maps):
+    """The ctypes arrays (keys, planes, plane_trials) of ``frame_param_maps_arg``'s result; the planes stay referenced by
+    ``maps``."""
+    n = max(len(maps), 1)
+    keys = (C.c_int * n)(*[_PARAM_KEYS.index(k) for k, _ in maps])
+    planes = (C.c_void_p * n)(*[a.ctypes.data for _, a in maps])
+    counts = (C.c_int * n)(*[a.shape[0] for _, a in maps])
+    return keys, planes, counts
+
+
+def variability_maps(H, W, rel_sigma, params=None, seed=0, trials=None, dtype=np.float32):  # noqa: N803
     """Device-to-device variability as parameter maps (host helper; the kernels know nothing about it): for every key of
     ``rel_sigma`` the plane ``float32(p[key] * (1 + rel_sigma[key] * N(0, 1)))`` with ``p`` = ``params`` (``None``: ``PARAMS``),
     drawn from ``np.random.default_rng(seed)`` in ``_PARAM_KEYS`` order -- the result does not depend on the mapping's order --
     and clipped into the model's domain: ``voff`` / ``von`` / ``koff`` / ``kon`` keep their sign, ``son`` / ``soff`` / ``wini``
-    stay in [0, 1], ``Ron`` / ``Roff`` at least the smallest positive normal float32."""
+    stay in [0, 1], ``Ron`` / ``Roff`` at least the smallest positive normal float32.
+    ``trials=T``: ``[T][H][W]`` planes for the Monte-Carlo trials of the frame-driven path (``simulate_frames*``'s
+    ``param_maps``), trial ``t`` exactly the planes of ``seed + t``.  ``dtype=np.float64`` keeps the planes unrounded (the
+    frame-driven path reads doubles), so a spread of 0 gives the nominal value itself."""
+    if trials is not None:
+        if not isinstance(trials, (int, np.integer)) or isinstance(trials, (bool, np.bool_)) or trials < 1:
+            raise NsofValueError(f"variability_maps: trials = {trials!r} is not a whole number >= 1")
+        per = [variability_maps(H, W, rel_sigma, params, seed + t, dtype=dtype) for t in range(int(trials))]
+        return {k: np.stack([m[k] for m in per]) for k in per[0]}
+    if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise NsofValueError(f"variability_maps: dtype {dtype!r} is neither float32 nor float64")
     p = PARAMS if params is None else params
     unknown = [k for k in rel_sigma if k not in _PARAM_KEYS]
     if unknown:
@@ -130,7 +193,7 @@ def variability_maps(H, W, rel_sigma, params=None, seed=0):  # noqa: N803
             v = np.clip(v, 0.0, 1.0)
         elif k in ("Ron", "Roff"):
             v = np.maximum(v, tiny)
-        out[k] = v.astype(np.float32)
+        out[k] = v.astype(dtype)
     return out
 
 
@@ -544,18 +607,32 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
     return out
 
 
-def simulate_frames(compressed_images, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, *, ctx=None, params=None):
+def simulate_frames(compressed_images, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, *, ctx=None, params=None,
+                    param_maps=None):
     """Frame-driven accumulator of /root/reference/simulation/simulationcode_v4_transistor_uav.m
     (``simulate_memristor_array``, :187-227): ``compressed_images`` float64 [n][H][W] in [0,1] (the output of the
     script's Lanczos ``compress_image``).  Returns ``(w_array, resistances_over_time)`` with the initial snapshot
     first, as the script stores them.  uav: th1=0.7, th2=1.5; vehicle: th1=2.  ``params``: the script's ``params`` struct as
-    a mapping with the keys of ``PARAMS`` (``None``: ``PARAMS``), read as float64; ``dt`` is the argument it is."""
+    a mapping with the keys of ``PARAMS`` (``None``: ``PARAMS``), read as float64; ``dt`` is the argument it is.
+    ``param_maps`` (a mapping key of ``PARAMS`` -> ``[H][W]`` or ``[T][H][W]`` array, ``frame_param_maps_arg``): a device per
+    cell and per trial, all ``T`` trials in one launch (``nsof_accum_frames_f64_maps``); the other keys keep the scalar of
+    ``params``.  Both results then gain a leading trial axis -- ``w [T][H][W]``, ``resistances [T][n][H][W]`` -- also for
+    ``T`` = 1 (every plane 2-D); each (trial, cell) equals the uniform run at that cell's parameters bit for bit."""
     ap = accum_params(params)
-    ctx = ctx or default_context()
     imgs = np.ascontiguousarray(compressed_images, np.float64)
     if imgs.ndim != 3:
         raise NsofValueError("compressed_images must be [n][H][W]")
     n, H, W = imgs.shape  # noqa: N806
+    if param_maps is not None:
+        trials, maps = frame_param_maps_arg(param_maps, (H, W))
+        ctx = ctx or default_context()
+        w = np.empty((trials, H, W), np.float64)
+        res = np.empty((trials, n, H, W), np.float64)
+        ctx.check(ctx._lib.nsof_accum_frames_f64_maps(ctx.ptr, imgs.ctypes.data, n, H, W, float(dt), int(n_sub_steps), float(th1),
+                                                      float(th2), C.byref(ap), trials, len(maps), *_frame_maps_c(trials, maps),
+                                                      w.ctypes.data, res.ctypes.data), "simulate_frames")
+        return w, res
+    ctx = ctx or default_context()
     w = np.empty((H, W), np.float64)
     res = np.empty((n, H, W), np.float64)
     ctx.check(ctx._lib.nsof_accum_frames_f64_p(ctx.ptr, imgs.ctypes.data, n, H, W, float(dt), int(n_sub_steps),
@@ -564,12 +641,16 @@ def simulate_frames(compressed_images, dt=0.0005, n_sub_steps=1000, th1=0.7, th2
     return w, res
 
 
-def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, v_ds=1.0, *, ctx=None, params=None):
+def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, v_ds=1.0, *, ctx=None, params=None,
+                        param_maps=None):
     """``simulate_frames`` on a float64 CUDA tensor [n][H][W] (``frames.process_images_dev``'s output) in one launch
     (``nsof_accum_frames_f64_dev``): returns ``(w [H][W], resistances [n][H][W], current [n-1][H][W])`` as float64 CUDA
     tensors -- ``w`` and ``resistances`` equal ``simulate_frames`` bit for bit, ``current[f] = v_ds / resistances[f + 1]``
     is the device current after pair (f, f+1), the layout ``gating.roi_from_surface_dev`` reads.  Nothing is copied;
-    asynchronous on the context's stream.  ``params`` as for ``simulate_frames``."""
+    asynchronous on the context's stream.  ``params`` as for ``simulate_frames``.
+    ``param_maps`` as for ``simulate_frames`` (host arrays; they are uploaded through a buffer of the context): every
+    result gains a leading trial axis -- ``w [T][H][W]``, ``resistances [T][n][H][W]``, ``current [T][n-1][H][W]`` -- and
+    ``current[t]`` is a gating stack of its own (``nsof_accum_frames_f64_maps_dev``)."""
     ap = accum_params(params)
     torch = _torch()
     if not isinstance(compressed, torch.Tensor) or not compressed.is_cuda:
@@ -578,9 +659,20 @@ def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.
         raise NsofValueError(f"simulate_frames_dev: float64 expected (got {compressed.dtype})", _lib.NSOF_EINVAL)
     if compressed.dim() != 3 or compressed.shape[0] < 1 or not compressed.is_contiguous():
         raise NsofValueError("simulate_frames_dev: contiguous [n][H][W] frames expected", _lib.NSOF_ESHAPE)
-    ctx = ctx or default_context()
     n, H, W = (int(v) for v in compressed.shape)  # noqa: N806
     dev = compressed.device
+    if param_maps is not None:
+        trials, maps = frame_param_maps_arg(param_maps, (H, W))
+        ctx = ctx or default_context()
+        w = torch.empty((trials, H, W), dtype=torch.float64, device=dev)
+        res = torch.empty((trials, n, H, W), dtype=torch.float64, device=dev)
+        cur = torch.empty((trials, n - 1, H, W), dtype=torch.float64, device=dev)
+        ctx.check(ctx._lib.nsof_accum_frames_f64_maps_dev(ctx.ptr, dev_ptr(compressed), n, H, W, float(dt), int(n_sub_steps),
+                                                          float(th1), float(th2), float(v_ds), C.byref(ap), trials, len(maps),
+                                                          *_frame_maps_c(trials, maps), dev_ptr(w), dev_ptr(res),
+                                                          dev_ptr(cur) if n > 1 else None), "simulate_frames_dev")
+        return w, res, cur
+    ctx = ctx or default_context()
     w = torch.empty((H, W), dtype=torch.float64, device=dev)
     res = torch.empty((n, H, W), dtype=torch.float64, device=dev)
     cur = torch.empty((n - 1, H, W), dtype=torch.float64, device=dev)

@@ -291,6 +291,44 @@ def roi_from_surface_dev(d_current, n_maps, map_hw, frame_hw, cfg, max_rects=32,
     return (counts, rects, gray) if want_gray else (counts, rects)
 
 
+def gate_stats(current, nominal, thres):
+    """Gate statistics of a variability study on the host (NumPy; the statement ``gate_stats_dev`` is held to): ``current``
+    ``[T][F][rows][cols]`` are the device currents of ``T`` trials, ``nominal`` ``[F][rows][cols]`` those of the nominal
+    array; a cell is gated when ``current_to_gray(I) >= thres``.  Returns ``(counts int32 [F][rows][cols]`` -- the trials in
+    which the cell is gated -- ``, flips int32 [T][F]`` -- the cells of a trial's map whose gated bit differs from the
+    nominal's ``)``."""
+    cur, nom = np.asarray(current, np.float64), np.asarray(nominal, np.float64)
+    if cur.ndim != 4 or nom.shape != cur.shape[1:]:
+        raise ValueError(f"gate_stats: current {cur.shape} is not [T] + nominal {nom.shape}")
+    gated, gated_nom = current_to_gray(cur) >= thres, current_to_gray(nom) >= thres
+    return gated.sum(axis=0, dtype=np.int32), (gated != gated_nom[None]).sum(axis=(2, 3), dtype=np.int32)
+
+
+def gate_stats_dev(d_current, d_nominal, thres, ctx=None):
+    """``gate_stats`` for stacks already in HBM (``nsof_gate_stats_dev``): ``d_current`` float64 CUDA tensor
+    ``[T][F][rows][cols]`` (``simulate_frames_dev(..., param_maps=)``'s currents), ``d_nominal`` ``[F][rows][cols]``.  One
+    launch; returns the CUDA tensors ``(counts int32 [F][rows][cols], flips int32 [T][F])``, exact.  Asynchronous on the
+    context's stream."""
+    import torch
+
+    from . import _lib
+    from .context import default_context, dev_ptr
+    from .errors import NsofValueError
+    for name, t in (("d_current", d_current), ("d_nominal", d_nominal)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+            raise NsofValueError(f"gate_stats_dev: {name} must be a contiguous float64 CUDA tensor", _lib.NSOF_EINVAL)
+    if d_current.dim() != 4 or tuple(d_nominal.shape) != tuple(d_current.shape[1:]) or d_current.numel() == 0:
+        raise NsofValueError(f"gate_stats_dev: d_current {tuple(d_current.shape)} is not [T] + d_nominal "
+                             f"{tuple(d_nominal.shape)}", _lib.NSOF_ESHAPE)
+    ctx = ctx or default_context()
+    T, F, rows, cols = (int(v) for v in d_current.shape)  # noqa: N806
+    counts = torch.empty((F, rows, cols), dtype=torch.int32, device=d_current.device)
+    flips = torch.empty((T, F), dtype=torch.int32, device=d_current.device)
+    ctx.check(ctx._lib.nsof_gate_stats_dev(ctx.ptr, dev_ptr(d_current), dev_ptr(d_nominal), T, F, rows, cols, int(thres),
+                                           dev_ptr(counts), dev_ptr(flips)), "gate_stats_dev")
+    return counts, flips
+
+
 def rects_to_host(counts, rects, ctx=None):
     """``[[(x0, y0, x1, y1), ...] per map]`` from the device tables of ``roi_from_surface_dev`` (one small D2H copy)."""
     from .context import default_context

@@ -501,36 +501,82 @@ def _sequence_flows(frames_bgr, mem_state, cfg, with_original, max_rects, ctx, w
     return gray, counts, rtab, rects, flow_mem, flow_orig, gf
 
 
-def gating_stack_from_frames_dev(frames_bgr, cfg, m=None, n=None, region=None, ctx=None, **sim):
-    """The gating stack of a video, simulated in HBM: ``frames_bgr`` uint8 CUDA tensor [k][H][W][3] (BGR as ``cv2.imread``
-    gives them) -> gray frames (``gray_u8_dev``, the RGB2GRAY the flow stage converts with) -> Lanczos-3 grids of
-    ``region`` (``(region_ul, region_lr)``, MATLAB corners; the whole frame by default) compressed by ``m`` columns and ``n``
-    rows per cell (``frames.process_images_dev``; both default to ``cfg.MEMSIZE``, so the grid is the transition picture)
-    -> the array run over all pairs in one launch (``simulate_frames_dev``; ``sim`` passes ``dt``, ``n_sub_steps``,
-    ``th1``, ``th2``, ``v_ds`` on).  Returns the device currents, float64 CUDA tensor [k-1][rows][cols]: slice f is the
-    array after pair (f, f+1) -- what ``prediction_sequence_dev`` / ``segmentation_sequence_dev`` take as ``mem_state``
-    without a copy.  Equal to ``frames.process_images`` -> ``simulate_frames`` -> ``v_ds / resistances[1:]`` on the host gray
-    frames, bit for bit.  Nothing visits the host; synchronises at the end (the intermediates are released)."""
+def _compressed_grids_dev(frames_bgr, cfg, m, n, region, ctx, who):
+    """The front half of the frame-driven gating path: BGR frames -> gray frames (``gray_u8_dev``, RGB2GRAY) -> Lanczos-3
+    grids of ``region`` (``frames.process_images_dev``), float64 CUDA tensor [k][rows][cols]."""
     import torch
 
     from . import frames as fr
     from . import predict
-    from .accumulator import simulate_frames_dev
-    from .context import default_context
-    predict._u8_frames(frames_bgr, "gating_stack_from_frames_dev")
+    predict._u8_frames(frames_bgr, who)
     if frames_bgr.dim() != 4 or frames_bgr.shape[3] != 3 or frames_bgr.shape[0] < 2:
-        raise predict.NsofValueError("gating_stack_from_frames_dev: at least two uint8 [k][H][W][3] frames expected")
-    ctx = ctx or default_context()
+        raise predict.NsofValueError(f"{who}: at least two uint8 [k][H][W][3] frames expected")
     k, H, W = (int(v) for v in frames_bgr.shape[:3])  # noqa: N806
     gray = torch.empty((k, H, W), dtype=torch.uint8, device=frames_bgr.device)
     torch.cuda.synchronize(frames_bgr.device)
     for i in range(k):
         predict.gray_u8_dev(frames_bgr[i], gray[i], "RGB2GRAY", ctx=ctx)
     ul, lr = region if region is not None else (None, None)
-    grids = fr.process_images_dev(gray, cfg.MEMSIZE if m is None else m, cfg.MEMSIZE if n is None else n, ul, lr, ctx=ctx)
+    return fr.process_images_dev(gray, cfg.MEMSIZE if m is None else m, cfg.MEMSIZE if n is None else n, ul, lr, ctx=ctx)
+
+
+def gating_stack_from_frames_dev(frames_bgr, cfg, m=None, n=None, region=None, ctx=None, **sim):
+    """The gating stack of a video, simulated in HBM: ``frames_bgr`` uint8 CUDA tensor [k][H][W][3] (BGR as ``cv2.imread``
+    gives them) -> gray frames (``gray_u8_dev``, the RGB2GRAY the flow stage converts with) -> Lanczos-3 grids of
+    ``region`` (``(region_ul, region_lr)``, MATLAB corners; the whole frame by default) compressed by ``m`` columns and ``n``
+    rows per cell (``frames.process_images_dev``; both default to ``cfg.MEMSIZE``, so the grid is the transition picture)
+    -> the array run over all pairs in one launch (``simulate_frames_dev``; ``sim`` passes ``dt``, ``n_sub_steps``,
+    ``th1``, ``th2``, ``v_ds``, ``params``, ``param_maps`` on).  Returns the device currents, float64 CUDA tensor
+    [k-1][rows][cols]: slice f is the array after pair (f, f+1) -- what ``prediction_sequence_dev`` /
+    ``segmentation_sequence_dev`` take as ``mem_state`` without a copy.  With ``param_maps=`` (a device per cell and per
+    trial, ``simulate_frames_dev``) the result is [T][k-1][rows][cols], one such stack per trial.  Equal to
+    ``frames.process_images`` -> ``simulate_frames`` -> ``v_ds / resistances[1:]`` on the host gray frames, bit for bit.
+    Nothing visits the host; synchronises at the end (the intermediates are released)."""
+    from .accumulator import simulate_frames_dev
+    from .context import default_context
+    ctx = ctx or default_context()
+    grids = _compressed_grids_dev(frames_bgr, cfg, m, n, region, ctx, "gating_stack_from_frames_dev")
     cur = simulate_frames_dev(grids, ctx=ctx, **sim)[2]
     ctx.synchronize()
     return cur
+
+
+def gating_variability_dev(frames_bgr, cfg, rel_sigma, trials, seed=0, params=None, max_rects=32, m=None, n=None, region=None,
+                           ctx=None, **sim):
+    """What device-to-device variability does to the gate of a sequence, in HBM: the frames are compressed once
+    (``gating_stack_from_frames_dev``'s front half), the array is run for the nominal device ``params`` (``None``:
+    ``PARAMS``) and for ``trials`` arrays whose cells are drawn with the relative spreads ``rel_sigma`` (``{key: sigma}``;
+    ``variability_maps(rows, cols, rel_sigma, params, seed, trials=trials, dtype=float64)``: trial ``t`` is seed ``seed + t``)
+    -- one launch each --, then one launch of gate statistics (``gating.gate_stats_dev`` at ``cfg.THRES``) and one gating call
+    over all ``trials * (k - 1)`` maps (``gating.roi_from_surface_dev``).  ``sim`` passes ``dt``, ``n_sub_steps``, ``th1``,
+    ``th2``, ``v_ds`` on.  Returns a dict of CUDA tensors: ``nominal`` float64 [k-1][rows][cols], ``stacks`` float64
+    [T][k-1][rows][cols] (``stacks[t]`` is a ``mem_state`` of the sequence experiments, no copy), ``counts`` int32
+    [k-1][rows][cols] and ``p_gate`` float64 (``counts / T``: the gate probability per cell), ``flips`` int32 [T][k-1]
+    (cells of trial t's map f gated differently from the nominal's), ``rects`` int32 [T][k-1][max_rects][4] with
+    ``rect_counts`` int32 [T][k-1] (the tables of ``roi_from_surface_dev`` per map).  A spread of 0 on every key reproduces
+    ``nominal`` in every trial bit for bit.  Synchronises at the end."""
+    import numpy as np
+    import torch
+
+    from .accumulator import simulate_frames_dev, variability_maps
+    from .context import default_context
+    maps = variability_maps(1, 1, rel_sigma, params, seed, trials=trials, dtype=np.float64)   # refuses before any device work
+    ctx = ctx or default_context()
+    grids = _compressed_grids_dev(frames_bgr, cfg, m, n, region, ctx, "gating_variability_dev")
+    k, rows, cols = (int(v) for v in grids.shape)
+    H, W = (int(v) for v in frames_bgr.shape[1:3])  # noqa: N806
+    nominal = simulate_frames_dev(grids, ctx=ctx, params=params, **sim)[2]
+    if maps:
+        maps = variability_maps(rows, cols, rel_sigma, params, seed, trials=trials, dtype=np.float64)
+        stacks = simulate_frames_dev(grids, ctx=ctx, params=params, param_maps=maps, **sim)[2]
+    else:
+        stacks = nominal.unsqueeze(0).repeat(int(trials), 1, 1, 1)
+    counts, flips = gating.gate_stats_dev(stacks, nominal, cfg.THRES, ctx=ctx)
+    rect_counts, rects = gating.roi_from_surface_dev(stacks, int(trials) * (k - 1), (rows, cols), (H, W), cfg, max_rects=max_rects,
+                                                     ctx=ctx)
+    ctx.synchronize()
+    return dict(nominal=nominal, stacks=stacks, counts=counts, p_gate=counts.to(torch.float64) / int(trials), flips=flips,
+                rects=rects.view(int(trials), k - 1, max_rects, 4), rect_counts=rect_counts.view(int(trials), k - 1))
 
 
 def _experiment_boxes(rects, cfg, merge_flag, frame_hw):
