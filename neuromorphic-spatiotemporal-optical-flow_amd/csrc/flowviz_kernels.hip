@@ -19,7 +19,9 @@
 // Non-finite flows, where the NumPy coding has no answer (np.max propagates a NaN into every pixel's divisor, and a NaN
 // wheel position cannot index the wheel), are defined here instead:
 //   * the divisor is the largest magnitude over the pixels whose magnitude is not NaN (fmaxf skips NaN), + 1e-5;
-//     an infinite component makes it +inf, and every finite component then codes as 0;
+//     an infinite component makes it +inf, and every finite component then codes as 0 -- unless the pixel's other
+//     component is NaN: sqrt(inf + NaN) is NaN, so (inf, NaN) is skipped like any NaN pixel.  A finite component whose
+//     square overflows float32 (3e38) has the magnitude +inf too;
 //   * a pixel whose normalised u or v is NaN (a NaN flow, or an infinite one over an infinite divisor) is (0, 0, 0),
 //     a colour no finite flow produces: one wheel channel is always 255 inside the unit circle and 191 outside;
 //   * an infinite normalised component (a finite divisor from max_flow) is an ordinary pixel outside the unit circle:

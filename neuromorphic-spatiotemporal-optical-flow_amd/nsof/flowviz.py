@@ -80,8 +80,10 @@ def flow_to_image_dev(flows, out=None, *, clip_flow=None, max_flow=None, convert
     ``flow_to_image(sign * flow, clip_flow, convert_to_bgr, max_flow)`` of each float32 flow, with atan2 rounded
     once from float64 (NumPy's float32 arctan2 is off by an ulp now and then, so its output differs on about one pixel
     in a million, by one level).  Non-finite flows, which the NumPy coding cannot colour, are defined: pixels with a NaN
-    magnitude do not enter the largest magnitude, a pixel whose normalised u or v is NaN is (0, 0, 0) (a colour no
-    finite flow gets), and an infinite normalised component is coloured like any pixel outside the unit circle.
+    magnitude ((inf, NaN) among them) do not enter the largest magnitude, an infinite magnitude (an infinite component,
+    or a finite one whose float32 square overflows) makes the divisor +inf, a pixel whose normalised u or v is NaN is
+    (0, 0, 0) (a colour no finite flow gets), and an infinite normalised component is coloured like any pixel outside
+    the unit circle.
     ``norms`` (float32 CUDA tensor [n]) receives each flow's float32 divisor.
     Asynchronous on the context's stream: ``ctx.synchronize()`` before reading ``out`` elsewhere."""
     import torch

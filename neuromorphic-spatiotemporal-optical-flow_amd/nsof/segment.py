@@ -66,8 +66,9 @@ def erode(src, kernel, anchor=(-1, -1), iterations=1, *, ctx=None):
 def motion_mask(flow, seg_th=1, ksize=10, iterations=5, out=None, *, ctx=None):
     """The whole head on a flow field or a strided crop of one: uint8 [H][W] of 0/255.  float64 canvases (what
     ``opticalFlow3D`` returns) hold float32 values and are narrowed without loss; the sign of the flow is
-    irrelevant.  A pixel moves when its float64 magnitude exceeds ``seg_th``: a NaN component never does, an infinite
-    one always does."""
+    irrelevant.  A pixel moves when its float64 magnitude sqrt(u*u + v*v) exceeds ``seg_th``: a NaN component never
+    does (not even beside an infinite one: inf + NaN is NaN), an infinite one otherwise exceeds every finite
+    threshold, and a finite one whose square overflows float32 (3e38) is compared as the finite float64 it is."""
     ctx = ctx or default_context()
     flow = np.asarray(flow)
     if flow.ndim != 3 or flow.shape[2] != 2:
