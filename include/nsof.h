@@ -570,7 +570,10 @@ int nsof_accum_block_current_dev(nsof_accum* acc, int which, int64_t snapshot, i
 /* Frame-driven variant of the same device ODE (simulation/simulationcode_v4_transistor_uav.m:146-227,332-347),
  * float64: imgs = HOST compressed frames [n_frames][H][W] in [0,1]; per frame pair the drive voltage comes
  * from |a-b|*256 through the piecewise map (th1, th2) and modulatefunc, followed by n_sub_steps Euler sub-steps
- * of dt/n_sub_steps.  w_out [H][W]; res_out [n_frames][H][W] (initial array, then one snapshot per pair). */
+ * of dt/n_sub_steps.  w_out [H][W]; res_out [n_frames][H][W] (initial array, then one snapshot per pair).
+ * One implementation serves all six nsof_accum_frames_f64* entries: this one is nsof_accum_frames_f64_maps with one trial and
+ * no maps (upload, ONE launch, download; synchronous), so it shares that entry's launch range -- NSOF_EUNSUPPORTED beyond
+ * 2^32 - 64 cells, which no real array comes near. */
 int nsof_accum_frames_f64(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
                           int n_sub_steps, double th1, double th2, double* w_out, double* res_out);
 /* simulate_memristor_array(..., params): the same run for the given device (NULL = defaults), the fields read as doubles;
@@ -583,7 +586,10 @@ int nsof_accum_frames_f64_p(nsof_ctx* ctx, const double* imgs, int n_frames, int
  * context's stream, nothing copied: d_imgs [n_frames][H][W]; d_w [H][W]; d_res [n_frames][H][W], slice 0 the initial array
  * and slice f + 1 the state after pair (f, f + 1); d_current (may be NULL) [n_frames - 1][H][W], d_current[f] = v_ds /
  * d_res[f + 1] as an IEEE double division -- the device current of a grid that already is the gating map, the layout
- * nsof_roi_from_surface_dev reads.  d_w and d_res equal nsof_accum_frames_f64's outputs bit for bit. */
+ * nsof_roi_from_surface_dev reads.  This is nsof_accum_frames_f64_maps_dev with one trial and no maps, except that d_res
+ * must be given; the host entries run the same kernel, so d_w and d_res equal their outputs bit for bit, and the bits
+ * themselves -- those of the per-pair host entry this kernel replaced -- are recorded in tests/golden/frames_run_bits.npz
+ * (tests/test_frames_bits_gpu.py). */
 int nsof_accum_frames_f64_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
                               int n_sub_steps, double th1, double th2, double v_ds, double* d_w, double* d_res,
                               double* d_current);
@@ -597,11 +603,13 @@ int nsof_accum_frames_f64_p_dev(nsof_ctx* ctx, const double* d_imgs, int n_frame
  * th1, th2, v_ds and n_sub_steps stay scalars.  Values are read as doubles (a float32 plane widened is exact).  The frames
  * d_imgs [n_frames][H][W] are shared by the trials; d_w [T][H][W], d_res [T][n_frames][H][W] (may be NULL), d_current
  * [T][n_frames - 1][H][W] (may be NULL), each trial laid out as nsof_accum_frames_f64_dev lays out its one.
- * Per (trial, cell) the arithmetic is the uniform entry's with that cell's fields -- the same device functions in the same
- * order -- and the two values the uniform entry forms on the host are formed on the host here too, per (trial, cell), and
- * uploaded as planes: lambda = log(Roff / Ron) and the initial resistance Ron / exp(-lambda * (1 - wini)).  So a cell's w,
- * res and current equal, bit for bit, nsof_accum_frames_f64_p_dev's at that cell's parameters; constant planes equal to the
- * scalars give the uniform entry's bits; with n_maps == 0, n_trials == 1 and d_res given the call IS that entry.
+ * This is the entry that launches; every other nsof_accum_frames_f64* entry ends here.  One kernel walks a (trial, cell)'s
+ * frame pairs whatever the source of its device model -- the fitted constants, the scalars of params, planes -- so per
+ * (trial, cell) the arithmetic is the uniform call's with that cell's fields.  The two values formed on the host with the C
+ * library, lambda = log(Roff / Ron) and the initial resistance Ron / exp(-lambda * (1 - wini)), are formed there per (trial,
+ * cell) wherever Ron, Roff or wini is a plane, and uploaded as planes.  So a cell's w, res and current equal, bit for bit,
+ * nsof_accum_frames_f64_p_dev's at that cell's parameters; constant planes equal to the scalars give the uniform bits; with
+ * n_maps == 0 every trial is the uniform run.
  * Thread g of the launch is trial g / (H * W), cell g % (H * W), in workgroups of 64.  The planes go up through a buffer of
  * the context, stream-ordered: the call waits only for its own previous upload to have left the pinned copy, or to grow it;
  * otherwise asynchronous on the context's stream.
@@ -609,14 +617,14 @@ int nsof_accum_frames_f64_p_dev(nsof_ctx* ctx, const double* d_imgs, int n_frame
  * NULL plane, plane_trials[j] other than 1 or n_trials, and any value outside the domain nsof_accum_create_p checks
  * (non-finite as double or as float32, voff >= 0, von <= 0, son / soff / wini outside [0, 1], Ron or Roff <= 0, ln(Roff /
  * Ron) not finite) -- the message naming key, trial, row, column and value of the first one, planes in the order given.
- * NSOF_EUNSUPPORTED: n_trials * H * W beyond one launch's index range.
+ * NSOF_EUNSUPPORTED (likewise before anything is uploaded): n_trials * H * W beyond one launch's index range, 2^32 - 64.
  * Out of scope: per-cell th1 / th2 / dt, the linear resistance map, float32 planes on the device. */
 int nsof_accum_frames_f64_maps_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
                                    int n_sub_steps, double th1, double th2, double v_ds, const nsof_accum_params* params,
                                    int n_trials, int n_maps, const int* keys, const double* const* planes,
                                    const int* plane_trials, double* d_w, double* d_res, double* d_current);
-/* The same with HOST frames and outputs (w_out [T][H][W], res_out [T][n_frames][H][W]): upload, the one launch, download;
- * the device entry's bits.  Synchronous. */
+/* The same with HOST frames and outputs (w_out [T][H][W], res_out [T][n_frames][H][W]) -- the one host path: validate,
+ * upload, the device entry, download, synchronise.  The device entry's bits. */
 int nsof_accum_frames_f64_maps(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
                                int n_sub_steps, double th1, double th2, const nsof_accum_params* params, int n_trials,
                                int n_maps, const int* keys, const double* const* planes, const int* plane_trials,

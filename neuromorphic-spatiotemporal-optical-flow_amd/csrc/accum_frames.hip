@@ -1,0 +1,311 @@
+// Frame-driven synaptic accumulator, float64: simulate_memristor_array of
+// /root/reference/simulation/simulationcode_v4_transistor_uav.m (:146-227, 332-347) for gfx950.
+//
+// One kernel, one launch site, one host path.  k_frames_run walks every frame pair of one (trial, cell) in one thread -- a
+// cell's pairs are one dependent chain, the cells and the trials are independent -- and is instantiated per SOURCE of the
+// device model: the fitted constants, one device in the kernel arguments, or planes with a value per (trial, cell).  The
+// source is read once, before the loop; the loop itself exists once.  nsof_accum_frames_f64_maps_dev is the only function
+// that launches it and nsof_accum_frames_f64_maps the only one that copies; the other four entries forward to them.
+// The bits of the run -- the default device, two other devices, the dead zone -- are recorded in
+// tests/golden/frames_run_bits.npz, written by the per-pair host entry this file replaced (tests/test_frames_bits_gpu.py).
+#include <algorithm>
+#include <cstring>
+
+#include "accum_model.h"
+
+namespace {
+
+// update_state(w, V, dt, params) of the script (:173-181): k * A^alpha * B^b, left to right; alpha == 1 calls no pow.
+__device__ __forceinline__ double frame_gain(double V, double v0, double k, double alpha)
+{
+    const double a = V / v0 - 1;
+    return k * (alpha == 1.0 ? a : pow(a, alpha));
+}
+__device__ __forceinline__ double frame_update(double w, double V, double dt, const DevD& p)
+{
+    double dwdt = 0.0;
+    if (V < p.voff) dwdt = frame_gain(V, p.voff, p.koff, p.alphaoff) * pow(1 - w * p.soff, p.boff);
+    else if (V > p.von) dwdt = frame_gain(V, p.von, p.kon, p.alphaon) * pow(1 - w * p.son, p.bon);
+    const double nw = w + dwdt * dt;
+    return nw < 0 ? 0 : (nw > 1 ? 1 : nw);
+}
+
+// One frame pair of one grid pixel: the state after n_sub sub-steps under the drive voltage of |a - b|.
+__device__ __forceinline__ double frame_pair(double a, double b, double ww, double dts, int n_sub, double th1, double th2,
+                                             const DevD& p)
+{
+    const double d = fabs(a * 256 - b * 256);
+    double V = d > th1 ? (d + 4) * 0.75 : (d - 5.5) * 0.6;   // func2 == func3 in the source
+    V = V > 0 ? -(0.3 * V + 0) : (V < 0 ? -(3 * V + -3) : 0.0);
+    for (int s = 0; s < n_sub; s++) ww = frame_update(ww, V, dts, p);
+    return ww;
+}
+
+// The three sources of a thread's DevD, read through frame_cell(source, trial, cell):
+//   FittedD    the fitted device: compile-time constants but for the two values the host forms with libm
+//   DevD       one device in the kernel arguments, the same for every thread
+//   FrameMaps  per field the scalar of the call or the thread's element of a plane [1 or n_trials][n] (trial stride 0: the
+//              plane is shared by the trials); lambda and r0 are planes too wherever Ron, Roff or wini is one
+struct FittedD { double lambda, r0; };
+enum { FM_VOFF, FM_VON, FM_KOFF, FM_KON, FM_SON, FM_SOFF, FM_BON, FM_BOFF, FM_ALPHAOFF, FM_ALPHAON, FM_RON, FM_LAMBDA, FM_WINI, FM_R0, FM_COUNT };   // DevD's fields, in order
+struct FrameMaps {
+    const double* plane[FM_COUNT];   // nullptr: the field is the scalar
+    size_t stride[FM_COUNT];         // between the trials of a plane: 0 or n
+    double scalar[FM_COUNT];
+};
+__device__ __forceinline__ DevD frame_cell(const DevD& p, size_t, size_t) { return p; }
+__device__ __forceinline__ DevD frame_cell(FittedD a, size_t, size_t)
+{
+    DevD p = fitted_d();
+    p.lambda = a.lambda;
+    p.r0 = a.r0;
+    return p;
+}
+__device__ __forceinline__ DevD frame_cell(const FrameMaps& m, size_t trial, size_t i)
+{
+    auto get = [&](int s) { return m.plane[s] ? m.plane[s][trial * m.stride[s] + i] : m.scalar[s]; };
+    return DevD{get(FM_VOFF), get(FM_VON), get(FM_KOFF), get(FM_KON), get(FM_SON), get(FM_SOFF), get(FM_BON), get(FM_BOFF),
+                get(FM_ALPHAOFF), get(FM_ALPHAON), get(FM_RON), get(FM_LAMBDA), get(FM_WINI), get(FM_R0)};
+}
+
+// The whole run in one launch: thread g is trial g / n, cell g % n, and walks every frame pair.  imgs [n_frames][n] is
+// shared by the trials; w [T][n]; res [T][n_frames][n] (optional), slice 0 = r0; current [T][n_frames - 1][n] = v_ds /
+// res[f + 1] (optional).  total = T * n.
+template <class Src>
+__global__ __launch_bounds__(64) void k_frames_run(const double* __restrict__ imgs, int n_frames, double* __restrict__ w,
+                                                    double* __restrict__ res, double* __restrict__ current, size_t n,
+                                                    size_t total, double dts, int n_sub, double th1, double th2, Src src,
+                                                    double v_ds)
+{
+    const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (g >= total) return;
+    const size_t trial = g / n, i = g - trial * n;
+    const DevD p = frame_cell(src, trial, i);
+    double* const rt = res ? res + trial * (size_t)n_frames * n : nullptr;
+    double* const ct = current ? current + trial * (size_t)(n_frames - 1) * n : nullptr;
+    double ww = p.wini, b = imgs[i];
+    if (rt) rt[i] = p.r0;
+    for (int f = 0; f + 1 < n_frames; f++) {
+        const double a = b;
+        b = imgs[(size_t)(f + 1) * n + i];
+        ww = frame_pair(a, b, ww, dts, n_sub, th1, th2, p);
+        const double r = p.ron / exp(-p.lambda * (1 - ww));
+        if (rt) rt[(size_t)(f + 1) * n + i] = r;
+        if (ct) ct[(size_t)f * n + i] = v_ds / r;
+    }
+    w[g] = ww;
+}
+
+// The planes of a mapped call, per key (nullptr: the key keeps its scalar) with their trial counts.
+struct FramePlanes {
+    const double* plane[NSOF_ACCUM_KEY_COUNT] = {};
+    int trials[NSOF_ACCUM_KEY_COUNT] = {};
+    bool any = false;
+    // the value of key k at (trial t, cell i): the plane's, or `scalar`
+    double at(int k, double scalar, size_t t, size_t i, size_t npx) const
+    {
+        return plane[k] ? plane[k][(trials[k] == 1 ? 0 : t) * npx + i] : scalar;
+    }
+    double lambda_at(const nsof_accum_params& sp, size_t t, size_t i, size_t npx) const
+    {
+        return std::log(at(NSOF_ACCUM_KEY_ROFF, sp.Roff, t, i, npx) / at(NSOF_ACCUM_KEY_RON, sp.Ron, t, i, npx));
+    }
+    int lambda_trials() const   // 0: lambda is the scalar
+    {
+        return std::max(trials[NSOF_ACCUM_KEY_RON], trials[NSOF_ACCUM_KEY_ROFF]);
+    }
+};
+
+// Everything that can refuse a frame-driven call, decided on the host before anything is uploaded, launched or written:
+// the arguments, the launch range, the scalars (model_of) and every value of every plane against the same domain
+// (key_value_refused) -- so a plane is refused exactly where the uniform entry refuses that scalar.
+int frame_planes_of(nsof_ctx* ctx, int n_frames, int height, int width, int n_sub_steps, const nsof_accum_params* params,
+                    int n_trials, int n_maps, const int* keys, const double* const* planes, const int* plane_trials, Model* model,
+                    FramePlanes* fp)
+{
+    if (n_frames < 1 || height < 1 || width < 1 || n_sub_steps < 1)
+        return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
+    if (n_trials < 1) return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: %d trials (at least 1)", n_trials);
+    if (n_maps < 0 || n_maps > NSOF_ACCUM_KEY_COUNT || (n_maps > 0 && (!keys || !planes || !plane_trials)))
+        return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: %d maps (0..%d, with their keys, planes and trial counts)", n_maps,
+                              NSOF_ACCUM_KEY_COUNT);
+    for (int j = 0; j < n_maps; j++) {
+        const int k = keys[j];
+        if (k < 0 || k >= NSOF_ACCUM_KEY_COUNT)
+            return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: key %d is no parameter (0..%d)", k, NSOF_ACCUM_KEY_COUNT - 1);
+        if (!planes[j]) return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: the plane of %s is NULL", kKeyNames[k]);
+        if (fp->plane[k]) return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: %s given twice", kKeyNames[k]);
+        if (plane_trials[j] != 1 && plane_trials[j] != n_trials)
+            return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: the plane of %s holds %d trials (1 or %d)", kKeyNames[k],
+                                  plane_trials[j], n_trials);
+        fp->plane[k] = planes[j];
+        fp->trials[k] = plane_trials[j];
+        fp->any = true;
+    }
+    if (int rc = model_of(ctx, params, model)) return rc;
+    const size_t npx = (size_t)height * width;
+    for (int j = 0; j < n_maps; j++)
+        for (size_t e = 0; e < (size_t)plane_trials[j] * npx; e++)
+            if (const char* why = key_value_refused(keys[j], planes[j][e]))
+                return nsof_set_error(ctx, NSOF_EINVAL, "frame map %s: trial %zu, row %zu, column %zu = %g %s", kKeyNames[keys[j]],
+                                      e / npx, e % npx / (size_t)width, e % (size_t)width, planes[j][e], why);
+    for (size_t e = 0; e < (size_t)fp->lambda_trials() * npx; e++)
+        if (!std::isfinite(fp->lambda_at(model->prm, e / npx, e % npx, npx)))
+            return nsof_set_error(ctx, NSOF_EINVAL, "frame maps Ron / Roff: ln(Roff / Ron) is not finite at trial %zu, row %zu, column %zu",
+                                  e / npx, e % npx / (size_t)width, e % (size_t)width);
+    if (npx > (0xffffffffull - 63) / (size_t)n_trials)
+        return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "%d trials of %zu cells: too large for one launch", n_trials, npx);
+    return NSOF_OK;
+}
+
+// The kernel's FrameMaps of a mapped call: one table -- the caller's planes, then lambda and r0 per (trial, cell) wherever
+// Ron, Roff or wini is a plane, formed with the host's log / exp as model_of forms the two scalars -- through the pinned
+// copy of the context, which waits for this entry's previous upload only (or to grow).
+int frame_maps_upload(nsof_ctx* ctx, const Model& model, const FramePlanes& fp, size_t npx, FrameMaps* fm)
+{
+    // slot -> key of nsof_accum_params (lambda and r0 have none)
+    static const int key_of[FM_COUNT] = {NSOF_ACCUM_KEY_VOFF, NSOF_ACCUM_KEY_VON, NSOF_ACCUM_KEY_KOFF, NSOF_ACCUM_KEY_KON,
+                                         NSOF_ACCUM_KEY_SON, NSOF_ACCUM_KEY_SOFF, NSOF_ACCUM_KEY_BON, NSOF_ACCUM_KEY_BOFF,
+                                         NSOF_ACCUM_KEY_ALPHAOFF, NSOF_ACCUM_KEY_ALPHAON, NSOF_ACCUM_KEY_RON, -1,
+                                         NSOF_ACCUM_KEY_WINI, -1};
+    const DevD& md = model.d;
+    const nsof_accum_params& sp = model.prm;
+    const double scalars[FM_COUNT] = {md.voff, md.von, md.koff, md.kon, md.son, md.soff, md.bon, md.boff, md.alphaoff, md.alphaon,
+                                      md.ron, md.lambda, md.wini, md.r0};
+    const int t_lam = fp.lambda_trials(), t_r0 = std::max(t_lam, fp.trials[NSOF_ACCUM_KEY_WINI]);
+    size_t off[FM_COUNT], doubles = 0;
+    int trials[FM_COUNT];
+    for (int s = 0; s < FM_COUNT; s++) {
+        trials[s] = s == FM_LAMBDA ? t_lam : (s == FM_R0 ? t_r0 : fp.trials[key_of[s]]);
+        off[s] = doubles;
+        doubles += (size_t)trials[s] * npx;
+    }
+    const size_t bytes = doubles * sizeof(double);
+    if (int rc = ctx->frame_maps.stage(ctx, bytes, (bytes + bytes / 2 + 4095) & ~(size_t)4095)) return rc;
+    double* h = (double*)ctx->frame_maps.h.p;
+    for (int s = 0; s < FM_COUNT; s++) {
+        double* dst = h + off[s];
+        const size_t cnt = (size_t)trials[s] * npx;
+        if (s == FM_LAMBDA) {
+            for (size_t e = 0; e < cnt; e++) dst[e] = fp.lambda_at(sp, e / npx, e % npx, npx);
+        } else if (s == FM_R0) {
+            for (size_t e = 0; e < cnt; e++) {
+                const size_t t = e / npx, i = e % npx;
+                const double lam = t_lam ? h[off[FM_LAMBDA] + (t_lam == 1 ? 0 : t) * npx + i] : md.lambda;
+                dst[e] = fp.at(NSOF_ACCUM_KEY_RON, sp.Ron, t, i, npx) / std::exp(-lam * (1 - fp.at(NSOF_ACCUM_KEY_WINI, sp.wini, t, i, npx)));
+            }
+        } else if (cnt) {
+            memcpy(dst, fp.plane[key_of[s]], cnt * sizeof(double));
+        }
+    }
+    const double* d_planes = (const double*)ctx->frame_maps.upload(ctx, bytes);
+    if (!d_planes) return NSOF_EDEVICE;
+    for (int s = 0; s < FM_COUNT; s++) {
+        fm->plane[s] = trials[s] ? d_planes + off[s] : nullptr;
+        fm->stride[s] = trials[s] > 1 ? npx : 0;
+        fm->scalar[s] = scalars[s];
+    }
+    return NSOF_OK;
+}
+
+}  // namespace
+
+// The device entry every other one ends in: see include/nsof.h.
+extern "C" int nsof_accum_frames_f64_maps_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
+                                              int n_sub_steps, double th1, double th2, double v_ds, const nsof_accum_params* params,
+                                              int n_trials, int n_maps, const int* keys, const double* const* planes,
+                                              const int* plane_trials, double* d_w, double* d_res, double* d_current)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!d_imgs || !d_w) return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
+    Model model;
+    FramePlanes fp;
+    if (int rc = frame_planes_of(ctx, n_frames, height, width, n_sub_steps, params, n_trials, n_maps, keys, planes, plane_trials,
+                                 &model, &fp))
+        return rc;
+    const size_t npx = (size_t)height * width, total = npx * (size_t)n_trials;
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    auto launch = [&](auto src) {
+        hipLaunchKernelGGL(k_frames_run<decltype(src)>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, d_imgs, n_frames,
+                           d_w, d_res, d_current, npx, total, dt / n_sub_steps, n_sub_steps, th1, th2, src, v_ds);
+    };
+    if (fp.any) {
+        FrameMaps fm;
+        if (int rc = frame_maps_upload(ctx, model, fp, npx, &fm)) return rc;
+        launch(fm);
+    } else if (model.fitted) {
+        launch(FittedD{model.d.lambda, model.d.r0});
+    } else {
+        launch(model.d);
+    }
+    NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
+}
+
+extern "C" int nsof_accum_frames_f64_p_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
+                                           int n_sub_steps, double th1, double th2, double v_ds, const nsof_accum_params* params,
+                                           double* d_w, double* d_res, double* d_current)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!d_imgs || !d_w || !d_res || n_frames < 1 || height < 1 || width < 1 || n_sub_steps < 1)
+        return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
+    return nsof_accum_frames_f64_maps_dev(ctx, d_imgs, n_frames, height, width, dt, n_sub_steps, th1, th2, v_ds, params, 1, 0, nullptr,
+                                          nullptr, nullptr, d_w, d_res, d_current);
+}
+
+extern "C" int nsof_accum_frames_f64_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
+                                         int n_sub_steps, double th1, double th2, double v_ds, double* d_w, double* d_res,
+                                         double* d_current)
+{
+    return nsof_accum_frames_f64_p_dev(ctx, d_imgs, n_frames, height, width, dt, n_sub_steps, th1, th2, v_ds, nullptr, d_w, d_res,
+                                       d_current);
+}
+
+// The host path: validate, upload the frames, the device entry, download, synchronise.
+extern "C" int nsof_accum_frames_f64_maps(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
+                                          int n_sub_steps, double th1, double th2, const nsof_accum_params* params, int n_trials,
+                                          int n_maps, const int* keys, const double* const* planes, const int* plane_trials,
+                                          double* w_out, double* res_out)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!imgs || !w_out || !res_out) return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
+    {   // refuse before anything is allocated or copied
+        Model model;
+        FramePlanes fp;
+        if (int rc = frame_planes_of(ctx, n_frames, height, width, n_sub_steps, params, n_trials, n_maps, keys, planes, plane_trials,
+                                     &model, &fp))
+            return rc;
+    }
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t npx = (size_t)height * width, nw = npx * (size_t)n_trials, nr = nw * (size_t)n_frames;
+    nsof_dev_buf<double> img_buf, w_buf, res_buf;
+    int rc = img_buf.reserve(ctx, (size_t)n_frames * npx * 8);
+    if (!rc) rc = w_buf.reserve(ctx, nw * 8);
+    if (!rc) rc = res_buf.reserve(ctx, nr * 8);
+    if (rc) return rc;
+    NSOF_HIP(ctx, hipMemcpyAsync(img_buf.p, imgs, (size_t)n_frames * npx * 8, hipMemcpyHostToDevice, ctx->stream));
+    rc = nsof_accum_frames_f64_maps_dev(ctx, img_buf.p, n_frames, height, width, dt, n_sub_steps, th1, th2, 1.0, params, n_trials,
+                                        n_maps, keys, planes, plane_trials, w_buf.p, res_buf.p, nullptr);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(w_out, w_buf.p, nw * 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(res_out, res_buf.p, nr * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);   // also before the buffers go
+    if (rc) return rc;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return nsof_set_error(ctx, NSOF_EDEVICE, "frame accumulator: %s", hipGetErrorString(e));
+    return NSOF_OK;
+}
+
+extern "C" int nsof_accum_frames_f64_p(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
+                                       int n_sub_steps, double th1, double th2, const nsof_accum_params* params, double* w_out,
+                                       double* res_out)
+{
+    return nsof_accum_frames_f64_maps(ctx, imgs, n_frames, height, width, dt, n_sub_steps, th1, th2, params, 1, 0, nullptr, nullptr,
+                                      nullptr, w_out, res_out);
+}
+
+extern "C" int nsof_accum_frames_f64(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
+                                     int n_sub_steps, double th1, double th2, double* w_out, double* res_out)
+{
+    return nsof_accum_frames_f64_p(ctx, imgs, n_frames, height, width, dt, n_sub_steps, th1, th2, nullptr, w_out, res_out);
+}

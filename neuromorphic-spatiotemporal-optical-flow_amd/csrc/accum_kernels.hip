@@ -1,4 +1,5 @@
-// Synaptic accumulator ("memristor array"): HIP kernels + host driver for gfx950.
+// Synaptic accumulator ("memristor array"), event-driven, float32: HIP kernels + host driver for gfx950.  (The float64
+// frame-driven run is accum_frames.hip; the device model both take is accum_model.h.)
 //
 // Replaces /root/reference/eventsim/event_mem_sim.py: update_state (:40-57),
 // resistance_exp (:60-63) and the slice loop of simulate (:164-286).
@@ -15,7 +16,7 @@
 //    one scatter per group as in scheme 1, the eligibility walk inside the fused update (RefrTab).
 //  * The device model (PARAMS, DT, REFRACTORY_US of the reference) is an argument of the accumulator (nsof_accum_params):
 //    float32 fields by value in the kernel arguments, the fitted device of the paper as a compile-time instantiation of
-//    the hot kernels (DevF, fitted_f below).  Per-pixel parameter maps (nsof_accum_set_param_maps) are a third kind: one
+//    the hot kernels (DevF, fitted_f: accum_model.h).  Per-pixel parameter maps (nsof_accum_set_param_maps) are a third kind: one
 //    set-up kernel writes every pixel's drives and resistance pair, the hot kernels load them per driven pixel (MapF).
 //  * pow/exp go through double precision so that the float32 result is the correctly
 //    rounded one: equal to it on every state in [0, 1] outside the ~3e-7 of inputs that lie
@@ -30,48 +31,12 @@
 #include <type_traits>
 #include <vector>
 
-#include "nsof_internal.h"
+#include "accum_model.h"
 
 namespace {
 
-// The device model (PARAMS, DT of event_mem_sim.py:20-30) as the float32 kernels take it: every field of nsof_accum_params
-// rounded to float32 ONCE on the host -- NumPy does the same to the Python scalars of PARAMS next to a float32 array -- and
-// neg_lam = (float)(-ln(Roff / Ron)), the logarithm taken in double as np.log takes it.  Passed BY VALUE in the kernel
-// arguments: uniform, so the fields sit in SGPRs; no __constant__ symbol is written per call and no pixel loads anything
-// for them, and two accumulators with different devices run back to back on one context.
-struct DevF {
-    float voff, von, koff, kon, son, soff, bon, boff, alphaoff, alphaon, dt, ron, neg_lam;
-};
-// The same model for the float64 frame-driven path; lambda = ln(Roff / Ron).
-struct DevD {
-    double voff, von, koff, kon, son, soff, bon, boff, alphaoff, alphaon, ron, lambda, wini;
-};
-// The fitted device of the paper (event_mem_sim.py:20-34) as compile-time constants.  The hot kernels -- the fused updates,
-// the tile walk, the float64 frame loop -- are instantiated per model kind: the fitted one (MK_FITTED; FITTED in the float64 loop) takes an empty argument and folds these constants, so
-// the default path runs the code it ran before the parameters became arguments (same bits, same time: measured, a run-time
-// model cost the launch-bound scheme-2 groups 1.5-2.5 %); the other instantiation reads the argument.  NULL or default
-// parameters are routed to the fitted instantiation (Model::fitted); per-pixel planes are the third kind (MapF below).
-__host__ __device__ constexpr DevF fitted_f()
-{
-    return DevF{(float)-0.2, (float)0.1, (float)51.03, (float)-2.91, (float)0.2, (float)0.8, (float)-5.12, (float)3.10,
-                1.f, 1.f, (float)5e-4, 163305.f, -0x1.473018p+1f /* (float)-ln(2104377 / 163305) */};
-}
-__host__ __device__ constexpr DevD fitted_d()
-{
-    return DevD{-0.2, 0.1, 51.03, -2.91, 0.2, 0.8, -5.12, 3.10, 1.0, 1.0, 163305.0, 0.0 /* lambda: never read, see FrameArg */, 0.5};
-}
 struct NoModel {};
-// Per-pixel parameter maps (nsof_accum_set_param_maps): the third kind of model.  The voltages are fixed per accumulator, so
-// everything a pixel's update needs is formed ONCE by k_setup_maps -- the active and the silent Drive (ka, s, b: 12 bytes
-// each, dt stays a scalar) and the pair (ron, neg_lam) of its resistance -- and the hot kernels load a pixel's drive where
-// they formed one from SGPRs: 12 bytes per driven pixel, nothing for an idle one.
-struct MapF {
-    const float* act;    // [npx][3]: drive_of(active voltage, the pixel's DevF)
-    const float* sil;    // [npx][3]: drive_of(silent_v, the pixel's DevF)
-    const float2* res;   // [npx]: (ron, neg_lam)
-    float dt;
-};
-// KIND of the hot kernels: the fitted device as compile-time constants / one device in the kernel arguments / per-pixel planes.
+// KIND of the hot kernels (DevF, fitted_f, MapF: accum_model.h): the fitted device as compile-time constants / one device in the kernel arguments / per-pixel planes.
 // (int constants, not an unnamed enum: ModelArg<KIND> is part of every hot kernel's signature, and an unnamed type in a mangled
 // name is numbered differently by the host and the device pass -- the host would register a name the code object lacks)
 constexpr int MK_FITTED = 0, MK_UNIFORM = 1, MK_MAPPED = 2;
@@ -85,17 +50,6 @@ __device__ __forceinline__ DevF model_arg(const MapF& m)   // dt is all the pixe
 {
     DevF p{};
     p.dt = m.dt;
-    return p;
-}
-// The float64 frame loop: lambda = ln(Roff / Ron) is formed on the host in either case (std::log is no constant expression).
-struct FittedD { double lambda; };
-template <bool FITTED>
-using FrameArg = std::conditional_t<FITTED, FittedD, DevD>;
-__device__ __forceinline__ DevD frame_arg(const DevD& p) { return p; }
-__device__ __forceinline__ DevD frame_arg(FittedD a)
-{
-    DevD p = fitted_d();
-    p.lambda = a.lambda;
     return p;
 }
 constexpr int MAX_GROUP = 32;
@@ -613,110 +567,6 @@ __global__ __launch_bounds__(256) void k_update_all(float* __restrict__ w, unsig
     }
 }
 
-// Frame-driven variant (/root/reference/simulation/simulationcode_v4_transistor_uav.m:146-227, 332-347), float64:
-// drive voltage from the absolute difference of two compressed frames, then n_sub Euler sub-steps of the same ODE.
-// update_state(w, V, dt, params) of the script (:173-181): k * A^alpha * B^b, left to right; alpha == 1 calls no pow.
-__device__ __forceinline__ double frame_gain(double V, double v0, double k, double alpha)
-{
-    const double a = V / v0 - 1;
-    return k * (alpha == 1.0 ? a : pow(a, alpha));
-}
-__device__ __forceinline__ double frame_update(double w, double V, double dt, const DevD& p)
-{
-    double dwdt = 0.0;
-    if (V < p.voff) dwdt = frame_gain(V, p.voff, p.koff, p.alphaoff) * pow(1 - w * p.soff, p.boff);
-    else if (V > p.von) dwdt = frame_gain(V, p.von, p.kon, p.alphaon) * pow(1 - w * p.son, p.bon);
-    const double nw = w + dwdt * dt;
-    return nw < 0 ? 0 : (nw > 1 ? 1 : nw);
-}
-
-// One frame pair of one grid pixel: the state after n_sub sub-steps under the drive voltage of |a - b|.
-__device__ __forceinline__ double frame_pair(double a, double b, double ww, double dts, int n_sub, double th1, double th2,
-                                             const DevD& p)
-{
-    const double d = fabs(a * 256 - b * 256);
-    double V = d > th1 ? (d + 4) * 0.75 : (d - 5.5) * 0.6;   // func2 == func3 in the source
-    V = V > 0 ? -(0.3 * V + 0) : (V < 0 ? -(3 * V + -3) : 0.0);
-    for (int s = 0; s < n_sub; s++) ww = frame_update(ww, V, dts, p);
-    return ww;
-}
-
-template <bool FITTED>
-__global__ __launch_bounds__(64) void k_frame_step(const double* __restrict__ a, const double* __restrict__ b,
-                                                    double* __restrict__ w, double* __restrict__ res, size_t n,
-                                                    double dts, int n_sub, double th1, double th2, FrameArg<FITTED> model)
-{
-    const DevD p = frame_arg(model);
-    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    const double ww = frame_pair(a[i], b[i], w[i], dts, n_sub, th1, th2, p);
-    w[i] = ww;
-    res[i] = p.ron / exp(-p.lambda * (1 - ww));
-}
-
-// The whole run in one launch: one thread per grid pixel walks every frame pair (a pixel's pairs are one dependent
-// chain, the pixels are independent).  imgs [n_frames][n]; res [n_frames][n], slice 0 = r0 (the initial resistance, formed
-// on the host as nsof_accum_frames_f64 forms it); current [n_frames - 1][n] = v_ds / res[f + 1] (optional).
-template <bool FITTED>
-__global__ __launch_bounds__(64) void k_frames_run(const double* __restrict__ imgs, int n_frames, double* __restrict__ w,
-                                                    double* __restrict__ res, double* __restrict__ current, size_t n,
-                                                    double dts, int n_sub, double th1, double th2, FrameArg<FITTED> model,
-                                                    double r0, double v_ds)
-{
-    const DevD p = frame_arg(model);
-    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    double ww = p.wini, b = imgs[i];
-    res[i] = r0;
-    for (int f = 0; f + 1 < n_frames; f++) {
-        const double a = b;
-        b = imgs[(size_t)(f + 1) * n + i];
-        ww = frame_pair(a, b, ww, dts, n_sub, th1, th2, p);
-        const double r = p.ron / exp(-p.lambda * (1 - ww));
-        res[(size_t)(f + 1) * n + i] = r;
-        if (current) current[(size_t)f * n + i] = v_ds / r;
-    }
-    w[i] = ww;
-}
-
-// The same run with a device model per (trial, cell) -- nsof_accum_frames_f64_maps_dev: thread g is trial g / n, cell g % n.
-// Every field of a thread's DevD is a scalar of the call or that thread's element of a plane [1 or n_trials][n] (trial
-// stride 0: shared by the trials); lambda and the initial resistance r0 are planes too, formed on the host with the
-// library's log / exp as the uniform entry forms its two scalars.  From there on the loop is k_frames_run's, statement for
-// statement, so a thread's bits are the uniform kernel's at that thread's parameters.  imgs [n_frames][n] is shared by the
-// trials; w [T][n], res [T][n_frames][n] (optional), current [T][n_frames - 1][n] (optional).
-enum { FM_VOFF, FM_VON, FM_KOFF, FM_KON, FM_SON, FM_SOFF, FM_BON, FM_BOFF, FM_ALPHAOFF, FM_ALPHAON, FM_RON, FM_LAMBDA, FM_WINI, FM_R0, FM_COUNT };
-struct FrameMaps {
-    const double* plane[FM_COUNT];   // nullptr: the field is the scalar
-    size_t stride[FM_COUNT];         // between the trials of a plane: 0 or n
-    double scalar[FM_COUNT];
-};
-__global__ __launch_bounds__(64) void k_frames_run_maps(const double* __restrict__ imgs, int n_frames, double* __restrict__ w,
-                                                         double* __restrict__ res, double* __restrict__ current, size_t n,
-                                                         size_t total, double dts, int n_sub, double th1, double th2, FrameMaps m,
-                                                         double v_ds)
-{
-    const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (g >= total) return;
-    const size_t trial = g / n, i = g - trial * n;
-    auto get = [&](int s) { return m.plane[s] ? m.plane[s][trial * m.stride[s] + i] : m.scalar[s]; };
-    const DevD p{get(FM_VOFF), get(FM_VON), get(FM_KOFF), get(FM_KON), get(FM_SON), get(FM_SOFF), get(FM_BON), get(FM_BOFF),
-                 get(FM_ALPHAOFF), get(FM_ALPHAON), get(FM_RON), get(FM_LAMBDA), get(FM_WINI)};
-    double* const rt = res ? res + trial * (size_t)n_frames * n : nullptr;
-    double* const ct = current ? current + trial * (size_t)(n_frames - 1) * n : nullptr;
-    double ww = p.wini, b = imgs[i];
-    if (rt) rt[i] = get(FM_R0);
-    for (int f = 0; f + 1 < n_frames; f++) {
-        const double a = b;
-        b = imgs[(size_t)(f + 1) * n + i];
-        ww = frame_pair(a, b, ww, dts, n_sub, th1, th2, p);
-        const double r = p.ron / exp(-p.lambda * (1 - ww));
-        if (rt) rt[(size_t)(f + 1) * n + i] = r;
-        if (ct) ct[(size_t)f * n + i] = v_ds / r;
-    }
-    w[g] = ww;
-}
-
 // Temporal-prior surface as an 8-bit frame.
 //   mode 0  the reference's bridge from device state to the gating input, g = uint8(clip(-3366 / log10(I) - 306, 0,
 //           255)) with I = V_ds / R, V_ds = 1 V (optical_flow_seg.py:426-431, simulationcode_v4_transistor_uav.m:36),
@@ -973,30 +823,6 @@ inline int grid_for(size_t n, int cap = 4096)
     return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
 }
 
-// event_mem_sim.py:20-34
-inline nsof_accum_params default_params()
-{
-    nsof_accum_params p;
-    p.alphaoff = 1; p.alphaon = 1; p.voff = -0.2; p.von = 0.1; p.koff = 51.03; p.kon = -2.91; p.son = 0.2; p.soff = 0.8;
-    p.bon = -5.12; p.boff = 3.10; p.Ron = 163305.0; p.Roff = 2104377.0; p.wini = 0.5;
-    p.dt = 5e-4;
-    p.refractory_us = 800;
-    return p;
-}
-
-// A parameter set the kernels can run (NULL: the defaults), with its float32 and float64 device forms; everything else is
-// refused before anything is launched.  The sign tests are made on the float32 values too: those are what the float32
-// kernels divide by and compare with.
-struct Model {
-    nsof_accum_params prm;
-    DevF f;
-    DevD d;
-    float wini_f;
-    bool fitted;   // every field equals the fitted device's: the MK_FITTED kernel instantiations apply
-    // per-pixel parameter maps (nsof_accum_set_param_maps; the planes belong to the accumulator's ParamMaps)
-    bool mapped = false;
-    MapF map{nullptr, nullptr, nullptr, 0.f};
-};
 // f(KindTag<MK_FITTED>, NoModel) for the fitted device, f(KindTag<MK_UNIFORM>, DevF) for another one, f(KindTag<MK_MAPPED>,
 // MapF) with parameter maps: the kernel instantiation and its argument
 template <class Fn>
@@ -1020,12 +846,6 @@ void with_res(const Model& m, Fn&& f)
     if (m.mapped) f(MapRes{m.map.res});
     else f(m.f);
 }
-template <class Fn>
-void with_frame_model(const Model& m, Fn&& f)
-{
-    if (m.fitted) f(std::true_type{}, FittedD{m.d.lambda});
-    else f(std::false_type{}, m.d);
-}
 // The counter layout of a threshold: bits = ceil(log2(theta + 1)) per slice (theta >= 1, at most 31 bits).
 inline Theta theta_of(int theta)
 {
@@ -1040,41 +860,6 @@ void with_theta(int theta, Fn&& f)
     if (theta == 1) f(std::false_type{}, NoTheta{});
     else f(std::true_type{}, theta_of(theta));
 }
-int model_of(nsof_ctx* ctx, const nsof_accum_params* in, Model* m)
-{
-    const nsof_accum_params p = in ? *in : default_params();
-    const double fields[] = {p.alphaoff, p.alphaon, p.voff, p.von, p.koff, p.kon, p.son, p.soff, p.bon, p.boff, p.Ron, p.Roff, p.wini, p.dt};
-    static const char* const names[] = {"alphaoff", "alphaon", "voff", "von", "koff", "kon", "son", "soff", "bon", "boff", "Ron", "Roff", "wini", "dt"};
-    for (int i = 0; i < 14; i++)
-        if (!std::isfinite(fields[i]) || !std::isfinite((float)fields[i]))
-            return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameter %s = %g is not a finite float32", names[i], fields[i]);
-    if (!(p.voff < 0 && 0 < p.von) || !((float)p.voff < 0.f && 0.f < (float)p.von))
-        return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: voff < 0 < von required (voff %g, von %g)", p.voff, p.von);
-    if (!(p.son >= 0 && p.son <= 1 && p.soff >= 0 && p.soff <= 1))
-        return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: son, soff must lie in [0, 1] (son %g, soff %g)", p.son, p.soff);
-    if (!(p.Ron > 0 && p.Roff > 0) || !((float)p.Ron > 0.f))
-        return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: Ron, Roff must be positive (Ron %g, Roff %g)", p.Ron, p.Roff);
-    if (!(p.wini >= 0 && p.wini <= 1)) return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: wini %g outside [0, 1]", p.wini);
-    if (!(p.dt > 0) || !((float)p.dt > 0.f)) return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: dt %g must be positive", p.dt);
-    if (p.refractory_us < 0)
-        return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: refractory_us %lld is negative", (long long)p.refractory_us);
-    const double lambda = std::log(p.Roff / p.Ron);
-    if (!std::isfinite(lambda)) return nsof_set_error(ctx, NSOF_EINVAL, "accumulator parameters: ln(Roff / Ron) is not finite");
-    m->prm = p;
-    m->f = DevF{(float)p.voff, (float)p.von, (float)p.koff, (float)p.kon, (float)p.son, (float)p.soff, (float)p.bon, (float)p.boff,
-                (float)p.alphaoff, (float)p.alphaon, (float)p.dt, (float)p.Ron, (float)(-lambda)};
-    m->d = DevD{p.voff, p.von, p.koff, p.kon, p.son, p.soff, p.bon, p.boff, p.alphaoff, p.alphaon, p.Ron, lambda, p.wini};
-    m->wini_f = (float)p.wini;
-    // The model's own fields decide (dt as the float32 the kernels multiply by; refractory_us never reaches a kernel).  The
-    // constants of fitted_f / fitted_d, neg_lam's literal included, are pinned by the tests that hold the default path to the
-    // correctly rounded reference bit for bit.
-    const nsof_accum_params q = default_params();
-    m->fitted = p.alphaoff == q.alphaoff && p.alphaon == q.alphaon && p.voff == q.voff && p.von == q.von && p.koff == q.koff &&
-                p.kon == q.kon && p.son == q.son && p.soff == q.soff && p.bon == q.bon && p.boff == q.boff && p.Ron == q.Ron &&
-                p.Roff == q.Roff && p.wini == q.wini && (float)p.dt == (float)q.dt;
-    return NSOF_OK;
-}
-
 // The set-up pass of the parameter maps (nsof_accum_set_param_maps), once per call: per pixel the DevF of that pixel -- a
 // mapped key's float32 value, an unmapped one's scalar -- and from it exactly what the uniform kernels form per launch:
 // drive_of at the accumulator's two voltages and (ron, neg_lam), neg_lam = (float)(-ln(Roff / Ron)) with the logarithm in
@@ -1195,16 +980,14 @@ extern "C" int nsof_accum_set_param_maps(nsof_accum* a, int n_maps, const int* k
 {
     if (!a) return NSOF_EINVAL;
     nsof_ctx* ctx = a->ctx;
-    static const char* const names[NSOF_ACCUM_KEY_COUNT] = {"alphaoff", "alphaon", "voff", "von", "koff", "kon", "son", "soff", "bon",
-                                                           "boff", "Ron", "Roff", "wini"};
     if (n_maps < 0 || n_maps > NSOF_ACCUM_KEY_COUNT || (n_maps > 0 && (!keys || !maps)))
         return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: %d maps (0..%d, with their keys and planes)", n_maps, NSOF_ACCUM_KEY_COUNT);
     const float* plane[NSOF_ACCUM_KEY_COUNT] = {};
     for (int j = 0; j < n_maps; j++) {
         const int k = keys[j];
         if (k < 0 || k >= NSOF_ACCUM_KEY_COUNT) return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: key %d is no parameter (0..%d)", k, NSOF_ACCUM_KEY_COUNT - 1);
-        if (!maps[j]) return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: the plane of %s is NULL", names[k]);
-        if (plane[k]) return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: %s given twice", names[k]);
+        if (!maps[j]) return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: the plane of %s is NULL", kKeyNames[k]);
+        if (plane[k]) return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: %s given twice", kKeyNames[k]);
         plane[k] = maps[j];
     }
     if (a->slice_counter != 0 || a->snap_count != 0)
@@ -1213,22 +996,11 @@ extern "C" int nsof_accum_set_param_maps(nsof_accum* a, int n_maps, const int* k
     const Model& mo = a->model;
     const size_t npx = a->npx;
     // the domain of model_of, per pixel of every plane, in the order the planes were given
-    for (int j = 0; j < n_maps; j++) {
-        const int k = keys[j];
-        const float* q = maps[j];
-        for (size_t i = 0; i < npx; i++) {
-            const float v = q[i];
-            const char* why = nullptr;
-            if (!std::isfinite(v)) why = "is not finite";
-            else if (k == NSOF_ACCUM_KEY_VOFF && !(v < 0.f)) why = "must be negative (voff < 0 < von)";
-            else if (k == NSOF_ACCUM_KEY_VON && !(v > 0.f)) why = "must be positive (voff < 0 < von)";
-            else if ((k == NSOF_ACCUM_KEY_SON || k == NSOF_ACCUM_KEY_SOFF || k == NSOF_ACCUM_KEY_WINI) && !(v >= 0.f && v <= 1.f)) why = "lies outside [0, 1]";
-            else if ((k == NSOF_ACCUM_KEY_RON || k == NSOF_ACCUM_KEY_ROFF) && !(v > 0.f)) why = "must be positive";
-            if (why)
-                return nsof_set_error(ctx, NSOF_EINVAL, "parameter map %s: pixel (row %zu, column %zu) = %g %s", names[k], i / (size_t)a->W,
-                                      i % (size_t)a->W, (double)v, why);
-        }
-    }
+    for (int j = 0; j < n_maps; j++)
+        for (size_t i = 0; i < npx; i++)
+            if (const char* why = key_value_refused(keys[j], maps[j][i]))
+                return nsof_set_error(ctx, NSOF_EINVAL, "parameter map %s: pixel (row %zu, column %zu) = %g %s", kKeyNames[keys[j]],
+                                      i / (size_t)a->W, i % (size_t)a->W, (double)maps[j][i], why);
     if (plane[NSOF_ACCUM_KEY_RON] || plane[NSOF_ACCUM_KEY_ROFF])   // (two positive floats: the quotient is a finite positive double)
         for (size_t i = 0; i < npx; i++) {
             const double ron = plane[NSOF_ACCUM_KEY_RON] ? (double)plane[NSOF_ACCUM_KEY_RON][i] : mo.prm.Ron;
@@ -2007,271 +1779,4 @@ extern "C" int64_t nsof_accum_slice_bounds(const int64_t* t, int64_t n, int64_t 
         }
     }
     return nb;
-}
-
-// Frame-driven accumulator on HOST arrays: imgs float64 [n_frames][H][W] (compressed frames in [0,1]);
-// w_out float64 [H][W]; res_out float64 [n_frames][H][W] (initial state, then one snapshot per frame pair).
-extern "C" int nsof_accum_frames_f64(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
-                                     int n_sub_steps, double th1, double th2, double* w_out, double* res_out)
-{
-    return nsof_accum_frames_f64_p(ctx, imgs, n_frames, height, width, dt, n_sub_steps, th1, th2, nullptr, w_out, res_out);
-}
-
-// The same with the device model as an argument (NULL: the defaults); the step dt stays the argument it is, params->dt and
-// params->refractory_us are checked with the rest of the set and not read.
-extern "C" int nsof_accum_frames_f64_p(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
-                                       int n_sub_steps, double th1, double th2, const nsof_accum_params* params, double* w_out,
-                                       double* res_out)
-{
-    if (!ctx) return NSOF_EINVAL;
-    if (!imgs || !w_out || !res_out || n_frames < 1 || height < 1 || width < 1 || n_sub_steps < 1)
-        return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
-    Model model;
-    if (int rc = model_of(ctx, params, &model)) return rc;
-    const DevD& md = model.d;
-    NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t npx = (size_t)height * width;
-    nsof_dev_buf<double> img_buf, w_buf, res_buf;
-    int rc = img_buf.reserve(ctx, (size_t)n_frames * npx * 8);
-    if (!rc) rc = w_buf.reserve(ctx, npx * 8);
-    if (!rc) rc = res_buf.reserve(ctx, (size_t)n_frames * npx * 8);
-    double *d_img = img_buf.p, *d_w = w_buf.p, *d_res = res_buf.p;
-    if (!rc) {
-        std::vector<double> init(npx, md.wini), r0(npx, md.ron / std::exp(-md.lambda * (1 - md.wini)));
-        hipError_t e = hipMemcpyAsync(d_img, imgs, (size_t)n_frames * npx * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_w, init.data(), npx * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_res, r0.data(), npx * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        for (int f = 0; f + 1 < n_frames && e == hipSuccess; f++) {
-            with_frame_model(model, [&](auto D, auto fm) {
-                hipLaunchKernelGGL(k_frame_step<decltype(D)::value>, dim3((unsigned)((npx + 63) / 64)), dim3(64), 0, ctx->stream,
-                                   d_img + (size_t)f * npx, d_img + (size_t)(f + 1) * npx, d_w, d_res + (size_t)(f + 1) * npx,
-                                   npx, dt / n_sub_steps, n_sub_steps, th1, th2, fm);
-            });
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(w_out, d_w, npx * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(res_out, d_res, (size_t)n_frames * npx * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = nsof_set_error(ctx, NSOF_EDEVICE, "frame accumulator: %s", hipGetErrorString(e));
-    }
-    return rc;
-}
-
-// The same run on DEVICE arrays, one launch, nothing copied or synchronised: d_imgs [n_frames][H][W], d_w [H][W],
-// d_res [n_frames][H][W], d_current [n_frames - 1][H][W] = v_ds / d_res[f + 1] (may be NULL).  Same w and res as
-// nsof_accum_frames_f64, bit for bit: the same device functions in the same order per pixel.
-extern "C" int nsof_accum_frames_f64_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
-                                         int n_sub_steps, double th1, double th2, double v_ds, double* d_w, double* d_res,
-                                         double* d_current)
-{
-    return nsof_accum_frames_f64_p_dev(ctx, d_imgs, n_frames, height, width, dt, n_sub_steps, th1, th2, v_ds, nullptr, d_w, d_res,
-                                       d_current);
-}
-
-extern "C" int nsof_accum_frames_f64_p_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
-                                           int n_sub_steps, double th1, double th2, double v_ds, const nsof_accum_params* params,
-                                           double* d_w, double* d_res, double* d_current)
-{
-    if (!ctx) return NSOF_EINVAL;
-    if (!d_imgs || !d_w || !d_res || n_frames < 1 || height < 1 || width < 1 || n_sub_steps < 1)
-        return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
-    Model model;
-    if (int rc = model_of(ctx, params, &model)) return rc;
-    const DevD& md = model.d;
-    const size_t npx = (size_t)height * width;
-    if (npx > 0xffffffffull - 63) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "grid of %zu pixels: too large for one launch", npx);
-    NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    with_frame_model(model, [&](auto D, auto fm) {
-        hipLaunchKernelGGL(k_frames_run<decltype(D)::value>, dim3((unsigned)((npx + 63) / 64)), dim3(64), 0, ctx->stream, d_imgs,
-                           n_frames, d_w, d_res, d_current, npx, dt / n_sub_steps, n_sub_steps, th1, th2, fm,
-                           md.ron / std::exp(-md.lambda * (1 - md.wini)), v_ds);
-    });
-    NSOF_HIP(ctx, hipGetLastError());
-    return NSOF_OK;
-}
-
-// ---- the frame-driven run with a device model per (trial, cell) ------------------------------------------------------
-namespace {
-
-const char* const kKeyNames[NSOF_ACCUM_KEY_COUNT] = {"alphaoff", "alphaon", "voff", "von", "koff", "kon", "son", "soff", "bon",
-                                                     "boff", "Ron", "Roff", "wini"};
-
-// The planes of a mapped frame-driven call, per key (nullptr: the key keeps its scalar) with their trial counts.
-struct FramePlanes {
-    const double* plane[NSOF_ACCUM_KEY_COUNT] = {};
-    int trials[NSOF_ACCUM_KEY_COUNT] = {};
-    bool any = false;
-};
-
-// Everything that can refuse a mapped frame-driven call, decided on the host before anything is uploaded, launched or
-// written: the arguments, the scalars (model_of) and every value of every plane against model_of's domain -- the tests
-// on the float32 value included, so a plane is refused exactly where the uniform entry refuses that scalar.
-int frame_planes_of(nsof_ctx* ctx, int n_frames, int height, int width, int n_sub_steps, const nsof_accum_params* params,
-                    int n_trials, int n_maps, const int* keys, const double* const* planes, const int* plane_trials, Model* model,
-                    FramePlanes* fp)
-{
-    if (n_frames < 1 || height < 1 || width < 1 || n_sub_steps < 1)
-        return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
-    if (n_trials < 1) return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: %d trials (at least 1)", n_trials);
-    if (n_maps < 0 || n_maps > NSOF_ACCUM_KEY_COUNT || (n_maps > 0 && (!keys || !planes || !plane_trials)))
-        return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: %d maps (0..%d, with their keys, planes and trial counts)", n_maps,
-                              NSOF_ACCUM_KEY_COUNT);
-    for (int j = 0; j < n_maps; j++) {
-        const int k = keys[j];
-        if (k < 0 || k >= NSOF_ACCUM_KEY_COUNT)
-            return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: key %d is no parameter (0..%d)", k, NSOF_ACCUM_KEY_COUNT - 1);
-        if (!planes[j]) return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: the plane of %s is NULL", kKeyNames[k]);
-        if (fp->plane[k]) return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: %s given twice", kKeyNames[k]);
-        if (plane_trials[j] != 1 && plane_trials[j] != n_trials)
-            return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: the plane of %s holds %d trials (1 or %d)", kKeyNames[k],
-                                  plane_trials[j], n_trials);
-        fp->plane[k] = planes[j];
-        fp->trials[k] = plane_trials[j];
-        fp->any = true;
-    }
-    if (int rc = model_of(ctx, params, model)) return rc;
-    const size_t npx = (size_t)height * width;
-    for (int j = 0; j < n_maps; j++) {
-        const int k = keys[j];
-        const double* q = planes[j];
-        for (size_t e = 0; e < (size_t)plane_trials[j] * npx; e++) {
-            const double v = q[e];
-            const float vf = (float)v;
-            const char* why = nullptr;
-            if (!std::isfinite(v) || !std::isfinite(vf)) why = "is not a finite float32";
-            else if (k == NSOF_ACCUM_KEY_VOFF && !(v < 0 && vf < 0.f)) why = "must be negative (voff < 0 < von)";
-            else if (k == NSOF_ACCUM_KEY_VON && !(v > 0 && vf > 0.f)) why = "must be positive (voff < 0 < von)";
-            else if ((k == NSOF_ACCUM_KEY_SON || k == NSOF_ACCUM_KEY_SOFF || k == NSOF_ACCUM_KEY_WINI) && !(v >= 0 && v <= 1)) why = "lies outside [0, 1]";
-            else if (k == NSOF_ACCUM_KEY_RON && !(v > 0 && vf > 0.f)) why = "must be positive";
-            else if (k == NSOF_ACCUM_KEY_ROFF && !(v > 0)) why = "must be positive";
-            if (why)
-                return nsof_set_error(ctx, NSOF_EINVAL, "frame map %s: trial %zu, row %zu, column %zu = %g %s", kKeyNames[k], e / npx,
-                                      e % npx / (size_t)width, e % (size_t)width, v, why);
-        }
-    }
-    return NSOF_OK;
-}
-
-}  // namespace
-
-extern "C" int nsof_accum_frames_f64_maps_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
-                                              int n_sub_steps, double th1, double th2, double v_ds, const nsof_accum_params* params,
-                                              int n_trials, int n_maps, const int* keys, const double* const* planes,
-                                              const int* plane_trials, double* d_w, double* d_res, double* d_current)
-{
-    if (!ctx) return NSOF_EINVAL;
-    if (!d_imgs || !d_w) return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
-    Model model;
-    FramePlanes fp;
-    if (int rc = frame_planes_of(ctx, n_frames, height, width, n_sub_steps, params, n_trials, n_maps, keys, planes, plane_trials,
-                                 &model, &fp))
-        return rc;
-    if (!fp.any && n_trials == 1 && d_res)   // one device, one trial: the uniform entry
-        return nsof_accum_frames_f64_p_dev(ctx, d_imgs, n_frames, height, width, dt, n_sub_steps, th1, th2, v_ds, params, d_w,
-                                           d_res, d_current);
-    const size_t npx = (size_t)height * width;
-    if (npx > (0xffffffffull - 63) / (size_t)n_trials)
-        return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "%d trials of %zu cells: too large for one launch", n_trials, npx);
-    const size_t total = npx * (size_t)n_trials;
-    // lambda and r0 per (trial, cell) wherever Ron, Roff or wini is a plane: the host's log / exp, as the uniform entry's
-    const double *p_ron = fp.plane[NSOF_ACCUM_KEY_RON], *p_roff = fp.plane[NSOF_ACCUM_KEY_ROFF], *p_wini = fp.plane[NSOF_ACCUM_KEY_WINI];
-    const int t_lam = (p_ron || p_roff) ? std::max(fp.trials[NSOF_ACCUM_KEY_RON], fp.trials[NSOF_ACCUM_KEY_ROFF]) : 0;
-    const int t_r0 = (t_lam || p_wini) ? std::max(t_lam, fp.trials[NSOF_ACCUM_KEY_WINI]) : 0;
-    const nsof_accum_params& sp = model.prm;
-    auto at = [&](int k, double scalar, size_t t, size_t i) {
-        return fp.plane[k] ? fp.plane[k][(fp.trials[k] == 1 ? 0 : t) * npx + i] : scalar;
-    };
-    auto lambda_at = [&](size_t t, size_t i) {
-        return std::log(at(NSOF_ACCUM_KEY_ROFF, sp.Roff, t, i) / at(NSOF_ACCUM_KEY_RON, sp.Ron, t, i));
-    };
-    for (size_t e = 0; e < (size_t)t_lam * npx; e++)
-        if (!std::isfinite(lambda_at(e / npx, e % npx)))
-            return nsof_set_error(ctx, NSOF_EINVAL, "frame maps Ron / Roff: ln(Roff / Ron) is not finite at trial %zu, row %zu, column %zu",
-                                  e / npx, e % npx / (size_t)width, e % (size_t)width);
-    // slot -> key of nsof_accum_params (lambda and r0 have none)
-    static const int key_of[FM_COUNT] = {NSOF_ACCUM_KEY_VOFF, NSOF_ACCUM_KEY_VON, NSOF_ACCUM_KEY_KOFF, NSOF_ACCUM_KEY_KON,
-                                         NSOF_ACCUM_KEY_SON, NSOF_ACCUM_KEY_SOFF, NSOF_ACCUM_KEY_BON, NSOF_ACCUM_KEY_BOFF,
-                                         NSOF_ACCUM_KEY_ALPHAOFF, NSOF_ACCUM_KEY_ALPHAON, NSOF_ACCUM_KEY_RON, -1,
-                                         NSOF_ACCUM_KEY_WINI, -1};
-    const DevD& md = model.d;
-    FrameMaps fm;
-    const double scalars[FM_COUNT] = {md.voff, md.von, md.koff, md.kon, md.son, md.soff, md.bon, md.boff, md.alphaoff, md.alphaon,
-                                      md.ron, md.lambda, md.wini, md.ron / std::exp(-md.lambda * (1 - md.wini))};
-    size_t off[FM_COUNT], doubles = 0;
-    int trials[FM_COUNT];
-    for (int s = 0; s < FM_COUNT; s++) {
-        trials[s] = s == FM_LAMBDA ? t_lam : (s == FM_R0 ? t_r0 : fp.trials[key_of[s]]);
-        off[s] = doubles;
-        doubles += (size_t)trials[s] * npx;
-    }
-    NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    const double* d_planes = nullptr;
-    if (doubles) {   // one table, through the pinned copy: waits for this entry's previous upload only (or to grow)
-        const size_t bytes = doubles * sizeof(double);
-        if (int rc = ctx->frame_maps.stage(ctx, bytes, (bytes + bytes / 2 + 4095) & ~(size_t)4095)) return rc;
-        double* h = (double*)ctx->frame_maps.h.p;
-        for (int s = 0; s < FM_COUNT; s++) {
-            double* dst = h + off[s];
-            const size_t cnt = (size_t)trials[s] * npx;
-            if (s == FM_LAMBDA) {
-                for (size_t e = 0; e < cnt; e++) dst[e] = lambda_at(e / npx, e % npx);
-            } else if (s == FM_R0) {
-                for (size_t e = 0; e < cnt; e++) {
-                    const size_t t = e / npx, i = e % npx;
-                    const double lam = t_lam ? h[off[FM_LAMBDA] + (t_lam == 1 ? 0 : t) * npx + i] : md.lambda;
-                    dst[e] = at(NSOF_ACCUM_KEY_RON, sp.Ron, t, i) / std::exp(-lam * (1 - at(NSOF_ACCUM_KEY_WINI, sp.wini, t, i)));
-                }
-            } else if (cnt) {
-                memcpy(dst, fp.plane[key_of[s]], cnt * sizeof(double));
-            }
-        }
-        d_planes = (const double*)ctx->frame_maps.upload(ctx, bytes);
-        if (!d_planes) return NSOF_EDEVICE;
-    }
-    for (int s = 0; s < FM_COUNT; s++) {
-        fm.plane[s] = trials[s] ? d_planes + off[s] : nullptr;
-        fm.stride[s] = trials[s] > 1 ? npx : 0;
-        fm.scalar[s] = scalars[s];
-    }
-    hipLaunchKernelGGL(k_frames_run_maps, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, d_imgs, n_frames, d_w, d_res,
-                       d_current, npx, total, dt / n_sub_steps, n_sub_steps, th1, th2, fm, v_ds);
-    NSOF_HIP(ctx, hipGetLastError());
-    return NSOF_OK;
-}
-
-// The same on HOST frames and outputs: upload, the one launch, download -- the device entry's bits.
-extern "C" int nsof_accum_frames_f64_maps(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
-                                          int n_sub_steps, double th1, double th2, const nsof_accum_params* params, int n_trials,
-                                          int n_maps, const int* keys, const double* const* planes, const int* plane_trials,
-                                          double* w_out, double* res_out)
-{
-    if (!ctx) return NSOF_EINVAL;
-    if (!imgs || !w_out || !res_out) return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
-    {   // refuse before anything is allocated or copied
-        Model model;
-        FramePlanes fp;
-        if (int rc = frame_planes_of(ctx, n_frames, height, width, n_sub_steps, params, n_trials, n_maps, keys, planes, plane_trials,
-                                     &model, &fp))
-            return rc;
-    }
-    NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t npx = (size_t)height * width, nw = npx * (size_t)n_trials, nr = nw * (size_t)n_frames;
-    nsof_dev_buf<double> img_buf, w_buf, res_buf;
-    int rc = img_buf.reserve(ctx, (size_t)n_frames * npx * 8);
-    if (!rc) rc = w_buf.reserve(ctx, nw * 8);
-    if (!rc) rc = res_buf.reserve(ctx, nr * 8);
-    if (rc) return rc;
-    NSOF_HIP(ctx, hipMemcpyAsync(img_buf.p, imgs, (size_t)n_frames * npx * 8, hipMemcpyHostToDevice, ctx->stream));
-    rc = nsof_accum_frames_f64_maps_dev(ctx, img_buf.p, n_frames, height, width, dt, n_sub_steps, th1, th2, 1.0, params, n_trials,
-                                        n_maps, keys, planes, plane_trials, w_buf.p, res_buf.p, nullptr);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(w_out, w_buf.p, nw * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (!rc && e == hipSuccess) e = hipMemcpyAsync(res_out, res_buf.p, nr * 8, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t es = hipStreamSynchronize(ctx->stream);   // also before the buffers go
-    if (rc) return rc;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return nsof_set_error(ctx, NSOF_EDEVICE, "frame accumulator: %s", hipGetErrorString(e));
-    return NSOF_OK;
 }

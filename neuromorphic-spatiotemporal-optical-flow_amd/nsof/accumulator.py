@@ -74,67 +74,34 @@ def event_threshold(theta_events=None, version=1):
     return int(th)
 
 
-def param_maps_arg(param_maps, shape=None):
-    """Per-pixel parameter maps as the library takes them: ``[(key, float32 [H][W])]`` in ``_PARAM_KEYS`` order (``None`` or an
-    empty mapping: ``[]``).  Raises ``NsofValueError`` -- before any context exists or the library is called -- for a key that
-    is no device parameter (``won`` / ``woff``, ``dt`` and ``refractory_us`` stay scalars), a plane that is not ``shape`` (where
-    given) and a non-finite value.  The domain of each value (``voff < 0 < von``, ...) is the library's check."""
-    if param_maps is None:
-        return []
-    try:
-        items = dict(param_maps.items())
-    except AttributeError:
-        raise NsofValueError("param_maps must be a mapping of parameter name -> [H][W] array") from None
-    unknown = [k for k in items if k not in _PARAM_KEYS]
-    if unknown:
-        raise NsofValueError(f"param_maps: {unknown[0]!r} is not a per-pixel parameter (one of {', '.join(_PARAM_KEYS)})")
-    out = []
-    for k in _PARAM_KEYS:
-        if k not in items:
-            continue
-        try:
-            a = np.ascontiguousarray(items[k], np.float32)
-        except (TypeError, ValueError):
-            raise NsofValueError(f"param_maps[{k!r}] is not an array of numbers") from None
-        if a.ndim != 2 or (shape is not None and a.shape != tuple(shape)):
-            raise NsofValueError(f"param_maps[{k!r}] is {a.shape}, the array is {tuple(shape) if shape is not None else '[H][W]'}",
-                                 _lib.NSOF_ESHAPE)
-        if not np.isfinite(a).all():
-            r, c = (int(v) for v in np.argwhere(~np.isfinite(a))[0])
-            raise NsofValueError(f"param_maps[{k!r}][{r}][{c}] = {a[r, c]} is not finite")
-        out.append((k, a))
-    return out
-
-
-def frame_param_maps_arg(param_maps, shape=None):
-    """Per-cell, per-trial parameter planes as the frame-driven entries take them (``nsof_accum_frames_f64_maps*``):
-    ``(n_trials, [(key, float64 [1 or n_trials][H][W])])`` in ``_PARAM_KEYS`` order.  A plane is ``[H][W]`` (shared by the
-    trials) or ``[T][H][W]`` (one per trial), float32 or float64 -- read as float64, a float32 plane widened is exact;
-    ``n_trials`` is the ``T`` of the 3-D planes, 1 when every plane is 2-D (or the mapping is empty).  Raises
-    ``NsofValueError`` -- before any context exists or the library is called -- for a key that is no device parameter, a
-    plane that is neither 2-D nor 3-D or not ``shape`` (where given; ``NSOF_ESHAPE``), 3-D planes whose trial counts differ,
-    and a non-finite value.  The domain of each value (``voff < 0 < von``, ...) is the library's check."""
+def _plane_maps(param_maps, shape, dtype, trial_axis):
+    """``(n_trials, [(key, dtype [1 or n_trials][H][W])])`` in ``_PARAM_KEYS`` order of a ``param_maps`` mapping (``None`` or
+    empty: ``(1, [])``).  A plane is ``[H][W]`` or, with ``trial_axis``, ``[T][H][W]``; ``n_trials`` is the ``T`` of the 3-D
+    planes, 1 when every plane is 2-D.  Raises ``NsofValueError`` -- before any context exists or the library is called -- for
+    a key that is no device parameter (``won`` / ``woff``, ``dt`` and ``refractory_us`` stay scalars), a plane of the wrong
+    rank or not ``shape`` (where given; ``NSOF_ESHAPE``), 3-D planes whose trial counts differ, and a non-finite value.  The
+    domain of each value (``voff < 0 < von``, ...) is the library's check."""
+    layout = "[H][W] or [T][H][W]" if trial_axis else "[H][W]"
     if param_maps is None:
         return 1, []
     try:
         items = dict(param_maps.items())
     except AttributeError:
-        raise NsofValueError("param_maps must be a mapping of parameter name -> [H][W] or [T][H][W] array") from None
+        raise NsofValueError(f"param_maps must be a mapping of parameter name -> {layout} array") from None
     unknown = [k for k in items if k not in _PARAM_KEYS]
     if unknown:
-        raise NsofValueError(f"param_maps: {unknown[0]!r} is not a per-cell parameter (one of {', '.join(_PARAM_KEYS)})")
+        raise NsofValueError(f"param_maps: {unknown[0]!r} is not a {'per-cell' if trial_axis else 'per-pixel'} parameter (one of {', '.join(_PARAM_KEYS)})")
     out, trials = [], None
     for k in _PARAM_KEYS:
         if k not in items:
             continue
         try:
-            a = np.ascontiguousarray(items[k], np.float64)
+            a = np.ascontiguousarray(items[k], dtype)
         except (TypeError, ValueError):
             raise NsofValueError(f"param_maps[{k!r}] is not an array of numbers") from None
-        if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[0] < 1) or (shape is not None and a.shape[-2:] != tuple(shape)):
-            raise NsofValueError(f"param_maps[{k!r}] is {a.shape}, the array is "
-                                 f"{tuple(shape) if shape is not None else '[H][W]'} (with or without a leading trial axis)",
-                                 _lib.NSOF_ESHAPE)
+        if a.ndim not in ((2, 3) if trial_axis else (2,)) or 0 in a.shape[:-2] or (shape is not None and a.shape[-2:] != tuple(shape)):
+            raise NsofValueError(f"param_maps[{k!r}] is {a.shape}, the array is {tuple(shape) if shape is not None else '[H][W]'}"
+                                 + (" (with or without a leading trial axis)" if trial_axis else ""), _lib.NSOF_ESHAPE)
         if a.ndim == 3:
             if trials is not None and a.shape[0] != trials[1]:
                 raise NsofValueError(f"param_maps[{k!r}] holds {a.shape[0]} trials, param_maps[{trials[0]!r}] {trials[1]}",
@@ -144,9 +111,24 @@ def frame_param_maps_arg(param_maps, shape=None):
             a = a[None]
         if not np.isfinite(a).all():
             t, r, c = (int(v) for v in np.argwhere(~np.isfinite(a))[0])
-            raise NsofValueError(f"param_maps[{k!r}] trial {t}, row {r}, column {c} = {a[t, r, c]} is not finite")
+            where = f" trial {t}, row {r}, column {c}" if trial_axis else f"[{r}][{c}]"
+            raise NsofValueError(f"param_maps[{k!r}]{where} = {a[t, r, c]} is not finite")
         out.append((k, a))
     return (trials[1] if trials else 1), out
+
+
+def param_maps_arg(param_maps, shape=None):
+    """Per-pixel parameter maps as the accumulator takes them (``nsof_accum_set_param_maps``): ``[(key, float32 [H][W])]`` in
+    ``_PARAM_KEYS`` order; refusals as ``_plane_maps`` states them."""
+    return [(k, a[0]) for k, a in _plane_maps(param_maps, shape, np.float32, False)[1]]
+
+
+def frame_param_maps_arg(param_maps, shape=None):
+    """Per-cell, per-trial parameter planes as the frame-driven entries take them (``nsof_accum_frames_f64_maps*``):
+    ``(n_trials, [(key, float64 [1 or n_trials][H][W])])`` in ``_PARAM_KEYS`` order.  A plane is ``[H][W]`` (shared by the
+    trials) or ``[T][H][W]`` (one per trial), float32 or float64 -- read as float64, a float32 plane widened is exact;
+    refusals as ``_plane_maps`` states them."""
+    return _plane_maps(param_maps, shape, np.float64, True)
 
 
 def _frame_maps_c(n_trials, maps):
@@ -615,42 +597,35 @@ def simulate_frames(compressed_images, dt=0.0005, n_sub_steps=1000, th1=0.7, th2
     first, as the script stores them.  uav: th1=0.7, th2=1.5; vehicle: th1=2.  ``params``: the script's ``params`` struct as
     a mapping with the keys of ``PARAMS`` (``None``: ``PARAMS``), read as float64; ``dt`` is the argument it is.
     ``param_maps`` (a mapping key of ``PARAMS`` -> ``[H][W]`` or ``[T][H][W]`` array, ``frame_param_maps_arg``): a device per
-    cell and per trial, all ``T`` trials in one launch (``nsof_accum_frames_f64_maps``); the other keys keep the scalar of
+    cell and per trial, all ``T`` trials in one launch; the other keys keep the scalar of
     ``params``.  Both results then gain a leading trial axis -- ``w [T][H][W]``, ``resistances [T][n][H][W]`` -- also for
-    ``T`` = 1 (every plane 2-D); each (trial, cell) equals the uniform run at that cell's parameters bit for bit."""
+    ``T`` = 1 (every plane 2-D); each (trial, cell) equals the uniform run at that cell's parameters bit for bit.  Either
+    way it is one call of ``nsof_accum_frames_f64_maps``: without maps, one trial whose axis is dropped (a view)."""
     ap = accum_params(params)
     imgs = np.ascontiguousarray(compressed_images, np.float64)
     if imgs.ndim != 3:
         raise NsofValueError("compressed_images must be [n][H][W]")
     n, H, W = imgs.shape  # noqa: N806
-    if param_maps is not None:
-        trials, maps = frame_param_maps_arg(param_maps, (H, W))
-        ctx = ctx or default_context()
-        w = np.empty((trials, H, W), np.float64)
-        res = np.empty((trials, n, H, W), np.float64)
-        ctx.check(ctx._lib.nsof_accum_frames_f64_maps(ctx.ptr, imgs.ctypes.data, n, H, W, float(dt), int(n_sub_steps), float(th1),
-                                                      float(th2), C.byref(ap), trials, len(maps), *_frame_maps_c(trials, maps),
-                                                      w.ctypes.data, res.ctypes.data), "simulate_frames")
-        return w, res
+    trials, maps = frame_param_maps_arg(param_maps, (H, W))
     ctx = ctx or default_context()
-    w = np.empty((H, W), np.float64)
-    res = np.empty((n, H, W), np.float64)
-    ctx.check(ctx._lib.nsof_accum_frames_f64_p(ctx.ptr, imgs.ctypes.data, n, H, W, float(dt), int(n_sub_steps),
-                                               float(th1), float(th2), C.byref(ap), w.ctypes.data, res.ctypes.data),
-              "simulate_frames")
-    return w, res
+    w = np.empty((trials, H, W), np.float64)
+    res = np.empty((trials, n, H, W), np.float64)
+    ctx.check(ctx._lib.nsof_accum_frames_f64_maps(ctx.ptr, imgs.ctypes.data, n, H, W, float(dt), int(n_sub_steps), float(th1),
+                                                  float(th2), C.byref(ap), trials, len(maps), *_frame_maps_c(trials, maps),
+                                                  w.ctypes.data, res.ctypes.data), "simulate_frames")
+    return (w, res) if param_maps is not None else (w[0], res[0])
 
 
 def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, v_ds=1.0, *, ctx=None, params=None,
                         param_maps=None):
     """``simulate_frames`` on a float64 CUDA tensor [n][H][W] (``frames.process_images_dev``'s output) in one launch
-    (``nsof_accum_frames_f64_dev``): returns ``(w [H][W], resistances [n][H][W], current [n-1][H][W])`` as float64 CUDA
+    (``nsof_accum_frames_f64_maps_dev``, with or without maps): returns ``(w [H][W], resistances [n][H][W], current [n-1][H][W])`` as float64 CUDA
     tensors -- ``w`` and ``resistances`` equal ``simulate_frames`` bit for bit, ``current[f] = v_ds / resistances[f + 1]``
     is the device current after pair (f, f+1), the layout ``gating.roi_from_surface_dev`` reads.  Nothing is copied;
     asynchronous on the context's stream.  ``params`` as for ``simulate_frames``.
     ``param_maps`` as for ``simulate_frames`` (host arrays; they are uploaded through a buffer of the context): every
     result gains a leading trial axis -- ``w [T][H][W]``, ``resistances [T][n][H][W]``, ``current [T][n-1][H][W]`` -- and
-    ``current[t]`` is a gating stack of its own (``nsof_accum_frames_f64_maps_dev``)."""
+    ``current[t]`` is a gating stack of its own."""
     ap = accum_params(params)
     torch = _torch()
     if not isinstance(compressed, torch.Tensor) or not compressed.is_cuda:
@@ -661,25 +636,16 @@ def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.
         raise NsofValueError("simulate_frames_dev: contiguous [n][H][W] frames expected", _lib.NSOF_ESHAPE)
     n, H, W = (int(v) for v in compressed.shape)  # noqa: N806
     dev = compressed.device
-    if param_maps is not None:
-        trials, maps = frame_param_maps_arg(param_maps, (H, W))
-        ctx = ctx or default_context()
-        w = torch.empty((trials, H, W), dtype=torch.float64, device=dev)
-        res = torch.empty((trials, n, H, W), dtype=torch.float64, device=dev)
-        cur = torch.empty((trials, n - 1, H, W), dtype=torch.float64, device=dev)
-        ctx.check(ctx._lib.nsof_accum_frames_f64_maps_dev(ctx.ptr, dev_ptr(compressed), n, H, W, float(dt), int(n_sub_steps),
-                                                          float(th1), float(th2), float(v_ds), C.byref(ap), trials, len(maps),
-                                                          *_frame_maps_c(trials, maps), dev_ptr(w), dev_ptr(res),
-                                                          dev_ptr(cur) if n > 1 else None), "simulate_frames_dev")
-        return w, res, cur
+    trials, maps = frame_param_maps_arg(param_maps, (H, W))
     ctx = ctx or default_context()
-    w = torch.empty((H, W), dtype=torch.float64, device=dev)
-    res = torch.empty((n, H, W), dtype=torch.float64, device=dev)
-    cur = torch.empty((n - 1, H, W), dtype=torch.float64, device=dev)
-    ctx.check(ctx._lib.nsof_accum_frames_f64_p_dev(ctx.ptr, dev_ptr(compressed), n, H, W, float(dt), int(n_sub_steps),
-                                                   float(th1), float(th2), float(v_ds), C.byref(ap), dev_ptr(w), dev_ptr(res),
-                                                   dev_ptr(cur) if n > 1 else None), "simulate_frames_dev")
-    return w, res, cur
+    w = torch.empty((trials, H, W), dtype=torch.float64, device=dev)
+    res = torch.empty((trials, n, H, W), dtype=torch.float64, device=dev)
+    cur = torch.empty((trials, n - 1, H, W), dtype=torch.float64, device=dev)
+    ctx.check(ctx._lib.nsof_accum_frames_f64_maps_dev(ctx.ptr, dev_ptr(compressed), n, H, W, float(dt), int(n_sub_steps),
+                                                      float(th1), float(th2), float(v_ds), C.byref(ap), trials, len(maps),
+                                                      *_frame_maps_c(trials, maps), dev_ptr(w), dev_ptr(res),
+                                                      dev_ptr(cur) if n > 1 else None), "simulate_frames_dev")
+    return (w, res, cur) if param_maps is not None else (w[0], res[0], cur[0])
 
 
 def _save_outputs(prefix, out, version, slice_us, polarity, h5_path, params=None, dt=None, refractory_us=None,

@@ -10,7 +10,7 @@
              bytes it must read (frames x 1080 x 1920) over that time, as a share of 8 TB/s
   array run: ``simulate_frames_dev`` (one launch, one thread per grid cell), the same way
   join:      ``pipeline.gating_stack_from_frames_dev`` from BGR frames (gray conversion, compress, array run)
-  host:      ``frames.process_images`` (NumPy float64) + ``simulate_frames`` (one launch per pair, copies both ways) on the
+  host:      ``frames.process_images`` (NumPy float64) + ``simulate_frames`` (the same launch with copies both ways) on the
              same frames, timed once; and whether the device results equal the host chain bit for bit"""
 import argparse
 import json

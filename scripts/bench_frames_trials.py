@@ -9,7 +9,8 @@ simulate_frames_dev(params=...) calls -- the code before maps existed, what a us
 Two ways to call it.
   worker   bench_frames_trials.py [--tree DIR] [--configs uniform,trials]      one process, one JSON line.  --tree DIR measures
            the package under DIR (a checkout of another commit with its own libnsof.so; a tree without frame maps takes
-           --configs uniform).
+           --configs uniform).  --configs host (no session runs it) times the host entry, simulate_frames on host arrays, on
+           the same case.
   session  bench_frames_trials.py --parent DIR [--rounds 3] [--out profiles/frames_trials.json]
            starts workers alternately (the order swapped every round) -- parent at `uniform`, this tree at both -- `rounds`
            times in fresh processes and writes
@@ -88,6 +89,13 @@ def worker(a):
                 s["speedup_of_one_launch"] = round(s["ms"] / r["ms"], 2)
                 r["sequential_uniform_calls"] = s
             out["trials"][str(T)] = r
+    if "host" in a.configs:   # the host entry on the same case (simulate_frames on host arrays: copies both ways around the launch)
+        out["host"] = {}
+        h = frames.cpu().numpy()
+        for name, params in (("fitted", None), ("koff50", other)):
+            r = timed(lambda: A.simulate_frames(h, n_sub_steps=N_SUB, ctx=ctx, params=params), a.uniform_reps)   # noqa: B023
+            r["checksum"] = float(A.simulate_frames(h, n_sub_steps=N_SUB, ctx=ctx, params=params)[1].sum())
+            out["host"][name] = r
     ctx.close()
     print(json.dumps(out))
 

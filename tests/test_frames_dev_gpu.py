@@ -98,6 +98,9 @@ def _array_case(nsof_lib, ctx, grid, th):
 @pytest.mark.parametrize("th", THRESHOLDS)
 @pytest.mark.parametrize("grid", GRIDS)
 def test_array_run_equals_the_host_entry(nsof_lib, ctx, torch_dev, grid, th, v_ds):
+    """Host and device entry run one kernel, so this pins the PLUMBING of the two against each other -- the copies, the
+    layout of ``res`` and ``current``, ``v_ds``; the arithmetic itself is pinned by the recorded bits of
+    ``tests/test_frames_bits_gpu.py``."""
     import torch
     imgs, w_ref, res_ref = _array_case(nsof_lib, ctx, grid, th)
     assert np.unique(res_ref).size > 2          # the array moves: not the initial resistance everywhere
