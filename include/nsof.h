@@ -629,6 +629,40 @@ int nsof_accum_frames_f64_maps(nsof_ctx* ctx, const double* imgs, int n_frames, 
                                int n_sub_steps, double th1, double th2, const nsof_accum_params* params, int n_trials,
                                int n_maps, const int* keys, const double* const* planes, const int* plane_trials,
                                double* w_out, double* res_out);
+/* The EVENT-driven accumulator with a device model per pixel AND per trial: all n_trials Monte-Carlo trials of a
+ * device-variability study on one event stream, in one run.  Self-contained like nsof_accum_frames_f64_p_dev: no
+ * accumulator object, no resume.  Geometry, scheme, polarity_split, active_v, silent_v and params (NULL = the fitted device)
+ * as nsof_accum_create_p takes them, theta as nsof_accum_set_event_threshold (scheme 1 only beyond 1); x, y, p, t,
+ * slice_bounds and n_slices (>= 1) are HOST arrays as nsof_accum_step_events takes them (not retained).  keys / planes /
+ * plane_trials follow nsof_accum_frames_f64_maps_dev's convention with HOST float32 planes: plane_trials[j] is n_trials
+ * ([T][H][W]) or 1 ([H][W], shared by all trials); an unmapped key keeps the scalar of params.
+ * Outputs, DEVICE memory, A = 2 for scheme 2 with polarity_split, else 1:
+ *   d_w              float32 [A][T][H][W], the final state
+ *   d_resistance     float32 [A][T][H][W], resistance_exp of it
+ *   d_block_current  float64 [A][T][S][H / memsize][W / memsize], may be NULL (snap_every, memsize and v_ds are then not
+ *                    read): the block maximum of v_ds / R after the slices at which nsof_accum_step_events(snap_every)
+ *                    snapshots -- slice indices 0, k, 2k, ... -- so S = (n_slices - 1) / snap_every + 1.  No full-resolution
+ *                    snapshot is kept.
+ * Contract: trial t equals, bit for bit, the single-array path with trial t's planes -- nsof_accum_set_param_maps, then
+ * nsof_accum_step_events, nsof_accum_read_w / _read_resistance and nsof_accum_block_current_dev of snapshot s -- the same
+ * per-pixel arithmetic, neg_lam = (float)(-ln(Roff / Ron)) formed the same way, the state starting at the trial's wini.
+ * Which slices drive which pixel depends on the events alone (scheme 1's per-slice count against theta, scheme 2's
+ * refractory walk: one next_ok plane per array), so per group of up to 32 slices the events are scattered once, each
+ * touched pixel is resolved once, and T states are replayed with T drives.  That holds with silent_v in the dead zone
+ * [voff, von] of every pixel of every trial; otherwise every pixel is visited with its per-trial silent drive (a plain
+ * form).  The call returns once the run has finished (it synchronises the context's stream).
+ * NSOF_EINVAL, before anything is allocated, uploaded or launched: what the single-array entries refuse (geometry, scheme,
+ * params, theta < 1 or theta != 1 with scheme 2, slice bounds, an event outside the sensor), n_trials < 1, a key outside
+ * [0, NSOF_ACCUM_KEY_COUNT) or given twice, a NULL plane, plane_trials[j] other than 1 or n_trials, block currents with
+ * snap_every < 1, memsize outside [1, min(H, W)] or v_ds <= 0, and any plane value outside the domain
+ * nsof_accum_set_param_maps checks (ln(Roff / Ron) finite included) -- the message naming key, trial, row, column and value
+ * of the first one, planes in the order given.  NSOF_EUNSUPPORTED (likewise): more than 65535 trials or 2^31 events ("too
+ * large for one launch"). */
+int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int scheme, int polarity_split, float active_v, float silent_v,
+                          const nsof_accum_params* params, int theta, const int16_t* x, const int16_t* y, const int8_t* p,
+                          const int64_t* t, const int64_t* slice_bounds, int64_t n_slices, int64_t snap_every, int memsize,
+                          double v_ds, int n_trials, int n_maps, const int* keys, const float* const* planes,
+                          const int* plane_trials, float* d_w, float* d_resistance, double* d_block_current);
 /* compress_image of the same script (:111-121) for a stack of 8-bit DEVICE frames: imresize(im2double(frame), [out_h
  * out_w], 'lanczos3') of n_frames frames into d_out [n_frames][out_h][out_w] (DEVICE, dense float64).  d_frames points
  * at the first pixel of the region to compress -- a crop is a pointer offset plus width and height -- with row_stride and

@@ -1,0 +1,320 @@
+// The float32 state update of the event-driven accumulator as device code: what accum_kernels.hip (one array) and
+// accum_trials.hip (T Monte-Carlo trials of one stream) share -- the update arithmetic (update_one, Drive, drive_of,
+// update_drive, replay_driven, resistance_one), the scatter of a group of slices (k_scatter and its marks), scheme 1's
+// count threshold (Theta, driven_bits) and scheme 2's refractory walk (RefrTab, refractory_walk).  Everything sits in an
+// unnamed namespace, as in accum_model.h: each translation unit instantiates its own copies.
+#pragma once
+
+#include <type_traits>
+
+#include "accum_model.h"
+
+namespace {
+
+constexpr int MAX_GROUP = 32;
+
+// x ** b for the float32 state update, evaluated in double and rounded once (NumPy's float32 power is accurate to
+// about an ulp; this is correctly rounded except within ~1e-13 of a rounding boundary).  The library log()/exp() spend
+// most of their ~150 double-precision instructions on ranges and special cases that cannot occur here
+// (x = 1 - w*s lies in [0.2, 1] for a state in [0, 1]); the series below need ~55 and are accurate to 4e-14:
+//   log: x = m * 2^e with m in [sqrt(1/2), sqrt(2)), z = (m-1)/(m+1), log m = 2z(1 + z^2/3 + ... + z^14/15)
+//   exp: y = k ln2 + r with |r| <= ln2/2, exp r = sum r^n/n! (n <= 13), scaled by 2^k
+__device__ __forceinline__ double log_unit_range(double x)
+{
+    int e;
+    double m = frexp(x, &e);                       // m in [0.5, 1)
+    if (m < 0.70710678118654752440) { m *= 2.0; e -= 1; }
+    const double z = (m - 1.0) / (m + 1.0), w = z * z;
+    double p = 1.0 / 15.0;
+    p = fma(p, w, 1.0 / 13.0);
+    p = fma(p, w, 1.0 / 11.0);
+    p = fma(p, w, 1.0 / 9.0);
+    p = fma(p, w, 1.0 / 7.0);
+    p = fma(p, w, 1.0 / 5.0);
+    p = fma(p, w, 1.0 / 3.0);
+    p = fma(p, w, 1.0);
+    const double de = (double)e;
+    return fma(de, 0x1.62e42feep-1, fma(de, 0x1.a39ef35793c76p-33, 2.0 * z * p));   // e * ln2 in two parts
+}
+__device__ __forceinline__ double exp_small(double y)   // |y| < 700
+{
+    const double k = rint(y * 1.4426950408889634074);
+    const double r = fma(-k, 0x1.a39ef35793c76p-33, fma(-k, 0x1.62e42feep-1, y));
+    double p = 1.0 / 6227020800.0;
+    p = fma(p, r, 1.0 / 479001600.0);
+    p = fma(p, r, 1.0 / 39916800.0);
+    p = fma(p, r, 1.0 / 3628800.0);
+    p = fma(p, r, 1.0 / 362880.0);
+    p = fma(p, r, 1.0 / 40320.0);
+    p = fma(p, r, 1.0 / 5040.0);
+    p = fma(p, r, 1.0 / 720.0);
+    p = fma(p, r, 1.0 / 120.0);
+    p = fma(p, r, 1.0 / 24.0);
+    p = fma(p, r, 1.0 / 6.0);
+    p = fma(p, r, 0.5);
+    p = fma(p, r, 1.0);
+    p = fma(p, r, 1.0);
+    return ldexp(p, (int)k);
+}
+__device__ __forceinline__ float pow_f32(float x, float b)
+{
+    // A state outside [0,1] handed to the element-wise entry point can make x <= 0 or non-finite; the result then follows
+    // np.power on float32 operands (C99 powf): x ** 0 = 1 for every x, NaN included; a finite negative base gives nan for a
+    // non-integer exponent and (-1)^b |x|^b for an integer one; the bases 0 and -inf give 0 or inf by the sign of b, and
+    // carry the base's sign for an odd integer b.  (A float of magnitude >= 2^24 is an even integer.)
+    if (!(x > 0.f)) {
+        if (b == 0.f) return 1.f;
+        if (x != x) return x;
+        const bool whole = truncf(b) == b, odd = whole && fabsf(b) < 16777216.f && ((long long)b & 1);
+        if (x == 0.f || x == -__builtin_inff()) {
+            const float r = ((x == 0.f) == (b > 0.f)) ? 0.f : __builtin_inff();
+            return odd ? copysignf(r, x) : r;
+        }
+        if (!whole) return __builtin_nanf("");
+        const float r = (float)exp((double)b * log((double)-x));
+        return odd ? -r : r;
+    }
+    // The library path: a base far outside the model's range (1 - w*s lies in [0.2, 1] for the fitted device; another
+    // device's s may reach 0), or an exponent beyond 100 -- exp_small wants |b ln x| < 700, and |ln x| <= 6.91 on [1e-3, 2].
+    // The test on b is uniform: a scalar compare.
+    if (x > 2.f || x < 1e-3f || !(fabsf(b) <= 100.f)) return b == 0.f ? 1.f : (float)exp((double)b * log((double)x));
+    return (float)exp_small((double)b * log_unit_range((double)x));
+}
+
+// k * (V/v0 - 1) ** alpha: the first product of the reference's "k * A**alpha * B**b".  alpha == 1 (the fitted device) calls
+// no pow: x ** 1 is x.
+__device__ __forceinline__ float drive_gain(float V, float v0, float k, float alpha)
+{
+    const float a = V / v0 - 1.f;
+    return k * (alpha == 1.f ? a : pow_f32(a, alpha));
+}
+
+__device__ __forceinline__ float update_one(float w, float V, const DevF& p)
+{
+    float dwdt = 0.f;
+    if (V < p.voff) {
+        const float b = pow_f32(1.f - w * p.soff, p.boff);
+        dwdt = drive_gain(V, p.voff, p.koff, p.alphaoff) * b;
+    } else if (V > p.von) {
+        const float b = pow_f32(1.f - w * p.son, p.bon);
+        dwdt = drive_gain(V, p.von, p.kon, p.alphaon) * b;
+    }
+    const float wn = w + dwdt * p.dt;
+    return wn < 0.f ? 0.f : (wn > 1.f ? 1.f : wn);
+}
+
+// A slice's voltage is one of two values per run (active / silent), so everything of update_one that depends on V
+// alone is evaluated once: the branch taken, k * (V/v0 - 1) ** alpha (the first product of "k * A**alpha * B**b", same
+// rounding; the power, where alpha != 1, once per voltage and never per slice), and the (s, b) pair of the power term.  The
+// per-slice step is then branch-free: one pow, two multiplies, one add, the clip.
+struct Drive {
+    // dead zone: ka = 0 and the power term is (1 - w*0) ** 1 = 1 whatever the device's s and b, so dw = 0 * 1 = 0 and a finite
+    // w is unchanged bit for bit, as in update_one (a term like (1 - w*s) ** b could overflow for another device: 0 * inf)
+    float ka, s, b, dt;
+};
+__device__ __forceinline__ Drive drive_of(float V, const DevF& p)
+{
+    Drive d;
+    d.dt = p.dt;
+    if (V < p.voff) { d.ka = drive_gain(V, p.voff, p.koff, p.alphaoff); d.s = p.soff; d.b = p.boff; }
+    else if (V > p.von) { d.ka = drive_gain(V, p.von, p.kon, p.alphaon); d.s = p.son; d.b = p.bon; }
+    else { d.ka = 0.f; d.s = 0.f; d.b = 1.f; }
+    return d;
+}
+__device__ __forceinline__ float update_drive(float w, const Drive& d)
+{
+    const float wn = w + (d.ka * pow_f32(1.f - w * d.s, d.b)) * d.dt;
+    return wn < 0.f ? 0.f : (wn > 1.f ? 1.f : wn);
+}
+
+// resistance_exp: Ron / exp(-lam * (1 - w)), every operand float32 as NumPy makes them (the quotient of two floats formed in
+// double and rounded once is the float32 quotient)
+__device__ __forceinline__ float resistance_one(float w, const DevF& p)
+{
+    const float e = (float)exp((double)(p.neg_lam * (1.0f - w)));
+    return (float)((double)p.ron / (double)e);
+}
+
+// A pixel's drive and resistance constants from the planes k_setup_maps wrote.
+__device__ __forceinline__ Drive drive_at(const float* __restrict__ plane, size_t pix, float dt)
+{
+    const float* q = plane + 3 * pix;
+    return Drive{q[0], q[1], q[2], dt};
+}
+
+// Largest s in [0, n_sl) with bounds[s] <= e: the slice of event e.  bounds = event indices of the slice boundaries
+// (n_sl + 1 entries).
+__device__ __forceinline__ int slice_of(const long long* bounds, int n_sl, long long e)
+{
+    int lo = 0, hi = n_sl;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (bounds[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Marks (pixel, slice bit) in a mask of 32- or 64-bit words; a pixel's first touch in this group enters the compact list
+// once, so no two threads of the list update ever hold the same pixel.  The list's counter is ONE word: appended to per lane
+// it serialises every first touch of a group at the L2 atomic unit (~10 ns each: 300 us for the 33 k events of a 32-slice
+// group at 1 M events/s, found with rocprofv3), so the appends of a wave are aggregated -- one atomicAdd of the wave's
+// count, ranks from the ballot.  Call with the whole wave (inactive lanes pass active = false); list == nullptr
+// (every-pixel update: no list is read) skips the list entirely.
+__device__ __forceinline__ void list_append(unsigned* list, unsigned* count, unsigned pix, bool first)
+{
+    const unsigned long long b = __ballot(first);
+    if (!b) return;
+    const int lane = threadIdx.x & 63, leader = __ffsll((long long)b) - 1;
+    unsigned base = 0;
+    if (lane == leader) base = atomicAdd(count, (unsigned)__popcll(b));
+    base = __shfl(base, leader);
+    if (first) list[base + (unsigned)__popcll(b & ((1ull << lane) - 1ull))] = pix;
+}
+template <class MaskT>
+__device__ __forceinline__ void mark(MaskT* mask, unsigned* list, unsigned* count, unsigned pix, MaskT bit, bool active)
+{
+    const MaskT old = active ? atomicOr(&mask[pix], bit) : (MaskT)1;
+    if (!list) return;
+    list_append(list, count, pix, active && old == 0);
+}
+
+// Scheme 1's event-count threshold (THETA_EVENTS of event_mem_sim.py:33, :208-217: a pixel pulses in a slice when
+// bincount_2d(x[sl], y[sl]) >= theta).  theta == 1 is the mask bit above.  theta > 1: the same mask word holds one saturating
+// counter of `bits` = ceil(log2(theta + 1)) bits per slice instead of one bit, so a 32-bit word carries spw = 32 / bits
+// slices of a group and a 64-bit word 64 / bits; a compare-and-swap loop adds 1 and stops at theta, so a field never
+// carries into its neighbour however many events the cell receives (theta <= INT32_MAX: bits <= 31).  "old word == 0" is
+// still the pixel's first touch in the group -- a count of 1 makes the word non-zero -- so the list append is mark's; the
+// update kernels turn fields into driven bits (field == theta) as they load the word and clear it as they always did: no
+// plane, no launch and no clearing step is added, and a group simply holds fewer slices.
+struct Theta {
+    int theta, bits, spw;   // spw: slices per 32-bit word
+};
+struct NoTheta {};
+template <bool COUNT>
+using ThetaArg = std::conditional_t<COUNT, Theta, NoTheta>;   // theta == 1 passes nothing: the instantiations it always ran
+
+// One event of (pixel, the slice whose field starts at bit `shift`).
+template <class MaskT>
+__device__ __forceinline__ void mark_count(MaskT* mask, unsigned* list, unsigned* count, unsigned pix, int shift, const Theta& th,
+                                           bool active)
+{
+    MaskT old = 1;
+    if (active) {
+        const MaskT fm = ((MaskT)1 << th.bits) - 1, one = (MaskT)1 << shift;
+        // a stale value costs a retry and nothing else: fields only grow within a group, so "saturated" stays true, and
+        // the first touch is decided by the compare-and-swap that replaces 0
+        MaskT cur = __hip_atomic_load(&mask[pix], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (;;) {
+            old = cur;
+            if (((cur >> shift) & fm) >= (MaskT)th.theta) break;   // saturated (cur != 0: no first touch)
+            const MaskT seen = atomicCAS(&mask[pix], cur, cur + one);
+            if (seen == cur) break;
+            cur = seen;
+        }
+    }
+    if (!list) return;
+    list_append(list, count, pix, active && old == 0);
+}
+
+// Counter fields of a mask word -> one bit per slice whose count reached theta (bit s = the word's s-th field).
+template <class MaskT>
+__device__ __forceinline__ MaskT driven_bits(MaskT f, const Theta& th)
+{
+    const MaskT fm = ((MaskT)1 << th.bits) - 1;
+    MaskT m = 0;
+    for (int s = 0; f; s++, f >>= th.bits)
+        if ((f & fm) >= (MaskT)th.theta) m |= (MaskT)1 << s;
+    return m;
+}
+
+// One scatter per group of slices, both schemes: every event marks (pixel, its slice) in its array's mask.
+//   split == 0  every event -> array 0 (scheme 1 :208-217, scheme 2 magnitude; p is not read)
+//   split == 1  p == 1 -> array 0, p == 0 -> array 1 (:238, :250; other polarity values drive nothing)
+// Slices 32..63 of a group (scheme 1's every-pixel update only: n_sl <= 32 otherwise) go to the second mask word mask_hi.
+//   COUNT  scheme 1 with theta > 1 (no split): the event counts into its slice's field (mark_count); slices th.spw..2 * th.spw - 1
+//          of a group are the second word's
+template <bool COUNT>
+__global__ __launch_bounds__(256) void k_scatter(const short* __restrict__ x, const short* __restrict__ y,
+                                                  const signed char* __restrict__ p, long long ev0, long long n_ev,
+                                                  const long long* __restrict__ bounds, int n_sl, int W, int split,
+                                                  unsigned* mask0, unsigned* list0, unsigned* count0, unsigned* mask1,
+                                                  unsigned* list1, unsigned* count1, unsigned* mask_hi, ThetaArg<COUNT> th)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < n_ev;
+    const long long e = ev0 + (live ? i : 0);
+    int arr = 0;
+    if (split) {
+        const int pv = (int)p[e];
+        arr = pv == 1 ? 0 : (pv == 0 ? 1 : -1);
+    }
+    const int s = slice_of(bounds, n_sl, e);
+    if constexpr (COUNT) {
+        const unsigned pix = (unsigned)y[e] * (unsigned)W + (unsigned)x[e];
+        const bool hi = s >= th.spw;
+        mark_count(hi ? mask_hi : mask0, list0, count0, pix, (hi ? s - th.spw : s) * th.bits, th, live);
+    } else {
+        const unsigned pix = (unsigned)y[e] * (unsigned)W + (unsigned)x[e], bit = 1u << (s & 31);
+        mark(s < 32 ? mask0 : mask_hi, list0, count0, pix, bit, live && arr == 0);
+        if (split) mark(mask1, list1, count1, pix, bit, live && arr == 1);
+    }
+}
+
+// Scheme 2's refractory rule (event_mem_sim.py:237-269) looks like a chain over slices -- slice s+1 tests the next_ok that
+// slice s wrote -- but the chain is PER PIXEL: a pixel's next_ok depends on that pixel's own earlier events only, and within a
+// slice every event of a pixel sees the same next_ok (NumPy reads next_ok[ys, xs] before it writes).  So a group of up to 32
+// slices needs ONE scatter, "which slices have an event (of the array's polarity) at this pixel" (bit s of E), and the
+// eligibility walk moves into the fused state update: per touched pixel, over the set bits of E in slice order,
+//     if next_ok <= t_first[s]:  the pixel is driven in slice s;  next_ok = t_last[s] + REFRACTORY
+// with the per-slice constants in a 64-entry table.  No atomics on next_ok, two launches per group and array as in scheme 1.
+struct RefrTab {
+    long long t_first[32], t_next[32];
+};
+struct NoTab {};
+template <bool REFR>
+using TabArg = std::conditional_t<REFR, RefrTab, NoTab>;   // scheme 1 passes no table
+
+// slices with an event -> slices in which the pixel is driven; ok = the pixel's next_ok (updated)
+__device__ __forceinline__ unsigned refractory_walk(unsigned e, long long& ok, const long long* tf, const long long* tn)
+{
+    unsigned m = 0;
+    for (; e; e &= e - 1) {
+        const int s = __ffs((int)e) - 1;
+        if (ok <= tf[s]) {
+            m |= 1u << s;
+            ok = tn[s];
+        }
+    }
+    return m;
+}
+
+// The active drive once per set bit of m: the driven slices of a pixel in slice order (the silent ones are no-ops).
+template <class MaskT>
+__device__ __forceinline__ float replay_driven(float ww, MaskT m, const Drive& da)
+{
+    for (; m; m &= m - 1) ww = update_drive(ww, da);
+    return ww;
+}
+
+inline int grid_for(size_t n, int cap = 4096)
+{
+    size_t g = (n + 255) / 256;
+    return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
+}
+
+// The counter layout of a threshold: bits = ceil(log2(theta + 1)) per slice (theta >= 1, at most 31 bits).
+inline Theta theta_of(int theta)
+{
+    int bits = 1;
+    while ((1ll << bits) < (long long)theta + 1) bits++;
+    return Theta{theta, bits, 32 / bits};
+}
+// f(std::false_type, NoTheta) for theta == 1, f(std::true_type, Theta) for a count threshold
+template <class Fn>
+void with_theta(int theta, Fn&& f)
+{
+    if (theta == 1) f(std::false_type{}, NoTheta{});
+    else f(std::true_type{}, theta_of(theta));
+}
+
+}  // namespace

@@ -22,7 +22,7 @@ from .farneback import (OPTFLOW_FARNEBACK_GAUSSIAN, OPTFLOW_USE_INITIAL_FLOW, Fa
                         pinned_empty, uninstall)
 from .accumulator import (PARAMS, DT, THETA_EVENTS, REFRACTORY_US, Accumulator, accum_params, bincount_2d,  # noqa: F401
                           frame_param_maps_arg, generate_synthetic_events, load_events, resistance_exp, simulate, simulate_frames, simulate_frames_dev,
-                          slice_indices, update_state, variability_maps)
+                          simulate_trials, simulate_trials_dev, slice_indices, trial_param_maps_arg, update_state, variability_maps)
 
 from .gating import (GatingConfig, connectedComponentsWithStats, current_to_gray, dataset_config, frame_to_gray,  # noqa: F401,E402
                      gate_stats, gate_stats_dev, gating_maps, load_gating_stack, opticalFlow3D, process_merged_region, process_separate_regions, update_transition_pic)
@@ -32,7 +32,7 @@ from .segment import (MORPH_CROSS, MORPH_ELLIPSE, MORPH_RECT, dilate, erode, get
 from .predict import (BORDER_CONSTANT, BORDER_REPLICATE, INTER_LINEAR, calculateIntegralError, gray_u8_dev,  # noqa: F401,E402
                       predict_region, predict_region_dev, predict_sequence_dev, remap, ssim_batch_dev,
                       structural_similarity)
-from .pipeline import gating_stack_from_frames_dev, gating_variability_dev, prediction_sequence_dev, run_prediction, run_segmentation, segmentation_sequence_dev  # noqa: F401,E402
+from .pipeline import events_variability_dev, gating_stack_from_frames_dev, gating_variability_dev, prediction_sequence_dev, run_prediction, run_segmentation, segmentation_sequence_dev  # noqa: F401,E402
 from .frames import compress_image, crop_image, im2double, imresize_lanczos3, process_images, process_images_dev  # noqa: F401,E402
 from .flowviz import flow_to_image, flow_to_image_dev, flow_uv_to_colors, make_colorwheel, save_viz, viz  # noqa: F401,E402
 

@@ -107,6 +107,10 @@ SIGNATURES = {
                                             C.POINTER(_i), _vp, _vp, _vp]),
     "nsof_accum_frames_f64_maps": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _ap, _i, _i, C.POINTER(_i), C.POINTER(_vp),
                                         C.POINTER(_i), _vp, _vp]),
+    # ctx, H, W, scheme, split, active_v, silent_v, params, theta, x, y, p, t, bounds, n_slices, snap_every, memsize, v_ds,
+    # n_trials, n_maps, keys, planes, plane_trials, d_w, d_resistance, d_block_current
+    "nsof_accum_trials_dev": (_i, [_vp, _i, _i, _i, _i, _f, _f, _ap, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _d, _i, _i,
+                                   C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i), _vp, _vp, _vp]),
     "nsof_gate_stats_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "nsof_accum_destroy": (None, [_vp]),
     "nsof_accum_set_param_maps": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_vp)]),

@@ -131,6 +131,24 @@ def frame_param_maps_arg(param_maps, shape=None):
     return _plane_maps(param_maps, shape, np.float64, True)
 
 
+def trial_param_maps_arg(param_maps, shape=None):
+    """Per-pixel, per-trial parameter planes as the event-driven trial run takes them (``nsof_accum_trials_dev``):
+    ``(n_trials, [(key, float32 [1 or n_trials][H][W])])`` in ``_PARAM_KEYS`` order; a plane is ``[H][W]`` (shared by the
+    trials) or ``[T][H][W]``.  Refusals as ``_plane_maps`` states them, and -- so that nothing reaches the device first -- the
+    domain the library checks again (``voff < 0 < von``, ``son`` / ``soff`` / ``wini`` in [0, 1], ``Ron`` / ``Roff`` positive),
+    naming key, trial, row, column and value."""
+    trials, maps = _plane_maps(param_maps, shape, np.float32, True)
+    domain = dict(voff=(lambda a: a < 0, "must be negative (voff < 0 < von)"), von=(lambda a: a > 0, "must be positive (voff < 0 < von)"),
+                  Ron=(lambda a: a > 0, "must be positive"), Roff=(lambda a: a > 0, "must be positive"))
+    domain.update({k: (lambda a: (a >= 0) & (a <= 1), "lies outside [0, 1]") for k in ("son", "soff", "wini")})
+    for k, a in maps:
+        # (the extremes decide, without a temporary of the planes' size: every value is finite here)
+        if k in domain and not (domain[k][0](a.min()) and domain[k][0](a.max())):
+            t, r, c = (int(v) for v in np.argwhere(~domain[k][0](a))[0])
+            raise NsofValueError(f"param_maps[{k!r}] trial {t}, row {r}, column {c} = {a[t, r, c]} {domain[k][1]}")
+    return trials, maps
+
+
 def _frame_maps_c(n_trials, maps):
     """The ctypes arrays (keys, planes, plane_trials) of ``frame_param_maps_arg``'s result; the planes stay referenced by
     ``maps``."""
@@ -147,9 +165,10 @@ def variability_maps(H, W, rel_sigma, params=None, seed=0, trials=None, dtype=np
     drawn from ``np.random.default_rng(seed)`` in ``_PARAM_KEYS`` order -- the result does not depend on the mapping's order --
     and clipped into the model's domain: ``voff`` / ``von`` / ``koff`` / ``kon`` keep their sign, ``son`` / ``soff`` / ``wini``
     stay in [0, 1], ``Ron`` / ``Roff`` at least the smallest positive normal float32.
-    ``trials=T``: ``[T][H][W]`` planes for the Monte-Carlo trials of the frame-driven path (``simulate_frames*``'s
-    ``param_maps``), trial ``t`` exactly the planes of ``seed + t``.  ``dtype=np.float64`` keeps the planes unrounded (the
-    frame-driven path reads doubles), so a spread of 0 gives the nominal value itself."""
+    ``trials=T``: ``[T][H][W]`` planes for Monte-Carlo trials -- the ``param_maps`` of the frame-driven path
+    (``simulate_frames*``) and of the event-driven trial run (``simulate_trials*``) --, trial ``t`` exactly the planes of
+    ``seed + t``.  ``dtype=np.float64`` keeps the planes unrounded (the frame-driven path reads doubles), so a spread of 0
+    gives the nominal value itself; the event-driven path reads float32."""
     if trials is not None:
         if not isinstance(trials, (int, np.integer)) or isinstance(trials, (bool, np.bool_)) or trials < 1:
             raise NsofValueError(f"variability_maps: trials = {trials!r} is not a whole number >= 1")
@@ -587,6 +606,76 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
     if prefix is not None:
         _save_outputs(prefix, out, version, slice_us, polarity, h5_path, *used, theta_events=theta, param_maps=maps)
     return out
+
+
+def simulate_trials_dev(events, param_maps, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, polarity="split", *,
+                        sensor_size=None, params=None, dt=None, refractory_us=None, theta_events=None, snapshot_every=None,
+                        memsize=None, v_ds=1.0, ctx=None):
+    """Monte-Carlo device trials of the event-driven accumulator in one run (``nsof_accum_trials_dev``): ``events`` as for
+    ``simulate``, ``param_maps`` a mapping key of ``PARAMS`` -> ``[H][W]`` (shared by the trials) or ``[T][H][W]`` array read as
+    float32 (``trial_param_maps_arg``; ``variability_maps(..., trials=T)`` draws them), the other arguments as for
+    ``Accumulator``.  Returns a dict of CUDA tensors, ``A`` = 2 for ``version=2`` with ``polarity="split"``, else 1:
+    ``w`` float32 [A][T][H][W] the final states, ``resistance`` float32 [A][T][H][W], and with ``memsize`` also
+    ``block_current`` float64 [A][T][S][H // memsize][W // memsize] -- the block maxima of ``v_ds / R`` after the slices at
+    which ``Accumulator.step(snap_every=snapshot_every)`` snapshots (``snapshot_every=None``: ``simulate``'s cadence,
+    ``max(1, nslices // 100)``), what ``block_current_dev(memsize, snapshot=s)`` gives; ``block_current[0][t]`` is a gating
+    stack.  Trial ``t`` equals ``Accumulator(param_maps=planes[t])`` stepped over the same stream bit for bit; the events are
+    scattered and resolved once for all trials.  Every refusal -- arguments, shapes, the value domain of every plane -- comes
+    before any device work.  Synchronous."""
+    if version not in (1, 2):
+        raise NsofValueError("version must be 1 or 2")
+    if polarity not in ("split", "magnitude"):
+        raise NsofValueError("polarity must be 'split' or 'magnitude'")
+    ap = accum_params(params, dt, refractory_us)
+    theta = event_threshold(theta_events, version)
+    if isinstance(events, (str, Path)):
+        x, y, p, t, H, W = load_events(Path(events))  # noqa: N806
+    else:
+        x, y, p, t = events
+        x, y, t = np.asarray(x), np.asarray(y), np.asarray(t)
+        if x.size == 0:
+            raise NsofValueError("empty event stream")
+        H, W = (int(y.max()) + 1, int(x.max()) + 1) if sensor_size is None else (int(v) for v in sensor_size)  # noqa: N806
+    trials, maps = trial_param_maps_arg(param_maps, (H, W))
+    for name, v in (("snapshot_every", snapshot_every), ("memsize", memsize)):
+        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)) or v < 1):
+            raise NsofValueError(f"{name} = {v!r} is not a whole number >= 1")
+    if memsize is not None and memsize > min(H, W):
+        raise NsofValueError(f"memsize = {memsize} is larger than the {H}x{W} sensor")
+    if not v_ds > 0:
+        raise NsofValueError(f"v_ds = {v_ds!r} must be positive")
+    x16, y16 = np.ascontiguousarray(x, np.int16), np.ascontiguousarray(y, np.int16)
+    p8, t64 = np.ascontiguousarray(p, np.int8), np.ascontiguousarray(t, np.int64)
+    if not (x16.size == y16.size == p8.size == t64.size):
+        raise NsofValueError("event arrays of differing lengths")
+    idx = slice_index_array(t64, slice_us)
+    nslices = len(idx) - 1
+    if nslices < 1:
+        raise NsofValueError("the event stream holds no slice")
+    every = max(1, nslices // 100) if snapshot_every is None else int(snapshot_every)
+    split = version == 2 and polarity == "split"
+    torch = _torch()
+    ctx = ctx or default_context()
+    dev = torch.device("cuda", ctx.device)
+    narr = 2 if split else 1
+    out = dict(w=torch.empty((narr, trials, H, W), dtype=torch.float32, device=dev),
+               resistance=torch.empty((narr, trials, H, W), dtype=torch.float32, device=dev))
+    if memsize is not None:
+        out["block_current"] = torch.empty((narr, trials, (nslices - 1) // every + 1, H // int(memsize), W // int(memsize)),
+                                           dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)
+    ctx.check(ctx._lib.nsof_accum_trials_dev(ctx.ptr, H, W, version, int(split), float(active_v), float(silent_v), C.byref(ap), theta,
+                                             x16.ctypes.data, y16.ctypes.data, p8.ctypes.data, t64.ctypes.data, idx.ctypes.data,
+                                             nslices, every, 0 if memsize is None else int(memsize), float(v_ds), trials, len(maps),
+                                             *_frame_maps_c(trials, maps), dev_ptr(out["w"]), dev_ptr(out["resistance"]),
+                                             dev_ptr(out["block_current"]) if memsize is not None else None), "simulate_trials")
+    return out
+
+
+def simulate_trials(events, param_maps, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, polarity="split", **kw):
+    """``simulate_trials_dev`` with the results downloaded: the same dict of NumPy arrays."""
+    return {k: v.cpu().numpy() for k, v in simulate_trials_dev(events, param_maps, version, slice_us, active_v, silent_v, polarity,
+                                                               **kw).items()}
 
 
 def simulate_frames(compressed_images, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, *, ctx=None, params=None,

@@ -63,6 +63,55 @@ def events_to_rois(x, y, p, t, sensor_hw, cfg, version=1, polarity="split", slic
     return [(g[k], lists[k]) for k in range(n)]
 
 
+def events_variability_dev(x, y, p, t, sensor_hw, cfg, rel_sigma, trials, seed=0, version=1, polarity="split", slice_us=1000,
+                           active_v=-6.0, silent_v=0.0, snapshot_every=33, params=None, dt=None, refractory_us=None,
+                           theta_events=None, max_rects=32, ctx=None):
+    """What device-to-device variability does to the ROIs of an event stream, in HBM -- ``gating_variability_dev`` for the
+    event pipeline.  The nominal array (``params``; ``None``: ``PARAMS``) is run as ``events_to_rois`` runs it (an
+    ``Accumulator``, ``block_current_dev`` per snapshot); the ``trials`` arrays, whose pixels are drawn with the relative
+    spreads ``rel_sigma`` (``variability_maps(H, W, rel_sigma, params, seed, trials=trials)``: trial ``t`` is seed
+    ``seed + t``), take ONE trial run (``simulate_trials_dev``: the stream is scattered and resolved once for all of them).
+    Then one launch of gate statistics (``gating.gate_stats_dev`` at ``cfg.THRES``) and one gating call over all
+    ``trials * S`` maps of array 0 (``gating.roi_from_surface_dev``), ``S`` the number of snapshots.  Returns
+    ``gating_variability_dev``'s dict of CUDA tensors: ``nominal`` float64 [S][rows][cols], ``stacks`` float64
+    [T][S][rows][cols], ``counts`` int32 [S][rows][cols] and ``p_gate`` float64 (``counts / T``), ``flips`` int32 [T][S],
+    ``rects`` int32 [T][S][max_rects][4] with ``rect_counts`` int32 [T][S].  An empty ``rel_sigma``, or a spread of 0 on every
+    key, reproduces ``nominal`` in every trial bit for bit (a key whose spread is 0 keeps its scalar).  Synchronises at the end."""
+    import torch
+
+    from .accumulator import simulate_trials_dev, variability_maps
+    from .context import default_context
+    H, W = (int(v) for v in sensor_hw)  # noqa: N806
+    variability_maps(1, 1, rel_sigma, params, seed, trials=trials)   # refuses before any device work
+    ctx = ctx or default_context()
+    rows, cols = H // cfg.MEMSIZE, W // cfg.MEMSIZE
+    acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, params=params, dt=dt, refractory_us=refractory_us,
+                      theta_events=theta_events)
+    try:
+        acc.step(x, y, p, t, slice_index_array(t, slice_us), snap_every=snapshot_every)
+        n = acc.snapshot_count()
+        nominal = torch.empty((n, rows, cols), dtype=torch.float64, device=torch.device("cuda", ctx.device))
+        for k in range(n):
+            acc.block_current_dev(cfg.MEMSIZE, nominal[k], snapshot=k)
+        ctx.synchronize()
+    finally:
+        acc.close()
+    # the planes of the keys that do vary (the draws of the others are made all the same: a key's plane does not depend on
+    # which other spreads are zero)
+    maps = {k: v for k, v in variability_maps(H, W, rel_sigma, params, seed, trials=trials).items() if float(rel_sigma[k]) != 0.0}
+    if maps:
+        stacks = simulate_trials_dev((x, y, p, t), maps, version, slice_us, active_v, silent_v, polarity, sensor_size=(H, W),
+                                     params=params, dt=dt, refractory_us=refractory_us, theta_events=theta_events,
+                                     snapshot_every=snapshot_every, memsize=cfg.MEMSIZE, ctx=ctx)["block_current"][0]
+    else:
+        stacks = nominal.unsqueeze(0).repeat(int(trials), 1, 1, 1)
+    counts, flips = gating.gate_stats_dev(stacks, nominal, cfg.THRES, ctx=ctx)
+    rect_counts, rects = gating.roi_from_surface_dev(stacks, int(trials) * n, (rows, cols), (H, W), cfg, max_rects=max_rects, ctx=ctx)
+    ctx.synchronize()
+    return dict(nominal=nominal, stacks=stacks, counts=counts, p_gate=counts.to(torch.float64) / int(trials), flips=flips,
+                rects=rects.view(int(trials), n, max_rects, 4), rect_counts=rect_counts.view(int(trials), n))
+
+
 def events_to_rois_host(x, y, p, t, sensor_hw, cfg, version=1, polarity="split", slice_us=1000, active_v=-6.0,
                         silent_v=0.0, snapshot_every=33, ctx=None, params=None, dt=None, refractory_us=None, theta_events=None):
     """The same through the host-side mirror of the reference's gating (``gating.connectedComponentsWithStats`` on the
