@@ -96,63 +96,20 @@ __global__ __launch_bounds__(64) void k_frames_run(const double* __restrict__ im
     w[g] = ww;
 }
 
-// The planes of a mapped call, per key (nullptr: the key keeps its scalar) with their trial counts.
-struct FramePlanes {
-    const double* plane[NSOF_ACCUM_KEY_COUNT] = {};
-    int trials[NSOF_ACCUM_KEY_COUNT] = {};
-    bool any = false;
-    // the value of key k at (trial t, cell i): the plane's, or `scalar`
-    double at(int k, double scalar, size_t t, size_t i, size_t npx) const
-    {
-        return plane[k] ? plane[k][(trials[k] == 1 ? 0 : t) * npx + i] : scalar;
-    }
-    double lambda_at(const nsof_accum_params& sp, size_t t, size_t i, size_t npx) const
-    {
-        return std::log(at(NSOF_ACCUM_KEY_ROFF, sp.Roff, t, i, npx) / at(NSOF_ACCUM_KEY_RON, sp.Ron, t, i, npx));
-    }
-    int lambda_trials() const   // 0: lambda is the scalar
-    {
-        return std::max(trials[NSOF_ACCUM_KEY_RON], trials[NSOF_ACCUM_KEY_ROFF]);
-    }
-};
-
 // Everything that can refuse a frame-driven call, decided on the host before anything is uploaded, launched or written:
 // the arguments, the launch range, the scalars (model_of) and every value of every plane against the same domain
 // (key_value_refused) -- so a plane is refused exactly where the uniform entry refuses that scalar.
 int frame_planes_of(nsof_ctx* ctx, int n_frames, int height, int width, int n_sub_steps, const nsof_accum_params* params,
                     int n_trials, int n_maps, const int* keys, const double* const* planes, const int* plane_trials, Model* model,
-                    FramePlanes* fp)
+                    PlaneSet<double>* fp)
 {
     if (n_frames < 1 || height < 1 || width < 1 || n_sub_steps < 1)
         return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
-    if (n_trials < 1) return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: %d trials (at least 1)", n_trials);
-    if (n_maps < 0 || n_maps > NSOF_ACCUM_KEY_COUNT || (n_maps > 0 && (!keys || !planes || !plane_trials)))
-        return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: %d maps (0..%d, with their keys, planes and trial counts)", n_maps,
-                              NSOF_ACCUM_KEY_COUNT);
-    for (int j = 0; j < n_maps; j++) {
-        const int k = keys[j];
-        if (k < 0 || k >= NSOF_ACCUM_KEY_COUNT)
-            return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: key %d is no parameter (0..%d)", k, NSOF_ACCUM_KEY_COUNT - 1);
-        if (!planes[j]) return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: the plane of %s is NULL", kKeyNames[k]);
-        if (fp->plane[k]) return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: %s given twice", kKeyNames[k]);
-        if (plane_trials[j] != 1 && plane_trials[j] != n_trials)
-            return nsof_set_error(ctx, NSOF_EINVAL, "frame maps: the plane of %s holds %d trials (1 or %d)", kKeyNames[k],
-                                  plane_trials[j], n_trials);
-        fp->plane[k] = planes[j];
-        fp->trials[k] = plane_trials[j];
-        fp->any = true;
-    }
     if (int rc = model_of(ctx, params, model)) return rc;
+    if (int rc = plane_set_of(ctx, PlaneLabels{"frame maps", "frame map"}, *model, height, width, n_trials, n_maps, keys, planes,
+                              plane_trials, fp))
+        return rc;
     const size_t npx = (size_t)height * width;
-    for (int j = 0; j < n_maps; j++)
-        for (size_t e = 0; e < (size_t)plane_trials[j] * npx; e++)
-            if (const char* why = key_value_refused(keys[j], planes[j][e]))
-                return nsof_set_error(ctx, NSOF_EINVAL, "frame map %s: trial %zu, row %zu, column %zu = %g %s", kKeyNames[keys[j]],
-                                      e / npx, e % npx / (size_t)width, e % (size_t)width, planes[j][e], why);
-    for (size_t e = 0; e < (size_t)fp->lambda_trials() * npx; e++)
-        if (!std::isfinite(fp->lambda_at(model->prm, e / npx, e % npx, npx)))
-            return nsof_set_error(ctx, NSOF_EINVAL, "frame maps Ron / Roff: ln(Roff / Ron) is not finite at trial %zu, row %zu, column %zu",
-                                  e / npx, e % npx / (size_t)width, e % (size_t)width);
     if (npx > (0xffffffffull - 63) / (size_t)n_trials)
         return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "%d trials of %zu cells: too large for one launch", n_trials, npx);
     return NSOF_OK;
@@ -161,7 +118,7 @@ int frame_planes_of(nsof_ctx* ctx, int n_frames, int height, int width, int n_su
 // The kernel's FrameMaps of a mapped call: one table -- the caller's planes, then lambda and r0 per (trial, cell) wherever
 // Ron, Roff or wini is a plane, formed with the host's log / exp as model_of forms the two scalars -- through the pinned
 // copy of the context, which waits for this entry's previous upload only (or to grow).
-int frame_maps_upload(nsof_ctx* ctx, const Model& model, const FramePlanes& fp, size_t npx, FrameMaps* fm)
+int frame_maps_upload(nsof_ctx* ctx, const Model& model, const PlaneSet<double>& fp, size_t npx, FrameMaps* fm)
 {
     // slot -> key of nsof_accum_params (lambda and r0 have none)
     static const int key_of[FM_COUNT] = {NSOF_ACCUM_KEY_VOFF, NSOF_ACCUM_KEY_VON, NSOF_ACCUM_KEY_KOFF, NSOF_ACCUM_KEY_KON,
@@ -219,7 +176,7 @@ extern "C" int nsof_accum_frames_f64_maps_dev(nsof_ctx* ctx, const double* d_img
     if (!ctx) return NSOF_EINVAL;
     if (!d_imgs || !d_w) return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
     Model model;
-    FramePlanes fp;
+    PlaneSet<double> fp;
     if (int rc = frame_planes_of(ctx, n_frames, height, width, n_sub_steps, params, n_trials, n_maps, keys, planes, plane_trials,
                                  &model, &fp))
         return rc;
@@ -271,7 +228,7 @@ extern "C" int nsof_accum_frames_f64_maps(nsof_ctx* ctx, const double* imgs, int
     if (!imgs || !w_out || !res_out) return nsof_set_error(ctx, NSOF_EINVAL, "bad frame-accumulator arguments");
     {   // refuse before anything is allocated or copied
         Model model;
-        FramePlanes fp;
+        PlaneSet<double> fp;
         if (int rc = frame_planes_of(ctx, n_frames, height, width, n_sub_steps, params, n_trials, n_maps, keys, planes, plane_trials,
                                      &model, &fp))
             return rc;

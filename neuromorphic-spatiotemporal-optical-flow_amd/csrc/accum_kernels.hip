@@ -53,37 +53,11 @@ __device__ __forceinline__ DevF model_arg(const MapF& m)   // dt is all the pixe
     p.dt = m.dt;
     return p;
 }
-// The model resistance_one / surface_gray_value read (ron, neg_lam; mode 1 of the surface reads neither: no load): the
-// uniform device itself, or pixel pix of a mapped one.
-struct MapRes {
-    const float2* res;
-};
-__device__ __forceinline__ const DevF& res_at(const DevF& p, size_t, int) { return p; }
-__device__ __forceinline__ DevF res_at(const float2* __restrict__ res, size_t pix, int mode)
-{
-    DevF q{};
-    if (mode == 0) {
-        const float2 r = res[pix];
-        q.ron = r.x;
-        q.neg_lam = r.y;
-    }
-    return q;
-}
-__device__ __forceinline__ DevF res_at(MapRes m, size_t pix, int mode) { return res_at(m.res, pix, mode); }
-
 __global__ __launch_bounds__(256) void k_update_state(const float* __restrict__ w, const float* __restrict__ V,
                                                        float* __restrict__ out, size_t n, DevF p)
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
         out[i] = update_one(w[i], V[i], p);
-}
-
-//   ResT  DevF (one device) or MapRes (element i is pixel i of a mapped accumulator)
-template <class ResT>
-__global__ __launch_bounds__(256) void k_resistance(const float* __restrict__ w, float* __restrict__ out, size_t n, ResT p)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-        out[i] = resistance_one(w[i], res_at(p, i, 0));
 }
 
 __global__ __launch_bounds__(256) void k_fill(float* __restrict__ p, size_t n, float v)
@@ -557,50 +531,6 @@ void with_res(const Model& m, Fn&& f)
     if (m.mapped) f(MapRes{m.map.res});
     else f(m.f);
 }
-// The set-up pass of the parameter maps (nsof_accum_set_param_maps), once per call: per pixel the DevF of that pixel -- a
-// mapped key's float32 value, an unmapped one's scalar -- and from it exactly what the uniform kernels form per launch:
-// drive_of at the accumulator's two voltages and (ron, neg_lam), neg_lam = (float)(-ln(Roff / Ron)) with the logarithm in
-// double of the values as held (a plane's float32 widened, the scalar's double).
-struct MapSrc {
-    const float* plane[NSOF_ACCUM_KEY_COUNT];   // nullptr: the key is uniform
-    float scalar[NSOF_ACCUM_KEY_COUNT];
-    double ron, roff;                           // the scalars' doubles
-    float dt;
-};
-__global__ __launch_bounds__(256) void k_setup_maps(MapSrc src, size_t n, float v_act, float v_sil, float* __restrict__ act,
-                                                     float* __restrict__ sil, float2* __restrict__ res)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        auto get = [&](int k) { return src.plane[k] ? src.plane[k][i] : src.scalar[k]; };
-        DevF p;
-        p.alphaoff = get(NSOF_ACCUM_KEY_ALPHAOFF); p.alphaon = get(NSOF_ACCUM_KEY_ALPHAON);
-        p.voff = get(NSOF_ACCUM_KEY_VOFF); p.von = get(NSOF_ACCUM_KEY_VON);
-        p.koff = get(NSOF_ACCUM_KEY_KOFF); p.kon = get(NSOF_ACCUM_KEY_KON);
-        p.son = get(NSOF_ACCUM_KEY_SON); p.soff = get(NSOF_ACCUM_KEY_SOFF);
-        p.bon = get(NSOF_ACCUM_KEY_BON); p.boff = get(NSOF_ACCUM_KEY_BOFF);
-        p.dt = src.dt;
-        p.ron = get(NSOF_ACCUM_KEY_RON);
-        const double ron = src.plane[NSOF_ACCUM_KEY_RON] ? (double)p.ron : src.ron;
-        const double roff = src.plane[NSOF_ACCUM_KEY_ROFF] ? (double)src.plane[NSOF_ACCUM_KEY_ROFF][i] : src.roff;
-        p.neg_lam = (float)(-log(roff / ron));
-        const Drive da = drive_of(v_act, p), ds = drive_of(v_sil, p);
-        act[3 * i] = da.ka; act[3 * i + 1] = da.s; act[3 * i + 2] = da.b;
-        sil[3 * i] = ds.ka; sil[3 * i + 1] = ds.s; sil[3 * i + 2] = ds.b;
-        res[i] = make_float2(p.ron, p.neg_lam);
-    }
-}
-
-// List counters of the event-pixel update, [parity][array]: two sets used alternately.  A group's update kernels zero the
-// OTHER set -- the one the next group's scatter appends to -- so no group needs a memset (a launch of its own): one per call.
-struct ListCounts {
-    unsigned* base;
-    int par = 0;
-    hipError_t zero_all(hipStream_t s) const { return hipMemsetAsync(base, 0, 4 * sizeof(unsigned), s); }
-    unsigned* cur() const { return base + 2 * par; }
-    unsigned* next() const { return base + 2 * (par ^ 1); }
-    void flip() { par ^= 1; }
-};
-
 }  // namespace
 
 struct nsof_accum {
@@ -620,17 +550,11 @@ struct nsof_accum {
     nsof_dev_buf<unsigned short> tile_recs;
     nsof_dev_buf<unsigned> list[2];
     nsof_dev_buf<unsigned> count;  // [2]
-    // event staging
-    nsof_dev_buf<short> dx, dy;
-    nsof_dev_buf<signed char> dp;
-    nsof_dev_buf<long long> dbounds;
+    StagedStream ev;   // nsof_accum_set_events / the staging half of nsof_accum_step_events
     // snapshots
     nsof_dev_buf<float> snap[2];
     int64_t snap_cap = 0, snap_count = 0;
     int64_t slice_counter = 0;
-    // staged stream (nsof_accum_set_events / the staging half of nsof_accum_step_events): slice bounds relative to
-    // the first staged event, and for scheme 2 the first / last+refractory timestamp of every slice
-    std::vector<long long> h_rel, h_tfirst, h_tnext;
     Model model;             // the device the array is made of (nsof_accum_create_p): the scalars are fixed for the accumulator's life
     // per-pixel parameter maps (nsof_accum_set_param_maps): the raw float32 planes of the mapped keys (kept for
     // nsof_accum_read_param_map; the wini plane is what reset copies) and what k_setup_maps made of them (model.map points here)
@@ -670,51 +594,26 @@ extern "C" int nsof_accum_reset(nsof_accum* a)
     return NSOF_OK;
 }
 
-// Per-pixel parameter maps: see include/nsof.h.  Everything that can refuse the call -- the arguments, the accumulator's state,
-// the domain of every pixel of every plane -- is decided on the host before the accumulator or the device is touched; the
-// new planes are allocated aside and swapped in only once they are all there.
+// Per-pixel parameter maps: see include/nsof.h.  Everything that can refuse the call -- the accumulator's state, the plane list,
+// the domain of every pixel of every plane (plane_set_of, with one trial) -- is decided on the host before the accumulator or
+// the device is touched; the new planes are allocated aside and swapped in only once they are all there.
 extern "C" int nsof_accum_set_param_maps(nsof_accum* a, int n_maps, const int* keys, const float* const* maps)
 {
     if (!a) return NSOF_EINVAL;
     nsof_ctx* ctx = a->ctx;
-    if (n_maps < 0 || n_maps > NSOF_ACCUM_KEY_COUNT || (n_maps > 0 && (!keys || !maps)))
-        return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: %d maps (0..%d, with their keys and planes)", n_maps, NSOF_ACCUM_KEY_COUNT);
-    const float* plane[NSOF_ACCUM_KEY_COUNT] = {};
-    for (int j = 0; j < n_maps; j++) {
-        const int k = keys[j];
-        if (k < 0 || k >= NSOF_ACCUM_KEY_COUNT) return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: key %d is no parameter (0..%d)", k, NSOF_ACCUM_KEY_COUNT - 1);
-        if (!maps[j]) return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: the plane of %s is NULL", kKeyNames[k]);
-        if (plane[k]) return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: %s given twice", kKeyNames[k]);
-        plane[k] = maps[j];
-    }
     if (a->slice_counter != 0 || a->snap_count != 0)
         return nsof_set_error(ctx, NSOF_EINVAL, "set_param_maps: the accumulator has advanced (slice %lld, %lld snapshots); reset it first",
                               (long long)a->slice_counter, (long long)a->snap_count);
     const Model& mo = a->model;
     const size_t npx = a->npx;
-    // the domain of model_of, per pixel of every plane, in the order the planes were given
-    for (int j = 0; j < n_maps; j++)
-        for (size_t i = 0; i < npx; i++)
-            if (const char* why = key_value_refused(keys[j], maps[j][i]))
-                return nsof_set_error(ctx, NSOF_EINVAL, "parameter map %s: pixel (row %zu, column %zu) = %g %s", kKeyNames[keys[j]],
-                                      i / (size_t)a->W, i % (size_t)a->W, (double)maps[j][i], why);
-    if (plane[NSOF_ACCUM_KEY_RON] || plane[NSOF_ACCUM_KEY_ROFF])   // (two positive floats: the quotient is a finite positive double)
-        for (size_t i = 0; i < npx; i++) {
-            const double ron = plane[NSOF_ACCUM_KEY_RON] ? (double)plane[NSOF_ACCUM_KEY_RON][i] : mo.prm.Ron;
-            const double roff = plane[NSOF_ACCUM_KEY_ROFF] ? (double)plane[NSOF_ACCUM_KEY_ROFF][i] : mo.prm.Roff;
-            if (!std::isfinite(std::log(roff / ron)))
-                return nsof_set_error(ctx, NSOF_EINVAL, "parameter maps Ron / Roff: ln(Roff / Ron) is not finite at pixel (row %zu, column %zu)",
-                                      i / (size_t)a->W, i % (size_t)a->W);
-        }
-    // silent_v inside the dead zone of EVERY pixel (the float32 comparisons update_one makes): what decides between the
-    // event-pixel update / the no-op silent slices and the every-pixel pass with a per-pixel silent drive
-    bool dead = true;
-    {
-        const float* vo = plane[NSOF_ACCUM_KEY_VOFF];
-        const float* vn = plane[NSOF_ACCUM_KEY_VON];
-        for (size_t i = 0; i < npx && dead; i++)
-            dead = !(a->silent_v < (vo ? vo[i] : mo.f.voff)) && !(a->silent_v > (vn ? vn[i] : mo.f.von));
-    }
+    int one_trial[NSOF_ACCUM_KEY_COUNT];
+    std::fill(one_trial, one_trial + NSOF_ACCUM_KEY_COUNT, 1);
+    PlaneSet<float> ps;
+    if (int rc = plane_set_of(ctx, PlaneLabels{"set_param_maps", "parameter map"}, mo, a->H, a->W, 1, n_maps, keys, maps, one_trial, &ps))
+        return rc;
+    // what decides between the event-pixel update / the no-op silent slices and the every-pixel pass with a per-pixel
+    // silent drive
+    const bool dead = silent_in_every_dead_zone(ps, mo.f, a->silent_v, npx);
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     if (n_maps == 0) {   // back to the uniform model (the planes stay allocated for a later call)
         a->map_mask = 0;
@@ -726,27 +625,16 @@ extern "C" int nsof_accum_set_param_maps(nsof_accum* a, int n_maps, const int* k
     int rc = nact.reserve(ctx, npx * 3 * sizeof(float));
     if (!rc) rc = nsil.reserve(ctx, npx * 3 * sizeof(float));
     if (!rc) rc = nres.reserve(ctx, npx * 2 * sizeof(float));
-    for (int k = 0; k < NSOF_ACCUM_KEY_COUNT && !rc; k++)
-        if (plane[k]) rc = np_[k].reserve(ctx, npx * sizeof(float));
-    if (rc) return rc;
-    const float scal[NSOF_ACCUM_KEY_COUNT] = {mo.f.alphaoff, mo.f.alphaon, mo.f.voff, mo.f.von, mo.f.koff, mo.f.kon, mo.f.son, mo.f.soff,
-                                              mo.f.bon, mo.f.boff, mo.f.ron, (float)mo.prm.Roff, mo.wini_f};
     MapSrc src;
+    if (!rc) rc = upload_planes(ctx, mo, ps, npx, np_, &src);
+    if (rc) return rc;
     unsigned mask = 0;
-    for (int k = 0; k < NSOF_ACCUM_KEY_COUNT; k++) {
-        src.plane[k] = nullptr;
-        src.scalar[k] = scal[k];
-        if (!plane[k]) continue;
-        NSOF_HIP(ctx, hipMemcpyAsync(np_[k].p, plane[k], npx * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        src.plane[k] = np_[k].p;
-        mask |= 1u << k;
-    }
-    src.ron = mo.prm.Ron;
-    src.roff = mo.prm.Roff;
-    src.dt = mo.f.dt;
+    for (int k = 0; k < NSOF_ACCUM_KEY_COUNT; k++)
+        if (ps.plane[k]) mask |= 1u << k;
     const float v_act = a->scheme == 1 ? a->active_v : a->silent_v + a->active_v;
-    hipLaunchKernelGGL(k_setup_maps, dim3(grid_for(npx)), dim3(256), 0, ctx->stream, src, npx, v_act, a->silent_v, nact.p, nsil.p,
-                       reinterpret_cast<float2*>(nres.p));
+    // (one trial; the state is nsof_accum_reset's, below)
+    hipLaunchKernelGGL(k_setup_maps, dim3(grid_for(npx)), dim3(256), 0, ctx->stream, src, npx, 1, v_act, a->silent_v, nact.p, nsil.p,
+                       reinterpret_cast<float2*>(nres.p), (float*)nullptr, (float*)nullptr);
     NSOF_HIP(ctx, hipGetLastError());
     NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the caller's planes are not retained; the old ones are free to go
     for (int k = 0; k < NSOF_ACCUM_KEY_COUNT; k++) a->map_plane[k].swap(np_[k]);
@@ -886,53 +774,18 @@ static int accum_snapshot(nsof_accum* a)
     return NSOF_OK;
 }
 
-// Upload the events of slices [0, n_slices) (bounds sb index the caller's arrays) and keep what the slice loop needs
-// on the host: the bounds relative to the first uploaded event and, for scheme 2, every slice's first timestamp and
-// last timestamp + refractory period.
+// Stage the events of slices [0, n_slices) (StagedStream) and make room for the lists of touched pixels.
 static int accum_stage(nsof_accum* a, const int16_t* x, const int16_t* y, const int8_t* p, const int64_t* t,
                        const int64_t* sb, int64_t n_slices)
 {
     nsof_ctx* ctx = a->ctx;
-    if (n_slices < 0 || !sb) return nsof_set_error(ctx, NSOF_EINVAL, "bad slice bounds");
-    NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    const int64_t e0 = sb[0], e1 = sb[n_slices], n_ev = e1 - e0;
-    if (n_ev < 0) return nsof_set_error(ctx, NSOF_EINVAL, "slice bounds not monotone");
-    if (n_ev > 0 && (!x || !y || !t || (a->scheme == 2 && a->split && !p)))
-        return nsof_set_error(ctx, NSOF_EINVAL, "null event array");
-    for (int64_t s = 0; s < n_slices; s++)
-        if (sb[s + 1] < sb[s]) return nsof_set_error(ctx, NSOF_EINVAL, "slice bounds not monotone");
-    // validate coordinates on the host: an out-of-range event would be an out-of-bounds store on the device
-    for (int64_t e = e0; e < e1; e++)
-        if ((unsigned)x[e] >= (unsigned)a->W || (unsigned)y[e] >= (unsigned)a->H)
-            return nsof_set_error(ctx, NSOF_EINVAL, "event %lld at (%d,%d) outside the %dx%d sensor", (long long)e,
-                                  (int)x[e], (int)y[e], a->W, a->H);
-    const int narr = a->split ? 2 : 1;
-    int rc;
-    const size_t cap = (size_t)n_ev + (size_t)n_ev / 4 + 1024;   // events
-    if ((rc = a->dx.reserve(ctx, (size_t)n_ev * 2, cap * 2)) || (rc = a->dy.reserve(ctx, (size_t)n_ev * 2, cap * 2)) ||
-        (rc = a->dp.reserve(ctx, (size_t)n_ev, cap)))
-        return rc;
-    for (int i = 0; i < narr; i++)
-        if ((rc = a->list[i].reserve(ctx, (size_t)n_ev * sizeof(unsigned), cap * sizeof(unsigned)))) return rc;
-    if ((rc = a->dbounds.reserve(ctx, (size_t)(n_slices + 1) * 8))) return rc;
-    if (n_ev > 0) {
-        NSOF_HIP(ctx, hipMemcpyAsync(a->dx.p, x + e0, (size_t)n_ev * 2, hipMemcpyHostToDevice, ctx->stream));
-        NSOF_HIP(ctx, hipMemcpyAsync(a->dy.p, y + e0, (size_t)n_ev * 2, hipMemcpyHostToDevice, ctx->stream));
-        if (p) NSOF_HIP(ctx, hipMemcpyAsync(a->dp.p, p + e0, (size_t)n_ev, hipMemcpyHostToDevice, ctx->stream));
-    }
-    a->h_rel.resize((size_t)n_slices + 1);
-    for (int64_t s = 0; s <= n_slices; s++) a->h_rel[s] = (long long)(sb[s] - e0);
-    a->h_tfirst.assign((size_t)n_slices, 0);
-    a->h_tnext.assign((size_t)n_slices, 0);
-    if (a->scheme == 2)
-        for (int64_t s = 0; s < n_slices; s++)
-            if (sb[s + 1] > sb[s]) {
-                a->h_tfirst[s] = t[sb[s]];
-                a->h_tnext[s] = t[sb[s + 1] - 1] + a->model.prm.refractory_us;
-            }
-    NSOF_HIP(ctx, hipMemcpyAsync(a->dbounds.p, a->h_rel.data(), a->h_rel.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = a->ev.stage(ctx, a->W, a->H, a->scheme, a->split, a->model.prm.refractory_us, x, y, p, t, sb, n_slices)) return rc;
+    const size_t n_ev = (size_t)a->ev.rel.back();
+    int rc = NSOF_OK;
+    for (int i = 0; i < (a->split ? 2 : 1) && !rc; i++)
+        rc = a->list[i].reserve(ctx, n_ev * sizeof(unsigned), StagedStream::event_cap((int64_t)n_ev) * sizeof(unsigned));
     NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's arrays are not retained
-    return NSOF_OK;
+    return rc;
 }
 
 // Scheme 2 reads two timestamps per slice -- its first event's (the refractory test, event_mem_sim.py:243,253,265) and
@@ -943,12 +796,12 @@ extern "C" int nsof_accum_set_slice_times(nsof_accum* a, const int64_t* t_first,
 {
     if (!a) return NSOF_EINVAL;
     nsof_ctx* ctx = a->ctx;
-    if (!t_first || !t_last || n_slices != (int64_t)a->h_tfirst.size())
-        return nsof_set_error(ctx, NSOF_EINVAL, "set_slice_times: %lld slices given, %zu staged", (long long)n_slices, a->h_tfirst.size());
+    if (!t_first || !t_last || n_slices != (int64_t)a->ev.tfirst.size())
+        return nsof_set_error(ctx, NSOF_EINVAL, "set_slice_times: %lld slices given, %zu staged", (long long)n_slices, a->ev.tfirst.size());
     if (a->scheme != 2) return NSOF_OK;   // scheme 1 reads no timestamps
     for (int64_t s = 0; s < n_slices; s++) {
-        a->h_tfirst[s] = t_first[s];
-        a->h_tnext[s] = t_last[s] + a->model.prm.refractory_us;
+        a->ev.tfirst[s] = t_first[s];
+        a->ev.tnext[s] = t_last[s] + a->model.prm.refractory_us;
     }
     return NSOF_OK;
 }
@@ -985,13 +838,13 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
                          int surf_which = 0)
 {
     nsof_ctx* ctx = a->ctx;
-    if (s_begin < 0 || n_slices < 0 || (size_t)(s_begin + n_slices + 1) > a->h_rel.size())
+    if (s_begin < 0 || n_slices < 0 || (size_t)(s_begin + n_slices + 1) > a->ev.rel.size())
         return nsof_set_error(ctx, NSOF_EINVAL, "slices [%lld, %lld) outside the staged stream", (long long)s_begin,
                               (long long)(s_begin + n_slices));
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     const int narr = a->split ? 2 : 1;
     int rc;
-    const std::vector<long long>& rel = a->h_rel;
+    const std::vector<long long>& rel = a->ev.rel;
     const bool dead_zone = dead_zone_of(a);
     // Scheme 1 with the silent voltage in the dead zone: the event-pixel update (lists, groups of 32 slices) and the
     // every-pixel pass (groups of 64 slices, no lists) give the same bits; which one is faster depends on the sensor size.
@@ -1018,13 +871,7 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
     ListCounts cnt{a->count.p};
     if (sparse && s0 < s_end) NSOF_HIP(ctx, cnt.zero_all(ctx->stream));
     while (s0 < s_end) {
-        // group = up to max_group slices, ending right after the next snapshot slice
-        int64_t g = s_end - s0 < max_group ? s_end - s0 : max_group;
-        if (snap_every > 0) {
-            const int64_t c = a->slice_counter;
-            const int64_t to_snap = (c % snap_every == 0) ? 1 : (snap_every - c % snap_every) + 1;
-            if (to_snap < g) g = to_snap;
-        }
+        const int64_t g = group_len(s0, s_end, max_group, snap_every, a->slice_counter);
         const long long ge0 = rel[s0], ge1 = rel[s0 + g], gn = ge1 - ge0;
         if (sparse && gn == 0) NSOF_HIP(ctx, hipMemsetAsync(cnt.next(), 0, 2 * sizeof(unsigned), ctx->stream));   // no update kernel will
         if (gn > 0) {
@@ -1032,8 +879,8 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
             unsigned* const l0 = sparse ? a->list[0].p : nullptr;   // the every-pixel update reads no list
             unsigned* const l1 = sparse ? a->list[a->split].p : nullptr;
             with_theta(a->theta, [&](auto C, auto th) {
-                hipLaunchKernelGGL(k_scatter<decltype(C)::value>, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream, a->dx.p,
-                                   a->dy.p, a->dp.p, ge0, gn, a->dbounds.p + s0, (int)g, a->W, a->split, a->mask[0].p, l0, cnt.cur(),
+                hipLaunchKernelGGL(k_scatter<decltype(C)::value>, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, ctx->stream, a->ev.dx.p,
+                                   a->ev.dy.p, a->ev.dp.p, ge0, gn, a->ev.dbounds.p + s0, (int)g, a->W, a->split, a->mask[0].p, l0, cnt.cur(),
                                    a->mask[a->split].p, l1, cnt.cur() + 1, a->mask_hi.p, th);
             });
             NSOF_HIP(ctx, hipGetLastError());
@@ -1074,12 +921,7 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
                 with_theta(a->theta, [&](auto C, auto th) { update_c(R, tab, i, C, th); });
             };
             if (a->scheme == 2) {
-                RefrTab tab;
-                for (int s = 0; s < 32; s++) {
-                    const bool live = s < g && rel[s0 + s + 1] > rel[s0 + s];
-                    tab.t_first[s] = live ? a->h_tfirst[s0 + s] : 0;
-                    tab.t_next[s] = live ? a->h_tnext[s0 + s] : 0;
-                }
+                const RefrTab tab = refr_tab_of(a->ev, s0, g);
                 for (int i = 0; i < narr; i++) update(std::true_type{}, tab, i);
             } else {
                 update(std::false_type{}, NoTab{}, 0);
@@ -1089,7 +931,7 @@ static int accum_advance(nsof_accum* a, int64_t s_begin, int64_t n_slices, int64
         a->slice_counter += g;
         s0 += g;
         if (sparse) cnt.flip();
-        if (snap_every > 0 && (a->slice_counter - 1) % snap_every == 0)
+        if (snapshot_due(a->slice_counter, snap_every))
             if ((rc = accum_snapshot(a))) return rc;
     }
     return surf && !surf_done ? accum_surface(a, surf_which, *surf) : NSOF_OK;
@@ -1157,7 +999,7 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
     if (!surface_args_ok(a, which, mode, d_frames, row_stride) || n_frames < 0 || every < 1 || frame_stride < 0) return NSOF_EINVAL;
     nsof_ctx* ctx = a->ctx;
     if (n_frames == 0) return NSOF_OK;
-    if (first_slice < 0 || (size_t)(first_slice + n_frames * every + 1) > a->h_rel.size())
+    if (first_slice < 0 || (size_t)(first_slice + n_frames * every + 1) > a->ev.rel.size())
         return nsof_set_error(ctx, NSOF_EINVAL, "slices [%lld, %lld) outside the staged stream", (long long)first_slice,
                               (long long)(first_slice + n_frames * every));
     const bool dead_zone = dead_zone_of(a);
@@ -1175,7 +1017,7 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
     }
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
-    const std::vector<long long>& rel = a->h_rel;
+    const std::vector<long long>& rel = a->ev.rel;
     const long long ev0 = rel[first_slice], n_ev = rel[first_slice + n_frames * every] - ev0;
     // ---- the tile walk: whole run in four launches (frames write-only); needs 16-byte-addressable frame rows
     const bool tile_ok = (a->W & 15) == 0 && (row_stride & 15) == 0 && (frame_stride & 15) == 0 &&
@@ -1191,8 +1033,8 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
             (rc = a->tile_recs.reserve(ctx, (size_t)n_ev * 2, ((size_t)n_ev + (size_t)n_ev / 4 + 1024) * 2)))
             return rc;
         nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
-        hipLaunchKernelGGL(k_tile_bucket, dim3((unsigned)n_frames), dim3(1024), (size_t)ntiles * 4, ctx->stream, a->dx.p, a->dy.p, ev0,
-                           a->dbounds.p + first_slice, (int)every, a->W, ntiles, a->tile_off.p, a->tile_recs.p, (int)n_frames);
+        hipLaunchKernelGGL(k_tile_bucket, dim3((unsigned)n_frames), dim3(1024), (size_t)ntiles * 4, ctx->stream, a->ev.dx.p, a->ev.dy.p, ev0,
+                           a->ev.dbounds.p + first_slice, (int)every, a->W, ntiles, a->tile_off.p, a->tile_recs.p, (int)n_frames);
         with_uniform_model(a->model, [&](auto D, auto model) {
             hipLaunchKernelGGL(k_tile_frames<decltype(D)::value>, dim3((ntiles + 3) / 4), dim3(256), 0, ctx->stream, a->w[0].p, a->npx,
                                a->W, (const unsigned*)a->tile_off.p, (const unsigned short*)a->tile_recs.p, ntiles, (int)n_frames,
@@ -1224,7 +1066,7 @@ extern "C" int nsof_accum_run_frames(nsof_accum* a, int64_t first_slice, int64_t
                 const unsigned blocks = prev ? copy_blocks : (unsigned)((gn + 255) / 256);
                 with_theta(a->theta, [&](auto C, auto th) {
                     hipLaunchKernelGGL(k_frames_scatter_copy<decltype(C)::value>, dim3(blocks), dim3(256), 0, ctx->stream, prev, cur.out,
-                                       a->W, a->H, (long long)row_stride, a->dx.p, a->dy.p, ge0, gn, a->dbounds.p + s0, (int)rn,
+                                       a->W, a->H, (long long)row_stride, a->ev.dx.p, a->ev.dy.p, ge0, gn, a->ev.dbounds.p + s0, (int)rn,
                                        a->mask64.p, a->list[0].p, cnt.cur(), th);
                 });
             }
@@ -1363,13 +1205,10 @@ extern "C" int nsof_accum_read_resistance(nsof_accum* a, int which, float* out)
     nsof_dev_buf<float> tmp;
     int rc = tmp.reserve(ctx, a->npx * sizeof(float));
     if (rc) return rc;
-    if (a->model.mapped) {
-        hipLaunchKernelGGL(k_resistance<MapRes>, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[which].p, tmp.p, a->npx,
-                           MapRes{a->model.map.res});
-        if (hipGetLastError() != hipSuccess) rc = nsof_set_error(ctx, NSOF_EDEVICE, "resistance launch failed");
-    } else {
-        rc = nsof_accum_resistance_p_dev(ctx, &a->model.prm, a->w[which].p, tmp.p, a->npx);
-    }
+    with_res(a->model, [&](auto res) {
+        hipLaunchKernelGGL(k_resistance<decltype(res)>, dim3(grid_for(a->npx)), dim3(256), 0, ctx->stream, a->w[which].p, tmp.p, a->npx, res);
+    });
+    if (hipGetLastError() != hipSuccess) rc = nsof_set_error(ctx, NSOF_EDEVICE, "resistance launch failed");
     if (!rc) {
         hipError_t e = hipMemcpyAsync(out, tmp.p, a->npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1380,31 +1219,7 @@ extern "C" int nsof_accum_read_resistance(nsof_accum* a, int which, float* out)
 
 extern "C" int64_t nsof_accum_snapshot_count(const nsof_accum* a) { return a ? a->snap_count : 0; }
 
-// Block maximum of the device current I = v_ds / R over memsize x memsize pixel blocks: the gating image's input
-// (one value per block) formed on the device instead of from a downloaded surface.
-// max(v_ds / R) = v_ds / min(R) exactly (division by a positive float is monotone), so a block reduces min(R) in
-// float32 -- R from a stored snapshot, or resistance_one(w) of the current state -- and thread 0 divides in double.
-//   ResT  DevF (one device) or MapRes (per-pixel resistance constants, read where the source is the state)
-template <class ResT>
-__global__ __launch_bounds__(256) void k_block_min_resistance(const float* __restrict__ src, int is_w, int W, int memsize,
-                                                               int cols, ResT p, double v_ds, double* __restrict__ out)
-{
-    __shared__ float part[4];
-    const int bx = blockIdx.x, by = blockIdx.y;
-    const size_t base = ((size_t)by * memsize) * W + (size_t)bx * memsize;
-    float m = INFINITY;
-    for (int i = threadIdx.x; i < memsize * memsize; i += 256) {
-        const size_t pix = base + (size_t)(i / memsize) * W + (i % memsize);
-        const float v = src[pix];
-        m = fminf(m, is_w ? resistance_one(v, res_at(p, pix, 0)) : v);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) out[(size_t)by * cols + bx] = v_ds / (double)fminf(fminf(part[0], part[1]), fminf(part[2], part[3]));
-}
-
+// Block maximum of the device current (k_block_min_resistance) of the current state (snapshot < 0) or of a stored snapshot.
 extern "C" int nsof_accum_block_current(nsof_accum* a, int which, int64_t snapshot, int memsize, double v_ds, double* out)
 {
     if (!a || !out || which < 0 || which > (a->split ? 1 : 0) || memsize < 1 || memsize > a->W || memsize > a->H || !(v_ds > 0))
@@ -1419,7 +1234,7 @@ extern "C" int nsof_accum_block_current(nsof_accum* a, int which, int64_t snapsh
     const float* src = snapshot < 0 ? a->w[which].p : a->snap[which].p + (size_t)snapshot * a->npx;
     with_res(a->model, [&](auto res) {
         hipLaunchKernelGGL(k_block_min_resistance<decltype(res)>, dim3(cols, rows), dim3(256), 0, ctx->stream, src,
-                           snapshot < 0 ? 1 : 0, a->W, memsize, cols, res, v_ds, (double*)ctx->tmp.p);
+                           snapshot < 0 ? 1 : 0, a->W, memsize, cols, res, v_ds, (double*)ctx->tmp.p, (size_t)0, (size_t)0);
     });
     NSOF_HIP(ctx, hipGetLastError());
     NSOF_HIP(ctx, hipMemcpyAsync(out, ctx->tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1440,7 +1255,7 @@ extern "C" int nsof_accum_block_current_dev(nsof_accum* a, int which, int64_t sn
     const float* src = snapshot < 0 ? a->w[which].p : a->snap[which].p + (size_t)snapshot * a->npx;
     with_res(a->model, [&](auto res) {
         hipLaunchKernelGGL(k_block_min_resistance<decltype(res)>, dim3(cols, rows), dim3(256), 0, ctx->stream, src,
-                           snapshot < 0 ? 1 : 0, a->W, memsize, cols, res, v_ds, d_out);
+                           snapshot < 0 ? 1 : 0, a->W, memsize, cols, res, v_ds, d_out, (size_t)0, (size_t)0);
     });
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;

@@ -1,8 +1,10 @@
-// The device model of the synaptic accumulator as the host hands it to the kernels: what accum_kernels.hip (float32,
-// event-driven) and accum_frames.hip (float64, frame-driven) share.  Everything sits in an unnamed namespace: each of
-// the two translation units has its own copy, and DevF / DevD stay local to the unit whose kernel signatures name them.
+// The device model of the synaptic accumulator as the host hands it to the kernels, and the caller's parameter planes as the
+// host checks them: what accum_kernels.hip, accum_trials.hip (float32, event-driven) and accum_frames.hip (float64,
+// frame-driven) share.  Everything sits in an unnamed namespace: each of
+// the translation units has its own copy, and DevF / DevD stay local to the unit whose kernel signatures name them.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 
 #include "nsof_internal.h"
@@ -129,6 +131,92 @@ inline int model_of(nsof_ctx* ctx, const nsof_accum_params* in, Model* m)
                 p.kon == q.kon && p.son == q.son && p.soff == q.soff && p.bon == q.bon && p.boff == q.boff && p.Ron == q.Ron &&
                 p.Roff == q.Roff && p.wini == q.wini && (float)p.dt == (float)q.dt;
     return NSOF_OK;
+}
+
+// The caller's planes by key: plane[k] (nullptr: the key keeps its scalar) holds trials[k] trials, 1 or the call's n_trials.
+template <class T>
+struct PlaneSet {
+    const T* plane[NSOF_ACCUM_KEY_COUNT] = {};
+    int trials[NSOF_ACCUM_KEY_COUNT] = {};
+    bool any = false;
+    // the value of key k at (trial t, pixel i): the plane's, or `scalar`
+    template <class S>
+    S at(int k, S scalar, size_t t, size_t i, size_t npx) const
+    {
+        return plane[k] ? (S)plane[k][(trials[k] == 1 ? 0 : t) * npx + i] : scalar;
+    }
+    double lambda_at(const nsof_accum_params& sp, size_t t, size_t i, size_t npx) const
+    {
+        return std::log(at(NSOF_ACCUM_KEY_ROFF, sp.Roff, t, i, npx) / at(NSOF_ACCUM_KEY_RON, sp.Ron, t, i, npx));
+    }
+    int lambda_trials() const   // 0: lambda is the scalar
+    {
+        return std::max(trials[NSOF_ACCUM_KEY_RON], trials[NSOF_ACCUM_KEY_ROFF]);
+    }
+};
+
+// How an entry point's refusals begin: "<call>: ..." for the plane list, "<map> <key>: ..." for a value ("<map>s" for Ron / Roff).
+struct PlaneLabels {
+    const char *call, *map;
+};
+
+// Everything about a plane list that can refuse a call, on the host, before anything is uploaded or launched: the counts,
+// every key / plane / trial count of the list, then every value of every plane, in the order given, against the domain the
+// scalars have (key_value_refused) -- so a plane is refused exactly where model_of refuses that scalar -- then ln(Roff / Ron)
+// per (trial, pixel) wherever either is a plane.  `mo` holds the scalars of the unmapped keys; the planes are [trials][H][W].
+template <class T>
+int plane_set_of(nsof_ctx* ctx, PlaneLabels lb, const Model& mo, int height, int width, int n_trials, int n_maps, const int* keys,
+                 const T* const* planes, const int* plane_trials, PlaneSet<T>* ps)
+{
+    if (n_trials < 1) return nsof_set_error(ctx, NSOF_EINVAL, "%s: %d trials (at least 1)", lb.call, n_trials);
+    if (n_maps < 0 || n_maps > NSOF_ACCUM_KEY_COUNT || (n_maps > 0 && (!keys || !planes || !plane_trials)))
+        return nsof_set_error(ctx, NSOF_EINVAL, "%s: %d maps (0..%d, with their keys, planes and trial counts)", lb.call, n_maps,
+                              NSOF_ACCUM_KEY_COUNT);
+    for (int j = 0; j < n_maps; j++) {
+        const int k = keys[j];
+        if (k < 0 || k >= NSOF_ACCUM_KEY_COUNT)
+            return nsof_set_error(ctx, NSOF_EINVAL, "%s: key %d is no parameter (0..%d)", lb.call, k, NSOF_ACCUM_KEY_COUNT - 1);
+        if (!planes[j]) return nsof_set_error(ctx, NSOF_EINVAL, "%s: the plane of %s is NULL", lb.call, kKeyNames[k]);
+        if (ps->plane[k]) return nsof_set_error(ctx, NSOF_EINVAL, "%s: %s given twice", lb.call, kKeyNames[k]);
+        if (plane_trials[j] != 1 && plane_trials[j] != n_trials)
+            return nsof_set_error(ctx, NSOF_EINVAL, "%s: the plane of %s holds %d trials (1 or %d)", lb.call, kKeyNames[k],
+                                  plane_trials[j], n_trials);
+        ps->plane[k] = planes[j];
+        ps->trials[k] = plane_trials[j];
+        ps->any = true;
+    }
+    const size_t npx = (size_t)height * width, W = (size_t)width;
+    for (int j = 0; j < n_maps; j++)
+        for (size_t e = 0; e < (size_t)plane_trials[j] * npx; e++)
+            if (const char* why = key_value_refused(keys[j], planes[j][e]))
+                return nsof_set_error(ctx, NSOF_EINVAL, "%s %s: trial %zu, row %zu, column %zu = %g %s", lb.map, kKeyNames[keys[j]],
+                                      e / npx, e % npx / W, e % W, (double)planes[j][e], why);
+    for (size_t t = 0; t < (size_t)ps->lambda_trials(); t++) {
+        const T* const pon = ps->plane[NSOF_ACCUM_KEY_RON] ? ps->plane[NSOF_ACCUM_KEY_RON] + (ps->trials[NSOF_ACCUM_KEY_RON] == 1 ? 0 : t) * npx : nullptr;
+        const T* const poff = ps->plane[NSOF_ACCUM_KEY_ROFF] ? ps->plane[NSOF_ACCUM_KEY_ROFF] + (ps->trials[NSOF_ACCUM_KEY_ROFF] == 1 ? 0 : t) * npx : nullptr;
+        for (size_t i = 0; i < npx; i++) {
+            // (ln q is finite exactly for a finite q > 0 -- subnormal q included: decided without T * H * W logarithms)
+            const double q = (poff ? (double)poff[i] : mo.prm.Roff) / (pon ? (double)pon[i] : mo.prm.Ron);
+            if (!(q > 0 && std::isfinite(q)))
+                return nsof_set_error(ctx, NSOF_EINVAL, "%ss Ron / Roff: ln(Roff / Ron) is not finite at trial %zu, row %zu, column %zu",
+                                      lb.map, t, i / W, i % W);
+        }
+    }
+    return NSOF_OK;
+}
+
+// silent_v inside the dead zone [voff, von] of EVERY pixel of EVERY trial (the float32 comparisons update_one makes): an idle
+// pixel is then a bit-exact no-op.  The two thresholds are tested independently, so each plane is one flat pass.
+inline bool silent_in_every_dead_zone(const PlaneSet<float>& ps, const DevF& f, float silent_v, size_t npx)
+{
+    auto every_value = [&](int k, float scalar, auto&& ok) {
+        if (!ps.plane[k]) return ok(scalar);
+        for (size_t e = 0; e < (size_t)ps.trials[k] * npx; e++)
+            if (!ok(ps.plane[k][e])) return false;
+        return true;
+    };
+    return every_value(NSOF_ACCUM_KEY_VOFF, f.voff, [&](float v) { return !(silent_v < v); }) &&
+           every_value(NSOF_ACCUM_KEY_VON, f.von, [&](float v) { return !(silent_v > v); });
 }
 
 }  // namespace

@@ -6,7 +6,7 @@
 // What cannot differ between trials is done once.  Which slices drive which pixel depends on the events alone -- scheme
 // 1 compares a pixel's per-slice event count with theta, scheme 2 walks the event times against the pixel's next_ok, and
 // neither reads a device parameter -- so per group of up to 32 slices (th.spw with a count threshold), cut at the snapshot
-// slices exactly as the single-array path cuts them:
+// slices by the single-array path's group_len:
 //   k_scatter          (accum_update.h, unchanged) the group's events -> per-pixel mask words + the list of touched pixels
 //   k_trials_resolve   one thread per listed pixel: counter fields -> driven bits, scheme 2's refractory walk (ONE next_ok
 //                      plane per array, not T), the mask word cleared, the driven word stored parallel to the list, the
@@ -17,9 +17,10 @@
 // That form needs silent_v in the dead zone of EVERY pixel of EVERY trial (an idle pixel is then a bit-exact no-op).
 // Otherwise k_trials_update_all visits every pixel with its per-trial silent drive: one thread per pixel owns the mask
 // word and next_ok and walks the T trials itself -- the plain form; leaking arrays are not what the trial run is for.
-// k_trials_setup is k_setup_maps with a trial axis (and the initial state), k_trials_block_current is
-// k_block_min_resistance's reduction with one, taken from the state at the snapshot slices: no full-resolution snapshot
-// stack exists.
+// Everything else is the single-array path's own code (accum_model.h, accum_update.h): the check of the plane list, the staged
+// stream, the group cuts at the snapshot slices, and -- with the trial as a grid dimension -- k_setup_maps (which also writes the
+// initial state here), k_resistance and k_block_min_resistance, the latter taken from the state at the snapshot slices: no
+// full-resolution snapshot stack exists.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -30,53 +31,6 @@ namespace {
 
 constexpr int TRIAL_CHUNK = 4;       // trials per thread of k_trials_update
 constexpr int MAX_TRIALS = 65535;    // the trial axis is a grid dimension
-
-// The planes as the set-up pass reads them: the value of key k at (trial t, pixel i) is plane[k][t * stride[k] + i]
-// (stride 0: one plane shared by the trials) or, without a plane, scalar[k].
-struct TrialSrc {
-    const float* plane[NSOF_ACCUM_KEY_COUNT];
-    size_t stride[NSOF_ACCUM_KEY_COUNT];
-    float scalar[NSOF_ACCUM_KEY_COUNT];
-    double ron, roff;   // the scalars' doubles
-    float dt;
-};
-
-// Per (trial, pixel): the initial state (the trial's wini) of every array and, for the first drive_trials trials, what
-// k_setup_maps forms per pixel -- drive_of at the two voltages and (ron, neg_lam), neg_lam = (float)(-ln(Roff / Ron)) with the
-// logarithm in double of the values as held.  drive_trials is T, or 1 when no plane but wini has a trial axis.
-//   sil  nullptr where no kernel reads the silent drive (the touched-pixels form)
-__global__ __launch_bounds__(256) void k_trials_setup(TrialSrc src, size_t n, int drive_trials, float v_act, float v_sil,
-                                                       float* __restrict__ act, float* __restrict__ sil, float2* __restrict__ res,
-                                                       float* __restrict__ w0, float* __restrict__ w1)
-{
-    const size_t t = blockIdx.y;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        auto get = [&](int k) { return src.plane[k] ? src.plane[k][t * src.stride[k] + i] : src.scalar[k]; };
-        const size_t e = t * n + i;
-        const float wini = get(NSOF_ACCUM_KEY_WINI);
-        w0[e] = wini;
-        if (w1) w1[e] = wini;
-        if (t >= (size_t)drive_trials) continue;
-        DevF p;
-        p.alphaoff = get(NSOF_ACCUM_KEY_ALPHAOFF); p.alphaon = get(NSOF_ACCUM_KEY_ALPHAON);
-        p.voff = get(NSOF_ACCUM_KEY_VOFF); p.von = get(NSOF_ACCUM_KEY_VON);
-        p.koff = get(NSOF_ACCUM_KEY_KOFF); p.kon = get(NSOF_ACCUM_KEY_KON);
-        p.son = get(NSOF_ACCUM_KEY_SON); p.soff = get(NSOF_ACCUM_KEY_SOFF);
-        p.bon = get(NSOF_ACCUM_KEY_BON); p.boff = get(NSOF_ACCUM_KEY_BOFF);
-        p.dt = src.dt;
-        p.ron = get(NSOF_ACCUM_KEY_RON);
-        const double ron = src.plane[NSOF_ACCUM_KEY_RON] ? (double)p.ron : src.ron;
-        const double roff = src.plane[NSOF_ACCUM_KEY_ROFF] ? (double)get(NSOF_ACCUM_KEY_ROFF) : src.roff;
-        p.neg_lam = (float)(-log(roff / ron));
-        const Drive da = drive_of(v_act, p);
-        act[3 * e] = da.ka; act[3 * e + 1] = da.s; act[3 * e + 2] = da.b;
-        if (sil) {
-            const Drive ds = drive_of(v_sil, p);
-            sil[3 * e] = ds.ka; sil[3 * e + 1] = ds.s; sil[3 * e + 2] = ds.b;
-        }
-        res[e] = make_float2(p.ron, p.neg_lam);
-    }
-}
 
 // The group's refractory table in LDS (scheme 2), as the single-array update kernels hold it.
 template <bool REFR>
@@ -176,55 +130,6 @@ __global__ __launch_bounds__(256) void k_trials_update_all(float* __restrict__ w
     }
 }
 
-__device__ __forceinline__ float trial_resistance(float w, float2 r)
-{
-    DevF q{};
-    q.ron = r.x;
-    q.neg_lam = r.y;
-    return resistance_one(w, q);
-}
-
-// resistance_one of every (array, trial, pixel): w is [A][T][npx], res [T or 1][npx].
-__global__ __launch_bounds__(256) void k_trials_resistance(const float* __restrict__ w, const float2* __restrict__ res,
-                                                            size_t res_stride, size_t npx, int n_trials, size_t total,
-                                                            float* __restrict__ out)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const size_t pix = i % npx, t = i / npx % (size_t)n_trials;
-        out[i] = trial_resistance(w[i], res[t * res_stride + pix]);
-    }
-}
-
-// Block maximum of the device current v_ds / R of one array's T states (blockIdx.z: the trial): min(R) over the memsize x
-// memsize block in float32, one division in double -- what nsof_accum_block_current_dev forms from a stored snapshot of
-// resistance_one(w).  out points at this array's [T][n_snaps][rows][cols]; the launch fills snapshot `snap` of every trial.
-__global__ __launch_bounds__(256) void k_trials_block_current(const float* __restrict__ w, const float2* __restrict__ res,
-                                                               size_t res_stride, size_t npx, int W, int memsize, int cols,
-                                                               size_t snap, size_t n_snaps, double v_ds, double* __restrict__ out)
-{
-    __shared__ float part[4];
-    const int bx = blockIdx.x, by = blockIdx.y;
-    const size_t t = blockIdx.z;
-    const size_t base = ((size_t)by * memsize) * W + (size_t)bx * memsize;
-    float m = INFINITY;
-    for (int i = threadIdx.x; i < memsize * memsize; i += 256) {
-        const size_t pix = base + (size_t)(i / memsize) * W + (i % memsize);
-        m = fminf(m, trial_resistance(w[t * npx + pix], res[t * res_stride + pix]));
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        out[((t * n_snaps + snap) * gridDim.y + by) * cols + bx] = v_ds / (double)fminf(fminf(part[0], part[1]), fminf(part[2], part[3]));
-}
-
-// The caller's planes by key: plane[k] (nullptr: the key is uniform) holds trials[k] trials, 1 or n_trials.
-struct TrialPlanes {
-    const float* plane[NSOF_ACCUM_KEY_COUNT] = {};
-    int trials[NSOF_ACCUM_KEY_COUNT] = {};
-};
-
 }  // namespace
 
 extern "C" int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int scheme, int polarity_split, float active_v,
@@ -234,101 +139,49 @@ extern "C" int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int s
                                      const int* plane_trials, float* d_w, float* d_resistance, double* d_block_current)
 {
     if (!ctx) return NSOF_EINVAL;
-    // ---- everything that can refuse the call, on the host, before anything is allocated, uploaded or launched
+    // ---- everything that can refuse the call, on the host, before anything is uploaded or launched (the stream's own checks
+    // are StagedStream::stage's, below, ahead of its uploads)
     if (!d_w || !d_resistance) return nsof_set_error(ctx, NSOF_EINVAL, "accumulator trials: NULL output");
     if (height < 1 || width < 1 || (scheme != 1 && scheme != 2))
         return nsof_set_error(ctx, NSOF_EINVAL, "bad accumulator geometry %dx%d or scheme %d", height, width, scheme);
     if (theta < 1) return nsof_set_error(ctx, NSOF_EINVAL, "event threshold %d: at least 1 event", theta);
     if (scheme == 2 && theta != 1)
         return nsof_set_error(ctx, NSOF_EINVAL, "event threshold %d: scheme 2 has no count threshold (only 1 is accepted)", theta);
-    if (n_trials < 1) return nsof_set_error(ctx, NSOF_EINVAL, "accumulator trials: %d trials (at least 1)", n_trials);
-    if (n_maps < 0 || n_maps > NSOF_ACCUM_KEY_COUNT || (n_maps > 0 && (!keys || !planes || !plane_trials)))
-        return nsof_set_error(ctx, NSOF_EINVAL, "accumulator trials: %d maps (0..%d, with their keys, planes and trial counts)", n_maps,
-                              NSOF_ACCUM_KEY_COUNT);
-    TrialPlanes tp;
-    for (int j = 0; j < n_maps; j++) {
-        const int k = keys[j];
-        if (k < 0 || k >= NSOF_ACCUM_KEY_COUNT)
-            return nsof_set_error(ctx, NSOF_EINVAL, "accumulator trials: key %d is no parameter (0..%d)", k, NSOF_ACCUM_KEY_COUNT - 1);
-        if (!planes[j]) return nsof_set_error(ctx, NSOF_EINVAL, "accumulator trials: the plane of %s is NULL", kKeyNames[k]);
-        if (tp.plane[k]) return nsof_set_error(ctx, NSOF_EINVAL, "accumulator trials: %s given twice", kKeyNames[k]);
-        if (plane_trials[j] != 1 && plane_trials[j] != n_trials)
-            return nsof_set_error(ctx, NSOF_EINVAL, "accumulator trials: the plane of %s holds %d trials (1 or %d)", kKeyNames[k],
-                                  plane_trials[j], n_trials);
-        tp.plane[k] = planes[j];
-        tp.trials[k] = plane_trials[j];
-    }
     Model mo;
     if (int rc = model_of(ctx, params, &mo)) return rc;
+    PlaneSet<float> tp;
+    if (int rc = plane_set_of(ctx, PlaneLabels{"accumulator trials", "trial parameter map"}, mo, height, width, n_trials, n_maps, keys,
+                              planes, plane_trials, &tp))
+        return rc;
     const bool blocks = d_block_current != nullptr;
     if (blocks && (snap_every < 1 || memsize < 1 || memsize > width || memsize > height || !(v_ds > 0)))
         return nsof_set_error(ctx, NSOF_EINVAL, "accumulator trials: block currents need snap_every >= 1 (%lld), 1 <= memsize <= %d (%d), v_ds > 0 (%g)",
                               (long long)snap_every, std::min(width, height), memsize, v_ds);
     if (n_slices < 1 || !sb) return nsof_set_error(ctx, NSOF_EINVAL, "bad slice bounds");
-    const int64_t e0 = sb[0], n_ev = sb[n_slices] - e0;
-    if (n_ev < 0) return nsof_set_error(ctx, NSOF_EINVAL, "slice bounds not monotone");
+    const int64_t n_ev = sb[n_slices] - sb[0];
     const int split = (scheme == 2 && polarity_split) ? 1 : 0, narr = split ? 2 : 1;
-    if (n_ev > 0 && (!x || !y || !t || (split && !p))) return nsof_set_error(ctx, NSOF_EINVAL, "null event array");
-    for (int64_t s = 0; s < n_slices; s++)
-        if (sb[s + 1] < sb[s]) return nsof_set_error(ctx, NSOF_EINVAL, "slice bounds not monotone");
-    // an out-of-range event would be an out-of-bounds store on the device
-    for (int64_t e = e0; e < e0 + n_ev; e++)
-        if ((unsigned)x[e] >= (unsigned)width || (unsigned)y[e] >= (unsigned)height)
-            return nsof_set_error(ctx, NSOF_EINVAL, "event %lld at (%d,%d) outside the %dx%d sensor", (long long)e, (int)x[e], (int)y[e],
-                                  width, height);
     const size_t npx = (size_t)height * width, T = (size_t)n_trials;
-    // the domain of model_of, per pixel of every plane of every trial, in the order the planes were given
-    for (int j = 0; j < n_maps; j++)
-        for (size_t e = 0; e < (size_t)plane_trials[j] * npx; e++)
-            if (const char* why = key_value_refused(keys[j], planes[j][e]))
-                return nsof_set_error(ctx, NSOF_EINVAL, "trial parameter map %s: trial %zu, row %zu, column %zu = %g %s", kKeyNames[keys[j]],
-                                      e / npx, e % npx / (size_t)width, e % (size_t)width, (double)planes[j][e], why);
-    const int lam_trials = std::max(tp.trials[NSOF_ACCUM_KEY_RON], tp.trials[NSOF_ACCUM_KEY_ROFF]);
-    for (size_t tr = 0; tr < (size_t)lam_trials; tr++) {
-        const float* const pon = tp.plane[NSOF_ACCUM_KEY_RON] ? tp.plane[NSOF_ACCUM_KEY_RON] + (tp.trials[NSOF_ACCUM_KEY_RON] == 1 ? 0 : tr) * npx : nullptr;
-        const float* const poff = tp.plane[NSOF_ACCUM_KEY_ROFF] ? tp.plane[NSOF_ACCUM_KEY_ROFF] + (tp.trials[NSOF_ACCUM_KEY_ROFF] == 1 ? 0 : tr) * npx : nullptr;
-        for (size_t i = 0; i < npx; i++) {
-            // (ln q is finite exactly for a finite q > 0 -- subnormal q included: decided without T * H * W logarithms)
-            const double q = (poff ? (double)poff[i] : mo.prm.Roff) / (pon ? (double)pon[i] : mo.prm.Ron);
-            if (!(q > 0 && std::isfinite(q)))
-                return nsof_set_error(ctx, NSOF_EINVAL, "trial parameter maps Ron / Roff: ln(Roff / Ron) is not finite at trial %zu, row %zu, column %zu",
-                                      tr, i / (size_t)width, i % (size_t)width);
-        }
-    }
     if (npx > 0xFFFFFFFFull) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "sensor too large");
     if (n_trials > MAX_TRIALS || n_ev >= (1ll << 31))
         return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "%d trials of %zu pixels, %lld events: too large for one launch", n_trials, npx,
                               (long long)n_ev);
-    // silent_v inside the dead zone of EVERY pixel of EVERY trial (the float32 comparisons update_one makes): the
-    // touched-pixels form; otherwise the every-pixel form
-    // (the two thresholds are tested independently, so each plane is one flat pass)
-    auto every_value = [&](int k, float scalar, auto&& ok) {
-        if (!tp.plane[k]) return ok(scalar);
-        for (size_t e = 0; e < (size_t)tp.trials[k] * npx; e++)
-            if (!ok(tp.plane[k][e])) return false;
-        return true;
-    };
-    const bool dead = every_value(NSOF_ACCUM_KEY_VOFF, mo.f.voff, [&](float v) { return !(silent_v < v); }) &&
-                      every_value(NSOF_ACCUM_KEY_VON, mo.f.von, [&](float v) { return !(silent_v > v); });
+    // silent_v inside the dead zone of EVERY pixel of EVERY trial: the touched-pixels form; otherwise the every-pixel form
+    const bool dead = silent_in_every_dead_zone(tp, mo.f, silent_v, npx);
     // no plane but wini with a trial axis: the drives and resistance pairs are one set for all trials
     int drive_trials = 1;
     for (int k = 0; k < NSOF_ACCUM_KEY_COUNT; k++)
         if (k != NSOF_ACCUM_KEY_WINI && tp.trials[k] > 1) drive_trials = n_trials;
     const size_t n_drive = (size_t)drive_trials;
 
-    // ---- device memory: the staged stream, the planes, per-array masks / lists / next_ok, the per-trial drives
+    // ---- device memory: the staged stream (refusing a bad one), the planes, per-array masks / lists / next_ok, the per-trial drives
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    nsof_dev_buf<short> dx, dy;
-    nsof_dev_buf<signed char> dp;
-    nsof_dev_buf<long long> dbounds, next_ok[2];
+    StagedStream ev;
+    if (int rc = ev.stage(ctx, width, height, scheme, split, mo.prm.refractory_us, x, y, p, t, sb, n_slices)) return rc;
+    nsof_dev_buf<long long> next_ok[2];
     nsof_dev_buf<unsigned> mask[2], list[2], driven[2], count;
     nsof_dev_buf<float> dplane[NSOF_ACCUM_KEY_COUNT], dact, dsil, dres;
     const size_t nev = (size_t)std::max<int64_t>(n_ev, 1);
-    int rc = dx.reserve(ctx, nev * 2);
-    if (!rc) rc = dy.reserve(ctx, nev * 2);
-    if (!rc) rc = dp.reserve(ctx, nev);
-    if (!rc) rc = dbounds.reserve(ctx, (size_t)(n_slices + 1) * 8);
-    if (!rc) rc = count.reserve(ctx, 4 * sizeof(unsigned));
+    int rc = count.reserve(ctx, 4 * sizeof(unsigned));
     for (int i = 0; i < narr && !rc; i++) {
         rc = mask[i].reserve(ctx, npx * sizeof(unsigned));
         if (!rc && dead) rc = list[i].reserve(ctx, nev * sizeof(unsigned));
@@ -338,52 +191,23 @@ extern "C" int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int s
     if (!rc) rc = dact.reserve(ctx, n_drive * npx * 3 * sizeof(float));
     if (!rc && !dead) rc = dsil.reserve(ctx, n_drive * npx * 3 * sizeof(float));
     if (!rc) rc = dres.reserve(ctx, n_drive * npx * 2 * sizeof(float));
-    for (int k = 0; k < NSOF_ACCUM_KEY_COUNT && !rc; k++)
-        if (tp.plane[k]) rc = dplane[k].reserve(ctx, (size_t)tp.trials[k] * npx * sizeof(float));
+    MapSrc src;
+    if (!rc) rc = upload_planes(ctx, mo, tp, npx, dplane, &src);
     if (rc) return rc;
 
     hipStream_t st = ctx->stream;
-    if (n_ev > 0) {
-        NSOF_HIP(ctx, hipMemcpyAsync(dx.p, x + e0, (size_t)n_ev * 2, hipMemcpyHostToDevice, st));
-        NSOF_HIP(ctx, hipMemcpyAsync(dy.p, y + e0, (size_t)n_ev * 2, hipMemcpyHostToDevice, st));
-        if (p) NSOF_HIP(ctx, hipMemcpyAsync(dp.p, p + e0, (size_t)n_ev, hipMemcpyHostToDevice, st));
-    }
-    // slice bounds relative to the first staged event; scheme 2: every slice's first timestamp and last + refractory
-    std::vector<long long> rel((size_t)n_slices + 1), tfirst((size_t)n_slices, 0), tnext((size_t)n_slices, 0);
-    for (int64_t s = 0; s <= n_slices; s++) rel[s] = (long long)(sb[s] - e0);
-    if (scheme == 2)
-        for (int64_t s = 0; s < n_slices; s++)
-            if (sb[s + 1] > sb[s]) {
-                tfirst[s] = t[sb[s]];
-                tnext[s] = t[sb[s + 1] - 1] + mo.prm.refractory_us;
-            }
-    NSOF_HIP(ctx, hipMemcpyAsync(dbounds.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
+    const std::vector<long long>& rel = ev.rel;
     for (int i = 0; i < narr; i++) {
         NSOF_HIP(ctx, hipMemsetAsync(mask[i].p, 0, npx * sizeof(unsigned), st));
         if (scheme == 2) NSOF_HIP(ctx, hipMemsetAsync(next_ok[i].p, 0, npx * sizeof(long long), st));
     }
-    NSOF_HIP(ctx, hipMemsetAsync(count.p, 0, 4 * sizeof(unsigned), st));
-
-    const float scal[NSOF_ACCUM_KEY_COUNT] = {mo.f.alphaoff, mo.f.alphaon, mo.f.voff, mo.f.von, mo.f.koff, mo.f.kon, mo.f.son, mo.f.soff,
-                                              mo.f.bon, mo.f.boff, mo.f.ron, (float)mo.prm.Roff, mo.wini_f};
-    TrialSrc src;
-    for (int k = 0; k < NSOF_ACCUM_KEY_COUNT; k++) {
-        src.plane[k] = nullptr;
-        src.stride[k] = 0;
-        src.scalar[k] = scal[k];
-        if (!tp.plane[k]) continue;
-        NSOF_HIP(ctx, hipMemcpyAsync(dplane[k].p, tp.plane[k], (size_t)tp.trials[k] * npx * sizeof(float), hipMemcpyHostToDevice, st));
-        src.plane[k] = dplane[k].p;
-        src.stride[k] = tp.trials[k] > 1 ? npx : 0;
-    }
-    src.ron = mo.prm.Ron;
-    src.roff = mo.prm.Roff;
-    src.dt = mo.f.dt;
+    ListCounts cnt{count.p};   // a group's resolve zeroes the set the next group's scatter appends to
+    NSOF_HIP(ctx, cnt.zero_all(st));
     const float v_act = scheme == 1 ? active_v : silent_v + active_v;
     float* const w_arr[2] = {d_w, d_w + T * npx};
-    const float2* const res = reinterpret_cast<const float2*>(dres.p);
-    const size_t res_stride = drive_trials > 1 ? npx : 0, drive_stride = 3 * res_stride;
-    hipLaunchKernelGGL(k_trials_setup, dim3(grid_for(npx), (unsigned)n_trials), dim3(256), 0, st, src, npx, drive_trials, v_act, silent_v,
+    const TrialRes res{reinterpret_cast<const float2*>(dres.p), drive_trials > 1 ? npx : 0, npx, n_trials};
+    const size_t drive_stride = 3 * res.stride;
+    hipLaunchKernelGGL(k_setup_maps, dim3(grid_for(npx), (unsigned)n_trials), dim3(256), 0, st, src, npx, drive_trials, v_act, silent_v,
                        dact.p, dead ? nullptr : dsil.p, reinterpret_cast<float2*>(dres.p), w_arr[0], split ? w_arr[1] : nullptr);
     NSOF_HIP(ctx, hipGetLastError());
 
@@ -393,24 +217,19 @@ extern "C" int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int s
     const int rows = blocks ? height / memsize : 0, cols = blocks ? width / memsize : 0;
     const int64_t word_slices = theta == 1 ? MAX_GROUP : theta_of(theta).spw;
     const unsigned trial_chunks = (unsigned)((n_trials + TRIAL_CHUNK - 1) / TRIAL_CHUNK);
-    int par = 0;   // list counters [parity][array]: a group's resolve zeroes the set the next group's scatter appends to
     size_t snap = 0;
-    int64_t s0 = 0;
+    int64_t s0 = 0;   // also the slice counter: the run starts at a fresh array
     while (s0 < n_slices) {
-        int64_t g = std::min<int64_t>(n_slices - s0, word_slices);
-        if (every > 0) {
-            const int64_t to_snap = (s0 % every == 0) ? 1 : (every - s0 % every) + 1;
-            if (to_snap < g) g = to_snap;
-        }
+        const int64_t g = group_len(s0, n_slices, word_slices, every, s0);
         const long long ge0 = rel[s0], gn = rel[s0 + g] - ge0;
-        unsigned* const cur = count.p + 2 * par;
-        unsigned* const nxt = count.p + 2 * (par ^ 1);
+        unsigned* const cur = cnt.cur();
+        unsigned* const nxt = cnt.next();
         {
             nsof_prof_scope ps(ctx, NSOF_K_ACCUM);
             if (gn > 0)
                 with_theta(theta, [&](auto C, auto th) {
-                    hipLaunchKernelGGL(k_scatter<decltype(C)::value>, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, st, dx.p, dy.p, dp.p,
-                                       ge0, gn, dbounds.p + s0, (int)g, width, split, mask[0].p, dead ? list[0].p : nullptr, cur,
+                    hipLaunchKernelGGL(k_scatter<decltype(C)::value>, dim3((unsigned)((gn + 255) / 256)), dim3(256), 0, st, ev.dx.p, ev.dy.p, ev.dp.p,
+                                       ge0, gn, ev.dbounds.p + s0, (int)g, width, split, mask[0].p, dead ? list[0].p : nullptr, cur,
                                        mask[split].p, dead ? list[split].p : nullptr, cur + 1, (unsigned*)nullptr, th);
                 });
             // array i of the group; R: std::true_type for scheme 2, whose kernels take the group's refractory table
@@ -433,12 +252,7 @@ extern "C" int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int s
                 });
             };
             if (scheme == 2) {
-                RefrTab tab;
-                for (int s = 0; s < 32; s++) {
-                    const bool live = s < g && rel[s0 + s + 1] > rel[s0 + s];
-                    tab.t_first[s] = live ? tfirst[s0 + s] : 0;
-                    tab.t_next[s] = live ? tnext[s0 + s] : 0;
-                }
+                const RefrTab tab = refr_tab_of(ev, s0, g);
                 for (int i = 0; i < narr; i++) update(std::true_type{}, tab, i);
             } else {
                 update(std::false_type{}, NoTab{}, 0);
@@ -446,19 +260,19 @@ extern "C" int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int s
             NSOF_HIP(ctx, hipGetLastError());
         }
         s0 += g;
-        if (dead && gn > 0) par ^= 1;
-        if (every > 0 && (s0 - 1) % every == 0) {
+        if (dead && gn > 0) cnt.flip();
+        if (snapshot_due(s0, every)) {
+            const size_t map = (size_t)rows * cols;   // doubles per (trial, snapshot)
             for (int i = 0; i < narr; i++)
-                hipLaunchKernelGGL(k_trials_block_current, dim3(cols, rows, (unsigned)n_trials), dim3(256), 0, st, w_arr[i], res, res_stride,
-                                   npx, width, memsize, cols, snap, n_snaps, v_ds,
-                                   d_block_current + (size_t)i * T * n_snaps * (size_t)rows * cols);
+                hipLaunchKernelGGL(k_block_min_resistance<TrialRes>, dim3(cols, rows, (unsigned)n_trials), dim3(256), 0, st, w_arr[i], 1,
+                                   width, memsize, cols, res, v_ds, d_block_current + ((size_t)i * T * n_snaps + snap) * map, npx,
+                                   n_snaps * map);
             NSOF_HIP(ctx, hipGetLastError());
             snap++;
         }
     }
     const size_t total = (size_t)narr * T * npx;
-    hipLaunchKernelGGL(k_trials_resistance, dim3(grid_for(total, 8192)), dim3(256), 0, st, d_w, res, res_stride, npx, n_trials, total,
-                       d_resistance);
+    hipLaunchKernelGGL(k_resistance<TrialRes>, dim3(grid_for(total, 8192)), dim3(256), 0, st, d_w, d_resistance, total, res);
     NSOF_HIP(ctx, hipGetLastError());
     // the caller's arrays are not retained and the buffers above go with this frame: the run ends here
     NSOF_HIP(ctx, hipStreamSynchronize(st));

@@ -1,11 +1,14 @@
-// The float32 state update of the event-driven accumulator as device code: what accum_kernels.hip (one array) and
-// accum_trials.hip (T Monte-Carlo trials of one stream) share -- the update arithmetic (update_one, Drive, drive_of,
-// update_drive, replay_driven, resistance_one), the scatter of a group of slices (k_scatter and its marks), scheme 1's
-// count threshold (Theta, driven_bits) and scheme 2's refractory walk (RefrTab, refractory_walk).  Everything sits in an
-// unnamed namespace, as in accum_model.h: each translation unit instantiates its own copies.
+// The float32 event-driven accumulator: what accum_kernels.hip (one array) and accum_trials.hip (T Monte-Carlo trials of one
+// stream) share.  Device code: the update arithmetic (update_one, Drive, drive_of, update_drive, replay_driven,
+// resistance_one), the scatter of a group of slices (k_scatter and its marks), scheme 1's count threshold (Theta,
+// driven_bits), scheme 2's refractory walk (RefrTab, refractory_walk), the set-up pass of per-pixel devices (k_setup_maps)
+// and the resistance read-outs (k_resistance, k_block_min_resistance).  Host code: the staged stream (StagedStream) and the
+// walk over its groups (group_len, snapshot_due, refr_tab_of, ListCounts).  Everything sits in an unnamed namespace, as in
+// accum_model.h: each translation unit instantiates its own copies.
 #pragma once
 
 #include <type_traits>
+#include <vector>
 
 #include "accum_model.h"
 
@@ -316,5 +319,232 @@ void with_theta(int theta, Fn&& f)
     if (theta == 1) f(std::false_type{}, NoTheta{});
     else f(std::true_type{}, theta_of(theta));
 }
+
+// ---- per-pixel (and per-trial) devices: the set-up pass ---------------------------------------------------------------
+// The planes as the set-up pass reads them: the value of key k at (trial t, pixel i) is plane[k][t * stride[k] + i]
+// (stride 0: one plane shared by the trials) or, without a plane, scalar[k].
+struct MapSrc {
+    const float* plane[NSOF_ACCUM_KEY_COUNT];   // nullptr: the key is uniform
+    size_t stride[NSOF_ACCUM_KEY_COUNT];
+    float scalar[NSOF_ACCUM_KEY_COUNT];
+    double ron, roff;                           // the scalars' doubles
+    float dt;
+};
+// Once per nsof_accum_set_param_maps / nsof_accum_trials_dev call, per (trial = blockIdx.y, pixel): the DevF of that pixel --
+// a mapped key's float32 value, an unmapped one's scalar -- and from it exactly what the uniform kernels form per launch:
+// drive_of at the two voltages and (ron, neg_lam), neg_lam = (float)(-ln(Roff / Ron)) with the logarithm in double of the
+// values as held (a plane's float32 widened, the scalar's double).
+//   drive_trials  the trials that get drives and a resistance pair: all, or 1 when no plane but wini has a trial axis
+//   sil           nullptr where no kernel reads the silent drive (the trial run's touched-pixels form)
+//   w0, w1        the initial state (the trial's wini) of every array; nullptr where nsof_accum_reset sets it (one array)
+__global__ __launch_bounds__(256) void k_setup_maps(MapSrc src, size_t n, int drive_trials, float v_act, float v_sil,
+                                                     float* __restrict__ act, float* __restrict__ sil, float2* __restrict__ res,
+                                                     float* __restrict__ w0, float* __restrict__ w1)
+{
+    const size_t t = blockIdx.y;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        auto get = [&](int k) { return src.plane[k] ? src.plane[k][t * src.stride[k] + i] : src.scalar[k]; };
+        const size_t e = t * n + i;
+        if (w0) {
+            const float wini = get(NSOF_ACCUM_KEY_WINI);
+            w0[e] = wini;
+            if (w1) w1[e] = wini;
+        }
+        if (t >= (size_t)drive_trials) continue;
+        DevF p;
+        p.alphaoff = get(NSOF_ACCUM_KEY_ALPHAOFF); p.alphaon = get(NSOF_ACCUM_KEY_ALPHAON);
+        p.voff = get(NSOF_ACCUM_KEY_VOFF); p.von = get(NSOF_ACCUM_KEY_VON);
+        p.koff = get(NSOF_ACCUM_KEY_KOFF); p.kon = get(NSOF_ACCUM_KEY_KON);
+        p.son = get(NSOF_ACCUM_KEY_SON); p.soff = get(NSOF_ACCUM_KEY_SOFF);
+        p.bon = get(NSOF_ACCUM_KEY_BON); p.boff = get(NSOF_ACCUM_KEY_BOFF);
+        p.dt = src.dt;
+        p.ron = get(NSOF_ACCUM_KEY_RON);
+        const double ron = src.plane[NSOF_ACCUM_KEY_RON] ? (double)p.ron : src.ron;
+        const double roff = src.plane[NSOF_ACCUM_KEY_ROFF] ? (double)get(NSOF_ACCUM_KEY_ROFF) : src.roff;
+        p.neg_lam = (float)(-log(roff / ron));
+        const Drive da = drive_of(v_act, p);
+        act[3 * e] = da.ka; act[3 * e + 1] = da.s; act[3 * e + 2] = da.b;
+        if (sil) {
+            const Drive ds = drive_of(v_sil, p);
+            sil[3 * e] = ds.ka; sil[3 * e + 1] = ds.s; sil[3 * e + 2] = ds.b;
+        }
+        res[e] = make_float2(p.ron, p.neg_lam);
+    }
+}
+// The checked planes to device memory (dplane[k], on ctx->stream; the caller's arrays must outlive the copies) and the MapSrc
+// of them: the model's float32 scalars for the unmapped keys.
+inline int upload_planes(nsof_ctx* ctx, const Model& mo, const PlaneSet<float>& ps, size_t npx, nsof_dev_buf<float>* dplane, MapSrc* src)
+{
+    const float scal[NSOF_ACCUM_KEY_COUNT] = {mo.f.alphaoff, mo.f.alphaon, mo.f.voff, mo.f.von, mo.f.koff, mo.f.kon, mo.f.son, mo.f.soff,
+                                              mo.f.bon, mo.f.boff, mo.f.ron, (float)mo.prm.Roff, mo.wini_f};
+    for (int k = 0; k < NSOF_ACCUM_KEY_COUNT; k++) {
+        src->plane[k] = nullptr;
+        src->stride[k] = 0;
+        src->scalar[k] = scal[k];
+        if (!ps.plane[k]) continue;
+        const size_t bytes = (size_t)ps.trials[k] * npx * sizeof(float);
+        if (int rc = dplane[k].reserve(ctx, bytes)) return rc;
+        NSOF_HIP(ctx, hipMemcpyAsync(dplane[k].p, ps.plane[k], bytes, hipMemcpyHostToDevice, ctx->stream));
+        src->plane[k] = dplane[k].p;
+        src->stride[k] = ps.trials[k] > 1 ? npx : 0;
+    }
+    src->ron = mo.prm.Ron;
+    src->roff = mo.prm.Roff;
+    src->dt = mo.f.dt;
+    return NSOF_OK;
+}
+
+// ---- resistance ---------------------------------------------------------------------------------------------------------
+// The model resistance_one / surface_gray_value read (ron, neg_lam; mode 1 of the surface reads neither: no load): the
+// uniform device itself, pixel pix of a mapped one, or element i of the trial run's [A][T][npx] states.
+struct MapRes {
+    const float2* res;
+};
+struct TrialRes {
+    const float2* res;   // [T or 1][npx]
+    size_t stride, npx;  // stride: float2s between the planes of consecutive trials (0: one plane for all)
+    int n_trials;
+};
+__device__ __forceinline__ const DevF& res_at(const DevF& p, size_t, int) { return p; }
+__device__ __forceinline__ DevF res_at(const float2* __restrict__ res, size_t pix, int mode)
+{
+    DevF q{};
+    if (mode == 0) {
+        const float2 r = res[pix];
+        q.ron = r.x;
+        q.neg_lam = r.y;
+    }
+    return q;
+}
+__device__ __forceinline__ DevF res_at(MapRes m, size_t pix, int mode) { return res_at(m.res, pix, mode); }
+__device__ __forceinline__ DevF res_at(const TrialRes& v, size_t i, int mode)
+{
+    return res_at(v.res + (i / v.npx % (size_t)v.n_trials) * v.stride, i % v.npx, mode);
+}
+
+//   ResT  DevF (one device), MapRes (element i is pixel i of a mapped accumulator) or TrialRes
+template <class ResT>
+__global__ __launch_bounds__(256) void k_resistance(const float* __restrict__ w, float* __restrict__ out, size_t n, ResT p)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+        out[i] = resistance_one(w[i], res_at(p, i, 0));
+}
+
+// Block maximum of the device current I = v_ds / R over memsize x memsize pixel blocks: the gating image's input
+// (one value per block) formed on the device instead of from a downloaded surface.
+// max(v_ds / R) = v_ds / min(R) exactly (division by a positive float is monotone), so a block reduces min(R) in
+// float32 -- R from a stored snapshot, or resistance_one(w) of the current state -- and thread 0 divides in double.
+//   ResT        DevF, MapRes or TrialRes: the resistance constants, read where the source is the state
+//   blockIdx.z  the trial: its plane of src starts at z * src_stride floats, its map of out at z * out_stride doubles (one
+//               array: z = 0)
+template <class ResT>
+__global__ __launch_bounds__(256) void k_block_min_resistance(const float* __restrict__ src, int is_w, int W, int memsize,
+                                                               int cols, ResT p, double v_ds, double* __restrict__ out,
+                                                               size_t src_stride, size_t out_stride)
+{
+    __shared__ float part[4];
+    const int bx = blockIdx.x, by = blockIdx.y;
+    const size_t base = blockIdx.z * src_stride + ((size_t)by * memsize) * W + (size_t)bx * memsize;
+    float m = INFINITY;
+    for (int i = threadIdx.x; i < memsize * memsize; i += 256) {
+        const size_t pix = base + (size_t)(i / memsize) * W + (i % memsize);
+        const float v = src[pix];
+        m = fminf(m, is_w ? resistance_one(v, res_at(p, pix, 0)) : v);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        out[blockIdx.z * out_stride + (size_t)by * cols + bx] = v_ds / (double)fminf(fminf(part[0], part[1]), fminf(part[2], part[3]));
+}
+
+// ---- the staged stream and the walk over its groups (host) --------------------------------------------------------------
+// The events of slices [0, n_slices) on the device and what the slice loop needs of them on the host: the slice bounds
+// relative to the first staged event and, for scheme 2, every slice's first timestamp and last timestamp + refractory period.
+struct StagedStream {
+    std::vector<long long> rel, tfirst, tnext;   // (declared first: the buffers below wait for the device as they go)
+    nsof_dev_buf<short> dx, dy;
+    nsof_dev_buf<signed char> dp;
+    nsof_dev_buf<long long> dbounds;
+    // Checks and uploads on ctx->stream (bounds sb index the caller's arrays, which are not retained: synchronise before
+    // they go).
+    int stage(nsof_ctx* ctx, int W, int H, int scheme, int split, long long refractory_us, const int16_t* x, const int16_t* y,
+              const int8_t* p, const int64_t* t, const int64_t* sb, int64_t n_slices)
+    {
+        if (n_slices < 0 || !sb) return nsof_set_error(ctx, NSOF_EINVAL, "bad slice bounds");
+        NSOF_HIP(ctx, hipSetDevice(ctx->device));
+        const int64_t e0 = sb[0], e1 = sb[n_slices], n_ev = e1 - e0;
+        if (n_ev < 0) return nsof_set_error(ctx, NSOF_EINVAL, "slice bounds not monotone");
+        if (n_ev > 0 && (!x || !y || !t || (scheme == 2 && split && !p))) return nsof_set_error(ctx, NSOF_EINVAL, "null event array");
+        for (int64_t s = 0; s < n_slices; s++)
+            if (sb[s + 1] < sb[s]) return nsof_set_error(ctx, NSOF_EINVAL, "slice bounds not monotone");
+        // validate coordinates on the host: an out-of-range event would be an out-of-bounds store on the device
+        for (int64_t e = e0; e < e1; e++)
+            if ((unsigned)x[e] >= (unsigned)W || (unsigned)y[e] >= (unsigned)H)
+                return nsof_set_error(ctx, NSOF_EINVAL, "event %lld at (%d,%d) outside the %dx%d sensor", (long long)e, (int)x[e],
+                                      (int)y[e], W, H);
+        int rc;
+        const size_t cap = event_cap(n_ev);
+        if ((rc = dx.reserve(ctx, (size_t)n_ev * 2, cap * 2)) || (rc = dy.reserve(ctx, (size_t)n_ev * 2, cap * 2)) ||
+            (rc = dp.reserve(ctx, (size_t)n_ev, cap)) || (rc = dbounds.reserve(ctx, (size_t)(n_slices + 1) * 8)))
+            return rc;
+        if (n_ev > 0) {
+            NSOF_HIP(ctx, hipMemcpyAsync(dx.p, x + e0, (size_t)n_ev * 2, hipMemcpyHostToDevice, ctx->stream));
+            NSOF_HIP(ctx, hipMemcpyAsync(dy.p, y + e0, (size_t)n_ev * 2, hipMemcpyHostToDevice, ctx->stream));
+            if (p) NSOF_HIP(ctx, hipMemcpyAsync(dp.p, p + e0, (size_t)n_ev, hipMemcpyHostToDevice, ctx->stream));
+        }
+        rel.resize((size_t)n_slices + 1);
+        for (int64_t s = 0; s <= n_slices; s++) rel[s] = (long long)(sb[s] - e0);
+        tfirst.assign((size_t)n_slices, 0);
+        tnext.assign((size_t)n_slices, 0);
+        if (scheme == 2)
+            for (int64_t s = 0; s < n_slices; s++)
+                if (sb[s + 1] > sb[s]) {
+                    tfirst[s] = t[sb[s]];
+                    tnext[s] = t[sb[s + 1] - 1] + refractory_us;
+                }
+        NSOF_HIP(ctx, hipMemcpyAsync(dbounds.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        return NSOF_OK;
+    }
+    // entries an event-sized buffer is given so that a slightly longer stream reuses it
+    static size_t event_cap(int64_t n_ev) { return (size_t)n_ev + (size_t)n_ev / 4 + 1024; }
+};
+
+// The next group: up to max_group slices of [s0, s_end), ending right after the next snapshot slice (`counter`: the slices
+// run since the array was reset, which times the snapshots).
+inline int64_t group_len(int64_t s0, int64_t s_end, int64_t max_group, int64_t snap_every, int64_t counter)
+{
+    int64_t g = s_end - s0 < max_group ? s_end - s0 : max_group;
+    if (snap_every > 0) {
+        const int64_t to_snap = (counter % snap_every == 0) ? 1 : (snap_every - counter % snap_every) + 1;
+        if (to_snap < g) g = to_snap;
+    }
+    return g;
+}
+// ... and whether the group that brought the counter here ended on one
+inline bool snapshot_due(int64_t counter, int64_t snap_every) { return snap_every > 0 && (counter - 1) % snap_every == 0; }
+// Scheme 2's table of the group of g <= 32 slices from s0 (an empty slice drives nothing: zeros)
+inline RefrTab refr_tab_of(const StagedStream& st, int64_t s0, int64_t g)
+{
+    RefrTab tab;
+    for (int s = 0; s < 32; s++) {
+        const bool live = s < g && st.rel[s0 + s + 1] > st.rel[s0 + s];
+        tab.t_first[s] = live ? st.tfirst[s0 + s] : 0;
+        tab.t_next[s] = live ? st.tnext[s0 + s] : 0;
+    }
+    return tab;
+}
+
+// List counters of the event-pixel update, [parity][array]: two sets used alternately.  A group's update kernels zero the
+// OTHER set -- the one the next group's scatter appends to -- so no group needs a memset (a launch of its own): one per call.
+struct ListCounts {
+    unsigned* base;
+    int par = 0;
+    hipError_t zero_all(hipStream_t s) const { return hipMemsetAsync(base, 0, 4 * sizeof(unsigned), s); }
+    unsigned* cur() const { return base + 2 * par; }
+    unsigned* next() const { return base + 2 * (par ^ 1); }
+    void flip() { par ^= 1; }
+};
 
 }  // namespace

@@ -10,7 +10,8 @@ Both start from the same host arrays (events, [T][H][W] float32 planes drawn bef
 synchronise with their maps in HBM; the two stacks are compared bit for bit once per process.
 
 Two ways to call it.
-  worker   bench_accum_trials.py --what trials|loop      one process, one JSON line
+  worker   bench_accum_trials.py --what trials|loop [--tree DIR]      one process, one JSON line.  --tree DIR measures the
+           package under DIR (a checkout of another commit with its own libnsof.so), for a parent-against-branch comparison
   session  bench_accum_trials.py --session [--rounds 3] [--out profiles/accum_trials.json]
            starts the two kinds of worker alternately, `rounds` times in fresh processes, and writes the medians over the
            processes with their min-max spread and, per T, whether the trial run's median stays below the loop's minimum.
@@ -34,7 +35,8 @@ TRIALS = (1, 16, 64)
 
 
 def worker(a):
-    sys.path[:0] = [HERE, os.path.join(HERE, "neuromorphic-spatiotemporal-optical-flow_amd")]
+    root = os.path.abspath(a.tree)
+    sys.path[:0] = [root, os.path.join(root, "neuromorphic-spatiotemporal-optical-flow_amd")]
     os.environ.setdefault("NSOF_SKIP_BUILD", "1")
     import numpy as np
     import torch
@@ -47,7 +49,7 @@ def worker(a):
     n_sl = len(idx) - 1
     n_snap = (n_sl - 1) // EVERY + 1
     rows, cols = H // MEMSIZE, W // MEMSIZE
-    out = {"what": a.what, "reps": a.reps, "slices": n_sl, "snapshots": n_snap, "trials": {}}
+    out = {"what": a.what, "tree": root, "lib": nsof._lib.LIB_PATH, "reps": a.reps, "slices": n_sl, "snapshots": n_snap, "trials": {}}
 
     def trials_run(maps):
         return A.simulate_trials_dev(ev, maps, 1, 1000, -6.0, 0.0, sensor_size=(H, W), snapshot_every=EVERY, memsize=MEMSIZE,
@@ -126,6 +128,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", choices=("trials", "loop"), default="trials")
     ap.add_argument("--session", action="store_true")
+    ap.add_argument("--tree", default=HERE)
     ap.add_argument("--trials", default=TRIALS, type=lambda s: tuple(int(v) for v in s.split(",")))
     ap.add_argument("--check-up-to", type=int, default=16, help="compare the two forms' stacks bit for bit up to this many trials")
     ap.add_argument("--reps", type=int, default=3)

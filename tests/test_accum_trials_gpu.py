@@ -37,13 +37,14 @@ def case_kw(case):
                 refractory_us=c["refractory_us"], theta_events=c["theta"])
 
 
-def single_array(ctx, case, maps, snap_every=T.SNAP_EVERY, memsize=T.MEMSIZE, kw=None):
+def single_array(ctx, case, maps, snap_every=T.SNAP_EVERY, memsize=T.MEMSIZE, kw=None, dense=None):
     """The existing path with one trial's planes (``None``: the uniform device) -> (w [A][H][W], resistance [A][H][W], block
-    currents [A][S][rows][cols])."""
+    currents [A][S][rows][cols]).  ``dense``: as for ``Accumulator`` (``None`` automatic)."""
     from nsof.accumulator import Accumulator, slice_index_array
     kw = dict(case_kw(case) if kw is None else kw)
     ev, (H, W) = K.stream_of(case)  # noqa: N806
-    acc = Accumulator(H, W, kw.pop("version"), kw.pop("polarity"), kw.pop("active_v"), kw.pop("silent_v"), ctx=ctx, param_maps=maps, **kw)
+    acc = Accumulator(H, W, kw.pop("version"), kw.pop("polarity"), kw.pop("active_v"), kw.pop("silent_v"), ctx=ctx, param_maps=maps,
+                      dense=dense, **kw)
     try:
         acc.step(*ev, slice_index_array(ev[3], 1000), snap_every=snap_every)
         arrays = range(2 if acc.split else 1)
@@ -139,6 +140,37 @@ def test_constant_planes_give_the_uniform_accumulators_bits(nsof_lib, ctx, mode)
     uniform = single_array(ctx, "small_v1", None, kw=kw)
     assert_trials_equal(got, [uniform, uniform], mode)
     assert len(np.unique(uniform[0])) > 10
+
+
+@pytest.mark.parametrize("case", ["small_v1", "small_v2_split"])
+@pytest.mark.parametrize("device", ["fitted", "alpha"])
+def test_no_plane_at_all_is_the_uniform_accumulator(nsof_lib, ctx, case, device):
+    """``param_maps={}``: one trial whose every key is a scalar -- the scalar-only route through the shared set-up kernel --
+    for the fitted device (``params=None``) and for ``K.PARAMS``, schemes 1 and 2: the uniform ``Accumulator``'s state,
+    resistance and block currents, bit for bit."""
+    kw = case_kw(case) if device == "alpha" else dict(case_kw(case), params=None, dt=None)
+    ev, shape = K.stream_of(case)
+    got = nsof_lib.simulate_trials(ev, {}, sensor_size=shape, snapshot_every=T.SNAP_EVERY, memsize=T.MEMSIZE, ctx=ctx, **kw)
+    uniform = single_array(ctx, case, None, kw=kw)
+    assert got["w"].shape[1] == 1 and got["block_current"].shape[2] == 6
+    assert_trials_equal(got, [uniform], (case, device))
+    assert len(np.unique(uniform[0])) > 10 and not same_bits(uniform[0], np.full_like(uniform[0], 0.5))
+
+
+@pytest.mark.parametrize("every,n_snaps", [(1, 40), (32, 2), (33, 2), (41, 1)])
+@pytest.mark.parametrize("case", ["small_v1", "small_v1_theta3", "small_v2_split"])
+def test_group_cuts_at_the_edges(nsof_lib, ctx, case, every, n_snaps):
+    """A snapshot after every slice, at the 32-slice word boundary, one past it, and beyond the 40-slice stream (the
+    other tests cut at 7 only).  Every trial equals the single array run with the event-pixel update (``dense=False``:
+    groups of one mask word, 32 slices, 16 with theta = 3) and with the every-pixel pass (``dense=True``: scheme 1 takes
+    two words, 64 and 32 slices) -- the shared ``group_len`` at both widths against the trial run's one."""
+    seeds = (1, 3, 7)
+    maps, per = T.trial_maps(case, seeds)
+    ev, shape = K.stream_of(case)
+    got = nsof_lib.simulate_trials(ev, maps, sensor_size=shape, snapshot_every=every, memsize=T.MEMSIZE, ctx=ctx, **case_kw(case))
+    assert got["block_current"].shape[2] == n_snaps == (40 - 1) // every + 1
+    for dense in (False, True):
+        assert_trials_equal(got, [single_array(ctx, case, m, snap_every=every, dense=dense) for m in per], (case, every, dense))
 
 
 def test_golden_stream(nsof_lib, ctx):
