@@ -371,6 +371,13 @@ int nsof_stage_iterate(nsof_ctx* ctx, int n_pairs, const float* d_R, const float
 int nsof_stage_iterate_upsample(nsof_ctx* ctx, int n_pairs, const float* d_R, const float* d_coarse_flow,
                                 int src_w, int src_h, int width, int height, int winsize, double pyr_scale,
                                 float* d_flow_out);
+/* One exact-order fused iteration whose flow_in is resample(d_coarse_flow [src_h][src_w][2]) * (1/pyr_scale), formed
+ * inside the kernel as its rows are fetched (k_iterate_xr): bit for bit nsof_stage_flow_upsample followed by
+ * nsof_stage_iterate in exact mode.  NSOF_EUNSUPPORTED, nothing written, unless width == 2 * src_w,
+ * height == 2 * src_h and winsize is 2..15. */
+int nsof_stage_iterate_x_resample(nsof_ctx* ctx, int n_pairs, const float* d_R, const float* d_coarse_flow,
+                                  int src_w, int src_h, int width, int height, int winsize, double pyr_scale,
+                                  float* d_flow_out);
 int nsof_stage_flow_upsample(nsof_ctx* ctx, int n_pairs, const float* d_src, int src_w, int src_h,
                              float* d_dst, int dst_w, int dst_h, double pyr_scale);
 

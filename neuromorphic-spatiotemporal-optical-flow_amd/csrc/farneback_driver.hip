@@ -143,9 +143,18 @@ static int three_level_images(Run& r)
     return rc == NSOF_EUNSUPPORTED ? NSOF_OK : rc;
 }
 
+// Does level k's first iteration read the coarser level's flow (pw x ph) itself, resampling it as it fetches
+// (nsof_launch_iterate_x_resample), so that the level needs no flow resample launch?  The one-kernel exact form, on an
+// exact doubling, with the two-rounding blend; everything else keeps the two kernels.
+static bool first_iteration_resamples(const Run& r, int wk, int hk, int pw, int ph)
+{
+    return r.form == NSOF_ITER_EXACT && r.p.iterations >= 1 && wk == 2 * pw && hk == 2 * ph && !r.ctx->opt_pyr_fma;
+}
+
 // The iterations of level k (wk x hk) on the flow in fb[*cur]: the form dispatch and the buffer flips.  A fused iteration
-// moves the flow to the other buffer, an unfused one updates it in place.
-static int iterate_level(const Run& r, int k, int wk, int hk, float* const fb[2], int* cur)
+// moves the flow to the other buffer, an unfused one updates it in place.  pw > 0: fb[*cur] still holds the COARSER
+// level's flow, pw x ph, and the first iteration resamples it (first_iteration_resamples).
+static int iterate_level(const Run& r, int k, int wk, int hk, float* const fb[2], int* cur, int pw, int ph)
 {
     nsof_ctx* ctx = r.ctx;
     const int n_pairs = r.f.n_pairs, winsize = r.p.winsize;
@@ -162,6 +171,9 @@ static int iterate_level(const Run& r, int k, int wk, int hk, float* const fb[2]
             float* in = fb[*cur];
             float* out = fb[*cur ^= 1];
             if (r.form == NSOF_ITER_EXACT_LAT) rc = nsof_launch_iterate_lat(ctx, n_pairs, R0, R1, 5 * nk, in, out, wk, hk, winsize, dM, dV);
+            else if (r.form == NSOF_ITER_EXACT && it == 0 && pw > 0)
+                rc = nsof_launch_iterate_x_resample(ctx, n_pairs, R0, R1, 5 * nk, in, pw, ph, (float)(1. / r.p.pyr_scale), out, wk, hk,
+                                                    winsize);
             else if (r.form == NSOF_ITER_EXACT) rc = nsof_launch_iterate_x(ctx, n_pairs, R0, R1, 5 * nk, in, out, wk, hk, winsize);
             else rc = nsof_launch_iterate(ctx, n_pairs, R0, R1, 5 * nk, in, out, wk, hk, winsize);
         } else {
@@ -188,9 +200,17 @@ static int run_levels(Run& r, float* d_flow)
     r.cv.base = (char*)ctx->ws.p;
     // Two flow buffers, A = the caller's output and S = scratch; every level uses their leading B*nk pixels.
     // Each upsample and each fused iteration moves the flow to the other buffer, so the buffer the coarsest
-    // level starts in is chosen such that the last iteration of level 0 writes A.
+    // level starts in is chosen such that the last iteration of level 0 writes A.  A level whose first iteration
+    // resamples the coarser flow itself has no resample launch, and no flip for one.
     float* const fb[2] = {d_flow, r.cv.S()};
-    const int flips = nsof_form_fused(r.form) ? L * (1 + iterations) + iterations : L;
+    int flips = nsof_form_fused(r.form) ? L * (1 + iterations) + iterations : L;
+    for (int k = L, cw = 0, ch = 0; k >= 0; k--) {   // (cw, ch): level k + 1
+        int wk, hk;
+        nsof_farneback_level_size(f.width, f.height, r.p.pyr_scale, k, &wk, &hk, nullptr, nullptr);
+        if (k < L && first_iteration_resamples(r, wk, hk, cw, ch)) flips--;
+        cw = wk;
+        ch = hk;
+    }
     int cur = flips & 1;
 
     const hipStream_t mainS = ctx->stream;
@@ -203,9 +223,10 @@ static int run_levels(Run& r, float* d_flow)
         int wk, hk;
         nsof_blur_taps btaps;
         if ((rc = nsof_level_geom(ctx, f.width, f.height, r.p.pyr_scale, k, &wk, &hk, &btaps))) return rc;
+        const bool resample_in_first = k < L && first_iteration_resamples(r, wk, hk, pw, ph);
         if (k == L) {
             NSOF_HIP(ctx, hipMemsetAsync(fb[cur], 0, r.B * wk * hk * 8, mainS));
-        } else {
+        } else if (!resample_in_first) {
             if ((rc = nsof_launch_flow_upsample(ctx, f.n_pairs, fb[cur], pw, ph, fb[cur ^ 1], wk, hk, (float)(1. / r.p.pyr_scale))))
                 return rc;
             cur ^= 1;
@@ -215,7 +236,7 @@ static int run_levels(Run& r, float* d_flow)
         } else if (k < L) {
             NSOF_HIP(ctx, hipStreamWaitEvent(mainS, ctx->ov_events[k], 0));   // this level's expansion is ready
         }
-        if ((rc = iterate_level(r, k, wk, hk, fb, &cur))) return rc;
+        if ((rc = iterate_level(r, k, wk, hk, fb, &cur, resample_in_first ? pw : 0, ph))) return rc;
         pw = wk;
         ph = hk;
     }

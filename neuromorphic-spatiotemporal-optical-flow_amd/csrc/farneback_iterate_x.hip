@@ -35,6 +35,16 @@
 // 16-byte LDS load, ~30 per 16-byte LDS store: scripts/scan_probe.hip), about 31 clocks per column: it is the longest
 // role of a step and nothing else may sit on its critical path.  Arithmetic and its order are the library's, bit for bit.
 // HBM traffic per pixel per iteration: 56 B as k_iterate_q (+ 80 B per strip boundary and row of carries).
+//
+// Where the producers' flow_in comes from is a policy type of the walk (x_produce, x_rows_above, x_producer_loop,
+// x_remainder_loop; the types are in iterate_common.h).  FlowSrc, the level's own flow buffer, makes k_iterate_x<MH, HET>.
+// FlowResample2x makes k_iterate_xr<MH>: the FIRST iteration of a level that is an exact doubling of the coarser one reads
+// the coarser level's flow and forms resize(INTER_LINEAR) x (1 / pyr_scale) for the pixels it fetches, with the flow
+// resample's own coordinates, clamps and two-rounding blends -- the same bits, and the level needs no resample launch
+// (8 B written and 8 B read back per fine pixel; the coarse field is a quarter of that and is served by the cache).  Its
+// full producer waves fetch per WINDOW (the two coarse rows their two fine rows add, blended horizontally once) instead of
+// per row, one window ahead; everything else -- geometry, roles, tickets, carries, epoch tags, bounded waits, error word --
+// is the one walk (x_walk).  256 pairs 1080p, set A, same box: 7164 -> 7485 pairs/s (profiles/iterate_resample.json).
 #include "iterate_common.h"
 
 namespace {
@@ -109,32 +119,39 @@ constexpr unsigned X_SPIN_LIMIT = 1u << 21;   // polls of a carry before giving 
 // its flow for step + 4 (i + 16).  i = stream index = image row (clamped at the bottom).
 // A row's flow lives for four windows: fetched, the gather address two windows later, dx / dy of the matrix another two
 // later.  `dd` is the flow of the row in `in`, `fl` the one fetched two windows ago (it becomes `dd`; its register takes
-// the new fetch).
-template <int MH>
-__device__ __forceinline__ void x_produce(RowIn& in, float2& dd, float2& fl, const XRing& ring, const Planes& R0,
-                                          const Planes& R1, const FlowSrc& F, int W, int H, int xc, int col, int i)
+// the new fetch).  The flow source is a policy (FS: FlowSrc or FlowResample2x, iterate_common.h): what is fetched is its
+// Pend, turned into the flow (value()) where the gather address needs it.
+template <int MH, class FS>
+__device__ __forceinline__ void x_produce(RowIn& in, float2& dd, typename FS::Pend& fl, const XRing& ring, const Planes& R0,
+                                          const Planes& R1, const FS& F, int W, int H, int xc, int col, int i)
 {
     constexpr int RL = XGeom<MH>::RL;
     float Mn[5];
     matrix_from(in, dd.x, dd.y, xc, min(i, H - 1), W, H, Mn);
     ring.put((i + MH + 1) % RL, col, Mn);
-    issue_row(in, R0, R1, W, H, xc, min(i + 8, H - 1), fl);
-    dd = fl;
+    const int y = min(i + 8, H - 1);
+    dd = F.value(fl, y);
+    issue_row(in, R0, R1, W, H, xc, y, dd);
     fl = F.fetch(min(i + 16, H - 1));
 }
 
 // rows 0..m-1 of the window of image row 0 for this thread's column; the m+1 rows above the image replicate row 0.
 // ring slot of stream index i is (i + m + 1) % RL.
-template <int MH>
-__device__ __forceinline__ void x_rows_above(const XRing& ring, const Planes& R0, const Planes& R1, const FlowSrc& F,
+template <int MH, class FS>
+__device__ __forceinline__ void x_rows_above(const XRing& ring, const Planes& R0, const Planes& R1, const FS& F,
                                              int W, int H, int xc, int col)
 {
     // A job's start-up is a chain of memory latencies (flow -> gather address -> gather -> matrix), ~1.5-2 us each under
     // load: taken one row at a time they cost 22 us per job (3 % of a 1080p strip, 17 % of its 135-row level).  So: the
     // flow of all m rows first, then the gathers of up to four rows in flight at once.
     float2 fl[MH];
+    {
+        typename FS::Pend pd[MH];
 #pragma unroll
-    for (int i = 0; i < MH; i++) fl[i] = F.fetch(min(i, H - 1));
+        for (int i = 0; i < MH; i++) pd[i] = F.fetch(min(i, H - 1));
+#pragma unroll
+        for (int i = 0; i < MH; i++) fl[i] = F.value(pd[i], min(i, H - 1));
+    }
     constexpr int GRP = 4;
 #pragma unroll
     for (int g0 = 0; g0 < MH; g0 += GRP) {
@@ -164,19 +181,20 @@ __device__ __forceinline__ void x_rows_above(const XRing& ring, const Planes& R0
 //               and segment 1 of step t-1; I/O wave: carries (see x_remainder_loop)
 // A ring of 2m+9 rows holds exactly the rows the consumers read in a window (2m+5) and the four being written.
 // Full producer wave: thread <-> ring column, rows 2 GP, 2 GP + 1 of every step.
-template <int MH, int GP>
+template <int MH, int GP, class FS>
 __device__ __forceinline__ void x_producer_loop(const XRing& ring, const Planes& R0, const Planes& R1,
-                                                const FlowSrc& F, int W, int H, int xc, int col, int nimg)
+                                                const FS& F, int W, int H, int xc, int col, int nimg)
 {
     if constexpr (GP == 0) x_rows_above<MH>(ring, R0, R1, F, W, H, xc, col);
     RowIn in[2][2];
-    float2 dd[2][2], fl[2][2];
+    float2 dd[2][2];
+    typename FS::Pend fl[2][2];
 #pragma unroll
     for (int ts = 0; ts < 2; ts++)
 #pragma unroll
         for (int rr = 0; rr < 2; rr++) {
             const int r = min(4 * ts + MH + 2 * GP + rr, H - 1);
-            dd[ts][rr] = F.fetch(r);
+            dd[ts][rr] = F.value(F.fetch(r), r);
             issue_row(in[ts][rr], R0, R1, W, H, xc, r, dd[ts][rr]);
         }
 #pragma unroll
@@ -197,6 +215,73 @@ __device__ __forceinline__ void x_producer_loop(const XRing& ring, const Planes&
     // in[0] were issued last" into the loop header: every trip began by waiting for the loads its previous window had
     // just issued (vmcnt(18), (9), (0): a full memory latency).
     int t = 0;
+    for (; t < nimg; t += 2) {
+        step(std::integral_constant<int, 0>{}, t + 2);
+        __syncthreads();                                                             // B(t)
+        step(std::integral_constant<int, 1>{}, t + 3);
+        __syncthreads();                                                             // B(t+1)
+    }
+    if (t == nimg) {
+        step(std::integral_constant<int, 0>{}, t + 2);
+        __syncthreads();                                                             // B(nimg)
+    }
+}
+
+// The same loop for the resampling source, in its pair form (FlowResample2x, iterate_common.h): the plain policy loop
+// above keeps four rows' loads pending per thread, 32 registers, and spills.  Here a WINDOW fetches: the two coarse rows
+// its two fine rows add, 8 registers, ONE window ahead and BEFORE the window's own gathers -- loads return in order, so the
+// wait for them at the top of the next window (vmcnt(18)) leaves that window's 18 gather loads in flight, and the gathers
+// keep their two windows.  (The coarse field is a quarter of the level's and is read by every thread pair: cache hits.)
+// Barriers, ring slots, rows and the order of the matrix arithmetic are those of the loop above.
+template <int MH, int GP>
+__device__ __forceinline__ void x_producer_loop(const XRing& ring, const Planes& R0, const Planes& R1,
+                                                const FlowResample2x& F, int W, int H, int xc, int col, int nimg)
+{
+    constexpr int RL = XGeom<MH>::RL;
+    constexpr bool ODD = (MH & 1) != 0;   // parity of a window's first row, 4 t + MH + 2 GP
+    if constexpr (GP == 0) x_rows_above<MH>(ring, R0, R1, F, W, H, xc, col);
+    RowIn in[2][2];
+    float2 dd[2][2];
+    {
+        FlowResample2x::Pend p[2][2];
+#pragma unroll
+        for (int ts = 0; ts < 2; ts++)
+#pragma unroll
+            for (int rr = 0; rr < 2; rr++) p[ts][rr] = F.fetch(min(4 * ts + MH + 2 * GP + rr, H - 1));
+#pragma unroll
+        for (int ts = 0; ts < 2; ts++)
+#pragma unroll
+            for (int rr = 0; rr < 2; rr++) {
+                const int r = min(4 * ts + MH + 2 * GP + rr, H - 1);
+                dd[ts][rr] = F.value(p[ts][rr], r);
+                issue_row(in[ts][rr], R0, R1, W, H, xc, r, dd[ts][rr]);
+            }
+    }
+    // step 2's rows: pending, and (even windows) the blend of the row above them
+    float2 z = make_float2(0.f, 0.f);
+    if constexpr (!ODD) z = F.upper_row(min(8 + MH + 2 * GP, H - 1));
+    FlowResample2x::Pend2 pd = F.template fetch2<ODD>(min(8 + MH + 2 * GP, H - 1), min(9 + MH + 2 * GP, H - 1));
+    auto step = [&](auto tsc, int t) {
+        constexpr int TS = decltype(tsc)::value;
+        const int i = 4 * t + MH + 2 * GP;
+#pragma unroll
+        for (int rr = 0; rr < 2; rr++) {
+            float Mn[5];
+            matrix_from(in[TS][rr], dd[TS][rr].x, dd[TS][rr].y, xc, min(i + rr, H - 1), W, H, Mn);
+            ring.put((i + rr + MH + 1) % RL, col, Mn);
+        }
+        const int ya = min(i + 8, H - 1), yb = min(i + 9, H - 1);
+        F.template value2<ODD>(pd, z, ya, yb, dd[TS][0], dd[TS][1]);
+        pd = F.template fetch2<ODD>(min(i + 12, H - 1), min(i + 13, H - 1));
+        asm volatile("" ::: "memory");   // the coarse rows are requested before the gathers (see above)
+        issue_row(in[TS][0], R0, R1, W, H, xc, ya, dd[TS][0]);
+        issue_row(in[TS][1], R0, R1, W, H, xc, yb, dd[TS][1]);
+    };
+    step(std::integral_constant<int, 0>{}, 0);
+    __syncthreads();                                                                 // Ba
+    step(std::integral_constant<int, 1>{}, 1);
+    __syncthreads();                                                                 // Bb
+    int t = 0;   // two windows per trip and one exit, at the bottom (see above)
     for (; t < nimg; t += 2) {
         step(std::integral_constant<int, 0>{}, t + 2);
         __syncthreads();                                                             // B(t)
@@ -254,9 +339,9 @@ __device__ __forceinline__ void x_solve_rows(const double* sv, volatile lds_int*
 // payload} with relaxed agent-scope stores and loads -- no fences, no flags.
 // A strip settles about a step plus the hand-off latency behind its left neighbour and then never waits (a fetch that
 // finds a stale tag is repeated, which delays this strip's barrier: the lag only grows until the fetches succeed).
-template <int MH>
+template <int MH, class FS>
 __device__ __forceinline__ void x_remainder_loop(const XRing& ring, double* cb, const Planes& R0, const Planes& R1,
-                                                 const FlowSrc& F, int W, int H, int xc, int col, int r, int nimg,
+                                                 const FS& F, int W, int H, int xc, int col, int r, int nimg,
                                                  gu64* cin, gu64* cout, unsigned epoch, gu32* err, const double* sv,
                                                  volatile lds_int* ioflag, float2* Fout, size_t fpitch, int x0, double scale)
 {
@@ -271,7 +356,8 @@ __device__ __forceinline__ void x_remainder_loop(const XRing& ring, double* cb, 
     // for two and four steps ahead (a full memory latency, ~1800 clocks per step: harmless while the wave had nothing else to
     // do, not once it solves).  vmcnt(9): the carry loads are older than the 9 loads x_produce always issues after them
     // (8 of issue_row + the flow fetch; the asm statements clobber "memory", so none of those moves ahead of them), loads
-    // return in order, so "at most 9 outstanding" means the carries have arrived.
+    // return in order, so "at most 9 outstanding" means the carries have arrived.  (The resampling source fetches four
+    // loads per row where FlowSrc has one: 12 younger loads, the same wait.)
     unsigned long long g0 = 0, g1 = 0;
     auto carry_load = [&](int s) {
         const gu64* q = cin + 40 * s + 2 * l;
@@ -313,11 +399,12 @@ __device__ __forceinline__ void x_remainder_loop(const XRing& ring, double* cb, 
     };
     if (r == 0) x_rows_above<MH>(ring, R0, R1, F, W, H, xc, col);
     RowIn in[2];
-    float2 dd[2], fl[2];
+    float2 dd[2];
+    typename FS::Pend fl[2];
 #pragma unroll
     for (int ts = 0; ts < 2; ts++) {
         const int y = min(4 * ts + MH + r, H - 1);
-        dd[ts] = F.fetch(y);
+        dd[ts] = F.value(F.fetch(y), y);
         issue_row(in[ts], R0, R1, W, H, xc, y, dd[ts]);
     }
 #pragma unroll
@@ -647,12 +734,14 @@ __device__ __forceinline__ void x_scanner_loop(double* sv, const double* vinit, 
 // = item << 8 | strip, the i-th job of XCD k's list (nstrips = the lists' common stride); built on the host so that
 // only strips that exist are ever taken and the strips of an item follow each other in one list.  The grid is exactly
 // the number of jobs: a workgroup whose XCD's list has run out takes the next job of another list.
-template <int MH, bool HET>
-__global__ __launch_bounds__((XGeom<MH>::THREADS)) void k_iterate_x(
+// The walk is one body for both kernels below: F holds what the flow source needs beyond its field `flow_in` (nothing for
+// FlowSrc), and the producers bind it to their pair and column.
+template <int MH, bool HET, class FS>
+__device__ __forceinline__ void x_walk(
     const float* __restrict__ R0b, const float* __restrict__ R1b, size_t pair_stride, const float* __restrict__ flow_in,
     float* __restrict__ flow_out, int W, int H, int block_size, const nsof_het_item* __restrict__ items, int het_final,
     int n, int nstrips, unsigned long long* carry, unsigned* tickets, unsigned epoch, unsigned* err, int fault,
-    const unsigned* __restrict__ xjobs)
+    const unsigned* __restrict__ xjobs, FS F)
 {
     using G = XGeom<MH>;
     constexpr int SW = G::SW, COLS = G::COLS;
@@ -740,9 +829,7 @@ __global__ __launch_bounds__((XGeom<MH>::THREADS)) void k_iterate_x(
         // producers: waves NCW+1 .. NCW+NB rows 0,1 of blocks 0..NB-1; wave NCW+NB+1 the remainder; then rows 2,3
         const int pw = wave - (G::NCW + 1);
         const int lane = tid & 63;
-        FlowSrc F;
-        F.base = reinterpret_cast<const char*>(flow_in) + (HET ? 0 : (size_t)pair * plane * 8);
-        F.W = (unsigned)W;
+        F.template bind<HET>(flow_in, pair, plane, W);
         // wave -> role.  Waves go to SIMD (wave % 4): 4-6 rows 0,1 of blocks 0-2; 7 I/O; 8-10 rows 2,3 of blocks 0-2.
         const bool is_io = pw == G::NB;
         const int gp = pw < G::NB ? 0 : 1;
@@ -750,7 +837,7 @@ __global__ __launch_bounds__((XGeom<MH>::THREADS)) void k_iterate_x(
         if (is_io) {
             const int col = G::NB * 64 + (lane & 15), r = lane >> 4;
             const int xc = clampi(x0 - MH - 1 + col, 0, W - 1);
-            F.xc = (unsigned)xc;
+            F.column(xc);
             const size_t per_strip = (size_t)nimg * 40;
             gu64* cin = strip > 0 ? cbase + (size_t)(strip - 1) * per_strip : nullptr;
             // NSOF_OPT_DEBUG_FAULT bit 0 (test hook): strip 0 of item 0 keeps its carries to itself
@@ -761,13 +848,54 @@ __global__ __launch_bounds__((XGeom<MH>::THREADS)) void k_iterate_x(
         } else {
             const int col = blk * 64 + lane;
             const int xc = clampi(x0 - MH - 1 + col, 0, W - 1);
-            F.xc = (unsigned)xc;
+            F.column(xc);
             if (gp == 0)
                 x_producer_loop<MH, 0>(ring, R0, R1, F, W, H, xc, col, nimg);
             else
                 x_producer_loop<MH, 1>(ring, R0, R1, F, W, H, xc, col, nimg);
         }
     }
+}
+
+template <int MH, bool HET>
+__global__ __launch_bounds__((XGeom<MH>::THREADS)) void k_iterate_x(
+    const float* __restrict__ R0b, const float* __restrict__ R1b, size_t pair_stride, const float* __restrict__ flow_in,
+    float* __restrict__ flow_out, int W, int H, int block_size, const nsof_het_item* __restrict__ items, int het_final,
+    int n, int nstrips, unsigned long long* carry, unsigned* tickets, unsigned epoch, unsigned* err, int fault,
+    const unsigned* __restrict__ xjobs)
+{
+    x_walk<MH, HET>(R0b, R1b, pair_stride, flow_in, flow_out, W, H, block_size, items, het_final, n, nstrips, carry, tickets, epoch,
+                    err, fault, xjobs, FlowSrc{});
+}
+
+// The first iteration of a level that is an exact doubling of the coarser one: k_iterate_x<MH, false> with its flow_in
+// resampled from the coarser level's flow (pw x ph, W == 2 * pw, H == 2 * ph) as it is fetched -- FlowResample2x.  Same
+// geometry, roles, tickets, carries, epoch tags, bounded waits and error word; uniform batches only.
+template <int MH>
+__global__ __launch_bounds__((XGeom<MH>::THREADS)) void k_iterate_xr(
+    const float* __restrict__ R0b, const float* __restrict__ R1b, size_t pair_stride, const float* __restrict__ coarse,
+    int pw, int ph, float mul, float* __restrict__ flow_out, int W, int H, int block_size, int n, int nstrips,
+    unsigned long long* carry, unsigned* tickets, unsigned epoch, unsigned* err, int fault)
+{
+    FlowResample2x F;
+    F.pw = (unsigned)pw;
+    F.ph = ph;
+    F.mul = mul;
+    x_walk<MH, false>(R0b, R1b, pair_stride, coarse, flow_out, W, H, block_size, nullptr, 0, n, nstrips, carry, tickets, epoch, err,
+                      fault, nullptr, F);
+}
+
+// What a launch of either kernel needs of the context: carry buffer, cleared tickets, error word, a fresh epoch.
+int x_launch_state(nsof_ctx* ctx, size_t cbytes, unsigned long long** carry, unsigned** tickets, unsigned** err, unsigned* epoch)
+{
+    if (int rc = nsof_xsync_reserve(ctx, cbytes, carry, tickets, err)) return rc;
+    NSOF_HIP(ctx, hipMemsetAsync(*tickets, 0, 8 * 32 * sizeof(unsigned), ctx->stream));
+    *epoch = ++ctx->x_epoch;
+    if (*epoch == 0) {   // wrapped: every tag in the buffer is stale but may match again -> clear it
+        NSOF_HIP(ctx, hipMemsetAsync(ctx->x_carry.p, 0, ctx->x_carry.cap, ctx->stream));
+        *epoch = ++ctx->x_epoch;
+    }
+    return NSOF_OK;
 }
 
 template <int MH, bool HET>
@@ -782,19 +910,34 @@ int launch_x(nsof_ctx* ctx, int n, int max_w, int max_h, const float* R0, const 
     unsigned long long* carry = nullptr;
     unsigned* tickets = nullptr;
     unsigned* err = nullptr;
+    unsigned epoch = 0;
     // uniform batches: [pair][strip][row][5] doubles as two granules each; work lists: the mirror of the expansion buffer
     const size_t cbytes = HET ? 0 : (size_t)n * nstrips * (size_t)((max_h + 3) / 4) * 40 * 8;
-    if (int rc = nsof_xsync_reserve(ctx, cbytes, &carry, &tickets, &err)) return rc;
-    NSOF_HIP(ctx, hipMemsetAsync(tickets, 0, 8 * 32 * sizeof(unsigned), ctx->stream));
-    unsigned epoch = ++ctx->x_epoch;
-    if (epoch == 0) {   // wrapped: every tag in the buffer is stale but may match again -> clear it
-        NSOF_HIP(ctx, hipMemsetAsync(ctx->x_carry.p, 0, ctx->x_carry.cap, ctx->stream));
-        epoch = ++ctx->x_epoch;
-    }
+    if (int rc = x_launch_state(ctx, cbytes, &carry, &tickets, &err, &epoch)) return rc;
     const unsigned grid = HET ? (unsigned)njobs : 8u * (unsigned)((n + 7) / 8) * (unsigned)nstrips;
     hipLaunchKernelGGL((k_iterate_x<MH, HET>), dim3(grid), dim3(G::THREADS), G::SMEM, ctx->stream, R0, R1, pair_stride, flow_in,
                        flow_out, W, H, winsize, items, final ? 1 : 0, n, nstrips, carry, tickets, epoch, err, ctx->dbg_fault,
                        xjobs);
+    return NSOF_OK;
+}
+
+// The resampling twin's launcher: the uniform arm of the one above, for k_iterate_xr.
+template <int MH>
+int launch_xr(nsof_ctx* ctx, int n, const float* R0, const float* R1, size_t pair_stride, const float* coarse, int pw, int ph,
+              float mul, float* flow_out, int W, int H, int winsize)
+{
+    using G = XGeom<MH>;
+    if (int rc = lds_opt_in(ctx, k_iterate_xr<MH>, G::SMEM)) return rc;
+    const int nstrips = (W + G::SW - 1) / G::SW;
+    unsigned long long* carry = nullptr;
+    unsigned* tickets = nullptr;
+    unsigned* err = nullptr;
+    unsigned epoch = 0;
+    const size_t cbytes = (size_t)n * nstrips * (size_t)((H + 3) / 4) * 40 * 8;
+    if (int rc = x_launch_state(ctx, cbytes, &carry, &tickets, &err, &epoch)) return rc;
+    const unsigned grid = 8u * (unsigned)((n + 7) / 8) * (unsigned)nstrips;
+    hipLaunchKernelGGL((k_iterate_xr<MH>), dim3(grid), dim3(G::THREADS), G::SMEM, ctx->stream, R0, R1, pair_stride, coarse, pw, ph,
+                       mul, flow_out, W, H, winsize, n, nstrips, carry, tickets, epoch, err, ctx->dbg_fault);
     return NSOF_OK;
 }
 
@@ -811,6 +954,24 @@ int nsof_launch_iterate_x(nsof_ctx* ctx, int n_pairs, const float* R0, const flo
                                                   false, nullptr, 0, 0);
     });
     if (!known) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "exact-order fused iteration supports winsize 2..15");
+    if (rc) return rc;
+    NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
+}
+
+// The same with flow_in = resample(coarse_flow) * mul formed inside the kernel (k_iterate_xr): a level's first iteration.
+int nsof_launch_iterate_x_resample(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
+                                   const float* coarse_flow, int pw, int ph, float mul, float* flow_out, int W, int H, int winsize)
+{
+    if (pw < 1 || ph < 1 || W != 2 * pw || H != 2 * ph)
+        return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "resampling iteration: %dx%d is not the double of %dx%d", W, H, pw, ph);
+    if (winsize < 2 || winsize > 15)
+        return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "exact-order fused iteration supports winsize 2..15");
+    nsof_prof_scope ps(ctx, NSOF_K_ITERATE);
+    int rc = NSOF_OK;
+    nsof_with_int<1, 7>(winsize / 2, [&](auto mh) {
+        rc = launch_xr<decltype(mh)::value>(ctx, n_pairs, R0, R1, pair_stride, coarse_flow, pw, ph, mul, flow_out, W, H, winsize);
+    });
     if (rc) return rc;
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;

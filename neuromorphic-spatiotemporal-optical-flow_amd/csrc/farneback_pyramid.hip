@@ -21,21 +21,7 @@
 
 namespace {
 
-// resize(INTER_LINEAR) coordinate: f = (float)((d+0.5)*scale-0.5); s = floor(f); a = f-s.
-__device__ __forceinline__ void lin_coord_x(int d, double scale, int slen, int& s, float& a)
-{
-    float f = (float)((d + 0.5) * scale - 0.5);
-    s = floor_f(f);
-    a = f - s;
-    if (s < 0) { s = 0; a = 0.f; }
-    if (s >= slen - 1) { s = slen - 1; a = 0.f; }
-}
-__device__ __forceinline__ void lin_coord_y(int d, double scale, int& s, float& a)
-{
-    float f = (float)((d + 0.5) * scale - 0.5);
-    s = floor_f(f);
-    a = f - s;
-}
+// (resize(INTER_LINEAR) coordinates: lin_coord_x / lin_coord_y, nsof_internal.h)
 
 // ---------------------------------------------------------------------------------------
 // Pyramid level preparation: u8 / f32 -> f32, separable Gaussian (sepFilter2D order), bilinear

@@ -116,14 +116,143 @@ __device__ __forceinline__ void matrix_from(const RowIn& in, float dx, float dy,
     M[4] = r6 * r2 + r5 * r3;
 }
 
-// Where a thread's flow_in comes from: the level's own flow buffer.  fetch() only issues the load (the result is
-// consumed windows later).
+// Where a thread's flow_in comes from: a policy type of the strip walker (k_iterate_x).  fetch(r) only issues the loads of
+// image row r at the thread's column -> Pend (consumed windows later); value(pend, r) is the flow of that pixel.
+//   bind(field, pair, plane, W)   this pair's field (HET: `field` is the item's own already)
+//   column(xc)                    the thread's image column
+// FlowSrc: the level's own flow buffer, one 8-byte load per row, value() is the identity.
 struct FlowSrc {
+    typedef float2 Pend;
     const char* base;   // flow_in of this pair
     unsigned W, xc;
+    template <bool HET>
+    __device__ __forceinline__ void bind(const float* field, int pair, size_t plane, int w)
+    {
+        base = reinterpret_cast<const char*>(field) + (HET ? 0 : (size_t)pair * plane * 8);
+        W = (unsigned)w;
+    }
+    __device__ __forceinline__ void column(int c) { xc = (unsigned)c; }
     __device__ __forceinline__ float2 fetch(int r) const
     {
         return *reinterpret_cast<const float2*>(base + ((unsigned)r * W + xc) * 8u);
+    }
+    __device__ __forceinline__ float2 value(const float2& p, int) const { return p; }
+};
+
+// FlowResample2x: the flow of the COARSER level, pw x ph with W == 2 * pw and H == 2 * ph, resampled on the fly: for fine
+// pixel (x, y) exactly what k_flow_upsample (farneback_pyramid.hip) writes and FlowSrc then reads,
+//     t0 = p00*a0 + p01*a1;  t1 = p10*a0 + p11*a1;  o = (t0*b0 + t1*b1) * mul        (every a*b + c two roundings),
+// with the coordinates, weights and clamps of lin_coord_x / lin_coord_y at scale 0.5.  The column pair and a0, a1 belong to
+// the thread (column()).  Rows: at scale 0.5 the coordinate of row 2k + p is f = k + (p + 0.5) * 0.5 - 0.5, exact in double
+// and in float (k < 2^21), so lin_coord_y(2k + p) = (k + sy(p), b1(p)): the helper is evaluated for rows 0 and 1 once
+// (bind()) and a row costs a shift, an add and two clamps -- scalar work where the row is wave-uniform.
+// A weight of zero does not excuse its load (0 * NaN is NaN): the clamped pixel is loaded and multiplied as k_flow_upsample
+// does.  Every address is clamped into this pair's coarse field.
+// Two forms.  The plain one (fetch / value, the policy's interface): the four 8-byte loads of a fine row stay pending -- 8
+// registers where FlowSrc has 2 -- and every blend is done per fine row.  Four such rows in flight do not fit the strip
+// walker's 168 registers (45-69 spilled), so its full producer waves, whose two rows per window are wave-uniform and
+// adjacent, take the pair form (fetch2 / value2): a window's rows (ra, rb) = (i, i + 1), both clamped to H - 1, sample
+//     i odd:   ra and rb both the coarse rows (s, s + 1), s = sy(ra)               -> X = s, Y = s + 1
+//     i even:  ra the rows (s, s + 1), rb the rows (s + 1, s + 2)                  -> X = s + 1, Y = sy(rb) + 1
+// (each clamped to the field), so a window loads the two rows X and Y at the thread's column pair (8 registers pending),
+// blends each horizontally ONCE and uses it for both fine rows; for even i row s is the previous window's Y, whose blend
+// is carried in two registers (z).  That holds with the clamps: H is even, so a clamped fine row is H - 1, odd, with
+// sy = ph - 1, and clamp(ph) = clamp(ph - 1) = ph - 1; consecutive windows are i and i + 4.  The blends themselves are
+// the expressions above on the same operands, shared as k_flow_upsample_walk shares them.
+struct FlowResample2x {
+    struct Pend {
+        float2 p00, p01, p10, p11;
+    };
+    struct Pend2 {
+        float2 x0, x1, y0, y1;   // coarse rows X and Y at the column pair
+    };
+    const char* base;   // coarse flow of this pair
+    unsigned pw;
+    int ph;
+    float mul;
+    int sy0, sy1;       // lin_coord_y of rows 0 and 1
+    float b10, b11;
+    unsigned c0, c1;    // byte offsets of the column pair in a coarse row
+    float a0, a1;
+    template <bool HET>
+    __device__ __forceinline__ void bind(const float* field, int pair, size_t, int)
+    {
+        static_assert(!HET, "uniform batches only");
+        base = reinterpret_cast<const char*>(field) + (size_t)pair * pw * (size_t)ph * 8;
+        lin_coord_y(0, 0.5, sy0, b10);
+        lin_coord_y(1, 0.5, sy1, b11);
+        // wave-uniform by construction; say so, so that the per-row arithmetic stays on the scalar unit
+        sy0 = __builtin_amdgcn_readfirstlane(sy0);
+        sy1 = __builtin_amdgcn_readfirstlane(sy1);
+        b10 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, b10)));
+        b11 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, b11)));
+    }
+    __device__ __forceinline__ void column(int c)
+    {
+        int sx;
+        lin_coord_x(c, 0.5, (int)pw, sx, a1);
+        a0 = 1.f - a1;
+        c0 = (unsigned)sx * 8u;
+        c1 = (unsigned)min(sx + 1, (int)pw - 1) * 8u;
+    }
+    // lin_coord_y of fine row r: its upper coarse row (unclamped), and its weight b1
+    __device__ __forceinline__ int row_sy(int r) const { return (r >> 1) + ((r & 1) ? sy1 : sy0); }
+    __device__ __forceinline__ float row_b1(int r) const { return (r & 1) ? b11 : b10; }
+    // byte offset of coarse row cr, clamped into the field
+    __device__ __forceinline__ unsigned row_off(int cr) const { return (unsigned)clampi(cr, 0, ph - 1) * pw * 8u; }
+    __device__ __forceinline__ float2 at(unsigned off) const { return *reinterpret_cast<const float2*>(base + off); }
+    // t = p0*a0 + p1*a1 of one coarse row; o = (t0*b0 + t1*b1) * mul of fine row r
+    __device__ __forceinline__ float2 hblend(const float2& p0, const float2& p1) const
+    {
+        return make_float2(nsof_madd<false>(p0.x, a0, p1.x * a1), nsof_madd<false>(p0.y, a0, p1.y * a1));
+    }
+    __device__ __forceinline__ float2 vblend(const float2& t0, const float2& t1, int r) const
+    {
+        const float b1 = row_b1(r), b0 = 1.f - b1;
+        return make_float2(nsof_madd<false>(t0.x, b0, t1.x * b1) * mul, nsof_madd<false>(t0.y, b0, t1.y * b1) * mul);
+    }
+    // ---- the plain form
+    __device__ __forceinline__ Pend fetch(int r) const
+    {
+        const int sy = row_sy(r);
+        const unsigned r0 = row_off(sy), r1 = row_off(sy + 1);
+        Pend p;
+        p.p00 = at(r0 + c0);
+        p.p01 = at(r0 + c1);
+        p.p10 = at(r1 + c0);
+        p.p11 = at(r1 + c1);
+        return p;
+    }
+    __device__ __forceinline__ float2 value(const Pend& p, int r) const
+    {
+        return vblend(hblend(p.p00, p.p01), hblend(p.p10, p.p11), r);
+    }
+    // ---- the pair form: rows (ra, rb) of a window whose first stream index has parity ODD
+    template <bool ODD>
+    __device__ __forceinline__ Pend2 fetch2(int ra, int rb) const
+    {
+        const unsigned rx = row_off(row_sy(ra) + (ODD ? 0 : 1)), ry = row_off((ODD ? row_sy(ra) : row_sy(rb)) + 1);
+        Pend2 q;
+        q.x0 = at(rx + c0);
+        q.x1 = at(rx + c1);
+        q.y0 = at(ry + c0);
+        q.y1 = at(ry + c1);
+        return q;
+    }
+    // z: the blend of the previous window's row Y (ODD: unused)
+    template <bool ODD>
+    __device__ __forceinline__ void value2(const Pend2& q, float2& z, int ra, int rb, float2& oa, float2& ob) const
+    {
+        const float2 hx = hblend(q.x0, q.x1), hy = hblend(q.y0, q.y1);
+        oa = ODD ? vblend(hx, hy, ra) : vblend(z, hx, ra);
+        ob = vblend(hx, hy, rb);
+        z = hy;
+    }
+    // the blend of the upper coarse row of fine row r, at once: the first even window's z
+    __device__ __forceinline__ float2 upper_row(int r) const
+    {
+        const unsigned r0 = row_off(row_sy(r));
+        return hblend(at(r0 + c0), at(r0 + c1));
     }
 };
 

@@ -624,6 +624,18 @@ extern "C" int nsof_stage_iterate_upsample(nsof_ctx* ctx, int n_pairs, const flo
     return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "fused upsample+iteration not available for winsize %d", winsize);
 }
 
+extern "C" int nsof_stage_iterate_x_resample(nsof_ctx* ctx, int n_pairs, const float* d_R, const float* d_coarse_flow,
+                                             int src_w, int src_h, int width, int height, int winsize, double pyr_scale,
+                                             float* d_flow_out)
+{
+    if (!ctx || !d_R || !d_coarse_flow || !d_flow_out || d_coarse_flow == d_flow_out || n_pairs < 1 || width < 1 || height < 1 ||
+        src_w < 1 || src_h < 1)
+        return NSOF_EINVAL;
+    const size_t plane = (size_t)width * height;
+    return nsof_launch_iterate_x_resample(ctx, n_pairs, d_R, d_R + 5 * plane, 10 * plane, d_coarse_flow, src_w, src_h,
+                                          (float)(1. / pyr_scale), d_flow_out, width, height, winsize);
+}
+
 extern "C" int nsof_stage_flow_upsample(nsof_ctx* ctx, int n_pairs, const float* d_src, int sw, int sh, float* d_dst,
                                         int dw, int dh, double pyr_scale)
 {

@@ -319,6 +319,12 @@ int nsof_launch_iterate(nsof_ctx* ctx, int n_pairs, const float* R0, const float
 // Exact-order fused iteration in ONE kernel (running row sums inside the strip walker, strips chained by carries).
 int nsof_launch_iterate_x(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
                           const float* flow_in, float* flow_out, int W, int H, int winsize);
+// The same iteration reading its flow_in as resample(coarse_flow [ph][pw][2]) * mul, formed on the fly (k_iterate_xr): what
+// nsof_launch_flow_upsample followed by nsof_launch_iterate_x computes, bit for bit, for an exact doubling and the
+// two-rounding blend.  NSOF_EUNSUPPORTED, nothing launched, unless W == 2 * pw, H == 2 * ph and winsize is 2..15.
+int nsof_launch_iterate_x_resample(nsof_ctx* ctx, int n_pairs, const float* R0, const float* R1, size_t pair_stride,
+                                   const float* coarse_flow, int pw, int ph, float mul, float* flow_out, int W, int H,
+                                   int winsize);
 // d_xjobs: the level's job table -- 8 counts, then 8 lists (one per XCD, `stride` entries apart) of item << 8 | strip;
 // njobs = the sum of the counts = the grid; strips are NSOF_X_STRIP output columns wide.
 #define NSOF_X_STRIP 192
@@ -432,6 +438,22 @@ __device__ __forceinline__ int floor_f(float v)
     if (!(v >= -2147483648.0f && v < 2147483648.0f)) return v < 0.f ? 2147483647 : -2147483647 - 1;
     int i = (int)v;
     return i - (i > v);
+}
+// resize(INTER_LINEAR) coordinate: f = (float)((d+0.5)*scale-0.5); s = floor(f); a = f-s.  The pyramid levels, the flow
+// resample (farneback_pyramid.hip) and the resampling flow source of the exact iteration (iterate_common.h).
+__device__ __forceinline__ void lin_coord_x(int d, double scale, int slen, int& s, float& a)
+{
+    float f = (float)((d + 0.5) * scale - 0.5);
+    s = floor_f(f);
+    a = f - s;
+    if (s < 0) { s = 0; a = 0.f; }
+    if (s >= slen - 1) { s = slen - 1; a = 0.f; }
+}
+__device__ __forceinline__ void lin_coord_y(int d, double scale, int& s, float& a)
+{
+    float f = (float)((d + 0.5) * scale - 0.5);
+    s = floor_f(f);
+    a = f - s;
 }
 
 // cv2's fixed-point cvtColor to gray of one interleaved 3-channel 8-bit pixel (c0, c1, c2): weights in units of 2^-15,
