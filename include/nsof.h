@@ -670,6 +670,35 @@ int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int scheme, int 
                           const int64_t* t, const int64_t* slice_bounds, int64_t n_slices, int64_t snap_every, int memsize,
                           double v_ds, int n_trials, int n_maps, const int* keys, const float* const* planes,
                           const int* plane_trials, float* d_w, float* d_resistance, double* d_block_current);
+/* Cycle-to-cycle (C2C) write noise of the trial run: the same device, driven by the same pulse, moves by a different amount
+ * each time.  One standard variate xi belongs to each update, a pure function of (seed, array a, trial t, pixel = y * W + x,
+ * slice = the absolute 0-based index of the slice in the call's slice_bounds); nothing is consumed, so xi does not depend on
+ * the grouping, the snapshot cadence, the number of trials or which kernel form runs.
+ *   generator  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85), counter =
+ *              (pixel, slice & 0xffffffff, slice >> 32, t + 65536 * a), key = (seed & 0xffffffff, seed >> 32)
+ *   variate    S = the sum of the 16 bytes of the four output words (0..4080); xi = (float)(S - 2040) * 0x1.bb688cp-9f, the
+ *              float32 of 1 / sqrt(87380): Irwin-Hall(16) on bytes, mean 0, variance 1, support +-6.90.  Integer steps and
+ *              one rounded multiply: host and device agree bit for bit
+ *   update     with g = ka * pow(1 - w*s, b) as the noiseless update forms it: f = max(0, 1 + sigma * xi) -- product rounded,
+ *              sum rounded, clamped at 0: a pulse may fail to switch, it never switches backwards --, wn = w + (g * f) * dt,
+ *              then the clip.  sigma = sigma_off where the drive took the V < voff branch, sigma_on where it took V > von; a
+ *              dead-zone drive is untouched.  The active and the silent drive alike. */
+typedef struct nsof_accum_c2c {
+    uint64_t seed;
+    float sigma_on, sigma_off;
+} nsof_accum_c2c;
+/* nsof_accum_trials_dev with C2C noise: the same arguments, then c2c.  c2c == NULL, or both sigmas 0, is the noiseless run:
+ * nsof_accum_trials_dev's kernels and bits (that entry IS this one called with NULL).  NSOF_EINVAL, before anything is
+ * allocated: a sigma that is negative or not finite, the message naming the field and the value. */
+int nsof_accum_trials_c2c_dev(nsof_ctx* ctx, int height, int width, int scheme, int polarity_split, float active_v,
+                              float silent_v, const nsof_accum_params* params, int theta, const int16_t* x, const int16_t* y,
+                              const int8_t* p, const int64_t* t, const int64_t* slice_bounds, int64_t n_slices,
+                              int64_t snap_every, int memsize, double v_ds, int n_trials, int n_maps, const int* keys,
+                              const float* const* planes, const int* plane_trials, float* d_w, float* d_resistance,
+                              double* d_block_current, const nsof_accum_c2c* c2c);
+/* The variates of that run on the HOST (no context, no device): out[i] = xi of (seed, array, trial, pixel, slice + i) for
+ * i in [0, n_slices). */
+void nsof_accum_c2c_noise(uint64_t seed, int array, int trial, uint32_t pixel, int64_t slice, int64_t n_slices, float* out);
 /* compress_image of the same script (:111-121) for a stack of 8-bit DEVICE frames: imresize(im2double(frame), [out_h
  * out_w], 'lanczos3') of n_frames frames into d_out [n_frames][out_h][out_w] (DEVICE, dense float64).  d_frames points
  * at the first pixel of the region to compress -- a crop is a pointer offset plus width and height -- with row_stride and

@@ -21,6 +21,11 @@
 // stream, the group cuts at the snapshot slices, and -- with the trial as a grid dimension -- k_setup_maps (which also writes the
 // initial state here), k_resistance and k_block_min_resistance, the latter taken from the state at the snapshot slices: no
 // full-resolution snapshot stack exists.
+//
+// Cycle-to-cycle write noise (nsof_accum_trials_c2c_dev): every update is scaled by f = max(0, 1 + sigma * xi), xi one
+// standard variate per (seed, array, trial, pixel, slice) from a counter generator (c2c_xi: nothing is consumed, so the
+// draw does not depend on the grouping, the trial chunk or the kernel form).  The NOISE arms of the two update kernels
+// carry it; a call without noise runs the NOISE = false arms, which are the kernels as they were.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -31,6 +36,89 @@ namespace {
 
 constexpr int TRIAL_CHUNK = 4;       // trials per thread of k_trials_update
 constexpr int MAX_TRIALS = 65535;    // the trial axis is a grid dimension
+
+// ---- cycle-to-cycle write noise ------------------------------------------------------------------------------------------
+// Philox4x32-10 (Salmon et al., SC'11): c <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)) ten times,
+// the key bumped by the Weyl constants after each of the first nine rounds.  Integer arithmetic only: host and device agree.
+__host__ __device__ inline void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1)
+{
+    constexpr unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+    for (int r = 0; r < 10; r++) {
+        const unsigned long long p0 = (unsigned long long)M0 * c[0], p1 = (unsigned long long)M1 * c[2];
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1;
+        c[0] = n0; c[1] = (unsigned)p1; c[2] = n2; c[3] = (unsigned)p0;
+        k0 += W0; k1 += W1;   // (the bump after the tenth round is never read)
+    }
+}
+// The variate of one update: counter (pixel, slice low, slice high, trial + 65536 * array), key = the seed's two words; S =
+// the sum of the 16 output bytes (0..4080, Irwin-Hall(16) on bytes: mean 2040, variance 87380), xi = float(S - 2040) * c
+// with c = float32(1 / sqrt(87380)): one exact conversion and one rounded multiply.  The bytes are summed two per 16-bit
+// lane (8 * 255 fits), then the lanes: plain integer code, the same on both sides.
+__host__ __device__ inline float c2c_xi(unsigned k0, unsigned k1, unsigned pixel, unsigned long long slice, unsigned trial_word)
+{
+    unsigned c[4] = {pixel, (unsigned)slice, (unsigned)(slice >> 32), trial_word};
+    philox4x32_10(c, k0, k1);
+    unsigned lanes = 0;
+    for (int i = 0; i < 4; i++) lanes += (c[i] & 0x00ff00ffu) + ((c[i] >> 8) & 0x00ff00ffu);
+    const int sum = (int)((lanes & 0xffffu) + (lanes >> 16));
+    return (float)(sum - 2040) * 0x1.bb688cp-9f;
+}
+__host__ __device__ inline unsigned c2c_trial_word(int array, int trial) { return (unsigned)trial + 65536u * (unsigned)array; }
+
+// What a NOISE arm is handed per launch.  branch: per (drive trial, pixel) one byte, bits 0-1 the branch the active drive
+// took, bits 2-3 the silent drive's (BR_DEAD: ka = 0, no noise; BR_OFF: V < voff, sigma_off; BR_ON: V > von, sigma_on).
+enum { BR_DEAD = 0, BR_OFF = 1, BR_ON = 2 };
+struct C2c {
+    unsigned k0, k1;
+    float sigma_off, sigma_on;
+    const unsigned char* branch;
+    size_t branch_stride;      // bytes between the planes of consecutive trials (0: one plane for all)
+    long long slice0;          // the absolute index of the group's first slice
+    unsigned array_word;       // 65536 * array
+};
+struct NoC2c {};
+template <bool NOISE>
+using C2cArg = std::conditional_t<NOISE, C2c, NoC2c>;   // no noise passes nothing: the instantiations there always were
+
+__device__ __forceinline__ float sigma_of(const C2c& nz, unsigned br) { return br == BR_OFF ? nz.sigma_off : (br == BR_ON ? nz.sigma_on : 0.f); }
+
+// update_drive with the step scaled by f = max(0, 1 + sigma * xi): a pulse may fail to switch, it never switches backwards.
+// Every operation is rounded on its own (-ffp-contract=off).  sigma == 0 -- the dead zone, or a branch without noise -- gives
+// f = 1 + 0 = 1 and (g * 1) * dt = g * dt: update_drive's bits, so the draw is skipped.
+__device__ __forceinline__ float update_drive_c2c(float w, const Drive& d, float sigma, const C2c& nz, unsigned pix, long long slice,
+                                                  unsigned trial_word)
+{
+    const float g = d.ka * pow_f32(1.f - w * d.s, d.b);
+    float f = 1.f;
+    if (sigma != 0.f) {
+        const float sx = sigma * c2c_xi(nz.k0, nz.k1, pix, (unsigned long long)slice, trial_word);
+        const float u = 1.f + sx;
+        f = u < 0.f ? 0.f : u;
+    }
+    const float wn = w + (g * f) * d.dt;
+    return wn < 0.f ? 0.f : (wn > 1.f ? 1.f : wn);
+}
+// replay_driven with each set bit's own slice: the group's first slice plus the slice the bit stands for (a count
+// threshold's driven word has one bit per field, in slice order).
+__device__ __forceinline__ float replay_driven_c2c(float ww, unsigned m, const Drive& da, float sigma, const C2c& nz, unsigned pix,
+                                                   unsigned trial_word)
+{
+    for (; m; m &= m - 1) ww = update_drive_c2c(ww, da, sigma, nz, pix, nz.slice0 + (__ffs((int)m) - 1), trial_word);
+    return ww;
+}
+
+// Once per noisy call, per (drive trial = blockIdx.y, pixel): the branches drive_of takes at the two voltages, from the same
+// float32 thresholds (a mapped key's value, an unmapped one's scalar) with the same comparisons.
+__global__ __launch_bounds__(256) void k_setup_c2c(MapSrc src, size_t n, float v_act, float v_sil, unsigned char* __restrict__ branch)
+{
+    const size_t t = blockIdx.y;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        auto get = [&](int k) { return src.plane[k] ? src.plane[k][t * src.stride[k] + i] : src.scalar[k]; };
+        const float voff = get(NSOF_ACCUM_KEY_VOFF), von = get(NSOF_ACCUM_KEY_VON);
+        auto br = [&](float v) { return v < voff ? (unsigned)BR_OFF : (v > von ? (unsigned)BR_ON : (unsigned)BR_DEAD); };
+        branch[t * n + i] = (unsigned char)(br(v_act) | (br(v_sil) << 2));
+    }
+}
 
 // The group's refractory table in LDS (scheme 2), as the single-array update kernels hold it.
 template <bool REFR>
@@ -81,10 +169,12 @@ __global__ __launch_bounds__(256) void k_trials_resolve(unsigned* __restrict__ m
 
 // blockIdx.y: a chunk of TRIAL_CHUNK trials.  act_stride: floats between the drive planes of consecutive trials (0: one
 // plane for all).  Nothing here is shared between trial chunks but the read-only list and driven words.
+//   NOISE  cycle-to-cycle write noise: one more byte per (trial, listed pixel), the active drive's branch
+template <bool NOISE>
 __global__ __launch_bounds__(256) void k_trials_update(float* __restrict__ w, const unsigned* __restrict__ list,
                                                         const unsigned* __restrict__ count, const unsigned* __restrict__ driven,
                                                         const float* __restrict__ act, size_t act_stride, size_t npx, int n_trials,
-                                                        float dt)
+                                                        float dt, C2cArg<NOISE> nz)
 {
     const unsigned n = *count;
     const int t0 = blockIdx.y * TRIAL_CHUNK;
@@ -94,26 +184,36 @@ __global__ __launch_bounds__(256) void k_trials_update(float* __restrict__ w, co
         const size_t pix = list[i];
         float ww[TRIAL_CHUNK];
         Drive d[TRIAL_CHUNK];
+        [[maybe_unused]] float sg[TRIAL_CHUNK];
 #pragma unroll
         for (int k = 0; k < TRIAL_CHUNK; k++)
             if (t0 + k < n_trials) {
                 ww[k] = w[(size_t)(t0 + k) * npx + pix];
                 d[k] = drive_at(act + (size_t)(t0 + k) * act_stride, pix, dt);
+                if constexpr (NOISE) sg[k] = sigma_of(nz, nz.branch[(size_t)(t0 + k) * nz.branch_stride + pix] & 3u);
             }
 #pragma unroll
         for (int k = 0; k < TRIAL_CHUNK; k++)
-            if (t0 + k < n_trials) w[(size_t)(t0 + k) * npx + pix] = replay_driven(ww[k], m, d[k]);
+            if (t0 + k < n_trials) {
+                if constexpr (NOISE)
+                    w[(size_t)(t0 + k) * npx + pix] =
+                        replay_driven_c2c(ww[k], m, d[k], sg[k], nz, (unsigned)pix, nz.array_word + (unsigned)(t0 + k));
+                else
+                    w[(size_t)(t0 + k) * npx + pix] = replay_driven(ww[k], m, d[k]);
+            }
     }
 }
 
 // The every-pixel form: silent_v outside the dead zone of some pixel of some trial.  One thread per pixel resolves the
 // pixel's mask word once and replays all n_sl slices of the group for each trial with that trial's two drives (a pixel whose
 // own dead zone holds silent_v carries the no-op drive, ka = 0), as k_update_all does for one mapped array.
-template <bool REFR, bool COUNT>
+//   NOISE  cycle-to-cycle write noise on both drives, each with the sigma of its own branch (a dead-zone drive has none)
+template <bool REFR, bool COUNT, bool NOISE>
 __global__ __launch_bounds__(256) void k_trials_update_all(float* __restrict__ w, unsigned* __restrict__ mask,
                                                             long long* __restrict__ next_ok, size_t npx, int n_sl, TabArg<REFR> tab,
                                                             const float* __restrict__ act, const float* __restrict__ sil,
-                                                            size_t drive_stride, int n_trials, float dt, ThetaArg<COUNT> th)
+                                                            size_t drive_stride, int n_trials, float dt, ThetaArg<COUNT> th,
+                                                            C2cArg<NOISE> nz)
 {
     __shared__ RefrLds<REFR> l;
     load_tab<REFR>(l, tab);
@@ -124,7 +224,16 @@ __global__ __launch_bounds__(256) void k_trials_update_all(float* __restrict__ w
         for (int t = 0; t < n_trials; t++) {
             const Drive pa = drive_at(act + (size_t)t * drive_stride, pix, dt), ps = drive_at(sil + (size_t)t * drive_stride, pix, dt);
             float ww = w[(size_t)t * npx + pix];
-            for (int s = 0; s < n_sl; s++) ww = update_drive(ww, (m >> s) & 1u ? pa : ps);
+            if constexpr (NOISE) {
+                const unsigned br = nz.branch[(size_t)t * nz.branch_stride + pix];
+                const float sa = sigma_of(nz, br & 3u), ss = sigma_of(nz, br >> 2);
+                for (int s = 0; s < n_sl; s++) {
+                    const bool on = (m >> s) & 1u;
+                    ww = update_drive_c2c(ww, on ? pa : ps, on ? sa : ss, nz, (unsigned)pix, nz.slice0 + s, nz.array_word + (unsigned)t);
+                }
+            } else {
+                for (int s = 0; s < n_sl; s++) ww = update_drive(ww, (m >> s) & 1u ? pa : ps);
+            }
             w[(size_t)t * npx + pix] = ww;
         }
     }
@@ -132,11 +241,30 @@ __global__ __launch_bounds__(256) void k_trials_update_all(float* __restrict__ w
 
 }  // namespace
 
+extern "C" void nsof_accum_c2c_noise(uint64_t seed, int array, int trial, uint32_t pixel, int64_t slice, int64_t n_slices, float* out)
+{
+    for (int64_t i = 0; i < n_slices; i++)
+        out[i] = c2c_xi((unsigned)seed, (unsigned)(seed >> 32), pixel, (unsigned long long)slice + (unsigned long long)i,
+                        c2c_trial_word(array, trial));
+}
+
 extern "C" int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int scheme, int polarity_split, float active_v,
                                      float silent_v, const nsof_accum_params* params, int theta, const int16_t* x, const int16_t* y,
                                      const int8_t* p, const int64_t* t, const int64_t* sb, int64_t n_slices, int64_t snap_every,
                                      int memsize, double v_ds, int n_trials, int n_maps, const int* keys, const float* const* planes,
                                      const int* plane_trials, float* d_w, float* d_resistance, double* d_block_current)
+{
+    return nsof_accum_trials_c2c_dev(ctx, height, width, scheme, polarity_split, active_v, silent_v, params, theta, x, y, p, t, sb, n_slices,
+                                     snap_every, memsize, v_ds, n_trials, n_maps, keys, planes, plane_trials, d_w, d_resistance,
+                                     d_block_current, nullptr);
+}
+
+extern "C" int nsof_accum_trials_c2c_dev(nsof_ctx* ctx, int height, int width, int scheme, int polarity_split, float active_v,
+                                         float silent_v, const nsof_accum_params* params, int theta, const int16_t* x, const int16_t* y,
+                                         const int8_t* p, const int64_t* t, const int64_t* sb, int64_t n_slices, int64_t snap_every,
+                                         int memsize, double v_ds, int n_trials, int n_maps, const int* keys,
+                                         const float* const* planes, const int* plane_trials, float* d_w, float* d_resistance,
+                                         double* d_block_current, const nsof_accum_c2c* c2c)
 {
     if (!ctx) return NSOF_EINVAL;
     // ---- everything that can refuse the call, on the host, before anything is uploaded or launched (the stream's own checks
@@ -147,6 +275,13 @@ extern "C" int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int s
     if (theta < 1) return nsof_set_error(ctx, NSOF_EINVAL, "event threshold %d: at least 1 event", theta);
     if (scheme == 2 && theta != 1)
         return nsof_set_error(ctx, NSOF_EINVAL, "event threshold %d: scheme 2 has no count threshold (only 1 is accepted)", theta);
+    if (c2c) {
+        if (!(c2c->sigma_on >= 0.f) || !std::isfinite(c2c->sigma_on))
+            return nsof_set_error(ctx, NSOF_EINVAL, "cycle-to-cycle noise: sigma_on = %g is not a finite number >= 0", (double)c2c->sigma_on);
+        if (!(c2c->sigma_off >= 0.f) || !std::isfinite(c2c->sigma_off))
+            return nsof_set_error(ctx, NSOF_EINVAL, "cycle-to-cycle noise: sigma_off = %g is not a finite number >= 0", (double)c2c->sigma_off);
+    }
+    const bool noise = c2c && (c2c->sigma_on != 0.f || c2c->sigma_off != 0.f);   // both 0: the noiseless kernels
     Model mo;
     if (int rc = model_of(ctx, params, &mo)) return rc;
     PlaneSet<float> tp;
@@ -180,6 +315,7 @@ extern "C" int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int s
     nsof_dev_buf<long long> next_ok[2];
     nsof_dev_buf<unsigned> mask[2], list[2], driven[2], count;
     nsof_dev_buf<float> dplane[NSOF_ACCUM_KEY_COUNT], dact, dsil, dres;
+    nsof_dev_buf<unsigned char> dbranch;
     const size_t nev = (size_t)std::max<int64_t>(n_ev, 1);
     int rc = count.reserve(ctx, 4 * sizeof(unsigned));
     for (int i = 0; i < narr && !rc; i++) {
@@ -191,6 +327,7 @@ extern "C" int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int s
     if (!rc) rc = dact.reserve(ctx, n_drive * npx * 3 * sizeof(float));
     if (!rc && !dead) rc = dsil.reserve(ctx, n_drive * npx * 3 * sizeof(float));
     if (!rc) rc = dres.reserve(ctx, n_drive * npx * 2 * sizeof(float));
+    if (!rc && noise) rc = dbranch.reserve(ctx, n_drive * npx);
     MapSrc src;
     if (!rc) rc = upload_planes(ctx, mo, tp, npx, dplane, &src);
     if (rc) return rc;
@@ -209,7 +346,20 @@ extern "C" int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int s
     const size_t drive_stride = 3 * res.stride;
     hipLaunchKernelGGL(k_setup_maps, dim3(grid_for(npx), (unsigned)n_trials), dim3(256), 0, st, src, npx, drive_trials, v_act, silent_v,
                        dact.p, dead ? nullptr : dsil.p, reinterpret_cast<float2*>(dres.p), w_arr[0], split ? w_arr[1] : nullptr);
+    C2c nz{};
+    if (noise) {
+        nz = C2c{(unsigned)c2c->seed, (unsigned)(c2c->seed >> 32), c2c->sigma_off, c2c->sigma_on, dbranch.p, res.stride, 0, 0};
+        hipLaunchKernelGGL(k_setup_c2c, dim3(grid_for(npx), (unsigned)drive_trials), dim3(256), 0, st, src, npx, v_act, silent_v, dbranch.p);
+    }
     NSOF_HIP(ctx, hipGetLastError());
+    // f(std::true_type, the C2c of array i of the group from slice s0) with noise, f(std::false_type, NoC2c) without
+    auto with_noise = [&](int i, int64_t s0, auto&& f) {
+        if (!noise) return f(std::false_type{}, NoC2c{});
+        C2c a = nz;
+        a.slice0 = s0;
+        a.array_word = c2c_trial_word(i, 0);
+        f(std::true_type{}, a);
+    };
 
     // ---- the groups: up to 32 slices (th.spw with a count threshold), ending right after the next snapshot slice
     const int64_t every = blocks ? snap_every : 0;
@@ -243,11 +393,16 @@ extern "C" int nsof_accum_trials_dev(nsof_ctx* ctx, int height, int width, int s
                         if (gn == 0) return;
                         hipLaunchKernelGGL((k_trials_resolve<REFR, COUNT>), dim3(grid_for((size_t)gn, 1024)), dim3(256), 0, st, mask[i].p,
                                            next_ok[i].p, list[i].p, cur + i, tab, driven[i].p, nxt + i, th);
-                        hipLaunchKernelGGL(k_trials_update, dim3(grid_for((size_t)gn, 1024), trial_chunks), dim3(256), 0, st, w_arr[i],
-                                           list[i].p, cur + i, driven[i].p, dact.p, drive_stride, npx, n_trials, mo.f.dt);
+                        with_noise(i, s0, [&](auto N, auto na) {
+                            hipLaunchKernelGGL(k_trials_update<decltype(N)::value>, dim3(grid_for((size_t)gn, 1024), trial_chunks), dim3(256), 0,
+                                               st, w_arr[i], list[i].p, cur + i, driven[i].p, dact.p, drive_stride, npx, n_trials, mo.f.dt, na);
+                        });
                     } else {
-                        hipLaunchKernelGGL((k_trials_update_all<REFR, COUNT>), dim3(grid_for(npx, 8192)), dim3(256), 0, st, w_arr[i],
-                                           mask[i].p, next_ok[i].p, npx, (int)g, tab, dact.p, dsil.p, drive_stride, n_trials, mo.f.dt, th);
+                        with_noise(i, s0, [&](auto N, auto na) {
+                            hipLaunchKernelGGL((k_trials_update_all<REFR, COUNT, decltype(N)::value>), dim3(grid_for(npx, 8192)), dim3(256), 0,
+                                               st, w_arr[i], mask[i].p, next_ok[i].p, npx, (int)g, tab, dact.p, dsil.p, drive_stride, n_trials,
+                                               mo.f.dt, th, na);
+                        });
                     }
                 });
             };

@@ -42,6 +42,11 @@ class AccumParams(C.Structure):
                                   "Roff", "wini", "dt")] + [("refractory_us", _i64)]
 
 
+class AccumC2c(C.Structure):
+    """``nsof_accum_c2c`` of include/nsof.h: the seed and the two spreads of the trial run's cycle-to-cycle write noise."""
+    _fields_ = [("seed", C.c_uint64), ("sigma_on", _f), ("sigma_off", _f)]
+
+
 _ap = C.POINTER(AccumParams)
 _ll = C.POINTER(C.c_longlong)
 _fb = [_d, _i, _i, _i, _i, _d, _i]   # pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags
@@ -112,6 +117,11 @@ SIGNATURES = {
     # n_trials, n_maps, keys, planes, plane_trials, d_w, d_resistance, d_block_current
     "nsof_accum_trials_dev": (_i, [_vp, _i, _i, _i, _i, _f, _f, _ap, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _d, _i, _i,
                                    C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i), _vp, _vp, _vp]),
+    # ... the same, then c2c (NULL: no cycle-to-cycle noise)
+    "nsof_accum_trials_c2c_dev": (_i, [_vp, _i, _i, _i, _i, _f, _f, _ap, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _d, _i, _i,
+                                       C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i), _vp, _vp, _vp, C.POINTER(AccumC2c)]),
+    # seed, array, trial, pixel, slice, n_slices, out
+    "nsof_accum_c2c_noise": (None, [C.c_uint64, _i, _i, C.c_uint32, _i64, _i64, _vp]),
     "nsof_gate_stats_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "nsof_accum_destroy": (None, [_vp]),
     "nsof_accum_set_param_maps": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_vp)]),

@@ -608,9 +608,56 @@ def simulate(events, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, sav
     return out
 
 
+def c2c_arg(c2c):
+    """Cycle-to-cycle write noise as the trial run takes it: ``None`` stays ``None``; a mapping with ``sigma`` (both
+    directions) or ``sigma_on`` / ``sigma_off`` (a missing one is 0) and ``seed`` (default 0) becomes ``(seed, sigma_on,
+    sigma_off)``.  Raises ``NsofValueError`` -- nothing else is touched -- for anything but a mapping, an unknown key, ``sigma``
+    together with a directional key, a spread that is no number, negative or not finite, and a seed that is no whole
+    number in ``[0, 2**64)``."""
+    if c2c is None:
+        return None
+    try:
+        items = dict(c2c.items())
+    except AttributeError:
+        raise NsofValueError("c2c must be a mapping with the keys sigma or sigma_on / sigma_off, and seed") from None
+    unknown = [k for k in items if k not in ("sigma", "sigma_on", "sigma_off", "seed")]
+    if unknown:
+        raise NsofValueError(f"c2c: {unknown[0]!r} is not one of sigma, sigma_on, sigma_off, seed")
+    if "sigma" in items and ("sigma_on" in items or "sigma_off" in items):
+        raise NsofValueError("c2c: sigma sets both directions; give it, or sigma_on / sigma_off, not both")
+
+    def spread(name):
+        v = items.get("sigma", 0.0) if "sigma" in items else items.get(name, 0.0)
+        name = "sigma" if "sigma" in items else name
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise NsofValueError(f"c2c[{name!r}] = {v!r} is not a number")
+        if not np.isfinite(v) or v < 0:
+            raise NsofValueError(f"c2c[{name!r}] = {v!r} is not a finite number >= 0")
+        return float(v)
+    sigma_on, sigma_off = spread("sigma_on"), spread("sigma_off")
+    seed = items.get("seed", 0)
+    if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2**64:
+        raise NsofValueError(f"c2c['seed'] = {seed!r} is not a whole number in [0, 2**64)")
+    return int(seed), sigma_on, sigma_off
+
+
+def c2c_noise(seed, array, trial, pixel, first_slice, n):
+    """The standard variates of the trial run's cycle-to-cycle noise, float32 ``[n]``: xi of (``seed``, ``array`` 0 / 1,
+    ``trial``, ``pixel`` = y * W + x, slice ``first_slice + i``) -- Philox4x32-10 and a 16-byte Irwin-Hall sum, computed by the
+    library on the host (``nsof_accum_c2c_noise``): the bits the kernels use."""
+    if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2**64:
+        raise NsofValueError(f"seed = {seed!r} is not a whole number in [0, 2**64)")
+    if array not in (0, 1) or not 0 <= int(trial) < 65535 or not 0 <= int(pixel) < 2**32 or not 0 <= int(first_slice) < 2**63 or int(n) < 0:
+        raise NsofValueError(f"c2c_noise: array {array!r} (0 or 1), trial {trial!r} (0..65534), pixel {pixel!r} (< 2**32), first_slice "
+                             f"{first_slice!r} or n {n!r} out of range")
+    out = np.empty(int(n), np.float32)
+    _lib.load().nsof_accum_c2c_noise(int(seed), int(array), int(trial), int(pixel), int(first_slice), int(n), out.ctypes.data)
+    return out
+
+
 def simulate_trials_dev(events, param_maps, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, polarity="split", *,
                         sensor_size=None, params=None, dt=None, refractory_us=None, theta_events=None, snapshot_every=None,
-                        memsize=None, v_ds=1.0, ctx=None):
+                        memsize=None, v_ds=1.0, ctx=None, trials=None, c2c=None):
     """Monte-Carlo device trials of the event-driven accumulator in one run (``nsof_accum_trials_dev``): ``events`` as for
     ``simulate``, ``param_maps`` a mapping key of ``PARAMS`` -> ``[H][W]`` (shared by the trials) or ``[T][H][W]`` array read as
     float32 (``trial_param_maps_arg``; ``variability_maps(..., trials=T)`` draws them), the other arguments as for
@@ -620,14 +667,23 @@ def simulate_trials_dev(events, param_maps, version=1, slice_us=1_000, active_v=
     which ``Accumulator.step(snap_every=snapshot_every)`` snapshots (``snapshot_every=None``: ``simulate``'s cadence,
     ``max(1, nslices // 100)``), what ``block_current_dev(memsize, snapshot=s)`` gives; ``block_current[0][t]`` is a gating
     stack.  Trial ``t`` equals ``Accumulator(param_maps=planes[t])`` stepped over the same stream bit for bit; the events are
-    scattered and resolved once for all trials.  Every refusal -- arguments, shapes, the value domain of every plane -- comes
-    before any device work.  Synchronous."""
+    scattered and resolved once for all trials.  ``trials=T``: the number of trials where no plane says it (``param_maps``
+    may then be ``None`` or ``{}``: identical devices); a ``[T'][H][W]`` plane with ``T' != T`` is refused.
+    ``c2c``: cycle-to-cycle write noise (``c2c_arg``: ``dict(sigma=...)`` or ``dict(sigma_on=..., sigma_off=...)``, with
+    ``seed``) -- every update ``w + g * dt`` becomes ``w + (g * f) * dt`` with ``f = max(0, 1 + sigma * xi)``, ``sigma`` that of
+    the branch the drive took (``sigma_off``: ``V < voff``, ``sigma_on``: ``V > von``) and ``xi = c2c_noise(seed, a, t, y * W + x,
+    slice, 1)``, a pure function of its arguments: results do not depend on ``snapshot_every`` or on how many trials run.
+    ``None``, or both spreads 0, is the noiseless run bit for bit.  Every refusal -- arguments, shapes, the value domain of
+    every plane -- comes before any device work.  Synchronous."""
     if version not in (1, 2):
         raise NsofValueError("version must be 1 or 2")
     if polarity not in ("split", "magnitude"):
         raise NsofValueError("polarity must be 'split' or 'magnitude'")
     ap = accum_params(params, dt, refractory_us)
     theta = event_threshold(theta_events, version)
+    noise = c2c_arg(c2c)
+    if trials is not None and (not isinstance(trials, (int, np.integer)) or isinstance(trials, (bool, np.bool_)) or trials < 1):
+        raise NsofValueError(f"trials = {trials!r} is not a whole number >= 1")
     if isinstance(events, (str, Path)):
         x, y, p, t, H, W = load_events(Path(events))  # noqa: N806
     else:
@@ -636,7 +692,12 @@ def simulate_trials_dev(events, param_maps, version=1, slice_us=1_000, active_v=
         if x.size == 0:
             raise NsofValueError("empty event stream")
         H, W = (int(y.max()) + 1, int(x.max()) + 1) if sensor_size is None else (int(v) for v in sensor_size)  # noqa: N806
-    trials, maps = trial_param_maps_arg(param_maps, (H, W))
+    n_trials, maps = trial_param_maps_arg(param_maps, (H, W))
+    if trials is not None:
+        for k, a in maps:   # (a 2-D plane arrives here as [1][H][W]: shared by the trials)
+            if np.ndim(param_maps[k]) == 3 and a.shape[0] != trials:
+                raise NsofValueError(f"param_maps[{k!r}] holds {a.shape[0]} trials, trials = {trials}", _lib.NSOF_ESHAPE)
+        n_trials = int(trials)
     for name, v in (("snapshot_every", snapshot_every), ("memsize", memsize)):
         if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)) or v < 1):
             raise NsofValueError(f"{name} = {v!r} is not a whole number >= 1")
@@ -658,17 +719,18 @@ def simulate_trials_dev(events, param_maps, version=1, slice_us=1_000, active_v=
     ctx = ctx or default_context()
     dev = torch.device("cuda", ctx.device)
     narr = 2 if split else 1
-    out = dict(w=torch.empty((narr, trials, H, W), dtype=torch.float32, device=dev),
-               resistance=torch.empty((narr, trials, H, W), dtype=torch.float32, device=dev))
+    out = dict(w=torch.empty((narr, n_trials, H, W), dtype=torch.float32, device=dev),
+               resistance=torch.empty((narr, n_trials, H, W), dtype=torch.float32, device=dev))
     if memsize is not None:
-        out["block_current"] = torch.empty((narr, trials, (nslices - 1) // every + 1, H // int(memsize), W // int(memsize)),
+        out["block_current"] = torch.empty((narr, n_trials, (nslices - 1) // every + 1, H // int(memsize), W // int(memsize)),
                                            dtype=torch.float64, device=dev)
     torch.cuda.synchronize(dev)
-    ctx.check(ctx._lib.nsof_accum_trials_dev(ctx.ptr, H, W, version, int(split), float(active_v), float(silent_v), C.byref(ap), theta,
-                                             x16.ctypes.data, y16.ctypes.data, p8.ctypes.data, t64.ctypes.data, idx.ctypes.data,
-                                             nslices, every, 0 if memsize is None else int(memsize), float(v_ds), trials, len(maps),
-                                             *_frame_maps_c(trials, maps), dev_ptr(out["w"]), dev_ptr(out["resistance"]),
-                                             dev_ptr(out["block_current"]) if memsize is not None else None), "simulate_trials")
+    nz = None if noise is None else C.byref(_lib.AccumC2c(*noise))
+    ctx.check(ctx._lib.nsof_accum_trials_c2c_dev(ctx.ptr, H, W, version, int(split), float(active_v), float(silent_v), C.byref(ap), theta,
+                                                 x16.ctypes.data, y16.ctypes.data, p8.ctypes.data, t64.ctypes.data, idx.ctypes.data,
+                                                 nslices, every, 0 if memsize is None else int(memsize), float(v_ds), n_trials, len(maps),
+                                                 *_frame_maps_c(n_trials, maps), dev_ptr(out["w"]), dev_ptr(out["resistance"]),
+                                                 dev_ptr(out["block_current"]) if memsize is not None else None, nz), "simulate_trials")
     return out
 
 

@@ -65,7 +65,7 @@ def events_to_rois(x, y, p, t, sensor_hw, cfg, version=1, polarity="split", slic
 
 def events_variability_dev(x, y, p, t, sensor_hw, cfg, rel_sigma, trials, seed=0, version=1, polarity="split", slice_us=1000,
                            active_v=-6.0, silent_v=0.0, snapshot_every=33, params=None, dt=None, refractory_us=None,
-                           theta_events=None, max_rects=32, ctx=None):
+                           theta_events=None, max_rects=32, ctx=None, c2c=None):
     """What device-to-device variability does to the ROIs of an event stream, in HBM -- ``gating_variability_dev`` for the
     event pipeline.  The nominal array (``params``; ``None``: ``PARAMS``) is run as ``events_to_rois`` runs it (an
     ``Accumulator``, ``block_current_dev`` per snapshot); the ``trials`` arrays, whose pixels are drawn with the relative
@@ -76,13 +76,17 @@ def events_variability_dev(x, y, p, t, sensor_hw, cfg, rel_sigma, trials, seed=0
     ``gating_variability_dev``'s dict of CUDA tensors: ``nominal`` float64 [S][rows][cols], ``stacks`` float64
     [T][S][rows][cols], ``counts`` int32 [S][rows][cols] and ``p_gate`` float64 (``counts / T``), ``flips`` int32 [T][S],
     ``rects`` int32 [T][S][max_rects][4] with ``rect_counts`` int32 [T][S].  An empty ``rel_sigma``, or a spread of 0 on every
-    key, reproduces ``nominal`` in every trial bit for bit (a key whose spread is 0 keeps its scalar).  Synchronises at the end."""
+    key, reproduces ``nominal`` in every trial bit for bit (a key whose spread is 0 keeps its scalar).  ``c2c``: cycle-to-cycle
+    write noise on the trial arrays (``simulate_trials_dev``'s ``c2c``; the nominal array stays noiseless) -- the trial run is
+    then always taken, with ``trials=trials``, also when ``rel_sigma`` is empty or all zero: identical devices that differ by
+    their noise alone.  Synchronises at the end."""
     import torch
 
-    from .accumulator import simulate_trials_dev, variability_maps
+    from .accumulator import c2c_arg, simulate_trials_dev, variability_maps
     from .context import default_context
     H, W = (int(v) for v in sensor_hw)  # noqa: N806
     variability_maps(1, 1, rel_sigma, params, seed, trials=trials)   # refuses before any device work
+    c2c_arg(c2c)                                                      # ... and so does this
     ctx = ctx or default_context()
     rows, cols = H // cfg.MEMSIZE, W // cfg.MEMSIZE
     acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, params=params, dt=dt, refractory_us=refractory_us,
@@ -99,10 +103,11 @@ def events_variability_dev(x, y, p, t, sensor_hw, cfg, rel_sigma, trials, seed=0
     # the planes of the keys that do vary (the draws of the others are made all the same: a key's plane does not depend on
     # which other spreads are zero)
     maps = {k: v for k, v in variability_maps(H, W, rel_sigma, params, seed, trials=trials).items() if float(rel_sigma[k]) != 0.0}
-    if maps:
+    if maps or c2c is not None:
+        noisy = {} if c2c is None else dict(trials=int(trials), c2c=c2c)
         stacks = simulate_trials_dev((x, y, p, t), maps, version, slice_us, active_v, silent_v, polarity, sensor_size=(H, W),
                                      params=params, dt=dt, refractory_us=refractory_us, theta_events=theta_events,
-                                     snapshot_every=snapshot_every, memsize=cfg.MEMSIZE, ctx=ctx)["block_current"][0]
+                                     snapshot_every=snapshot_every, memsize=cfg.MEMSIZE, ctx=ctx, **noisy)["block_current"][0]
     else:
         stacks = nominal.unsqueeze(0).repeat(int(trials), 1, 1, 1)
     counts, flips = gating.gate_stats_dev(stacks, nominal, cfg.THRES, ctx=ctx)
