@@ -30,6 +30,64 @@ def test_contributions_match_the_mirror(nsof_lib, in_len, out_len):
     assert np.abs(wts - ref_w).max() < 1e-13
 
 
+def _kernel_constant(name):
+    """An integer `constexpr int NAME = value;` of csrc/frames_kernels.hip."""
+    import os
+    import re
+    from conftest import PKG
+    with open(os.path.join(PKG, "csrc", "frames_kernels.hip")) as f:
+        return int(re.search(rf"constexpr int {name} = (\d+);", f.read()).group(1))
+
+
+def _compress_geometry(h, w, m, n):
+    """What nsof_frames_compress_u8_dev launches for an h x w frame compressed by n, m -> (rows_first, x tiles and last x
+    tile's width of k_resize_rows, y tiles and last y tile's height of k_resize_cols, taps y, taps x), with the tile
+    sizes the issue of this coverage names (256 columns, 64 rows)."""
+    from nsof import frames
+    out_h, out_w = h // n, w // m
+    rows_first = out_h * w <= out_w * h                 # the smaller scale first, rows on a tie
+    other_rows = w if rows_first else out_w             # the axis the rows pass does not resize
+    other_cols = out_h if rows_first else h
+    taps_y = frames._contributions(h, out_h, out_h / h)[0].shape[1]
+    taps_x = frames._contributions(w, out_w, out_w / w)[0].shape[1]
+    return (rows_first, -(-other_rows // 256), (other_rows - 1) % 256 + 1, -(-other_cols // 64), (other_cols - 1) % 64 + 1,
+            taps_y, taps_x)
+
+
+# the cases that give more than one tile: (rows first, x tiles, last x tile, y tiles, last y tile, taps y, taps x)
+TILED_CASES = {
+    (130, 600, 2, 2): (True, 3, 88, 2, 1, 12, 12),
+    (65, 257, 1, 1): (True, 2, 1, 2, 1, 5, 5),
+    (64, 256, 1, 1): (True, 1, 256, 1, 64, 5, 5),
+    (200, 520, 2, 1): (False, 2, 4, 4, 8, 5, 12),
+    (150, 1030, 4, 2): (False, 2, 1, 3, 22, 12, 25),
+    (130, 2600, 10, 1): (False, 2, 4, 3, 2, 5, 60),
+    (700, 66, 1, 10): (True, 1, 66, 2, 6, 60, 5),
+}
+
+
+def test_compress_cases_cover_many_tiles_on_both_axes():
+    """The GPU test's COMPRESS_CASES, recomputed from the shapes and the mirror's tap tables: both kernels run with more
+    than one tile in either pass order, with a last tile of one element, and the LDS staging takes a second round in a
+    second row tile.  An edit of the list that loses one of these fails here, without a GPU."""
+    from test_frames_dev_gpu import COMPRESS_CASES
+    assert (_kernel_constant("ROWS_BLOCK"), _kernel_constant("COLS_ROWS"), _kernel_constant("COLS_TAPS")) == (256, 64, 32)
+    geo = {case: _compress_geometry(*case) for case in COMPRESS_CASES}
+    for case, want in TILED_CASES.items():
+        assert geo[case] == want, (case, geo[case])
+    # the pass order of the mirror is the one computed here
+    for (h, w, m, n), g in geo.items():
+        assert g[0] == ((h // n) / h <= (w // m) / w), (h, w, m, n)
+    g = list(geo.values())
+    for rows_first in (True, False):
+        assert any(c[0] == rows_first and c[1] > 1 for c in g), ("more than one x tile, rows first:", rows_first)
+        assert any(c[0] == rows_first and c[3] > 1 for c in g), ("more than one y tile, rows first:", rows_first)
+    assert any(c[1] > 1 and c[2] == 1 for c in g), "a last x tile of one column"
+    assert any(c[3] > 1 and c[4] == 1 for c in g), "a last y tile of one row"
+    assert any(c[1] == 1 and c[2] == 256 for c in g) and any(c[3] == 1 and c[4] == 64 for c in g), "one full tile"
+    assert any(c[6] > 32 and c[3] > 1 for c in g), "a columns pass with a second staging round and a second row tile"
+
+
 def test_contributions_refusals(nsof_lib):
     from nsof import _lib
     lib = _lib.load()

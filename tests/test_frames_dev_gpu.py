@@ -19,6 +19,15 @@ COMPRESS_CASES = [
     (33, 90, 45, 4),      # 8x2
     (45, 64, 8, 1),       # 45x8, scale 1 on rows
     (96, 128, 16, 16),    # 6x8
+    # more than one tile on the axis that is not resized: k_resize_rows takes 256 columns per workgroup, k_resize_cols 64
+    # rows, 32 taps per staging round (tests/test_frames_dev_cpu.py recomputes pass order, tile and tap counts of every case)
+    (130, 600, 2, 2),     # 65x300, rows first: 3 column tiles (the last 88 wide), 2 row tiles (the last 1 row)
+    (65, 257, 1, 1),      # 65x257, rows first: one element past the tile edge on both axes
+    (64, 256, 1, 1),      # 64x256: exactly one full tile each
+    (200, 520, 2, 1),     # 200x260, columns first over 4 row tiles (the last 8 rows) of the 8-bit source; rows: 2 tiles
+    (150, 1030, 4, 2),    # 75x257, columns first over 3 row tiles; rows over the float64 intermediate, 2 tiles (the last 1)
+    (130, 2600, 10, 1),   # 130x260, columns first: 60 taps = two staging rounds (32 + 28) in each of 3 row tiles
+    (700, 66, 1, 10),     # 70x66, rows first with 60 taps; columns over the intermediate with 2 row tiles
 ]
 
 

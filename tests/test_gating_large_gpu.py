@@ -155,6 +155,144 @@ def test_large_map_gating_is_deterministic(nsof_lib, ctx):
         assert gating.rects_to_host(*a, ctx=ctx) == want, conn
 
 
+# ---- more maps than one chunk ---------------------------------------------------------------------------------------------
+# nsof_roi_from_surface_dev labels maps above 64 x 64 cells a chunk of maps at a time (csrc/gating_kernels.hip).  The mirror
+# of its chunk arithmetic: tiles of CCL_TILE = 256 cells; FLAG 1 needs 4 bytes per cell and per tile of workspace; a
+# chunk is at most 2^23 tiles, and at most what the context's workspace holds, taken as at least 64 MiB.
+CCL_TILE = 256
+MAX_CHUNK_TILES = 1 << 23
+WORKSPACE_FLOOR = 64 << 20
+CHUNK_ROWS, CHUNK_COLS = 128, 130
+
+
+def _chunk_maps(rows, cols, workspace_bytes=0):
+    """Maps per chunk of a FLAG 1 call on a context whose workspace holds `workspace_bytes` (a fresh one: 0)."""
+    ncell = rows * cols
+    ntile = -(-ncell // CCL_TILE)
+    per_map = 4 * (ncell + ntile)
+    return min(max(1, MAX_CHUNK_TILES // ntile), max(1, max(workspace_bytes, WORKSPACE_FLOOR) // per_map))
+
+
+def _n_maps_for_three_chunks():
+    return 2 * _chunk_maps(CHUNK_ROWS, CHUNK_COLS) + 3
+
+
+def test_chunk_arithmetic_of_the_many_maps_case():
+    """128 x 130 cells: 16640 cells in 65 tiles, 66820 bytes per map, 1004 maps per chunk on a fresh context -- 2011 maps
+    are two full chunks and a tail of three.  (The constants are read back from the source, so that the mirror above
+    cannot fall behind them unnoticed.)"""
+    import os
+    import re
+    from conftest import PKG
+    with open(os.path.join(PKG, "csrc", "gating_kernels.hip")) as f:
+        src = f.read()
+    assert int(re.search(r"constexpr int CCL_TILE = (\d+);", src).group(1)) == CCL_TILE
+    assert "((size_t)1 << 23) / ntile" in src and "(size_t)64 << 20" in src
+    assert CHUNK_ROWS > 64 and CHUNK_COLS > 64                      # the union-find path, not one wavefront per map
+    assert 4 * (128 * 130 + 65) == 66820
+    chunk = _chunk_maps(CHUNK_ROWS, CHUNK_COLS)
+    assert chunk == min(2 ** 23 // 65, 2 ** 26 // 66820) == 1004
+    n_maps = _n_maps_for_three_chunks()
+    assert n_maps == 2011 and n_maps > 2 * chunk and n_maps - 2 * chunk == 3
+    assert _chunk_maps(CHUNK_ROWS, CHUNK_COLS, 1 << 30) >= n_maps   # a context with a 1 GiB workspace takes one pass
+
+
+def _sparse_currents(n_maps, rows, cols, pad):
+    """`n_maps` sparse maps, each from its own seed, as device currents in one buffer [n_maps][rows * cols + pad] (the pad
+    NaN) -> (buffer, ON masks).  A map has 1..20 blobs: up to three diagonal chains of 2..4 cells (one component under
+    CONNECT 8, one per cell under CONNECT 4) and small rectangles otherwise -- at most 3 * 4 + 17 components, within a
+    table of 32.  ON / OFF currents as `_currents` draws them; up to three OFF cells are 0 or negative."""
+    cells = rows * cols
+    buf = np.full((n_maps, cells + pad), np.nan)
+    ons = np.zeros((n_maps, rows, cols), bool)
+    for k in range(n_maps):
+        rng = np.random.default_rng(500_000 + k)
+        on = ons[k]
+        blobs = int(rng.integers(1, 21))
+        chains = min(blobs, int(rng.integers(0, 4)))
+        for _ in range(chains):
+            n, step = int(rng.integers(2, 5)), int(rng.choice((-1, 1)))
+            r0, c0 = int(rng.integers(0, rows - 4)), int(rng.integers(4, cols - 4))
+            on[r0 + np.arange(n), c0 + step * np.arange(n)] = True
+        for _ in range(blobs - chains):
+            r0, c0 = int(rng.integers(0, rows)), int(rng.integers(0, cols))
+            on[r0:r0 + int(rng.integers(1, 7)), c0:c0 + int(rng.integers(1, 9))] = True
+        cur = 10.0 ** np.where(on, rng.uniform(-6.6, -4.0, on.shape), rng.uniform(-12.0, -7.0, on.shape))
+        pick = rng.integers(0, cells, 3)
+        pick = pick[~on.flat[pick]]
+        cur.flat[pick[:2]] = 0.0
+        cur.flat[pick[2:]] = -1.0
+        buf[k, :cells] = cur.ravel()
+    return buf, ons
+
+
+@pytest.mark.gpu
+def test_more_maps_than_one_chunk(nsof_lib, ctx):
+    """2011 maps of 128 x 130 cells in one call on a fresh context: the chunk loop of nsof_roi_from_surface_dev runs three
+    times (1004 + 1004 + 3 maps, `_chunk_maps`), each time from offsets into the currents, the counts, the rectangle
+    table and the gray maps.  Every map's rectangles equal the host mirror's and its gray map current_to_gray, for CONNECT
+    4 and 8; the shared context (whose workspace, and so whose chunking, is whatever earlier calls left) and the fresh
+    context a second time (its workspace now reserved) give the same tables.  FLAG 2 on the same batch equals its
+    mirror too, but in a single pass: it needs no workspace, and its own chunk of 2^23 // 65 maps is out of a test's
+    reach."""
+    import torch
+    from nsof import gating
+    rows, cols, ms, pad, cap = CHUNK_ROWS, CHUNK_COLS, 3, 17, 32
+    chunk = _chunk_maps(rows, cols)
+    n_maps = _n_maps_for_three_chunks()
+    assert n_maps > 2 * chunk and rows > 64
+    h, w = rows * ms + 2, cols * ms + 5
+    buf, ons = _sparse_currents(n_maps, rows, cols, pad)
+    curs = buf[:, :rows * cols].reshape(n_maps, rows, cols)
+    assert (curs <= 0).any(axis=(1, 2)).sum() > n_maps // 2          # cells of gray 0 through the NaN path
+    for k in range(n_maps):                                           # a map read at another chunk's offset is another map
+        for other in (k + chunk, k + 2 * chunk):
+            assert other >= n_maps or not np.array_equal(ons[k], ons[other]), (k, other)
+    gray_ref = gating.current_to_gray(curs)
+    assert np.array_equal(gray_ref >= 200, ons)
+    dev = torch.device("cuda", ctx.device)
+    d = torch.from_numpy(buf).to(dev)
+    torch.cuda.synchronize()
+    stride = rows * cols + pad
+    fresh = nsof_lib.Context(0)
+    try:
+        want = {}
+        for conn in (4, 8):
+            cfg = _cfg(gating, 1, conn, ms)
+            want[conn] = [gating.roi_from_surface(c, (h, w), cfg) for c in curs]
+            n_rects = [len(v) for v in want[conn]]
+            assert 1 <= min(n_rects) and max(n_rects) <= cap, (conn, min(n_rects), max(n_rects))
+            for m0 in range(0, n_maps, chunk):                        # a count written at another map's slot shows
+                assert len(set(n_rects[m0:m0 + chunk])) >= 2, (conn, m0)
+            counts, rects, gray = gating.roi_from_surface_dev(d, n_maps, (rows, cols), (h, w), cfg, max_rects=cap, ctx=fresh,
+                                                              want_gray=True, map_stride=stride)
+            got = gating.rects_to_host(counts, rects, ctx=fresh)
+            for k in range(n_maps):
+                assert got[k] == want[conn][k], (conn, k, k // chunk, got[k][:4], want[conn][k][:4])
+            g = gray.cpu().numpy()
+            for k in range(n_maps):
+                assert np.array_equal(g[k], gray_ref[k]), (conn, k, k // chunk)
+            # FLAG 2: one pass over the whole batch
+            cfg2 = _cfg(gating, 2, conn, ms)
+            c2, r2 = gating.roi_from_surface_dev(d, n_maps, (rows, cols), (h, w), cfg2, max_rects=cap, ctx=fresh,
+                                                 map_stride=stride)
+            got2 = gating.rects_to_host(c2, r2, ctx=fresh)
+            for k in range(n_maps):
+                assert got2[k] == gating.roi_from_surface(curs[k], (h, w), cfg2), (conn, k)
+            # the shared context, then the fresh one again: counts and every stored rectangle are the same
+            c_ref, r_ref = counts.cpu().numpy(), rects.cpu().numpy()
+            stored = np.arange(cap)[None, :] < c_ref[:, None]
+            for which in (ctx, fresh):
+                c3, r3 = gating.roi_from_surface_dev(d, n_maps, (rows, cols), (h, w), cfg, max_rects=cap, ctx=which,
+                                                     map_stride=stride)
+                which.synchronize()
+                assert np.array_equal(c3.cpu().numpy(), c_ref), (conn, which is ctx)
+                assert np.array_equal(r3.cpu().numpy()[stored], r_ref[stored]), (conn, which is ctx)
+        assert sum(a != b for a, b in zip(want[4], want[8])) > n_maps // 4   # the chains: CONNECT 4 and 8 differ
+    finally:
+        fresh.close()
+
+
 def _union(rects):
     return [(min(r[0] for r in rects), min(r[1] for r in rects), max(r[2] for r in rects), max(r[3] for r in rects))] if rects else []
 

@@ -4,7 +4,8 @@ On an exact doubling the first iteration of a pyramid level reads the COARSER le
 x (1 / pyr_scale) per fetched pixel, so the level needs no flow-resample launch.  It must compute what the two kernels
 compute -- nsof_stage_flow_upsample, then nsof_stage_iterate -- bit for bit: at every window size (each MH is its own
 instance, and its parity picks the row pairing of the resampling walk), over one, two and three strips, over steps with
-clamped rows, with samples inside and outside the image, and on non-finite input.  The driver takes it only where it is
+clamped rows, with samples inside and outside the image, on non-finite input, and with a factor 1 / pyr_scale that is not
+a power of two (0.501, 0.499: the levels of 0.5, an inexact product).  The driver takes it only where it is
 that computation: the scope counters show which launches a call made.
 """
 import numpy as np
@@ -17,6 +18,10 @@ pytestmark = pytest.mark.gpu
 
 WINSIZES = list(range(2, 16))
 A = (0.5, 3, 15, 3, 5, 1.2, 0)
+# 1 / 0.5 is a power of two, so the resampled field's final product with it is exact and its place in the blend does not
+# show; 0.501 and 0.499 give a 272 x 400 frame the level sizes of 0.5 and a factor with a non-zero mantissa
+# (tests/test_float_reference.py checks both without a GPU)
+PYR_SCALES = (0.5, 0.501, 0.499)
 
 
 def _shapes(m):
@@ -68,8 +73,9 @@ def level_inputs(oracle):
     return get
 
 
-def _both_paths(ctx, torch_dev, R0, R1, coarse, h, w, winsize):
-    """-> (the resampling iteration, flow_upsample then iterate) of a batch of two pairs with the same R."""
+def _both_paths(ctx, torch_dev, R0, R1, coarse, h, w, winsize, pyr_scale):
+    """-> (the resampling iteration, flow_upsample then iterate) of a batch of two pairs with the same R; both multiply the
+    resampled field by float(1 / pyr_scale)."""
     import torch
     lib = ctx._lib
     Rp = np.stack([np.stack([_rlayout(R0), _rlayout(R1)])] * 2)
@@ -78,22 +84,25 @@ def _both_paths(ctx, torch_dev, R0, R1, coarse, h, w, winsize):
     two = torch.zeros_like(up)
     one = torch.zeros_like(up)
     torch.cuda.synchronize()
-    ctx.check(lib.nsof_stage_flow_upsample(ctx.ptr, 2, dC.data_ptr(), w // 2, h // 2, up.data_ptr(), w, h, 0.5))
+    ctx.check(lib.nsof_stage_flow_upsample(ctx.ptr, 2, dC.data_ptr(), w // 2, h // 2, up.data_ptr(), w, h, pyr_scale))
     ctx.check(lib.nsof_stage_iterate(ctx.ptr, 2, dR.data_ptr(), up.data_ptr(), w, h, winsize, two.data_ptr()))
-    ctx.check(lib.nsof_stage_iterate_x_resample(ctx.ptr, 2, dR.data_ptr(), dC.data_ptr(), w // 2, h // 2, w, h, winsize, 0.5,
-                                                one.data_ptr()))
+    ctx.check(lib.nsof_stage_iterate_x_resample(ctx.ptr, 2, dR.data_ptr(), dC.data_ptr(), w // 2, h // 2, w, h, winsize,
+                                                pyr_scale, one.data_ptr()))
     ctx.synchronize()
     return one.cpu().numpy(), two.cpu().numpy()
 
 
-@pytest.mark.parametrize("winsize", WINSIZES)
-def test_stage_resample_equals_two_kernels_and_oracle(ctx, oracle, torch_dev, level_inputs, winsize):
+@pytest.mark.parametrize("pyr_scale,winsize", [(ps, ws) for ps in PYR_SCALES for ws in WINSIZES],
+                         ids=[(f"{ws}" if ps == 0.5 else f"{ws}-ps{ps}") for ps in PYR_SCALES for ws in WINSIZES])
+def test_stage_resample_equals_two_kernels_and_oracle(ctx, oracle, torch_dev, level_inputs, pyr_scale, winsize):
+    """At pyr_scale 0.5 the factor is 2 and the product with it exact, whatever its place in the blend; at 0.501 and 0.499
+    it is not, and (t0*b0 + t1*b1) * mul, t0*(b0*mul) + t1*(b1*mul) and a contracted product give different bits."""
     m = winsize // 2
     for (h, w) in _shapes(m):
         R0, R1, coarse = level_inputs(h, w)
-        one, two = _both_paths(ctx, torch_dev, R0, R1, coarse, h, w, winsize)
+        one, two = _both_paths(ctx, torch_dev, R0, R1, coarse, h, w, winsize, pyr_scale)
         for i in range(2):
-            fine = oracle.resize_linear(coarse[i], w, h) * np.float32(2.0)
+            fine = oracle.resize_linear(coarse[i], w, h) * np.float32(1.0 / pyr_scale)
             ins, sides = _inside(fine)
             assert ins.any() and not ins.all(), (winsize, (h, w), i, "both values of `inside` must occur")
             assert all(sides), (winsize, (h, w), i, "samples must leave the image on every side", sides)
@@ -103,9 +112,10 @@ def test_stage_resample_equals_two_kernels_and_oracle(ctx, oracle, torch_dev, le
             assert np.array_equal(one[i], want), (winsize, (h, w), i, "oracle", _diff(one[i], want))
 
 
-def test_stage_resample_non_finite_input(ctx, oracle, torch_dev, level_inputs):
+@pytest.mark.parametrize("pyr_scale", PYR_SCALES)
+def test_stage_resample_non_finite_input(ctx, oracle, torch_dev, level_inputs, pyr_scale):
     """A NaN and a +inf in the coarse field, the inf in the last coarse column (whose right neighbour is the clamped
-    column itself, weight 0: 0 x inf must still be formed).  The bits of the two-kernel path."""
+    column itself, weight 0: 0 x inf must still be formed).  The bits of the two-kernel path, at every factor."""
     h, w, winsize = 20, 194, 15
     R0, R1, coarse = level_inputs(h, w)
     coarse = coarse.copy()
@@ -113,7 +123,7 @@ def test_stage_resample_non_finite_input(ctx, oracle, torch_dev, level_inputs):
     coarse[0, 6, w // 2 - 1, 1] = np.inf
     coarse[1, 9, w // 2 - 1, 0] = np.nan
     coarse[1, 0, 0, 1] = np.inf
-    one, two = _both_paths(ctx, torch_dev, R0, R1, coarse, h, w, winsize)
+    one, two = _both_paths(ctx, torch_dev, R0, R1, coarse, h, w, winsize, pyr_scale)
     assert not np.isfinite(two).all(), "the non-finite input must reach the result"
     assert np.array_equal(one.view(np.uint32), two.view(np.uint32)), _diff(one, two)
 
@@ -170,6 +180,37 @@ def test_whole_call_exact_doublings(nsof_lib, ctx, oracle, jobs):
     want = [oracle.farneback(frames[i], frames[i + 1], *A) for i in range(2)]
     assert all(np.isfinite(x).all() and np.abs(x).max() > 1.0 for x in want)
     P = nsof_lib.FarnebackParams(*A)
+    dev = torch.device("cuda", 0)
+    dp, dn = torch.from_numpy(frames[:-1].copy()).to(dev), torch.from_numpy(frames[1:].copy()).to(dev)
+    ds = torch.from_numpy(frames).to(dev)
+    fb = torch.empty((2, h, w, 2), dtype=torch.float32, device=dev)
+    fs = torch.empty_like(fb)
+    torch.cuda.synchronize()
+    _, ups, its = _counted(ctx, lambda: nsof_lib.farneback_batch(dp, dn, fb, 2, h, w, P, ctx=ctx))
+    assert (ups, its) == (0, 12), ("batch", ups, its)
+    _, ups, its = _counted(ctx, lambda: nsof_lib.farneback_sequence(ds, fs, 3, h, w, P, ctx=ctx))
+    assert (ups, its) == (0, 12), ("sequence", ups, its)
+    got_b, got_s = fb.cpu().numpy(), fs.cpu().numpy()
+    for i in range(2):
+        assert np.array_equal(got_b[i], want[i]), ("batch", i, _diff(got_b[i], want[i]))
+        assert np.array_equal(got_s[i], want[i]), ("sequence", i, _diff(got_s[i], want[i]))
+
+
+@pytest.mark.parametrize("pyr_scale,winsize", [(0.501, 15), (0.499, 15), (0.501, 4)])
+def test_whole_call_exact_doublings_at_other_scales(nsof_lib, ctx, oracle, jobs, pyr_scale, winsize):
+    """The same 2 pairs of 272 x 400 at pyr_scale 0.501 and 0.499: the levels are still 400 / 200 / 100 / 50 by 272 / 136 /
+    68 / 34, so every level takes the resampling first iteration -- with the factor float(1 / pyr_scale), which is not a
+    power of two.  No resample launch, 4 x 3 iterations, the oracle's bits, batch entry and sequence entry; window 4 runs
+    an even-MH instance (MH = 2) inside a whole call beside window 15's odd one."""
+    import torch
+    jobs(0)
+    h, w = 272, 400
+    params = (pyr_scale, 3, winsize, 3, 5, 1.2, 0)
+    assert _transitions(nsof_lib, h, w, params) == (3, 0)
+    frames = _frames(4242, 3, h, w)
+    want = [oracle.farneback(frames[i], frames[i + 1], *params) for i in range(2)]
+    assert all(np.isfinite(x).all() and np.abs(x).max() > 1.0 for x in want)
+    P = nsof_lib.FarnebackParams(*params)
     dev = torch.device("cuda", 0)
     dp, dn = torch.from_numpy(frames[:-1].copy()).to(dev), torch.from_numpy(frames[1:].copy()).to(dev)
     ds = torch.from_numpy(frames).to(dev)
