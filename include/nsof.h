@@ -578,7 +578,7 @@ int nsof_accum_block_current_dev(nsof_accum* acc, int which, int64_t snapshot, i
  * float64: imgs = HOST compressed frames [n_frames][H][W] in [0,1]; per frame pair the drive voltage comes
  * from |a-b|*256 through the piecewise map (th1, th2) and modulatefunc, followed by n_sub_steps Euler sub-steps
  * of dt/n_sub_steps.  w_out [H][W]; res_out [n_frames][H][W] (initial array, then one snapshot per pair).
- * One implementation serves all six nsof_accum_frames_f64* entries: this one is nsof_accum_frames_f64_maps with one trial and
+ * One implementation serves all eight nsof_accum_frames_f64* entries: this one is nsof_accum_frames_f64_maps with one trial and
  * no maps (upload, ONE launch, download; synchronous), so it shares that entry's launch range -- NSOF_EUNSUPPORTED beyond
  * 2^32 - 64 cells, which no real array comes near. */
 int nsof_accum_frames_f64(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
@@ -610,7 +610,8 @@ int nsof_accum_frames_f64_p_dev(nsof_ctx* ctx, const double* d_imgs, int n_frame
  * th1, th2, v_ds and n_sub_steps stay scalars.  Values are read as doubles (a float32 plane widened is exact).  The frames
  * d_imgs [n_frames][H][W] are shared by the trials; d_w [T][H][W], d_res [T][n_frames][H][W] (may be NULL), d_current
  * [T][n_frames - 1][H][W] (may be NULL), each trial laid out as nsof_accum_frames_f64_dev lays out its one.
- * This is the entry that launches; every other nsof_accum_frames_f64* entry ends here.  One kernel walks a (trial, cell)'s
+ * Every other noiseless nsof_accum_frames_f64* entry ends here, and this one in nsof_accum_frames_f64_c2c_dev (below), the
+ * entry that launches, called without noise.  One kernel walks a (trial, cell)'s
  * frame pairs whatever the source of its device model -- the fitted constants, the scalars of params, planes -- so per
  * (trial, cell) the arithmetic is the uniform call's with that cell's fields.  The two values formed on the host with the C
  * library, lambda = log(Roff / Ron) and the initial resistance Ron / exp(-lambda * (1 - wini)), are formed there per (trial,
@@ -697,8 +698,44 @@ int nsof_accum_trials_c2c_dev(nsof_ctx* ctx, int height, int width, int scheme, 
                               const float* const* planes, const int* plane_trials, float* d_w, float* d_resistance,
                               double* d_block_current, const nsof_accum_c2c* c2c);
 /* The variates of that run on the HOST (no context, no device): out[i] = xi of (seed, array, trial, pixel, slice + i) for
- * i in [0, n_slices). */
+ * i in [0, n_slices).  For the frame-driven run below: array = 0, pixel = the cell, slice = the pair index. */
 void nsof_accum_c2c_noise(uint64_t seed, int array, int trial, uint32_t pixel, int64_t slice, int64_t n_slices, float* out);
+/* C2C write noise in the FRAME-driven run, and a pair-index origin: nsof_accum_frames_f64_maps_dev's arguments, then c2c and
+ * first_pair.  The same generator and the same nsof_accum_c2c as the event path.  For trial t, cell i = r * W + c of the
+ * compressed grid as passed, and frame pair q = first_pair + f (f = 0 .. n_frames - 2):
+ *   V       the pair's drive voltage exactly as the noiseless run forms it
+ *   branch  decided against that cell's own voff / von: V < voff uses sigma_off, V > von uses sigma_on, anything else is the
+ *           dead zone: no noise and no draw
+ *   xi      nsof_accum_c2c_noise(seed, array = 0, trial = t, pixel = i, slice = q): the counter (i, q & 0xffffffff, q >> 32,
+ *           t), the key (seed & 0xffffffff, seed >> 32).  The frame path is "array 0"; its "slice" is the pair index
+ *   factor  f = max(0, u) with u = 1.0 + (double)sigma * (double)xi: sigma is the float of nsof_accum_c2c, its product with
+ *           the float32 xi is exact in double, the sum is rounded once.  A pulse may fail to switch, it never switches
+ *           backwards
+ *   update  ONE factor per pair, held for all n_sub_steps sub-steps of that pair: every sub-step is nw = w + (dwdt * f) *
+ *           dts, then the clip to [0, 1], each operation rounded on its own.  A "cycle" is one write, one frame interval;
+ *           the sub-steps are the Euler integration of that one pulse, so the result does not depend on n_sub_steps as a
+ *           noise setting
+ * sigma == 0 for the branch taken gives the noiseless bits for that pair.  c2c == NULL, or both spreads 0, is the noiseless
+ * run: the kernels nsof_accum_frames_f64_maps_dev launched before this entry existed are launched (that entry IS this one
+ * called with NULL, 0), and first_pair has no effect.  The result is a pure function of (seed, t, i, q) and the inputs: it
+ * does not depend on how many trials run, on the source of the device model, or on how a video is cut into calls -- frames
+ * [0, k] and then frames [k, n) with wini = the state after the first call (a plane) and first_pair = k give the one-shot
+ * run's w, res and current bit for bit.
+ * NSOF_EINVAL, before anything is uploaded, launched or written: a sigma that is negative or not finite (the message names
+ * the field and the value), first_pair < 0 or first_pair + n_frames beyond int64.  NSOF_EUNSUPPORTED (likewise): noise with
+ * n_trials > 65535, since the trial shares the counter word's layout with the event path.  Then everything
+ * nsof_accum_frames_f64_maps_dev refuses. */
+int nsof_accum_frames_f64_c2c_dev(nsof_ctx* ctx, const double* d_imgs, int n_frames, int height, int width, double dt,
+                                  int n_sub_steps, double th1, double th2, double v_ds, const nsof_accum_params* params,
+                                  int n_trials, int n_maps, const int* keys, const double* const* planes,
+                                  const int* plane_trials, double* d_w, double* d_res, double* d_current,
+                                  const nsof_accum_c2c* c2c, int64_t first_pair);
+/* The host twin (nsof_accum_frames_f64_maps with c2c and first_pair): the one host path -- validate, upload, the device
+ * entry, download, synchronise.  The device entry's bits. */
+int nsof_accum_frames_f64_c2c(nsof_ctx* ctx, const double* imgs, int n_frames, int height, int width, double dt,
+                              int n_sub_steps, double th1, double th2, const nsof_accum_params* params, int n_trials,
+                              int n_maps, const int* keys, const double* const* planes, const int* plane_trials,
+                              double* w_out, double* res_out, const nsof_accum_c2c* c2c, int64_t first_pair);
 /* compress_image of the same script (:111-121) for a stack of 8-bit DEVICE frames: imresize(im2double(frame), [out_h
  * out_w], 'lanczos3') of n_frames frames into d_out [n_frames][out_h][out_w] (DEVICE, dense float64).  d_frames points
  * at the first pixel of the region to compress -- a crop is a pointer offset plus width and height -- with row_stride and

@@ -113,6 +113,11 @@ SIGNATURES = {
                                             C.POINTER(_i), _vp, _vp, _vp]),
     "nsof_accum_frames_f64_maps": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _ap, _i, _i, C.POINTER(_i), C.POINTER(_vp),
                                         C.POINTER(_i), _vp, _vp]),
+    # ... the same two, then c2c (NULL: no cycle-to-cycle noise) and first_pair
+    "nsof_accum_frames_f64_c2c_dev": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _d, _ap, _i, _i, C.POINTER(_i), C.POINTER(_vp),
+                                           C.POINTER(_i), _vp, _vp, _vp, C.POINTER(AccumC2c), _i64]),
+    "nsof_accum_frames_f64_c2c": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _d, _d, _ap, _i, _i, C.POINTER(_i), C.POINTER(_vp),
+                                       C.POINTER(_i), _vp, _vp, C.POINTER(AccumC2c), _i64]),
     # ctx, H, W, scheme, split, active_v, silent_v, params, theta, x, y, p, t, bounds, n_slices, snap_every, memsize, v_ds,
     # n_trials, n_maps, keys, planes, plane_trials, d_w, d_resistance, d_block_current
     "nsof_accum_trials_dev": (_i, [_vp, _i, _i, _i, _i, _f, _f, _ap, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _d, _i, _i,

@@ -644,7 +644,9 @@ def c2c_arg(c2c):
 def c2c_noise(seed, array, trial, pixel, first_slice, n):
     """The standard variates of the trial run's cycle-to-cycle noise, float32 ``[n]``: xi of (``seed``, ``array`` 0 / 1,
     ``trial``, ``pixel`` = y * W + x, slice ``first_slice + i``) -- Philox4x32-10 and a 16-byte Irwin-Hall sum, computed by the
-    library on the host (``nsof_accum_c2c_noise``): the bits the kernels use."""
+    library on the host (``nsof_accum_c2c_noise``): the bits the kernels use.  For the frame-driven run
+    (``simulate_frames*(c2c=)``): ``array`` = 0, ``pixel`` is the cell ``r * W + c`` of the compressed grid and ``first_slice``
+    the pair index (``first_pair + f``)."""
     if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2**64:
         raise NsofValueError(f"seed = {seed!r} is not a whole number in [0, 2**64)")
     if array not in (0, 1) or not 0 <= int(trial) < 65535 or not 0 <= int(pixel) < 2**32 or not 0 <= int(first_slice) < 2**63 or int(n) < 0:
@@ -740,8 +742,36 @@ def simulate_trials(events, param_maps, version=1, slice_us=1_000, active_v=-8.0
                                                                **kw).items()}
 
 
+def _frame_noise_args(trials, c2c, first_pair):
+    """The scalar arguments the two frame-driven entries share, checked before the frames are looked at: ``(c2c_arg(c2c),
+    int(first_pair))``.  Raises ``NsofValueError``, in this order, for what ``c2c_arg`` refuses, ``trials`` other than
+    ``None`` or a whole number >= 1, and ``first_pair`` other than a whole number in ``[0, 2**63)``."""
+    noise = c2c_arg(c2c)
+    if trials is not None and (not isinstance(trials, (int, np.integer)) or isinstance(trials, (bool, np.bool_)) or trials < 1):
+        raise NsofValueError(f"trials = {trials!r} is not a whole number >= 1")
+    if isinstance(first_pair, (bool, np.bool_)) or not isinstance(first_pair, (int, np.integer)) or not 0 <= int(first_pair) < 2**63:
+        raise NsofValueError(f"first_pair = {first_pair!r} is not a whole number >= 0 (a pair index)")
+    return noise, int(first_pair)
+
+
+def _frame_trial_maps(param_maps, shape, trials, noise):
+    """``(n_trials, maps, AccumC2c or None)`` of a frame-driven call on ``shape`` = ``(H, W)`` frames: ``trials`` sets the trial
+    count where no plane does.  Raises ``NsofValueError`` -- before a context exists -- for what ``frame_param_maps_arg``
+    refuses, a ``[T'][H][W]`` plane with ``T' != trials`` (``NSOF_ESHAPE``) and noise with more than 65535 trials
+    (``NSOF_EUNSUPPORTED``: the trial shares its counter word with the array)."""
+    n_trials, maps = frame_param_maps_arg(param_maps, shape)
+    if trials is not None:
+        for k, a in maps:   # (a 2-D plane arrives here as [1][H][W]: shared by the trials)
+            if np.ndim(param_maps[k]) == 3 and a.shape[0] != trials:
+                raise NsofValueError(f"param_maps[{k!r}] holds {a.shape[0]} trials, trials = {trials}", _lib.NSOF_ESHAPE)
+        n_trials = int(trials)
+    if noise is not None and (np.float32(noise[1]) != 0 or np.float32(noise[2]) != 0) and n_trials > 65535:
+        raise NsofValueError(f"c2c with {n_trials} trials: at most 65535 trials draw distinct variates", _lib.NSOF_EUNSUPPORTED)
+    return n_trials, maps, None if noise is None else _lib.AccumC2c(*noise)
+
+
 def simulate_frames(compressed_images, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, *, ctx=None, params=None,
-                    param_maps=None):
+                    param_maps=None, trials=None, c2c=None, first_pair=0):
     """Frame-driven accumulator of /root/reference/simulation/simulationcode_v4_transistor_uav.m
     (``simulate_memristor_array``, :187-227): ``compressed_images`` float64 [n][H][W] in [0,1] (the output of the
     script's Lanczos ``compress_image``).  Returns ``(w_array, resistances_over_time)`` with the initial snapshot
@@ -751,33 +781,55 @@ def simulate_frames(compressed_images, dt=0.0005, n_sub_steps=1000, th1=0.7, th2
     cell and per trial, all ``T`` trials in one launch; the other keys keep the scalar of
     ``params``.  Both results then gain a leading trial axis -- ``w [T][H][W]``, ``resistances [T][n][H][W]`` -- also for
     ``T`` = 1 (every plane 2-D); each (trial, cell) equals the uniform run at that cell's parameters bit for bit.  Either
-    way it is one call of ``nsof_accum_frames_f64_maps``: without maps, one trial whose axis is dropped (a view)."""
+    way it is one call of ``nsof_accum_frames_f64_c2c``: without maps, one trial whose axis is dropped (a view).
+    ``trials=T``: the number of trials where no plane says it (``param_maps`` may then be ``None`` or ``{}``: identical
+    devices); a ``[T'][H][W]`` plane with ``T' != T`` is refused.  The results carry the trial axis if and only if
+    ``param_maps is not None or trials is not None``.
+    ``c2c``: cycle-to-cycle write noise (``c2c_arg``: ``dict(sigma=...)`` or ``dict(sigma_on=..., sigma_off=...)``, with
+    ``seed`` -- the event path's definition): per frame pair ``q = first_pair + f`` of trial ``t`` and cell ``i = r * W + c``
+    one factor ``f = max(0, 1 + sigma * xi)`` with ``xi = c2c_noise(seed, 0, t, i, q, 1)`` and ``sigma`` that of the branch
+    the pair's voltage takes at the cell's own thresholds (``sigma_off``: ``V < voff``, ``sigma_on``: ``V > von``, the dead
+    zone: none), held for all ``n_sub_steps`` sub-steps: ``w + (dwdt * f) * dt / n_sub_steps``.  A pure function of its
+    arguments: a trial's result does not depend on how many trials run.  ``None``, or both spreads 0, is the noiseless run
+    bit for bit; ``c2c`` alone runs trial 0 and returns today's shapes.
+    ``first_pair`` (a whole number >= 0): the index of the call's first pair -- a video can be run in chunks, frames
+    ``[0:k + 1]`` and then ``[k:]`` with ``param_maps=dict(wini=w_of_the_first_call)`` and ``first_pair=k``, and gives the
+    one-shot run's ``w`` and the matching slices of ``resistances`` bit for bit.  Without noise it has no effect.
+    Every refusal -- ``c2c``, ``trials``, ``first_pair``, then the shapes -- comes before a context is created."""
     ap = accum_params(params)
+    noise, first_pair = _frame_noise_args(trials, c2c, first_pair)
     imgs = np.ascontiguousarray(compressed_images, np.float64)
     if imgs.ndim != 3:
         raise NsofValueError("compressed_images must be [n][H][W]")
     n, H, W = imgs.shape  # noqa: N806
-    trials, maps = frame_param_maps_arg(param_maps, (H, W))
+    n_trials, maps, nz = _frame_trial_maps(param_maps, (H, W), trials, noise)
     ctx = ctx or default_context()
-    w = np.empty((trials, H, W), np.float64)
-    res = np.empty((trials, n, H, W), np.float64)
-    ctx.check(ctx._lib.nsof_accum_frames_f64_maps(ctx.ptr, imgs.ctypes.data, n, H, W, float(dt), int(n_sub_steps), float(th1),
-                                                  float(th2), C.byref(ap), trials, len(maps), *_frame_maps_c(trials, maps),
-                                                  w.ctypes.data, res.ctypes.data), "simulate_frames")
-    return (w, res) if param_maps is not None else (w[0], res[0])
+    w = np.empty((n_trials, H, W), np.float64)
+    res = np.empty((n_trials, n, H, W), np.float64)
+    ctx.check(ctx._lib.nsof_accum_frames_f64_c2c(ctx.ptr, imgs.ctypes.data, n, H, W, float(dt), int(n_sub_steps), float(th1),
+                                                 float(th2), C.byref(ap), n_trials, len(maps), *_frame_maps_c(n_trials, maps),
+                                                 w.ctypes.data, res.ctypes.data, None if nz is None else C.byref(nz), first_pair),
+              "simulate_frames")
+    return (w, res) if param_maps is not None or trials is not None else (w[0], res[0])
 
 
 def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.5, v_ds=1.0, *, ctx=None, params=None,
-                        param_maps=None):
+                        param_maps=None, trials=None, c2c=None, first_pair=0):
     """``simulate_frames`` on a float64 CUDA tensor [n][H][W] (``frames.process_images_dev``'s output) in one launch
-    (``nsof_accum_frames_f64_maps_dev``, with or without maps): returns ``(w [H][W], resistances [n][H][W], current [n-1][H][W])`` as float64 CUDA
+    (``nsof_accum_frames_f64_c2c_dev``, with or without maps or noise): returns ``(w [H][W], resistances [n][H][W], current [n-1][H][W])`` as float64 CUDA
     tensors -- ``w`` and ``resistances`` equal ``simulate_frames`` bit for bit, ``current[f] = v_ds / resistances[f + 1]``
     is the device current after pair (f, f+1), the layout ``gating.roi_from_surface_dev`` reads.  Nothing is copied;
     asynchronous on the context's stream.  ``params`` as for ``simulate_frames``.
     ``param_maps`` as for ``simulate_frames`` (host arrays; they are uploaded through a buffer of the context): every
     result gains a leading trial axis -- ``w [T][H][W]``, ``resistances [T][n][H][W]``, ``current [T][n-1][H][W]`` -- and
-    ``current[t]`` is a gating stack of its own."""
+    ``current[t]`` is a gating stack of its own.
+    ``trials``, ``c2c`` and ``first_pair`` as for ``simulate_frames``: the trial count where no plane says it, cycle-to-cycle
+    write noise (one factor per frame pair) and the index of the call's first pair; the trial axis is there if and only if
+    ``param_maps is not None or trials is not None``.  A chunked run -- frames ``[0:k + 1]``, then ``[k:]`` with
+    ``param_maps=dict(wini=w.cpu().numpy())`` and ``first_pair=k`` -- equals the one-shot run in ``w``, ``resistances[..., k + 1:, :, :]``
+    and ``current[..., k:, :, :]`` bit for bit."""
     ap = accum_params(params)
+    noise, first_pair = _frame_noise_args(trials, c2c, first_pair)
     torch = _torch()
     if not isinstance(compressed, torch.Tensor) or not compressed.is_cuda:
         raise NsofValueError("simulate_frames_dev: a CUDA tensor expected", _lib.NSOF_EINVAL)
@@ -787,16 +839,17 @@ def simulate_frames_dev(compressed, dt=0.0005, n_sub_steps=1000, th1=0.7, th2=1.
         raise NsofValueError("simulate_frames_dev: contiguous [n][H][W] frames expected", _lib.NSOF_ESHAPE)
     n, H, W = (int(v) for v in compressed.shape)  # noqa: N806
     dev = compressed.device
-    trials, maps = frame_param_maps_arg(param_maps, (H, W))
+    n_trials, maps, nz = _frame_trial_maps(param_maps, (H, W), trials, noise)
     ctx = ctx or default_context()
-    w = torch.empty((trials, H, W), dtype=torch.float64, device=dev)
-    res = torch.empty((trials, n, H, W), dtype=torch.float64, device=dev)
-    cur = torch.empty((trials, n - 1, H, W), dtype=torch.float64, device=dev)
-    ctx.check(ctx._lib.nsof_accum_frames_f64_maps_dev(ctx.ptr, dev_ptr(compressed), n, H, W, float(dt), int(n_sub_steps),
-                                                      float(th1), float(th2), float(v_ds), C.byref(ap), trials, len(maps),
-                                                      *_frame_maps_c(trials, maps), dev_ptr(w), dev_ptr(res),
-                                                      dev_ptr(cur) if n > 1 else None), "simulate_frames_dev")
-    return (w, res, cur) if param_maps is not None else (w[0], res[0], cur[0])
+    w = torch.empty((n_trials, H, W), dtype=torch.float64, device=dev)
+    res = torch.empty((n_trials, n, H, W), dtype=torch.float64, device=dev)
+    cur = torch.empty((n_trials, n - 1, H, W), dtype=torch.float64, device=dev)
+    ctx.check(ctx._lib.nsof_accum_frames_f64_c2c_dev(ctx.ptr, dev_ptr(compressed), n, H, W, float(dt), int(n_sub_steps),
+                                                     float(th1), float(th2), float(v_ds), C.byref(ap), n_trials, len(maps),
+                                                     *_frame_maps_c(n_trials, maps), dev_ptr(w), dev_ptr(res),
+                                                     dev_ptr(cur) if n > 1 else None, None if nz is None else C.byref(nz),
+                                                     first_pair), "simulate_frames_dev")
+    return (w, res, cur) if param_maps is not None or trials is not None else (w[0], res[0], cur[0])
 
 
 def _save_outputs(prefix, out, version, slice_us, polarity, h5_path, params=None, dt=None, refractory_us=None,

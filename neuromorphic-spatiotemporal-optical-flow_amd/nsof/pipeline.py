@@ -583,7 +583,9 @@ def gating_stack_from_frames_dev(frames_bgr, cfg, m=None, n=None, region=None, c
     ``th1``, ``th2``, ``v_ds``, ``params``, ``param_maps`` on).  Returns the device currents, float64 CUDA tensor
     [k-1][rows][cols]: slice f is the array after pair (f, f+1) -- what ``prediction_sequence_dev`` /
     ``segmentation_sequence_dev`` take as ``mem_state`` without a copy.  With ``param_maps=`` (a device per cell and per
-    trial, ``simulate_frames_dev``) the result is [T][k-1][rows][cols], one such stack per trial.  Equal to
+    trial, ``simulate_frames_dev``) or ``trials=`` the result is [T][k-1][rows][cols], one such stack per trial.  ``sim`` also
+    passes ``trials`` (the trial count where no plane says it), ``c2c`` (cycle-to-cycle write noise, one factor per frame
+    pair) and ``first_pair`` (the index of the first pair, for a video run in chunks through ``wini``) on.  Without noise equal to
     ``frames.process_images`` -> ``simulate_frames`` -> ``v_ds / resistances[1:]`` on the host gray frames, bit for bit.
     Nothing visits the host; synchronises at the end (the intermediates are released)."""
     from .accumulator import simulate_frames_dev
@@ -596,7 +598,7 @@ def gating_stack_from_frames_dev(frames_bgr, cfg, m=None, n=None, region=None, c
 
 
 def gating_variability_dev(frames_bgr, cfg, rel_sigma, trials, seed=0, params=None, max_rects=32, m=None, n=None, region=None,
-                           ctx=None, **sim):
+                           ctx=None, c2c=None, **sim):
     """What device-to-device variability does to the gate of a sequence, in HBM: the frames are compressed once
     (``gating_stack_from_frames_dev``'s front half), the array is run for the nominal device ``params`` (``None``:
     ``PARAMS``) and for ``trials`` arrays whose cells are drawn with the relative spreads ``rel_sigma`` (``{key: sigma}``;
@@ -608,23 +610,30 @@ def gating_variability_dev(frames_bgr, cfg, rel_sigma, trials, seed=0, params=No
     [k-1][rows][cols] and ``p_gate`` float64 (``counts / T``: the gate probability per cell), ``flips`` int32 [T][k-1]
     (cells of trial t's map f gated differently from the nominal's), ``rects`` int32 [T][k-1][max_rects][4] with
     ``rect_counts`` int32 [T][k-1] (the tables of ``roi_from_surface_dev`` per map).  A spread of 0 on every key reproduces
-    ``nominal`` in every trial bit for bit.  Synchronises at the end."""
+    ``nominal`` in every trial bit for bit.  ``c2c``: cycle-to-cycle write noise on the trial arrays (``simulate_frames_dev``'s
+    ``c2c``: one factor per frame pair; the nominal array stays noiseless) -- the trial run is then always taken, with
+    ``trials=trials``, also when ``rel_sigma`` is empty: identical devices that differ by their noise alone.  Synchronises at
+    the end."""
     import numpy as np
     import torch
 
-    from .accumulator import simulate_frames_dev, variability_maps
+    from .accumulator import c2c_arg, simulate_frames_dev, variability_maps
     from .context import default_context
     maps = variability_maps(1, 1, rel_sigma, params, seed, trials=trials, dtype=np.float64)   # refuses before any device work
+    c2c_arg(c2c)                                                                              # ... and so does this
     ctx = ctx or default_context()
     grids = _compressed_grids_dev(frames_bgr, cfg, m, n, region, ctx, "gating_variability_dev")
     k, rows, cols = (int(v) for v in grids.shape)
     H, W = (int(v) for v in frames_bgr.shape[1:3])  # noqa: N806
     nominal = simulate_frames_dev(grids, ctx=ctx, params=params, **sim)[2]
-    if maps:
-        maps = variability_maps(rows, cols, rel_sigma, params, seed, trials=trials, dtype=np.float64)
-        stacks = simulate_frames_dev(grids, ctx=ctx, params=params, param_maps=maps, **sim)[2]
+    if maps or c2c is not None:
+        maps = variability_maps(rows, cols, rel_sigma, params, seed, trials=trials, dtype=np.float64) if maps else None
+        noisy = {} if c2c is None else dict(trials=int(trials), c2c=c2c)
+        stacks = simulate_frames_dev(grids, ctx=ctx, params=params, param_maps=maps, **noisy, **sim)[2]
     else:
+        ctx.synchronize()                                # torch copies on its own stream: the nominal run must have finished
         stacks = nominal.unsqueeze(0).repeat(int(trials), 1, 1, 1)
+        torch.cuda.synchronize(nominal.device)           # ... and the copy, before the context's stream reads it
     counts, flips = gating.gate_stats_dev(stacks, nominal, cfg.THRES, ctx=ctx)
     rect_counts, rects = gating.roi_from_surface_dev(stacks, int(trials) * (k - 1), (rows, cols), (H, W), cfg, max_rects=max_rects,
                                                      ctx=ctx)
