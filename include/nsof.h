@@ -700,6 +700,63 @@ int nsof_accum_trials_c2c_dev(nsof_ctx* ctx, int height, int width, int scheme, 
 /* The variates of that run on the HOST (no context, no device): out[i] = xi of (seed, array, trial, pixel, slice + i) for
  * i in [0, n_slices).  For the frame-driven run below: array = 0, pixel = the cell, slice = the pair index. */
 void nsof_accum_c2c_noise(uint64_t seed, int array, int trial, uint32_t pixel, int64_t slice, int64_t n_slices, float* out);
+/* The trial run as an OBJECT: the T states, the per-array refractory maps and the slice counter stay in HBM and the stream is
+ * handed over chunk by chunk -- nsof_accum_trials_dev without its limit on the length of a recording, with read-outs between
+ * chunks and with a drive voltage per trial.  A run cut into chunks at ANY slices equals the one-shot run bit for bit: the
+ * groups are cut and the snapshots timed by the object's absolute slice counter, scheme 2's next_ok carries over, and a
+ * noise variate is a function of the absolute slice index.  (nsof_accum_trials_dev / _c2c_dev are create, one step, the
+ * read-outs and destroy over this implementation.)
+ * nsof_accum_trials_create: geometry, scheme, polarity_split, params, theta, n_trials, the plane list and c2c exactly as
+ * nsof_accum_trials_c2c_dev takes them (c2c may be NULL).  active_v [n_active] and silent_v [n_silent] are HOST arrays, each
+ * of 1 value (all trials) or n_trials values (trial t drives with active_v[t], leaks with silent_v[t]; scheme 2's active
+ * drive is the float32 sum silent_v[t] + active_v[t]).  With a voltage per trial every trial has its own drive planes, and
+ * the touched-pixels form runs only if silent_v[t] lies in the dead zone of every pixel of trial t for EVERY t -- one leaking
+ * trial puts all trials on the every-pixel form (same bits, trial by trial).  theta stays one value.  snap_every, memsize and
+ * v_ds are fixed for the object's life; memsize == 0: no block currents (snap_every and v_ds are then not read).
+ * NSOF_EINVAL / NSOF_EUNSUPPORTED before anything is allocated, uploaded or launched: everything nsof_accum_trials_c2c_dev
+ * refuses that does not concern the stream, n_active / n_silent other than 1 or n_trials (or a NULL array), and a voltage
+ * that is not finite, the message naming the trial. */
+typedef struct nsof_accum_trials nsof_accum_trials;
+int nsof_accum_trials_create(nsof_ctx* ctx, int height, int width, int scheme, int polarity_split,
+                             const nsof_accum_params* params, int theta, int n_trials, int n_maps, const int* keys,
+                             const float* const* planes, const int* plane_trials, const nsof_accum_c2c* c2c,
+                             const float* active_v, int n_active, const float* silent_v, int n_silent, int64_t snap_every,
+                             int memsize, double v_ds, nsof_accum_trials** out);
+void nsof_accum_trials_destroy(nsof_accum_trials* a);
+/* The snapshot slices -- absolute indices 0, k, 2k, ... -- among the n_slices slices from `counter` on (pure host arithmetic),
+ * and the same for the object's own counter and cadence (0 without block currents): S_chunk of the next step. */
+int64_t nsof_accum_snaps_between(int64_t counter, int64_t n_slices, int64_t snap_every);
+int64_t nsof_accum_trials_snaps_in(const nsof_accum_trials* a, int64_t n_slices);
+/* Advance over n_slices slices of HOST event arrays (as nsof_accum_step_events takes them; only this chunk is staged, and
+ * the arrays are not retained: the call returns once the chunk has run).  d_block_current (DEVICE, may be NULL where
+ * S_chunk = nsof_accum_trials_snaps_in(a, n_slices) is 0) receives float64 [A][T][S_chunk][rows][cols], the block maxima after
+ * the snapshot slices inside the chunk; *n_snaps (may be NULL) = S_chunk.  n_slices == 0 does nothing.  A refused step --
+ * NSOF_EINVAL for bad bounds, a NULL array or an event outside the sensor, NSOF_EUNSUPPORTED for 2^31 events or more in ONE
+ * step -- launches nothing and leaves the object as it was. */
+int nsof_accum_trials_step(nsof_accum_trials* a, const int16_t* x, const int16_t* y, const int8_t* p, const int64_t* t,
+                           const int64_t* slice_bounds, int64_t n_slices, double* d_block_current, int64_t* n_snaps);
+/* Read-outs to DEVICE memory, asynchronous on the context's stream: the states and their resistances, float32 [A][T][H][W];
+ * the block maxima of v_ds / R of the CURRENT states, float64 [A][T][rows][cols] (needs memsize). */
+int nsof_accum_trials_w_dev(nsof_accum_trials* a, float* d_out);
+int nsof_accum_trials_resistance_dev(nsof_accum_trials* a, float* d_out);
+int nsof_accum_trials_block_current_dev(nsof_accum_trials* a, double* d_out);
+/* The surface of array `which` of every trial as frames [T][H][W] (mode as nsof_accum_surface_u8_dev: 0 current, 1 state):
+ * trial t's frame starts trial_stride after trial t-1's, its rows are row_stride apart (u8: both in bytes = pixels, row_stride
+ * >= W; f32: both in BYTES, multiples of 4, row_stride >= 4 * W; trial_stride >= H * row_stride).  Frame t holds, bit for bit,
+ * what nsof_accum_surface_u8_dev / _f32_dev write for an accumulator with trial t's planes in the same state.  One launch;
+ * asynchronous on the context's stream. */
+int nsof_accum_trials_surface_u8_dev(nsof_accum_trials* a, int which, int mode, uint8_t* d_out, ptrdiff_t row_stride,
+                                     ptrdiff_t trial_stride);
+int nsof_accum_trials_surface_f32_dev(nsof_accum_trials* a, int which, int mode, float* d_out, ptrdiff_t row_stride_bytes,
+                                      ptrdiff_t trial_stride_bytes);
+/* Checkpoint / resume through the HOST: w float32 [A][T][H][W], next_ok int64 [A][H][W] (one plane per array, as the kernels
+ * hold it; zeros for scheme 1) and the slice counter.  Any output of read_state may be NULL.  write_state: n_w_planes must be
+ * A * T and, where next_ok_in is given, n_next_ok_planes A (NSOF_EINVAL otherwise, nothing written); next_ok_in == NULL writes
+ * zeros (n_next_ok_planes is not read).  Both synchronise.  reset: back to the wini planes, next_ok zero, counter 0. */
+int nsof_accum_trials_read_state(nsof_accum_trials* a, float* w_out, int64_t* next_ok_out, int64_t* slice_counter);
+int nsof_accum_trials_write_state(nsof_accum_trials* a, const float* w_in, int64_t n_w_planes, const int64_t* next_ok_in,
+                                  int64_t n_next_ok_planes, int64_t slice_counter);
+int nsof_accum_trials_reset(nsof_accum_trials* a);
 /* C2C write noise in the FRAME-driven run, and a pair-index origin: nsof_accum_frames_f64_maps_dev's arguments, then c2c and
  * first_pair.  The same generator and the same nsof_accum_c2c as the event path.  For trial t, cell i = r * W + c of the
  * compressed grid as passed, and frame pair q = first_pair + f (f = 0 .. n_frames - 2):

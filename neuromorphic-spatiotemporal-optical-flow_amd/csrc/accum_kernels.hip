@@ -65,24 +65,7 @@ __global__ __launch_bounds__(256) void k_fill(float* __restrict__ p, size_t n, f
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = v;
 }
 
-// The surface value of one pixel before its 8-bit truncation: g in [0, 255], double (modes: see k_surface_gray).
-__device__ __forceinline__ double surface_gray_value(float ww, const DevF& p, int mode)
-{
-    double g;
-    if (mode == 0) {
-        const double r = (double)resistance_one(ww, p);
-        g = -3366.0 / log10(1.0 / r) - 306.0;
-    } else {
-        g = (double)(ww * 255.0f);
-    }
-    g = g < 0.0 ? 0.0 : (g > 255.0 ? 255.0 : g);   // NaN (I == 1 A exactly, R == 1 Ohm) does not occur for the fitted R in [Ron, Roff]
-    return g;
-}
-// The surface as an 8-bit frame, one pixel.
-__device__ __forceinline__ uint8_t surface_gray_one(float ww, const DevF& p, int mode)
-{
-    return (uint8_t)surface_gray_value(ww, p, mode);
-}
+// (surface_gray_value / surface_gray_one: accum_update.h, shared with the trial run's surface kernel)
 // Where the fused dense update leaves the frame of the state it has just written (out == nullptr: nowhere).
 struct SurfOut {
     uint8_t* out;
@@ -634,7 +617,7 @@ extern "C" int nsof_accum_set_param_maps(nsof_accum* a, int n_maps, const int* k
     const float v_act = a->scheme == 1 ? a->active_v : a->silent_v + a->active_v;
     // (one trial; the state is nsof_accum_reset's, below)
     hipLaunchKernelGGL(k_setup_maps, dim3(grid_for(npx)), dim3(256), 0, ctx->stream, src, npx, 1, v_act, a->silent_v, nact.p, nsil.p,
-                       reinterpret_cast<float2*>(nres.p), (float*)nullptr, (float*)nullptr);
+                       reinterpret_cast<float2*>(nres.p), (float*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
     NSOF_HIP(ctx, hipGetLastError());
     NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the caller's planes are not retained; the old ones are free to go
     for (int k = 0; k < NSOF_ACCUM_KEY_COUNT; k++) a->map_plane[k].swap(np_[k]);

@@ -218,5 +218,24 @@ inline bool silent_in_every_dead_zone(const PlaneSet<float>& ps, const DevF& f, 
     return every_value(NSOF_ACCUM_KEY_VOFF, f.voff, [&](float v) { return !(silent_v < v); }) &&
            every_value(NSOF_ACCUM_KEY_VON, f.von, [&](float v) { return !(silent_v > v); });
 }
+// The same rule with a silent voltage per trial: silent_v[t] inside the dead zone of every pixel of trial t, for EVERY t (a
+// plane shared by the trials is trial t's).
+inline bool silent_in_every_dead_zone(const PlaneSet<float>& ps, const DevF& f, const float* silent_v, int n_trials, size_t npx)
+{
+    for (size_t t = 0; t < (size_t)n_trials; t++) {
+        const float sv = silent_v[t];
+        auto every_value = [&](int k, float scalar, auto&& ok) {
+            if (!ps.plane[k]) return ok(scalar);
+            const float* q = ps.plane[k] + (ps.trials[k] == 1 ? 0 : t) * npx;
+            for (size_t i = 0; i < npx; i++)
+                if (!ok(q[i])) return false;
+            return true;
+        };
+        if (!every_value(NSOF_ACCUM_KEY_VOFF, f.voff, [&](float v) { return !(sv < v); }) ||
+            !every_value(NSOF_ACCUM_KEY_VON, f.von, [&](float v) { return !(sv > v); }))
+            return false;
+    }
+    return true;
+}
 
 }  // namespace

@@ -1,6 +1,6 @@
 // The float32 event-driven accumulator: what accum_kernels.hip (one array) and accum_trials.hip (T Monte-Carlo trials of one
 // stream) share.  Device code: the update arithmetic (update_one, Drive, drive_of, update_drive, replay_driven,
-// resistance_one), the scatter of a group of slices (k_scatter and its marks), scheme 1's count threshold (Theta,
+// resistance_one, surface_gray_value), the scatter of a group of slices (k_scatter and its marks), scheme 1's count threshold (Theta,
 // driven_bits), scheme 2's refractory walk (RefrTab, refractory_walk), the set-up pass of per-pixel devices (k_setup_maps)
 // and the resistance read-outs (k_resistance, k_block_min_resistance).  Host code: the staged stream (StagedStream) and the
 // walk over its groups (group_len, snapshot_due, refr_tab_of, ListCounts).  Everything sits in an unnamed namespace, as in
@@ -136,6 +136,25 @@ __device__ __forceinline__ float resistance_one(float w, const DevF& p)
 {
     const float e = (float)exp((double)(p.neg_lam * (1.0f - w)));
     return (float)((double)p.ron / (double)e);
+}
+
+// The surface value of one pixel before its 8-bit truncation: g in [0, 255], double (modes: see k_surface_gray).
+__device__ __forceinline__ double surface_gray_value(float ww, const DevF& p, int mode)
+{
+    double g;
+    if (mode == 0) {
+        const double r = (double)resistance_one(ww, p);
+        g = -3366.0 / log10(1.0 / r) - 306.0;
+    } else {
+        g = (double)(ww * 255.0f);
+    }
+    g = g < 0.0 ? 0.0 : (g > 255.0 ? 255.0 : g);   // NaN (I == 1 A exactly, R == 1 Ohm) does not occur for the fitted R in [Ron, Roff]
+    return g;
+}
+// The surface as an 8-bit frame, one pixel.
+__device__ __forceinline__ uint8_t surface_gray_one(float ww, const DevF& p, int mode)
+{
+    return (uint8_t)surface_gray_value(ww, p, mode);
 }
 
 // A pixel's drive and resistance constants from the planes k_setup_maps wrote.
@@ -337,11 +356,17 @@ struct MapSrc {
 //   drive_trials  the trials that get drives and a resistance pair: all, or 1 when no plane but wini has a trial axis
 //   sil           nullptr where no kernel reads the silent drive (the trial run's touched-pixels form)
 //   w0, w1        the initial state (the trial's wini) of every array; nullptr where nsof_accum_reset sets it (one array)
+//   v_act_t, v_sil_t  the two voltages per trial ([drive_trials] each, both or neither); nullptr: v_act / v_sil for all
 __global__ __launch_bounds__(256) void k_setup_maps(MapSrc src, size_t n, int drive_trials, float v_act, float v_sil,
                                                      float* __restrict__ act, float* __restrict__ sil, float2* __restrict__ res,
-                                                     float* __restrict__ w0, float* __restrict__ w1)
+                                                     float* __restrict__ w0, float* __restrict__ w1,
+                                                     const float* __restrict__ v_act_t, const float* __restrict__ v_sil_t)
 {
     const size_t t = blockIdx.y;
+    if (v_act_t && t < (size_t)drive_trials) {
+        v_act = v_act_t[t];
+        v_sil = v_sil_t[t];
+    }
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         auto get = [&](int k) { return src.plane[k] ? src.plane[k][t * src.stride[k] + i] : src.scalar[k]; };
         const size_t e = t * n + i;
@@ -467,13 +492,11 @@ struct StagedStream {
     nsof_dev_buf<short> dx, dy;
     nsof_dev_buf<signed char> dp;
     nsof_dev_buf<long long> dbounds;
-    // Checks and uploads on ctx->stream (bounds sb index the caller's arrays, which are not retained: synchronise before
-    // they go).
-    int stage(nsof_ctx* ctx, int W, int H, int scheme, int split, long long refractory_us, const int16_t* x, const int16_t* y,
-              const int8_t* p, const int64_t* t, const int64_t* sb, int64_t n_slices)
+    // Everything about a stream that refuses it, on the host: nothing is allocated, uploaded or launched.
+    static int check(nsof_ctx* ctx, int W, int H, int scheme, int split, const int16_t* x, const int16_t* y, const int8_t* p,
+                     const int64_t* t, const int64_t* sb, int64_t n_slices)
     {
         if (n_slices < 0 || !sb) return nsof_set_error(ctx, NSOF_EINVAL, "bad slice bounds");
-        NSOF_HIP(ctx, hipSetDevice(ctx->device));
         const int64_t e0 = sb[0], e1 = sb[n_slices], n_ev = e1 - e0;
         if (n_ev < 0) return nsof_set_error(ctx, NSOF_EINVAL, "slice bounds not monotone");
         if (n_ev > 0 && (!x || !y || !t || (scheme == 2 && split && !p))) return nsof_set_error(ctx, NSOF_EINVAL, "null event array");
@@ -484,6 +507,17 @@ struct StagedStream {
             if ((unsigned)x[e] >= (unsigned)W || (unsigned)y[e] >= (unsigned)H)
                 return nsof_set_error(ctx, NSOF_EINVAL, "event %lld at (%d,%d) outside the %dx%d sensor", (long long)e, (int)x[e],
                                       (int)y[e], W, H);
+        return NSOF_OK;
+    }
+    // Checks and uploads on ctx->stream (bounds sb index the caller's arrays, which are not retained: synchronise before
+    // they go).  checked: the caller has run check() on these very arguments.
+    int stage(nsof_ctx* ctx, int W, int H, int scheme, int split, long long refractory_us, const int16_t* x, const int16_t* y,
+              const int8_t* p, const int64_t* t, const int64_t* sb, int64_t n_slices, bool checked = false)
+    {
+        if (!checked)
+            if (int rc = check(ctx, W, H, scheme, split, x, y, p, t, sb, n_slices)) return rc;
+        NSOF_HIP(ctx, hipSetDevice(ctx->device));
+        const int64_t e0 = sb[0], e1 = sb[n_slices], n_ev = e1 - e0;
         int rc;
         const size_t cap = event_cap(n_ev);
         if ((rc = dx.reserve(ctx, (size_t)n_ev * 2, cap * 2)) || (rc = dy.reserve(ctx, (size_t)n_ev * 2, cap * 2)) ||

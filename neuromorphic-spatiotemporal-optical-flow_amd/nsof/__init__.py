@@ -20,7 +20,7 @@ from .farneback import (OPTFLOW_FARNEBACK_GAUSSIAN, OPTFLOW_USE_INITIAL_FLOW, Fa
                         farneback_roi_sequence_f32_dev,
                         farneback_sequence, install, level_size,
                         pinned_empty, uninstall)
-from .accumulator import (PARAMS, DT, THETA_EVENTS, REFRACTORY_US, Accumulator, accum_params, bincount_2d,  # noqa: F401
+from .accumulator import (PARAMS, DT, THETA_EVENTS, REFRACTORY_US, Accumulator, TrialAccumulator, accum_params, bincount_2d,  # noqa: F401
                           c2c_arg, c2c_noise, frame_param_maps_arg, generate_synthetic_events, load_events, resistance_exp, simulate, simulate_frames, simulate_frames_dev,
                           simulate_trials, simulate_trials_dev, slice_indices, trial_param_maps_arg, update_state, variability_maps)
 

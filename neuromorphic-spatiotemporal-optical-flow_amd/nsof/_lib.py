@@ -127,6 +127,25 @@ SIGNATURES = {
                                        C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i), _vp, _vp, _vp, C.POINTER(AccumC2c)]),
     # seed, array, trial, pixel, slice, n_slices, out
     "nsof_accum_c2c_noise": (None, [C.c_uint64, _i, _i, C.c_uint32, _i64, _i64, _vp]),
+    # the trial run as an object.  create: ctx, H, W, scheme, split, params, theta, n_trials, n_maps, keys, planes, plane_trials,
+    # c2c, active_v, n_active, silent_v, n_silent, snap_every, memsize, v_ds, out
+    "nsof_accum_trials_create": (_i, [_vp, _i, _i, _i, _i, _ap, _i, _i, _i, C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i),
+                                      C.POINTER(AccumC2c), _vp, _i, _vp, _i, _i64, _i, _d, C.POINTER(_vp)]),
+    "nsof_accum_trials_destroy": (None, [_vp]),
+    "nsof_accum_snaps_between": (_i64, [_i64, _i64, _i64]),
+    "nsof_accum_trials_snaps_in": (_i64, [_vp, _i64]),
+    # a, x, y, p, t, bounds, n_slices, d_block_current, n_snaps
+    "nsof_accum_trials_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, C.POINTER(_i64)]),
+    "nsof_accum_trials_w_dev": (_i, [_vp, _vp]),
+    "nsof_accum_trials_resistance_dev": (_i, [_vp, _vp]),
+    "nsof_accum_trials_block_current_dev": (_i, [_vp, _vp]),
+    # a, which, mode, d_out, row_stride, trial_stride
+    "nsof_accum_trials_surface_u8_dev": (_i, [_vp, _i, _i, _vp, _pd, _pd]),
+    "nsof_accum_trials_surface_f32_dev": (_i, [_vp, _i, _i, _vp, _pd, _pd]),
+    "nsof_accum_trials_read_state": (_i, [_vp, _vp, _vp, C.POINTER(_i64)]),
+    # a, w, n_w_planes, next_ok, n_next_ok_planes, slice_counter
+    "nsof_accum_trials_write_state": (_i, [_vp, _vp, _i64, _vp, _i64, _i64]),
+    "nsof_accum_trials_reset": (_i, [_vp]),
     "nsof_gate_stats_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "nsof_accum_destroy": (None, [_vp]),
     "nsof_accum_set_param_maps": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_vp)]),

@@ -657,6 +657,232 @@ def c2c_noise(seed, array, trial, pixel, first_slice, n):
     return out
 
 
+def trial_voltage_arg(name, v, trials):
+    """A drive voltage of the trial run as the library takes it: a number -> float32 ``[1]`` (all trials), a sequence of
+    ``trials`` numbers -> float32 ``[trials]`` (one per trial).  Raises ``NsofValueError`` for a sequence of another length,
+    a value that is no number, and one that is not a finite float32."""
+    def num(u, where):
+        if isinstance(u, (bool, np.bool_)) or not isinstance(u, (int, float, np.integer, np.floating)):
+            raise NsofValueError(f"{name}{where} = {u!r} is not a number")
+        with np.errstate(over="ignore"):
+            f = np.float32(u)
+        if not np.isfinite(u) or not np.isfinite(f):
+            raise NsofValueError(f"{name}{where} = {u!r} is not a finite float32")
+        return f
+    if isinstance(v, np.ndarray) and v.ndim == 0:
+        v = v.item()
+    if isinstance(v, (str, bytes)) or np.ndim(v) == 0:
+        return np.array([num(v, "")], np.float32)
+    if np.ndim(v) != 1:
+        raise NsofValueError(f"{name} is neither a number nor a sequence of {trials} numbers (one per trial)")
+    seq = list(v)
+    if len(seq) != trials:
+        raise NsofValueError(f"{name} holds {len(seq)} voltages, the run has {trials} trials", _lib.NSOF_ESHAPE)
+    return np.array([num(u, f"[{i}]") for i, u in enumerate(seq)], np.float32)
+
+
+def _trial_scalars(version, polarity, params, dt, refractory_us, theta_events, c2c, trials):
+    """What the trial run checks before it looks at the sensor or the events -> dict(version, split, ap, theta, noise)."""
+    if version not in (1, 2):
+        raise NsofValueError("version must be 1 or 2")
+    if polarity not in ("split", "magnitude"):
+        raise NsofValueError("polarity must be 'split' or 'magnitude'")
+    ap = accum_params(params, dt, refractory_us)
+    theta = event_threshold(theta_events, version)
+    noise = c2c_arg(c2c)
+    if trials is not None and (not isinstance(trials, (int, np.integer)) or isinstance(trials, (bool, np.bool_)) or trials < 1):
+        raise NsofValueError(f"trials = {trials!r} is not a whole number >= 1")
+    return dict(version=version, split=version == 2 and polarity == "split", ap=ap, theta=theta, noise=noise)
+
+
+def _trial_config(early, H, W, param_maps, active_v, silent_v, trials, snapshot_every, memsize, v_ds):  # noqa: N803
+    """... and what it checks once the sensor is known: the planes, the trial count, the voltages, the block currents.
+    Everything ``TrialAccumulator`` hands to ``nsof_accum_trials_create``; no context is touched."""
+    n_trials, maps = trial_param_maps_arg(param_maps, (H, W))
+    if trials is not None:
+        for k, a in maps:   # (a 2-D plane arrives here as [1][H][W]: shared by the trials)
+            if np.ndim(param_maps[k]) == 3 and a.shape[0] != trials:
+                raise NsofValueError(f"param_maps[{k!r}] holds {a.shape[0]} trials, trials = {trials}", _lib.NSOF_ESHAPE)
+        n_trials = int(trials)
+    v_act, v_sil = trial_voltage_arg("active_v", active_v, n_trials), trial_voltage_arg("silent_v", silent_v, n_trials)
+    for name, v in (("snapshot_every", snapshot_every), ("memsize", memsize)):
+        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)) or v < 1):
+            raise NsofValueError(f"{name} = {v!r} is not a whole number >= 1")
+    if memsize is not None and memsize > min(H, W):
+        raise NsofValueError(f"memsize = {memsize} is larger than the {H}x{W} sensor")
+    if memsize is not None and snapshot_every is None:
+        raise NsofValueError("memsize needs snapshot_every: the cadence of the block currents is fixed for the object's life")
+    if not v_ds > 0:
+        raise NsofValueError(f"v_ds = {v_ds!r} must be positive")
+    return dict(early, H=int(H), W=int(W), n_trials=n_trials, maps=maps, v_act=v_act, v_sil=v_sil,
+                every=1 if snapshot_every is None else int(snapshot_every), memsize=None if memsize is None else int(memsize),
+                v_ds=float(v_ds))
+
+
+class TrialAccumulator:
+    """The Monte-Carlo trial run as a device-resident object (``nsof_accum_trials``): the ``T`` states, the refractory maps
+    and the slice counter stay in HBM and the stream is handed over chunk by chunk, so a recording of any length runs, the
+    state can be read out between chunks, and each trial may have its own drive voltages.
+
+    ``param_maps`` / ``trials`` / ``c2c`` and the device arguments as for ``simulate_trials_dev``.  ``active_v`` / ``silent_v``: a
+    number, or a sequence of ``T`` numbers -- trial ``t`` writes with ``active_v[t]`` and leaks with ``silent_v[t]``
+    (``version=2`` drives with the float32 sum of the two).  ``memsize`` (with ``snapshot_every`` and ``v_ds``, all fixed for
+    the object's life) makes ``step`` return block currents.  A run cut into chunks at any slices equals the run in one
+    chunk bit for bit, noise included: groups and snapshots follow the absolute slice counter, and a noise variate is a
+    function of the absolute slice index.  Trial ``t`` equals ``Accumulator(param_maps=planes[t], active_v=active_v[t], ...)``
+    stepped over the same slices bit for bit.  Every refusal of the arguments comes before a context exists."""
+
+    def __init__(self, height, width, param_maps, version=1, polarity="split", active_v=-8.0, silent_v=0.0, *, trials=None,
+                 c2c=None, params=None, dt=None, refractory_us=None, theta_events=None, snapshot_every=None, memsize=None, v_ds=1.0,
+                 ctx=None, _config=None):
+        self._p = None
+        cfg = _config or _trial_config(_trial_scalars(version, polarity, params, dt, refractory_us, theta_events, c2c, trials),
+                                       int(height), int(width), param_maps, active_v, silent_v, trials, snapshot_every, memsize, v_ds)
+        self.H, self.W, self.version, self.split = cfg["H"], cfg["W"], cfg["version"], cfg["split"]
+        self.trials, self.arrays, self.memsize, self.snapshot_every = cfg["n_trials"], 2 if cfg["split"] else 1, cfg["memsize"], cfg["every"]
+        self.ctx = ctx or default_context()
+        maps, noise = cfg["maps"], cfg["noise"]
+        p = C.c_void_p()
+        self.ctx.check(self.ctx._lib.nsof_accum_trials_create(
+            self.ctx.ptr, self.H, self.W, self.version, int(self.split), C.byref(cfg["ap"]), cfg["theta"], self.trials, len(maps),
+            *_frame_maps_c(self.trials, maps), None if noise is None else C.byref(_lib.AccumC2c(*noise)), cfg["v_act"].ctypes.data,
+            cfg["v_act"].size, cfg["v_sil"].ctypes.data, cfg["v_sil"].size, self.snapshot_every, self.memsize or 0, cfg["v_ds"],
+            C.byref(p)), "accum_trials_create")
+        self._p = p
+
+    @property
+    def _h(self):
+        if self._p is None:
+            raise NsofValueError("the trial accumulator is closed")
+        return self._p
+
+    def _empty(self, shape, dtype):
+        torch = _torch()
+        dev = torch.device("cuda", self.ctx.device)
+        out = torch.empty(shape, dtype=dtype, device=dev)
+        torch.cuda.synchronize(dev)   # the library writes on the context's stream
+        return out
+
+    @property
+    def slice_counter(self):
+        """The slices run since creation, ``reset()`` or the loaded state's own count."""
+        cnt = C.c_int64()
+        self.ctx.check(self.ctx._lib.nsof_accum_trials_read_state(self._h, None, None, C.byref(cnt)), "accum_trials_read_state")
+        return cnt.value
+
+    def step(self, x, y, p, t, bounds):
+        """Advance over slices ``[bounds[i], bounds[i+1])`` of the host event arrays (synchronous).  With ``memsize``: returns
+        the float64 CUDA tensor ``[A][T][S][H // memsize][W // memsize]`` of the block currents after the ``S`` snapshot slices
+        -- absolute indices 0, ``snapshot_every``, ... -- inside this chunk (the chunks' tensors concatenated along ``S`` are
+        the one-shot run's ``block_current``); otherwise ``None``."""
+        h = self._h
+        x = np.ascontiguousarray(x, np.int16)
+        y = np.ascontiguousarray(y, np.int16)
+        p = np.ascontiguousarray(p, np.int8)
+        t = np.ascontiguousarray(t, np.int64)
+        bounds = np.ascontiguousarray(bounds, np.int64)
+        if bounds.ndim != 1 or not (x.size == y.size == p.size == t.size):
+            raise NsofValueError("event arrays of differing lengths")
+        n = max(bounds.size - 1, 0)
+        if n and (bounds[-1] > x.size or bounds[0] < 0):
+            raise NsofValueError("event arrays shorter than the slice bounds")
+        cur = None
+        if self.memsize is not None:
+            s = int(self.ctx._lib.nsof_accum_trials_snaps_in(h, n))
+            cur = self._empty((self.arrays, self.trials, s, self.H // self.memsize, self.W // self.memsize), _torch().float64)
+        if n:
+            self.ctx.check(self.ctx._lib.nsof_accum_trials_step(h, x.ctypes.data, y.ctypes.data, p.ctypes.data, t.ctypes.data,
+                                                                bounds.ctypes.data, n, dev_ptr(cur) if cur is not None and cur.numel() else None,
+                                                                None), "accum_trials_step")
+        return cur
+
+    def w_dev(self):
+        """The states, float32 CUDA tensor ``[A][T][H][W]`` (asynchronous on the context's stream, like every ``*_dev``)."""
+        out = self._empty((self.arrays, self.trials, self.H, self.W), _torch().float32)
+        self.ctx.check(self.ctx._lib.nsof_accum_trials_w_dev(self._h, dev_ptr(out)), "accum_trials_w")
+        return out
+
+    def resistance_dev(self):
+        """``resistance_exp`` of the states, float32 CUDA tensor ``[A][T][H][W]``."""
+        out = self._empty((self.arrays, self.trials, self.H, self.W), _torch().float32)
+        self.ctx.check(self.ctx._lib.nsof_accum_trials_resistance_dev(self._h, dev_ptr(out)), "accum_trials_resistance")
+        return out
+
+    def block_current_dev(self):
+        """The block maxima of ``v_ds / R`` of the CURRENT states, float64 CUDA tensor ``[A][T][H // memsize][W // memsize]``."""
+        if self.memsize is None:
+            raise NsofValueError("block currents need a memsize at creation")
+        out = self._empty((self.arrays, self.trials, self.H // self.memsize, self.W // self.memsize), _torch().float64)
+        self.ctx.check(self.ctx._lib.nsof_accum_trials_block_current_dev(self._h, dev_ptr(out)), "accum_trials_block_current")
+        return out
+
+    def _surface(self, fn, dtype, out, which, mode):
+        torch = _torch()
+        if mode not in ("current", "state"):
+            raise NsofValueError("mode must be 'current' or 'state'")
+        if out is None:
+            out = self._empty((self.trials, self.H, self.W), dtype)
+        if out.dtype != dtype or tuple(out.shape) != (self.trials, self.H, self.W) or out.stride(2) != 1 or not out.is_cuda:
+            raise NsofValueError(f"the surfaces are a {dtype} CUDA tensor [{self.trials}][{self.H}][{self.W}] with pixel stride 1 "
+                                 f"(got {out.dtype} {tuple(out.shape)}, strides {tuple(out.stride())})", _lib.NSOF_ESHAPE)
+        size = out.element_size()
+        self.ctx.check(fn(self._h, int(which), {"current": 0, "state": 1}[mode], dev_ptr(out), out.stride(1) * size,
+                          (out.stride(0) if self.trials > 1 else self.H * out.stride(1)) * size), "accum_trials_surface")
+        return out
+
+    def surface_u8_dev(self, out=None, which=0, mode="state"):
+        """The surfaces of array ``which`` of all trials as 8-bit frames, uint8 CUDA tensor ``[T][H][W]`` (``out``: such a
+        tensor, rows and trials may be padded; ``None``: a new one) -- frame ``t`` is ``Accumulator.surface_u8`` of trial
+        ``t``'s array, the frames ``farneback_sequence`` takes.  One launch; ``mode`` as there."""
+        return self._surface(self.ctx._lib.nsof_accum_trials_surface_u8_dev, _torch().uint8, out, which, mode)
+
+    def surface_f32_dev(self, out=None, which=0, mode="state"):
+        """The same surfaces unquantised, float32 ``[T][H][W]`` (``Accumulator.surface_f32``)."""
+        return self._surface(self.ctx._lib.nsof_accum_trials_surface_f32_dev, _torch().float32, out, which, mode)
+
+    def state(self):
+        """-> dict(w float32 [A][T][H][W], next_ok int64 [A][H][W], slice_counter): everything a resume needs."""
+        w = np.empty((self.arrays, self.trials, self.H, self.W), np.float32)
+        nok = np.empty((self.arrays, self.H, self.W), np.int64)
+        cnt = C.c_int64()
+        self.ctx.check(self.ctx._lib.nsof_accum_trials_read_state(self._h, w.ctypes.data, nok.ctypes.data, C.byref(cnt)),
+                       "accum_trials_read_state")
+        return dict(w=w, next_ok=nok, slice_counter=cnt.value)
+
+    def load_state(self, state):
+        """Inverse of ``state()``; ``next_ok`` may be missing (zeros), ``slice_counter`` too (0).  Shapes that do not match
+        are refused before the library is called."""
+        w = np.ascontiguousarray(state["w"], np.float32)
+        if w.shape != (self.arrays, self.trials, self.H, self.W):
+            raise NsofValueError(f"state['w'] is {w.shape}, the object holds {(self.arrays, self.trials, self.H, self.W)}", _lib.NSOF_ESHAPE)
+        nok = state.get("next_ok")
+        if nok is not None:
+            nok = np.ascontiguousarray(nok, np.int64)
+            if nok.shape != (self.arrays, self.H, self.W):
+                raise NsofValueError(f"state['next_ok'] is {nok.shape}, the object holds {(self.arrays, self.H, self.W)}", _lib.NSOF_ESHAPE)
+        cnt = state.get("slice_counter", 0)
+        if isinstance(cnt, (bool, np.bool_)) or not isinstance(cnt, (int, np.integer)) or cnt < 0:
+            raise NsofValueError(f"state['slice_counter'] = {cnt!r} is not a whole number >= 0")
+        self.ctx.check(self.ctx._lib.nsof_accum_trials_write_state(self._h, w.ctypes.data, self.arrays * self.trials,
+                                                                   None if nok is None else nok.ctypes.data, self.arrays, int(cnt)),
+                       "accum_trials_write_state")
+
+    def reset(self):
+        """Back to the ``wini`` planes, zero refractory maps, slice counter 0."""
+        self.ctx.check(self.ctx._lib.nsof_accum_trials_reset(self._h), "accum_trials_reset")
+
+    def close(self):
+        if getattr(self, "_p", None) is not None:
+            self.ctx._lib.nsof_accum_trials_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
 def simulate_trials_dev(events, param_maps, version=1, slice_us=1_000, active_v=-8.0, silent_v=0.0, polarity="split", *,
                         sensor_size=None, params=None, dt=None, refractory_us=None, theta_events=None, snapshot_every=None,
                         memsize=None, v_ds=1.0, ctx=None, trials=None, c2c=None):
@@ -675,17 +901,10 @@ def simulate_trials_dev(events, param_maps, version=1, slice_us=1_000, active_v=
     ``seed``) -- every update ``w + g * dt`` becomes ``w + (g * f) * dt`` with ``f = max(0, 1 + sigma * xi)``, ``sigma`` that of
     the branch the drive took (``sigma_off``: ``V < voff``, ``sigma_on``: ``V > von``) and ``xi = c2c_noise(seed, a, t, y * W + x,
     slice, 1)``, a pure function of its arguments: results do not depend on ``snapshot_every`` or on how many trials run.
-    ``None``, or both spreads 0, is the noiseless run bit for bit.  Every refusal -- arguments, shapes, the value domain of
-    every plane -- comes before any device work.  Synchronous."""
-    if version not in (1, 2):
-        raise NsofValueError("version must be 1 or 2")
-    if polarity not in ("split", "magnitude"):
-        raise NsofValueError("polarity must be 'split' or 'magnitude'")
-    ap = accum_params(params, dt, refractory_us)
-    theta = event_threshold(theta_events, version)
-    noise = c2c_arg(c2c)
-    if trials is not None and (not isinstance(trials, (int, np.integer)) or isinstance(trials, (bool, np.bool_)) or trials < 1):
-        raise NsofValueError(f"trials = {trials!r} is not a whole number >= 1")
+    ``None``, or both spreads 0, is the noiseless run bit for bit.  ``active_v`` / ``silent_v``: a number, or a sequence of ``T``
+    numbers, one per trial (``TrialAccumulator``, which this function creates, steps once over the whole stream and closes).
+    Every refusal -- arguments, shapes, the value domain of every plane -- comes before any device work.  Synchronous."""
+    early = _trial_scalars(version, polarity, params, dt, refractory_us, theta_events, c2c, trials)
     if isinstance(events, (str, Path)):
         x, y, p, t, H, W = load_events(Path(events))  # noqa: N806
     else:
@@ -694,19 +913,9 @@ def simulate_trials_dev(events, param_maps, version=1, slice_us=1_000, active_v=
         if x.size == 0:
             raise NsofValueError("empty event stream")
         H, W = (int(y.max()) + 1, int(x.max()) + 1) if sensor_size is None else (int(v) for v in sensor_size)  # noqa: N806
-    n_trials, maps = trial_param_maps_arg(param_maps, (H, W))
-    if trials is not None:
-        for k, a in maps:   # (a 2-D plane arrives here as [1][H][W]: shared by the trials)
-            if np.ndim(param_maps[k]) == 3 and a.shape[0] != trials:
-                raise NsofValueError(f"param_maps[{k!r}] holds {a.shape[0]} trials, trials = {trials}", _lib.NSOF_ESHAPE)
-        n_trials = int(trials)
-    for name, v in (("snapshot_every", snapshot_every), ("memsize", memsize)):
-        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)) or v < 1):
-            raise NsofValueError(f"{name} = {v!r} is not a whole number >= 1")
-    if memsize is not None and memsize > min(H, W):
-        raise NsofValueError(f"memsize = {memsize} is larger than the {H}x{W} sensor")
-    if not v_ds > 0:
-        raise NsofValueError(f"v_ds = {v_ds!r} must be positive")
+    # (the cadence is checked here with a stand-in where it follows from the stream: that is known only below)
+    cfg = _trial_config(early, H, W, param_maps, active_v, silent_v, trials, 1 if snapshot_every is None and memsize is not None else snapshot_every,
+                        memsize, v_ds)
     x16, y16 = np.ascontiguousarray(x, np.int16), np.ascontiguousarray(y, np.int16)
     p8, t64 = np.ascontiguousarray(p, np.int8), np.ascontiguousarray(t, np.int64)
     if not (x16.size == y16.size == p8.size == t64.size):
@@ -715,24 +924,16 @@ def simulate_trials_dev(events, param_maps, version=1, slice_us=1_000, active_v=
     nslices = len(idx) - 1
     if nslices < 1:
         raise NsofValueError("the event stream holds no slice")
-    every = max(1, nslices // 100) if snapshot_every is None else int(snapshot_every)
-    split = version == 2 and polarity == "split"
-    torch = _torch()
-    ctx = ctx or default_context()
-    dev = torch.device("cuda", ctx.device)
-    narr = 2 if split else 1
-    out = dict(w=torch.empty((narr, n_trials, H, W), dtype=torch.float32, device=dev),
-               resistance=torch.empty((narr, n_trials, H, W), dtype=torch.float32, device=dev))
-    if memsize is not None:
-        out["block_current"] = torch.empty((narr, n_trials, (nslices - 1) // every + 1, H // int(memsize), W // int(memsize)),
-                                           dtype=torch.float64, device=dev)
-    torch.cuda.synchronize(dev)
-    nz = None if noise is None else C.byref(_lib.AccumC2c(*noise))
-    ctx.check(ctx._lib.nsof_accum_trials_c2c_dev(ctx.ptr, H, W, version, int(split), float(active_v), float(silent_v), C.byref(ap), theta,
-                                                 x16.ctypes.data, y16.ctypes.data, p8.ctypes.data, t64.ctypes.data, idx.ctypes.data,
-                                                 nslices, every, 0 if memsize is None else int(memsize), float(v_ds), n_trials, len(maps),
-                                                 *_frame_maps_c(n_trials, maps), dev_ptr(out["w"]), dev_ptr(out["resistance"]),
-                                                 dev_ptr(out["block_current"]) if memsize is not None else None, nz), "simulate_trials")
+    cfg["every"] = max(1, nslices // 100) if snapshot_every is None else int(snapshot_every)
+    acc = TrialAccumulator(H, W, param_maps, ctx=ctx, _config=cfg)
+    try:
+        cur = acc.step(x16, y16, p8, t64, idx)
+        out = dict(w=acc.w_dev(), resistance=acc.resistance_dev())
+        if cur is not None:
+            out["block_current"] = cur
+        acc.ctx.synchronize()
+    finally:
+        acc.close()
     return out
 
 

@@ -84,9 +84,14 @@ def events_variability_dev(x, y, p, t, sensor_hw, cfg, rel_sigma, trials, seed=0
 
     from .accumulator import c2c_arg, simulate_trials_dev, variability_maps
     from .context import default_context
+    from .errors import NsofValueError
     H, W = (int(v) for v in sensor_hw)  # noqa: N806
     variability_maps(1, 1, rel_sigma, params, seed, trials=trials)   # refuses before any device work
     c2c_arg(c2c)                                                      # ... and so does this
+    for name, v in (("active_v", active_v), ("silent_v", silent_v)):
+        if isinstance(v, (str, bytes)) or np.ndim(v) != 0:
+            raise NsofValueError(f"events_variability_dev: {name} = {v!r} must be one number -- the nominal array has one operating "
+                                 "point; a voltage per trial is TrialAccumulator's / simulate_trials_dev's")
     ctx = ctx or default_context()
     rows, cols = H // cfg.MEMSIZE, W // cfg.MEMSIZE
     acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, params=params, dt=dt, refractory_us=refractory_us,
