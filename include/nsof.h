@@ -981,6 +981,30 @@ int nsof_flow_to_image_dev(nsof_ctx* ctx, int n, const float* d_flows, ptrdiff_t
                            ptrdiff_t item_stride_floats, int width, int height, int sign, double clip_flow,
                            double max_flow, int convert_to_bgr, uint8_t* d_out, ptrdiff_t out_row_stride,
                            ptrdiff_t out_item_stride, float* d_norms);
+/* Statistics of an ensemble of flow fields against a reference flow (csrc/flow_ensemble.hip): the
+ * reduction of the Monte-Carlo trials' flows of a study.  Field f of trial t is an interleaved (u, v) float32 image at
+ * d_flows + t*trial_stride_floats + f*field_stride_floats, rows row_stride_floats apart (even, the base 8-byte aligned);
+ * d_ref: n_fields such fields with strides of their own, or NULL for a zero reference.  Per pixel, for the trials in
+ * index order, in double, every operation rounded on its own:
+ *     du = (double)flow.u - (double)ref.u, dv likewise;  sum += (du, dv);  sq += (du*du, dv*dv, du*dv);
+ *     e2 = du*du + dv*dv;  if (e2 > m) m = e2     (a NaN never enters the maximum, +inf does)
+ * into d_sum [n_fields][H][W][2], d_sq [n_fields][H][W][3] and d_epe2_max [n_fields][H][W].  accumulate 0 starts them from
+ * zero (they are written, not read), 1 continues from the stored values: a run cut into chunks of trials at any points
+ * equals the one-shot run bit for bit.  Per (trial, field), [n_trials][n_fields]: d_outliers counts the pixels with
+ * e2 > tau*tau (formed once on the host), d_nonfinite those with !(e2 < inf), d_aee = (sum over the pixels of sqrt(e2)) /
+ * (W*H) with IEEE propagation of non-finite pixels; the pixel sum has a fixed order that depends on the image size alone
+ * (per wave, per workgroup, then the workgroups' partials in index order; no float atomics), so d_aee has the same bits
+ * from run to run and however the trials are chunked.  All pointers DEVICE memory; asynchronous on the context's stream
+ * (only growing the context's workspace, on a first or larger call, waits for it).
+ * NSOF_EINVAL, nothing launched and no output touched, the value named in nsof_last_error: n_trials, n_fields, width or
+ * height < 1, a null pointer other than d_ref, an odd or too-short row stride or a base or stride that is not 8-byte
+ * aligned, accumulate outside {0, 1}, tau negative or NaN.  NSOF_EUNSUPPORTED (likewise): W*H > 2^27, or sizes beyond
+ * one launch (height > 262140, more than 65535 fields). */
+int nsof_flow_ensemble_dev(nsof_ctx* ctx, int n_trials, int n_fields, const float* d_flows, ptrdiff_t row_stride_floats,
+                           ptrdiff_t field_stride_floats, ptrdiff_t trial_stride_floats, int width, int height,
+                           const float* d_ref, ptrdiff_t ref_row_stride_floats, ptrdiff_t ref_field_stride_floats,
+                           double tau, int accumulate, double* d_sum, double* d_sq, double* d_epe2_max, double* d_aee,
+                           int32_t* d_outliers, int32_t* d_nonfinite);
 
 #ifdef __cplusplus
 }

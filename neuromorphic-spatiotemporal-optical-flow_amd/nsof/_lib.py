@@ -197,6 +197,9 @@ SIGNATURES = {
     "nsof_predict_sequence_u8_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "nsof_ssim_u8_batch_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _d, _vp]),
     "nsof_flow_to_image_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _i, _d, _d, _i, _vp, _pd, _pd, _vp]),
+    # ctx, n_trials, n_fields, flows, row / field / trial stride, width, height, ref, ref row / field stride, tau, accumulate,
+    # sum, sq, epe2_max, aee, outliers, nonfinite
+    "nsof_flow_ensemble_dev": (_i, [_vp, _i, _i, _vp, _pd, _pd, _pd, _i, _i, _vp, _pd, _pd, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

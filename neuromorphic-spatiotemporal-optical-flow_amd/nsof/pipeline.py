@@ -12,6 +12,7 @@ import numpy as np
 
 from . import gating
 from .accumulator import Accumulator, slice_index_array
+from .flowstats import events_flow_variability_dev  # noqa: F401  (the flow study of the event pipeline lives with its statistics)
 
 
 def surface_to_block_current(resistance, memsize, v_ds=1.0):
