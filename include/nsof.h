@@ -1006,6 +1006,60 @@ int nsof_flow_ensemble_dev(nsof_ctx* ctx, int n_trials, int n_fields, const floa
                            double tau, int accumulate, double* d_sum, double* d_sq, double* d_epe2_max, double* d_aee,
                            int32_t* d_outliers, int32_t* d_nonfinite);
 
+/* Event streams from frame sequences (csrc/events_from_frames.hip): a per-pixel level-crossing
+ * event generator, the contrast-threshold model of an event camera, in integers throughout.  d_frames: n uint8 frames
+ * [height][width] in DEVICE memory, row_stride / frame_stride bytes apart (any values that keep the frames readable);
+ * times: HOST int64 [n], microseconds, strictly increasing by less than 2^31; lut: HOST int32 [256], entries in [0, 2^30], the
+ * level of a grey value (256 * i: linear, in 1/256 grey levels); L[k] = lut[F[k]].  Thresholds c_on, c_off >= 1 in the
+ * table's units, or d_thr_plane != NULL: DEVICE int32 [height][width][2] (c_on, c_off) per pixel, the scalars unused.
+ * Every pixel keeps a reference level r (ref_mode NSOF_EVENTS_REF_ZERO: 0; _FIRST: L[0], so that frame 0 emits nothing;
+ * _GIVEN: d_ref_in, DEVICE int32 [height][width], the d_ref_out of a previous call; d_ref_in is NULL in the other modes)
+ * and takes one step per frame, in order, to the level b = L[k]:
+ *     b - r >= c_on:   m = (b - r) / c_on ON events at the levels r + j * c_on, j = 1..m;   r += m * c_on
+ *     r - b >= c_off:  m = (r - b) / c_off OFF events at the levels r - j * c_off;          r -= m * c_off
+ * after which -c_off < L[k] - r < c_on.  The events of frame 0 are stamped times[0]; those of frame k >= 1 times[k]
+ * (timestamps_mode NSOF_EVENTS_T_FRAME) or, the intensity taken to move linearly from a = L[k-1] to b (_T_LINEAR),
+ * times[k-1] + (|level - a| * (times[k] - times[k-1])) / |b - a| in int64, rounded down.  The stream has the frames in
+ * index order and within a frame ascends by (t, ON before OFF, y, x, j): the events of frame k are
+ * [frame_bounds[k], frame_bounds[k+1]), t never decreases, and with _T_FRAME and a binary sequence the order is that of
+ * generate_synthetic_events (event_mem_sim.py:109-158).  A run over frames [0, n) equals one over [0, k] followed by one
+ * over [k, n) from the first one's d_ref_out, bit for bit, and two runs give the same bits.
+ *
+ * The output size depends on the data, so there are two entries.  nsof_events_from_frames_count_dev forms the counts,
+ * synchronises and fills the HOST frame_bounds_out [n + 1] (frame_bounds_out[n]: the total); nothing else is written.
+ * nsof_events_from_frames_emit_dev takes those bounds back (frame_bounds, HOST [n + 1], with the arguments of the count
+ * call), forms the counts again on the stream and writes frame_bounds[n] events to d_x, d_y (int16), d_p (int8: p_on or
+ * p_off) and d_t (int64), DEVICE arrays of `capacity` elements, and the final r to d_ref_out (DEVICE int32
+ * [height][width], may be d_ref_in, may be NULL); it is asynchronous on the context's stream (only growing the
+ * context's workspace, on a first or larger call, waits for it).  The emit pass compares the total it has formed itself
+ * with frame_bounds[n] on the device and writes nothing at all, d_ref_out included, if they differ: bounds of another
+ * call cannot send a store past `capacity`.
+ * NSOF_EINVAL, nothing launched and nothing written, the value named in nsof_last_error: n < 1, height or width < 1 or
+ * above 32767, a null frames / times / lut / bounds pointer, times that do not increase strictly or a gap >= 2^31, a
+ * table entry outside [0, 2^30], a scalar threshold < 1, ref_mode and d_ref_in that do not match; emit alone: an unknown
+ * timestamps_mode, p_on or p_off outside an int8, capacity < frame_bounds[n], a null output array with events to write.
+ * A threshold plane that holds a value < 1 is seen by the count pass only (such a pixel emits nothing): the count entry
+ * returns NSOF_EINVAL without filling frame_bounds_out, the emit entry writes nothing.  NSOF_EUNSUPPORTED: a stream of
+ * 2^31 or more events (the count entry, frame_bounds_out untouched: the counts are 64-bit, the total is known before
+ * anything is emitted), more than 2^24 frames.
+ * Workspace: both entries keep the count table in the context's workspace, 16 bytes per frame and per 256 pixels
+ * (2 * n * ceil(height * width / 256) uint64: 130 KB per 1080p frame, 130 MB per 1000 of them), and the emit entry with
+ * _T_LINEAR adds 24 bytes per event plus the sort's temporary storage (a few MB).  The workspace grows on demand, is
+ * never shrunk before nsof_destroy, and a call it cannot hold returns NSOF_ENOMEM: long sequences are meant to be run in
+ * chunks of some hundred frames, each continuing from the previous one's d_ref_out (same stream, bit for bit). */
+enum { NSOF_EVENTS_REF_ZERO = 0, NSOF_EVENTS_REF_FIRST = 1, NSOF_EVENTS_REF_GIVEN = 2 };
+enum { NSOF_EVENTS_T_FRAME = 0, NSOF_EVENTS_T_LINEAR = 1 };
+int nsof_events_from_frames_count_dev(nsof_ctx* ctx, const uint8_t* d_frames, ptrdiff_t row_stride, ptrdiff_t frame_stride,
+                                      int n, int height, int width, const int64_t* times, const int32_t* lut, int c_on,
+                                      int c_off, const int32_t* d_thr_plane, const int32_t* d_ref_in, int ref_mode,
+                                      int64_t* frame_bounds_out);
+int nsof_events_from_frames_emit_dev(nsof_ctx* ctx, const uint8_t* d_frames, ptrdiff_t row_stride, ptrdiff_t frame_stride,
+                                     int n, int height, int width, const int64_t* times, const int32_t* lut, int c_on,
+                                     int c_off, const int32_t* d_thr_plane, const int32_t* d_ref_in, int ref_mode,
+                                     const int64_t* frame_bounds, int timestamps_mode, int p_on, int p_off,
+                                     int64_t capacity, int16_t* d_x, int16_t* d_y, int8_t* d_p, int64_t* d_t,
+                                     int32_t* d_ref_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,8 @@ struct nsof_ctx {
     nsof_table frames;
     // per-(trial, cell) parameter planes of the mapped frame-driven run (nsof_accum_frames_f64_maps_dev)
     nsof_table frame_maps;
+    // response table and frame times of the event generator (nsof_events_from_frames_*_dev)
+    nsof_table events;
     // exact-order fused iteration (farneback_iterate_x.hip): strip-to-strip carries (tagged granules, zeroed when
     // allocated, never again: a launch's tag is its epoch), the per-XCD ticket counters + timeout word (x_sync:
     // tickets at word 0, timeout word at word 256), the launch epoch, and whether a launch's timeout word needs a look

@@ -25,6 +25,9 @@ NSOF_OK, NSOF_EINVAL, NSOF_ESHAPE, NSOF_EDEVICE, NSOF_ENOMEM, NSOF_EUNSUPPORTED 
 PIXEL_U8, PIXEL_F32, PIXEL_U16, PIXEL_S16 = 0, 1, 2, 3
 # NSOF_ACCUM_KEY_* of include/nsof.h: the fields of nsof_accum_params a per-pixel map may replace, in struct order
 ACCUM_KEYS = ("alphaoff", "alphaon", "voff", "von", "koff", "kon", "son", "soff", "bon", "boff", "Ron", "Roff", "wini")
+# NSOF_EVENTS_REF_* / NSOF_EVENTS_T_* of include/nsof.h (nsof_events_from_frames_*_dev)
+EVENTS_REF_ZERO, EVENTS_REF_FIRST, EVENTS_REF_GIVEN = 0, 1, 2
+EVENTS_T_FRAME, EVENTS_T_LINEAR = 0, 1
 K_PREP, K_POLYEXP, K_UPSAMPLE, K_UPDMAT, K_BLUR, K_ACCUM, K_ITERATE, K_SEGMENT, K_MORPH, K_REMAP, K_SSIM, K_COUNT = range(12)
 
 _vp, _i, _d, _f, _sz, _pd, _i64 = C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_size_t, C.c_ssize_t, C.c_int64
@@ -200,6 +203,11 @@ SIGNATURES = {
     # ctx, n_trials, n_fields, flows, row / field / trial stride, width, height, ref, ref row / field stride, tau, accumulate,
     # sum, sq, epe2_max, aee, outliers, nonfinite
     "nsof_flow_ensemble_dev": (_i, [_vp, _i, _i, _vp, _pd, _pd, _pd, _i, _i, _vp, _pd, _pd, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # ctx, frames, row / frame stride, n, height, width, times, lut, c_on, c_off, thr_plane, ref_in, ref_mode, frame_bounds;
+    # emit: then timestamps_mode, p_on, p_off, capacity, x, y, p, t, ref_out
+    "nsof_events_from_frames_count_dev": (_i, [_vp, _vp, _pd, _pd, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    "nsof_events_from_frames_emit_dev": (_i, [_vp, _vp, _pd, _pd, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i64,
+                                              _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

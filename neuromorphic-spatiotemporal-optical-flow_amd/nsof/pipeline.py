@@ -12,6 +12,7 @@ import numpy as np
 
 from . import gating
 from .accumulator import Accumulator, slice_index_array
+from .events import events_from_frames_dev, events_from_video_dev, render_box_frames  # noqa: F401  (frames -> events, in HBM)
 from .flowstats import events_flow_variability_dev  # noqa: F401  (the flow study of the event pipeline lives with its statistics)
 
 
@@ -270,6 +271,24 @@ def events_to_flow_sequence(x, y, p, t, sensor_hw, params=None, slice_us=1000, a
     if timings is not None:
         timings.update(accumulator_s=t1 - t0, flow_s=t2 - t1, slices=n_frames * snapshot_every, frames=n_frames)
     return frames, flows
+
+
+def video_to_flow_sequence(frames, times_us=None, *, frame_us=None, threshold=10.0, threshold_off=None, threshold_maps=None,
+                           response=None, ref=None, timestamps="linear", p_on=1, p_off=-1, ctx=None, **accumulator_args):
+    """A grey video in HBM through the event pipeline: ``events_from_frames_dev(frames, ...)`` (the arguments up to
+    ``p_off``) turns the frames into an event stream in HBM, one copy brings it to the host (the accumulator's entries
+    stage host event arrays), and ``events_to_flow_sequence(x, y, p, t, (H, W), **accumulator_args)`` accumulates it and
+    takes the flow between its surface frames.  Returns ``(surface frames uint8 [m][H][W], flows float32 [m-1][H][W][2],
+    events)``, ``events`` the generator's result dict (``x, y, p, t`` CUDA tensors, ``frame_bounds``, ``ref``)."""
+    from .context import default_context
+    ctx = ctx or default_context()
+    ev = events_from_frames_dev(frames, times_us, frame_us=frame_us, threshold=threshold, threshold_off=threshold_off,
+                                threshold_maps=threshold_maps, response=response, ref=ref, timestamps=timestamps, p_on=p_on,
+                                p_off=p_off, ctx=ctx)
+    ctx.synchronize()
+    x, y, p, t = (ev[k].cpu().numpy() for k in "xypt")
+    surfaces, flows = events_to_flow_sequence(x, y, p, t, (int(frames.shape[1]), int(frames.shape[2])), ctx=ctx, **accumulator_args)
+    return surfaces, flows, ev
 
 
 def events_to_flow_sequence_sharded(x, y, p, t, sensor_hw, params=None, slice_us=1000, active_v=-6.0, silent_v=0.0,

@@ -41,6 +41,25 @@ def make_pair(seed, height=1080, width=1920, shift=(2.5, -1.25), rot_deg=0.2, si
     return to_u8(prev), to_u8(nxt)
 
 
+def make_sequence(seed, n, height=1080, width=1920, shift=(2.5, -1.25), rot_deg=0.2, sigma=3.0, pad=24):
+    """uint8 frames [n][height][width] of one texture drifting: frame k is ``make_pair(seed, height, width, (k * shift[0],
+    k * shift[1]), k * rot_deg, sigma)[1]``, the texture formed once.  ``pad``: the texture's margin around the frame (24:
+    ``make_pair``'s; a drift beyond it samples the texture's edge)."""
+    rng = np.random.default_rng(seed)
+    base = _gauss_blur(rng.random((height + 2 * pad, width + 2 * pad)), sigma)
+    base = (base - base.min()) / (base.max() - base.min()) * 255.0
+    yy, xx = np.mgrid[0:height, 0:width].astype(np.float64)
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+    out = np.empty((n, height, width), np.uint8)
+    for k in range(n):
+        th = np.deg2rad(k * rot_deg)
+        dx, dy = xx - cx - k * shift[0], yy - cy - k * shift[1]
+        sx = np.cos(th) * dx + np.sin(th) * dy + cx
+        sy = -np.sin(th) * dx + np.cos(th) * dy + cy
+        out[k] = np.clip(np.rint(_bilinear(base, sy + pad, sx + pad)), 0, 255).astype(np.uint8)
+    return out
+
+
 def true_flow(height, width, shift=(2.5, -1.25), rot_deg=0.2):
     """The (u, v) field make_pair() applies, float64 (H, W, 2)."""
     yy, xx = np.mgrid[0:height, 0:width].astype(np.float64)
