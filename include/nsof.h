@@ -1060,6 +1060,61 @@ int nsof_events_from_frames_emit_dev(nsof_ctx* ctx, const uint8_t* d_frames, ptr
                                      int64_t capacity, int16_t* d_x, int16_t* d_y, int8_t* d_p, int64_t* d_t,
                                      int32_t* d_ref_out);
 
+/* The same generator with two effects of a real sensor: a per-pixel refractory period and
+ * background-activity noise events.  Integers only, a counter generator, no atomics: two runs give the same bits and a
+ * run cut at any frame equals the one-shot run.  Everything not named here is as above.
+ *
+ * Per-pixel state besides r: t_ok (int64), the earliest time at which the pixel may fire again; INT64_MIN: never fired
+ * (d_t_ok_in NULL starts every pixel there).  The candidates of pixel q = y * width + x at frame k of the call:
+ *   signal  the m crossings of the step above with their stamps t_1 <= ... <= t_m (times[k] with _T_FRAME and for frame 0
+ *           of a call, else the linear formula).  r moves by m thresholds whether or not the events survive (the
+ *           comparator resets, only the read-out is blocked), so d_ref_out does not depend on noise or refractory time.
+ *   noise   for k >= 1 only (frame 0 of a call has no interval before it).  One Philox4x32-10 block per pixel and frame:
+ *           counter (q, f & 0xffffffff, f >> 32, 0x4E534546) with f = first_frame + k the absolute frame index, key
+ *           (seed & 0xffffffff, seed >> 32); outputs c0..c3.  With D = times[k] - times[k-1] and a rate in units of 2^-32
+ *           per microsecond, P_on = min(2^32 - 1, rate_on_q * D) in uint64 (likewise P_off): an ON noise event exists iff
+ *           c0 < P_on, an OFF one iff c1 < P_off; stamped times[k] (_T_FRAME) or times[k-1] + ((c2 * D) >> 32) (ON) and
+ *           the same with c3 (OFF), which lie in [times[k-1], times[k]).  Noise does not move r.  A rate above 1 / D
+ *           saturates at one noise event per pixel, polarity and interval.  d_rate_plane != NULL: DEVICE uint32
+ *           [height][width][2] (rate_on_q, rate_off_q) per pixel -- hot pixels -- the scalars unused.
+ * The candidates of a pixel and frame are walked in the order (t, signal before ON noise before OFF noise), the signal
+ * crossings in their own order; a candidate is emitted iff t >= t_ok, and then t_ok = t + refractory_us.  With
+ * refractory_us = 0 and no d_t_ok_in nothing is ever dropped.  Stream order as above, a noise event being the last j of
+ * its polarity for its pixel and frame; with _T_LINEAR that is the stable sort by t of the order (frame, polarity, y, x, j).
+ * The calls over frames [0, k] with first_frame = f and over [k, n) with first_frame = f + k, d_ref_in and d_t_ok_in the
+ * first call's d_ref_out and d_t_ok_out, give the one-shot stream, d_ref_out and d_t_ok_out bit for bit.
+ *
+ * The counts depend on the stamps once candidates can be dropped, so the count entry takes timestamps_mode too, and both
+ * entries must be given the same mode and the same *sensor.  sensor == NULL: exactly the entries above (d_t_ok_out is
+ * then not written).  d_t_ok_out: DEVICE int64 [height][width], may be d_t_ok_in, may be NULL.
+ * NSOF_EINVAL beyond the refusals above, nothing launched and nothing written: refractory_us outside [0, 2^31),
+ * first_frame < 0 or first_frame + n beyond 2^62, a timestamps_mode the count entry does not know, a d_t_ok_in without a
+ * d_t_ok_out (emit entry).  A walk through single crossings is needed only with _T_LINEAR and a refractory time or a
+ * d_t_ok_in; there a pixel that crosses 2^20 thresholds or more in one step is refused like a bad threshold plane (the
+ * count entry returns NSOF_EUNSUPPORTED without filling frame_bounds_out, the emit entry writes nothing). */
+typedef struct nsof_events_sensor {
+    int64_t refractory_us;        /* [0, 2^31) */
+    uint64_t seed;                /* the key of the noise draws */
+    int64_t first_frame;          /* the absolute index of frame 0 of this call */
+    uint32_t rate_on_q, rate_off_q;   /* noise rates, 2^-32 events per microsecond */
+    const uint32_t* d_rate_plane; /* DEVICE [height][width][2] or NULL */
+    const int64_t* d_t_ok_in;     /* DEVICE [height][width] or NULL */
+} nsof_events_sensor;
+int nsof_events_from_frames_sensor_count_dev(nsof_ctx* ctx, const uint8_t* d_frames, ptrdiff_t row_stride,
+                                             ptrdiff_t frame_stride, int n, int height, int width, const int64_t* times,
+                                             const int32_t* lut, int c_on, int c_off, const int32_t* d_thr_plane,
+                                             const int32_t* d_ref_in, int ref_mode, int timestamps_mode,
+                                             const nsof_events_sensor* sensor, int64_t* frame_bounds_out);
+int nsof_events_from_frames_sensor_emit_dev(nsof_ctx* ctx, const uint8_t* d_frames, ptrdiff_t row_stride,
+                                            ptrdiff_t frame_stride, int n, int height, int width, const int64_t* times,
+                                            const int32_t* lut, int c_on, int c_off, const int32_t* d_thr_plane,
+                                            const int32_t* d_ref_in, int ref_mode, const int64_t* frame_bounds,
+                                            int timestamps_mode, int p_on, int p_off, int64_t capacity, int16_t* d_x,
+                                            int16_t* d_y, int8_t* d_p, int64_t* d_t, int32_t* d_ref_out,
+                                            const nsof_events_sensor* sensor, int64_t* d_t_ok_out);
+/* The four words c0..c3 of the noise block of (seed, pixel, frame) above, computed on the host: the bits the kernels use. */
+void nsof_events_noise_draw(uint64_t seed, uint32_t pixel, int64_t frame, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

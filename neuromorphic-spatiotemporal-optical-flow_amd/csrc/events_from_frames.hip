@@ -22,8 +22,15 @@
 // No float anywhere and no atomics: every offset is a sum of integers in a fixed order, so two runs give the same bits.
 // Counts are 64-bit and the scans saturate, so no stream -- whatever the caller's reference plane holds -- can wrap a
 // total: the emit pass writes only when the total it has formed itself equals the one the caller sized the outputs for.
+//
+// The sensor entries (nsof_events_from_frames_sensor_*_dev) run the SENSOR instantiations of the
+// count and emit kernels: per pixel and frame one Philox block gives up to two noise candidates, and -- with a refractory
+// time or a given t_ok plane -- the pixel's candidates are walked in time order against t_ok, which lives in a register
+// like r.  The count pass runs the same walk as the emit pass, so its counts depend on the stamp mode.  The plain
+// instantiations hold none of this.
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "accum_c2c.h"
 #include "nsof_internal.h"
 
 namespace {
@@ -45,6 +52,22 @@ struct ef_args {
     const int32_t* thr;       // DEVICE [H][W][2] (c_on, c_off) or nullptr
     const int32_t* ref_in;    // DEVICE [H][W] (ref_mode NSOF_EVENTS_REF_GIVEN)
     int ref_mode;
+};
+
+// What the SENSOR instantiations read besides (the plain ones take it and leave it alone).
+constexpr unsigned EF_NOISE_WORD = 0x4E534546u;   // the fourth counter word: apart from the c2c draws of the same seed
+constexpr unsigned EF_NONE = 0xffffffffu;         // no noise candidate (an offset into the interval is below 2^31)
+constexpr unsigned EF_WALK_MAX = 1u << 20;        // crossings of one step a thread walks one by one
+struct ef_sensor {
+    long long refractory;     // microseconds, [0, 2^31)
+    long long first_frame;    // the absolute index of frame 0
+    unsigned k0, k1;          // the Philox key: the seed's two words
+    unsigned rate_on, rate_off;   // 2^-32 per microsecond (rate_plane == nullptr)
+    const unsigned* rate_plane;   // DEVICE [H][W][2] or nullptr
+    const int64_t* t_ok_in;   // DEVICE [H][W] or nullptr: every pixel starts at INT64_MIN
+    int noise;                // some rate may be non-zero
+    int walk;                 // a candidate may be dropped: refractory > 0 or t_ok_in given
+    int linear;               // the stamp mode (the count pass; the emit pass has it as a template argument)
 };
 
 // A thread's pixel.  A thread past the last pixel walks pixel 0 (every load stays inside the frames and none is
@@ -119,12 +142,144 @@ __device__ __forceinline__ u64 sat_add(u64 a, u64 b)
     return s < a ? ~0ull : s;
 }
 
-__global__ __launch_bounds__(EF_WG) void k_ef_count(ef_args a, u64* __restrict__ table, u64* __restrict__ bad)
+// ---- the sensor model (SENSOR instantiations only) ------------------------------------------------------------------
+// A pixel's sensor state: its noise rates and t_ok, the earliest time at which it may fire again.
+struct ef_spx {
+    unsigned rate_on, rate_off;
+    int64_t t_ok;
+};
+
+__device__ __forceinline__ ef_spx ef_sensor_init(const ef_sensor& s, const ef_px& q)
+{
+    ef_spx p;
+    p.rate_on = s.rate_plane ? s.rate_plane[2 * (size_t)q.pix] : s.rate_on;
+    p.rate_off = s.rate_plane ? s.rate_plane[2 * (size_t)q.pix + 1] : s.rate_off;
+    p.t_ok = s.t_ok_in ? s.t_ok_in[q.pix] : INT64_MIN;
+    return p;
+}
+
+// The noise candidates of a pixel in the interval before frame k >= 1 of the call, dt = T[k] - T[k-1] < 2^31: their
+// offsets from T[k-1], EF_NONE for none.  One Philox block; a silent pixel draws nothing.
+__device__ __forceinline__ void ef_noise(const ef_sensor& s, const ef_px& q, const ef_spx& p, int k, u64 dt, unsigned& off_on,
+                                         unsigned& off_off)
+{
+    off_on = off_off = EF_NONE;
+    if (!(p.rate_on | p.rate_off)) return;
+    const u64 f = (u64)(s.first_frame + k);
+    unsigned c[4] = {(unsigned)q.pix, (unsigned)f, (unsigned)(f >> 32), EF_NOISE_WORD};
+    philox4x32_10(c, s.k0, s.k1);
+    const u64 p_on = min((u64)p.rate_on * dt, 0xffffffffull), p_off = min((u64)p.rate_off * dt, 0xffffffffull);
+    if (c[0] < p_on) off_on = (unsigned)(((u64)c[2] * dt) >> 32);
+    if (c[1] < p_off) off_off = (unsigned)(((u64)c[3] * dt) >> 32);
+}
+
+// The candidates of a pixel at one frame.
+struct ef_cands {
+    unsigned m;               // signal: m crossings of polarity `on` at the levels r0 +- j * c
+    bool on;
+    int r0, c;
+    int a_level, lev;         // L[k-1], L[k]
+    int64_t t_prev, t_k;      // T[k-1], T[k]
+    bool same;                // every candidate is stamped t_k (frame stamps, or frame 0 of the call)
+    unsigned off_on, off_off; // noise: offsets from t_prev, EF_NONE for none
+};
+
+// The refractory walk of one frame: the candidates in the order (t, signal before ON noise before OFF noise), a candidate
+// emitted iff t >= t_ok, and then t_ok = t + refractory.  emit(kind, count, t): kind 0 = `count` signal crossings in a row
+// (the next ones of the pixel's order), 1 = the ON noise event, 2 = the OFF noise event.  With one stamp for all the walk
+// is closed: nothing if t_k < t_ok, the first candidate alone under a refractory time, else all of them.
+template <int LINEAR, class Emit>
+__device__ __forceinline__ void ef_walk(const ef_cands& c, long long refractory, int64_t& t_ok, Emit&& emit)
+{
+    const bool has_on = c.off_on != EF_NONE, has_off = c.off_off != EF_NONE;
+    if (!LINEAR || c.same) {
+        if (!(c.m || has_on || has_off) || c.t_k < t_ok) return;
+        if (refractory > 0) {
+            emit(c.m ? 0 : has_on ? 1 : 2, 1u, c.t_k);
+        } else {
+            if (c.m) emit(0, c.m, c.t_k);
+            if (has_on) emit(1, 1u, c.t_k);
+            if (has_off) emit(2, 1u, c.t_k);
+        }
+        t_ok = (int64_t)((u64)c.t_k + (u64)refractory);
+        return;
+    }
+    // the (at most two) noise candidates in time order, ON first on a tie
+    int nn = (int)has_on + (int)has_off;
+    int64_t tn0 = c.t_prev + (int64_t)c.off_on, tn1 = c.t_prev + (int64_t)c.off_off;
+    int kn0 = 1, kn1 = 2;
+    if (!has_on || (has_off && tn1 < tn0)) {
+        const int64_t t = tn0;
+        tn0 = tn1;
+        tn1 = t;
+        kn0 = 2;
+        kn1 = 1;
+    }
+    const u64 dt = (u64)(c.t_k - c.t_prev);
+    const long long span = (long long)c.lev - (long long)c.a_level;
+    const u64 den = (u64)(span < 0 ? -span : span);
+    long long level = c.r0;
+    for (unsigned i = 0; i < c.m; i++) {
+        level += c.on ? c.c : -c.c;
+        int64_t t = c.t_k;
+        if (den) {
+            const long long off = level - (long long)c.a_level;
+            t = c.t_prev + (int64_t)(((u64)(off < 0 ? -off : off) * dt) / den);
+        }
+        while (nn && tn0 < t) {   // noise strictly before this crossing: a signal crossing goes first on a tie
+            if (tn0 >= t_ok) {
+                t_ok = (int64_t)((u64)tn0 + (u64)refractory);
+                emit(kn0, 1u, tn0);
+            }
+            tn0 = tn1;
+            kn0 = kn1;
+            nn--;
+        }
+        if (t >= t_ok) {
+            t_ok = (int64_t)((u64)t + (u64)refractory);
+            emit(0, 1u, t);
+        }
+    }
+    while (nn) {
+        if (tn0 >= t_ok) {
+            t_ok = (int64_t)((u64)tn0 + (u64)refractory);
+            emit(kn0, 1u, tn0);
+        }
+        tn0 = tn1;
+        kn0 = kn1;
+        nn--;
+    }
+}
+
+// The events of a pixel at frame k that survive, per polarity; t_ok moves on.  Without a walk (nothing can be dropped)
+// they are the candidates and t_ok is left alone.
+template <int LINEAR>
+__device__ __forceinline__ void ef_survivors(const ef_sensor& s, const ef_cands& c, int64_t& t_ok, unsigned& n_on, unsigned& n_off)
+{
+    n_on = n_off = 0;
+    if (!s.walk) {
+        n_on = (c.on ? c.m : 0u) + (c.off_on != EF_NONE);
+        n_off = (c.on ? 0u : c.m) + (c.off_off != EF_NONE);
+        return;
+    }
+    ef_walk<LINEAR>(c, s.refractory, t_ok, [&](int kind, unsigned count, int64_t) {
+        const bool to_on = kind == 0 ? c.on : kind == 1;   // (no branch: the two sums stay in registers)
+        n_on += to_on ? count : 0u;
+        n_off += to_on ? 0u : count;
+    });
+}
+
+// bad[0]: a threshold plane holds a value < 1; bad[1]: a step of EF_WALK_MAX crossings or more under a walk (SENSOR).
+template <int SENSOR>
+__global__ __launch_bounds__(EF_WG) void k_ef_count(ef_args a, ef_sensor s, u64* __restrict__ table, u64* __restrict__ bad)
 {
     __shared__ int sh_lut[256];
     __shared__ u64 sh[2][EF_BATCH][2][4];   // [set][frame of the batch][polarity][wave]; two sets used in turn: one barrier per batch
     ef_px q = ef_init(a, sh_lut);
     if (q.in && (q.c_on < 1 || q.c_off < 1)) *bad = 1;
+    ef_spx sp{};
+    int prev_level = 0;   // L[k - 1] (SENSOR)
+    if (SENSOR) sp = ef_sensor_init(s, q);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t n_wg = gridDim.x;
     int set = 0;
@@ -135,15 +290,44 @@ __global__ __launch_bounds__(EF_WG) void k_ef_count(ef_args a, u64* __restrict__
         for (int j = 0; j < EF_BATCH; j++) {
             bool on = false;
             unsigned m = 0;
-            if (k0 + j < a.n) m = ef_step(q.r, sh_lut[f[j]], q.c_on, q.c_off, on);
-            if (!q.in) m = 0;
+            unsigned n_on, n_off;   // the pixel's events of the frame
+            if (!SENSOR) {
+                if (k0 + j < a.n) m = ef_step(q.r, sh_lut[f[j]], q.c_on, q.c_off, on);
+                if (!q.in) m = 0;
+                n_on = on ? m : 0u;
+                n_off = on ? 0u : m;
+            } else {
+                const int k = k0 + j;
+                n_on = n_off = 0;
+                if (k < a.n) {
+                    ef_cands c;
+                    c.lev = sh_lut[f[j]];
+                    c.a_level = prev_level;
+                    prev_level = c.lev;
+                    c.r0 = q.r;
+                    c.m = ef_step(q.r, c.lev, q.c_on, q.c_off, c.on);
+                    c.c = c.on ? q.c_on : q.c_off;
+                    c.t_k = a.times[k];
+                    c.t_prev = a.times[max(k - 1, 0)];
+                    c.same = !s.linear || k == 0;
+                    c.off_on = c.off_off = EF_NONE;
+                    if (s.noise && k > 0) ef_noise(s, q, sp, k, (u64)(c.t_k - c.t_prev), c.off_on, c.off_off);
+                    if (s.walk && !c.same && c.m >= EF_WALK_MAX) {
+                        if (q.in) bad[1] = 1;
+                        c.m = 0;   // the call is refused: no long walk for nothing
+                    }
+                    ef_survivors<1>(s, c, sp.t_ok, n_on, n_off);
+                    if (!q.in) n_on = n_off = 0;
+                }
+                m = n_on | n_off;
+            }
             u64 s_on, s_off;
             if (!__any(m >> 24)) {   // every lane below 2^24 (any frame of the linear table): the wave's sums fit 32 bits
-                s_on = ef_wave_last(ef_wave_scan(on ? m : 0u));
-                s_off = ef_wave_last(ef_wave_scan(on ? 0u : m));
+                s_on = ef_wave_last(ef_wave_scan(n_on));
+                s_off = ef_wave_last(ef_wave_scan(n_off));
             } else {
-                s_on = on ? m : 0u;
-                s_off = on ? 0u : m;
+                s_on = n_on;
+                s_off = n_off;
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) {
                     s_on += __shfl_xor(s_on, o, 64);
@@ -197,17 +381,34 @@ __global__ __launch_bounds__(EF_WG) void k_ef_scan(u64* __restrict__ data, size_
     if (threadIdx.x == 0) tot[blockIdx.x] = carry;
 }
 
-// meta: [0 .. 2n) the bases of the (frame, polarity) rows, [2n] the total, [2n + 1] the bad-threshold flag.
+// meta: [0 .. 2n) the bases of the (frame, polarity) rows, [2n] the total, [2n + 1] the bad-threshold flag, [2n + 2] the
+// long-walk flag (which the plain kernels never raise).
 __device__ __forceinline__ bool ef_guard(const u64* meta, int n, u64 expected) { return meta[2 * (size_t)n] == expected && meta[2 * (size_t)n + 1] == 0; }
 
+// Where the emit pass writes.
+struct ef_out {
+    int p_on, p_off;
+    int16_t *x, *y;           // frame stamps: the caller's arrays
+    int8_t* p;
+    int64_t* t;
+    u64* keys;                // linear stamps: (t - T[0], (x, y, polarity)) pairs for the reorder
+    unsigned* vals;
+    int32_t* ref;
+    int64_t* t_ok;            // SENSOR
+};
+
+// The plain emit pass (k_ef_emit<LINEAR, 0>).
 template <int LINEAR>
-__global__ __launch_bounds__(EF_WG) void k_ef_emit(ef_args a, const u64* __restrict__ table, const u64* __restrict__ meta,
-                                                   u64 expected, int p_on, int p_off, int16_t* __restrict__ ox,
-                                                   int16_t* __restrict__ oy, int8_t* __restrict__ op, int64_t* __restrict__ ot,
-                                                   u64* __restrict__ keys, unsigned* __restrict__ vals,
-                                                   int32_t* __restrict__ ref_out)
+__device__ __forceinline__ void ef_emit_plain(const ef_args& a, const u64* __restrict__ table, const u64* __restrict__ meta, const ef_out& o)
 {
-    if (!ef_guard(meta, a.n, expected)) return;   // the same for every thread of the grid: nothing is written
+    const int p_on = o.p_on, p_off = o.p_off;
+    int16_t* __restrict__ ox = o.x;
+    int16_t* __restrict__ oy = o.y;
+    int8_t* __restrict__ op = o.p;
+    int64_t* __restrict__ ot = o.t;
+    u64* __restrict__ keys = o.keys;
+    unsigned* __restrict__ vals = o.vals;
+    int32_t* __restrict__ ref_out = o.ref;
     __shared__ int sh_lut[256];
     __shared__ unsigned sh[2][EF_BATCH][2][4];
     ef_px q = ef_init(a, sh_lut);
@@ -291,12 +492,122 @@ __global__ __launch_bounds__(EF_WG) void k_ef_emit(ef_args a, const u64* __restr
     if (q.in && ref_out) ref_out[q.pix] = q.r;
 }
 
+// The emit pass of the sensor model (k_ef_emit<LINEAR, 1>).  A pixel may have events of both polarities at one frame (a
+// signal step and noise), so both prefixes are kept.  Each frame is walked twice, from two copies of t_ok that move alike:
+// before the barrier for the counts the prefixes need, after it to write.  A noise event is the last of its polarity.
+template <int LINEAR>
+__device__ __forceinline__ void ef_emit_sensor(const ef_args& a, const ef_sensor& s, const u64* __restrict__ table,
+                                               const u64* __restrict__ meta, const ef_out& o)
+{
+    __shared__ int sh_lut[256];
+    __shared__ unsigned sh[2][EF_BATCH][2][4];
+    ef_px q = ef_init(a, sh_lut);
+    ef_spx sp = ef_sensor_init(s, q);
+    int64_t t_ok = sp.t_ok;   // the writing walk's copy; sp.t_ok is the counting walk's
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t n_wg = gridDim.x;
+    const int64_t t_first = a.times[0];
+    const unsigned packed = (unsigned)q.x | ((unsigned)q.y << 15);
+    const int p_on = o.p_on, p_off = o.p_off;
+    int prev_level = 0;   // L[k - 1]
+    int set = 0;
+    for (int k0 = 0; k0 < a.n; k0 += EF_BATCH, set ^= 1) {
+        unsigned f[EF_BATCH];
+        ef_load(a, q, k0, f);
+        ef_cands c[EF_BATCH];
+        unsigned incl[EF_BATCH][2], cnt[EF_BATCH][2];
+        u64 base[EF_BATCH][2];   // where the workgroup's ON and OFF events of each frame start (the same in every lane)
+#pragma unroll
+        for (int j = 0; j < EF_BATCH; j++) {
+            const size_t row = (size_t)min(k0 + j, a.n - 1) * 2;
+            base[j][0] = meta[row] + table[row * n_wg + blockIdx.x];
+            base[j][1] = meta[row + 1] + table[(row + 1) * n_wg + blockIdx.x];
+        }
+#pragma unroll
+        for (int j = 0; j < EF_BATCH; j++) {
+            const int k = k0 + j;
+            cnt[j][0] = cnt[j][1] = 0;
+            c[j].m = 0;
+            c[j].off_on = c[j].off_off = EF_NONE;
+            if (k < a.n) {
+                c[j].lev = sh_lut[f[j]];
+                c[j].a_level = prev_level;
+                prev_level = c[j].lev;
+                c[j].r0 = q.r;
+                c[j].m = ef_step(q.r, c[j].lev, q.c_on, q.c_off, c[j].on);
+                c[j].c = c[j].on ? q.c_on : q.c_off;
+                c[j].t_k = a.times[k];
+                c[j].t_prev = a.times[max(k - 1, 0)];
+                c[j].same = !LINEAR || k == 0;
+                if (s.noise && k > 0) ef_noise(s, q, sp, k, (u64)(c[j].t_k - c[j].t_prev), c[j].off_on, c[j].off_off);
+                ef_survivors<LINEAR>(s, c[j], sp.t_ok, cnt[j][0], cnt[j][1]);
+                if (!q.in) cnt[j][0] = cnt[j][1] = 0;
+            }
+            // the total is below 2^31 (the guard), so 32 bits hold every prefix
+            incl[j][0] = ef_wave_scan(cnt[j][0]);
+            incl[j][1] = ef_wave_scan(cnt[j][1]);
+            if (lane == 63) {
+                sh[set][j][0][wave] = incl[j][0];
+                sh[set][j][1][wave] = incl[j][1];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < EF_BATCH; j++) {
+            if (k0 + j >= a.n) break;
+            unsigned before[2] = {0, 0};
+#pragma unroll
+            for (int w = 0; w < 4; w++)
+                if (w < wave) {
+                    before[0] += sh[set][j][0][w];
+                    before[1] += sh[set][j][1][w];
+                }
+            if (!q.in || (c[j].m == 0 && c[j].off_on == EF_NONE && c[j].off_off == EF_NONE)) continue;
+            // the pixel's ON events are [end_on - cnt, end_on), its OFF events likewise
+            const size_t end_on = (size_t)base[j][0] + before[0] + incl[j][0], end_off = (size_t)base[j][1] + before[1] + incl[j][1];
+            size_t at = c[j].on ? end_on - cnt[j][0] : end_off - cnt[j][1];   // the next signal event
+            const bool sig_on = c[j].on;
+            ef_walk<LINEAR>(c[j], s.refractory, t_ok, [&](int kind, unsigned count, int64_t t) {
+                const bool is_on = kind == 0 ? sig_on : kind == 1;
+                size_t w = kind == 0 ? at : kind == 1 ? end_on - 1 : end_off - 1;
+                at += kind == 0 ? count : 0u;
+                for (unsigned i = 0; i < count; i++, w++) {
+                    if (LINEAR) {
+                        o.keys[w] = (u64)(t - t_first);
+                        o.vals[w] = packed | (is_on ? 1u << 30 : 0u);
+                    } else {
+                        o.x[w] = (int16_t)q.x;
+                        o.y[w] = (int16_t)q.y;
+                        o.p[w] = (int8_t)(is_on ? p_on : p_off);
+                        o.t[w] = t;
+                    }
+                }
+            });
+        }
+    }
+    if (q.in && o.ref) o.ref[q.pix] = q.r;
+    if (q.in && o.t_ok) o.t_ok[q.pix] = t_ok;
+}
+
+template <int LINEAR, int SENSOR>
+__global__ __launch_bounds__(EF_WG) void k_ef_emit(ef_args a, ef_sensor s, const u64* __restrict__ table, const u64* __restrict__ meta,
+                                                   u64 expected, ef_out o)
+{
+    if (!ef_guard(meta, a.n, expected)) return;   // the same for every thread of the grid: nothing is written
+    if constexpr (SENSOR) {
+        if (meta[2 * (size_t)a.n + 2]) return;
+        ef_emit_sensor<LINEAR>(a, s, table, meta, o);
+    } else {
+        ef_emit_plain<LINEAR>(a, table, meta, o);
+    }
+}
+
 __global__ __launch_bounds__(EF_WG) void k_ef_unpack(size_t count, const u64* __restrict__ keys, const unsigned* __restrict__ vals,
                                                      const u64* __restrict__ meta, int n, u64 expected, int64_t t_first, int p_on,
                                                      int p_off, int16_t* __restrict__ ox, int16_t* __restrict__ oy,
                                                      int8_t* __restrict__ op, int64_t* __restrict__ ot)
 {
-    if (!ef_guard(meta, n, expected)) return;
+    if (!ef_guard(meta, n, expected) || meta[2 * (size_t)n + 2]) return;
     const size_t i = (size_t)blockIdx.x * EF_WG + threadIdx.x;
     if (i >= count) return;
     const unsigned v = vals[i];
@@ -317,6 +628,8 @@ struct ef_call {
     const int32_t* d_thr;
     const int32_t* d_ref_in;
     int ref_mode;
+    int mode;                         // the stamp mode (the count entry of the plain pair: unused)
+    const nsof_events_sensor* sensor; // nullptr: the plain generator
 };
 
 // Every refusal of the arguments both entries share; nothing launched.
@@ -342,14 +655,44 @@ int ef_check(nsof_ctx* ctx, const char* who, const ef_call& c)
         return nsof_set_error(ctx, NSOF_EINVAL, "%s: thresholds c_on = %d, c_off = %d: both must be >= 1", who, c.c_on, c.c_off);
     if (c.ref_mode < NSOF_EVENTS_REF_ZERO || c.ref_mode > NSOF_EVENTS_REF_GIVEN || (c.ref_mode == NSOF_EVENTS_REF_GIVEN) != (c.d_ref_in != nullptr))
         return nsof_set_error(ctx, NSOF_EINVAL, "%s: ref_mode %d with d_ref_in %s", who, c.ref_mode, c.d_ref_in ? "given" : "NULL");
+    if (c.mode != NSOF_EVENTS_T_FRAME && c.mode != NSOF_EVENTS_T_LINEAR)
+        return nsof_set_error(ctx, NSOF_EINVAL, "%s: timestamps_mode %d", who, c.mode);
+    if (const nsof_events_sensor* s = c.sensor) {
+        if (s->refractory_us < 0 || s->refractory_us >= (1ll << 31))
+            return nsof_set_error(ctx, NSOF_EINVAL, "%s: refractory_us = %lld is outside [0, 2^31)", who, (long long)s->refractory_us);
+        if (s->first_frame < 0 || s->first_frame > (1ll << 62) - c.n)
+            return nsof_set_error(ctx, NSOF_EINVAL, "%s: first_frame = %lld with %d frames: frame indices lie in [0, 2^62]", who,
+                                  (long long)s->first_frame, c.n);
+    }
     return NSOF_OK;
+}
+
+// The sensor arguments as the kernels take them (all zero for the plain generator, whose kernels leave them alone).
+ef_sensor ef_sensor_args(const ef_call& c)
+{
+    ef_sensor d{};
+    if (const nsof_events_sensor* s = c.sensor) {
+        d.refractory = s->refractory_us;
+        d.first_frame = s->first_frame;
+        d.k0 = (unsigned)s->seed;
+        d.k1 = (unsigned)(s->seed >> 32);
+        d.rate_on = s->rate_on_q;
+        d.rate_off = s->rate_off_q;
+        d.rate_plane = s->d_rate_plane;
+        d.t_ok_in = s->d_t_ok_in;
+        d.noise = s->d_rate_plane || s->rate_on_q || s->rate_off_q;
+        d.walk = s->refractory_us > 0 || s->d_t_ok_in;
+        d.linear = c.mode == NSOF_EVENTS_T_LINEAR;
+    }
+    return d;
 }
 
 // The workspace of a call, carved from ctx->tmp in one reservation.
 struct ef_plan {
     ef_args args;
     size_t n_wg;
-    u64 *table, *meta;        // [2n][n_wg]; [2n + 2]
+    ef_sensor sensor;
+    u64 *table, *meta;        // [2n][n_wg]; [2n + 3]
     u64 *keys_in, *keys_out;  // linear time stamps: [count] each
     unsigned *vals_in, *vals_out;
     void* sort_tmp;
@@ -379,7 +722,7 @@ int ef_count_pass(nsof_ctx* ctx, const ef_call& c, size_t sort_count, ef_plan* p
     const int npx = c.H * c.W;   // <= 32767^2 < 2^30
     pl->n_wg = (size_t)(npx + EF_WG - 1) / EF_WG;
     const size_t rows = 2 * (size_t)c.n;
-    const size_t o_meta = align_up(rows * pl->n_wg * sizeof(u64), 256), o_keys = o_meta + align_up((rows + 2) * sizeof(u64), 256);
+    const size_t o_meta = align_up(rows * pl->n_wg * sizeof(u64), 256), o_keys = o_meta + align_up((rows + 3) * sizeof(u64), 256);
     size_t bytes = o_keys;
     pl->sort_bytes = 0;
     size_t o_keys_out = 0, o_vals = 0, o_vals_out = 0, o_sort = 0;
@@ -417,13 +760,85 @@ int ef_count_pass(nsof_ctx* ctx, const ef_call& c, size_t sort_count, ef_plan* p
     a.ref_in = c.d_ref_in;
     a.ref_mode = c.ref_mode;
 
-    NSOF_HIP(ctx, hipMemsetAsync(pl->meta + rows + 1, 0, sizeof(u64), ctx->stream));   // the bad-threshold flag
-    hipLaunchKernelGGL(k_ef_count, dim3((unsigned)pl->n_wg), dim3(EF_WG), 0, ctx->stream, a, pl->table, pl->meta + rows + 1);
+    pl->sensor = ef_sensor_args(c);
+    NSOF_HIP(ctx, hipMemsetAsync(pl->meta + rows + 1, 0, 2 * sizeof(u64), ctx->stream));   // the bad-threshold and long-walk flags
+    if (c.sensor)
+        hipLaunchKernelGGL(k_ef_count<1>, dim3((unsigned)pl->n_wg), dim3(EF_WG), 0, ctx->stream, a, pl->sensor, pl->table, pl->meta + rows + 1);
+    else
+        hipLaunchKernelGGL(k_ef_count<0>, dim3((unsigned)pl->n_wg), dim3(EF_WG), 0, ctx->stream, a, pl->sensor, pl->table, pl->meta + rows + 1);
     NSOF_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_ef_scan, dim3((unsigned)rows), dim3(EF_WG), 0, ctx->stream, pl->table, pl->n_wg, pl->meta);
     NSOF_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_ef_scan, dim3(1), dim3(EF_WG), 0, ctx->stream, pl->meta, rows, pl->meta + rows);
     NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
+}
+
+// The count entry of both pairs.
+int ef_count_entry(nsof_ctx* ctx, const char* who, const ef_call& c, int64_t* frame_bounds_out)
+{
+    if (int rc = ef_check(ctx, who, c)) return rc;
+    if (!frame_bounds_out) return nsof_set_error(ctx, NSOF_EINVAL, "%s: null pointer (frame_bounds_out)", who);
+    ef_plan pl;
+    if (int rc = ef_count_pass(ctx, c, 0, &pl)) return rc;
+    const int n = c.n;
+    const size_t rows = 2 * (size_t)n;
+    std::vector<u64> meta(rows + 3);
+    NSOF_HIP(ctx, hipMemcpyAsync(meta.data(), pl.meta, meta.size() * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (meta[rows + 1])
+        return nsof_set_error(ctx, NSOF_EINVAL, "%s: the threshold plane holds a value < 1", who);
+    if (meta[rows + 2])
+        return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "%s: a pixel crosses 2^20 thresholds or more in one step, beyond the refractory walk "
+                              "of linear time stamps", who);
+    if (meta[rows] >= (1ull << 31))
+        return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "%s: %llu%s events, 2^31 or more", who, meta[rows], meta[rows] == ~0ull ? " or more" : "");
+    for (int k = 0; k < n; k++) frame_bounds_out[k] = (int64_t)meta[2 * (size_t)k];
+    frame_bounds_out[n] = (int64_t)meta[rows];
+    return NSOF_OK;
+}
+
+// The emit entry of both pairs.
+int ef_emit_entry(nsof_ctx* ctx, const char* who, const ef_call& c, const int64_t* frame_bounds, int p_on, int p_off, int64_t capacity,
+                  int16_t* d_x, int16_t* d_y, int8_t* d_p, int64_t* d_t, int32_t* d_ref_out, int64_t* d_t_ok_out)
+{
+    if (int rc = ef_check(ctx, who, c)) return rc;
+    const int n = c.n;
+    if (!frame_bounds) return nsof_set_error(ctx, NSOF_EINVAL, "%s: null pointer (frame_bounds)", who);
+    if (p_on < -128 || p_on > 127 || p_off < -128 || p_off > 127)
+        return nsof_set_error(ctx, NSOF_EINVAL, "%s: p_on = %d, p_off = %d do not fit an int8", who, p_on, p_off);
+    const int64_t total = frame_bounds[n];
+    if (total < 0 || total >= (1ll << 31))
+        return nsof_set_error(ctx, NSOF_EINVAL, "%s: frame_bounds[%d] = %lld is not a total the count entry gives", who, n, (long long)total);
+    if (capacity < total)
+        return nsof_set_error(ctx, NSOF_EINVAL, "%s: capacity %lld is below the %lld events of the stream", who, (long long)capacity,
+                              (long long)total);
+    if (total > 0 && (!d_x || !d_y || !d_p || !d_t))
+        return nsof_set_error(ctx, NSOF_EINVAL, "%s: null pointer (%s)", who, !d_x ? "d_x" : !d_y ? "d_y" : !d_p ? "d_p" : "d_t");
+    if (c.sensor && c.sensor->d_t_ok_in && !d_t_ok_out)
+        return nsof_set_error(ctx, NSOF_EINVAL, "%s: d_t_ok_in without d_t_ok_out: the run could not be continued", who);
+    const bool linear = c.mode == NSOF_EVENTS_T_LINEAR && total > 0;
+    ef_plan pl;
+    if (int rc = ef_count_pass(ctx, c, linear ? (size_t)total : 0, &pl)) return rc;
+    const ef_out o{p_on, p_off, d_x, d_y, d_p, d_t, pl.keys_in, pl.vals_in, d_ref_out, d_t_ok_out};
+    const dim3 grid((unsigned)pl.n_wg), block(EF_WG);
+    // (an empty linear stream has no pairs to sort, but the kernel still writes ref and t_ok)
+    if (c.sensor && c.mode == NSOF_EVENTS_T_LINEAR)
+        hipLaunchKernelGGL((k_ef_emit<1, 1>), grid, block, 0, ctx->stream, pl.args, pl.sensor, pl.table, pl.meta, (u64)total, o);
+    else if (c.sensor)
+        hipLaunchKernelGGL((k_ef_emit<0, 1>), grid, block, 0, ctx->stream, pl.args, pl.sensor, pl.table, pl.meta, (u64)total, o);
+    else if (linear)
+        hipLaunchKernelGGL((k_ef_emit<1, 0>), grid, block, 0, ctx->stream, pl.args, pl.sensor, pl.table, pl.meta, (u64)total, o);
+    else
+        hipLaunchKernelGGL((k_ef_emit<0, 0>), grid, block, 0, ctx->stream, pl.args, pl.sensor, pl.table, pl.meta, (u64)total, o);
+    NSOF_HIP(ctx, hipGetLastError());
+    if (linear) {
+        NSOF_HIP(ctx, rocprim::radix_sort_pairs(pl.sort_tmp, pl.sort_bytes, (const u64*)pl.keys_in, pl.keys_out, (const unsigned*)pl.vals_in,
+                                                pl.vals_out, (size_t)total, 0u, ef_key_bits(c), ctx->stream));
+        hipLaunchKernelGGL(k_ef_unpack, dim3((unsigned)(((size_t)total + EF_WG - 1) / EF_WG)), block, 0, ctx->stream, (size_t)total,
+                           pl.keys_out, pl.vals_out, pl.meta, n, (u64)total, c.times[0], p_on, p_off, d_x, d_y, d_p, d_t);
+        NSOF_HIP(ctx, hipGetLastError());
+    }
     return NSOF_OK;
 }
 
@@ -435,23 +850,9 @@ extern "C" int nsof_events_from_frames_count_dev(nsof_ctx* ctx, const uint8_t* d
                                                  int64_t* frame_bounds_out)
 {
     if (!ctx) return NSOF_EINVAL;
-    const char* who = "events_from_frames_count";
-    const ef_call c{d_frames, row_stride, frame_stride, n, height, width, times, lut, c_on, c_off, d_thr_plane, d_ref_in, ref_mode};
-    if (int rc = ef_check(ctx, who, c)) return rc;
-    if (!frame_bounds_out) return nsof_set_error(ctx, NSOF_EINVAL, "%s: null pointer (frame_bounds_out)", who);
-    ef_plan pl;
-    if (int rc = ef_count_pass(ctx, c, 0, &pl)) return rc;
-    const size_t rows = 2 * (size_t)n;
-    std::vector<u64> meta(rows + 2);
-    NSOF_HIP(ctx, hipMemcpyAsync(meta.data(), pl.meta, meta.size() * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (meta[rows + 1])
-        return nsof_set_error(ctx, NSOF_EINVAL, "%s: the threshold plane holds a value < 1", who);
-    if (meta[rows] >= (1ull << 31))
-        return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "%s: %llu%s events, 2^31 or more", who, meta[rows], meta[rows] == ~0ull ? " or more" : "");
-    for (int k = 0; k < n; k++) frame_bounds_out[k] = (int64_t)meta[2 * (size_t)k];
-    frame_bounds_out[n] = (int64_t)meta[rows];
-    return NSOF_OK;
+    const ef_call c{d_frames, row_stride, frame_stride, n, height, width, times, lut, c_on, c_off, d_thr_plane, d_ref_in, ref_mode,
+                    NSOF_EVENTS_T_FRAME, nullptr};
+    return ef_count_entry(ctx, "events_from_frames_count", c, frame_bounds_out);
 }
 
 extern "C" int nsof_events_from_frames_emit_dev(nsof_ctx* ctx, const uint8_t* d_frames, ptrdiff_t row_stride, ptrdiff_t frame_stride,
@@ -462,38 +863,41 @@ extern "C" int nsof_events_from_frames_emit_dev(nsof_ctx* ctx, const uint8_t* d_
                                                 int32_t* d_ref_out)
 {
     if (!ctx) return NSOF_EINVAL;
-    const char* who = "events_from_frames_emit";
-    const ef_call c{d_frames, row_stride, frame_stride, n, height, width, times, lut, c_on, c_off, d_thr_plane, d_ref_in, ref_mode};
-    if (int rc = ef_check(ctx, who, c)) return rc;
-    if (!frame_bounds) return nsof_set_error(ctx, NSOF_EINVAL, "%s: null pointer (frame_bounds)", who);
-    if (timestamps_mode != NSOF_EVENTS_T_FRAME && timestamps_mode != NSOF_EVENTS_T_LINEAR)
-        return nsof_set_error(ctx, NSOF_EINVAL, "%s: timestamps_mode %d", who, timestamps_mode);
-    if (p_on < -128 || p_on > 127 || p_off < -128 || p_off > 127)
-        return nsof_set_error(ctx, NSOF_EINVAL, "%s: p_on = %d, p_off = %d do not fit an int8", who, p_on, p_off);
-    const int64_t total = frame_bounds[n];
-    if (total < 0 || total >= (1ll << 31))
-        return nsof_set_error(ctx, NSOF_EINVAL, "%s: frame_bounds[%d] = %lld is not a total the count entry gives", who, n, (long long)total);
-    if (capacity < total)
-        return nsof_set_error(ctx, NSOF_EINVAL, "%s: capacity %lld is below the %lld events of the stream", who, (long long)capacity,
-                              (long long)total);
-    if (total > 0 && (!d_x || !d_y || !d_p || !d_t))
-        return nsof_set_error(ctx, NSOF_EINVAL, "%s: null pointer (%s)", who, !d_x ? "d_x" : !d_y ? "d_y" : !d_p ? "d_p" : "d_t");
-    const bool linear = timestamps_mode == NSOF_EVENTS_T_LINEAR && total > 0;
-    ef_plan pl;
-    if (int rc = ef_count_pass(ctx, c, linear ? (size_t)total : 0, &pl)) return rc;
-    if (linear)
-        hipLaunchKernelGGL(k_ef_emit<1>, dim3((unsigned)pl.n_wg), dim3(EF_WG), 0, ctx->stream, pl.args, pl.table, pl.meta, (u64)total, p_on,
-                           p_off, d_x, d_y, d_p, d_t, pl.keys_in, pl.vals_in, d_ref_out);
-    else
-        hipLaunchKernelGGL(k_ef_emit<0>, dim3((unsigned)pl.n_wg), dim3(EF_WG), 0, ctx->stream, pl.args, pl.table, pl.meta, (u64)total, p_on,
-                           p_off, d_x, d_y, d_p, d_t, pl.keys_in, pl.vals_in, d_ref_out);
-    NSOF_HIP(ctx, hipGetLastError());
-    if (linear) {
-        NSOF_HIP(ctx, rocprim::radix_sort_pairs(pl.sort_tmp, pl.sort_bytes, (const u64*)pl.keys_in, pl.keys_out, (const unsigned*)pl.vals_in,
-                                                pl.vals_out, (size_t)total, 0u, ef_key_bits(c), ctx->stream));
-        hipLaunchKernelGGL(k_ef_unpack, dim3((unsigned)(((size_t)total + EF_WG - 1) / EF_WG)), dim3(EF_WG), 0, ctx->stream, (size_t)total,
-                           pl.keys_out, pl.vals_out, pl.meta, n, (u64)total, times[0], p_on, p_off, d_x, d_y, d_p, d_t);
-        NSOF_HIP(ctx, hipGetLastError());
-    }
-    return NSOF_OK;
+    const ef_call c{d_frames, row_stride, frame_stride, n, height, width, times, lut, c_on, c_off, d_thr_plane, d_ref_in, ref_mode,
+                    timestamps_mode, nullptr};
+    return ef_emit_entry(ctx, "events_from_frames_emit", c, frame_bounds, p_on, p_off, capacity, d_x, d_y, d_p, d_t, d_ref_out, nullptr);
+}
+
+extern "C" int nsof_events_from_frames_sensor_count_dev(nsof_ctx* ctx, const uint8_t* d_frames, ptrdiff_t row_stride,
+                                                        ptrdiff_t frame_stride, int n, int height, int width, const int64_t* times,
+                                                        const int32_t* lut, int c_on, int c_off, const int32_t* d_thr_plane,
+                                                        const int32_t* d_ref_in, int ref_mode, int timestamps_mode,
+                                                        const nsof_events_sensor* sensor, int64_t* frame_bounds_out)
+{
+    if (!ctx) return NSOF_EINVAL;
+    const ef_call c{d_frames, row_stride, frame_stride, n, height, width, times, lut, c_on, c_off, d_thr_plane, d_ref_in, ref_mode,
+                    timestamps_mode, sensor};
+    return ef_count_entry(ctx, "events_from_frames_sensor_count", c, frame_bounds_out);
+}
+
+extern "C" int nsof_events_from_frames_sensor_emit_dev(nsof_ctx* ctx, const uint8_t* d_frames, ptrdiff_t row_stride,
+                                                       ptrdiff_t frame_stride, int n, int height, int width, const int64_t* times,
+                                                       const int32_t* lut, int c_on, int c_off, const int32_t* d_thr_plane,
+                                                       const int32_t* d_ref_in, int ref_mode, const int64_t* frame_bounds,
+                                                       int timestamps_mode, int p_on, int p_off, int64_t capacity, int16_t* d_x,
+                                                       int16_t* d_y, int8_t* d_p, int64_t* d_t, int32_t* d_ref_out,
+                                                       const nsof_events_sensor* sensor, int64_t* d_t_ok_out)
+{
+    if (!ctx) return NSOF_EINVAL;
+    const ef_call c{d_frames, row_stride, frame_stride, n, height, width, times, lut, c_on, c_off, d_thr_plane, d_ref_in, ref_mode,
+                    timestamps_mode, sensor};
+    return ef_emit_entry(ctx, "events_from_frames_sensor_emit", c, frame_bounds, p_on, p_off, capacity, d_x, d_y, d_p, d_t, d_ref_out,
+                         d_t_ok_out);
+}
+
+extern "C" void nsof_events_noise_draw(uint64_t seed, uint32_t pixel, int64_t frame, uint32_t* out)
+{
+    unsigned c[4] = {pixel, (unsigned)(uint64_t)frame, (unsigned)((uint64_t)frame >> 32), EF_NOISE_WORD};
+    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+    for (int i = 0; i < 4; i++) out[i] = c[i];
 }

@@ -45,6 +45,13 @@ class AccumParams(C.Structure):
                                   "Roff", "wini", "dt")] + [("refractory_us", _i64)]
 
 
+class EventsSensor(C.Structure):
+    """``nsof_events_sensor`` of include/nsof.h: the refractory time, the noise seed and rates, the absolute index of the
+    call's first frame, the per-pixel rate plane and the incoming ``t_ok`` plane (device pointers or NULL)."""
+    _fields_ = [("refractory_us", C.c_int64), ("seed", C.c_uint64), ("first_frame", C.c_int64), ("rate_on_q", C.c_uint32),
+                ("rate_off_q", C.c_uint32), ("d_rate_plane", C.c_void_p), ("d_t_ok_in", C.c_void_p)]
+
+
 class AccumC2c(C.Structure):
     """``nsof_accum_c2c`` of include/nsof.h: the seed and the two spreads of the trial run's cycle-to-cycle write noise."""
     _fields_ = [("seed", C.c_uint64), ("sigma_on", _f), ("sigma_off", _f)]
@@ -208,6 +215,13 @@ SIGNATURES = {
     "nsof_events_from_frames_count_dev": (_i, [_vp, _vp, _pd, _pd, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
     "nsof_events_from_frames_emit_dev": (_i, [_vp, _vp, _pd, _pd, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i64,
                                               _vp, _vp, _vp, _vp, _vp]),
+    # the sensor pair: count takes timestamps_mode and sensor before frame_bounds; emit ends in sensor, t_ok_out
+    "nsof_events_from_frames_sensor_count_dev": (_i, [_vp, _vp, _pd, _pd, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i,
+                                                      C.POINTER(EventsSensor), _vp]),
+    "nsof_events_from_frames_sensor_emit_dev": (_i, [_vp, _vp, _pd, _pd, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i,
+                                                     _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(EventsSensor), _vp]),
+    # seed, pixel, frame, out [4]
+    "nsof_events_noise_draw": (None, [C.c_uint64, C.c_uint32, _i64, _vp]),
 }
 
 _lib = None

@@ -6,7 +6,9 @@ the ``/CD/events`` schema, which every event entry of the package takes.
 ``events_from_frames_dev`` is the generator, ``events_from_video_dev`` the same behind ``gray_u8_dev``;
 ``render_box_frames`` draws the frames of the reference's ``generate_synthetic_events`` (event_mem_sim.py:109-158), of
 which the generator with a threshold of one grey level (any in (1/2, 1]), ``ref=None`` and ``timestamps="frame"`` gives
-exactly the events.
+exactly the events.  ``refractory_us`` / ``noise`` / ``t_ok`` / ``first_frame`` add a per-pixel refractory period and
+background-activity noise events (``nsof_events_from_frames_sensor_*_dev``); ``events_noise_draw``
+gives the noise generator's words on the host.
 """
 import ctypes as C
 
@@ -116,6 +118,93 @@ def _threshold_plane(who, threshold_maps, h, w):
     return np.ascontiguousarray(units.astype(np.int32))
 
 
+NOISE_KEYS = ("seed", "rate_hz", "rate_on_hz", "rate_off_hz", "rate_maps")
+
+
+def _rate_units(who, name, v):
+    """A noise rate in Hz as the library holds it: round(rate * 2^32 / 10^6), which must lie in [0, 2^32)."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+        raise NsofValueError(f"{who}: noise[{name!r}] = {v!r} is not a finite number", _lib.NSOF_EINVAL)
+    q = int(round(float(v) * 4294967296.0 / 1e6))   # the power of two is exact: one rounding
+    if not 0 <= q < 1 << 32:
+        raise NsofValueError(f"{who}: noise[{name!r}] = {v!r} Hz is {q} units of 2^-32 per microsecond; 0 .. 2^32 - 1 expected",
+                             _lib.NSOF_EINVAL)
+    return q
+
+
+def _rate_plane(who, rate_maps, h, w):
+    """``noise['rate_maps']`` (Hz, ``[H][W][2]``: ON, OFF per pixel) as a host uint32 plane of rate units."""
+    import torch
+    m = rate_maps.detach().cpu().numpy() if isinstance(rate_maps, torch.Tensor) else np.asarray(rate_maps)
+    if m.dtype.kind not in "iuf" or m.shape != (h, w, 2):
+        raise NsofValueError(f"{who}: noise['rate_maps'] must be numbers [{h}][{w}][2] (got {m.dtype} {m.shape})", _lib.NSOF_ESHAPE)
+    m = m.astype(np.float64)
+    if not np.isfinite(m).all():
+        raise NsofValueError(f"{who}: noise['rate_maps'] holds a value that is not finite", _lib.NSOF_EINVAL)
+    q = np.rint(m * 4294967296.0 / 1e6)
+    if q.min() < 0 or q.max() >= 1 << 32:
+        y, x, c = (int(v) for v in np.argwhere((q < 0) | (q >= 1 << 32))[0])
+        raise NsofValueError(f"{who}: noise['rate_maps'][{y}][{x}][{c}] = {float(m[y, x, c])!r} Hz is {int(q[y, x, c])} units of 2^-32 per "
+                             "microsecond; 0 .. 2^32 - 1 expected", _lib.NSOF_EINVAL)
+    return np.ascontiguousarray(q.astype(np.uint32))
+
+
+def _sensor_args(who, n, h, w, refractory_us, noise, t_ok, first_frame):
+    """The four sensor arguments checked on the host -> ``None`` when all are at their defaults (the plain generator),
+    else a dict: ``refractory_us``, ``seed``, ``first_frame``, ``rate_on_q``, ``rate_off_q``, ``plane`` (host uint32
+    ``[H][W][2]`` or ``None``) and ``t_ok`` (the tensor or ``None``; its device is checked with the frames')."""
+    import torch
+    refractory_us = _whole(who, "refractory_us", refractory_us)
+    if not 0 <= refractory_us < 1 << 31:
+        raise NsofValueError(f"{who}: refractory_us = {refractory_us} must be in [0, 2^31)", _lib.NSOF_EINVAL)
+    first_frame = _whole(who, "first_frame", first_frame)
+    if first_frame < 0 or first_frame + n > 1 << 62:
+        raise NsofValueError(f"{who}: first_frame = {first_frame} with {n} frames: frame indices lie in [0, 2^62]", _lib.NSOF_EINVAL)
+    out = dict(refractory_us=refractory_us, seed=0, first_frame=first_frame, rate_on_q=0, rate_off_q=0, plane=None, t_ok=None)
+    if noise is not None:
+        if not isinstance(noise, dict) or "seed" not in noise or any(k not in NOISE_KEYS for k in noise):
+            raise NsofValueError(f"{who}: noise = {noise!r}; a dict with 'seed' and rates ('rate_hz', or 'rate_on_hz' / 'rate_off_hz', or "
+                                 "'rate_maps') expected", _lib.NSOF_EINVAL)
+        seed = noise["seed"]
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+            raise NsofValueError(f"{who}: noise['seed'] = {seed!r} is not a whole number in [0, 2^64)", _lib.NSOF_EINVAL)
+        out["seed"] = int(seed)
+        ways = [k for k in ("rate_hz", "rate_maps") if k in noise] + (["rate_on_hz / rate_off_hz"] if "rate_on_hz" in noise or
+                                                                      "rate_off_hz" in noise else [])
+        if len(ways) != 1:
+            raise NsofValueError(f"{who}: noise gives its rates {len(ways)} ways ({', '.join(ways) or 'none'}); one of 'rate_hz', "
+                                 "'rate_on_hz' / 'rate_off_hz', 'rate_maps' expected", _lib.NSOF_EINVAL)
+        if "rate_maps" in noise:
+            out["plane"] = _rate_plane(who, noise["rate_maps"], h, w)
+        elif "rate_hz" in noise:
+            out["rate_on_q"] = out["rate_off_q"] = _rate_units(who, "rate_hz", noise["rate_hz"])
+        else:
+            out["rate_on_q"] = _rate_units(who, "rate_on_hz", noise.get("rate_on_hz", 0))
+            out["rate_off_q"] = _rate_units(who, "rate_off_hz", noise.get("rate_off_hz", 0))
+    if t_ok is not None:
+        if not isinstance(t_ok, torch.Tensor) or t_ok.dtype != torch.int64 or tuple(t_ok.shape) != (h, w) or not t_ok.is_contiguous():
+            raise NsofValueError(f"{who}: t_ok must be a contiguous int64 tensor [{h}][{w}] (got {getattr(t_ok, 'dtype', type(t_ok))} "
+                                 f"{tuple(getattr(t_ok, 'shape', ()))})", _lib.NSOF_ESHAPE)
+        out["t_ok"] = t_ok
+    if refractory_us == 0 and noise is None and t_ok is None and first_frame == 0:
+        return None
+    return out
+
+
+def events_noise_draw(seed, pixel, frame):
+    """The four 32-bit words ``c0..c3`` of the noise generator for (``seed``, ``pixel`` = y * W + x, absolute ``frame``
+    index), uint32 ``[4]``: Philox4x32-10 on the counter ``(pixel, frame & 0xffffffff, frame >> 32, 0x4E534546)`` under the
+    key ``(seed & 0xffffffff, seed >> 32)``, computed by the library on the host (``nsof_events_noise_draw``) -- the bits
+    the kernels use.  ``c0`` / ``c1`` decide whether the ON / OFF noise event of the interval before the frame exists,
+    ``c2`` / ``c3`` place it in the interval."""
+    for name, v, top in (("seed", seed, 1 << 64), ("pixel", pixel, 1 << 32), ("frame", frame, (1 << 62) + 1)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < top:
+            raise NsofValueError(f"events_noise_draw: {name} = {v!r} is not a whole number in [0, {top})", _lib.NSOF_EINVAL)
+    out = np.empty(4, np.uint32)
+    _lib.load().nsof_events_noise_draw(int(seed), int(pixel), int(frame), out.ctypes.data)
+    return out
+
+
 def _polarity_arg(who, name, v):
     v = _whole(who, name, v)
     if not -128 <= v <= 127:
@@ -124,7 +213,8 @@ def _polarity_arg(who, name, v):
 
 
 def events_from_frames_dev(frames, times_us=None, *, frame_us=None, threshold=10.0, threshold_off=None, threshold_maps=None,
-                           response=None, ref=None, timestamps="linear", p_on=1, p_off=-1, ctx=None):
+                           response=None, ref=None, timestamps="linear", p_on=1, p_off=-1, refractory_us=0, noise=None, t_ok=None,
+                           first_frame=0, ctx=None):
     """A frame sequence in HBM as an event stream in HBM (``nsof_events_from_frames_*_dev``).  ``frames``: uint8 CUDA
     tensor ``[n][H][W]``, frame and row strides free, pixels of a row dense.  Times in microseconds: ``times_us`` (``n``
     whole numbers, strictly increasing by less than 2^31) or ``frame_us`` (frame ``k`` at ``k * frame_us``).  With
@@ -152,7 +242,27 @@ def events_from_frames_dev(frames, times_us=None, *, frame_us=None, threshold=10
     to return the bounds; the emit pass is then queued and the call returns.  Until ``ctx.synchronize()`` the caller must
     neither read the result elsewhere nor free or overwrite ``frames`` and ``ref`` (torch's caching allocator reuses a freed
     block on torch's stream at once).  The one temporary of the call's own that the queued kernels read, the uploaded
-    ``threshold_maps`` plane, is covered here: with ``threshold_maps`` the call ends in ``ctx.synchronize()``."""
+    ``threshold_maps`` plane, is covered here: with ``threshold_maps`` the call ends in ``ctx.synchronize()``.
+
+    The sensor model (``nsof_events_from_frames_sensor_*_dev``; all four arguments at their defaults: the plain generator
+    and exactly the result above).  Every pixel also keeps ``t_ok``, the earliest time at which it may fire again.
+    ``refractory_us`` (whole, [0, 2^31)): the candidates of a pixel and frame are taken in the order (t, signal before ON
+    noise before OFF noise); one is emitted iff ``t >= t_ok``, and then ``t_ok = t + refractory_us``.  ``r`` moves by every
+    crossing whether or not its event survives, so ``ref`` does not depend on these arguments.  ``noise``: a dict with
+    ``seed`` (whole, [0, 2^64)) and the background-activity rates in Hz, given one way: ``rate_hz`` (both polarities),
+    ``rate_on_hz`` / ``rate_off_hz``, or ``rate_maps`` (``[H][W][2]``, array or tensor, checked and converted on the host
+    like ``threshold_maps``: hot pixels); a rate is held as ``round(rate * 2^32 / 10^6)``, which must be below 2^32.  In the
+    interval before every frame but the call's first a pixel draws one Philox block (``events_noise_draw``): an ON noise
+    event exists iff ``c0 < min(2^32 - 1, rate_on_q * (T[k] - T[k-1]))``, stamped ``T[k]`` (``"frame"``) or ``T[k-1] + ((c2 *
+    (T[k] - T[k-1])) >> 32)`` (``"linear"``); OFF likewise with ``c1`` and ``c3``.  A rate above one event per interval
+    saturates at one noise event per pixel, polarity and interval; noise does not move ``r``; a noise event comes after
+    the signal events of its pixel, frame and polarity.  ``first_frame`` is the absolute index of ``frames[0]`` (the noise
+    counter), ``t_ok`` the ``t_ok`` of a previous result: ``frames[0:k+1]`` with ``first_frame=f`` and then ``frames[k:n]``
+    with ``first_frame=f+k`` and the first call's ``ref`` and ``t_ok`` give the one-shot stream, ``ref`` and ``t_ok`` bit for
+    bit.  The result then also carries ``t_ok`` (int64 CUDA ``[H][W]``; a pixel that never fired holds the smallest int64).
+    With ``"linear"`` stamps and a refractory time or a ``t_ok`` the crossings of a step are walked one by one, and a pixel
+    that crosses 2^20 thresholds or more in one step is refused (``NSOF_EUNSUPPORTED``).  With ``rate_maps`` the call ends
+    in ``ctx.synchronize()``, like ``threshold_maps``."""
     import torch
 
     from .context import default_context, dev_ptr
@@ -173,6 +283,7 @@ def events_from_frames_dev(frames, times_us=None, *, frame_us=None, threshold=10
     if timestamps not in _TIMESTAMPS:
         raise NsofValueError(f"{who}: timestamps = {timestamps!r}; 'frame' or 'linear' expected", _lib.NSOF_EINVAL)
     p_on, p_off = _polarity_arg(who, "p_on", p_on), _polarity_arg(who, "p_off", p_off)
+    sensor = _sensor_args(who, n, h, w, refractory_us, noise, t_ok, first_frame)
     if ref is None or (isinstance(ref, str) and ref == "first"):
         ref_mode, ref_in = (_lib.EVENTS_REF_ZERO if ref is None else _lib.EVENTS_REF_FIRST), None
     elif isinstance(ref, torch.Tensor):
@@ -184,14 +295,20 @@ def events_from_frames_dev(frames, times_us=None, *, frame_us=None, threshold=10
         raise NsofValueError(f"{who}: ref = {ref!r}; None, 'first' or the ref of a previous result expected", _lib.NSOF_EINVAL)
     if not frames.is_cuda or (ref_in is not None and ref_in.device != frames.device):
         raise NsofValueError(f"{who}: frames (and ref) must be CUDA tensors on one device", _lib.NSOF_EINVAL)
+    if sensor is not None and sensor["t_ok"] is not None and sensor["t_ok"].device != frames.device:
+        raise NsofValueError(f"{who}: t_ok must be a CUDA tensor on the frames' device", _lib.NSOF_EINVAL)
 
     ctx = ctx or default_context()
     dev = frames.device
     d_plane = None if plane is None else torch.from_numpy(plane).to(dev)
     bounds = np.empty(n + 1, np.int64)
     common = (dev_ptr(frames), int(frames.stride(1)), int(frames.stride(0)), n, h, w, times.ctypes.data_as(C.c_void_p),
-              lut.ctypes.data_as(C.c_void_p), c_on, c_off, dev_ptr(d_plane), dev_ptr(ref_in), ref_mode,
-              bounds.ctypes.data_as(C.c_void_p))
+              lut.ctypes.data_as(C.c_void_p), c_on, c_off, dev_ptr(d_plane), dev_ptr(ref_in), ref_mode)
+    p_bounds = bounds.ctypes.data_as(C.c_void_p)
+    if sensor is not None:
+        return _sensor_call(ctx, who, sensor, common, p_bounds, bounds, _TIMESTAMPS[timestamps], p_on, p_off, n, h, w, dev,
+                            d_plane is not None)
+    common += (p_bounds,)
     torch.cuda.synchronize(dev)   # the frames, ref and the plane's upload are torch's work; the library reads them on the context's stream
     try:
         ctx.check(ctx._lib.nsof_events_from_frames_count_dev(ctx.ptr, *common), who)
@@ -208,6 +325,33 @@ def events_from_frames_dev(frames, times_us=None, *, frame_us=None, threshold=10
             # on torch's stream at once: the plane may go only when the context's stream has drained
             ctx.synchronize()
     return dict(x=x, y=y, p=p, t=t, frame_bounds=bounds, ref=ref_out)
+
+
+def _sensor_call(ctx, who, sensor, common, p_bounds, bounds, mode, p_on, p_off, n, h, w, dev, has_plane):
+    """The count and emit entries of the sensor pair for ``events_from_frames_dev``: the same two steps as the plain
+    pair, with the stamp mode and the sensor struct in both calls and ``t_ok`` in the result."""
+    import torch
+
+    from .context import dev_ptr
+    d_rates = None if sensor["plane"] is None else torch.from_numpy(sensor["plane"].view(np.int32)).to(dev)   # the bits of the uint32 plane
+    st = _lib.EventsSensor(sensor["refractory_us"], sensor["seed"], sensor["first_frame"], sensor["rate_on_q"], sensor["rate_off_q"],
+                           dev_ptr(d_rates), dev_ptr(sensor["t_ok"]))
+    torch.cuda.synchronize(dev)   # the frames, ref, t_ok and the planes' uploads are torch's work
+    try:
+        ctx.check(ctx._lib.nsof_events_from_frames_sensor_count_dev(ctx.ptr, *common, mode, C.byref(st), p_bounds), who)
+        total = int(bounds[n])
+        x, y = (torch.empty(total, dtype=torch.int16, device=dev) for _ in range(2))
+        p = torch.empty(total, dtype=torch.int8, device=dev)
+        t = torch.empty(total, dtype=torch.int64, device=dev)
+        ref_out = torch.empty((h, w), dtype=torch.int32, device=dev)
+        t_ok_out = torch.empty((h, w), dtype=torch.int64, device=dev)
+        ctx.check(ctx._lib.nsof_events_from_frames_sensor_emit_dev(ctx.ptr, *common, p_bounds, mode, p_on, p_off, total, dev_ptr(x),
+                                                                   dev_ptr(y), dev_ptr(p), dev_ptr(t), dev_ptr(ref_out), C.byref(st),
+                                                                   dev_ptr(t_ok_out)), who)
+    finally:
+        if has_plane or d_rates is not None:
+            ctx.synchronize()   # the queued kernels read the uploaded planes (see events_from_frames_dev)
+    return dict(x=x, y=y, p=p, t=t, frame_bounds=bounds, ref=ref_out, t_ok=t_ok_out)
 
 
 def events_from_video_dev(frames_bgr, times_us=None, *, code="BGR2GRAY", ctx=None, **kwargs):

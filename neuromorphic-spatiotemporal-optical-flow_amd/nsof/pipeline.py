@@ -274,17 +274,26 @@ def events_to_flow_sequence(x, y, p, t, sensor_hw, params=None, slice_us=1000, a
 
 
 def video_to_flow_sequence(frames, times_us=None, *, frame_us=None, threshold=10.0, threshold_off=None, threshold_maps=None,
-                           response=None, ref=None, timestamps="linear", p_on=1, p_off=-1, ctx=None, **accumulator_args):
+                           response=None, ref=None, timestamps="linear", p_on=1, p_off=-1, sensor=None, ctx=None, **accumulator_args):
     """A grey video in HBM through the event pipeline: ``events_from_frames_dev(frames, ...)`` (the arguments up to
     ``p_off``) turns the frames into an event stream in HBM, one copy brings it to the host (the accumulator's entries
     stage host event arrays), and ``events_to_flow_sequence(x, y, p, t, (H, W), **accumulator_args)`` accumulates it and
     takes the flow between its surface frames.  Returns ``(surface frames uint8 [m][H][W], flows float32 [m-1][H][W][2],
-    events)``, ``events`` the generator's result dict (``x, y, p, t`` CUDA tensors, ``frame_bounds``, ``ref``)."""
+    events)``, ``events`` the generator's result dict (``x, y, p, t`` CUDA tensors, ``frame_bounds``, ``ref``).  ``sensor``: a
+    dict of the generator's sensor arguments (``refractory_us``, ``noise``, ``t_ok``, ``first_frame``), forwarded to it --
+    apart from ``accumulator_args``, where ``refractory_us`` is the accumulator's; ``events`` then carries ``t_ok`` too."""
+    from . import _lib
     from .context import default_context
-    ctx = ctx or default_context()
+    from .errors import NsofValueError
+    sensor = {} if sensor is None else sensor
+    if not isinstance(sensor, dict) or any(k not in ("refractory_us", "noise", "t_ok", "first_frame") for k in sensor):
+        raise NsofValueError(f"video_to_flow_sequence: sensor = {sensor!r}; a dict of refractory_us, noise, t_ok, first_frame expected",
+                             _lib.NSOF_EINVAL)
+    # (the generator refuses its arguments before it asks for a context; the default one is process-wide)
     ev = events_from_frames_dev(frames, times_us, frame_us=frame_us, threshold=threshold, threshold_off=threshold_off,
                                 threshold_maps=threshold_maps, response=response, ref=ref, timestamps=timestamps, p_on=p_on,
-                                p_off=p_off, ctx=ctx)
+                                p_off=p_off, ctx=ctx, **sensor)
+    ctx = ctx or default_context()
     ctx.synchronize()
     x, y, p, t = (ev[k].cpu().numpy() for k in "xypt")
     surfaces, flows = events_to_flow_sequence(x, y, p, t, (int(frames.shape[1]), int(frames.shape[2])), ctx=ctx, **accumulator_args)
