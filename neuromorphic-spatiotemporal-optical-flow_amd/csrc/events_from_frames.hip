@@ -28,6 +28,12 @@
 // time or a given t_ok plane -- the pixel's candidates are walked in time order against t_ok, which lives in a register
 // like r.  The count pass runs the same walk as the emit pass, so its counts depend on the stamp mode.  The plain
 // instantiations hold none of this.
+//
+// What the two passes must agree on exists once: ef_frame builds a frame's candidates (the level step, and with SENSOR the
+// times and the noise draw) for k_ef_count and for the sensor emit body, ef_survivors counts them (without SENSOR: the
+// candidates themselves), ef_stamp is the linear stamp of a crossing, ef_store writes an event, ef_bases forms a batch's row
+// bases and ef_guard is the one test under which the emit and unpack kernels write.  The emit pass keeps two bodies,
+// ef_emit_plain and ef_emit_sensor: folded into one, the plain linear kernel went from 64 to 90 VGPRs.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "accum_c2c.h"
@@ -184,6 +190,39 @@ struct ef_cands {
     unsigned off_on, off_off; // noise: offsets from t_prev, EF_NONE for none
 };
 
+// The linear stamp of the crossing of `level` on the way from a_level at t_prev to lev at t_k (no way at all: t_k).
+__device__ __forceinline__ int64_t ef_stamp(long long level, int a_level, int lev, int64_t t_prev, int64_t t_k)
+{
+    const long long span = (long long)lev - (long long)a_level, off = level - (long long)a_level;
+    const u64 den = (u64)(span < 0 ? -span : span);
+    return den ? t_prev + (int64_t)(((u64)(off < 0 ? -off : off) * (u64)(t_k - t_prev)) / den) : t_k;
+}
+
+// The candidates of frame k from its level: r and prev_level (L[k - 1]) move on.  A frame past the last has none and moves
+// nothing.  Without SENSOR there are no times and no noise: the crossings alone.
+template <int SENSOR>
+__device__ __forceinline__ void ef_frame(const ef_args& a, const ef_sensor& s, ef_px& q, const ef_spx& p, int k, int lev, bool linear,
+                                         int& prev_level, ef_cands& c)
+{
+    c.m = 0;
+    c.on = false;
+    c.same = true;
+    c.off_on = c.off_off = EF_NONE;
+    if (k >= a.n) return;
+    c.lev = lev;
+    c.a_level = prev_level;
+    prev_level = lev;
+    c.r0 = q.r;
+    c.m = ef_step(q.r, lev, q.c_on, q.c_off, c.on);
+    c.c = c.on ? q.c_on : q.c_off;
+    if constexpr (SENSOR) {
+        c.t_k = a.times[k];
+        c.t_prev = a.times[max(k - 1, 0)];
+        c.same = !linear || k == 0;
+        if (s.noise && k > 0) ef_noise(s, q, p, k, (u64)(c.t_k - c.t_prev), c.off_on, c.off_off);
+    }
+}
+
 // The refractory walk of one frame: the candidates in the order (t, signal before ON noise before OFF noise), a candidate
 // emitted iff t >= t_ok, and then t_ok = t + refractory.  emit(kind, count, t): kind 0 = `count` signal crossings in a row
 // (the next ones of the pixel's order), 1 = the ON noise event, 2 = the OFF noise event.  With one stamp for all the walk
@@ -215,17 +254,10 @@ __device__ __forceinline__ void ef_walk(const ef_cands& c, long long refractory,
         kn0 = 2;
         kn1 = 1;
     }
-    const u64 dt = (u64)(c.t_k - c.t_prev);
-    const long long span = (long long)c.lev - (long long)c.a_level;
-    const u64 den = (u64)(span < 0 ? -span : span);
     long long level = c.r0;
     for (unsigned i = 0; i < c.m; i++) {
         level += c.on ? c.c : -c.c;
-        int64_t t = c.t_k;
-        if (den) {
-            const long long off = level - (long long)c.a_level;
-            t = c.t_prev + (int64_t)(((u64)(off < 0 ? -off : off) * dt) / den);
-        }
+        const int64_t t = ef_stamp(level, c.a_level, c.lev, c.t_prev, c.t_k);
         while (nn && tn0 < t) {   // noise strictly before this crossing: a signal crossing goes first on a tie
             if (tn0 >= t_ok) {
                 t_ok = (int64_t)((u64)tn0 + (u64)refractory);
@@ -251,13 +283,13 @@ __device__ __forceinline__ void ef_walk(const ef_cands& c, long long refractory,
     }
 }
 
-// The events of a pixel at frame k that survive, per polarity; t_ok moves on.  Without a walk (nothing can be dropped)
-// they are the candidates and t_ok is left alone.
-template <int LINEAR>
+// The events of a pixel at frame k that survive, per polarity; t_ok moves on.  Without a walk (nothing can be dropped:
+// always so without SENSOR) they are the candidates and t_ok is left alone.
+template <int LINEAR, int SENSOR>
 __device__ __forceinline__ void ef_survivors(const ef_sensor& s, const ef_cands& c, int64_t& t_ok, unsigned& n_on, unsigned& n_off)
 {
     n_on = n_off = 0;
-    if (!s.walk) {
+    if (!SENSOR || !s.walk) {
         n_on = (c.on ? c.m : 0u) + (c.off_on != EF_NONE);
         n_off = (c.on ? 0u : c.m) + (c.off_off != EF_NONE);
         return;
@@ -278,7 +310,7 @@ __global__ __launch_bounds__(EF_WG) void k_ef_count(ef_args a, ef_sensor s, u64*
     ef_px q = ef_init(a, sh_lut);
     if (q.in && (q.c_on < 1 || q.c_off < 1)) *bad = 1;
     ef_spx sp{};
-    int prev_level = 0;   // L[k - 1] (SENSOR)
+    int prev_level = 0;   // L[k - 1]
     if (SENSOR) sp = ef_sensor_init(s, q);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t n_wg = gridDim.x;
@@ -288,41 +320,17 @@ __global__ __launch_bounds__(EF_WG) void k_ef_count(ef_args a, ef_sensor s, u64*
         ef_load(a, q, k0, f);
 #pragma unroll
         for (int j = 0; j < EF_BATCH; j++) {
-            bool on = false;
-            unsigned m = 0;
-            unsigned n_on, n_off;   // the pixel's events of the frame
-            if (!SENSOR) {
-                if (k0 + j < a.n) m = ef_step(q.r, sh_lut[f[j]], q.c_on, q.c_off, on);
-                if (!q.in) m = 0;
-                n_on = on ? m : 0u;
-                n_off = on ? 0u : m;
-            } else {
-                const int k = k0 + j;
-                n_on = n_off = 0;
-                if (k < a.n) {
-                    ef_cands c;
-                    c.lev = sh_lut[f[j]];
-                    c.a_level = prev_level;
-                    prev_level = c.lev;
-                    c.r0 = q.r;
-                    c.m = ef_step(q.r, c.lev, q.c_on, q.c_off, c.on);
-                    c.c = c.on ? q.c_on : q.c_off;
-                    c.t_k = a.times[k];
-                    c.t_prev = a.times[max(k - 1, 0)];
-                    c.same = !s.linear || k == 0;
-                    c.off_on = c.off_off = EF_NONE;
-                    if (s.noise && k > 0) ef_noise(s, q, sp, k, (u64)(c.t_k - c.t_prev), c.off_on, c.off_off);
-                    if (s.walk && !c.same && c.m >= EF_WALK_MAX) {
-                        if (q.in) bad[1] = 1;
-                        c.m = 0;   // the call is refused: no long walk for nothing
-                    }
-                    ef_survivors<1>(s, c, sp.t_ok, n_on, n_off);
-                    if (!q.in) n_on = n_off = 0;
-                }
-                m = n_on | n_off;
+            ef_cands c;
+            ef_frame<SENSOR>(a, s, q, sp, k0 + j, sh_lut[f[j]], s.linear, prev_level, c);
+            if (SENSOR && s.walk && !c.same && c.m >= EF_WALK_MAX) {
+                if (q.in) bad[1] = 1;
+                c.m = 0;   // the call is refused: no long walk for nothing
             }
+            unsigned n_on, n_off;   // the pixel's events of the frame
+            ef_survivors<1, SENSOR>(s, c, sp.t_ok, n_on, n_off);   // (the stamp mode of the count pass is c.same)
+            if (!q.in) n_on = n_off = 0;
             u64 s_on, s_off;
-            if (!__any(m >> 24)) {   // every lane below 2^24 (any frame of the linear table): the wave's sums fit 32 bits
+            if (!__any((n_on | n_off) >> 24)) {   // every lane below 2^24 (any frame of the linear table): the wave's sums fit 32 bits
                 s_on = ef_wave_last(ef_wave_scan(n_on));
                 s_off = ef_wave_last(ef_wave_scan(n_off));
             } else {
@@ -382,8 +390,13 @@ __global__ __launch_bounds__(EF_WG) void k_ef_scan(u64* __restrict__ data, size_
 }
 
 // meta: [0 .. 2n) the bases of the (frame, polarity) rows, [2n] the total, [2n + 1] the bad-threshold flag, [2n + 2] the
-// long-walk flag (which the plain kernels never raise).
-__device__ __forceinline__ bool ef_guard(const u64* meta, int n, u64 expected) { return meta[2 * (size_t)n] == expected && meta[2 * (size_t)n + 1] == 0; }
+// long-walk flag (which the plain kernels never raise).  The emit and unpack kernels write only under the guard: the total
+// is the one the caller sized the outputs for and no flag is up.  The same for every thread of the grid.
+__device__ __forceinline__ bool ef_guard(const u64* meta, int n, u64 expected)
+{
+    const u64* m = meta + 2 * (size_t)n;
+    return m[0] == expected && m[1] == 0 && m[2] == 0;
+}
 
 // Where the emit pass writes.
 struct ef_out {
@@ -397,23 +410,42 @@ struct ef_out {
     int64_t* t_ok;            // SENSOR
 };
 
+// Event `at` of the emitted order: the pixel's, of polarity `on` (pv: its byte, chosen by the caller -- a select between
+// o.p_on and o.p_off in here put both on the stack), stamped t.
+template <int LINEAR>
+__device__ __forceinline__ void ef_store(const ef_out& o, size_t at, const ef_px& q, bool on, int8_t pv, int64_t t, int64_t t_first)
+{
+    if (LINEAR) {
+        o.keys[at] = (u64)(t - t_first);
+        o.vals[at] = (unsigned)q.x | ((unsigned)q.y << 15) | (on ? 1u << 30 : 0u);
+    } else {
+        o.x[at] = (int16_t)q.x;
+        o.y[at] = (int16_t)q.y;
+        o.p[at] = pv;
+        o.t[at] = t;
+    }
+}
+
+// Where the workgroup's ON and OFF events of the frames k0 .. k0 + EF_BATCH - 1 start (the same in every lane).
+__device__ __forceinline__ void ef_bases(const ef_args& a, const u64* __restrict__ table, const u64* __restrict__ meta, int k0,
+                                         u64 (&base)[EF_BATCH][2])
+{
+#pragma unroll
+    for (int j = 0; j < EF_BATCH; j++) {
+        const size_t row = (size_t)min(k0 + j, a.n - 1) * 2;
+        base[j][0] = meta[row] + table[row * gridDim.x + blockIdx.x];
+        base[j][1] = meta[row + 1] + table[(row + 1) * gridDim.x + blockIdx.x];
+    }
+}
+
 // The plain emit pass (k_ef_emit<LINEAR, 0>).
 template <int LINEAR>
 __device__ __forceinline__ void ef_emit_plain(const ef_args& a, const u64* __restrict__ table, const u64* __restrict__ meta, const ef_out& o)
 {
-    const int p_on = o.p_on, p_off = o.p_off;
-    int16_t* __restrict__ ox = o.x;
-    int16_t* __restrict__ oy = o.y;
-    int8_t* __restrict__ op = o.p;
-    int64_t* __restrict__ ot = o.t;
-    u64* __restrict__ keys = o.keys;
-    unsigned* __restrict__ vals = o.vals;
-    int32_t* __restrict__ ref_out = o.ref;
     __shared__ int sh_lut[256];
     __shared__ unsigned sh[2][EF_BATCH][2][4];
     ef_px q = ef_init(a, sh_lut);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t n_wg = gridDim.x;
     const int64_t t_first = a.times[0];
     int prev_level = 0;   // L[k - 1]
     int set = 0;
@@ -423,13 +455,8 @@ __device__ __forceinline__ void ef_emit_plain(const ef_args& a, const u64* __res
         unsigned m[EF_BATCH], excl[EF_BATCH];
         int r0[EF_BATCH], lev[EF_BATCH];
         bool on[EF_BATCH];
-        u64 base[EF_BATCH][2];   // where the workgroup's ON and OFF events of each frame start (the same in every lane)
-#pragma unroll
-        for (int j = 0; j < EF_BATCH; j++) {
-            const size_t row = (size_t)min(k0 + j, a.n - 1) * 2;
-            base[j][0] = meta[row] + table[row * n_wg + blockIdx.x];
-            base[j][1] = meta[row + 1] + table[(row + 1) * n_wg + blockIdx.x];
-        }
+        u64 base[EF_BATCH][2];
+        ef_bases(a, table, meta, k0, base);
 #pragma unroll
         for (int j = 0; j < EF_BATCH; j++) {
             lev[j] = sh_lut[f[j]];
@@ -463,33 +490,16 @@ __device__ __forceinline__ void ef_emit_plain(const ef_args& a, const u64* __res
             const int64_t t_k = a.times[k];
             const bool linear = LINEAR && k > 0;
             const int64_t t_prev = linear ? a.times[k - 1] : t_k;
-            const u64 dt = (u64)(t_k - t_prev);
-            const long long span = (long long)lev[j] - (long long)a_level;
-            const u64 den = (u64)(span < 0 ? -span : span);
             const int c = on[j] ? q.c_on : q.c_off;
-            const int8_t pv = (int8_t)(on[j] ? p_on : p_off);
-            const unsigned packed = (unsigned)q.x | ((unsigned)q.y << 15) | (on[j] ? 1u << 30 : 0u);
+            const int8_t pv = (int8_t)(on[j] ? o.p_on : o.p_off);
             long long level = r0[j];
             for (unsigned i = 0; i < m[j]; i++, at++) {
                 level += on[j] ? c : -c;
-                int64_t t = t_k;
-                if (linear && den) {
-                    const long long off = level - (long long)a_level;
-                    t = t_prev + (int64_t)(((u64)(off < 0 ? -off : off) * dt) / den);
-                }
-                if (LINEAR) {
-                    keys[at] = (u64)(t - t_first);
-                    vals[at] = packed;
-                } else {
-                    ox[at] = (int16_t)q.x;
-                    oy[at] = (int16_t)q.y;
-                    op[at] = pv;
-                    ot[at] = t;
-                }
+                ef_store<LINEAR>(o, at, q, on[j], pv, linear ? ef_stamp(level, a_level, lev[j], t_prev, t_k) : t_k, t_first);
             }
         }
     }
-    if (q.in && ref_out) ref_out[q.pix] = q.r;
+    if (q.in && o.ref) o.ref[q.pix] = q.r;
 }
 
 // The emit pass of the sensor model (k_ef_emit<LINEAR, 1>).  A pixel may have events of both polarities at one frame (a
@@ -505,10 +515,7 @@ __device__ __forceinline__ void ef_emit_sensor(const ef_args& a, const ef_sensor
     ef_spx sp = ef_sensor_init(s, q);
     int64_t t_ok = sp.t_ok;   // the writing walk's copy; sp.t_ok is the counting walk's
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t n_wg = gridDim.x;
     const int64_t t_first = a.times[0];
-    const unsigned packed = (unsigned)q.x | ((unsigned)q.y << 15);
-    const int p_on = o.p_on, p_off = o.p_off;
     int prev_level = 0;   // L[k - 1]
     int set = 0;
     for (int k0 = 0; k0 < a.n; k0 += EF_BATCH, set ^= 1) {
@@ -516,33 +523,13 @@ __device__ __forceinline__ void ef_emit_sensor(const ef_args& a, const ef_sensor
         ef_load(a, q, k0, f);
         ef_cands c[EF_BATCH];
         unsigned incl[EF_BATCH][2], cnt[EF_BATCH][2];
-        u64 base[EF_BATCH][2];   // where the workgroup's ON and OFF events of each frame start (the same in every lane)
+        u64 base[EF_BATCH][2];
+        ef_bases(a, table, meta, k0, base);
 #pragma unroll
         for (int j = 0; j < EF_BATCH; j++) {
-            const size_t row = (size_t)min(k0 + j, a.n - 1) * 2;
-            base[j][0] = meta[row] + table[row * n_wg + blockIdx.x];
-            base[j][1] = meta[row + 1] + table[(row + 1) * n_wg + blockIdx.x];
-        }
-#pragma unroll
-        for (int j = 0; j < EF_BATCH; j++) {
-            const int k = k0 + j;
-            cnt[j][0] = cnt[j][1] = 0;
-            c[j].m = 0;
-            c[j].off_on = c[j].off_off = EF_NONE;
-            if (k < a.n) {
-                c[j].lev = sh_lut[f[j]];
-                c[j].a_level = prev_level;
-                prev_level = c[j].lev;
-                c[j].r0 = q.r;
-                c[j].m = ef_step(q.r, c[j].lev, q.c_on, q.c_off, c[j].on);
-                c[j].c = c[j].on ? q.c_on : q.c_off;
-                c[j].t_k = a.times[k];
-                c[j].t_prev = a.times[max(k - 1, 0)];
-                c[j].same = !LINEAR || k == 0;
-                if (s.noise && k > 0) ef_noise(s, q, sp, k, (u64)(c[j].t_k - c[j].t_prev), c[j].off_on, c[j].off_off);
-                ef_survivors<LINEAR>(s, c[j], sp.t_ok, cnt[j][0], cnt[j][1]);
-                if (!q.in) cnt[j][0] = cnt[j][1] = 0;
-            }
+            ef_frame<1>(a, s, q, sp, k0 + j, sh_lut[f[j]], LINEAR, prev_level, c[j]);
+            ef_survivors<LINEAR, 1>(s, c[j], sp.t_ok, cnt[j][0], cnt[j][1]);
+            if (!q.in) cnt[j][0] = cnt[j][1] = 0;
             // the total is below 2^31 (the guard), so 32 bits hold every prefix
             incl[j][0] = ef_wave_scan(cnt[j][0]);
             incl[j][1] = ef_wave_scan(cnt[j][1]);
@@ -567,21 +554,12 @@ __device__ __forceinline__ void ef_emit_sensor(const ef_args& a, const ef_sensor
             const size_t end_on = (size_t)base[j][0] + before[0] + incl[j][0], end_off = (size_t)base[j][1] + before[1] + incl[j][1];
             size_t at = c[j].on ? end_on - cnt[j][0] : end_off - cnt[j][1];   // the next signal event
             const bool sig_on = c[j].on;
-            ef_walk<LINEAR>(c[j], s.refractory, t_ok, [&](int kind, unsigned count, int64_t t) {
+            // (the polarity bytes are captured by value: chosen between through two references they went to the stack)
+            ef_walk<LINEAR>(c[j], s.refractory, t_ok, [&, p_on = o.p_on, p_off = o.p_off](int kind, unsigned count, int64_t t) {
                 const bool is_on = kind == 0 ? sig_on : kind == 1;
                 size_t w = kind == 0 ? at : kind == 1 ? end_on - 1 : end_off - 1;
                 at += kind == 0 ? count : 0u;
-                for (unsigned i = 0; i < count; i++, w++) {
-                    if (LINEAR) {
-                        o.keys[w] = (u64)(t - t_first);
-                        o.vals[w] = packed | (is_on ? 1u << 30 : 0u);
-                    } else {
-                        o.x[w] = (int16_t)q.x;
-                        o.y[w] = (int16_t)q.y;
-                        o.p[w] = (int8_t)(is_on ? p_on : p_off);
-                        o.t[w] = t;
-                    }
-                }
+                for (unsigned i = 0; i < count; i++, w++) ef_store<LINEAR>(o, w, q, is_on, (int8_t)(is_on ? p_on : p_off), t, t_first);
             });
         }
     }
@@ -593,13 +571,11 @@ template <int LINEAR, int SENSOR>
 __global__ __launch_bounds__(EF_WG) void k_ef_emit(ef_args a, ef_sensor s, const u64* __restrict__ table, const u64* __restrict__ meta,
                                                    u64 expected, ef_out o)
 {
-    if (!ef_guard(meta, a.n, expected)) return;   // the same for every thread of the grid: nothing is written
-    if constexpr (SENSOR) {
-        if (meta[2 * (size_t)a.n + 2]) return;
+    if (!ef_guard(meta, a.n, expected)) return;
+    if constexpr (SENSOR)
         ef_emit_sensor<LINEAR>(a, s, table, meta, o);
-    } else {
+    else
         ef_emit_plain<LINEAR>(a, table, meta, o);
-    }
 }
 
 __global__ __launch_bounds__(EF_WG) void k_ef_unpack(size_t count, const u64* __restrict__ keys, const unsigned* __restrict__ vals,
@@ -607,7 +583,7 @@ __global__ __launch_bounds__(EF_WG) void k_ef_unpack(size_t count, const u64* __
                                                      int p_off, int16_t* __restrict__ ox, int16_t* __restrict__ oy,
                                                      int8_t* __restrict__ op, int64_t* __restrict__ ot)
 {
-    if (!ef_guard(meta, n, expected) || meta[2 * (size_t)n + 2]) return;
+    if (!ef_guard(meta, n, expected)) return;
     const size_t i = (size_t)blockIdx.x * EF_WG + threadIdx.x;
     if (i >= count) return;
     const unsigned v = vals[i];
@@ -699,6 +675,19 @@ struct ef_plan {
     size_t sort_bytes;
 };
 
+// The count and the emit launch: the instantiation picked, then launched on one workgroup per 256 pixels.
+void ef_launch_count(hipStream_t stream, const ef_plan& pl, bool sensor)
+{
+    const auto kernel = sensor ? k_ef_count<1> : k_ef_count<0>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)pl.n_wg), dim3(EF_WG), 0, stream, pl.args, pl.sensor, pl.table, pl.meta + 2 * (size_t)pl.args.n + 1);
+}
+
+void ef_launch_emit(hipStream_t stream, const ef_plan& pl, bool linear, bool sensor, u64 total, const ef_out& o)
+{
+    const auto kernel = sensor ? (linear ? k_ef_emit<1, 1> : k_ef_emit<0, 1>) : (linear ? k_ef_emit<1, 0> : k_ef_emit<0, 0>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)pl.n_wg), dim3(EF_WG), 0, stream, pl.args, pl.sensor, pl.table, pl.meta, total, o);
+}
+
 unsigned ef_key_bits(const ef_call& c)
 {
     u64 span = (u64)c.times[c.n - 1] - (u64)c.times[0];
@@ -762,10 +751,7 @@ int ef_count_pass(nsof_ctx* ctx, const ef_call& c, size_t sort_count, ef_plan* p
 
     pl->sensor = ef_sensor_args(c);
     NSOF_HIP(ctx, hipMemsetAsync(pl->meta + rows + 1, 0, 2 * sizeof(u64), ctx->stream));   // the bad-threshold and long-walk flags
-    if (c.sensor)
-        hipLaunchKernelGGL(k_ef_count<1>, dim3((unsigned)pl->n_wg), dim3(EF_WG), 0, ctx->stream, a, pl->sensor, pl->table, pl->meta + rows + 1);
-    else
-        hipLaunchKernelGGL(k_ef_count<0>, dim3((unsigned)pl->n_wg), dim3(EF_WG), 0, ctx->stream, a, pl->sensor, pl->table, pl->meta + rows + 1);
+    ef_launch_count(ctx->stream, *pl, c.sensor != nullptr);
     NSOF_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_ef_scan, dim3((unsigned)rows), dim3(EF_WG), 0, ctx->stream, pl->table, pl->n_wg, pl->meta);
     NSOF_HIP(ctx, hipGetLastError());
@@ -821,21 +807,13 @@ int ef_emit_entry(nsof_ctx* ctx, const char* who, const ef_call& c, const int64_
     ef_plan pl;
     if (int rc = ef_count_pass(ctx, c, linear ? (size_t)total : 0, &pl)) return rc;
     const ef_out o{p_on, p_off, d_x, d_y, d_p, d_t, pl.keys_in, pl.vals_in, d_ref_out, d_t_ok_out};
-    const dim3 grid((unsigned)pl.n_wg), block(EF_WG);
-    // (an empty linear stream has no pairs to sort, but the kernel still writes ref and t_ok)
-    if (c.sensor && c.mode == NSOF_EVENTS_T_LINEAR)
-        hipLaunchKernelGGL((k_ef_emit<1, 1>), grid, block, 0, ctx->stream, pl.args, pl.sensor, pl.table, pl.meta, (u64)total, o);
-    else if (c.sensor)
-        hipLaunchKernelGGL((k_ef_emit<0, 1>), grid, block, 0, ctx->stream, pl.args, pl.sensor, pl.table, pl.meta, (u64)total, o);
-    else if (linear)
-        hipLaunchKernelGGL((k_ef_emit<1, 0>), grid, block, 0, ctx->stream, pl.args, pl.sensor, pl.table, pl.meta, (u64)total, o);
-    else
-        hipLaunchKernelGGL((k_ef_emit<0, 0>), grid, block, 0, ctx->stream, pl.args, pl.sensor, pl.table, pl.meta, (u64)total, o);
+    // (an empty linear stream has no pairs to sort, but the sensor kernel still takes its stamp mode: ref and t_ok)
+    ef_launch_emit(ctx->stream, pl, c.sensor ? c.mode == NSOF_EVENTS_T_LINEAR : linear, c.sensor != nullptr, (u64)total, o);
     NSOF_HIP(ctx, hipGetLastError());
     if (linear) {
         NSOF_HIP(ctx, rocprim::radix_sort_pairs(pl.sort_tmp, pl.sort_bytes, (const u64*)pl.keys_in, pl.keys_out, (const unsigned*)pl.vals_in,
                                                 pl.vals_out, (size_t)total, 0u, ef_key_bits(c), ctx->stream));
-        hipLaunchKernelGGL(k_ef_unpack, dim3((unsigned)(((size_t)total + EF_WG - 1) / EF_WG)), block, 0, ctx->stream, (size_t)total,
+        hipLaunchKernelGGL(k_ef_unpack, dim3((unsigned)(((size_t)total + EF_WG - 1) / EF_WG)), dim3(EF_WG), 0, ctx->stream, (size_t)total,
                            pl.keys_out, pl.vals_out, pl.meta, n, (u64)total, c.times[0], p_on, p_off, d_x, d_y, d_p, d_t);
         NSOF_HIP(ctx, hipGetLastError());
     }

@@ -11,6 +11,7 @@ background-activity noise events (``nsof_events_from_frames_sensor_*_dev``; DESI
 gives the noise generator's words on the host.
 """
 import ctypes as C
+import typing
 
 import numpy as np
 
@@ -59,14 +60,55 @@ def _whole(who, name, v):
     return int(v)
 
 
-def _threshold_units(who, name, v):
-    """A threshold in grey levels as table units: round(256 * v), which must be >= 1."""
+class _Quantity(typing.NamedTuple):
+    """An argument in the caller's units that the library holds in whole units of its own: ``round(v * mul / div)`` (the
+    two steps in this order, so that a power of two is exact: one rounding), which must lie in ``[lo, hi]``."""
+    mul: float
+    div: float
+    lo: int
+    hi: int
+    dtype: type      # of a per-pixel plane
+    label: str       # how a message names the argument ``name``
+    unit: str        # the caller's unit
+    units: str       # the library's
+    span: str        # [lo, hi] in words
+    shown: object    # a plane's value as its message shows it: NumPy's float64 (thresholds) or a Python float (rates)
+
+
+_THRESHOLD = _Quantity(float(LEVELS_PER_GREY), 1.0, 1, 0x7fffffff, np.int32, "{}", "grey levels", "table units", "1 .. 2^31 - 1",
+                       lambda v: v)
+_RATE = _Quantity(4294967296.0, 1e6, 0, (1 << 32) - 1, np.uint32, "noise[{!r}]", "Hz", "units of 2^-32 per microsecond",
+                  "0 .. 2^32 - 1", float)
+
+
+def _units(who, qty, name, v):
+    """A number in the caller's units (a threshold in grey levels, a noise rate in Hz) as the library's whole units."""
+    label = qty.label.format(name)
     if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-        raise NsofValueError(f"{who}: {name} = {v!r} is not a finite number", _lib.NSOF_EINVAL)
-    c = int(round(LEVELS_PER_GREY * float(v)))
-    if c < 1 or c > 0x7fffffff:
-        raise NsofValueError(f"{who}: {name} = {v!r} grey levels is {c} table units; 1 .. 2^31 - 1 expected", _lib.NSOF_EINVAL)
-    return c
+        raise NsofValueError(f"{who}: {label} = {v!r} is not a finite number", _lib.NSOF_EINVAL)
+    u = int(round(float(v) * qty.mul / qty.div))
+    if not qty.lo <= u <= qty.hi:
+        raise NsofValueError(f"{who}: {label} = {v!r} {qty.unit} is {u} {qty.units}; {qty.span} expected", _lib.NSOF_EINVAL)
+    return u
+
+
+def _units_plane(who, qty, name, maps, h, w):
+    """``maps`` (the caller's units, ``[H][W][2]``: ON, OFF per pixel; array or tensor) as a host plane of the library's whole
+    units, of ``qty.dtype``."""
+    import torch
+    label = qty.label.format(name)
+    m = maps.detach().cpu().numpy() if isinstance(maps, torch.Tensor) else np.asarray(maps)
+    if m.dtype.kind not in "iuf" or m.shape != (h, w, 2):
+        raise NsofValueError(f"{who}: {label} must be numbers [{h}][{w}][2] (got {m.dtype} {m.shape})", _lib.NSOF_ESHAPE)
+    m = m.astype(np.float64)
+    if not np.isfinite(m).all():
+        raise NsofValueError(f"{who}: {label} holds a value that is not finite", _lib.NSOF_EINVAL)
+    u = np.rint(m * qty.mul / qty.div)
+    if u.min() < qty.lo or u.max() > qty.hi:
+        y, x, c = (int(v) for v in np.argwhere((u < qty.lo) | (u > qty.hi))[0])
+        raise NsofValueError(f"{who}: {label}[{y}][{x}][{c}] = {qty.shown(m[y, x, c])!r} {qty.unit} is {int(u[y, x, c])} {qty.units}; "
+                             f"{qty.span} expected", _lib.NSOF_EINVAL)
+    return np.ascontiguousarray(u.astype(qty.dtype))
 
 
 def _times_arg(who, n, times_us, frame_us):
@@ -101,52 +143,7 @@ def _response_arg(who, response):
     return np.ascontiguousarray(lut, np.int32)
 
 
-def _threshold_plane(who, threshold_maps, h, w):
-    """``threshold_maps`` (grey levels, ``[H][W][2]``: c_on, c_off per pixel) as a host int32 plane of table units."""
-    import torch
-    m = threshold_maps.detach().cpu().numpy() if isinstance(threshold_maps, torch.Tensor) else np.asarray(threshold_maps)
-    if m.dtype.kind not in "iuf" or m.shape != (h, w, 2):
-        raise NsofValueError(f"{who}: threshold_maps must be numbers [{h}][{w}][2] (got {m.dtype} {m.shape})", _lib.NSOF_ESHAPE)
-    m = m.astype(np.float64)
-    if not np.isfinite(m).all():
-        raise NsofValueError(f"{who}: threshold_maps holds a value that is not finite", _lib.NSOF_EINVAL)
-    units = np.rint(LEVELS_PER_GREY * m)
-    if units.min() < 1 or units.max() > 0x7fffffff:
-        y, x, s = (int(v) for v in np.argwhere((units < 1) | (units > 0x7fffffff))[0])
-        raise NsofValueError(f"{who}: threshold_maps[{y}][{x}][{s}] = {m[y, x, s]!r} grey levels is {int(units[y, x, s])} table units; "
-                             "1 .. 2^31 - 1 expected", _lib.NSOF_EINVAL)
-    return np.ascontiguousarray(units.astype(np.int32))
-
-
 NOISE_KEYS = ("seed", "rate_hz", "rate_on_hz", "rate_off_hz", "rate_maps")
-
-
-def _rate_units(who, name, v):
-    """A noise rate in Hz as the library holds it: round(rate * 2^32 / 10^6), which must lie in [0, 2^32)."""
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-        raise NsofValueError(f"{who}: noise[{name!r}] = {v!r} is not a finite number", _lib.NSOF_EINVAL)
-    q = int(round(float(v) * 4294967296.0 / 1e6))   # the power of two is exact: one rounding
-    if not 0 <= q < 1 << 32:
-        raise NsofValueError(f"{who}: noise[{name!r}] = {v!r} Hz is {q} units of 2^-32 per microsecond; 0 .. 2^32 - 1 expected",
-                             _lib.NSOF_EINVAL)
-    return q
-
-
-def _rate_plane(who, rate_maps, h, w):
-    """``noise['rate_maps']`` (Hz, ``[H][W][2]``: ON, OFF per pixel) as a host uint32 plane of rate units."""
-    import torch
-    m = rate_maps.detach().cpu().numpy() if isinstance(rate_maps, torch.Tensor) else np.asarray(rate_maps)
-    if m.dtype.kind not in "iuf" or m.shape != (h, w, 2):
-        raise NsofValueError(f"{who}: noise['rate_maps'] must be numbers [{h}][{w}][2] (got {m.dtype} {m.shape})", _lib.NSOF_ESHAPE)
-    m = m.astype(np.float64)
-    if not np.isfinite(m).all():
-        raise NsofValueError(f"{who}: noise['rate_maps'] holds a value that is not finite", _lib.NSOF_EINVAL)
-    q = np.rint(m * 4294967296.0 / 1e6)
-    if q.min() < 0 or q.max() >= 1 << 32:
-        y, x, c = (int(v) for v in np.argwhere((q < 0) | (q >= 1 << 32))[0])
-        raise NsofValueError(f"{who}: noise['rate_maps'][{y}][{x}][{c}] = {float(m[y, x, c])!r} Hz is {int(q[y, x, c])} units of 2^-32 per "
-                             "microsecond; 0 .. 2^32 - 1 expected", _lib.NSOF_EINVAL)
-    return np.ascontiguousarray(q.astype(np.uint32))
 
 
 def _sensor_args(who, n, h, w, refractory_us, noise, t_ok, first_frame):
@@ -175,12 +172,12 @@ def _sensor_args(who, n, h, w, refractory_us, noise, t_ok, first_frame):
             raise NsofValueError(f"{who}: noise gives its rates {len(ways)} ways ({', '.join(ways) or 'none'}); one of 'rate_hz', "
                                  "'rate_on_hz' / 'rate_off_hz', 'rate_maps' expected", _lib.NSOF_EINVAL)
         if "rate_maps" in noise:
-            out["plane"] = _rate_plane(who, noise["rate_maps"], h, w)
+            out["plane"] = _units_plane(who, _RATE, "rate_maps", noise["rate_maps"], h, w)
         elif "rate_hz" in noise:
-            out["rate_on_q"] = out["rate_off_q"] = _rate_units(who, "rate_hz", noise["rate_hz"])
+            out["rate_on_q"] = out["rate_off_q"] = _units(who, _RATE, "rate_hz", noise["rate_hz"])
         else:
-            out["rate_on_q"] = _rate_units(who, "rate_on_hz", noise.get("rate_on_hz", 0))
-            out["rate_off_q"] = _rate_units(who, "rate_off_hz", noise.get("rate_off_hz", 0))
+            out["rate_on_q"] = _units(who, _RATE, "rate_on_hz", noise.get("rate_on_hz", 0))
+            out["rate_off_q"] = _units(who, _RATE, "rate_off_hz", noise.get("rate_off_hz", 0))
     if t_ok is not None:
         if not isinstance(t_ok, torch.Tensor) or t_ok.dtype != torch.int64 or tuple(t_ok.shape) != (h, w) or not t_ok.is_contiguous():
             raise NsofValueError(f"{who}: t_ok must be a contiguous int64 tensor [{h}][{w}] (got {getattr(t_ok, 'dtype', type(t_ok))} "
@@ -277,9 +274,9 @@ def events_from_frames_dev(frames, times_us=None, *, frame_us=None, threshold=10
         raise NsofValueError(f"{who}: {h}x{w} frames are beyond the int16 coordinates of an event", _lib.NSOF_ESHAPE)
     times = _times_arg(who, n, times_us, frame_us)
     lut = _response_arg(who, response)
-    c_on = _threshold_units(who, "threshold", threshold)
-    c_off = c_on if threshold_off is None else _threshold_units(who, "threshold_off", threshold_off)
-    plane = None if threshold_maps is None else _threshold_plane(who, threshold_maps, h, w)
+    c_on = _units(who, _THRESHOLD, "threshold", threshold)
+    c_off = c_on if threshold_off is None else _units(who, _THRESHOLD, "threshold_off", threshold_off)
+    plane = None if threshold_maps is None else _units_plane(who, _THRESHOLD, "threshold_maps", threshold_maps, h, w)
     if timestamps not in _TIMESTAMPS:
         raise NsofValueError(f"{who}: timestamps = {timestamps!r}; 'frame' or 'linear' expected", _lib.NSOF_EINVAL)
     p_on, p_off = _polarity_arg(who, "p_on", p_on), _polarity_arg(who, "p_off", p_off)
@@ -300,58 +297,44 @@ def events_from_frames_dev(frames, times_us=None, *, frame_us=None, threshold=10
 
     ctx = ctx or default_context()
     dev = frames.device
+    lib = ctx._lib
     d_plane = None if plane is None else torch.from_numpy(plane).to(dev)
     bounds = np.empty(n + 1, np.int64)
-    common = (dev_ptr(frames), int(frames.stride(1)), int(frames.stride(0)), n, h, w, times.ctypes.data_as(C.c_void_p),
-              lut.ctypes.data_as(C.c_void_p), c_on, c_off, dev_ptr(d_plane), dev_ptr(ref_in), ref_mode)
     p_bounds = bounds.ctypes.data_as(C.c_void_p)
+    mode = _TIMESTAMPS[timestamps]
+    common = (ctx.ptr, dev_ptr(frames), int(frames.stride(1)), int(frames.stride(0)), n, h, w, times.ctypes.data_as(C.c_void_p),
+              lut.ctypes.data_as(C.c_void_p), c_on, c_off, dev_ptr(d_plane), dev_ptr(ref_in), ref_mode)
+    # the plain or the sensor pair of entries; the sensor pair takes the stamp mode and the struct in both calls
+    d_rates = st = None
+    count, emit, count_extra = lib.nsof_events_from_frames_count_dev, lib.nsof_events_from_frames_emit_dev, ()
     if sensor is not None:
-        return _sensor_call(ctx, who, sensor, common, p_bounds, bounds, _TIMESTAMPS[timestamps], p_on, p_off, n, h, w, dev,
-                            d_plane is not None)
-    common += (p_bounds,)
-    torch.cuda.synchronize(dev)   # the frames, ref and the plane's upload are torch's work; the library reads them on the context's stream
+        if sensor["plane"] is not None:
+            d_rates = torch.from_numpy(sensor["plane"].view(np.int32)).to(dev)   # the bits of the uint32 plane
+        st = _lib.EventsSensor(sensor["refractory_us"], sensor["seed"], sensor["first_frame"], sensor["rate_on_q"], sensor["rate_off_q"],
+                               dev_ptr(d_rates), dev_ptr(sensor["t_ok"]))
+        count, emit, count_extra = (lib.nsof_events_from_frames_sensor_count_dev, lib.nsof_events_from_frames_sensor_emit_dev,
+                                    (mode, C.byref(st)))
+    torch.cuda.synchronize(dev)   # the frames, ref, t_ok and the planes' uploads are torch's work; the library reads them on the context's stream
     try:
-        ctx.check(ctx._lib.nsof_events_from_frames_count_dev(ctx.ptr, *common), who)
+        ctx.check(count(*common, *count_extra, p_bounds), who)
         total = int(bounds[n])
         x, y = (torch.empty(total, dtype=torch.int16, device=dev) for _ in range(2))
         p = torch.empty(total, dtype=torch.int8, device=dev)
         t = torch.empty(total, dtype=torch.int64, device=dev)
         ref_out = torch.empty((h, w), dtype=torch.int32, device=dev)   # fresh allocations: no pending work of torch's to wait for
-        ctx.check(ctx._lib.nsof_events_from_frames_emit_dev(ctx.ptr, *common, _TIMESTAMPS[timestamps], p_on, p_off, total, dev_ptr(x),
-                                                            dev_ptr(y), dev_ptr(p), dev_ptr(t), dev_ptr(ref_out)), who)
+        out = dict(x=x, y=y, p=p, t=t, frame_bounds=bounds, ref=ref_out)
+        emit_extra = ()
+        if st is not None:
+            out["t_ok"] = torch.empty((h, w), dtype=torch.int64, device=dev)
+            emit_extra = (C.byref(st), dev_ptr(out["t_ok"]))
+        ctx.check(emit(*common, p_bounds, mode, p_on, p_off, total, dev_ptr(x), dev_ptr(y), dev_ptr(p), dev_ptr(t), dev_ptr(ref_out),
+                       *emit_extra), who)
     finally:
-        if d_plane is not None:
-            # the queued kernels read the uploaded plane, and torch's allocator hands a freed block to the next allocation
-            # on torch's stream at once: the plane may go only when the context's stream has drained
+        if d_plane is not None or d_rates is not None:
+            # the queued kernels read the uploaded planes, and torch's allocator hands a freed block to the next allocation
+            # on torch's stream at once: a plane may go only when the context's stream has drained
             ctx.synchronize()
-    return dict(x=x, y=y, p=p, t=t, frame_bounds=bounds, ref=ref_out)
-
-
-def _sensor_call(ctx, who, sensor, common, p_bounds, bounds, mode, p_on, p_off, n, h, w, dev, has_plane):
-    """The count and emit entries of the sensor pair for ``events_from_frames_dev``: the same two steps as the plain
-    pair, with the stamp mode and the sensor struct in both calls and ``t_ok`` in the result."""
-    import torch
-
-    from .context import dev_ptr
-    d_rates = None if sensor["plane"] is None else torch.from_numpy(sensor["plane"].view(np.int32)).to(dev)   # the bits of the uint32 plane
-    st = _lib.EventsSensor(sensor["refractory_us"], sensor["seed"], sensor["first_frame"], sensor["rate_on_q"], sensor["rate_off_q"],
-                           dev_ptr(d_rates), dev_ptr(sensor["t_ok"]))
-    torch.cuda.synchronize(dev)   # the frames, ref, t_ok and the planes' uploads are torch's work
-    try:
-        ctx.check(ctx._lib.nsof_events_from_frames_sensor_count_dev(ctx.ptr, *common, mode, C.byref(st), p_bounds), who)
-        total = int(bounds[n])
-        x, y = (torch.empty(total, dtype=torch.int16, device=dev) for _ in range(2))
-        p = torch.empty(total, dtype=torch.int8, device=dev)
-        t = torch.empty(total, dtype=torch.int64, device=dev)
-        ref_out = torch.empty((h, w), dtype=torch.int32, device=dev)
-        t_ok_out = torch.empty((h, w), dtype=torch.int64, device=dev)
-        ctx.check(ctx._lib.nsof_events_from_frames_sensor_emit_dev(ctx.ptr, *common, p_bounds, mode, p_on, p_off, total, dev_ptr(x),
-                                                                   dev_ptr(y), dev_ptr(p), dev_ptr(t), dev_ptr(ref_out), C.byref(st),
-                                                                   dev_ptr(t_ok_out)), who)
-    finally:
-        if has_plane or d_rates is not None:
-            ctx.synchronize()   # the queued kernels read the uploaded planes (see events_from_frames_dev)
-    return dict(x=x, y=y, p=p, t=t, frame_bounds=bounds, ref=ref_out, t_ok=t_ok_out)
+    return out
 
 
 def events_from_video_dev(frames_bgr, times_us=None, *, code="BGR2GRAY", ctx=None, **kwargs):

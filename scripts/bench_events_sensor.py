@@ -15,10 +15,12 @@ grey levels, ``ref="first"``.
            median and min-max of each in ms, the number of events of each stream, and ``over_plain`` = median / the plain
            median of the same mode.
   parent   with --parent-lib (libnsof.so of the parent commit, built beside this one): the count and emit entries of the
-           plain pair, which both libraries export, called through ctypes on a context of each library, the two libraries
-           alternating within every round.  ``within_parent_range``: the new median of a call lies inside the parent's
-           min-max of this session (or below it).  The plain kernels are templates now, so this is the check that their
-           code did not change for the worse.
+           plain pair and of the sensor pair (refractory time and noise together, both stamp modes), which both libraries
+           export, called through ctypes on a fresh context of each library, the two libraries alternating within every round
+           and the one that goes first changing from round to round.
+           ``within_parent_range``: the new median of a call lies inside the parent's min-max of this session (or below
+           it); ``same_stream_sums``: after every emit entry the two libraries' x, y, p, t, ref and t_ok add up alike.
+           This is the check that a change of the kernels' code changed neither their results nor their time.
 --trace MODE:PATH (say linear:both) runs that one call --reps times after the warm-up and nothing else, for a separate
 ``rocprofv3 --kernel-trace --stats`` run (scripts/prof_py_kernels.sh): the count kernel is one instantiation for all
 sensor paths, so a trace of several would average them.
@@ -49,7 +51,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--parent-lib", default=None, help="libnsof.so of the parent commit, for the alternating plain-call check")
+    ap.add_argument("--parent-lib", default=None, help="libnsof.so of the parent commit, for the alternating entry-by-entry check")
     ap.add_argument("--trace", default=None, metavar="MODE:PATH", help="that call --reps times and nothing else")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
@@ -60,6 +62,7 @@ def main():
     import nsof
     from nsof import _lib, synth
     from events_from_frames_ref import units
+    from events_sensor_ref import rate_q
     dev = torch.device("cuda", 0)
     ctx = nsof.Context(0)
     stream = torch.cuda.Stream(dev)
@@ -113,52 +116,79 @@ def main():
         _lib.load()   # (the HIP runtime both libraries link against is in the process)
         libs = {"new": ctx._lib, "parent": C.CDLL(os.path.abspath(a.parent_lib))}
         for name in ("nsof_create", "nsof_destroy", "nsof_set_stream", "nsof_synchronize", "nsof_events_from_frames_count_dev",
-                     "nsof_events_from_frames_emit_dev"):
+                     "nsof_events_from_frames_emit_dev", "nsof_events_from_frames_sensor_count_dev",
+                     "nsof_events_from_frames_sensor_emit_dev"):
             fn = getattr(libs["parent"], name)
             fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-        p_ctx = C.c_void_p()
-        assert libs["parent"].nsof_create(0, C.byref(p_ctx)) == 0
-        assert libs["parent"].nsof_set_stream(p_ctx, C.c_void_p(stream.cuda_stream)) == 0
-        ptrs = {"new": ctx.ptr, "parent": p_ctx}
+        ptrs = {}
+        for which in ("parent", "new"):   # a fresh context of each library: the one above has the workspace of the paths it ran
+            ptrs[which] = C.c_void_p()
+            assert libs[which].nsof_create(0, C.byref(ptrs[which])) == 0
+            assert libs[which].nsof_set_stream(ptrs[which], C.c_void_p(stream.cuda_stream)) == 0
         lut = nsof.linear_response()
         c = units(THRESHOLD)
-        bounds = np.empty(n + 1, np.int64)
+        q = rate_q(NOISE["rate_hz"])
+        st = C.byref(_lib.EventsSensor(REFRACTORY_US, NOISE["seed"], 0, q, q, None, None))
         common = (frames.data_ptr(), frames.stride(1), frames.stride(0), n, H, W, times.ctypes.data, lut.ctypes.data, c, c, None, None,
-                  _lib.EVENTS_REF_FIRST, bounds.ctypes.data)
-        assert libs["new"].nsof_events_from_frames_count_dev(ptrs["new"], *common) == 0
-        total = int(bounds[n])
-        x, y = (torch.empty(total, dtype=torch.int16, device=dev) for _ in range(2))
-        p = torch.empty(total, dtype=torch.int8, device=dev)
-        t = torch.empty(total, dtype=torch.int64, device=dev)
+                  _lib.EVENTS_REF_FIRST)
+        stamp = {"frame": _lib.EVENTS_T_FRAME, "linear": _lib.EVENTS_T_LINEAR}
+        # the bounds of each stream, from the new library (the parent's must come out equal: its emit pass writes nothing otherwise)
+        bounds = {k: np.empty(n + 1, np.int64) for k in ("plain", "sensor_frame", "sensor_linear")}
+        assert libs["new"].nsof_events_from_frames_count_dev(ptrs["new"], *common, bounds["plain"].ctypes.data) == 0
+        for m in stamp:
+            assert libs["new"].nsof_events_from_frames_sensor_count_dev(ptrs["new"], *common, stamp[m], st,
+                                                                        bounds["sensor_" + m].ctypes.data) == 0
+        totals = {k: int(b[n]) for k, b in bounds.items()}
+        cap = max(totals.values())
+        x, y = (torch.empty(cap, dtype=torch.int16, device=dev) for _ in range(2))
+        p = torch.empty(cap, dtype=torch.int8, device=dev)
+        t = torch.empty(cap, dtype=torch.int64, device=dev)
         ref = torch.empty((H, W), dtype=torch.int32, device=dev)
+        t_ok = torch.empty((H, W), dtype=torch.int64, device=dev)
+        outs = (x.data_ptr(), y.data_ptr(), p.data_ptr(), t.data_ptr(), ref.data_ptr())
+
+        # what -> (the entry's name, its arguments after the common ones, the stream it writes or None)
+        whats = {"count": ("nsof_events_from_frames_count_dev", (bounds["plain"].ctypes.data,), None)}
+        for m in stamp:
+            whats["emit_" + m] = ("nsof_events_from_frames_emit_dev", (bounds["plain"].ctypes.data, stamp[m], 1, -1, totals["plain"]) + outs,
+                                  "plain")
+        for m in stamp:   # refractory time and noise together, the "both" of the paths above
+            b = bounds["sensor_" + m].ctypes.data
+            whats["sensor_count_" + m] = ("nsof_events_from_frames_sensor_count_dev", (stamp[m], st, b), None)
+            whats["sensor_emit_" + m] = ("nsof_events_from_frames_sensor_emit_dev",
+                                         (b, stamp[m], 1, -1, totals["sensor_" + m]) + outs + (st, t_ok.data_ptr()), "sensor_" + m)
 
         def entry_call(which, what):
-            lib, cp = libs[which], ptrs[which]
-            if what == "count":
-                rc = lib.nsof_events_from_frames_count_dev(cp, *common)
-            else:
-                rc = lib.nsof_events_from_frames_emit_dev(cp, *common, _lib.EVENTS_T_FRAME if what == "emit_frame" else _lib.EVENTS_T_LINEAR,
-                                                          1, -1, total, x.data_ptr(), y.data_ptr(), p.data_ptr(), t.data_ptr(), ref.data_ptr())
+            name, args, _ = whats[what]
+            rc = getattr(libs[which], name)(ptrs[which], *common, *args)
             assert rc == 0, (which, what, rc)
 
-        whats = ("count", "emit_frame", "emit_linear")
         sums = {}
-        for which in ("parent", "new"):   # warm-up, and the two libraries' streams compared
-            for what in whats:
+        for which in ("parent", "new"):   # warm-up, and the two libraries' streams compared after every emit entry
+            sums[which] = {}
+            for what, (_, _, written) in whats.items():
+                for v in (x, y, p, t, ref, t_ok):
+                    v.zero_()
+                torch.cuda.synchronize(dev)
                 entry_call(which, what)
-            ctx.synchronize()
-            sums[which] = [int(v.to(torch.int64).sum()) for v in (x, y, p, t, ref)]
+                torch.cuda.synchronize(dev)
+                if written:
+                    sums[which][what] = [int(v[:totals[written]].to(torch.int64).sum()) for v in (x, y, p, t)] + \
+                                        [int(ref.to(torch.int64).sum()), int(t_ok.sum())]
         pm = {(which, what): [] for which in libs for what in whats}
-        for _ in range(a.reps):
+        for r in range(a.reps):
             for what in whats:
-                for which in ("parent", "new"):
+                # who goes first changes every round: the second call of a pair took about half a percent longer, whichever
+                # library it was (the same library loaded twice showed it)
+                for which in (("parent", "new"), ("new", "parent"))[r % 2]:
                     pm[(which, what)].append(timed(lambda: entry_call(which, what))[0])
-        check = {"same_stream_sums": sums["new"] == sums["parent"]}
+        check = {"same_stream_sums": sums["new"] == sums["parent"], "events": totals}
         for what in whats:
             new, par = spread(pm[("new", what)]), spread(pm[("parent", what)])
             check[what] = {"new": new, "parent": par, "within_parent_range": new["median_ms"] <= par["max_ms"]}
-        line["plain_vs_parent"] = check
-        libs["parent"].nsof_destroy(p_ctx)
+        line["vs_parent"] = check
+        for which in ptrs:
+            libs[which].nsof_destroy(ptrs[which])
     line["not_measured"] = ["hardware counters", "frame sizes other than 1080p", "rate planes (hot pixels)", "chunked runs",
                             "a given t_ok plane"]
     print(json.dumps(line))
