@@ -1089,7 +1089,9 @@ int nsof_events_from_frames_emit_dev(nsof_ctx* ctx, const uint8_t* d_frames, ptr
  * then not written).  d_t_ok_out: DEVICE int64 [height][width], may be d_t_ok_in, may be NULL.
  * NSOF_EINVAL beyond the refusals above, nothing launched and nothing written: refractory_us outside [0, 2^31),
  * first_frame < 0 or first_frame + n beyond 2^62, a timestamps_mode the count entry does not know, a d_t_ok_in without a
- * d_t_ok_out (emit entry).  A walk through single crossings is needed only with _T_LINEAR and a refractory time or a
+ * d_t_ok_out (emit entry), refractory_us > 0 with times[n-1] > INT64_MAX - refractory_us (t_ok = t + refractory_us of a
+ * stamp up to times[n-1] would pass the int64 range; the plain entries, which keep no t_ok, take such times, and so do the
+ * sensor entries without a refractory time).  A walk through single crossings is needed only with _T_LINEAR and a refractory time or a
  * d_t_ok_in; there a pixel that crosses 2^20 thresholds or more in one step is refused like a bad threshold plane (the
  * count entry returns NSOF_EUNSUPPORTED without filling frame_bounds_out, the emit entry writes nothing). */
 typedef struct nsof_events_sensor {

@@ -639,6 +639,10 @@ int ef_check(nsof_ctx* ctx, const char* who, const ef_call& c)
         if (s->first_frame < 0 || s->first_frame > (1ll << 62) - c.n)
             return nsof_set_error(ctx, NSOF_EINVAL, "%s: first_frame = %lld with %d frames: frame indices lie in [0, 2^62]", who,
                                   (long long)s->first_frame, c.n);
+        // t_ok = t + refractory_us of the latest stamp there can be must stay an int64: wrapped, the pixel would never be blocked again
+        if (s->refractory_us > 0 && c.times[c.n - 1] > INT64_MAX - s->refractory_us)
+            return nsof_set_error(ctx, NSOF_EINVAL, "%s: times[%d] = %lld with refractory_us = %lld: t_ok = t + refractory_us would "
+                                  "pass the int64 range", who, c.n - 1, (long long)c.times[c.n - 1], (long long)s->refractory_us);
     }
     return NSOF_OK;
 }

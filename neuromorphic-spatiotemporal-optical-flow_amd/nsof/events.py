@@ -21,6 +21,7 @@ from .errors import NsofValueError
 
 LEVELS_PER_GREY = 256          # the units of the default (linear) response table: lut[i] = 256 * i
 LUT_MAX = 1 << 30
+INT64_MAX = (1 << 63) - 1
 _TIMESTAMPS = {"frame": _lib.EVENTS_T_FRAME, "linear": _lib.EVENTS_T_LINEAR}
 
 
@@ -258,7 +259,9 @@ def events_from_frames_dev(frames, times_us=None, *, frame_us=None, threshold=10
     with ``first_frame=f+k`` and the first call's ``ref`` and ``t_ok`` give the one-shot stream, ``ref`` and ``t_ok`` bit for
     bit.  The result then also carries ``t_ok`` (int64 CUDA ``[H][W]``; a pixel that never fired holds the smallest int64).
     With ``"linear"`` stamps and a refractory time or a ``t_ok`` the crossings of a step are walked one by one, and a pixel
-    that crosses 2^20 thresholds or more in one step is refused (``NSOF_EUNSUPPORTED``).  With ``rate_maps`` the call ends
+    that crosses 2^20 thresholds or more in one step is refused (``NSOF_EUNSUPPORTED``).  ``t_ok`` must stay an int64: with
+    ``refractory_us > 0`` a last time above ``2^63 - 1 - refractory_us`` is refused (``NSOF_EINVAL``, before any device work);
+    without a refractory time, and for the plain generator, any int64 times are taken.  With ``rate_maps`` the call ends
     in ``ctx.synchronize()``, like ``threshold_maps``."""
     import torch
 
@@ -281,6 +284,9 @@ def events_from_frames_dev(frames, times_us=None, *, frame_us=None, threshold=10
         raise NsofValueError(f"{who}: timestamps = {timestamps!r}; 'frame' or 'linear' expected", _lib.NSOF_EINVAL)
     p_on, p_off = _polarity_arg(who, "p_on", p_on), _polarity_arg(who, "p_off", p_off)
     sensor = _sensor_args(who, n, h, w, refractory_us, noise, t_ok, first_frame)
+    if sensor is not None and sensor["refractory_us"] > 0 and int(times[-1]) > INT64_MAX - sensor["refractory_us"]:
+        raise NsofValueError(f"{who}: times_us[{n - 1}] = {int(times[-1])} with refractory_us = {sensor['refractory_us']}: t_ok = t + "
+                             "refractory_us would pass the int64 range", _lib.NSOF_EINVAL)
     if ref is None or (isinstance(ref, str) and ref == "first"):
         ref_mode, ref_in = (_lib.EVENTS_REF_ZERO if ref is None else _lib.EVENTS_REF_FIRST), None
     elif isinstance(ref, torch.Tensor):

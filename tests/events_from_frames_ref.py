@@ -15,11 +15,12 @@ def units(grey_levels):
 
 
 def events_from_frames_ref(frames, times, c_on, c_off, lut=None, ref=None, timestamps="linear", p_on=1, p_off=-1,
-                           on_frame=None):
+                           on_frame=None, on_stamps=None):
     """frames uint8 [n][H][W], times int64 [n]; c_on / c_off: table units, scalars or [H][W] planes; lut: 256 levels (None:
     256 * i); ref: None (zeros), "first" or an int [H][W] plane.  Returns a dict of x, y (int16), p (int8), t (int64),
     frame_bounds (int64 [n + 1]) and ref (int32 [H][W]).  The invariant -c_off < L[k] - r < c_on is asserted after every
-    frame; on_frame(k, r, level) is called there too."""
+    frame; on_frame(k, r, level) is called there too.  on_stamps(k, num, dt, den, t) is called per frame and polarity with the
+    terms of the linear stamps t = T[k-1] + (num * dt) // den of its crossings (int64 arrays; dt an int)."""
     frames = np.asarray(frames)
     assert frames.dtype == np.uint8 and frames.ndim == 3 and timestamps in ("frame", "linear")
     n, h, w = frames.shape
@@ -60,6 +61,8 @@ def events_from_frames_ref(frames, times, c_on, c_off, lut=None, ref=None, times
                 assert (num > 0).all() and (den >= num).all()
                 t = times[k - 1] + (num * (times[k] - times[k - 1])) // den
                 assert (t >= times[k - 1]).all() and (t <= times[k]).all()
+                if on_stamps is not None:
+                    on_stamps(k, num, int(times[k] - times[k - 1]), den, t)
             fx.append(pix % w); fy.append(pix // w); fpol.append(np.full(pix.size, pol, np.int64)); ft.append(t); fj.append(j)
         r = r + m_on * con - m_off * coff
         assert ((b - r > -coff) & (b - r < con)).all(), f"invariant broken after frame {k}"

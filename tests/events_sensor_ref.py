@@ -40,11 +40,13 @@ def noise_candidates(seed, npx, frame, delta, rate_on, rate_off):
 
 
 def events_sensor_ref(frames, times, c_on, c_off, lut=None, ref=None, timestamps="linear", p_on=1, p_off=-1, refractory_us=0,
-                      seed=0, rate_on=0, rate_off=0, t_ok=None, first_frame=0):
+                      seed=0, rate_on=0, rate_off=0, t_ok=None, first_frame=0, counter_of=None):
     """frames uint8 [n][H][W], times int64 [n]; c_on / c_off: table units, scalars or [H][W]; rate_on / rate_off: rate
     units (rate_q), scalars or [H][W]; ref: None, "first" or an int [H][W] plane; t_ok: None or an int64 [H][W] plane.
     Returns a dict of x, y (int16), p (int8), t (int64), frame_bounds (int64 [n + 1]), ref (int32 [H][W]), t_ok (int64
-    [H][W]) and noise (int64 [2]: the ON and OFF noise candidates drawn, before the walk)."""
+    [H][W]) and noise (int64 [2]: the ON and OFF noise candidates drawn, before the walk).  counter_of(first_frame, k): the
+    frame index the noise block of frame k is drawn for (None: the model's first_frame + k; a test of the counter's carry
+    states a wrong generator with it).  t_ok = t + refractory_us must stay an int64, as the entries require."""
     frames = np.asarray(frames)
     assert frames.dtype == np.uint8 and frames.ndim == 3 and timestamps in ("frame", "linear")
     n, h, w = frames.shape
@@ -52,6 +54,7 @@ def events_sensor_ref(frames, times, c_on, c_off, lut=None, ref=None, timestamps
     times = np.asarray(times, np.int64)
     assert times.shape == (n,) and (np.diff(times) > 0).all() and (np.diff(times) < 1 << 31).all()
     assert 0 <= refractory_us < 1 << 31 and first_frame >= 0
+    assert refractory_us == 0 or int(times[-1]) <= np.iinfo(np.int64).max - refractory_us, "t_ok would pass the int64 range"
     lut = linear_lut() if lut is None else np.asarray(lut, np.int64)
     con = np.broadcast_to(np.asarray(c_on, np.int64), (h, w)).reshape(-1)
     coff = np.broadcast_to(np.asarray(c_off, np.int64), (h, w)).reshape(-1)
@@ -95,7 +98,8 @@ def events_sensor_ref(frames, times, c_on, c_off, lut=None, ref=None, timestamps
             cp.append(pix); cpol.append(np.full(pix.size, pol, np.int64)); ckind.append(np.zeros(pix.size, np.int64)); cj.append(j); ct.append(t)
         if k >= 1:
             delta = int(times[k] - times[k - 1])
-            has_on, o_on, has_off, o_off = noise_candidates(seed, npx, first_frame + k, delta, ron, roff)
+            has_on, o_on, has_off, o_off = noise_candidates(seed, npx, first_frame + k if counter_of is None else counter_of(first_frame, k),
+                                                           delta, ron, roff)
             for pol, has, off, m in ((0, has_on, o_on, m_on), (1, has_off, o_off, m_off)):
                 idx = np.flatnonzero(has)
                 drawn[pol] += idx.size

@@ -234,6 +234,8 @@ C_REFUSALS = [
     ("timestamps_mode unknown", "both", {}, dict(mode=2), "EINVAL", "timestamps_mode 2"),
     ("t_ok_in without t_ok_out", "emit", dict(d_t_ok_in="plane"), dict(t_ok_out=None), "EINVAL", "d_t_ok_in without d_t_ok_out"),
     ("c_on 0 (the shared check)", "both", {}, dict(c_on=0), "EINVAL", "thresholds c_on = 0, c_off = 1792"),
+    ("t_ok beyond int64", "both", {}, dict(times=np.iinfo(np.int64).max - 799 + 1000 * np.arange(-5, 1, dtype=np.int64)), "EINVAL",
+     "times[5] = 9223372036854775008 with refractory_us = 800"),
 ]
 
 
@@ -267,9 +269,9 @@ def test_c_entries_refuse_before_any_launch(nsof_lib, ctx, c_stack, what, entrie
     if fields.get("d_t_ok_in") == "plane":
         fields["d_t_ok_in"] = out["t_ok"].data_ptr()
     st = _struct(nsof_lib, **fields)
-    a = dict(mode=1, c_on=2560, t_ok_out=out["t_ok"].data_ptr())
+    a = dict(mode=1, c_on=2560, t_ok_out=out["t_ok"].data_ptr(), times=times)
     a.update(over)
-    common = (ctx.ptr, d.data_ptr(), d.stride(1), d.stride(0), 6, 19, 37, times.ctypes.data, lut.ctypes.data, a["c_on"], 1792, None, None, 0)
+    common = (ctx.ptr, d.data_ptr(), d.stride(1), d.stride(0), 6, 19, 37, a["times"].ctypes.data, lut.ctypes.data, a["c_on"], 1792, None, None, 0)
     for entry in ("count", "emit") if entries == "both" else (entries,):
         if entry == "count":
             b = np.full(7, -1, np.int64)
