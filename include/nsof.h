@@ -1117,6 +1117,52 @@ int nsof_events_from_frames_sensor_emit_dev(nsof_ctx* ctx, const uint8_t* d_fram
 /* The four words c0..c3 of the noise block of (seed, pixel, frame) above, computed on the host: the bits the kernels use. */
 void nsof_events_noise_draw(uint64_t seed, uint32_t pixel, int64_t frame, uint32_t* out);
 
+/* Background-activity filter for event streams (csrc/events_denoise.hip): the spatiotemporal
+ * correlation filter, in integers throughout.  The stream: d_x, d_y (int16), d_p (int8), d_t (int64), DEVICE arrays of n
+ * events, 0 <= n < 2^31, on a height x width sensor; t must not decrease over the stream and may hold any int64 -- the
+ * schema and order nsof_events_from_frames_*_dev emit.  State: last, int64 [C][height][width], C = 2 with same_polarity
+ * (plane 0 for p > 0, plane 1 otherwise), else 1: the time of the latest event seen at a pixel, INT64_MIN for never.
+ * d_last_in NULL: every pixel starts at never.  In stream order, for event i at pixel q of channel c:
+ *     lo      = max(t_i - dt_us, INT64_MIN + 1), formed without a wrap
+ *     support = the pixels m of the square of `radius` around q, clipped to the sensor, other than q itself unless
+ *               include_self, with last_c[m] >= lo
+ *     keep_i  = support >= min_support;   then last_c[q] = t_i, kept or not
+ * so that a decision depends on the input stream alone.  A run over events [0, k) followed by one over [k, n) from the
+ * first one's d_last_out gives the keep bytes, the kept stream and the final last of the one-shot run, bit for bit, for
+ * any k; two runs give the same bits (no float, no atomics).
+ *
+ * The output size depends on the data, so there are two entries.  nsof_events_denoise_mark_dev validates the stream on
+ * the device, writes d_keep (uint8 [n], DEVICE: 1 kept, 0 dropped), synchronises and fills the HOST *n_kept_out and, for
+ * the n_bounds HOST bounds (non-decreasing, in [0, n]; e.g. the generator's frame_bounds), bounds_out[k] = the kept events
+ * before bounds[k] (HOST [n_bounds]): the bounds of the kept stream.  nsof_events_denoise_compact_dev takes d_keep back,
+ * validates and counts again on the stream, writes the kept events in input order to d_x_out, d_y_out, d_p_out, d_t_out
+ * (DEVICE, `capacity` elements) and the updated state to d_last_out (DEVICE [C][height][width], may be d_last_in, may be
+ * NULL); it is asynchronous on the context's stream (only growing the context's workspace waits for it).  The compact pass
+ * compares the kept count it has formed itself with `capacity` on the device and writes nothing at all, d_last_out
+ * included, unless they are equal and the stream is valid: a keep array of another call cannot send a store past
+ * `capacity`.
+ * NSOF_EINVAL, nothing launched and nothing written, the value named in nsof_last_error: n outside [0, 2^31), height or
+ * width outside [1, 32767], same_polarity or include_self outside {0, 1}, a null stream array or d_keep with n > 0; mark
+ * alone: dt_us outside [0, 2^31), radius outside {1, 2}, min_support outside [1, (2 * radius + 1)^2], a null n_kept_out,
+ * n_bounds < 0 or above 2^24, bounds without bounds_out, bounds that decrease or leave [0, n]; compact alone: capacity
+ * outside [0, n], a null output array with capacity > 0.  A coordinate outside the sensor or a t[i] < t[i-1] is seen on
+ * the device only (such an event addresses nothing and supports nothing): the mark entry returns NSOF_EINVAL after its
+ * validation pass without writing d_keep, *n_kept_out or bounds_out, the compact entry writes nothing.  n = 0: the mark
+ * entry launches nothing and returns zeros, the compact entry only copies the state.
+ * Workspace, in the context's workspace, grown on demand and never shrunk before nsof_destroy: about 24 bytes per event
+ * -- the words, their sorted copy, and the sort's temporary storage, which holds a third array of n words (the sort is not
+ * double-buffered) besides its histograms -- plus 8 bytes per 256 events (the chunk counts) and 8 bytes per bound.
+ * Nothing of the sensor's size: the (channel, pixel) segments of the sorted stream are found by binary search, not through
+ * a table of offsets.  A call the workspace cannot hold returns NSOF_ENOMEM: run long streams in chunks. */
+int nsof_events_denoise_mark_dev(nsof_ctx* ctx, const int16_t* d_x, const int16_t* d_y, const int8_t* d_p, const int64_t* d_t,
+                                 int64_t n, int height, int width, int64_t dt_us, int radius, int min_support,
+                                 int same_polarity, int include_self, const int64_t* d_last_in, const int64_t* bounds,
+                                 int64_t n_bounds, uint8_t* d_keep, int64_t* n_kept_out, int64_t* bounds_out);
+int nsof_events_denoise_compact_dev(nsof_ctx* ctx, const int16_t* d_x, const int16_t* d_y, const int8_t* d_p,
+                                    const int64_t* d_t, int64_t n, int height, int width, int same_polarity,
+                                    const int64_t* d_last_in, const uint8_t* d_keep, int64_t capacity, int16_t* d_x_out,
+                                    int16_t* d_y_out, int8_t* d_p_out, int64_t* d_t_out, int64_t* d_last_out);
+
 #ifdef __cplusplus
 }
 #endif

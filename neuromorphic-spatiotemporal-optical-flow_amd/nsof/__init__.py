@@ -37,6 +37,7 @@ from .frames import compress_image, crop_image, im2double, imresize_lanczos3, pr
 from .flowviz import flow_to_image, flow_to_image_dev, flow_uv_to_colors, make_colorwheel, save_viz, viz  # noqa: F401,E402
 from .flowstats import events_flow_variability_dev, flow_ensemble_dev, flow_ensemble_summary  # noqa: F401,E402
 from .events import events_from_frames_dev, events_from_video_dev, events_noise_draw, linear_response, log_response, render_box_frames  # noqa: F401,E402
+from .denoise import events_denoise_dev  # noqa: F401,E402
 
 __all__ = ["calcOpticalFlowFarneback", "install", "uninstall", "FarnebackParams", "farneback_batch", "Context",
            "default_context", "simulate", "update_state", "resistance_exp", "Accumulator", "NsofError", "error"]

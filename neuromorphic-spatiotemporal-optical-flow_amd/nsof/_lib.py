@@ -222,6 +222,12 @@ SIGNATURES = {
                                                      _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(EventsSensor), _vp]),
     # seed, pixel, frame, out [4]
     "nsof_events_noise_draw": (None, [C.c_uint64, C.c_uint32, _i64, _vp]),
+    # ctx, x, y, p, t, n, height, width, dt_us, radius, min_support, same_polarity, include_self, last_in, bounds, n_bounds, keep,
+    # n_kept_out, bounds_out
+    "nsof_events_denoise_mark_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i64, _i, _i, _i, _i, _vp, _vp, _i64, _vp,
+                                          C.POINTER(_i64), _vp]),
+    # ctx, x, y, p, t, n, height, width, same_polarity, last_in, keep, capacity, x_out, y_out, p_out, t_out, last_out
+    "nsof_events_denoise_compact_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import gating
 from .accumulator import Accumulator, slice_index_array
+from .denoise import DENOISE_KEYS, events_denoise_dev, filter_args
 from .events import events_from_frames_dev, events_from_video_dev, render_box_frames  # noqa: F401  (frames -> events, in HBM)
 from .flowstats import events_flow_variability_dev  # noqa: F401  (the flow study of the event pipeline lives with its statistics)
 
@@ -274,14 +275,20 @@ def events_to_flow_sequence(x, y, p, t, sensor_hw, params=None, slice_us=1000, a
 
 
 def video_to_flow_sequence(frames, times_us=None, *, frame_us=None, threshold=10.0, threshold_off=None, threshold_maps=None,
-                           response=None, ref=None, timestamps="linear", p_on=1, p_off=-1, sensor=None, ctx=None, **accumulator_args):
+                           response=None, ref=None, timestamps="linear", p_on=1, p_off=-1, sensor=None, denoise=None, ctx=None,
+                           **accumulator_args):
     """A grey video in HBM through the event pipeline: ``events_from_frames_dev(frames, ...)`` (the arguments up to
     ``p_off``) turns the frames into an event stream in HBM, one copy brings it to the host (the accumulator's entries
     stage host event arrays), and ``events_to_flow_sequence(x, y, p, t, (H, W), **accumulator_args)`` accumulates it and
     takes the flow between its surface frames.  Returns ``(surface frames uint8 [m][H][W], flows float32 [m-1][H][W][2],
     events)``, ``events`` the generator's result dict (``x, y, p, t`` CUDA tensors, ``frame_bounds``, ``ref``).  ``sensor``: a
     dict of the generator's sensor arguments (``refractory_us``, ``noise``, ``t_ok``, ``first_frame``), forwarded to it --
-    apart from ``accumulator_args``, where ``refractory_us`` is the accumulator's; ``events`` then carries ``t_ok`` too."""
+    apart from ``accumulator_args``, where ``refractory_us`` is the accumulator's; ``events`` then carries ``t_ok`` too.
+    ``denoise``: a dict of the keyword arguments of ``events_denoise_dev`` (``dt_us``, and any of ``radius``, ``min_support``,
+    ``same_polarity``, ``include_self``, ``last``): the background-activity filter is applied to the stream in HBM, between the
+    generator and the host copy, with the generator's ``frame_bounds`` as its bounds.  ``events`` then holds the kept stream
+    (``x, y, p, t`` and its ``frame_bounds``) and gains ``keep`` (uint8 CUDA, one byte per generated event), ``n_kept`` and
+    ``last``.  A bad key or value of the dict is refused before the generator runs.  ``None``: no filter."""
     from . import _lib
     from .context import default_context
     from .errors import NsofValueError
@@ -289,11 +296,24 @@ def video_to_flow_sequence(frames, times_us=None, *, frame_us=None, threshold=10
     if not isinstance(sensor, dict) or any(k not in ("refractory_us", "noise", "t_ok", "first_frame") for k in sensor):
         raise NsofValueError(f"video_to_flow_sequence: sensor = {sensor!r}; a dict of refractory_us, noise, t_ok, first_frame expected",
                              _lib.NSOF_EINVAL)
+    if denoise is not None and (not isinstance(denoise, dict) or "dt_us" not in denoise or any(k not in DENOISE_KEYS for k in denoise)):
+        raise NsofValueError(f"video_to_flow_sequence: denoise = {denoise!r}; a dict of dt_us and any of radius, min_support, "
+                             "same_polarity, include_self, last expected", _lib.NSOF_EINVAL)
+    if denoise is not None and getattr(frames, "ndim", 0) == 3:   # (frames of another kind: the generator's refusal, below)
+        # the filter's values too are refused here, before the generator has done any device work
+        filter_args("video_to_flow_sequence: denoise", (int(frames.shape[1]), int(frames.shape[2])), **denoise)
+        last = denoise.get("last")
+        if last is not None and last.device != frames.device:
+            raise NsofValueError("video_to_flow_sequence: denoise: last must be a CUDA tensor on the frames' device", _lib.NSOF_EINVAL)
     # (the generator refuses its arguments before it asks for a context; the default one is process-wide)
     ev = events_from_frames_dev(frames, times_us, frame_us=frame_us, threshold=threshold, threshold_off=threshold_off,
                                 threshold_maps=threshold_maps, response=response, ref=ref, timestamps=timestamps, p_on=p_on,
                                 p_off=p_off, ctx=ctx, **sensor)
     ctx = ctx or default_context()
+    if denoise is not None:
+        kept = events_denoise_dev(ev["x"], ev["y"], ev["p"], ev["t"], (int(frames.shape[1]), int(frames.shape[2])),
+                                  bounds=ev["frame_bounds"], ctx=ctx, **denoise)
+        ev = dict(ev, frame_bounds=kept.pop("bounds"), **kept)
     ctx.synchronize()
     x, y, p, t = (ev[k].cpu().numpy() for k in "xypt")
     surfaces, flows = events_to_flow_sequence(x, y, p, t, (int(frames.shape[1]), int(frames.shape[2])), ctx=ctx, **accumulator_args)
