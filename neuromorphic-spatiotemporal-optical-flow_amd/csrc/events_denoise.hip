@@ -16,25 +16,24 @@
 //                hot pixel's long segment costs log2 N steps like any other).  That word is the latest earlier event at
 //                n, if its key is n's; else the incoming plane decides.  The searches of one row of the window run side by
 //                side (2 * radius + 1 independent gathers per step).  Writes keep[i].
-//   k_ed_count + k_ed_scan   the kept events of every 256 consecutive ones, then the exclusive prefix of those counts in
+//   k_ed_count + k_ev_scan   the kept events of every 256 consecutive ones, then the exclusive prefix of those counts in
 //                index order by one workgroup: the total.  k_ed_bounds: the kept count before each of the caller's bounds.
-//   k_ed_compact every workgroup re-forms the prefix inside its 256 events (DPP scan, the waves' sums through LDS) and
-//                scatters the kept x, y, p, t: the input order with the gaps closed.
+//   k_ed_compact every workgroup re-forms the prefix inside its 256 events and scatters the kept x, y, p, t: the input
+//                order with the gaps closed.
 //   k_ed_last_init + k_ed_last_set   last_out = last_in (or never), then the t of every segment's last word.
 //
-// No float and no atomics: every offset is a sum of integers in a fixed order, so two runs give the same bits.  The
-// compact entry trusts nothing it is handed: it validates the stream again, sorts again (for the segments' ends), counts the
-// keep bytes itself, and all its kernels leave unless that total equals the capacity the outputs were sized for and no
-// validation flag is up (ed_guard).
+// The wave scan, the workgroup prefix, the table scan (k_ev_scan) and the guard are the event kernels' shared ones
+// (events_common.h).  No float and no atomics: every offset is a sum of integers in a fixed order, so two runs give the same
+// bits.  The compact entry trusts nothing it is handed: it validates the stream again, sorts again (for the segments' ends),
+// counts the keep bytes itself, and all its kernels leave unless that total equals the capacity the outputs were sized for and
+// no validation flag is up (ev_guard on meta).
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "nsof_internal.h"
+#include "events_common.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int ED_WG = 256;   // threads of every workgroup; the count and compact kernels own ED_WG consecutive events (a chunk)
+constexpr int ED_WG = EV_WG;   // threads of every workgroup; the count and compact kernels own ED_WG consecutive events (a chunk)
 // meta: [0] the kept total, [1] a coordinate outside the sensor, [2] a decreasing t
 constexpr int ED_META = 4;
 
@@ -47,8 +46,6 @@ struct ed_stream {
     unsigned plane;           // H * W
     int channels;             // 2 with same_polarity
 };
-
-__device__ __forceinline__ bool ed_guard(const u64* meta, u64 expected) { return meta[0] == expected && meta[1] == 0 && meta[2] == 0; }
 
 __global__ __launch_bounds__(ED_WG) void k_ed_keys(ed_stream s, u64* __restrict__ words, u64* __restrict__ meta)
 {
@@ -129,24 +126,6 @@ __global__ __launch_bounds__(ED_WG) void k_ed_mark(ed_stream s, ed_rule r, const
     keep[i] = support >= r.min_support;
 }
 
-// Inclusive prefix sum over the 64 lanes of a wave (every lane active) by DPP moves: within the rows of 16 lanes by shifts
-// of 1, 2, 4 and 8, then lane 15 of rows 0 and 2 into rows 1 and 3, then lane 31 into rows 2 and 3.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned ed_dpp(unsigned v)
-{
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ unsigned ed_wave_scan(unsigned v)
-{
-    v += ed_dpp<0x111, 0xf>(v);   // row_shr:1
-    v += ed_dpp<0x112, 0xf>(v);   // row_shr:2
-    v += ed_dpp<0x114, 0xf>(v);   // row_shr:4
-    v += ed_dpp<0x118, 0xf>(v);   // row_shr:8
-    v += ed_dpp<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v += ed_dpp<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
-    return v;
-}
-
 // Whether the thread's event of the chunk is kept (one below `limit` only), the kept events of the workgroup's earlier
 // threads (excl) and of the whole workgroup (all).  Every thread of the workgroup calls it.
 __device__ __forceinline__ bool ed_chunk_prefix(const uint8_t* __restrict__ keep, size_t chunk, size_t limit, unsigned (&sh)[4],
@@ -154,18 +133,12 @@ __device__ __forceinline__ bool ed_chunk_prefix(const uint8_t* __restrict__ keep
 {
     const size_t i = chunk * ED_WG + threadIdx.x;
     const bool kept = i < limit && keep[i] != 0;
-    const unsigned incl = ed_wave_scan(kept);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 63) sh[wave] = incl;
+    const unsigned incl = ev_wave_scan(kept);
+    ev_wg_put(sh, incl);
     __syncthreads();
-    unsigned before = 0;
-    all = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        if (w < wave) before += sh[w];
-        all += sh[w];
-    }
-    excl = before + incl - kept;
+    const ev_wg_sums<unsigned> s = ev_wg_collect(sh);
+    all = s.all;
+    excl = s.before + incl - kept;
     return kept;
 }
 
@@ -175,31 +148,6 @@ __global__ __launch_bounds__(ED_WG) void k_ed_count(const uint8_t* __restrict__ 
     unsigned excl, all;
     ed_chunk_prefix(keep, blockIdx.x, n, sh, excl, all);
     if (threadIdx.x == 0) table[blockIdx.x] = all;
-}
-
-// table [len]: exclusive prefix sums in place, in index order; the sum to *tot.  One workgroup.
-__global__ __launch_bounds__(ED_WG) void k_ed_scan(u64* __restrict__ table, size_t len, u64* __restrict__ tot)
-{
-    __shared__ unsigned sh[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 carry = 0;
-    for (size_t b = 0; b < len; b += ED_WG) {
-        const size_t i = b + threadIdx.x;
-        const unsigned v = i < len ? (unsigned)table[i] : 0u;   // a chunk's count: at most ED_WG
-        const unsigned incl = ed_wave_scan(v);                  // ED_WG of them: at most 2^16
-        if (lane == 63) sh[wave] = incl;
-        __syncthreads();
-        unsigned before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            if (w < wave) before += sh[w];
-            all += sh[w];
-        }
-        if (i < len) table[i] = carry + before + (incl - v);
-        carry += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *tot = carry;
 }
 
 // out[k]: the kept events before bounds[k] (in [0, n], checked by the entry).  One workgroup per bound.
@@ -227,7 +175,7 @@ struct ed_out {
 __global__ __launch_bounds__(ED_WG) void k_ed_compact(ed_stream s, const uint8_t* __restrict__ keep, const u64* __restrict__ table,
                                                       const u64* __restrict__ meta, u64 expected, ed_out o)
 {
-    if (!ed_guard(meta, expected)) return;
+    if (!ev_guard(meta, expected)) return;
     __shared__ unsigned sh[4];
     unsigned excl, all;
     if (!ed_chunk_prefix(keep, blockIdx.x, s.n, sh, excl, all)) return;
@@ -242,7 +190,7 @@ __global__ __launch_bounds__(ED_WG) void k_ed_compact(ed_stream s, const uint8_t
 __global__ __launch_bounds__(ED_WG) void k_ed_last_init(size_t count, const int64_t* __restrict__ last_in, const u64* __restrict__ meta,
                                                         u64 expected, int64_t* __restrict__ last_out)
 {
-    if (!ed_guard(meta, expected)) return;
+    if (!ev_guard(meta, expected)) return;
     const size_t i = (size_t)blockIdx.x * ED_WG + threadIdx.x;
     if (i < count) last_out[i] = last_in ? last_in[i] : INT64_MIN;
 }
@@ -251,7 +199,7 @@ __global__ __launch_bounds__(ED_WG) void k_ed_last_init(size_t count, const int6
 __global__ __launch_bounds__(ED_WG) void k_ed_last_set(ed_stream s, const u64* __restrict__ sorted, const u64* __restrict__ meta,
                                                        u64 expected, int64_t* __restrict__ last_out)
 {
-    if (!ed_guard(meta, expected)) return;   // (no flag is up: every key is below C * H * W)
+    if (!ev_guard(meta, expected)) return;   // (no flag is up: every key is below C * H * W)
     const unsigned j = blockIdx.x * ED_WG + threadIdx.x;
     if (j >= s.n) return;
     const u64 w = sorted[j];
@@ -273,15 +221,13 @@ struct ed_call {
 // Every refusal of the arguments both entries share; nothing launched.
 int ed_check(nsof_ctx* ctx, const char* who, const ed_call& c)
 {
-    if (c.n < 0 || c.n >= (1ll << 31)) return nsof_set_error(ctx, NSOF_EINVAL, "%s: n = %lld is outside [0, 2^31)", who, (long long)c.n);
-    if (c.H < 1 || c.W < 1 || c.H > 32767 || c.W > 32767)
+    if (c.n < 0 || c.n >= EV_MAX_EVENTS) return nsof_set_error(ctx, NSOF_EINVAL, "%s: n = %lld is outside [0, 2^31)", who, (long long)c.n);
+    if (!ev_sensor_ok(c.H, c.W))
         return nsof_set_error(ctx, NSOF_EINVAL, "%s: a %dx%d sensor; height and width lie in [1, 32767], the int16 coordinates of an event",
                               who, c.W, c.H);
     if (c.same_polarity != 0 && c.same_polarity != 1)
         return nsof_set_error(ctx, NSOF_EINVAL, "%s: same_polarity = %d is neither 0 nor 1", who, c.same_polarity);
-    if (c.n > 0 && (!c.d_x || !c.d_y || !c.d_p || !c.d_t))
-        return nsof_set_error(ctx, NSOF_EINVAL, "%s: null pointer (%s)", who, !c.d_x ? "d_x" : !c.d_y ? "d_y" : !c.d_p ? "d_p" : "d_t");
-    return NSOF_OK;
+    return c.n > 0 ? ev_check_stream(ctx, who, c.d_x, c.d_y, c.d_p, c.d_t) : NSOF_OK;
 }
 
 // The workspace of a call, carved from ctx->tmp in one reservation.
@@ -309,12 +255,13 @@ int ed_reserve(nsof_ctx* ctx, const ed_call& c, size_t n_bounds, ed_plan* pl)
     if (c.n)
         NSOF_HIP(ctx, rocprim::radix_sort_keys(nullptr, pl->sort_bytes, (const u64*)nullptr, (u64*)nullptr, (size_t)c.n, 32u,
                                                32u + pl->key_bits, ctx->stream));
-    const size_t words = align_up((size_t)c.n * sizeof(u64), 256);
-    const size_t o_sorted = words, o_table = 2 * words, o_meta = o_table + align_up((size_t)pl->n_wg * sizeof(u64), 256);
-    const size_t o_bounds = o_meta + align_up(ED_META * sizeof(u64), 256), o_sort = o_bounds + align_up(n_bounds * sizeof(int64_t), 256);
+    ev_carve w;
+    const size_t o_words = w.take((size_t)c.n * sizeof(u64)), o_sorted = w.take((size_t)c.n * sizeof(u64));
+    const size_t o_table = w.take((size_t)pl->n_wg * sizeof(u64)), o_meta = w.take(ED_META * sizeof(u64));
+    const size_t o_bounds = w.take(n_bounds * sizeof(int64_t)), o_sort = w.at;
     if (int rc = ctx->tmp.reserve(ctx, o_sort + pl->sort_bytes)) return rc;
     char* ws = (char*)ctx->tmp.p;
-    pl->words = (u64*)ws;
+    pl->words = (u64*)(ws + o_words);
     pl->sorted = (u64*)(ws + o_sorted);
     pl->table = (u64*)(ws + o_table);
     pl->meta = (u64*)(ws + o_meta);
@@ -340,7 +287,8 @@ int ed_count_pass(nsof_ctx* ctx, const ed_plan& pl, const uint8_t* d_keep)
 {
     hipLaunchKernelGGL(k_ed_count, dim3(pl.n_wg), dim3(ED_WG), 0, ctx->stream, d_keep, (size_t)pl.s.n, pl.table);
     NSOF_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_ed_scan, dim3(1), dim3(ED_WG), 0, ctx->stream, pl.table, (size_t)pl.n_wg, pl.meta);
+    // one row; an entry is a chunk's count, at most ED_WG, so the ED_WG entries of a scan step add up to at most 2^16
+    hipLaunchKernelGGL(k_ev_scan<false>, dim3(1), dim3(ED_WG), 0, ctx->stream, pl.table, (size_t)pl.n_wg, pl.meta);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }

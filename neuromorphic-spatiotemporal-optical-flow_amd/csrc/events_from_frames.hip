@@ -9,7 +9,7 @@
 //                per frame and polarity the wave adds its lanes' counts (a DPP prefix sum in 32 bits while every lane's
 //                count is below 2^24, else a 64-bit butterfly) and, once per batch, the workgroup's first 2 * EF_BATCH
 //                threads add the four waves' sums into counts[frame][polarity][workgroup].
-//   k_ef_scan    an exclusive scan of every row of that table in place (one workgroup per row, 256 entries at a time)
+//   k_ev_scan    an exclusive scan of every row of that table in place (one workgroup per row, 256 entries at a time)
 //                and the rows' sums; a second launch scans the 2 n sums: the bases of the (frame, polarity) rows and the total.
 //   k_ef_emit    the same walk; per batch the waves take an inclusive prefix (DPP) of the counts of each frame and polarity,
 //                the four waves' sums go through LDS, and every pixel writes its events from row base + workgroup offset +
@@ -32,18 +32,17 @@
 // What the two passes must agree on exists once: ef_frame builds a frame's candidates (the level step, and with SENSOR the
 // times and the noise draw) for k_ef_count and for the sensor emit body, ef_survivors counts them (without SENSOR: the
 // candidates themselves), ef_stamp is the linear stamp of a crossing, ef_store writes an event, ef_bases forms a batch's row
-// bases and ef_guard is the one test under which the emit and unpack kernels write.  The emit pass keeps two bodies,
+// bases and ev_guard is the one test under which the emit and unpack kernels write.  The wave scan, the workgroup prefix, the
+// table scan and the guard are the event kernels' shared ones (events_common.h).  The emit pass keeps two bodies,
 // ef_emit_plain and ef_emit_sensor: folded into one, the plain linear kernel went from 64 to 90 VGPRs.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "accum_c2c.h"
-#include "nsof_internal.h"
+#include "events_common.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int EF_WG = 256;      // pixels per workgroup
+constexpr int EF_WG = EV_WG;    // pixels per workgroup
 constexpr int EF_BATCH = 4;     // frames whose loads are issued before the first of them is consumed
 constexpr int EF_LUT_MAX = 1 << 30;
 
@@ -120,32 +119,6 @@ __device__ __forceinline__ unsigned ef_step(int& r, int b, int c_on, int c_off, 
     const unsigned step = m * (unsigned)c;
     r = (int)(on ? (unsigned)r + step : (unsigned)r - step);
     return m;
-}
-
-// Inclusive prefix sum over the 64 lanes of a wave (every lane active) by DPP moves, without the LDS crossbar a shuffle
-// goes through: within the rows of 16 lanes by shifts of 1, 2, 4 and 8, then lane 15 of rows 0 and 2 into rows 1 and 3,
-// then lane 31 into rows 2 and 3.  A lane without a source adds 0.  Lane 63 holds the wave's sum.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned ef_dpp(unsigned v)
-{
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ unsigned ef_wave_scan(unsigned v)
-{
-    v += ef_dpp<0x111, 0xf>(v);   // row_shr:1
-    v += ef_dpp<0x112, 0xf>(v);   // row_shr:2
-    v += ef_dpp<0x114, 0xf>(v);   // row_shr:4
-    v += ef_dpp<0x118, 0xf>(v);   // row_shr:8
-    v += ef_dpp<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v += ef_dpp<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
-    return v;
-}
-__device__ __forceinline__ unsigned ef_wave_last(unsigned v) { return (unsigned)__builtin_amdgcn_readlane((int)v, 63); }
-
-__device__ __forceinline__ u64 sat_add(u64 a, u64 b)
-{
-    const u64 s = a + b;
-    return s < a ? ~0ull : s;
 }
 
 // ---- the sensor model (SENSOR instantiations only) ------------------------------------------------------------------
@@ -331,8 +304,8 @@ __global__ __launch_bounds__(EF_WG) void k_ef_count(ef_args a, ef_sensor s, u64*
             if (!q.in) n_on = n_off = 0;
             u64 s_on, s_off;
             if (!__any((n_on | n_off) >> 24)) {   // every lane below 2^24 (any frame of the linear table): the wave's sums fit 32 bits
-                s_on = ef_wave_last(ef_wave_scan(n_on));
-                s_off = ef_wave_last(ef_wave_scan(n_off));
+                s_on = ev_wave_last(ev_wave_scan(n_on));
+                s_off = ev_wave_last(ev_wave_scan(n_off));
             } else {
                 s_on = n_on;
                 s_off = n_off;
@@ -357,46 +330,8 @@ __global__ __launch_bounds__(EF_WG) void k_ef_count(ef_args a, ef_sensor s, u64*
     }
 }
 
-// Row blockIdx.x of data [rows][len]: exclusive prefix sums in place, the row's sum to tot[row].  Saturating.
-__global__ __launch_bounds__(EF_WG) void k_ef_scan(u64* __restrict__ data, size_t len, u64* __restrict__ tot)
-{
-    __shared__ u64 sh[4];
-    u64* row = data + (size_t)blockIdx.x * len;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 carry = 0;
-    for (size_t base = 0; base < len; base += EF_WG) {
-        const size_t i = base + threadIdx.x;
-        u64 incl = i < len ? row[i] : 0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u64 up = __shfl_up(incl, o, 64);
-            if (lane >= o) incl = sat_add(incl, up);
-        }
-        u64 excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 0;
-        if (lane == 63) sh[wave] = incl;
-        __syncthreads();
-        u64 before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            if (w < wave) before = sat_add(before, sh[w]);
-            all = sat_add(all, sh[w]);
-        }
-        if (i < len) row[i] = sat_add(carry, sat_add(before, excl));
-        carry = sat_add(carry, all);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) tot[blockIdx.x] = carry;
-}
-
 // meta: [0 .. 2n) the bases of the (frame, polarity) rows, [2n] the total, [2n + 1] the bad-threshold flag, [2n + 2] the
-// long-walk flag (which the plain kernels never raise).  The emit and unpack kernels write only under the guard: the total
-// is the one the caller sized the outputs for and no flag is up.  The same for every thread of the grid.
-__device__ __forceinline__ bool ef_guard(const u64* meta, int n, u64 expected)
-{
-    const u64* m = meta + 2 * (size_t)n;
-    return m[0] == expected && m[1] == 0 && m[2] == 0;
-}
+// long-walk flag (which the plain kernels never raise).  The emit and unpack kernels write only under ev_guard(meta + 2n).
 
 // Where the emit pass writes.
 struct ef_out {
@@ -445,7 +380,6 @@ __device__ __forceinline__ void ef_emit_plain(const ef_args& a, const u64* __res
     __shared__ int sh_lut[256];
     __shared__ unsigned sh[2][EF_BATCH][2][4];
     ef_px q = ef_init(a, sh_lut);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t t_first = a.times[0];
     int prev_level = 0;   // L[k - 1]
     int set = 0;
@@ -466,11 +400,9 @@ __device__ __forceinline__ void ef_emit_plain(const ef_args& a, const u64* __res
             if (k0 + j < a.n) m[j] = ef_step(q.r, lev[j], q.c_on, q.c_off, on[j]);
             if (!q.in) m[j] = 0;
             // the total is below 2^31 (the guard), so 32 bits hold every prefix
-            const unsigned i_on = ef_wave_scan(on[j] ? m[j] : 0u), i_off = ef_wave_scan(on[j] ? 0u : m[j]);
-            if (lane == 63) {
-                sh[set][j][0][wave] = i_on;
-                sh[set][j][1][wave] = i_off;
-            }
+            const unsigned i_on = ev_wave_scan(on[j] ? m[j] : 0u), i_off = ev_wave_scan(on[j] ? 0u : m[j]);
+            ev_wg_put(sh[set][j][0], i_on);
+            ev_wg_put(sh[set][j][1], i_off);
             excl[j] = (on[j] ? i_on : i_off) - m[j];
         }
         __syncthreads();
@@ -481,10 +413,7 @@ __device__ __forceinline__ void ef_emit_plain(const ef_args& a, const u64* __res
             const int a_level = prev_level;
             prev_level = lev[j];
             const int pol = on[j] ? 0 : 1;
-            unsigned before = 0;
-#pragma unroll
-            for (int w = 0; w < 4; w++)
-                if (w < wave) before += sh[set][j][pol][w];
+            const unsigned before = ev_wg_collect(sh[set][j][pol]).before;
             if (m[j] == 0) continue;
             size_t at = (size_t)(on[j] ? base[j][0] : base[j][1]) + before + excl[j];
             const int64_t t_k = a.times[k];
@@ -514,7 +443,6 @@ __device__ __forceinline__ void ef_emit_sensor(const ef_args& a, const ef_sensor
     ef_px q = ef_init(a, sh_lut);
     ef_spx sp = ef_sensor_init(s, q);
     int64_t t_ok = sp.t_ok;   // the writing walk's copy; sp.t_ok is the counting walk's
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t t_first = a.times[0];
     int prev_level = 0;   // L[k - 1]
     int set = 0;
@@ -531,24 +459,16 @@ __device__ __forceinline__ void ef_emit_sensor(const ef_args& a, const ef_sensor
             ef_survivors<LINEAR, 1>(s, c[j], sp.t_ok, cnt[j][0], cnt[j][1]);
             if (!q.in) cnt[j][0] = cnt[j][1] = 0;
             // the total is below 2^31 (the guard), so 32 bits hold every prefix
-            incl[j][0] = ef_wave_scan(cnt[j][0]);
-            incl[j][1] = ef_wave_scan(cnt[j][1]);
-            if (lane == 63) {
-                sh[set][j][0][wave] = incl[j][0];
-                sh[set][j][1][wave] = incl[j][1];
-            }
+            incl[j][0] = ev_wave_scan(cnt[j][0]);
+            incl[j][1] = ev_wave_scan(cnt[j][1]);
+            ev_wg_put(sh[set][j][0], incl[j][0]);
+            ev_wg_put(sh[set][j][1], incl[j][1]);
         }
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < EF_BATCH; j++) {
             if (k0 + j >= a.n) break;
-            unsigned before[2] = {0, 0};
-#pragma unroll
-            for (int w = 0; w < 4; w++)
-                if (w < wave) {
-                    before[0] += sh[set][j][0][w];
-                    before[1] += sh[set][j][1][w];
-                }
+            const unsigned before[2] = {ev_wg_collect(sh[set][j][0]).before, ev_wg_collect(sh[set][j][1]).before};
             if (!q.in || (c[j].m == 0 && c[j].off_on == EF_NONE && c[j].off_off == EF_NONE)) continue;
             // the pixel's ON events are [end_on - cnt, end_on), its OFF events likewise
             const size_t end_on = (size_t)base[j][0] + before[0] + incl[j][0], end_off = (size_t)base[j][1] + before[1] + incl[j][1];
@@ -571,7 +491,7 @@ template <int LINEAR, int SENSOR>
 __global__ __launch_bounds__(EF_WG) void k_ef_emit(ef_args a, ef_sensor s, const u64* __restrict__ table, const u64* __restrict__ meta,
                                                    u64 expected, ef_out o)
 {
-    if (!ef_guard(meta, a.n, expected)) return;
+    if (!ev_guard(meta + 2 * (size_t)a.n, expected)) return;
     if constexpr (SENSOR)
         ef_emit_sensor<LINEAR>(a, s, table, meta, o);
     else
@@ -583,7 +503,7 @@ __global__ __launch_bounds__(EF_WG) void k_ef_unpack(size_t count, const u64* __
                                                      int p_off, int16_t* __restrict__ ox, int16_t* __restrict__ oy,
                                                      int8_t* __restrict__ op, int64_t* __restrict__ ot)
 {
-    if (!ef_guard(meta, n, expected)) return;
+    if (!ev_guard(meta + 2 * (size_t)n, expected)) return;
     const size_t i = (size_t)blockIdx.x * EF_WG + threadIdx.x;
     if (i >= count) return;
     const unsigned v = vals[i];
@@ -613,7 +533,7 @@ int ef_check(nsof_ctx* ctx, const char* who, const ef_call& c)
 {
     if (c.n < 1 || c.H < 1 || c.W < 1)
         return nsof_set_error(ctx, NSOF_EINVAL, "%s: %d frames of %dx%d", who, c.n, c.W, c.H);
-    if (c.H > 32767 || c.W > 32767)
+    if (!ev_sensor_ok(c.H, c.W))
         return nsof_set_error(ctx, NSOF_EINVAL, "%s: %dx%d is beyond the int16 coordinates of an event (32767)", who, c.W, c.H);
     if (c.n > (1 << 24)) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "%s: %d frames are beyond one launch (2^24)", who, c.n);
     if (!c.d_frames || !c.times || !c.lut)
@@ -715,22 +635,17 @@ int ef_count_pass(nsof_ctx* ctx, const ef_call& c, size_t sort_count, ef_plan* p
     const int npx = c.H * c.W;   // <= 32767^2 < 2^30
     pl->n_wg = (size_t)(npx + EF_WG - 1) / EF_WG;
     const size_t rows = 2 * (size_t)c.n;
-    const size_t o_meta = align_up(rows * pl->n_wg * sizeof(u64), 256), o_keys = o_meta + align_up((rows + 3) * sizeof(u64), 256);
-    size_t bytes = o_keys;
     pl->sort_bytes = 0;
-    size_t o_keys_out = 0, o_vals = 0, o_vals_out = 0, o_sort = 0;
-    if (sort_count) {
+    if (sort_count)
         NSOF_HIP(ctx, rocprim::radix_sort_pairs(nullptr, pl->sort_bytes, (const u64*)nullptr, (u64*)nullptr, (const unsigned*)nullptr,
                                                 (unsigned*)nullptr, sort_count, 0u, ef_key_bits(c), ctx->stream));
-        o_keys_out = o_keys + align_up(sort_count * sizeof(u64), 256);
-        o_vals = o_keys_out + align_up(sort_count * sizeof(u64), 256);
-        o_vals_out = o_vals + align_up(sort_count * sizeof(unsigned), 256);
-        o_sort = o_vals_out + align_up(sort_count * sizeof(unsigned), 256);
-        bytes = o_sort + pl->sort_bytes;
-    }
-    if (int rc = ctx->tmp.reserve(ctx, bytes)) return rc;
+    ev_carve w;   // (sort_count == 0: the buffers of the reorder are empty and take nothing)
+    const size_t o_table = w.take(rows * pl->n_wg * sizeof(u64)), o_meta = w.take((rows + 3) * sizeof(u64));
+    const size_t o_keys = w.take(sort_count * sizeof(u64)), o_keys_out = w.take(sort_count * sizeof(u64));
+    const size_t o_vals = w.take(sort_count * sizeof(unsigned)), o_vals_out = w.take(sort_count * sizeof(unsigned)), o_sort = w.at;
+    if (int rc = ctx->tmp.reserve(ctx, o_sort + pl->sort_bytes)) return rc;
     char* ws = (char*)ctx->tmp.p;
-    pl->table = (u64*)ws;
+    pl->table = (u64*)(ws + o_table);
     pl->meta = (u64*)(ws + o_meta);
     pl->keys_in = (u64*)(ws + o_keys);
     pl->keys_out = (u64*)(ws + o_keys_out);
@@ -757,9 +672,9 @@ int ef_count_pass(nsof_ctx* ctx, const ef_call& c, size_t sort_count, ef_plan* p
     NSOF_HIP(ctx, hipMemsetAsync(pl->meta + rows + 1, 0, 2 * sizeof(u64), ctx->stream));   // the bad-threshold and long-walk flags
     ef_launch_count(ctx->stream, *pl, c.sensor != nullptr);
     NSOF_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_ef_scan, dim3((unsigned)rows), dim3(EF_WG), 0, ctx->stream, pl->table, pl->n_wg, pl->meta);
+    hipLaunchKernelGGL(k_ev_scan<true>, dim3((unsigned)rows), dim3(EF_WG), 0, ctx->stream, pl->table, pl->n_wg, pl->meta);
     NSOF_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_ef_scan, dim3(1), dim3(EF_WG), 0, ctx->stream, pl->meta, rows, pl->meta + rows);
+    hipLaunchKernelGGL(k_ev_scan<true>, dim3(1), dim3(EF_WG), 0, ctx->stream, pl->meta, rows, pl->meta + rows);
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
@@ -781,7 +696,7 @@ int ef_count_entry(nsof_ctx* ctx, const char* who, const ef_call& c, int64_t* fr
     if (meta[rows + 2])
         return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "%s: a pixel crosses 2^20 thresholds or more in one step, beyond the refractory walk "
                               "of linear time stamps", who);
-    if (meta[rows] >= (1ull << 31))
+    if (meta[rows] >= (u64)EV_MAX_EVENTS)
         return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "%s: %llu%s events, 2^31 or more", who, meta[rows], meta[rows] == ~0ull ? " or more" : "");
     for (int k = 0; k < n; k++) frame_bounds_out[k] = (int64_t)meta[2 * (size_t)k];
     frame_bounds_out[n] = (int64_t)meta[rows];
@@ -798,13 +713,13 @@ int ef_emit_entry(nsof_ctx* ctx, const char* who, const ef_call& c, const int64_
     if (p_on < -128 || p_on > 127 || p_off < -128 || p_off > 127)
         return nsof_set_error(ctx, NSOF_EINVAL, "%s: p_on = %d, p_off = %d do not fit an int8", who, p_on, p_off);
     const int64_t total = frame_bounds[n];
-    if (total < 0 || total >= (1ll << 31))
+    if (total < 0 || total >= EV_MAX_EVENTS)
         return nsof_set_error(ctx, NSOF_EINVAL, "%s: frame_bounds[%d] = %lld is not a total the count entry gives", who, n, (long long)total);
     if (capacity < total)
         return nsof_set_error(ctx, NSOF_EINVAL, "%s: capacity %lld is below the %lld events of the stream", who, (long long)capacity,
                               (long long)total);
-    if (total > 0 && (!d_x || !d_y || !d_p || !d_t))
-        return nsof_set_error(ctx, NSOF_EINVAL, "%s: null pointer (%s)", who, !d_x ? "d_x" : !d_y ? "d_y" : !d_p ? "d_p" : "d_t");
+    if (total > 0)
+        if (int rc = ev_check_stream(ctx, who, d_x, d_y, d_p, d_t)) return rc;
     if (c.sensor && c.sensor->d_t_ok_in && !d_t_ok_out)
         return nsof_set_error(ctx, NSOF_EINVAL, "%s: d_t_ok_in without d_t_ok_out: the run could not be continued", who);
     const bool linear = c.mode == NSOF_EVENTS_T_LINEAR && total > 0;

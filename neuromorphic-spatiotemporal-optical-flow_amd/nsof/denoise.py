@@ -9,11 +9,10 @@ import numpy as np
 
 from . import _lib
 from .errors import NsofValueError
-from .events import _whole
+from .events import _STREAM, _empty_stream, _whole
 
 NEVER = -(1 << 63)             # the state of a pixel no event has been seen at
 DENOISE_KEYS = ("dt_us", "radius", "min_support", "same_polarity", "include_self", "last")
-_STREAM = (("x", "int16"), ("y", "int16"), ("p", "int8"), ("t", "int64"))
 
 
 def _flag(who, name, v):
@@ -93,9 +92,7 @@ def events_denoise_dev(x, y, p, t, sensor_hw, dt_us, *, radius=1, min_support=1,
 
     from .context import default_context, dev_ptr
     who = "events_denoise_dev"
-    ev = dict(x=x, y=y, p=p, t=t)
-    for name, dtype in _STREAM:
-        v = ev[name]
+    for (name, dtype), v in zip(_STREAM, (x, y, p, t)):
         if not isinstance(v, torch.Tensor) or v.dtype != getattr(torch, dtype):
             raise NsofValueError(f"{who}: {name} must be an {dtype} tensor (got {getattr(v, 'dtype', type(v))})", _lib.NSOF_EINVAL)
         if v.dim() != 1 or v.shape != x.shape or not v.is_contiguous():
@@ -124,10 +121,8 @@ def events_denoise_dev(x, y, p, t, sensor_hw, dt_us, *, radius=1, min_support=1,
                                                None if b_in is None else b_in.ctypes.data_as(C.c_void_p), n_b, dev_ptr(keep),
                                                C.byref(n_kept), b_out.ctypes.data_as(C.c_void_p)), who)
     total = int(n_kept.value)
-    xo, yo = (torch.empty(total, dtype=torch.int16, device=dev) for _ in range(2))
-    po = torch.empty(total, dtype=torch.int8, device=dev)
-    to = torch.empty(total, dtype=torch.int64, device=dev)
+    out = _empty_stream(total, dev)
     last_out = torch.empty((c, h, w), dtype=torch.int64, device=dev)
-    ctx.check(lib.nsof_events_denoise_compact_dev(*stream, same_polarity, dev_ptr(last), dev_ptr(keep), total, dev_ptr(xo), dev_ptr(yo),
-                                                  dev_ptr(po), dev_ptr(to), dev_ptr(last_out)), who)
-    return dict(x=xo, y=yo, p=po, t=to, keep=keep, n_kept=total, bounds=None if b_in is None else b_out, last=last_out)
+    ctx.check(lib.nsof_events_denoise_compact_dev(*stream, same_polarity, dev_ptr(last), dev_ptr(keep), total,
+                                                  *(dev_ptr(out[k]) for k, _ in _STREAM), dev_ptr(last_out)), who)
+    return dict(out, keep=keep, n_kept=total, bounds=None if b_in is None else b_out, last=last_out)

@@ -23,6 +23,13 @@ LEVELS_PER_GREY = 256          # the units of the default (linear) response tabl
 LUT_MAX = 1 << 30
 INT64_MAX = (1 << 63) - 1
 _TIMESTAMPS = {"frame": _lib.EVENTS_T_FRAME, "linear": _lib.EVENTS_T_LINEAR}
+_STREAM = (("x", "int16"), ("y", "int16"), ("p", "int8"), ("t", "int64"))   # the arrays of an event stream and their dtypes
+
+
+def _empty_stream(total, dev):
+    """An output stream of ``total`` events on ``dev``, not yet written: ``{"x": ..., "y": ..., "p": ..., "t": ...}``."""
+    import torch
+    return {name: torch.empty(total, dtype=getattr(torch, dtype), device=dev) for name, dtype in _STREAM}
 
 
 def render_box_frames(H=240, W=320, box_h=50, box_w=50, speed_pps=300, duration_s=1.5):  # noqa: N803
@@ -324,16 +331,13 @@ def events_from_frames_dev(frames, times_us=None, *, frame_us=None, threshold=10
     try:
         ctx.check(count(*common, *count_extra, p_bounds), who)
         total = int(bounds[n])
-        x, y = (torch.empty(total, dtype=torch.int16, device=dev) for _ in range(2))
-        p = torch.empty(total, dtype=torch.int8, device=dev)
-        t = torch.empty(total, dtype=torch.int64, device=dev)
         ref_out = torch.empty((h, w), dtype=torch.int32, device=dev)   # fresh allocations: no pending work of torch's to wait for
-        out = dict(x=x, y=y, p=p, t=t, frame_bounds=bounds, ref=ref_out)
+        out = dict(_empty_stream(total, dev), frame_bounds=bounds, ref=ref_out)
         emit_extra = ()
         if st is not None:
             out["t_ok"] = torch.empty((h, w), dtype=torch.int64, device=dev)
             emit_extra = (C.byref(st), dev_ptr(out["t_ok"]))
-        ctx.check(emit(*common, p_bounds, mode, p_on, p_off, total, dev_ptr(x), dev_ptr(y), dev_ptr(p), dev_ptr(t), dev_ptr(ref_out),
+        ctx.check(emit(*common, p_bounds, mode, p_on, p_off, total, *(dev_ptr(out[k]) for k, _ in _STREAM), dev_ptr(ref_out),
                        *emit_extra), who)
     finally:
         if d_plane is not None or d_rates is not None:

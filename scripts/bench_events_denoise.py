@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The background-activity filter (``nsof.events_denoise_dev``); prints one JSON line.
 
-    python scripts/bench_events_denoise.py [--frames 64 --reps 10 --kernel-stats CSV --out profiles/events_denoise.json]
+    python scripts/bench_events_denoise.py [--frames 64 --reps 10 --kernel-stats CSV --parent-lib PATH --out profiles/events_denoise.json]
 
 Input: the stream of scripts/bench_events_sensor.py's "noise" path -- --frames frames of 1080p drifting texture 33333 us
 apart, threshold 10 grey levels, ``ref="first"``, linear stamps, 1 Hz of background activity -- left in HBM by the generator.
@@ -18,6 +18,11 @@ apart, threshold 10 grey levels, ``ref="first"``, linear stamps, 1 Hz of backgro
   shares    two kept shares that need no labels, at dt_us 1000, 5000 and 20000: of the stream of a constant video with noise
             only (every event is noise: the false-positive rate) and of the noiseless stream of the drifting texture (signal
             retention).
+  parent    with --parent-lib (libnsof.so of the parent commit, built beside this one), as in scripts/bench_events_sensor.py:
+            the mark entry and the compact entry of both libraries, each library on a fresh context and outputs of its own,
+            the two alternating within every round and the one that goes first changing from round to round.  The run
+            asserts that both give the same keep, bounds, kept stream and last; ``within_parent_range``: the new median of an
+            entry lies inside the parent's min-max of this session (or below it).
 --trace runs the call --reps times after the warm-up and nothing else.
 Not measured: see "not_measured" in the record."""
 import argparse
@@ -44,12 +49,12 @@ def spread(ms):
 
 
 def kernel_shares(path):
-    """The filter's kernels in a kernel_stats.csv: k_ed_* and the keys-only radix sort (the generator's sort carries values)."""
+    """The filter's kernels in a kernel_stats.csv: k_ed_*, its k_ev_scan and the keys-only radix sort (the generator's sort carries values)."""
     ns = {}
     for r in csv.DictReader(open(path)):
         name = r["Name"]
-        if "k_ed_" in name:
-            key = "k_ed_" + name.split("k_ed_")[1].split("(")[0].split("<")[0]
+        if "k_ed_" in name or "k_ev_scan<false>" in name:   # (k_ev_scan<true> is the generator's)
+            key = "k_e" + name.split("::k_e")[1].split("(")[0].split("<")[0]
         elif "rocprim" in name and "radix_sort" in name and "unsigned int const*" not in name:
             key = "rocprim_radix_sort"
         else:
@@ -66,6 +71,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--ref-frames", type=int, default=8, help="the NumPy restatement runs on the events of this many frames")
     ap.add_argument("--kernel-stats", default=None, help="kernel_stats.csv of a rocprofv3 run of --trace")
+    ap.add_argument("--parent-lib", default=None, help="libnsof.so of the parent commit, for the alternating entry-by-entry check")
     ap.add_argument("--trace", action="store_true", help="the call --reps times and nothing else")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
@@ -74,7 +80,7 @@ def main():
     import torch
 
     import nsof
-    from nsof import synth
+    from nsof import _lib, synth
     from events_denoise_ref import denoise_sorted
     dev = torch.device("cuda", 0)
     ctx = nsof.Context(0)
@@ -112,24 +118,29 @@ def main():
         ctx.close()
         return
 
-    # the two entries alone, on preallocated outputs
-    lib = ctx._lib
-    keep = torch.empty(total, dtype=torch.uint8, device=dev)
-    out = [torch.empty(n_kept, dtype=v.dtype, device=dev) for v in xs]
-    last = torch.empty((1, H, W), dtype=torch.int64, device=dev)
-    b_in, b_out, kept = ev["frame_bounds"], np.zeros(n + 1, np.int64), C.c_int64()
-    head = (ctx.ptr, *(v.data_ptr() for v in xs), total, H, W)
+    b_in = ev["frame_bounds"]
+
+    def entries(lib, ptr):
+        """The two entries of ``lib`` alone on its context ``ptr`` -> (mark, compact, their preallocated outputs: keep, x, y, p, t,
+        last, and the host bounds)."""
+        keep = torch.empty(total, dtype=torch.uint8, device=dev)
+        out = [torch.empty(n_kept, dtype=v.dtype, device=dev) for v in xs]
+        last = torch.empty((1, H, W), dtype=torch.int64, device=dev)
+        b_out, kept = np.zeros(n + 1, np.int64), C.c_int64()
+        head = (ptr, *(v.data_ptr() for v in xs), total, H, W)
+
+        def mark():
+            rc = lib.nsof_events_denoise_mark_dev(*head, FILTER["dt_us"], FILTER["radius"], FILTER["min_support"], 0, 0, None,
+                                                  b_in.ctypes.data, n + 1, keep.data_ptr(), C.byref(kept), b_out.ctypes.data)
+            assert rc == 0 and kept.value == n_kept, (rc, kept.value)
+
+        def compact():
+            rc = lib.nsof_events_denoise_compact_dev(*head, 0, None, keep.data_ptr(), n_kept, *(v.data_ptr() for v in out), last.data_ptr())
+            assert rc == 0, rc
+        return mark, compact, (keep, *out, last), b_out
+
+    mark, compact, (keep, *out, last), b_out = entries(ctx._lib, ctx.ptr)
     torch.cuda.synchronize(dev)
-
-    def mark():
-        rc = lib.nsof_events_denoise_mark_dev(*head, FILTER["dt_us"], FILTER["radius"], FILTER["min_support"], 0, 0, None, b_in.ctypes.data,
-                                              n + 1, keep.data_ptr(), C.byref(kept), b_out.ctypes.data)
-        assert rc == 0 and kept.value == n_kept, (rc, kept.value)
-
-    def compact():
-        rc = lib.nsof_events_denoise_compact_dev(*head, 0, None, keep.data_ptr(), n_kept, *(v.data_ptr() for v in out), last.data_ptr())
-        assert rc == 0, rc
-
     ms = {"call": [], "mark_entry": [], "compact_entry": []}
     for _ in range(a.reps):
         t_ms, r = timed(call)
@@ -147,6 +158,36 @@ def main():
     line["events_per_s"] = round(total / (line["call"]["median_ms"] * 1e-3))
     if a.kernel_stats:
         line.update(kernel_shares(a.kernel_stats))
+    if a.parent_lib:
+        libs = {"new": ctx._lib, "parent": C.CDLL(os.path.abspath(a.parent_lib))}
+        for name in ("nsof_create", "nsof_destroy", "nsof_set_stream", "nsof_events_denoise_mark_dev", "nsof_events_denoise_compact_dev"):
+            fn = getattr(libs["parent"], name)
+            fn.restype, fn.argtypes = _lib.SIGNATURES[name]
+        ptrs, calls, results = {}, {}, {}
+        for which in ("parent", "new"):   # a fresh context of each library: the one above has the workspace of the calls it ran
+            ptrs[which] = C.c_void_p()
+            assert libs[which].nsof_create(0, C.byref(ptrs[which])) == 0
+            assert libs[which].nsof_set_stream(ptrs[which], C.c_void_p(stream.cuda_stream)) == 0
+            calls[which, "mark_entry"], calls[which, "compact_entry"], *results[which] = entries(libs[which], ptrs[which])
+            for v in results[which][0]:
+                v.zero_()
+            torch.cuda.synchronize(dev)
+            calls[which, "mark_entry"]()   # warm-up; what the two libraries wrote is compared below
+            calls[which, "compact_entry"]()
+            torch.cuda.synchronize(dev)
+        assert all(torch.equal(v, w) for v, w in zip(results["new"][0], results["parent"][0])), "keep, the kept stream or last differ"
+        assert np.array_equal(results["new"][1], results["parent"][1]), "the bounds differ"
+        pm = {key: [] for key in calls}
+        for r in range(a.reps):
+            for what in ("mark_entry", "compact_entry"):
+                for which in (("parent", "new"), ("new", "parent"))[r % 2]:   # who goes first changes every round
+                    pm[which, what].append(timed(calls[which, what])[0])
+        line["vs_parent"] = {"same_keep_bounds_stream_and_last": True}
+        for what in ("mark_entry", "compact_entry"):
+            new, par = spread(pm["new", what]), spread(pm["parent", what])
+            line["vs_parent"][what] = {"new": new, "parent": par, "within_parent_range": new["median_ms"] <= par["max_ms"]}
+        for which in ptrs:
+            libs[which].nsof_destroy(ptrs[which])
 
     # the NumPy restatement on a prefix of the same stream
     m = int(ev["frame_bounds"][min(a.ref_frames, n)])

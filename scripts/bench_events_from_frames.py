@@ -25,7 +25,7 @@ that has settled on the first frame: with ``ref=None`` the first frame alone giv
            same input, host clock, once per mode; the device result is compared with it (x, y, p, t, frame_bounds, ref equal)
            and the device call on those frames is timed again (median of 5).
 --trace runs the three library calls (count, emit frame, emit linear) --reps times after the warm-up and nothing else, for a
-separate ``rocprofv3 --kernel-trace --stats`` run: every round then launches k_ef_count three times, k_ef_scan six times,
+separate ``rocprofv3 --kernel-trace --stats`` run: every round then launches k_ef_count three times, k_ev_scan six times,
 each k_ef_emit form, the sort's kernels and k_ef_unpack once.
 Not measured: other frame sizes, the threshold plane, response tables other than the linear one, chunked runs."""
 import argparse

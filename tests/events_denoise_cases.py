@@ -53,7 +53,24 @@ _random("9x4-dt0", 9, 4, 2000, 100, 4, dt_us=0, same_polarity=True, include_self
 # of 33 x 65 are 4290 keys, 13 bits of the sort; more than 16 key bits come from 300 x 301 -- with as many workgroups in
 # "300x301-many" -- and from the two 32767-long sensors.)
 _random("33x65", 33, 65, 70001, 60000, 5, dt_us=40, same_polarity=True)
-_random("5x5-r2-m9", 5, 5, 4000, 300, 6, dt_us=3, radius=2, min_support=9, include_self=True)   # a corner's whole window, self included
+# The exact chunk boundaries: one full chunk of 256 events and a second chunk of one event; a table of exactly 256 chunk counts
+# (one step of the scan, no carry) and a 257th count, the carry into a step of one entry -- which must not be zero.
+_random("5x7-256", 5, 7, 256, 213, 21, dt_us=3)
+_random("5x7-257", 5, 7, 257, 214, 22, dt_us=3)
+_random("33x65-65536", 33, 65, 65536, 56000, 23, dt_us=150, same_polarity=True)
+_random("33x65-65537", 33, 65, 65537, 56000, 24, dt_us=150, same_polarity=True)
+
+
+def _last_is_kept(name):
+    """The case's last event has an earlier event of its polarity within dt_us in its window of radius 1 (min_support is 1)."""
+    c = CASES[name]
+    x, y, p, t = (c[k].astype(np.int64) for k in "xypt")
+    near = (np.abs(x[:-1] - x[-1]) <= 1) & (np.abs(y[:-1] - y[-1]) <= 1) & ((x[:-1] != x[-1]) | (y[:-1] != y[-1]))
+    return bool((near & ((p[:-1] > 0) == (p[-1] > 0)) & (t[:-1] >= t[-1] - c["kw"]["dt_us"])).any())
+
+
+assert _last_is_kept("33x65-65537")
+_random("5x5-r2-m9",5, 5, 4000, 300, 6, dt_us=3, radius=2, min_support=9, include_self=True)   # a corner's whole window, self included
 
 
 def _hot_pixel():

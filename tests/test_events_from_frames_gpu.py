@@ -67,6 +67,17 @@ def test_random_frames(nsof_lib, ctx, torch_dev, random_frames, timestamps, thr,
     _assert_equal(got, want)
 
 
+@pytest.mark.parametrize("shape", [(3, 256, 256), (3, 257, 256), (128, 13, 17), (129, 13, 17)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("timestamps", ["frame", "linear"])
+def test_scan_chunk_boundaries(nsof_lib, ctx, torch_dev, timestamps, shape):
+    """The table scan at its chunk boundaries of 256 entries: 256 workgroups (a row of the table is exactly one chunk) and 257
+    (a second chunk of one entry); 128 and 129 frames (256 row sums: one chunk; 258: a second chunk of two)."""
+    frames = np.random.default_rng(31).integers(0, 256, shape, dtype=np.uint8)
+    got, want = _run(nsof_lib, ctx, torch_dev, frames, np.arange(shape[0], dtype=np.int64) * 1000, 40, timestamps=timestamps)
+    assert 10_000 < len(want["x"]) < 2_000_000
+    _assert_equal(got, want)
+
+
 @pytest.mark.parametrize("timestamps", ["frame", "linear"])
 def test_full_swing_at_the_finest_threshold(nsof_lib, ctx, torch_dev, timestamps):
     """0 -> 255 -> 0 at 1/256 grey level: 65280 events per pixel and step -- the per-pixel emit loop, offsets far beyond
