@@ -1,6 +1,10 @@
-// Farneback dense optical flow, pyramid stage: the pyramid-level kernels (k_prep_*) and the coarse-to-fine flow resample
-// (k_flow_upsample*) for gfx950 (CDNA4, wave64).  The expansion is in farneback_polyexp.hip, the unfused box-window solve
-// in farneback_blur.hip, the iterations in farneback_iterate*.hip.
+// Farneback dense optical flow, pyramid stage: the pyramid-level kernels (k_prep_*) for gfx950 (CDNA4, wave64).  The
+// coarse-to-fine flow resample is in farneback_resample.hip, the expansion in farneback_polyexp.hip, the unfused
+// box-window solve in farneback_blur.hip, the iterations in farneback_iterate*.hip.
+//
+// Layout of this file: pixel access and the two filters; the shared pieces of the resampling kernels (window loads,
+// the resample tail); the kernels, one per route; the launchers -- prep_route()
+// names the route of a uniform level, prep_impl() launches it.
 //
 // Replaces the arithmetic the reference obtains from cv2.calcOpticalFlowFarneback
 // (call sites: /root/reference/optical_flow_seg.py:158,203,494 and the ob/prediction/yolo
@@ -13,15 +17,15 @@
 // Every kernel and the helpers between them take the arithmetic variant as their last template argument FMA: each tap
 // and blend is nsof_madd<FMA> (nsof_internal.h), the plain multiply-then-add or one fused multiply-add.  The launchers at
 // the end of the file read the variant from ctx->opt_pyr_fma (NSOF_OPT_PYR_FMA).
+#include <algorithm>
 #include <cstdlib>
-
 #include <type_traits>
 
 #include "nsof_internal.h"
 
 namespace {
 
-// (resize(INTER_LINEAR) coordinates: lin_coord_x / lin_coord_y, nsof_internal.h)
+// (resize(INTER_LINEAR) taps and blends: lin_tap_x / lin_tap_y, lin_mix, lin_blend, nsof_internal.h)
 
 // ---------------------------------------------------------------------------------------
 // Pyramid level preparation: u8 / f32 -> f32, separable Gaussian (sepFilter2D order), bilinear
@@ -55,13 +59,14 @@ __device__ __forceinline__ float px_el(unsigned v, int e)
     else if constexpr (std::is_signed<T>::value) return (float)(int)(short)(v >> (16 * e));
     else return (float)((v >> (16 * e)) & 0xffffu);
 }
-// Four adjacent pixels of a 16-bit or float row as one aligned vector (8 / 16 bytes), and pixel e of it.
+// Four adjacent pixels of a row as one aligned vector (8-bit: a dword, 16-bit: 8 bytes, float: 16), and pixel e of it.
 template <typename T>
-using PxQuad = std::conditional_t<sizeof(T) == 2, uint2, float4>;
+using PxQuad = std::conditional_t<sizeof(T) == 1, unsigned, std::conditional_t<sizeof(T) == 2, uint2, float4>>;
 template <typename T>
 __device__ __forceinline__ float quad_el(const PxQuad<T>& v, int e)
 {
-    if constexpr (sizeof(T) == 2) return px_el<T>(e < 2 ? v.x : v.y, e & 1);
+    if constexpr (sizeof(T) == 1) return px_el<T>(v, e);
+    else if constexpr (sizeof(T) == 2) return px_el<T>(e < 2 ? v.x : v.y, e & 1);
     else return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w));
 }
 
@@ -90,6 +95,74 @@ __device__ __forceinline__ float col_filter(TapF tk, int ksize, int rr, LoadF hv
 #pragma unroll
     for (int j = 1; j <= r; j++) s = nsof_madd<FMA>(tk(r + j), hv(rr + j) + hv(rr - j), s);
     return s;
+}
+// The run-time taps of a block in LDS (see row_filter): threads first .. first + NSOF_MAX_BLUR_TAPS - 1 copy one each;
+// the caller's barrier publishes them.
+__device__ __forceinline__ void stage_taps(float (&s_tk)[NSOF_MAX_BLUR_TAPS], const nsof_blur_taps& t, int first = 0)
+{
+    const int j = (int)threadIdx.x - first;
+    if ((unsigned)j < (unsigned)NSOF_MAX_BLUR_TAPS) s_tk[j] = t.k[j];
+}
+
+// ---- the N pixels of a row from column c on, as floats ----------------------------------------------------------------
+// Fast form, for a window that lies inside the row: integer frames as unaligned dword loads of kPPD<T> pixels each
+// (the last one may reach up to kPPD<T> - 1 pixels past the window: window_fast() keeps that inside the row as well),
+// float frames pixel by pixel.
+template <typename T>
+using WinWord = std::conditional_t<kInt<T>, unsigned, float>;
+template <typename T, int N>
+constexpr int kWinWords = (N + kPPD<T> - 1) / kPPD<T>;
+template <typename T, int N, typename C>
+__device__ __forceinline__ void load_window(const T* rowp, C c, float (&b)[N])
+{
+    WinWord<T> raw[kWinWords<T, N>];
+#pragma unroll
+    for (int d = 0; d < kWinWords<T, N>; d++) __builtin_memcpy(&raw[d], rowp + c + kPPD<T> * d, 4);
+#pragma unroll
+    for (int d = 0; d < kWinWords<T, N>; d++)
+#pragma unroll
+        for (int e = 0; e < kPPD<T>; e++)
+            if (kPPD<T> * d + e < N) {
+                if constexpr (kInt<T>) b[kPPD<T> * d + e] = px_el<T>(raw[d], e);
+                else b[d] = raw[d];
+            }
+}
+// Border form: pixel by pixel with BORDER_REFLECT_101 columns.
+template <typename T, int N>
+__device__ __forceinline__ void load_window_reflect(const T* rowp, int c, int W, float (&b)[N])
+{
+#pragma unroll
+    for (int j = 0; j < N; j++) b[j] = px(rowp + reflect101(c + j, W));
+}
+// May the N-pixel window that starts R columns left of column c take the fast form?  With two columns: and is c1 the
+// column after c0, so that one window of KS + 1 pixels serves the row filter at both?
+template <typename T, int N>
+__device__ __forceinline__ bool window_fast(int c, int R, int W)
+{
+    return c - R >= 0 && c - R + kPPD<T> * kWinWords<T, N> <= W;
+}
+template <typename T, int N>
+__device__ __forceinline__ bool window_fast(int c0, int c1, int R, int W)
+{
+    return window_fast<T, N>(c0, R, W) && c1 == c0 + 1;
+}
+
+// ---- shared by the kernels that resample in registers (direct, cols) ---------------------------------------------------
+// The resample tail.  hv0(q) / hv1(q): the row-filtered values at a destination pixel's two columns of source row
+// r0 - R + q, q = 0 .. KS.  Column filter at r0 (window entry R), at r1 = r0 + 1 (entry R + 1) unless the two rows are
+// one (`two_rows`: r1 != r0), then resize's 2x2 blend with the column weight a1 and the row weight b1.
+template <int KS, bool FMA, typename TapF, typename H0F, typename H1F>
+__device__ __forceinline__ float resample_tail(TapF tk, H0F hv0, H1F hv1, bool two_rows, float a1, float b1)
+{
+    constexpr int R = KS / 2;
+    const float B00 = col_filter<KS, FMA>(tk, KS, R, hv0);
+    const float B01 = col_filter<KS, FMA>(tk, KS, R, hv1);
+    float B10 = B00, B11 = B01;
+    if (two_rows) {
+        B10 = col_filter<KS, FMA>(tk, KS, R + 1, hv0);
+        B11 = col_filter<KS, FMA>(tk, KS, R + 1, hv1);
+    }
+    return lin_blend<FMA>(B00, B01, B10, B11, a1, b1);
 }
 
 // Geometry of one image of a pyramid-level launch.  HET == false: the uniform batch (every image has the kernel
@@ -128,7 +201,7 @@ __global__ __launch_bounds__(256) void k_prep_same(const T* __restrict__ src, pt
                                                     int want_flag)
 {
     __shared__ float s_tk[NSOF_MAX_BLUR_TAPS];
-    if (threadIdx.x < NSOF_MAX_BLUR_TAPS) s_tk[threadIdx.x] = t.k[threadIdx.x];
+    stage_taps(s_tk, t);
     __syncthreads();
     auto tk = [&](int j) { return s_tk[j]; };
     PrepImg<T> g;
@@ -173,6 +246,8 @@ __global__ __launch_bounds__(256) void k_prep_same3_vec(const T* __restrict__ sr
     auto hrow = [&](int rr, float (&h)[4]) {                      // row filter of source row rr (reflected)
         const T* rowp = srow(img, reflect101(rr, H), row_stride);
         float s0, s1, s2, s3, sl, sr;
+        // (8-bit: the neighbours' raw dwords are exchanged and converted after; in the quad form below, which exchanges
+        // converted pixels, the level-0 launch of 64 1080p frames measured 133.5 us against 130.2 .. 131.7)
         if constexpr (kU8<T>) {
             const unsigned v = *reinterpret_cast<const unsigned*>(rowp + xl);
             unsigned lft = __shfl_up(v, 1) >> 24, rgt = __shfl_down(v, 1) & 0xffu;
@@ -260,13 +335,10 @@ __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdi
     // evaluates the row filter at this lane's sampled columns -> ring[slot]; between the two a row can stay in flight
     // while the rows before it are filtered (S <= 4: the rows of the NEXT output row are fetched before this one's are
     // used -- with one output row's 2 or 4 source rows in flight per wave the kernel waited for memory half the time).
-    struct RawU8 {
-        unsigned cw[CW / 4], hl[HD], hr[HD];
+    using Q = PxQuad<T>;   // 4 pixels: a dword / an 8-B / a 16-B vector
+    struct Raw {
+        Q cw[CW / 4], hl[HD], hr[HD];
     };
-    struct RawQ {   // 16-bit / f32: 4 pixels per 8-B / 16-B vector
-        PxQuad<T> cw[CW / 4], hl[HD], hr[HD];
-    };
-    using Raw = std::conditional_t<kU8<T>, RawU8, RawQ>;
     // Halo quad d of a side covers columns [xc0 - HB + 4d, +4) (left) / [xc0 + CW + 4d, +4) (right): whole quads, as
     // W % CW == 0.  A lane reads at most R + 1 - S/2 (<= 6) columns beyond its segment, and the edge lanes reflect into
     // their own pixels and their inner halo.  With HB <= CW the halos of every lane that is not at the image edge lie
@@ -283,49 +355,31 @@ __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdi
     };
     auto fetch = [&](int r, Raw& q) {
         const T* rowp = srow(img, reflect101(r, H), row_stride) + xc0;
-        if constexpr (!kU8<T>) {
-            using Q = PxQuad<T>;
+        if constexpr (kU8<T> && CW == 16) {   // 8-bit: the lane's CW bytes are one 16-B / 8-B load
+            const uint4 c = *reinterpret_cast<const uint4*>(rowp);
+            q.cw[0] = c.x; q.cw[1] = c.y; q.cw[2] = c.z; q.cw[3] = c.w;
+        } else if constexpr (kU8<T>) {
+            const uint2 c = *reinterpret_cast<const uint2*>(rowp);
+            q.cw[0] = c.x; q.cw[1] = c.y;
+        } else {
 #pragma unroll
             for (int d = 0; d < CW / 4; d++) q.cw[d] = reinterpret_cast<const Q*>(rowp)[d];
+        }
 #pragma unroll
-            for (int d = 0; d < HD; d++) {
-                q.hl[d] = *reinterpret_cast<const Q*>(halo_l(rowp, d));
-                q.hr[d] = *reinterpret_cast<const Q*>(halo_r(rowp, d));
-            }
-        } else {
-            if (CW == 16) {
-                const uint4 c = *reinterpret_cast<const uint4*>(rowp);
-                q.cw[0] = c.x; q.cw[1] = c.y; q.cw[(CW / 4 > 2) ? 2 : 0] = c.z; q.cw[(CW / 4 > 3) ? 3 : 0] = c.w;
-            } else {
-                const uint2 c = *reinterpret_cast<const uint2*>(rowp);
-                q.cw[0] = c.x; q.cw[1] = c.y;
-            }
-#pragma unroll
-            for (int d = 0; d < HD; d++) {
-                q.hl[d] = *reinterpret_cast<const unsigned*>(halo_l(rowp, d));
-                q.hr[d] = *reinterpret_cast<const unsigned*>(halo_r(rowp, d));
-            }
+        for (int d = 0; d < HD; d++) {
+            q.hl[d] = *reinterpret_cast<const Q*>(halo_l(rowp, d));
+            q.hr[d] = *reinterpret_cast<const Q*>(halo_r(rowp, d));
         }
     };
     auto filt = [&](const Raw& q, float (&dstrow)[NC]) {
         float raw[WIN];   // window [xc0 - HB, xc0 + CW + HB) as loaded
-        if constexpr (kU8<T>) {
 #pragma unroll
-            for (int b = 0; b < HB; b++) {
-                raw[b] = (float)((q.hl[b >> 2] >> (8 * (b & 3))) & 0xffu);
-                raw[HB + CW + b] = (float)((q.hr[b >> 2] >> (8 * (b & 3))) & 0xffu);
-            }
-#pragma unroll
-            for (int b = 0; b < CW; b++) raw[HB + b] = (float)((q.cw[b >> 2] >> (8 * (b & 3))) & 0xffu);
-        } else {
-#pragma unroll
-            for (int b = 0; b < HB; b++) {
-                raw[b] = quad_el<T>(q.hl[b >> 2], b & 3);
-                raw[HB + CW + b] = quad_el<T>(q.hr[b >> 2], b & 3);
-            }
-#pragma unroll
-            for (int b = 0; b < CW; b++) raw[HB + b] = quad_el<T>(q.cw[b >> 2], b & 3);
+        for (int b = 0; b < HB; b++) {
+            raw[b] = quad_el<T>(q.hl[b >> 2], b & 3);
+            raw[HB + CW + b] = quad_el<T>(q.hr[b >> 2], b & 3);
         }
+#pragma unroll
+        for (int b = 0; b < CW; b++) raw[HB + b] = quad_el<T>(q.cw[b >> 2], b & 3);
         float fb[WIN];
 #pragma unroll
         for (int b = 0; b < CW; b++) fb[HB + b] = raw[HB + b];
@@ -392,17 +446,7 @@ __device__ __forceinline__ void prep_decim_body(const T* __restrict__ src, ptrdi
                     const float t1 = B10 * 0.5f + B11 * 0.5f;
                     o[j] = t0 * 0.5f + t1 * 0.5f;
                 }
-                float* op = dst + (size_t)dy * wk + NPX * TG;
-                if (NPX == 8) {
-                    nsof_store_stream4(op, o[0], o[1 % NPX], o[2 % NPX], o[3 % NPX]);
-                    nsof_store_stream4(op + 4, o[4 % NPX], o[5 % NPX], o[6 % NPX], o[7 % NPX]);
-                } else if (NPX == 4) {
-                    nsof_store_stream4(op, o[0], o[1 % NPX], o[2 % NPX], o[3 % NPX]);
-                } else if (NPX == 2) {
-                    nsof_store_stream2(op, o[0], o[1 % NPX]);
-                } else {
-                    __builtin_nontemporal_store(o[0], op);
-                }
+                nsof_store_stream_n(dst + (size_t)dy * wk + NPX * TG, o);
             }
         }
     }
@@ -448,23 +492,17 @@ __global__ __launch_bounds__(256) void k_prep_naive(const T* __restrict__ src, p
                                                      float* __restrict__ out, const nsof_het_item* __restrict__ items)
 {
     __shared__ float s_tk[NSOF_MAX_BLUR_TAPS];
-    if (threadIdx.x < NSOF_MAX_BLUR_TAPS) s_tk[threadIdx.x] = t.k[threadIdx.x];
+    stage_taps(s_tk, t);
     __syncthreads();
     auto tk = [&](int j) { return s_tk[j]; };
     PrepImg<T> g;
     prep_geom<HET>(g, src, row_stride, img_stride, W, H, wk, hk, out, items, -1);
-    if constexpr (HET) { scale_x = 1. / ((double)wk / W); scale_y = 1. / ((double)hk / H); }
+    if constexpr (HET) { scale_x = inv_scale(wk, W); scale_y = inv_scale(hk, H); }
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (dx >= wk || dy >= hk) return;
     const T* img = g.img;
-    int sx, sy;
-    float a1, b1;
-    lin_coord_x(dx, scale_x, W, sx, a1);
-    lin_coord_y(dy, scale_y, sy, b1);
-    const float a0 = 1.f - a1, b0 = 1.f - b1;
-    const int c0 = sx, c1 = min(sx + 1, W - 1);
-    const int r0 = clampi(sy, 0, H - 1), r1 = clampi(sy + 1, 0, H - 1);
+    const LinTap tx = lin_tap_x(dx, scale_x, W), ty = lin_tap_y(dy, scale_y, H);
     auto blur = [&](int rr, int cc) {
         auto hv = [&](int q) {
             const T* rowp = srow(img, reflect101(q, H), row_stride);
@@ -472,9 +510,8 @@ __global__ __launch_bounds__(256) void k_prep_naive(const T* __restrict__ src, p
         };
         return col_filter<0, FMA>(tk, t.ksize, rr, hv);
     };
-    const float t0 = nsof_madd<FMA>(blur(r0, c0), a0, blur(r0, c1) * a1);
-    const float t1 = nsof_madd<FMA>(blur(r1, c0), a0, blur(r1, c1) * a1);
-    g.dst[(size_t)dy * wk + dx] = nsof_madd<FMA>(t0, b0, t1 * b1);
+    g.dst[(size_t)dy * wk + dx] = lin_blend<FMA>(blur(ty.i0, tx.i0), blur(ty.i0, tx.i1), blur(ty.i1, tx.i0),
+                                               blur(ty.i1, tx.i1), tx.w1, ty.w1);
 }
 
 // Resampled level, LDS-tiled: a 32x8 destination tile per 256-thread block.
@@ -495,8 +532,8 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const T* __restrict__ src, p
     PrepImg<T> g;
     prep_geom<HET>(g, src, row_stride, img_stride, W, H, wk, hk, out, items, -1);
     if constexpr (HET) {
-        scale_x = 1. / ((double)wk / W);
-        scale_y = 1. / ((double)hk / H);
+        scale_x = inv_scale(wk, W);
+        scale_y = inv_scale(hk, H);
         if (blockIdx.x * PREP_TW >= wk || blockIdx.y * PREP_TH >= hk) return;   // block-uniform
     }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -515,22 +552,18 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const T* __restrict__ src, p
     auto tk = [&](int j) { return KS ? t.k[j] : s_tk[j]; };   // KS > 0: j is a constant after unrolling
 
     if (tid < PREP_TW) {
-        int dx = min(dx0 + tid, wk - 1), sx;
-        float a;
-        lin_coord_x(dx, scale_x, W, sx, a);
-        s_c[2 * tid] = sx;
-        s_c[2 * tid + 1] = min(sx + 1, W - 1);
-        s_a[tid] = a;
+        const LinTap tx = lin_tap_x(min(dx0 + tid, wk - 1), scale_x, W);
+        s_c[2 * tid] = tx.i0;
+        s_c[2 * tid + 1] = tx.i1;
+        s_a[tid] = tx.w1;
     } else if (tid >= 64 && tid < 64 + PREP_TH) {
-        int i = tid - 64, dy = min(dy0 + i, hk - 1), sy;
-        float b;
-        lin_coord_y(dy, scale_y, sy, b);
-        s_r[2 * i] = clampi(sy, 0, H - 1);
-        s_r[2 * i + 1] = clampi(sy + 1, 0, H - 1);
-        s_b[i] = b;
-    } else if (!KS && tid >= 128 && tid < 128 + NSOF_MAX_BLUR_TAPS) {
-        s_tk[tid - 128] = t.k[tid - 128];
+        const int i = tid - 64;
+        const LinTap ty = lin_tap_y(min(dy0 + i, hk - 1), scale_y, H);
+        s_r[2 * i] = ty.i0;
+        s_r[2 * i + 1] = ty.i1;
+        s_b[i] = ty.w1;
     }
+    if constexpr (!KS) stage_taps(s_tk, t, 128);   // (threads of the third wave)
     __syncthreads();
     // coordinates are monotone in dx/dy, so the footprint is [first .. last]
     int C0 = s_c[0] - r;
@@ -574,12 +607,9 @@ __global__ __launch_bounds__(256) void k_prep_tiled(const T* __restrict__ src, p
     const int tx = tid & 31, ty = tid >> 5;
     const int dx = dx0 + tx, dy = dy0 + ty;
     if (dx < wk && dy < hk) {
-        const float a1 = s_a[tx], a0 = 1.f - a1, b1 = s_b[ty], b0 = 1.f - b1;
         const float* B0 = sB + (2 * ty) * (2 * PREP_TW) + 2 * tx;
         const float* B1 = B0 + 2 * PREP_TW;
-        const float t0 = nsof_madd<FMA>(B0[0], a0, B0[1] * a1);
-        const float t1 = nsof_madd<FMA>(B1[0], a0, B1[1] * a1);
-        g.dst[(size_t)dy * wk + dx] = nsof_madd<FMA>(t0, b0, t1 * b1);
+        g.dst[(size_t)dy * wk + dx] = lin_blend<FMA>(B0[0], B0[1], B1[0], B1[1], s_a[tx], s_b[ty]);
     }
 }
 
@@ -595,66 +625,37 @@ __global__ __launch_bounds__(256) void k_prep_direct(const T* __restrict__ src, 
                                                       double scale_x, double scale_y, nsof_blur_taps t,
                                                       float* __restrict__ out, const nsof_het_item* __restrict__ items)
 {
-    constexpr int R = KS / 2, NB = KS + 1, PPD = kPPD<T>, ND = (NB + PPD - 1) / PPD;
+    constexpr int R = KS / 2;
     PrepImg<T> g;
     prep_geom<HET>(g, src, row_stride, img_stride, W, H, wk, hk, out, items, -1);
-    if constexpr (HET) { scale_x = 1. / ((double)wk / W); scale_y = 1. / ((double)hk / H); }
+    if constexpr (HET) { scale_x = inv_scale(wk, W); scale_y = inv_scale(hk, H); }
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (dx >= wk || dy >= hk) return;
     const T* img = g.img;
-    int sx, sy;
-    float a1, b1;
-    lin_coord_x(dx, scale_x, W, sx, a1);
-    lin_coord_y(dy, scale_y, sy, b1);
-    const float a0 = 1.f - a1, b0 = 1.f - b1;
-    const int c0 = sx, c1 = min(sx + 1, W - 1);
-    const int r0 = clampi(sy, 0, H - 1), r1 = clampi(sy + 1, 0, H - 1);
-    const bool fast = c0 - R >= 0 && c0 - R + PPD * ND <= W && c1 == c0 + 1;
+    const LinTap tx = lin_tap_x(dx, scale_x, W), ty = lin_tap_y(dy, scale_y, H);
+    const bool fast = window_fast<T, KS + 1>(tx.i0, tx.i1, R, W);
     auto tk = [&](int j) { return t.k[j]; };   // j is a compile-time constant after unrolling
 
-    float H0[KS + 1], H1[KS + 1];
+    float H0[KS + 1], H1[KS + 1];   // row filter at columns c0 and c1 of source rows r0 - R .. r0 - R + KS
 #pragma unroll
     for (int i = 0; i <= KS; i++) {
-        const T* rowp = srow(img, reflect101(r0 - R + i, H), row_stride);
-        float b[NB], bb[NB];   // pixels around c0 and around c1
-        if (fast) {
-            if constexpr (kInt<T>) {
-#pragma unroll
-                for (int d = 0; d < ND; d++) {
-                    unsigned v;
-                    __builtin_memcpy(&v, rowp + (c0 - R) + PPD * d, 4);   // unaligned dword load
-#pragma unroll
-                    for (int e = 0; e < PPD; e++)
-                        if (PPD * d + e < NB) b[PPD * d + e] = px_el<T>(v, e);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < NB; j++) b[j] = rowp[c0 - R + j];
-            }
+        const T* rowp = srow(img, reflect101(ty.i0 - R + i, H), row_stride);
+        if (fast) {   // one window of KS + 1 pixels serves both columns
+            float b[KS + 1];
+            load_window<T, KS + 1>(rowp, tx.i0 - R, b);
             H0[i] = row_filter<KS, FMA>(tk, KS, R, [&](int c) { return b[c]; });
             H1[i] = row_filter<KS, FMA>(tk, KS, R + 1, [&](int c) { return b[c]; });
         } else {
-#pragma unroll
-            for (int j = 0; j < KS; j++) {
-                b[j] = px(rowp + reflect101(c0 - R + j, W));
-                bb[j] = px(rowp + reflect101(c1 - R + j, W));
-            }
+            float b[KS], bb[KS];
+            load_window_reflect<T, KS>(rowp, tx.i0 - R, W, b);
+            load_window_reflect<T, KS>(rowp, tx.i1 - R, W, bb);
             H0[i] = row_filter<KS, FMA>(tk, KS, R, [&](int c) { return b[c]; });
             H1[i] = row_filter<KS, FMA>(tk, KS, R, [&](int c) { return bb[c]; });
         }
     }
-    // rows of H0/H1 are r0-R .. r0-R+KS; the window of r1 = r0+1 starts one entry later
-    const float B00 = col_filter<KS, FMA>(tk, KS, R, [&](int q) { return H0[q]; });
-    const float B01 = col_filter<KS, FMA>(tk, KS, R, [&](int q) { return H1[q]; });
-    float B10 = B00, B11 = B01;
-    if (r1 != r0) {
-        B10 = col_filter<KS, FMA>(tk, KS, R + 1, [&](int q) { return H0[q]; });
-        B11 = col_filter<KS, FMA>(tk, KS, R + 1, [&](int q) { return H1[q]; });
-    }
-    const float t0 = nsof_madd<FMA>(B00, a0, B01 * a1);
-    const float t1 = nsof_madd<FMA>(B10, a0, B11 * a1);
-    g.dst[(size_t)dy * wk + dx] = nsof_madd<FMA>(t0, b0, t1 * b1);
+    g.dst[(size_t)dy * wk + dx] = resample_tail<KS, FMA>(
+        tk, [&](int q) { return H0[q]; }, [&](int q) { return H1[q]; }, ty.i1 != ty.i0, tx.w1, ty.w1);
 }
 
 // Resampled level, walking: thread <-> destination column, a wave walks a segment of destination rows top to bottom.
@@ -664,14 +665,16 @@ __global__ __launch_bounds__(256) void k_prep_direct(const T* __restrict__ src, 
 // window advances -- by 1 or 2 rows per destination row at pyr_scale 0.6, 4-5 at level 3) and loads / row-filters every
 // source row ONCE: 1.7 instead of 4 row evaluations per destination pixel at level 1, 4.6 instead of 10 at level 3.  The
 // advance loop is wave-uniform (source rows depend on the destination row only).  Same helper functions and operation
-// order as the direct kernel -> bit-identical output.  Parameter sets B / C (pyr_scale 0.6): levels 1 and 2 (3 / 5 taps).
-// Round 4: the walk is written for the scalar unit.  Everything that depends on the destination ROW only -- the source
-// rows of its window, "has the window's last row entered", the vertical blend weight -- is wave-uniform and now lives in
-// SGPRs (readfirstlane), so the loop's control flow is scalar branches instead of exec-mask bookkeeping; and whether a
-// lane may take the unaligned-dword fast path (its KS + 1 bytes lie inside the image) is decided once per WAVE: only the
-// waves that touch the left / right image border run the per-byte reflecting loads.  The first version spent ~240
-// instructions per source row, most of them mask handling around the per-lane fast / slow choice (ISA: 54 s_cbranch_execz,
-// 53 s_and_saveexec, 47 v_cndmask, 24 global_load_ubyte per 4 source rows), where the arithmetic needs ~20.
+// order as the direct kernel -> bit-identical output.  (This kernel spells its window loads, its tap set-up and its
+// resample tail out instead of taking load_window / lin_tap_x / resample_tail: written with them the integer walks
+// measured 0.1-0.9 % slower, the 1080p level-3 launch of 64 frames 236.6 us against 234.3 .. 234.6.)  Parameter sets B / C (pyr_scale 0.6):
+// levels 1, 2 and 3 (3 / 5 / 9 taps).
+// The walk is written for the scalar unit.  Everything that depends on the destination ROW only -- the source rows of
+// its window, "has the window's last row entered", the vertical blend weight -- is wave-uniform and lives in SGPRs
+// (readfirstlane), so the loop's control flow is scalar branches instead of exec-mask bookkeeping; and whether a lane
+// may take the fast window (its KS + 1 pixels lie inside the image) is decided once per WAVE: only the waves that touch
+// the left / right image border run the per-pixel reflecting loads.  With a per-lane choice in the loop the kernel spent
+// ~240 instructions per source row, most of them mask handling, where the arithmetic needs ~20.
 template <int U, int N, class F>
 __device__ __forceinline__ void prep_static_slots(F& f)
 {
@@ -845,15 +848,13 @@ __global__ __launch_bounds__(256) void k_prep_rows(const T* __restrict__ src, pt
                                                     ptrdiff_t img_stride, int W, int H, int wk, double scale_x,
                                                     nsof_blur_taps t, float* __restrict__ HA)
 {
-    constexpr int R = KS / 2, PPD = kPPD<T>, ND = (KS + PPD - 1) / PPD;
+    constexpr int R = KS / 2;
     const int j = blockIdx.x * 64 + (threadIdx.x & 63);
     const int rbase = (blockIdx.y * 4 + (threadIdx.x >> 6)) * PREPA_ROWS;
     if (j >= 2 * wk || rbase >= H) return;
-    int sx;
-    float a;
-    lin_coord_x(j >> 1, scale_x, W, sx, a);
-    const int c = (j & 1) ? min(sx + 1, W - 1) : sx;
-    const bool fast = c - R >= 0 && c - R + PPD * ND <= W;
+    const LinTap tx = lin_tap_x(j >> 1, scale_x, W);
+    const int c = (j & 1) ? tx.i1 : tx.i0;
+    const bool fast = window_fast<T, KS>(c, R, W);
     auto tk = [&](int q) { return t.k[q]; };
     const T* img = srow(src, blockIdx.z, img_stride);
     float* dst = HA + ((size_t)blockIdx.z * H) * (2 * wk) + j;
@@ -863,24 +864,8 @@ __global__ __launch_bounds__(256) void k_prep_rows(const T* __restrict__ src, pt
         if (r >= H) break;
         const T* rowp = srow(img, r, row_stride);
         float b[KS];
-        if (fast) {
-            if constexpr (kInt<T>) {
-#pragma unroll
-                for (int d = 0; d < ND; d++) {
-                    unsigned v;
-                    __builtin_memcpy(&v, rowp + (c - R) + PPD * d, 4);   // unaligned dword load
-#pragma unroll
-                    for (int e = 0; e < PPD; e++)
-                        if (PPD * d + e < KS) b[PPD * d + e] = px_el<T>(v, e);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < KS; i++) b[i] = rowp[c - R + i];
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < KS; i++) b[i] = px(rowp + reflect101(c - R + i, W));
-        }
+        if (fast) load_window<T, KS>(rowp, c - R, b);
+        else load_window_reflect<T, KS>(rowp, c - R, W, b);
         dst[(size_t)r * (2 * wk)] = row_filter<KS, FMA>(tk, KS, R, [&](int i) { return b[i]; });
     }
 }
@@ -894,238 +879,14 @@ __global__ __launch_bounds__(256) void k_prep_cols(const float* __restrict__ HA,
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (dx >= wk || dy >= hk) return;
-    int sx, sy;
-    float a1, b1;
-    lin_coord_x(dx, scale_x, W, sx, a1);
-    lin_coord_y(dy, scale_y, sy, b1);
-    const float a0 = 1.f - a1, b0 = 1.f - b1;
-    const int r0 = clampi(sy, 0, H - 1), r1 = clampi(sy + 1, 0, H - 1);
+    const LinTap tx = lin_tap_x(dx, scale_x, W), ty = lin_tap_y(dy, scale_y, H);   // (of tx, only the weight)
     auto tk = [&](int q) { return t.k[q]; };
     const float2* Hz = reinterpret_cast<const float2*>(HA) + ((size_t)blockIdx.z * H) * wk + dx;
-    float H0[KS + 1], H1[KS + 1];
+    float2 Hv[KS + 1];
 #pragma unroll
-    for (int i = 0; i <= KS; i++) {
-        const float2 h = Hz[(size_t)reflect101(r0 - R + i, H) * wk];
-        H0[i] = h.x;
-        H1[i] = h.y;
-    }
-    const float B00 = col_filter<KS, FMA>(tk, KS, R, [&](int q) { return H0[q]; });
-    const float B01 = col_filter<KS, FMA>(tk, KS, R, [&](int q) { return H1[q]; });
-    float B10 = B00, B11 = B01;
-    if (r1 != r0) {
-        B10 = col_filter<KS, FMA>(tk, KS, R + 1, [&](int q) { return H0[q]; });
-        B11 = col_filter<KS, FMA>(tk, KS, R + 1, [&](int q) { return H1[q]; });
-    }
-    const float t0 = nsof_madd<FMA>(B00, a0, B01 * a1);
-    const float t1 = nsof_madd<FMA>(B10, a0, B11 * a1);
-    out[((size_t)blockIdx.z * hk + dy) * wk + dx] = nsof_madd<FMA>(t0, b0, t1 * b1);
-}
-
-// ---------------------------------------------------------------------------------------
-// Coarse-to-fine flow resample: resize(prevFlow, INTER_LINEAR) then "flow *= 1/pyr_scale".
-// ---------------------------------------------------------------------------------------
-template <bool FMA>
-__global__ __launch_bounds__(256) void k_flow_upsample(const float* __restrict__ src, int sw, int sh,
-                                                        float* __restrict__ dst, int dw, int dh, double scale_x,
-                                                        double scale_y, float mul)
-{
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    int sx, sy;
-    float a1, b1;
-    lin_coord_x(dx, scale_x, sw, sx, a1);
-    lin_coord_y(dy, scale_y, sy, b1);
-    const float a0 = 1.f - a1, b0 = 1.f - b1;
-    const int c1 = min(sx + 1, sw - 1);
-    const int r0 = clampi(sy, 0, sh - 1), r1 = clampi(sy + 1, 0, sh - 1);
-    const float2* S = reinterpret_cast<const float2*>(src) + (size_t)blockIdx.z * sw * sh;
-    const float2 p00 = S[(size_t)r0 * sw + sx], p01 = S[(size_t)r0 * sw + c1];
-    const float2 p10 = S[(size_t)r1 * sw + sx], p11 = S[(size_t)r1 * sw + c1];
-    float2 o;
-    {
-        const float t0 = nsof_madd<FMA>(p00.x, a0, p01.x * a1), t1 = nsof_madd<FMA>(p10.x, a0, p11.x * a1);
-        o.x = nsof_madd<FMA>(t0, b0, t1 * b1) * mul;
-    }
-    {
-        const float t0 = nsof_madd<FMA>(p00.y, a0, p01.y * a1), t1 = nsof_madd<FMA>(p10.y, a0, p11.y * a1);
-        o.y = nsof_madd<FMA>(t0, b0, t1 * b1) * mul;
-    }
-    reinterpret_cast<float2*>(dst)[((size_t)blockIdx.z * dh + dy) * dw + dx] = o;
-}
-
-// Upsampling variant: a thread produces a 2x2 block of destination pixels.  When dst >= src in both directions,
-// consecutive destination coordinates map to source coordinates at most one apart, so the block's 4 pixels
-// sample from a 3x3 source neighbourhood: 9 float2 loads + 2 float4 stores per 4 pixels instead of 16 + 4 (the L1
-// serves 4 lanes per cycle per instruction, whatever its width).  Same arithmetic per pixel as k_flow_upsample.
-template <bool HET, bool FMA>
-__global__ __launch_bounds__(256) void k_flow_upsample2x2(const float* __restrict__ src, int sw, int sh,
-                                                           float* __restrict__ dst, int dw, int dh, double scale_x,
-                                                           double scale_y, float mul,
-                                                           const nsof_het_item* __restrict__ items)
-{
-    const int bx = blockIdx.x * 64 + (threadIdx.x & 63), by = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int dx0 = 2 * bx, dy0 = 2 * by;
-    size_t s_off, d_off;   // float2 offsets of this field in src / dst
-    if constexpr (HET) {
-        const nsof_het_item& it = items[blockIdx.z];
-        sw = it.pw; sh = it.ph; dw = it.wk; dh = it.hk;
-        s_off = it.offFc;
-        d_off = it.offF;
-        if (dx0 >= dw || dy0 >= dh) return;
-        if (sw == 0) {   // the item's coarsest level: its incoming flow is zero
-            float2* D = reinterpret_cast<float2*>(dst) + d_off;
-            for (int i = 0; i < 2 && dy0 + i < dh; i++)
-                for (int j = 0; j < 2 && dx0 + j < dw; j++) D[(size_t)(dy0 + i) * dw + dx0 + j] = make_float2(0.f, 0.f);
-            return;
-        }
-        scale_x = 1. / ((double)dw / sw);
-        scale_y = 1. / ((double)dh / sh);
-    } else {
-        s_off = (size_t)blockIdx.z * sw * sh;
-        d_off = (size_t)blockIdx.z * dw * dh;
-        if (dx0 >= dw || dy0 >= dh) return;
-    }
-    int sx[2], sy[2];
-    float a1[2], b1[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        lin_coord_x(min(dx0 + i, dw - 1), scale_x, sw, sx[i], a1[i]);
-        lin_coord_y(min(dy0 + i, dh - 1), scale_y, sy[i], b1[i]);
-    }
-    const float2* S = reinterpret_cast<const float2*>(src) + s_off;
-    // source columns sx[0]+{0,1,2} and rows sy[0]+{0,1,2}, clamped like the per-pixel kernel clamps them
-    float2 v[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const float2* row = S + (size_t)clampi(sy[0] + r, 0, sh - 1) * sw;
-#pragma unroll
-        for (int c = 0; c < 3; c++) v[r][c] = row[min(sx[0] + c, sw - 1)];
-    }
-    float2* D = reinterpret_cast<float2*>(dst) + d_off;
-#pragma unroll
-    for (int i = 0; i < 2; i++) {          // destination row dy0 + i
-        if (dy0 + i >= dh) break;
-        const int ro = sy[i] - sy[0];       // 0 or 1
-        const float bb1 = b1[i], bb0 = 1.f - bb1;
-        float2 o[2];
-#pragma unroll
-        for (int j = 0; j < 2; j++) {      // destination column dx0 + j
-            const int co = sx[j] - sx[0];   // 0 or 1
-            const float aa1 = a1[j], aa0 = 1.f - aa1;
-            const float2 p00 = ro ? (co ? v[1][1] : v[1][0]) : (co ? v[0][1] : v[0][0]);
-            const float2 p01 = ro ? (co ? v[1][2] : v[1][1]) : (co ? v[0][2] : v[0][1]);
-            const float2 p10 = ro ? (co ? v[2][1] : v[2][0]) : (co ? v[1][1] : v[1][0]);
-            const float2 p11 = ro ? (co ? v[2][2] : v[2][1]) : (co ? v[1][2] : v[1][1]);
-            {
-                const float t0 = nsof_madd<FMA>(p00.x, aa0, p01.x * aa1), t1 = nsof_madd<FMA>(p10.x, aa0, p11.x * aa1);
-                o[j].x = nsof_madd<FMA>(t0, bb0, t1 * bb1) * mul;
-            }
-            {
-                const float t0 = nsof_madd<FMA>(p00.y, aa0, p01.y * aa1), t1 = nsof_madd<FMA>(p10.y, aa0, p11.y * aa1);
-                o[j].y = nsof_madd<FMA>(t0, bb0, t1 * bb1) * mul;
-            }
-        }
-        float2* drow = D + (size_t)(dy0 + i) * dw + dx0;
-        if (dx0 + 1 < dw && (dw & 1) == 0 && (!HET || (d_off & 1) == 0))
-            nsof_store_stream4(reinterpret_cast<float*>(drow), o[0].x, o[0].y, o[1].x, o[1].y);
-        else {
-            drow[0] = o[0];
-            if (dx0 + 1 < dw) drow[1] = o[1];
-        }
-    }
-}
-
-// Upsampling as a row walk: a lane owns 2 adjacent destination columns (one 16-B store per row, so that a store
-// instruction of the wave writes 1 KiB contiguous) and walks down a segment of destination rows.  The (at most 3)
-// source columns its pixels sample are loaded once per SOURCE row, blended horizontally once, and reused by the
-// 2-3 destination rows that sample that source row.  Per-pixel arithmetic and its order are those of
-// k_flow_upsample.
-constexpr int UPW_SEG = 32;
-template <bool FMA>
-__global__ __launch_bounds__(256) void k_flow_upsample_walk(const float* __restrict__ src, int sw, int sh,
-                                                             float* __restrict__ dst, int dw, int dh, double scale_x,
-                                                             double scale_y, float mul)
-{
-    constexpr int NPL = 2, NV = NPL + 1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // the 4 waves of a block take adjacent column chunks of the SAME rows: 4 KiB contiguous per row and block
-    const int dx0 = ((blockIdx.x * 4 + wave) * 64 + lane) * NPL;
-    const int y0 = blockIdx.y * UPW_SEG;
-    if (y0 >= dh || (blockIdx.x * 4 + wave) * 64 * NPL >= dw) return;   // wave-uniform
-    const int y1 = min(y0 + UPW_SEG, dh);
-    const bool live = dx0 < dw;
-    int base = 0, i0[NPL], i1[NPL];
-    float a0[NPL], a1[NPL];
-#pragma unroll
-    for (int i = 0; i < NPL; i++) {
-        int sx;
-        lin_coord_x(min(dx0 + i, dw - 1), scale_x, sw, sx, a1[i]);
-        a0[i] = 1.f - a1[i];
-        if (i == 0) base = sx;
-        i0[i] = sx - base;                                    // 0..NPL-1 when upsampling
-        i1[i] = min(sx + 1, sw - 1) - base;                   // 0..NPL
-    }
-    const float2* S = reinterpret_cast<const float2*>(src) + (size_t)blockIdx.z * sw * sh;
-    float2* D = reinterpret_cast<float2*>(dst) + (size_t)blockIdx.z * dw * dh;
-    auto pick = [](const float2 (&V)[NV], int k) {
-        float2 r = V[0];
-#pragma unroll
-        for (int q = 1; q < NV; q++) r = k == q ? V[q] : r;
-        return r;
-    };
-    // horizontal blend of source row r at the lane's destination columns
-    auto hrow = [&](int r, float2 (&h)[NPL]) {
-        const float2* row = S + (size_t)r * sw;
-        float2 V[NV];
-#pragma unroll
-        for (int k = 0; k < NV; k++) V[k] = row[min(base + k, sw - 1)];
-#pragma unroll
-        for (int i = 0; i < NPL; i++) {
-            const float2 p0 = pick(V, i0[i]), p1 = pick(V, i1[i]);
-            h[i].x = nsof_madd<FMA>(p0.x, a0[i], p1.x * a1[i]);
-            h[i].y = nsof_madd<FMA>(p0.y, a0[i], p1.y * a1[i]);
-        }
-    };
-    float2 hA[NPL], hB[NPL];
-    int ra = -1, rb = -1;
-    for (int dy = y0; dy < y1; dy++) {
-        int sy;
-        float b1;
-        lin_coord_y(dy, scale_y, sy, b1);
-        const float b0 = 1.f - b1;
-        const int r0 = clampi(sy, 0, sh - 1), r1 = clampi(sy + 1, 0, sh - 1);
-        if (r0 != ra) {                                       // all branches are wave-uniform
-            if (r0 == rb) {
-#pragma unroll
-                for (int i = 0; i < NPL; i++) hA[i] = hB[i];
-            } else {
-                hrow(r0, hA);
-            }
-            ra = r0;
-        }
-        const bool same = r1 == ra;
-        if (!same && r1 != rb) {
-            hrow(r1, hB);
-            rb = r1;
-        }
-        if (live) {
-            float2 o[NPL];
-#pragma unroll
-            for (int i = 0; i < NPL; i++) {
-                const float2 t0 = hA[i], t1 = same ? hA[i] : hB[i];
-                o[i].x = nsof_madd<FMA>(t0.x, b0, t1.x * b1) * mul;
-                o[i].y = nsof_madd<FMA>(t0.y, b0, t1.y * b1) * mul;
-            }
-            float2* drow = D + (size_t)dy * dw + dx0;
-            if (dx0 + 1 < dw && (dw & 1) == 0) {
-                nsof_store_stream4(reinterpret_cast<float*>(drow), o[0].x, o[0].y, o[1].x, o[1].y);
-            } else {
-                drow[0] = o[0];
-                if (dx0 + 1 < dw) drow[1] = o[1];
-            }
-        }
-    }
+    for (int i = 0; i <= KS; i++) Hv[i] = Hz[(size_t)reflect101(ty.i0 - R + i, H) * wk];
+    out[((size_t)blockIdx.z * hk + dy) * wk + dx] = resample_tail<KS, FMA>(
+        tk, [&](int q) { return Hv[q].x; }, [&](int q) { return Hv[q].y; }, ty.i1 != ty.i0, tx.w1, ty.w1);
 }
 
 }  // namespace
@@ -1133,10 +894,60 @@ __global__ __launch_bounds__(256) void k_flow_upsample_walk(const float* __restr
 // =========================================================================================
 // launchers
 // =========================================================================================
+namespace {
+// ---- sizing ---------------------------------------------------------------------------------------------------------
+// Dynamic LDS of k_prep_tiled for source steps (scale_x, scale_y) per destination pixel: row-filtered rows
+// [rh_cap][2 TW] and blurred samples [2 TH][2 TW] as f32, then a tile's source footprint [rh_cap][rw_cap] in pixels of
+// px_bytes.  The kernel derives the footprint from the same arithmetic (+4 columns of slack for its aligned copy).
+struct TiledLds {
+    int rw_cap, rh_cap;
+    size_t bytes;
+};
+TiledLds tiled_lds(double scale_x, double scale_y, int ksize, size_t px_bytes)
+{
+    const int r = ksize / 2;
+    TiledLds l;
+    l.rw_cap = ((int)ceil(PREP_TW * scale_x) + 2 * r + 8 + 3) / 4 * 4;
+    l.rh_cap = (int)ceil(PREP_TH * scale_y) + 2 * r + 4;
+    l.bytes = sizeof(float) * ((size_t)l.rh_cap * 2 * PREP_TW + 2 * PREP_TH * 2 * PREP_TW) + (size_t)l.rh_cap * l.rw_cap * px_bytes;
+    return l;
+}
+// Rows of a wave's segment in the walking kernels: `rows`, stepped down by `shorter` while it is above min_rows and the
+// launch (waves_x waves across, n_img images of total_rows rows) has fewer than want_waves waves.  A segment re-runs
+// ~KS + 1 source rows of warm-up, which only matters when the GPU is full anyway.
+template <class Shorter>
+int segment_rows(int rows, int min_rows, long waves_x, int total_rows, int n_img, long want_waves, Shorter shorter)
+{
+    while (rows > min_rows && waves_x * ((total_rows + rows - 1) / rows) * n_img < want_waves) rows = shorter(rows);
+    return rows;
+}
+// k_prep_tiled<tiled_ks(ksize), HET, T, FMA> over `grid`; more than 64 KB of LDS (work lists of 16-bit frames) is opted in.
+template <bool HET, typename T, bool FMA>
+int launch_tiled(nsof_ctx* ctx, dim3 grid, const TiledLds& l, const T* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
+                 int H, int wk, int hk, double scale_x, double scale_y, const nsof_blur_taps& taps, float* out,
+                 const nsof_het_item* d_items)
+{
+    int rc = NSOF_OK;
+    nsof_with_int<0, 19>(tiled_ks(taps.ksize), [&](auto ks) {
+        constexpr int KS = decltype(ks)::value;
+        if constexpr (KS == tiled_ks(KS)) {
+            rc = [&]() -> int {
+                auto kern = k_prep_tiled<KS, HET, T, FMA>;
+                if (l.bytes > 64 * 1024)
+                    NSOF_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.bytes));
+                hipLaunchKernelGGL(kern, grid, dim3(256), l.bytes, ctx->stream, src, row_stride, img_stride, W, H, wk, hk, scale_x,
+                                   scale_y, l.rw_cap, l.rh_cap, taps, out, d_items);
+                return NSOF_OK;
+            }();
+        }
+    });
+    return rc;
+}
+dim3 tiled_grid(int wk, int hk, int n) { return dim3((wk + PREP_TW - 1) / PREP_TW, (hk + PREP_TH - 1) / PREP_TH, n); }
+
 // Levels 1..3 of a pyr_scale 0.5 pyramid in one launch (k_prep_decim3).  Returns NSOF_EUNSUPPORTED without launching
 // when the frames do not decimate exactly by 8 (or are not aligned for the vector walks): the caller then runs the
 // levels one by one.  out[k - 1]: level k's images, [n_img][H >> k][W >> k].
-namespace {
 template <typename T, bool FMA>
 int prep_decim3_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H,
                      const nsof_blur_taps* taps, float* const* out)
@@ -1155,10 +966,9 @@ int prep_decim3_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_strid
         d.out[k] = out[k];
     }
     // a wave's segment covers the same 96 source rows at every level (48 / 24 / 12 output rows: multiples of the walks'
-    // unroll counts 2 / 3 / 3); few images: shorter segments, as in the one-level launcher
-    int src_rows = 96;
+    // unroll counts 2 / 3 / 3); few images: shorter segments, down to 24 source rows, until there are ~1000 waves
     const long waves_x = (W / CWL + 63) / 64;
-    while (src_rows > 24 && waves_x * ((H + src_rows - 1) / src_rows) * n_img < 1024) src_rows -= 24;
+    const int src_rows = segment_rows(96, 24, waves_x, H, n_img, 1024, [](int rows) { return rows - 24; });
     d.seg_rows[0] = src_rows / 2;
     d.seg_rows[1] = src_rows / 4;
     d.seg_rows[2] = src_rows / 8;
@@ -1173,218 +983,149 @@ int prep_decim3_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_strid
     return NSOF_OK;
 }
 
+// ---- one uniform level: the route, then its launch -------------------------------------------------------------------
+enum PrepRoute {
+    ROUTE_SAME3_VEC,   // same size, 3 taps, rows aligned for 4-pixel vector loads
+    ROUTE_SAME,        // same size, anything else
+    ROUTE_DECIM,       // exact decimation by 2 / 4 / 8 with the kernel sizes the pyr_scale 0.5 pyramid produces
+    ROUTE_WALK,        // 3 / 5 / 9 taps while consecutive destination rows share source rows
+    ROUTE_DIRECT,      // 3 / 5 taps otherwise (larger kernels: registers run out)
+    ROUTE_ROWS_COLS,   // 19 taps: two passes
+    ROUTE_TILED,       // what fits the LDS budget
+    ROUTE_NAIVE        // upscaling, or a footprint too large for the LDS
+};
+constexpr int decim_lane_cols(int W) { return (W & 15) == 0 ? 16 : 8; }   // source columns per lane of k_prep_decim
+
+// The kernel a level takes, by precedence.  The measurements that set the order (MI355X, 1080p):
+//   walk over direct, per 128-image launch at pyr_scale 0.6: level 1 (3 taps) 637 -> 334 us, level 2 (5 taps) 403 ->
+//     266 us; per 256 images 3 taps 658 -> 497 us, 5 taps 519 -> 490 us;
+//   walk over tiled at 9 taps (level 3: 415 x 233 outputs, 4.6 source rows per destination row): 762 vs 813 us per 256;
+//   rows + cols over tiled at 19 taps, 64 frames: 459 -> 244 us; 9 taps is still faster tiled (231 vs 254 us).
+template <typename T>
+PrepRoute prep_route(const T* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H, int wk, int hk, int ksize)
+{
+    auto aligned = [&](int a) {
+        return (row_stride % a) == 0 && (img_stride % a) == 0 && (reinterpret_cast<uintptr_t>(src) % a) == 0;
+    };
+    // the 4-pixel lanes' vector row loads: a dword (u8) / 8 bytes (16-bit) / 16 bytes (f32) at every 4th column
+    const bool rows_va = aligned(4 * (int)sizeof(T));
+    if (wk == W && hk == H) return ksize == 3 && (W & 3) == 0 && rows_va && W >= 8 ? ROUTE_SAME3_VEC : ROUTE_SAME;
+
+    const double scale_x = inv_scale(wk, W), scale_y = inv_scale(hk, H);
+    const bool downscale = scale_x >= 1.0 && scale_y >= 1.0;
+    const int S = W / wk, CWL = decim_lane_cols(W);
+    // 8-bit: a lane's CWL bytes are one load; 16-bit / f32: 8- / 16-byte aligned rows (4-pixel vector loads), and f32
+    // takes 8-column lanes only while the blur halo fits in one (S = 2, 4)
+    const bool decim_al = kU8<T> ? aligned(CWL) : rows_va && (CWL == 16 || S <= 4 || sizeof(T) == 2);
+    const bool decim_ok = S >= 2 && W == S * wk && H == S * hk && (W % CWL) == 0 && W >= 64 && decim_al &&
+                          ((S == 2 && ksize == 3) || (S == 4 && ksize == 9) || (S == 8 && ksize == 19)) && H > ksize;
+    const bool walk_ok = downscale && scale_y < ksize && (ksize == 3 || ksize == 5 || ksize == 9);
+    const bool direct_ok = downscale && (ksize == 3 || ksize == 5);
+    if (decim_ok) return ROUTE_DECIM;
+    if (walk_ok) return ROUTE_WALK;
+    if (direct_ok) return ROUTE_DIRECT;
+    if (downscale && ksize == 19) return ROUTE_ROWS_COLS;
+    if (downscale && tiled_lds(scale_x, scale_y, ksize, sizeof(T)).bytes <= 60 * 1024) return ROUTE_TILED;
+    return ROUTE_NAIVE;
+}
+
 template <typename T, bool FMA>
 int prep_impl(nsof_ctx* ctx, int n_img, const T* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H, int wk, int hk,
               const nsof_blur_taps& taps, float* out)
 {
     nsof_prof_scope ps(ctx, NSOF_K_PREP);
-    // the 4-pixel lanes' vector row loads: a dword (u8) / 8 bytes (16-bit) / 16 bytes (f32) at every 4th column
-    const int VA = 4 * (int)sizeof(T);
-    const bool rows_va = (row_stride % VA) == 0 && (img_stride % VA) == 0 && (reinterpret_cast<uintptr_t>(src) % VA) == 0;
-    if (wk == W && hk == H) {
-        const bool aligned = (W & 3) == 0 && rows_va && W >= 8;
-        if (taps.ksize == 3 && aligned) {
-            dim3 grid((W / 4 + 63) / 64, (H + 4 * PREP0_ROWS - 1) / (4 * PREP0_ROWS), n_img);
-            hipLaunchKernelGGL((k_prep_same3_vec<false, T, FMA>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W,
-                               H, taps.k[1], taps.k[2], out, nullptr);
-        } else {
-            dim3 grid((W + 63) / 64, (H + 3) / 4, n_img);
-            hipLaunchKernelGGL((k_prep_same<false, T, FMA>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
-                               taps, out, nullptr, -1);
+    const double scale_x = inv_scale(wk, W), scale_y = inv_scale(hk, H);
+    const dim3 block(256), per_pixel = nsof_pixel_grid(wk, hk, n_img);
+    switch (prep_route(src, row_stride, img_stride, W, H, wk, hk, taps.ksize)) {
+    case ROUTE_SAME3_VEC:
+        hipLaunchKernelGGL((k_prep_same3_vec<false, T, FMA>), dim3((W / 4 + 63) / 64, (H + 4 * PREP0_ROWS - 1) / (4 * PREP0_ROWS), n_img),
+                           block, 0, ctx->stream, src, row_stride, img_stride, W, H, taps.k[1], taps.k[2], out, nullptr);
+        break;
+    case ROUTE_SAME:
+        hipLaunchKernelGGL((k_prep_same<false, T, FMA>), per_pixel, block, 0, ctx->stream, src, row_stride, img_stride, W, H, taps,
+                           out, nullptr, -1);
+        break;
+    case ROUTE_DECIM: {
+        const int S = W / wk, CWL = decim_lane_cols(W);
+        // segments of output rows: multiples of the unroll count, ~16 source rows of warm-up amortised
+        const int U = S == 2 ? 2 : 3;
+        int seg_rows = S == 2 ? 32 : (S == 4 ? 24 : 15);
+        seg_rows = (seg_rows + U - 1) / U * U;
+        // few images (one call per camera frame): shorter segments so that the launch still has ~1000 waves
+        const long waves_x = (W / CWL + 63) / 64;
+        if (waves_x * ((hk + seg_rows - 1) / seg_rows) * n_img < 1024) {
+            const long want_seg = (1024 + waves_x * n_img - 1) / (waves_x * n_img);
+            seg_rows = std::min(seg_rows, (int)std::max<long>(U, (hk / want_seg) / U * U));
         }
-    } else {
-        const double scale_x = 1. / ((double)wk / W), scale_y = 1. / ((double)hk / H);
-        const int r = taps.ksize / 2;
-        const int rw_cap = ((int)ceil(PREP_TW * scale_x) + 2 * r + 8 + 3) / 4 * 4;
-        const int rh_cap = (int)ceil(PREP_TH * scale_y) + 2 * r + 4;
-        const size_t smem = sizeof(float) * ((size_t)rh_cap * 2 * PREP_TW + 2 * PREP_TH * 2 * PREP_TW) +
-                            (size_t)rh_cap * rw_cap * sizeof(T);
-        const bool direct_ok = scale_x >= 1.0 && scale_y >= 1.0 &&
-                               (taps.ksize == 3 || taps.ksize == 5);   // larger kernels: registers run out
-        // exact decimation by 2 / 4 / 8 with the kernel sizes the pyr_scale 0.5 pyramid produces
-        const int S = W / wk;
-        const int CWL = (W & 15) == 0 ? 16 : 8;   // source columns per lane
-        // 16-bit / f32: 8- / 16-byte aligned rows (4-pixel vector loads); f32 takes 8-column lanes only while the blur
-        // halo fits in one (S = 2, 4)
-        const bool decim_al = kU8<T> ? (row_stride % CWL) == 0 && (img_stride % CWL) == 0 &&
-                                           (reinterpret_cast<uintptr_t>(src) % CWL) == 0
-                                     : rows_va && (CWL == 16 || S <= 4 || sizeof(T) == 2);
-        const bool decim_ok = S >= 2 && W == S * wk && H == S * hk && (W % CWL) == 0 && W >= 64 && decim_al &&
-                              ((S == 2 && taps.ksize == 3) || (S == 4 && taps.ksize == 9) ||
-                               (S == 8 && taps.ksize == 19)) &&
-                              H > taps.ksize;
-        if (decim_ok) {
-            // segments of output rows: multiples of the unroll count, ~16 source rows of warm-up amortised
-            const int U = S == 2 ? 2 : 3;
-            int seg_rows = S == 2 ? 32 : (S == 4 ? 24 : 15);
-            seg_rows = (seg_rows + U - 1) / U * U;
-            {
-                // few images (one call per camera frame): shorter segments so that the launch still has ~1000 waves;
-                // a segment re-runs ~KS+1 source rows of warm-up, which only matters when the GPU is full anyway
-                const long waves_x = (W / CWL + 63) / 64;
-                const long have = waves_x * ((hk + seg_rows - 1) / seg_rows) * n_img;
-                if (have < 1024) {
-                    const long want_seg = (1024 + waves_x * n_img - 1) / (waves_x * n_img);
-                    const int rows = (int)std::max<long>(U, (hk / want_seg) / U * U);
-                    if (rows < seg_rows) seg_rows = rows;
-                }
-            }
-            const int nseg = (hk + seg_rows - 1) / seg_rows;
-            dim3 grid((W / CWL + 63) / 64, (nseg + 3) / 4, n_img);
-            // level k = 1, 2, 3 (S = 2^k with 3, 9, 19 taps) x 8- or 16-column lanes; no float 8-column walk at S = 8
-            // (decim_al above)
-            nsof_with_int<1, 3>(S == 2 ? 1 : (S == 4 ? 2 : 3), [&](auto k) {
-                constexpr int SS = 1 << decltype(k)::value, KS = SS == 2 ? 3 : (SS == 4 ? 9 : 19);
-                nsof_with_int<1, 2>(CWL / 8, [&](auto c) {
-                    constexpr int CW = 8 * decltype(c)::value;
-                    if constexpr (CW == 16 || SS < 8 || sizeof(T) <= 2)
-                        hipLaunchKernelGGL((k_prep_decim<SS, KS, CW, T, FMA>), grid, dim3(256), 0, ctx->stream, src, row_stride,
-                                           img_stride, W, H, wk, hk, seg_rows, taps, out);
-                });
+        const int nseg = (hk + seg_rows - 1) / seg_rows;
+        dim3 grid((unsigned)waves_x, (nseg + 3) / 4, n_img);
+        // level k = 1, 2, 3 (S = 2^k with 3, 9, 19 taps) x 8- or 16-column lanes; no float 8-column walk at S = 8
+        nsof_with_int<1, 3>(S == 2 ? 1 : (S == 4 ? 2 : 3), [&](auto k) {
+            constexpr int SS = 1 << decltype(k)::value, KS = SS == 2 ? 3 : (SS == 4 ? 9 : 19);
+            nsof_with_int<1, 2>(CWL / 8, [&](auto c) {
+                constexpr int CW = 8 * decltype(c)::value;
+                if constexpr (CW == 16 || SS < 8 || sizeof(T) <= 2)
+                    hipLaunchKernelGGL((k_prep_decim<SS, KS, CW, T, FMA>), grid, block, 0, ctx->stream, src, row_stride, img_stride,
+                                       W, H, wk, hk, seg_rows, taps, out);
             });
-        } else if (scale_x >= 1.0 && scale_y >= 1.0 && scale_y < taps.ksize &&
-                   (taps.ksize == 3 || taps.ksize == 5 || taps.ksize == 9)) {
-            // measured per 128-image launch at 1080p, pyr_scale 0.6: level 1 (3 taps) 637 -> 334 us, level 2 (5 taps) 403 ->
-            // 266 us against the direct kernel (static-slot ring: 367 / 322 us with a shifting ring).  Round 4 (scalar
-            // control flow, per-wave fast path, a block of loads in flight; per 256 images): 3 taps 658 -> 497 us, 5 taps
-            // 519 -> 490 us, and with 9 taps (level 3: 415 x 233 outputs, 4.6 source rows per destination row) the walk
-            // now beats the tiled kernel too (762 vs 813 us), which it lost to before (624 vs 415 us per 128)
-            // segments of destination rows: long enough that the KS+1 rows of warm-up are a few per cent, short enough
-            // that a small batch still has a few thousand waves
-            int seg_rows = 32;
-            const long waves_x = (wk + 63) / 64;
-            while (seg_rows > 8 && waves_x * ((hk + seg_rows - 1) / seg_rows) * n_img < 2048) seg_rows /= 2;
-            const int nseg = (hk + seg_rows - 1) / seg_rows;
-            dim3 grid((unsigned)waves_x, (nseg + 3) / 4, n_img);
-            nsof_with_int<3, 9>(taps.ksize, [&](auto ks) {
-                constexpr int KS = decltype(ks)::value;
-                if constexpr (KS == 3 || KS == 5 || KS == 9)
-                    hipLaunchKernelGGL((k_prep_walk<KS, T, FMA>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
-                                       wk, hk, scale_x, scale_y, seg_rows, taps, out);
-            });
-        } else if (direct_ok) {
-            dim3 grid((wk + 63) / 64, (hk + 3) / 4, n_img);
-            nsof_with_int<3, 5>(taps.ksize, [&](auto ks) {
-                constexpr int KS = decltype(ks)::value;
-                if constexpr (KS != 4)
-                    hipLaunchKernelGGL((k_prep_direct<KS, false, T, FMA>), grid, dim3(256), 0, ctx->stream, src, row_stride,
-                                       img_stride, W, H, wk, hk, scale_x, scale_y, taps, out, nullptr);
-            });
-        } else if (taps.ksize == 19 && scale_x >= 1.0 && scale_y >= 1.0) {
-            // measured at 1080p x 64 frames: 19 taps 459 -> 244 us; 9 taps is still faster tiled (231 vs 254 us)
-            int rc = ctx->tmp.reserve(ctx, (size_t)n_img * H * 2 * wk * sizeof(float));
-            if (rc) return rc;
-            float* HA = static_cast<float*>(ctx->tmp.p);
-            dim3 ga((2 * wk + 63) / 64, (H + 4 * PREPA_ROWS - 1) / (4 * PREPA_ROWS), n_img);
-            dim3 gb((wk + 63) / 64, (hk + 3) / 4, n_img);
-            hipLaunchKernelGGL((k_prep_rows<19, T, FMA>), ga, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H, wk,
-                               scale_x, taps, HA);
-            hipLaunchKernelGGL((k_prep_cols<19, FMA>), gb, dim3(256), 0, ctx->stream, HA, W, H, wk, hk, scale_x, scale_y, taps,
-                               out);
-        } else if (smem <= 60 * 1024 && scale_x >= 1.0 && scale_y >= 1.0) {
-            dim3 grid((wk + PREP_TW - 1) / PREP_TW, (hk + PREP_TH - 1) / PREP_TH, n_img);
-            nsof_with_int<0, 19>(tiled_ks(taps.ksize), [&](auto ks) {
-                constexpr int KS = decltype(ks)::value;
-                if constexpr (KS == tiled_ks(KS))
-                    hipLaunchKernelGGL((k_prep_tiled<KS, false, T, FMA>), grid, dim3(256), smem, ctx->stream, src, row_stride,
-                                       img_stride, W, H, wk, hk, scale_x, scale_y, rw_cap, rh_cap, taps, out, nullptr);
-            });
-        } else {
-            dim3 grid((wk + 63) / 64, (hk + 3) / 4, n_img);
-            hipLaunchKernelGGL((k_prep_naive<false, T, FMA>), grid, dim3(256), 0, ctx->stream, src, row_stride, img_stride, W, H,
-                               wk, hk, scale_x, scale_y, taps, out, nullptr);
-        }
+        });
+        break;
+    }
+    case ROUTE_WALK: {
+        // segments of destination rows: long enough that the KS + 1 rows of warm-up are a few per cent, short enough
+        // that a small batch still has a few thousand waves
+        const long waves_x = (wk + 63) / 64;
+        const int seg_rows = segment_rows(32, 8, waves_x, hk, n_img, 2048, [](int rows) { return rows / 2; });
+        const int nseg = (hk + seg_rows - 1) / seg_rows;
+        dim3 grid((unsigned)waves_x, (nseg + 3) / 4, n_img);
+        nsof_with_int<3, 9>(taps.ksize, [&](auto ks) {
+            constexpr int KS = decltype(ks)::value;
+            if constexpr (KS == 3 || KS == 5 || KS == 9)
+                hipLaunchKernelGGL((k_prep_walk<KS, T, FMA>), grid, block, 0, ctx->stream, src, row_stride, img_stride, W, H, wk, hk,
+                                   scale_x, scale_y, seg_rows, taps, out);
+        });
+        break;
+    }
+    case ROUTE_DIRECT:
+        nsof_with_int<3, 5>(taps.ksize, [&](auto ks) {
+            constexpr int KS = decltype(ks)::value;
+            if constexpr (KS != 4)
+                hipLaunchKernelGGL((k_prep_direct<KS, false, T, FMA>), per_pixel, block, 0, ctx->stream, src, row_stride, img_stride,
+                                   W, H, wk, hk, scale_x, scale_y, taps, out, nullptr);
+        });
+        break;
+    case ROUTE_ROWS_COLS: {
+        int rc = ctx->tmp.reserve(ctx, (size_t)n_img * H * 2 * wk * sizeof(float));
+        if (rc) return rc;
+        float* HA = static_cast<float*>(ctx->tmp.p);
+        dim3 ga((2 * wk + 63) / 64, (H + 4 * PREPA_ROWS - 1) / (4 * PREPA_ROWS), n_img);
+        hipLaunchKernelGGL((k_prep_rows<19, T, FMA>), ga, block, 0, ctx->stream, src, row_stride, img_stride, W, H, wk, scale_x,
+                           taps, HA);
+        hipLaunchKernelGGL((k_prep_cols<19, FMA>), per_pixel, block, 0, ctx->stream, HA, W, H, wk, hk, scale_x, scale_y, taps, out);
+        break;
+    }
+    case ROUTE_TILED: {
+        int rc = launch_tiled<false, T, FMA>(ctx, tiled_grid(wk, hk, n_img), tiled_lds(scale_x, scale_y, taps.ksize, sizeof(T)), src,
+                                             row_stride, img_stride, W, H, wk, hk, scale_x, scale_y, taps, out, nullptr);
+        if (rc) return rc;
+        break;
+    }
+    case ROUTE_NAIVE:
+        hipLaunchKernelGGL((k_prep_naive<false, T, FMA>), per_pixel, block, 0, ctx->stream, src, row_stride, img_stride, W, H, wk,
+                           hk, scale_x, scale_y, taps, out, nullptr);
+        break;
     }
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
-}  // namespace
 
-int nsof_launch_prep_decim3(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H,
-                            const nsof_blur_taps* taps, float* const* out, int src_type)
-{
-    // f32 frames take the three one-level launches (k_prep_decim<.., float>): at 768 threads per workgroup a wave has
-    // 168 registers, and the float rows of the three walks side by side spilled (~400 registers' worth to scratch)
-    int rc = NSOF_EUNSUPPORTED;
-    nsof_with_src_type(src_type, [&](auto px_tag) {
-        using T = typename decltype(px_tag)::type;
-        if constexpr (kInt<T>) {
-            const T* s = static_cast<const T*>(src);
-            rc = ctx->opt_pyr_fma ? prep_decim3_impl<T, true>(ctx, n_img, s, row_stride, img_stride, W, H, taps, out)
-                                  : prep_decim3_impl<T, false>(ctx, n_img, s, row_stride, img_stride, W, H, taps, out);
-        }
-    });
-    return rc;
-}
-
-int nsof_launch_prep(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H, int wk,
-                     int hk, const nsof_blur_taps& taps, float* out, int src_type)
-{
-    int rc = NSOF_OK;
-    const bool known = nsof_with_src_type(src_type, [&](auto px_tag) {
-        using T = typename decltype(px_tag)::type;
-        const T* s = static_cast<const T*>(src);
-        rc = ctx->opt_pyr_fma ? prep_impl<T, true>(ctx, n_img, s, row_stride, img_stride, W, H, wk, hk, taps, out)
-                              : prep_impl<T, false>(ctx, n_img, s, row_stride, img_stride, W, H, wk, hk, taps, out);
-    });
-    return known ? rc : nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", src_type);
-}
-
-namespace {
-template <bool FMA>
-int flow_upsample_impl(nsof_ctx* ctx, int n_pairs, const float* src, int sw, int sh, float* dst, int dw, int dh, float mul)
-{
-    nsof_prof_scope ps(ctx, NSOF_K_UPSAMPLE);
-    const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
-    if (dw >= sw && dh >= sh && sw >= 1 && sh >= 1 && dw >= 256) {
-        // upsampling: source steps of 0 or 1 between neighbours; rows wide enough for a lane per 2 columns
-        dim3 g(((dw + 1) / 2 + 255) / 256, (dh + UPW_SEG - 1) / UPW_SEG, n_pairs);
-        hipLaunchKernelGGL(k_flow_upsample_walk<FMA>, g, dim3(256), 0, ctx->stream, src, sw, sh, dst, dw, dh, scale_x,
-                           scale_y, mul);
-        NSOF_HIP(ctx, hipGetLastError());
-        return NSOF_OK;
-    }
-    if (dw >= sw && dh >= sh && sw >= 1 && sh >= 1) {   // upsampling: source steps of 0 or 1 between neighbours
-        dim3 g2(((dw + 1) / 2 + 63) / 64, ((dh + 1) / 2 + 3) / 4, n_pairs);
-        hipLaunchKernelGGL((k_flow_upsample2x2<false, FMA>), g2, dim3(256), 0, ctx->stream, src, sw, sh, dst, dw, dh, scale_x,
-                           scale_y, mul, nullptr);
-        NSOF_HIP(ctx, hipGetLastError());
-        return NSOF_OK;
-    }
-    dim3 grid((dw + 63) / 64, (dh + 3) / 4, n_pairs);
-    hipLaunchKernelGGL(k_flow_upsample<FMA>, grid, dim3(256), 0, ctx->stream, src, sw, sh, dst, dw, dh, scale_x, scale_y,
-                       mul);
-    NSOF_HIP(ctx, hipGetLastError());
-    return NSOF_OK;
-}
-}  // namespace
-
-int nsof_launch_flow_upsample(nsof_ctx* ctx, int n_pairs, const float* src, int sw, int sh, float* dst, int dw, int dh, float mul)
-{
-    return ctx->opt_pyr_fma ? flow_upsample_impl<true>(ctx, n_pairs, src, sw, sh, dst, dw, dh, mul)
-                            : flow_upsample_impl<false>(ctx, n_pairs, src, sw, sh, dst, dw, dh, mul);
-}
-
-// =========================================================================================
-// work-list (shape-heterogeneous) launchers: one launch per stage and level over a device table
-// =========================================================================================
-namespace {
-template <int KS, typename T, bool FMA>
-int launch_tiled_het(nsof_ctx* ctx, dim3 grid, size_t smem, int rw_cap, int rh_cap, const nsof_blur_taps& taps, float* I,
-                     const nsof_het_item* d_items)
-{
-    auto kern = k_prep_tiled<KS, true, T, FMA>;
-    if (smem > 64 * 1024)
-        NSOF_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(kern, grid, dim3(256), smem, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1., rw_cap, rh_cap, taps, I,
-                       d_items);
-    return NSOF_OK;
-}
-
-// T: the pixel type of every item's frames (the list's src_type).  Kernel choice as for 8-bit items; with 16-bit / float
-// frames NSOF_HET_VEC0 means 8- / 16-byte aligned rows (k_prep_same3_vec's 4-pixel loads), the scalar k_prep_same takes
-// the rest.  The LDS-tiled kernel's budget is 60 KB, and 78 KB for 16-bit frames: the 19-tap scale-8 level of large
-// crops needs ~75 KB at 2 B/px (50 KB at 1), and two workgroups still fit the CU's 160 KB.
+// ---- work lists (shape-heterogeneous): one launch per level over a device table -----------------------------------
+// T: the pixel type of every item's frames (the list's src_type).  The rule set is shorter than a uniform level's (no
+// decimating walk, no row walk, no two-pass form): same-size levels as above, per item; 3 / 5 taps direct; then tiled
+// within the LDS budget, else per pixel.  With 16-bit / float frames NSOF_HET_VEC0 means 8- / 16-byte aligned rows
+// (k_prep_same3_vec's 4-pixel loads), the scalar k_prep_same takes the rest.  The LDS-tiled kernel's budget is 60 KB,
+// and 78 KB for 16-bit frames: the 19-tap scale-8 level of large crops needs ~75 KB at 2 B/px (50 KB at 1), and two
+// workgroups still fit the CU's 160 KB.
 template <typename T, bool FMA>
 int prep_het_impl(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items, bool level0,
                   const nsof_blur_taps& taps, float* I)
@@ -1394,77 +1135,88 @@ int prep_het_impl(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, cons
     double max_sx = 1, max_sy = 1;
     for (int i = 0; i < n_items; i++) {
         const nsof_het_item& it = h_items[i];
-        max_wk = it.wk > max_wk ? it.wk : max_wk;
-        max_hk = it.hk > max_hk ? it.hk : max_hk;
+        max_wk = std::max(max_wk, it.wk);
+        max_hk = std::max(max_hk, it.hk);
         n_vec += (it.flags & NSOF_HET_VEC0) ? 1 : 0;
-        const double sx = 1. / ((double)it.wk / it.W), sy = 1. / ((double)it.hk / it.H);
-        max_sx = sx > max_sx ? sx : max_sx;
-        max_sy = sy > max_sy ? sy : max_sy;
+        max_sx = std::max(max_sx, inv_scale(it.wk, it.W));
+        max_sy = std::max(max_sy, inv_scale(it.hk, it.H));
     }
     const int nz = 2 * n_items;
+    const dim3 block(256), per_pixel = nsof_pixel_grid(max_wk, max_hk, nz);
+    const TiledLds lds = tiled_lds(max_sx, max_sy, taps.ksize, sizeof(T));
     if (level0) {   // same-size level: 3 taps; aligned items take the vector kernel, the others the generic one
         if (taps.ksize == 3 && n_vec > 0) {
             dim3 grid((max_wk / 4 + 63) / 64, (max_hk + 4 * PREP0_ROWS - 1) / (4 * PREP0_ROWS), nz);
-            hipLaunchKernelGGL((k_prep_same3_vec<true, T, FMA>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps.k[1],
+            hipLaunchKernelGGL((k_prep_same3_vec<true, T, FMA>), grid, block, 0, ctx->stream, nullptr, 0, 0, 0, 0, taps.k[1],
                                taps.k[2], I, d_items);
         }
-        if (taps.ksize != 3 || n_vec < n_items) {
-            dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
-            hipLaunchKernelGGL((k_prep_same<true, T, FMA>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, taps, I, d_items,
+        if (taps.ksize != 3 || n_vec < n_items)
+            hipLaunchKernelGGL((k_prep_same<true, T, FMA>), per_pixel, block, 0, ctx->stream, nullptr, 0, 0, 0, 0, taps, I, d_items,
                                taps.ksize == 3 ? 0 : -1);
-        }
+    } else if (taps.ksize == 3 || taps.ksize == 5) {
+        nsof_with_int<3, 5>(taps.ksize, [&](auto ks) {
+            constexpr int KS = decltype(ks)::value;
+            if constexpr (KS != 4)
+                hipLaunchKernelGGL((k_prep_direct<KS, true, T, FMA>), per_pixel, block, 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1.,
+                                   1., taps, I, d_items);
+        });
+    } else if (lds.bytes <= (sizeof(T) == 2 ? 78 : 60) * 1024) {
+        int rc = launch_tiled<true, T, FMA>(ctx, tiled_grid(max_wk, max_hk, nz), lds, nullptr, 0, 0, 0, 0, 0, 0, 1., 1., taps, I,
+                                            d_items);
+        if (rc) return rc;
     } else {
-        const int r = taps.ksize / 2;
-        const int rw_cap = ((int)ceil(PREP_TW * max_sx) + 2 * r + 8 + 3) / 4 * 4;
-        const int rh_cap = (int)ceil(PREP_TH * max_sy) + 2 * r + 4;
-        const size_t smem = sizeof(float) * ((size_t)rh_cap * 2 * PREP_TW + 2 * PREP_TH * 2 * PREP_TW) +
-                            (size_t)rh_cap * rw_cap * sizeof(T);
-        if (taps.ksize == 3 || taps.ksize == 5) {
-            dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
-            nsof_with_int<3, 5>(taps.ksize, [&](auto ks) {
-                constexpr int KS = decltype(ks)::value;
-                if constexpr (KS != 4)
-                    hipLaunchKernelGGL((k_prep_direct<KS, true, T, FMA>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0,
-                                       1., 1., taps, I, d_items);
-            });
-        } else if (smem <= (sizeof(T) == 2 ? 78 : 60) * 1024) {
-            dim3 grid((max_wk + PREP_TW - 1) / PREP_TW, (max_hk + PREP_TH - 1) / PREP_TH, nz);
-            int rc = NSOF_OK;
-            nsof_with_int<0, 19>(tiled_ks(taps.ksize), [&](auto ks) {
-                constexpr int KS = decltype(ks)::value;
-                if constexpr (KS == tiled_ks(KS)) rc = launch_tiled_het<KS, T, FMA>(ctx, grid, smem, rw_cap, rh_cap, taps, I, d_items);
-            });
-            if (rc) return rc;
-        } else {
-            dim3 grid((max_wk + 63) / 64, (max_hk + 3) / 4, nz);
-            hipLaunchKernelGGL((k_prep_naive<true, T, FMA>), grid, dim3(256), 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1.,
-                               taps, I, d_items);
-        }
+        hipLaunchKernelGGL((k_prep_naive<true, T, FMA>), per_pixel, block, 0, ctx->stream, nullptr, 0, 0, 0, 0, 0, 0, 1., 1., taps, I,
+                           d_items);
     }
     NSOF_HIP(ctx, hipGetLastError());
     return NSOF_OK;
 }
 }  // namespace
 
-int nsof_launch_prep_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items, bool level0,
-                         const nsof_blur_taps& taps, float* I, int src_type)
+// f(nsof_px_tag<T>{}, std::bool_constant<FMA>{}) for a pixel type (nsof_src_type) and the context's arithmetic variant;
+// false, f not called, for an unknown type.
+namespace {
+template <class Fn>
+bool with_px_fma(const nsof_ctx* ctx, int src_type, Fn&& f)
+{
+    return nsof_with_src_type(src_type, [&](auto px_tag) { nsof_with_fma(ctx, [&](auto fma) { f(px_tag, fma); }); });
+}
+}  // namespace
+
+// f32 frames take the three one-level launches (k_prep_decim<.., float>): at 768 threads per workgroup a wave has 168
+// registers, and the float rows of the three walks side by side spilled (~400 registers' worth to scratch)
+int nsof_launch_prep_decim3(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H,
+                            const nsof_blur_taps* taps, float* const* out, int src_type)
+{
+    int rc = NSOF_EUNSUPPORTED;
+    with_px_fma(ctx, src_type, [&](auto px_tag, auto fma) {
+        using T = typename decltype(px_tag)::type;
+        if constexpr (kInt<T>)
+            rc = prep_decim3_impl<T, decltype(fma)::value>(ctx, n_img, static_cast<const T*>(src), row_stride, img_stride, W, H, taps,
+                                                           out);
+    });
+    return rc;
+}
+
+int nsof_launch_prep(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W, int H, int wk,
+                     int hk, const nsof_blur_taps& taps, float* out, int src_type)
 {
     int rc = NSOF_OK;
-    const bool known = nsof_with_src_type(src_type, [&](auto px_tag) {
+    const bool known = with_px_fma(ctx, src_type, [&](auto px_tag, auto fma) {
         using T = typename decltype(px_tag)::type;
-        rc = ctx->opt_pyr_fma ? prep_het_impl<T, true>(ctx, n_items, d_items, h_items, level0, taps, I)
-                              : prep_het_impl<T, false>(ctx, n_items, d_items, h_items, level0, taps, I);
+        rc = prep_impl<T, decltype(fma)::value>(ctx, n_img, static_cast<const T*>(src), row_stride, img_stride, W, H, wk, hk, taps,
+                                                out);
     });
     return known ? rc : nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", src_type);
 }
 
-int nsof_launch_flow_upsample_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, int max_h,
-                                  const float* src, float* dst, float mul)
+int nsof_launch_prep_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, const nsof_het_item* h_items, bool level0,
+                         const nsof_blur_taps& taps, float* I, int src_type)
 {
-    nsof_prof_scope ps(ctx, NSOF_K_UPSAMPLE);
-    dim3 g2(((max_w + 1) / 2 + 63) / 64, ((max_h + 1) / 2 + 3) / 4, n_items);
-    auto kern = ctx->opt_pyr_fma ? k_flow_upsample2x2<true, true> : k_flow_upsample2x2<true, false>;
-    hipLaunchKernelGGL(kern, g2, dim3(256), 0, ctx->stream, src, 0, 0, dst, 0, 0, 1., 1., mul, d_items);
-    NSOF_HIP(ctx, hipGetLastError());
-    return NSOF_OK;
+    int rc = NSOF_OK;
+    const bool known = with_px_fma(ctx, src_type, [&](auto px_tag, auto fma) {
+        using T = typename decltype(px_tag)::type;
+        rc = prep_het_impl<T, decltype(fma)::value>(ctx, n_items, d_items, h_items, level0, taps, I);
+    });
+    return known ? rc : nsof_set_error(ctx, NSOF_EINVAL, "unknown pixel type %d", src_type);
 }

@@ -140,7 +140,7 @@ struct FlowSrc {
 };
 
 // FlowResample2x: the flow of the COARSER level, pw x ph with W == 2 * pw and H == 2 * ph, resampled on the fly: for fine
-// pixel (x, y) exactly what k_flow_upsample (farneback_pyramid.hip) writes and FlowSrc then reads,
+// pixel (x, y) exactly what k_flow_upsample (farneback_resample.hip) writes and FlowSrc then reads,
 //     t0 = p00*a0 + p01*a1;  t1 = p10*a0 + p11*a1;  o = (t0*b0 + t1*b1) * mul        (every a*b + c two roundings),
 // with the coordinates, weights and clamps of lin_coord_x / lin_coord_y at scale 0.5.  The column pair and a0, a1 belong to
 // the thread (column()).  Rows: at scale 0.5 the coordinate of row 2k + p is f = k + (p + 0.5) * 0.5 - 0.5, exact in double

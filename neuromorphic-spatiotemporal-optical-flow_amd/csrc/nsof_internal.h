@@ -205,7 +205,7 @@ struct nsof_fb_frames {
 int nsof_farneback_core(nsof_ctx* ctx, const nsof_fb_frames& frames, float* d_flow, const nsof_fb_params& params);
 void nsof_pipe_destroy(nsof_ctx* ctx);
 
-// ---- Farneback launchers (farneback_pyramid.hip, farneback_polyexp.hip, farneback_blur.hip) ----
+// ---- Farneback launchers (farneback_pyramid.hip, farneback_resample.hip, farneback_polyexp.hip, farneback_blur.hip) ----
 struct nsof_blur_taps {
     int ksize;
     float k[NSOF_MAX_BLUR_TAPS];
@@ -286,7 +286,8 @@ int nsof_launch_flow_upsample_het(nsof_ctx* ctx, int n_items, const nsof_het_ite
 // final: the flow goes to the items' own output fields (out / out_pitch) instead of flow_out.
 int nsof_launch_iterate_het(nsof_ctx* ctx, int n_items, const nsof_het_item* d_items, int max_w, const float* R,
                             const float* flow_in, float* flow_out, bool final, int winsize);
-// The pyramid-level and flow-resample launchers (farneback_pyramid.hip) take the arithmetic variant from ctx->opt_pyr_fma.
+// The pyramid-level and flow-resample launchers (farneback_pyramid.hip, farneback_resample.hip) take the arithmetic
+// variant from ctx->opt_pyr_fma.
 // src: n_img frames of pixel type src_type (nsof_src_type), row / image strides in bytes.
 int nsof_launch_prep(nsof_ctx* ctx, int n_img, const void* src, ptrdiff_t row_stride, ptrdiff_t img_stride, int W,
                      int H, int wk, int hk, const nsof_blur_taps& taps, float* out, int src_type);
@@ -442,7 +443,7 @@ __device__ __forceinline__ int floor_f(float v)
     return i - (i > v);
 }
 // resize(INTER_LINEAR) coordinate: f = (float)((d+0.5)*scale-0.5); s = floor(f); a = f-s.  The pyramid levels, the flow
-// resample (farneback_pyramid.hip) and the resampling flow source of the exact iteration (iterate_common.h).
+// resample (farneback_pyramid.hip, farneback_resample.hip) and the resampling flow source of the exact iteration (iterate_common.h).
 __device__ __forceinline__ void lin_coord_x(int d, double scale, int slen, int& s, float& a)
 {
     float f = (float)((d + 0.5) * scale - 0.5);
@@ -456,6 +457,44 @@ __device__ __forceinline__ void lin_coord_y(int d, double scale, int& s, float& 
     float f = (float)((d + 0.5) * scale - 0.5);
     s = floor_f(f);
     a = f - s;
+}
+// One axis of a bilinear sample as resize takes it: the two source indices and the weight of the second (the first
+// gets 1 - w1).  x: the index pair stops at the last column; y: both indices are clamped into the image.
+struct LinTap {
+    int i0, i1;
+    float w1;
+};
+__device__ __forceinline__ LinTap lin_tap_x(int d, double scale, int len)
+{
+    LinTap t;
+    lin_coord_x(d, scale, len, t.i0, t.w1);
+    t.i1 = min(t.i0 + 1, len - 1);
+    return t;
+}
+__device__ __forceinline__ LinTap lin_tap_y(int d, double scale, int len)
+{
+    LinTap t;
+    int s;
+    lin_coord_y(d, scale, s, t.w1);
+    t.i0 = clampi(s, 0, len - 1);
+    t.i1 = clampi(s + 1, 0, len - 1);
+    return t;
+}
+// resize's blend of two samples, p * (1 - w1) + q * w1 in that order, and of 2x2: horizontal first, then vertical.
+template <bool FMA>
+__device__ __forceinline__ float lin_mix(float p, float q, float w1)
+{
+    return nsof_madd<FMA>(p, 1.f - w1, q * w1);
+}
+template <bool FMA>
+__device__ __forceinline__ float2 lin_mix(float2 p, float2 q, float w1)
+{
+    return make_float2(lin_mix<FMA>(p.x, q.x, w1), lin_mix<FMA>(p.y, q.y, w1));
+}
+template <bool FMA, typename V>
+__device__ __forceinline__ V lin_blend(V p00, V p01, V p10, V p11, float a1, float b1)
+{
+    return lin_mix<FMA>(lin_mix<FMA>(p00, p01, a1), lin_mix<FMA>(p10, p11, a1), b1);
 }
 
 // cv2's fixed-point cvtColor to gray of one interleaved 3-channel 8-bit pixel (c0, c1, c2): weights in units of 2^-15,
@@ -473,5 +512,31 @@ __device__ __forceinline__ void nsof_store_stream4(float* p, float a, float b, f
 __device__ __forceinline__ void nsof_store_stream2(float* p, float a, float b)
 {
     __builtin_nontemporal_store((nsof_f2v){a, b}, reinterpret_cast<nsof_f2v*>(p));
+}
+// N = 1, 2, 4 or 8 adjacent floats in the widest streamed stores (p aligned to min(N, 4) floats).
+template <int N>
+__device__ __forceinline__ void nsof_store_stream_n(float* p, const float (&o)[N])
+{
+    static_assert(N == 1 || N == 2 || N == 4 || N == 8, "1, 2, 4 or 8 floats");
+    if constexpr (N == 1) __builtin_nontemporal_store(o[0], p);
+    else if constexpr (N == 2) nsof_store_stream2(p, o[0], o[1]);
+    else {
+#pragma unroll
+        for (int i = 0; i < N; i += 4) nsof_store_stream4(p + i, o[i], o[i + 1], o[i + 2], o[i + 3]);
+    }
+}
+
+// ---- pyramid-level and flow-resample launchers (farneback_pyramid.hip, farneback_resample.hip) ----------------------
+// resize's source step per destination pixel, on the host and for a work item on the device: this double expression,
+// which the resample coordinates' bits depend on.
+__host__ __device__ inline double inv_scale(int dst, int src) { return 1. / ((double)dst / src); }
+// Grid of the kernels that give a 256-thread block 64 x 4 outputs.
+static inline dim3 nsof_pixel_grid(int w, int h, int n) { return dim3((w + 63) / 64, (h + 3) / 4, n); }
+// f(std::bool_constant<FMA>{}) for the arithmetic variant of the context (NSOF_OPT_PYR_FMA).
+template <class Fn>
+void nsof_with_fma(const nsof_ctx* ctx, Fn&& f)
+{
+    if (ctx->opt_pyr_fma) f(std::true_type{});
+    else f(std::false_type{});
 }
 #endif

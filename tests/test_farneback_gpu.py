@@ -90,6 +90,58 @@ def test_pyr_level_bit_exact(ctx, oracle, torch_dev, frames, pyr_scale, level, s
     assert np.array_equal(got[1], oracle.pyr_level(frames[shape][1], pyr_scale, level))
 
 
+# Images shorter than the blur window: the routes whose window loads reflect more than once, and the uniform (not
+# work-list) k_prep_direct, which the launcher takes only when H / hk >= ksize.  (H, W), pyr_scale, level, then what
+# nsof_farneback_level_size must give for it -- (wk, hk, taps) -- so that a case keeps reaching the route it names.
+SHORT_CASES = [((3, 40), 0.42, 1, (17, 1, 3)),      # uniform k_prep_direct<3>
+               ((3, 40), 0.45, 1, (18, 1, 3)),      # uniform k_prep_direct<3>
+               ((3, 40), 0.5, 2, (10, 1, 9)),       # k_prep_walk<9>, H < KS
+               ((5, 40), 0.35, 1, (14, 2, 5)),      # k_prep_walk<5>, every wave a border wave
+               ((5, 40), 0.35, 2, (5, 1, 19)),      # k_prep_rows / k_prep_cols, window 19 on 5 rows
+               ((9, 130), 0.35, 2, (16, 1, 19)),    # rows / cols, wider than one wave
+               ((9, 130), 0.3, 1, (39, 3, 7))]      # k_prep_tiled<0> with run-time taps
+# dtype, nsof_pixel_type, factor on the 8-bit values: powers of two and a sign are exact in float32, so the oracle's
+# result times the factor is the expected level bit for bit -- and the 16-bit frames fill their types' upper bytes
+# (uint16 up to 65280, int16 down to -32640), which a wrong zero- or sign-extension of the packed loads would change
+SHORT_DTYPES = [("uint8", 0, 1), ("float32", 1, 1), ("uint16", 2, 256), ("int16", 3, -128)]
+
+
+@pytest.mark.parametrize("fma", [0, 1], ids=["plain", "fma"])
+@pytest.mark.parametrize("shape,pyr_scale,level,geom", SHORT_CASES)
+def test_pyr_level_short_images_bit_exact(nsof_lib, ctx, oracle, torch_dev, shape, pyr_scale, level, geom, fma):
+    """As test_pyr_level_bit_exact (two images per launch, the second with a padded pitch, the oracle's bits), through
+    nsof_stage_pyr_level_px for every pixel type and both arithmetic variants.  One oracle result serves all four types
+    (SHORT_DTYPES)."""
+    import torch
+    from nsof import _lib, synth
+    h, w = shape
+    assert nsof_lib.level_size(w, h, pyr_scale, level)[:3] == geom
+    wk, hk, _ = geom
+    imgs = synth.make_pair(100 + h + w, h, w)
+    pitch = w + 13   # pixels
+    try:
+        ctx.set_option(_lib.OPT_PYR_FMA, fma)
+        oracle.set_pyr_fma(bool(fma))
+        want = [oracle.pyr_level(img, pyr_scale, level) for img in imgs]
+        assert want[0].shape == (hk, wk)
+        for dtype, pt, factor in SHORT_DTYPES:
+            buf = np.zeros((2, h, pitch), dtype)
+            buf[0, :, :w] = imgs[0].astype(np.int32) * factor
+            buf[1, :, :w] = imgs[1].astype(np.int32) * factor
+            d = _dev(torch_dev, buf)
+            out = torch.full((2, hk, wk), -1.0, dtype=torch.float32, device=torch_dev)
+            ctx.check(ctx._lib.nsof_stage_pyr_level_px(ctx.ptr, pt, 2, d.data_ptr(), pitch * buf.itemsize,
+                                                       h * pitch * buf.itemsize, w, h, pyr_scale, level, out.data_ptr()))
+            ctx.synchronize()
+            got = out.cpu().numpy()
+            for i in range(2):
+                exp = want[i] * np.float32(factor)
+                assert np.array_equal(got[i], exp), (dtype, i, float(np.abs(got[i] - exp).max()))
+    finally:
+        ctx.set_option(_lib.OPT_PYR_FMA, 0)
+        oracle.set_pyr_fma(False)
+
+
 @pytest.mark.parametrize("level", [1, 2, 3])
 @pytest.mark.parametrize("shape", [(272, 480), (24, 16), (184, 1040), (1080, 1920), (1920, 1080), (200, 72),
                                    (96, 64)])
