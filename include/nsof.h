@@ -123,7 +123,9 @@ int nsof_get_option(const nsof_ctx* ctx, int option, int* value);
  * start at any element are fine (the pyramid kernels take their vector loads where rows are aligned for them -- 16 bytes
  * for float frames -- and scalar loads elsewhere; the result does not depend on it).  The lone host pair takes ANY row
  * stride for 8-bit frames (its rows are copied) and the stage entry leaves an 8-bit row stride unchecked.  Otherwise a
- * violation, or an unknown pixel type, returns NSOF_EINVAL before anything is launched. */
+ * violation, or an unknown pixel type, returns NSOF_EINVAL before anything is launched.  An entry writes no byte outside
+ * the logical elements of its outputs, and its results do not depend on memory outside the logical elements of its inputs
+ * (row padding, the space between images, whatever lies before and after a buffer: tests/test_bounds_*_gpu.py). */
 /* flags, cv2's values.  0: the box window (FarnebackUpdateFlow_Blur).  NSOF_FARNEBACK_GAUSSIAN (256): every iteration
  * weights its window with a separable Gaussian of sigma 0.3 * (winsize / 2) (FarnebackUpdateFlow_GaussianBlur); winsize 2m
  * and 2m + 1 then give the same flow, winsize up to 193.  Such a call runs k_update_matrices + k_gauss_blur_solve per
