@@ -13,9 +13,10 @@
 //                 Pixels outside the image never take part (cv2's default border for morphology), which is the
 //                 `inside` mask applied after every pass.  The bit image is 1/64 of the flow's size, so the halo
 //                 re-reads are free and the head as a whole stays bound by the one read of the flow.
-//   k_mag_pack_jobs / k_morph_jobs / k_mask_compose   the head over the boxes of a whole sequence: the two kernels
-//                 above applied per box (each box its own image) from host-built job lists, then one pass over every
-//                 canvas pixel that takes the bit of the last box covering it (the paste order of the reference).
+//   k_mag_pack_jobs / k_morph_jobs / k_mask_compose   the head over the boxes of a whole sequence: the bodies of the
+//                 two kernels above (mag_pack_rows, morph_tile) applied per box (each box its own image) from
+//                 host-built job lists, then one pass over every canvas pixel that takes the bit of the last box
+//                 covering it (the paste order of the reference).
 //   k_pa_partial / k_pa_final   pixel accuracy of a batch of masks against thresholded gray ground-truth frames,
 //                 counted in integers.
 #include <algorithm>
@@ -44,15 +45,38 @@ struct MorphElem {
     int n_patterns, kw, kh, ax, ay;
 };
 
+// One wave packs pixels k64 * 64 .. k64 * 64 + 63 of rows 8 by .. 8 by + 7: `mag > thresh` -> one ballot per row.
+// The pointers are not __restrict__ here (the kernels' own parameters are): with the qualifier repeated on the inlined
+// copy, k_mag_pack_jobs' loop recomputes its store addresses per row and the pack stage of a sequence measured 1-2 %
+// slower; without it both kernels keep the loop, registers and instruction count they had with the body written out.
+__device__ __forceinline__ void mag_pack_rows(const float* flow, ptrdiff_t fstride, int w, int h, double thresh,
+                                              uint32_t* bits, int wp, int k64, int lane, int by)
+{
+    const int x = k64 * 64 + lane;
+    const int y0 = by * 8;
+    float2 v[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int y = y0 + r;
+        v[r] = (x < w && y < h) ? *(const float2*)(flow + (ptrdiff_t)y * fstride + 2 * x) : make_float2(0.f, 0.f);
+    }
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int y = y0 + r;
+        const double a = v[r].x, b = v[r].y;
+        const bool set = x < w && y < h && sqrt(a * a + b * b) > thresh;   // cartToPolar on float64, then `mag > th`
+        const unsigned long long m = __ballot(set);
+        if (lane == 0 && y < h) *(unsigned long long*)(bits + (size_t)y * wp + 2 * k64) = m;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_mag_pack(const float* __restrict__ flow, ptrdiff_t fstride, int w, int h,
                                                   double thresh, uint32_t* __restrict__ bits, int wp)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int k64 = blockIdx.x * 4 + wave;   // 64-pixel group of the row
     if (k64 * 2 >= wp) return;
-#define PACK_BY blockIdx.y
-#include "segment_mag_pack.inc"
-#undef PACK_BY
+    mag_pack_rows(flow, fstride, w, h, thresh, bits, wp, k64, lane, blockIdx.y);
 }
 
 __global__ __launch_bounds__(256) void k_u8_pack(const uint8_t* __restrict__ src, ptrdiff_t sstride, int w, int h,
@@ -129,19 +153,88 @@ constexpr MorphElem ellipse10()
     return e;
 }
 
-// ops: bit p = 1 -> pass p is a dilate, 0 -> erode.  Output: out_u8 (0/255) when non-null, else out_bits.
-// FIXED10: ignore el_arg and use ellipse10().
+// One output tile (bx, by) of a chain launch; the whole workgroup runs it.  ops: bit p = 1 -> pass p is a dilate,
+// 0 -> erode.  Output: out_u8 (0/255) when non-null, else out_bits.  FIXED10: ignore el_arg and use ellipse10().
+template <bool FIXED10>
+__device__ __forceinline__ void morph_tile(const uint32_t* __restrict__ in_bits, int wp, int w, int h,
+                                           const MorphElem& el_arg, int n_pass, unsigned ops, int top, int rows,
+                                           uint32_t* __restrict__ out_bits, uint8_t* __restrict__ out_u8,
+                                           ptrdiff_t ostride, int bx, int by)
+{
+    constexpr MorphElem fixed = ellipse10();
+    const MorphElem& el = FIXED10 ? fixed : el_arg;
+    extern __shared__ uint32_t lds[];
+    uint32_t* cur = lds;                       // [rows][TW]
+    uint32_t* H = lds + (size_t)rows * TW;     // [n_patterns][rows][TW]
+    const int tid = threadIdx.x;
+    const int gk0 = bx * TILE_WORDS - HALO_WORDS;
+    const int gy0 = by * TILE_H - top;
+    const int n = rows * TW;
+    const int k = tid & (TW - 1);              // 1024 % TW == 0: a thread keeps its word column
+    const int gk = gk0 + k;
+
+    for (int i = tid; i < n; i += MORPH_THREADS) {
+        const int gy = gy0 + (i >> 4);
+        cur[i] = (gy >= 0 && gy < h && gk >= 0 && gk < wp) ? in_bits[(size_t)gy * wp + gk] : 0u;
+    }
+    __syncthreads();
+
+    for (int p = 0; p < n_pass; p++) {
+        const bool dil = (ops >> p) & 1u;
+        // H step: per distinct row pattern, OR of the funnel-shifted words (one v_alignbit per element column)
+        for (int i = tid; i < n; i += MORPH_THREADS) {
+            const int gy = gy0 + (i >> 4);
+            uint32_t lo = k > 0 ? cur[i - 1] : 0u, mid = cur[i], hi = k + 1 < TW ? cur[i + 1] : 0u;
+            if (!dil) {   // complement inside the image; outside stays 0 (= "does not take part" in a minimum)
+                lo = k > 0 ? ~lo & inside_bits(gy, gk - 1, w, h) : 0u;
+                mid = ~mid & inside_bits(gy, gk, w, h);
+                hi = k + 1 < TW ? ~hi & inside_bits(gy, gk + 1, w, h) : 0u;
+            }
+            h_patterns<0>(el, H, n, i, lo, mid, hi);
+        }
+        __syncthreads();
+        // V step: OR over the element rows of the matching H array
+        for (int i = tid; i < n; i += MORPH_THREADS) {
+            const int r = i >> 4;
+            const uint32_t acc = v_rows<0>(el, H, n, r, k, rows);
+            cur[i] = (dil ? acc : ~acc) & inside_bits(gy0 + r, gk, w, h);
+        }
+        __syncthreads();
+    }
+
+    // write the tile's own rows/words
+    if (out_u8) {
+        for (int i = tid; i < TILE_H * TILE_WORDS * 8; i += MORPH_THREADS) {   // 4 pixels per item
+            const int r = i / (TILE_WORDS * 8), q = i - r * (TILE_WORDS * 8);
+            const int gy = by * TILE_H + r, gx = bx * TILE_WORDS * 32 + q * 4;
+            if (gy >= h || gx >= w) continue;
+            const uint32_t word = cur[(r + top) * TW + HALO_WORDS + (q >> 3)];
+            const uint32_t nib = (word >> ((q & 7) * 4)) & 0xfu;
+            uint8_t* o = out_u8 + (ptrdiff_t)gy * ostride + gx;
+            if (gx + 4 <= w && (((uintptr_t)o) & 3) == 0) {
+                *(uint32_t*)o = ((nib & 1u) ? 0xffu : 0u) | ((nib & 2u) ? 0xff00u : 0u) | ((nib & 4u) ? 0xff0000u : 0u) |
+                                ((nib & 8u) ? 0xff000000u : 0u);
+            } else {
+                for (int b = 0; b < 4 && gx + b < w; b++) o[b] = (nib >> b) & 1u ? 255 : 0;
+            }
+        }
+    } else {
+        for (int i = tid; i < TILE_H * TILE_WORDS; i += MORPH_THREADS) {
+            const int r = i / TILE_WORDS, kk = i - r * TILE_WORDS;
+            const int gy = by * TILE_H + r, gk = bx * TILE_WORDS + kk;
+            if (gy < h && gk < wp) out_bits[(size_t)gy * wp + gk] = cur[(r + top) * TW + HALO_WORDS + kk];
+        }
+    }
+}
+
 template <bool FIXED10>
 __global__ __launch_bounds__(MORPH_THREADS) void k_morph_bits(const uint32_t* __restrict__ in_bits, int wp, int w,
                                                               int h, const MorphElem el_arg, int n_pass, unsigned ops,
                                                               int top, int rows, uint32_t* __restrict__ out_bits,
                                                               uint8_t* __restrict__ out_u8, ptrdiff_t ostride)
 {
-#define TILE_BX blockIdx.x
-#define TILE_BY blockIdx.y
-#include "segment_morph_tile.inc"
-#undef TILE_BX
-#undef TILE_BY
+    morph_tile<FIXED10>(in_bits, wp, w, h, el_arg, n_pass, ops, top, rows, out_bits, out_u8, ostride, blockIdx.x,
+                        blockIdx.y);
 }
 
 // ---- the head over the boxes of a whole sequence (nsof_motion_mask_sequence_dev) --------------------------------
@@ -166,14 +259,8 @@ __global__ __launch_bounds__(256) void k_mag_pack_jobs(const SegJob* __restrict_
     const SegBox box = boxes[j.box];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float* flow = flows + (((size_t)box.pair * H + box.y0) * W + box.x0) * 2;
-    const ptrdiff_t fstride = 2 * (ptrdiff_t)W;
-    const int w = box.w, h = box.h, wp = box.wp;
-    uint32_t* bits = ws + box.off;
-    for (int k64 = wave; k64 * 2 < wp; k64 += 4) {
-#define PACK_BY j.tile
-#include "segment_mag_pack.inc"
-#undef PACK_BY
-    }
+    for (int k64 = wave; k64 * 2 < box.wp; k64 += 4)
+        mag_pack_rows(flow, 2 * (ptrdiff_t)W, box.w, box.h, thresh, ws + box.off, box.wp, k64, lane, j.tile);
 }
 
 // Morph: one workgroup per (box, tile), the tile walk of k_morph_bits on the box's own image.  src_b: read B, write A.
@@ -185,19 +272,11 @@ __global__ __launch_bounds__(MORPH_THREADS) void k_morph_jobs(const SegJob* __re
 {
     const SegJob j = jobs[blockIdx.x];
     const SegBox box = boxes[j.box];
-    const int w = box.w, h = box.h, wp = box.wp;
-    const int tiles_x = (wp + TILE_WORDS - 1) / TILE_WORDS;
+    const int tiles_x = (box.wp + TILE_WORDS - 1) / TILE_WORDS;
     const int ty = j.tile / tiles_x, tx = j.tile - ty * tiles_x;
-    const size_t img = (size_t)wp * h;
-    const uint32_t* in_bits = ws + box.off + (src_b ? img : 0);
-    uint32_t* out_bits = ws + box.off + (src_b ? 0 : img);
-    uint8_t* const out_u8 = nullptr;
-    const ptrdiff_t ostride = 0;
-#define TILE_BX tx
-#define TILE_BY ty
-#include "segment_morph_tile.inc"
-#undef TILE_BX
-#undef TILE_BY
+    const size_t img = (size_t)box.wp * box.h;
+    morph_tile<FIXED10>(ws + box.off + (src_b ? img : 0), box.wp, box.w, box.h, el_arg, n_pass, ops, top, rows,
+                        ws + box.off + (src_b ? 0 : img), nullptr, 0, tx, ty);
 }
 
 // Compose: 4 canvas pixels per thread (256 x 4 per workgroup), blockIdx.z = pair.  A pixel takes the bit of the LAST
@@ -345,37 +424,48 @@ int plan_chunk(nsof_ctx* ctx, const MorphElem& el, int left, int* rows_out, size
     return chunk;
 }
 
-// Runs the chain `ops` (n_pass passes) on bits; result to out_u8.  scratch: second bit image for multi-chunk chains.
-int run_chain(nsof_ctx* ctx, uint32_t* bits, uint32_t* scratch, int w, int h, const MorphElem& el, int n_pass,
-              unsigned ops, uint8_t* out_u8, ptrdiff_t ostride)
+// The one place a chain is run: `ops` (n_pass passes) of element `el`, split into launches by plan_chunk, ping-pong
+// between bit images A and B starting from A.  kern_fixed / kern_any are the FIXED10 / run-time-element arms of the
+// kernel; launch(kern, smem, src_b, last, chunk, ops, top, rows) starts one chunk that reads B when src_b, else A, and
+// writes the other.  Returns which image holds the result (0 = A, 1 = B), or an nsof_status (< 0).
+template <class Kern, class Launch>
+int run_chain(nsof_ctx* ctx, const MorphElem& el, int n_pass, unsigned ops, Kern kern_fixed, Kern kern_any,
+              Launch launch)
 {
-    const int wp = words_per_row(w);
-    const int up = el.ay;
-    dim3 grid((wp + TILE_WORDS - 1) / TILE_WORDS, (h + TILE_H - 1) / TILE_H);
-    int done = 0;
-    uint32_t* src = bits;
-    uint32_t* dst = scratch;
-    do {
+    constexpr MorphElem e10 = ellipse10();
+    const Kern kern = memcmp(&el, &e10, sizeof(MorphElem)) == 0 ? kern_fixed : kern_any;
+    int src_b = 0;
+    for (int done = 0; done < n_pass; src_b ^= 1) {
         size_t smem;
         int rows;
         const int chunk = plan_chunk(ctx, el, n_pass - done, &rows, &smem);
         if (chunk < 0) return chunk;
-        const bool last = done + chunk >= n_pass;
-        constexpr MorphElem e10 = ellipse10();
-        const bool fixed10 = memcmp(&el, &e10, sizeof(MorphElem)) == 0;
-        auto kern = fixed10 ? k_morph_bits<true> : k_morph_bits<false>;
         if (smem > 64 * 1024)
             NSOF_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         {
             nsof_prof_scope ps(ctx, NSOF_K_MORPH);
-            hipLaunchKernelGGL(kern, grid, dim3(MORPH_THREADS), smem, ctx->stream, src, wp, w, h, el, chunk,
-                               ops >> done, chunk * up, rows, last ? nullptr : dst, last ? out_u8 : nullptr, ostride);
+            launch(kern, smem, src_b, done + chunk >= n_pass, chunk, ops >> done, chunk * el.ay, rows);
         }
         NSOF_HIP(ctx, hipGetLastError());
         done += chunk;
-        uint32_t* t = src; src = dst; dst = t;
-    } while (done < n_pass);
-    return NSOF_OK;
+    }
+    return src_b;
+}
+
+// The chain on one w x h image as a grid of tiles: a holds the input, b is the second bit image; the last chunk writes
+// out_u8 when it is non-null.
+int run_chain_image(nsof_ctx* ctx, uint32_t* a, uint32_t* b, int w, int h, const MorphElem& el, int n_pass,
+                    unsigned ops, uint8_t* out_u8, ptrdiff_t ostride)
+{
+    const int wp = words_per_row(w);
+    const dim3 grid((wp + TILE_WORDS - 1) / TILE_WORDS, (h + TILE_H - 1) / TILE_H);
+    uint32_t* const img[2] = {a, b};
+    return run_chain(ctx, el, n_pass, ops, k_morph_bits<true>, k_morph_bits<false>,
+                     [&](auto kern, size_t smem, int src_b, bool last, int chunk, unsigned chunk_ops, int top, int rows) {
+                         uint8_t* const u8 = last ? out_u8 : nullptr;
+                         hipLaunchKernelGGL(kern, grid, dim3(MORPH_THREADS), smem, ctx->stream, img[src_b], wp, w, h, el,
+                                            chunk, chunk_ops, top, rows, u8 ? nullptr : img[src_b ^ 1], u8, ostride);
+                     });
 }
 
 // The chain of the motion head: `iterations` x (dilate, erode) with the ksize x ksize ellipse; with no iterations a
@@ -383,21 +473,16 @@ int run_chain(nsof_ctx* ctx, uint32_t* bits, uint32_t* scratch, int w, int h, co
 int mask_chain(nsof_ctx* ctx, int ksize, int iterations, MorphElem* el, int* n_pass, unsigned* ops)
 {
     if (ksize < 1 || ksize > MAX_K) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "ksize 1..%d supported", MAX_K);
+    if (iterations == 0) ksize = 1;   // the 1x1 ellipse is the one set pixel
     uint8_t elem[MAX_K * MAX_K];
     nsof_structuring_element(NSOF_MORPH_ELLIPSE, ksize, ksize, elem);
-    int rc = build_elem(ctx, elem, ksize, ksize, -1, -1, el);
-    if (rc) return rc;
-    if (iterations == 0) {
-        uint8_t one = 1;
-        *n_pass = 1;
-        *ops = 1u;
-        return build_elem(ctx, &one, 1, 1, 0, 0, el);
-    }
-    *ops = 0;
-    for (int k = 0; k < iterations; k++) *ops |= 1u << (2 * k);   // even passes dilate, odd passes erode
-    *n_pass = 2 * iterations;
-    return NSOF_OK;
+    *ops = 1u;
+    for (int k = 1; k < iterations; k++) *ops |= 1u << (2 * k);   // even passes dilate, odd passes erode
+    *n_pass = iterations ? 2 * iterations : 1;
+    return build_elem(ctx, elem, ksize, ksize, -1, -1, el);
 }
+
+inline dim3 pack_grid(int wp, int h) { return dim3((wp / 2 + 3) / 4, (h + 7) / 8); }   // 4 waves x 64 px, 8 rows
 
 int reserve_bits(nsof_ctx* ctx, int w, int h, uint32_t** a, uint32_t** b)
 {
@@ -456,12 +541,13 @@ extern "C" int nsof_morph_binary_u8_dev(nsof_ctx* ctx, int op, const uint8_t* d_
     const int wp = words_per_row(width);
     {
         nsof_prof_scope ps(ctx, NSOF_K_SEGMENT);
-        hipLaunchKernelGGL(k_u8_pack, dim3((wp / 2 + 3) / 4, (height + 7) / 8), dim3(256), 0, ctx->stream, d_src,
-                           src_stride, width, height, a, wp);
+        hipLaunchKernelGGL(k_u8_pack, pack_grid(wp, height), dim3(256), 0, ctx->stream, d_src, src_stride, width,
+                           height, a, wp);
     }
     NSOF_HIP(ctx, hipGetLastError());
-    return run_chain(ctx, a, b, width, height, el, iterations, op == NSOF_MORPH_DILATE ? 0xffffffffu : 0u, d_dst,
-                     dst_stride);
+    rc = run_chain_image(ctx, a, b, width, height, el, iterations, op == NSOF_MORPH_DILATE ? 0xffffffffu : 0u, d_dst,
+                         dst_stride);
+    return rc < 0 ? rc : NSOF_OK;
 }
 
 extern "C" int nsof_motion_mask_dev(nsof_ctx* ctx, const float* d_flow, ptrdiff_t flow_stride_floats, int width,
@@ -485,11 +571,12 @@ extern "C" int nsof_motion_mask_dev(nsof_ctx* ctx, const float* d_flow, ptrdiff_
     const int wp = words_per_row(width);
     {
         nsof_prof_scope ps(ctx, NSOF_K_SEGMENT);
-        hipLaunchKernelGGL(k_mag_pack, dim3((wp / 2 + 3) / 4, (height + 7) / 8), dim3(256), 0, ctx->stream, d_flow,
-                           flow_stride_floats, width, height, thresh, a, wp);
+        hipLaunchKernelGGL(k_mag_pack, pack_grid(wp, height), dim3(256), 0, ctx->stream, d_flow, flow_stride_floats,
+                           width, height, thresh, a, wp);
     }
     NSOF_HIP(ctx, hipGetLastError());
-    return run_chain(ctx, a, b, width, height, el, n_pass, ops, d_mask, mask_stride);
+    rc = run_chain_image(ctx, a, b, width, height, el, n_pass, ops, d_mask, mask_stride);
+    return rc < 0 ? rc : NSOF_OK;
 }
 
 extern "C" int nsof_motion_mask(nsof_ctx* ctx, const float* flow, ptrdiff_t flow_stride_bytes, int width, int height,
@@ -600,27 +687,14 @@ extern "C" int nsof_motion_mask_sequence_dev(nsof_ctx* ctx, int n_pairs, const f
                                    ctx->stream, d_pack + i, d_boxes, d_flows, width, height, thresh, ws);
         }
         NSOF_HIP(ctx, hipGetLastError());
-        constexpr MorphElem e10 = ellipse10();
-        const bool fixed10 = memcmp(&el, &e10, sizeof(MorphElem)) == 0;
-        auto kern = fixed10 ? k_morph_jobs<true> : k_morph_jobs<false>;
-        for (int done = 0; done < n_pass;) {
-            size_t smem;
-            int rows;
-            const int chunk = plan_chunk(ctx, el, n_pass - done, &rows, &smem);
-            if (chunk < 0) return chunk;
-            if (smem > 64 * 1024)
-                NSOF_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            {
-                nsof_prof_scope ps(ctx, NSOF_K_MORPH);
-                for (size_t i = 0; i < morph.size(); i += MAX_JOBS)
-                    hipLaunchKernelGGL(kern, dim3((unsigned)std::min(MAX_JOBS, morph.size() - i)), dim3(MORPH_THREADS),
-                                       smem, ctx->stream, d_morph + i, d_boxes, ws, final_b, el, chunk, ops >> done,
-                                       chunk * el.ay, rows);
-            }
-            NSOF_HIP(ctx, hipGetLastError());
-            done += chunk;
-            final_b ^= 1;
-        }
+        final_b = run_chain(ctx, el, n_pass, ops, k_morph_jobs<true>, k_morph_jobs<false>,
+                            [&](auto kern, size_t smem, int src_b, bool, int chunk, unsigned chunk_ops, int top, int rows) {
+                                for (size_t i = 0; i < morph.size(); i += MAX_JOBS)
+                                    hipLaunchKernelGGL(kern, dim3((unsigned)std::min(MAX_JOBS, morph.size() - i)),
+                                                       dim3(MORPH_THREADS), smem, ctx->stream, d_morph + i, d_boxes, ws,
+                                                       src_b, el, chunk, chunk_ops, top, rows);
+                            });
+        if (final_b < 0) return final_b;
     }
     {
         nsof_prof_scope ps(ctx, NSOF_K_SEGMENT);

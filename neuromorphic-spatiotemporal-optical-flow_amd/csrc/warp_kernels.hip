@@ -257,6 +257,36 @@ int check_remap_args(nsof_ctx* ctx, int cn, int sw, int sh, ptrdiff_t sstride, i
     return NSOF_OK;
 }
 
+// SSIM of n pairs (item i at a + i * a_item, b + i * b_item): one tile grid of partials per pair in ctx->tmp, then one
+// k_ssim_final block per pair.  The n scores go to *d_out; when that is null, behind the partials, and *d_out is set.
+int ssim_launch(nsof_ctx* ctx, int n, const uint8_t* d_a, ptrdiff_t a_stride, ptrdiff_t a_item, int a_pixel_step,
+                const uint8_t* d_b, ptrdiff_t b_stride, ptrdiff_t b_item, int b_pixel_step, int width, int height,
+                double data_range, double** d_out)
+{
+    if (width < WIN || height < WIN)
+        return nsof_set_error(ctx, NSOF_ESHAPE, "ssim: win_size 7 exceeds the image extent %dx%d", width, height);
+    if (a_pixel_step < 1 || b_pixel_step < 1 || a_stride < (ptrdiff_t)width * a_pixel_step ||
+        b_stride < (ptrdiff_t)width * b_pixel_step || (n > 1 && (a_item < 0 || b_item < 0)))
+        return nsof_set_error(ctx, NSOF_EINVAL, "ssim: stride");
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    const int ow = width - 2 * PAD, oh = height - 2 * PAD;
+    const dim3 grid((ow + SX - 1) / SX, (oh + SY - 1) / SY, n);
+    const int nblk = grid.x * grid.y;   // the same tile grid and reduction order per pair for every n
+    int rc = ctx->tmp.reserve(ctx, ((size_t)n * nblk + (*d_out ? 0 : n)) * sizeof(double));
+    if (rc) return rc;
+    double* partial = (double*)ctx->tmp.p;
+    if (!*d_out) *d_out = partial + (size_t)n * nblk;
+    const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
+    {
+        nsof_prof_scope ps(ctx, NSOF_K_SSIM);
+        hipLaunchKernelGGL(k_ssim_partial, grid, dim3(256), 0, ctx->stream, d_a, a_stride, a_pixel_step, a_item, d_b,
+                           b_stride, b_pixel_step, b_item, width, height, c1, c2, partial);
+    }
+    hipLaunchKernelGGL(k_ssim_final, dim3(n), dim3(256), 0, ctx->stream, partial, nblk, (double)ow * (double)oh, *d_out);
+    NSOF_HIP(ctx, hipGetLastError());
+    return NSOF_OK;
+}
+
 }  // namespace
 
 // cv2.cvtColor(frame, COLOR_RGB2GRAY / COLOR_BGR2GRAY) for 8-bit frames: (c0*w0 + c1*w1 + c2*w2 + 2^14) >> 15 with the
@@ -391,28 +421,11 @@ extern "C" int nsof_ssim_u8_dev(nsof_ctx* ctx, const uint8_t* d_a, ptrdiff_t a_s
 {
     if (!ctx) return NSOF_EINVAL;
     if (!d_a || !d_b || !ssim_out) return nsof_set_error(ctx, NSOF_EINVAL, "null pointer");
-    if (width < WIN || height < WIN)
-        return nsof_set_error(ctx, NSOF_ESHAPE, "ssim: win_size 7 exceeds the image extent %dx%d", width, height);
-    if (a_pixel_step < 1 || b_pixel_step < 1 || a_stride < (ptrdiff_t)width * a_pixel_step ||
-        b_stride < (ptrdiff_t)width * b_pixel_step)
-        return nsof_set_error(ctx, NSOF_EINVAL, "ssim: stride");
-    NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    const int ow = width - 2 * PAD, oh = height - 2 * PAD;
-    dim3 grid((ow + SX - 1) / SX, (oh + SY - 1) / SY);
-    const int nblk = grid.x * grid.y;
-    int rc = ctx->tmp.reserve(ctx, ((size_t)nblk + 1) * sizeof(double));
+    double* score = nullptr;
+    int rc = ssim_launch(ctx, 1, d_a, a_stride, 0, a_pixel_step, d_b, b_stride, 0, b_pixel_step, width, height, data_range,
+                         &score);
     if (rc) return rc;
-    double* partial = (double*)ctx->tmp.p;
-    const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
-    {
-        nsof_prof_scope ps(ctx, NSOF_K_SSIM);
-        hipLaunchKernelGGL(k_ssim_partial, grid, dim3(256), 0, ctx->stream, d_a, a_stride, a_pixel_step, (ptrdiff_t)0,
-                           d_b, b_stride, b_pixel_step, (ptrdiff_t)0, width, height, c1, c2, partial);
-    }
-    hipLaunchKernelGGL(k_ssim_final, dim3(1), dim3(256), 0, ctx->stream, partial, nblk, (double)ow * (double)oh,
-                       partial + nblk);
-    NSOF_HIP(ctx, hipGetLastError());
-    NSOF_HIP(ctx, hipMemcpyAsync(ssim_out, partial + nblk, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    NSOF_HIP(ctx, hipMemcpyAsync(ssim_out, score, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (int rcs = nsof_stream_sync_checked(ctx)) return rcs;   // incl. a lost hand-over of the exact-order flow kernels
     return NSOF_OK;
 }
@@ -492,25 +505,6 @@ extern "C" int nsof_ssim_u8_batch_dev(nsof_ctx* ctx, int n, const uint8_t* d_a, 
     if (!d_a || !d_b || !d_out) return nsof_set_error(ctx, NSOF_EINVAL, "null pointer");
     if (n < 1) return nsof_set_error(ctx, NSOF_ESHAPE, "ssim_batch: n %d < 1", n);
     if (n > 65535) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "ssim_batch: more than 65535 pairs");
-    if (width < WIN || height < WIN)
-        return nsof_set_error(ctx, NSOF_ESHAPE, "ssim: win_size 7 exceeds the image extent %dx%d", width, height);
-    if (a_pixel_step < 1 || b_pixel_step < 1 || a_stride < (ptrdiff_t)width * a_pixel_step ||
-        b_stride < (ptrdiff_t)width * b_pixel_step || (n > 1 && (a_item_stride < 0 || b_item_stride < 0)))
-        return nsof_set_error(ctx, NSOF_EINVAL, "ssim: stride");
-    NSOF_HIP(ctx, hipSetDevice(ctx->device));
-    const int ow = width - 2 * PAD, oh = height - 2 * PAD;
-    const dim3 grid((ow + SX - 1) / SX, (oh + SY - 1) / SY, n);
-    const int nblk = grid.x * grid.y;   // same tile grid and reduction order per pair as nsof_ssim_u8_dev
-    int rc = ctx->tmp.reserve(ctx, (size_t)n * nblk * sizeof(double));
-    if (rc) return rc;
-    double* partial = (double*)ctx->tmp.p;
-    const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
-    {
-        nsof_prof_scope ps(ctx, NSOF_K_SSIM);
-        hipLaunchKernelGGL(k_ssim_partial, grid, dim3(256), 0, ctx->stream, d_a, a_stride, a_pixel_step, a_item_stride,
-                           d_b, b_stride, b_pixel_step, b_item_stride, width, height, c1, c2, partial);
-    }
-    hipLaunchKernelGGL(k_ssim_final, dim3(n), dim3(256), 0, ctx->stream, partial, nblk, (double)ow * (double)oh, d_out);
-    NSOF_HIP(ctx, hipGetLastError());
-    return NSOF_OK;
+    return ssim_launch(ctx, n, d_a, a_stride, a_item_stride, a_pixel_step, d_b, b_stride, b_item_stride, b_pixel_step,
+                       width, height, data_range, &d_out);
 }

@@ -1,6 +1,6 @@
 """GPU: the heads that consume a flow on the device -- the colour coding (csrc/flowviz_kernels.hip), the prediction warp
-(csrc/warp_kernels.hip: remap, fused warp, sequence warp) and the motion mask (csrc/segment_mag_pack.inc in both of its
-kernels) -- on flows that are partly NaN, infinite, beyond float32's square range, subnormal or -0.0: the hand-made
+(csrc/warp_kernels.hip: remap, fused warp, sequence warp) and the motion mask (mag_pack_rows of csrc/segment_kernels.hip in both
+of its kernels) -- on flows that are partly NaN, infinite, beyond float32's square range, subnormal or -0.0: the hand-made
 fields of tests/heads_nonfinite_cases.py, and a float-frame Farneback flow that is NaN on most of its pixels.
 
 Every comparison is exact (``np.array_equal`` on uint8 output, bit equality on the float32 divisors) against a CPU

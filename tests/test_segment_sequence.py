@@ -198,6 +198,86 @@ def test_mask_sequence_many_overlapping_boxes_and_long_reach(nsof_lib, ctx, orac
     assert np.array_equal(got.cpu().numpy(), _per_box_oracle(oracle, fl, bx, ksize=31, iterations=3))
 
 
+def _sparse_flows(torch_dev, seed, n, h, w, scale):
+    """Flows whose mask a closing neither empties nor fills: speckle of ``scale`` (rarely above 1), a block four times
+    as strong that straddles 1, and a lattice of vectors of magnitude exactly 1 (which `mag > 1` leaves unset)."""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    f = torch.randn((n, h, w, 2), generator=g) * scale
+    f[:, h // 4:h // 2, w // 5:w // 2] *= 4.0
+    f[:, ::7, ::5] = torch.tensor([1.0, 0.0])
+    f[:, 3::7, 2::5] = torch.tensor([0.0, -1.0])
+    return f.to(torch_dev)
+
+
+def _check_both_entries(nsof_lib, ctx, oracle, flows, boxes, **kw):
+    """The sequence entry against the single-image entry and the oracle, both applied box by box."""
+    from nsof import segment
+    got = segment.motion_mask_sequence_dev(flows, boxes, ctx=ctx, **kw)
+    ctx.synchronize()
+    got = got.cpu().numpy()
+    assert np.array_equal(got, _per_box(nsof_lib, ctx, flows, boxes, **kw))
+    assert np.array_equal(got, _per_box_oracle(oracle, flows.cpu().numpy(), boxes, **kw))
+    return got
+
+
+@pytest.mark.gpu
+def test_fixed_element_chain_of_two_launches_across_tiles(nsof_lib, ctx, oracle, torch_dev):
+    """ksize 10, iterations 7: 14 passes of reach 5, while the 64-pixel halo holds 12, so plan_chunk gives launches of
+    12 and 2 passes; 70 x 400 px is 3 tile rows of 32 and 2 tiles of 384 px.  cv2 does not reflect the even-sized
+    element, so the sixth and seventh iteration differ (the oracle shows it) and reading the wrong bit image would too."""
+    h, w = 70, 400
+    flows = _sparse_flows(torch_dev, 11, 3, h, w, 0.35)
+    boxes = [[(0, 0, w, h)], [(0, 0, w, h)], [(3, 2, 397, 66), (150, 20, 391, 70)]]   # x1 = 397, 391: inside a word
+    got = _check_both_entries(nsof_lib, ctx, oracle, flows, boxes, ksize=10, iterations=7)
+    assert all(0 < (m != 0).sum() < m.size for m in got[:2])
+    whole = _check_both_entries(nsof_lib, ctx, oracle, flows[:1], None, ksize=10, iterations=7)
+    assert np.array_equal(whole[0], got[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hw", [(37, 53), (40, 450)])
+def test_run_time_element_on_both_entries(nsof_lib, ctx, oracle, torch_dev, hw):
+    """ksize 9 is not the fixed 10 x 10 ellipse: the arm that reads the element from the kernel argument."""
+    h, w = hw
+    flows = _sparse_flows(torch_dev, 12, 2, h, w, 0.35)
+    got = _check_both_entries(nsof_lib, ctx, oracle, flows, [[(0, 0, w, h)], [(1, 2, w - 3, h - 1), (w // 3, 0, w, h // 2)]],
+                              ksize=9, iterations=2)
+    assert 0 < (got[0] != 0).sum() < got[0].size
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ksize,iterations", [(31, 1), (31, 2), (31, 3), (31, 4), (15, 5)])
+def test_job_list_chain_result_buffer_parity(nsof_lib, ctx, oracle, torch_dev, ksize, iterations):
+    """k_mask_compose must read the bit image the chain's last launch wrote.
+    ksize 31 (reach 15, 10 distinct rows): plan_chunk allows min(64 / 15, passes left) = up to 4 passes per launch
+    (tile of 32 + 4 * 30 = 152 rows, 11 * 152 * 64 B = 107008 B of LDS, above the 64 KB default and below the 144 KB
+    budget), so iterations 1, 2, 3, 4 (2, 4, 6, 8 passes) take 1, 1, 2, 2 launches and leave the result in bit image
+    B, B, A, A.  An odd-sized ellipse is symmetric, so its (dilate, erode) is a closing and idempotent: after the first
+    launch of iterations 3 and 4 (4 passes, two whole iterations) the other image already holds the final bits.  Hence
+    ksize 15, iterations 5 as well: reach 7 allows 64 / 7 = 9 of the 10 passes (158 rows, 6 * 158 * 64 B = 60672 B),
+    so the launches are 9 + 1, the result is in A and B holds the state after a dilate."""
+    h, w = 60, 200
+    flows = _sparse_flows(torch_dev, 13, 2, h, w, 0.25)
+    boxes = [[(0, 0, 150, 50), (40, 10, 197, 60)], [(0, 0, w, h)]]
+    got = _check_both_entries(nsof_lib, ctx, oracle, flows, boxes, ksize=ksize, iterations=iterations)
+    assert 0 < (got[1] != 0).sum() < got[1].size
+
+
+@pytest.mark.gpu
+def test_identity_pass_on_both_entries(nsof_lib, ctx, oracle, torch_dev):
+    """iterations 0: one pass with the 1 x 1 element, on a 1 x 1 box and a 33 x 65 box."""
+    h, w = 40, 70
+    flows = _sparse_flows(torch_dev, 14, 2, h, w, 0.8)
+    flows[0, 7, 5] = flows.new_tensor([3.0, 0.0])                  # the 1 x 1 box holds a set pixel
+    boxes = [[(5, 7, 6, 8)], [(2, 4, 67, 37)]]
+    got = _check_both_entries(nsof_lib, ctx, oracle, flows, boxes, iterations=0)
+    assert got[0].sum() == 255 and got[0, 7, 5] == 255
+    assert 0 < (got[1, 4:37, 2:67] != 0).sum() < 33 * 65
+    mag = np.hypot(*np.moveaxis(flows[1].cpu().numpy().astype(np.float64), -1, 0))
+    assert np.array_equal(got[1, 4:37, 2:67] != 0, mag[4:37, 2:67] > 1)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("hw", [(1080, 1920), (1920, 1080)])
 def test_mask_sequence_whole_frame(nsof_lib, ctx, oracle, torch_dev, hw):
