@@ -508,6 +508,25 @@ int nsof_accum_step_events(nsof_accum* acc, const int16_t* x, const int16_t* y, 
 int nsof_accum_set_events(nsof_accum* acc, const int16_t* x, const int16_t* y, const int8_t* p,
                           const int64_t* t, const int64_t* slice_bounds, int64_t n_slices);
 int nsof_accum_run(nsof_accum* acc, int64_t first_slice, int64_t n_slices, int64_t snap_every);
+/* nsof_accum_set_events / nsof_accum_step_events for a stream that lies in DEVICE memory -- what
+ * nsof_events_from_frames_*_dev and nsof_events_denoise_compact_dev write: d_x, d_y (int16), d_p (int8; may be NULL where
+ * the host entry allows it: every case but scheme 2 with polarity_split) and d_t (int64) hold n_events events; slice_bounds
+ * is a HOST array of n_slices + 1 indices into them, 0 <= slice_bounds[0] and slice_bounds[n_slices] <= n_events, else
+ * NSOF_EINVAL.  The contracts are the host twins': the same refusals with the same messages -- an event outside the sensor
+ * is "event %lld at (%d,%d) outside the %dx%d sensor", the first one in stream order -- found by one pass on the device
+ * (a wave reduces, then one atomic minimum per wave that found a fault).  A refused call launches nothing that writes the
+ * accumulator: state, snapshots and a previously staged stream stay as they were.  After a successful call the state,
+ * snapshots, surfaces and frames equal the host entry's on the same stream bit for bit; the caller's arrays are not
+ * retained.
+ * Stream: the entries work on the context's stream and WAIT for it twice per staged stream: once for the check's verdict
+ * (which, for scheme 2, brings every slice's first and last time along: 32 B + 16 B per slice, one copy; 8 B per slice of
+ * bounds went up before), and once at the end of the staging, after the events have been copied device to device, so
+ * that the caller may free or overwrite its arrays when the call returns.  The events never cross PCIe.  Work that
+ * produced the arrays on another stream must have completed before the call. */
+int nsof_accum_set_events_dev(nsof_accum* acc, const int16_t* d_x, const int16_t* d_y, const int8_t* d_p, const int64_t* d_t,
+                              int64_t n_events, const int64_t* slice_bounds, int64_t n_slices);
+int nsof_accum_step_events_dev(nsof_accum* acc, const int16_t* d_x, const int16_t* d_y, const int8_t* d_p, const int64_t* d_t,
+                               int64_t n_events, const int64_t* slice_bounds, int64_t n_slices, int64_t snap_every);
 /* Scheme 2 only (a no-op for scheme 1): replace the per-slice timestamps nsof_accum_set_events derived from the staged
  * events -- the first event's time (refractory test) and the last event's (next_ok = t_last + 800 us),
  * event_mem_sim.py:243-267 -- by those of the WHOLE stream's slices.  For an accumulator that holds a row band of the
@@ -737,6 +756,14 @@ int64_t nsof_accum_trials_snaps_in(const nsof_accum_trials* a, int64_t n_slices)
  * step -- launches nothing and leaves the object as it was. */
 int nsof_accum_trials_step(nsof_accum_trials* a, const int16_t* x, const int16_t* y, const int8_t* p, const int64_t* t,
                            const int64_t* slice_bounds, int64_t n_slices, double* d_block_current, int64_t* n_snaps);
+/* The same step over a chunk of a DEVICE stream: the four arrays, n_events and the host bounds as
+ * nsof_accum_set_events_dev takes them, checked and staged by the same code (one check, one staging, one message for both
+ * kinds of accumulator); everything else as nsof_accum_trials_step, the 2^31-event limit of ONE step included.  States,
+ * block currents and surfaces equal the host entry's bit for bit.  Waits for the context's stream twice: for the verdict,
+ * and when the chunk has run. */
+int nsof_accum_trials_step_dev(nsof_accum_trials* a, const int16_t* d_x, const int16_t* d_y, const int8_t* d_p, const int64_t* d_t,
+                               int64_t n_events, const int64_t* slice_bounds, int64_t n_slices, double* d_block_current,
+                               int64_t* n_snaps);
 /* Read-outs to DEVICE memory, asynchronous on the context's stream: the states and their resistances, float32 [A][T][H][W];
  * the block maxima of v_ds / R of the CURRENT states, float64 [A][T][rows][cols] (needs memsize). */
 int nsof_accum_trials_w_dev(nsof_accum_trials* a, float* d_out);
@@ -820,6 +847,13 @@ int nsof_lanczos3_contributions(int in_len, int out_len, double* wts, int32_t* i
 /* slice_indices() of event_mem_sim.py:78-83 on a HOST timestamp array: returns the number
  * of bounds and fills idx (if not NULL) with up to cap entries. */
 int64_t nsof_accum_slice_bounds(const int64_t* t, int64_t n, int64_t slice_us, int64_t* idx, int64_t cap);
+/* slice_indices() on a DEVICE timestamp array: nsof_accum_slice_bounds' result, idx a HOST array (up to cap entries, cap
+ * < 2^31; a pinned table of cap entries carries them).  One pass checks the order and reads t[0] and t[n - 1]; with idx,
+ * one thread per bound then searches the sorted array for the first index with t >= t[0] + i * slice_us -- on a sorted
+ * array exactly the host scan's result.  Returns the number of bounds, or a negative status: NSOF_EINVAL for t not
+ * non-decreasing (the message names the first e with t[e] < t[e-1]).  Works on the context's stream and waits for it
+ * ONCE per call: the verdict, the two times and the table come back in one copy.  |t| < 2^62. */
+int64_t nsof_accum_slice_bounds_dev(nsof_ctx* ctx, const int64_t* d_t, int64_t n, int64_t slice_us, int64_t* idx, int64_t cap);
 
 /* ---- ROI gating: the rectangles the gated path crops -------------------------------------------- */
 /* opticalFlow3D's gating arithmetic (optical_flow_seg.py:211-252 with :115-121, :426-435) for ONE gating slice, pure

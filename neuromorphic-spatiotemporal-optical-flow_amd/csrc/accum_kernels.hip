@@ -758,11 +758,15 @@ static int accum_snapshot(nsof_accum* a)
 }
 
 // Stage the events of slices [0, n_slices) (StagedStream) and make room for the lists of touched pixels.
+// n_dev >= 0: the arrays are DEVICE memory holding n_dev events (StagedStream::stage_dev).
 static int accum_stage(nsof_accum* a, const int16_t* x, const int16_t* y, const int8_t* p, const int64_t* t,
-                       const int64_t* sb, int64_t n_slices)
+                       const int64_t* sb, int64_t n_slices, int64_t n_dev = -1)
 {
     nsof_ctx* ctx = a->ctx;
-    if (int rc = a->ev.stage(ctx, a->W, a->H, a->scheme, a->split, a->model.prm.refractory_us, x, y, p, t, sb, n_slices)) return rc;
+    const long long refr = a->model.prm.refractory_us;
+    if (int rc = n_dev >= 0 ? a->ev.stage_dev(ctx, a->W, a->H, a->scheme, a->split, refr, x, y, p, t, n_dev, sb, n_slices)
+                            : a->ev.stage(ctx, a->W, a->H, a->scheme, a->split, refr, x, y, p, t, sb, n_slices))
+        return rc;
     const size_t n_ev = (size_t)a->ev.rel.back();
     int rc = NSOF_OK;
     for (int i = 0; i < (a->split ? 2 : 1) && !rc; i++)
@@ -934,6 +938,24 @@ extern "C" int nsof_accum_set_events(nsof_accum* a, const int16_t* x, const int1
 {
     if (!a) return NSOF_EINVAL;
     return accum_stage(a, x, y, p, t, sb, n_slices);
+}
+
+extern "C" int nsof_accum_step_events_dev(nsof_accum* a, const int16_t* d_x, const int16_t* d_y, const int8_t* d_p, const int64_t* d_t,
+                                          int64_t n_events, const int64_t* sb, int64_t n_slices, int64_t snap_every)
+{
+    if (!a) return NSOF_EINVAL;
+    if (n_events < 0) return nsof_set_error(a->ctx, NSOF_EINVAL, "a device stream of %lld events", (long long)n_events);
+    if (n_slices == 0) return NSOF_OK;
+    if (int rc = accum_stage(a, d_x, d_y, d_p, d_t, sb, n_slices, n_events)) return rc;
+    return accum_advance(a, 0, n_slices, snap_every);
+}
+
+extern "C" int nsof_accum_set_events_dev(nsof_accum* a, const int16_t* d_x, const int16_t* d_y, const int8_t* d_p, const int64_t* d_t,
+                                         int64_t n_events, const int64_t* sb, int64_t n_slices)
+{
+    if (!a) return NSOF_EINVAL;
+    if (n_events < 0) return nsof_set_error(a->ctx, NSOF_EINVAL, "a device stream of %lld events", (long long)n_events);
+    return accum_stage(a, d_x, d_y, d_p, d_t, sb, n_slices, n_events);
 }
 
 extern "C" int nsof_accum_run(nsof_accum* a, int64_t first_slice, int64_t n_slices, int64_t snap_every)
@@ -1273,5 +1295,54 @@ extern "C" int64_t nsof_accum_slice_bounds(const int64_t* t, int64_t n, int64_t 
             idx[i] = pos;
         }
     }
+    return nb;
+}
+
+// Bound i of a sorted DEVICE timestamp array: the first index with t >= t[0] + i * slice_us, a binary search -- on a sorted
+// array what the scan above returns.  The two ends of t are the record's (k_stream_check, ORDER), so the number of bounds
+// is formed here as the host forms it; one thread per bound below cap.
+__global__ __launch_bounds__(256) static void k_slice_table(const long long* __restrict__ t, long long n, long long slice_us,
+                                                             const unsigned long long* __restrict__ rec, long long* __restrict__ idx,
+                                                             long long cap)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long start = (long long)rec[1], stop = (long long)rec[2] + slice_us;
+    const long long nb = (stop - start + slice_us - 1) / slice_us;
+    if (i >= cap || i >= nb) return;
+    const long long b = start + i * slice_us;
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = lo + ((hi - lo) >> 1);
+        if (t[mid] < b) lo = mid + 1; else hi = mid;
+    }
+    idx[i] = lo;
+}
+
+extern "C" int64_t nsof_accum_slice_bounds_dev(nsof_ctx* ctx, const int64_t* d_t, int64_t n, int64_t slice_us, int64_t* idx, int64_t cap)
+{
+    if (!ctx) return NSOF_EINVAL;
+    if (!d_t || n <= 0 || slice_us <= 0) return 0;
+    const int64_t m = idx && cap > 0 ? cap : 0;
+    if (m >= (1ll << 31)) return nsof_set_error(ctx, NSOF_EUNSUPPORTED, "slice_bounds: room for %lld bounds, 2^31 or more", (long long)m);
+    NSOF_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = stream_words(ctx, STREAM_REC + (size_t)m)) return rc;
+    long long *const h = ctx->evtab_h.p, *const d = ctx->evtab.p;
+    unsigned long long* const rec = reinterpret_cast<unsigned long long*>(d);
+    NSOF_HIP(ctx, hipMemsetAsync(d, 0xFF, 8, ctx->stream));
+    hipLaunchKernelGGL((k_stream_check<false, true>), dim3(grid_for((size_t)n)), dim3(256), 0, ctx->stream, (const short*)nullptr,
+                       (const short*)nullptr, (const long long*)d_t, 0ll, (long long)n, 0, 0, rec);
+    // the table is formed before the verdict is known: a search reads inside t whatever its order
+    if (m)
+        hipLaunchKernelGGL(k_slice_table, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, (const long long*)d_t, (long long)n,
+                           (long long)slice_us, (const unsigned long long*)rec, d + STREAM_REC, (long long)m);
+    NSOF_HIP(ctx, hipGetLastError());
+    NSOF_HIP(ctx, hipMemcpyAsync(h, d, (STREAM_REC + (size_t)m) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if ((unsigned long long)h[0] != STREAM_CLEAN)
+        return nsof_set_error(ctx, NSOF_EINVAL, "slice_bounds: t is not non-decreasing: t[%lld] < t[%lld]", h[0], h[0] - 1);
+    const int64_t start = h[1], stop = h[2] + slice_us;
+    int64_t nb = (stop - start + slice_us - 1) / slice_us;
+    if (nb < 0) nb = 0;
+    if (m) memcpy(idx, h + STREAM_REC, (size_t)std::min(nb, m) * 8);
     return nb;
 }

@@ -318,6 +318,7 @@ struct Chunk {
     const int8_t* p;
     const int64_t *t, *sb;
     int64_t n_slices;
+    int64_t n_dev = -1;   // >= 0: x, y, p, t are DEVICE arrays of that many events (StagedStream::stage_dev)
 };
 
 // the wini planes into the states (k_setup_maps with no drive trial writes nothing else), masks / next_ok / counters zero
@@ -463,7 +464,9 @@ int trials_step(nsof_accum_trials* a, const Chunk& c, bool checked, double* d_bl
     const Model& mo = a->mo;
     NSOF_HIP(ctx, hipSetDevice(ctx->device));
     StagedStream& ev = a->ev;
-    if (int rc = ev.stage(ctx, width, a->H, scheme, split, mo.prm.refractory_us, c.x, c.y, c.p, c.t, c.sb, n_slices, checked)) return rc;
+    if (int rc = c.n_dev >= 0 ? ev.stage_dev(ctx, width, a->H, scheme, split, mo.prm.refractory_us, c.x, c.y, c.p, c.t, c.n_dev, c.sb, n_slices)
+                              : ev.stage(ctx, width, a->H, scheme, split, mo.prm.refractory_us, c.x, c.y, c.p, c.t, c.sb, n_slices, checked))
+        return rc;
     if (dead) {
         const size_t nev = (size_t)std::max<int64_t>(n_ev, 1), cap = StagedStream::event_cap(n_ev);
         for (int i = 0; i < narr; i++) {
@@ -643,6 +646,17 @@ extern "C" int nsof_accum_trials_step(nsof_accum_trials* a, const int16_t* x, co
 {
     if (!a) return NSOF_EINVAL;
     if (int rc = trials_step(a, Chunk{x, y, p, t, sb, n_slices}, false, d_block_current, n_snaps)) return rc;
+    // the caller's arrays are not retained: the chunk ends here
+    NSOF_HIP(a->ctx, hipStreamSynchronize(a->ctx->stream));
+    return NSOF_OK;
+}
+
+extern "C" int nsof_accum_trials_step_dev(nsof_accum_trials* a, const int16_t* d_x, const int16_t* d_y, const int8_t* d_p, const int64_t* d_t,
+                                          int64_t n_events, const int64_t* sb, int64_t n_slices, double* d_block_current, int64_t* n_snaps)
+{
+    if (!a) return NSOF_EINVAL;
+    if (n_events < 0) return nsof_set_error(a->ctx, NSOF_EINVAL, "a device stream of %lld events", (long long)n_events);
+    if (int rc = trials_step(a, Chunk{d_x, d_y, d_p, d_t, sb, n_slices, n_events}, false, d_block_current, n_snaps)) return rc;
     // the caller's arrays are not retained: the chunk ends here
     NSOF_HIP(a->ctx, hipStreamSynchronize(a->ctx->stream));
     return NSOF_OK;

@@ -2,7 +2,8 @@
 // stream) share.  Device code: the update arithmetic (update_one, Drive, drive_of, update_drive, replay_driven,
 // resistance_one, surface_gray_value), the scatter of a group of slices (k_scatter and its marks), scheme 1's count threshold (Theta,
 // driven_bits), scheme 2's refractory walk (RefrTab, refractory_walk), the set-up pass of per-pixel devices (k_setup_maps)
-// and the resistance read-outs (k_resistance, k_block_min_resistance).  Host code: the staged stream (StagedStream) and the
+// the resistance read-outs (k_resistance, k_block_min_resistance) and the check and slice times of a stream that lies in
+// device memory (k_stream_check, k_slice_times).  Host code: the staged stream (StagedStream: stage, stage_dev) and the
 // walk over its groups (group_len, snapshot_due, refr_tab_of, ListCounts).  Everything sits in an unnamed namespace, as in
 // accum_model.h: each translation unit instantiates its own copies.
 #pragma once
@@ -484,6 +485,64 @@ __global__ __launch_bounds__(256) void k_block_min_resistance(const float* __res
         out[blockIdx.z * out_stride + (size_t)by * cols + bx] = v_ds / (double)fminf(fminf(part[0], part[1]), fminf(part[2], part[3]));
 }
 
+// ---- a stream in device memory: its check and its slice times ------------------------------------------------------------
+// The record a check leaves, 64-bit words: [0] the verdict -- the smallest index of an event at fault, all ones for none --,
+// [1] t[e0] and [2] t[e1 - 1] (ORDER only), [3] unused.  The host sets the verdict to all ones before the launch.
+constexpr int STREAM_REC = 4;
+constexpr unsigned long long STREAM_CLEAN = ~0ull;
+
+// One pass over events [e0, e1) of a device stream.  At fault is an event
+//   XY     whose coordinates lie outside the W x H sensor (x, y are read)
+//   ORDER  e > e0 whose time lies before its predecessor's (t is read, and its two ends go to the record)
+// A wave walks 64 consecutive events per step, so the first set bit of its ballot is the wave's smallest index of that step
+// and, the steps ascending, of the whole walk: that lane issues the wave's ONE atomic minimum and the wave leaves.
+template <bool XY, bool ORDER>
+__global__ __launch_bounds__(256) void k_stream_check(const short* __restrict__ x, const short* __restrict__ y,
+                                                       const long long* __restrict__ t, long long e0, long long e1, int W, int H,
+                                                       unsigned long long* rec)
+{
+    const int lane = threadIdx.x & 63;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long e = e0 + (long long)blockIdx.x * 256 + threadIdx.x; e - lane < e1; e += stride) {   // (the test is the wave's)
+        bool bad = false;
+        if (e < e1) {
+            if constexpr (XY) bad = (unsigned)x[e] >= (unsigned)W || (unsigned)y[e] >= (unsigned)H;
+            if constexpr (ORDER) {
+                const long long te = t[e];
+                bad = bad || (e > e0 && te < t[e - 1]);
+                if (e == e0) rec[1] = (unsigned long long)te;
+                if (e == e1 - 1) rec[2] = (unsigned long long)te;
+            }
+        }
+        const unsigned long long b = __ballot(bad);
+        if (b) {
+            if (lane == __ffsll((long long)b) - 1) atomicMin(&rec[0], (unsigned long long)e);
+            break;
+        }
+    }
+}
+// Scheme 2's two times per slice s of a device stream, as StagedStream::stage forms them on the host: t of the slice's first
+// event and t of its last + the refractory period, zeros for an empty slice.  rel: the n_slices + 1 bounds relative to e0.
+__global__ __launch_bounds__(256) void k_slice_times(const long long* __restrict__ t, long long e0, const long long* __restrict__ rel,
+                                                      long long n_slices, long long refractory_us, long long* __restrict__ tfirst,
+                                                      long long* __restrict__ tnext)
+{
+    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= n_slices) return;
+    const long long a = rel[s], b = rel[s + 1];
+    const bool live = b > a;
+    tfirst[s] = live ? t[e0 + a] : 0;
+    tnext[s] = live ? t[e0 + b - 1] + refractory_us : 0;
+}
+
+// The context's words for such a stream (device, and the pinned twin the copies go through): at least `words` of each.
+inline int stream_words(nsof_ctx* ctx, size_t words)
+{
+    const size_t bytes = words * sizeof(long long), cap = align_up(bytes + bytes / 2, 4096);
+    if (int rc = ctx->evtab.reserve(ctx, bytes, cap)) return rc;
+    return ctx->evtab_h.reserve(ctx, bytes, cap);
+}
+
 // ---- the staged stream and the walk over its groups (host) --------------------------------------------------------------
 // The events of slices [0, n_slices) on the device and what the slice loop needs of them on the host: the slice bounds
 // relative to the first staged event and, for scheme 2, every slice's first timestamp and last timestamp + refractory period.
@@ -492,21 +551,93 @@ struct StagedStream {
     nsof_dev_buf<short> dx, dy;
     nsof_dev_buf<signed char> dp;
     nsof_dev_buf<long long> dbounds;
+    // What refuses a stream whatever memory its events lie in: the bounds and the arrays that must be there.
+    static int check_bounds(nsof_ctx* ctx, int scheme, int split, bool have_xyt, bool have_p, const int64_t* sb, int64_t n_slices)
+    {
+        if (n_slices < 0 || !sb) return nsof_set_error(ctx, NSOF_EINVAL, "bad slice bounds");
+        const int64_t n_ev = sb[n_slices] - sb[0];
+        if (n_ev < 0) return nsof_set_error(ctx, NSOF_EINVAL, "slice bounds not monotone");
+        if (n_ev > 0 && (!have_xyt || (scheme == 2 && split && !have_p))) return nsof_set_error(ctx, NSOF_EINVAL, "null event array");
+        for (int64_t s = 0; s < n_slices; s++)
+            if (sb[s + 1] < sb[s]) return nsof_set_error(ctx, NSOF_EINVAL, "slice bounds not monotone");
+        return NSOF_OK;
+    }
+    // ... and the refusal of event e at (x, y), the first in stream order outside the sensor
+    static int refuse_event(nsof_ctx* ctx, int64_t e, int x, int y, int W, int H)
+    {
+        return nsof_set_error(ctx, NSOF_EINVAL, "event %lld at (%d,%d) outside the %dx%d sensor", (long long)e, x, y, W, H);
+    }
     // Everything about a stream that refuses it, on the host: nothing is allocated, uploaded or launched.
     static int check(nsof_ctx* ctx, int W, int H, int scheme, int split, const int16_t* x, const int16_t* y, const int8_t* p,
                      const int64_t* t, const int64_t* sb, int64_t n_slices)
     {
-        if (n_slices < 0 || !sb) return nsof_set_error(ctx, NSOF_EINVAL, "bad slice bounds");
-        const int64_t e0 = sb[0], e1 = sb[n_slices], n_ev = e1 - e0;
-        if (n_ev < 0) return nsof_set_error(ctx, NSOF_EINVAL, "slice bounds not monotone");
-        if (n_ev > 0 && (!x || !y || !t || (scheme == 2 && split && !p))) return nsof_set_error(ctx, NSOF_EINVAL, "null event array");
-        for (int64_t s = 0; s < n_slices; s++)
-            if (sb[s + 1] < sb[s]) return nsof_set_error(ctx, NSOF_EINVAL, "slice bounds not monotone");
+        if (int rc = check_bounds(ctx, scheme, split, x && y && t, p != nullptr, sb, n_slices)) return rc;
         // validate coordinates on the host: an out-of-range event would be an out-of-bounds store on the device
-        for (int64_t e = e0; e < e1; e++)
-            if ((unsigned)x[e] >= (unsigned)W || (unsigned)y[e] >= (unsigned)H)
-                return nsof_set_error(ctx, NSOF_EINVAL, "event %lld at (%d,%d) outside the %dx%d sensor", (long long)e, (int)x[e],
-                                      (int)y[e], W, H);
+        for (int64_t e = sb[0]; e < sb[n_slices]; e++)
+            if ((unsigned)x[e] >= (unsigned)W || (unsigned)y[e] >= (unsigned)H) return refuse_event(ctx, e, x[e], y[e], W, H);
+        return NSOF_OK;
+    }
+    // stage() for a stream that lies in DEVICE memory: d_x, d_y, d_p, d_t hold n_events events, sb (host) indexes them.  The
+    // check runs on the device (k_stream_check) and its verdict comes back, with scheme 2's slice times, in one copy:
+    // the first wait.  Only then is anything of this object written -- a refused stream leaves the staged one as it was --
+    // and the events are copied device to device.  Across PCIe go the bounds (8 B per slice, up), the record (32 B) and
+    // scheme 2's times (16 B per slice, down).  The caller's arrays are read until ctx->stream has drained: the caller's
+    // wait, the second.
+    int stage_dev(nsof_ctx* ctx, int W, int H, int scheme, int split, long long refractory_us, const int16_t* d_x, const int16_t* d_y,
+                  const int8_t* d_p, const int64_t* d_t, int64_t n_events, const int64_t* sb, int64_t n_slices)
+    {
+        if (int rc = check_bounds(ctx, scheme, split, d_x && d_y && d_t, d_p != nullptr, sb, n_slices)) return rc;
+        const int64_t e0 = sb[0], e1 = sb[n_slices], n_ev = e1 - e0;
+        if (e0 < 0 || e1 > n_events)
+            return nsof_set_error(ctx, NSOF_EINVAL, "slice bounds [%lld, %lld] outside the %lld events of the device stream", (long long)e0,
+                                  (long long)e1, (long long)n_events);
+        NSOF_HIP(ctx, hipSetDevice(ctx->device));
+        // the words: rel [ns + 1], the record [STREAM_REC], tfirst [ns], tnext [ns]
+        const size_t ns = (size_t)n_slices, rec = ns + 1, tf = rec + STREAM_REC, tn = tf + ns;
+        if (int rc = stream_words(ctx, tn + ns)) return rc;
+        long long *const h = ctx->evtab_h.p, *const d = ctx->evtab.p;
+        for (size_t s = 0; s <= ns; s++) h[s] = (long long)(sb[s] - e0);
+        NSOF_HIP(ctx, hipMemcpyAsync(d, h, rec * 8, hipMemcpyHostToDevice, ctx->stream));
+        const bool times = scheme == 2 && n_ev > 0;
+        if (n_ev > 0) {
+            NSOF_HIP(ctx, hipMemsetAsync(d + rec, 0xFF, 8, ctx->stream));
+            hipLaunchKernelGGL((k_stream_check<true, false>), dim3(grid_for((size_t)n_ev)), dim3(256), 0, ctx->stream, (const short*)d_x,
+                               (const short*)d_y, (const long long*)nullptr, (long long)e0, (long long)e1, W, H,
+                               reinterpret_cast<unsigned long long*>(d + rec));
+            if (times)
+                hipLaunchKernelGGL(k_slice_times, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream, (const long long*)d_t,
+                                   (long long)e0, (const long long*)d, (long long)n_slices, refractory_us, d + tf, d + tn);
+            NSOF_HIP(ctx, hipGetLastError());
+            NSOF_HIP(ctx, hipMemcpyAsync(h + rec, d + rec, (STREAM_REC + (times ? 2 * ns : 0)) * 8, hipMemcpyDeviceToHost, ctx->stream));
+            NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if ((unsigned long long)h[rec] != STREAM_CLEAN) {   // (the refusal's own two reads are not part of the count above)
+                const int64_t e = (int64_t)h[rec];
+                int16_t bx = 0, by = 0;
+                NSOF_HIP(ctx, hipMemcpyAsync(&bx, d_x + e, 2, hipMemcpyDeviceToHost, ctx->stream));
+                NSOF_HIP(ctx, hipMemcpyAsync(&by, d_y + e, 2, hipMemcpyDeviceToHost, ctx->stream));
+                NSOF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                return refuse_event(ctx, e, bx, by, W, H);
+            }
+        }
+        int rc;
+        const size_t cap = event_cap(n_ev);
+        if ((rc = dx.reserve(ctx, (size_t)n_ev * 2, cap * 2)) || (rc = dy.reserve(ctx, (size_t)n_ev * 2, cap * 2)) ||
+            (rc = dp.reserve(ctx, (size_t)n_ev, cap)) || (rc = dbounds.reserve(ctx, rec * 8)))
+            return rc;
+        if (n_ev > 0) {
+            NSOF_HIP(ctx, hipMemcpyAsync(dx.p, d_x + e0, (size_t)n_ev * 2, hipMemcpyDeviceToDevice, ctx->stream));
+            NSOF_HIP(ctx, hipMemcpyAsync(dy.p, d_y + e0, (size_t)n_ev * 2, hipMemcpyDeviceToDevice, ctx->stream));
+            if (d_p) NSOF_HIP(ctx, hipMemcpyAsync(dp.p, d_p + e0, (size_t)n_ev, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        NSOF_HIP(ctx, hipMemcpyAsync(dbounds.p, d, rec * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        rel.assign(h, h + rec);
+        if (times) {
+            tfirst.assign(h + tf, h + tf + ns);
+            tnext.assign(h + tn, h + tn + ns);
+        } else {
+            tfirst.assign(ns, 0);
+            tnext.assign(ns, 0);
+        }
         return NSOF_OK;
     }
     // Checks and uploads on ctx->stream (bounds sb index the caller's arrays, which are not retained: synchronise before

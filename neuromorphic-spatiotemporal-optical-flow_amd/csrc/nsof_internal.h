@@ -109,6 +109,10 @@ struct nsof_ctx {
     nsof_table frame_maps;
     // response table and frame times of the event generator (nsof_events_from_frames_*_dev)
     nsof_table events;
+    // event streams the accumulators read where they lie in device memory (accum_update.h, "a stream in device memory"):
+    // the slice bounds going up, the check's record and the slice tables coming back -- device words and their pinned twin
+    nsof_dev_buf<long long> evtab;
+    nsof_host_buf<long long> evtab_h;
     // exact-order fused iteration (farneback_iterate_x.hip): strip-to-strip carries (tagged granules, zeroed when
     // allocated, never again: a launch's tag is its epoch), the per-XCD ticket counters + timeout word (x_sync:
     // tickets at word 0, timeout word at word 256), the launch epoch, and whether a launch's timeout word needs a look

@@ -146,6 +146,8 @@ SIGNATURES = {
     "nsof_accum_trials_snaps_in": (_i64, [_vp, _i64]),
     # a, x, y, p, t, bounds, n_slices, d_block_current, n_snaps
     "nsof_accum_trials_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, C.POINTER(_i64)]),
+    # a, d_x, d_y, d_p, d_t, n_events, bounds, n_slices, d_block_current, n_snaps
+    "nsof_accum_trials_step_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, C.POINTER(_i64)]),
     "nsof_accum_trials_w_dev": (_i, [_vp, _vp]),
     "nsof_accum_trials_resistance_dev": (_i, [_vp, _vp]),
     "nsof_accum_trials_block_current_dev": (_i, [_vp, _vp]),
@@ -167,6 +169,9 @@ SIGNATURES = {
     "nsof_accum_reset": (_i, [_vp]),
     "nsof_accum_step_events": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
     "nsof_accum_set_events": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64]),
+    # acc, d_x, d_y, d_p, d_t, n_events, bounds, n_slices[, snap_every]
+    "nsof_accum_step_events_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64]),
+    "nsof_accum_set_events_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64]),
     "nsof_accum_set_slice_times": (_i, [_vp, _vp, _vp, _i64]),
     "nsof_accum_run": (_i, [_vp, _i64, _i64, _i64]),
     "nsof_accum_surface_u8_dev": (_i, [_vp, _i, _i, _vp, _pd]),
@@ -190,6 +195,7 @@ SIGNATURES = {
     "nsof_frames_compress_u8_dev": (_i, [_vp, _i, _vp, _pd, _pd, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "nsof_lanczos3_contributions": (_i, [_i, _i, _vp, _vp, _i, C.POINTER(_i)]),
     "nsof_accum_slice_bounds": (_i64, [_vp, _i64, _i64, _vp, _i64]),
+    "nsof_accum_slice_bounds_dev": (_i64, [_vp, _vp, _i64, _i64, _vp, _i64]),
     "nsof_roi_from_surface": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i]),
     "nsof_roi_from_surface_dev": (_i, [_vp, _vp, _i, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "nsof_structuring_element": (_i, [_i, _i, _i, _vp]),

@@ -243,8 +243,88 @@ def resistance_exp(w, p=PARAMS, *, ctx=None):
     return out.cpu().numpy()
 
 
-def slice_index_array(t, slice_us):
-    """searchsorted(t, arange(t[0], t[-1]+slice_us, slice_us)) of event_mem_sim.py:78-83 as one int64 array."""
+_EVENT_ARRAYS = (("x", "int16"), ("y", "int16"), ("p", "int8"), ("t", "int64"))   # an event stream's arrays and their dtypes
+
+
+def _is_cuda(v):
+    return bool(getattr(v, "is_cuda", False))
+
+
+def device_events(who, x, y, p, t, ctx=None):
+    """Whether the event arrays of a call are a stream in HBM.  None of them a CUDA tensor: ``None``, the host path as ever
+    (arrays, lists and CPU tensors).  Otherwise all four must be CUDA tensors of dtypes int16, int16, int8, int64, 1-D,
+    contiguous, of one length and on one device -- ``ctx``'s, where given -- and the number of events is returned; anything
+    else that holds a CUDA tensor (a mix of host and device arrays, another dtype -- nothing is converted on the device --, a
+    strided view, another device) raises ``NsofValueError`` before any device work."""
+    arrs = (x, y, p, t)
+    if not any(_is_cuda(v) for v in arrs):
+        return None
+    torch = _torch()
+    for (name, dtype), v in zip(_EVENT_ARRAYS, arrs):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda:
+            raise NsofValueError(f"{who}: {name} is no CUDA tensor while another event array is (got {type(v).__name__}"
+                                 f"{' on the CPU' if isinstance(v, torch.Tensor) else ''}); a stream lies on the host or in HBM, "
+                                 "all four arrays of it", _lib.NSOF_EINVAL)
+    for (name, dtype), v in zip(_EVENT_ARRAYS, arrs):
+        if v.dtype != getattr(torch, dtype):
+            raise NsofValueError(f"{who}: {name} must be an {dtype} tensor (got {v.dtype}); a device stream is not converted",
+                                 _lib.NSOF_EINVAL)
+        if v.dim() != 1 or v.shape != x.shape or not v.is_contiguous():
+            raise NsofValueError(f"{who}: {name} must be contiguous, one-dimensional and as long as x (got {tuple(v.shape)}, strides "
+                                 f"{tuple(v.stride())}, x {tuple(x.shape)})", _lib.NSOF_ESHAPE)
+        if v.device != x.device:
+            raise NsofValueError(f"{who}: {name} lies on {v.device}, x on {x.device}", _lib.NSOF_EINVAL)
+    if ctx is not None and x.device.index != ctx.device:
+        raise NsofValueError(f"{who}: the stream lies on {x.device}, the context works on cuda:{ctx.device}", _lib.NSOF_EINVAL)
+    return int(x.shape[0])
+
+
+def _device_stream(who, ctx, x, y, p, t, bounds):
+    """The arguments of a ``*_dev`` staging entry for a stream in HBM (``device_events``), ``None`` for a host stream:
+    ``(d_x, d_y, d_p, d_t, n_events, bounds, n_slices)`` -- ``bounds`` the host int64 array as a ctypes pointer that keeps
+    it alive, ``n_slices`` -1 for no bound at all -- after the one ``torch.cuda.synchronize`` that lets the library read
+    torch's tensors on the context's stream.  Bounds that reach outside the stream raise ``NsofValueError``."""
+    n = device_events(who, x, y, p, t, ctx)
+    if n is None:
+        return None
+    bounds = np.ascontiguousarray(bounds, np.int64)
+    if bounds.ndim != 1:
+        raise NsofValueError(f"{who}: the slice bounds must be one-dimensional (got {bounds.shape})", _lib.NSOF_ESHAPE)
+    if bounds.size and (bounds[-1] > n or bounds[0] < 0):
+        raise NsofValueError("event arrays shorter than the slice bounds")
+    _torch().cuda.synchronize(x.device)
+    return dev_ptr(x), dev_ptr(y), dev_ptr(p), dev_ptr(t), n, bounds.ctypes.data_as(C.c_void_p), bounds.size - 1
+
+
+def _device_bounds(ctx, lib_fn, d_t, slice_us, idx, cap):
+    n = int(lib_fn(ctx.ptr, dev_ptr(d_t), int(d_t.shape[0]), int(slice_us), idx, cap))
+    if n < 0:
+        ctx.check(n, "slice_index_array")
+    return n
+
+
+def slice_index_array(t, slice_us, ctx=None):
+    """searchsorted(t, arange(t[0], t[-1]+slice_us, slice_us)) of event_mem_sim.py:78-83 as one int64 array (host).
+    ``t``: anything array-like on the host or, for a stream in HBM, a contiguous 1-D int64 CUDA tensor on the device of
+    ``ctx`` (``None``: the default context; host arrays need none) -- the bounds are then found on the device
+    (``nsof_accum_slice_bounds_dev``: two calls, each waits for the context's stream once, after one
+    ``torch.cuda.synchronize``) and only they come back; a ``t`` that decreases raises ``NsofValueError`` (``NSOF_EINVAL``)
+    naming the first such event.  ``t`` may be freed when the call returns."""
+    if _is_cuda(t):
+        torch = _torch()
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+            raise NsofValueError(f"slice_index_array: a device t must be a contiguous one-dimensional int64 tensor (got "
+                                 f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))})", _lib.NSOF_EINVAL)
+        ctx = ctx or default_context()
+        if t.device.index != ctx.device:
+            raise NsofValueError(f"slice_index_array: t lies on {t.device}, the context works on cuda:{ctx.device}", _lib.NSOF_EINVAL)
+        fn = ctx._lib.nsof_accum_slice_bounds_dev
+        torch.cuda.synchronize(t.device)   # t is torch's work; the library reads it on the context's stream
+        n = _device_bounds(ctx, fn, t, slice_us, None, 0)
+        idx = np.empty(n, np.int64)
+        if n:
+            _device_bounds(ctx, fn, t, slice_us, idx.ctypes.data, n)
+        return idx
     t = np.ascontiguousarray(t, np.int64)
     lib = _lib.load()
     n = lib.nsof_accum_slice_bounds(t.ctypes.data, t.size, int(slice_us), None, 0)
@@ -393,7 +473,16 @@ class Accumulator:
         self.ctx.check(self.ctx._lib.nsof_accum_reset(self._p), "accum_reset")
 
     def step(self, x, y, p, t, bounds, snap_every=0):
-        """Advance over slices ``[bounds[i], bounds[i+1])`` of the host event arrays."""
+        """Advance over slices ``[bounds[i], bounds[i+1])`` of the event arrays: host arrays, or -- a stream in HBM -- four
+        CUDA tensors as ``device_events`` takes them (``nsof_accum_step_events_dev``: checked on the device, copied device
+        to device, the same state and snapshots bit for bit; ``bounds`` stays a host array).  The device form waits for the
+        device once before the library reads the tensors and returns when they have been copied: the caller may free or
+        overwrite them then."""
+        dev = _device_stream("Accumulator.step", self.ctx, x, y, p, t, bounds)
+        if dev is not None:
+            if dev[-1] >= 1:
+                self.ctx.check(self.ctx._lib.nsof_accum_step_events_dev(self._p, *dev, int(snap_every)), "accum_step_events")
+            return
         x = np.ascontiguousarray(x, np.int16)
         y = np.ascontiguousarray(y, np.int16)
         p = np.ascontiguousarray(p, np.int8)
@@ -408,7 +497,16 @@ class Accumulator:
                                                             int(snap_every)), "accum_step_events")
 
     def set_events(self, x, y, p, t, bounds):
-        """Upload the events of all slices once (``nsof_accum_set_events``); ``run`` then advances over sub-ranges."""
+        """Upload the events of all slices once (``nsof_accum_set_events``); ``run`` then advances over sub-ranges.  Four CUDA
+        tensors (``device_events``) are staged where they lie (``nsof_accum_set_events_dev``), as ``step`` takes them: the
+        accumulator keeps its own copy, so the tensors may be freed when the call returns."""
+        dev = _device_stream("Accumulator.set_events", self.ctx, x, y, p, t, bounds)
+        if dev is not None:
+            if dev[-1] < 0:
+                raise NsofValueError("event arrays shorter than the slice bounds")
+            self.n_staged = dev[-1]
+            self.ctx.check(self.ctx._lib.nsof_accum_set_events_dev(self._p, *dev), "accum_set_events")
+            return
         x = np.ascontiguousarray(x, np.int16)
         y = np.ascontiguousarray(y, np.int16)
         p = np.ascontiguousarray(p, np.int8)
@@ -771,29 +869,37 @@ class TrialAccumulator:
         return cnt.value
 
     def step(self, x, y, p, t, bounds):
-        """Advance over slices ``[bounds[i], bounds[i+1])`` of the host event arrays (synchronous).  With ``memsize``: returns
+        """Advance over slices ``[bounds[i], bounds[i+1])`` of the event arrays (synchronous).  With ``memsize``: returns
         the float64 CUDA tensor ``[A][T][S][H // memsize][W // memsize]`` of the block currents after the ``S`` snapshot slices
         -- absolute indices 0, ``snapshot_every``, ... -- inside this chunk (the chunks' tensors concatenated along ``S`` are
-        the one-shot run's ``block_current``); otherwise ``None``."""
+        the one-shot run's ``block_current``); otherwise ``None``.  A stream in HBM -- four CUDA tensors as ``device_events``
+        takes them -- is checked and staged where it lies (``nsof_accum_trials_step_dev``), with the same results bit for
+        bit; the tensors may be freed when the call returns."""
         h = self._h
-        x = np.ascontiguousarray(x, np.int16)
-        y = np.ascontiguousarray(y, np.int16)
-        p = np.ascontiguousarray(p, np.int8)
-        t = np.ascontiguousarray(t, np.int64)
-        bounds = np.ascontiguousarray(bounds, np.int64)
-        if bounds.ndim != 1 or not (x.size == y.size == p.size == t.size):
-            raise NsofValueError("event arrays of differing lengths")
-        n = max(bounds.size - 1, 0)
-        if n and (bounds[-1] > x.size or bounds[0] < 0):
-            raise NsofValueError("event arrays shorter than the slice bounds")
+        dev = _device_stream("TrialAccumulator.step", self.ctx, x, y, p, t, bounds)
+        if dev is None:
+            x = np.ascontiguousarray(x, np.int16)
+            y = np.ascontiguousarray(y, np.int16)
+            p = np.ascontiguousarray(p, np.int8)
+            t = np.ascontiguousarray(t, np.int64)
+            bounds = np.ascontiguousarray(bounds, np.int64)
+            if bounds.ndim != 1 or not (x.size == y.size == p.size == t.size):
+                raise NsofValueError("event arrays of differing lengths")
+            n = max(bounds.size - 1, 0)
+            if n and (bounds[-1] > x.size or bounds[0] < 0):
+                raise NsofValueError("event arrays shorter than the slice bounds")
+        else:
+            n = max(dev[-1], 0)
         cur = None
         if self.memsize is not None:
             s = int(self.ctx._lib.nsof_accum_trials_snaps_in(h, n))
             cur = self._empty((self.arrays, self.trials, s, self.H // self.memsize, self.W // self.memsize), _torch().float64)
-        if n:
+        d_cur = dev_ptr(cur) if cur is not None and cur.numel() else None
+        if n and dev is None:
             self.ctx.check(self.ctx._lib.nsof_accum_trials_step(h, x.ctypes.data, y.ctypes.data, p.ctypes.data, t.ctypes.data,
-                                                                bounds.ctypes.data, n, dev_ptr(cur) if cur is not None and cur.numel() else None,
-                                                                None), "accum_trials_step")
+                                                                bounds.ctypes.data, n, d_cur, None), "accum_trials_step")
+        elif n:
+            self.ctx.check(self.ctx._lib.nsof_accum_trials_step_dev(h, *dev, d_cur, None), "accum_trials_step")
         return cur
 
     def w_dev(self):
@@ -903,10 +1009,22 @@ def simulate_trials_dev(events, param_maps, version=1, slice_us=1_000, active_v=
     slice, 1)``, a pure function of its arguments: results do not depend on ``snapshot_every`` or on how many trials run.
     ``None``, or both spreads 0, is the noiseless run bit for bit.  ``active_v`` / ``silent_v``: a number, or a sequence of ``T``
     numbers, one per trial (``TrialAccumulator``, which this function creates, steps once over the whole stream and closes).
+    ``events`` may be a stream in HBM -- four CUDA tensors as ``device_events`` takes them: bounds, check and staging then
+    run on the device (``slice_index_array``, ``TrialAccumulator.step``), ``sensor_size`` must be given (without it the call
+    is refused before any device work), and the tensors may be freed when the call returns.
     Every refusal -- arguments, shapes, the value domain of every plane -- comes before any device work.  Synchronous."""
-    early = _trial_scalars(version, polarity, params, dt, refractory_us, theta_events, c2c, trials)
+    early =_trial_scalars(version, polarity, params, dt, refractory_us, theta_events, c2c, trials)
+    in_hbm = not isinstance(events, (str, Path)) and any(_is_cuda(v) for v in events)
     if isinstance(events, (str, Path)):
         x, y, p, t, H, W = load_events(Path(events))  # noqa: N806
+    elif in_hbm:
+        # a stream in HBM (device_events): the sensor is not inferred -- that would be a reduction and a wait of its own
+        if sensor_size is None:
+            raise NsofValueError("simulate_trials_dev: a device event stream needs sensor_size = (H, W)")
+        x, y, p, t = events
+        if device_events("simulate_trials_dev", x, y, p, t, ctx) == 0:
+            raise NsofValueError("empty event stream")
+        H, W = (int(v) for v in sensor_size)  # noqa: N806
     else:
         x, y, p, t = events
         x, y, t = np.asarray(x), np.asarray(y), np.asarray(t)
@@ -916,11 +1034,15 @@ def simulate_trials_dev(events, param_maps, version=1, slice_us=1_000, active_v=
     # (the cadence is checked here with a stand-in where it follows from the stream: that is known only below)
     cfg = _trial_config(early, H, W, param_maps, active_v, silent_v, trials, 1 if snapshot_every is None and memsize is not None else snapshot_every,
                         memsize, v_ds)
-    x16, y16 = np.ascontiguousarray(x, np.int16), np.ascontiguousarray(y, np.int16)
-    p8, t64 = np.ascontiguousarray(p, np.int8), np.ascontiguousarray(t, np.int64)
-    if not (x16.size == y16.size == p8.size == t64.size):
-        raise NsofValueError("event arrays of differing lengths")
-    idx = slice_index_array(t64, slice_us)
+    if in_hbm:
+        x16, y16, p8, t64 = x, y, p, t
+        ctx = ctx or default_context()
+    else:
+        x16, y16 = np.ascontiguousarray(x, np.int16), np.ascontiguousarray(y, np.int16)
+        p8, t64 = np.ascontiguousarray(p, np.int8), np.ascontiguousarray(t, np.int64)
+        if not (x16.size == y16.size == p8.size == t64.size):
+            raise NsofValueError("event arrays of differing lengths")
+    idx = slice_index_array(t64, slice_us, ctx)
     nslices = len(idx) - 1
     if nslices < 1:
         raise NsofValueError("the event stream holds no slice")

@@ -177,7 +177,7 @@ def events_flow_variability_dev(x, y, p, t, sensor_hw, rel_sigma, trials, seed=0
                                                    theta_events=theta_events)
     t1 = time.perf_counter()
     n = int(frames.shape[0])
-    idx = slice_index_array(t, slice_us)
+    idx = slice_index_array(t, slice_us, ctx)
     # the planes of the keys that do vary (events_variability_dev: a key's plane does not depend on which other spreads are zero)
     maps = {k: v for k, v in variability_maps(H, W, rel_sigma, accum_params, seed, trials=trials).items() if float(rel_sigma[k]) != 0.0}
     stats = {k: torch.empty((n - 1, H, W) + ((c,) if c else ()), dtype=torch.float64, device=dev) for k, c in _STATE}

@@ -40,7 +40,7 @@ def events_to_rois(x, y, p, t, sensor_hw, cfg, version=1, polarity="split", slic
     from .context import default_context
     ctx = ctx or default_context()
     H, W = sensor_hw  # noqa: N806
-    idx = slice_index_array(t, slice_us)
+    idx = slice_index_array(t, slice_us, ctx)
     rows, cols = H // cfg.MEMSIZE, W // cfg.MEMSIZE
     acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, params=params, dt=dt, refractory_us=refractory_us,
                       theta_events=theta_events)
@@ -100,7 +100,7 @@ def events_variability_dev(x, y, p, t, sensor_hw, cfg, rel_sigma, trials, seed=0
     acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, params=params, dt=dt, refractory_us=refractory_us,
                       theta_events=theta_events)
     try:
-        acc.step(x, y, p, t, slice_index_array(t, slice_us), snap_every=snapshot_every)
+        acc.step(x, y, p, t, slice_index_array(t, slice_us, ctx), snap_every=snapshot_every)
         n = acc.snapshot_count()
         nominal = torch.empty((n, rows, cols), dtype=torch.float64, device=torch.device("cuda", ctx.device))
         for k in range(n):
@@ -130,7 +130,7 @@ def events_to_rois_host(x, y, p, t, sensor_hw, cfg, version=1, polarity="split",
     """The same through the host-side mirror of the reference's gating (``gating.connectedComponentsWithStats`` on the
     downloaded block currents): kept as the independent path the device kernel is tested against."""
     H, W = sensor_hw  # noqa: N806
-    idx = slice_index_array(t, slice_us)
+    idx = slice_index_array(t, slice_us, ctx)
     acc = Accumulator(H, W, version, polarity, active_v, silent_v, ctx=ctx, params=params, dt=dt, refractory_us=refractory_us,
                       theta_events=theta_events)
     try:
@@ -181,7 +181,7 @@ def events_to_roi_flows(x, y, p, t, sensor_hw, cfg, slice_us=1000, active_v=-6.0
     f32 = surface_dtype == "float32"
     H, W = sensor_hw  # noqa: N806
     dev = torch.device("cuda", ctx.device)
-    idx = slice_index_array(t, slice_us)
+    idx = slice_index_array(t, slice_us, ctx)
     n_frames = (len(idx) - 1) // snapshot_every
     if n_frames < 2:
         raise ValueError("the stream is shorter than two snapshots")
@@ -248,7 +248,7 @@ def events_to_flow_sequence(x, y, p, t, sensor_hw, params=None, slice_us=1000, a
     params = params or PARAMS_A
     H, W = sensor_hw  # noqa: N806
     dev = torch.device("cuda", ctx.device)
-    idx = slice_index_array(t, slice_us)
+    idx = slice_index_array(t, slice_us, ctx)
     n_slices = len(idx) - 1
     n_frames = n_slices // snapshot_every
     if n_frames < 2:
@@ -278,15 +278,16 @@ def video_to_flow_sequence(frames, times_us=None, *, frame_us=None, threshold=10
                            response=None, ref=None, timestamps="linear", p_on=1, p_off=-1, sensor=None, denoise=None, ctx=None,
                            **accumulator_args):
     """A grey video in HBM through the event pipeline: ``events_from_frames_dev(frames, ...)`` (the arguments up to
-    ``p_off``) turns the frames into an event stream in HBM, one copy brings it to the host (the accumulator's entries
-    stage host event arrays), and ``events_to_flow_sequence(x, y, p, t, (H, W), **accumulator_args)`` accumulates it and
-    takes the flow between its surface frames.  Returns ``(surface frames uint8 [m][H][W], flows float32 [m-1][H][W][2],
+    ``p_off``) turns the frames into an event stream in HBM, and ``events_to_flow_sequence(x, y, p, t, (H, W),
+    **accumulator_args)`` takes it where it lies -- slice bounds, check and staging on the device
+    (``slice_index_array``, ``Accumulator.set_events``); only the bounds come to the host --, accumulates it and takes the
+    flow between its surface frames.  Returns ``(surface frames uint8 [m][H][W], flows float32 [m-1][H][W][2],
     events)``, ``events`` the generator's result dict (``x, y, p, t`` CUDA tensors, ``frame_bounds``, ``ref``).  ``sensor``: a
     dict of the generator's sensor arguments (``refractory_us``, ``noise``, ``t_ok``, ``first_frame``), forwarded to it --
     apart from ``accumulator_args``, where ``refractory_us`` is the accumulator's; ``events`` then carries ``t_ok`` too.
     ``denoise``: a dict of the keyword arguments of ``events_denoise_dev`` (``dt_us``, and any of ``radius``, ``min_support``,
     ``same_polarity``, ``include_self``, ``last``): the background-activity filter is applied to the stream in HBM, between the
-    generator and the host copy, with the generator's ``frame_bounds`` as its bounds.  ``events`` then holds the kept stream
+    generator and the accumulator, with the generator's ``frame_bounds`` as its bounds.  ``events`` then holds the kept stream
     (``x, y, p, t`` and its ``frame_bounds``) and gains ``keep`` (uint8 CUDA, one byte per generated event), ``n_kept`` and
     ``last``.  A bad key or value of the dict is refused before the generator runs.  ``None``: no filter."""
     from . import _lib
@@ -315,8 +316,8 @@ def video_to_flow_sequence(frames, times_us=None, *, frame_us=None, threshold=10
                                   bounds=ev["frame_bounds"], ctx=ctx, **denoise)
         ev = dict(ev, frame_bounds=kept.pop("bounds"), **kept)
     ctx.synchronize()
-    x, y, p, t = (ev[k].cpu().numpy() for k in "xypt")
-    surfaces, flows = events_to_flow_sequence(x, y, p, t, (int(frames.shape[1]), int(frames.shape[2])), ctx=ctx, **accumulator_args)
+    surfaces, flows = events_to_flow_sequence(ev["x"], ev["y"], ev["p"], ev["t"], (int(frames.shape[1]), int(frames.shape[2])), ctx=ctx,
+                                              **accumulator_args)
     return surfaces, flows, ev
 
 
