@@ -323,7 +323,7 @@ int nsof_farneback_core(nsof_ctx* ctx, const nsof_fb_frames& frames, float* d_fl
 // ---- the uniform routes: device batch and device sequence ----------------------------------------------------------
 // Every route has ONE typed entry (nsof_pixel_type == nsof_src_type) that does the work, in this order: context, pixel
 // type, null pointers and counts, frame layout, then the driver with its parameter checks.  The nsof_farneback_u8* and
-// nsof_farneback_f32* exports name the pixel type and forward (the end of this file and of farneback_batch.hip).
+// nsof_farneback_f32* exports name the pixel type and forward (the end of this file and of farneback_batch.hip, farneback_pipe.hip, farneback_roi.hip).
 extern "C" int nsof_farneback_px_batch_dev(nsof_ctx* ctx, int pixel_type, int n_pairs, const void* d_prev, const void* d_next,
                                            ptrdiff_t row_stride, ptrdiff_t pair_stride, int width, int height, float* d_flow,
                                            double pyr_scale, int levels, int winsize, int iterations, int poly_n,

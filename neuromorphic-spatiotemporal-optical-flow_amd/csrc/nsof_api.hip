@@ -1,4 +1,5 @@
-// libnsof.so host side: context, error channel, profiling hooks, filter taps, level geometry, stage entry points.
+// libnsof.so host side: context, error channel, page-locked host memory, profiling hooks, filter taps, level geometry,
+// stage entry points.
 // (The Farneback level driver is farneback_driver.hip.)
 #include <cctype>
 #include <cfloat>
@@ -153,6 +154,21 @@ void* nsof_pinned_alloc(int device, size_t bytes)
         return nullptr;
     }
     return p;
+}
+
+extern "C" void* nsof_host_alloc(size_t bytes)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        (void)hipGetLastError();
+        dev = 0;
+    }
+    return nsof_pinned_alloc(dev, bytes);   // on the current device's NUMA node where the host lets us choose
+}
+
+extern "C" void nsof_host_free(void* p)
+{
+    if (p) (void)hipHostFree(p);
 }
 
 int nsof_buf_grow(nsof_ctx* ctx, bool pinned, void** p, size_t* cap, size_t need, size_t new_cap)

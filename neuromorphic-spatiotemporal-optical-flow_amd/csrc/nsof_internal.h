@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <type_traits>
 #include <utility>
@@ -159,7 +160,7 @@ struct nsof_prof_scope {
     ~nsof_prof_scope();
 };
 
-// ---- Farneback driver pieces shared between farneback_driver.hip and farneback_batch.hip -------------------------------
+// ---- Farneback driver pieces shared between farneback_driver.hip and the work-list files (farneback_batch / _pipe / _roi) ----
 // Pixel type of the frames a uniform batch reads (the pyramid stage is the only one that reads them).  Frame pointers
 // stay byte addresses and every stride stays in bytes for all of them.  The values are those of the public
 // nsof_pixel_type.
@@ -207,6 +208,33 @@ struct nsof_fb_frames {
 };
 // Uniform-shape device batch (farneback_driver.hip); d_flow: n_pairs dense fields.
 int nsof_farneback_core(nsof_ctx* ctx, const nsof_fb_frames& frames, float* d_flow, const nsof_fb_params& params);
+// What a typed work-list entry was called with (built there): the Farneback parameters and the pixel type of the list (a
+// constructor, so that leaving the pixel type out does not compile).
+struct nsof_list_params : nsof_fb_params {
+    int src;   // nsof_src_type of every frame of the list
+    nsof_list_params(int s, const nsof_fb_params& fb) : nsof_fb_params(fb), src(s) {}
+    size_t px() const { return (size_t)nsof_src_bytes(src); }   // bytes per pixel
+};
+// The work-list driver (farneback_batch.hip).  descs: HOST array of n items whose pointers are DEVICE addresses; the
+// pipelined host entry (farneback_pipe.hip) and the gated ROI sequence (farneback_roi.hip) hand it their lists.  It checks
+// every item with nsof_farneback_list_check, which the host entry also applies to its HOST descriptors before any work
+// (`i`: the item's index in the caller's list, for the message).  Hidden, as they were while the three lived in one file:
+// the library's dynamic symbol list gains no function.
+__attribute__((visibility("hidden"))) int nsof_farneback_list_core(nsof_ctx* ctx, int n, const nsof_pair_desc* descs, const nsof_list_params& p);
+__attribute__((visibility("hidden"))) int nsof_farneback_list_check(nsof_ctx* ctx, int i, const nsof_pair_desc& d, const nsof_list_params& p);
+// The three descriptor structs of nsof.h have one layout (they differ in the type their frame pointers name); the drivers
+// take nsof_pair_desc, whose frame pointers are byte addresses.
+template <class D> constexpr bool nsof_is_pair_desc_layout()
+{
+    return sizeof(D) == sizeof(nsof_pair_desc) && offsetof(D, prev) == offsetof(nsof_pair_desc, prev) &&
+           offsetof(D, prev_stride) == offsetof(nsof_pair_desc, prev_stride) && offsetof(D, next) == offsetof(nsof_pair_desc, next) &&
+           offsetof(D, next_stride) == offsetof(nsof_pair_desc, next_stride) && offsetof(D, width) == offsetof(nsof_pair_desc, width) &&
+           offsetof(D, height) == offsetof(nsof_pair_desc, height) && offsetof(D, flow) == offsetof(nsof_pair_desc, flow) &&
+           offsetof(D, flow_stride) == offsetof(nsof_pair_desc, flow_stride);
+}
+static_assert(nsof_is_pair_desc_layout<nsof_pair_desc_px>(), "nsof_pair_desc_px must keep nsof_pair_desc's layout");
+static_assert(nsof_is_pair_desc_layout<nsof_pair_desc_f32>(), "nsof_pair_desc_f32 must keep nsof_pair_desc's layout");
+template <class D> static const nsof_pair_desc_px* as_px(const D* pairs) { return reinterpret_cast<const nsof_pair_desc_px*>(pairs); }
 void nsof_pipe_destroy(nsof_ctx* ctx);
 
 // ---- Farneback launchers (farneback_pyramid.hip, farneback_resample.hip, farneback_polyexp.hip, farneback_blur.hip) ----

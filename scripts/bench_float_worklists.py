@@ -80,7 +80,7 @@ def leg_device_crops(nsof, torch, steps, n=64, ch=200, cw=520):
     p = nsof.farneback.PARAMS_A
     from nsof import _lib
     # crop origins quadratic in i: no constant pointer step between items (a constant step with equal shapes and dense
-    # consecutive flows is what het_core hands to the uniform driver)
+    # consecutive flows is what nsof_farneback_list_core hands to the uniform driver)
     origins = [((7 * i * i + 3 * i) % (1080 - ch), (37 * i + (i * i) % 11) % (1920 - cw)) for i in range(n)]
     steps_x = {origins[i + 1][1] - origins[i][1] for i in range(n - 1)}
     steps_y = {origins[i + 1][0] - origins[i][0] for i in range(n - 1)}

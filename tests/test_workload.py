@@ -275,6 +275,85 @@ def test_pipelined_entry_drains_on_error(nsof_lib, ctx, oracle):
         assert np.array_equal(f, oracle.farneback(np.ascontiguousarray(a), np.ascontiguousarray(b), *A))
 
 
+# Eleven items in eight chunks at NSOF_PIPE_CHUNK_MB=1 (a chunk closes once it holds >= 1 MiB of flow, so an item of at
+# least 256x512 ends its chunk and smaller ones ride along with the next large one).  The pipeline has three slots: every
+# slot is reused at least once, chunks 6 and 7 reuse one for the second time, and chunks 3..7 are larger than the chunk
+# their slot held before, so the slot's buffers grow on reuse.
+DEEP_CHUNKS = [[(256, 512)], [(40, 40), (256, 512)], [(256, 512)], [(264, 512)], [(33, 70), (2, 2), (272, 512)],
+               [(280, 520)], [(288, 520)], [(256, 512)]]
+
+
+@pytest.fixture(scope="module")
+def deep_list(nsof_lib, ctx):
+    """The crops of DEEP_CHUNKS (strided views of one 300x560 pair) and the lone call's flow of each."""
+    p = nsof_lib.FarnebackParams(*A)
+    pairs = _crops(23, [s for chunk in DEEP_CHUNKS for s in chunk], frame_hw=(300, 560))
+    want = [nsof_lib.calcOpticalFlowFarneback(a, b, None, **p.as_kwargs(), ctx=ctx) for a, b in pairs]
+    for w in want:
+        w.setflags(write=False)
+    return pairs, want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("arrangement", ["pageable", "pinned", "mixed"])
+def test_pipeline_slot_reuse_growth_and_mixed_memory(nsof_lib, deep_list, capfd, arrangement):
+    """The pipelined host entry over eight chunks on a fresh context (empty slots): slot reuse two rounds deep, slot
+    buffers that must grow, and frames / flows that are all pageable (strided crops, strided views into zeroed canvases),
+    all page-locked, or mixed item by item (prev page-locked for even i, next for i % 3 == 0, flow for odd i: chunks
+    mixed on both sides next to single-item chunks wholly of one kind).  Every flow equals the lone call's bit for bit;
+    the mixed run also reads the chunk count from the library's own NSOF_PIPE_TRACE output."""
+    nsof = nsof_lib
+    from nsof.farneback import pinned_empty
+    p = nsof.FarnebackParams(*A)
+    pairs, want = deep_list
+    assert len(pairs) == 11
+
+    def locked(a):
+        out = pinned_empty(a.shape, a.dtype)
+        out[...] = a
+        return out
+
+    def lock_prev(i):
+        return arrangement == "pinned" or (arrangement == "mixed" and i % 2 == 0)
+
+    def lock_next(i):
+        return arrangement == "pinned" or (arrangement == "mixed" and i % 3 == 0)
+
+    def lock_flow(i):
+        return arrangement == "pinned" or (arrangement == "mixed" and i % 2 == 1)
+
+    frames = [(locked(a) if lock_prev(i) else a, locked(b) if lock_next(i) else b) for i, (a, b) in enumerate(pairs)]
+    canvases = {i: np.zeros((a.shape[0] + 9, a.shape[1] + 5, 2), np.float32)
+                for i, (a, _) in enumerate(pairs) if not lock_flow(i)}
+    flows = [pinned_empty(a.shape + (2,), np.float32) if lock_flow(i) else canvases[i][7:7 + a.shape[0], 3:3 + a.shape[1]]
+             for i, (a, _) in enumerate(pairs)]
+    env = {"NSOF_PIPE_CHUNK_MB": "1"}
+    if arrangement == "mixed":
+        env["NSOF_PIPE_TRACE"] = "1"
+    own = nsof.Context(0)   # a context whose slots are empty: their buffers have to grow
+    capfd.readouterr()
+    os.environ.update(env)
+    try:
+        nsof.farneback_pairs(frames, p, flows, ctx=own)
+    finally:
+        for k in env:
+            del os.environ[k]
+        own.close()
+    err = capfd.readouterr().err
+    if arrangement == "mixed":
+        import re
+        m = re.search(r"\[nsof pipe\] (\d+) chunks", err)
+        assert m, err
+        assert int(m.group(1)) == len(DEEP_CHUNKS) == 8
+    for i, (f, w) in enumerate(zip(flows, want)):
+        assert np.array_equal(f, w), (arrangement, i, f.shape, float(np.abs(f - w).max()))
+    for i, c in canvases.items():
+        h, w = pairs[i][0].shape
+        outside = c.copy()
+        outside[7:7 + h, 3:3 + w] = 0
+        assert not outside.any(), (arrangement, i)      # nothing outside the view was written
+
+
 @pytest.mark.gpu
 def test_work_list_device_crops(nsof_lib, ctx, torch_dev):
     """Device-resident twin: crops of frames already in HBM, flows into crops of a device canvas."""
